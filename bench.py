@@ -6,22 +6,29 @@ over ONE batch of replicates already resident in HBM.  N=1: BASELINE configs[1] 
 replicates on 1 x MI355X).  N>1: one process per GPU (torch.distributed, backend nccl = RCCL), the
 replicate batch is sharded with the same 1024 replicates per GPU (weak scaling: the N = 1 line equals the single-GPU
 bench); the per-replicate log-likelihoods are all-gathered ONCE per timed block (north_star prescribes the collective per EM
-iteration; `--gather step` / secondary.pass_gather_every_step = after every pass).  A default `--gpus N` run also times, as
-`secondary`: BASELINE configs[2]'s per-GPU shard (`c3`: 8192 replicates per GPU = 65 536 at N = 8) and the EM iteration with
-its all-gather of {loglik, active} (`em`).
+iteration; `--gather step` / secondary.pass_gather_every_step = after every pass).  A default `--gpus N --full` run also
+times, as `secondary`: BASELINE configs[2]'s per-GPU shard (`c3`: 8192 replicates per GPU = 65 536 at N = 8) and the EM
+iteration with its all-gather of {loglik, active} (`em`).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--repeats 9] [--batch-per-gpu 1024] [--missing 0.0]
-                  [--mode pass|em|pca] [--driver torch|lib] [--no-secondary] [--no-cpu-baseline]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch-per-gpu 1024] [--missing 0.0] [--mode pass|em|pca]
+                  [--driver torch|lib] [--dump-outputs DIR] [--full [--repeats 9] [--no-secondary] [--no-cpu-baseline]]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 `--gpus N` WITHOUT a torchrun environment launches the N ranks itself (re-exec under torch.distributed.run on
 127.0.0.1) and fails loudly when the box has fewer than N devices; n_gpus in the line is dist.get_world_size().
 
-Timing: an untimed pre-heat of >= 50 ms of the same steps (clocks ramp on a fresh box), W untimed warm-up steps, then
-`--repeats` blocks of EXACTLY K steps, each block bracketed by barrier + torch.cuda.synchronize() on both sides and
-reduced with MAX over ranks; `value` / `ms_per_step` are the MEDIAN block, min / max / every block are printed beside
-them.  Panels come from the product's own device generator (dfm_synth_panels_dev: counter-based Philox keyed by (seed,
-global replicate index); checked cell by cell against its host restatement in the GPU tests).
+A plain run does only what the headline needs: set-up, an untimed pre-heat of >= 50 ms of the same steps (clocks ramp on a
+fresh box), W untimed warm-up steps, then ONE block of EXACTLY K timed steps bracketed by barrier + torch.cuda.synchronize()
+on both sides and reduced with MAX over ranks; `ms_per_step` = that block / K, `value` = units per second over it.
+`--full` adds everything else: `--repeats` timed blocks of K steps (`value` / `ms_per_step` are then the MEDIAN block, min /
+max / every block are printed beside them), and the objects below.  Panels come from the product's own device generator
+(dfm_synth_panels_dev: counter-based Philox keyed by (seed, global replicate index); checked cell by cell
+against its host restatement in the GPU tests), so the inputs are the same in every run with the same arguments.
+
+--dump-outputs DIR: after the timed steps, what the last timed step computed is written as DIR/<name>.npy (float64, rank 0's
+            replicates): pass mode f_smooth / P_smooth / loglik, EM mode the updated Lam / R / A / Q / mu0 / P0 and the
+            log-likelihood path of the timed block, PCA mode the start Lam / R / A / Q / mu0 / P0.  At most 64 MB in all: a
+            larger batch is cut to a fixed, seeded sample of replicates (the same rows of every array), named in the line.
 
 --mode em : a step = ONE EM ITERATION (E-step pass + M-step, SURVEY §8(d) "EM iteration") of the replicate-sharded
             driver shard.em_batch_sharded -- dfm_em_iterate_batch_dev on the shard, then the all-gather of {loglik,
@@ -31,12 +38,12 @@ global replicate index); checked cell by cell against its host re
             ONE process drives --gpus N devices, the job is generated where it lives (dfm_multi_synth), `--mode em` times
             dfm_multi_em (one ncclAllGather per iteration inside the library), `--mode pass` dfm_multi_ks_pass.
 
-Prints ONE JSON line (rank 0).  Extra objects: "roofline" (dominant kernel, HIP-event timed on the launch stream inside
-this script; `ceiling_measured` = this box's own streaming ceilings from dfm_hbm_probe), "cpu_baseline" (oracle/
-dfm_oracle.c, the C restatement, timed on the host cores of this box on a bounded sample of the same workload; rank 0,
-N=1 only), "device" (clocks / power sampled while the bench batch runs) and -- default invocation only -- "secondary":
-the other lines of the path (B = 8192 shard, 10 % missing, EM, config 4, config 4 with missing cells, PCA start), three
-blocks each, same method.
+Prints ONE JSON line (rank 0).  Extra objects of a `--full` run (null in a plain one): "roofline" (dominant kernel,
+HIP-event timed on the launch stream inside this script over K more steps; `ceiling_measured` = this box's own streaming
+ceilings from dfm_hbm_probe), "cpu_baseline" (oracle/dfm_oracle.c, the C restatement, timed on the host cores of this box on
+a bounded sample of the same workload; rank 0, N=1 only), "device" (clocks / power sampled while the bench batch runs) and
+-- default shape only -- "secondary": the other lines of the path (B = 8192 shard, 10 % missing, EM, config 4, config 4
+with missing cells, PCA start), three blocks each, same method.
 """
 from __future__ import annotations
 
@@ -68,6 +75,35 @@ def algorithmic_bytes(N, T, r):
     inputs = 8 * (N * T + N * r + N + 2 * r * r + r + r * r)
     outputs = 8 * (T * r + T * r * (r + 1) // 2 + 1)
     return inputs, outputs
+
+
+DUMP_LIMIT_BYTES = 64 * 10**6
+DUMP_SEED = 20160415
+
+
+def dump_outputs(outdir, arrays, limit=DUMP_LIMIT_BYTES, seed=DUMP_SEED):
+    """--dump-outputs: every array of `arrays` (name -> tensor, replicates first) as outdir/<name>.npy in float64.  When the
+    whole batch would exceed `limit` bytes, the same fixed, seeded sample of replicates (sorted) is taken from every array.
+    Returns what was written (for the JSON line)."""
+    import numpy as np
+    import torch
+    os.makedirs(outdir, exist_ok=True)
+    B = next(iter(arrays.values())).shape[0]
+    per_replicate = 8 * sum(a[0].numel() for a in arrays.values())
+    budget = limit - 256 * len(arrays)                                  # (.npy headers)
+    S = min(B, max(1, budget // per_replicate))
+    idx = None
+    if S < B:
+        idx = np.sort(np.random.default_rng(seed).choice(B, S, replace=False))
+    written = 0
+    for name, a in arrays.items():
+        x = a if idx is None else a.index_select(0, torch.from_numpy(idx).to(a.device))
+        x = x.detach().to("cpu", torch.float64).contiguous().numpy()
+        path = os.path.join(outdir, name + ".npy")
+        np.save(path, x)
+        written += os.path.getsize(path)
+    return dict(dir=outdir, files=sorted(arrays), dtype="float64", bytes=written, replicates=S, of_replicates=B,
+                sample=None if idx is None else f"numpy default_rng({seed}).choice({B}, {S}, replace=False), sorted")
 
 
 def source_hash():
@@ -346,12 +382,15 @@ class Workload:
         for c in range(1, self.cold):
             pan, par = ctx.synth_panels(seed + 7919 * c, rank * B, B, T, N, r, missing_prob=missing)
             self.cold_sets.append((pan, par, torch.empty_like(self.f), torch.empty_like(self.P), torch.empty_like(self.ll)))
-        self.em_params = None
+        self.em_params = self.em_start = None
         if mode == "em":
             if self.may_missing:
                 self.em_params = [p.clone() for p in self.params]       # DGP parameters as the start (PCA needs a balanced panel)
             else:
                 self.em_params = list(ctx.pca_init_batch(self.panel, r, want_factors=False)[:6])
+            # the start, restored behind the (time-bounded) pre-heat: the timed block begins W iterations after it in every run
+            self.em_start = [p.clone() for p in self.em_params]
+        self.last = None                                            # what the last step returned (outputs())
 
     def steps(self, k, profile=False):
         # multi-rank: the passes go on a HIGH-priority stream.  The step's collective and the next pass become eligible at the same
@@ -374,9 +413,10 @@ class Workload:
                     pending[u] = None
                 if self.cold > 1 and it % self.cold:
                     pan, par, f_, P_, ll_ = self.cold_sets[it % self.cold - 1]
-                    ctx.ks_pass_batch(pan, *par, may_have_missing=self.may_missing, out=(f_, P_, ll_))
+                    self.last = ctx.ks_pass_batch(pan, *par, may_have_missing=self.may_missing, out=(f_, P_, ll_))
                     continue
-                ctx.ks_pass_batch(self.panel, *self.params, may_have_missing=self.may_missing, out=(self.f, self.P, self.ll_pair[u]))
+                self.last = ctx.ks_pass_batch(self.panel, *self.params, may_have_missing=self.may_missing,
+                                              out=(self.f, self.P, self.ll_pair[u]))
                 if self.distributed and not profile and (self.gather == "step" or it == k - 1):
                     pending[u] = dist.all_gather_into_tensor(self.ll_all[u], self.ll_pair[u], async_op=True)
             for h in pending:
@@ -385,11 +425,21 @@ class Workload:
         elif self.mode == "em":
             # k EM iterations of the sharded driver: dfm_em_iterate_batch_dev + the all-gather of {loglik, active} EVERY
             # iteration (tol = 0: no early stop, so exactly k iterations are timed)
-            self.shard.em_batch_sharded(ctx, self.panel, *self.em_params, B_global=self.world * self.B, max_iter=k, tol=0.0,
-                                        want_smooth=False, may_have_missing=self.may_missing)
+            self.last = self.shard.em_batch_sharded(ctx, self.panel, *self.em_params, B_global=self.world * self.B, max_iter=k, tol=0.0,
+                                                    want_smooth=False, may_have_missing=self.may_missing)
         else:
             for _ in range(k):
-                ctx.pca_init_batch(self.panel, self.r, want_factors=False)
+                self.last = ctx.pca_init_batch(self.panel, self.r, want_factors=False)
+
+    def outputs(self):
+        """What the last step handed its caller, by name (device tensors, replicates first): the arrays --dump-outputs writes."""
+        if self.mode == "pass":
+            f, P, ll = self.last
+            return {"f_smooth": f, "P_smooth": P, "loglik": ll}
+        names = ("Lam", "R", "A", "Q", "mu0", "P0")
+        if self.mode == "em":                              # (parameters updated in place by the iterations)
+            return dict(zip(names, self.em_params), loglik_path=self.last["path"])
+        return dict(zip(names, self.last[:6]))
 
     def fence(self):
         self.torch.cuda.synchronize()
@@ -397,7 +447,9 @@ class Workload:
             self.dist.barrier()
         self.torch.cuda.synchronize()
 
-    def run(self, steps, warmup, repeats, preheat_ms=PREHEAT_MS):
+    def run(self, steps, warmup, repeats, preheat_ms=PREHEAT_MS, roofline_leg=True, dump_dir=None):
+        """Pre-heat, W warm-up steps, `repeats` timed blocks of K steps; then (dump_dir) the last step's outputs are written and
+        (roofline_leg) K more steps are timed kernel by kernel with HIP-event pairs."""
         torch, dist = self.torch, self.dist
         # pre-heat: the same steps, untimed, until >= preheat_ms of device time have passed (DVFS ramp of a fresh box)
         # (every rank decides by its OWN clock how long it pre-heats, so the pre-heat steps must not contain a collective:
@@ -412,6 +464,9 @@ class Workload:
             while (time.perf_counter() - t0) * 1e3 < preheat_ms:
                 self.steps(max(2, steps // 4), profile=True); heat += max(2, steps // 4)
                 torch.cuda.synchronize()
+        if self.em_start is not None:
+            for p, p0 in zip(self.em_params, self.em_start):
+                p.copy_(p0)
         self.steps(max(warmup, 1) if self.mode == "em" else warmup)
         blocks = []
         for _ in range(max(repeats, 1)):
@@ -430,14 +485,18 @@ class Workload:
         if self.mode == "pass":
             assert bool(torch.isfinite(self.ll).all()), "non-finite log-likelihood in the bench batch"
             self.ctx.synchronize()              # + the status word of the last pass (an expired bounded wait would raise)
-        # roofline leg: K more steps with a HIP-event pair around every kernel launch (on the launch stream)
-        self.ctx.profile_enable(True)
-        self.steps(steps, profile=True)
-        prof = self.ctx.profile_read()
-        self.ctx.profile_enable(False)
-        return dict(ms_per_step=1e3 * elapsed / steps, value=self.world * self.B * steps / elapsed, blocks=blocks, sorted=srt,
-                    avg={k: v[0] / v[1] for k, v in prof.items()}, launches={k: v[1] for k, v in prof.items()}, steps=steps,
-                    preheat_steps=heat)
+        out = dict(ms_per_step=1e3 * elapsed / steps, value=self.world * self.B * steps / elapsed, blocks=blocks, sorted=srt, steps=steps,
+                   preheat_steps=heat, avg=None, launches=None, dumped=None)
+        if dump_dir is not None and self.rank == 0:
+            out["dumped"] = dump_outputs(dump_dir, self.outputs())
+        if roofline_leg:
+            # roofline leg: K more steps with a HIP-event pair around every kernel launch (on the launch stream)
+            self.ctx.profile_enable(True)
+            self.steps(steps, profile=True)
+            prof = self.ctx.profile_read()
+            self.ctx.profile_enable(False)
+            out.update(avg={k: v[0] / v[1] for k, v in prof.items()}, launches={k: v[1] for k, v in prof.items()})
+        return out
 
     def roofline(self, res):
         """The roofline object of one line (rank 0)."""
@@ -846,6 +905,11 @@ def workload_name(N, T, r, B):
             "BASELINE configs[3]" if (N, T, r) == (1000, 2000, 20) else "custom")
 
 
+def repeats_of(args):
+    """Timed blocks of K steps: one in a plain run (exactly --steps timed steps), --repeats under --full."""
+    return max(args.repeats, 1) if args.full else 1
+
+
 def run_lib_driver(args, torch):
     """--driver lib: ONE process, the library's dfm_multi object over --gpus N devices (what the Julia host binds)."""
     from dynamic_factor_models_amd import DfmMulti
@@ -867,7 +931,7 @@ def run_lib_driver(args, torch):
             steps(max(2, args.steps // 4))
         steps(max(args.warmup, 1))
         blocks = []
-        for _ in range(max(args.repeats, 1)):
+        for _ in range(repeats_of(args)):
             t0 = time.perf_counter()
             steps(args.steps)                    # (every call of the object synchronises all its GPUs before it returns)
             blocks.append(time.perf_counter() - t0)
@@ -902,7 +966,8 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--repeats", type=int, default=9)
+    ap.add_argument("--repeats", type=int, default=9, help="--full: timed blocks of K steps, the median one is the headline "
+                                                           "(a plain run times one block)")
     ap.add_argument("--batch-per-gpu", type=int, default=1024)
     ap.add_argument("--N", type=int, default=200)
     ap.add_argument("--T", type=int, default=500)
@@ -913,8 +978,13 @@ def main():
     ap.add_argument("--force-comm", action="store_true", help="--driver lib: build the RCCL communicator also for one GPU")
     ap.add_argument("--gather", choices=("block", "step"), default="block",
                     help="multi-rank pass mode: all-gather the log-likelihoods once per timed block (default) or after every pass")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64, at most 64 MB in all)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements beside the headline: --repeats blocks, the per-kernel roofline leg, device telemetry, "
+                         "the HBM ceiling probe, the CPU baseline and (default shape) the secondary lines")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="--full without the secondary lines")
     ap.add_argument("--cpu-seconds", type=float, default=20.0)
     args = ap.parse_args()
 
@@ -932,6 +1002,8 @@ def main():
     if args.driver == "lib":
         if args.mode == "pca":
             raise SystemExit("--driver lib times --mode pass or --mode em")
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs: the library driver keeps its outputs inside dfm_multi (use --driver torch)")
         return run_lib_driver(args, torch)
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -967,16 +1039,16 @@ def main():
     default_line = (args.mode, B, N, T, r, args.missing) == ("pass", 1024, 200, 500, 8, 0.0)
 
     wl = Workload(torch, dist, ctx, shard, world, rank, dev, B, N, T, r, args.missing, args.mode, gather=args.gather)
-    res = wl.run(args.steps, args.warmup, args.repeats)
-    # clocks / power while the bench batch runs: enqueue ~0.5 s of steps, read rocm-smi meanwhile (rank 0)
+    res = wl.run(args.steps, args.warmup, repeats_of(args), roofline_leg=args.full, dump_dir=args.dump_outputs)
+    # --full: clocks / power while the bench batch runs: enqueue ~0.5 s of steps, read rocm-smi meanwhile (rank 0)
     telemetry = None
-    if rank == 0:
+    if rank == 0 and args.full:
         if args.mode != "em":                                     # (no collective in these steps: rank 0 may run them alone)
             wl.steps(int(min(4000, max(50, 500.0 / max(res["ms_per_step"], 1e-3)))), profile=True)
         telemetry = device_telemetry()                            # (EM mode: read right behind the timed blocks)
         torch.cuda.synchronize()
     ceiling = None
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         try:
             pr = ctx.hbm_probe(1 << 30, 10)
             ceiling = dict(read_dma_gbs=pr["read_dma"], copy_gbs=pr["copy"], write_gbs=pr["write"],
@@ -987,12 +1059,14 @@ def main():
 
     out = None
     if rank == 0:
-        roofline = wl.roofline(res)
-        roofline["ceiling_measured"] = ceiling
-        if ceiling and "copy_gbs" in ceiling and roofline.get("whole_step"):
-            roofline["whole_step"]["frac_of_measured_copy_ceiling"] = roofline["whole_step"]["achieved"] / ceiling["copy_gbs"]
+        roofline = None
+        if args.full:
+            roofline = wl.roofline(res)
+            roofline["ceiling_measured"] = ceiling
+            if ceiling and "copy_gbs" in ceiling and roofline.get("whole_step"):
+                roofline["whole_step"]["frac_of_measured_copy_ceiling"] = roofline["whole_step"]["achieved"] / ceiling["copy_gbs"]
         cpu = None
-        if world == 1 and not args.no_cpu_baseline and args.mode == "pass":
+        if world == 1 and args.full and not args.no_cpu_baseline and args.mode == "pass":
             from oracle import c_oracle as co
             S = min(B, max(256, 8 * co.num_threads()))
             ph = wl.panel[:S].cpu().numpy()
@@ -1016,16 +1090,21 @@ def main():
                                                    distinct_devices=len({(d or {}).get("pci_bus_id", i) for i, d in enumerate(rank_devices)}),
                                                    nccl_max_nchannels=os.environ.get("NCCL_MAX_NCHANNELS"))
                                               if (world > 1 or force_dist) else None)),
-                   timing=dict(repeats=len(res["blocks"]), statistic="median of the timed blocks (each: K steps between fences, MAX over ranks)",
+                   timing=dict(repeats=len(res["blocks"]),
+                               statistic=("median of the timed blocks (each: K steps between fences, MAX over ranks)" if len(res["blocks"]) > 1 else
+                                          "one timed block of K steps between fences (MAX over ranks)"),
                                preheat=f">= {PREHEAT_MS:.0f} ms of untimed steps before the W warm-up steps ({res['preheat_steps']} steps)",
                                ms_per_step_min=1e3 * srt[0] / args.steps, ms_per_step_max=1e3 * srt[-1] / args.steps,
                                value_min=world * B * args.steps / srt[-1], value_max=world * B * args.steps / srt[0],
                                ms_per_step_blocks=[round(1e3 * b / args.steps, 5) for b in res["blocks"]]),
-                   roofline=roofline, cpu_baseline=cpu, device=telemetry, host_cores=os.cpu_count(), source_hash=source_hash())
+                   roofline=roofline, cpu_baseline=cpu, device=telemetry, host_cores=os.cpu_count(), source_hash=source_hash(),
+                   full=args.full)
+        if res["dumped"] is not None:
+            out["outputs"] = res["dumped"]
     wl.free()
 
-    # ---- the other lines of the path, driver-visible (default invocation only; about a minute together) ----
-    plan = secondary_plan(world, default_line, args.no_secondary)
+    # ---- --full: the other lines of the path, driver-visible (default shape only; about a minute together) ----
+    plan = secondary_plan(world, default_line, args.no_secondary) if args.full else []
     sec = {}
     for key in plan:
         t0 = time.perf_counter()

@@ -7,8 +7,8 @@ mkdir -p $OUT
 timeout 900 python -m pytest tests/test_gpu_round3.py tests/test_gpu_ks_pass.py tests/test_gpu_em.py tests/test_gpu_fuzz.py -q -x 2>&1 | grep -v "^$" | tail -6
 B="--no-cpu-baseline --no-secondary --repeats 3 --N 1000 --T 2000 --r 20 --batch-per-gpu 256 --missing 0.1 --steps 2 --warmup 1"
 for rep in 1 2; do
-  timeout 300 python bench.py $B > $OUT/new_$rep.json 2> $OUT/new_$rep.err
-  DFM_CT_OLD=1 timeout 300 python bench.py $B > $OUT/old_$rep.json 2> $OUT/old_$rep.err
+  timeout 300 python bench.py --full $B > $OUT/new_$rep.json 2> $OUT/new_$rep.err
+  DFM_CT_OLD=1 timeout 300 python bench.py --full $B > $OUT/old_$rep.json 2> $OUT/old_$rep.err
 done
 for f in $OUT/new_1 $OUT/old_1 $OUT/new_2 $OUT/old_2; do
   python - $f.json <<'PY'

@@ -34,6 +34,6 @@ done
 wait $LP
 grep "ms per" /tmp/loop.log
 timeout 60 scripts/microbench/icache
-timeout 60 python bench.py --no-cpu-baseline --no-secondary --repeats 3 2>/dev/null | python -c "
+timeout 60 python bench.py --full --no-cpu-baseline --no-secondary --repeats 3 2>/dev/null | python -c "
 import json,sys
 d=json.loads([l for l in sys.stdin.read().splitlines() if l.startswith('{')][-1]); print('bench value=%.4g'%d['value'])"

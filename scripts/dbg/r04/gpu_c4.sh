@@ -10,7 +10,7 @@ if [ -n "$3" ]; then
 fi
 for k in $(seq 1 $K); do
 for mode in pass em; do
-  timeout 300 python bench.py --N 1000 --T 2000 --r 20 --batch-per-gpu 256 --mode $mode --steps 10 --warmup 3 --repeats 5 --no-cpu-baseline --no-secondary > $OUT/c4_${mode}.json 2> $OUT/c4_${mode}.err
+  timeout 300 python bench.py --full --N 1000 --T 2000 --r 20 --batch-per-gpu 256 --mode $mode --steps 10 --warmup 3 --repeats 5 --no-cpu-baseline --no-secondary > $OUT/c4_${mode}.json 2> $OUT/c4_${mode}.err
   python - $OUT/c4_${mode}.json $mode <<'PY'
 import json,sys
 try:

@@ -11,7 +11,7 @@ fi
 for k in $(seq 1 $K); do
 for off in 0 1; do
 for mode in pass em; do
-  env $VAR=$off timeout 300 python bench.py --N 1000 --T 2000 --r 20 --batch-per-gpu 256 --mode $mode --steps 10 --warmup 3 --repeats 5 --no-cpu-baseline --no-secondary > $OUT/c4_${mode}_$off.json 2> $OUT/c4_${mode}_$off.err
+  env $VAR=$off timeout 300 python bench.py --full --N 1000 --T 2000 --r 20 --batch-per-gpu 256 --mode $mode --steps 10 --warmup 3 --repeats 5 --no-cpu-baseline --no-secondary > $OUT/c4_${mode}_$off.json 2> $OUT/c4_${mode}_$off.err
   python - $OUT/c4_${mode}_$off.json $mode $VAR $off <<'PY'
 import json,sys
 try:

@@ -11,8 +11,8 @@ tail -30 $OUT/pytest_tile.log
 timeout 600 python -m pytest tests/test_gpu_round3.py -q -m gpu -k config4 2>&1 | tail -20 > $OUT/pytest_c4.log
 tail -12 $OUT/pytest_c4.log
 for nt in 0 1; do
-  DFM_NO_TILE=$nt timeout 300 python bench.py --N 1000 --T 2000 --r 20 --batch-per-gpu 256 --missing 0.1 --steps 2 --warmup 1 --repeats 3 --no-cpu-baseline --no-secondary > $OUT/bench_c4m_notile$nt.json 2> $OUT/bench_c4m_notile$nt.err
-  DFM_NO_TILE=$nt timeout 300 python bench.py --N 1000 --T 2000 --r 20 --batch-per-gpu 256 --missing 0.1 --mode em --steps 2 --warmup 1 --repeats 3 --no-cpu-baseline --no-secondary > $OUT/bench_c4m_em_notile$nt.json 2> $OUT/bench_c4m_em_notile$nt.err
+  DFM_NO_TILE=$nt timeout 300 python bench.py --full --N 1000 --T 2000 --r 20 --batch-per-gpu 256 --missing 0.1 --steps 2 --warmup 1 --repeats 3 --no-cpu-baseline --no-secondary > $OUT/bench_c4m_notile$nt.json 2> $OUT/bench_c4m_notile$nt.err
+  DFM_NO_TILE=$nt timeout 300 python bench.py --full --N 1000 --T 2000 --r 20 --batch-per-gpu 256 --missing 0.1 --mode em --steps 2 --warmup 1 --repeats 3 --no-cpu-baseline --no-secondary > $OUT/bench_c4m_em_notile$nt.json 2> $OUT/bench_c4m_em_notile$nt.err
 done
 for f in $OUT/bench_c4m*.json; do python - $f <<'PY'
 import json, sys

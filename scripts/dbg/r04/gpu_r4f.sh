@@ -8,10 +8,10 @@ export TMPDIR=/tmp
 uname -r > $OUT/device.txt
 timeout 1200 python -m pytest tests -q -m gpu --maxfail=12 2>&1 | tail -40 > $OUT/pytest.log
 tail -8 $OUT/pytest.log
-timeout 300 python bench.py --N 1000 --T 2000 --r 20 --batch-per-gpu 256 --missing 0.1 --steps 2 --warmup 1 --repeats 3 --no-cpu-baseline --no-secondary > $OUT/bench_c4m.json 2> $OUT/bench_c4m.err
-timeout 300 python bench.py --N 1000 --T 2000 --r 20 --batch-per-gpu 256 --missing 0.1 --mode em --steps 2 --warmup 1 --repeats 3 --no-cpu-baseline --no-secondary > $OUT/bench_c4m_em.json 2> $OUT/bench_c4m_em.err
-timeout 300 python bench.py --mode em --steps 20 --warmup 3 --repeats 5 --no-cpu-baseline --no-secondary > $OUT/bench_em.json 2> $OUT/bench_em.err
-DFM_NO_DEFER_EM=1 timeout 300 python bench.py --mode em --steps 20 --warmup 3 --repeats 5 --no-cpu-baseline --no-secondary > $OUT/bench_em_nodefer.json 2> $OUT/bench_em_nodefer.err
+timeout 300 python bench.py --full --N 1000 --T 2000 --r 20 --batch-per-gpu 256 --missing 0.1 --steps 2 --warmup 1 --repeats 3 --no-cpu-baseline --no-secondary > $OUT/bench_c4m.json 2> $OUT/bench_c4m.err
+timeout 300 python bench.py --full --N 1000 --T 2000 --r 20 --batch-per-gpu 256 --missing 0.1 --mode em --steps 2 --warmup 1 --repeats 3 --no-cpu-baseline --no-secondary > $OUT/bench_c4m_em.json 2> $OUT/bench_c4m_em.err
+timeout 300 python bench.py --full --mode em --steps 20 --warmup 3 --repeats 5 --no-cpu-baseline --no-secondary > $OUT/bench_em.json 2> $OUT/bench_em.err
+DFM_NO_DEFER_EM=1 timeout 300 python bench.py --full --mode em --steps 20 --warmup 3 --repeats 5 --no-cpu-baseline --no-secondary > $OUT/bench_em_nodefer.json 2> $OUT/bench_em_nodefer.err
 for f in $OUT/bench_*.json; do python - $f <<'PY'
 import json, sys
 try:

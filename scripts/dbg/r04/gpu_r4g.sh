@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 uname -r > $OUT/device.txt
 timeout 900 python -m pytest tests/test_gpu_round3.py tests/test_gpu_fuzz.py tests/test_gpu_em.py tests/test_gpu_round4.py -q -m gpu --maxfail=12 2>&1 | tail -30 > $OUT/pytest.log
 tail -6 $OUT/pytest.log
-timeout 300 python bench.py --N 1000 --T 2000 --r 20 --batch-per-gpu 256 --missing 0.1 --steps 2 --warmup 1 --repeats 3 --no-cpu-baseline --no-secondary > $OUT/bench_c4m.json 2> $OUT/bench_c4m.err
+timeout 300 python bench.py --full --N 1000 --T 2000 --r 20 --batch-per-gpu 256 --missing 0.1 --steps 2 --warmup 1 --repeats 3 --no-cpu-baseline --no-secondary > $OUT/bench_c4m.json 2> $OUT/bench_c4m.err
 for f in $OUT/bench_*.json; do python - $f <<'PY'
 import json, sys
 try:

@@ -4,7 +4,7 @@ TAG=${1:-r4j}
 R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out/$TAG; mkdir -p $OUT
 export TMPDIR=/tmp
 for x in 0 1 2 3 4 5; do
-  DFM_LIB=diag DFM_PCA_STOP=$x timeout 300 python bench.py --mode pca --steps 5 --warmup 1 --repeats 3 --no-cpu-baseline --no-secondary > $OUT/p$x.json 2> $OUT/p$x.err
+  DFM_LIB=diag DFM_PCA_STOP=$x timeout 300 python bench.py --full --mode pca --steps 5 --warmup 1 --repeats 3 --no-cpu-baseline --no-secondary > $OUT/p$x.json 2> $OUT/p$x.err
   python - $OUT/p$x.json $x <<'PY'
 import json,sys
 try:

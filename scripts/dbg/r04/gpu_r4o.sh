@@ -10,7 +10,7 @@ timeout 300 python scripts/dbg/inproc_ab.py $V batch=8192 2>&1 | grep -v "^RCCL\
 cat $OUT/ab_dma_mod_B1024.txt $OUT/ab_dma_mod_B8192.txt
 for n in default nt sc1 ntsc1 sc0; do
   L=""; [ $n != default ] && L=$R/gpurun_tmp/libdfmhip_$n.so
-  DFM_LIB=$L timeout 300 python bench.py --N 1000 --T 2000 --r 20 --batch-per-gpu 256 --steps 5 --warmup 2 --repeats 5 --no-cpu-baseline --no-secondary > $OUT/c4_$n.json 2> $OUT/c4_$n.err
+  DFM_LIB=$L timeout 300 python bench.py --full --N 1000 --T 2000 --r 20 --batch-per-gpu 256 --steps 5 --warmup 2 --repeats 5 --no-cpu-baseline --no-secondary > $OUT/c4_$n.json 2> $OUT/c4_$n.err
   python - $OUT/c4_$n.json $n <<'PY'
 import json,sys
 try:

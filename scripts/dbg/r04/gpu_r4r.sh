@@ -6,7 +6,7 @@ uname -r > $OUT/device.txt
 timeout 900 python -m pytest tests/test_gpu_ks_pass.py tests/test_gpu_em.py tests/test_gpu_round3.py -q -m gpu --maxfail=12 2>&1 | tail -5 > $OUT/pytest.log
 tail -2 $OUT/pytest.log
 for nt in 0 1; do for mode in pass em; do
-  DFM_DMA_NT=$nt timeout 300 python bench.py --mode $mode --missing 0.1 --steps 10 --warmup 3 --repeats 7 --no-cpu-baseline --no-secondary > $OUT/${mode}_m_nt$nt.json 2> $OUT/${mode}_m_nt$nt.err
+  DFM_DMA_NT=$nt timeout 300 python bench.py --full --mode $mode --missing 0.1 --steps 10 --warmup 3 --repeats 7 --no-cpu-baseline --no-secondary > $OUT/${mode}_m_nt$nt.json 2> $OUT/${mode}_m_nt$nt.err
   python - $OUT/${mode}_m_nt$nt.json $mode $nt <<'PY'
 import json,sys
 try:

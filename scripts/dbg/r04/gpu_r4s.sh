@@ -7,7 +7,7 @@ uname -r > $OUT/device.txt
 for n in default w2nt mwnt bothnt; do
   L=""; [ $n != default ] && L=$R/gpurun_tmp/libdfmhip_$n.so
   for mode in pass em; do
-    DFM_LIB=$L timeout 300 python bench.py --N 1000 --T 2000 --r 20 --batch-per-gpu 256 --mode $mode --steps 5 --warmup 2 --repeats 5 --no-cpu-baseline --no-secondary > $OUT/c4_${mode}_$n.json 2> $OUT/c4_${mode}_$n.err
+    DFM_LIB=$L timeout 300 python bench.py --full --N 1000 --T 2000 --r 20 --batch-per-gpu 256 --mode $mode --steps 5 --warmup 2 --repeats 5 --no-cpu-baseline --no-secondary > $OUT/c4_${mode}_$n.json 2> $OUT/c4_${mode}_$n.err
     python - $OUT/c4_${mode}_$n.json $n $mode <<'PY'
 import json,sys
 try:

@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 uname -r > $OUT/device.txt
 for k in 1 2; do
 for ns in 0 1; do
-  DFM_LIB=diag DFM_NO_SIDE=$ns timeout 300 python bench.py --N 1000 --T 2000 --r 20 --batch-per-gpu 256 --mode pass --steps 10 --warmup 3 --repeats 5 --no-cpu-baseline --no-secondary > $OUT/c4_ns$ns.json 2> $OUT/c4_ns$ns.err
+  DFM_LIB=diag DFM_NO_SIDE=$ns timeout 300 python bench.py --full --N 1000 --T 2000 --r 20 --batch-per-gpu 256 --mode pass --steps 10 --warmup 3 --repeats 5 --no-cpu-baseline --no-secondary > $OUT/c4_ns$ns.json 2> $OUT/c4_ns$ns.err
   python - $OUT/c4_ns$ns.json $ns <<'PY'
 import json,sys
 try:

@@ -10,7 +10,7 @@ cat $OUT/pytest.log
 for k in 1 2; do
 for off in 0 1; do
 for mode in pass em; do
-  DFM_NO_COV_TILE=$off timeout 300 python bench.py --N 1000 --T 2000 --r 20 --batch-per-gpu 256 --mode $mode --steps 10 --warmup 3 --repeats 5 --no-cpu-baseline --no-secondary > $OUT/c4_${mode}_off$off.json 2> $OUT/c4_${mode}_off$off.err
+  DFM_NO_COV_TILE=$off timeout 300 python bench.py --full --N 1000 --T 2000 --r 20 --batch-per-gpu 256 --mode $mode --steps 10 --warmup 3 --repeats 5 --no-cpu-baseline --no-secondary > $OUT/c4_${mode}_off$off.json 2> $OUT/c4_${mode}_off$off.err
   python - $OUT/c4_${mode}_off$off.json $mode $off <<'PY'
 import json,sys
 try:

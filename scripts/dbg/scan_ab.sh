@@ -10,13 +10,13 @@ timeout 900 python -m pytest tests/test_gpu_pass_fused.py tests/test_gpu_round3.
 tail -5 $OUT/pytest_sel.log
 B="--no-cpu-baseline --no-secondary --repeats 5"
 for i in 1 2; do
-  timeout 200 python bench.py $B > $OUT/new_$i.json 2> $OUT/new_$i.err
-  DFM_SCAN_ABL=512 timeout 200 python bench.py $B > $OUT/old_$i.json 2> $OUT/old_$i.err
+  timeout 200 python bench.py --full $B > $OUT/new_$i.json 2> $OUT/new_$i.err
+  DFM_SCAN_ABL=512 timeout 200 python bench.py --full $B > $OUT/old_$i.json 2> $OUT/old_$i.err
 done
-timeout 200 python bench.py $B --batch-per-gpu 8192 --steps 10 --warmup 2 > $OUT/new_b8192.json 2> $OUT/new_b8192.err
-DFM_SCAN_ABL=512 timeout 200 python bench.py $B --batch-per-gpu 8192 --steps 10 --warmup 2 > $OUT/old_b8192.json 2> $OUT/old_b8192.err
-timeout 200 python bench.py $B --mode em --steps 20 > $OUT/new_em.json 2> $OUT/new_em.err
-DFM_SCAN_ABL=512 timeout 200 python bench.py $B --mode em --steps 20 > $OUT/old_em.json 2> $OUT/old_em.err
+timeout 200 python bench.py --full $B --batch-per-gpu 8192 --steps 10 --warmup 2 > $OUT/new_b8192.json 2> $OUT/new_b8192.err
+DFM_SCAN_ABL=512 timeout 200 python bench.py --full $B --batch-per-gpu 8192 --steps 10 --warmup 2 > $OUT/old_b8192.json 2> $OUT/old_b8192.err
+timeout 200 python bench.py --full $B --mode em --steps 20 > $OUT/new_em.json 2> $OUT/new_em.err
+DFM_SCAN_ABL=512 timeout 200 python bench.py --full $B --mode em --steps 20 > $OUT/old_em.json 2> $OUT/old_em.err
 B=1024 DFM_PASS_NSW=4 timeout 120 python scripts/pf_prof.py > $OUT/timeline_new.txt 2>&1
 B=1024 DFM_PASS_NSW=4 PF_ABL=512 timeout 120 python scripts/pf_prof.py > $OUT/timeline_old.txt 2>&1
 for f in new_1 old_1 new_2 old_2 new_b8192 old_b8192 new_em old_em; do

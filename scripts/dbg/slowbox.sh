@@ -7,7 +7,7 @@
 cd $GRAFT_REPO_ROOT
 echo "kernel: $(uname -r)"
 timeout 60 scripts/microbench/icache
-timeout 120 python bench.py --no-cpu-baseline --no-secondary --repeats 3 2>/dev/null | python -c "
+timeout 120 python bench.py --full --no-cpu-baseline --no-secondary --repeats 3 2>/dev/null | python -c "
 import json,sys
 d=json.loads([l for l in sys.stdin.read().splitlines() if l.startswith('{')][-1]); print('bench value=%.4g frac=%.3f'%(d['value'], d['roofline']['whole_step']['frac']))"
 B=1024 DFM_PASS_NSW=4 timeout 120 python scripts/pf_prof.py 2>&1 | grep -v amdgpu | grep '^round\|first cov\|last scan end\|span\|cov round\|scan: compute'

@@ -6,7 +6,7 @@ if [ -z "$ANYBOX" ] && ! uname -r | grep -q "6.18.50"; then echo "fast box: noth
 run() {
   echo "=== $*"
   env "$@" timeout 60 scripts/microbench/icache | sed -n '2,5p'
-  env "$@" timeout 120 python bench.py --no-cpu-baseline --no-secondary --repeats 3 2>/dev/null | python -c "
+  env "$@" timeout 120 python bench.py --full --no-cpu-baseline --no-secondary --repeats 3 2>/dev/null | python -c "
 import json,sys
 d=json.loads([l for l in sys.stdin.read().splitlines() if l.startswith('{')][-1]); print('bench value=%.4g ms=%.4f'%(d['value'], d['ms_per_step']))"
 }

@@ -8,16 +8,16 @@ timeout 900 python -m pytest tests/test_gpu_pass_fused.py tests/test_gpu_round3.
 B="--no-cpu-baseline --no-secondary --repeats 5"
 for rep in 1 2 3; do
 for ABL in 0 65536; do
-  DFM_SCAN_ABL=$ABL timeout 200 python bench.py $B > $OUT/b1024_${ABL}_$rep.json 2> $OUT/b1024_${ABL}_$rep.err
+  DFM_SCAN_ABL=$ABL timeout 200 python bench.py --full $B > $OUT/b1024_${ABL}_$rep.json 2> $OUT/b1024_${ABL}_$rep.err
 done
 done
 for rep in 1 2; do
 for ABL in 0 65536; do
-  DFM_SCAN_ABL=$ABL timeout 200 python bench.py $B --batch-per-gpu 8192 --steps 10 --warmup 2 --repeats 3 > $OUT/b8192_${ABL}_$rep.json 2> $OUT/b8192_${ABL}_$rep.err
+  DFM_SCAN_ABL=$ABL timeout 200 python bench.py --full $B --batch-per-gpu 8192 --steps 10 --warmup 2 --repeats 3 > $OUT/b8192_${ABL}_$rep.json 2> $OUT/b8192_${ABL}_$rep.err
 done
 done
 for ABL in 0 65536; do
-  DFM_SCAN_ABL=$ABL timeout 200 python bench.py $B --mode em --steps 20 > $OUT/em_$ABL.json 2> $OUT/em_$ABL.err
+  DFM_SCAN_ABL=$ABL timeout 200 python bench.py --full $B --mode em --steps 20 > $OUT/em_$ABL.json 2> $OUT/em_$ABL.err
 done
 B=1024 DFM_PASS_NSW=4 timeout 120 python scripts/pf_prof.py > $OUT/timeline_new.txt 2>&1
 for f in $OUT/b1024_*.json $OUT/b8192_*.json $OUT/em_*.json; do

@@ -14,20 +14,20 @@ if [ -z "$SKIP_TESTS" ]; then
   timeout 1500 python -m pytest tests -q -m gpu --maxfail=25 2>&1 | tail -60 > $OUT/pytest_gpu.log
   timeout 300 python __graft_entry__.py --smoke 2>&1 | tail -3 > $OUT/smoke.log
 fi
-timeout 400 python bench.py > $OUT/bench.json 2> $OUT/bench.err
+timeout 400 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 if [ -z "$SKIP_EXTRA" ]; then
-  DFM_PASS_FUSED=0 timeout 300 python bench.py --no-cpu-baseline --repeats 5 > $OUT/bench_two_launch.json 2> $OUT/bench_two_launch.err
-  timeout 300 python bench.py --batch-per-gpu 8192 --steps 10 --warmup 2 --repeats 5 --no-cpu-baseline > $OUT/bench_b8192.json 2> $OUT/bench_b8192.err
-  timeout 300 python bench.py --N 1000 --T 2000 --r 20 --batch-per-gpu 256 --steps 5 --warmup 2 --repeats 5 --no-cpu-baseline > $OUT/bench_c4.json 2> $OUT/bench_c4.err
-  timeout 300 python bench.py --mode em --steps 20 --warmup 3 --repeats 5 > $OUT/bench_em.json 2> $OUT/bench_em.err
-  timeout 300 python bench.py --mode pca --steps 5 --warmup 1 --repeats 5 > $OUT/bench_pca.json 2> $OUT/bench_pca.err
-  timeout 300 python bench.py --missing 0.1 --steps 20 --warmup 3 --repeats 5 --no-cpu-baseline > $OUT/bench_missing10.json 2> $OUT/bench_missing10.err
-  timeout 300 python bench.py --N 1000 --T 2000 --r 20 --batch-per-gpu 256 --missing 0.1 --steps 3 --warmup 1 --repeats 3 --no-cpu-baseline > $OUT/bench_c4_missing10.json 2> $OUT/bench_c4_missing10.err
-  timeout 300 python bench.py --mode em --N 1000 --T 2000 --r 20 --batch-per-gpu 256 --steps 3 --warmup 1 --repeats 3 --no-cpu-baseline > $OUT/bench_c4_em.json 2> $OUT/bench_c4_em.err
+  DFM_PASS_FUSED=0 timeout 300 python bench.py --full --no-cpu-baseline --repeats 5 > $OUT/bench_two_launch.json 2> $OUT/bench_two_launch.err
+  timeout 300 python bench.py --full --batch-per-gpu 8192 --steps 10 --warmup 2 --repeats 5 --no-cpu-baseline > $OUT/bench_b8192.json 2> $OUT/bench_b8192.err
+  timeout 300 python bench.py --full --N 1000 --T 2000 --r 20 --batch-per-gpu 256 --steps 5 --warmup 2 --repeats 5 --no-cpu-baseline > $OUT/bench_c4.json 2> $OUT/bench_c4.err
+  timeout 300 python bench.py --full --mode em --steps 20 --warmup 3 --repeats 5 > $OUT/bench_em.json 2> $OUT/bench_em.err
+  timeout 300 python bench.py --full --mode pca --steps 5 --warmup 1 --repeats 5 > $OUT/bench_pca.json 2> $OUT/bench_pca.err
+  timeout 300 python bench.py --full --missing 0.1 --steps 20 --warmup 3 --repeats 5 --no-cpu-baseline > $OUT/bench_missing10.json 2> $OUT/bench_missing10.err
+  timeout 300 python bench.py --full --N 1000 --T 2000 --r 20 --batch-per-gpu 256 --missing 0.1 --steps 3 --warmup 1 --repeats 3 --no-cpu-baseline > $OUT/bench_c4_missing10.json 2> $OUT/bench_c4_missing10.err
+  timeout 300 python bench.py --full --mode em --N 1000 --T 2000 --r 20 --batch-per-gpu 256 --steps 3 --warmup 1 --repeats 3 --no-cpu-baseline > $OUT/bench_c4_em.json 2> $OUT/bench_c4_em.err
   bash $R/scripts/dbg/extra_shapes.sh $TAG > /dev/null 2>&1
 fi
 if [ -n "$PROFILE" ]; then
-  (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o bench -- python $R/bench.py --steps 30 --warmup 5 --repeats 3 --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.err)
+  (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o bench -- python $R/bench.py --full --steps 30 --warmup 5 --repeats 3 --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.err)
   cp $(find $OUT/stats -name '*kernel_stats.csv' | head -1) $OUT/kernel_stats.csv 2>/dev/null
 fi
 (echo '--- after the runs'; rocm-smi --showclocks --showpower 2>/dev/null | grep -v '^=' | grep -v '^$') >> $OUT/device.txt

@@ -14,17 +14,17 @@ if [ -z "$SKIP_TESTS" ]; then
   timeout 1500 python -m pytest tests -q -m gpu --maxfail=25 2>&1 | tail -80 > $OUT/pytest_gpu.log
   timeout 300 python __graft_entry__.py --smoke 2>&1 | tail -3 > $OUT/smoke.log
 fi
-timeout 600 python bench.py > $OUT/bench.json 2> $OUT/bench.err
+timeout 600 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 B=1024 DFM_PASS_NSW=4 timeout 120 python scripts/pf_prof.py > $OUT/fused_timeline_B1024.txt 2>&1
 if [ -z "$SKIP_LIB" ]; then
-  timeout 300 python bench.py --driver lib --mode em --steps 20 --warmup 3 --repeats 5 > $OUT/bench_lib_em.json 2> $OUT/bench_lib_em.err
-  timeout 300 python bench.py --driver lib --mode em --force-comm --steps 20 --warmup 3 --repeats 5 > $OUT/bench_lib_em_comm.json 2> $OUT/bench_lib_em_comm.err
-  timeout 300 python bench.py --driver lib --mode em --batch-per-gpu 8192 --steps 10 --warmup 2 --repeats 3 > $OUT/bench_lib_em_b8192.json 2> $OUT/bench_lib_em_b8192.err
-  timeout 300 python bench.py --mode em --batch-per-gpu 8192 --steps 10 --warmup 2 --repeats 3 --no-cpu-baseline > $OUT/bench_em_b8192.json 2> $OUT/bench_em_b8192.err
-  timeout 300 python bench.py --driver lib --mode pass --steps 20 --warmup 3 --repeats 5 > $OUT/bench_lib_pass.json 2> $OUT/bench_lib_pass.err
+  timeout 300 python bench.py --full --driver lib --mode em --steps 20 --warmup 3 --repeats 5 > $OUT/bench_lib_em.json 2> $OUT/bench_lib_em.err
+  timeout 300 python bench.py --full --driver lib --mode em --force-comm --steps 20 --warmup 3 --repeats 5 > $OUT/bench_lib_em_comm.json 2> $OUT/bench_lib_em_comm.err
+  timeout 300 python bench.py --full --driver lib --mode em --batch-per-gpu 8192 --steps 10 --warmup 2 --repeats 3 > $OUT/bench_lib_em_b8192.json 2> $OUT/bench_lib_em_b8192.err
+  timeout 300 python bench.py --full --mode em --batch-per-gpu 8192 --steps 10 --warmup 2 --repeats 3 --no-cpu-baseline > $OUT/bench_em_b8192.json 2> $OUT/bench_em_b8192.err
+  timeout 300 python bench.py --full --driver lib --mode pass --steps 20 --warmup 3 --repeats 5 > $OUT/bench_lib_pass.json 2> $OUT/bench_lib_pass.err
 fi
 if [ -z "$SKIP_PMC" ]; then
-  (cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o bench -- python $R/bench.py --steps 30 --warmup 5 --repeats 3 --no-cpu-baseline --no-secondary > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.err)
+  (cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o bench -- python $R/bench.py --full --steps 30 --warmup 5 --repeats 3 --no-cpu-baseline --no-secondary > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.err)
   cp $(find $OUT/stats -name '*kernel_stats.csv' | head -1) $OUT/kernel_stats.csv 2>/dev/null
   rm -rf $OUT/stats
   (cd /tmp && timeout 60 rocprofv3 -L > $OUT/counters_avail.txt 2>&1)

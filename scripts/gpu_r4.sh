@@ -12,16 +12,16 @@ if [ -z "$SKIP_TESTS" ]; then
   timeout 1500 python -m pytest tests -q -m gpu --maxfail=25 2>&1 | tail -40 > $OUT/pytest_gpu.log
   timeout 300 python __graft_entry__.py --smoke 2>&1 | tail -3 > $OUT/smoke.log
 fi
-timeout 900 python bench.py > $OUT/bench.json 2> $OUT/bench.err
-(cd /tmp && timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o bench -- python $R/bench.py --steps 30 --warmup 5 --repeats 3 --no-cpu-baseline --no-secondary > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.err)
+timeout 900 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
+(cd /tmp && timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o bench -- python $R/bench.py --full --steps 30 --warmup 5 --repeats 3 --no-cpu-baseline --no-secondary > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.err)
 cp $(find $OUT/stats -name '*kernel_stats.csv' | head -1) $OUT/kernel_stats.csv 2>/dev/null; rm -rf $OUT/stats
-(cd /tmp && timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o bench -- python $R/bench.py --N 1000 --T 2000 --r 20 --batch-per-gpu 256 --missing 0.1 --steps 2 --warmup 1 --repeats 2 --no-cpu-baseline --no-secondary > $OUT/bench_c4m_under_rocprof.json 2> $OUT/bench_c4m_under_rocprof.err)
+(cd /tmp && timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o bench -- python $R/bench.py --full --N 1000 --T 2000 --r 20 --batch-per-gpu 256 --missing 0.1 --steps 2 --warmup 1 --repeats 2 --no-cpu-baseline --no-secondary > $OUT/bench_c4m_under_rocprof.json 2> $OUT/bench_c4m_under_rocprof.err)
 cp $(find $OUT/stats -name '*kernel_stats.csv' | head -1) $OUT/kernel_stats_c4_missing10.csv 2>/dev/null; rm -rf $OUT/stats
-(cd /tmp && timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o bench -- python $R/bench.py --N 1000 --T 2000 --r 20 --batch-per-gpu 256 --missing 0.1 --mode em --steps 2 --warmup 1 --repeats 2 --no-cpu-baseline --no-secondary > $OUT/bench_c4m_em_under_rocprof.json 2> $OUT/bench_c4m_em_under_rocprof.err)
+(cd /tmp && timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o bench -- python $R/bench.py --full --N 1000 --T 2000 --r 20 --batch-per-gpu 256 --missing 0.1 --mode em --steps 2 --warmup 1 --repeats 2 --no-cpu-baseline --no-secondary > $OUT/bench_c4m_em_under_rocprof.json 2> $OUT/bench_c4m_em_under_rocprof.err)
 cp $(find $OUT/stats -name '*kernel_stats.csv' | head -1) $OUT/kernel_stats_c4_em_missing10.csv 2>/dev/null; rm -rf $OUT/stats
-(cd /tmp && timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o bench -- python $R/bench.py --N 1000 --T 2000 --r 20 --batch-per-gpu 256 --steps 10 --warmup 2 --repeats 3 --no-cpu-baseline --no-secondary > $OUT/bench_c4_under_rocprof.json 2> $OUT/bench_c4_under_rocprof.err)
+(cd /tmp && timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o bench -- python $R/bench.py --full --N 1000 --T 2000 --r 20 --batch-per-gpu 256 --steps 10 --warmup 2 --repeats 3 --no-cpu-baseline --no-secondary > $OUT/bench_c4_under_rocprof.json 2> $OUT/bench_c4_under_rocprof.err)
 cp $(find $OUT/stats -name '*kernel_stats.csv' | head -1) $OUT/kernel_stats_c4.csv 2>/dev/null; rm -rf $OUT/stats
-(cd /tmp && timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o bench -- python $R/bench.py --mode em --steps 20 --warmup 3 --repeats 3 --no-cpu-baseline --no-secondary > $OUT/bench_em_under_rocprof.json 2> $OUT/bench_em_under_rocprof.err)
+(cd /tmp && timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o bench -- python $R/bench.py --full --mode em --steps 20 --warmup 3 --repeats 3 --no-cpu-baseline --no-secondary > $OUT/bench_em_under_rocprof.json 2> $OUT/bench_em_under_rocprof.err)
 cp $(find $OUT/stats -name '*kernel_stats.csv' | head -1) $OUT/kernel_stats_em.csv 2>/dev/null; rm -rf $OUT/stats
 if [ -z "$SKIP_PMC" ]; then
   (cd /tmp && K=6 timeout 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -o p -- python $R/scripts/gpu_trace.py > /dev/null 2> $OUT/pmc_fetch.err)

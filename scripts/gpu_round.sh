@@ -10,7 +10,7 @@ if [ -z "$SKIP_TESTS" ]; then
   timeout 900 python -m pytest tests -x -q -m gpu 2>&1 | tail -15 > $OUT/pytest_gpu.log
   timeout 300 python __graft_entry__.py --smoke 2>&1 | tail -3 > $OUT/smoke.log
 fi
-timeout 400 python bench.py --steps 30 --warmup 5 ${BENCH_ARGS} > $OUT/bench.json 2> $OUT/bench.err
+timeout 400 python bench.py --full --steps 30 --warmup 5 ${BENCH_ARGS} > $OUT/bench.json 2> $OUT/bench.err
 if [ -n "$PROBE" ]; then
   timeout 600 python scripts/gpu_probe.py --skip-parity "$@" > $OUT/probe.log 2>&1
 fi

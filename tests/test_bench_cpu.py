@@ -143,3 +143,37 @@ def test_em_iteration_bytes():
     """Compulsory bytes of an EM iteration with a k-wide companion state: the panel twice, the parameters in and out."""
     assert bench.em_iteration_bytes(139, 222, 4, 16) == 8 * (2 * 139 * 222 + 2 * (139 * 4 + 139 + 4 * 16 + 16 + 16 + 256) + 1)
     assert bench.em_iteration_bytes(139, 222, 4, 20, 4) - bench.em_iteration_bytes(139, 222, 4, 20) == 8 * 2 * 139 * 4
+
+
+def test_a_plain_run_times_exactly_the_requested_steps():
+    """`--steps K` is the number of timed steps of a plain run (one block); --full times --repeats blocks as before."""
+    import argparse
+    assert bench.repeats_of(argparse.Namespace(full=False, repeats=9)) == 1
+    assert bench.repeats_of(argparse.Namespace(full=True, repeats=9)) == 9
+    assert bench.repeats_of(argparse.Namespace(full=True, repeats=0)) == 1
+
+
+def test_dump_outputs_are_float64_within_the_limit_and_a_fixed_sample(tmp_path):
+    """--dump-outputs: every array as <name>.npy in float64; over the limit, the same seeded replicates of every array."""
+    import numpy as np
+    import torch
+    g = torch.Generator().manual_seed(0)
+    arrays = {"f_smooth": torch.randn(64, 30, 4, generator=g, dtype=torch.float64),
+              "P_smooth": torch.randn(64, 30, 10, generator=g, dtype=torch.float64),
+              "loglik": torch.randn(64, generator=g, dtype=torch.float64)}
+    whole = bench.dump_outputs(str(tmp_path / "whole"), arrays)
+    assert whole["replicates"] == 64 and whole["sample"] is None
+    for name, a in arrays.items():
+        x = np.load(tmp_path / "whole" / f"{name}.npy")
+        assert x.dtype == np.float64 and np.array_equal(x, a.numpy())
+    limit = 20000
+    cut = [bench.dump_outputs(str(tmp_path / d), arrays, limit=limit) for d in ("a", "b")]
+    assert cut[0]["replicates"] == cut[1]["replicates"] < 64 and cut[0]["bytes"] <= limit
+    files = lambda d: {n: np.load(tmp_path / d / f"{n}.npy") for n in arrays}
+    a, b = files("a"), files("b")
+    assert all(np.array_equal(a[n], b[n]) for n in arrays)                     # the same sample in every run
+    S = cut[0]["replicates"]
+    idx = [int(np.nonzero((arrays["loglik"].numpy() == v))[0][0]) for v in a["loglik"]]
+    assert len(idx) == S and idx == sorted(idx)
+    assert np.array_equal(a["f_smooth"], arrays["f_smooth"].numpy()[idx])       # the same replicates of every array
+    assert np.array_equal(a["P_smooth"], arrays["P_smooth"].numpy()[idx])

@@ -17,7 +17,8 @@ from oracle import als_oracle as ao
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLD = json.load(open(os.path.join(HERE, "golden", "notebook_goldens.json")))
-REF_XLSX = "/root/reference/data/hom_fac_1.xlsx"
+# the two sheets of the reference's spreadsheet that readin_data reads, cell values only (tests/golden/make_sw_fixture.py)
+REF_XLSX = os.path.join(HERE, "golden", "hom_fac_1_sheets.xlsx")
 INIT, LAST = 3, 224          # (1959,3)..(2014,4): Stock_Watson.ipynb:217-218
 
 
@@ -54,9 +55,8 @@ def test_fixture_dimensions(sw):
     assert GOLD["dims"]["quarterly"] == [224, 85]
 
 
-@pytest.mark.skipif(not os.path.exists(REF_XLSX), reason="reference spreadsheet not mounted (GPU box)")
 def test_fixture_matches_spreadsheet(sw):
-    """The committed fixture is what the restated `readin_data` produces from the reference's xlsx."""
+    """The committed fixture is what the restated `readin_data` produces from the reference's xlsx (its two sheets)."""
     from oracle import sw_panel as sp
     dA = sp.readin_data(REF_XLSX, "All")
     dR = sp.readin_data(REF_XLSX, "Real")
