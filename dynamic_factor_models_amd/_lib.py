@@ -38,6 +38,7 @@ _EMSTEP_ARGS = [c_vp, c_int, c_int, c_int, c_int] + [c_vp] * 8 + [c_uint]
 _EM_ARGS = [c_vp, c_int, c_int, c_int, c_int] + [c_vp] * 7 + [c_int, ctypes.c_double] + [c_vp] * 4 + [c_uint]
 _VPASS_ARGS = [c_vp, c_int, c_int, c_int, c_int, c_int] + [c_vp] * 10 + [c_uint]
 _VEM_ARGS = [c_vp, c_int, c_int, c_int, c_int, c_int] + [c_vp] * 7 + [c_int, ctypes.c_double] + [c_vp] * 4 + [c_uint]
+_FC_ARGS = [c_vp, c_int, c_int, c_int, c_int, c_int, c_int] + [c_vp] * 15 + [c_uint]
 _ARPASS_ARGS = [c_vp, c_int, c_int, c_int, c_int, c_int, c_int] + [c_vp] * 11 + [c_uint]
 _AREM_ARGS = [c_vp, c_int, c_int, c_int, c_int, c_int, c_int] + [c_vp] * 8 + [c_int, ctypes.c_double] + [c_vp] * 4 + [c_uint]
 _OBSEM_ARGS = [c_vp, c_int, c_int, c_int, c_int, c_int] + [c_vp] * 8 + [c_int, ctypes.c_double] + [c_vp] * 4 + [c_uint]
@@ -86,6 +87,8 @@ SYMBOLS = {
     "dfm_ks_pass_varp_batch": (c_int, _VPASS_ARGS),
     "dfm_em_varp_batch_dev": (c_int, _VEM_ARGS),
     "dfm_em_varp_batch": (c_int, _VEM_ARGS),
+    "dfm_forecast_batch_dev": (c_int, _FC_ARGS),
+    "dfm_forecast_batch": (c_int, _FC_ARGS),
     "dfm_ks_pass_ar_batch_dev": (c_int, _ARPASS_ARGS),
     "dfm_ks_pass_ar_batch": (c_int, _ARPASS_ARGS),
     "dfm_em_ar_batch_dev": (c_int, _AREM_ARGS),

@@ -397,6 +397,103 @@ def _bootstrap_replicates(z, params, nrep, seed, ngpu, max_em_iter, tol_em, sing
     return dict(params=new, loglik_path=path, iters=iters, iterations=ran, panels=panels)
 
 
+# ----------------------------------------------------------------------------- nowcasts and forecasts of the panel
+def _forecast_inputs(m: DFMModel, through: int):
+    """The series `estimate` used (inclcode == 1 and the `enough` rule), the estimation window's mean and population s.d.
+    (standardize_data, dfm_functions.ipynb:501-509), and rows initperiod..through standardised with them."""
+    incl = m.inclcode == 1
+    xwin = m.data[m.initperiod - 1:m.lastperiod, :][:, incl]
+    n = np.count_nonzero(~np.isnan(xwin), axis=0)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mu = np.nansum(xwin, axis=0) / n
+    z, sd = standardize_data(xwin)
+    enough = (~np.isnan(z)).sum(axis=0) >= m.nt_min_factor_estimation
+    cols = np.nonzero(incl)[0][enough]
+    mu, sd = mu[enough], sd[0][enough]
+    x = m.data[m.initperiod - 1:through, :][:, cols]
+    return cols, (x - mu) / sd, mu, sd
+
+
+def forecast(m: DFMModel, H: int, *, through: Optional[int] = None, quantiles=None, ctx=None) -> dict:
+    """Nowcasts and H-step forecasts of the panel from the parametric fit (`estimate(m, Parametric())`, nfac_o = 0).
+
+    Parameters come from the estimation window (m.em_params; its series and its mean / population s.d.); the state conditions
+    on rows initperiod..`through` (1-based, lastperiod <= through <= m.T, default lastperiod), standardised with the window's
+    mean and s.d. -- rows after lastperiod are the ragged edge a nowcast is for.  One dfm_forecast_batch call on the GPU.
+    Returns a dict (data units unless noted):
+      rows        1-based periods initperiod .. through + H (the last H are the forecast horizon)
+      cols        column indices (0-based) of m.data: the series estimate() used
+      x           [rows, cols] observed cells as they are, every other cell E[x_ti | X]
+      x_sd        [rows, cols] s.d. of x given X: 0 on observed cells, sd_i sqrt(lam_i' P_t lam_i + R_i) elsewhere
+      common      [rows, cols] mean_i + sd_i lam_i' E[f_t | X]
+      factor      [rows, r] E[f_t | X] (the model's standardised factor units), factor_cov [rows, r, r] = Var[f_t | X]
+      loglik      log-likelihood of the observed cells of rows initperiod..through at the fitted parameters
+    `quantiles` (needs m.replicates from estimate(..., nrep=...)): every replicate's parameter set runs in ONE batched call on
+    the same panel, and dfm_quantile_bands over the replicates' horizon rows gives bands [nq, H, len(cols)] (nearest rank).
+    These bands are the PARAMETER uncertainty of the point forecast only; x_sd carries the shock part.  `m` is not modified."""
+    H = int(H)
+    if H < 0:
+        raise ValueError("H must be >= 0")
+    if m.em_params is None:
+        raise ValueError("the model has not been estimated: run estimate(m, Parametric()) first")
+    if m.nfac_o != 0:
+        raise ValueError("forecast needs nfac_o = 0 (the future values of observed factors are unknown)")
+    through = m.lastperiod if through is None else int(through)
+    if not (m.lastperiod <= through <= m.T):
+        raise ValueError(f"through must lie in lastperiod..T ({m.lastperiod}..{m.T})")
+    qs = None
+    if quantiles is not None:
+        qs = np.atleast_1d(np.asarray(quantiles, dtype=np.float64))
+        if getattr(m, "replicates", None) is None:
+            raise ValueError("quantile bands need bootstrap replicates: estimate(m, Parametric(), nrep=...) first")
+        if H < 1:
+            raise ValueError("quantile bands need H >= 1")
+        if qs.size < 1 or not np.all((qs > 0.0) & (qs <= 1.0)):
+            raise ValueError("quantiles must lie in (0, 1]")
+    ep = m.em_params
+    Lam, R, Q = ep["Lam"], ep["R"], ep["Q"]
+    A = ep["Avar"] if "Avar" in ep else ep["A"]
+    mu0, P0 = ep["mu0"], ep["P0"]
+    r = Lam.shape[1]
+    cols, z, mu, sd = _forecast_inputs(m, through)
+    if Lam.shape[0] != cols.size:
+        raise ValueError("m.em_params does not match the model's series (was the model changed after estimate?)")
+    from ._lib import DfmError
+    ctx, own = _own(ctx)
+    try:
+        def run(Lb, Rb, Ab, Qb, m0, P0b, **kw):
+            B = Lb.shape[0]
+            rep = lambda a: np.ascontiguousarray(np.broadcast_to(a, (B,) + a.shape))
+            args = (rep(z), Lb, Rb, Ab, Qb, m0, P0b, H)
+            kw.update(mean=rep(mu), sd=rep(sd), may_have_missing=bool(np.isnan(z).any()))
+            try:
+                return ctx.forecast_batch_host(*args, **kw)
+            except DfmError as err:                 # the information form inverts Q: as estimate(), retry in covariance form
+                if err.code != -5:
+                    raise
+                return ctx.forecast_batch_host(*args, singular_q=True, **kw)
+        o = run(Lam[None], R[None], A[None], Q[None], mu0[None], P0[None])
+        bands = None
+        if qs is not None:
+            rp = m.replicates["params"]
+            ob = run(rp["Lam"], rp["R"], rp["A"], rp["Q"], rp["mu0"], rp["P0"], want_var=False, want_common=False, want_P=False)
+            bands = ctx.quantile_bands_host(ob["xhat"][:, -H:, :], qs)
+    finally:
+        if own:
+            ctx.close()
+    il = np.tril_indices(r)                                             # packed lower, row-major (include/dfm_hip.h)
+    Pp = o["P"][0]
+    cov = np.empty((Pp.shape[0], r, r))
+    cov[:, il[0], il[1]] = Pp
+    cov[:, il[1], il[0]] = Pp
+    out = dict(rows=np.arange(m.initperiod, through + H + 1), cols=cols, x=o["xhat"][0], x_sd=np.sqrt(o["xvar"][0]),
+               common=o["common"][0], factor=o["f"][0], factor_cov=cov, loglik=float(o["loglik"][0]))
+    if bands is not None:
+        out["quantiles"] = qs
+        out["bands"] = bands
+    return out
+
+
 # ============================================================================= the NON-parametric path
 # `estimate!(m, ::NonParametric)` (dfm_functions.ipynb:530-543) = estimate_factor! -> estimate_factor_loading!
 # -> estimate_var!, with every regression run by the batched HIP kernels of als.hip (dfm_als_batch /

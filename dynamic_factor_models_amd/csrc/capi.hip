@@ -71,6 +71,8 @@ struct dfm_handle {
     dfm::EmUpdArgs deferred_em;
     void* odd = nullptr;                   // panel / loadings / R with one all-missing series appended (odd N beyond the tilings, odd_pad)
     size_t odd_bytes = 0;
+    void* fc = nullptr;                    // dfm_forecast_batch_dev: the pass's T-row moments, the forecast tail, P and loglik when the
+    size_t fc_bytes = 0;                   // caller does not take them (beside h->ws: the pass itself may reallocate that)
     const double* odd_panel_src = nullptr; int odd_panel_dims[3] = {0, 0, 0};   // the panel whose padded copy h->odd holds (odd_pad keep_panel)
     std::string prof_file;                 // DFM_PF_PROF_FILE with DFM_SCAN_ABL=256: phase stamps of the fused pass
     char err[512] = {0};
@@ -82,11 +84,11 @@ struct dfm_handle {
 };
 
 enum KernelId { K_COLLAPSE = 0, K_RECURSION, K_MSTEP_STATS, K_MSTEP_SOLVE, K_PCA, K_SYNTH, K_PAD,
-                K_COLLAPSE_DMA, K_GRAM, K_COV, K_MEANSCAN, K_PFILL, K_COLLAPSE_MFMA, K_ALS, K_OLS, K_BOOT, K_QUANT, K_COLLAPSE_WIDE, K_EM_UPDATE, K_CHOW, K_MSTEP_MFMA, K_GRAM_XX, K_PASS_FUSED, K_COUNT };
+                K_COLLAPSE_DMA, K_GRAM, K_COV, K_MEANSCAN, K_PFILL, K_COLLAPSE_MFMA, K_ALS, K_OLS, K_BOOT, K_QUANT, K_COLLAPSE_WIDE, K_EM_UPDATE, K_CHOW, K_MSTEP_MFMA, K_GRAM_XX, K_PASS_FUSED, K_FC_TAIL, K_FC_FILL, K_FC_PAD, K_COUNT };
 static const char* const kKernelNames[K_COUNT] = {"collapse_kernel", "recursion_kernel", "mstep_lam_kernel",
                                                   "mstep_solve_kernel", "pca_kernel", "synth_kernel",
                                                   "pad_params_kernel", "collapse_dma_kernel", "gram_kernel",
-                                                  "cov_kernel", "meanscan_kernel", "pfill_kernel", "collapse_mfma_kernel", "als_kernel", "ols_kernel", "var_boot_kernel", "quantile_kernel", "collapse_wide_kernel", "em_update_kernel", "chow_kernel", "mstep_mfma_kernel", "gram_xx_kernel", "pass_fused_kernel"};
+                                                  "cov_kernel", "meanscan_kernel", "pfill_kernel", "collapse_mfma_kernel", "als_kernel", "ols_kernel", "var_boot_kernel", "quantile_kernel", "collapse_wide_kernel", "em_update_kernel", "chow_kernel", "mstep_mfma_kernel", "gram_xx_kernel", "pass_fused_kernel", "forecast_tail_kernel", "forecast_fill_kernel", "forecast_pad_kernel"};
 
 namespace dfm { int handle_device(const dfm_handle* h) { return h->device; } }   // (probe.hip)
 
@@ -1447,6 +1449,7 @@ int dfm_destroy(dfm_handle* h) {
     if (h->ev_join) hipEventDestroy(h->ev_join);
     if (h->ws) hipFree(h->ws);
     if (h->odd) hipFree(h->odd);
+    if (h->fc) hipFree(h->fc);
     if (h->status_dev) hipFree(h->status_dev);
     if (h->own_stream && h->stream) hipStreamDestroy(h->stream);
     delete h;
@@ -2318,4 +2321,138 @@ int dfm_standardize_batch_dev(dfm_handle* h, int B, int T, int N, double* panel,
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, launch_standardize(B, T, N, panel, mean, sd, h->stream));
     return 0;
+}
+
+
+// ---- nowcasts and forecasts of the panel (forecast.hip) ---------------------------------------------------------------
+// p = 1: the plain pass on the caller's T-row panel (its own route: fused balanced pass, chunked recursion, pipe, odd-N pad) into
+// h->fc, forecast_tail_kernel for the H rows behind it, forecast_fill_kernel for the panel-sized outputs (it also writes f_out /
+// P_out in the T + H row layout).  p > 1: the panel with H all-missing rows appended goes into xhat, the companion pass runs on it
+// as a (T + H)-row panel with missing cells straight into f_out / P_out (the smoothed moments of the empty rows are the forecast
+// moments), forecast_fill_kernel rewrites xhat in place.
+static int ensure_fc(dfm_handle* h, size_t bytes) {
+    if (bytes <= h->fc_bytes) return 0;
+    if (h->fc) {
+        HIP_TRY(h, hipDeviceSynchronize());
+        HIP_TRY(h, hipFree(h->fc));
+        h->fc = nullptr;
+        h->fc_bytes = 0;
+    }
+    HIP_TRY(h, hipMalloc(&h->fc, bytes));
+    h->fc_bytes = bytes;
+    return 0;
+}
+
+int dfm_forecast_batch_dev(dfm_handle* h, int B, int T, int N, int r, int p, int H, const double* panel, const double* Lam,
+                           const double* R, const double* Avar, const double* Q, const double* mu0, const double* P0,
+                           const double* mean, const double* sd, double* xhat, double* xvar, double* common, double* f_out,
+                           double* P_out, double* loglik, unsigned flags) {
+    if (int rc = check_dims(h, B, T, N, r)) return rc;
+    if (H < 0) return fail(h, DFM_E_DIMS, "H must be >= 0%s");
+    if (p < 1) return fail(h, DFM_E_DIMS, "number of factor lags must be >= 1%s");
+    if (r * p > DFM_MAX_R) return fail(h, DFM_E_R_UNSUPPORTED, "r * p > DFM_MAX_R (32)%s");
+    if (!panel || !Lam || !R || !Avar || !Q || !mu0 || !P0 || !xhat || !f_out)
+        return fail(h, DFM_E_NULL, "required pointer is NULL%s");
+    if ((mean == nullptr) != (sd == nullptr)) return fail(h, DFM_E_NULL, "mean and sd must both be given or both be NULL%s");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t d = sizeof(double), np = (size_t)r * (r + 1) / 2, TH = (size_t)T + H;
+    const bool needP = xvar != nullptr || P_out != nullptr;
+    FcFillArgs fa{};
+    fa.B = B; fa.T = T; fa.H = H; fa.N = N; fa.r = r;
+    fa.Lam = Lam; fa.R = R; fa.mean = mean; fa.sd = sd;
+    fa.xhat = xhat; fa.xvar = xvar; fa.common = common;
+    if (p == 1) {
+        size_t off = 0;
+        const size_t o_f = take(off, (size_t)B * T * r * d), o_P = needP ? take(off, (size_t)B * T * np * d) : (size_t)-1,
+                     o_ft = H ? take(off, (size_t)B * H * r * d) : (size_t)-1,
+                     o_Pt = (H && needP) ? take(off, (size_t)B * H * np * d) : (size_t)-1, o_ll = take(off, (size_t)B * d);
+        if (int rc = ensure_fc(h, off)) return rc;
+        char* base = static_cast<char*>(h->fc);
+        auto ptr = [&](size_t o) { return o == (size_t)-1 ? nullptr : reinterpret_cast<double*>(base + o); };
+        double *fsm = ptr(o_f), *Psm = ptr(o_P), *ft = ptr(o_ft), *Pt = ptr(o_Pt);
+        if (int rc = dfm_ks_pass_batch_dev(h, B, T, N, r, panel, Lam, R, Avar, Q, mu0, P0, fsm, Psm, loglik ? loglik : ptr(o_ll),
+                                           flags)) return rc;
+        if (H) {
+            FcTailArgs ta{B, T, H, r, fsm, Psm, Avar, Q, ft, Pt};
+            ProfScope ps(h, K_FC_TAIL);
+            HIP_TRY(h, launch_forecast_tail(ta, h->stream));
+        }
+        fa.panel = panel; fa.panel_rows = T;
+        fa.fh = fsm; fa.Ph = needP ? Psm : nullptr; fa.Th = T; fa.ft = ft; fa.Pt = Pt;
+        fa.f_out = f_out; fa.P_out = P_out;
+    } else {
+        double* Pbuf = P_out;
+        size_t off = 0;
+        const size_t o_P = (!P_out && xvar) ? take(off, (size_t)B * TH * np * d) : (size_t)-1, o_ll = take(off, (size_t)B * d);
+        if (int rc = ensure_fc(h, off)) return rc;
+        char* base = static_cast<char*>(h->fc);
+        if (o_P != (size_t)-1) Pbuf = reinterpret_cast<double*>(base + o_P);
+        {
+            ProfScope ps(h, K_FC_PAD);
+            HIP_TRY(h, launch_forecast_pad(B, T, H, N, panel, xhat, !(flags & DFM_F_MAY_HAVE_MISSING), h->status_dev, h->stream));
+        }
+        if (int rc = dfm_ks_pass_varp_batch_dev(h, B, (int)TH, N, r, p, xhat, Lam, R, Avar, Q, mu0, P0, f_out, Pbuf,
+                                                loglik ? loglik : reinterpret_cast<double*>(base + o_ll),
+                                                flags | DFM_F_MAY_HAVE_MISSING)) return rc;
+        fa.panel = xhat; fa.panel_rows = (int)TH;
+        fa.fh = f_out; fa.Ph = xvar ? Pbuf : nullptr; fa.Th = (int)TH; fa.ft = nullptr; fa.Pt = nullptr;
+        fa.f_out = nullptr; fa.P_out = nullptr;
+    }
+    ProfScope ps(h, K_FC_FILL);
+    HIP_TRY(h, launch_forecast_fill(fa, h->stream));
+    return 0;
+}
+
+int dfm_forecast_batch(dfm_handle* h, int B, int T, int N, int r, int p, int H, const double* panel, const double* Lam,
+                       const double* R, const double* Avar, const double* Q, const double* mu0, const double* P0,
+                       const double* mean, const double* sd, double* xhat, double* xvar, double* common, double* f_out,
+                       double* P_out, double* loglik, unsigned flags) {
+    if (int rc = check_dims(h, B, T, N, r)) return rc;
+    if (H < 0) return fail(h, DFM_E_DIMS, "H must be >= 0%s");
+    if (p < 1) return fail(h, DFM_E_DIMS, "number of factor lags must be >= 1%s");
+    if (r * p > DFM_MAX_R) return fail(h, DFM_E_R_UNSUPPORTED, "r * p > DFM_MAX_R (32)%s");
+    if (!panel || !Lam || !R || !Avar || !Q || !mu0 || !P0 || !xhat || !f_out)
+        return fail(h, DFM_E_NULL, "required pointer is NULL%s");
+    if ((mean == nullptr) != (sd == nullptr)) return fail(h, DFM_E_NULL, "mean and sd must both be given or both be NULL%s");
+    if (int rc = status_epoch(h)) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t d = sizeof(double), k = (size_t)r * p, np = (size_t)r * (r + 1) / 2, TH = (size_t)T + H;
+    const size_t n_panel = (size_t)B * T * N, n_lam = (size_t)B * N * r, n_R = (size_t)B * N, n_a = (size_t)B * r * k,
+                 n_q = (size_t)B * r * r, n_v = (size_t)B * k, n_p0 = (size_t)B * k * k, n_x = (size_t)B * TH * N,
+                 n_f = (size_t)B * TH * r, n_P = (size_t)B * TH * np;
+    const size_t total = n_panel + n_lam + n_R + n_a + n_q + n_v + n_p0 + (mean ? 2 * n_R : 0) + n_x * (1 + (xvar ? 1 : 0) + (common ? 1 : 0)) +
+                         n_f + (P_out ? n_P : 0) + B + 16 * 32;   // (+ every array 256-byte aligned: the fill kernel's 16-byte accesses)
+    double* buf = nullptr;
+    HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&buf), total * d));
+    double* dp = buf;
+    auto take_d = [&](size_t n) { double* dst = dp; dp += (n + 31) & ~(size_t)31; return dst; };
+    auto up = [&](const double* src, size_t n) -> double* {
+        double* dst = take_d(n);
+        (void)hipMemcpyAsync(dst, src, n * d, hipMemcpyHostToDevice, h->stream);
+        return dst;
+    };
+    auto out = [&](bool want, size_t n) -> double* { return want ? take_d(n) : nullptr; };
+    double *x_d = up(panel, n_panel), *lam_d = up(Lam, n_lam), *R_d = up(R, n_R), *A_d = up(Avar, n_a), *Q_d = up(Q, n_q),
+           *mu_d = up(mu0, n_v), *P0_d = up(P0, n_p0);
+    double *mean_d = mean ? up(mean, n_R) : nullptr, *sd_d = sd ? up(sd, n_R) : nullptr;
+    double *xh_d = out(true, n_x), *xv_d = out(xvar != nullptr, n_x), *cm_d = out(common != nullptr, n_x), *f_d = out(true, n_f),
+           *P_d = out(P_out != nullptr, n_P), *ll_d = out(true, (size_t)B);
+    int rc = dfm_forecast_batch_dev(h, B, T, N, r, p, H, x_d, lam_d, R_d, A_d, Q_d, mu_d, P0_d, mean_d, sd_d, xh_d, xv_d, cm_d,
+                                    f_d, P_d, ll_d, flags);
+    std::vector<double> ll_host((size_t)B);
+    if (rc == 0) {
+        auto down = [&](void* dst, const void* src, size_t n) { (void)hipMemcpyAsync(dst, src, n * d, hipMemcpyDeviceToHost, h->stream); };
+        down(xhat, xh_d, n_x);
+        if (xvar) down(xvar, xv_d, n_x);
+        if (common) down(common, cm_d, n_x);
+        down(f_out, f_d, n_f);
+        if (P_out) down(P_out, P_d, n_P);
+        down(ll_host.data(), ll_d, (size_t)B);
+        hipError_t e = hipStreamSynchronize(h->stream);
+        if (e != hipSuccess) rc = hip_fail(h, e, "hipStreamSynchronize");
+    }
+    if (rc == 0) rc = post_check(h, ll_host.data(), B);
+    if (rc == 0 && loglik) memcpy(loglik, ll_host.data(), (size_t)B * d);
+    (void)hipFree(buf);
+    return rc;
 }

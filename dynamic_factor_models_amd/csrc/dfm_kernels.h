@@ -440,6 +440,31 @@ struct ChowArgs {
 };
 hipError_t launch_chow(const ChowArgs& a, hipStream_t s);
 
+// Nowcasts and forecasts of the panel from a fitted model (forecast.hip).
+struct FcTailArgs {             // p = 1: f_{T+h|T}, P_{T+h|T} for h = 1..H from the terminal smoothed moments
+    int B, T, H, r;
+    const double* fsm;          // [B][T][r] smoothed factors
+    const double* Psm;          // [B][T][r(r+1)/2] packed, or null (no covariances wanted)
+    const double* A; const double* Q;   // [B][r][r]
+    double* ft;                 // [B][H][r]
+    double* Pt;                 // [B][H][r(r+1)/2] or null
+};
+hipError_t launch_forecast_tail(const FcTailArgs& a, hipStream_t s);
+struct FcFillArgs {
+    int B, T, H, N, r;
+    const double* panel; int panel_rows;   // [B][panel_rows][N], rows t < T read (panel_rows = T, or T + H for xhat in place)
+    const double* fh; const double* Ph; int Th;   // head rows t < Th: [B][Th][r], [B][Th][r(r+1)/2] (Ph null: no covariances)
+    const double* ft; const double* Pt;           // rows Th <= t < T + H: [B][H][..] (p = 1 tail)
+    const double* Lam; const double* R;           // [B][N][r], [B][N]
+    const double* mean; const double* sd;         // [B][N] or both null
+    double* xhat; double* xvar; double* common;   // [B][T+H][N]; xvar / common may be null
+    double* f_out; double* P_out;                 // copy of the staged rows in the [B][T+H] layout, or null
+    int RC, NPB, G, nchunk, nsblk;                // geometry (set by the launcher)
+};
+hipError_t launch_forecast_fill(const FcFillArgs& a, hipStream_t s);
+hipError_t launch_forecast_pad(int B, int T, int H, int N, const double* panel, double* out, bool check_nan, int* status,
+                               hipStream_t s);
+
 // Device-side synthetic replicates (synth.hip); all arrays in the caller's layout (r).
 struct SynthArgs {
     int B, T, N, r;

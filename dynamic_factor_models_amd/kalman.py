@@ -494,6 +494,75 @@ class DfmContext:
         _check(self._h, rc)
         return f, P, ll
 
+    # ------------------------------------------------------------------ nowcasts and forecasts (forecast.hip)
+    def forecast_batch(self, panel, Lam, R, Avar, Q, mu0, P0, H: int, mean=None, sd=None, want_var: bool = True,
+                       want_common: bool = True, want_P: bool = True, may_have_missing: Optional[bool] = None,
+                       singular_q: bool = False):
+        """dfm_forecast_batch_dev (device tensors, torch's current stream): smoothed / forecast moments and the panel's
+        nowcasts over T + H rows.  Avar [B,r,r p] ([A_1 .. A_p]; p = 1: A), Q [B,r,r], mu0 [B,r p], P0 [B,r p,r p];
+        mean / sd [B,N] (both or neither) put the outputs into data units.  Returns dict(xhat, xvar, common [B,T+H,N],
+        f [B,T+H,r], P [B,T+H,r(r+1)/2], loglik [B]); the outputs not asked for are None."""
+        torch = self._torch
+        B, T, N = panel.shape
+        r = Lam.shape[2]
+        k = Avar.shape[2]
+        p = k // r
+        if int(H) < 0:
+            raise ValueError("H must be >= 0")
+        if (mean is None) != (sd is None):
+            raise ValueError("mean and sd go together")
+        flags = self._flags(panel, may_have_missing, singular_q)
+        TH = T + int(H)
+        dev = panel.device
+        new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)
+        xhat = new(B, TH, N)
+        xvar = new(B, TH, N) if want_var else None
+        common = new(B, TH, N) if want_common else None
+        f = new(B, TH, r)
+        P = new(B, TH, r * (r + 1) // 2) if want_P else None
+        ll = new(B)
+        opt = lambda t, name, shape=None: None if t is None else self._dev(t, name, shape)
+        self._sync_stream()
+        rc = self._lib.dfm_forecast_batch_dev(
+            self._h, B, T, N, r, p, int(H), self._dev(panel, "panel"), self._dev(Lam, "Lam", (B, N, r)),
+            self._dev(R, "R", (B, N)), self._dev(Avar, "Avar", (B, r, r * p)), self._dev(Q, "Q", (B, r, r)),
+            self._dev(mu0, "mu0", (B, k)), self._dev(P0, "P0", (B, k, k)), opt(mean, "mean", (B, N)), opt(sd, "sd", (B, N)),
+            self._dev(xhat, "xhat"), opt(xvar, "xvar"), opt(common, "common"), self._dev(f, "f_out"), opt(P, "P_out"),
+            self._dev(ll, "loglik"), flags)
+        _check(self._h, rc)
+        return dict(xhat=xhat, xvar=xvar, common=common, f=f, P=P, loglik=ll)
+
+    def forecast_batch_host(self, panel, Lam, R, Avar, Q, mu0, P0, H: int, mean=None, sd=None, want_var: bool = True,
+                            want_common: bool = True, want_P: bool = True, may_have_missing: Optional[bool] = None,
+                            singular_q: bool = False):
+        """dfm_forecast_batch (host pointers; what Julia's ccall binds): NumPy in / out, same dict as forecast_batch."""
+        c = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+        panel, Lam, R, Avar, Q, mu0, P0 = map(c, (panel, Lam, R, Avar, Q, mu0, P0))
+        if (mean is None) != (sd is None):
+            raise ValueError("mean and sd go together")
+        mean = None if mean is None else c(mean)
+        sd = None if sd is None else c(sd)
+        B, T, N = panel.shape
+        r = Lam.shape[2]
+        p_lag = Avar.shape[2] // r
+        if int(H) < 0:
+            raise ValueError("H must be >= 0")
+        if may_have_missing is None:
+            may_have_missing = bool(np.isnan(panel).any())
+        flags = (_lib.DFM_F_MAY_HAVE_MISSING if may_have_missing else 0) | (_lib.DFM_F_SINGULAR_Q if singular_q else 0)
+        TH = T + int(H)
+        xhat = np.empty((B, TH, N))
+        xvar = np.empty((B, TH, N)) if want_var else None
+        common = np.empty((B, TH, N)) if want_common else None
+        f = np.empty((B, TH, r))
+        P = np.empty((B, TH, r * (r + 1) // 2)) if want_P else None
+        ll = np.empty(B)
+        p = lambda a: None if a is None else ctypes.c_void_p(a.ctypes.data)
+        rc = self._lib.dfm_forecast_batch(self._h, B, T, N, r, p_lag, int(H), p(panel), p(Lam), p(R), p(Avar), p(Q), p(mu0),
+                                          p(P0), p(mean), p(sd), p(xhat), p(xvar), p(common), p(f), p(P), p(ll), flags)
+        _check(self._h, rc)
+        return dict(xhat=xhat, xvar=xvar, common=common, f=f, P=P, loglik=ll)
+
     # ------------------------------------------------------------------ AR idiosyncratic terms (quasi-differencing)
     def ks_pass_ar_batch(self, panel, Lam, sig2, rho, Avar, Q, mu0, P0, want_P: bool = True,
                          may_have_missing: Optional[bool] = None, singular_q: bool = False):

@@ -240,6 +240,33 @@ int dfm_em_varp_batch(dfm_handle* h, int B, int T, int N, int r, int p, const do
                       double* R, double* Avar, double* Q, double* mu0, double* P0, int max_iter, double tol,
                       double* loglik_path, int* iters, double* f_smooth, double* P_smooth, unsigned flags);
 
+/* --- nowcasts and forecasts of the panel from a fitted model ------------------------------------------------------------
+ * The model of dfm_ks_pass_batch (p = 1) / dfm_ks_pass_varp_batch (p >= 1); every moment conditions on the replicate's observed
+ * cells X (T rows), output rows t = 0 .. T+H-1, rows T .. the forecast horizon (H >= 0; H = 0 is a pure nowcast):
+ *   f_out[b][t]  = E[f_t | X]   (t < T: the smoothed factors; t >= T: the forecast f_{t|T})               [B][T+H][r]
+ *   P_out[b][t]  = Var[f_t | X] packed lower (may be NULL)                                               [B][T+H][r(r+1)/2]
+ *   common[b][t][i] = mean_i + sd_i lam_i' f_out[t]                                   (may be NULL)      [B][T+H][N]
+ *   xhat[b][t][i]   = mean_i + sd_i x_ti on an observed cell (bit for bit x_ti when mean / sd are NULL); on a missing cell
+ *                     and for t >= T: mean_i + sd_i lam_i' f_out[t]                                      [B][T+H][N]
+ *   xvar[b][t][i]   = exactly 0 on an observed cell, else sd_i^2 (lam_i' P_out[t] lam_i + R_i)   (may be NULL)  [B][T+H][N]
+ *   loglik[b]       = log-likelihood of the observed cells, as the plain pass on the T-row panel    (may be NULL)
+ * Inputs: panel [B][T][N] (NaN = missing), Lam [B][N][r], R [B][N], Avar [B][r][r p] = [A_1 .. A_p], Q [B][r][r],
+ * mu0 [B][r p], P0 [B][r p][r p]; mean / sd [B][N] (both or neither; what dfm_standardize_batch_dev returns) put the outputs
+ * back into data units.  Flags as the pass (DFM_F_MAY_HAVE_MISSING, DFM_F_SINGULAR_Q: a NaN panel without the first gives
+ * DFM_E_MISSING); a shape the underlying pass refuses gives that pass's status; H < 0: DFM_E_DIMS.  Outputs must not overlap the
+ * inputs.  p = 1 runs the plain pass on the T-row panel and extends its terminal moments (f <- A f, P <- A P A' + Q); p > 1 writes
+ * the panel with H all-missing rows into xhat and runs the companion pass on it as a (T+H)-row panel with missing cells. */
+int dfm_forecast_batch_dev(dfm_handle* h, int B, int T, int N, int r, int p, int H, const double* panel,
+                           const double* Lam, const double* R, const double* Avar, const double* Q,
+                           const double* mu0, const double* P0, const double* mean, const double* sd,
+                           double* xhat, double* xvar, double* common, double* f_out, double* P_out,
+                           double* loglik, unsigned flags);
+int dfm_forecast_batch(dfm_handle* h, int B, int T, int N, int r, int p, int H, const double* panel,
+                       const double* Lam, const double* R, const double* Avar, const double* Q,
+                       const double* mu0, const double* P0, const double* mean, const double* sd,
+                       double* xhat, double* xvar, double* common, double* f_out, double* P_out,
+                       double* loglik, unsigned flags);
+
 /* --- AR idiosyncratic terms --------------------------------------------------------
  *   x_it = lam_i' f_t + e_it,   e_it = rho_i1 e_i,t-1 + .. + rho_iq e_i,t-q + eps_it,  eps_it ~ N(0, sig2_i)
  * with rho [B][N][q] / sig2 [B][N] in the role of the reference's uar_coef / uar_ser^2 (AR(n_uarlag) of the loading

@@ -310,6 +310,34 @@ function em_varp(h::Handle, z::Matrix{Float64}, p, nlag::Integer; max_iter::Inte
             factor = permutedims(f[:, :, 1]))
 end
 
+"Nowcasts and H-step forecasts of the panel (dfm_forecast_batch; include/dfm_hip.h): z is T x N (NaN = missing, standardised
+as in the fit), params the fitted model (Lam N x r, R, A or Avar r x (r nlag), Q, mu0, P0 as `em` / `em_varp` return them);
+mean / sd (length N, both or neither) put the outputs into data units.  Rows 1..T+H: x = observed cells as they are and
+E[x_ti | X] elsewhere, xvar (0 on observed cells), common, factor (T+H x r), P (packed lower per row), loglik."
+function forecast(h::Handle, z::Matrix{Float64}, params, H::Integer; nlag::Integer = 1, mean = nothing, sd = nothing,
+                  singular_q::Bool = false)
+    (mean === nothing) == (sd === nothing) || error("mean and sd go together")
+    T, N = size(z); r = size(params.Lam, 2); k = r * nlag; TH = T + H
+    Av = hasproperty(params, :Avar) ? params.Avar : params.A
+    panel = to_c_panel(z)
+    Lam = permutedims(params.Lam); R = copy(params.R); AC = permutedims(Av); QC = permutedims(params.Q)
+    mu0 = copy(params.mu0); P0C = permutedims(params.P0)
+    meanC = mean === nothing ? C_NULL : Vector{Float64}(mean); sdC = sd === nothing ? C_NULL : Vector{Float64}(sd)
+    xhat = Array{Float64}(undef, N, TH); xvar = Array{Float64}(undef, N, TH); common = Array{Float64}(undef, N, TH)
+    f = Array{Float64}(undef, r, TH); np = div(r * (r + 1), 2); P = Array{Float64}(undef, np, TH); ll = Array{Float64}(undef, 1)
+    flags = (any(isnan, z) ? DFM_F_MAY_HAVE_MISSING : Cuint(0)) | (singular_q ? DFM_F_SINGULAR_Q : Cuint(0))
+    GC.@preserve panel Lam R AC QC mu0 P0C meanC sdC xhat xvar common f P ll begin
+        rc = ccall((:dfm_forecast_batch, LIB), Cint,
+                   (Ptr{Cvoid}, Cint, Cint, Cint, Cint, Cint, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                    Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                    Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cuint),
+                   h.ptr, 1, T, N, r, nlag, H, panel, Lam, R, AC, QC, mu0, P0C, meanC, sdC, xhat, xvar, common, f, P, ll, flags)
+        check(h.ptr, rc)
+    end
+    return (x = permutedims(xhat), xvar = permutedims(xvar), common = permutedims(common), factor = permutedims(f),
+            P = permutedims(P), loglik = ll[1])
+end
+
 "Smoother pass with AR(q) idiosyncratic terms (dfm_ks_pass_ar_batch; include/dfm_hip.h): x is T x N (NaN = missing, in
 deviations from its intercept), Lam N x r, sig2 = uar_ser.^2, rho = uar_coef (N x q), Avar r x (r p), Q r x r, mu0 / P0
 the moments of z_q, r max(p, q+1) wide.  Returns the smoothed factors of rows q+1..T and the conditional log-likelihood."
