@@ -39,6 +39,7 @@ _EM_ARGS = [c_vp, c_int, c_int, c_int, c_int] + [c_vp] * 7 + [c_int, ctypes.c_do
 _VPASS_ARGS = [c_vp, c_int, c_int, c_int, c_int, c_int] + [c_vp] * 10 + [c_uint]
 _VEM_ARGS = [c_vp, c_int, c_int, c_int, c_int, c_int] + [c_vp] * 7 + [c_int, ctypes.c_double] + [c_vp] * 4 + [c_uint]
 _FC_ARGS = [c_vp, c_int, c_int, c_int, c_int, c_int, c_int] + [c_vp] * 15 + [c_uint]
+_SS_ARGS = [c_vp] + [c_int] * 7 + [c_vp] * 9 + [ctypes.c_uint64, ctypes.c_int64, c_vp, c_vp, c_uint]
 _ARPASS_ARGS = [c_vp, c_int, c_int, c_int, c_int, c_int, c_int] + [c_vp] * 11 + [c_uint]
 _AREM_ARGS = [c_vp, c_int, c_int, c_int, c_int, c_int, c_int] + [c_vp] * 8 + [c_int, ctypes.c_double] + [c_vp] * 4 + [c_uint]
 _OBSEM_ARGS = [c_vp, c_int, c_int, c_int, c_int, c_int] + [c_vp] * 8 + [c_int, ctypes.c_double] + [c_vp] * 4 + [c_uint]
@@ -89,6 +90,8 @@ SYMBOLS = {
     "dfm_em_varp_batch": (c_int, _VEM_ARGS),
     "dfm_forecast_batch_dev": (c_int, _FC_ARGS),
     "dfm_forecast_batch": (c_int, _FC_ARGS),
+    "dfm_simsmooth_batch_dev": (c_int, _SS_ARGS),
+    "dfm_simsmooth_batch": (c_int, _SS_ARGS),
     "dfm_ks_pass_ar_batch_dev": (c_int, _ARPASS_ARGS),
     "dfm_ks_pass_ar_batch": (c_int, _ARPASS_ARGS),
     "dfm_em_ar_batch_dev": (c_int, _AREM_ARGS),

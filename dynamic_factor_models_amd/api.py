@@ -494,6 +494,80 @@ def forecast(m: DFMModel, H: int, *, through: Optional[int] = None, quantiles=No
     return out
 
 
+def draw_paths(m: DFMModel, ndraws: int, H: int = 0, *, through: Optional[int] = None, seed: int = 20160415,
+               first_draw: int = 0, parameter_draws: bool = False, ctx=None) -> dict:
+    """Joint posterior draws of the factor path and of the panel's missing and future cells from the parametric fit
+    (`estimate(m, Parametric())`, nfac_o = 0): the counterpart of `forecast`, which gives the marginal moments only.
+
+    Same window, series, standardisation and ragged-edge `through` as `forecast`.  Each draw is an exact, independent draw of
+    (f_{initperiod..through+H}, the missing and future cells) given the observed cells, by the simulation smoother of Durbin and
+    Koopman (2002): one dfm_simsmooth_batch call on the GPU (include/dfm_hip.h: the random stream is a pure function of `seed`
+    and the draw's index first_draw + d, so draws [k, k + n) equal those of a call with first_draw = k).
+    Returns a dict:
+      rows        1-based periods initperiod .. through + H
+      cols        column indices (0-based) of m.data: the series estimate() used
+      factor      [ndraws, rows, r] factor paths (the model's standardised factor units)
+      x           [ndraws, rows, cols] data units: observed cells as they are, every other cell drawn
+    `parameter_draws=True` (needs m.replicates from estimate(..., nrep=...)): every bootstrap replicate's parameter set is one
+    replicate of the same call, so the draws carry parameter and shock uncertainty together: factor [nrep, ndraws, rows, r],
+    x [nrep, ndraws, rows, cols].  AR idiosyncratic terms and observed factors are refused.  `m` is not modified."""
+    ndraws, H, first_draw = int(ndraws), int(H), int(first_draw)
+    if ndraws < 1:
+        raise ValueError("ndraws must be >= 1")
+    if H < 0:
+        raise ValueError("H must be >= 0")
+    if first_draw < 0:
+        raise ValueError("first_draw must be >= 0")
+    if m.em_params is None:
+        raise ValueError("the model has not been estimated: run estimate(m, Parametric()) first")
+    if m.nfac_o != 0:
+        raise ValueError("draw_paths needs nfac_o = 0 (observed factors have no draws here)")
+    through = m.lastperiod if through is None else int(through)
+    if not (m.lastperiod <= through <= m.T):
+        raise ValueError(f"through must lie in lastperiod..T ({m.lastperiod}..{m.T})")
+    if parameter_draws and getattr(m, "replicates", None) is None:
+        raise ValueError("parameter draws need bootstrap replicates: estimate(m, Parametric(), nrep=...) first")
+    ep = m.em_params
+    Lam, R, Q = ep["Lam"], ep["R"], ep["Q"]
+    A = ep["Avar"] if "Avar" in ep else ep["A"]
+    mu0, P0 = ep["mu0"], ep["P0"]
+    cols, z, mu, sd = _forecast_inputs(m, through)
+    if Lam.shape[0] != cols.size:
+        raise ValueError("m.em_params does not match the model's series (was the model changed after estimate?)")
+    if np.any(np.nan_to_num(np.asarray(m.uar_coef, dtype=np.float64)[cols]) != 0.0):
+        raise ValueError("draw_paths has no AR idiosyncratic terms: the model carries uar_coef (estimate_ar_idio?)")
+    if z.shape[0] < A.shape[1] // Lam.shape[1]:
+        raise ValueError("the window is shorter than the number of factor lags")
+    from ._lib import DfmError
+    ctx, own = _own(ctx)
+    try:
+        def run(Lb, Rb, Ab, Qb, m0, P0b):
+            B = Lb.shape[0]
+            rep = lambda a: np.ascontiguousarray(np.broadcast_to(a, (B,) + a.shape))
+            args = (rep(z), Lb, Rb, Ab, Qb, m0, P0b, ndraws, H)
+            kw = dict(seed=int(seed), first_draw=first_draw, mean=rep(mu), sd=rep(sd), may_have_missing=bool(np.isnan(z).any()))
+            try:
+                return ctx.simsmooth_batch_host(*args, **kw)
+            except DfmError as err:                 # the information form inverts Q: as estimate(), retry in covariance form
+                if err.code != -5:
+                    raise
+                return ctx.simsmooth_batch_host(*args, singular_q=True, **kw)
+        if parameter_draws:
+            rp = m.replicates["params"]
+            o = run(rp["Lam"], rp["R"], rp["A"], rp["Q"], rp["mu0"], rp["P0"])
+            factor, x = o["f"], o["x"]
+        else:
+            o = run(Lam[None], R[None], A[None], Q[None], mu0[None], P0[None])
+            factor, x = o["f"][0], o["x"][0]
+    finally:
+        if own:
+            ctx.close()
+    xr = m.data[m.initperiod - 1:through, :][:, cols]                  # observed cells: the data itself, not mean + sd z
+    obs = ~np.isnan(xr)
+    x[..., :xr.shape[0], :][..., obs] = xr[obs]
+    return dict(rows=np.arange(m.initperiod, through + H + 1), cols=cols, factor=factor, x=x)
+
+
 # ============================================================================= the NON-parametric path
 # `estimate!(m, ::NonParametric)` (dfm_functions.ipynb:530-543) = estimate_factor! -> estimate_factor_loading!
 # -> estimate_var!, with every regression run by the batched HIP kernels of als.hip (dfm_als_batch /

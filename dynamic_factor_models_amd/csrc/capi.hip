@@ -73,6 +73,8 @@ struct dfm_handle {
     size_t odd_bytes = 0;
     void* fc = nullptr;                    // dfm_forecast_batch_dev: the pass's T-row moments, the forecast tail, P and loglik when the
     size_t fc_bytes = 0;                   // caller does not take them (beside h->ws: the pass itself may reallocate that)
+    void* ss = nullptr;                    // dfm_simsmooth_batch_dev: roots, the slice's pass parameters, smoothed means, logliks and
+    size_t ss_bytes = 0;                   // (no x_draw) difference panels -- beside h->ws for the same reason
     const double* odd_panel_src = nullptr; int odd_panel_dims[3] = {0, 0, 0};   // the panel whose padded copy h->odd holds (odd_pad keep_panel)
     std::string prof_file;                 // DFM_PF_PROF_FILE with DFM_SCAN_ABL=256: phase stamps of the fused pass
     char err[512] = {0};
@@ -84,11 +86,11 @@ struct dfm_handle {
 };
 
 enum KernelId { K_COLLAPSE = 0, K_RECURSION, K_MSTEP_STATS, K_MSTEP_SOLVE, K_PCA, K_SYNTH, K_PAD,
-                K_COLLAPSE_DMA, K_GRAM, K_COV, K_MEANSCAN, K_PFILL, K_COLLAPSE_MFMA, K_ALS, K_OLS, K_BOOT, K_QUANT, K_COLLAPSE_WIDE, K_EM_UPDATE, K_CHOW, K_MSTEP_MFMA, K_GRAM_XX, K_PASS_FUSED, K_FC_TAIL, K_FC_FILL, K_FC_PAD, K_COUNT };
+                K_COLLAPSE_DMA, K_GRAM, K_COV, K_MEANSCAN, K_PFILL, K_COLLAPSE_MFMA, K_ALS, K_OLS, K_BOOT, K_QUANT, K_COLLAPSE_WIDE, K_EM_UPDATE, K_CHOW, K_MSTEP_MFMA, K_GRAM_XX, K_PASS_FUSED, K_FC_TAIL, K_FC_FILL, K_FC_PAD, K_SS_PREP, K_SS_EXPAND, K_SS_PATH, K_SS_DIFF, K_SS_FINISH, K_SS_FILL, K_COUNT };
 static const char* const kKernelNames[K_COUNT] = {"collapse_kernel", "recursion_kernel", "mstep_lam_kernel",
                                                   "mstep_solve_kernel", "pca_kernel", "synth_kernel",
                                                   "pad_params_kernel", "collapse_dma_kernel", "gram_kernel",
-                                                  "cov_kernel", "meanscan_kernel", "pfill_kernel", "collapse_mfma_kernel", "als_kernel", "ols_kernel", "var_boot_kernel", "quantile_kernel", "collapse_wide_kernel", "em_update_kernel", "chow_kernel", "mstep_mfma_kernel", "gram_xx_kernel", "pass_fused_kernel", "forecast_tail_kernel", "forecast_fill_kernel", "forecast_pad_kernel"};
+                                                  "cov_kernel", "meanscan_kernel", "pfill_kernel", "collapse_mfma_kernel", "als_kernel", "ols_kernel", "var_boot_kernel", "quantile_kernel", "collapse_wide_kernel", "em_update_kernel", "chow_kernel", "mstep_mfma_kernel", "gram_xx_kernel", "pass_fused_kernel", "forecast_tail_kernel", "forecast_fill_kernel", "forecast_pad_kernel", "simsmooth_prep_kernel", "simsmooth_expand_kernel", "simsmooth_path_kernel", "simsmooth_diff_kernel", "simsmooth_finish_kernel", "simsmooth_fill_kernel"};
 
 namespace dfm { int handle_device(const dfm_handle* h) { return h->device; } }   // (probe.hip)
 
@@ -1450,6 +1452,7 @@ int dfm_destroy(dfm_handle* h) {
     if (h->ws) hipFree(h->ws);
     if (h->odd) hipFree(h->odd);
     if (h->fc) hipFree(h->fc);
+    if (h->ss) hipFree(h->ss);
     if (h->status_dev) hipFree(h->status_dev);
     if (h->own_stream && h->stream) hipStreamDestroy(h->stream);
     delete h;
@@ -2453,6 +2456,158 @@ int dfm_forecast_batch(dfm_handle* h, int B, int T, int N, int r, int p, int H, 
     }
     if (rc == 0) rc = post_check(h, ll_host.data(), B);
     if (rc == 0 && loglik) memcpy(loglik, ll_host.data(), (size_t)B * d);
+    (void)hipFree(buf);
+    return rc;
+}
+
+
+// ---- posterior draws of factor and panel paths: the simulation smoother (simsmooth.hip) --------------------------------------
+// Per slice of at most kSsSlice pass replicates j = b D + d: expand the parameters (mu0 = 0), simulate f+ into f_draw, stream the
+// difference panels, run the existing pass on them into h->ss, add its smoothed mean and draw the horizon, then (x_draw) the cells.
+// The difference panels of a slice live at the start of that slice's part of x_draw when the caller takes x_draw (the fill reads
+// only the panel and f_draw, and runs after the pass in stream order), else in h->ss.
+static constexpr int kSsSlice = 8192;
+
+static int ensure_ss(dfm_handle* h, size_t bytes) {
+    if (bytes <= h->ss_bytes) return 0;
+    if (h->ss) {
+        HIP_TRY(h, hipDeviceSynchronize());
+        HIP_TRY(h, hipFree(h->ss));
+        h->ss = nullptr;
+        h->ss_bytes = 0;
+    }
+    HIP_TRY(h, hipMalloc(&h->ss, bytes));
+    h->ss_bytes = bytes;
+    return 0;
+}
+
+static int simsmooth_check(dfm_handle* h, int B, int D, int T, int N, int r, int p, int H, const double* panel, const double* Lam,
+                           const double* R, const double* Avar, const double* Q, const double* mu0, const double* P0,
+                           const double* mean, const double* sd, const double* f_draw) {
+    if (int rc = check_dims(h, B, T, N, r)) return rc;
+    if (D < 1) return fail(h, DFM_E_DIMS, "D (draws per replicate) must be >= 1%s");
+    if (H < 0) return fail(h, DFM_E_DIMS, "H must be >= 0%s");
+    if (p < 1) return fail(h, DFM_E_DIMS, "number of factor lags must be >= 1%s");
+    if (r * p > DFM_MAX_R) return fail(h, DFM_E_R_UNSUPPORTED, "r * p > DFM_MAX_R (32)%s");
+    if (T < p) return fail(h, DFM_E_DIMS, "T must be >= p (the horizon starts from the last p rows of the draw)%s");
+    if ((long long)B * D > 0x7fffffffLL) return fail(h, DFM_E_DIMS, "B * D must be < 2^31%s");
+    if (!panel || !Lam || !R || !Avar || !Q || !mu0 || !P0 || !f_draw) return fail(h, DFM_E_NULL, "required pointer is NULL%s");
+    if ((mean == nullptr) != (sd == nullptr)) return fail(h, DFM_E_NULL, "mean and sd must both be given or both be NULL%s");
+    return 0;
+}
+
+// ll_all: [B D] device log-likelihoods of the difference panels (the host entry checks them), or null (h->ss, per slice)
+static int simsmooth_run(dfm_handle* h, int B, int D, int T, int N, int r, int p, int H, const double* panel, const double* Lam,
+                         const double* R, const double* Avar, const double* Q, const double* mu0, const double* P0,
+                         const double* mean, const double* sd, uint64_t seed, int64_t first_draw, double* f_draw,
+                         double* x_draw, double* ll_all, unsigned flags) {
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t d = sizeof(double), k = (size_t)r * p, TH = (size_t)T + H;
+    const long long BD = (long long)B * D;
+    const int Smax = (int)(BD < kSsSlice ? BD : kSsSlice);
+    size_t off = 0;
+    const size_t o_LP0 = take(off, (size_t)B * k * k * d), o_LQ = take(off, (size_t)B * r * r * d),
+                 o_L = take(off, (size_t)Smax * N * r * d), o_R = take(off, (size_t)Smax * N * d),
+                 o_A = take(off, (size_t)Smax * r * k * d), o_Q = take(off, (size_t)Smax * r * r * d),
+                 o_m = take(off, (size_t)Smax * k * d), o_P = take(off, (size_t)Smax * k * k * d),
+                 o_g = take(off, (size_t)Smax * T * r * d), o_ll = ll_all ? (size_t)-1 : take(off, (size_t)Smax * d),
+                 o_x = x_draw ? (size_t)-1 : take(off, (size_t)Smax * T * N * d);
+    if (int rc = ensure_ss(h, off)) return rc;
+    char* base = static_cast<char*>(h->ss);
+    auto ptr = [&](size_t o) { return o == (size_t)-1 ? nullptr : reinterpret_cast<double*>(base + o); };
+    SsArgs a{};
+    a.B = B; a.D = D; a.T = T; a.N = N; a.r = r; a.p = p; a.H = H;
+    a.panel = panel; a.Lam = Lam; a.R = R; a.A = Avar; a.Q = Q; a.mu0 = mu0; a.P0 = P0; a.mean = mean; a.sd = sd;
+    a.seed = seed; a.first_draw = first_draw; a.f_draw = f_draw; a.x_draw = x_draw;
+    a.LP0 = ptr(o_LP0); a.LQ = ptr(o_LQ);
+    a.eLam = ptr(o_L); a.eR = ptr(o_R); a.eA = ptr(o_A); a.eQ = ptr(o_Q); a.emu0 = ptr(o_m); a.eP0 = ptr(o_P); a.g = ptr(o_g);
+    {
+        ProfScope ps(h, K_SS_PREP);
+        HIP_TRY(h, launch_simsmooth_prep(a, h->stream));
+    }
+    for (long long j0 = 0; j0 < BD; j0 += Smax) {
+        const int S = (int)(BD - j0 < Smax ? BD - j0 : Smax);
+        a.j0 = j0; a.S = S;
+        a.diff = x_draw ? x_draw + (size_t)j0 * TH * N : ptr(o_x);
+        double* ll = ll_all ? ll_all + j0 : ptr(o_ll);
+        {
+            ProfScope ps(h, K_SS_EXPAND);
+            HIP_TRY(h, launch_simsmooth_expand(a, h->stream));
+        }
+        {
+            ProfScope ps(h, K_SS_PATH);
+            HIP_TRY(h, launch_simsmooth_path(a, h->stream));
+        }
+        {
+            ProfScope ps(h, K_SS_DIFF);
+            HIP_TRY(h, launch_simsmooth_diff(a, h->stream));
+        }
+        double* g = ptr(o_g);
+        if (p == 1) {
+            if (int rc = dfm_ks_pass_batch_dev(h, S, T, N, r, a.diff, a.eLam, a.eR, a.eA, a.eQ, a.emu0, a.eP0, g, nullptr, ll, flags))
+                return rc;
+        } else {
+            if (int rc = dfm_ks_pass_varp_batch_dev(h, S, T, N, r, p, a.diff, a.eLam, a.eR, a.eA, a.eQ, a.emu0, a.eP0, g, nullptr, ll,
+                                                    flags)) return rc;
+        }
+        {
+            ProfScope ps(h, K_SS_FINISH);
+            HIP_TRY(h, launch_simsmooth_finish(a, h->stream));
+        }
+        if (x_draw) {
+            ProfScope ps(h, K_SS_FILL);
+            HIP_TRY(h, launch_simsmooth_fill(a, h->stream));
+        }
+    }
+    return 0;
+}
+
+int dfm_simsmooth_batch_dev(dfm_handle* h, int B, int D, int T, int N, int r, int p, int H, const double* panel,
+                            const double* Lam, const double* R, const double* Avar, const double* Q, const double* mu0,
+                            const double* P0, const double* mean, const double* sd, uint64_t seed, int64_t first_draw,
+                            double* f_draw, double* x_draw, unsigned flags) {
+    if (int rc = simsmooth_check(h, B, D, T, N, r, p, H, panel, Lam, R, Avar, Q, mu0, P0, mean, sd, f_draw)) return rc;
+    return simsmooth_run(h, B, D, T, N, r, p, H, panel, Lam, R, Avar, Q, mu0, P0, mean, sd, seed, first_draw, f_draw, x_draw,
+                         nullptr, flags);
+}
+
+int dfm_simsmooth_batch(dfm_handle* h, int B, int D, int T, int N, int r, int p, int H, const double* panel, const double* Lam,
+                        const double* R, const double* Avar, const double* Q, const double* mu0, const double* P0,
+                        const double* mean, const double* sd, uint64_t seed, int64_t first_draw, double* f_draw,
+                        double* x_draw, unsigned flags) {
+    if (int rc = simsmooth_check(h, B, D, T, N, r, p, H, panel, Lam, R, Avar, Q, mu0, P0, mean, sd, f_draw)) return rc;
+    if (int rc = status_epoch(h)) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t d = sizeof(double), k = (size_t)r * p, TH = (size_t)T + H, BD = (size_t)B * D;
+    const size_t n_panel = (size_t)B * T * N, n_lam = (size_t)B * N * r, n_R = (size_t)B * N, n_a = (size_t)B * r * k,
+                 n_q = (size_t)B * r * r, n_v = (size_t)B * k, n_p0 = (size_t)B * k * k, n_f = BD * TH * r,
+                 n_x = x_draw ? BD * TH * N : 0;
+    const size_t total = n_panel + n_lam + n_R + n_a + n_q + n_v + n_p0 + (mean ? 2 * n_R : 0) + n_f + n_x + BD + 16 * 32;
+    double* buf = nullptr;
+    HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&buf), total * d));
+    double* dp = buf;
+    auto take_d = [&](size_t n) { double* dst = dp; dp += (n + 31) & ~(size_t)31; return dst; };
+    auto up = [&](const double* src, size_t n) -> double* {
+        double* dst = take_d(n);
+        (void)hipMemcpyAsync(dst, src, n * d, hipMemcpyHostToDevice, h->stream);
+        return dst;
+    };
+    double *x_d = up(panel, n_panel), *lam_d = up(Lam, n_lam), *R_d = up(R, n_R), *A_d = up(Avar, n_a), *Q_d = up(Q, n_q),
+           *mu_d = up(mu0, n_v), *P0_d = up(P0, n_p0);
+    double *mean_d = mean ? up(mean, n_R) : nullptr, *sd_d = sd ? up(sd, n_R) : nullptr;
+    double *f_d = take_d(n_f), *xo_d = x_draw ? take_d(n_x) : nullptr, *ll_d = take_d(BD);
+    int rc = simsmooth_run(h, B, D, T, N, r, p, H, x_d, lam_d, R_d, A_d, Q_d, mu_d, P0_d, mean_d, sd_d, seed, first_draw, f_d,
+                           xo_d, ll_d, flags);
+    std::vector<double> ll_host(BD);
+    if (rc == 0) {
+        auto down = [&](void* dst, const void* src, size_t n) { (void)hipMemcpyAsync(dst, src, n * d, hipMemcpyDeviceToHost, h->stream); };
+        down(f_draw, f_d, n_f);
+        if (x_draw) down(x_draw, xo_d, n_x);
+        down(ll_host.data(), ll_d, BD);
+        hipError_t e = hipStreamSynchronize(h->stream);
+        if (e != hipSuccess) rc = hip_fail(h, e, "hipStreamSynchronize");
+    }
+    if (rc == 0) rc = post_check(h, ll_host.data(), (int)BD);
     (void)hipFree(buf);
     return rc;
 }

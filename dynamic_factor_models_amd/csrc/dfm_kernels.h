@@ -465,6 +465,32 @@ hipError_t launch_forecast_fill(const FcFillArgs& a, hipStream_t s);
 hipError_t launch_forecast_pad(int B, int T, int H, int N, const double* panel, double* out, bool check_nan, int* status,
                                hipStream_t s);
 
+// Posterior draws of factor and panel paths, Durbin-Koopman simulation smoother (simsmooth.hip).  Pass replicate j = b D + d;
+// a call runs its B D pass replicates in slices j0 .. j0 + S - 1.
+struct SsArgs {
+    int B, D, T, N, r, p, H;
+    const double* panel;                          // [B][T][N] (NaN = missing)
+    const double* Lam; const double* R;           // [B][N][r], [B][N]
+    const double* A; const double* Q;             // [B][r][r p] = [A_1 .. A_p], [B][r][r]
+    const double* mu0; const double* P0;          // [B][r p], [B][r p][r p]
+    const double* mean; const double* sd;         // [B][N] or both null
+    uint64_t seed; int64_t first_draw;
+    double* f_draw;                               // [B][D][T+H][r]
+    double* x_draw;                               // [B][D][T+H][N] or null
+    double* LP0; double* LQ;                      // [B][r p][r p], [B][r][r]: lower PSD roots (simsmooth_prep_kernel)
+    long long j0; int S;                          // the slice
+    double* diff;                                 // [S][T][N] difference panels of the slice
+    double *eLam, *eR, *eA, *eQ, *emu0, *eP0;     // [S][..] the pass's parameters (mu0 = 0)
+    const double* g;                              // [S][T][r] smoothed mean of the difference panels
+    int NPB, G, RC, nchunk, nsblk;                // geometry of the cell kernels (set by their launchers)
+};
+hipError_t launch_simsmooth_prep(const SsArgs& a, hipStream_t s);
+hipError_t launch_simsmooth_expand(const SsArgs& a, hipStream_t s);
+hipError_t launch_simsmooth_path(const SsArgs& a, hipStream_t s);
+hipError_t launch_simsmooth_diff(SsArgs a, hipStream_t s);
+hipError_t launch_simsmooth_finish(const SsArgs& a, hipStream_t s);
+hipError_t launch_simsmooth_fill(SsArgs a, hipStream_t s);
+
 // Device-side synthetic replicates (synth.hip); all arrays in the caller's layout (r).
 struct SynthArgs {
     int B, T, N, r;

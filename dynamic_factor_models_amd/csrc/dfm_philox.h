@@ -1,5 +1,5 @@
 // dfm_philox.h -- Philox4x32-10 counter-based generator (Salmon et al. 2011): every number is a pure function
-// of (key, counter), so results do not depend on the launch geometry.  Shared by synth.hip and boot.hip.
+// of (key, counter), so results do not depend on the launch geometry.  Shared by synth.hip, boot.hip and simsmooth.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -26,5 +26,21 @@ struct Philox {
         for (int i = 0; i < 4; ++i) out[i] = c[i];
     }
 };
+
+// uniform in (0,1) with 53 random bits
+__device__ __forceinline__ double u01(uint32_t a, uint32_t b) {
+    const uint64_t x = ((uint64_t)a << 32) | b;
+    return ((double)(x >> 11) + 0.5) * (1.0 / 9007199254740992.0);
+}
+// two independent N(0,1) per counter (Box-Muller on two 53-bit uniforms)
+__device__ __forceinline__ void normal2(uint64_t key, uint64_t stream, uint64_t idx, double& z0, double& z1) {
+    uint32_t o[4];
+    Philox::block(key, idx, stream, o);
+    const double u = u01(o[0], o[1]), v = u01(o[2], o[3]);
+    const double rad = sqrt(-2.0 * log(u));
+    double sn, cs;
+    sincospi(2.0 * v, &sn, &cs);
+    z0 = rad * cs; z1 = rad * sn;
+}
 
 }  // namespace dfm

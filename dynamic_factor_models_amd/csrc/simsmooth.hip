@@ -1,0 +1,364 @@
+// simsmooth.hip -- posterior draws of factor and panel paths (dfm_simsmooth_batch, capi.hip): the simulation smoother of Durbin
+// and Koopman (2002).  For pass replicate j = b D + d (replicate b of the call, draw d):
+//   1. z+_0 = mu0 + L_P0 n,  f+_t = A_1 f+_{t-1} + .. + A_p f+_{t-p} + L_Q eta_t,  x+_ti = lam_i' f+_t + sqrt(R_i) eps+_ti
+//      (simsmooth_path_kernel writes f+ into rows 0..T-1 of f_draw; the cells are never stored)
+//   2. D_ti = X_ti - x+_ti on observed cells, NaN elsewhere                              (simsmooth_diff_kernel)
+//   3. g = E[f | D] with mu0 = 0: the existing pass on the difference panels                        (capi.hip)
+//   4. f_t = f+_t + g_t for t < T, then H steps of the companion recursion with fresh eta          (simsmooth_finish_kernel)
+//   5. x_ti = mean_i + sd_i X_ti on observed cells, mean_i + sd_i (lam_i' f_t + sqrt(R_i) eps_ti) elsewhere (simsmooth_fill_kernel)
+// Every normal is component c mod 2 of normal2(key, 16 b + s, idx) with key = seed ^ (0x9E3779B97F4A7C15 (first_draw + d + 1)):
+//   s = 1 z+_0 (idx c/2), 2 eta of row t (t ceil(r/2) + k/2), 3 eps+ (t ceil(N/2) + i/2), 4 eps (t ceil(N/2) + i/2)
+// (include/dfm_hip.h).  An index depends on neither the missing cells nor the launch geometry.
+//
+// The two cell kernels stream B D (T [+ H]) N cells: one workgroup owns a pass replicate's chunk of rows and a block of column
+// pairs, stages the chunk's f rows in LDS, keeps its two rows of loadings in registers, draws one Philox counter per pair of
+// cells and moves 16 bytes per lane where N is even.  blockIdx.x is the pass replicate: the D draws of a replicate run next to
+// each other, so the panel chunk every one of them reads comes from L2 / the Infinity Cache and HBM sees the writes.
+#include <utility>
+
+#include "dfm_kernels.h"
+#include "dfm_philox.h"
+
+namespace dfm {
+
+constexpr int kSsTC = 32;                     // rows per chunk of the companion recursion (normals and L_Q eta staged in LDS)
+constexpr int kSsMaxThreads = 512;            // cell kernels
+constexpr size_t kSsLds = 32 * 1024;          // cell kernels: f rows staged per workgroup
+constexpr double kSsPsdTol = 1e-12;           // PSD root: a pivot <= this x trace zeroes its column
+enum : uint64_t { kSsZ0 = 1, kSsEta = 2, kSsEpsPlus = 3, kSsEps = 4 };
+
+__device__ __forceinline__ uint64_t ss_key(uint64_t seed, int64_t first_draw, int d) {
+    return seed ^ (0x9E3779B97F4A7C15ull * (uint64_t)(first_draw + d + 1));
+}
+
+// Lower root L L' = M (n <= 32, lower triangle of M read) by Cholesky; a column whose pivot is <= kSsPsdTol trace(M) is zero, so a
+// positive semi-definite M has a root too.  L: LDS [n][n]; every thread of the workgroup takes part.
+__device__ void ss_psd_root(const double* M, int n, double* L) {
+    const int tid = threadIdx.x;
+    double tr = 0.0;
+    for (int i = 0; i < n; ++i) tr += M[i * n + i];
+    const double tol = kSsPsdTol * tr;
+    for (int e = tid; e < n * n; e += blockDim.x) L[e] = 0.0;
+    __syncthreads();
+    for (int j = 0; j < n; ++j) {
+        double dj = M[j * n + j];
+        for (int m = 0; m < j; ++m) dj -= L[j * n + m] * L[j * n + m];
+        const bool keep = dj > tol;
+        const double ljj = keep ? sqrt(dj) : 0.0;
+        for (int i = j + tid; i < n; i += blockDim.x) {
+            if (i == j) {
+                L[j * n + j] = ljj;
+            } else {
+                double v = M[i * n + j];
+                for (int m = 0; m < j; ++m) v -= L[i * n + m] * L[j * n + m];
+                L[i * n + j] = keep ? v / ljj : 0.0;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// One workgroup per replicate b: the roots of P0 and Q, once for all D draws.
+__global__ __launch_bounds__(64) void simsmooth_prep_kernel(SsArgs a) {
+    __shared__ double L[32 * 32];
+    const size_t b = blockIdx.x;
+    const int r = a.r, k = a.r * a.p;
+    ss_psd_root(a.P0 + b * k * k, k, L);
+    for (int e = threadIdx.x; e < k * k; e += blockDim.x) a.LP0[b * k * k + e] = L[e];
+    __syncthreads();
+    ss_psd_root(a.Q + b * r * r, r, L);
+    for (int e = threadIdx.x; e < r * r; e += blockDim.x) a.LQ[b * r * r + e] = L[e];
+}
+
+// The slice's pass parameters: replicate b's Lam, R, A, Q, P0 for each of its draws, mu0 = 0.  blockIdx.y = pass replicate.
+__global__ __launch_bounds__(256) void simsmooth_expand_kernel(SsArgs a) {
+    const int s = blockIdx.y;
+    const size_t b = (size_t)((a.j0 + s) / a.D);
+    const size_t N = a.N, r = a.r, k = (size_t)a.r * a.p;
+    const size_t nL = N * r, nR = N, nA = r * k, nQ = r * r, nm = k, nP = k * k;
+    size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e < nL) { a.eLam[s * nL + e] = a.Lam[b * nL + e]; return; }
+    e -= nL;
+    if (e < nR) { a.eR[s * nR + e] = a.R[b * nR + e]; return; }
+    e -= nR;
+    if (e < nA) { a.eA[s * nA + e] = a.A[b * nA + e]; return; }
+    e -= nA;
+    if (e < nQ) { a.eQ[s * nQ + e] = a.Q[b * nQ + e]; return; }
+    e -= nQ;
+    if (e < nm) { a.emu0[s * nm + e] = 0.0; return; }
+    e -= nm;
+    if (e < nP) a.eP0[s * nP + e] = a.P0[b * nP + e];
+}
+
+// The companion recursion f_t = A_1 f_{t-1} + .. + A_p f_{t-p} + L_Q eta_t over output rows t0 .. t1-1 of one pass replicate, one
+// wave.  zs[0][0 .. k) holds (row t0-1, .., row t0-p) on entry (zs: two LDS buffers of 32, used in turn: one barrier per row).
+// arow: lane c < r holds row c of [A_1 .. A_p].  Rows go to f ([rows][r]), a chunk at a time: they are staged in seta (dead once
+// L_Q eta is formed), because the barrier of every row would otherwise wait for that row's global store to complete.
+__device__ __forceinline__ void ss_recursion(const SsArgs& a, uint64_t key, uint64_t stream, int t0, int t1, const double* sLQ,
+                                             double* seta, double* sw, double (*zs)[32], const double (&arow)[32], double* f) {
+    const int r = a.r, k = a.r * a.p, hr = (a.r + 1) / 2, tid = threadIdx.x;
+    int cur = 0;
+    for (int c0 = t0; c0 < t1; c0 += kSsTC) {
+        const int nt = t1 - c0 < kSsTC ? t1 - c0 : kSsTC;
+        for (int e = tid; e < nt * hr; e += blockDim.x) {
+            const int tt = e / hr, q = e % hr;
+            double z0, z1;
+            normal2(key, stream, (uint64_t)(c0 + tt) * hr + q, z0, z1);
+            seta[tt * 32 + 2 * q] = z0;
+            if (2 * q + 1 < r) seta[tt * 32 + 2 * q + 1] = z1;
+        }
+        __syncthreads();
+        for (int e = tid; e < nt * r; e += blockDim.x) {
+            const int tt = e / r, c = e % r;
+            double v = 0.0;
+            for (int m = 0; m <= c; ++m) v = fma(sLQ[c * r + m], seta[tt * 32 + m], v);
+            sw[tt * 32 + c] = v;
+        }
+        __syncthreads();
+        for (int tt = 0; tt < nt; ++tt) {
+            const double* zin = zs[cur];
+            double v = 0.0;
+            if (tid < r) {
+                v = sw[tt * 32 + tid];
+#pragma unroll
+                for (int m = 0; m < 32; ++m)
+                    if (m < k) v = fma(arow[m], zin[m], v);
+                seta[tt * 32 + tid] = v;
+            } else if (tid < k) {
+                v = zin[tid - r];
+            }
+            if (tid < k) zs[cur ^ 1][tid] = v;
+            cur ^= 1;
+            __syncthreads();
+        }
+        for (int e = tid; e < nt * r; e += blockDim.x) f[(size_t)c0 * r + e] = seta[(e / r) * 32 + e % r];
+        __syncthreads();
+    }
+    // (the caller reads nothing of zs afterwards)
+}
+
+__device__ __forceinline__ void ss_load_arow(const SsArgs& a, size_t b, double (&arow)[32]) {
+    const int r = a.r, k = a.r * a.p, tid = threadIdx.x;
+#pragma unroll
+    for (int m = 0; m < 32; ++m) arow[m] = (tid < r && m < k) ? a.A[(b * r + tid) * k + m] : 0.0;
+}
+
+// Step 1 for rows 0..T-1: z+_0 from stream 1, then the recursion with eta from stream 2.  One wave per pass replicate of the slice.
+__global__ __launch_bounds__(64) void simsmooth_path_kernel(SsArgs a) {
+    __shared__ double sLQ[32 * 32], seta[kSsTC * 32], sw[kSsTC * 32], zs[2][32];
+    const long long j = a.j0 + blockIdx.x;
+    const size_t b = (size_t)(j / a.D);
+    const int d = (int)(j % a.D), r = a.r, k = a.r * a.p, tid = threadIdx.x;
+    const uint64_t key = ss_key(a.seed, a.first_draw, d);
+    for (int e = tid; e < r * r; e += blockDim.x) sLQ[e] = a.LQ[b * r * r + e];
+    if (tid < k) {
+        double z0, z1;
+        normal2(key, 16 * b + kSsZ0, (uint64_t)(tid / 2), z0, z1);
+        seta[tid] = (tid & 1) ? z1 : z0;
+    }
+    __syncthreads();
+    if (tid < k) {
+        double v = a.mu0[b * k + tid];
+        for (int m = 0; m <= tid; ++m) v = fma(a.LP0[(b * k + tid) * k + m], seta[m], v);
+        zs[0][tid] = v;
+    }
+    double arow[32];
+    ss_load_arow(a, b, arow);
+    __syncthreads();
+    ss_recursion(a, key, 16 * b + kSsEta, 0, a.T, sLQ, seta, sw, zs, arow, a.f_draw + (size_t)j * (a.T + a.H) * r);
+}
+
+// Step 4: f = f+ + g on rows 0..T-1, then rows T..T+H-1 by the recursion (eta of those rows from stream 2).
+__global__ __launch_bounds__(64) void simsmooth_finish_kernel(SsArgs a) {
+    __shared__ double sLQ[32 * 32], seta[kSsTC * 32], sw[kSsTC * 32], zs[2][32];
+    const int s = blockIdx.x;
+    const long long j = a.j0 + s;
+    const size_t b = (size_t)(j / a.D);
+    const int d = (int)(j % a.D), r = a.r, k = a.r * a.p, T = a.T, tid = threadIdx.x;
+    double* F = a.f_draw + (size_t)j * (T + a.H) * r;
+    const double* G = a.g + (size_t)s * T * r;
+    double z = 0.0;
+    if (tid < k && a.H > 0) {                                // companion state (row T-1, .., row T-p) of the draw (T >= p)
+        const size_t e = (size_t)(T - 1 - tid / r) * r + tid % r;
+        z = F[e] + G[e];
+    }
+    __syncthreads();
+    for (int e = tid; e < T * r; e += blockDim.x) F[e] = F[e] + G[e];
+    if (a.H == 0) return;
+    for (int e = tid; e < r * r; e += blockDim.x) sLQ[e] = a.LQ[b * r * r + e];
+    if (tid < k) zs[0][tid] = z;
+    double arow[32];
+    ss_load_arow(a, b, arow);
+    __syncthreads();
+    ss_recursion(a, ss_key(a.seed, a.first_draw, d), 16 * b + kSsEta, T, T + a.H, sLQ, seta, sw, zs, arow, F);
+}
+
+// The cell kernels.  FILL = false: D_ti of rows 0..T-1 into the slice's difference panels; FILL = true: x_draw rows 0..T+H-1.
+// RB >= r: loadings in registers; VEC: N even and 16-byte aligned pointers (double2 loads / stores).
+template <int RB, bool VEC, bool FILL>
+__device__ __forceinline__ void ss_cells(const SsArgs& a) {
+    extern __shared__ __attribute__((aligned(16))) double sfr[];
+    const int r = a.r, N = a.N, T = a.T, TH = a.T + a.H, tid = threadIdx.x;
+    const int rows = FILL ? TH : T;
+    const int s = blockIdx.x, c = blockIdx.y, sb = blockIdx.z;
+    const long long j = a.j0 + s;
+    const size_t b = (size_t)(j / a.D);
+    const int d = (int)(j % a.D);
+    const int t0 = c * a.RC, t1 = t0 + a.RC < rows ? t0 + a.RC : rows;
+    const double* F = a.f_draw + (size_t)j * TH * r;
+    for (int e = tid; e < (t1 - t0) * r; e += blockDim.x) sfr[e] = F[(size_t)t0 * r + e];
+    __syncthreads();
+    const int jj = tid % a.NPB, gr = tid / a.NPB;
+    if (gr >= a.G) return;
+    const int i0 = 2 * (sb * a.NPB + jj);
+    if (i0 >= N) return;
+    const bool two = i0 + 1 < N;                             // (VEC: N even, always)
+    double l0[RB], l1[RB];
+#pragma unroll
+    for (int q = 0; q < RB; ++q) {
+        l0[q] = q < r ? a.Lam[(b * N + i0) * r + q] : 0.0;
+        l1[q] = (q < r && two) ? a.Lam[(b * N + i0 + 1) * r + q] : 0.0;
+    }
+    const double sr0 = sqrt(a.R[b * N + i0]), sr1 = two ? sqrt(a.R[b * N + i0 + 1]) : 0.0;
+    const bool scale = FILL && a.mean != nullptr;
+    const double mu0 = scale ? a.mean[b * N + i0] : 0.0, mu1 = (scale && two) ? a.mean[b * N + i0 + 1] : 0.0;
+    const double sd0 = scale ? a.sd[b * N + i0] : 1.0, sd1 = (scale && two) ? a.sd[b * N + i0 + 1] : 1.0;
+    const uint64_t key = ss_key(a.seed, a.first_draw, d), stream = 16 * b + (FILL ? kSsEps : kSsEpsPlus);
+    const uint64_t hN = (uint64_t)(N + 1) / 2;
+    const double qnan = __longlong_as_double(0x7FF8000000000000ll);
+    auto load = [&](int t, double& x0, double& x1) {
+        x0 = qnan; x1 = qnan;
+        if (t < T && t < t1) {
+            const double* px = a.panel + (b * T + t) * N + i0;
+            if constexpr (VEC) {
+                const double2 v = *reinterpret_cast<const double2*>(px);
+                x0 = v.x; x1 = v.y;
+            } else {
+                x0 = px[0];
+                if (two) x1 = px[1];
+            }
+        }
+    };
+    double nx0, nx1;                                          // the next row's cells, in flight while this row is computed
+    load(t0 + gr, nx0, nx1);
+    for (int t = t0 + gr; t < t1; t += a.G) {
+        const double* f = sfr + (size_t)(t - t0) * r;
+        const double x0 = nx0, x1 = nx1;
+        load(t + a.G, nx0, nx1);
+        double m0 = 0.0, m1 = 0.0;
+#pragma unroll
+        for (int q = 0; q < RB; ++q)
+            if (q < r) {
+                const double fq = f[q];
+                m0 = fma(l0[q], fq, m0);
+                m1 = fma(l1[q], fq, m1);
+            }
+        const bool o0 = x0 == x0, o1 = x1 == x1;
+        double y0, y1;
+        if constexpr (!FILL) {
+            double e0 = 0.0, e1 = 0.0;
+            if (o0 || o1) normal2(key, stream, (uint64_t)t * hN + (uint64_t)(i0 / 2), e0, e1);
+            y0 = o0 ? x0 - (m0 + sr0 * e0) : x0;
+            y1 = o1 ? x1 - (m1 + sr1 * e1) : x1;
+        } else {
+            double e0 = 0.0, e1 = 0.0;
+            if (!o0 || (two && !o1)) normal2(key, stream, (uint64_t)t * hN + (uint64_t)(i0 / 2), e0, e1);
+            const double v0 = o0 ? x0 : m0 + sr0 * e0, v1 = o1 ? x1 : m1 + sr1 * e1;
+            y0 = scale ? mu0 + sd0 * v0 : v0;
+            y1 = scale ? mu1 + sd1 * v1 : v1;
+        }
+        double* out = FILL ? a.x_draw + ((size_t)j * TH + t) * N + i0 : a.diff + ((size_t)s * T + t) * N + i0;
+        if constexpr (VEC) {
+            *reinterpret_cast<double2*>(out) = double2{y0, y1};
+        } else {
+            out[0] = y0;
+            if (two) out[1] = y1;
+        }
+    }
+}
+
+template <int RB, bool VEC>
+__global__ __launch_bounds__(kSsMaxThreads) void simsmooth_diff_kernel(SsArgs a) { ss_cells<RB, VEC, false>(a); }
+template <int RB, bool VEC>
+__global__ __launch_bounds__(kSsMaxThreads) void simsmooth_fill_kernel(SsArgs a) { ss_cells<RB, VEC, true>(a); }
+
+hipError_t launch_simsmooth_prep(const SsArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(simsmooth_prep_kernel, dim3((unsigned)a.B), dim3(64), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_simsmooth_expand(const SsArgs& a, hipStream_t s) {
+    const size_t k = (size_t)a.r * a.p;
+    const size_t per = (size_t)a.N * a.r + a.N + a.r * k + (size_t)a.r * a.r + k + k * k;
+    hipLaunchKernelGGL(simsmooth_expand_kernel, dim3((unsigned)((per + 255) / 256), (unsigned)a.S), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_simsmooth_path(const SsArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(simsmooth_path_kernel, dim3((unsigned)a.S), dim3(64), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_simsmooth_finish(const SsArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(simsmooth_finish_kernel, dim3((unsigned)a.S), dim3(64), 0, s, a);
+    return hipGetLastError();
+}
+
+// Column pairs per workgroup (NPB), rows per pass over them (G) and per workgroup (RC): G x NPB lanes rounded up to whole waves,
+// G chosen so that the fewest lanes idle (N = 200: 5 x 100 of 512).
+static int ss_geometry(SsArgs& a, int rows, int& threads) {
+    const int npair = (a.N + 1) / 2;
+    a.nsblk = (npair + 255) / 256;
+    a.NPB = (npair + a.nsblk - 1) / a.nsblk;
+    int bestG = 1;
+    double best = -1.0;
+    for (int G = 1; G * a.NPB <= kSsMaxThreads; ++G) {
+        const int th = (G * a.NPB + 63) / 64 * 64;
+        if (th > kSsMaxThreads) break;
+        const double eff = (double)(G * a.NPB) / th;
+        if (eff > best + 1e-9) { best = eff; bestG = G; }
+    }
+    a.G = bestG;
+    threads = (a.G * a.NPB + 63) / 64 * 64;
+    int rc = a.G * 8;
+    const int cap = (int)(kSsLds / ((size_t)a.r * sizeof(double)));
+    if (rc > cap) rc = cap;
+    if (rc > rows) rc = rows;
+    if (rc < 1) rc = 1;
+    a.RC = rc;
+    a.nchunk = (rows + rc - 1) / rc;
+    return a.nchunk <= 65535 && a.nsblk <= 65535 ? 0 : -1;
+}
+
+template <bool FILL, int RB>
+static hipError_t launch_cells_rb(const SsArgs& a, int threads, bool vec, hipStream_t s) {
+    const dim3 grid((unsigned)a.S, (unsigned)a.nchunk, (unsigned)a.nsblk);
+    const size_t lds = (size_t)a.RC * a.r * sizeof(double);
+    if (vec) {
+        if constexpr (FILL) hipLaunchKernelGGL((simsmooth_fill_kernel<RB, true>), grid, dim3(threads), lds, s, a);
+        else hipLaunchKernelGGL((simsmooth_diff_kernel<RB, true>), grid, dim3(threads), lds, s, a);
+    } else {
+        if constexpr (FILL) hipLaunchKernelGGL((simsmooth_fill_kernel<RB, false>), grid, dim3(threads), lds, s, a);
+        else hipLaunchKernelGGL((simsmooth_diff_kernel<RB, false>), grid, dim3(threads), lds, s, a);
+    }
+    return hipGetLastError();
+}
+
+template <bool FILL>
+static hipError_t launch_cells(SsArgs a, hipStream_t s) {
+    if (a.r < 1 || a.r > 32 || a.S < 1) return hipErrorInvalidValue;
+    int threads = 0;
+    if (ss_geometry(a, FILL ? a.T + a.H : a.T, threads)) return hipErrorInvalidValue;
+    auto al16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
+    const double* out = FILL ? a.x_draw : a.diff;
+    const bool vec = (a.N & 1) == 0 && al16(a.panel) && al16(out);
+    if (a.r <= 4) return launch_cells_rb<FILL, 4>(a, threads, vec, s);
+    if (a.r <= 8) return launch_cells_rb<FILL, 8>(a, threads, vec, s);
+    if (a.r <= 16) return launch_cells_rb<FILL, 16>(a, threads, vec, s);
+    return launch_cells_rb<FILL, 32>(a, threads, vec, s);
+}
+
+hipError_t launch_simsmooth_diff(SsArgs a, hipStream_t s) { return launch_cells<false>(a, s); }
+hipError_t launch_simsmooth_fill(SsArgs a, hipStream_t s) { return launch_cells<true>(a, s); }
+
+}  // namespace dfm

@@ -12,21 +12,6 @@
 
 namespace dfm {
 
-// uniform in (0,1) with 53 random bits
-__device__ __forceinline__ double u01(uint32_t a, uint32_t b) {
-    const uint64_t x = ((uint64_t)a << 32) | b;
-    return ((double)(x >> 11) + 0.5) * (1.0 / 9007199254740992.0);
-}
-// two independent N(0,1) per counter (Box-Muller on two 53-bit uniforms)
-__device__ __forceinline__ void normal2(uint64_t key, uint64_t stream, uint64_t idx, double& z0, double& z1) {
-    uint32_t o[4];
-    Philox::block(key, idx, stream, o);
-    const double u = u01(o[0], o[1]), v = u01(o[2], o[3]);
-    const double rad = sqrt(-2.0 * log(u));
-    double sn, cs;
-    sincospi(2.0 * v, &sn, &cs);
-    z0 = rad * cs; z1 = rad * sn;
-}
 __device__ __forceinline__ double uniform1(uint64_t key, uint64_t stream, uint64_t idx) {
     uint32_t o[4];
     Philox::block(key, idx, stream, o);

@@ -563,6 +563,70 @@ class DfmContext:
         _check(self._h, rc)
         return dict(xhat=xhat, xvar=xvar, common=common, f=f, P=P, loglik=ll)
 
+    # ------------------------------------------------------------------ posterior path draws (simsmooth.hip)
+    def simsmooth_batch(self, panel, Lam, R, Avar, Q, mu0, P0, D: int, H: int = 0, seed: int = 0, first_draw: int = 0,
+                        mean=None, sd=None, want_x: bool = True, may_have_missing: Optional[bool] = None,
+                        singular_q: bool = False):
+        """dfm_simsmooth_batch_dev (device tensors, torch's current stream): D joint posterior draws per replicate of the factor
+        path and of the missing / future cells over T + H rows (include/dfm_hip.h).  Avar [B,r,r p] ([A_1 .. A_p]), Q [B,r,r],
+        mu0 [B,r p], P0 [B,r p,r p]; mean / sd [B,N] (both or neither) put x into data units.  Returns dict(f [B,D,T+H,r],
+        x [B,D,T+H,N] or None)."""
+        torch = self._torch
+        B, T, N = panel.shape
+        r = Lam.shape[2]
+        k = Avar.shape[2]
+        p = k // r
+        if int(D) < 1:
+            raise ValueError("D must be >= 1")
+        if int(H) < 0:
+            raise ValueError("H must be >= 0")
+        if (mean is None) != (sd is None):
+            raise ValueError("mean and sd go together")
+        flags = self._flags(panel, may_have_missing, singular_q)
+        TH = T + int(H)
+        dev = panel.device
+        f = torch.empty((B, int(D), TH, r), dtype=torch.float64, device=dev)
+        x = torch.empty((B, int(D), TH, N), dtype=torch.float64, device=dev) if want_x else None
+        opt = lambda t, name, shape=None: None if t is None else self._dev(t, name, shape)
+        self._sync_stream()
+        rc = self._lib.dfm_simsmooth_batch_dev(
+            self._h, B, int(D), T, N, r, p, int(H), self._dev(panel, "panel"), self._dev(Lam, "Lam", (B, N, r)),
+            self._dev(R, "R", (B, N)), self._dev(Avar, "Avar", (B, r, r * p)), self._dev(Q, "Q", (B, r, r)),
+            self._dev(mu0, "mu0", (B, k)), self._dev(P0, "P0", (B, k, k)), opt(mean, "mean", (B, N)), opt(sd, "sd", (B, N)),
+            int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_draw), self._dev(f, "f_draw"), opt(x, "x_draw"), flags)
+        _check(self._h, rc)
+        return dict(f=f, x=x)
+
+    def simsmooth_batch_host(self, panel, Lam, R, Avar, Q, mu0, P0, D: int, H: int = 0, seed: int = 0, first_draw: int = 0,
+                             mean=None, sd=None, want_x: bool = True, may_have_missing: Optional[bool] = None,
+                             singular_q: bool = False):
+        """dfm_simsmooth_batch (host pointers; what Julia's ccall binds): NumPy in / out, same dict as simsmooth_batch."""
+        c = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+        panel, Lam, R, Avar, Q, mu0, P0 = map(c, (panel, Lam, R, Avar, Q, mu0, P0))
+        if (mean is None) != (sd is None):
+            raise ValueError("mean and sd go together")
+        mean = None if mean is None else c(mean)
+        sd = None if sd is None else c(sd)
+        B, T, N = panel.shape
+        r = Lam.shape[2]
+        p_lag = Avar.shape[2] // r
+        if int(D) < 1:
+            raise ValueError("D must be >= 1")
+        if int(H) < 0:
+            raise ValueError("H must be >= 0")
+        if may_have_missing is None:
+            may_have_missing = bool(np.isnan(panel).any())
+        flags = (_lib.DFM_F_MAY_HAVE_MISSING if may_have_missing else 0) | (_lib.DFM_F_SINGULAR_Q if singular_q else 0)
+        TH = T + int(H)
+        f = np.empty((B, int(D), TH, r))
+        x = np.empty((B, int(D), TH, N)) if want_x else None
+        p = lambda a: None if a is None else ctypes.c_void_p(a.ctypes.data)
+        rc = self._lib.dfm_simsmooth_batch(self._h, B, int(D), T, N, r, p_lag, int(H), p(panel), p(Lam), p(R), p(Avar), p(Q),
+                                           p(mu0), p(P0), p(mean), p(sd), int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_draw),
+                                           p(f), p(x), flags)
+        _check(self._h, rc)
+        return dict(f=f, x=x)
+
     # ------------------------------------------------------------------ AR idiosyncratic terms (quasi-differencing)
     def ks_pass_ar_batch(self, panel, Lam, sig2, rho, Avar, Q, mu0, P0, want_P: bool = True,
                          may_have_missing: Optional[bool] = None, singular_q: bool = False):

@@ -267,6 +267,40 @@ int dfm_forecast_batch(dfm_handle* h, int B, int T, int N, int r, int p, int H, 
                        double* xhat, double* xvar, double* common, double* f_out, double* P_out,
                        double* loglik, unsigned flags);
 
+/* --- posterior draws of factor and panel paths: simulation smoother (Durbin and Koopman 2002) ---------------------------
+ * The model of dfm_forecast_batch: x_t = Lam f_t + e_t, e_t ~ N(0, diag R), f_t = A_1 f_{t-1} + .. + A_p f_{t-p} + eta_t,
+ * eta_t ~ N(0, Q), z_0 = (f_0, .., f_{1-p}) ~ N(mu0, P0).  For replicate b, each draw d = 0 .. D-1 is an exact, independent draw of
+ * (f_1 .. f_{T+H}, the missing and future cells of x) given the observed cells of X (T rows; H >= 0 horizon rows):
+ *   1. z+_0 ~ N(mu0, P0); f+_t = sum_j A_j f+_{t-j} + eta+_t (t = 1..T); x+_ti = lam_i' f+_t + sqrt(R_i) eps+_ti
+ *   2. D_ti = X_ti - x+_ti on observed cells, NaN where X is NaN
+ *   3. g = E[f_{1:T} | D] by the pass of dfm_ks_pass_batch (p = 1) / dfm_ks_pass_varp_batch with the caller's parameters and mu0 = 0
+ *   4. f_draw[b][d][t] = f+_t + g_t for rows t < T                                                                 [B][D][T+H][r]
+ *   5. rows t >= T: f_t = sum_j A_j f_{t-j} + eta_t with fresh eta (needs T >= p)
+ *   6. x_draw[b][d][t][i] = mean_i + sd_i X_ti on an observed cell (bit for bit X_ti when mean / sd are NULL); on a missing cell
+ *      and for t >= T: mean_i + sd_i (lam_i' f_t + sqrt(R_i) eps_ti)                              (may be NULL)   [B][D][T+H][N]
+ * Inputs as dfm_forecast_batch.  The random stream is part of the contract: Philox4x32-10 (counter lo = idx, hi = stream word),
+ * Box-Muller on two 53-bit uniforms (as dfm_synth_panels_dev), key = seed ^ (0x9E3779B97F4A7C15 * (first_draw + d + 1)),
+ * stream word 16 b + s, element c = component c mod 2 of the pair at idx; t = 0-based output row:
+ *   s = 1: z+_0 = mu0 + L_P0 n,         idx = c / 2,                            c = 0 .. r p - 1
+ *   s = 2: eta of row t = L_Q n,        idx = t ceil(r / 2) + k / 2,   c = k,   t = 0 .. T+H-1 (eta+ for t < T)
+ *   s = 3: eps+ of the difference,      idx = t ceil(N / 2) + i / 2,   c = i,   t < T
+ *   s = 4: eps of the drawn cells,      idx = t ceil(N / 2) + i / 2,   c = i
+ * L_P0, L_Q: lower Cholesky roots, a column whose pivot is <= 1e-12 trace is zero (so Q may be singular with DFM_F_SINGULAR_Q).
+ * Draws [k, k + D) of a call equal the draws of a call with first_draw = k.  Flags as the pass (a NaN panel needs
+ * DFM_F_MAY_HAVE_MISSING, else DFM_E_MISSING).  Status: D < 1, H < 0, T < p: DFM_E_DIMS; f_draw NULL: DFM_E_NULL; mean without sd
+ * or sd without mean: DFM_E_NULL; a shape the pass refuses: its status; a non-finite pass: DFM_E_NUMERIC (host entry).  Outputs
+ * must not overlap the inputs.  Allocates in the handle (kept for the next call): the roots [B], the pass parameters and
+ * smoothed means of one slice of at most 8192 pass replicates, and (x_draw NULL) that slice's [S][T][N] difference panels; with
+ * x_draw they live at the start of the slice's part of x_draw, which the fill then overwrites. */
+int dfm_simsmooth_batch_dev(dfm_handle* h, int B, int D, int T, int N, int r, int p, int H, const double* panel,
+                            const double* Lam, const double* R, const double* Avar, const double* Q,
+                            const double* mu0, const double* P0, const double* mean, const double* sd,
+                            uint64_t seed, int64_t first_draw, double* f_draw, double* x_draw, unsigned flags);
+int dfm_simsmooth_batch(dfm_handle* h, int B, int D, int T, int N, int r, int p, int H, const double* panel,
+                        const double* Lam, const double* R, const double* Avar, const double* Q,
+                        const double* mu0, const double* P0, const double* mean, const double* sd,
+                        uint64_t seed, int64_t first_draw, double* f_draw, double* x_draw, unsigned flags);
+
 /* --- AR idiosyncratic terms --------------------------------------------------------
  *   x_it = lam_i' f_t + e_it,   e_it = rho_i1 e_i,t-1 + .. + rho_iq e_i,t-q + eps_it,  eps_it ~ N(0, sig2_i)
  * with rho [B][N][q] / sig2 [B][N] in the role of the reference's uar_coef / uar_ser^2 (AR(n_uarlag) of the loading

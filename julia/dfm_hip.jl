@@ -338,6 +338,33 @@ function forecast(h::Handle, z::Matrix{Float64}, params, H::Integer; nlag::Integ
             P = permutedims(P), loglik = ll[1])
 end
 
+"Joint posterior draws of the factor path and of the missing / future cells (dfm_simsmooth_batch; include/dfm_hip.h): z, params,
+nlag, mean / sd as `forecast`; ndraws exact, independent draws over rows 1..T+H by the simulation smoother, a pure function of
+(seed, first_draw + draw index).  Returns factor (ndraws x (T+H) x r) and x (ndraws x (T+H) x N: observed cells as given)."
+function draw_paths(h::Handle, z::Matrix{Float64}, params, ndraws::Integer, H::Integer = 0; nlag::Integer = 1,
+                    seed::Integer = 20160415, first_draw::Integer = 0, mean = nothing, sd = nothing,
+                    singular_q::Bool = false)
+    (mean === nothing) == (sd === nothing) || error("mean and sd go together")
+    T, N = size(z); r = size(params.Lam, 2); TH = T + H
+    Av = hasproperty(params, :Avar) ? params.Avar : params.A
+    panel = to_c_panel(z)
+    Lam = permutedims(params.Lam); R = copy(params.R); AC = permutedims(Av); QC = permutedims(params.Q)
+    mu0 = copy(params.mu0); P0C = permutedims(params.P0)
+    meanC = mean === nothing ? C_NULL : Vector{Float64}(mean); sdC = sd === nothing ? C_NULL : Vector{Float64}(sd)
+    f = Array{Float64}(undef, r, TH, ndraws); x = Array{Float64}(undef, N, TH, ndraws)
+    flags = (any(isnan, z) ? DFM_F_MAY_HAVE_MISSING : Cuint(0)) | (singular_q ? DFM_F_SINGULAR_Q : Cuint(0))
+    GC.@preserve panel Lam R AC QC mu0 P0C meanC sdC f x begin
+        rc = ccall((:dfm_simsmooth_batch, LIB), Cint,
+                   (Ptr{Cvoid}, Cint, Cint, Cint, Cint, Cint, Cint, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                    Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, UInt64, Int64,
+                    Ptr{Float64}, Ptr{Float64}, Cuint),
+                   h.ptr, 1, ndraws, T, N, r, nlag, H, panel, Lam, R, AC, QC, mu0, P0C, meanC, sdC, UInt64(seed),
+                   Int64(first_draw), f, x, flags)
+        check(h.ptr, rc)
+    end
+    return (factor = permutedims(f, (3, 2, 1)), x = permutedims(x, (3, 2, 1)))
+end
+
 "Smoother pass with AR(q) idiosyncratic terms (dfm_ks_pass_ar_batch; include/dfm_hip.h): x is T x N (NaN = missing, in
 deviations from its intercept), Lam N x r, sig2 = uar_ser.^2, rho = uar_coef (N x q), Avar r x (r p), Q r x r, mu0 / P0
 the moments of z_q, r max(p, q+1) wide.  Returns the smoothed factors of rows q+1..T and the conditional log-likelihood."
