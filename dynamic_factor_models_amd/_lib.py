@@ -31,7 +31,8 @@ DFM_MULTI_F_FORCE_COMM = 1
 (DFM_MULTI_LAM, DFM_MULTI_R, DFM_MULTI_A, DFM_MULTI_Q, DFM_MULTI_MU0, DFM_MULTI_P0, DFM_MULTI_F_SMOOTH, DFM_MULTI_P_SMOOTH,
  DFM_MULTI_LOGLIK, DFM_MULTI_LOGLIK_PATH, DFM_MULTI_ITERS, DFM_MULTI_PANEL) = range(12)
 ERRORS = {-1: "DFM_E_DIMS", -2: "DFM_E_R_UNSUPPORTED", -3: "DFM_E_NULL", -4: "DFM_E_MISSING",
-          -5: "DFM_E_NUMERIC", -6: "DFM_E_NO_DEVICE", -7: "DFM_E_COMM"}
+          -5: "DFM_E_NUMERIC", -6: "DFM_E_NO_DEVICE", -7: "DFM_E_COMM",
+          -8: "DFM_E_VINTAGE"}
 
 _PASS_ARGS = [c_vp, c_int, c_int, c_int, c_int] + [c_vp] * 10 + [c_uint]
 _EMSTEP_ARGS = [c_vp, c_int, c_int, c_int, c_int] + [c_vp] * 8 + [c_uint]
@@ -40,6 +41,7 @@ _VPASS_ARGS = [c_vp, c_int, c_int, c_int, c_int, c_int] + [c_vp] * 10 + [c_uint]
 _VEM_ARGS = [c_vp, c_int, c_int, c_int, c_int, c_int] + [c_vp] * 7 + [c_int, ctypes.c_double] + [c_vp] * 4 + [c_uint]
 _FC_ARGS = [c_vp, c_int, c_int, c_int, c_int, c_int, c_int] + [c_vp] * 15 + [c_uint]
 _SS_ARGS = [c_vp] + [c_int] * 7 + [c_vp] * 9 + [ctypes.c_uint64, ctypes.c_int64, c_vp, c_vp, c_uint]
+_NW_ARGS = [c_vp] + [c_int] * 5 + [c_vp] * 10 + [c_int] + [c_vp] * 6 + [c_uint]
 _ARPASS_ARGS = [c_vp, c_int, c_int, c_int, c_int, c_int, c_int] + [c_vp] * 11 + [c_uint]
 _AREM_ARGS = [c_vp, c_int, c_int, c_int, c_int, c_int, c_int] + [c_vp] * 8 + [c_int, ctypes.c_double] + [c_vp] * 4 + [c_uint]
 _OBSEM_ARGS = [c_vp, c_int, c_int, c_int, c_int, c_int] + [c_vp] * 8 + [c_int, ctypes.c_double] + [c_vp] * 4 + [c_uint]
@@ -92,6 +94,8 @@ SYMBOLS = {
     "dfm_forecast_batch": (c_int, _FC_ARGS),
     "dfm_simsmooth_batch_dev": (c_int, _SS_ARGS),
     "dfm_simsmooth_batch": (c_int, _SS_ARGS),
+    "dfm_news_batch_dev": (c_int, _NW_ARGS),
+    "dfm_news_batch": (c_int, _NW_ARGS),
     "dfm_ks_pass_ar_batch_dev": (c_int, _ARPASS_ARGS),
     "dfm_ks_pass_ar_batch": (c_int, _ARPASS_ARGS),
     "dfm_em_ar_batch_dev": (c_int, _AREM_ARGS),

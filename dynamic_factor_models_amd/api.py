@@ -568,6 +568,122 @@ def draw_paths(m: DFMModel, ndraws: int, H: int = 0, *, through: Optional[int] =
     return dict(rows=np.arange(m.initperiod, through + H + 1), cols=cols, factor=factor, x=x)
 
 
+def news(m: DFMModel, old, new, targets, *, groups=None, quantiles=None, ctx=None) -> dict:
+    """News decomposition of the revision of nowcasts / forecasts between two data vintages (Banbura and Modugno 2014) from the
+    parametric fit (`estimate(m, Parametric())`, nfac_o = 0), with one parameter set for both vintages.
+
+    `old` / `new`: arrays shaped like m.data (same columns; the one with fewer rows is padded with NaN rows), or ints meaning
+    "m.data through that 1-based row" (pseudo real-time vintages).  Every cell observed in old must be observed in new.
+    `targets`: (column of m.data, 1-based period) pairs, as `forecast`'s rows; a period past the data is a forecast.
+    Series, window mean / s.d. and standardisation are those of `forecast`.  One dfm_news_batch call on the GPU.
+    Returns a dict (data units):
+      rows, cols        1-based periods initperiod .. the last row of the vintages; the series estimate() used
+      y_old, y_rev, y_new   [G] the target conditioned on old, on the revised old data (new values on old's cells), on new
+      revision          y_new - y_old = data_revision (y_rev - y_old) + news_effect (y_new - y_rev)
+      impact            [G, cols] contribution of each series' new releases; sums to news_effect
+      news              [rows, cols] the news I = x_new - E[x | revised old] on the new cells, 0 elsewhere
+      weight            [G, rows, cols] d y_new / d x on new's observed cells (on the news cells: Cov(y, I) Var(I)^-1)
+      groups            {name: [G]} impacts summed over the columns of each group (with `groups`: name -> columns of m.data)
+    `quantiles` (needs m.replicates from estimate(..., nrep=...)): every bootstrap parameter set runs in the same batched call,
+    and nearest-rank bands over the replicates give impact_bands [nq, G, cols] and revision_bands [nq, G].  `m` is not
+    modified."""
+    if m.em_params is None:
+        raise ValueError("the model has not been estimated: run estimate(m, Parametric()) first")
+    if m.nfac_o != 0:
+        raise ValueError("news needs nfac_o = 0 (observed factors have no news here)")
+    ncol = m.data.shape[1]
+
+    def vintage(v, name):
+        if np.isscalar(v) and float(v) == int(v):
+            t = int(v)
+            if not (m.initperiod <= t <= m.T):
+                raise ValueError(f"{name} vintage: through must lie in initperiod..T ({m.initperiod}..{m.T})")
+            return np.asarray(m.data[:t], dtype=np.float64)
+        x = np.asarray(v, dtype=np.float64)
+        if x.ndim != 2 or x.shape[1] != ncol or x.shape[0] < m.initperiod:
+            raise ValueError(f"{name} vintage: an array shaped like m.data ([rows >= initperiod, {ncol}]) or a 1-based row")
+        return x
+    xo, xn = vintage(old, "old"), vintage(new, "new")
+    last = max(xo.shape[0], xn.shape[0])
+    padr = lambda x: np.vstack([x, np.full((last - x.shape[0], ncol), np.nan)])
+    xo, xn = padr(xo), padr(xn)
+    if np.any(~np.isnan(xo) & np.isnan(xn)):
+        raise ValueError("vintage: a cell observed in the old vintage is missing in the new one")
+    tg = list(targets) if targets is not None else []
+    if len(tg) < 1:
+        raise ValueError("at least one target (column, period) is needed")
+    ep = m.em_params
+    Lam, R, Q = ep["Lam"], ep["R"], ep["Q"]
+    A = ep["Avar"] if "Avar" in ep else ep["A"]
+    mu0, P0 = ep["mu0"], ep["P0"]
+    cols, _, mu, sd = _forecast_inputs(m, m.lastperiod)
+    if Lam.shape[0] != cols.size:
+        raise ValueError("m.em_params does not match the model's series (was the model changed after estimate?)")
+    pos = {int(c): j for j, c in enumerate(cols)}
+    tt, ti = [], []
+    for c, per in tg:
+        if int(c) not in pos:
+            raise ValueError(f"target column {c} is not one of the series estimate() used")
+        if int(per) < m.initperiod:
+            raise ValueError(f"target period {per} lies before initperiod ({m.initperiod})")
+        tt.append(int(per) - m.initperiod)
+        ti.append(pos[int(c)])
+    gsum = None
+    if groups is not None:
+        gsum = {}
+        for name, gc in dict(groups).items():
+            idx = [pos.get(int(c), -1) for c in np.atleast_1d(gc)]
+            if len(idx) < 1 or min(idx) < 0:
+                raise ValueError(f"groups[{name!r}] must list columns estimate() used")
+            gsum[name] = np.asarray(idx)
+    if np.any(np.nan_to_num(np.asarray(m.uar_coef, dtype=np.float64)[cols]) != 0.0):
+        raise ValueError("news has no AR idiosyncratic terms: the model carries uar_coef (estimate_ar_idio?)")
+    qs = None
+    if quantiles is not None:
+        qs = np.atleast_1d(np.asarray(quantiles, dtype=np.float64))
+        if getattr(m, "replicates", None) is None:
+            raise ValueError("quantile bands need bootstrap replicates: estimate(m, Parametric(), nrep=...) first")
+        if qs.size < 1 or not np.all((qs > 0.0) & (qs <= 1.0)):
+            raise ValueError("quantiles must lie in (0, 1]")
+    zo = (xo[m.initperiod - 1:, cols] - mu) / sd
+    zn = (xn[m.initperiod - 1:, cols] - mu) / sd
+    pairs = list(zip(tt, ti))
+    from ._lib import DfmError
+    ctx, own = _own(ctx)
+    try:
+        prm = [Lam[None], R[None], A[None], Q[None], mu0[None], P0[None]]
+        if qs is not None:                          # replicate 0: the point estimate; 1 ..: the bootstrap parameter sets
+            rp = m.replicates["params"]
+            prm = [np.concatenate([a, rp[k]]) for a, k in zip(prm, ("Lam", "R", "A", "Q", "mu0", "P0"))]
+        B = prm[0].shape[0]
+        rep = lambda a: np.ascontiguousarray(np.broadcast_to(a, (B,) + a.shape))
+        args = (rep(zo), rep(zn), *prm, pairs)
+        kw = dict(mean=rep(mu), sd=rep(sd), may_have_missing=bool(np.isnan(zn).any()))
+        try:
+            o = ctx.news_batch_host(*args, **kw)
+        except DfmError as err:                     # the information form inverts Q: as estimate(), retry in covariance form
+            if err.code != -5:
+                raise
+            o = ctx.news_batch_host(*args, singular_q=True, **kw)
+        bands = None
+        if qs is not None:
+            bands = (ctx.quantile_bands_host(o["impact"][1:], qs),
+                     ctx.quantile_bands_host(o["yhat"][1:, 2] - o["yhat"][1:, 0], qs))
+    finally:
+        if own:
+            ctx.close()
+    y = o["yhat"][0]
+    out = dict(rows=np.arange(m.initperiod, last + 1), cols=cols, y_old=y[0], y_rev=y[1], y_new=y[2], revision=y[2] - y[0],
+               data_revision=y[1] - y[0], news_effect=y[2] - y[1], impact=o["impact"][0], news=o["news"][0],
+               weight=o["weight"][0])
+    if gsum is not None:
+        out["groups"] = {name: out["impact"][:, idx].sum(axis=1) for name, idx in gsum.items()}
+    if bands is not None:
+        out["quantiles"] = qs
+        out["impact_bands"], out["revision_bands"] = bands
+    return out
+
+
 # ============================================================================= the NON-parametric path
 # `estimate!(m, ::NonParametric)` (dfm_functions.ipynb:530-543) = estimate_factor! -> estimate_factor_loading!
 # -> estimate_var!, with every regression run by the batched HIP kernels of als.hip (dfm_als_batch /

@@ -75,6 +75,8 @@ struct dfm_handle {
     size_t fc_bytes = 0;                   // caller does not take them (beside h->ws: the pass itself may reallocate that)
     void* ss = nullptr;                    // dfm_simsmooth_batch_dev: roots, the slice's pass parameters, smoothed means, logliks and
     size_t ss_bytes = 0;                   // (no x_draw) difference panels -- beside h->ws for the same reason
+    void* nw = nullptr;                    // dfm_news_batch_dev: targets, the revised old panel, one forecast's xhat, the slice's pass
+    size_t nw_bytes = 0;                   // parameters, u / a vectors, smoothed means and (no weight) covariance panels
     const double* odd_panel_src = nullptr; int odd_panel_dims[3] = {0, 0, 0};   // the panel whose padded copy h->odd holds (odd_pad keep_panel)
     std::string prof_file;                 // DFM_PF_PROF_FILE with DFM_SCAN_ABL=256: phase stamps of the fused pass
     char err[512] = {0};
@@ -86,11 +88,11 @@ struct dfm_handle {
 };
 
 enum KernelId { K_COLLAPSE = 0, K_RECURSION, K_MSTEP_STATS, K_MSTEP_SOLVE, K_PCA, K_SYNTH, K_PAD,
-                K_COLLAPSE_DMA, K_GRAM, K_COV, K_MEANSCAN, K_PFILL, K_COLLAPSE_MFMA, K_ALS, K_OLS, K_BOOT, K_QUANT, K_COLLAPSE_WIDE, K_EM_UPDATE, K_CHOW, K_MSTEP_MFMA, K_GRAM_XX, K_PASS_FUSED, K_FC_TAIL, K_FC_FILL, K_FC_PAD, K_SS_PREP, K_SS_EXPAND, K_SS_PATH, K_SS_DIFF, K_SS_FINISH, K_SS_FILL, K_COUNT };
+                K_COLLAPSE_DMA, K_GRAM, K_COV, K_MEANSCAN, K_PFILL, K_COLLAPSE_MFMA, K_ALS, K_OLS, K_BOOT, K_QUANT, K_COLLAPSE_WIDE, K_EM_UPDATE, K_CHOW, K_MSTEP_MFMA, K_GRAM_XX, K_PASS_FUSED, K_FC_TAIL, K_FC_FILL, K_FC_PAD, K_SS_PREP, K_SS_EXPAND, K_SS_PATH, K_SS_DIFF, K_SS_FINISH, K_SS_FILL, K_NW_REVISE, K_NW_GATHER, K_NW_GAMMA, K_NW_COV, K_NW_IMPACT, K_COUNT };
 static const char* const kKernelNames[K_COUNT] = {"collapse_kernel", "recursion_kernel", "mstep_lam_kernel",
                                                   "mstep_solve_kernel", "pca_kernel", "synth_kernel",
                                                   "pad_params_kernel", "collapse_dma_kernel", "gram_kernel",
-                                                  "cov_kernel", "meanscan_kernel", "pfill_kernel", "collapse_mfma_kernel", "als_kernel", "ols_kernel", "var_boot_kernel", "quantile_kernel", "collapse_wide_kernel", "em_update_kernel", "chow_kernel", "mstep_mfma_kernel", "gram_xx_kernel", "pass_fused_kernel", "forecast_tail_kernel", "forecast_fill_kernel", "forecast_pad_kernel", "simsmooth_prep_kernel", "simsmooth_expand_kernel", "simsmooth_path_kernel", "simsmooth_diff_kernel", "simsmooth_finish_kernel", "simsmooth_fill_kernel"};
+                                                  "cov_kernel", "meanscan_kernel", "pfill_kernel", "collapse_mfma_kernel", "als_kernel", "ols_kernel", "var_boot_kernel", "quantile_kernel", "collapse_wide_kernel", "em_update_kernel", "chow_kernel", "mstep_mfma_kernel", "gram_xx_kernel", "pass_fused_kernel", "forecast_tail_kernel", "forecast_fill_kernel", "forecast_pad_kernel", "simsmooth_prep_kernel", "simsmooth_expand_kernel", "simsmooth_path_kernel", "simsmooth_diff_kernel", "simsmooth_finish_kernel", "simsmooth_fill_kernel", "news_revise_kernel", "news_gather_kernel", "news_gamma_kernel", "news_cov_panel_kernel", "news_impact_kernel"};
 
 namespace dfm { int handle_device(const dfm_handle* h) { return h->device; } }   // (probe.hip)
 
@@ -1453,6 +1455,7 @@ int dfm_destroy(dfm_handle* h) {
     if (h->odd) hipFree(h->odd);
     if (h->fc) hipFree(h->fc);
     if (h->ss) hipFree(h->ss);
+    if (h->nw) hipFree(h->nw);
     if (h->status_dev) hipFree(h->status_dev);
     if (h->own_stream && h->stream) hipStreamDestroy(h->stream);
     delete h;
@@ -1607,7 +1610,8 @@ int dfm_ks_pass_batch_dev(dfm_handle* h, int B, int T, int N, int r, const doubl
 
 // The status word of the last call's plan, read after the stream has been synchronised.  Bits: 1 = NaN in a panel that was
 // declared balanced, 2 = the PCA start's subspace iteration did not converge, 4 = a bounded wait between the waves of the
-// one-launch pass ran out (its outputs are invalid even where the log-likelihood happens to be finite).  Every synchronising
+// one-launch pass ran out (its outputs are invalid even where the log-likelihood happens to be finite), 8 = dfm_news_batch: a cell
+// of the old vintage is observed where the new one is missing.  Every synchronising
 // entry point goes through here; device-pointer callers get the same check from dfm_synchronize / dfm_check_status.
 static int status_check(dfm_handle* h) {
     if (!h->status_dev) return 0;
@@ -1615,6 +1619,7 @@ static int status_check(dfm_handle* h) {
     HIP_TRY(h, hipMemcpy(&st, h->status_dev, sizeof(int), hipMemcpyDeviceToHost));
     if (st) HIP_TRY(h, hipMemset(h->status_dev, 0, sizeof(int)));      // reported once
     if (st & 4) return fail(h, DFM_E_NUMERIC, "one-launch pass: a bounded wait between its waves ran out (results invalid)%s");
+    if (st & 8) return fail(h, DFM_E_VINTAGE, "news: a cell observed in the old vintage is missing in the new one%s");
     if (st & 1) return fail(h, DFM_E_MISSING, "panel contains NaN but DFM_F_MAY_HAVE_MISSING was not set%s");
     if (st & 2) return fail(h, DFM_E_NUMERIC, "PCA subspace iteration did not converge (near-degenerate spectrum at the cut)%s");
     return 0;
@@ -2608,6 +2613,191 @@ int dfm_simsmooth_batch(dfm_handle* h, int B, int D, int T, int N, int r, int p,
         if (e != hipSuccess) rc = hip_fail(h, e, "hipStreamSynchronize");
     }
     if (rc == 0) rc = post_check(h, ll_host.data(), (int)BD);
+    (void)hipFree(buf);
+    return rc;
+}
+
+
+// ---- news decomposition of nowcast revisions (news.hip) --------------------------------------------------------------------
+// The three conditional means run through dfm_forecast_batch_dev unchanged (old, new, then the revised old panel, whose xhat stays
+// in h->nw for the impacts).  The B G weight passes run in slices of at most kNwSlice pass replicates j = b G + g, as
+// simsmooth_run runs its difference panels: expand the parameters (mu0 = 0; simsmooth_expand_kernel with D = G), the a_t
+// vectors, the covariance panels, the existing pass over them, the impacts.  With weight the covariance panels of a slice live
+// in that slice's part of weight, which news_impact_kernel overwrites cell by cell.
+static constexpr int kNwSlice = 8192;
+
+static int ensure_nw(dfm_handle* h, size_t bytes) {
+    if (bytes <= h->nw_bytes) return 0;
+    if (h->nw) {
+        HIP_TRY(h, hipDeviceSynchronize());
+        HIP_TRY(h, hipFree(h->nw));
+        h->nw = nullptr;
+        h->nw_bytes = 0;
+    }
+    HIP_TRY(h, hipMalloc(&h->nw, bytes));
+    h->nw_bytes = bytes;
+    return 0;
+}
+
+// Argument check of both entries; *H = the horizon the targets need.
+static int news_check(dfm_handle* h, int B, int T, int N, int r, int p, const double* oldp, const double* newp, const double* Lam,
+                      const double* R, const double* Avar, const double* Q, const double* mu0, const double* P0,
+                      const double* mean, const double* sd, int G, const int* target_t, const int* target_i, const double* yhat,
+                      const double* impact, int* H) {
+    if (int rc = check_dims(h, B, T, N, r)) return rc;
+    if (G < 1) return fail(h, DFM_E_DIMS, "G (targets) must be >= 1%s");
+    if (p < 1) return fail(h, DFM_E_DIMS, "number of factor lags must be >= 1%s");
+    if (r * p > DFM_MAX_R) return fail(h, DFM_E_R_UNSUPPORTED, "r * p > DFM_MAX_R (32)%s");
+    if ((long long)B * G > 0x7fffffffLL) return fail(h, DFM_E_DIMS, "B * G must be < 2^31%s");
+    if (!oldp || !newp || !Lam || !R || !Avar || !Q || !mu0 || !P0 || !target_t || !target_i || !yhat || !impact)
+        return fail(h, DFM_E_NULL, "required pointer is NULL%s");
+    if ((mean == nullptr) != (sd == nullptr)) return fail(h, DFM_E_NULL, "mean and sd must both be given or both be NULL%s");
+    int tmax = 0;
+    for (int g = 0; g < G; ++g) {
+        if (target_t[g] < 0 || target_t[g] > 0x3fffffff || target_i[g] < 0 || target_i[g] >= N)
+            return fail(h, DFM_E_DIMS, "a target lies outside [0, T + H) x [0, N)%s");
+        if (target_t[g] > tmax) tmax = target_t[g];
+    }
+    *H = tmax + 1 > T ? tmax + 1 - T : 0;
+    return 0;
+}
+
+// ll_all: [3 B + B G] device log-likelihoods (the three forecasts, then the weight passes; the host entry checks them), or null
+static int news_run(dfm_handle* h, int B, int T, int N, int r, int p, int H, const double* oldp, const double* newp,
+                    const double* Lam, const double* R, const double* Avar, const double* Q, const double* mu0, const double* P0,
+                    const double* mean, const double* sd, int G, const int* target_t, const int* target_i, double* yhat,
+                    double* impact, double* news, double* weight, double* ll_all, unsigned flags) {
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t d = sizeof(double), k = (size_t)r * p, TH = (size_t)T + H;
+    const long long BG = (long long)B * G;
+    const int Smax = (int)(BG < kNwSlice ? BG : kNwSlice);
+    size_t off = 0;
+    const size_t o_t = take(off, (size_t)2 * G * sizeof(int)), o_rev = take(off, (size_t)B * T * N * d),
+                 o_x = take(off, (size_t)B * TH * N * d), o_f = take(off, (size_t)B * TH * r * d),
+                 o_L = take(off, (size_t)Smax * N * r * d), o_R = take(off, (size_t)Smax * N * d),
+                 o_A = take(off, (size_t)Smax * r * k * d), o_Q = take(off, (size_t)Smax * r * r * d),
+                 o_m = take(off, (size_t)Smax * k * d), o_P = take(off, (size_t)Smax * k * k * d),
+                 o_u = take(off, (size_t)Smax * T * k * d), o_av = take(off, (size_t)Smax * T * r * d),
+                 o_g = take(off, (size_t)Smax * T * r * d),
+                 o_ll = ll_all ? (size_t)-1 : take(off, (size_t)(B > Smax ? B : Smax) * d),
+                 o_c = weight ? (size_t)-1 : take(off, (size_t)Smax * T * N * d);
+    if (int rc = ensure_nw(h, off)) return rc;
+    char* base = static_cast<char*>(h->nw);
+    auto ptr = [&](size_t o) { return o == (size_t)-1 ? nullptr : reinterpret_cast<double*>(base + o); };
+    int* tgt = reinterpret_cast<int*>(base + o_t);
+    {
+        std::vector<int> tg((size_t)2 * G);                   // (a pageable source: staged before the call returns)
+        for (int g = 0; g < G; ++g) { tg[2 * g] = target_t[g]; tg[2 * g + 1] = target_i[g]; }
+        HIP_TRY(h, hipMemcpyAsync(tgt, tg.data(), tg.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    }
+    NwArgs a{};
+    a.B = B; a.T = T; a.N = N; a.r = r; a.p = p; a.G = G; a.TH = (int)TH;
+    a.oldp = oldp; a.newp = newp; a.Lam = Lam; a.R = R; a.A = Avar; a.P0 = P0; a.Q = Q; a.mean = mean; a.sd = sd;
+    a.tgt = tgt; a.rev = ptr(o_rev); a.xrev = ptr(o_x); a.yhat = yhat; a.impact = impact; a.news = news; a.weight = weight;
+    a.status = h->status_dev; a.u = ptr(o_u); a.av = ptr(o_av); a.g = ptr(o_g);
+    {
+        ProfScope ps(h, K_NW_REVISE);
+        HIP_TRY(h, launch_news_revise(a, h->stream));
+    }
+    // old, new, revised old: the last one's xhat stays in o_x for the impacts
+    const struct { const double* panel; unsigned fl; int which; } runs[3] = {
+        {oldp, flags | DFM_F_MAY_HAVE_MISSING, 0}, {newp, flags, 2}, {a.rev, flags | DFM_F_MAY_HAVE_MISSING, 1}};
+    for (const auto& run : runs) {
+        double* ll = ll_all ? ll_all + (size_t)run.which * B : ptr(o_ll);
+        if (int rc = dfm_forecast_batch_dev(h, B, T, N, r, p, H, run.panel, Lam, R, Avar, Q, mu0, P0, mean, sd, ptr(o_x), nullptr,
+                                            nullptr, ptr(o_f), nullptr, ll, run.fl)) return rc;
+        ProfScope ps(h, K_NW_GATHER);
+        HIP_TRY(h, launch_news_gather(a, ptr(o_x), run.which, h->stream));
+    }
+    SsArgs e{};
+    e.B = B; e.D = G; e.T = T; e.N = N; e.r = r; e.p = p;
+    e.Lam = Lam; e.R = R; e.A = Avar; e.Q = Q; e.mu0 = mu0; e.P0 = P0;
+    e.eLam = ptr(o_L); e.eR = ptr(o_R); e.eA = ptr(o_A); e.eQ = ptr(o_Q); e.emu0 = ptr(o_m); e.eP0 = ptr(o_P);
+    for (long long j0 = 0; j0 < BG; j0 += Smax) {
+        const int S = (int)(BG - j0 < Smax ? BG - j0 : Smax);
+        a.j0 = j0; a.S = S; e.j0 = j0; e.S = S;
+        a.cp = weight ? weight + (size_t)j0 * T * N : ptr(o_c);
+        double* ll = ll_all ? ll_all + (size_t)3 * B + j0 : ptr(o_ll);
+        {
+            ProfScope ps(h, K_SS_EXPAND);
+            HIP_TRY(h, launch_simsmooth_expand(e, h->stream));
+        }
+        {
+            ProfScope ps(h, K_NW_GAMMA);
+            HIP_TRY(h, launch_news_gamma(a, h->stream));
+        }
+        {
+            ProfScope ps(h, K_NW_COV);
+            HIP_TRY(h, launch_news_cov_panel(a, h->stream));
+        }
+        double* g = ptr(o_g);
+        if (p == 1) {
+            if (int rc = dfm_ks_pass_batch_dev(h, S, T, N, r, a.cp, e.eLam, e.eR, e.eA, e.eQ, e.emu0, e.eP0, g, nullptr, ll, flags))
+                return rc;
+        } else {
+            if (int rc = dfm_ks_pass_varp_batch_dev(h, S, T, N, r, p, a.cp, e.eLam, e.eR, e.eA, e.eQ, e.emu0, e.eP0, g, nullptr, ll,
+                                                    flags)) return rc;
+        }
+        ProfScope ps(h, K_NW_IMPACT);
+        HIP_TRY(h, launch_news_impact(a, h->stream));
+    }
+    return 0;
+}
+
+int dfm_news_batch_dev(dfm_handle* h, int B, int T, int N, int r, int p, const double* old_panel, const double* new_panel,
+                       const double* Lam, const double* R, const double* Avar, const double* Q, const double* mu0,
+                       const double* P0, const double* mean, const double* sd, int G, const int* target_t, const int* target_i,
+                       double* yhat, double* impact, double* news, double* weight, unsigned flags) {
+    int H = 0;
+    if (int rc = news_check(h, B, T, N, r, p, old_panel, new_panel, Lam, R, Avar, Q, mu0, P0, mean, sd, G, target_t, target_i, yhat,
+                            impact, &H)) return rc;
+    return news_run(h, B, T, N, r, p, H, old_panel, new_panel, Lam, R, Avar, Q, mu0, P0, mean, sd, G, target_t, target_i, yhat,
+                    impact, news, weight, nullptr, flags);
+}
+
+int dfm_news_batch(dfm_handle* h, int B, int T, int N, int r, int p, const double* old_panel, const double* new_panel,
+                   const double* Lam, const double* R, const double* Avar, const double* Q, const double* mu0, const double* P0,
+                   const double* mean, const double* sd, int G, const int* target_t, const int* target_i, double* yhat,
+                   double* impact, double* news, double* weight, unsigned flags) {
+    int H = 0;
+    if (int rc = news_check(h, B, T, N, r, p, old_panel, new_panel, Lam, R, Avar, Q, mu0, P0, mean, sd, G, target_t, target_i, yhat,
+                            impact, &H)) return rc;
+    if (int rc = status_epoch(h)) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t d = sizeof(double), k = (size_t)r * p, BG = (size_t)B * G;
+    const size_t n_panel = (size_t)B * T * N, n_lam = (size_t)B * N * r, n_R = (size_t)B * N, n_a = (size_t)B * r * k,
+                 n_q = (size_t)B * r * r, n_v = (size_t)B * k, n_p0 = (size_t)B * k * k, n_y = (size_t)B * 3 * G,
+                 n_imp = BG * N, n_news = news ? n_panel : 0, n_w = weight ? BG * T * N : 0, n_ll = (size_t)3 * B + BG;
+    const size_t total = 2 * n_panel + n_lam + n_R + n_a + n_q + n_v + n_p0 + (mean ? 2 * n_R : 0) + n_y + n_imp + n_news + n_w +
+                         n_ll + 16 * 32;
+    double* buf = nullptr;
+    HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&buf), total * d));
+    double* dp = buf;
+    auto take_d = [&](size_t n) { double* dst = dp; dp += (n + 31) & ~(size_t)31; return dst; };
+    auto up = [&](const double* src, size_t n) -> double* {
+        double* dst = take_d(n);
+        (void)hipMemcpyAsync(dst, src, n * d, hipMemcpyHostToDevice, h->stream);
+        return dst;
+    };
+    double *xo_d = up(old_panel, n_panel), *xn_d = up(new_panel, n_panel), *lam_d = up(Lam, n_lam), *R_d = up(R, n_R),
+           *A_d = up(Avar, n_a), *Q_d = up(Q, n_q), *mu_d = up(mu0, n_v), *P0_d = up(P0, n_p0);
+    double *mean_d = mean ? up(mean, n_R) : nullptr, *sd_d = sd ? up(sd, n_R) : nullptr;
+    double *y_d = take_d(n_y), *imp_d = take_d(n_imp), *news_d = news ? take_d(n_news) : nullptr,
+           *w_d = weight ? take_d(n_w) : nullptr, *ll_d = take_d(n_ll);
+    int rc = news_run(h, B, T, N, r, p, H, xo_d, xn_d, lam_d, R_d, A_d, Q_d, mu_d, P0_d, mean_d, sd_d, G, target_t, target_i, y_d,
+                      imp_d, news_d, w_d, ll_d, flags);
+    std::vector<double> ll_host(n_ll);
+    if (rc == 0) {
+        auto down = [&](void* dst, const void* src, size_t n) { (void)hipMemcpyAsync(dst, src, n * d, hipMemcpyDeviceToHost, h->stream); };
+        down(yhat, y_d, n_y);
+        down(impact, imp_d, n_imp);
+        if (news) down(news, news_d, n_news);
+        if (weight) down(weight, w_d, n_w);
+        down(ll_host.data(), ll_d, n_ll);
+        hipError_t e = hipStreamSynchronize(h->stream);
+        if (e != hipSuccess) rc = hip_fail(h, e, "hipStreamSynchronize");
+    }
+    if (rc == 0) rc = post_check(h, ll_host.data(), (int)n_ll);
     (void)hipFree(buf);
     return rc;
 }

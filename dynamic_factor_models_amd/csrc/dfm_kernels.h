@@ -491,6 +491,36 @@ hipError_t launch_simsmooth_diff(SsArgs a, hipStream_t s);
 hipError_t launch_simsmooth_finish(const SsArgs& a, hipStream_t s);
 hipError_t launch_simsmooth_fill(SsArgs a, hipStream_t s);
 
+// News decomposition of nowcast revisions (news.hip).  Pass replicate j = b G + g (replicate b, target g); a call runs its B G
+// weight passes in slices j0 .. j0 + S - 1.
+struct NwArgs {
+    int B, T, N, r, p, G, TH;                     // TH = T + H rows of the forecasts
+    const double* oldp; const double* newp;       // [B][T][N] (NaN = missing)
+    const double* Lam; const double* R;           // [B][N][r], [B][N]
+    const double* A; const double* P0;            // [B][r][r p], [B][r p][r p]
+    const double* Q;                              // [B][r][r]
+    const double* mean; const double* sd;         // [B][N] or both null
+    const int* tgt;                               // device [G][2] = (t*, i*)
+    double* rev;                                  // [B][T][N] revised old panel
+    const double* xrev;                           // [B][TH][N] xhat of the revised-old run
+    double* yhat;                                 // [B][3][G]
+    double* impact;                               // [B][G][N]
+    double* news;                                 // [B][T][N] or null
+    double* weight;                               // [B][G][T][N] or null
+    int* status;                                  // bit 8: a cell of old is observed where new is NaN
+    long long j0; int S;                          // the slice
+    double* u;                                    // [S][T][r p] (A_c')^(t*-t) S' lam_i* of the rows t < min(t*, T)
+    double* av;                                   // [S][T][r] S Cov(z_{t+1}, z_{t*+1}) S' lam_i*
+    double* cp;                                   // [S][T][N] covariance panels (may alias the slice's part of weight)
+    const double* g;                              // [S][T][r] E_0[f | c] of the covariance panels
+    int NPB, GR, RC, nchunk, nsblk;               // geometry of the cell kernels (set by their launchers)
+};
+hipError_t launch_news_revise(const NwArgs& a, hipStream_t s);
+hipError_t launch_news_gather(const NwArgs& a, const double* xhat, int which, hipStream_t s);
+hipError_t launch_news_gamma(const NwArgs& a, hipStream_t s);
+hipError_t launch_news_cov_panel(NwArgs a, hipStream_t s);
+hipError_t launch_news_impact(NwArgs a, hipStream_t s);
+
 // Device-side synthetic replicates (synth.hip); all arrays in the caller's layout (r).
 struct SynthArgs {
     int B, T, N, r;

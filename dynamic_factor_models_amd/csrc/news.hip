@@ -1,0 +1,436 @@
+// news.hip -- news decomposition of nowcast revisions (dfm_news_batch, capi.hip; Banbura and Modugno 2014).  For replicate b and
+// target g = (t*, i*) the weights w = dy_new / dx on the observed cells of the new vintage are Sigma^-1 c with
+// c = Cov(z_new, y_z); in the factor model x - Lam E_0[f | x] = R Sigma^-1 x, so one smoother pass with mu0 = 0 over the
+// covariance panel c gives them all.  Pass replicate j = b G + g:
+//   news_revise_kernel      the revised old panel (new values on the old vintage's cells) and the vintage check      [B][T][N]
+//   news_gather_kernel      the target cells of a forecast's xhat into yhat                                          [B][3][G]
+//   news_gamma_kernel       a_t = S Cov(z_{t+1}, z_{t*+1}) S' lam_i* for t < T from Gamma_t = Var(z_t)               [S][T][r]
+//   news_cov_panel_kernel   c_ti = lam_i' a_t (+ R_i* on the target cell) on the new vintage's cells, NaN elsewhere  [S][T][N]
+//   news_impact_kernel      w, the news I and the per-series impacts sum_t w I                                       [S][N]
+// The two cell kernels use the geometry of simsmooth.hip: one workgroup owns a pass replicate's rows (a chunk of them for the
+// covariance panel, all of them for the impacts, which are summed over t in registers and then across the workgroup's row groups
+// in LDS in a fixed order: no atomics, results do not depend on scheduling), stages the r-vectors of its rows in LDS, keeps the
+// loadings of its two columns in registers and moves 16 bytes per lane where N is even.  blockIdx.x is the pass replicate: the G
+// targets of a replicate run next to each other, so the panels they share come from L2 / the Infinity Cache.
+#include "dfm_kernels.h"
+
+namespace dfm {
+
+constexpr int kNwMaxThreads = 512;            // cell kernels
+constexpr size_t kNwLds = 32 * 1024;          // cell kernels: r-vectors of the rows staged per workgroup
+constexpr int kNwTC = 32;                     // news_gamma_kernel: rows per LDS chunk of u_t / a_t (global traffic once per chunk)
+constexpr int kNwVintageBit = 8;              // status word bit: Omega_old is not a subset of Omega_new
+
+// rev = new where old is observed, NaN elsewhere; a cell observed in old but missing in new raises the vintage bit.
+__global__ __launch_bounds__(256) void news_revise_kernel(NwArgs a) {
+    const size_t n = (size_t)a.B * a.T * a.N;
+    const double qnan = __longlong_as_double(0x7FF8000000000000ll);
+    bool bad = false;
+    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {
+        const double xo = a.oldp[e], xn = a.newp[e];
+        const bool oo = xo == xo;
+        bad = bad || (oo && xn != xn);
+        a.rev[e] = oo ? xn : qnan;
+    }
+    if (bad) atomicOr(a.status, kNwVintageBit);
+}
+
+__global__ __launch_bounds__(256) void news_gather_kernel(NwArgs a, const double* xhat, int which) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= a.B * a.G) return;
+    const int b = e / a.G, g = e % a.G;
+    const int ts = a.tgt[2 * g], is = a.tgt[2 * g + 1];
+    a.yhat[((size_t)b * 3 + which) * a.G + g] = xhat[((size_t)b * a.TH + ts) * a.N + is];
+}
+
+// One workgroup per pass replicate of the slice; KB >= k = r p.  With u_t = (A_c')^(t* - t) S' lam (u_t* = S' lam):
+//   rows t < min(t*, T):     a_t = S Gamma_{t+1} u_t           (Cov(z_{t+1}, z_{t*+1}) = Gamma_{t+1} (A_c')^(t* - t))
+//   row t = t* (if < T):     v = Gamma_{t*+1} S' lam,  a_t = S v
+//   rows t* < t < T:         v <- A_c v,  a_t = S v          (Cov(z_{t+1}, z_{t*+1}) = A_c^(t - t*) Gamma_{t*+1})
+// Gamma_0 = P0, Gamma_t = A_c Gamma_{t-1} A_c' + Q_c (symmetric: row m of Gamma is read for its column m).  Phase U runs the u
+// chain backwards from t* into u (global, staged 32 rows at a time); phase Gamma runs the recursion forwards and reads u back in
+// chunks.  a_t is staged the same way: a barrier waits for every outstanding global store, so no row stores on its own.
+template <int KB, int NT>
+__global__ __launch_bounds__(NT) void news_gamma_kernel(NwArgs a) {
+    constexpr int NE = (KB * KB + NT - 1) / NT;               // elements of Gamma per thread
+    __shared__ double sA[KB * KB], sG[KB * KB], sW[KB * KB];
+    __shared__ double sU[2][kNwTC * KB], sAv[2][kNwTC * KB], sv[2][KB], sl[KB];
+    const int s = blockIdx.x, tid = threadIdx.x;
+    const long long j = a.j0 + s;
+    const size_t b = (size_t)(j / a.G);
+    const int gi = (int)(j % a.G), r = a.r, k = a.r * a.p, T = a.T, N = a.N;
+    const int ts = a.tgt[2 * gi], is = a.tgt[2 * gi + 1];
+    double qe[NE];                                            // Q_c of this thread's elements
+#pragma unroll
+    for (int q = 0; q < NE; ++q) {
+        const int e = tid + q * NT, i = e / k, m = e % k;
+        qe[q] = 0.0;
+        if (e >= k * k) continue;
+        sA[i * KB + m] = i < r ? a.A[(b * r + i) * k + m] : (m == i - r ? 1.0 : 0.0);
+        sG[i * KB + m] = a.P0[(b * k + i) * k + m];
+        qe[q] = (i < r && m < r) ? a.Q[(b * r + i) * r + m] : 0.0;
+    }
+    if (tid < k) {
+        const double l = tid < r ? a.Lam[(b * N + is) * r + tid] : 0.0;
+        sl[tid] = l;
+        sv[0][tid] = l;
+    }
+    __syncthreads();
+    double* U = a.u + (size_t)s * T * k;
+    double* AV = a.av + (size_t)s * T * r;
+    // phase U: u_t for t = t* - 1 .. 0 (stored for t < T), the chunk of rows [t, t + 32) flushed when t reaches its first row
+    int cur = 0;
+    for (int t = ts - 1; t >= 0; --t) {
+        const int pb = (t / kNwTC) & 1;
+        if (tid < k) {
+            double v = 0.0;
+#pragma unroll
+            for (int m = 0; m < KB; ++m)
+                if (m < k) v = fma(sA[m * KB + tid], sv[cur][m], v);
+            sv[cur ^ 1][tid] = v;
+            if (t < T) sU[pb][(t % kNwTC) * KB + tid] = v;
+        }
+        cur ^= 1;
+        __syncthreads();
+        if (t < T && t % kNwTC == 0) {
+            const int nr = (t + kNwTC < T ? t + kNwTC : T) - t;
+            for (int e = tid; e < nr * k; e += NT) U[(size_t)t * k + e] = sU[pb][(e / k) * KB + e % k];
+        }
+    }
+    __syncthreads();                                          // (u is read back below by other threads)
+    const int tend = ts < T ? ts : T - 1;                     // the recursion runs to Gamma_{tend + 1}
+    auto flush_av = [&](int t) {                              // after a barrier: rows of t's chunk up to t
+        const int pb = (t / kNwTC) & 1, c0 = t - t % kNwTC;
+        for (int e = tid; e < (t - c0 + 1) * r; e += NT) AV[(size_t)c0 * r + e] = sAv[pb][(e / r) * KB + e % r];
+    };
+    for (int t = 0; t <= tend; ++t) {
+        const int pb = (t / kNwTC) & 1;
+        if (t < ts && t % kNwTC == 0) {                       // u rows of this chunk (read two barriers later)
+            const int t1 = t + kNwTC < ts ? (t + kNwTC < T ? t + kNwTC : T) : (ts < T ? ts : T);
+            for (int e = tid; e < (t1 - t) * k; e += NT) sU[pb][(e / k) * KB + e % k] = U[(size_t)t * k + e];
+        }
+#pragma unroll
+        for (int q = 0; q < NE; ++q) {                        // W = A_c Gamma
+            const int e = tid + q * NT, i = e / k, c = e % k;
+            if (e >= k * k) continue;
+            double v = 0.0;
+#pragma unroll
+            for (int m = 0; m < KB; ++m)
+                if (m < k) v = fma(sA[i * KB + m], sG[c * KB + m], v);
+            sW[i * KB + c] = v;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < NE; ++q) {                        // Gamma = W A_c' + Q_c
+            const int e = tid + q * NT, i = e / k, c = e % k;
+            if (e >= k * k) continue;
+            double v = qe[q];
+#pragma unroll
+            for (int m = 0; m < KB; ++m)
+                if (m < k) v = fma(sW[i * KB + m], sA[c * KB + m], v);
+            sG[i * KB + c] = v;
+        }
+        __syncthreads();
+        if (t < ts) {
+            if (tid < r) {
+                double v = 0.0;
+#pragma unroll
+                for (int m = 0; m < KB; ++m)
+                    if (m < k) v = fma(sG[tid * KB + m], sU[pb][(t % kNwTC) * KB + m], v);
+                sAv[pb][(t % kNwTC) * KB + tid] = v;
+            }
+        } else if (tid < k) {                                 // t = t* < T
+            double v = 0.0;
+#pragma unroll
+            for (int m = 0; m < KB; ++m)
+                if (m < r) v = fma(sG[tid * KB + m], sl[m], v);
+            sv[0][tid] = v;
+            if (tid < r) sAv[pb][(t % kNwTC) * KB + tid] = v;
+        }
+        if (t % kNwTC == kNwTC - 1 || t == T - 1) {
+            __syncthreads();
+            flush_av(t);
+        }
+    }
+    // rows t* < t < T: v <- A_c v
+    cur = 0;
+    __syncthreads();
+    for (int t = tend + 1; t < T; ++t) {
+        const int pb = (t / kNwTC) & 1;
+        if (tid < k) {
+            double v = 0.0;
+#pragma unroll
+            for (int m = 0; m < KB; ++m)
+                if (m < k) v = fma(sA[tid * KB + m], sv[cur][m], v);
+            sv[cur ^ 1][tid] = v;
+            if (tid < r) sAv[pb][(t % kNwTC) * KB + tid] = v;
+        }
+        cur ^= 1;
+        __syncthreads();
+        if (t % kNwTC == kNwTC - 1 || t == T - 1) flush_av(t);
+    }
+}
+
+// The covariance panels: chunk blockIdx.y of the rows of pass replicate blockIdx.x, column pairs of block blockIdx.z.
+template <int RB, bool VEC>
+__global__ __launch_bounds__(kNwMaxThreads) void news_cov_panel_kernel(NwArgs a) {
+    extern __shared__ __attribute__((aligned(16))) double sav[];
+    const int r = a.r, N = a.N, T = a.T, tid = threadIdx.x;
+    const int s = blockIdx.x, c = blockIdx.y, sb = blockIdx.z;
+    const long long j = a.j0 + s;
+    const size_t b = (size_t)(j / a.G);
+    const int gi = (int)(j % a.G);
+    const int t0 = c * a.RC, t1 = t0 + a.RC < T ? t0 + a.RC : T;
+    const double* AV = a.av + (size_t)s * T * r;
+    for (int e = tid; e < (t1 - t0) * r; e += blockDim.x) sav[e] = AV[(size_t)t0 * r + e];
+    __syncthreads();
+    const int jj = tid % a.NPB, gr = tid / a.NPB;
+    if (gr >= a.GR) return;
+    const int i0 = 2 * (sb * a.NPB + jj);
+    if (i0 >= N) return;
+    const bool two = i0 + 1 < N;
+    double l0[RB], l1[RB];
+#pragma unroll
+    for (int q = 0; q < RB; ++q) {
+        l0[q] = q < r ? a.Lam[(b * N + i0) * r + q] : 0.0;
+        l1[q] = (q < r && two) ? a.Lam[(b * N + i0 + 1) * r + q] : 0.0;
+    }
+    const int ts = a.tgt[2 * gi], is = a.tgt[2 * gi + 1];
+    const double radd = a.R[b * N + is];
+    const double qnan = __longlong_as_double(0x7FF8000000000000ll);
+    auto load = [&](int t, double& x0, double& x1) {
+        x0 = qnan; x1 = qnan;
+        if (t < t1) {
+            const double* px = a.newp + (b * T + t) * N + i0;
+            if constexpr (VEC) {
+                const double2 v = *reinterpret_cast<const double2*>(px);
+                x0 = v.x; x1 = v.y;
+            } else {
+                x0 = px[0];
+                if (two) x1 = px[1];
+            }
+        }
+    };
+    double nx0, nx1;
+    load(t0 + gr, nx0, nx1);
+    for (int t = t0 + gr; t < t1; t += a.GR) {
+        const double* av = sav + (size_t)(t - t0) * r;
+        const double x0 = nx0, x1 = nx1;
+        load(t + a.GR, nx0, nx1);
+        double m0 = 0.0, m1 = 0.0;
+#pragma unroll
+        for (int q = 0; q < RB; ++q)
+            if (q < r) {
+                const double v = av[q];
+                m0 = fma(l0[q], v, m0);
+                m1 = fma(l1[q], v, m1);
+            }
+        if (t == ts) {
+            if (i0 == is) m0 += radd;
+            if (i0 + 1 == is) m1 += radd;
+        }
+        const double y0 = x0 == x0 ? m0 : qnan, y1 = x1 == x1 ? m1 : qnan;
+        double* out = a.cp + ((size_t)s * T + t) * N + i0;
+        if constexpr (VEC) {
+            *reinterpret_cast<double2*>(out) = double2{y0, y1};
+        } else {
+            out[0] = y0;
+            if (two) out[1] = y1;
+        }
+    }
+}
+
+// w, I and the impacts of pass replicate blockIdx.x over all T rows, column pairs of block blockIdx.y.  The covariance panel may
+// be the slice's part of weight: each cell is read before the same lane writes w there.
+template <int RB, bool VEC>
+__global__ __launch_bounds__(kNwMaxThreads) void news_impact_kernel(NwArgs a) {
+    extern __shared__ __attribute__((aligned(16))) double sgr[];
+    double* sred = sgr + (size_t)a.RC * a.r;                 // [GR][NPB][2] per-row-group sums
+    const int r = a.r, N = a.N, T = a.T, tid = threadIdx.x;
+    const int s = blockIdx.x, sb = blockIdx.y;
+    const long long j = a.j0 + s;
+    const size_t b = (size_t)(j / a.G);
+    const int gi = (int)(j % a.G);
+    const int jj = tid % a.NPB, gr = tid / a.NPB;
+    const int i0 = 2 * (sb * a.NPB + jj);
+    const bool act = gr < a.GR && i0 < N;
+    const bool two = i0 + 1 < N;
+    double l0[RB], l1[RB];
+    double ir0 = 0.0, ir1 = 0.0, sc0 = 1.0, sc1 = 1.0, mu0 = 0.0, mu1 = 0.0, sd0 = 1.0, sd1 = 1.0;
+    const bool scale = a.mean != nullptr;
+#pragma unroll
+    for (int q = 0; q < RB; ++q) { l0[q] = 0.0; l1[q] = 0.0; }
+    if (act) {
+#pragma unroll
+        for (int q = 0; q < RB; ++q) {
+            l0[q] = q < r ? a.Lam[(b * N + i0) * r + q] : 0.0;
+            l1[q] = (q < r && two) ? a.Lam[(b * N + i0 + 1) * r + q] : 0.0;
+        }
+        ir0 = a.R[b * N + i0];
+        ir1 = two ? a.R[b * N + i0 + 1] : 1.0;
+        if (scale) {
+            const double sdt = a.sd[b * N + a.tgt[2 * gi + 1]];
+            mu0 = a.mean[b * N + i0]; sd0 = a.sd[b * N + i0]; sc0 = sdt / sd0;
+            if (two) { mu1 = a.mean[b * N + i0 + 1]; sd1 = a.sd[b * N + i0 + 1]; sc1 = sdt / sd1; }
+        }
+    }
+    const double* G = a.g + (size_t)s * T * r;
+    const bool want_news = a.news != nullptr && gi == 0;
+    double acc0 = 0.0, acc1 = 0.0;
+    for (int t0 = 0; t0 < T; t0 += a.RC) {
+        const int t1 = t0 + a.RC < T ? t0 + a.RC : T;
+        for (int e = tid; e < (t1 - t0) * r; e += blockDim.x) sgr[e] = G[(size_t)t0 * r + e];
+        __syncthreads();
+        if (act)
+            for (int t = t0 + gr; t < t1; t += a.GR) {
+                const double* gt = sgr + (size_t)(t - t0) * r;
+                const size_t cb = (b * T + t) * N + i0, cs = ((size_t)s * T + t) * N + i0, cx = (b * a.TH + t) * N + i0;
+                double xn0, xn1 = 0.0, xo0, xo1 = 0.0, c0, c1 = 0.0, xr0, xr1 = 0.0;
+                if constexpr (VEC) {
+                    const double2 vn = *reinterpret_cast<const double2*>(a.newp + cb);
+                    const double2 vo = *reinterpret_cast<const double2*>(a.oldp + cb);
+                    const double2 vc = *reinterpret_cast<const double2*>(a.cp + cs);
+                    const double2 vx = *reinterpret_cast<const double2*>(a.xrev + cx);
+                    xn0 = vn.x; xn1 = vn.y; xo0 = vo.x; xo1 = vo.y; c0 = vc.x; c1 = vc.y; xr0 = vx.x; xr1 = vx.y;
+                } else {
+                    xn0 = a.newp[cb]; xo0 = a.oldp[cb]; c0 = a.cp[cs]; xr0 = a.xrev[cx];
+                    if (two) { xn1 = a.newp[cb + 1]; xo1 = a.oldp[cb + 1]; c1 = a.cp[cs + 1]; xr1 = a.xrev[cx + 1]; }
+                }
+                double m0 = 0.0, m1 = 0.0;
+#pragma unroll
+                for (int q = 0; q < RB; ++q)
+                    if (q < r) {
+                        const double v = gt[q];
+                        m0 = fma(l0[q], v, m0);
+                        m1 = fma(l1[q], v, m1);
+                    }
+                const bool on0 = xn0 == xn0, on1 = two && xn1 == xn1;
+                const double w0 = on0 ? sc0 * ((c0 - m0) / ir0) : 0.0, w1 = on1 ? sc1 * ((c1 - m1) / ir1) : 0.0;
+                const double n0 = (on0 && xo0 != xo0) ? (scale ? mu0 + sd0 * xn0 : xn0) - xr0 : 0.0;
+                const double n1 = (on1 && xo1 != xo1) ? (scale ? mu1 + sd1 * xn1 : xn1) - xr1 : 0.0;
+                acc0 = fma(w0, n0, acc0);
+                acc1 = fma(w1, n1, acc1);
+                if (a.weight) {
+                    double* pw = a.weight + ((size_t)j * T + t) * N + i0;
+                    if constexpr (VEC) *reinterpret_cast<double2*>(pw) = double2{w0, w1};
+                    else { pw[0] = w0; if (two) pw[1] = w1; }
+                }
+                if (want_news) {
+                    double* pn = a.news + cb;
+                    if constexpr (VEC) *reinterpret_cast<double2*>(pn) = double2{n0, n1};
+                    else { pn[0] = n0; if (two) pn[1] = n1; }
+                }
+            }
+        __syncthreads();
+    }
+    if (act) {
+        sred[((size_t)gr * a.NPB + jj) * 2] = acc0;
+        sred[((size_t)gr * a.NPB + jj) * 2 + 1] = acc1;
+    }
+    __syncthreads();
+    if (act && gr == 0) {
+        double s0 = 0.0, s1 = 0.0;
+        for (int q = 0; q < a.GR; ++q) {
+            s0 += sred[((size_t)q * a.NPB + jj) * 2];
+            s1 += sred[((size_t)q * a.NPB + jj) * 2 + 1];
+        }
+        a.impact[(size_t)j * N + i0] = s0;
+        if (two) a.impact[(size_t)j * N + i0 + 1] = s1;
+    }
+}
+
+hipError_t launch_news_revise(const NwArgs& a, hipStream_t s) {
+    const size_t n = (size_t)a.B * a.T * a.N;
+    size_t blocks = (n + 255) / 256;
+    if (blocks > 8192) blocks = 8192;
+    hipLaunchKernelGGL(news_revise_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_news_gather(const NwArgs& a, const double* xhat, int which, hipStream_t s) {
+    const int n = a.B * a.G;
+    hipLaunchKernelGGL(news_gather_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a, xhat, which);
+    return hipGetLastError();
+}
+
+hipError_t launch_news_gamma(const NwArgs& a, hipStream_t s) {
+    const int k = a.r * a.p;
+    if (k < 1 || k > 32 || a.S < 1) return hipErrorInvalidValue;
+    // k > 8: four waves, one element of Gamma per lane at k = 16 (one wave with four elements per lane measured slower: 5.1 against
+    // 4.0 ms at k = 16, T = 222, 4096 pass replicates)
+    if (k <= 8) hipLaunchKernelGGL((news_gamma_kernel<8, 64>), dim3((unsigned)a.S), dim3(64), 0, s, a);
+    else if (k <= 16) hipLaunchKernelGGL((news_gamma_kernel<16, 256>), dim3((unsigned)a.S), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((news_gamma_kernel<32, 256>), dim3((unsigned)a.S), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+// Column pairs per workgroup (NPB), rows per pass over them (GR) and per LDS chunk (RC): GR x NPB lanes rounded up to whole
+// waves, GR chosen so that the fewest lanes idle (N = 200: 5 x 100 of 512) -- the geometry of simsmooth.hip's cell kernels.
+static int nw_geometry(NwArgs& a, int& threads) {
+    const int npair = (a.N + 1) / 2;
+    a.nsblk = (npair + 255) / 256;
+    a.NPB = (npair + a.nsblk - 1) / a.nsblk;
+    int best_g = 1;
+    double best = -1.0;
+    for (int g = 1; g * a.NPB <= kNwMaxThreads; ++g) {
+        const int th = (g * a.NPB + 63) / 64 * 64;
+        if (th > kNwMaxThreads) break;
+        const double eff = (double)(g * a.NPB) / th;
+        if (eff > best + 1e-9) { best = eff; best_g = g; }
+    }
+    a.GR = best_g;
+    threads = (a.GR * a.NPB + 63) / 64 * 64;
+    int rc = a.GR * 8;
+    const int cap = (int)(kNwLds / ((size_t)a.r * sizeof(double)));
+    if (rc > cap) rc = cap;
+    if (rc > a.T) rc = a.T;
+    if (rc < 1) rc = 1;
+    a.RC = rc;
+    a.nchunk = (a.T + rc - 1) / rc;
+    return a.nchunk <= 65535 && a.nsblk <= 65535 ? 0 : -1;
+}
+
+static bool al16(const void* q) { return ((uintptr_t)q & 15) == 0; }
+
+template <int RB>
+static hipError_t launch_cov_rb(const NwArgs& a, int threads, bool vec, hipStream_t s) {
+    const dim3 grid((unsigned)a.S, (unsigned)a.nchunk, (unsigned)a.nsblk);
+    const size_t lds = (size_t)a.RC * a.r * sizeof(double);
+    if (vec) hipLaunchKernelGGL((news_cov_panel_kernel<RB, true>), grid, dim3(threads), lds, s, a);
+    else hipLaunchKernelGGL((news_cov_panel_kernel<RB, false>), grid, dim3(threads), lds, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_news_cov_panel(NwArgs a, hipStream_t s) {
+    if (a.r < 1 || a.r > 32 || a.S < 1) return hipErrorInvalidValue;
+    int threads = 0;
+    if (nw_geometry(a, threads)) return hipErrorInvalidValue;
+    const bool vec = (a.N & 1) == 0 && al16(a.newp) && al16(a.cp);
+    if (a.r <= 4) return launch_cov_rb<4>(a, threads, vec, s);
+    if (a.r <= 8) return launch_cov_rb<8>(a, threads, vec, s);
+    if (a.r <= 16) return launch_cov_rb<16>(a, threads, vec, s);
+    return launch_cov_rb<32>(a, threads, vec, s);
+}
+
+template <int RB>
+static hipError_t launch_impact_rb(const NwArgs& a, int threads, bool vec, hipStream_t s) {
+    const dim3 grid((unsigned)a.S, (unsigned)a.nsblk);
+    const size_t lds = ((size_t)a.RC * a.r + (size_t)2 * a.GR * a.NPB) * sizeof(double);
+    if (vec) hipLaunchKernelGGL((news_impact_kernel<RB, true>), grid, dim3(threads), lds, s, a);
+    else hipLaunchKernelGGL((news_impact_kernel<RB, false>), grid, dim3(threads), lds, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_news_impact(NwArgs a, hipStream_t s) {
+    if (a.r < 1 || a.r > 32 || a.S < 1) return hipErrorInvalidValue;
+    int threads = 0;
+    if (nw_geometry(a, threads)) return hipErrorInvalidValue;
+    const bool vec = (a.N & 1) == 0 && al16(a.newp) && al16(a.oldp) && al16(a.cp) && al16(a.xrev) &&
+                     (a.weight == nullptr || al16(a.weight)) && (a.news == nullptr || al16(a.news));
+    if (a.r <= 4) return launch_impact_rb<4>(a, threads, vec, s);
+    if (a.r <= 8) return launch_impact_rb<8>(a, threads, vec, s);
+    if (a.r <= 16) return launch_impact_rb<16>(a, threads, vec, s);
+    return launch_impact_rb<32>(a, threads, vec, s);
+}
+
+}  // namespace dfm

@@ -627,6 +627,81 @@ class DfmContext:
         _check(self._h, rc)
         return dict(f=f, x=x)
 
+    # ------------------------------------------------------------------ news decomposition of nowcast revisions (news.hip)
+    @staticmethod
+    def _targets(targets, T, N):
+        tg = np.ascontiguousarray(np.asarray(targets, dtype=np.int64).reshape(-1, 2))
+        if tg.shape[0] < 1:
+            raise ValueError("at least one target is needed")
+        if np.any(tg[:, 0] < 0) or np.any(tg[:, 1] < 0) or np.any(tg[:, 1] >= N):
+            raise ValueError("targets are (row t* >= 0, column 0 <= i* < N) pairs")
+        return np.ascontiguousarray(tg[:, 0], dtype=np.int32), np.ascontiguousarray(tg[:, 1], dtype=np.int32)
+
+    def news_batch(self, old, new, Lam, R, Avar, Q, mu0, P0, targets, mean=None, sd=None, want_news: bool = True,
+                   want_weight: bool = True, may_have_missing: Optional[bool] = None, singular_q: bool = False):
+        """dfm_news_batch_dev (device tensors, torch's current stream): the news decomposition of the revision of G target cells
+        between two vintages old / new [B,T,N] (include/dfm_hip.h).  targets: G (row t*, column i*) pairs, 0-based, host side;
+        Avar [B,r,r p], Q [B,r,r], mu0 [B,r p], P0 [B,r p,r p]; mean / sd [B,N] (both or neither) put the outputs into data
+        units.  Returns dict(yhat [B,3,G] (old, revised, new), impact [B,G,N], news [B,T,N] or None, weight [B,G,T,N] or None);
+        the status word (DFM_E_VINTAGE) is read by synchronize()."""
+        torch = self._torch
+        B, T, N = new.shape
+        r = Lam.shape[2]
+        k = Avar.shape[2]
+        p = k // r
+        if tuple(old.shape) != (B, T, N):
+            raise ValueError("old and new must have the same shape")
+        if (mean is None) != (sd is None):
+            raise ValueError("mean and sd go together")
+        tt, ti = self._targets(targets, T, N)
+        G = tt.size
+        flags = self._flags(new, may_have_missing, singular_q)
+        dev = new.device
+        yhat = torch.empty((B, 3, G), dtype=torch.float64, device=dev)
+        impact = torch.empty((B, G, N), dtype=torch.float64, device=dev)
+        news = torch.empty((B, T, N), dtype=torch.float64, device=dev) if want_news else None
+        weight = torch.empty((B, G, T, N), dtype=torch.float64, device=dev) if want_weight else None
+        opt = lambda t, name, shape=None: None if t is None else self._dev(t, name, shape)
+        hp = lambda a: ctypes.c_void_p(a.ctypes.data)
+        self._sync_stream()
+        rc = self._lib.dfm_news_batch_dev(
+            self._h, B, T, N, r, p, self._dev(old, "old"), self._dev(new, "new"), self._dev(Lam, "Lam", (B, N, r)),
+            self._dev(R, "R", (B, N)), self._dev(Avar, "Avar", (B, r, r * p)), self._dev(Q, "Q", (B, r, r)),
+            self._dev(mu0, "mu0", (B, k)), self._dev(P0, "P0", (B, k, k)), opt(mean, "mean", (B, N)), opt(sd, "sd", (B, N)),
+            G, hp(tt), hp(ti), self._dev(yhat, "yhat"), self._dev(impact, "impact"), opt(news, "news"), opt(weight, "weight"),
+            flags)
+        _check(self._h, rc)
+        return dict(yhat=yhat, impact=impact, news=news, weight=weight)
+
+    def news_batch_host(self, old, new, Lam, R, Avar, Q, mu0, P0, targets, mean=None, sd=None, want_news: bool = True,
+                        want_weight: bool = True, may_have_missing: Optional[bool] = None, singular_q: bool = False):
+        """dfm_news_batch (host pointers; what Julia's ccall binds): NumPy in / out, same dict as news_batch."""
+        c = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+        old, new, Lam, R, Avar, Q, mu0, P0 = map(c, (old, new, Lam, R, Avar, Q, mu0, P0))
+        if (mean is None) != (sd is None):
+            raise ValueError("mean and sd go together")
+        mean = None if mean is None else c(mean)
+        sd = None if sd is None else c(sd)
+        B, T, N = new.shape
+        if old.shape != new.shape:
+            raise ValueError("old and new must have the same shape")
+        r = Lam.shape[2]
+        p_lag = Avar.shape[2] // r
+        tt, ti = self._targets(targets, T, N)
+        G = tt.size
+        if may_have_missing is None:
+            may_have_missing = bool(np.isnan(new).any())
+        flags = (_lib.DFM_F_MAY_HAVE_MISSING if may_have_missing else 0) | (_lib.DFM_F_SINGULAR_Q if singular_q else 0)
+        yhat = np.empty((B, 3, G))
+        impact = np.empty((B, G, N))
+        news = np.empty((B, T, N)) if want_news else None
+        weight = np.empty((B, G, T, N)) if want_weight else None
+        p = lambda a: None if a is None else ctypes.c_void_p(a.ctypes.data)
+        rc = self._lib.dfm_news_batch(self._h, B, T, N, r, p_lag, p(old), p(new), p(Lam), p(R), p(Avar), p(Q), p(mu0), p(P0),
+                                      p(mean), p(sd), G, p(tt), p(ti), p(yhat), p(impact), p(news), p(weight), flags)
+        _check(self._h, rc)
+        return dict(yhat=yhat, impact=impact, news=news, weight=weight)
+
     # ------------------------------------------------------------------ AR idiosyncratic terms (quasi-differencing)
     def ks_pass_ar_batch(self, panel, Lam, sig2, rho, Avar, Q, mu0, P0, want_P: bool = True,
                          may_have_missing: Optional[bool] = None, singular_q: bool = False):

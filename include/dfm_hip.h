@@ -46,7 +46,8 @@ enum {
     DFM_E_MISSING = -4,       /* NaN found in the panel but DFM_F_MAY_HAVE_MISSING not set */
     DFM_E_NUMERIC = -5,       /* non-finite log-likelihood in some replicate (non-PD Q/P0/...) */
     DFM_E_NO_DEVICE = -6,     /* no HIP device / extension not usable */
-    DFM_E_COMM = -7           /* multi-GPU entry points: RCCL could not be loaded or a collective failed */
+    DFM_E_COMM = -7,          /* multi-GPU entry points: RCCL could not be loaded or a collective failed */
+    DFM_E_VINTAGE = -8        /* dfm_news_batch: a cell observed in the old vintage is missing in the new one */
 };
 
 /* flags */
@@ -300,6 +301,43 @@ int dfm_simsmooth_batch(dfm_handle* h, int B, int D, int T, int N, int r, int p,
                         const double* Lam, const double* R, const double* Avar, const double* Q,
                         const double* mu0, const double* P0, const double* mean, const double* sd,
                         uint64_t seed, int64_t first_draw, double* f_draw, double* x_draw, unsigned flags);
+
+/* --- news decomposition of nowcast revisions (Banbura and Modugno 2014) -------------------------------------------------------
+ * The model and conventions of dfm_forecast_batch; two vintages old / new [B][T][N] of the same standardised panel (a period the
+ * old vintage did not have is all-NaN there).  Omega_old, Omega_new = their observed cells; Omega_old must be a subset of
+ * Omega_new.  Targets g = 0 .. G-1: cells (target_t[g], target_i[g]), 0 <= t* < T + H, 0 <= i* < N, shared by every replicate; H
+ * = max(0, max t* + 1 - T) is derived from them.  A target is y = E[x_t*i* | Omega] in data units (xhat of dfm_forecast_batch):
+ *   yhat[b][0][g] = y conditioned on old, yhat[b][1][g] on the REVISED old panel (new values on Omega_old, NaN elsewhere),
+ *   yhat[b][2][g] on new; yhat[1] - yhat[0] is the data-revision effect                                         [B][3][G]
+ *   news[b][t][i]  = I_ti = x_new_ti - E[x_ti | revised old] (data units) on the news cells Omega_new \ Omega_old, 0 elsewhere
+ *                                                                                                    (may be NULL) [B][T][N]
+ *   weight[b][g][t][i] = w = d y_new / d x_ti on Omega_new (data units: sd_i* / sd_i times the standardised weight), 0 on its
+ *                    missing cells; restricted to the news cells these are the news weights Cov(y, I) Var(I)^-1  (may be NULL)
+ *                                                                                                                [B][G][T][N]
+ *   impact[b][g][i] = sum over the news cells of series i of w I; sum_i impact = yhat[2] - yhat[1] exactly    [B][G][N]
+ * The weights come from one smoother pass per (b, g) instead of one per news cell: with Sigma = Var(z on Omega_new) and
+ * c = Cov(z_Omega_new, y_z), w = Sigma^-1 c, and x - Lam E_0[f | x] = R Sigma^-1 x (E_0: prior mean 0).  So c is written as a
+ * panel on the Omega_new mask (c_ti = lam_i' Cov(f_t+1, f_t*+1) lam_i*, plus R_i* on the target cell when it is observed), the
+ * pass of dfm_ks_pass_batch (p = 1) / dfm_ks_pass_varp_batch runs on it with mu0 = 0 and the caller's flags, and
+ * w_ti = (sd_i* / sd_i) (c_ti - lam_i' g_t) / R_i.  Inputs as dfm_forecast_batch; target_t / target_i [G] are HOST arrays in
+ * both entries (the horizon and the scratch depend on them).  Flags as the pass: the new panel and the covariance panels run
+ * with the caller's flags (a NaN in new without DFM_F_MAY_HAVE_MISSING: DFM_E_MISSING), the old and revised old panels always
+ * with DFM_F_MAY_HAVE_MISSING.  Status: G < 1 or a target outside [0, T + H) x [0, N): DFM_E_DIMS; a NULL required pointer,
+ * mean without sd or sd without mean: DFM_E_NULL; Omega_old not a subset of Omega_new: DFM_E_VINTAGE (a status-word bit: the
+ * host entry reports it, dfm_check_status after the "_dev" entry); a shape the pass refuses: its status; a non-finite pass:
+ * DFM_E_NUMERIC (host entry).  Outputs must not overlap the inputs.  Allocates in the handle (kept for the next call): the
+ * revised old panel and one forecast's [B][T+H][N] xhat, and per slice of at most 8192 pass replicates the pass parameters,
+ * [S][T][r p] + 2 [S][T][r] vectors and (weight NULL) the [S][T][N] covariance panels; with weight they live in the slice's
+ * part of weight, which the impacts overwrite.  Out of scope: re-estimation between vintages (one parameter set), a per-cell
+ * split of the data-revision effect. */
+int dfm_news_batch_dev(dfm_handle* h, int B, int T, int N, int r, int p, const double* old_panel, const double* new_panel,
+                       const double* Lam, const double* R, const double* Avar, const double* Q, const double* mu0,
+                       const double* P0, const double* mean, const double* sd, int G, const int* target_t,
+                       const int* target_i, double* yhat, double* impact, double* news, double* weight, unsigned flags);
+int dfm_news_batch(dfm_handle* h, int B, int T, int N, int r, int p, const double* old_panel, const double* new_panel,
+                   const double* Lam, const double* R, const double* Avar, const double* Q, const double* mu0,
+                   const double* P0, const double* mean, const double* sd, int G, const int* target_t,
+                   const int* target_i, double* yhat, double* impact, double* news, double* weight, unsigned flags);
 
 /* --- AR idiosyncratic terms --------------------------------------------------------
  *   x_it = lam_i' f_t + e_it,   e_it = rho_i1 e_i,t-1 + .. + rho_iq e_i,t-q + eps_it,  eps_it ~ N(0, sig2_i)

@@ -365,6 +365,35 @@ function draw_paths(h::Handle, z::Matrix{Float64}, params, ndraws::Integer, H::I
     return (factor = permutedims(f, (3, 2, 1)), x = permutedims(x, (3, 2, 1)))
 end
 
+"News decomposition of the revision of G target cells between two vintages (dfm_news_batch; include/dfm_hip.h): zold / znew
+are T x N (NaN = missing, standardised; every cell of zold observed in znew), params, nlag, mean / sd as `forecast`; targets =
+G (row, column) pairs, 1-based, rows past T are forecasts.  Returns yhat (3 x G: old, revised old, new), impact (G x N), news
+(T x N) and weight (G x T x N), in data units with mean / sd."
+function news(h::Handle, zold::Matrix{Float64}, znew::Matrix{Float64}, params, targets; nlag::Integer = 1, mean = nothing,
+              sd = nothing, singular_q::Bool = false)
+    (mean === nothing) == (sd === nothing) || error("mean and sd go together")
+    size(zold) == size(znew) || error("zold and znew must have the same size")
+    T, N = size(znew); r = size(params.Lam, 2); G = length(targets)
+    Av = hasproperty(params, :Avar) ? params.Avar : params.A
+    po = to_c_panel(zold); pn = to_c_panel(znew)
+    Lam = permutedims(params.Lam); R = copy(params.R); AC = permutedims(Av); QC = permutedims(params.Q)
+    mu0 = copy(params.mu0); P0C = permutedims(params.P0)
+    meanC = mean === nothing ? C_NULL : Vector{Float64}(mean); sdC = sd === nothing ? C_NULL : Vector{Float64}(sd)
+    tt = Cint[t - 1 for (t, _) in targets]; ti = Cint[i - 1 for (_, i) in targets]
+    yhat = Array{Float64}(undef, G, 3); impact = Array{Float64}(undef, N, G); nw = Array{Float64}(undef, N, T)
+    w = Array{Float64}(undef, N, T, G)
+    flags = (any(isnan, znew) ? DFM_F_MAY_HAVE_MISSING : Cuint(0)) | (singular_q ? DFM_F_SINGULAR_Q : Cuint(0))
+    GC.@preserve po pn Lam R AC QC mu0 P0C meanC sdC tt ti yhat impact nw w begin
+        rc = ccall((:dfm_news_batch, LIB), Cint,
+                   (Ptr{Cvoid}, Cint, Cint, Cint, Cint, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                    Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cint, Ptr{Cint},
+                    Ptr{Cint}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cuint),
+                   h.ptr, 1, T, N, r, nlag, po, pn, Lam, R, AC, QC, mu0, P0C, meanC, sdC, G, tt, ti, yhat, impact, nw, w, flags)
+        check(h.ptr, rc)
+    end
+    return (yhat = permutedims(yhat), impact = permutedims(impact), news = permutedims(nw), weight = permutedims(w, (3, 2, 1)))
+end
+
 "Smoother pass with AR(q) idiosyncratic terms (dfm_ks_pass_ar_batch; include/dfm_hip.h): x is T x N (NaN = missing, in
 deviations from its intercept), Lam N x r, sig2 = uar_ser.^2, rho = uar_coef (N x q), Avar r x (r p), Q r x r, mu0 / P0
 the moments of z_q, r max(p, q+1) wide.  Returns the smoothed factors of rows q+1..T and the conditional log-likelihood."
