@@ -44,6 +44,8 @@ _SS_ARGS = [c_vp] + [c_int] * 7 + [c_vp] * 9 + [ctypes.c_uint64, ctypes.c_int64,
 _NW_ARGS = [c_vp] + [c_int] * 5 + [c_vp] * 10 + [c_int] + [c_vp] * 6 + [c_uint]
 _ARPASS_ARGS = [c_vp, c_int, c_int, c_int, c_int, c_int, c_int] + [c_vp] * 11 + [c_uint]
 _AREM_ARGS = [c_vp, c_int, c_int, c_int, c_int, c_int, c_int] + [c_vp] * 8 + [c_int, ctypes.c_double] + [c_vp] * 4 + [c_uint]
+_MFPASS_ARGS = [c_vp, c_int, c_int, c_int, c_int, c_int, c_int] + [c_vp] * 11 + [c_uint]
+_MFEM_ARGS = [c_vp, c_int, c_int, c_int, c_int, c_int, c_int] + [c_vp] * 8 + [c_int, ctypes.c_double] + [c_vp] * 4 + [c_uint]
 _OBSEM_ARGS = [c_vp, c_int, c_int, c_int, c_int, c_int] + [c_vp] * 8 + [c_int, ctypes.c_double] + [c_vp] * 4 + [c_uint]
 _PCA_ARGS = [c_vp, c_int, c_int, c_int, c_int] + [c_vp] * 8
 c_ll = ctypes.c_longlong
@@ -100,6 +102,10 @@ SYMBOLS = {
     "dfm_ks_pass_ar_batch": (c_int, _ARPASS_ARGS),
     "dfm_em_ar_batch_dev": (c_int, _AREM_ARGS),
     "dfm_em_ar_batch": (c_int, _AREM_ARGS),
+    "dfm_ks_pass_mf_batch_dev": (c_int, _MFPASS_ARGS),
+    "dfm_ks_pass_mf_batch": (c_int, _MFPASS_ARGS),
+    "dfm_em_mf_batch_dev": (c_int, _MFEM_ARGS),
+    "dfm_em_mf_batch": (c_int, _MFEM_ARGS),
     "dfm_em_obs_batch_dev": (c_int, _OBSEM_ARGS),
     "dfm_em_obs_batch": (c_int, _OBSEM_ARGS),
     "dfm_pca_init_batch_dev": (c_int, _PCA_ARGS),

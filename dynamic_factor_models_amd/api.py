@@ -689,6 +689,181 @@ def news(m: DFMModel, old, new, targets, *, groups=None, quantiles=None, ctx=Non
 # -> estimate_var!, with every regression run by the batched HIP kernels of als.hip (dfm_als_batch /
 # dfm_ols_batch) and the PCA start by pca.hip.  The host code below is what the reference's Julia host code is:
 # slicing, standardising, building lag matrices, copying results into the model object.
+# ----------------------------------------------------------------------------- mixed frequency: monthly factors, quarterly series
+MF_WEIGHTS = {"m": (1.0,), "q_flow": (1 / 3, 2 / 3, 1.0, 2 / 3, 1 / 3), "q_avg": (1 / 3, 1 / 3, 1 / 3)}
+
+
+def mf_weights(weights, N: int) -> np.ndarray:
+    """[N][L] aggregation weights from the array itself or from a list of "m" (monthly), "q_flow" (quarterly growth rate,
+    Mariano-Murasawa (1, 2, 3, 2, 1) / 3) and "q_avg" (quarterly mean of a monthly level, (1, 1, 1) / 3)."""
+    if len(weights) and isinstance(weights[0], str):
+        unknown = sorted(set(weights) - set(MF_WEIGHTS))
+        if unknown:
+            raise ValueError(f"unknown weight pattern {unknown}: use 'm', 'q_flow', 'q_avg' or an [N][L] array")
+        W = np.zeros((len(weights), max(len(MF_WEIGHTS[k]) for k in weights)))
+        for i, k in enumerate(weights):
+            W[i, :len(MF_WEIGHTS[k])] = MF_WEIGHTS[k]
+    else:
+        W = np.array(weights, dtype=np.float64, ndmin=2)
+    if W.shape[0] != N:
+        raise ValueError(f"weights: {W.shape[0]} rows for {N} series")
+    return np.ascontiguousarray(W)
+
+
+def _mf_expanded(Lam, W, Avar, Q):
+    """The mixed-frequency model as a plain p = 1 model on the companion state: (LamK [N, k], M [k, k], Qk [k, k]), k = r max(p, L)."""
+    N, r = Lam.shape
+    L = W.shape[1]
+    p = Avar.shape[1] // r
+    m = max(p, L)
+    k = r * m
+    LamK = np.zeros((N, m, r))
+    LamK[:, :L] = W[:, :, None] * Lam[:, None, :]
+    M = np.zeros((k, k))
+    M[:r, :r * p] = Avar
+    M[r:, :k - r] = np.eye(k - r)
+    Qk = np.zeros((k, k))
+    Qk[:r, :r] = Q
+    return LamK.reshape(N, k), M, Qk
+
+
+def _mf_start(ctx, z, W, r, p):
+    """Start of the EM: PCA factors of the fully observed MONTHLY series (pca_start), every series' loadings by a regression on
+    the aggregated PCA factors over its observed cells, VAR(p) by OLS, P0 = the stacked lags' second moment."""
+    T, N = z.shape
+    L = W.shape[1]
+    m = max(p, L)
+    monthly = (W[:, 0] == 1.0) & np.all(W[:, 1:] == 0.0, axis=1)
+    if not monthly.any():
+        raise ValueError("no monthly series (weights (1, 0, ..)): nothing to start the factors from")
+    F = pca_start(ctx, z[:, monthly], r)
+    Flag = np.stack([np.vstack([np.zeros((l, r)), F[:T - l]]) for l in range(L)])       # [L, T, r]: f_{t-l}
+    Lam = np.zeros((N, r)); R = np.ones(N)
+    for i in range(N):
+        g = np.tensordot(W[i], Flag, axes=1)
+        o = ~np.isnan(z[:, i]); o[:L - 1] = False
+        if o.sum() < r + 1:
+            continue
+        Lam[i] = np.linalg.lstsq(g[o], z[o, i], rcond=None)[0]
+        R[i] = max(np.mean((z[o, i] - g[o] @ Lam[i]) ** 2), 0.05)
+    Z = np.hstack([F[p - 1 - l:T - l] for l in range(p)])
+    Y, Xl = F[p:], Z[:-1]
+    Avar = np.linalg.solve(Xl.T @ Xl, Xl.T @ Y).T
+    e = Y - Xl @ Avar.T
+    Q = e.T @ e / (T - p)
+    Zm = np.hstack([F[m - 1 - l:T - l] for l in range(m)])
+    P0 = Zm.T @ Zm / Zm.shape[0] + 1e-3 * np.eye(r * m)
+    return dict(Lam=Lam, R=R, Avar=Avar, Q=0.5 * (Q + Q.T), mu0=np.zeros(r * m), P0=0.5 * (P0 + P0.T))
+
+
+def estimate_mixed_frequency(x, weights, r: int, p: int, *, max_em_iter: int = 50, tol_em: float = 1e-6, nrep: int = 0,
+                             seed: int = 20160415, ctx=None) -> dict:
+    """Maximum likelihood of the mixed-frequency DFM by EM (include/dfm_hip.h: dfm_em_mf_batch): monthly factors f_t with
+    VAR(p) dynamics, series i loading on sum_l w_il f_{t-l}.
+
+    x [T, N] is the MONTHLY panel in data units: a quarterly series sits in the third month of each quarter and is NaN elsewhere.
+    `weights`: the [N][L] array, or a list of "m" / "q_flow" / "q_avg" (mf_weights).  Every series is standardised with its own
+    mean and population s.d. over its observed cells (standardize_data).  Start: `_mf_start`.  Returns a dict: Lam [N, r], R [N],
+    Avar [r, r p], Q, mu0, P0 (standardised units), W, mean, sd, loglik_path (NaN past convergence), iters, f_smooth [T, r],
+    start (the parameters the EM started from); with nrep > 0 also `replicates`: parametric-bootstrap panels drawn from the fit
+    with the panel's missing pattern and re-estimated from the point estimate in ONE batched call (params, loglik_path, iters)."""
+    from ._lib import DfmError
+    x = np.asarray(x, dtype=np.float64)
+    T, N = x.shape
+    W = mf_weights(weights, N)
+    n = np.count_nonzero(~np.isnan(x), axis=0)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mu = np.nansum(x, axis=0) / n
+    z, sd = standardize_data(x)
+    sd = np.asarray(sd).reshape(N)
+    ctx, own = _own(ctx)
+    try:
+        start = _mf_start(ctx, z, W, int(r), int(p))
+        keys = ("Lam", "R", "Avar", "Q", "mu0", "P0")
+
+        def run(panels, st, **kw):
+            args = [panels, st["Lam"], st["R"], W, st["Avar"], st["Q"], st["mu0"], st["P0"]]
+            try:
+                return ctx.em_mf_batch_host(*args, max_iter=max_em_iter, tol=tol_em, may_have_missing=True, **kw)
+            except DfmError as err:                 # the information form inverts Q: as estimate(), retry in covariance form
+                if err.code != -5:
+                    raise
+                return ctx.em_mf_batch_host(*args, max_iter=max_em_iter, tol=tol_em, may_have_missing=True, singular_q=True, **kw)
+        est, path, iters, f, _ = run(z[None], {k: start[k][None] for k in keys})
+        out = {k: est[k][0] for k in keys}
+        out.update(W=W, mean=mu, sd=sd, loglik_path=path[0], iters=int(iters[0]), f_smooth=f[0], start=start)
+        if nrep > 0:
+            LamK, M, Qk = _mf_expanded(out["Lam"], W, out["Avar"], out["Q"])
+            k = M.shape[0]
+            rng = np.random.default_rng(seed)
+            LQ, LS, sq = _psd_sqrt(Qk), _psd_sqrt(out["P0"]), np.sqrt(out["R"])
+            panels = np.empty((nrep, T, N))
+            for b in range(nrep):
+                s = out["mu0"] + LS @ rng.standard_normal(k)
+                for t in range(T):
+                    s = M @ s + LQ @ rng.standard_normal(k)
+                    panels[b, t] = LamK @ s + sq * rng.standard_normal(N)
+            panels[:, np.isnan(z)] = np.nan
+            rest, rpath, riters, _, _ = run(panels, {k: np.repeat(out[k][None], nrep, axis=0) for k in keys})
+            out["replicates"] = dict(params=rest, loglik_path=rpath, iters=riters)
+    finally:
+        if own:
+            ctx.close()
+    return out
+
+
+def forecast_mixed(fit: dict, x, H: int, quantiles=None, *, ctx=None) -> dict:
+    """Nowcasts and H-step forecasts of every cell of a mixed-frequency panel, quarterly series included, in data units.
+
+    `fit` is what estimate_mixed_frequency returned; x [T, N] the monthly panel to condition on (the fit's own, or a later
+    vintage with a longer ragged edge).  The expanded model -- loadings N x k, companion transition, [Q 0; 0 0] -- is a plain
+    p = 1 model with k = r max(p, L) factors, so this is ONE dfm_forecast_batch call in covariance form; a shape that entry
+    refuses raises its status unchanged.  Returns a dict: x [T + H, N] (observed cells as they are, every other cell -- the
+    months a quarterly series is not published in, too -- E[x_ti | X]), x_sd (0 on observed cells), common, factor [T + H, r],
+    loglik.  `quantiles` (needs fit["replicates"], H >= 1): bands [nq, H, N] over the replicates' point forecasts."""
+    H = int(H)
+    if H < 0:
+        raise ValueError("H must be >= 0")
+    x = np.asarray(x, dtype=np.float64)
+    W, mu, sd = fit["W"], fit["mean"], fit["sd"]
+    r = fit["Lam"].shape[1]
+    if x.ndim != 2 or x.shape[1] != W.shape[0]:
+        raise ValueError("x must be [T, N] with the fit's series")
+    qs = None
+    if quantiles is not None:
+        qs = np.atleast_1d(np.asarray(quantiles, dtype=np.float64))
+        if fit.get("replicates") is None:
+            raise ValueError("quantile bands need bootstrap replicates: estimate_mixed_frequency(..., nrep=...) first")
+        if H < 1:
+            raise ValueError("quantile bands need H >= 1")
+        if qs.size < 1 or not np.all((qs > 0.0) & (qs <= 1.0)):
+            raise ValueError("quantiles must lie in (0, 1]")
+    z = (x - mu) / sd
+    ctx, own = _own(ctx)
+    try:
+        def run(ps, **kw):
+            B = ps["Lam"].shape[0]
+            ex = [_mf_expanded(ps["Lam"][b], W, ps["Avar"][b], ps["Q"][b]) for b in range(B)]
+            rep = lambda a: np.ascontiguousarray(np.broadcast_to(a, (B,) + a.shape))
+            return ctx.forecast_batch_host(rep(z), np.stack([e[0] for e in ex]), ps["R"], np.stack([e[1] for e in ex]),
+                                           np.stack([e[2] for e in ex]), ps["mu0"], ps["P0"], H, mean=rep(mu), sd=rep(sd),
+                                           may_have_missing=True, singular_q=True, **kw)
+        o = run({k: fit[k][None] for k in ("Lam", "R", "Avar", "Q", "mu0", "P0")}, want_P=False)
+        bands = None
+        if qs is not None:
+            ob = run(fit["replicates"]["params"], want_var=False, want_common=False, want_P=False)
+            bands = ctx.quantile_bands_host(ob["xhat"][:, -H:, :], qs)
+    finally:
+        if own:
+            ctx.close()
+    out = dict(x=o["xhat"][0], x_sd=np.sqrt(o["xvar"][0]), common=o["common"][0], factor=o["f"][0][:, :r],
+               loglik=float(o["loglik"][0]))
+    if bands is not None:
+        out["quantiles"] = qs
+        out["bands"] = bands
+    return out
+
+
 def _lagmat(X: np.ndarray, lags) -> np.ndarray:
     """dfm_functions.ipynb:295-303."""
     X = X.reshape(X.shape[0], -1)

@@ -88,11 +88,11 @@ struct dfm_handle {
 };
 
 enum KernelId { K_COLLAPSE = 0, K_RECURSION, K_MSTEP_STATS, K_MSTEP_SOLVE, K_PCA, K_SYNTH, K_PAD,
-                K_COLLAPSE_DMA, K_GRAM, K_COV, K_MEANSCAN, K_PFILL, K_COLLAPSE_MFMA, K_ALS, K_OLS, K_BOOT, K_QUANT, K_COLLAPSE_WIDE, K_EM_UPDATE, K_CHOW, K_MSTEP_MFMA, K_GRAM_XX, K_PASS_FUSED, K_FC_TAIL, K_FC_FILL, K_FC_PAD, K_SS_PREP, K_SS_EXPAND, K_SS_PATH, K_SS_DIFF, K_SS_FINISH, K_SS_FILL, K_NW_REVISE, K_NW_GATHER, K_NW_GAMMA, K_NW_COV, K_NW_IMPACT, K_COUNT };
+                K_COLLAPSE_DMA, K_GRAM, K_COV, K_MEANSCAN, K_PFILL, K_COLLAPSE_MFMA, K_ALS, K_OLS, K_BOOT, K_QUANT, K_COLLAPSE_WIDE, K_EM_UPDATE, K_CHOW, K_MSTEP_MFMA, K_GRAM_XX, K_PASS_FUSED, K_FC_TAIL, K_FC_FILL, K_FC_PAD, K_SS_PREP, K_SS_EXPAND, K_SS_PATH, K_SS_DIFF, K_SS_FINISH, K_SS_FILL, K_NW_REVISE, K_NW_GATHER, K_NW_GAMMA, K_NW_COV, K_NW_IMPACT, K_MF_TABLE, K_MF_MOMENTS, K_MF_SOLVE, K_COUNT };
 static const char* const kKernelNames[K_COUNT] = {"collapse_kernel", "recursion_kernel", "mstep_lam_kernel",
                                                   "mstep_solve_kernel", "pca_kernel", "synth_kernel",
                                                   "pad_params_kernel", "collapse_dma_kernel", "gram_kernel",
-                                                  "cov_kernel", "meanscan_kernel", "pfill_kernel", "collapse_mfma_kernel", "als_kernel", "ols_kernel", "var_boot_kernel", "quantile_kernel", "collapse_wide_kernel", "em_update_kernel", "chow_kernel", "mstep_mfma_kernel", "gram_xx_kernel", "pass_fused_kernel", "forecast_tail_kernel", "forecast_fill_kernel", "forecast_pad_kernel", "simsmooth_prep_kernel", "simsmooth_expand_kernel", "simsmooth_path_kernel", "simsmooth_diff_kernel", "simsmooth_finish_kernel", "simsmooth_fill_kernel", "news_revise_kernel", "news_gather_kernel", "news_gamma_kernel", "news_cov_panel_kernel", "news_impact_kernel"};
+                                                  "cov_kernel", "meanscan_kernel", "pfill_kernel", "collapse_mfma_kernel", "als_kernel", "ols_kernel", "var_boot_kernel", "quantile_kernel", "collapse_wide_kernel", "em_update_kernel", "chow_kernel", "mstep_mfma_kernel", "gram_xx_kernel", "pass_fused_kernel", "forecast_tail_kernel", "forecast_fill_kernel", "forecast_pad_kernel", "simsmooth_prep_kernel", "simsmooth_expand_kernel", "simsmooth_path_kernel", "simsmooth_diff_kernel", "simsmooth_finish_kernel", "simsmooth_fill_kernel", "news_revise_kernel", "news_gather_kernel", "news_gamma_kernel", "news_cov_panel_kernel", "news_impact_kernel", "mf_table_kernel", "mf_moments_kernel", "mf_solve_kernel"};
 
 namespace dfm { int handle_device(const dfm_handle* h) { return h->device; } }   // (probe.hip)
 
@@ -1264,6 +1264,169 @@ int ar_em_run(dfm_handle* h, int B, int T, int N, int r, int nlag, int q, const 
     return 0;
 }
 
+// ---- mixed frequency (mstep_mf.hip; tests/mf_expect.py) ---------------------------------------------------------------------
+// x_it = lam_i' sum_{l<L} w_il f_{t-l} + e_it with known weights W [N][L] shared by the batch: a sibling of the AR model above without
+// quasi-differencing and without a rho step.  Loadings [w_i0 lam_i, .., w_i,L-1 lam_i, 0..] on the companion state of
+// m = max(p, L) lags, the pass and the restricted transition step as ar_em_run, then the series step from a per-class table.
+struct MfClasses {
+    int C = 0, ntiles = 0;
+    std::vector<double> Wc;            // [C][L]
+    std::vector<int> tile_class, tile_series;
+};
+// the distinct rows of W (exact comparison) and the series dealt into class-pure tiles of 16 (index lists, -1 = padding)
+int mf_classes(dfm_handle* h, int N, int L, const std::vector<double>& W, MfClasses* mc) {
+    std::vector<int> cls(N);
+    for (int i = 0; i < N; ++i) {
+        for (int l = 0; l < L; ++l)
+            if (!isfinite(W[(size_t)i * L + l])) return fail(h, DFM_E_DIMS, "mixed frequency: a weight is not finite%s");
+        int c = 0;
+        for (; c < mc->C; ++c) {
+            bool same = true;
+            for (int l = 0; l < L; ++l) same = same && mc->Wc[(size_t)c * L + l] == W[(size_t)i * L + l];
+            if (same) break;
+        }
+        if (c == mc->C) {
+            if (mc->C == kMfMaxClasses) return fail(h, DFM_E_DIMS, "mixed frequency: more than 8 distinct weight vectors%s");
+            mc->Wc.insert(mc->Wc.end(), W.begin() + (size_t)i * L, W.begin() + (size_t)(i + 1) * L);
+            ++mc->C;
+        }
+        cls[i] = c;
+    }
+    for (int c = 0; c < mc->C; ++c) {
+        int fill = 0;
+        for (int i = 0; i < N; ++i) {
+            if (cls[i] != c) continue;
+            if (fill == 0) mc->tile_class.push_back(c);
+            mc->tile_series.push_back(i);
+            fill = (fill + 1) & 15;
+        }
+        while (fill) { mc->tile_series.push_back(-1); fill = (fill + 1) & 15; }
+    }
+    mc->ntiles = (int)mc->tile_class.size();
+    return 0;
+}
+
+int mf_check(dfm_handle* h, int B, int T, int N, int r, int nlag, int L) {
+    if (!h) return DFM_E_NULL;
+    if (nlag < 1 || L < 1) return fail(h, DFM_E_DIMS, "need p >= 1 factor lags and L >= 1 aggregation lags%s");
+    if (L > kMfMaxLags) return fail(h, DFM_E_DIMS, "mixed frequency: L <= 5 aggregation lags%s");
+    if (int rc = check_dims(h, B, T, N, r)) return rc;
+    const int m = nlag > L ? nlag : L, k = r * m;
+    if (k > DFM_MAX_R) return fail(h, DFM_E_R_UNSUPPORTED, "r * max(p, L) > DFM_MAX_R (32)%s");
+    return check_general_n(h, N, k);
+}
+
+int mf_pass_run(dfm_handle* h, int B, int T, int N, int r, int nlag, int L, const double* panel, const double* Lam, const double* R,
+                const double* W, const double* Avar, const double* Q, const double* mu0, const double* P0, double* f_smooth,
+                double* P_smooth, double* loglik, unsigned flags) {
+    if (int rc = mf_check(h, B, T, N, r, nlag, L)) return rc;
+    if (!panel || !Lam || !R || !W || !Avar || !Q || !mu0 || !P0 || !f_smooth || !loglik)
+        return fail(h, DFM_E_NULL, "required pointer is NULL%s");
+    HIP_TRY(h, hipSetDevice(h->device));
+    std::vector<double> Wh((size_t)N * L);
+    HIP_TRY(h, hipMemcpyAsync(Wh.data(), W, Wh.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    for (double w : Wh)
+        if (!isfinite(w)) return fail(h, DFM_E_DIMS, "mixed frequency: a weight is not finite%s");
+    const int m = nlag > L ? nlag : L, k = r * m;
+    Plan p = make_plan(B, T, N, k, flags | DFM_F_SINGULAR_Q, false, false);
+    p.kdim = k; p.kb = r; p.ka = r * nlag;                   // (the companion structure, as ar_pass_run)
+    p.qsing = (flags & DFM_F_SINGULAR_Q) ? 1 : 0;
+    if (int rc = ensure_ws(h, p.total)) return rc;
+    const int Rk = p.Rp;
+    double *LamP = at<double>(h, p.LamP), *AP = at<double>(h, p.AP), *QP = at<double>(h, p.QP),
+           *mu0P = at<double>(h, p.mu0P), *P0P = at<double>(h, p.P0P);
+    HIP_TRY(h, launch_mf_loadings(B, N, r, L, Rk, Lam, W, LamP, h->stream));
+    {
+        const size_t nm = (size_t)B * Rk * Rk;
+        hipLaunchKernelGGL(companion_pad_kernel, dim3((unsigned)((nm + 255) / 256)), dim3(256), 0, h->stream, B, N, r, k,
+                           r * nlag, Rk, Rk, (const double*)nullptr, Avar, Q, mu0, P0, LamP, AP, QP, mu0P, P0P);
+        HIP_TRY(h, hipGetLastError());
+    }
+    PaddedParams pp{LamP, AP, QP, mu0P, P0P};
+    return enqueue_pass(h, p, B, T, N, r, panel, pp, R, f_smooth, P_smooth, loglik, nullptr);
+}
+
+int mf_run(dfm_handle* h, int B, int T, int N, int r, int nlag, int L, const double* panel, double* Lam, double* R, const double* W,
+           double* Avar, double* Q, double* mu0, double* P0, int max_iter, double tol, double* loglik_path, int* iters,
+           double* f_smooth, double* P_smooth, unsigned flags) {
+    if (int rc = mf_check(h, B, T, N, r, nlag, L)) return rc;
+    if (!mstep_mf_supported(r, L)) return fail(h, DFM_E_R_UNSUPPORTED, "mixed-frequency estimation needs r <= 8%s");
+    if (!panel || !Lam || !R || !W || !Avar || !Q || !mu0 || !P0 || !loglik_path || !iters)
+        return fail(h, DFM_E_NULL, "required pointer is NULL%s");
+    if (max_iter < 1) return fail(h, DFM_E_DIMS, "max_iter must be >= 1%s");
+    HIP_TRY(h, hipSetDevice(h->device));
+    MfClasses mc;
+    {
+        std::vector<double> Wh((size_t)N * L);
+        HIP_TRY(h, hipMemcpyAsync(Wh.data(), W, Wh.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        if (int rc = mf_classes(h, N, L, Wh, &mc)) return rc;
+    }
+    const int m = nlag > L ? nlag : L, k = r * m;
+    Plan p = make_plan(B, T, N, k, flags | DFM_F_SINGULAR_Q, true, false);
+    p.qsing = (flags & DFM_F_SINGULAR_Q) ? 1 : 0;
+    p.kdim = k; p.kb = r; p.ka = r * nlag;                   // companion constraints; the observation loads on L blocks (rl = 0)
+    // behind the pass's plan: the series step's table and moments, then the class weights and the tile lists
+    size_t off = (p.total + 255) & ~(size_t)255;
+    const size_t moff = take(off, mstep_mf_workspace(B, T, N, r, mc.C));
+    const size_t woff = take(off, mc.Wc.size() * sizeof(double));
+    const size_t coff = take(off, mc.tile_class.size() * sizeof(int));
+    const size_t soff = take(off, mc.tile_series.size() * sizeof(int));
+    if (int rc = ensure_ws(h, off)) return rc;
+    HIP_TRY(h, hipMemcpyAsync(at<double>(h, woff), mc.Wc.data(), mc.Wc.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(at<int>(h, coff), mc.tile_class.data(), mc.tile_class.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(at<int>(h, soff), mc.tile_series.data(), mc.tile_series.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));             // (the host vectors go out of scope with this call)
+    const int Rk = p.Rp;
+    double *LamP = at<double>(h, p.LamP), *AP = at<double>(h, p.AP), *QP = at<double>(h, p.QP),
+           *mu0P = at<double>(h, p.mu0P), *P0P = at<double>(h, p.P0P), *mws = at<double>(h, moff);
+    {
+        const size_t nm = (size_t)B * Rk * Rk;
+        hipLaunchKernelGGL(companion_pad_kernel, dim3((unsigned)((nm + 255) / 256)), dim3(256), 0, h->stream, B, N, r, k,
+                           r * nlag, Rk, Rk, (const double*)nullptr, Avar, Q, mu0, P0, LamP, AP, QP, mu0P, P0P);
+        HIP_TRY(h, hipGetLastError());
+    }
+    double* fsm = at<double>(h, p.fsm);
+    double* Psm = at<double>(h, p.Psm);
+    double* llbuf = at<double>(h, p.llbuf);
+    int* active = at<int>(h, p.active);
+    HIP_TRY(h, hipMemsetAsync(loglik_path, 0xFF, (size_t)B * max_iter * sizeof(double), h->stream));  // NaN
+    HIP_TRY(h, hipMemsetAsync(iters, 0, (size_t)B * sizeof(int), h->stream));
+    const size_t np = (size_t)r * (r + 1) / 2, npk = (size_t)Rk * (Rk + 1) / 2;
+    PaddedParams pp{LamP, AP, QP, mu0P, P0P};
+    MfMstepArgs ma;
+    ma.B = B; ma.T = T; ma.N = N; ma.r = r; ma.L = L; ma.Rk = Rk; ma.C = mc.C; ma.VW = mstep_mf_row_width(r); ma.ntiles = mc.ntiles;
+    ma.panel = panel; ma.zsm = fsm; ma.Psm = Psm; ma.active = active; ma.Wc = at<double>(h, woff);
+    ma.tile_class = at<int>(h, coff); ma.tile_series = at<int>(h, soff); ma.Lam = Lam; ma.R = R;
+    std::vector<int> act_host;
+    for (int it = 0; it < max_iter; ++it) {
+        { ProfScope ps(h, K_PAD); HIP_TRY(h, launch_mf_loadings(B, N, r, L, Rk, Lam, W, LamP, h->stream)); }
+        EmOpts eo;
+        eo.A_out = AP; eo.Q_out = QP; eo.mu0_out = mu0P; eo.P0_out = P0P;
+        eo.active = active; eo.iters = iters; eo.ll_path = loglik_path; eo.k = it; eo.max_iter = max_iter; eo.tol = tol;
+        if (int rc = enqueue_pass(h, p, B, T, N, Rk, panel, pp, R, fsm, Psm, llbuf, &eo)) return rc;
+        { ProfScope ps(h, K_MF_TABLE); HIP_TRY(h, launch_mf_table(ma, mws, h->stream)); }
+        { ProfScope ps(h, K_MF_MOMENTS); HIP_TRY(h, launch_mf_moments(ma, mws, h->stream)); }
+        { ProfScope ps(h, K_MF_SOLVE); HIP_TRY(h, launch_mf_solve(ma, mws, h->stream)); }
+        if (tol > 0.0 && it + 1 < max_iter) {
+            act_host.resize(B);
+            HIP_TRY(h, hipMemcpyAsync(act_host.data(), active, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+            HIP_TRY(h, hipStreamSynchronize(h->stream));
+            bool any = false;
+            for (int b = 0; b < B; ++b) any = any || act_host[b] != 0;
+            if (!any) break;
+        }
+    }
+    if (int rc = copy_block(h, B, Rk, Rk, r, r * nlag, AP, Avar)) return rc;
+    if (int rc = copy_block(h, B, Rk, Rk, r, r, QP, Q)) return rc;
+    if (int rc = copy_block(h, B, Rk, Rk, k, k, P0P, P0)) return rc;
+    if (int rc = copy_block(h, B, 1, Rk, 1, k, mu0P, mu0)) return rc;
+    if (f_smooth) if (int rc = copy_block(h, (size_t)B * T, 1, Rk, 1, r, fsm, f_smooth)) return rc;
+    if (P_smooth) if (int rc = copy_block(h, (size_t)B * T, 1, (int)npk, 1, (int)np, Psm, P_smooth)) return rc;
+    return 0;
+}
+
 // ---- observed factors (mstep_obs.hip, oracle/obs_oracle.py em_obs) ------------------------------------
 // Per iteration: y = x - Lam_o g and the padded Lam_u -> the ordinary smoother pass on y with the transition M-step (the
 // pass's own EM epilogue: A, Q, mu0, P0 of the unobserved block) -> the joint loadings regression on z = (g, f).
@@ -1934,6 +2097,85 @@ int dfm_em_ar_batch(dfm_handle* h, int B, int T, int N, int r, int p, int q, con
     if (rc == 0) rc = post_check(h, loglik_path, B, (size_t)max_iter);
     (void)hipFree(buf);
     return rc;
+}
+
+// ---- mixed frequency ---------------------------------------------------------------------------------------------------
+int dfm_ks_pass_mf_batch_dev(dfm_handle* h, int B, int T, int N, int r, int p, int L, const double* panel, const double* Lam,
+                             const double* R, const double* W, const double* Avar, const double* Q, const double* mu0,
+                             const double* P0, double* f_smooth, double* P_smooth, double* loglik, unsigned flags) {
+    return mf_pass_run(h, B, T, N, r, p, L, panel, Lam, R, W, Avar, Q, mu0, P0, f_smooth, P_smooth, loglik, flags);
+}
+
+int dfm_em_mf_batch_dev(dfm_handle* h, int B, int T, int N, int r, int p, int L, const double* panel, double* Lam, double* R,
+                        const double* W, double* Avar, double* Q, double* mu0, double* P0, int max_iter, double tol,
+                        double* loglik_path, int* iters, double* f_smooth, double* P_smooth, unsigned flags) {
+    return mf_run(h, B, T, N, r, p, L, panel, Lam, R, W, Avar, Q, mu0, P0, max_iter, tol, loglik_path, iters, f_smooth, P_smooth,
+                  flags);
+}
+
+// host entry points: em = false is the pass (loglik_path = loglik [B], iters unused)
+static int mf_host(dfm_handle* h, int B, int T, int N, int r, int p, int L, const double* panel, double* Lam, double* R,
+                   const double* W, double* Avar, double* Q, double* mu0, double* P0, int max_iter, double tol, double* loglik_path,
+                   int* iters, double* f_smooth, double* P_smooth, unsigned flags, bool em) {
+    if (int rc = mf_check(h, B, T, N, r, p, L)) return rc;
+    if (!panel || !Lam || !R || !W || !Avar || !Q || !mu0 || !P0 || !loglik_path || (em && !iters) || (!em && !f_smooth))
+        return fail(h, DFM_E_NULL, "required pointer is NULL%s");
+    if (max_iter < 1) return fail(h, DFM_E_DIMS, "max_iter must be >= 1%s");
+    if (int rc = status_epoch(h)) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const int m = p > L ? p : L;
+    const size_t d = sizeof(double), k = (size_t)r * m, np = (size_t)r * (r + 1) / 2;
+    const size_t n_panel = (size_t)B * T * N, n_lam = (size_t)B * N * r, n_R = (size_t)B * N, n_w = (size_t)N * L,
+                 n_a = (size_t)B * r * r * p, n_q = (size_t)B * r * r, n_v = (size_t)B * k, n_p0 = (size_t)B * k * k,
+                 n_f = (size_t)B * T * r, n_P = (size_t)B * T * np, n_ll = (size_t)B * (em ? max_iter : 1);
+    double* buf = nullptr;
+    HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&buf),
+                         (n_panel + n_lam + n_R + n_w + n_a + n_q + n_v + n_p0 + n_f + n_P + n_ll) * d + (size_t)B * sizeof(int)));
+    double* dp = buf;
+    auto up = [&](const double* src, size_t n) -> double* {
+        double* dst = dp; dp += n;
+        if (n) (void)hipMemcpyAsync(dst, src, n * d, hipMemcpyHostToDevice, h->stream);
+        return dst;
+    };
+    double *x_d = up(panel, n_panel), *lam_d = up(Lam, n_lam), *R_d = up(R, n_R), *w_d = up(W, n_w), *A_d = up(Avar, n_a),
+           *Q_d = up(Q, n_q), *mu_d = up(mu0, n_v), *P0_d = up(P0, n_p0);
+    double* f_d = dp; dp += n_f;
+    double* P_d = dp; dp += n_P;
+    double* ll_d = dp; dp += n_ll;
+    int* it_d = reinterpret_cast<int*>(dp);
+    int rc = em ? mf_run(h, B, T, N, r, p, L, x_d, lam_d, R_d, w_d, A_d, Q_d, mu_d, P0_d, max_iter, tol, ll_d, it_d,
+                         f_smooth ? f_d : nullptr, P_smooth ? P_d : nullptr, flags)
+                : mf_pass_run(h, B, T, N, r, p, L, x_d, lam_d, R_d, w_d, A_d, Q_d, mu_d, P0_d, f_d, P_smooth ? P_d : nullptr, ll_d, flags);
+    if (rc == 0) {
+        auto down = [&](void* dst, const void* src, size_t bytes) { if (bytes) (void)hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream); };
+        if (em) {
+            down(Lam, lam_d, n_lam * d); down(R, R_d, n_R * d); down(Avar, A_d, n_a * d); down(Q, Q_d, n_q * d);
+            down(mu0, mu_d, n_v * d); down(P0, P0_d, n_p0 * d); down(iters, it_d, (size_t)B * sizeof(int));
+        }
+        down(loglik_path, ll_d, n_ll * d);
+        if (f_smooth) down(f_smooth, f_d, n_f * d);
+        if (P_smooth) down(P_smooth, P_d, n_P * d);
+        hipError_t e = hipStreamSynchronize(h->stream);
+        if (e != hipSuccess) rc = hip_fail(h, e, "hipStreamSynchronize");
+    }
+    if (rc == 0) rc = post_check(h, loglik_path, B, em ? (size_t)max_iter : 1);
+    (void)hipFree(buf);
+    return rc;
+}
+
+int dfm_ks_pass_mf_batch(dfm_handle* h, int B, int T, int N, int r, int p, int L, const double* panel, const double* Lam,
+                         const double* R, const double* W, const double* Avar, const double* Q, const double* mu0,
+                         const double* P0, double* f_smooth, double* P_smooth, double* loglik, unsigned flags) {
+    return mf_host(h, B, T, N, r, p, L, panel, const_cast<double*>(Lam), const_cast<double*>(R), W, const_cast<double*>(Avar),
+                   const_cast<double*>(Q), const_cast<double*>(mu0), const_cast<double*>(P0), 1, 0.0, loglik, nullptr, f_smooth,
+                   P_smooth, flags, false);
+}
+
+int dfm_em_mf_batch(dfm_handle* h, int B, int T, int N, int r, int p, int L, const double* panel, double* Lam, double* R,
+                    const double* W, double* Avar, double* Q, double* mu0, double* P0, int max_iter, double tol, double* loglik_path,
+                    int* iters, double* f_smooth, double* P_smooth, unsigned flags) {
+    return mf_host(h, B, T, N, r, p, L, panel, Lam, R, W, Avar, Q, mu0, P0, max_iter, tol, loglik_path, iters, f_smooth, P_smooth,
+                   flags, true);
 }
 
 // ---- observed factors ------------------------------------------------------------------------------------------------

@@ -267,6 +267,32 @@ bool mstep_ar_supported(int r, int q);
 size_t mstep_ar_workspace(int B, int T, int N, int r, int q, int Rk);
 // ws: mstep_ar_workspace bytes (ar_moments_kernel + ar_solve_kernel)
 hipError_t launch_mstep_ar(const ArMstepArgs& a, double* ws, hipStream_t s);
+// Series block of the EM iteration of the mixed-frequency model (mstep_mf.hip): x_it = lam_i' sum_l w_il f_{t-l} + e_it with known
+// weights in C <= kMfMaxClasses distinct classes; the series dealt by index into tiles of 16 of one class each.
+constexpr int kMfMaxClasses = 8, kMfMaxLags = 5;
+struct MfMstepArgs {
+    int B, T, N, r, L, Rk, C;   // Rk: padded state width (r max(p, L) <= Rk)
+    int VW;                     // mstep_mf_row_width(r): columns of a class row of the table
+    int ntiles;                 // series tiles
+    const double* panel;        // [B][T][N], NaN = missing
+    const double* zsm;          // [B][T][Rk]             smoothed means of z_t = (f_t, .., f_{t-m+1})
+    const double* Psm;          // [B][T][Rk(Rk+1)/2]     smoothed covariances, packed lower
+    const int* active;          // [B] or null
+    const double* Wc;           // [C][L]      the classes' weights
+    const int* tile_class;      // [ntiles]
+    const int* tile_series;     // [ntiles][16] series index, -1 = padding
+    double* Lam;                // [B][N][r]   in / out
+    double* R;                  // [B][N]      in / out
+};
+bool mstep_mf_supported(int r, int L);
+int mstep_mf_row_width(int r);
+size_t mstep_mf_workspace(int B, int T, int N, int r, int C);
+// LamK [B][N][Rk] = [w_i0 lam_i, .., w_i,L-1 lam_i, 0..] from Lam [B][N][r], W [N][L]
+hipError_t launch_mf_loadings(int B, int N, int r, int L, int Rk, const double* Lam, const double* W, double* LamK, hipStream_t s);
+// ws: mstep_mf_workspace bytes, the same block for the three launches of an iteration
+hipError_t launch_mf_table(const MfMstepArgs& a, double* ws, hipStream_t s);
+hipError_t launch_mf_moments(const MfMstepArgs& a, double* ws, hipStream_t s);
+hipError_t launch_mf_solve(const MfMstepArgs& a, double* ws, hipStream_t s);
 // V[b][t][tt16] = [vec(E f f' + P) of the leading r states (packed lower), zeros to ntm16 | f_t (Rp columns), zeros] (mstep_miss.hip)
 hipError_t launch_mmw_vec(const double* fsm, const double* Psm, const int* active, int B, int T, int r, int Rp, int ntm16, int tt16,
                           double* V, hipStream_t s);

@@ -796,6 +796,99 @@ class DfmContext:
         _check(self._h, rc)
         return dict(Lam=Lam, sig2=sig2, rho=rho, Avar=Avar, Q=Q, mu0=mu0, P0=P0), path, iters, f, P
 
+    # ------------------------------------------------------------------ mixed frequency (monthly factors, quarterly series)
+    def ks_pass_mf_batch(self, panel, Lam, R, W, Avar, Q, mu0, P0, want_P: bool = True,
+                         may_have_missing: Optional[bool] = None, singular_q: bool = False):
+        """Smoother pass of the mixed-frequency model (include/dfm_hip.h: dfm_ks_pass_mf_batch_dev): series i loads on
+        sum_l W[i,l] f_{t-l}; W [N,L] is shared by the batch; mu0 [B,r m], P0 [B,r m,r m], m = max(p, L).  Device tensors.
+        Returns (f_smooth [B,T,r], P_smooth or None, loglik [B])."""
+        torch = self._torch
+        B, T, N = panel.shape
+        r = Lam.shape[2]
+        p = Avar.shape[2] // r
+        L = W.shape[1]
+        k = r * max(p, L)
+        flags = self._flags(panel, may_have_missing, singular_q)
+        f = torch.empty((B, T, r), dtype=torch.float64, device=panel.device)
+        P = torch.empty((B, T, r * (r + 1) // 2), dtype=torch.float64, device=panel.device) if want_P else None
+        ll = torch.empty((B,), dtype=torch.float64, device=panel.device)
+        self._sync_stream()
+        rc = self._lib.dfm_ks_pass_mf_batch_dev(
+            self._h, B, T, N, r, p, L, self._dev(panel, "panel"), self._dev(Lam, "Lam", (B, N, r)), self._dev(R, "R", (B, N)),
+            self._dev(W, "W", (N, L)), self._dev(Avar, "Avar", (B, r, r * p)), self._dev(Q, "Q", (B, r, r)),
+            self._dev(mu0, "mu0", (B, k)), self._dev(P0, "P0", (B, k, k)), self._dev(f, "f_smooth"),
+            self._dev(P, "P_smooth") if P is not None else None, self._dev(ll, "loglik"), flags)
+        _check(self._h, rc)
+        return f, P, ll
+
+    def ks_pass_mf_batch_host(self, panel, Lam, R, W, Avar, Q, mu0, P0, may_have_missing: Optional[bool] = None, singular_q: bool = False):
+        """Host-pointer entry (what Julia's ccall binds)."""
+        c = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+        panel, Lam, R, W, Avar, Q, mu0, P0 = map(c, (panel, Lam, R, W, Avar, Q, mu0, P0))
+        B, T, N = panel.shape
+        r = Lam.shape[2]
+        p_lag = Avar.shape[2] // r
+        L = W.shape[1]
+        if may_have_missing is None:
+            may_have_missing = bool(np.isnan(panel).any())
+        flags = (_lib.DFM_F_MAY_HAVE_MISSING if may_have_missing else 0) | (_lib.DFM_F_SINGULAR_Q if singular_q else 0)
+        f = np.empty((B, T, r)); P = np.empty((B, T, r * (r + 1) // 2)); ll = np.empty(B)
+        p = lambda a: ctypes.c_void_p(a.ctypes.data) if a.size else None
+        rc = self._lib.dfm_ks_pass_mf_batch(self._h, B, T, N, r, p_lag, L, p(panel), p(Lam), p(R), p(W), p(Avar), p(Q),
+                                            p(mu0), p(P0), p(f), p(P), p(ll), flags)
+        _check(self._h, rc)
+        return f, P, ll
+
+    def em_mf_batch(self, panel, Lam, R, W, Avar, Q, mu0, P0, max_iter: int = 10, tol: float = 0.0,
+                    want_smooth: bool = True, want_P: bool = True, may_have_missing: Optional[bool] = None, singular_q: bool = False):
+        """EM estimation of the mixed-frequency model (include/dfm_hip.h: dfm_em_mf_batch_dev).  Device tensors; Lam [B,N,r],
+        R [B,N], Avar [B,r,r p], Q, mu0 [B,r m], P0 [B,r m,r m] are UPDATED IN PLACE; W [N,L] is read only.
+        Returns (loglik_path [B,max_iter], iters [B], f_smooth [B,T,r] or None, P_smooth or None)."""
+        torch = self._torch
+        B, T, N = panel.shape
+        r = Lam.shape[2]
+        p = Avar.shape[2] // r
+        L = W.shape[1]
+        k = r * max(p, L)
+        flags = self._flags(panel, may_have_missing, singular_q)
+        dev = panel.device
+        path = torch.empty((B, max_iter), dtype=torch.float64, device=dev)
+        iters = torch.empty((B,), dtype=torch.int32, device=dev)
+        f = torch.empty((B, T, r), dtype=torch.float64, device=dev) if want_smooth else None
+        P = torch.empty((B, T, r * (r + 1) // 2), dtype=torch.float64, device=dev) if (want_smooth and want_P) else None
+        self._sync_stream()
+        rc = self._lib.dfm_em_mf_batch_dev(
+            self._h, B, T, N, r, p, L, self._dev(panel, "panel"), self._dev(Lam, "Lam", (B, N, r)), self._dev(R, "R", (B, N)),
+            self._dev(W, "W", (N, L)), self._dev(Avar, "Avar", (B, r, r * p)), self._dev(Q, "Q", (B, r, r)),
+            self._dev(mu0, "mu0", (B, k)), self._dev(P0, "P0", (B, k, k)), int(max_iter), float(tol),
+            self._dev(path, "loglik_path"), ctypes.c_void_p(iters.data_ptr()), self._dev(f, "f_smooth") if f is not None else None,
+            self._dev(P, "P_smooth") if P is not None else None, flags)
+        _check(self._h, rc)
+        return path, iters, f, P
+
+    def em_mf_batch_host(self, panel, Lam, R, W, Avar, Q, mu0, P0, max_iter: int = 10, tol: float = 0.0,
+                         may_have_missing: Optional[bool] = None, singular_q: bool = False):
+        """Host-pointer entry (what Julia's ccall binds).  Returns (params dict, loglik_path, iters, f_smooth, P_smooth);
+        inputs are not modified."""
+        c = lambda a: np.array(a, dtype=np.float64, order="C", copy=True)
+        panel = np.ascontiguousarray(panel, dtype=np.float64)
+        W = np.ascontiguousarray(W, dtype=np.float64)
+        Lam, R, Avar, Q, mu0, P0 = map(c, (Lam, R, Avar, Q, mu0, P0))
+        B, T, N = panel.shape
+        r = Lam.shape[2]
+        p_lag = Avar.shape[2] // r
+        L = W.shape[1]
+        if may_have_missing is None:
+            may_have_missing = bool(np.isnan(panel).any())
+        flags = (_lib.DFM_F_MAY_HAVE_MISSING if may_have_missing else 0) | (_lib.DFM_F_SINGULAR_Q if singular_q else 0)
+        path = np.empty((B, max_iter)); iters = np.empty(B, dtype=np.int32)
+        f = np.empty((B, T, r)); P = np.empty((B, T, r * (r + 1) // 2))
+        p = lambda a: ctypes.c_void_p(a.ctypes.data) if a.size else None
+        rc = self._lib.dfm_em_mf_batch(self._h, B, T, N, r, p_lag, L, p(panel), p(Lam), p(R), p(W), p(Avar), p(Q),
+                                       p(mu0), p(P0), int(max_iter), float(tol), p(path), p(iters), p(f), p(P), flags)
+        _check(self._h, rc)
+        return dict(Lam=Lam, R=R, Avar=Avar, Q=Q, mu0=mu0, P0=P0), path, iters, f, P
+
     # ------------------------------------------------------------------ PCA initialisation / synthetic panels
     def pca_init_batch(self, panel, r: int, want_factors: bool = True):
         """PCA + OLS start of EM on balanced standardised panels (device tensor [B,T,N], no NaN).

@@ -374,6 +374,44 @@ int dfm_em_ar_batch(dfm_handle* h, int B, int T, int N, int r, int p, int q, con
                     double* sig2, double* rho, double* Avar, double* Q, double* mu0, double* P0, int max_iter, double tol,
                     double* loglik_path, int* iters, double* f_smooth, double* P_smooth, unsigned flags);
 
+/* --- MIXED FREQUENCY: monthly factors, quarterly series (Mariano and Murasawa 2003; Banbura and Modugno 2014) ---------------
+ *   x_it = lam_i' g_it + e_it,   g_it = sum_{l<L} w_il f_{t-l},   e_it ~ N(0, R_i),
+ *   f_t  = A_1 f_{t-1} + .. + A_p f_{t-p} + eta_t,   eta_t ~ N(0, Q)
+ * on a MONTHLY time index.  W [N][L] (one matrix for the whole batch) holds KNOWN aggregation weights: a monthly series has
+ * (1, 0, ..), a quarterly growth rate (flow) (1, 2, 3, 2, 1) / 3, a quarterly average of a monthly level (1, 1, 1) / 3; any finite
+ * W is legal, the library does not interpret it.  A quarterly series is NaN outside the third month of each quarter: ordinary
+ * missing data.  The state is z_t = (f_t, .., f_{t-m+1}), m = max(p, L), loadings [w_i0 lam_i, .., w_i,L-1 lam_i, 0..], transition
+ * of [A_1..A_p, 0], innovation covariance [Q 0; 0 0] -- the AR model above without quasi-differencing and without rho.
+ * Lam [B][N][r], R [B][N], Avar [B][r][r p], Q [B][r][r], mu0 [B][r m], P0 [B][r m][r m] (moments of z_0, P0 positive definite);
+ * f_smooth [B][T][r], P_smooth [B][T][r(r+1)/2] (or NULL): those of f_t = z_t[:r]; loglik [B].  L = 1, W = 1 is
+ * dfm_ks_pass_varp_batch.  DFM_F_MAY_HAVE_MISSING / DFM_F_SINGULAR_Q as for dfm_*_varp_*.
+ * Limits: 1 <= L <= 5 and finite weights (else DFM_E_DIMS), r max(p, L) <= DFM_MAX_R (else DFM_E_R_UNSUPPORTED), N as
+ * dfm_*_ar_* for a state r max(p, L) wide (N <= 1024 up to 8, 512 up to 16, 256 beyond). */
+int dfm_ks_pass_mf_batch_dev(dfm_handle* h, int B, int T, int N, int r, int p, int L, const double* panel, const double* Lam,
+                             const double* R, const double* W, const double* Avar, const double* Q, const double* mu0,
+                             const double* P0, double* f_smooth, double* P_smooth, double* loglik, unsigned flags);
+int dfm_ks_pass_mf_batch(dfm_handle* h, int B, int T, int N, int r, int p, int L, const double* panel, const double* Lam,
+                         const double* R, const double* W, const double* Avar, const double* Q, const double* mu0,
+                         const double* P0, double* f_smooth, double* P_smooth, double* loglik, unsigned flags);
+
+/* Maximum likelihood of the same model by EM.  Per iteration: (1) the smoother pass of the expanded model; (2) the transition
+ * step, a VAR(p) inside the state of m lags: [A_1..A_p] = S10[:r, :rp] S00[:rp, :rp]^-1, Q = (S11[:r,:r] - A S10[:r,:rp]') / T
+ * symmetrised, mu0 / P0 = smoothed moments of z_0; (3) per series, over its n_i observed periods,
+ *   G_i = sum_t E[g_it g_it'],  b_i = sum_t x_it E[g_it],  lam_i = G_i^-1 b_i,  R_i = (sum_t x_it^2 - 2 lam_i' b_i + lam_i' G_i lam_i) / n_i
+ * with E[g_it] and E[g_it g_it'] read from the smoothed mean and covariance of z_t (L <= m: every lag is inside the state).  A
+ * series with fewer than r + 1 observed cells keeps lam_i and R_i.  Parameters are updated in place; loglik_path [B][max_iter]
+ * (the likelihood at the parameters ENTERING each iteration, NaN past convergence, non-decreasing), iters and tol as
+ * dfm_em_batch; f_smooth / P_smooth (may be NULL): the last E-step.  The distinct rows of W (compared exactly) are the weight
+ * CLASSES; the aggregated moments are tabulated once per period and class, so a panel may hold at most 8 classes (else
+ * DFM_E_DIMS; every use above has two or three).  Limits as the pass, and r <= 8 (else DFM_E_R_UNSUPPORTED).  W is read back
+ * to the host once per call (the call synchronises the stream before its first launch). */
+int dfm_em_mf_batch_dev(dfm_handle* h, int B, int T, int N, int r, int p, int L, const double* panel, double* Lam, double* R,
+                        const double* W, double* Avar, double* Q, double* mu0, double* P0, int max_iter, double tol,
+                        double* loglik_path, int* iters, double* f_smooth, double* P_smooth, unsigned flags);
+int dfm_em_mf_batch(dfm_handle* h, int B, int T, int N, int r, int p, int L, const double* panel, double* Lam, double* R,
+                    const double* W, double* Avar, double* Q, double* mu0, double* P0, int max_iter, double tol,
+                    double* loglik_path, int* iters, double* f_smooth, double* P_smooth, unsigned flags);
+
 /* --- OBSERVED factors ------------------------------------------------------------------------------
  *   x_it = lam_o,i' g_t + lam_u,i' f_t + e_it,   e_it ~ N(0, R_i),     f_t = A f_{t-1} + eta_t,  eta_t ~ N(0, Q)
  * The reference's DFMModel has `nfac_o` observed factors in front of the `nfac_u` estimated ones (`factor` is T x nfac_t,

@@ -444,6 +444,120 @@ function em_ar(h::Handle, x::Matrix{Float64}, Lam::Matrix{Float64}, sig2::Vector
 end
 
 # ---- the reference's NON-parametric estimator on the GPU (als.hip) ------------------------------------------------
+
+const MF_WEIGHTS = Dict("m" => [1.0], "q_flow" => [1, 2, 3, 2, 1] ./ 3, "q_avg" => [1, 1, 1] ./ 3)
+
+"N x L aggregation weights from the matrix itself or from a vector of \"m\" / \"q_flow\" / \"q_avg\" (include/dfm_hip.h, mixed frequency)."
+function mf_weights(weights, N::Integer)
+    if weights isa AbstractMatrix
+        W = Matrix{Float64}(weights)
+    else
+        L = maximum(length(MF_WEIGHTS[k]) for k in weights)
+        W = zeros(length(weights), L)
+        for (i, k) in enumerate(weights)
+            w = MF_WEIGHTS[k]
+            W[i, 1:length(w)] = w
+        end
+    end
+    size(W, 1) == N || error("weights: $(size(W, 1)) rows for $N series")
+    return W
+end
+
+"EM iterations of the mixed-frequency model from a given start (dfm_em_mf_batch; include/dfm_hip.h): z is the standardised MONTHLY
+panel (T x N, NaN = missing; a quarterly series sits in the third month of its quarter), W N x L, Lam N x r, R, Avar r x (r p), Q,
+mu0 / P0 the moments of z_0, r max(p, L) wide.  Returns the updated parameters, the log-likelihood path and the smoothed factors."
+function em_mf(h::Handle, z::Matrix{Float64}, W::Matrix{Float64}, Lam::Matrix{Float64}, R::Vector{Float64}, Avar::Matrix{Float64},
+               Q::Matrix{Float64}, mu0::Vector{Float64}, P0::Matrix{Float64}; max_iter::Integer = 50, tol::Real = 1e-6,
+               singular_q::Bool = false)
+    T, N = size(z); r = size(Lam, 2); L = size(W, 2); p = div(size(Avar, 2), r)
+    panel = to_c_panel(z)
+    LamC = permutedims(Lam); Rc = copy(R); WC = permutedims(W); AC = permutedims(Avar); QC = permutedims(Q)
+    mu = copy(mu0); P0C = permutedims(P0)
+    path = Array{Float64}(undef, max_iter); iters = Array{Cint}(undef, 1)
+    f = Array{Float64}(undef, r, T); np = div(r * (r + 1), 2); P = Array{Float64}(undef, np, T)
+    flags = (any(isnan, z) ? DFM_F_MAY_HAVE_MISSING : Cuint(0)) | (singular_q ? DFM_F_SINGULAR_Q : Cuint(0))
+    GC.@preserve panel LamC Rc WC AC QC mu P0C path iters f P begin
+        rc = ccall((:dfm_em_mf_batch, LIB), Cint,
+                   (Ptr{Cvoid}, Cint, Cint, Cint, Cint, Cint, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                    Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cint, Cdouble, Ptr{Float64}, Ptr{Cint},
+                    Ptr{Float64}, Ptr{Float64}, Cuint),
+                   h.ptr, 1, T, N, r, p, L, panel, LamC, Rc, WC, AC, QC, mu, P0C, max_iter, tol, path, iters, f, P, flags)
+        check(h.ptr, rc)
+    end
+    kk = Int(iters[1])
+    return (Lam = permutedims(LamC), R = Rc, Avar = permutedims(AC), Q = permutedims(QC), mu0 = mu, P0 = permutedims(P0C),
+            loglik = path[1:kk], iters = kk, factor = permutedims(f))
+end
+
+"Smoother pass of the mixed-frequency model (dfm_ks_pass_mf_batch): arguments as em_mf; returns the smoothed monthly factors, their
+packed covariances and the log-likelihood."
+function ks_pass_mf(h::Handle, z::Matrix{Float64}, W::Matrix{Float64}, Lam::Matrix{Float64}, R::Vector{Float64}, Avar::Matrix{Float64},
+                    Q::Matrix{Float64}, mu0::Vector{Float64}, P0::Matrix{Float64}; singular_q::Bool = false)
+    T, N = size(z); r = size(Lam, 2); L = size(W, 2); p = div(size(Avar, 2), r)
+    panel = to_c_panel(z)
+    LamC = permutedims(Lam); WC = permutedims(W); AC = permutedims(Avar); QC = permutedims(Q); P0C = permutedims(P0)
+    f = Array{Float64}(undef, r, T); np = div(r * (r + 1), 2); P = Array{Float64}(undef, np, T)
+    ll = Array{Float64}(undef, 1)
+    flags = (any(isnan, z) ? DFM_F_MAY_HAVE_MISSING : Cuint(0)) | (singular_q ? DFM_F_SINGULAR_Q : Cuint(0))
+    GC.@preserve panel LamC R WC AC QC mu0 P0C f P ll begin
+        rc = ccall((:dfm_ks_pass_mf_batch, LIB), Cint,
+                   (Ptr{Cvoid}, Cint, Cint, Cint, Cint, Cint, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                    Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cuint),
+                   h.ptr, 1, T, N, r, p, L, panel, LamC, R, WC, AC, QC, mu0, P0C, f, P, ll, flags)
+        check(h.ptr, rc)
+    end
+    return (factor = permutedims(f), P = permutedims(P), loglik = ll[1])
+end
+
+"Maximum likelihood of the mixed-frequency DFM (api.estimate_mixed_frequency's steps): x is the MONTHLY panel in data units (T x N,
+NaN = missing), `weights` the N x L matrix or a vector of \"m\" / \"q_flow\" / \"q_avg\".  Every series is standardised with its own
+mean and population s.d.; the start is the PCA of the fully observed monthly series (pca_init), every series' loadings by a
+regression on the aggregated PCA factors, a VAR(p) by OLS; then dfm_em_mf_batch.  Returns the parameters (standardised units),
+W, mean, sd, the log-likelihood path and the smoothed monthly factors.  (No bootstrap replicates here: nrep is Python's.)"
+function estimate_mixed(x::Matrix{Float64}, weights, r::Integer, p::Integer; max_em_iter::Integer = 50, tol_em::Real = 1e-6,
+                        h::Handle = handle())
+    T, N = size(x)
+    W = mf_weights(weights, N)
+    L = size(W, 2); m = max(p, L)
+    obs = .!isnan.(x)
+    mu = [sum(x[obs[:, i], i]) / count(obs[:, i]) for i in 1:N]
+    sd = [sqrt(sum((x[obs[:, i], i] .- mu[i]) .^ 2) / count(obs[:, i])) for i in 1:N]
+    z = (x .- mu') ./ sd'
+    monthly = [W[i, 1] == 1.0 && all(W[i, 2:end] .== 0.0) for i in 1:N]
+    bal = [monthly[i] && all(obs[:, i]) for i in 1:N]
+    count(bal) >= r || error("fewer fully observed monthly series than factors: cannot initialise by PCA")
+    F = pca_init(h, z[:, bal], r).F
+    Lam = zeros(N, r); R = ones(N)
+    for i in 1:N
+        g = zeros(T, r)
+        for l in 0:L-1
+            g[l+1:T, :] .+= W[i, l+1] .* F[1:T-l, :]
+        end
+        o = copy(obs[:, i]); o[1:L-1] .= false
+        count(o) < r + 1 && continue
+        Lam[i, :] = g[o, :] \ z[o, i]
+        R[i] = max(sum((z[o, i] .- g[o, :] * Lam[i, :]) .^ 2) / count(o), 0.05)
+    end
+    lagged(k) = hcat([F[k-l:T-l, :] for l in 0:k-1]...)          # rows (f_t, .., f_{t-k+1}), t = k..T
+    Z = lagged(p)
+    Y = F[p+1:T, :]; Xl = Z[1:end-1, :]
+    Avar = permutedims((Xl' * Xl) \ (Xl' * Y))
+    e = Y .- Xl * Avar'
+    Q = e' * e ./ (T - p); Q = (Q .+ Q') ./ 2
+    Zm = lagged(m)
+    P0 = Zm' * Zm ./ size(Zm, 1); P0 = (P0 .+ P0') ./ 2
+    for j in 1:r*m
+        P0[j, j] += 1e-3
+    end
+    est = try
+        em_mf(h, z, W, Lam, R, Avar, Q, zeros(r * m), P0; max_iter = max_em_iter, tol = tol_em)
+    catch err                                                    # the information form inverts Q: retry in covariance form
+        (err isa ErrorException && occursin("status $(DFM_E_NUMERIC):", err.msg)) || rethrow()
+        em_mf(h, z, W, Lam, R, Avar, Q, zeros(r * m), P0; max_iter = max_em_iter, tol = tol_em, singular_q = true)
+    end
+    return merge(est, (W = W, mean = mu, sd = sd))
+end
+
 "`estimate_factor!` sweeps (dfm_functions.ipynb:352-370) for ONE run: z is the standardised T x N window (NaN =
 missing), F0 the T x r start (pca_score).  dfm_als_batch; returns factors, loadings (NaN rows: no loadings), ssr,
 iterations, R2."
