@@ -2,7 +2,8 @@
 tests/forecast_expect.py (the oracle's smoother pass over the panel with H all-missing rows appended, and the header's cell
 formulas) at 1e-9: the p = 1 routes (fused balanced pass, time-chunked recursion with the odd-N pad, the tile route at r = 20,
 covariance form), the companion routes at p > 1, the invariants of the outputs, api.forecast on the Stock-Watson panel and its
-bootstrap bands, and the status codes."""
+bootstrap bands, and the status codes.  tests/test_gpu_post_geometry.py covers the fill kernel's launch classes (series blocks,
+LDS cap, buckets r = 1 .. 32, long horizons)."""
 import os
 
 import numpy as np

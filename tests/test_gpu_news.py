@@ -2,7 +2,8 @@
 forecast's expectation model for the three conditional means, the oracle's pass over the covariance panels for the weights) at
 1e-9: the fused balanced pass, the time-chunked recursion with odd N, the tile route at r = 20, the companion routes, singular Q;
 then the output invariants, the device entry, a call across the 8192-replicate slice boundary, api.news on the Stock-Watson panel
-with groups and bootstrap bands, and the status codes."""
+with groups and bootstrap bands, and the status codes.  tests/test_gpu_post_geometry.py covers the cell and gamma kernels'
+launch classes (column-pair blocks, LDS cap, every bucket, targets at chunk edges and far beyond T)."""
 import os
 
 import numpy as np

@@ -3,7 +3,8 @@ tests/simsmooth_expect.py (the header's steps on the header's random stream, the
 the fused balanced pass, the time-chunked recursion with odd N, the tile route at r = 20, singular Q, the companion routes, with
 and without the horizon and mean / sd; then f_draw without x_draw, the first_draw split, a call across the 8192-replicate slice
 boundary, the draws' moments against dfm_forecast_batch, api.draw_paths on the Stock-Watson panel, parameter draws, and the
-status codes."""
+status codes.  tests/test_gpu_post_geometry.py covers the cell kernels' launch classes (column-pair blocks, LDS cap, every
+loadings bucket, long horizons)."""
 import os
 
 import numpy as np
