@@ -16,6 +16,33 @@ using namespace dfm;
 
 thread_local const char* dfm::t_launched_kernel = nullptr;
 
+// A grow-only device block of the handle.  Growing synchronises the device first: every stream the handle has launched on (the
+// caller may have swapped streams with dfm_set_stream, and the side / post streams of the fast path) must be done with the old
+// block before it goes back to the allocator.
+namespace {
+struct DevBlock {
+    void* p = nullptr;
+    size_t bytes = 0;
+    hipError_t grow(size_t need) {
+        if (need <= bytes) return hipSuccess;
+        if (p) {
+            if (hipError_t e = hipDeviceSynchronize()) return e;
+            if (hipError_t e = hipFree(p)) return e;
+            p = nullptr;
+            bytes = 0;
+        }
+        if (hipError_t e = hipMalloc(&p, need)) return e;
+        bytes = need;
+        return hipSuccess;
+    }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        bytes = 0;
+    }
+};
+}  // namespace
+
 struct dfm_handle {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -61,22 +88,20 @@ struct dfm_handle {
     bool gram_xx_valu = false;             // DFM_GRAM_XX_VALU=1: X'X of the PCA start on the VALU kernel (diagnostics)
     int pass_ncov = 0;                     // DFM_PASS_NCOV: covariance waves per workgroup of that launch (0 = automatic)
     bool cov_wave = false;                 // DFM_COV_WAVE=1: one-wave-per-replicate covariance recursion on the separate-launch path
-    void* ws = nullptr;
-    size_t ws_bytes = 0;
+    DevBlock ws;                           // the workspace every entry point plans (make_plan) and sizes (ensure_ws) before it uses it
     const int* ck_fail_dev = nullptr; int ck_fail_n = 0;   // chunk_fail of the last launch on recursion_chunk_kernel (dfm_chunk_fallbacks)
     // EM on the fast path at Rp <= 8: the transition M-step is not launched behind the E-step but handed to the loadings step's
     // streaming launch (mstep_mfma.hip runs it as extra workgroups): em_iteration sets defer_em, enqueue_pass_fast parks the
     // arguments here
     bool defer_em = false, have_deferred_em = false;
     dfm::EmUpdArgs deferred_em;
-    void* odd = nullptr;                   // panel / loadings / R with one all-missing series appended (odd N beyond the tilings, odd_pad)
-    size_t odd_bytes = 0;
-    void* fc = nullptr;                    // dfm_forecast_batch_dev: the pass's T-row moments, the forecast tail, P and loglik when the
-    size_t fc_bytes = 0;                   // caller does not take them (beside h->ws: the pass itself may reallocate that)
-    void* ss = nullptr;                    // dfm_simsmooth_batch_dev: roots, the slice's pass parameters, smoothed means, logliks and
-    size_t ss_bytes = 0;                   // (no x_draw) difference panels -- beside h->ws for the same reason
-    void* nw = nullptr;                    // dfm_news_batch_dev: targets, the revised old panel, one forecast's xhat, the slice's pass
-    size_t nw_bytes = 0;                   // parameters, u / a vectors, smoothed means and (no weight) covariance panels
+    DevBlock odd;                          // panel / loadings / R with one all-missing series appended (odd N beyond the tilings, odd_pad)
+    DevBlock fc;                           // dfm_forecast_batch_dev: the pass's T-row moments, the forecast tail, P and loglik when the
+                                           // caller does not take them (beside h->ws: the pass itself may reallocate that)
+    DevBlock ss;                           // dfm_simsmooth_batch_dev: roots, the slice's pass parameters, smoothed means, logliks and
+                                           // (no x_draw) difference panels -- beside h->ws for the same reason
+    DevBlock nw;                           // dfm_news_batch_dev: targets, the revised old panel, one forecast's xhat, the slice's pass
+                                           // parameters, u / a vectors, smoothed means and (no weight) covariance panels
     const double* odd_panel_src = nullptr; int odd_panel_dims[3] = {0, 0, 0};   // the panel whose padded copy h->odd holds (odd_pad keep_panel)
     std::string prof_file;                 // DFM_PF_PROF_FILE with DFM_SCAN_ABL=256: phase stamps of the fused pass
     char err[512] = {0};
@@ -278,24 +303,75 @@ int ensure_ws(dfm_handle* h, size_t bytes) {
     // every entry point sizes the workspace before it uses it: whatever chunk_fail flags the last pass left in the block are about to
     // be overwritten or freed -- dfm_chunk_fallbacks must not read them (enqueue_pass sets the pointer again behind its launch)
     h->ck_fail_dev = nullptr; h->ck_fail_n = 0;
-    if (bytes <= h->ws_bytes) return 0;
-    if (h->ws) {
-        // every stream this handle has launched on (the caller may have swapped streams with dfm_set_stream, and the
-        // side / post streams of the fast path) must be done with the old block before it goes back to the allocator
-        HIP_TRY(h, hipDeviceSynchronize());
-        HIP_TRY(h, hipFree(h->ws));
-        h->ws = nullptr;
-        h->ws_bytes = 0;
-    }
-    HIP_TRY(h, hipMalloc(&h->ws, bytes));
-    h->ws_bytes = bytes;
+    HIP_TRY(h, h->ws.grow(bytes));
     return 0;
 }
 
+// byte offset `off` of a block as a typed pointer; (size_t)-1 = "not planned" = null
+template <class T>
+T* at(const DevBlock& b, size_t off) {
+    return off == (size_t)-1 ? nullptr : reinterpret_cast<T*>(static_cast<char*>(b.p) + off);
+}
 template <class T>
 T* at(dfm_handle* h, size_t off) {
-    return off == (size_t)-1 ? nullptr : reinterpret_cast<T*>(static_cast<char*>(h->ws) + off);
+    return at<T>(h->ws, off);
 }
+
+// The device side of ONE call of a host-pointer entry point: one block that holds every array of the call, allocated for the
+// call and freed when it returns.  The entry declares its arrays in the order they lie in the block -- in (copied in), out (copied
+// back by finish), inout (both; back = false: copied in only) -- each with its element count and the variable that receives its
+// device pointer; begin() allocates the sum and enqueues the uploads.  A null host pointer keeps its n elements of space and gets a
+// null device pointer, which is what the _dev twins take to mean "not wanted"; an array that is to take no space when it is not
+// wanted is declared with n = 0.  Zero-length arrays enqueue no copy.
+// align: bytes every array starts on, at least its element size.  1 = packed; 256 where a kernel moves its rows 16 bytes at a time
+// (forecast_fill_kernel).  Several kernels pick their store width from the alignment of the pointer they are given, so an entry's
+// order and rounding are part of its results bit for bit.
+class HostStage {
+  public:
+    explicit HostStage(dfm_handle* h, size_t align = 1) : h_(h), align_(align) {}
+    ~HostStage() { if (buf_) (void)hipFree(buf_); }
+    HostStage(const HostStage&) = delete;
+    HostStage& operator=(const HostStage&) = delete;
+    template <class T> void in(const T* host, size_t n, T*& dev) { add(host, nullptr, host != nullptr, n, sizeof(T), &dev); }
+    template <class T> void out(T* host, size_t n, T*& dev) { add(nullptr, host, host != nullptr, n, sizeof(T), &dev); }
+    template <class T> void inout(T* host, size_t n, T*& dev, bool back = true) { add(host, back ? host : nullptr, host != nullptr, n, sizeof(T), &dev); }
+    int begin() {
+        const size_t bytes = (total_ + align_ - 1) / align_ * align_;      // (the last array's rounding belongs to the block too)
+        if (hipError_t e = hipMalloc(reinterpret_cast<void**>(&buf_), bytes)) return hip_fail(h_, e, "hipMalloc (host-pointer entry)");
+        for (const Arr& a : arrs_) {
+            *a.dev = a.wanted ? buf_ + a.off : nullptr;
+            if (a.up && a.bytes) note(hipMemcpyAsync(buf_ + a.off, a.up, a.bytes, hipMemcpyHostToDevice, h_->stream), "hipMemcpyAsync (host to device)");
+        }
+        return 0;
+    }
+    // rc: what the _dev twin returned.  rc == 0: copies the outputs back and waits for them.  Returns rc, else the first failed copy.
+    int finish(int rc) {
+        if (rc == 0 && err_ == hipSuccess) {
+            for (const Arr& a : arrs_)
+                if (a.down && a.bytes) note(hipMemcpyAsync(a.down, buf_ + a.off, a.bytes, hipMemcpyDeviceToHost, h_->stream), "hipMemcpyAsync (device to host)");
+            note(hipStreamSynchronize(h_->stream), "hipStreamSynchronize");
+        }
+        if (rc == 0 && err_ != hipSuccess) return hip_fail(h_, err_, where_);
+        return rc;
+    }
+
+  private:
+    struct Arr { const void* up; void* down; size_t off, bytes; void** dev; bool wanted; };
+    template <class T>
+    void add(const void* up, void* down, bool wanted, size_t n, size_t elem, T** dev) {
+        const size_t al = align_ > elem ? align_ : elem;
+        total_ = (total_ + al - 1) / al * al;
+        arrs_.push_back(Arr{up, down, total_, n * elem, reinterpret_cast<void**>(dev), wanted});
+        total_ += n * elem;
+    }
+    void note(hipError_t e, const char* where) { if (e != hipSuccess && err_ == hipSuccess) { err_ = e; where_ = where; } }
+    dfm_handle* h_;
+    size_t align_, total_ = 0;
+    char* buf_ = nullptr;
+    std::vector<Arr> arrs_;
+    hipError_t err_ = hipSuccess;
+    const char* where_ = "";
+};
 
 int check_dims(dfm_handle* h, int B, int T, int N, int r) {
     if (!h) return DFM_E_NULL;
@@ -397,14 +473,10 @@ int odd_pad(dfm_handle* h, int B, int T, int N, int r, const double* panel, cons
             bool keep_panel = false) {
     const size_t n_panel = (size_t)B * T * (N + 1), n_lam = (size_t)B * (N + 1) * r, n_R = (size_t)B * (N + 1);
     const size_t bytes = (n_panel + n_lam + n_R) * sizeof(double) + 768;
-    if (bytes > h->odd_bytes) {
-        if (h->odd) { HIP_TRY(h, hipDeviceSynchronize()); HIP_TRY(h, hipFree(h->odd)); h->odd = nullptr; h->odd_bytes = 0; }
-        h->odd_panel_src = nullptr;
-        HIP_TRY(h, hipMalloc(&h->odd, bytes));
-        h->odd_bytes = bytes;
-    }
+    if (bytes > h->odd.bytes) h->odd_panel_src = nullptr;      // (the padded copy goes with the old block)
+    HIP_TRY(h, h->odd.grow(bytes));
     auto al = [](size_t n) { return (n + 31) & ~(size_t)31; };
-    out->panel = static_cast<double*>(h->odd);
+    out->panel = static_cast<double*>(h->odd.p);
     out->Lam = out->panel + al(n_panel);
     out->R = out->Lam + al(n_lam);
     auto grid = [](size_t n) { return dim3((unsigned)((n + 255) / 256)); };
@@ -471,7 +543,7 @@ int pipe_run(dfm_handle* h, int B, size_t slot_bytes, Body body) {
     const int Bs = pipe_sub(h), S = (B + Bs - 1) / Bs;
     const size_t slot = (slot_bytes + 255) & ~(size_t)255;
     if (int rc = ensure_ws(h, 2 * slot + (size_t)B * sizeof(int))) return rc;
-    char* base = static_cast<char*>(h->ws);
+    char* base = static_cast<char*>(h->ws.p);
     int* agg = reinterpret_cast<int*>(base + 2 * slot);       // chunk_fail of every replicate (dfm_chunk_fallbacks)
     hipStream_t main = h->stream;
     HIP_TRY(h, hipEventRecord(h->ev_fork, main));
@@ -481,7 +553,7 @@ int pipe_run(dfm_handle* h, int B, size_t slot_bytes, Body body) {
     h->in_pipe = true;
     for (int s_ = 0; s_ < S && rc == 0; ++s_) {
         const int b0 = s_ * Bs, bn = (B - b0 < Bs) ? B - b0 : Bs;
-        h->ws = base + (size_t)(s_ & 1) * slot;
+        h->ws.p = base + (size_t)(s_ & 1) * slot;
         h->stream = (s_ & 1) ? h->post : main;
         rc = body(b0, bn);
         if (rc == 0) {
@@ -492,7 +564,7 @@ int pipe_run(dfm_handle* h, int B, size_t slot_bytes, Body body) {
         }
     }
     h->in_pipe = false;
-    h->ws = base; h->stream = main;
+    h->ws.p = base; h->stream = main;
     (void)hipEventRecord(h->ev_post, h->post);
     (void)hipStreamWaitEvent(main, h->ev_post, 0);              // join (also after a failure: the slots are in use until then)
     h->ck_fail_dev = (rc == 0 && have_fail) ? agg : nullptr;
@@ -1614,11 +1686,7 @@ int dfm_destroy(dfm_handle* h) {
     for (auto e : h->ev_sub) hipEventDestroy(e);
     if (h->ev_fork) hipEventDestroy(h->ev_fork);
     if (h->ev_join) hipEventDestroy(h->ev_join);
-    if (h->ws) hipFree(h->ws);
-    if (h->odd) hipFree(h->odd);
-    if (h->fc) hipFree(h->fc);
-    if (h->ss) hipFree(h->ss);
-    if (h->nw) hipFree(h->nw);
+    for (DevBlock* b : {&h->ws, &h->odd, &h->fc, &h->ss, &h->nw}) b->release();
     if (h->status_dev) hipFree(h->status_dev);
     if (h->own_stream && h->stream) hipStreamDestroy(h->stream);
     delete h;
@@ -1803,34 +1871,15 @@ int dfm_ks_pass_batch(dfm_handle* h, int B, int T, int N, int r, const double* p
         return fail(h, DFM_E_NULL, "required pointer is NULL%s");
     if (int rc = status_epoch(h)) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
-    const size_t d = sizeof(double), np = (size_t)r * (r + 1) / 2;
-    const size_t n_panel = (size_t)B * T * N, n_lam = (size_t)B * N * r, n_R = (size_t)B * N,
-                 n_m = (size_t)B * r * r, n_v = (size_t)B * r, n_f = (size_t)B * T * r, n_P = (size_t)B * T * np;
-    const size_t total = (n_panel + n_lam + n_R + 3 * n_m + n_v + n_f + (P_smooth ? n_P : 0) + B) * d;
-    double* buf = nullptr;
-    HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&buf), total));
-    double* dp = buf;
-    auto up = [&](const double* src, size_t n) -> double* {
-        double* dst = dp;
-        dp += n;
-        hipMemcpyAsync(dst, src, n * d, hipMemcpyHostToDevice, h->stream);
-        return dst;
-    };
-    double *x_d = up(panel, n_panel), *lam_d = up(Lam, n_lam), *R_d = up(R, n_R), *A_d = up(A, n_m),
-           *Q_d = up(Q, n_m), *mu_d = up(mu0, n_v), *P0_d = up(P0, n_m);
-    double* f_d = dp; dp += n_f;
-    double* P_d = P_smooth ? dp : nullptr; if (P_smooth) dp += n_P;
-    double* ll_d = dp;
-    int rc = dfm_ks_pass_batch_dev(h, B, T, N, r, x_d, lam_d, R_d, A_d, Q_d, mu_d, P0_d, f_d, P_d, ll_d, flags);
-    if (rc == 0) {
-        hipMemcpyAsync(f_smooth, f_d, n_f * d, hipMemcpyDeviceToHost, h->stream);
-        if (P_smooth) hipMemcpyAsync(P_smooth, P_d, n_P * d, hipMemcpyDeviceToHost, h->stream);
-        hipMemcpyAsync(loglik, ll_d, B * d, hipMemcpyDeviceToHost, h->stream);
-        hipError_t e = hipStreamSynchronize(h->stream);
-        if (e != hipSuccess) rc = hip_fail(h, e, "hipStreamSynchronize");
-    }
+    const size_t np = (size_t)r * (r + 1) / 2, n_m = (size_t)B * r * r;
+    HostStage st(h);
+    double *x_d, *lam_d, *R_d, *A_d, *Q_d, *mu_d, *P0_d, *f_d, *P_d, *ll_d;
+    st.in(panel, (size_t)B * T * N, x_d); st.in(Lam, (size_t)B * N * r, lam_d); st.in(R, (size_t)B * N, R_d);
+    st.in(A, n_m, A_d); st.in(Q, n_m, Q_d); st.in(mu0, (size_t)B * r, mu_d); st.in(P0, n_m, P0_d);
+    st.out(f_smooth, (size_t)B * T * r, f_d); st.out(P_smooth, P_smooth ? (size_t)B * T * np : 0, P_d); st.out(loglik, (size_t)B, ll_d);
+    if (int rc = st.begin()) return rc;
+    int rc = st.finish(dfm_ks_pass_batch_dev(h, B, T, N, r, x_d, lam_d, R_d, A_d, Q_d, mu_d, P0_d, f_d, P_d, ll_d, flags));
     if (rc == 0) rc = post_check(h, loglik, B);
-    hipFree(buf);
     return rc;
 }
 
@@ -1873,38 +1922,17 @@ int dfm_em_batch(dfm_handle* h, int B, int T, int N, int r, const double* panel,
     if (max_iter < 1) return fail(h, DFM_E_DIMS, "max_iter must be >= 1%s");
     if (int rc = status_epoch(h)) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
-    const size_t d = sizeof(double), np = (size_t)r * (r + 1) / 2;
-    const size_t n_panel = (size_t)B * T * N, n_lam = (size_t)B * N * r, n_R = (size_t)B * N, n_m = (size_t)B * r * r,
-                 n_v = (size_t)B * r, n_f = (size_t)B * T * r, n_P = (size_t)B * T * np, n_ll = (size_t)B * max_iter;
-    const size_t total = (n_panel + n_lam + n_R + 3 * n_m + n_v + n_f + n_P + n_ll) * d + (size_t)B * sizeof(int);
-    double* buf = nullptr;
-    HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&buf), total));
-    double* dp = buf;
-    auto up = [&](const double* src, size_t n) -> double* {
-        double* dst = dp; dp += n;
-        (void)hipMemcpyAsync(dst, src, n * d, hipMemcpyHostToDevice, h->stream);
-        return dst;
-    };
-    double *x_d = up(panel, n_panel), *lam_d = up(Lam, n_lam), *R_d = up(R, n_R), *A_d = up(A, n_m), *Q_d = up(Q, n_m),
-           *mu_d = up(mu0, n_v), *P0_d = up(P0, n_m);
-    double* f_d = dp; dp += n_f;
-    double* P_d = dp; dp += n_P;
-    double* ll_d = dp; dp += n_ll;
-    int* it_d = reinterpret_cast<int*>(dp);
-    int rc = dfm_em_batch_dev(h, B, T, N, r, x_d, lam_d, R_d, A_d, Q_d, mu_d, P0_d, max_iter, tol, ll_d, it_d,
-                              f_smooth ? f_d : nullptr, P_smooth ? P_d : nullptr, flags);
-    if (rc == 0) {
-        auto down = [&](void* dst, const void* src, size_t bytes) { (void)hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream); };
-        down(Lam, lam_d, n_lam * d); down(R, R_d, n_R * d); down(A, A_d, n_m * d); down(Q, Q_d, n_m * d);
-        down(mu0, mu_d, n_v * d); down(P0, P0_d, n_m * d); down(loglik_path, ll_d, n_ll * d);
-        down(iters, it_d, (size_t)B * sizeof(int));
-        if (f_smooth) down(f_smooth, f_d, n_f * d);
-        if (P_smooth) down(P_smooth, P_d, n_P * d);
-        hipError_t e = hipStreamSynchronize(h->stream);
-        if (e != hipSuccess) rc = hip_fail(h, e, "hipStreamSynchronize");
-    }
+    const size_t np = (size_t)r * (r + 1) / 2, n_m = (size_t)B * r * r;
+    HostStage st(h);
+    double *x_d, *lam_d, *R_d, *A_d, *Q_d, *mu_d, *P0_d, *f_d, *P_d, *ll_d;
+    int* it_d;
+    st.in(panel, (size_t)B * T * N, x_d); st.inout(Lam, (size_t)B * N * r, lam_d); st.inout(R, (size_t)B * N, R_d);
+    st.inout(A, n_m, A_d); st.inout(Q, n_m, Q_d); st.inout(mu0, (size_t)B * r, mu_d); st.inout(P0, n_m, P0_d);
+    st.out(f_smooth, (size_t)B * T * r, f_d); st.out(P_smooth, (size_t)B * T * np, P_d);
+    st.out(loglik_path, (size_t)B * max_iter, ll_d); st.out(iters, (size_t)B, it_d);
+    if (int rc = st.begin()) return rc;
+    int rc = st.finish(dfm_em_batch_dev(h, B, T, N, r, x_d, lam_d, R_d, A_d, Q_d, mu_d, P0_d, max_iter, tol, ll_d, it_d, f_d, P_d, flags));
     if (rc == 0) rc = post_check(h, loglik_path, B, (size_t)max_iter);
-    (void)hipFree(buf);
     return rc;
 }
 // ---- VAR(p) factor dynamics -------------------------------------------------------------------------
@@ -1938,45 +1966,20 @@ static int varp_host(dfm_handle* h, int B, int T, int N, int r, int p, const dou
     if (max_iter < 1) return fail(h, DFM_E_DIMS, "max_iter must be >= 1%s");
     if (int rc = status_epoch(h)) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
-    const size_t d = sizeof(double), k = (size_t)r * p, np = (size_t)r * (r + 1) / 2;
-    const size_t n_panel = (size_t)B * T * N, n_lam = (size_t)B * N * r, n_R = (size_t)B * N, n_a = (size_t)B * r * k,
-                 n_q = (size_t)B * r * r, n_v = (size_t)B * k, n_p0 = (size_t)B * k * k, n_f = (size_t)B * T * r,
-                 n_P = (size_t)B * T * np, n_ll = em ? (size_t)B * max_iter : (size_t)B;
-    const size_t total = (n_panel + n_lam + n_R + n_a + n_q + n_v + n_p0 + n_f + n_P + n_ll) * d + (size_t)B * sizeof(int);
-    double* buf = nullptr;
-    HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&buf), total));
-    double* dp = buf;
-    auto up = [&](const double* src, size_t n) -> double* {
-        double* dst = dp; dp += n;
-        (void)hipMemcpyAsync(dst, src, n * d, hipMemcpyHostToDevice, h->stream);
-        return dst;
-    };
-    double *x_d = up(panel, n_panel), *lam_d = up(Lam, n_lam), *R_d = up(R, n_R), *A_d = up(Avar, n_a), *Q_d = up(Q, n_q),
-           *mu_d = up(mu0, n_v), *P0_d = up(P0, n_p0);
-    double* f_d = dp; dp += n_f;
-    double* P_d = dp; dp += n_P;
-    double* ll_d = dp; dp += n_ll;
-    int* it_d = reinterpret_cast<int*>(dp);
-    int rc = em ? dfm_em_varp_batch_dev(h, B, T, N, r, p, x_d, lam_d, R_d, A_d, Q_d, mu_d, P0_d, max_iter, tol, ll_d, it_d,
-                                        f_smooth ? f_d : nullptr, P_smooth ? P_d : nullptr, flags)
-                : dfm_ks_pass_varp_batch_dev(h, B, T, N, r, p, x_d, lam_d, R_d, A_d, Q_d, mu_d, P0_d, f_d,
-                                             P_smooth ? P_d : nullptr, ll_d, flags);
-    if (rc == 0) {
-        auto down = [&](void* dst, const void* src, size_t bytes) { (void)hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream); };
-        if (em) {
-            down(Lam, lam_d, n_lam * d); down(R, R_d, n_R * d); down(Avar, A_d, n_a * d); down(Q, Q_d, n_q * d);
-            down(mu0, mu_d, n_v * d); down(P0, P0_d, n_p0 * d); down(loglik_path, ll_d, n_ll * d);
-            down(iters, it_d, (size_t)B * sizeof(int));
-        } else {
-            down(loglik, ll_d, n_ll * d);
-        }
-        if (f_smooth) down(f_smooth, f_d, n_f * d);
-        if (P_smooth) down(P_smooth, P_d, n_P * d);
-        hipError_t e = hipStreamSynchronize(h->stream);
-        if (e != hipSuccess) rc = hip_fail(h, e, "hipStreamSynchronize");
-    }
-    if (rc == 0) rc = post_check(h, em ? loglik_path : loglik, B, em ? (size_t)max_iter : (size_t)1);
-    (void)hipFree(buf);
+    const size_t k = (size_t)r * p, np = (size_t)r * (r + 1) / 2;
+    double* ll = em ? loglik_path : loglik;                      // [B max_iter] | [B]
+    HostStage st(h);
+    double *x_d, *lam_d, *R_d, *A_d, *Q_d, *mu_d, *P0_d, *f_d, *P_d, *ll_d;
+    int* it_d;
+    st.in(panel, (size_t)B * T * N, x_d); st.inout(Lam, (size_t)B * N * r, lam_d, em); st.inout(R, (size_t)B * N, R_d, em);
+    st.inout(Avar, (size_t)B * r * k, A_d, em); st.inout(Q, (size_t)B * r * r, Q_d, em); st.inout(mu0, (size_t)B * k, mu_d, em);
+    st.inout(P0, (size_t)B * k * k, P0_d, em);
+    st.out(f_smooth, (size_t)B * T * r, f_d); st.out(P_smooth, (size_t)B * T * np, P_d);
+    st.out(ll, em ? (size_t)B * max_iter : (size_t)B, ll_d); st.out(iters, (size_t)B, it_d);
+    if (int rc = st.begin()) return rc;
+    int rc = st.finish(em ? dfm_em_varp_batch_dev(h, B, T, N, r, p, x_d, lam_d, R_d, A_d, Q_d, mu_d, P0_d, max_iter, tol, ll_d, it_d, f_d, P_d, flags)
+                          : dfm_ks_pass_varp_batch_dev(h, B, T, N, r, p, x_d, lam_d, R_d, A_d, Q_d, mu_d, P0_d, f_d, P_d, ll_d, flags));
+    if (rc == 0) rc = post_check(h, ll, B, em ? (size_t)max_iter : (size_t)1);
     return rc;
 }
 
@@ -2002,46 +2005,42 @@ int dfm_ks_pass_ar_batch_dev(dfm_handle* h, int B, int T, int N, int r, int p, i
     return ar_pass_run(h, B, T, N, r, p, q, panel, Lam, sig2, rho, Avar, Q, mu0, P0, f_smooth, P_smooth, loglik, flags);
 }
 
+// host entry points: em = false is the pass (loglik_path = loglik [B], iters unused)
+static int ar_host(dfm_handle* h, int B, int T, int N, int r, int p, int q, const double* panel, double* Lam, double* sig2, double* rho,
+                   double* Avar, double* Q, double* mu0, double* P0, int max_iter, double tol, double* loglik_path, int* iters,
+                   double* f_smooth, double* P_smooth, unsigned flags, bool em) {
+    if (int rc = check_dims(h, B, T, N, r)) return rc;
+    if (p < 1 || q < 0 || T <= q + (em ? 1 : 0))
+        return fail(h, DFM_E_DIMS, em ? "need p >= 1, 0 <= q < T - 1%s" : "need p >= 1, 0 <= q < T%s");
+    const int m = p > q + 1 ? p : q + 1;
+    if (r * m > DFM_MAX_R) return fail(h, DFM_E_R_UNSUPPORTED, "r * max(p, q + 1) > DFM_MAX_R (32)%s");
+    if (!panel || !Lam || !sig2 || (q > 0 && !rho) || !Avar || !Q || !mu0 || !P0 || !loglik_path || (em ? !iters : !f_smooth))
+        return fail(h, DFM_E_NULL, "required pointer is NULL%s");
+    if (max_iter < 1) return fail(h, DFM_E_DIMS, "max_iter must be >= 1%s");
+    if (int rc = status_epoch(h)) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t k = (size_t)r * m, np = (size_t)r * (r + 1) / 2, Tq = (size_t)(T - q);
+    HostStage st(h);
+    double *x_d, *lam_d, *R_d, *rho_d, *A_d, *Q_d, *mu_d, *P0_d, *f_d, *P_d, *ll_d;
+    int* it_d;
+    st.in(panel, (size_t)B * T * N, x_d); st.inout(Lam, (size_t)B * N * r, lam_d, em); st.inout(sig2, (size_t)B * N, R_d, em);
+    st.inout(rho, (size_t)B * N * q, rho_d, em); st.inout(Avar, (size_t)B * r * r * p, A_d, em); st.inout(Q, (size_t)B * r * r, Q_d, em);
+    st.inout(mu0, (size_t)B * k, mu_d, em); st.inout(P0, (size_t)B * k * k, P0_d, em);
+    st.out(f_smooth, (size_t)B * Tq * r, f_d); st.out(P_smooth, (size_t)B * Tq * np, P_d);
+    st.out(loglik_path, (size_t)B * (em ? max_iter : 1), ll_d); st.out(iters, (size_t)B, it_d);
+    if (int rc = st.begin()) return rc;
+    int rc = st.finish(em ? ar_em_run(h, B, T, N, r, p, q, x_d, lam_d, R_d, rho_d, A_d, Q_d, mu_d, P0_d, max_iter, tol, ll_d, it_d, f_d, P_d, flags)
+                          : ar_pass_run(h, B, T, N, r, p, q, x_d, lam_d, R_d, rho_d, A_d, Q_d, mu_d, P0_d, f_d, P_d, ll_d, flags));
+    if (rc == 0) rc = post_check(h, loglik_path, B, em ? (size_t)max_iter : 1);
+    return rc;
+}
+
 int dfm_ks_pass_ar_batch(dfm_handle* h, int B, int T, int N, int r, int p, int q, const double* panel, const double* Lam,
                          const double* sig2, const double* rho, const double* Avar, const double* Q, const double* mu0,
                          const double* P0, double* f_smooth, double* P_smooth, double* loglik, unsigned flags) {
-    if (int rc = check_dims(h, B, T, N, r)) return rc;
-    if (p < 1 || q < 0 || T <= q) return fail(h, DFM_E_DIMS, "need p >= 1, 0 <= q < T%s");
-    const int m = p > q + 1 ? p : q + 1;
-    if (r * m > DFM_MAX_R) return fail(h, DFM_E_R_UNSUPPORTED, "r * max(p, q + 1) > DFM_MAX_R (32)%s");
-    if (!panel || !Lam || !sig2 || (q > 0 && !rho) || !Avar || !Q || !mu0 || !P0 || !f_smooth || !loglik)
-        return fail(h, DFM_E_NULL, "required pointer is NULL%s");
-    if (int rc = status_epoch(h)) return rc;
-    HIP_TRY(h, hipSetDevice(h->device));
-    const size_t d = sizeof(double), k = (size_t)r * m, np = (size_t)r * (r + 1) / 2, Tq = (size_t)(T - q);
-    const size_t n_panel = (size_t)B * T * N, n_lam = (size_t)B * N * r, n_R = (size_t)B * N, n_rho = (size_t)B * N * q,
-                 n_a = (size_t)B * r * r * p, n_q = (size_t)B * r * r, n_v = (size_t)B * k, n_p0 = (size_t)B * k * k,
-                 n_f = (size_t)B * Tq * r, n_P = (size_t)B * Tq * np;
-    double* buf = nullptr;
-    HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&buf), (n_panel + n_lam + n_R + n_rho + n_a + n_q + n_v + n_p0 + n_f + n_P + B) * d));
-    double* dp = buf;
-    auto up = [&](const double* src, size_t n) -> double* {
-        double* dst = dp; dp += n;
-        if (n) (void)hipMemcpyAsync(dst, src, n * d, hipMemcpyHostToDevice, h->stream);
-        return dst;
-    };
-    double *x_d = up(panel, n_panel), *lam_d = up(Lam, n_lam), *R_d = up(sig2, n_R), *rho_d = up(rho, n_rho),
-           *A_d = up(Avar, n_a), *Q_d = up(Q, n_q), *mu_d = up(mu0, n_v), *P0_d = up(P0, n_p0);
-    double* f_d = dp; dp += n_f;
-    double* P_d = dp; dp += n_P;
-    double* ll_d = dp;
-    int rc = ar_pass_run(h, B, T, N, r, p, q, x_d, lam_d, R_d, rho_d, A_d, Q_d, mu_d, P0_d, f_d, P_smooth ? P_d : nullptr, ll_d,
-                         flags);
-    if (rc == 0) {
-        (void)hipMemcpyAsync(f_smooth, f_d, n_f * d, hipMemcpyDeviceToHost, h->stream);
-        if (P_smooth) (void)hipMemcpyAsync(P_smooth, P_d, n_P * d, hipMemcpyDeviceToHost, h->stream);
-        (void)hipMemcpyAsync(loglik, ll_d, (size_t)B * d, hipMemcpyDeviceToHost, h->stream);
-        hipError_t e = hipStreamSynchronize(h->stream);
-        if (e != hipSuccess) rc = hip_fail(h, e, "hipStreamSynchronize");
-    }
-    if (rc == 0) rc = post_check(h, loglik, B);
-    (void)hipFree(buf);
-    return rc;
+    return ar_host(h, B, T, N, r, p, q, panel, const_cast<double*>(Lam), const_cast<double*>(sig2), const_cast<double*>(rho),
+                   const_cast<double*>(Avar), const_cast<double*>(Q), const_cast<double*>(mu0), const_cast<double*>(P0), 1, 0.0, loglik,
+                   nullptr, f_smooth, P_smooth, flags, false);
 }
 
 int dfm_em_ar_batch_dev(dfm_handle* h, int B, int T, int N, int r, int p, int q, const double* panel, double* Lam, double* sig2,
@@ -2054,49 +2053,8 @@ int dfm_em_ar_batch_dev(dfm_handle* h, int B, int T, int N, int r, int p, int q,
 int dfm_em_ar_batch(dfm_handle* h, int B, int T, int N, int r, int p, int q, const double* panel, double* Lam, double* sig2,
                     double* rho, double* Avar, double* Q, double* mu0, double* P0, int max_iter, double tol, double* loglik_path,
                     int* iters, double* f_smooth, double* P_smooth, unsigned flags) {
-    if (int rc = check_dims(h, B, T, N, r)) return rc;
-    if (p < 1 || q < 0 || T <= q + 1) return fail(h, DFM_E_DIMS, "need p >= 1, 0 <= q < T - 1%s");
-    const int m = p > q + 1 ? p : q + 1;
-    if (r * m > DFM_MAX_R) return fail(h, DFM_E_R_UNSUPPORTED, "r * max(p, q + 1) > DFM_MAX_R (32)%s");
-    if (!panel || !Lam || !sig2 || (q > 0 && !rho) || !Avar || !Q || !mu0 || !P0 || !loglik_path || !iters)
-        return fail(h, DFM_E_NULL, "required pointer is NULL%s");
-    if (max_iter < 1) return fail(h, DFM_E_DIMS, "max_iter must be >= 1%s");
-    if (int rc = status_epoch(h)) return rc;
-    HIP_TRY(h, hipSetDevice(h->device));
-    const size_t d = sizeof(double), k = (size_t)r * m, np = (size_t)r * (r + 1) / 2, Tq = (size_t)(T - q);
-    const size_t n_panel = (size_t)B * T * N, n_lam = (size_t)B * N * r, n_R = (size_t)B * N, n_rho = (size_t)B * N * q,
-                 n_a = (size_t)B * r * r * p, n_q = (size_t)B * r * r, n_v = (size_t)B * k, n_p0 = (size_t)B * k * k,
-                 n_f = (size_t)B * Tq * r, n_P = (size_t)B * Tq * np, n_ll = (size_t)B * max_iter;
-    double* buf = nullptr;
-    HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&buf),
-                         (n_panel + n_lam + n_R + n_rho + n_a + n_q + n_v + n_p0 + n_f + n_P + n_ll) * d + (size_t)B * sizeof(int)));
-    double* dp = buf;
-    auto up = [&](const double* src, size_t n) -> double* {
-        double* dst = dp; dp += n;
-        if (n) (void)hipMemcpyAsync(dst, src, n * d, hipMemcpyHostToDevice, h->stream);
-        return dst;
-    };
-    double *x_d = up(panel, n_panel), *lam_d = up(Lam, n_lam), *R_d = up(sig2, n_R), *rho_d = up(rho, n_rho),
-           *A_d = up(Avar, n_a), *Q_d = up(Q, n_q), *mu_d = up(mu0, n_v), *P0_d = up(P0, n_p0);
-    double* f_d = dp; dp += n_f;
-    double* P_d = dp; dp += n_P;
-    double* ll_d = dp; dp += n_ll;
-    int* it_d = reinterpret_cast<int*>(dp);
-    int rc = ar_em_run(h, B, T, N, r, p, q, x_d, lam_d, R_d, rho_d, A_d, Q_d, mu_d, P0_d, max_iter, tol, ll_d, it_d,
-                       f_smooth ? f_d : nullptr, P_smooth ? P_d : nullptr, flags);
-    if (rc == 0) {
-        auto down = [&](void* dst, const void* src, size_t bytes) { if (bytes) (void)hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream); };
-        down(Lam, lam_d, n_lam * d); down(sig2, R_d, n_R * d); down(rho, rho_d, n_rho * d); down(Avar, A_d, n_a * d);
-        down(Q, Q_d, n_q * d); down(mu0, mu_d, n_v * d); down(P0, P0_d, n_p0 * d); down(loglik_path, ll_d, n_ll * d);
-        down(iters, it_d, (size_t)B * sizeof(int));
-        if (f_smooth) down(f_smooth, f_d, n_f * d);
-        if (P_smooth) down(P_smooth, P_d, n_P * d);
-        hipError_t e = hipStreamSynchronize(h->stream);
-        if (e != hipSuccess) rc = hip_fail(h, e, "hipStreamSynchronize");
-    }
-    if (rc == 0) rc = post_check(h, loglik_path, B, (size_t)max_iter);
-    (void)hipFree(buf);
-    return rc;
+    return ar_host(h, B, T, N, r, p, q, panel, Lam, sig2, rho, Avar, Q, mu0, P0, max_iter, tol, loglik_path, iters, f_smooth, P_smooth,
+                   flags, true);
 }
 
 // ---- mixed frequency ---------------------------------------------------------------------------------------------------
@@ -2123,43 +2081,19 @@ static int mf_host(dfm_handle* h, int B, int T, int N, int r, int p, int L, cons
     if (max_iter < 1) return fail(h, DFM_E_DIMS, "max_iter must be >= 1%s");
     if (int rc = status_epoch(h)) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
-    const int m = p > L ? p : L;
-    const size_t d = sizeof(double), k = (size_t)r * m, np = (size_t)r * (r + 1) / 2;
-    const size_t n_panel = (size_t)B * T * N, n_lam = (size_t)B * N * r, n_R = (size_t)B * N, n_w = (size_t)N * L,
-                 n_a = (size_t)B * r * r * p, n_q = (size_t)B * r * r, n_v = (size_t)B * k, n_p0 = (size_t)B * k * k,
-                 n_f = (size_t)B * T * r, n_P = (size_t)B * T * np, n_ll = (size_t)B * (em ? max_iter : 1);
-    double* buf = nullptr;
-    HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&buf),
-                         (n_panel + n_lam + n_R + n_w + n_a + n_q + n_v + n_p0 + n_f + n_P + n_ll) * d + (size_t)B * sizeof(int)));
-    double* dp = buf;
-    auto up = [&](const double* src, size_t n) -> double* {
-        double* dst = dp; dp += n;
-        if (n) (void)hipMemcpyAsync(dst, src, n * d, hipMemcpyHostToDevice, h->stream);
-        return dst;
-    };
-    double *x_d = up(panel, n_panel), *lam_d = up(Lam, n_lam), *R_d = up(R, n_R), *w_d = up(W, n_w), *A_d = up(Avar, n_a),
-           *Q_d = up(Q, n_q), *mu_d = up(mu0, n_v), *P0_d = up(P0, n_p0);
-    double* f_d = dp; dp += n_f;
-    double* P_d = dp; dp += n_P;
-    double* ll_d = dp; dp += n_ll;
-    int* it_d = reinterpret_cast<int*>(dp);
-    int rc = em ? mf_run(h, B, T, N, r, p, L, x_d, lam_d, R_d, w_d, A_d, Q_d, mu_d, P0_d, max_iter, tol, ll_d, it_d,
-                         f_smooth ? f_d : nullptr, P_smooth ? P_d : nullptr, flags)
-                : mf_pass_run(h, B, T, N, r, p, L, x_d, lam_d, R_d, w_d, A_d, Q_d, mu_d, P0_d, f_d, P_smooth ? P_d : nullptr, ll_d, flags);
-    if (rc == 0) {
-        auto down = [&](void* dst, const void* src, size_t bytes) { if (bytes) (void)hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream); };
-        if (em) {
-            down(Lam, lam_d, n_lam * d); down(R, R_d, n_R * d); down(Avar, A_d, n_a * d); down(Q, Q_d, n_q * d);
-            down(mu0, mu_d, n_v * d); down(P0, P0_d, n_p0 * d); down(iters, it_d, (size_t)B * sizeof(int));
-        }
-        down(loglik_path, ll_d, n_ll * d);
-        if (f_smooth) down(f_smooth, f_d, n_f * d);
-        if (P_smooth) down(P_smooth, P_d, n_P * d);
-        hipError_t e = hipStreamSynchronize(h->stream);
-        if (e != hipSuccess) rc = hip_fail(h, e, "hipStreamSynchronize");
-    }
+    const size_t k = (size_t)r * (p > L ? p : L), np = (size_t)r * (r + 1) / 2;
+    HostStage st(h);
+    double *x_d, *lam_d, *R_d, *w_d, *A_d, *Q_d, *mu_d, *P0_d, *f_d, *P_d, *ll_d;
+    int* it_d;
+    st.in(panel, (size_t)B * T * N, x_d); st.inout(Lam, (size_t)B * N * r, lam_d, em); st.inout(R, (size_t)B * N, R_d, em);
+    st.in(W, (size_t)N * L, w_d); st.inout(Avar, (size_t)B * r * r * p, A_d, em); st.inout(Q, (size_t)B * r * r, Q_d, em);
+    st.inout(mu0, (size_t)B * k, mu_d, em); st.inout(P0, (size_t)B * k * k, P0_d, em);
+    st.out(f_smooth, (size_t)B * T * r, f_d); st.out(P_smooth, (size_t)B * T * np, P_d);
+    st.out(loglik_path, (size_t)B * (em ? max_iter : 1), ll_d); st.out(iters, (size_t)B, it_d);
+    if (int rc = st.begin()) return rc;
+    int rc = st.finish(em ? mf_run(h, B, T, N, r, p, L, x_d, lam_d, R_d, w_d, A_d, Q_d, mu_d, P0_d, max_iter, tol, ll_d, it_d, f_d, P_d, flags)
+                          : mf_pass_run(h, B, T, N, r, p, L, x_d, lam_d, R_d, w_d, A_d, Q_d, mu_d, P0_d, f_d, P_d, ll_d, flags));
     if (rc == 0) rc = post_check(h, loglik_path, B, em ? (size_t)max_iter : 1);
-    (void)hipFree(buf);
     return rc;
 }
 
@@ -2198,38 +2132,18 @@ int dfm_em_obs_batch(dfm_handle* h, int B, int T, int N, int r_u, int r_o, const
         if (G[k] != G[k]) return fail(h, DFM_E_MISSING, "observed factors must not contain NaN%s");
     if (int rc = status_epoch(h)) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
-    const size_t d = sizeof(double), re = (size_t)r_o + r_u, np = (size_t)r_u * (r_u + 1) / 2;
-    const size_t n_panel = (size_t)B * T * N, n_g = (size_t)B * T * r_o, n_lam = (size_t)B * N * re, n_R = (size_t)B * N,
-                 n_m = (size_t)B * r_u * r_u, n_v = (size_t)B * r_u, n_f = (size_t)B * T * r_u, n_P = (size_t)B * T * np,
-                 n_ll = (size_t)B * max_iter;
-    double* buf = nullptr;
-    HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&buf), (n_panel + n_g + n_lam + n_R + 3 * n_m + n_v + n_f + n_P + n_ll) * d + (size_t)B * sizeof(int)));
-    double* dp = buf;
-    auto up = [&](const double* src, size_t n) -> double* {
-        double* dst = dp; dp += n;
-        (void)hipMemcpyAsync(dst, src, n * d, hipMemcpyHostToDevice, h->stream);
-        return dst;
-    };
-    double *x_d = up(panel, n_panel), *g_d = up(G, n_g), *lam_d = up(Lam, n_lam), *R_d = up(R, n_R), *A_d = up(A, n_m),
-           *Q_d = up(Q, n_m), *mu_d = up(mu0, n_v), *P0_d = up(P0, n_m);
-    double* f_d = dp; dp += n_f;
-    double* P_d = dp; dp += n_P;
-    double* ll_d = dp; dp += n_ll;
-    int* it_d = reinterpret_cast<int*>(dp);
-    int rc = obs_em_run(h, B, T, N, r_u, r_o, x_d, g_d, lam_d, R_d, A_d, Q_d, mu_d, P0_d, max_iter, tol, ll_d, it_d,
-                        f_smooth ? f_d : nullptr, P_smooth ? P_d : nullptr, flags);
-    if (rc == 0) {
-        auto down = [&](void* dst, const void* src, size_t bytes) { (void)hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream); };
-        down(Lam, lam_d, n_lam * d); down(R, R_d, n_R * d); down(A, A_d, n_m * d); down(Q, Q_d, n_m * d);
-        down(mu0, mu_d, n_v * d); down(P0, P0_d, n_m * d); down(loglik_path, ll_d, n_ll * d);
-        down(iters, it_d, (size_t)B * sizeof(int));
-        if (f_smooth) down(f_smooth, f_d, n_f * d);
-        if (P_smooth) down(P_smooth, P_d, n_P * d);
-        hipError_t e = hipStreamSynchronize(h->stream);
-        if (e != hipSuccess) rc = hip_fail(h, e, "hipStreamSynchronize");
-    }
+    const size_t re = (size_t)r_o + r_u, np = (size_t)r_u * (r_u + 1) / 2, n_m = (size_t)B * r_u * r_u;
+    HostStage st(h);
+    double *x_d, *g_d, *lam_d, *R_d, *A_d, *Q_d, *mu_d, *P0_d, *f_d, *P_d, *ll_d;
+    int* it_d;
+    st.in(panel, (size_t)B * T * N, x_d); st.in(G, (size_t)B * T * r_o, g_d); st.inout(Lam, (size_t)B * N * re, lam_d);
+    st.inout(R, (size_t)B * N, R_d); st.inout(A, n_m, A_d); st.inout(Q, n_m, Q_d); st.inout(mu0, (size_t)B * r_u, mu_d);
+    st.inout(P0, n_m, P0_d);
+    st.out(f_smooth, (size_t)B * T * r_u, f_d); st.out(P_smooth, (size_t)B * T * np, P_d);
+    st.out(loglik_path, (size_t)B * max_iter, ll_d); st.out(iters, (size_t)B, it_d);
+    if (int rc = st.begin()) return rc;
+    int rc = st.finish(obs_em_run(h, B, T, N, r_u, r_o, x_d, g_d, lam_d, R_d, A_d, Q_d, mu_d, P0_d, max_iter, tol, ll_d, it_d, f_d, P_d, flags));
     if (rc == 0) rc = post_check(h, loglik_path, B, (size_t)max_iter);
-    (void)hipFree(buf);
     return rc;
 }
 
@@ -2267,27 +2181,16 @@ int dfm_pca_init_batch(dfm_handle* h, int B, int T, int N, int r, const double* 
     if (!panel || !Lam || !R || !A || !Q || !mu0 || !P0) return fail(h, DFM_E_NULL, "required pointer is NULL%s");
     if (int rc = status_epoch(h)) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
-    const size_t d = sizeof(double);
-    const size_t n_panel = (size_t)B * T * N, n_lam = (size_t)B * N * r, n_R = (size_t)B * N, n_m = (size_t)B * r * r,
-                 n_v = (size_t)B * r, n_f = (size_t)B * T * r;
+    const size_t n_panel = (size_t)B * T * N, n_m = (size_t)B * r * r;
     for (size_t k = 0; k < n_panel; ++k)
         if (panel[k] != panel[k]) return fail(h, DFM_E_MISSING, "PCA initialisation needs a balanced panel (NaN found)%s");
-    double* buf = nullptr;
-    HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&buf), (n_panel + n_lam + n_R + 3 * n_m + n_v + n_f) * d));
-    double* x_d = buf; double* lam_d = x_d + n_panel; double* R_d = lam_d + n_lam; double* A_d = R_d + n_R;
-    double* Q_d = A_d + n_m; double* P0_d = Q_d + n_m; double* mu_d = P0_d + n_m; double* f_d = mu_d + n_v;
-    (void)hipMemcpyAsync(x_d, panel, n_panel * d, hipMemcpyHostToDevice, h->stream);
-    int rc = dfm_pca_init_batch_dev(h, B, T, N, r, x_d, lam_d, R_d, A_d, Q_d, mu_d, P0_d, factors ? f_d : nullptr);
-    if (rc == 0) {
-        auto down = [&](void* dst, const void* src, size_t bytes) { (void)hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream); };
-        down(Lam, lam_d, n_lam * d); down(R, R_d, n_R * d); down(A, A_d, n_m * d); down(Q, Q_d, n_m * d);
-        down(mu0, mu_d, n_v * d); down(P0, P0_d, n_m * d);
-        if (factors) down(factors, f_d, n_f * d);
-        hipError_t e = hipStreamSynchronize(h->stream);
-        if (e != hipSuccess) rc = hip_fail(h, e, "hipStreamSynchronize");
-    }
+    HostStage st(h);
+    double *x_d, *lam_d, *R_d, *A_d, *Q_d, *P0_d, *mu_d, *f_d;
+    st.in(panel, n_panel, x_d); st.out(Lam, (size_t)B * N * r, lam_d); st.out(R, (size_t)B * N, R_d); st.out(A, n_m, A_d);
+    st.out(Q, n_m, Q_d); st.out(P0, n_m, P0_d); st.out(mu0, (size_t)B * r, mu_d); st.out(factors, (size_t)B * T * r, f_d);
+    if (int rc = st.begin()) return rc;
+    int rc = st.finish(dfm_pca_init_batch_dev(h, B, T, N, r, x_d, lam_d, R_d, A_d, Q_d, mu_d, P0_d, f_d));
     if (rc == 0) rc = status_check(h);
-    (void)hipFree(buf);
     return rc;
 }
 int dfm_synth_panels_dev(dfm_handle* h, uint64_t seed, int64_t first_replicate, int B, int T, int N, int r,
@@ -2344,35 +2247,15 @@ int dfm_als_batch(dfm_handle* h, int B, int T, int N, int r, const double* z, lo
     if (B < 1 || T < 1 || N < 1 || r < 1 || z_stride < 0) return fail(h, DFM_E_DIMS, "B, T, N, r must be >= 1%s");
     if (!z || !F || !Lam || !iters || !ssr) return fail(h, DFM_E_NULL, "required pointer is NULL%s");
     HIP_TRY(h, hipSetDevice(h->device));
-    const size_t d = sizeof(double);
     const size_t n_z = z_stride == 0 ? (size_t)T * N : (size_t)(B - 1) * z_stride + (size_t)T * N;
-    const size_t n_F = (size_t)B * T * r, n_L = (size_t)B * N * r, n_p = ssr_path ? (size_t)B * path_cap : 0,
-                 n_R2 = R2 ? (size_t)B * N : 0;
-    char* buf = nullptr;
-    const size_t bytes = (n_z + n_F + n_L + n_p + n_R2 + B) * d + (size_t)2 * B * sizeof(int) + 64;
-    HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&buf), bytes));
-    double* z_d = reinterpret_cast<double*>(buf);
-    double* F_d = z_d + n_z; double* L_d = F_d + n_F; double* p_d = L_d + n_L; double* R2_d = p_d + n_p;
-    double* ssr_d = R2_d + n_R2;
-    int* it_d = reinterpret_cast<int*>(ssr_d + B);
-    int* re_d = it_d + B;
-    hipMemcpyAsync(z_d, z, n_z * d, hipMemcpyHostToDevice, h->stream);
-    hipMemcpyAsync(F_d, F, n_F * d, hipMemcpyHostToDevice, h->stream);
-    if (r_each) hipMemcpyAsync(re_d, r_each, (size_t)B * sizeof(int), hipMemcpyHostToDevice, h->stream);
-    int rc = dfm_als_batch_dev(h, B, T, N, r, z_d, z_stride, r_each ? re_d : nullptr, F_d, L_d, nt_min, max_iter, tol,
-                               ssr_path ? p_d : nullptr, path_cap, it_d, ssr_d, R2 ? R2_d : nullptr);
-    if (rc == 0) {
-        hipMemcpyAsync(F, F_d, n_F * d, hipMemcpyDeviceToHost, h->stream);
-        hipMemcpyAsync(Lam, L_d, n_L * d, hipMemcpyDeviceToHost, h->stream);
-        if (ssr_path) hipMemcpyAsync(ssr_path, p_d, n_p * d, hipMemcpyDeviceToHost, h->stream);
-        if (R2) hipMemcpyAsync(R2, R2_d, n_R2 * d, hipMemcpyDeviceToHost, h->stream);
-        hipMemcpyAsync(ssr, ssr_d, (size_t)B * d, hipMemcpyDeviceToHost, h->stream);
-        hipMemcpyAsync(iters, it_d, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, h->stream);
-        hipError_t e = hipStreamSynchronize(h->stream);
-        if (e != hipSuccess) rc = hip_fail(h, e, "hipStreamSynchronize");
-    }
-    hipFree(buf);
-    return rc;
+    HostStage st(h);
+    double *z_d, *F_d, *L_d, *p_d, *R2_d, *ssr_d;
+    int *it_d, *re_d;
+    st.in(z, n_z, z_d); st.inout(F, (size_t)B * T * r, F_d); st.out(Lam, (size_t)B * N * r, L_d);
+    st.out(ssr_path, ssr_path ? (size_t)B * path_cap : 0, p_d); st.out(R2, R2 ? (size_t)B * N : 0, R2_d); st.out(ssr, (size_t)B, ssr_d);
+    st.out(iters, (size_t)B, it_d); st.in(r_each, (size_t)B, re_d);
+    if (int rc = st.begin()) return rc;
+    return st.finish(dfm_als_batch_dev(h, B, T, N, r, z_d, z_stride, re_d, F_d, L_d, nt_min, max_iter, tol, p_d, path_cap, it_d, ssr_d, R2_d));
 }
 
 int dfm_ols_batch_dev(dfm_handle* h, int P, int T, int K, const double* X, long long x_stride, const double* y,
@@ -2400,31 +2283,15 @@ int dfm_ols_batch(dfm_handle* h, int P, int T, int K, const double* X, long long
         return fail(h, DFM_E_DIMS, "P, T, K, y_inc must be >= 1, strides >= 0%s");
     if (!X || !y || !beta || !ssr || !nobs) return fail(h, DFM_E_NULL, "required pointer is NULL%s");
     HIP_TRY(h, hipSetDevice(h->device));
-    const size_t d = sizeof(double);
     const size_t n_X = (x_stride == 0 ? 0 : (size_t)(P - 1) * x_stride) + (size_t)T * K;
     const size_t n_y = (size_t)(P - 1) * y_stride + (size_t)(T - 1) * y_inc + 1;
-    const size_t n_b = (size_t)P * K, n_e = resid ? (size_t)P * T : 0;
-    char* buf = nullptr;
-    HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&buf), (n_X + n_y + n_b + n_e + 2 * (size_t)P) * d + (size_t)P * sizeof(int) + 64));
-    double* X_d = reinterpret_cast<double*>(buf);
-    double* y_d = X_d + n_X; double* b_d = y_d + n_y; double* e_d = b_d + n_b; double* ssr_d = e_d + n_e;
-    double* tss_d = ssr_d + P;
-    int* n_d = reinterpret_cast<int*>(tss_d + P);
-    hipMemcpyAsync(X_d, X, n_X * d, hipMemcpyHostToDevice, h->stream);
-    hipMemcpyAsync(y_d, y, n_y * d, hipMemcpyHostToDevice, h->stream);
-    int rc = dfm_ols_batch_dev(h, P, T, K, X_d, x_stride, y_d, y_stride, y_inc, nt_min, b_d, resid ? e_d : nullptr, ssr_d,
-                               tss_d, n_d);
-    if (rc == 0) {
-        hipMemcpyAsync(beta, b_d, n_b * d, hipMemcpyDeviceToHost, h->stream);
-        if (resid) hipMemcpyAsync(resid, e_d, n_e * d, hipMemcpyDeviceToHost, h->stream);
-        hipMemcpyAsync(ssr, ssr_d, (size_t)P * d, hipMemcpyDeviceToHost, h->stream);
-        if (tss) hipMemcpyAsync(tss, tss_d, (size_t)P * d, hipMemcpyDeviceToHost, h->stream);
-        hipMemcpyAsync(nobs, n_d, (size_t)P * sizeof(int), hipMemcpyDeviceToHost, h->stream);
-        hipError_t e = hipStreamSynchronize(h->stream);
-        if (e != hipSuccess) rc = hip_fail(h, e, "hipStreamSynchronize");
-    }
-    hipFree(buf);
-    return rc;
+    HostStage st(h);
+    double *X_d, *y_d, *b_d, *e_d, *ssr_d, *tss_d;
+    int* n_d;
+    st.in(X, n_X, X_d); st.in(y, n_y, y_d); st.out(beta, (size_t)P * K, b_d); st.out(resid, resid ? (size_t)P * T : 0, e_d);
+    st.out(ssr, (size_t)P, ssr_d); st.out(tss, (size_t)P, tss_d); st.out(nobs, (size_t)P, n_d);
+    if (int rc = st.begin()) return rc;
+    return st.finish(dfm_ols_batch_dev(h, P, T, K, X_d, x_stride, y_d, y_stride, y_inc, nt_min, b_d, e_d, ssr_d, tss_d, n_d));
 }
 
 
@@ -2456,26 +2323,13 @@ int dfm_var_bootstrap_irf(dfm_handle* h, int B, int T, int ns, int p, int H, con
     if (B < 1 || ns < 1 || p < 1 || H < 1 || T < 1) return fail(h, DFM_E_DIMS, "B, T, ns, p, H must be >= 1%s");
     if (!y || !betahat || !resid || !irf) return fail(h, DFM_E_NULL, "required pointer is NULL%s");
     HIP_TRY(h, hipSetDevice(h->device));
-    const size_t d = sizeof(double), K = 1 + (size_t)ns * p;
-    const size_t n_y = (size_t)T * ns, n_b = K * ns, n_s = signs ? (size_t)B * T : 0, n_bo = beta_out ? (size_t)B * K * ns : 0,
-                 n_irf = (size_t)B * ns * H * ns;
-    double* buf = nullptr;
-    HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&buf), (2 * n_y + n_b + n_s + n_bo + n_irf) * d));
-    double *y_d = buf, *b_d = y_d + n_y, *e_d = b_d + n_b, *s_d = e_d + n_y, *bo_d = s_d + n_s, *irf_d = bo_d + n_bo;
-    hipMemcpyAsync(y_d, y, n_y * d, hipMemcpyHostToDevice, h->stream);
-    hipMemcpyAsync(b_d, betahat, n_b * d, hipMemcpyHostToDevice, h->stream);
-    hipMemcpyAsync(e_d, resid, n_y * d, hipMemcpyHostToDevice, h->stream);
-    if (signs) hipMemcpyAsync(s_d, signs, n_s * d, hipMemcpyHostToDevice, h->stream);
-    int rc = dfm_var_bootstrap_irf_dev(h, B, T, ns, p, H, y_d, b_d, e_d, signs ? s_d : nullptr, seed, first_draw,
-                                       beta_out ? bo_d : nullptr, irf_d);
-    if (rc == 0) {
-        hipMemcpyAsync(irf, irf_d, n_irf * d, hipMemcpyDeviceToHost, h->stream);
-        if (beta_out) hipMemcpyAsync(beta_out, bo_d, n_bo * d, hipMemcpyDeviceToHost, h->stream);
-        hipError_t e = hipStreamSynchronize(h->stream);
-        if (e != hipSuccess) rc = hip_fail(h, e, "hipStreamSynchronize");
-    }
-    hipFree(buf);
-    return rc;
+    const size_t K = 1 + (size_t)ns * p, n_y = (size_t)T * ns;
+    HostStage st(h);
+    double *y_d, *b_d, *e_d, *s_d, *bo_d, *irf_d;
+    st.in(y, n_y, y_d); st.in(betahat, K * ns, b_d); st.in(resid, n_y, e_d); st.in(signs, signs ? (size_t)B * T : 0, s_d);
+    st.out(beta_out, beta_out ? (size_t)B * K * ns : 0, bo_d); st.out(irf, (size_t)B * ns * H * ns, irf_d);
+    if (int rc = st.begin()) return rc;
+    return st.finish(dfm_var_bootstrap_irf_dev(h, B, T, ns, p, H, y_d, b_d, e_d, s_d, seed, first_draw, bo_d, irf_d));
 }
 
 int dfm_quantile_bands_dev(dfm_handle* h, int B, int S, int nq, const double* x, const double* q, double* out) {
@@ -2494,20 +2348,11 @@ int dfm_quantile_bands(dfm_handle* h, int B, int S, int nq, const double* x, con
     if (B < 1 || S < 1 || nq < 1) return fail(h, DFM_E_DIMS, "B, S, nq must be >= 1%s");
     if (!x || !q || !out) return fail(h, DFM_E_NULL, "required pointer is NULL%s");
     HIP_TRY(h, hipSetDevice(h->device));
-    const size_t d = sizeof(double), n_x = (size_t)B * S, n_o = (size_t)nq * S;
-    double* buf = nullptr;
-    HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&buf), (n_x + nq + n_o) * d));
-    double *x_d = buf, *q_d = x_d + n_x, *o_d = q_d + nq;
-    hipMemcpyAsync(x_d, x, n_x * d, hipMemcpyHostToDevice, h->stream);
-    hipMemcpyAsync(q_d, q, (size_t)nq * d, hipMemcpyHostToDevice, h->stream);
-    int rc = dfm_quantile_bands_dev(h, B, S, nq, x_d, q_d, o_d);
-    if (rc == 0) {
-        hipMemcpyAsync(out, o_d, n_o * d, hipMemcpyDeviceToHost, h->stream);
-        hipError_t e = hipStreamSynchronize(h->stream);
-        if (e != hipSuccess) rc = hip_fail(h, e, "hipStreamSynchronize");
-    }
-    hipFree(buf);
-    return rc;
+    HostStage st(h);
+    double *x_d, *q_d, *o_d;
+    st.in(x, (size_t)B * S, x_d); st.in(q, (size_t)nq, q_d); st.out(out, (size_t)nq * S, o_d);
+    if (int rc = st.begin()) return rc;
+    return st.finish(dfm_quantile_bands_dev(h, B, S, nq, x_d, q_d, o_d));
 }
 
 
@@ -2540,27 +2385,14 @@ int dfm_chow_batch(dfm_handle* h, int S, int Tmax, int k, const double* y, const
             return fail(h, DFM_E_DIMS, "problem list: series, break date or bandwidth out of range%s");
     }
     HIP_TRY(h, hipSetDevice(h->device));
-    const size_t d = sizeof(double), n_y = (size_t)S * Tmax, n_X = n_y * k;
-    char* buf = nullptr;
-    HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&buf), (n_y + n_X + P) * d + ((size_t)S + 3 * (size_t)P) * sizeof(int) + 64));
-    double* y_d = reinterpret_cast<double*>(buf);
-    double* X_d = y_d + n_y; double* c_d = X_d + n_X;
-    int* T_d = reinterpret_cast<int*>(c_d + P);
-    int* ps_d = T_d + S; int* pb_d = ps_d + P; int* pq_d = pb_d + P;
-    hipMemcpyAsync(y_d, y, n_y * d, hipMemcpyHostToDevice, h->stream);
-    hipMemcpyAsync(X_d, X, n_X * d, hipMemcpyHostToDevice, h->stream);
-    hipMemcpyAsync(T_d, Tlen, (size_t)S * sizeof(int), hipMemcpyHostToDevice, h->stream);
-    hipMemcpyAsync(ps_d, prob_series, (size_t)P * sizeof(int), hipMemcpyHostToDevice, h->stream);
-    hipMemcpyAsync(pb_d, prob_break, (size_t)P * sizeof(int), hipMemcpyHostToDevice, h->stream);
-    hipMemcpyAsync(pq_d, prob_q, (size_t)P * sizeof(int), hipMemcpyHostToDevice, h->stream);
-    int rc = dfm_chow_batch_dev(h, S, Tmax, k, y_d, X_d, T_d, P, ps_d, pb_d, pq_d, c_d);
-    if (rc == 0) {
-        hipMemcpyAsync(chow, c_d, (size_t)P * d, hipMemcpyDeviceToHost, h->stream);
-        hipError_t e = hipStreamSynchronize(h->stream);
-        if (e != hipSuccess) rc = hip_fail(h, e, "hipStreamSynchronize");
-    }
-    hipFree(buf);
-    return rc;
+    const size_t n_y = (size_t)S * Tmax;
+    HostStage st(h);
+    double *y_d, *X_d, *c_d;
+    int *T_d, *ps_d, *pb_d, *pq_d;
+    st.in(y, n_y, y_d); st.in(X, n_y * k, X_d); st.out(chow, (size_t)P, c_d);
+    st.in(Tlen, (size_t)S, T_d); st.in(prob_series, (size_t)P, ps_d); st.in(prob_break, (size_t)P, pb_d); st.in(prob_q, (size_t)P, pq_d);
+    if (int rc = st.begin()) return rc;
+    return st.finish(dfm_chow_batch_dev(h, S, Tmax, k, y_d, X_d, T_d, P, ps_d, pb_d, pq_d, c_d));
 }
 
 
@@ -2580,19 +2412,6 @@ int dfm_standardize_batch_dev(dfm_handle* h, int B, int T, int N, double* panel,
 // P_out in the T + H row layout).  p > 1: the panel with H all-missing rows appended goes into xhat, the companion pass runs on it
 // as a (T + H)-row panel with missing cells straight into f_out / P_out (the smoothed moments of the empty rows are the forecast
 // moments), forecast_fill_kernel rewrites xhat in place.
-static int ensure_fc(dfm_handle* h, size_t bytes) {
-    if (bytes <= h->fc_bytes) return 0;
-    if (h->fc) {
-        HIP_TRY(h, hipDeviceSynchronize());
-        HIP_TRY(h, hipFree(h->fc));
-        h->fc = nullptr;
-        h->fc_bytes = 0;
-    }
-    HIP_TRY(h, hipMalloc(&h->fc, bytes));
-    h->fc_bytes = bytes;
-    return 0;
-}
-
 int dfm_forecast_batch_dev(dfm_handle* h, int B, int T, int N, int r, int p, int H, const double* panel, const double* Lam,
                            const double* R, const double* Avar, const double* Q, const double* mu0, const double* P0,
                            const double* mean, const double* sd, double* xhat, double* xvar, double* common, double* f_out,
@@ -2616,12 +2435,10 @@ int dfm_forecast_batch_dev(dfm_handle* h, int B, int T, int N, int r, int p, int
         const size_t o_f = take(off, (size_t)B * T * r * d), o_P = needP ? take(off, (size_t)B * T * np * d) : (size_t)-1,
                      o_ft = H ? take(off, (size_t)B * H * r * d) : (size_t)-1,
                      o_Pt = (H && needP) ? take(off, (size_t)B * H * np * d) : (size_t)-1, o_ll = take(off, (size_t)B * d);
-        if (int rc = ensure_fc(h, off)) return rc;
-        char* base = static_cast<char*>(h->fc);
-        auto ptr = [&](size_t o) { return o == (size_t)-1 ? nullptr : reinterpret_cast<double*>(base + o); };
-        double *fsm = ptr(o_f), *Psm = ptr(o_P), *ft = ptr(o_ft), *Pt = ptr(o_Pt);
-        if (int rc = dfm_ks_pass_batch_dev(h, B, T, N, r, panel, Lam, R, Avar, Q, mu0, P0, fsm, Psm, loglik ? loglik : ptr(o_ll),
-                                           flags)) return rc;
+        HIP_TRY(h, h->fc.grow(off));
+        double *fsm = at<double>(h->fc, o_f), *Psm = at<double>(h->fc, o_P), *ft = at<double>(h->fc, o_ft), *Pt = at<double>(h->fc, o_Pt);
+        if (int rc = dfm_ks_pass_batch_dev(h, B, T, N, r, panel, Lam, R, Avar, Q, mu0, P0, fsm, Psm,
+                                           loglik ? loglik : at<double>(h->fc, o_ll), flags)) return rc;
         if (H) {
             FcTailArgs ta{B, T, H, r, fsm, Psm, Avar, Q, ft, Pt};
             ProfScope ps(h, K_FC_TAIL);
@@ -2634,15 +2451,14 @@ int dfm_forecast_batch_dev(dfm_handle* h, int B, int T, int N, int r, int p, int
         double* Pbuf = P_out;
         size_t off = 0;
         const size_t o_P = (!P_out && xvar) ? take(off, (size_t)B * TH * np * d) : (size_t)-1, o_ll = take(off, (size_t)B * d);
-        if (int rc = ensure_fc(h, off)) return rc;
-        char* base = static_cast<char*>(h->fc);
-        if (o_P != (size_t)-1) Pbuf = reinterpret_cast<double*>(base + o_P);
+        HIP_TRY(h, h->fc.grow(off));
+        if (o_P != (size_t)-1) Pbuf = at<double>(h->fc, o_P);
         {
             ProfScope ps(h, K_FC_PAD);
             HIP_TRY(h, launch_forecast_pad(B, T, H, N, panel, xhat, !(flags & DFM_F_MAY_HAVE_MISSING), h->status_dev, h->stream));
         }
         if (int rc = dfm_ks_pass_varp_batch_dev(h, B, (int)TH, N, r, p, xhat, Lam, R, Avar, Q, mu0, P0, f_out, Pbuf,
-                                                loglik ? loglik : reinterpret_cast<double*>(base + o_ll),
+                                                loglik ? loglik : at<double>(h->fc, o_ll),
                                                 flags | DFM_F_MAY_HAVE_MISSING)) return rc;
         fa.panel = xhat; fa.panel_rows = (int)TH;
         fa.fh = f_out; fa.Ph = xvar ? Pbuf : nullptr; fa.Th = (int)TH; fa.ft = nullptr; fa.Pt = nullptr;
@@ -2666,44 +2482,20 @@ int dfm_forecast_batch(dfm_handle* h, int B, int T, int N, int r, int p, int H, 
     if ((mean == nullptr) != (sd == nullptr)) return fail(h, DFM_E_NULL, "mean and sd must both be given or both be NULL%s");
     if (int rc = status_epoch(h)) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
-    const size_t d = sizeof(double), k = (size_t)r * p, np = (size_t)r * (r + 1) / 2, TH = (size_t)T + H;
-    const size_t n_panel = (size_t)B * T * N, n_lam = (size_t)B * N * r, n_R = (size_t)B * N, n_a = (size_t)B * r * k,
-                 n_q = (size_t)B * r * r, n_v = (size_t)B * k, n_p0 = (size_t)B * k * k, n_x = (size_t)B * TH * N,
-                 n_f = (size_t)B * TH * r, n_P = (size_t)B * TH * np;
-    const size_t total = n_panel + n_lam + n_R + n_a + n_q + n_v + n_p0 + (mean ? 2 * n_R : 0) + n_x * (1 + (xvar ? 1 : 0) + (common ? 1 : 0)) +
-                         n_f + (P_out ? n_P : 0) + B + 16 * 32;   // (+ every array 256-byte aligned: the fill kernel's 16-byte accesses)
-    double* buf = nullptr;
-    HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&buf), total * d));
-    double* dp = buf;
-    auto take_d = [&](size_t n) { double* dst = dp; dp += (n + 31) & ~(size_t)31; return dst; };
-    auto up = [&](const double* src, size_t n) -> double* {
-        double* dst = take_d(n);
-        (void)hipMemcpyAsync(dst, src, n * d, hipMemcpyHostToDevice, h->stream);
-        return dst;
-    };
-    auto out = [&](bool want, size_t n) -> double* { return want ? take_d(n) : nullptr; };
-    double *x_d = up(panel, n_panel), *lam_d = up(Lam, n_lam), *R_d = up(R, n_R), *A_d = up(Avar, n_a), *Q_d = up(Q, n_q),
-           *mu_d = up(mu0, n_v), *P0_d = up(P0, n_p0);
-    double *mean_d = mean ? up(mean, n_R) : nullptr, *sd_d = sd ? up(sd, n_R) : nullptr;
-    double *xh_d = out(true, n_x), *xv_d = out(xvar != nullptr, n_x), *cm_d = out(common != nullptr, n_x), *f_d = out(true, n_f),
-           *P_d = out(P_out != nullptr, n_P), *ll_d = out(true, (size_t)B);
-    int rc = dfm_forecast_batch_dev(h, B, T, N, r, p, H, x_d, lam_d, R_d, A_d, Q_d, mu_d, P0_d, mean_d, sd_d, xh_d, xv_d, cm_d,
-                                    f_d, P_d, ll_d, flags);
-    std::vector<double> ll_host((size_t)B);
-    if (rc == 0) {
-        auto down = [&](void* dst, const void* src, size_t n) { (void)hipMemcpyAsync(dst, src, n * d, hipMemcpyDeviceToHost, h->stream); };
-        down(xhat, xh_d, n_x);
-        if (xvar) down(xvar, xv_d, n_x);
-        if (common) down(common, cm_d, n_x);
-        down(f_out, f_d, n_f);
-        if (P_out) down(P_out, P_d, n_P);
-        down(ll_host.data(), ll_d, (size_t)B);
-        hipError_t e = hipStreamSynchronize(h->stream);
-        if (e != hipSuccess) rc = hip_fail(h, e, "hipStreamSynchronize");
-    }
+    const size_t k = (size_t)r * p, np = (size_t)r * (r + 1) / 2, TH = (size_t)T + H, n_R = (size_t)B * N, n_x = (size_t)B * TH * N;
+    std::vector<double> ll_host((size_t)B);                     // (checked before the caller's loglik, which is optional, is written)
+    HostStage st(h, 256);
+    double *x_d, *lam_d, *R_d, *A_d, *Q_d, *mu_d, *P0_d, *mean_d, *sd_d, *xh_d, *xv_d, *cm_d, *f_d, *P_d, *ll_d;
+    st.in(panel, (size_t)B * T * N, x_d); st.in(Lam, (size_t)B * N * r, lam_d); st.in(R, n_R, R_d); st.in(Avar, (size_t)B * r * k, A_d);
+    st.in(Q, (size_t)B * r * r, Q_d); st.in(mu0, (size_t)B * k, mu_d); st.in(P0, (size_t)B * k * k, P0_d);
+    st.in(mean, mean ? n_R : 0, mean_d); st.in(sd, sd ? n_R : 0, sd_d);
+    st.out(xhat, n_x, xh_d); st.out(xvar, xvar ? n_x : 0, xv_d); st.out(common, common ? n_x : 0, cm_d);
+    st.out(f_out, (size_t)B * TH * r, f_d); st.out(P_out, P_out ? (size_t)B * TH * np : 0, P_d); st.out(ll_host.data(), (size_t)B, ll_d);
+    if (int rc = st.begin()) return rc;
+    int rc = st.finish(dfm_forecast_batch_dev(h, B, T, N, r, p, H, x_d, lam_d, R_d, A_d, Q_d, mu_d, P0_d, mean_d, sd_d, xh_d, xv_d, cm_d,
+                                              f_d, P_d, ll_d, flags));
     if (rc == 0) rc = post_check(h, ll_host.data(), B);
-    if (rc == 0 && loglik) memcpy(loglik, ll_host.data(), (size_t)B * d);
-    (void)hipFree(buf);
+    if (rc == 0 && loglik) memcpy(loglik, ll_host.data(), (size_t)B * sizeof(double));
     return rc;
 }
 
@@ -2715,17 +2507,12 @@ int dfm_forecast_batch(dfm_handle* h, int B, int T, int N, int r, int p, int H, 
 // only the panel and f_draw, and runs after the pass in stream order), else in h->ss.
 static constexpr int kSsSlice = 8192;
 
-static int ensure_ss(dfm_handle* h, size_t bytes) {
-    if (bytes <= h->ss_bytes) return 0;
-    if (h->ss) {
-        HIP_TRY(h, hipDeviceSynchronize());
-        HIP_TRY(h, hipFree(h->ss));
-        h->ss = nullptr;
-        h->ss_bytes = 0;
-    }
-    HIP_TRY(h, hipMalloc(&h->ss, bytes));
-    h->ss_bytes = bytes;
-    return 0;
+// The pass over one slice of S expanded replicates (simsmooth_run's difference panels, news_run's covariance panels) with the
+// parameters simsmooth_expand_kernel left in e: the plain pass at p = 1, the companion pass beyond; smoothed means only.
+static int slice_pass(dfm_handle* h, int S, int T, int N, int r, int p, const double* panels, const SsArgs& e, double* g, double* ll,
+                      unsigned flags) {
+    if (p == 1) return dfm_ks_pass_batch_dev(h, S, T, N, r, panels, e.eLam, e.eR, e.eA, e.eQ, e.emu0, e.eP0, g, nullptr, ll, flags);
+    return dfm_ks_pass_varp_batch_dev(h, S, T, N, r, p, panels, e.eLam, e.eR, e.eA, e.eQ, e.emu0, e.eP0, g, nullptr, ll, flags);
 }
 
 static int simsmooth_check(dfm_handle* h, int B, int D, int T, int N, int r, int p, int H, const double* panel, const double* Lam,
@@ -2759,15 +2546,13 @@ static int simsmooth_run(dfm_handle* h, int B, int D, int T, int N, int r, int p
                  o_m = take(off, (size_t)Smax * k * d), o_P = take(off, (size_t)Smax * k * k * d),
                  o_g = take(off, (size_t)Smax * T * r * d), o_ll = ll_all ? (size_t)-1 : take(off, (size_t)Smax * d),
                  o_x = x_draw ? (size_t)-1 : take(off, (size_t)Smax * T * N * d);
-    if (int rc = ensure_ss(h, off)) return rc;
-    char* base = static_cast<char*>(h->ss);
-    auto ptr = [&](size_t o) { return o == (size_t)-1 ? nullptr : reinterpret_cast<double*>(base + o); };
+    HIP_TRY(h, h->ss.grow(off));
     SsArgs a{};
     a.B = B; a.D = D; a.T = T; a.N = N; a.r = r; a.p = p; a.H = H;
     a.panel = panel; a.Lam = Lam; a.R = R; a.A = Avar; a.Q = Q; a.mu0 = mu0; a.P0 = P0; a.mean = mean; a.sd = sd;
     a.seed = seed; a.first_draw = first_draw; a.f_draw = f_draw; a.x_draw = x_draw;
-    a.LP0 = ptr(o_LP0); a.LQ = ptr(o_LQ);
-    a.eLam = ptr(o_L); a.eR = ptr(o_R); a.eA = ptr(o_A); a.eQ = ptr(o_Q); a.emu0 = ptr(o_m); a.eP0 = ptr(o_P); a.g = ptr(o_g);
+    a.LP0 = at<double>(h->ss, o_LP0); a.LQ = at<double>(h->ss, o_LQ);
+    a.eLam = at<double>(h->ss, o_L); a.eR = at<double>(h->ss, o_R); a.eA = at<double>(h->ss, o_A); a.eQ = at<double>(h->ss, o_Q); a.emu0 = at<double>(h->ss, o_m); a.eP0 = at<double>(h->ss, o_P); a.g = at<double>(h->ss, o_g);
     {
         ProfScope ps(h, K_SS_PREP);
         HIP_TRY(h, launch_simsmooth_prep(a, h->stream));
@@ -2775,8 +2560,8 @@ static int simsmooth_run(dfm_handle* h, int B, int D, int T, int N, int r, int p
     for (long long j0 = 0; j0 < BD; j0 += Smax) {
         const int S = (int)(BD - j0 < Smax ? BD - j0 : Smax);
         a.j0 = j0; a.S = S;
-        a.diff = x_draw ? x_draw + (size_t)j0 * TH * N : ptr(o_x);
-        double* ll = ll_all ? ll_all + j0 : ptr(o_ll);
+        a.diff = x_draw ? x_draw + (size_t)j0 * TH * N : at<double>(h->ss, o_x);
+        double* ll = ll_all ? ll_all + j0 : at<double>(h->ss, o_ll);
         {
             ProfScope ps(h, K_SS_EXPAND);
             HIP_TRY(h, launch_simsmooth_expand(a, h->stream));
@@ -2789,14 +2574,7 @@ static int simsmooth_run(dfm_handle* h, int B, int D, int T, int N, int r, int p
             ProfScope ps(h, K_SS_DIFF);
             HIP_TRY(h, launch_simsmooth_diff(a, h->stream));
         }
-        double* g = ptr(o_g);
-        if (p == 1) {
-            if (int rc = dfm_ks_pass_batch_dev(h, S, T, N, r, a.diff, a.eLam, a.eR, a.eA, a.eQ, a.emu0, a.eP0, g, nullptr, ll, flags))
-                return rc;
-        } else {
-            if (int rc = dfm_ks_pass_varp_batch_dev(h, S, T, N, r, p, a.diff, a.eLam, a.eR, a.eA, a.eQ, a.emu0, a.eP0, g, nullptr, ll,
-                                                    flags)) return rc;
-        }
+        if (int rc = slice_pass(h, S, T, N, r, p, a.diff, a, at<double>(h->ss, o_g), ll, flags)) return rc;
         {
             ProfScope ps(h, K_SS_FINISH);
             HIP_TRY(h, launch_simsmooth_finish(a, h->stream));
@@ -2825,37 +2603,18 @@ int dfm_simsmooth_batch(dfm_handle* h, int B, int D, int T, int N, int r, int p,
     if (int rc = simsmooth_check(h, B, D, T, N, r, p, H, panel, Lam, R, Avar, Q, mu0, P0, mean, sd, f_draw)) return rc;
     if (int rc = status_epoch(h)) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
-    const size_t d = sizeof(double), k = (size_t)r * p, TH = (size_t)T + H, BD = (size_t)B * D;
-    const size_t n_panel = (size_t)B * T * N, n_lam = (size_t)B * N * r, n_R = (size_t)B * N, n_a = (size_t)B * r * k,
-                 n_q = (size_t)B * r * r, n_v = (size_t)B * k, n_p0 = (size_t)B * k * k, n_f = BD * TH * r,
-                 n_x = x_draw ? BD * TH * N : 0;
-    const size_t total = n_panel + n_lam + n_R + n_a + n_q + n_v + n_p0 + (mean ? 2 * n_R : 0) + n_f + n_x + BD + 16 * 32;
-    double* buf = nullptr;
-    HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&buf), total * d));
-    double* dp = buf;
-    auto take_d = [&](size_t n) { double* dst = dp; dp += (n + 31) & ~(size_t)31; return dst; };
-    auto up = [&](const double* src, size_t n) -> double* {
-        double* dst = take_d(n);
-        (void)hipMemcpyAsync(dst, src, n * d, hipMemcpyHostToDevice, h->stream);
-        return dst;
-    };
-    double *x_d = up(panel, n_panel), *lam_d = up(Lam, n_lam), *R_d = up(R, n_R), *A_d = up(Avar, n_a), *Q_d = up(Q, n_q),
-           *mu_d = up(mu0, n_v), *P0_d = up(P0, n_p0);
-    double *mean_d = mean ? up(mean, n_R) : nullptr, *sd_d = sd ? up(sd, n_R) : nullptr;
-    double *f_d = take_d(n_f), *xo_d = x_draw ? take_d(n_x) : nullptr, *ll_d = take_d(BD);
-    int rc = simsmooth_run(h, B, D, T, N, r, p, H, x_d, lam_d, R_d, A_d, Q_d, mu_d, P0_d, mean_d, sd_d, seed, first_draw, f_d,
-                           xo_d, ll_d, flags);
+    const size_t k = (size_t)r * p, TH = (size_t)T + H, BD = (size_t)B * D, n_R = (size_t)B * N;
     std::vector<double> ll_host(BD);
-    if (rc == 0) {
-        auto down = [&](void* dst, const void* src, size_t n) { (void)hipMemcpyAsync(dst, src, n * d, hipMemcpyDeviceToHost, h->stream); };
-        down(f_draw, f_d, n_f);
-        if (x_draw) down(x_draw, xo_d, n_x);
-        down(ll_host.data(), ll_d, BD);
-        hipError_t e = hipStreamSynchronize(h->stream);
-        if (e != hipSuccess) rc = hip_fail(h, e, "hipStreamSynchronize");
-    }
+    HostStage st(h, 256);
+    double *x_d, *lam_d, *R_d, *A_d, *Q_d, *mu_d, *P0_d, *mean_d, *sd_d, *f_d, *xo_d, *ll_d;
+    st.in(panel, (size_t)B * T * N, x_d); st.in(Lam, (size_t)B * N * r, lam_d); st.in(R, n_R, R_d); st.in(Avar, (size_t)B * r * k, A_d);
+    st.in(Q, (size_t)B * r * r, Q_d); st.in(mu0, (size_t)B * k, mu_d); st.in(P0, (size_t)B * k * k, P0_d);
+    st.in(mean, mean ? n_R : 0, mean_d); st.in(sd, sd ? n_R : 0, sd_d);
+    st.out(f_draw, BD * TH * r, f_d); st.out(x_draw, x_draw ? BD * TH * N : 0, xo_d); st.out(ll_host.data(), BD, ll_d);
+    if (int rc = st.begin()) return rc;
+    int rc = st.finish(simsmooth_run(h, B, D, T, N, r, p, H, x_d, lam_d, R_d, A_d, Q_d, mu_d, P0_d, mean_d, sd_d, seed, first_draw, f_d,
+                                     xo_d, ll_d, flags));
     if (rc == 0) rc = post_check(h, ll_host.data(), (int)BD);
-    (void)hipFree(buf);
     return rc;
 }
 
@@ -2867,19 +2626,6 @@ int dfm_simsmooth_batch(dfm_handle* h, int B, int D, int T, int N, int r, int p,
 // vectors, the covariance panels, the existing pass over them, the impacts.  With weight the covariance panels of a slice live
 // in that slice's part of weight, which news_impact_kernel overwrites cell by cell.
 static constexpr int kNwSlice = 8192;
-
-static int ensure_nw(dfm_handle* h, size_t bytes) {
-    if (bytes <= h->nw_bytes) return 0;
-    if (h->nw) {
-        HIP_TRY(h, hipDeviceSynchronize());
-        HIP_TRY(h, hipFree(h->nw));
-        h->nw = nullptr;
-        h->nw_bytes = 0;
-    }
-    HIP_TRY(h, hipMalloc(&h->nw, bytes));
-    h->nw_bytes = bytes;
-    return 0;
-}
 
 // Argument check of both entries; *H = the horizon the targets need.
 static int news_check(dfm_handle* h, int B, int T, int N, int r, int p, const double* oldp, const double* newp, const double* Lam,
@@ -2923,10 +2669,8 @@ static int news_run(dfm_handle* h, int B, int T, int N, int r, int p, int H, con
                  o_g = take(off, (size_t)Smax * T * r * d),
                  o_ll = ll_all ? (size_t)-1 : take(off, (size_t)(B > Smax ? B : Smax) * d),
                  o_c = weight ? (size_t)-1 : take(off, (size_t)Smax * T * N * d);
-    if (int rc = ensure_nw(h, off)) return rc;
-    char* base = static_cast<char*>(h->nw);
-    auto ptr = [&](size_t o) { return o == (size_t)-1 ? nullptr : reinterpret_cast<double*>(base + o); };
-    int* tgt = reinterpret_cast<int*>(base + o_t);
+    HIP_TRY(h, h->nw.grow(off));
+    int* tgt = at<int>(h->nw, o_t);
     {
         std::vector<int> tg((size_t)2 * G);                   // (a pageable source: staged before the call returns)
         for (int g = 0; g < G; ++g) { tg[2 * g] = target_t[g]; tg[2 * g + 1] = target_i[g]; }
@@ -2935,8 +2679,8 @@ static int news_run(dfm_handle* h, int B, int T, int N, int r, int p, int H, con
     NwArgs a{};
     a.B = B; a.T = T; a.N = N; a.r = r; a.p = p; a.G = G; a.TH = (int)TH;
     a.oldp = oldp; a.newp = newp; a.Lam = Lam; a.R = R; a.A = Avar; a.P0 = P0; a.Q = Q; a.mean = mean; a.sd = sd;
-    a.tgt = tgt; a.rev = ptr(o_rev); a.xrev = ptr(o_x); a.yhat = yhat; a.impact = impact; a.news = news; a.weight = weight;
-    a.status = h->status_dev; a.u = ptr(o_u); a.av = ptr(o_av); a.g = ptr(o_g);
+    a.tgt = tgt; a.rev = at<double>(h->nw, o_rev); a.xrev = at<double>(h->nw, o_x); a.yhat = yhat; a.impact = impact; a.news = news; a.weight = weight;
+    a.status = h->status_dev; a.u = at<double>(h->nw, o_u); a.av = at<double>(h->nw, o_av); a.g = at<double>(h->nw, o_g);
     {
         ProfScope ps(h, K_NW_REVISE);
         HIP_TRY(h, launch_news_revise(a, h->stream));
@@ -2945,21 +2689,21 @@ static int news_run(dfm_handle* h, int B, int T, int N, int r, int p, int H, con
     const struct { const double* panel; unsigned fl; int which; } runs[3] = {
         {oldp, flags | DFM_F_MAY_HAVE_MISSING, 0}, {newp, flags, 2}, {a.rev, flags | DFM_F_MAY_HAVE_MISSING, 1}};
     for (const auto& run : runs) {
-        double* ll = ll_all ? ll_all + (size_t)run.which * B : ptr(o_ll);
-        if (int rc = dfm_forecast_batch_dev(h, B, T, N, r, p, H, run.panel, Lam, R, Avar, Q, mu0, P0, mean, sd, ptr(o_x), nullptr,
-                                            nullptr, ptr(o_f), nullptr, ll, run.fl)) return rc;
+        double* ll = ll_all ? ll_all + (size_t)run.which * B : at<double>(h->nw, o_ll);
+        if (int rc = dfm_forecast_batch_dev(h, B, T, N, r, p, H, run.panel, Lam, R, Avar, Q, mu0, P0, mean, sd, at<double>(h->nw, o_x), nullptr,
+                                            nullptr, at<double>(h->nw, o_f), nullptr, ll, run.fl)) return rc;
         ProfScope ps(h, K_NW_GATHER);
-        HIP_TRY(h, launch_news_gather(a, ptr(o_x), run.which, h->stream));
+        HIP_TRY(h, launch_news_gather(a, at<double>(h->nw, o_x), run.which, h->stream));
     }
     SsArgs e{};
     e.B = B; e.D = G; e.T = T; e.N = N; e.r = r; e.p = p;
     e.Lam = Lam; e.R = R; e.A = Avar; e.Q = Q; e.mu0 = mu0; e.P0 = P0;
-    e.eLam = ptr(o_L); e.eR = ptr(o_R); e.eA = ptr(o_A); e.eQ = ptr(o_Q); e.emu0 = ptr(o_m); e.eP0 = ptr(o_P);
+    e.eLam = at<double>(h->nw, o_L); e.eR = at<double>(h->nw, o_R); e.eA = at<double>(h->nw, o_A); e.eQ = at<double>(h->nw, o_Q); e.emu0 = at<double>(h->nw, o_m); e.eP0 = at<double>(h->nw, o_P);
     for (long long j0 = 0; j0 < BG; j0 += Smax) {
         const int S = (int)(BG - j0 < Smax ? BG - j0 : Smax);
         a.j0 = j0; a.S = S; e.j0 = j0; e.S = S;
-        a.cp = weight ? weight + (size_t)j0 * T * N : ptr(o_c);
-        double* ll = ll_all ? ll_all + (size_t)3 * B + j0 : ptr(o_ll);
+        a.cp = weight ? weight + (size_t)j0 * T * N : at<double>(h->nw, o_c);
+        double* ll = ll_all ? ll_all + (size_t)3 * B + j0 : at<double>(h->nw, o_ll);
         {
             ProfScope ps(h, K_SS_EXPAND);
             HIP_TRY(h, launch_simsmooth_expand(e, h->stream));
@@ -2972,14 +2716,7 @@ static int news_run(dfm_handle* h, int B, int T, int N, int r, int p, int H, con
             ProfScope ps(h, K_NW_COV);
             HIP_TRY(h, launch_news_cov_panel(a, h->stream));
         }
-        double* g = ptr(o_g);
-        if (p == 1) {
-            if (int rc = dfm_ks_pass_batch_dev(h, S, T, N, r, a.cp, e.eLam, e.eR, e.eA, e.eQ, e.emu0, e.eP0, g, nullptr, ll, flags))
-                return rc;
-        } else {
-            if (int rc = dfm_ks_pass_varp_batch_dev(h, S, T, N, r, p, a.cp, e.eLam, e.eR, e.eA, e.eQ, e.emu0, e.eP0, g, nullptr, ll,
-                                                    flags)) return rc;
-        }
+        if (int rc = slice_pass(h, S, T, N, r, p, a.cp, e, at<double>(h->nw, o_g), ll, flags)) return rc;
         ProfScope ps(h, K_NW_IMPACT);
         HIP_TRY(h, launch_news_impact(a, h->stream));
     }
@@ -3006,40 +2743,18 @@ int dfm_news_batch(dfm_handle* h, int B, int T, int N, int r, int p, const doubl
                             impact, &H)) return rc;
     if (int rc = status_epoch(h)) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
-    const size_t d = sizeof(double), k = (size_t)r * p, BG = (size_t)B * G;
-    const size_t n_panel = (size_t)B * T * N, n_lam = (size_t)B * N * r, n_R = (size_t)B * N, n_a = (size_t)B * r * k,
-                 n_q = (size_t)B * r * r, n_v = (size_t)B * k, n_p0 = (size_t)B * k * k, n_y = (size_t)B * 3 * G,
-                 n_imp = BG * N, n_news = news ? n_panel : 0, n_w = weight ? BG * T * N : 0, n_ll = (size_t)3 * B + BG;
-    const size_t total = 2 * n_panel + n_lam + n_R + n_a + n_q + n_v + n_p0 + (mean ? 2 * n_R : 0) + n_y + n_imp + n_news + n_w +
-                         n_ll + 16 * 32;
-    double* buf = nullptr;
-    HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&buf), total * d));
-    double* dp = buf;
-    auto take_d = [&](size_t n) { double* dst = dp; dp += (n + 31) & ~(size_t)31; return dst; };
-    auto up = [&](const double* src, size_t n) -> double* {
-        double* dst = take_d(n);
-        (void)hipMemcpyAsync(dst, src, n * d, hipMemcpyHostToDevice, h->stream);
-        return dst;
-    };
-    double *xo_d = up(old_panel, n_panel), *xn_d = up(new_panel, n_panel), *lam_d = up(Lam, n_lam), *R_d = up(R, n_R),
-           *A_d = up(Avar, n_a), *Q_d = up(Q, n_q), *mu_d = up(mu0, n_v), *P0_d = up(P0, n_p0);
-    double *mean_d = mean ? up(mean, n_R) : nullptr, *sd_d = sd ? up(sd, n_R) : nullptr;
-    double *y_d = take_d(n_y), *imp_d = take_d(n_imp), *news_d = news ? take_d(n_news) : nullptr,
-           *w_d = weight ? take_d(n_w) : nullptr, *ll_d = take_d(n_ll);
-    int rc = news_run(h, B, T, N, r, p, H, xo_d, xn_d, lam_d, R_d, A_d, Q_d, mu_d, P0_d, mean_d, sd_d, G, target_t, target_i, y_d,
-                      imp_d, news_d, w_d, ll_d, flags);
+    const size_t k = (size_t)r * p, BG = (size_t)B * G, n_panel = (size_t)B * T * N, n_R = (size_t)B * N, n_ll = (size_t)3 * B + BG;
     std::vector<double> ll_host(n_ll);
-    if (rc == 0) {
-        auto down = [&](void* dst, const void* src, size_t n) { (void)hipMemcpyAsync(dst, src, n * d, hipMemcpyDeviceToHost, h->stream); };
-        down(yhat, y_d, n_y);
-        down(impact, imp_d, n_imp);
-        if (news) down(news, news_d, n_news);
-        if (weight) down(weight, w_d, n_w);
-        down(ll_host.data(), ll_d, n_ll);
-        hipError_t e = hipStreamSynchronize(h->stream);
-        if (e != hipSuccess) rc = hip_fail(h, e, "hipStreamSynchronize");
-    }
+    HostStage st(h, 256);
+    double *xo_d, *xn_d, *lam_d, *R_d, *A_d, *Q_d, *mu_d, *P0_d, *mean_d, *sd_d, *y_d, *imp_d, *news_d, *w_d, *ll_d;
+    st.in(old_panel, n_panel, xo_d); st.in(new_panel, n_panel, xn_d); st.in(Lam, (size_t)B * N * r, lam_d); st.in(R, n_R, R_d);
+    st.in(Avar, (size_t)B * r * k, A_d); st.in(Q, (size_t)B * r * r, Q_d); st.in(mu0, (size_t)B * k, mu_d); st.in(P0, (size_t)B * k * k, P0_d);
+    st.in(mean, mean ? n_R : 0, mean_d); st.in(sd, sd ? n_R : 0, sd_d);
+    st.out(yhat, (size_t)B * 3 * G, y_d); st.out(impact, BG * N, imp_d); st.out(news, news ? n_panel : 0, news_d);
+    st.out(weight, weight ? BG * T * N : 0, w_d); st.out(ll_host.data(), n_ll, ll_d);
+    if (int rc = st.begin()) return rc;
+    int rc = st.finish(news_run(h, B, T, N, r, p, H, xo_d, xn_d, lam_d, R_d, A_d, Q_d, mu_d, P0_d, mean_d, sd_d, G, target_t, target_i, y_d,
+                                imp_d, news_d, w_d, ll_d, flags));
     if (rc == 0) rc = post_check(h, ll_host.data(), (int)n_ll);
-    (void)hipFree(buf);
     return rc;
 }
