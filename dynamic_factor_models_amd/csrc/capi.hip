@@ -41,31 +41,15 @@ struct DevBlock {
         bytes = 0;
     }
 };
-}  // namespace
 
-struct dfm_handle {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    hipStream_t side = nullptr;            // data-independent kernels (gram, cov) run beside the collapse
-    hipStream_t post = nullptr;            // meanscan of sub-batch s runs here, beside the collapse of sub-batch s+1
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_post = nullptr;
-    std::vector<hipEvent_t> ev_sub;        // collapse of sub-batch s done
+struct RouteOpts {
     int subbatch = 0;                      // DFM_SUBBATCH: sub-batches per fast pass (0 = automatic)
     bool force_general = false;            // DFM_FORCE_GENERAL=1: never take the balanced fast path
     int collapse_variant = 0;              // DFM_COLLAPSE_VARIANT: 0 = automatic; 1..199 VALU kernel tunings; 200 = MFMA kernel
     int collapse_wpr = 0;                  // DFM_COLLAPSE_WPR: period segments (waves) per replicate of the MFMA collapse; 0 = automatic
-    int num_cu = 256;
-    int scan_abl = 0;
+    int scan_abl = 0;                      // DFM_SCAN_ABL: ablation bits of the fast path's scan (diagnostics)
     bool no_side = false;                  // DFM_NO_SIDE=1: gram/cov on the main stream (diagnostics)
     bool no_pipe = false;                  // DFM_PIPE=0 (diagnostics build): large batches with missing cells as ONE batch on one stream (pipe_eligible)
-    bool in_pipe = false;                  // inside a sub-batch of pipe_run: no nesting
-    // The handle's status word: its own 256-byte allocation, zeroed at creation and again by whoever READS a non-zero value
-    // (status_check).  It is sticky between checks -- no memset per call: that was a 5 us fill kernel in front of every pass,
-    // 2 % of the headline's step.  Device-pointer callers that never check see nothing; dfm_synchronize / dfm_check_status and
-    // every host-pointer entry report (and clear) whatever was raised since the last check.
-    int* status_dev = nullptr;
-    int discarded_status = 0;              // status bits of earlier, unchecked device-pointer calls that a host-pointer entry cleared (status_epoch)
     bool no_rec_wave = false;              // DFM_NO_RECURSION_WAVE=1: lane-group recursion_kernel also at Rp = 8 (A/B)
     int tile_nc = 0, tile_w = 0;   // DFM_TILE_NC (route): chunks per replicate on recursion_tile_kernel (0 = automatic, 1 = the sequential kernel), DFM_TILE_W: warm-up periods
     bool no_chunk = false; int chunk_w = 0; double chunk_tol = 0.0;   // DFM_NO_CHUNK=1 (route): panels with missing cells at Rp = 8 on the sequential kernels;
@@ -88,6 +72,75 @@ struct dfm_handle {
     bool gram_xx_valu = false;             // DFM_GRAM_XX_VALU=1: X'X of the PCA start on the VALU kernel (diagnostics)
     int pass_ncov = 0;                     // DFM_PASS_NCOV: covariance waves per workgroup of that launch (0 = automatic)
     bool cov_wave = false;                 // DFM_COV_WAVE=1: one-wave-per-replicate covariance recursion on the separate-launch path
+    int mstep_miss_mode = 1;               // DFM_MSTEP_MISS (route): loadings step with missing cells on the matrix pipe (mstep_miss.hip): 0 = never
+                                           // (mstep_lam_kernel), 1 = where mstep_lam_kernel keeps its per-series accumulators in global memory
+                                           // (Rp > 8 or N > 256), 2 = wherever supported
+    bool odd_pad8 = true;                  // DFM_ODD_PAD8=0 (diagnostics build): odd N at states up to 8 wide stays on collapse_kernel
+};
+
+// Every switch of the library, read from the environment ONCE: route_env names select among production kernels, diag_env names
+// exist in the diagnostics build only (dfm_kernels.h).  A handle keeps the values of its own creation (dfm_handle::opt), so one
+// process can hold handles on either kernel; dfm_workspace_bytes, which has no handle, reads them at the call.
+RouteOpts route_opts_from_env() {
+    auto num = [](const char* v, int dflt) { return v ? atoi(v) : dflt; };
+    auto on = [](const char* v) { return v && atoi(v) != 0; };             // NAME=1 turns it on
+    auto off = [](const char* v) { return v && atoi(v) == 0; };            // NAME=0 turns it off
+    auto pos = [](const char* v) { return v && atoi(v) > 0 ? atoi(v) : 0; };
+    RouteOpts o;
+    o.force_general = on(route_env("DFM_FORCE_GENERAL"));
+    o.collapse_variant = num(diag_env("DFM_COLLAPSE_VARIANT"), 0);
+    o.collapse_wpr = num(diag_env("DFM_COLLAPSE_WPR"), 0);
+    if (o.collapse_wpr < 0 || o.collapse_wpr > kSsumSlots) o.collapse_wpr = 0;
+    o.no_side = on(diag_env("DFM_NO_SIDE"));
+    o.no_pipe = off(diag_env("DFM_PIPE"));
+    o.no_rec_wave = on(diag_env("DFM_NO_RECURSION_WAVE"));
+    if (const char* v = diag_env("DFM_PAIR_BMAX")) o.pair_bmax = pos(v);
+    if (on(route_env("DFM_NO_PAIR"))) o.pair_bmax = 0;
+    o.no_pfill = on(diag_env("DFM_NO_PFILL"));
+    o.fused_gram = !off(diag_env("DFM_FUSED_GRAM"));
+    o.no_fuse_cov = on(diag_env("DFM_NO_FUSE_COV"));
+    o.no_mstep_mfma = on(diag_env("DFM_NO_MSTEP_MFMA"));
+    o.no_defer_em = on(diag_env("DFM_NO_DEFER_EM"));
+    o.em_general = on(diag_env("DFM_EM_GENERAL"));
+    o.fuse_gram = on(diag_env("DFM_FUSE_GRAM"));
+    o.subbatch = num(diag_env("DFM_SUBBATCH"), 0);
+    o.scan_abl = num(diag_env("DFM_SCAN_ABL"), 0);
+    o.mstep_miss_mode = num(route_env("DFM_MSTEP_MISS"), 1);
+    o.pass_fused = num(route_env("DFM_PASS_FUSED"), 1);
+    o.pass_nsw = num(diag_env("DFM_PASS_NSW"), 0);
+    o.pass_ncov = num(diag_env("DFM_PASS_NCOV"), 0);
+    o.gram_xx_valu = on(diag_env("DFM_GRAM_XX_VALU"));
+    o.collapse_miss_old = on(diag_env("DFM_COLLAPSE_MISS_OLD"));
+    o.narrow_tab_off = off(diag_env("DFM_NARROW_TAB"));
+    o.odd_pad8 = !off(diag_env("DFM_ODD_PAD8"));
+    o.no_chunk = on(route_env("DFM_NO_CHUNK"));
+    o.chunk_w = pos(route_env("DFM_CHUNK_W"));
+    if (const char* v = route_env("DFM_CHUNK_TOL")) o.chunk_tol = atof(v) > 0.0 ? atof(v) : 0.0;
+    o.tile_nc = pos(route_env("DFM_TILE_NC"));
+    o.tile_w = pos(route_env("DFM_TILE_W"));
+    o.wide_old = on(diag_env("DFM_WIDE_OLD"));
+    o.cov_wave = on(diag_env("DFM_COV_WAVE"));
+    return o;
+}
+}  // namespace
+
+struct dfm_handle {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    bool own_stream = false;
+    hipStream_t side = nullptr;            // data-independent kernels (gram, cov) run beside the collapse
+    hipStream_t post = nullptr;            // meanscan of sub-batch s runs here, beside the collapse of sub-batch s+1
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_post = nullptr;
+    std::vector<hipEvent_t> ev_sub;        // collapse of sub-batch s done
+    const RouteOpts opt = route_opts_from_env();   // every switch, as the environment stood when this handle was created
+    int num_cu = 256;                      // the device's compute units; DFM_NUM_CU (route): persistent grids sized for fewer
+    bool in_pipe = false;                  // inside a sub-batch of pipe_run: no nesting
+    // The handle's status word: its own 256-byte allocation, zeroed at creation and again by whoever READS a non-zero value
+    // (status_check).  It is sticky between checks -- no memset per call: that was a 5 us fill kernel in front of every pass,
+    // 2 % of the headline's step.  Device-pointer callers that never check see nothing; dfm_synchronize / dfm_check_status and
+    // every host-pointer entry report (and clear) whatever was raised since the last check.
+    int* status_dev = nullptr;
+    int discarded_status = 0;              // status bits of earlier, unchecked device-pointer calls that a host-pointer entry cleared (status_epoch)
     DevBlock ws;                           // the workspace every entry point plans (make_plan) and sizes (ensure_ws) before it uses it
     const int* ck_fail_dev = nullptr; int ck_fail_n = 0;   // chunk_fail of the last launch on recursion_chunk_kernel (dfm_chunk_fallbacks)
     // EM on the fast path at Rp <= 8: the transition M-step is not launched behind the E-step but handed to the loadings step's
@@ -175,6 +228,7 @@ struct Plan {  // byte offsets into the workspace (all 256-byte aligned)
     size_t ms_ws = (size_t)-1; int ms_wpr = 0;   // mstep_mfma partial sums (EM on the fast path)
     size_t mw_ws = (size_t)-1;                     // mstep_wide: Sxf, Sxx of the Rp = 32 loadings step (EM on the fast path)
     size_t mm_ws = (size_t)-1;                     // mstep_miss: V, [D | Sxf], Sxx, counts of the loadings step with missing cells
+    bool ms_mfma = false, ms_wide = false, ms_miss = false;   // which of the three the EM iteration launches (none: mstep_lam_kernel)
     size_t Wwide = (size_t)-1;                     // W = lam / R of the Rp = 32 collapse (collapse_wide2.hip)
     bool fast;
     // covariance-form recursion (DFM_F_SINGULAR_Q) and companion states (dfm_*_varp_*): see RecursionArgs
@@ -190,27 +244,39 @@ size_t take(size_t& off, size_t bytes) {
 
 // Sequential path with r <= 4: the state is padded to 8 so that the one-wave-per-replicate recursion (recursion_wave.hip)
 // applies; collapse, loadings and the loadings M-step stay pad_r(r) wide (Plan::Rc).  DFM_NO_RECURSION_WAVE=1 turns it off.
-bool g_widen_small_r = true;
-// DFM_NO_CHUNK=1 (route switch; process-wide like g_widen_small_r: follows the most recently created handle): no chunk scratch /
-// observation table in the plans (184 KB per replicate at T = 500 that the sequential kernels never touch)
-bool g_plan_chunk = true;
-// Loadings step with missing cells on the matrix pipe (mstep_miss.hip).  DFM_MSTEP_MISS: 0 = never (mstep_lam_kernel),
-// 1 = where mstep_lam_kernel keeps its per-series accumulators in global memory (Rp > 8 or N > 256; default), 2 = wherever supported.
-int g_mstep_miss_mode = 1;
+// (one wave per replicate pays while the batch leaves SIMDs idle under the lane-group kernel: measured crossover
+// at r = 4 between B = 1024 (0.39 vs 0.60 ms) and B = 4096 (1.52 vs 0.65 ms))
+bool widens_small_r(const RouteOpts& o, int B) { return !o.no_rec_wave && B <= 1536; }
+// Loadings step with missing cells on the matrix pipe (mstep_miss.hip) for loadings Rw wide with rl factors: what
+// DFM_MSTEP_MISS (RouteOpts::mstep_miss_mode) says about this shape
+bool mstep_miss_wanted(const RouteOpts& o, int Rw, int rl, int N) {
+    return o.mstep_miss_mode && mstep_miss_supported(Rw, rl, N) && (o.mstep_miss_mode == 2 || mstep_needs_dmiss(Rw, N));
+}
+// A companion state behind the factors (dfm_*_varp_*, the AR and mixed-frequency models): see RecursionArgs.  table: the
+// chunk-major observation table of collapse_miss_kernel is wanted where the shape allows it (enqueue_pass comp_table).
+struct Companion { int Rc = 0, rl = 0, kdim = 0, kb = 0, ka = 0, qsing = 0; bool table = false; };
+// the AR and mixed-frequency models: a k-wide state of r-wide lag blocks, VAR(nlag) inside it (recursion_comp.hip's route), observed
+// on several blocks (rl = 0: loadings as wide as the state)
+Companion lag_blocks(int k, int r, int nlag, unsigned flags) {
+    Companion c;
+    c.kdim = k; c.kb = r; c.ka = r * nlag; c.qsing = (flags & DFM_F_SINGULAR_Q) ? 1 : 0;
+    return c;
+}
 
 // rows of the w_t scratch per replicate: T, plus (fast path, Rp >= 16) the chunk-major region of meanscan_mfma_kernel
 static size_t wtab_rows(bool fast, int Rp, int T) {
     return (size_t)T + ((fast && Rp >= 16) ? (size_t)fast_scan_groups(Rp) * fast_chunk_len(Rp, T) : 0);
 }
-Plan make_plan(int B, int T, int N, int r, unsigned flags, bool em, bool fast = false) {
+// The whole plan of one call: r = width of the state (r p of a companion model, whose flags carry DFM_F_SINGULAR_Q).  Nobody
+// writes to a Plan afterwards.
+Plan make_plan(const RouteOpts& o, int B, int T, int N, int r, unsigned flags, bool em, bool fast = false,
+               const Companion& comp = Companion()) {
     Plan p;
     int Rp = pad_r(r);
     p.r = r;
     p.fast = fast;
     p.cov = (flags & DFM_F_SINGULAR_Q) != 0;
-    // (one wave per replicate pays while the batch leaves SIMDs idle under the lane-group kernel: measured crossover
-    // at r = 4 between B = 1024 (0.39 vs 0.60 ms) and B = 4096 (1.52 vs 0.65 ms))
-    if (!fast && !p.cov && Rp < 8 && g_widen_small_r && B <= 1536) {
+    if (!fast && !p.cov && Rp < 8 && widens_small_r(o, B)) {
         p.Rc = Rp; p.rl = Rp;
         Rp = 8;
     }
@@ -253,7 +319,7 @@ Plan make_plan(int B, int T, int N, int r, unsigned flags, bool em, bool fast = 
     // (fast path, Rp >= 16: the mean scan on the matrix pipe keeps the steady part of w_t in a second, chunk-major region behind the
     // T natural rows -- scan_mfma32.hip)
     p.wtab = take(off, (size_t)B * wtab_rows(fast, Rp, T) * Rp * d);
-    if (!fast && !p.cov && Rp == 8 && g_plan_chunk) {
+    if (!fast && !p.cov && Rp == 8 && !o.no_chunk) {   // (184 KB per replicate at T = 500 that the sequential kernels never touch)
         p.ck_scr = take(off, recursion_chunk_scratch_bytes(B, T));
         p.ck_obs = take(off, recursion_chunk_obs_bytes(B, T));
         if (collapse_miss_supported(8, N)) p.ck_rows = take(off, recursion_chunk_rows_bytes(B, T));   // (also r <= 4 on the 8-wide state: CollapseArgs::lam_w)
@@ -290,11 +356,21 @@ Plan make_plan(int B, int T, int N, int r, unsigned flags, bool em, bool fast = 
             p.ms_ws = take(off, mstep_mfma_workspace(B, N, Rp, w));
         }
         if (fast && mstep_wide_supported(Rp, N)) p.mw_ws = take(off, mstep_wide_workspace(B, N, Rp));
-        // (sized for loadings as wide as the state: companion models narrow them after the plan is made)
-        if (!fast && g_mstep_miss_mode && mstep_miss_supported(Rp, r < Rp ? r : Rp, N) &&
-            (g_mstep_miss_mode == 2 || mstep_needs_dmiss(Rp, N)))
-            p.mm_ws = take(off, mstep_miss_workspace(B, T, N, Rp, r < Rp ? r : Rp));
+        // (sized for loadings as wide as the state, whatever a companion model narrows them to)
+        if (!fast && mstep_miss_wanted(o, Rp, r < Rp ? r : Rp, N)) p.mm_ws = take(off, mstep_miss_workspace(B, T, N, Rp, r < Rp ? r : Rp));
     }
+    if (comp.kdim > 0) {                                      // (always with p.cov: nothing above has set these)
+        p.Rc = comp.Rc; p.rl = comp.rl; p.kdim = comp.kdim; p.kb = comp.kb; p.ka = comp.ka; p.qsing = comp.qsing;
+        if (comp.table && collapse_miss_supported(8, N) && (size_t)B * recursion_chunk_len(T) <= 0x7fffffffu) {
+            p.ck_rows = take(off, recursion_chunk_rows_bytes(B, T));    // rows + masks, the chunk-major table
+            p.ck_obs = take(off, recursion_chunk_obs_bytes(B, T));
+        }
+    }
+    // the loadings step this plan's EM iterations launch (em_iteration)
+    p.ms_mfma = p.ms_ws != (size_t)-1 && !o.no_mstep_mfma;
+    p.ms_wide = p.mw_ws != (size_t)-1 && !o.no_mstep_mfma;
+    const int Rl = p.Rc ? p.Rc : Rp;                          // width of the loadings, their factor count
+    p.ms_miss = p.mm_ws != (size_t)-1 && mstep_miss_wanted(o, Rl, p.Rc ? (p.rl ? p.rl : Rl) : (r < Rl ? r : Rl), N);
     p.total = off;
     return p;
 }
@@ -392,7 +468,7 @@ int check_general_n(dfm_handle* h, int N, int r, bool plain = false) {
 
 // EM: balanced panels keep the fast-path E-step at any N (the wide collapse has no register tiling); what bounds them
 // is the loadings M-step (mstep_lam_kernel: lane = series, N <= 1024; BASELINE config 4 is N = 1000, r = 20).
-int check_em_n(dfm_handle* h, int N, int r, unsigned flags);
+int check_em_n(dfm_handle* h, int N, int r, bool fast);
 
 // Embed caller parameters (factor dimension r) into the padded dimension Rp.
 __global__ void pad_params_kernel(int B, int N, int r, int Rp, int Rl, const double* Lam, const double* A,
@@ -496,25 +572,26 @@ struct EmOpts {          // all-null for a plain pass
 };
 
 // Balanced panel, even N, plain pass: may this call take the fast path (fastpath.hip)?
-bool fast_eligible(const dfm_handle* h, int N, int r, unsigned flags) {
-    if (h->force_general || (flags & (DFM_F_MAY_HAVE_MISSING | DFM_F_SINGULAR_Q))) return false;
+bool fast_eligible(const RouteOpts& o, int N, int r, unsigned flags) {
+    if (o.force_general || (flags & (DFM_F_MAY_HAVE_MISSING | DFM_F_SINGULAR_Q))) return false;
     return collapse_dma_supported(pad_r(r), N) || collapse_wide_supported(pad_r(r), N);
 }
+// ... and the E-steps of an EM run on it?
+bool em_fast_eligible(const dfm_handle* h, int N, int r, unsigned flags) { return fast_eligible(h->opt, N, r, flags) && !h->opt.em_general; }
 
-bool g_odd_pad8 = true;                  // DFM_ODD_PAD8=0 (diagnostics build): odd N at states up to 8 wide stays on collapse_kernel
-bool needs_odd_pad(bool fast, int N, int r, unsigned flags = 0, int B = 0) {
+bool needs_odd_pad(const RouteOpts& o, bool fast, int N, int r, unsigned flags, int B) {
     if (fast) return false;
     // states up to 8 wide, panels with missing cells: collapse_miss_kernel's rows are moved 16 bytes at a time (even N).  With the
     // appended series the pass takes its table mode (+ recursion_chunk_kernel) instead of collapse_kernel + chunk_bridge_kernel:
     // the Stock-Watson window (N = 139) is such a panel.  (r <= 4 beyond 1536 replicates stays on the 4-wide lane-group kernels.)
-    if (g_odd_pad8 && pad_r(r) <= 8 && (N & 1) && (flags & DFM_F_MAY_HAVE_MISSING) && !(flags & DFM_F_SINGULAR_Q) && collapse_miss_supported(8, N + 1) &&
-        (pad_r(r) == 8 || (g_widen_small_r && B <= 1536)))
+    if (o.odd_pad8 && pad_r(r) <= 8 && (N & 1) && (flags & DFM_F_MAY_HAVE_MISSING) && !(flags & DFM_F_SINGULAR_Q) && collapse_miss_supported(8, N + 1) &&
+        (pad_r(r) == 8 || widens_small_r(o, B)))
         return true;
     return pad_r(r) == 32 && (N & 1) && N > collapse_max_n(32) && collapse_wide2_supported(32, N + 1);
 }
 
-int check_em_n(dfm_handle* h, int N, int r, unsigned flags) {
-    if (fast_eligible(h, N, r, flags) && !h->em_general) {
+int check_em_n(dfm_handle* h, int N, int r, bool fast) {   // fast: em_fast_eligible
+    if (fast) {
         if (N > 1024 && !mstep_mfma_supported(pad_r(r), N))
             return fail(h, DFM_E_DIMS, "N > 1024: the loadings M-step (one lane per series, 4 series per lane) does not cover this cross-section%s");
         return 0;
@@ -534,9 +611,9 @@ int check_em_n(dfm_handle* h, int N, int r, unsigned flags) {
 // body(b0, bn): enqueue everything for replicates [b0, b0 + bn) on h->stream with h->ws as its workspace.
 int pipe_sub(const dfm_handle* h) { return 8 * h->num_cu; }
 bool pipe_eligible(const dfm_handle* h, int B, int N, int r, unsigned flags) {
-    if (h->no_pipe || h->in_pipe || !h->post) return false;
+    if (h->opt.no_pipe || h->in_pipe || !h->post) return false;
     if (pad_r(r) != 8 || !(flags & DFM_F_MAY_HAVE_MISSING) || (flags & DFM_F_SINGULAR_Q)) return false;
-    return B >= 2 * pipe_sub(h) && collapse_miss_supported(8, N) && !h->collapse_miss_old && !h->no_chunk;
+    return B >= 2 * pipe_sub(h) && collapse_miss_supported(8, N) && !h->opt.collapse_miss_old && !h->opt.no_chunk;
 }
 template <class Body>
 int pipe_run(dfm_handle* h, int B, size_t slot_bytes, Body body) {
@@ -598,12 +675,12 @@ int enqueue_pass_fast(dfm_handle* h, const Plan& p, int B, int T, int N, int out
     // (collapse_mfma.hip), else the VALU kernel (collapse_dma.hip); DFM_COLLAPSE_VARIANT < 200 forces the latter
     // shapes outside the register tilings (or DFM_COLLAPSE_VARIANT=198): the wide kernel
     // Rp = 16 | 32 with an even N: the streaming collapse of collapse_wide2.hip (Rp = 16 used to take the VALU kernel: 1.4-2.1 TB/s)
-    const bool prefer_wide2 = !h->wide_old && h->collapse_variant == 0 && p.Wwide != (size_t)-1 && collapse_wide2_supported(p.Rp, N);
-    const bool use_wide = prefer_wide2 || !collapse_dma_supported(p.Rp, N) || h->collapse_variant == 198;
-    const bool use_mfma = !use_wide && collapse_mfma_supported(p.Rp, N) && (h->collapse_variant == 0 || h->collapse_variant >= 200);
-    const int cvariant = use_mfma ? (h->collapse_variant >= 200 ? h->collapse_variant : 200)
-                                  : (h->collapse_variant == 199 ? 0 : h->collapse_variant);   // 199: the VALU kernel's default
-    const bool use_wide2 = use_wide && !h->wide_old && p.Wwide != (size_t)-1 && collapse_wide2_supported(p.Rp, N);
+    const bool wide2_ok = !h->opt.wide_old && p.Wwide != (size_t)-1;      // (planned where collapse_wide2_supported says so: make_plan)
+    const bool use_wide = (wide2_ok && h->opt.collapse_variant == 0) || !collapse_dma_supported(p.Rp, N) || h->opt.collapse_variant == 198;
+    const bool use_mfma = !use_wide && collapse_mfma_supported(p.Rp, N) && (h->opt.collapse_variant == 0 || h->opt.collapse_variant >= 200);
+    const int cvariant = use_mfma ? (h->opt.collapse_variant >= 200 ? h->opt.collapse_variant : 200)
+                                  : (h->opt.collapse_variant == 199 ? 0 : h->opt.collapse_variant);   // 199: the VALU kernel's default
+    const bool use_wide2 = use_wide && wide2_ok;
     if (use_wide) {   // sum_t s_t arrives as partials per tile of the collapse kernel that will run
         fa.scol = ca.scol;
         fa.ntile = !use_wide2 ? collapse_wide_tiles(T) : collapse_wide2_tiles(T);
@@ -625,17 +702,17 @@ int enqueue_pass_fast(dfm_handle* h, const Plan& p, int B, int T, int N, int out
     // (3 workgroups x 4 waves on each CU), so that the launch is one balanced round
     int wpr = 4;
     if (use_mfma) {
-        wpr = h->collapse_wpr > 0 ? h->collapse_wpr : (h->num_cu * 12) / B;
+        wpr = h->opt.collapse_wpr > 0 ? h->opt.collapse_wpr : (h->num_cu * 12) / B;
         if (wpr < 1) wpr = 1;
         if (wpr > 8) wpr = 8;
         while (wpr > 1 && T / wpr < 8) --wpr;     // keep segments a few row blocks long
     }
     ca.wpr = wpr;
     fa.nseg = use_mfma ? wpr : 4;
-    const bool fuse_gram = cov_fuses_gram(p.Rp, N) && h->fuse_gram;
+    const bool fuse_gram = cov_fuses_gram(p.Rp, N) && h->opt.fuse_gram;
     if (fuse_gram) { fa.Lam = pp.Lam; fa.Rv = Rv; }
     fa.f_smooth = f_smooth; fa.P_smooth = P_smooth; fa.loglik = loglik;
-    fa.abl = h->scan_abl;
+    fa.abl = h->opt.scan_abl;
     if (em) {   // EM: covariance sums from cov_kernel, E[f_0 | X] from meanscan (workspace slots of S10 / S00 reused)
         fa.SP11 = at<double>(h, p.S10); fa.SU = at<double>(h, p.S00); fa.P0s = at<double>(h, p.P0s);
         fa.f0s = at<double>(h, p.f0s);
@@ -654,7 +731,7 @@ int enqueue_pass_fast(dfm_handle* h, const Plan& p, int B, int T, int N, int out
         { ProfScope ps(h, K_EM_UPDATE); HIP_TRY(h, launch_em_update(p.Rp, ua, h->stream)); }
         return 0;
     };
-    if (h->no_side) {   // diagnostics: everything in order on the main stream
+    if (h->opt.no_side) {   // diagnostics: everything in order on the main stream
         if (!fuse_gram) { ProfScope ps(h, K_GRAM); HIP_TRY(h, run_gram(h->stream)); }
         { ProfScope ps(h, K_COV); HIP_TRY(h, launch_cov(p.Rp, fa, h->stream)); }
         { ProfScope ps(h, use_wide ? K_COLLAPSE_WIDE : use_mfma ? K_COLLAPSE_MFMA : K_COLLAPSE_DMA); HIP_TRY(h, run_collapse(ca, h->stream)); }
@@ -663,18 +740,18 @@ int enqueue_pass_fast(dfm_handle* h, const Plan& p, int B, int T, int N, int out
     }
     // Measured on MI355X (profiles/r01): every cross-stream event edge costs 7-25 us, more than the
     // overlap buys at B = 1024, so the default is one sub-batch; DFM_SUBBATCH keeps the knob for big batches.
-    int S = h->subbatch > 0 ? h->subbatch : 1;
+    int S = h->opt.subbatch > 0 ? h->opt.subbatch : 1;
     if (S > B) S = B;
     if (use_wide2) S = 1;                                     // (its workspace -- W, tile queues -- is laid out for the whole batch)
-    if (S == 1 && h->pass_fused && use_mfma && pass_fused_supported(p.Rp, T, N) && h->collapse_variant == 0) {
+    if (S == 1 && h->opt.pass_fused && use_mfma && pass_fused_supported(p.Rp, T, N) && h->opt.collapse_variant == 0) {
         // ONE launch: persistent workgroups, b_t / w_t and the covariance tables never leave the chip (pass_fused.hip)
         fa.Lam = pp.Lam; fa.Rv = Rv;
-        if (h->scan_abl & 256) {                                  // phase stamps of every replicate -> scol; readable through the
+        if (h->opt.scan_abl & 256) {                                  // phase stamps of every replicate -> scol; readable through the
             ca.scol = at<double>(h, p.scol);                      // workspace dump below (diagnostics)
             if (const char* f = diag_env("DFM_PF_PROF_FILE")) h->prof_file = f;
         }
-        { ProfScope ps(h, K_PASS_FUSED); HIP_TRY(h, launch_pass_fused(ca, fa, h->pass_nsw, h->pass_ncov, h->num_cu, h->stream)); }
-        if ((h->scan_abl & 256) && !h->prof_file.empty()) {       // diagnostics: dump the stamps of this pass (synchronises)
+        { ProfScope ps(h, K_PASS_FUSED); HIP_TRY(h, launch_pass_fused(ca, fa, h->opt.pass_nsw, h->opt.pass_ncov, h->num_cu, h->stream)); }
+        if ((h->opt.scan_abl & 256) && !h->prof_file.empty()) {       // diagnostics: dump the stamps of this pass (synchronises)
             std::vector<double> st((size_t)B * T);
             HIP_TRY(h, hipStreamSynchronize(h->stream));
             HIP_TRY(h, hipMemcpy(st.data(), ca.scol, st.size() * sizeof(double), hipMemcpyDeviceToHost));
@@ -689,10 +766,10 @@ int enqueue_pass_fast(dfm_handle* h, const Plan& p, int B, int T, int N, int out
         }
         return em_update();
     }
-    if (S == 1 && use_mfma && !fuse_gram && !h->no_fuse_cov && collapse_mfma_fuses_cov(p.Rp, N)) {
+    if (S == 1 && use_mfma && !fuse_gram && !h->opt.no_fuse_cov && collapse_mfma_fuses_cov(p.Rp, N)) {
         // ONE stream, two launches: [Gram + covariance workgroups + P_smooth fill | streaming collapse] -> scan.
         // The covariance waves sit at the front of the collapse grid (resident first, no cross-stream events).
-        if (h->fused_gram) { fa.Lam = pp.Lam; fa.Rv = Rv; }   // the covariance workgroups compute their Gram matrices themselves
+        if (h->opt.fused_gram) { fa.Lam = pp.Lam; fa.Rv = Rv; }   // the covariance workgroups compute their Gram matrices themselves
         else { ProfScope ps(h, K_GRAM); HIP_TRY(h, run_gram(h->stream)); }
         ca.fuse_cov = &fa;
         { ProfScope ps(h, K_COLLAPSE_MFMA); HIP_TRY(h, launch_collapse_dma(p.Rp, ca, h->stream, cvariant)); }
@@ -735,7 +812,7 @@ int enqueue_pass_fast(dfm_handle* h, const Plan& p, int B, int T, int N, int out
             { ProfScope ps(h, K_COLLAPSE_WIDE, h->side); HIP_TRY(h, launch_collapse_wide2(sub_args(s_), sub_ws(s_), p.Rp, p.r, h->num_cu, h->side)); }
             HIP_TRY(h, hipEventRecord(h->ev_sub[s_], h->side));
         }
-        const bool fill = !h->no_pfill && P_smooth;
+        const bool fill = !h->opt.no_pfill && P_smooth;
         if (fill) {                       // 0.86 GB of stores at config 4: beside the scan of the last sub-batch, not beside the collapse
             HIP_TRY(h, hipStreamWaitEvent(h->post, h->ev_sub[Sw], 0));
             HIP_TRY(h, hipStreamWaitEvent(h->post, h->ev_sub[Sw - 1], 0));
@@ -759,10 +836,10 @@ int enqueue_pass_fast(dfm_handle* h, const Plan& p, int B, int T, int N, int out
         if (!fuse_gram || use_wide2) { ProfScope ps(h, K_GRAM); HIP_TRY(h, run_gram(h->stream)); }   // 12 us, alone
         HIP_TRY(h, hipEventRecord(h->ev_fork, h->stream));
         HIP_TRY(h, hipStreamWaitEvent(h->side, h->ev_fork, 0));
-        { ProfScope ps(h, K_COV); HIP_TRY(h, (h->cov_wave && p.Rp == 8 && !fuse_gram) ? launch_cov_wave(fa, h->stream) : launch_cov(p.Rp, fa, h->stream)); }
+        { ProfScope ps(h, K_COV); HIP_TRY(h, (h->opt.cov_wave && p.Rp == 8 && !fuse_gram) ? launch_cov_wave(fa, h->stream) : launch_cov(p.Rp, fa, h->stream)); }
         { ProfScope ps(h, use_wide ? K_COLLAPSE_WIDE : use_mfma ? K_COLLAPSE_MFMA : K_COLLAPSE_DMA, h->side); HIP_TRY(h, run_collapse(ca, h->side)); }
         HIP_TRY(h, hipEventRecord(h->ev_join, h->side));
-        const bool fill = !h->no_pfill && P_smooth;
+        const bool fill = !h->opt.no_pfill && P_smooth;
         // Rp = 32 (config 4): the fill is 0.86 GB of stores -- beside the collapse they cost it 0.4 ms of its 1.13; beside the
         // latency-bound scan they are free.  So: cov -> [event] ; collapse (side) -> [event] ; fill on the third stream
         // after both, scan on the caller's stream after the collapse, join at the end.
@@ -839,15 +916,15 @@ int enqueue_pass(dfm_handle* h, const Plan& p, int B, int T, int N, int out_r, c
     RecursionArgs ra;
     memset(&ra, 0, sizeof(ra));
     ra.B = B; ra.T = T; ra.N = N; ra.r = out_r;
-    ra.rstate = p.r; ra.cov = p.cov ? 1 : 0; ra.Rc = p.Rc; ra.rl = p.rl; ra.kdim = p.kdim; ra.kb = p.kb; ra.ka = p.ka; ra.qsing = p.qsing; ra.wave = h->no_rec_wave ? 0 : 1;
-    ra.pair_bmax = h->pair_bmax >= 0 ? h->pair_bmax : 4 * h->num_cu;
+    ra.rstate = p.r; ra.cov = p.cov ? 1 : 0; ra.Rc = p.Rc; ra.rl = p.rl; ra.kdim = p.kdim; ra.kb = p.kb; ra.ka = p.ka; ra.qsing = p.qsing; ra.wave = h->opt.no_rec_wave ? 0 : 1;
+    ra.pair_bmax = h->opt.pair_bmax >= 0 ? h->opt.pair_bmax : 4 * h->num_cu;
     ra.A = pp.A; ra.Q = pp.Q; ra.mu0 = pp.mu0; ra.P0 = pp.P0;
     ra.bcol = ca.bcol; ra.scol = ca.scol; ra.nobs = ca.nobs; ra.ldrow = ca.ldrow; ra.Ct = ca.Ct;
     ra.Cfull = ca.Cfull; ra.ldfull = ca.ldfull;
     ra.ZJtab = at<double>(h, p.ZJ); ra.wtab = at<double>(h, p.wtab); ra.eidx = nullptr;
-    ra.chunk_scr = h->no_chunk ? nullptr : at<double>(h, p.ck_scr); ra.chunk_W = h->chunk_w; ra.chunk_tol = h->chunk_tol; ra.chunk_obs = at<double>(h, p.ck_obs); ra.chunk_cst = at<double>(h, p.ck_cst); ra.chunk_term = at<double>(h, p.ck_term); ra.chunk_fail = at<int>(h, p.ck_fail);
+    ra.chunk_scr = at<double>(h, p.ck_scr); ra.chunk_W = h->opt.chunk_w; ra.chunk_tol = h->opt.chunk_tol; ra.chunk_obs = at<double>(h, p.ck_obs); ra.chunk_cst = at<double>(h, p.ck_cst); ra.chunk_term = at<double>(h, p.ck_term); ra.chunk_fail = at<int>(h, p.ck_fail);
     ra.chunk_skip = at<int>(h, p.ck_skip);
-    ra.tile_scr = at<double>(h, p.tk_scr); ra.tile_scr_bytes = p.tk_bytes; ra.tile_nc = h->tile_nc; ra.tile_w = h->tile_w; ra.num_cu = h->num_cu;
+    ra.tile_scr = at<double>(h, p.tk_scr); ra.tile_scr_bytes = p.tk_bytes; ra.tile_nc = h->opt.tile_nc; ra.tile_w = h->opt.tile_w; ra.num_cu = h->num_cu;
     ra.f_smooth = f_smooth; ra.P_smooth = P_smooth; ra.loglik = loglik;
     ra.ncov = at<int>(h, p.ncov);
     if (em) {
@@ -857,10 +934,12 @@ int enqueue_pass(dfm_handle* h, const Plan& p, int B, int T, int N, int out_r, c
         ra.active = em->active; ra.iters = em->iters; ra.ll_path = em->ll_path;
         ra.k = em->k; ra.max_iter = em->max_iter; ra.tol = em->tol;
     }
+    // which recursion launch_recursion will pick, as far as this function has to know (the kernel files' own predicates, asked once)
+    const bool chunked = ra.wave && recursion_chunk_supported(p.Rp, ra), tiled = ra.wave && recursion_tile_supported(p.Rp, ra);
     // C_t rows: the packed leading block when recursion_tile_kernel reads them (it executes ceil(r / 4) block pivots of the 32-wide
     // state: the rest is padding whose entries equal Cfull's), the full Rp (Rp + 1) / 2 layout for the other recursion kernels
     ca.ct_r = 0;
-    if (ra.wave && p.Wwide != (size_t)-1 && N > collapse_max_n(p.Rc ? p.Rc : p.Rp) && recursion_tile_supported(p.Rp, ra) &&
+    if (tiled && p.Wwide != (size_t)-1 && N > collapse_max_n(p.Rc ? p.Rc : p.Rp) &&
         ct_miss_wide_compact_ok(N, 4 * ((p.r + 3) / 4))) ca.ct_r = 4 * ((p.r + 3) / 4);
     ra.ct_r = ca.ct_r;
     {
@@ -870,8 +949,8 @@ int enqueue_pass(dfm_handle* h, const Plan& p, int B, int T, int N, int out_r, c
         // (r <= 4 widened to the 8-wide state, Plan::Rc = 2 / 4: the kernel pads the loadings with zero columns in its LDS tables --
         // CollapseArgs::lam_w -- and the table is the 8-wide one the chunks read anyway; collapse_kernel<4> + chunk_bridge_kernel took
         // 0.25 ms per 1024 replicates of the Stock-Watson window where this takes 0.1)
-        const bool narrow_tab = p.Rc > 0 && p.Rc < 8 && p.kdim == 0 && p.rl == p.Rc && !h->narrow_tab_off;
-        const bool table = ra.wave && !h->collapse_miss_old && (p.Rc == 0 || narrow_tab) && recursion_chunk_supported(p.Rp, ra);
+        const bool narrow_tab = p.Rc > 0 && p.Rc < 8 && p.kdim == 0 && p.rl == p.Rc && !h->opt.narrow_tab_off;
+        const bool table = chunked && !h->opt.collapse_miss_old && (p.Rc == 0 || narrow_tab);
         // companion states (VAR(p) factor dynamics) with loadings up to 4 wide: the same table, then EVERY replicate's rows written
         // back in the layout the sequential kernels read (chunk_unbridge_kernel<Rc>: b_t, s_t, C_t of every period, nobs = 0) --
         // collapse_kernel<4> took 0.235 ms per 1024 replicates of the Stock-Watson window where these two take 0.12
@@ -894,7 +973,7 @@ int enqueue_pass(dfm_handle* h, const Plan& p, int B, int T, int N, int out_r, c
             ra.chunk_obs_ready = 1;
             ProfScope ps(h, K_COLLAPSE); HIP_TRY(h, launch_collapse_miss(ca, h->num_cu, h->stream));
         } else
-        if (!h->collapse_miss_old && collapse_miss_supported(Rcol, N)) { ProfScope ps(h, K_COLLAPSE); HIP_TRY(h, launch_collapse_miss(ca, h->num_cu, h->stream)); }
+        if (!h->opt.collapse_miss_old && collapse_miss_supported(Rcol, N)) { ProfScope ps(h, K_COLLAPSE); HIP_TRY(h, launch_collapse_miss(ca, h->num_cu, h->stream)); }
         else if (p.Wwide != (size_t)-1 && N > collapse_max_n(Rcol)) {   // Rp = 32 beyond the register tiling (config 4 with missing cells)
             double* W = at<double>(h, p.Wwide);
             double* V = at<double>(h, p.Vwide);
@@ -904,8 +983,7 @@ int enqueue_pass(dfm_handle* h, const Plan& p, int B, int T, int N, int out_r, c
         } else { ProfScope ps(h, K_COLLAPSE); HIP_TRY(h, launch_collapse(Rcol, ca, h->stream)); }
     }
     h->ck_fail_dev = nullptr; h->ck_fail_n = 0;
-    if (ra.wave && recursion_chunk_supported(p.Rp, ra)) { h->ck_fail_dev = ra.chunk_fail; h->ck_fail_n = B; }
-    else if (ra.wave && recursion_tile_supported(p.Rp, ra) && recursion_tile_writes_fail(ra)) { h->ck_fail_dev = ra.chunk_fail; h->ck_fail_n = B; }
+    if (chunked || (tiled && recursion_tile_writes_fail(ra))) { h->ck_fail_dev = ra.chunk_fail; h->ck_fail_n = B; }
     { ProfScope ps(h, K_RECURSION); HIP_TRY(h, launch_recursion(p.Rp, ra, h->stream)); }
     return 0;
 }
@@ -935,8 +1013,7 @@ int em_iteration(dfm_handle* h, const Plan& p, int B, int T, int N, const double
     const int Rp = p.Rc ? p.Rc : p.Rp;          // width of the loadings (narrower than the state for a companion model)
     PaddedParams pp{LamP, AP, QP, mu0P, P0P};
     eo.A_out = AP; eo.Q_out = QP; eo.mu0_out = mu0P; eo.P0_out = P0P;
-    const bool ms_mfma = p.fast && p.ms_ws != (size_t)-1 && !h->no_mstep_mfma;
-    h->defer_em = ms_mfma && p.Rp <= 8 && !h->no_defer_em;  // the transition M-step rides in the loadings step's launch
+    h->defer_em = p.ms_mfma && p.Rp <= 8 && !h->opt.no_defer_em;  // the transition M-step rides in the loadings step's launch
     h->have_deferred_em = false;
     const int rc_pass = enqueue_pass(h, p, B, T, N, Rp, panel, pp, Rv, fsm, Psm, loglik, &eo);
     h->defer_em = false;
@@ -947,29 +1024,53 @@ int em_iteration(dfm_handle* h, const Plan& p, int B, int T, int N, const double
     ma.S11 = at<double>(h, p.S11); ma.S11inv = at<double>(h, p.Sxf);
     ma.Dmiss = mstep_needs_dmiss(Rp, N) ? at<double>(h, p.Dmiss) : nullptr;
     ma.active = eo.active; ma.Lam_out = LamP; ma.R_out = Rv; ma.lam_stride = Rp; ma.min_cells = 1;
-    if (p.fast && p.ms_ws != (size_t)-1 && !h->no_mstep_mfma) {   // balanced panel: second panel read on the matrix pipe
+    if (p.ms_mfma) {   // balanced panel: second panel read on the matrix pipe
         ProfScope ps(h, K_MSTEP_MFMA);
         HIP_TRY(h, launch_mstep_mfma(Rp, ma, p.ms_wpr, at<double>(h, p.ms_ws), h->stream, h->have_deferred_em ? &h->deferred_em : nullptr));
         h->have_deferred_em = false;
         return 0;
     }
-    if (p.fast && p.mw_ws != (size_t)-1 && !h->no_mstep_mfma) {   // ... Rp = 32 (config 4): the same on the streaming machinery of its collapse
+    if (p.ms_wide) {   // ... Rp = 32 (config 4): the same on the streaming machinery of its collapse
         ProfScope ps(h, K_MSTEP_MFMA);
         HIP_TRY(h, launch_mstep_wide(ma, at<double>(h, p.mw_ws), Rp, p.r, h->num_cu, h->stream));
         return 0;
     }
-    {
-        // panels with missing cells: both contractions of the loadings step as one product per replicate on the matrix pipe
+    if (p.ms_miss) {   // panels with missing cells: both contractions of the loadings step as one product per replicate on the matrix pipe
         const int rl = p.Rc ? (p.rl ? p.rl : Rp) : (p.r < Rp ? p.r : Rp);     // the loadings' factor count
-        if (p.mm_ws != (size_t)-1 && mstep_miss_supported(Rp, rl, N) && (g_mstep_miss_mode == 2 || mstep_needs_dmiss(Rp, N))) {
-            ProfScope ps(h, K_MSTEP_STATS);
-            HIP_TRY(h, launch_mstep_miss(ma, at<double>(h, p.mm_ws), Rp, rl, h->num_cu, h->stream));
-            return 0;
-        }
+        ProfScope ps(h, K_MSTEP_STATS);
+        HIP_TRY(h, launch_mstep_miss(ma, at<double>(h, p.mm_ws), Rp, rl, h->num_cu, h->stream));
+        return 0;
     }
     if (ma.Dmiss)
         HIP_TRY(h, hipMemsetAsync(ma.Dmiss, 0, (size_t)B * N * (Rp * (Rp + 1) / 2) * sizeof(double), h->stream));
     { ProfScope ps(h, K_MSTEP_STATS); HIP_TRY(h, launch_mstep_lam(Rp, ma, h->stream)); }
+    return 0;
+}
+
+// The loop of every EM driver: iterations k_first .. k_end - 1 of a run of max_iter, one(eo) enqueues iteration eo.k.  With
+// bookkeeping (loglik_path; iters and the device flags `active` go with it) a run that starts at 0 gets its path NaN-filled and its
+// counts zeroed, and with poll && tol > 0 the loop stops launching once no replicate of this batch is active.
+template <class One>
+int em_loop(dfm_handle* h, int B, int k_first, int k_end, int max_iter, double tol, double* loglik_path, int* iters, int* active,
+            bool poll, One one) {
+    if (loglik_path && k_first == 0) {
+        HIP_TRY(h, hipMemsetAsync(loglik_path, 0xFF, (size_t)B * max_iter * sizeof(double), h->stream));  // NaN
+        HIP_TRY(h, hipMemsetAsync(iters, 0, (size_t)B * sizeof(int), h->stream));
+    }
+    const bool stop_early = poll && loglik_path && tol > 0.0;
+    std::vector<int> act_host(stop_early ? (size_t)B : 0);
+    for (int k = k_first; k < k_end; ++k) {
+        EmOpts eo;
+        eo.active = active; eo.iters = iters; eo.ll_path = loglik_path; eo.k = k; eo.max_iter = max_iter; eo.tol = tol;
+        if (int rc = one(eo)) return rc;
+        if (stop_early && k + 1 < k_end) {
+            HIP_TRY(h, hipMemcpyAsync(act_host.data(), active, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+            HIP_TRY(h, hipStreamSynchronize(h->stream));
+            bool any = false;
+            for (int b = 0; b < B; ++b) any = any || act_host[b] != 0;
+            if (!any) break;
+        }
+    }
     return 0;
 }
 
@@ -981,11 +1082,12 @@ int em_run(dfm_handle* h, int B, int T, int N, int r, const double* panel, doubl
            double* loglik_single, double* f_smooth, double* P_smooth, unsigned flags, int k_first = 0, int k_count = -1,
            int* active_ext = nullptr) {
     if (int rc = check_dims(h, B, T, N, r)) return rc;
-    if (int rc = check_em_n(h, N, r, flags)) return rc;
+    const bool fast = em_fast_eligible(h, N, r, flags);
+    if (int rc = check_em_n(h, N, r, fast)) return rc;
     if (!panel || !Lam || !R || !A || !Q || !mu0 || !P0) return fail(h, DFM_E_NULL, "required pointer is NULL%s");
     if (max_iter < 1) return fail(h, DFM_E_DIMS, "max_iter must be >= 1%s");
     HIP_TRY(h, hipSetDevice(h->device));
-    if (needs_odd_pad(fast_eligible(h, N, r, flags) && !h->em_general, N, r, flags, B)) {   // odd N beyond the tilings: one all-missing series appended
+    if (needs_odd_pad(h->opt, fast, N, r, flags, B)) {   // odd N beyond the tilings: one all-missing series appended
         OddPad o;
         if (int rc = odd_pad(h, B, T, N, r, panel, Lam, R, &o, k_first > 0)) return rc;
         // (the appended series is missing in EVERY period: the padded problem has missing cells whatever the caller said about N)
@@ -998,7 +1100,7 @@ int em_run(dfm_handle* h, int B, int T, int N, int r, const double* panel, doubl
         return 0;
     }
     if (pipe_eligible(h, B, N, r, flags)) {     // sub-batches as EM runs of their own on two streams (pipe_run)
-        const Plan ps = make_plan(pipe_sub(h), T, N, r, flags, true, false);
+        const Plan ps = make_plan(h->opt, pipe_sub(h), T, N, r, flags, true, false);
         const size_t rr = (size_t)r * r, np = (size_t)r * (r + 1) / 2;
         return pipe_run(h, B, ps.total, [&](int b0, int bn) -> int {
             return em_run(h, bn, T, N, r, panel + (size_t)b0 * T * N, Lam + (size_t)b0 * N * r, R + (size_t)b0 * N, A + b0 * rr, Q + b0 * rr,
@@ -1010,7 +1112,7 @@ int em_run(dfm_handle* h, int B, int T, int N, int r, const double* panel, doubl
     }
     // balanced panels: E-step on the fast path (collapse on the matrix pipe, time-parallel scan), transition
     // M-step by em_update_kernel; panels with missing cells: recursion_kernel does both
-    const Plan p = make_plan(B, T, N, r, flags, true, fast_eligible(h, N, r, flags) && !h->em_general);
+    const Plan p = make_plan(h->opt, B, T, N, r, flags, true, fast);
     if (int rc = ensure_ws(h, p.total)) return rc;
     const int Rp = p.Rp, Rl = p.Rc ? p.Rc : p.Rp;            // state width, loadings width
     const size_t np = (size_t)r * (r + 1) / 2, npp = (size_t)Rl * (Rl + 1) / 2;
@@ -1028,29 +1130,15 @@ int em_run(dfm_handle* h, int B, int T, int N, int r, const double* panel, doubl
     // balanced panels with the loadings step on the matrix pipe: nothing in the EM reads the per-period smoothed covariances
     // (the M-step works from their sums, cov_kernel's SP11 / SU) -- unless the caller asked for them, the E-steps do not
     // write them (0.15 GB of stores per iteration at config 2, 0.86 GB at config 4)
-    if (!P_smooth && p.fast && !h->no_mstep_mfma && (p.ms_ws != (size_t)-1 || p.mw_ws != (size_t)-1)) Psm = nullptr;
+    if (!P_smooth && (p.ms_mfma || p.ms_wide)) Psm = nullptr;
     double* llbuf = loglik_single ? loglik_single : at<double>(h, p.llbuf);
-    const bool book = loglik_path != nullptr;
+    const bool book = loglik_path != nullptr;                // (dfm_em_step_batch_dev: none)
     int* active = book ? (active_ext ? active_ext : at<int>(h, p.active)) : nullptr;
-    if (book && k_first == 0) {
-        HIP_TRY(h, hipMemsetAsync(loglik_path, 0xFF, (size_t)B * max_iter * sizeof(double), h->stream));  // NaN
-        HIP_TRY(h, hipMemsetAsync(iters, 0, (size_t)B * sizeof(int), h->stream));
-    }
     const int k_end = k_count < 0 ? max_iter : (k_first + k_count < max_iter ? k_first + k_count : max_iter);
-    std::vector<int> act_host;
-    for (int k = k_first; k < k_end; ++k) {
-        EmOpts eo;
-        eo.active = active; eo.iters = iters; eo.ll_path = loglik_path; eo.k = k; eo.max_iter = max_iter; eo.tol = tol;
-        if (int rc = em_iteration(h, p, B, T, N, panel, LamP, R, AP, QP, mu0P, P0P, fsm, Psm, llbuf, eo)) return rc;
-        if (book && !active_ext && tol > 0.0 && k + 1 < k_end) {   // stop launching once every replicate has converged
-            act_host.resize(B);
-            HIP_TRY(h, hipMemcpyAsync(act_host.data(), active, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-            HIP_TRY(h, hipStreamSynchronize(h->stream));
-            bool any = false;
-            for (int b = 0; b < B; ++b) any = any || act_host[b] != 0;
-            if (!any) break;
-        }
-    }
+    // (active_ext: the caller owns the flags and decides when to stop)
+    if (int rc = em_loop(h, B, k_first, k_end, max_iter, tol, loglik_path, iters, active, !active_ext, [&](const EmOpts& eo) {
+            return em_iteration(h, p, B, T, N, panel, LamP, R, AP, QP, mu0P, P0P, fsm, Psm, llbuf, eo);
+        })) return rc;
     if (padded) {
         if (int rc = copy_block(h, (size_t)B * N, 1, Rl, 1, r, LamP, Lam)) return rc;
         if (int rc = copy_block(h, B, Rp, Rp, r, r, AP, A)) return rc;
@@ -1114,7 +1202,7 @@ int varp_run(dfm_handle* h, int B, int T, int N, int r, int nlag, const double* 
     HIP_TRY(h, hipSetDevice(h->device));
     // panels with missing cells, loadings up to 4 wide: the collapse on collapse_miss_kernel's table mode (comp_table below); odd N
     // gets one all-missing series appended for it, as in em_run (the Stock-Watson window has 139 series)
-    const bool comp_tab_ok = g_odd_pad8 && !h->narrow_tab_off && !h->collapse_miss_old && pad_r(r) < 8 && (flags & DFM_F_MAY_HAVE_MISSING);
+    const bool comp_tab_ok = h->opt.odd_pad8 && !h->opt.narrow_tab_off && !h->opt.collapse_miss_old && pad_r(r) < 8 && (flags & DFM_F_MAY_HAVE_MISSING);
     if (comp_tab_ok && (N & 1) && collapse_miss_supported(8, N + 1)) {
         OddPad o;
         if (int rc = odd_pad(h, B, T, N, r, panel, Lam, R, &o)) return rc;
@@ -1128,14 +1216,9 @@ int varp_run(dfm_handle* h, int B, int T, int N, int r, int nlag, const double* 
         }
         return 0;
     }
-    Plan p = make_plan(B, T, N, k, flags | DFM_F_SINGULAR_Q, em, false);
-    p.Rc = pad_r(r); p.rl = r; p.kdim = k; p.qsing = (flags & DFM_F_SINGULAR_Q) ? 1 : 0;
-    if (comp_tab_ok && collapse_miss_supported(8, N) && (size_t)B * recursion_chunk_len(T) <= 0x7fffffffu) {
-        size_t off = p.total;                                 // rows + masks, the chunk-major table (comp_table)
-        p.ck_rows = take(off, recursion_chunk_rows_bytes(B, T));
-        p.ck_obs = take(off, recursion_chunk_obs_bytes(B, T));
-        p.total = off;
-    }
+    Companion comp;                                           // loadings on the first block only, pad_r(r) wide
+    comp.Rc = pad_r(r); comp.rl = r; comp.kdim = k; comp.qsing = (flags & DFM_F_SINGULAR_Q) ? 1 : 0; comp.table = comp_tab_ok;
+    const Plan p = make_plan(h->opt, B, T, N, k, flags | DFM_F_SINGULAR_Q, em, false, comp);
     if (int rc = ensure_ws(h, p.total)) return rc;
     const int Rk = p.Rp, Rc = p.Rc;
     double *LamP = at<double>(h, p.LamP), *AP = at<double>(h, p.AP), *QP = at<double>(h, p.QP),
@@ -1153,26 +1236,10 @@ int varp_run(dfm_handle* h, int B, int T, int N, int r, int nlag, const double* 
     double* fsm = at<double>(h, p.fsm);
     double* Psm = at<double>(h, p.Psm);
     double* llbuf = loglik_single ? loglik_single : at<double>(h, p.llbuf);
-    const bool book = loglik_path != nullptr;
-    int* active = book ? at<int>(h, p.active) : nullptr;
-    if (book) {
-        HIP_TRY(h, hipMemsetAsync(loglik_path, 0xFF, (size_t)B * max_iter * sizeof(double), h->stream));  // NaN
-        HIP_TRY(h, hipMemsetAsync(iters, 0, (size_t)B * sizeof(int), h->stream));
-    }
-    std::vector<int> act_host;
-    for (int it = 0; it < max_iter; ++it) {
-        EmOpts eo;
-        eo.active = active; eo.iters = iters; eo.ll_path = loglik_path; eo.k = it; eo.max_iter = max_iter; eo.tol = tol;
-        if (int rc = em_iteration(h, p, B, T, N, panel, LamP, R, AP, QP, mu0P, P0P, fsm, Psm, llbuf, eo)) return rc;
-        if (book && tol > 0.0 && it + 1 < max_iter) {
-            act_host.resize(B);
-            HIP_TRY(h, hipMemcpyAsync(act_host.data(), active, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-            HIP_TRY(h, hipStreamSynchronize(h->stream));
-            bool any = false;
-            for (int b = 0; b < B; ++b) any = any || act_host[b] != 0;
-            if (!any) break;
-        }
-    }
+    int* active = loglik_path ? at<int>(h, p.active) : nullptr;
+    if (int rc = em_loop(h, B, 0, max_iter, max_iter, tol, loglik_path, iters, active, true, [&](const EmOpts& eo) {
+            return em_iteration(h, p, B, T, N, panel, LamP, R, AP, QP, mu0P, P0P, fsm, Psm, llbuf, eo);
+        })) return rc;
     if (int rc = copy_block(h, (size_t)B * N, 1, Rc, 1, r, LamP, Lam)) return rc;
     if (int rc = copy_block(h, B, Rk, Rk, r, k, AP, Avar)) return rc;
     if (int rc = copy_block(h, B, Rk, Rk, r, r, QP, Q)) return rc;
@@ -1222,9 +1289,7 @@ int ar_pass_run(dfm_handle* h, int B, int T, int N, int r, int nlag, int q, cons
         return fail(h, DFM_E_NULL, "required pointer is NULL%s");
     HIP_TRY(h, hipSetDevice(h->device));
     const int Tq = T - q;
-    Plan p = make_plan(B, Tq, N, k, flags | DFM_F_SINGULAR_Q, false, false);
-    p.kdim = k; p.kb = r; p.ka = r * nlag;                   // (the companion structure: recursion_comp.hip's route; collapse width)
-    p.qsing = (flags & DFM_F_SINGULAR_Q) ? 1 : 0;
+    const Plan p = make_plan(h->opt, B, Tq, N, k, flags | DFM_F_SINGULAR_Q, false, false, lag_blocks(k, r, nlag, flags));
     const size_t xoff = (p.total + 255) & ~(size_t)255;
     if (int rc = ensure_ws(h, xoff + (size_t)B * Tq * N * sizeof(double))) return rc;
     const int Rk = p.Rp;
@@ -1271,9 +1336,7 @@ int ar_em_run(dfm_handle* h, int B, int T, int N, int r, int nlag, int q, const 
     if (max_iter < 1) return fail(h, DFM_E_DIMS, "max_iter must be >= 1%s");
     HIP_TRY(h, hipSetDevice(h->device));
     const int Tq = T - q;
-    Plan p = make_plan(B, Tq, N, k, flags | DFM_F_SINGULAR_Q, true, false);
-    p.qsing = (flags & DFM_F_SINGULAR_Q) ? 1 : 0;
-    p.kdim = k; p.kb = r; p.ka = r * nlag;                   // companion constraints; the observation loads on q + 1 blocks (rl = 0)
+    const Plan p = make_plan(h->opt, B, Tq, N, k, flags | DFM_F_SINGULAR_Q, true, false, lag_blocks(k, r, nlag, flags));   // (the observation loads on q + 1 blocks)
     const size_t xoff = (p.total + 255) & ~(size_t)255;
     const int Rk = p.Rp;
     const size_t moff = (xoff + (size_t)B * Tq * N * sizeof(double) + 255) & ~(size_t)255;   // the series CM-steps' moments (mstep_ar.hip)
@@ -1290,12 +1353,9 @@ int ar_em_run(dfm_handle* h, int B, int T, int N, int r, int nlag, int q, const 
     double* Psm = at<double>(h, p.Psm);
     double* llbuf = at<double>(h, p.llbuf);
     int* active = at<int>(h, p.active);
-    HIP_TRY(h, hipMemsetAsync(loglik_path, 0xFF, (size_t)B * max_iter * sizeof(double), h->stream));  // NaN
-    HIP_TRY(h, hipMemsetAsync(iters, 0, (size_t)B * sizeof(int), h->stream));
     const size_t np = (size_t)r * (r + 1) / 2, npk = (size_t)Rk * (Rk + 1) / 2;
     PaddedParams pp{LamP, AP, QP, mu0P, P0P};
-    std::vector<int> act_host;
-    for (int it = 0; it < max_iter; ++it) {
+    if (int rc = em_loop(h, B, 0, max_iter, max_iter, tol, loglik_path, iters, active, true, [&](EmOpts eo) -> int {
         const double* xin = panel;
         if (q > 0) {
             const size_t n = (size_t)B * Tq * N;
@@ -1310,23 +1370,14 @@ int ar_em_run(dfm_handle* h, int B, int T, int N, int r, int nlag, int q, const 
                                rho, LamP);
             HIP_TRY(h, hipGetLastError());
         }
-        EmOpts eo;
         eo.A_out = AP; eo.Q_out = QP; eo.mu0_out = mu0P; eo.P0_out = P0P;
-        eo.active = active; eo.iters = iters; eo.ll_path = loglik_path; eo.k = it; eo.max_iter = max_iter; eo.tol = tol;
         if (int rc = enqueue_pass(h, p, B, Tq, N, Rk, xin, pp, sig2, fsm, Psm, llbuf, &eo)) return rc;
         ArMstepArgs ma;
         ma.B = B; ma.T = T; ma.N = N; ma.r = r; ma.q = q; ma.Rk = Rk;
         ma.panel = panel; ma.zsm = fsm; ma.Psm = Psm; ma.active = active; ma.Lam = Lam; ma.rho = rho; ma.sig2 = sig2;
         { ProfScope ps(h, K_MSTEP_STATS); HIP_TRY(h, launch_mstep_ar(ma, mws, h->stream)); }
-        if (tol > 0.0 && it + 1 < max_iter) {
-            act_host.resize(B);
-            HIP_TRY(h, hipMemcpyAsync(act_host.data(), active, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-            HIP_TRY(h, hipStreamSynchronize(h->stream));
-            bool any = false;
-            for (int b = 0; b < B; ++b) any = any || act_host[b] != 0;
-            if (!any) break;
-        }
-    }
+        return 0;
+    })) return rc;
     if (int rc = copy_block(h, B, Rk, Rk, r, r * nlag, AP, Avar)) return rc;
     if (int rc = copy_block(h, B, Rk, Rk, r, r, QP, Q)) return rc;
     if (int rc = copy_block(h, B, Rk, Rk, k, k, P0P, P0)) return rc;
@@ -1401,9 +1452,7 @@ int mf_pass_run(dfm_handle* h, int B, int T, int N, int r, int nlag, int L, cons
     for (double w : Wh)
         if (!isfinite(w)) return fail(h, DFM_E_DIMS, "mixed frequency: a weight is not finite%s");
     const int m = nlag > L ? nlag : L, k = r * m;
-    Plan p = make_plan(B, T, N, k, flags | DFM_F_SINGULAR_Q, false, false);
-    p.kdim = k; p.kb = r; p.ka = r * nlag;                   // (the companion structure, as ar_pass_run)
-    p.qsing = (flags & DFM_F_SINGULAR_Q) ? 1 : 0;
+    const Plan p = make_plan(h->opt, B, T, N, k, flags | DFM_F_SINGULAR_Q, false, false, lag_blocks(k, r, nlag, flags));
     if (int rc = ensure_ws(h, p.total)) return rc;
     const int Rk = p.Rp;
     double *LamP = at<double>(h, p.LamP), *AP = at<double>(h, p.AP), *QP = at<double>(h, p.QP),
@@ -1436,9 +1485,7 @@ int mf_run(dfm_handle* h, int B, int T, int N, int r, int nlag, int L, const dou
         if (int rc = mf_classes(h, N, L, Wh, &mc)) return rc;
     }
     const int m = nlag > L ? nlag : L, k = r * m;
-    Plan p = make_plan(B, T, N, k, flags | DFM_F_SINGULAR_Q, true, false);
-    p.qsing = (flags & DFM_F_SINGULAR_Q) ? 1 : 0;
-    p.kdim = k; p.kb = r; p.ka = r * nlag;                   // companion constraints; the observation loads on L blocks (rl = 0)
+    const Plan p = make_plan(h->opt, B, T, N, k, flags | DFM_F_SINGULAR_Q, true, false, lag_blocks(k, r, nlag, flags));   // (the observation loads on L blocks)
     // behind the pass's plan: the series step's table and moments, then the class weights and the tile lists
     size_t off = (p.total + 255) & ~(size_t)255;
     const size_t moff = take(off, mstep_mf_workspace(B, T, N, r, mc.C));
@@ -1463,33 +1510,21 @@ int mf_run(dfm_handle* h, int B, int T, int N, int r, int nlag, int L, const dou
     double* Psm = at<double>(h, p.Psm);
     double* llbuf = at<double>(h, p.llbuf);
     int* active = at<int>(h, p.active);
-    HIP_TRY(h, hipMemsetAsync(loglik_path, 0xFF, (size_t)B * max_iter * sizeof(double), h->stream));  // NaN
-    HIP_TRY(h, hipMemsetAsync(iters, 0, (size_t)B * sizeof(int), h->stream));
     const size_t np = (size_t)r * (r + 1) / 2, npk = (size_t)Rk * (Rk + 1) / 2;
     PaddedParams pp{LamP, AP, QP, mu0P, P0P};
     MfMstepArgs ma;
     ma.B = B; ma.T = T; ma.N = N; ma.r = r; ma.L = L; ma.Rk = Rk; ma.C = mc.C; ma.VW = mstep_mf_row_width(r); ma.ntiles = mc.ntiles;
     ma.panel = panel; ma.zsm = fsm; ma.Psm = Psm; ma.active = active; ma.Wc = at<double>(h, woff);
     ma.tile_class = at<int>(h, coff); ma.tile_series = at<int>(h, soff); ma.Lam = Lam; ma.R = R;
-    std::vector<int> act_host;
-    for (int it = 0; it < max_iter; ++it) {
+    if (int rc = em_loop(h, B, 0, max_iter, max_iter, tol, loglik_path, iters, active, true, [&](EmOpts eo) -> int {
         { ProfScope ps(h, K_PAD); HIP_TRY(h, launch_mf_loadings(B, N, r, L, Rk, Lam, W, LamP, h->stream)); }
-        EmOpts eo;
         eo.A_out = AP; eo.Q_out = QP; eo.mu0_out = mu0P; eo.P0_out = P0P;
-        eo.active = active; eo.iters = iters; eo.ll_path = loglik_path; eo.k = it; eo.max_iter = max_iter; eo.tol = tol;
         if (int rc = enqueue_pass(h, p, B, T, N, Rk, panel, pp, R, fsm, Psm, llbuf, &eo)) return rc;
         { ProfScope ps(h, K_MF_TABLE); HIP_TRY(h, launch_mf_table(ma, mws, h->stream)); }
         { ProfScope ps(h, K_MF_MOMENTS); HIP_TRY(h, launch_mf_moments(ma, mws, h->stream)); }
         { ProfScope ps(h, K_MF_SOLVE); HIP_TRY(h, launch_mf_solve(ma, mws, h->stream)); }
-        if (tol > 0.0 && it + 1 < max_iter) {
-            act_host.resize(B);
-            HIP_TRY(h, hipMemcpyAsync(act_host.data(), active, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-            HIP_TRY(h, hipStreamSynchronize(h->stream));
-            bool any = false;
-            for (int b = 0; b < B; ++b) any = any || act_host[b] != 0;
-            if (!any) break;
-        }
-    }
+        return 0;
+    })) return rc;
     if (int rc = copy_block(h, B, Rk, Rk, r, r * nlag, AP, Avar)) return rc;
     if (int rc = copy_block(h, B, Rk, Rk, r, r, QP, Q)) return rc;
     if (int rc = copy_block(h, B, Rk, Rk, k, k, P0P, P0)) return rc;
@@ -1510,14 +1545,15 @@ int obs_em_run(dfm_handle* h, int B, int T, int N, int ru, int ro, const double*
     const bool wide_obs = mstep_obs_wide_supported(ro, ru);   // r_o + r_u = 9 .. 32: the ordinary loadings step on augmented moments
     if (!mstep_obs_supported(ro, ru) && !wide_obs)
         return fail(h, DFM_E_R_UNSUPPORTED, "observed factors: need r_o >= 1, r_u >= 1 and r_o + r_u <= 32%s");
-    if (int rc = check_em_n(h, N, ru, flags)) return rc;
+    const bool fast = em_fast_eligible(h, N, ru, flags);
+    if (int rc = check_em_n(h, N, ru, fast)) return rc;
     if (wide_obs && N > 1024)   // (the joint regression at r_o + r_u > 8 runs on mstep_lam_kernel: lane = series, N <= 1024)
         return fail(h, DFM_E_DIMS, "observed factors with r_o + r_u > 8: N <= 1024%s");
     if (!panel || !G || !Lam || !R || !A || !Q || !mu0 || !P0 || !loglik_path || !iters)
         return fail(h, DFM_E_NULL, "required pointer is NULL%s");
     if (max_iter < 1) return fail(h, DFM_E_DIMS, "max_iter must be >= 1%s");
     HIP_TRY(h, hipSetDevice(h->device));
-    const Plan p = make_plan(B, T, N, ru, flags, true, fast_eligible(h, N, ru, flags) && !h->em_general);
+    const Plan p = make_plan(h->opt, B, T, N, ru, flags, true, fast);
     const size_t yoff = (p.total + 255) & ~(size_t)255;
     // wide joint regression: z [B][T][Re] | Var z [B][T][NPe] | LamAug [B][N][Re] | S11, S11inv [B][Re][Re] | Dmiss [B][N][NPe]
     const int Re = wide_obs ? mstep_obs_wide_width(ro, ru) : 0;
@@ -1546,18 +1582,13 @@ int obs_em_run(dfm_handle* h, int B, int T, int N, int ru, int ro, const double*
     double* Psm = at<double>(h, p.Psm);
     double* llbuf = at<double>(h, p.llbuf);
     int* active = at<int>(h, p.active);
-    HIP_TRY(h, hipMemsetAsync(loglik_path, 0xFF, (size_t)B * max_iter * sizeof(double), h->stream));  // NaN
-    HIP_TRY(h, hipMemsetAsync(iters, 0, (size_t)B * sizeof(int), h->stream));
     ObsArgs oa;
     oa.B = B; oa.T = T; oa.N = N; oa.ro = ro; oa.ru = ru; oa.Rl = Rl;
     oa.panel = panel; oa.G = G; oa.fsm = fsm; oa.Psm = Psm; oa.active = active; oa.Lam = Lam; oa.R = R;
     PaddedParams pp{LamP, AP, QP, mu0P, P0P};
-    std::vector<int> act_host;
-    for (int it = 0; it < max_iter; ++it) {
+    if (int rc = em_loop(h, B, 0, max_iter, max_iter, tol, loglik_path, iters, active, true, [&](EmOpts eo) -> int {
         { ProfScope ps(h, K_PAD); HIP_TRY(h, launch_obs_residual(oa, y, LamP, h->stream)); }
-        EmOpts eo;
         eo.A_out = AP; eo.Q_out = QP; eo.mu0_out = mu0P; eo.P0_out = P0P;
-        eo.active = active; eo.iters = iters; eo.ll_path = loglik_path; eo.k = it; eo.max_iter = max_iter; eo.tol = tol;
         if (int rc = enqueue_pass(h, p, B, T, N, Rl, y, pp, R, fsm, Psm, llbuf, &eo)) return rc;
         if (!wide_obs) {
             ProfScope ps(h, K_MSTEP_STATS);
@@ -1575,15 +1606,8 @@ int obs_em_run(dfm_handle* h, int B, int T, int N, int ru, int ro, const double*
             { ProfScope ps(h, K_MSTEP_STATS); HIP_TRY(h, launch_mstep_lam(Re, ma, h->stream)); }
             if (int rc = copy_block(h, (size_t)B * N, 1, Re, 1, ro + ru, LamAug, Lam)) return rc;   // (inactive replicates: their own values back)
         }
-        if (tol > 0.0 && it + 1 < max_iter) {
-            act_host.resize(B);
-            HIP_TRY(h, hipMemcpyAsync(act_host.data(), active, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-            HIP_TRY(h, hipStreamSynchronize(h->stream));
-            bool any = false;
-            for (int b = 0; b < B; ++b) any = any || act_host[b] != 0;
-            if (!any) break;
-        }
-    }
+        return 0;
+    })) return rc;
     const size_t np = (size_t)ru * (ru + 1) / 2, npl = (size_t)Rl * (Rl + 1) / 2;
     if (padded) {
         if (int rc = copy_block(h, B, Rp, Rp, ru, ru, AP, A)) return rc;
@@ -1635,43 +1659,8 @@ int dfm_create(dfm_handle** out, int device_id, void* stream) {
         delete h;
         return (int)e;
     }
-    if (const char* v = route_env("DFM_FORCE_GENERAL")) h->force_general = atoi(v) != 0;
-    if (const char* v = diag_env("DFM_COLLAPSE_VARIANT")) h->collapse_variant = atoi(v);
-    if (const char* v = diag_env("DFM_COLLAPSE_WPR")) { h->collapse_wpr = atoi(v); if (h->collapse_wpr < 0 || h->collapse_wpr > kSsumSlots) h->collapse_wpr = 0; }
     { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, h->device) == hipSuccess && prop.multiProcessorCount > 0) h->num_cu = prop.multiProcessorCount; }
     if (const char* v = route_env("DFM_NUM_CU")) { if (atoi(v) > 0) h->num_cu = atoi(v); }   // diagnostics: persistent grids sized for fewer CUs
-    if (const char* v = diag_env("DFM_NO_SIDE")) h->no_side = atoi(v) != 0;
-    if (const char* v = diag_env("DFM_PIPE")) h->no_pipe = atoi(v) == 0;
-    if (const char* v = diag_env("DFM_NO_RECURSION_WAVE")) h->no_rec_wave = atoi(v) != 0;
-    if (const char* v = diag_env("DFM_PAIR_BMAX")) h->pair_bmax = atoi(v) > 0 ? atoi(v) : 0;
-    if (const char* v = route_env("DFM_NO_PAIR")) { if (atoi(v) != 0) h->pair_bmax = 0; }
-    g_widen_small_r = !h->no_rec_wave;      // process-wide: follows the most recently created handle
-    if (const char* v = diag_env("DFM_NO_PFILL")) h->no_pfill = atoi(v) != 0;
-    if (const char* v = diag_env("DFM_FUSED_GRAM")) h->fused_gram = atoi(v) != 0;
-    if (const char* v = diag_env("DFM_NO_FUSE_COV")) h->no_fuse_cov = atoi(v) != 0;
-    if (const char* v = diag_env("DFM_NO_MSTEP_MFMA")) h->no_mstep_mfma = atoi(v) != 0;
-    if (const char* v = diag_env("DFM_NO_DEFER_EM")) h->no_defer_em = atoi(v) != 0;
-    if (const char* v = diag_env("DFM_EM_GENERAL")) h->em_general = atoi(v) != 0;
-    if (const char* v = diag_env("DFM_FUSE_GRAM")) h->fuse_gram = atoi(v) != 0;
-    if (const char* v = diag_env("DFM_SUBBATCH")) h->subbatch = atoi(v);
-    if (const char* v = diag_env("DFM_SCAN_ABL")) h->scan_abl = atoi(v);
-    if (const char* v = route_env("DFM_MSTEP_MISS")) g_mstep_miss_mode = atoi(v);
-    if (const char* v = route_env("DFM_PASS_FUSED")) h->pass_fused = atoi(v);
-    if (const char* v = diag_env("DFM_PASS_NSW")) h->pass_nsw = atoi(v);
-    if (const char* v = diag_env("DFM_PASS_NCOV")) h->pass_ncov = atoi(v);
-    if (const char* v = diag_env("DFM_GRAM_XX_VALU")) h->gram_xx_valu = atoi(v) != 0;
-    if (const char* v = diag_env("DFM_COLLAPSE_MISS_OLD")) h->collapse_miss_old = atoi(v) != 0;
-    if (const char* v = diag_env("DFM_NARROW_TAB")) h->narrow_tab_off = atoi(v) == 0;
-    g_odd_pad8 = true;                       // (process-wide like g_widen_small_r: follows the most recently created handle)
-    if (const char* v = diag_env("DFM_ODD_PAD8")) g_odd_pad8 = atoi(v) != 0;
-    if (const char* v = route_env("DFM_NO_CHUNK")) h->no_chunk = atoi(v) != 0;
-    g_plan_chunk = !h->no_chunk;
-    if (const char* v = route_env("DFM_CHUNK_W")) h->chunk_w = atoi(v) > 0 ? atoi(v) : 0;
-    if (const char* v = route_env("DFM_CHUNK_TOL")) h->chunk_tol = atof(v) > 0.0 ? atof(v) : 0.0;
-    if (const char* v = route_env("DFM_TILE_NC")) h->tile_nc = atoi(v) > 0 ? atoi(v) : 0;
-    if (const char* v = route_env("DFM_TILE_W")) h->tile_w = atoi(v) > 0 ? atoi(v) : 0;
-    if (const char* v = diag_env("DFM_WIDE_OLD")) h->wide_old = atoi(v) != 0;
-    if (const char* v = diag_env("DFM_COV_WAVE")) h->cov_wave = atoi(v) != 0;
     *out = h;
     return 0;
 }
@@ -1795,11 +1784,12 @@ const char* dfm_last_error(const dfm_handle* h) { return h ? h->err : "null hand
 size_t dfm_workspace_bytes(int B, int T, int N, int r, unsigned flags) {
     if (B < 1 || T < 1 || N < 1 || r < 1 || r > DFM_MAX_R) return 0;
     // the larger of the two plans an entry point may take for this shape: sequential (general) path, or -- balanced
-    // panels only -- the time-parallel fast path, whose `tab` ([B][T][3][Rp][Rp]) and M-step partial sums are larger
-    size_t best = make_plan(B, T, N, r, flags, true, false).total;
-    const int Rp = pad_r(r);
-    if (!(flags & (DFM_F_MAY_HAVE_MISSING | DFM_F_SINGULAR_Q)) && (collapse_dma_supported(Rp, N) || collapse_wide_supported(Rp, N))) {
-        const size_t f = make_plan(B, T, N, r, flags, true, true).total;
+    // panels only -- the time-parallel fast path, whose `tab` ([B][T][3][Rp][Rp]) and M-step partial sums are larger.
+    // No handle: the switches as the environment stands now, i.e. what a handle created at this moment would plan.
+    const RouteOpts o = route_opts_from_env();
+    size_t best = make_plan(o, B, T, N, r, flags, true, false).total;
+    if (fast_eligible(o, N, r, flags)) {
+        const size_t f = make_plan(o, B, T, N, r, flags, true, true).total;
         if (f > best) best = f;
     }
     return best;
@@ -1812,10 +1802,11 @@ int dfm_ks_pass_batch_dev(dfm_handle* h, int B, int T, int N, int r, const doubl
     if (int rc = check_dims(h, B, T, N, r)) return rc;
     if (!panel || !Lam || !R || !A || !Q || !mu0 || !P0 || !f_smooth || !loglik)
         return fail(h, DFM_E_NULL, "required pointer is NULL%s");
-    if (!fast_eligible(h, N, r, flags))
+    const bool fast = fast_eligible(h->opt, N, r, flags);
+    if (!fast)
         if (int rc = check_general_n(h, N, r, true)) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
-    if (needs_odd_pad(fast_eligible(h, N, r, flags), N, r, flags, B)) {  // odd N beyond the tilings: one all-missing series appended
+    if (needs_odd_pad(h->opt, fast, N, r, flags, B)) {  // odd N beyond the tilings: one all-missing series appended
         OddPad o;
         if (int rc = odd_pad(h, B, T, N, r, panel, Lam, R, &o)) return rc;
         // (the appended series is missing in EVERY period: the padded problem has missing cells whatever the caller said about N)
@@ -1823,7 +1814,7 @@ int dfm_ks_pass_batch_dev(dfm_handle* h, int B, int T, int N, int r, const doubl
                                      flags | DFM_F_MAY_HAVE_MISSING);
     }
     if (pipe_eligible(h, B, N, r, flags)) {
-        const Plan ps = make_plan(pipe_sub(h), T, N, r, flags, false, false);
+        const Plan ps = make_plan(h->opt, pipe_sub(h), T, N, r, flags, false, false);
         const size_t rr = (size_t)r * r, np = (size_t)r * (r + 1) / 2;
         return pipe_run(h, B, ps.total, [&](int b0, int bn) -> int {
             PaddedParams pp;
@@ -1832,7 +1823,7 @@ int dfm_ks_pass_batch_dev(dfm_handle* h, int B, int T, int N, int r, const doubl
                                 P_smooth ? P_smooth + (size_t)b0 * T * np : nullptr, loglik + b0, nullptr);
         });
     }
-    const Plan p = make_plan(B, T, N, r, flags, false, fast_eligible(h, N, r, flags));
+    const Plan p = make_plan(h->opt, B, T, N, r, flags, false, fast);
     if (int rc = ensure_ws(h, p.total)) return rc;
     PaddedParams pp;
     if (int rc = pad_params(h, p, B, N, r, Lam, A, Q, mu0, P0, &pp)) return rc;
@@ -1916,7 +1907,7 @@ int dfm_em_batch(dfm_handle* h, int B, int T, int N, int r, const double* panel,
                  double* Q, double* mu0, double* P0, int max_iter, double tol, double* loglik_path, int* iters,
                  double* f_smooth, double* P_smooth, unsigned flags) {
     if (int rc = check_dims(h, B, T, N, r)) return rc;
-    if (int rc = check_em_n(h, N, r, flags)) return rc;
+    if (int rc = check_em_n(h, N, r, em_fast_eligible(h, N, r, flags))) return rc;
     if (!panel || !Lam || !R || !A || !Q || !mu0 || !P0 || !loglik_path || !iters)
         return fail(h, DFM_E_NULL, "required pointer is NULL%s");
     if (max_iter < 1) return fail(h, DFM_E_DIMS, "max_iter must be >= 1%s");
@@ -2169,7 +2160,7 @@ int dfm_pca_init_batch_dev(dfm_handle* h, int B, int T, int N, int r, const doub
     pa.S = at<double>(h, oS); pa.V = at<double>(h, oV); pa.Y = at<double>(h, oY); pa.F = at<double>(h, oF);
     pa.Lam = Lam; pa.Rv = R; pa.A = A; pa.Q = Q; pa.mu0 = mu0; pa.P0 = P0; pa.factors = factors;
     pa.status = h->status_dev;
-    { ProfScope ps(h, K_GRAM_XX); HIP_TRY(h, launch_gram_xx(pa, h->stream, h->gram_xx_valu ? 1 : 0)); }
+    { ProfScope ps(h, K_GRAM_XX); HIP_TRY(h, launch_gram_xx(pa, h->stream, h->opt.gram_xx_valu ? 1 : 0)); }
     { ProfScope ps(h, K_PCA); HIP_TRY(h, launch_pca(Rp, pa, h->stream)); }
     return 0;
 }

@@ -102,7 +102,8 @@ int dfm_chunk_fallbacks(dfm_handle* h, int* n_failed, int* n_total);
 /* Bytes of device workspace the handle will hold for a pass / EM call on a (B,T,N,r) problem with these flags (for
  * capacity planning; the larger of the sequential and -- for balanced panels -- the time-parallel plan).  The VAR(p),
  * AR-idiosyncratic, PCA and synthetic-panel entry points add their own scratch on top (a quasi-differenced panel copy,
- * [B][N][N] Gram matrices, ...). */
+ * [B][N][N] Gram matrices, ...).  Environment switches are read at this call: the figure is that of a handle created now
+ * (a handle keeps the switches of its own creation). */
 size_t dfm_workspace_bytes(int B, int T, int N, int r, unsigned flags);
 
 /* --- one full Kalman-smoother pass per replicate (SURVEY.md §8(d) "pass") ---------------------

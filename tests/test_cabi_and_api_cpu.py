@@ -38,6 +38,17 @@ def test_argument_errors_without_a_device():
     assert lib.dfm_workspace_bytes(0, 10, 10, 2, 0) == 0
     assert lib.dfm_workspace_bytes(4, 10, 10, 40, 0) == 0          # r > DFM_MAX_R
     assert lib.dfm_workspace_bytes(4, 50, 20, 3, 1) > lib.dfm_workspace_bytes(4, 50, 20, 3, 0) > 0
+    # no handle: it prices what a handle created now would plan (Rp = 8 with missing cells: the time-chunked recursion's scratch)
+    old = os.environ.pop("DFM_NO_CHUNK", None)
+    try:
+        chunked = lib.dfm_workspace_bytes(4, 500, 200, 8, 1)
+        os.environ["DFM_NO_CHUNK"] = "1"
+        assert 0 < lib.dfm_workspace_bytes(4, 500, 200, 8, 1) < chunked
+        del os.environ["DFM_NO_CHUNK"]
+        assert lib.dfm_workspace_bytes(4, 500, 200, 8, 1) == chunked
+    finally:
+        if old is not None:
+            os.environ["DFM_NO_CHUNK"] = old
     assert lib.dfm_create(None, 0, None) == -3                     # DFM_E_NULL
     assert lib.dfm_last_error(None) == b"null handle"
     assert lib.dfm_synchronize(None) == -3
