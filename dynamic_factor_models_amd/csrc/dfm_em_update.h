@@ -1,12 +1,14 @@
 // dfm_em_update.h -- the transition half of the M-step on the balanced fast path for Rp <= 8 as a DEVICE FUNCTION of one wave
-// (em_update_kernel's algorithm, fastpath.hip: one lane group of R lanes per replicate row, 64 / R time slices per wave), so that
+// (one lane group of R lanes per replicate row, 64 / R time slices per wave), so that
 // it can run as extra workgroups at the front of the loadings step's streaming launch (mstep_mfma.hip) instead of as its own
 // 33-us launch between the E-step and the second panel stream: nothing in it depends on the panel, and the streaming launch
-// leaves plenty of idle issue slots.  Sufficient statistics, A = S10 S00^-1, Q = sym(S11 - A S10') / T, mu0, P0, S11^-1 and the
-// per-replicate EM bookkeeping exactly as em_update_kernel / the epilogue of recursion_kernel (Shumway-Stoffer 1982).
+// leaves plenty of idle issue slots.  The sufficient statistics are formed here; the per-replicate EM bookkeeping and the transition
+// M-step are dfm_em_epilogue.h's (em_decide / em_record, transition_mstep_rows), as in the epilogue of recursion_kernel.
+// em_update_kernel (fastpath.hip) is this function as a launch of its own: one 64-thread workgroup per replicate.
 #pragma once
 #include "dfm_kernels.h"
 #include "dfm_smallmat.h"
+#include "dfm_em_epilogue.h"
 
 namespace dfm {
 
@@ -58,62 +60,19 @@ __device__ __forceinline__ void em_update_wave(const EmUpdArgs& a, int b, bool v
         S00[j] = S11[j] - fma(fTi, fTj, a.PT[o + j]) + fma(f0i, f0[j], P0s[j]);
     }
     bool em_apply = true;
-    if (a.active) {                                          // EM bookkeeping (oracle/kalman_oracle.py em())
+    if (a.active) {                                          // EM bookkeeping (dfm_em_epilogue.h)
         const double ll = a.loglik[b];
-        const bool was = a.k == 0 ? true : (a.active[b] != 0);
-        bool go = was;
-        if (was && a.k >= 1 && a.tol > 0.0) {
-            const double llp = a.ll_path[(size_t)b * a.max_iter + a.k - 1];
-            go = !((ll - llp) / (0.5 * (fabs(ll) + fabs(llp))) < a.tol);
-        }
-        em_apply = go;
+        const EmDecision d = em_decide(a, b, ll);
+        em_apply = d.go;
         wave_lds_sync();                                     // (every lane has read active / ll_path)
         __builtin_amdgcn_s_waitcnt(0);
-        if (live && i == 0) {
-            if (was) { a.ll_path[(size_t)b * a.max_iter + a.k] = ll; a.iters[b] = a.k + 1; }
-            a.active[b] = go ? 1 : 0;
-        }
+        if (live && i == 0) em_record(a, b, ll, d);
     }
-    double inv[R], An[R], tmp[R], Qn[R], P0n[R];
-#pragma unroll
-    for (int j = 0; j < R; ++j) inv[j] = S00[j];
-    (void)gj_inverse<R, true>(inv, X, i);
-    wave_lds_sync();
-    store_row<R>(X, i, inv);
-    wave_lds_sync();
-    mm_rows<R>(An, S10, X);                                  // A row i
-    wave_lds_sync();
-    store_row<R>(X, i, S10);
-    wave_lds_sync();
-    mm_rowsT<R>(tmp, An, X);                                 // (A S10')[i][:]
-#pragma unroll
-    for (int j = 0; j < R; ++j) Qn[j] = (S11[j] - tmp[j]) / (double)T;
-    wave_lds_sync();
-    store_row<R>(X, i, Qn);
-    wave_lds_sync();
-#pragma unroll
-    for (int j = 0; j < R; ++j) Qn[j] = 0.5 * (Qn[j] + X[j * R + i]);
-    wave_lds_sync();
-    store_row<R>(X, i, P0s);
-    wave_lds_sync();
-#pragma unroll
-    for (int j = 0; j < R; ++j) P0n[j] = 0.5 * (P0s[j] + X[j * R + i]);
-#pragma unroll
-    for (int j = 0; j < R; ++j) inv[j] = S11[j];
-    (void)gj_inverse<R, true>(inv, X, i);
     if (live) {
 #pragma unroll
-        for (int j = 0; j < R; ++j) { a.S11[o + j] = S11[j]; a.S11inv[o + j] = inv[j]; }
-        if (em_apply) {
-#pragma unroll
-            for (int j = 0; j < R; ++j) {
-                a.A_out[o + j] = An[j];
-                a.Q_out[o + j] = Qn[j];
-                a.P0_out[o + j] = P0n[j];
-            }
-            a.mu0_out[(size_t)b * R + i] = f0i;
-        }
+        for (int j = 0; j < R; ++j) a.S11[o + j] = S11[j];
     }
+    transition_mstep_rows<R, true>(X, i, a, b, T, live, S11, S10, S00, P0s, f0i, em_apply);
 }
 
 }  // namespace dfm

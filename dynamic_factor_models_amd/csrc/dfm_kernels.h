@@ -248,7 +248,7 @@ bool mstep_mfma_supported(int Rpad, int N);
 size_t mstep_mfma_workspace(int B, int N, int Rpad, int wpr);
 struct EmUpdArgs;
 // ua != nullptr (Rp <= 8): the transition M-step of every replicate runs as extra workgroups at the front of the streaming launch
-// (dfm_em_update.h) instead of as em_update_kernel's own launch
+// (dfm_em_update.h: em_update_wave) instead of as em_update_kernel's launch of the same function
 hipError_t launch_mstep_mfma(int Rpad, const MstepArgs& a, int wpr, double* workspace, hipStream_t s, const EmUpdArgs* ua = nullptr);
 
 // Series block of the ECM iteration with AR(q) idiosyncratic terms (mstep_ar.hip): loadings, AR coefficients and innovation

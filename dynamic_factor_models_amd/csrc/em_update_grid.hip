@@ -1,11 +1,11 @@
 // em_update_grid.hip -- the transition half of the M-step on the balanced fast path for the wide states (Rp = 16, 32):
-// em_update_kernel's contract (fastpath.hip) with an ELEMENT of every Rp x Rp matrix per thread.
+// the contract of em_update_wave (dfm_em_update.h, Rp <= 8) with an ELEMENT of every Rp x Rp matrix per thread.
 //
 //     S11 = sum_{t=1..T} E[f_t f_t' | X],  S10 = sum_{t=1..T} E[f_t f_{t-1}' | X],  S00 = sum_{t=0..T-1} E[f_t f_t' | X]
-//     A = S10 S00^-1,  Q = sym(S11 - A S10') / T,  mu0 = f_0|T,  P0 = sym(P_0|T),  S11^-1 for the loadings step
+//     then the bookkeeping and the transition M-step of dfm_em_epilogue.h (em_decide / em_record, transition_mstep_grid)
 //
-// em_update_kernel gives a replicate lane groups of Rp lanes (lane = matrix row): at Rp = 32 its two Gauss-Jordan inversions
-// and three products hold 5 rows of 32 doubles per lane -- 512 VGPRs and 357 spilled: 0.40 ms per EM iteration of config 4
+// The row-per-lane form gives a replicate lane groups of Rp lanes (lane = matrix row): at Rp = 32 its two Gauss-Jordan inversions
+// and three products held 5 rows of 32 doubles per lane -- 512 VGPRs and 357 spilled: 0.40 ms per EM iteration of config 4
 // (0.20 ms at Rp = 16), the largest piece of the iteration after the two panel reads.  Here:
 //   * sum_t f_t f_t' and sum_t f_t f_{t-1}' on the matrix pipe: the (Rp / 16)^2 tiles x 4 slices of the periods = one wave each
 //     (v_mfma_f64_16x16x4 with A[i][k] = f_{t+k}[16 it + i], B[k][j] = f_{t+k}[16 jt + j] resp. f_{t+k-1}), slices summed in LDS;
@@ -17,6 +17,7 @@
 #include "dfm_kernels.h"
 #include "dfm_smallmat.h"
 #include "dfm_grid.h"
+#include "dfm_em_epilogue.h"
 
 namespace dfm {
 
@@ -95,49 +96,16 @@ __global__ __launch_bounds__(R * R) void em_update_grid_kernel(EmUpdArgs a) {
     const double P0s = a.P0s[o];
     const double S00 = S11 - fma(fTi, fTj, a.PT[o]) + fma(f0i, f0j, P0s);
 
-    // EM bookkeeping (oracle/kalman_oracle.py em()): record ll_k; stop WITHOUT applying this M-step when the relative
-    // improvement over ll_{k-1} is below tol
     bool em_apply = true;
-    if (a.active) {
+    if (a.active) {                                          // EM bookkeeping (dfm_em_epilogue.h)
         const double ll = a.loglik[b];
-        const bool was = a.k == 0 ? true : (a.active[b] != 0);
-        bool go = was;
-        if (was && a.k >= 1 && a.tol > 0.0) {
-            const double llp = a.ll_path[(size_t)b * a.max_iter + a.k - 1];
-            go = !((ll - llp) / (0.5 * (fabs(ll) + fabs(llp))) < a.tol);
-        }
-        em_apply = go;
+        const EmDecision d = em_decide(a, b, ll);
+        em_apply = d.go;
         __syncthreads();                                     // every thread has read active / ll_path
-        if (l == 0) {
-            if (was) { a.ll_path[(size_t)b * a.max_iter + a.k] = ll; a.iters[b] = a.k + 1; }
-            a.active[b] = go ? 1 : 0;
-        }
+        if (l == 0) em_record(a, b, ll, d);
     }
-
-    // A = S10 S00^-1
-    double inv = S00;
-    (void)G.sweep_inverse(inv);
-    L0[TS * i + j] = S10;
-    L1[TS * i + j] = inv;                                     // symmetric: row j = column j
-    __syncthreads();
-    const double An = dot_rows<R>(L0, L1, i, j);
-    __syncthreads();
-    L1[TS * i + j] = An;
-    __syncthreads();
-    const double AS = dot_rows<R>(L1, L0, i, j);              // (A S10')[i][j] = sum_k A[i][k] S10[j][k]
-    const double Qr = (S11 - AS) / (double)T;
-    const double Qn = 0.5 * (Qr + G.transposed(Qr));
-    const double P0n = 0.5 * (P0s + G.transposed(P0s));
-    double inv11 = S11;
-    (void)G.sweep_inverse(inv11);
     a.S11[o] = S11;
-    a.S11inv[o] = inv11;
-    if (em_apply) {
-        a.A_out[o] = An;
-        a.Q_out[o] = Qn;
-        a.P0_out[o] = P0n;
-        if (j == 0) a.mu0_out[(size_t)b * R + i] = f0i;
-    }
+    transition_mstep_grid<R>(G, L0, L1, a, b, T, S11, S10, S00, P0s, f0i, em_apply);
 }
 
 namespace {

@@ -25,6 +25,7 @@
 
 #include "dfm_cov.h"
 #include "dfm_scan.h"
+#include "dfm_em_update.h"
 
 namespace dfm {
 
@@ -273,172 +274,28 @@ __global__ __launch_bounds__(scan_threads(R)) void meanscan_kernel(FastArgs a) {
 
 
 // ================================================================================================
-// em_update_kernel: the transition half of the M-step on the balanced fast path
+// em_update_kernel: the transition half of the M-step on the balanced fast path, Rp <= 8
 // ================================================================================================
-// Sufficient statistics from the smoother output (means: f_smooth in the padded layout, f0s; covariance sums
-// SP11, SU, P0s, P_T from cov_kernel):
-//     S11 = sum_{t=1..T} E[f_t f_t' | X],   S10 = sum_{t=1..T} E[f_t f_{t-1}' | X],   S00 = sum_{t=0..T-1} E[f_t f_t' | X]
-// then  A = S10 S00^-1,  Q = sym(S11 - A S10') / T,  mu0 = f_0|T,  P0 = sym(P_0|T)  (Shumway-Stoffer 1982), the
-// S11, S11^-1 the loadings step needs, and the per-replicate EM bookkeeping -- exactly the epilogue of
-// recursion_kernel (recursion.hip), which does the same for panels with missing cells.
-// One lane group of R lanes per replicate (lane i = row i), 64 / R replicates per wave.
-__host__ __device__ constexpr int em_update_waves(int R) { return R >= 16 ? 4 : 1; }
+// em_update_wave (dfm_em_update.h) as a launch of its own: one wave per replicate.  The same function runs inside the loadings
+// step's streaming launch (mstep_mfma.hip) when the transition step is deferred into it; Rp = 16 / 32 is em_update_grid.hip.
 template <int R>
-__global__ __launch_bounds__(64 * em_update_waves(R)) void em_update_kernel(EmUpdArgs a) {
-    // NW waves per replicate (1 for Rp <= 8; 4 for the wide states, where one wave walked T / 2 periods of 64 dependent FMAs per
-    // lane: 0.79 ms per EM iteration of config 4): lane (i = l % R, slice = NW-wave x l / R) sums row i of f_t f_t' and
-    // f_t f_{t-1}' over the periods t = slice (mod NW 64 / R) -- independent loads -- then the slices are folded with
-    // xor-shuffles, the waves through LDS (every wave adds the NW partial sums in the same order), and every slice runs the
-    // (tiny) epilogue redundantly on its own LDS region; slice 0 of wave 0 writes.
-    constexpr int GPW = 64 / R;
-    constexpr int NW = em_update_waves(R);
-    extern __shared__ __attribute__((aligned(16))) double ems[];
-    double* Xs = ems;                                        // [NW * GPW][R * R + 2 R]
-    double* red = ems + NW * GPW * (R * R + 2 * R);          // NW > 1: [NW][2][R * R]
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int g = lane / R, i = lane % R;
-    const int b = blockIdx.x;
-    const bool live = (g == 0 && wave == 0);
-    double* X = Xs + (wave * GPW + g) * (R * R + 2 * R);
-    const int T = a.T;
-    const size_t o = (size_t)b * R * R + (size_t)i * R;
-    const double* __restrict__ f = a.fsm + (size_t)b * T * R;
-    const double* __restrict__ f0 = a.f0s + (size_t)b * R;
-
-    double M11[R], M10[R];
-#pragma unroll
-    for (int j = 0; j < R; ++j) { M11[j] = 0.0; M10[j] = 0.0; }
-#pragma unroll 2
-    for (int t = wave * GPW + g; t < T; t += NW * GPW) {
-        double cur[R], prev[R];
-        const double* pp = (t == 0) ? f0 : f + (size_t)(t - 1) * R;
-#pragma unroll
-        for (int j = 0; j < R; ++j) { cur[j] = f[(size_t)t * R + j]; prev[j] = pp[j]; }
-        const double ci = f[(size_t)t * R + i];
-#pragma unroll
-        for (int j = 0; j < R; ++j) {
-            M11[j] = fma(ci, cur[j], M11[j]);
-            M10[j] = fma(ci, prev[j], M10[j]);
-        }
-    }
-#pragma unroll
-    for (int off = R; off < 64; off <<= 1) {
-#pragma unroll
-        for (int j = 0; j < R; ++j) {
-            M11[j] += __shfl_xor(M11[j], off, kWave);
-            M10[j] += __shfl_xor(M10[j], off, kWave);
-        }
-    }
-    if constexpr (NW > 1) {
-        if (g == 0) {
-#pragma unroll
-            for (int j = 0; j < R; ++j) { red[(wave * 2 + 0) * R * R + i * R + j] = M11[j]; red[(wave * 2 + 1) * R * R + i * R + j] = M10[j]; }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < R; ++j) {
-            double s1 = 0.0, s0 = 0.0;
-#pragma unroll
-            for (int w = 0; w < NW; ++w) { s1 += red[(w * 2 + 0) * R * R + i * R + j]; s0 += red[(w * 2 + 1) * R * R + i * R + j]; }
-            M11[j] = s1; M10[j] = s0;
-        }
-    }
-    const double f0i = f0[i];
-    const double fTi = f[(size_t)(T - 1) * R + i];
-    double fT[R];
-#pragma unroll
-    for (int j = 0; j < R; ++j) fT[j] = f[(size_t)(T - 1) * R + j];
-    double S11[R], S10[R], S00[R], P0s[R];
-#pragma unroll
-    for (int j = 0; j < R; ++j) {
-        S11[j] = a.SP11[o + j] + M11[j];
-        S10[j] = a.SU[o + j] + M10[j];
-        P0s[j] = a.P0s[o + j];
-        S00[j] = S11[j] - fma(fTi, fT[j], a.PT[o + j]) + fma(f0i, a.f0s[(size_t)b * R + j], P0s[j]);
-    }
-    // EM bookkeeping (oracle/kalman_oracle.py em()): record ll_k; stop WITHOUT applying this M-step when the
-    // relative improvement over ll_{k-1} is below tol
-    bool em_apply = true;
-    if (a.active) {
-        const double ll = a.loglik[b];
-        const bool was = a.k == 0 ? true : (a.active[b] != 0);
-        bool go = was;
-        if (was && a.k >= 1 && a.tol > 0.0) {
-            const double llp = a.ll_path[(size_t)b * a.max_iter + a.k - 1];
-            go = !((ll - llp) / (0.5 * (fabs(ll) + fabs(llp))) < a.tol);
-        }
-        em_apply = go;
-        __syncthreads();                                     // every lane has read active / ll_path
-        if (live && i == 0) {
-            if (was) { a.ll_path[(size_t)b * a.max_iter + a.k] = ll; a.iters[b] = a.k + 1; }
-            a.active[b] = go ? 1 : 0;
-        }
-    }
-    double inv[R], An[R], tmp[R], Qn[R], P0n[R];
-#pragma unroll
-    for (int j = 0; j < R; ++j) inv[j] = S00[j];
-    (void)gj_inverse<R>(inv, X, i);
-    __syncthreads();
-    store_row<R>(X, i, inv);
-    __syncthreads();
-    mm_rows<R>(An, S10, X);                                  // A row i
-    __syncthreads();
-    store_row<R>(X, i, S10);
-    __syncthreads();
-    mm_rowsT<R>(tmp, An, X);                                 // (A S10')[i][:]
-#pragma unroll
-    for (int j = 0; j < R; ++j) Qn[j] = (S11[j] - tmp[j]) / (double)T;
-    __syncthreads();
-    store_row<R>(X, i, Qn);
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < R; ++j) Qn[j] = 0.5 * (Qn[j] + X[j * R + i]);
-    __syncthreads();
-    store_row<R>(X, i, P0s);
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < R; ++j) P0n[j] = 0.5 * (P0s[j] + X[j * R + i]);
-#pragma unroll
-    for (int j = 0; j < R; ++j) inv[j] = S11[j];
-    (void)gj_inverse<R>(inv, X, i);
-    if (live) {
-#pragma unroll
-        for (int j = 0; j < R; ++j) { a.S11[o + j] = S11[j]; a.S11inv[o + j] = inv[j]; }
-        if (em_apply) {
-#pragma unroll
-            for (int j = 0; j < R; ++j) {
-                a.A_out[o + j] = An[j];
-                a.Q_out[o + j] = Qn[j];
-                a.P0_out[o + j] = P0n[j];
-            }
-            a.mu0_out[(size_t)b * R + i] = f0i;
-        }
-    }
+__global__ __launch_bounds__(64) void em_update_kernel(EmUpdArgs a) {
+    extern __shared__ __attribute__((aligned(16))) double ems[];   // [64 / R][R * R + 2 R]
+    em_update_wave<R>(a, blockIdx.x, true, threadIdx.x, ems);
 }
 
 template <int R>
 static hipError_t launch_em_update_r(const EmUpdArgs& a, hipStream_t s) {
-    constexpr int NW = em_update_waves(R), GPW = 64 / R;
-    const size_t lds = ((size_t)NW * GPW * (R * R + 2 * R) + (NW > 1 ? (size_t)NW * 2 * R * R : 0)) * sizeof(double);
-    static LdsOptIn attr_done;
-    if (!attr_done && lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&em_update_kernel<R>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
-        if (e != hipSuccess) return e;
-        attr_done = true;
-    }
-    hipLaunchKernelGGL((em_update_kernel<R>), dim3(a.B), dim3(64 * NW), lds, s, a);
+    const size_t lds = (size_t)(64 / R) * (R * R + 2 * R) * sizeof(double);
+    hipLaunchKernelGGL((em_update_kernel<R>), dim3(a.B), dim3(64), lds, s, a);
     return hipGetLastError();
 }
 hipError_t launch_em_update(int Rpad, const EmUpdArgs& a, hipStream_t s) {
-    static const bool old_wide = [] { const char* v = diag_env("DFM_EM_UPDATE_OLD"); return v && atoi(v) != 0; }();
-    if (!old_wide && em_update_grid_supported(Rpad)) return launch_em_update_grid(Rpad, a, s);   // em_update_grid.hip
+    if (em_update_grid_supported(Rpad)) return launch_em_update_grid(Rpad, a, s);   // em_update_grid.hip
     switch (Rpad) {
         case 2: return launch_em_update_r<2>(a, s);
         case 4: return launch_em_update_r<4>(a, s);
         case 8: return launch_em_update_r<8>(a, s);
-        case 16: return launch_em_update_r<16>(a, s);
-        case 32: return launch_em_update_r<32>(a, s);
         default: return hipErrorInvalidValue;
     }
 }

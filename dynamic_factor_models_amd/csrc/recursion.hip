@@ -22,6 +22,7 @@
 // bitmask remembers at which periods a new pair was made.
 #include "dfm_kernels.h"
 #include "dfm_smallmat.h"
+#include "dfm_em_epilogue.h"
 
 namespace dfm {
 
@@ -367,20 +368,10 @@ __global__ __launch_bounds__(64) void recursion_kernel(RecursionArgs a) {
             a.loglik[b] = ll;
             if (a.ncov) a.ncov[b] = e + 1;
         }
-        // EM bookkeeping (oracle/kalman_oracle.py em()): record ll_k; stop WITHOUT applying this
-        // M-step when the relative improvement over ll_{k-1} is below tol.
-        if (a.active) {
-            const bool was = a.k == 0 ? true : (a.active[b] != 0);
-            bool go = was;
-            if (was && a.k >= 1 && a.tol > 0.0) {
-                const double llp = a.ll_path[(size_t)b * a.max_iter + a.k - 1];
-                go = !((ll - llp) / (0.5 * (fabs(ll) + fabs(llp))) < a.tol);
-            }
-            em_apply = go;
-            if (live && i == 0) {
-                if (was) { a.ll_path[(size_t)b * a.max_iter + a.k] = ll; a.iters[b] = a.k + 1; }
-                a.active[b] = go ? 1 : 0;
-            }
+        if (a.active) {   // EM bookkeeping (dfm_em_epilogue.h)
+            const EmDecision d = em_decide(a, b, ll);
+            em_apply = d.go;
+            if (live && i == 0) em_record(a, b, ll, d);
         }
     }
 
@@ -532,7 +523,8 @@ __global__ __launch_bounds__(64) void recursion_kernel(RecursionArgs a) {
             a.f0s[(size_t)b * R + i] = fs;
         }
         if (a.A_out) {
-            // A = S10 S00^-1 ;  Q = sym(S11 - A S10') / T ;  mu0 = f_0|T ;  P0 = sym(P_0|T) ;  S11^-1
+            // the text of transition_mstep_rows (dfm_em_epilogue.h) written out: inlined from there, recursion_kernel<32, true>
+            // needs 32 bytes more scratch per lane (hipcc of ROCm 7.2.0)
             double inv[R], An[R], tmp[R], Qn[R], P0n[R];
             const int kd = a.kdim;                         // > 0: companion state (f_t, .., f_{t-p+1}) of width kd
 #pragma unroll

@@ -21,13 +21,14 @@
 // (recursion_pair: ~410 instructions per period at one element per lane).  Scratch: -Z_t and w_t (44 doubles per period,
 // chunk-major so that lanes are contiguous: 180 KB per replicate instead of the 1 MB (Z, J) table).
 // EM (template EM): the lane adds U_t = Cov(f_t+1, f_t) + f_t+1 f_t' and P_t + f_t f_t' of its counted periods into LDS
-// accumulators (ds_add_f64, two lanes per slot); the wave then finishes S11 / S10 / S00 and the transition M-step in the
-// element-per-lane layout exactly as recursion_pair_kernel does.
+// accumulators (ds_add_f64, two lanes per slot); the wave then finishes S11 / S10 / S00 in the element-per-lane layout
+// and calls the shared stop rule and transition M-step (dfm_em_epilogue.h).
 // Reference counterpart: none (dfm_functions.ipynb:21-23 declares `Parametric` only); oracle: oracle/kalman_oracle.py.
 #include <stdlib.h>
 #include "dfm_kernels.h"
 #include "dfm_smallmat.h"
 #include "dfm_grid.h"
+#include "dfm_em_epilogue.h"
 #include "dfm_chunk_core.h"
 #include "dfm_ctbuild.h"
 
@@ -572,34 +573,23 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
     if constexpr (!EM) return;
 
     // =================================================== EM epilogue =======================================================
-    // element-per-lane layout (lane = 8 i + j), as recursion_pair_kernel's: sufficient statistics, EM bookkeeping, transition M-step
+    // element-per-lane layout (lane = 8 i + j): sufficient statistics, then EM bookkeeping and transition M-step of dfm_em_epilogue.h
     if constexpr (EM) {
         constexpr int TS = kTileStride<R>, RT = R * TS, RR = 64;
         double* L0 = acc10 + 100 * kAccSlots;
         double* L1 = L0 + RT;
         bool em_apply = true;
-        if (a.active) {
-            const bool was = a.k == 0 ? true : (a.active[b] != 0);
-            bool go = was;
-            if (was && a.k >= 1 && a.tol > 0.0) {
-                const double llp = a.ll_path[(size_t)b * a.max_iter + a.k - 1];
-                go = !((ll - llp) / (0.5 * (fabs(ll) + fabs(llp))) < a.tol);
-            }
-            em_apply = go;
+        if (a.active) {   // EM bookkeeping (dfm_em_epilogue.h)
+            const EmDecision d = em_decide(a, b, ll);
+            em_apply = d.go;
             __builtin_amdgcn_wave_barrier();
-            if (lane == 0) {
-                if (was) { a.ll_path[(size_t)b * a.max_iter + a.k] = ll; a.iters[b] = a.k + 1; }
-                a.active[b] = go ? 1 : 0;
-            }
+            if (lane == 0) em_record(a, b, ll, d);
         }
         wave_mem_fence();                                           // state 0 (term[44..]) and the LDS accumulators
         wave_lds_sync();
         const int i = lane >> 3, j = lane & 7;
         Grid<R> G;
         G.l = lane; G.i = i; G.j = j;
-        const int Rc = a.Rc > 0 ? a.Rc : R;
-        const bool inC = i < Rc && j < Rc;
-        const bool inL = i < rl && j < rl;
         double S10 = 0.0, S11 = 0.0;
         {
             const int pk = pidx(i, j);
@@ -617,41 +607,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
         S11 += PsT + fTfT;                                         // state T
         const double S00 = S11 - (PsT + fTfT) + fma(f0r, f0c, Ps);
         const size_t o = (size_t)b * RR + lane;
-        const bool narrow = a.rl > 0;
-        if (!narrow) a.S11[o] = S11;
+        if (a.rl == 0) a.S11[o] = S11;
         a.S10[o] = S10;
         a.S00[o] = S00;
         a.P0s[o] = Ps;
         if (j == 0) a.f0s[(size_t)b * R + i] = f0r;
-        if (a.A_out) {
-            double inv = S00;
-            (void)G.sweep_inverse(inv);
-            G.sync();
-            L0[TS * i + j] = S10;
-            L1[TS * i + j] = inv;
-            G.sync();
-            const double An = dot_rows<R>(L0, L1, i, j);
-            G.sync();
-            L1[TS * i + j] = An;
-            G.sync();
-            double Qn = (S11 - dot_rows<R>(L1, L0, i, j)) / (double)T;
-            Qn = 0.5 * (Qn + G.transposed(Qn));
-            const double P0n = 0.5 * (Ps + G.transposed(Ps));
-            double inv2 = S11;
-            if (narrow) {
-                if (!inL) inv2 = (i == j) ? (double)T : 0.0;
-                if (inC) a.S11[(size_t)b * Rc * Rc + i * Rc + j] = inv2;
-            }
-            (void)G.sweep_inverse(inv2);
-            if (narrow) { if (inC) a.S11inv[(size_t)b * Rc * Rc + i * Rc + j] = inv2; }
-            else a.S11inv[o] = inv2;
-            if (em_apply) {
-                a.A_out[o] = An;
-                a.Q_out[o] = Qn;
-                a.P0_out[o] = P0n;
-                if (j == 0) a.mu0_out[(size_t)b * R + i] = f0r;
-            }
-        }
+        if (a.A_out) transition_mstep_grid<R>(G, L0, L1, a, b, T, S11, S10, S00, Ps, f0r, em_apply, MstepCons{0, 0, 0, a.rl, a.Rc});
     }
 }
 

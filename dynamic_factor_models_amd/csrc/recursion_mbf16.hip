@@ -20,14 +20,15 @@
 // A is kept in both layouts, and every product of the recursion is arranged so that its left factor is symmetric, constant, or the
 // transpose of something just computed (no cross-lane transposition anywhere).  Rank-4 terms are ONE instruction (k = 4).
 // Vectors live in LDS (one wave: its DS operations are served in order, no barrier).
-// The EM epilogue (A, Q, mu0, P0, S11^-1, bookkeeping: companion constraints and all) is recursion_wave_kernel<16, COV>'s text with an
-// element per thread, as its own small launch on the sums this kernel leaves (cov_epilogue_kernel below).
+// The EM epilogue (A, Q, mu0, P0, S11^-1, bookkeeping: companion constraints and all) is dfm_em_epilogue.h's (transition_mstep_grid<16>,
+// em_decide / em_record), as its own small launch on the sums this kernel leaves (cov_epilogue_kernel below).
 // Reference counterpart: none (dfm_functions.ipynb:21-23 declares `Parametric` only); oracle: oracle/varp_oracle.py, oracle/ar_oracle.py.
 #include <stdlib.h>
 
 #include "dfm_kernels.h"
 #include "dfm_smallmat.h"
 #include "dfm_grid.h"
+#include "dfm_em_epilogue.h"
 
 namespace dfm {
 
@@ -522,9 +523,9 @@ __global__ __launch_bounds__(64) void recursion_mbf16_kernel(RecursionArgs a) {
     }
 }
 
-// ---- the EM epilogue: recursion_wave_kernel<16, COV>'s, element (i, j) of every 16 x 16 matrix per thread, on the sums the pass left ------
-// EM bookkeeping (log-likelihood path, iteration counts, who keeps iterating), A = S10 S00^-1 with the companion constraints
-// (RecursionArgs::kdim / ka / kb), Q = sym(S11 - A S10') / T, mu0, P0, S11 / S11^-1 in the loadings step's layout.
+// ---- the EM epilogue on the sums the pass left, element (i, j) of every 16 x 16 matrix per thread: the bookkeeping and the transition
+// M-step of dfm_em_epilogue.h (em_decide / em_record, transition_mstep_grid with the companion constraints RecursionArgs::kdim / ka / kb
+// and S11 / S11^-1 in the loadings step's layout).
 template <int R>
 __global__ __launch_bounds__(R * R) void cov_epilogue_kernel(RecursionArgs a) {
     constexpr int RR = R * R, TS = kTileStride<R>, RT = R * TS;
@@ -540,72 +541,21 @@ __global__ __launch_bounds__(R * R) void cov_epilogue_kernel(RecursionArgs a) {
     const int i = lane / R, j = lane % R;
     G.l = lane; G.i = i; G.j = j;
     const int T = a.T;
-    const int Rc = a.Rc > 0 ? a.Rc : R;
-    const bool inC = i < Rc && j < Rc;
-    const int rl = a.rl > 0 ? a.rl : R;
-    const bool inL = i < rl && j < rl;
     const size_t o = (size_t)b * RR + lane;
     const double ll = a.loglik[b];
     bool em_apply = true;
     if (a.active) {
-        const bool was = a.k == 0 ? true : (a.active[b] != 0);
-        bool go = was;
-        if (was && a.k >= 1 && a.tol > 0.0) {
-            const double llp = a.ll_path[(size_t)b * a.max_iter + a.k - 1];
-            go = !((ll - llp) / (0.5 * (fabs(ll) + fabs(llp))) < a.tol);
-        }
-        em_apply = go;
+        const EmDecision d = em_decide(a, b, ll);
+        em_apply = d.go;
         __syncthreads();
-        if (lane == 0) {
-            if (was) { a.ll_path[(size_t)b * a.max_iter + a.k] = ll; a.iters[b] = a.k + 1; }
-            a.active[b] = go ? 1 : 0;
-        }
+        if (lane == 0) em_record(a, b, ll, d);
     }
     const double S11 = a.ZJtab[(size_t)b * (T + 1) * kSlotE + (size_t)T * kSlotE + lane];
     const double S10 = a.S10[o], S00 = a.S00[o], Ps = a.P0s[o];
     const double fs_r = a.f0s[(size_t)b * R + i];
-    const bool narrow = a.rl > 0;
-    if (!narrow) a.S11[o] = S11;
+    if (a.rl == 0) a.S11[o] = S11;
     if (!a.A_out) return;
-    double inv = S00;
-    double S10m = S10;
-    if (a.kdim > 0 && a.ka > 0) {   // VAR(p) inside a wider state: A = S10[:, :ka] S00[:ka, :ka]^-1, zero beyond
-        if (i >= a.ka || j >= a.ka) inv = (i == j) ? 1.0 : 0.0;
-        if (j >= a.ka) S10m = 0.0;
-    }
-    (void)G.sweep_inverse(inv);
-    G.sync();
-    L0[TS * i + j] = S10m;
-    L1[TS * i + j] = inv;                                    // symmetric: rows = columns
-    G.sync();
-    const double An = dot_rows<R>(L0, L1, i, j);
-    G.sync();
-    L1[TS * i + j] = An;
-    G.sync();
-    double Qn = (S11 - dot_rows<R>(L1, L0, i, j)) / (double)T;   // (A S10')_ij = row i of A . row j of S10
-    Qn = 0.5 * (Qn + G.transposed(Qn));
-    double Aout = An;
-    if (a.kdim > 0) {   // companion state: only [A_1 .. A_p] and the innovation covariance of f_t are free
-        const int kd = a.kdim;
-        const int rb = a.kb > 0 ? a.kb : rl;               // block size of the companion state
-        if (i >= rb && i < kd) Aout = (j == i - rb) ? 1.0 : 0.0;
-        if ((i >= rb && i < kd) || (j >= rb && j < kd)) Qn = 0.0;
-    }
-    const double P0n = 0.5 * (Ps + G.transposed(Ps));
-    double inv2 = S11;
-    if (narrow) {
-        if (!inL) inv2 = (i == j) ? (double)T : 0.0;
-        if (inC) a.S11[(size_t)b * Rc * Rc + i * Rc + j] = inv2;
-    }
-    (void)G.sweep_inverse(inv2);
-    if (narrow) { if (inC) a.S11inv[(size_t)b * Rc * Rc + i * Rc + j] = inv2; }
-    else a.S11inv[o] = inv2;
-    if (em_apply) {
-        a.A_out[o] = Aout;
-        a.Q_out[o] = Qn;
-        a.P0_out[o] = P0n;
-        if (j == 0) a.mu0_out[(size_t)b * R + i] = fs_r;
-    }
+    transition_mstep_grid<R>(G, L0, L1, a, b, T, S11, S10, S00, Ps, fs_r, em_apply, MstepCons{a.kdim, a.ka, a.kb, a.rl, a.Rc});
 }
 
 template <int R>
@@ -621,7 +571,7 @@ hipError_t launch_cov_epilogue(int Rpad, const RecursionArgs& a, hipStream_t s) 
 }
 
 // Rp = 16, covariance form, observation on the first rc <= 4 state components in the collapse kernels' narrow layout (VAR(p) factor
-// dynamics: dfm_*_varp_*); the EM epilogue is recursion_wave_kernel<16, COV>'s (RecursionArgs::sums_ready)
+// dynamics: dfm_*_varp_*); the EM epilogue is cov_epilogue_kernel (RecursionArgs::sums_ready)
 bool recursion_mbf16_supported(int Rpad, const RecursionArgs& a) {
     static const bool off = [] { const char* v = diag_env("DFM_NO_MBF16"); return v && atoi(v) != 0; }();
     if (off || Rpad != 16 || !a.cov || a.kb != 0) return false;

@@ -22,6 +22,7 @@
 #include "dfm_kernels.h"
 #include "dfm_smallmat.h"
 #include "dfm_grid.h"
+#include "dfm_em_epilogue.h"
 
 namespace dfm {
 
@@ -254,19 +255,11 @@ __global__ __launch_bounds__(128, 2) void recursion_pair_kernel(RecursionArgs a)
                 a.loglik[b] = ll;
                 if (a.ncov) a.ncov[b] = e + 1;
             }
-            if (a.active) {   // EM bookkeeping, as recursion_kernel
-                const bool was = a.k == 0 ? true : (a.active[b] != 0);
-                bool go = was;
-                if (was && a.k >= 1 && a.tol > 0.0) {
-                    const double llp = a.ll_path[(size_t)b * a.max_iter + a.k - 1];
-                    go = !((ll - llp) / (0.5 * (fabs(ll) + fabs(llp))) < a.tol);
-                }
-                em_apply = go;
+            if (a.active) {   // EM bookkeeping (dfm_em_epilogue.h)
+                const EmDecision d = em_decide(a, b, ll);
+                em_apply = d.go;
                 __builtin_amdgcn_wave_barrier();
-                if (lane == 0) {
-                    if (was) { a.ll_path[(size_t)b * a.max_iter + a.k] = ll; a.iters[b] = a.k + 1; }
-                    a.active[b] = go ? 1 : 0;
-                }
+                if (lane == 0) em_record(a, b, ll, d);
             }
         }
 
@@ -392,7 +385,8 @@ __global__ __launch_bounds__(128, 2) void recursion_pair_kernel(RecursionArgs a)
             a.S00[o] = S00;
             a.P0s[o] = Ps;
             if (j == 0) a.f0s[(size_t)b * R + i] = f0r;
-            if (a.A_out) {
+            if (a.A_out) {   // the text of transition_mstep_grid (dfm_em_epilogue.h) written out: inlined from there, this kernel
+                             // spills four more SGPRs (hipcc of ROCm 7.2.0)
                 double inv = S00;
                 double S10m_ = S10;
                 if (a.kdim > 0 && a.ka > 0) {

@@ -22,13 +22,14 @@
 // lane-level NumPy model of this file that reproduces oracle/kalman_oracle.py.  Every period is a new covariance step (no
 // memoisation: at these widths a row without a missing cell is the exception).  EM: sums of P_t and U_t are accumulated in TL;
 // sum f f' terms are three more products over time (MFMA k = 4 periods) in the epilogue; the transition M-step is
-// tile_mstep_kernel (Grid<32>, the epilogue of recursion_wave_kernel on the sums this kernel leaves in the workspace).
+// tile_mstep_kernel (transition_mstep_grid<32> of dfm_em_epilogue.h on the sums this kernel leaves in the workspace).
 // The reference has no counterpart (dfm_functions.ipynb:21-23 declares `Parametric` only).
 #include <stdlib.h>
 
 #include "dfm_cov.h"
 #include "dfm_gram.h"
 #include "dfm_grid.h"
+#include "dfm_em_epilogue.h"
 #include "dfm_kernels.h"
 #include "dfm_smallmat.h"
 
@@ -512,16 +513,7 @@ __global__ __launch_bounds__(256, CH ? 2 : 1) void recursion_tile_kernel(Recursi
                 const double ll = -0.5 * (nsum * kLog2PiT + ldsum + LD + ssum + qd);
                 a.loglik[b] = ll;
                 if (a.ncov) a.ncov[b] = T;
-                if (a.active) {                                  // EM bookkeeping, as recursion_kernel
-                    const bool was = a.k == 0 ? true : (a.active[b] != 0);
-                    bool go = was;
-                    if (was && a.k >= 1 && a.tol > 0.0) {
-                        const double llp = a.ll_path[(size_t)b * a.max_iter + a.k - 1];
-                        go = !((ll - llp) / (0.5 * (fabs(ll) + fabs(llp))) < a.tol);
-                    }
-                    if (was) { a.ll_path[(size_t)b * a.max_iter + a.k] = ll; a.iters[b] = a.k + 1; }
-                    a.active[b] = go ? 1 : 0;
-                }
+                if (a.active) em_record(a, b, ll, em_decide(a, b, ll));   // EM bookkeeping (dfm_em_epilogue.h); tile_mstep_kernel reads active
             }
         }
     }
@@ -1410,16 +1402,7 @@ __global__ __launch_bounds__(256) void tile_chunk_finish_kernel(RecursionArgs a,
         const double ll = -0.5 * tot;
         a.loglik[b] = ll;
         if (a.ncov) a.ncov[b] = T;
-        if (a.active) {                                          // EM bookkeeping, as recursion_kernel
-            const bool was = a.k == 0 ? true : (a.active[b] != 0);
-            bool go = was;
-            if (was && a.k >= 1 && a.tol > 0.0) {
-                const double llp = a.ll_path[(size_t)b * a.max_iter + a.k - 1];
-                go = !((ll - llp) / (0.5 * (fabs(ll) + fabs(llp))) < a.tol);
-            }
-            if (was) { a.ll_path[(size_t)b * a.max_iter + a.k] = ll; a.iters[b] = a.k + 1; }
-            a.active[b] = go ? 1 : 0;
-        }
+        if (a.active) em_record(a, b, ll, em_decide(a, b, ll));   // EM bookkeeping (dfm_em_epilogue.h); tile_mstep_kernel reads active
     }
     if (a.S11 == nullptr) return;
     // EM sums: the chunks' parts of sum P_t and sum U_t, plus the three products over f_smooth
@@ -1446,8 +1429,8 @@ __global__ __launch_bounds__(256) void tile_chunk_finish_kernel(RecursionArgs a,
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// The transition M-step on the sums recursion_tile_kernel leaves in the workspace -- the epilogue of recursion_wave_kernel<32>
-// (element per thread, Grid<32>):  A = S10 S00^-1,  Q = sym(S11 - A S10') / T,  mu0 = f_0|T,  P0 = sym(P_0|T),  S11^-1.
+// The transition M-step on the sums recursion_tile_kernel leaves in the workspace: transition_mstep_grid (dfm_em_epilogue.h) on a
+// Grid<32>, element per thread, with no companion constraints.
 // ------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(1024, 1) void tile_mstep_kernel(RecursionArgs a) {
     constexpr int R = kRt, RR = R * R;
@@ -1463,30 +1446,10 @@ __global__ __launch_bounds__(1024, 1) void tile_mstep_kernel(RecursionArgs a) {
     G.l = lane; G.i = i; G.j = j;
     const int b = blockIdx.x;
     const size_t o = (size_t)b * RR + lane;
-    const double S11 = a.S11[o], S10 = a.S10[o], S00 = a.S00[o], Ps = a.P0s[o];
+    // (em_apply: what the pass's em_record left -- a replicate that stopped in this iteration keeps its parameters)
     const bool em_apply = a.active ? (a.active[b] != 0) : true;
-    double inv = S00;
-    (void)G.sweep_inverse(inv);
-    G.sync();
-    L0[TS * i + j] = S10;
-    L1[TS * i + j] = inv;                                      // symmetric: rows = columns
-    G.sync();
-    const double An = dot_rows<R>(L0, L1, i, j);
-    G.sync();
-    L1[TS * i + j] = An;
-    G.sync();
-    double Qn = (S11 - dot_rows<R>(L1, L0, i, j)) / (double)a.T;   // (A S10')_ij = row i of A . row j of S10
-    Qn = 0.5 * (Qn + G.transposed(Qn));
-    const double P0n = 0.5 * (Ps + G.transposed(Ps));
-    double inv2 = S11;
-    (void)G.sweep_inverse(inv2);
-    a.S11inv[o] = inv2;
-    if (em_apply) {
-        a.A_out[o] = An;
-        a.Q_out[o] = Qn;
-        a.P0_out[o] = P0n;
-        if (j == 0) a.mu0_out[(size_t)b * R + i] = a.f0s[(size_t)b * R + i];
-    }
+    transition_mstep_grid<R>(G, L0, L1, a, b, a.T, a.S11[o], a.S10[o], a.S00[o], a.P0s[o], (j == 0 && em_apply) ? a.f0s[(size_t)b * R + i] : 0.0,
+                             em_apply);
 }
 
 // ------------------------------------------------------------------------------------------------------------------

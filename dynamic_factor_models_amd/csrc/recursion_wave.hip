@@ -18,6 +18,7 @@
 #include "dfm_kernels.h"
 #include "dfm_smallmat.h"
 #include "dfm_grid.h"
+#include "dfm_em_epilogue.h"
 
 namespace dfm {
 
@@ -291,12 +292,14 @@ __global__ __launch_bounds__(R * R, (R == 16 ? DFM_WG16_WAVES : 1)) void recursi
             a.loglik[b] = ll;
             if (a.ncov) a.ncov[b] = e + 1;
         }
-        if (a.active) {   // EM bookkeeping, as recursion_kernel
+        // EM bookkeeping and, below, the transition M-step are written out here and not taken from dfm_em_epilogue.h (only em_improved
+        // is): with the shared functions inlined, recursion_wave_kernel<8, true, *> spills more SGPRs (hipcc of ROCm 7.2.0)
+        if (a.active) {
             const bool was = a.k == 0 ? true : (a.active[b] != 0);
             bool go = was;
             if (was && a.k >= 1 && a.tol > 0.0) {
                 const double llp = a.ll_path[(size_t)b * a.max_iter + a.k - 1];
-                go = !((ll - llp) / (0.5 * (fabs(ll) + fabs(llp))) < a.tol);
+                go = em_improved(ll, llp, a.tol);
             }
             em_apply = go;
             __builtin_amdgcn_wave_barrier();
@@ -430,7 +433,7 @@ __global__ __launch_bounds__(R * R, (R == 16 ? DFM_WG16_WAVES : 1)) void recursi
         a.P0s[o] = Ps;
         if (j == 0) a.f0s[(size_t)b * R + i] = fs_r;
         if (a.A_out) {
-            // A = S10 S00^-1 ;  Q = sym(S11 - A S10') / T ;  mu0 = f_0|T ;  P0 = sym(P_0|T) ;  S11^-1
+            // the text of transition_mstep_grid (dfm_em_epilogue.h), see the note at the EM bookkeeping above
             double inv = S00;
             double S10m = S10;
             if (a.kdim > 0 && a.ka > 0) {   // VAR(p) inside a wider state: A = S10[:, :ka] S00[:ka, :ka]^-1, zero beyond
