@@ -25,6 +25,7 @@ c_uint = ctypes.c_uint
 
 DFM_F_MAY_HAVE_MISSING = 1
 DFM_F_SINGULAR_Q = 2
+DFM_SV_UNIT_EFFECT = 4
 DFM_MAX_R = 32
 DFM_MULTI_F_FORCE_COMM = 1
 # dfm_multi_fetch `what` (enum in include/dfm_hip.h)
@@ -42,6 +43,8 @@ _VEM_ARGS = [c_vp, c_int, c_int, c_int, c_int, c_int] + [c_vp] * 7 + [c_int, cty
 _FC_ARGS = [c_vp, c_int, c_int, c_int, c_int, c_int, c_int] + [c_vp] * 15 + [c_uint]
 _SS_ARGS = [c_vp] + [c_int] * 7 + [c_vp] * 9 + [ctypes.c_uint64, ctypes.c_int64, c_vp, c_vp, c_uint]
 _NW_ARGS = [c_vp] + [c_int] * 5 + [c_vp] * 10 + [c_int] + [c_vp] * 6 + [c_uint]
+_IRF_ARGS = [c_vp] + [c_int] * 5 + [c_vp] * 9 + [c_uint]
+_HD_ARGS = [c_vp] + [c_int] * 5 + [c_vp] * 13 + [c_uint]
 _ARPASS_ARGS = [c_vp, c_int, c_int, c_int, c_int, c_int, c_int] + [c_vp] * 11 + [c_uint]
 _AREM_ARGS = [c_vp, c_int, c_int, c_int, c_int, c_int, c_int] + [c_vp] * 8 + [c_int, ctypes.c_double] + [c_vp] * 4 + [c_uint]
 _MFPASS_ARGS = [c_vp, c_int, c_int, c_int, c_int, c_int, c_int] + [c_vp] * 11 + [c_uint]
@@ -98,6 +101,10 @@ SYMBOLS = {
     "dfm_simsmooth_batch": (c_int, _SS_ARGS),
     "dfm_news_batch_dev": (c_int, _NW_ARGS),
     "dfm_news_batch": (c_int, _NW_ARGS),
+    "dfm_irf_batch_dev": (c_int, _IRF_ARGS),
+    "dfm_irf_batch": (c_int, _IRF_ARGS),
+    "dfm_histdecomp_batch_dev": (c_int, _HD_ARGS),
+    "dfm_histdecomp_batch": (c_int, _HD_ARGS),
     "dfm_ks_pass_ar_batch_dev": (c_int, _ARPASS_ARGS),
     "dfm_ks_pass_ar_batch": (c_int, _ARPASS_ARGS),
     "dfm_em_ar_batch_dev": (c_int, _AREM_ARGS),

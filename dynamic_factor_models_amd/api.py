@@ -494,6 +494,144 @@ def forecast(m: DFMModel, H: int, *, through: Optional[int] = None, quantiles=No
     return out
 
 
+# ----------------------------------------------------------------------------- structural analysis of the parametric fit
+def _structural_checks(m: DFMModel):
+    if m.em_params is None:
+        raise ValueError("the model has not been estimated: run estimate(m, Parametric()) first")
+    if m.nfac_o != 0:
+        raise ValueError("structural analysis needs nfac_o = 0")
+
+
+def _to_cols(idx, cols, what):
+    """Column indices of m.data as positions in `cols`; a series estimate() dropped is named in the error."""
+    out = []
+    for i in np.atleast_1d(np.asarray(idx, dtype=np.int64)):
+        at = np.nonzero(cols == i)[0]
+        if at.size != 1:
+            raise ValueError(f"{what}: series {int(i)} is not among the series estimate() used")
+        out.append(int(at[0]))
+    return np.asarray(out, dtype=np.int32)
+
+
+def _numeric_retry(call):
+    """As forecast: the information form inverts Q, so a numeric failure is retried once in covariance form."""
+    from ._lib import DfmError
+    try:
+        return call(False)
+    except DfmError as err:
+        if err.code != -5:
+            raise
+        return call(True)
+
+
+def structural_irf(m: DFMModel, H: int, *, named=None, cumulate=None, unit_effect: bool = False, fevd: bool = True,
+                   quantiles=None, ctx=None) -> dict:
+    """Identified impulse responses and forecast-error variance decompositions of every series of the panel from the parametric
+    fit (`estimate(m, Parametric())`, nfac_o = 0); definitions in include/dfm_hip.h (dfm_irf_batch).
+
+    `named`: r distinct column indices of m.data: factor k is the common component of series named[k], and their order is the
+    recursive (Cholesky) ordering; None: S = chol(Q) in the fit's own rotation.  `cumulate`: column indices of the series that
+    entered in differences; their responses are cumulated.  `unit_effect` (needs named): shock k moves series named[k] by one
+    data unit on impact.  Returns a dict:
+      cols        column indices of m.data: the series estimate() used
+      irf         [len(cols), H, r] in data units (series, horizon, shock: the reference's impulse_response order)
+      fevd        [len(cols), H, r + 1] shares of the forecast-error variance, the last slot idiosyncratic (None if not asked for)
+    `quantiles` (needs m.replicates and named: replicates are not in a common rotation otherwise): every replicate runs in ONE
+    batched call, dfm_quantile_bands gives bands [nq, len(cols), H, r].  AR-idiosyncratic and mixed-frequency fits are out of
+    scope.  `m` is not modified."""
+    H = int(H)
+    if H < 1:
+        raise ValueError("H must be >= 1")
+    _structural_checks(m)
+    if unit_effect and named is None:
+        raise ValueError("unit_effect needs named series")
+    qs = None
+    if quantiles is not None:
+        if named is None:
+            raise ValueError("quantile bands need named series: the replicates are not in a common rotation otherwise")
+        if getattr(m, "replicates", None) is None:
+            raise ValueError("quantile bands need bootstrap replicates: estimate(m, Parametric(), nrep=...) first")
+        qs = np.atleast_1d(np.asarray(quantiles, dtype=np.float64))
+        if qs.size < 1 or not np.all((qs > 0.0) & (qs <= 1.0)):
+            raise ValueError("quantiles must lie in (0, 1]")
+    ep = m.em_params
+    Lam, R, Q = ep["Lam"], ep["R"], ep["Q"]
+    A = ep["Avar"] if "Avar" in ep else ep["A"]
+    N, r = Lam.shape
+    cols, _, _, sd = _forecast_inputs(m, m.lastperiod)
+    if N != cols.size:
+        raise ValueError("m.em_params does not match the model's series (was the model changed after estimate?)")
+    nm = None if named is None else _to_cols(named, cols, "named")
+    if nm is not None and (nm.size != r or np.unique(nm).size != r):
+        raise ValueError(f"named must be {r} distinct series")
+    cum = None
+    if cumulate is not None:
+        cum = np.zeros(N, dtype=np.int32)
+        cum[_to_cols(cumulate, cols, "cumulate")] = 1
+    ctx, own = _own(ctx)
+    try:
+        def run(Lb, Ab, Qb, Rb, want_fevd):
+            B = Lb.shape[0]
+            sdb = np.ascontiguousarray(np.broadcast_to(sd, (B, N)))
+            return ctx.irf_batch_host(Lb, Ab, Qb, Rb, H, sd=sdb, named=nm, cum=cum, unit_effect=unit_effect, want_fevd=want_fevd)
+        o = run(Lam[None], A[None], Q[None], R[None], fevd)
+        bands = None
+        if qs is not None:
+            rp = m.replicates["params"]
+            ob = run(rp["Lam"], rp["A"], rp["Q"], rp["R"], False)
+            bands = ctx.quantile_bands_host(ob["irf"].reshape(ob["irf"].shape[0], -1), qs).reshape(qs.size, r, H, N)
+    finally:
+        if own:
+            ctx.close()
+    out = dict(cols=cols, irf=np.ascontiguousarray(o["irf"][0].transpose(2, 1, 0)),
+               fevd=None if o["fevd"] is None else np.ascontiguousarray(o["fevd"][0].transpose(2, 1, 0)))
+    if bands is not None:
+        out["quantiles"] = qs
+        out["bands"] = np.ascontiguousarray(bands.transpose(0, 3, 2, 1))
+    return out
+
+
+def historical_decomposition(m: DFMModel, *, named=None, through: Optional[int] = None, ctx=None) -> dict:
+    """Which shocks drove every series through the sample: the contribution of each identified factor shock and of the initial
+    condition to the common component of every cell, from the parametric fit (`estimate(m, Parametric())`, nfac_o = 0);
+    definitions in include/dfm_hip.h (dfm_histdecomp_batch).  Window, series, standardisation and `through` as `forecast`;
+    `named` as `structural_irf`.  Q must be positive definite: a numeric failure is retried once in covariance form and then
+    reported.  Returns a dict:
+      rows           1-based periods initperiod .. through
+      cols           column indices of m.data: the series estimate() used
+      contributions  [rows, cols, r + 1] in data units without the mean (the last slot is the initial condition); the slots sum
+                     to sd_i lam_i' E[f_t | X]
+      shocks         [rows, r] the unit-variance structural shocks (zero in the first factor_lags rows)
+      factor         [rows, r] E[f_t | X]
+      loglik         log-likelihood of the observed cells
+    AR-idiosyncratic and mixed-frequency fits are out of scope.  `m` is not modified."""
+    _structural_checks(m)
+    through = m.lastperiod if through is None else int(through)
+    if not (m.lastperiod <= through <= m.T):
+        raise ValueError(f"through must lie in lastperiod..T ({m.lastperiod}..{m.T})")
+    ep = m.em_params
+    Lam, R, Q = ep["Lam"], ep["R"], ep["Q"]
+    A = ep["Avar"] if "Avar" in ep else ep["A"]
+    r = Lam.shape[1]
+    cols, z, _, sd = _forecast_inputs(m, through)
+    if Lam.shape[0] != cols.size:
+        raise ValueError("m.em_params does not match the model's series (was the model changed after estimate?)")
+    nm = None if named is None else _to_cols(named, cols, "named")
+    if nm is not None and (nm.size != r or np.unique(nm).size != r):
+        raise ValueError(f"named must be {r} distinct series")
+    ctx, own = _own(ctx)
+    try:
+        o = _numeric_retry(lambda sq: ctx.histdecomp_batch_host(
+            z[None], Lam[None], R[None], A[None], Q[None], ep["mu0"][None], ep["P0"][None], sd=sd[None], named=nm,
+            may_have_missing=bool(np.isnan(z).any()), singular_q=sq))
+    finally:
+        if own:
+            ctx.close()
+    return dict(rows=np.arange(m.initperiod, through + 1), cols=cols,
+                contributions=np.ascontiguousarray(o["hd"][0].transpose(1, 2, 0)), shocks=o["shocks"][0], factor=o["f"][0],
+                loglik=float(o["loglik"][0]))
+
+
 def draw_paths(m: DFMModel, ndraws: int, H: int = 0, *, through: Optional[int] = None, seed: int = 20160415,
                first_draw: int = 0, parameter_draws: bool = False, ctx=None) -> dict:
     """Joint posterior draws of the factor path and of the panel's missing and future cells from the parametric fit

@@ -155,6 +155,9 @@ struct dfm_handle {
                                            // (no x_draw) difference panels -- beside h->ws for the same reason
     DevBlock nw;                           // dfm_news_batch_dev: targets, the revised old panel, one forecast's xhat, the slice's pass
                                            // parameters, u / a vectors, smoothed means and (no weight) covariance panels
+    DevBlock sv;                           // dfm_irf_batch_dev / dfm_histdecomp_batch_dev: named / cum, S, S^-1, the Theta tables, shocks and
+                                           // contribution paths, and the pass outputs the caller does not take
+    std::vector<int> sv_idx;               // host copy of named / cum while their upload is in flight
     const double* odd_panel_src = nullptr; int odd_panel_dims[3] = {0, 0, 0};   // the panel whose padded copy h->odd holds (odd_pad keep_panel)
     std::string prof_file;                 // DFM_PF_PROF_FILE with DFM_SCAN_ABL=256: phase stamps of the fused pass
     char err[512] = {0};
@@ -166,11 +169,11 @@ struct dfm_handle {
 };
 
 enum KernelId { K_COLLAPSE = 0, K_RECURSION, K_MSTEP_STATS, K_MSTEP_SOLVE, K_PCA, K_SYNTH, K_PAD,
-                K_COLLAPSE_DMA, K_GRAM, K_COV, K_MEANSCAN, K_PFILL, K_COLLAPSE_MFMA, K_ALS, K_OLS, K_BOOT, K_QUANT, K_COLLAPSE_WIDE, K_EM_UPDATE, K_CHOW, K_MSTEP_MFMA, K_GRAM_XX, K_PASS_FUSED, K_FC_TAIL, K_FC_FILL, K_FC_PAD, K_SS_PREP, K_SS_EXPAND, K_SS_PATH, K_SS_DIFF, K_SS_FINISH, K_SS_FILL, K_NW_REVISE, K_NW_GATHER, K_NW_GAMMA, K_NW_COV, K_NW_IMPACT, K_MF_TABLE, K_MF_MOMENTS, K_MF_SOLVE, K_COUNT };
+                K_COLLAPSE_DMA, K_GRAM, K_COV, K_MEANSCAN, K_PFILL, K_COLLAPSE_MFMA, K_ALS, K_OLS, K_BOOT, K_QUANT, K_COLLAPSE_WIDE, K_EM_UPDATE, K_CHOW, K_MSTEP_MFMA, K_GRAM_XX, K_PASS_FUSED, K_FC_TAIL, K_FC_FILL, K_FC_PAD, K_SS_PREP, K_SS_EXPAND, K_SS_PATH, K_SS_DIFF, K_SS_FINISH, K_SS_FILL, K_NW_REVISE, K_NW_GATHER, K_NW_GAMMA, K_NW_COV, K_NW_IMPACT, K_MF_TABLE, K_MF_MOMENTS, K_MF_SOLVE, K_SV_PREP, K_SV_IRF_FILL, K_SV_SHOCK, K_SV_PATH, K_SV_HD_FILL, K_COUNT };
 static const char* const kKernelNames[K_COUNT] = {"collapse_kernel", "recursion_kernel", "mstep_lam_kernel",
                                                   "mstep_solve_kernel", "pca_kernel", "synth_kernel",
                                                   "pad_params_kernel", "collapse_dma_kernel", "gram_kernel",
-                                                  "cov_kernel", "meanscan_kernel", "pfill_kernel", "collapse_mfma_kernel", "als_kernel", "ols_kernel", "var_boot_kernel", "quantile_kernel", "collapse_wide_kernel", "em_update_kernel", "chow_kernel", "mstep_mfma_kernel", "gram_xx_kernel", "pass_fused_kernel", "forecast_tail_kernel", "forecast_fill_kernel", "forecast_pad_kernel", "simsmooth_prep_kernel", "simsmooth_expand_kernel", "simsmooth_path_kernel", "simsmooth_diff_kernel", "simsmooth_finish_kernel", "simsmooth_fill_kernel", "news_revise_kernel", "news_gather_kernel", "news_gamma_kernel", "news_cov_panel_kernel", "news_impact_kernel", "mf_table_kernel", "mf_moments_kernel", "mf_solve_kernel"};
+                                                  "cov_kernel", "meanscan_kernel", "pfill_kernel", "collapse_mfma_kernel", "als_kernel", "ols_kernel", "var_boot_kernel", "quantile_kernel", "collapse_wide_kernel", "em_update_kernel", "chow_kernel", "mstep_mfma_kernel", "gram_xx_kernel", "pass_fused_kernel", "forecast_tail_kernel", "forecast_fill_kernel", "forecast_pad_kernel", "simsmooth_prep_kernel", "simsmooth_expand_kernel", "simsmooth_path_kernel", "simsmooth_diff_kernel", "simsmooth_finish_kernel", "simsmooth_fill_kernel", "news_revise_kernel", "news_gather_kernel", "news_gamma_kernel", "news_cov_panel_kernel", "news_impact_kernel", "mf_table_kernel", "mf_moments_kernel", "mf_solve_kernel", "sv_prep_kernel", "sv_irf_fill_kernel", "sv_shock_kernel", "sv_path_kernel", "sv_hd_fill_kernel"};
 
 namespace dfm { int handle_device(const dfm_handle* h) { return h->device; } }   // (probe.hip)
 
@@ -1675,7 +1678,7 @@ int dfm_destroy(dfm_handle* h) {
     for (auto e : h->ev_sub) hipEventDestroy(e);
     if (h->ev_fork) hipEventDestroy(h->ev_fork);
     if (h->ev_join) hipEventDestroy(h->ev_join);
-    for (DevBlock* b : {&h->ws, &h->odd, &h->fc, &h->ss, &h->nw}) b->release();
+    for (DevBlock* b : {&h->ws, &h->odd, &h->fc, &h->ss, &h->nw, &h->sv}) b->release();
     if (h->status_dev) hipFree(h->status_dev);
     if (h->own_stream && h->stream) hipStreamDestroy(h->stream);
     delete h;
@@ -1833,7 +1836,8 @@ int dfm_ks_pass_batch_dev(dfm_handle* h, int B, int T, int N, int r, const doubl
 // The status word of the last call's plan, read after the stream has been synchronised.  Bits: 1 = NaN in a panel that was
 // declared balanced, 2 = the PCA start's subspace iteration did not converge, 4 = a bounded wait between the waves of the
 // one-launch pass ran out (its outputs are invalid even where the log-likelihood happens to be finite), 8 = dfm_news_batch: a cell
-// of the old vintage is observed where the new one is missing.  Every synchronising
+// of the old vintage is observed where the new one is missing, 16 = dfm_irf_batch / dfm_histdecomp_batch: a zero pivot in
+// Lam[named, :] or (decomposition) in the root of Q.  Every synchronising
 // entry point goes through here; device-pointer callers get the same check from dfm_synchronize / dfm_check_status.
 static int status_check(dfm_handle* h) {
     if (!h->status_dev) return 0;
@@ -1843,6 +1847,7 @@ static int status_check(dfm_handle* h) {
     if (st & 4) return fail(h, DFM_E_NUMERIC, "one-launch pass: a bounded wait between its waves ran out (results invalid)%s");
     if (st & 8) return fail(h, DFM_E_VINTAGE, "news: a cell observed in the old vintage is missing in the new one%s");
     if (st & 1) return fail(h, DFM_E_MISSING, "panel contains NaN but DFM_F_MAY_HAVE_MISSING was not set%s");
+    if (st & 16) return fail(h, DFM_E_NUMERIC, "structural identification: Lam[named, :] is singular, or Q is not positive definite where S^-1 is needed%s");
     if (st & 2) return fail(h, DFM_E_NUMERIC, "PCA subspace iteration did not converge (near-degenerate spectrum at the cut)%s");
     return 0;
 }
@@ -2609,6 +2614,160 @@ int dfm_simsmooth_batch(dfm_handle* h, int B, int D, int T, int N, int r, int p,
     return rc;
 }
 
+
+// ---- structural IRFs, variance and historical decompositions (structural.hip) ------------------------------------------------
+// Sizes first (they are decided before the handle is looked at), then the handle and the required pointers.
+static int sv_check(dfm_handle* h, int B, int T, int N, int r, int p, const int* named, unsigned flags) {
+    if (B < 1 || T < 1 || N < 1 || r < 1) return fail(h, DFM_E_DIMS, "B, T, N, r must be >= 1%s");
+    if (p < 1) return fail(h, DFM_E_DIMS, "number of factor lags must be >= 1%s");
+    if (r > DFM_MAX_R || (long long)r * p > DFM_MAX_R) return fail(h, DFM_E_R_UNSUPPORTED, "r * p > DFM_MAX_R (32)%s");
+    if (named)
+        for (int a = 0; a < r; ++a) {
+            if (named[a] < 0 || named[a] >= N) return fail(h, DFM_E_DIMS, "a named series lies outside [0, N)%s");
+            for (int c = 0; c < a; ++c)
+                if (named[c] == named[a]) return fail(h, DFM_E_DIMS, "a named series is repeated%s");
+        }
+    if (!h) return DFM_E_NULL;
+    if ((flags & DFM_SV_UNIT_EFFECT) && !named) return fail(h, DFM_E_NULL, "DFM_SV_UNIT_EFFECT needs named series%s");
+    return 0;
+}
+
+// named [r] and cum [N] as device ints at the start of h->sv (offsets o_named, o_cum; (size_t)-1: not given)
+static int sv_upload_idx(dfm_handle* h, int r, int N, const int* named, const int* cum, size_t o_named, size_t o_cum) {
+    h->sv_idx.clear();
+    if (named) h->sv_idx.insert(h->sv_idx.end(), named, named + r);
+    if (cum) h->sv_idx.insert(h->sv_idx.end(), cum, cum + N);
+    const int* src = h->sv_idx.data();
+    if (named) HIP_TRY(h, hipMemcpyAsync(at<int>(h->sv, o_named), src, (size_t)r * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    if (cum) HIP_TRY(h, hipMemcpyAsync(at<int>(h->sv, o_cum), src + (named ? r : 0), (size_t)N * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    return 0;
+}
+
+int dfm_irf_batch_dev(dfm_handle* h, int B, int N, int r, int p, int H, const double* Lam, const double* Avar, const double* Q,
+                      const double* R, const double* sd, const int* named, const int* cum, double* irf, double* fevd,
+                      unsigned flags) {
+    if (H < 1) return fail(h, DFM_E_DIMS, "H must be >= 1%s");
+    if (int rc = sv_check(h, B, 1, N, r, p, named, flags)) return rc;
+    if (!Lam || !Avar || !Q || !irf || (fevd && !R)) return fail(h, DFM_E_NULL, "required pointer is NULL%s");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t d = sizeof(double), rr = (size_t)r * r;
+    bool any_cum = false;
+    if (cum)
+        for (int i = 0; i < N; ++i) any_cum = any_cum || cum[i] != 0;
+    if (!any_cum) cum = nullptr;
+    size_t off = 0;
+    const size_t o_named = named ? take(off, (size_t)r * sizeof(int)) : (size_t)-1, o_cum = cum ? take(off, (size_t)N * sizeof(int)) : (size_t)-1,
+                 o_S = take(off, B * rr * d), o_sc = (flags & DFM_SV_UNIT_EFFECT) ? take(off, (size_t)B * r * d) : (size_t)-1,
+                 o_Th = take(off, (size_t)B * H * rr * d), o_Thc = cum ? take(off, (size_t)B * H * rr * d) : (size_t)-1;
+    HIP_TRY(h, h->sv.grow(off));
+    if (int rc = sv_upload_idx(h, r, N, named, cum, o_named, o_cum)) return rc;
+    SvArgs a{};
+    a.B = B; a.N = N; a.r = r; a.p = p; a.H = H; a.T = 0;
+    a.Lam = Lam; a.R = fevd ? R : nullptr; a.A = Avar; a.Q = Q; a.sd = sd;
+    a.named = at<int>(h->sv, o_named); a.cum = at<int>(h->sv, o_cum);
+    a.status = h->status_dev;
+    a.S = at<double>(h->sv, o_S); a.scale = at<double>(h->sv, o_sc); a.Th = at<double>(h->sv, o_Th); a.Thc = at<double>(h->sv, o_Thc);
+    a.irf = irf; a.fevd = fevd;
+    {
+        ProfScope ps(h, K_SV_PREP);
+        HIP_TRY(h, launch_sv_prep(a, h->stream));
+    }
+    ProfScope ps(h, K_SV_IRF_FILL);
+    HIP_TRY(h, launch_sv_irf_fill(a, h->stream));
+    return 0;
+}
+
+int dfm_irf_batch(dfm_handle* h, int B, int N, int r, int p, int H, const double* Lam, const double* Avar, const double* Q,
+                  const double* R, const double* sd, const int* named, const int* cum, double* irf, double* fevd,
+                  unsigned flags) {
+    if (H < 1) return fail(h, DFM_E_DIMS, "H must be >= 1%s");
+    if (int rc = sv_check(h, B, 1, N, r, p, named, flags)) return rc;
+    if (!Lam || !Avar || !Q || !irf || (fevd && !R)) return fail(h, DFM_E_NULL, "required pointer is NULL%s");
+    if (int rc = status_epoch(h)) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t n_R = (size_t)B * N, n_o = (size_t)B * H * N;
+    HostStage st(h, 256);
+    double *lam_d, *A_d, *Q_d, *R_d, *sd_d, *irf_d, *fv_d;
+    st.in(Lam, n_R * r, lam_d); st.in(Avar, (size_t)B * r * r * p, A_d); st.in(Q, (size_t)B * r * r, Q_d);
+    st.in(R, R ? n_R : 0, R_d); st.in(sd, sd ? n_R : 0, sd_d);
+    st.out(irf, n_o * r, irf_d); st.out(fevd, fevd ? n_o * (r + 1) : 0, fv_d);
+    if (int rc = st.begin()) return rc;
+    int rc = st.finish(dfm_irf_batch_dev(h, B, N, r, p, H, lam_d, A_d, Q_d, R_d, sd_d, named, cum, irf_d, fv_d, flags));
+    if (rc == 0) rc = status_check(h);
+    return rc;
+}
+
+int dfm_histdecomp_batch_dev(dfm_handle* h, int B, int T, int N, int r, int p, const double* panel, const double* Lam,
+                             const double* R, const double* Avar, const double* Q, const double* mu0, const double* P0,
+                             const double* sd, const int* named, double* hd, double* shocks, double* f_out, double* loglik,
+                             unsigned flags) {
+    if (T < p + 1) return fail(h, DFM_E_DIMS, "T must be >= p + 1%s");
+    if (int rc = sv_check(h, B, T, N, r, p, named, 0)) return rc;
+    if (!panel || !Lam || !R || !Avar || !Q || !mu0 || !P0 || !hd) return fail(h, DFM_E_NULL, "required pointer is NULL%s");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t d = sizeof(double), rr = (size_t)r * r, n_f = (size_t)B * T * r;
+    size_t off = 0;
+    const size_t o_named = named ? take(off, (size_t)r * sizeof(int)) : (size_t)-1, o_S = take(off, B * rr * d), o_Si = take(off, B * rr * d),
+                 o_f = f_out ? (size_t)-1 : take(off, n_f * d), o_ll = loglik ? (size_t)-1 : take(off, (size_t)B * d),
+                 o_u = shocks ? (size_t)-1 : take(off, n_f * d), o_C = take(off, n_f * (r + 1) * d);
+    HIP_TRY(h, h->sv.grow(off));
+    if (int rc = sv_upload_idx(h, r, N, named, nullptr, o_named, (size_t)-1)) return rc;
+    double* f = f_out ? f_out : at<double>(h->sv, o_f);
+    double* ll = loglik ? loglik : at<double>(h->sv, o_ll);
+    const unsigned pass_flags = flags & (DFM_F_MAY_HAVE_MISSING | DFM_F_SINGULAR_Q);
+    if (p == 1) {
+        if (int rc = dfm_ks_pass_batch_dev(h, B, T, N, r, panel, Lam, R, Avar, Q, mu0, P0, f, nullptr, ll, pass_flags)) return rc;
+    } else {
+        if (int rc = dfm_ks_pass_varp_batch_dev(h, B, T, N, r, p, panel, Lam, R, Avar, Q, mu0, P0, f, nullptr, ll, pass_flags)) return rc;
+    }
+    SvArgs a{};
+    a.B = B; a.N = N; a.r = r; a.p = p; a.H = 0; a.T = T;
+    a.Lam = Lam; a.A = Avar; a.Q = Q; a.sd = sd;
+    a.named = at<int>(h->sv, o_named);
+    a.need_pd = 1; a.status = h->status_dev;
+    a.S = at<double>(h->sv, o_S); a.Sinv = at<double>(h->sv, o_Si);
+    a.f = f; a.u = shocks ? shocks : at<double>(h->sv, o_u); a.C = at<double>(h->sv, o_C); a.hd = hd;
+    {
+        ProfScope ps(h, K_SV_PREP);
+        HIP_TRY(h, launch_sv_prep(a, h->stream));
+    }
+    {
+        ProfScope ps(h, K_SV_SHOCK);
+        HIP_TRY(h, launch_sv_shock(a, h->stream));
+    }
+    {
+        ProfScope ps(h, K_SV_PATH);
+        HIP_TRY(h, launch_sv_path(a, h->stream));
+    }
+    ProfScope ps(h, K_SV_HD_FILL);
+    HIP_TRY(h, launch_sv_hd_fill(a, h->stream));
+    return 0;
+}
+
+int dfm_histdecomp_batch(dfm_handle* h, int B, int T, int N, int r, int p, const double* panel, const double* Lam,
+                         const double* R, const double* Avar, const double* Q, const double* mu0, const double* P0,
+                         const double* sd, const int* named, double* hd, double* shocks, double* f_out, double* loglik,
+                         unsigned flags) {
+    if (T < p + 1) return fail(h, DFM_E_DIMS, "T must be >= p + 1%s");
+    if (int rc = sv_check(h, B, T, N, r, p, named, 0)) return rc;
+    if (!panel || !Lam || !R || !Avar || !Q || !mu0 || !P0 || !hd) return fail(h, DFM_E_NULL, "required pointer is NULL%s");
+    if (int rc = status_epoch(h)) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t k = (size_t)r * p, n_R = (size_t)B * N, n_f = (size_t)B * T * r;
+    std::vector<double> ll_host((size_t)B);                     // (checked before the caller's loglik, which is optional, is written)
+    HostStage st(h, 256);
+    double *x_d, *lam_d, *R_d, *A_d, *Q_d, *mu_d, *P0_d, *sd_d, *hd_d, *u_d, *f_d, *ll_d;
+    st.in(panel, (size_t)B * T * N, x_d); st.in(Lam, n_R * r, lam_d); st.in(R, n_R, R_d); st.in(Avar, (size_t)B * r * k, A_d);
+    st.in(Q, (size_t)B * r * r, Q_d); st.in(mu0, (size_t)B * k, mu_d); st.in(P0, (size_t)B * k * k, P0_d); st.in(sd, sd ? n_R : 0, sd_d);
+    st.out(hd, (size_t)B * (r + 1) * T * N, hd_d); st.out(shocks, shocks ? n_f : 0, u_d); st.out(f_out, f_out ? n_f : 0, f_d);
+    st.out(ll_host.data(), (size_t)B, ll_d);
+    if (int rc = st.begin()) return rc;
+    int rc = st.finish(dfm_histdecomp_batch_dev(h, B, T, N, r, p, x_d, lam_d, R_d, A_d, Q_d, mu_d, P0_d, sd_d, named, hd_d, u_d, f_d, ll_d,
+                                                flags));
+    if (rc == 0) rc = post_check(h, ll_host.data(), B);
+    if (rc == 0 && loglik) memcpy(loglik, ll_host.data(), (size_t)B * sizeof(double));
+    return rc;
+}
 
 // ---- news decomposition of nowcast revisions (news.hip) --------------------------------------------------------------------
 // The three conditional means run through dfm_forecast_batch_dev unchanged (old, new, then the revised old panel, whose xhat stays

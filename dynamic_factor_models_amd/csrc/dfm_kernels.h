@@ -547,6 +547,32 @@ hipError_t launch_news_gamma(const NwArgs& a, hipStream_t s);
 hipError_t launch_news_cov_panel(NwArgs a, hipStream_t s);
 hipError_t launch_news_impact(NwArgs a, hipStream_t s);
 
+// Structural analysis of the factor VAR: identified impulse responses, variance and historical decompositions (structural.hip).
+struct SvArgs {
+    int B, N, r, p, H, T;
+    const double* Lam; const double* R;           // [B][N][r], [B][N] (R null: no fevd)
+    const double* A; const double* Q;             // [B][r][r p] = [A_1 .. A_p], [B][r][r]
+    const double* sd;                             // [B][N] or null
+    const int* named;                             // device [r] distinct series, or null (S = chol Q)
+    const int* cum;                               // device [N], non-zero = cumulated outputs, or null
+    int unit_effect, need_pd;                     // need_pd: a zero column of the root raises status bit 16 (S^-1 is wanted)
+    int* status;                                  // bit 16: Ln singular, or (need_pd) the root has a zero pivot
+    double* S; double* Sinv;                      // [B][r][r] eta = S u; Sinv = S^-1 (null: not wanted)
+    double* scale;                                // [B][r] impact response of series named[k] to shock k in output units, or null
+    double* Th; double* Thc;                      // [B][H][r][r] shock-major: Th[h][k][m] = (Theta_h)_mk; Thc cumulated (null: no cum)
+    double* irf; double* fevd;                    // [B][r][H][N], [B][r+1][H][N] or null
+    const double* f;                              // [B][T][r] smoothed factors
+    double* u;                                    // [B][T][r] structural shocks, zero rows for t < p
+    double* C;                                    // [B][r+1][T][r] contribution paths, slot r = the initial condition
+    double* hd;                                   // [B][r+1][T][N]
+    int NPB, G, RC, nchunk, nsblk, CP, TC;        // geometry (set by the launchers)
+};
+hipError_t launch_sv_prep(const SvArgs& a, hipStream_t s);
+hipError_t launch_sv_irf_fill(SvArgs a, hipStream_t s);
+hipError_t launch_sv_shock(const SvArgs& a, hipStream_t s);
+hipError_t launch_sv_path(SvArgs a, hipStream_t s);
+hipError_t launch_sv_hd_fill(SvArgs a, hipStream_t s);
+
 // Device-side synthetic replicates (synth.hip); all arrays in the caller's layout (r).
 struct SynthArgs {
     int B, T, N, r;

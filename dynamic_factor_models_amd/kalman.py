@@ -859,3 +859,6 @@ class DfmContext:
         rc = self._lib.dfm_standardize_batch_dev(self._h, B, T, N, be.ptr(panel, "panel"), be.ptr(mu, "mean"), be.ptr(sd, "sd"))
         _check(self._h, rc)
         return mu, sd
+
+
+from . import structural  # noqa: E402,F401  (attaches the structural entries to DfmContext)

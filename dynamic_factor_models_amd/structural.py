@@ -1,0 +1,100 @@
+"""Binding of the structural entries of include/dfm_hip.h (csrc/structural.hip): dfm_irf_batch[_dev] and
+dfm_histdecomp_batch[_dev].  The functions take a DfmContext; importing this module (kalman.py does) also attaches them to
+DfmContext as irf_batch, irf_batch_host, histdecomp_batch and histdecomp_batch_host, with the marshalling conventions of
+forecast_batch(_host): device tensors in and out on torch's current stream, or NumPy through the host-pointer entries.
+"""
+from __future__ import annotations
+
+from typing import Optional
+
+import numpy as np
+
+from . import _lib
+from . import kalman as _k
+
+
+def _index(idx, n, what, distinct):
+    """A host int32 array of series indices (None stays None)."""
+    if idx is None:
+        return None
+    a = np.ascontiguousarray(np.asarray(idx, dtype=np.int64).reshape(-1))
+    if a.size != n:
+        raise ValueError(f"{what} must have {n} entries")
+    if distinct and (np.any(a < 0) or np.unique(a).size != a.size):
+        raise ValueError(f"{what} must be distinct, non-negative series indices")
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def _irf(ctx, be, Lam, Avar, Q, R, H, sd, named, cum, unit_effect, want_fevd):
+    Lam, Avar, Q = be.inp(Lam), be.inp(Avar), be.inp(Q)
+    B, N, r = Lam.shape
+    p = Avar.shape[2] // r
+    if int(H) < 1:
+        raise ValueError("H must be >= 1")
+    if unit_effect and named is None:
+        raise ValueError("unit_effect needs named series")
+    if want_fevd and R is None:
+        raise ValueError("the variance decomposition needs R")
+    R = None if R is None else be.inp(R)
+    sd = None if sd is None else be.inp(sd)
+    named = _index(named, r, "named", True)
+    cum = _index(cum, N, "cum", False)
+    irf = be.out(B, r, int(H), N)
+    fevd = be.out(B, r + 1, int(H), N) if want_fevd else None
+    be.sync()
+    rc = getattr(ctx._lib, "dfm_irf_batch" + be.suffix)(
+        ctx._h, B, N, r, p, int(H), be.ptr(Lam, "Lam", (B, N, r)), be.ptr(Avar, "Avar", (B, r, r * p)), be.ptr(Q, "Q", (B, r, r)),
+        be.ptr(R, "R", (B, N)), be.ptr(sd, "sd", (B, N)), _k._ptr(named), _k._ptr(cum), be.ptr(irf, "irf"), be.ptr(fevd, "fevd"),
+        _lib.DFM_SV_UNIT_EFFECT if unit_effect else 0)
+    _k._check(ctx._h, rc)
+    return dict(irf=irf, fevd=fevd)
+
+
+def _histdecomp(ctx, be, panel, params, sd, named, want_shocks, may_have_missing, singular_q):
+    panel, params, dims, _, shapes = _k._model(_k._VARP, be, panel, params)
+    B, T, N, r, p = dims
+    sd = None if sd is None else be.inp(sd)
+    named = _index(named, r, "named", True)
+    flags = _k._flags(may_have_missing, singular_q, be, panel)
+    hd = be.out(B, r + 1, T, N)
+    shocks = be.out(B, T, r) if want_shocks else None
+    f, ll = be.out(B, T, r), be.out(B)
+    be.sync()
+    rc = getattr(ctx._lib, "dfm_histdecomp_batch" + be.suffix)(
+        ctx._h, B, T, N, r, p, be.ptr(panel, "panel"), *_k._ptrs(be, _k._VARP, params, shapes), be.ptr(sd, "sd", (B, N)),
+        _k._ptr(named), be.ptr(hd, "hd"), be.ptr(shocks, "shocks"), be.ptr(f, "f_out"), be.ptr(ll, "loglik"), flags)
+    _k._check(ctx._h, rc)
+    return dict(hd=hd, shocks=shocks, f=f, loglik=ll)
+
+
+def irf_batch(ctx, Lam, Avar, Q, R, H: int, sd=None, named=None, cum=None, unit_effect: bool = False, want_fevd: bool = True):
+    """dfm_irf_batch_dev (device tensors, torch's current stream): identified impulse responses irf [B,r,H,N] and forecast-error
+    variance shares fevd [B,r+1,H,N] (None when not asked for) of every series.  Lam [B,N,r], Avar [B,r,r p], Q [B,r,r], R [B,N];
+    sd [B,N] puts irf into data units; named (r distinct series, host side) identifies the shocks, cum (N flags, host side) marks
+    the series whose outputs are cumulated.  The status word (a singular Lam[named]) is read by synchronize()."""
+    return _irf(ctx, _k._Torch(ctx, Lam), Lam, Avar, Q, R, H, sd, named, cum, unit_effect, want_fevd)
+
+
+def irf_batch_host(ctx, Lam, Avar, Q, R, H: int, sd=None, named=None, cum=None, unit_effect: bool = False,
+                   want_fevd: bool = True):
+    """dfm_irf_batch (host pointers; what Julia's ccall binds): NumPy in / out, same dict as irf_batch."""
+    return _irf(ctx, _k._NP, Lam, Avar, Q, R, H, sd, named, cum, unit_effect, want_fevd)
+
+
+def histdecomp_batch(ctx, panel, Lam, R, Avar, Q, mu0, P0, sd=None, named=None, want_shocks: bool = True,
+                     may_have_missing: Optional[bool] = None, singular_q: bool = False):
+    """dfm_histdecomp_batch_dev (device tensors, torch's current stream): the smoother pass, the structural shocks and the
+    contribution of every shock and of the initial condition to every cell.  Parameters as forecast_batch; returns dict(hd
+    [B,r+1,T,N], shocks [B,T,r] or None, f [B,T,r], loglik [B])."""
+    return _histdecomp(ctx, _k._Torch(ctx, panel), panel, (Lam, R, Avar, Q, mu0, P0), sd, named, want_shocks, may_have_missing,
+                       singular_q)
+
+
+def histdecomp_batch_host(ctx, panel, Lam, R, Avar, Q, mu0, P0, sd=None, named=None, want_shocks: bool = True,
+                          may_have_missing: Optional[bool] = None, singular_q: bool = False):
+    """dfm_histdecomp_batch (host pointers; what Julia's ccall binds): NumPy in / out, same dict as histdecomp_batch."""
+    return _histdecomp(ctx, _k._NP, panel, (Lam, R, Avar, Q, mu0, P0), sd, named, want_shocks, may_have_missing, singular_q)
+
+
+for _f in (irf_batch, irf_batch_host, histdecomp_batch, histdecomp_batch_host):
+    setattr(_k.DfmContext, _f.__name__, _f)

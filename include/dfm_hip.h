@@ -56,6 +56,7 @@ enum {
                                    * recursion in covariance form (never inverts Q; P0 must still be positive
                                    * definite).  Slower than the default information form; balanced panels lose the
                                    * time-parallel fast path. */
+#define DFM_SV_UNIT_EFFECT 4u     /* dfm_irf_batch: unit-effect normalisation of the impulse responses (needs `named`) */
 
 typedef struct dfm_handle dfm_handle;
 
@@ -339,6 +340,60 @@ int dfm_news_batch(dfm_handle* h, int B, int T, int N, int r, int p, const doubl
                    const double* Lam, const double* R, const double* Avar, const double* Q, const double* mu0,
                    const double* P0, const double* mean, const double* sd, int G, const int* target_t,
                    const int* target_i, double* yhat, double* impact, double* news, double* weight, unsigned flags);
+
+/* --- structural IRFs, variance and historical decompositions of the panel ---------------------------------------------------
+ * The model of dfm_forecast_batch: x_t = Lam f_t + e_t, f_t = A_1 f_{t-1} + .. + A_p f_{t-p} + eta_t, Var eta = Q, with
+ * 1 <= r p <= DFM_MAX_R.  The structural shocks are eta_t = S u_t with Var u = I.
+ * Identification: named-factor normalisation plus Cholesky ordering.  `named` is a HOST int[r] of distinct series indices shared
+ * by every replicate, as the news targets are; it may be NULL.  With Ln = Lam[named, :] (r x r): S = Ln^-1 chol(Ln Q Ln').
+ * Factor k then *is* the common component of series named[k]; the order of `named` is the recursive ordering.  With named = NULL:
+ * S = chol(Q).  chol is the lower root with the zero-column rule of dfm_simsmooth_batch: a pivot <= 1e-12 trace gives a zero
+ * column.  Ln is factored with partial pivoting; a pivot <= 1e-12 max|Ln| in any replicate raises a status bit, which the host
+ * entry reports as DFM_E_NUMERIC (dfm_check_status after the "_dev" entry).  With `named` the outputs do not change under
+ * Lam -> Lam M^-1, A_j -> M A_j M^-1, Q -> M Q M': that invariance is the point.
+ * Responses: Theta_h = Psi_h S for h = 0 .. H-1, from the companion recursion; Theta^c_h = sum_{j<=h} Theta_j.  `cum` is a HOST
+ * int[N] that may be NULL; cum[i] != 0 means series i entered in differences and its outputs are cumulated.  sd [B][N] may be
+ * NULL; it puts the IRF and the historical decomposition into data units (no mean is involved).
+ *
+ * dfm_irf_batch: inputs Lam [B][N][r], Avar [B][r][r p], Q [B][r][r], R [B][N] (needed with fevd), sd, named, cum; no panel, no
+ * pass.
+ *   irf[b][k][h][i]  = sd_i lam_i' Theta_h e_k, with Theta^c_h where cum[i]                                       [B][r][H][N]
+ *     flag DFM_SV_UNIT_EFFECT (needs named, else DFM_E_NULL) divides column k by the impact response of series named[k] in
+ *     output units; that response is then exactly 1 at h = 0.  It scales the IRF only.
+ *   fevd[b][k][h][i] (may be NULL), always from the unit-variance shocks:                                         [B][r+1][H][N]
+ *     num_k = sum_{j<=h} (lam_i' Theta_j e_k)^2, cumulated responses where cum[i]; idio = R_i, or (h+1) R_i where cum[i];
+ *     fevd[k] = num_k / (sum_k num_k + idio); slot k = r is the idiosyncratic share; the r+1 slots sum to 1.
+ *   Status: H < 1 or a named entry out of range or repeated: DFM_E_DIMS; a NULL required pointer: DFM_E_NULL;
+ *   r p > DFM_MAX_R: DFM_E_R_UNSUPPORTED.  Sizes are checked before the handle.  A rank-deficient Q is accepted (zero column).
+ *
+ * dfm_histdecomp_batch: inputs as dfm_forecast_batch without H and mean, plus named.
+ *   1. the smoother pass of dfm_ks_pass_batch_dev (p = 1) / dfm_ks_pass_varp_batch_dev with the caller's flags and without
+ *      P_smooth, exactly as dfm_forecast_batch_dev calls it
+ *   2. for t >= p: etahat_t = f_t|T - sum_j A_j f_{t-j|T} and u_t = S^-1 etahat_t; with named that is L*^-1 Ln etahat_t by forward
+ *      substitution (L* = chol(Ln Q Ln')).  A zero pivot gives the status bit and DFM_E_NUMERIC, so this entry needs Q positive
+ *      definite.  Rows t < p carry no shock.
+ *   3. contribution paths c^(k)_t = sum_j A_j c^(k)_{t-j} + S e_k u_{k,t} from zero, for k < r; slot k = r is the initial
+ *      condition: c^(r)_t = f_t|T for t < p, then the shock-free recursion
+ *   4. hd[b][k][t][i] = sd_i lam_i' c^(k)_t, every cell whether observed or not; the r+1 slots sum to sd_i lam_i' f_t|T
+ *                                                                                                                 [B][r+1][T][N]
+ *   5. optional outputs (may be NULL): shocks [B][T][r] (u_t, zero rows for t < p), f_out [B][T][r], loglik [B]
+ *   6. Status: T < p + 1: DFM_E_DIMS; the rest as the pass.
+ * Both allocate in the handle (kept for the next call): S, S^-1, the Theta tables [B][H][r][r], the contribution paths
+ * [B][r+1][T][r] and whatever optional output the caller does not take.  Outputs must not overlap the inputs. */
+int dfm_irf_batch_dev(dfm_handle* h, int B, int N, int r, int p, int H, const double* Lam, const double* Avar,
+                      const double* Q, const double* R, const double* sd, const int* named, const int* cum, double* irf,
+                      double* fevd, unsigned flags);
+int dfm_irf_batch(dfm_handle* h, int B, int N, int r, int p, int H, const double* Lam, const double* Avar, const double* Q,
+                  const double* R, const double* sd, const int* named, const int* cum, double* irf, double* fevd,
+                  unsigned flags);
+int dfm_histdecomp_batch_dev(dfm_handle* h, int B, int T, int N, int r, int p, const double* panel, const double* Lam,
+                             const double* R, const double* Avar, const double* Q, const double* mu0, const double* P0,
+                             const double* sd, const int* named, double* hd, double* shocks, double* f_out, double* loglik,
+                             unsigned flags);
+int dfm_histdecomp_batch(dfm_handle* h, int B, int T, int N, int r, int p, const double* panel, const double* Lam,
+                         const double* R, const double* Avar, const double* Q, const double* mu0, const double* P0,
+                         const double* sd, const int* named, double* hd, double* shocks, double* f_out, double* loglik,
+                         unsigned flags);
 
 /* --- AR idiosyncratic terms --------------------------------------------------------
  *   x_it = lam_i' f_t + e_it,   e_it = rho_i1 e_i,t-1 + .. + rho_iq e_i,t-q + eps_it,  eps_it ~ N(0, sig2_i)

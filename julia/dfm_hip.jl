@@ -21,6 +21,7 @@ module DFMHip
 const LIB = get(ENV, "DFMHIP_LIB", joinpath(@__DIR__, "..", "dynamic_factor_models_amd", "lib", "libdfmhip.so"))
 const DFM_F_MAY_HAVE_MISSING = Cuint(1)
 const DFM_F_SINGULAR_Q = Cuint(2)
+const DFM_SV_UNIT_EFFECT = Cuint(4)
 const DFM_E_NUMERIC = Cint(-5)
 
 mutable struct Handle
@@ -336,6 +337,59 @@ function forecast(h::Handle, z::Matrix{Float64}, params, H::Integer; nlag::Integ
     end
     return (x = permutedims(xhat), xvar = permutedims(xvar), common = permutedims(common), factor = permutedims(f),
             P = permutedims(P), loglik = ll[1])
+end
+
+"Identified impulse responses and forecast-error variance shares of every series (dfm_irf_batch; include/dfm_hip.h): params as
+`forecast`; named = r distinct series (1-based; factor k is the common component of series named[k], their order the recursive
+ordering) or nothing (S = chol Q); cumulate = series (1-based) whose responses are cumulated; sd (length N) puts the responses
+into data units.  Returns irf (N x H x r: series, horizon, shock) and fevd (N x H x (r+1), the last slot idiosyncratic)."
+function structural_irf(h::Handle, params, H::Integer; nlag::Integer = 1, named = nothing, cumulate = nothing, sd = nothing,
+                        unit_effect::Bool = false)
+    N, r = size(params.Lam)
+    Av = hasproperty(params, :Avar) ? params.Avar : params.A
+    Lam = permutedims(params.Lam); R = copy(params.R); AC = permutedims(Av); QC = permutedims(params.Q)
+    sdC = sd === nothing ? C_NULL : Vector{Float64}(sd)
+    namedC = named === nothing ? C_NULL : Vector{Cint}(named .- 1)
+    cumC = C_NULL
+    if cumulate !== nothing
+        cumC = zeros(Cint, N); cumC[cumulate] .= 1
+    end
+    irf = Array{Float64}(undef, N, H, r); fevd = Array{Float64}(undef, N, H, r + 1)
+    flags = unit_effect ? DFM_SV_UNIT_EFFECT : Cuint(0)
+    GC.@preserve Lam R AC QC sdC namedC cumC irf fevd begin
+        rc = ccall((:dfm_irf_batch, LIB), Cint,
+                   (Ptr{Cvoid}, Cint, Cint, Cint, Cint, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                    Ptr{Float64}, Ptr{Cint}, Ptr{Cint}, Ptr{Float64}, Ptr{Float64}, Cuint),
+                   h.ptr, 1, N, r, nlag, H, Lam, AC, QC, R, sdC, namedC, cumC, irf, fevd, flags)
+        check(h.ptr, rc)
+    end
+    return (irf = irf, fevd = fevd)              # the C layout [k][h][i] is column-major N x H x r as it stands
+end
+
+"Historical decomposition (dfm_histdecomp_batch; include/dfm_hip.h): z, params, nlag, sd, singular_q as `forecast`, named as
+`structural_irf`.  Returns contributions (T x N x (r+1): the last slot is the initial condition), shocks (T x r), factor
+(T x r) and loglik."
+function historical_decomposition(h::Handle, z::Matrix{Float64}, params; nlag::Integer = 1, named = nothing, sd = nothing,
+                                  singular_q::Bool = false)
+    T, N = size(z); r = size(params.Lam, 2)
+    Av = hasproperty(params, :Avar) ? params.Avar : params.A
+    panel = to_c_panel(z)
+    Lam = permutedims(params.Lam); R = copy(params.R); AC = permutedims(Av); QC = permutedims(params.Q)
+    mu0 = copy(params.mu0); P0C = permutedims(params.P0)
+    sdC = sd === nothing ? C_NULL : Vector{Float64}(sd)
+    namedC = named === nothing ? C_NULL : Vector{Cint}(named .- 1)
+    hd = Array{Float64}(undef, N, T, r + 1); u = Array{Float64}(undef, r, T); f = Array{Float64}(undef, r, T)
+    ll = Array{Float64}(undef, 1)
+    flags = (any(isnan, z) ? DFM_F_MAY_HAVE_MISSING : Cuint(0)) | (singular_q ? DFM_F_SINGULAR_Q : Cuint(0))
+    GC.@preserve panel Lam R AC QC mu0 P0C sdC namedC hd u f ll begin
+        rc = ccall((:dfm_histdecomp_batch, LIB), Cint,
+                   (Ptr{Cvoid}, Cint, Cint, Cint, Cint, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                    Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cint}, Ptr{Float64}, Ptr{Float64},
+                    Ptr{Float64}, Ptr{Float64}, Cuint),
+                   h.ptr, 1, T, N, r, nlag, panel, Lam, R, AC, QC, mu0, P0C, sdC, namedC, hd, u, f, ll, flags)
+        check(h.ptr, rc)
+    end
+    return (contributions = permutedims(hd, (2, 1, 3)), shocks = permutedims(u), factor = permutedims(f), loglik = ll[1])
 end
 
 "Joint posterior draws of the factor path and of the missing / future cells (dfm_simsmooth_batch; include/dfm_hip.h): z, params,
