@@ -70,6 +70,8 @@ __global__ __launch_bounds__(kBootThreads) void var_boot_kernel(BootArgs a) {
         if (a.signs) {
             sgn = a.signs[(size_t)dd * T + t];
         } else {
+            // THE sign source (restated by oracle/boot_oracle.py rademacher_signs): +1 if word 0 of the Philox4x32-10
+            // block keyed by `seed` with the 128-bit counter (period t, global draw first_draw + d) is odd, else -1
             uint32_t o[4];
             Philox::block(a.seed, (uint64_t)t, (uint64_t)(a.first_draw + dd), o);
             sgn = (o[0] & 1u) ? 1.0 : -1.0;

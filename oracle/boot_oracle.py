@@ -13,6 +13,26 @@ from __future__ import annotations
 import numpy as np
 
 from . import als_oracle as ao
+from . import synth_oracle as so
+
+
+def sign_block(seed: int, period, draw) -> np.ndarray:
+    """Philox::block(seed, period, draw) of dfm_philox.h as boot.hip calls it: the Philox4x32-10 block keyed by the
+    64-bit `seed` with the 128-bit counter (period lo, period hi, draw lo, draw hi).  `period` and `draw` are uint64
+    arrays of one shape; returns [..., 4] uint32."""
+    t, d = np.broadcast_arrays(np.asarray(period, dtype=np.uint64), np.asarray(draw, dtype=np.uint64))
+    ctr = np.stack([(t & so.MASK).astype(np.uint32), (t >> np.uint64(32)).astype(np.uint32),
+                    (d & so.MASK).astype(np.uint32), (d >> np.uint64(32)).astype(np.uint32)], axis=-1)
+    key = np.array([seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF], dtype=np.uint32)
+    return so.philox4x32_10(ctr, key)
+
+
+def rademacher_signs(seed: int, first_draw: int, B: int, T: int) -> np.ndarray:
+    """The device-drawn signs of boot.hip's draw loop, [B, T] of +-1.0: sign (d, t) is +1 if word 0 of
+    sign_block(seed, t, first_draw + d) is odd, else -1.  Periods t < p are listed too; the kernel never draws them."""
+    d = np.array([(first_draw + b) & 0xFFFFFFFFFFFFFFFF for b in range(B)], dtype=np.uint64)
+    w0 = sign_block(seed, np.arange(T, dtype=np.uint64)[None, :], d[:, None])[..., 0]
+    return np.where((w0 & np.uint32(1)) != 0, 1.0, -1.0)
 
 
 def var_bootstrap_irf(y, p, H, signs):
