@@ -5,6 +5,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "dfm_cellgeom.h"
 #include "dfm_device.h"
 
 namespace dfm {
@@ -485,7 +486,7 @@ struct FcFillArgs {
     const double* mean; const double* sd;         // [B][N] or both null
     double* xhat; double* xvar; double* common;   // [B][T+H][N]; xvar / common may be null
     double* f_out; double* P_out;                 // copy of the staged rows in the [B][T+H] layout, or null
-    int RC, NPB, G, nchunk, nsblk;                // geometry (set by the launcher)
+    CellGeom geo;                                 // geometry (set by the launcher)
 };
 hipError_t launch_forecast_fill(const FcFillArgs& a, hipStream_t s);
 hipError_t launch_forecast_pad(int B, int T, int H, int N, const double* panel, double* out, bool check_nan, int* status,
@@ -508,7 +509,7 @@ struct SsArgs {
     double* diff;                                 // [S][T][N] difference panels of the slice
     double *eLam, *eR, *eA, *eQ, *emu0, *eP0;     // [S][..] the pass's parameters (mu0 = 0)
     const double* g;                              // [S][T][r] smoothed mean of the difference panels
-    int NPB, G, RC, nchunk, nsblk;                // geometry of the cell kernels (set by their launchers)
+    CellGeom geo;                                 // geometry of the cell kernels (set by their launchers)
 };
 hipError_t launch_simsmooth_prep(const SsArgs& a, hipStream_t s);
 hipError_t launch_simsmooth_expand(const SsArgs& a, hipStream_t s);
@@ -539,7 +540,7 @@ struct NwArgs {
     double* av;                                   // [S][T][r] S Cov(z_{t+1}, z_{t*+1}) S' lam_i*
     double* cp;                                   // [S][T][N] covariance panels (may alias the slice's part of weight)
     const double* g;                              // [S][T][r] E_0[f | c] of the covariance panels
-    int NPB, GR, RC, nchunk, nsblk;               // geometry of the cell kernels (set by their launchers)
+    CellGeom geo;                                 // geometry of the cell kernels (set by their launchers)
 };
 hipError_t launch_news_revise(const NwArgs& a, hipStream_t s);
 hipError_t launch_news_gather(const NwArgs& a, const double* xhat, int which, hipStream_t s);
@@ -565,7 +566,7 @@ struct SvArgs {
     double* u;                                    // [B][T][r] structural shocks, zero rows for t < p
     double* C;                                    // [B][r+1][T][r] contribution paths, slot r = the initial condition
     double* hd;                                   // [B][r+1][T][N]
-    int NPB, G, RC, nchunk, nsblk, CP, TC;        // geometry (set by the launchers)
+    CellGeom geo; int CP, TC;                     // geometry (set by the launchers)
 };
 hipError_t launch_sv_prep(const SvArgs& a, hipStream_t s);
 hipError_t launch_sv_irf_fill(SvArgs a, hipStream_t s);

@@ -1,12 +1,14 @@
 // dfm_smallmat.h -- r x r dense helpers for the "lane i owns row i" layout of the recursion kernels:
 // a group of R lanes holds one matrix, rows other lanes need are exchanged through a per-group LDS
-// slot (one wave per workgroup, so __syncthreads() is a wave-level fence).
+// slot (one wave per workgroup, so __syncthreads() is a wave-level fence); and psd_root, the workgroup-wide
+// Cholesky root in LDS of the prep kernels (simsmooth.hip, structural.hip).
 #pragma once
 #include "dfm_device.h"
 
 namespace dfm {
 
 constexpr double kSteadyTol = 4.5e-16;  // ~2 ulp: successive Om_f / P_s this close are "equal"
+constexpr double kPsdTol = 1e-12;       // psd_root: a pivot <= this x trace zeroes its column
 
 template <int R>
 __device__ __forceinline__ void store_row(double* M, int i, const double (&row)[R]) {
@@ -116,6 +118,37 @@ __device__ __forceinline__ double equilibrate_rows(double (&m)[R], double* dx, i
 
 __device__ __forceinline__ bool close_enough(double a, double b) {
     return fabs(a - b) <= kSteadyTol * fabs(b);
+}
+
+// Lower root L L' = M (n <= 32, lower triangle of M read) by Cholesky; a column whose pivot is <= tol_rel trace(M) is zero, so a
+// positive semi-definite M has a root too.  Returns the number of zero columns.  L: LDS [n][n]; every thread of the workgroup
+// takes part.
+__device__ inline int psd_root(const double* M, int n, double* L, double tol_rel) {
+    const int tid = threadIdx.x;
+    double tr = 0.0;
+    for (int i = 0; i < n; ++i) tr += M[i * n + i];
+    const double tol = tol_rel * tr;
+    for (int e = tid; e < n * n; e += blockDim.x) L[e] = 0.0;
+    __syncthreads();
+    int dropped = 0;
+    for (int j = 0; j < n; ++j) {
+        double dj = M[j * n + j];
+        for (int m = 0; m < j; ++m) dj -= L[j * n + m] * L[j * n + m];
+        const bool keep = dj > tol;
+        dropped += keep ? 0 : 1;
+        const double ljj = keep ? sqrt(dj) : 0.0;
+        for (int i = j + tid; i < n; i += blockDim.x) {
+            if (i == j) {
+                L[j * n + j] = ljj;
+            } else {
+                double v = M[i * n + j];
+                for (int m = 0; m < j; ++m) v -= L[i * n + m] * L[j * n + m];
+                L[i * n + j] = keep ? v / ljj : 0.0;
+            }
+        }
+        __syncthreads();
+    }
+    return dropped;
 }
 
 }  // namespace dfm

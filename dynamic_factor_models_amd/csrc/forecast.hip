@@ -12,8 +12,6 @@
 // At r <= 8 (K = 8 + 36) the VALU does them in the shadow of the stores: one workgroup owns a replicate's chunk of rows and a
 // block of series, stages the chunk's f_t / P_t rows in LDS (every lane of a wave reads the same address: a broadcast), keeps its
 // series' loadings in registers and writes 16 bytes per lane (two adjacent series) when N is even.
-#include <utility>
-
 #include "dfm_kernels.h"
 
 namespace dfm {
@@ -97,12 +95,12 @@ __global__ __launch_bounds__(kFcFillMaxThreads) void forecast_fill_kernel(FcFill
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int TH = a.T + a.H, tid = threadIdx.x;
     unsigned blk = blockIdx.x;
-    const int s = (int)(blk % (unsigned)a.nsblk); blk /= (unsigned)a.nsblk;
-    const int c = (int)(blk % (unsigned)a.nchunk);
-    const size_t b = blk / (unsigned)a.nchunk;
-    const int t0 = c * a.RC, t1 = t0 + a.RC < TH ? t0 + a.RC : TH, nt = t1 - t0;
+    const int s = (int)(blk % (unsigned)a.geo.nsblk); blk /= (unsigned)a.geo.nsblk;
+    const int c = (int)(blk % (unsigned)a.geo.nchunk);
+    const size_t b = blk / (unsigned)a.geo.nchunk;
+    const int t0 = c * a.geo.RC, t1 = t0 + a.geo.RC < TH ? t0 + a.geo.RC : TH, nt = t1 - t0;
     double* sf = sm;
-    double* sP = sm + (size_t)a.RC * R;
+    double* sP = sm + (size_t)a.geo.RC * R;
     const bool loadP = a.Ph != nullptr, wantVar = a.xvar != nullptr;
     const bool copy = s == 0 && a.f_out != nullptr;
     // the chunk's factor rows (contiguous in both sources); series block 0 also writes them to the caller's T + H row layout
@@ -120,9 +118,9 @@ __global__ __launch_bounds__(kFcFillMaxThreads) void forecast_fill_kernel(FcFill
             if (copy && a.P_out) a.P_out[(b * TH + t) * NP + k] = v;
         }
     __syncthreads();
-    const int j = tid % a.NPB, g = tid / a.NPB;
-    if (g >= a.G) return;
-    const int i0 = (s * a.NPB + j) * SP;
+    const int j = tid % a.geo.NPB, g = tid / a.geo.NPB;
+    if (g >= a.geo.G) return;
+    const int i0 = (s * a.geo.NPB + j) * SP;
     if (i0 >= a.N) return;                                  // (SP = 2 only for even N: i0 + 1 < N)
     const bool scale = a.mean != nullptr;
     double lam[SP][R], Rv[SP], mu[SP], sd[SP];
@@ -135,7 +133,7 @@ __global__ __launch_bounds__(kFcFillMaxThreads) void forecast_fill_kernel(FcFill
         mu[q] = scale ? a.mean[bi] : 0.0;
         sd[q] = scale ? a.sd[bi] : 1.0;
     }
-    for (int t = t0 + g; t < t1; t += a.G) {
+    for (int t = t0 + g; t < t1; t += a.geo.G) {
         const double* f = sf + (size_t)(t - t0) * R;
         const double* P = sP + (size_t)(t - t0) * NP;
         double x[SP];
@@ -199,61 +197,27 @@ hipError_t launch_forecast_pad(int B, int T, int H, int N, const double* panel, 
     return hipGetLastError();
 }
 
-// Series per workgroup (NPB lanes of SP series), rows per pass over them (G) and per workgroup (RC): the workgroup is G x NPB lanes
-// rounded up to whole waves, G chosen so that the fewest lanes idle (N = 200, SP = 2: 5 x 100 of 512; N = 139: 3 x 139 of 448).
-static void fill_geometry(int N, int R, int SP, int TH, FcFillArgs& a, int& threads) {
-    const int np_tot = (N + SP - 1) / SP;
-    a.nsblk = (np_tot + 255) / 256;
-    a.NPB = (np_tot + a.nsblk - 1) / a.nsblk;
-    int bestG = 1;
-    double best = -1.0;
-    for (int G = 1; G * a.NPB <= kFcFillMaxThreads; ++G) {
-        const int th = (G * a.NPB + 63) / 64 * 64;
-        if (th > kFcFillMaxThreads) break;
-        const double eff = (double)(G * a.NPB) / th;
-        if (eff > best + 1e-9) { best = eff; bestG = G; }
-    }
-    a.G = bestG;
-    threads = (a.G * a.NPB + 63) / 64 * 64;
-    const size_t row_bytes = (size_t)(R + R * (R + 1) / 2) * sizeof(double);
-    int rc = a.G * 8;
-    const int cap = (int)(kFcFillLds / row_bytes);
-    if (rc > cap) rc = cap;
-    if (rc < 1) rc = 1;
-    if (rc > TH) rc = TH;
-    a.RC = rc;
-    a.nchunk = (TH + rc - 1) / rc;
-}
-
+// A lane per SP series; a staged row is f_t and the packed P_t (cell_geometry, dfm_cellgeom.h).
 template <int R>
 static hipError_t launch_fill_r(FcFillArgs a, hipStream_t s) {
-    auto al16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
     const int SP = ((a.N & 1) == 0 && R <= 16 && al16(a.panel) && al16(a.xhat) && al16(a.xvar) && al16(a.common)) ? 2 : 1;
-    int threads = 0;
-    fill_geometry(a.N, R, SP, a.T + a.H, a, threads);
-    const size_t lds = (size_t)a.RC * (R + R * (R + 1) / 2) * sizeof(double);
-    const size_t blocks = (size_t)a.B * a.nchunk * a.nsblk;
+    a.geo = cell_geometry((a.N + SP - 1) / SP, R + R * (R + 1) / 2, a.T + a.H, kFcFillMaxThreads, kFcFillLds);
+    const size_t lds = (size_t)a.geo.RC * (R + R * (R + 1) / 2) * sizeof(double);
+    const size_t blocks = (size_t)a.B * a.geo.nchunk * a.geo.nsblk;
     if (blocks > 0x7fffffffu) return hipErrorInvalidValue;
     if constexpr (R <= 16) {
         if (SP == 2) {
-            hipLaunchKernelGGL((forecast_fill_kernel<R, 2>), dim3((unsigned)blocks), dim3(threads), lds, s, a);
+            hipLaunchKernelGGL((forecast_fill_kernel<R, 2>), dim3((unsigned)blocks), dim3(a.geo.threads), lds, s, a);
             return hipGetLastError();
         }
     }
-    hipLaunchKernelGGL((forecast_fill_kernel<R, 1>), dim3((unsigned)blocks), dim3(threads), lds, s, a);
+    hipLaunchKernelGGL((forecast_fill_kernel<R, 1>), dim3((unsigned)blocks), dim3(a.geo.threads), lds, s, a);
     return hipGetLastError();
-}
-
-template <int... Rs>
-static hipError_t launch_fill_dispatch(const FcFillArgs& a, hipStream_t s, std::integer_sequence<int, Rs...>) {
-    hipError_t e = hipErrorInvalidValue;
-    (void)((a.r == Rs + 1 ? (e = launch_fill_r<Rs + 1>(a, s), true) : false) || ...);
-    return e;
 }
 
 hipError_t launch_forecast_fill(const FcFillArgs& a, hipStream_t s) {
     if (a.r < 1 || a.r > 32) return hipErrorInvalidValue;
-    return launch_fill_dispatch(a, s, std::make_integer_sequence<int, 32>{});
+    return dispatch_r_exact(a.r, hipErrorInvalidValue, [&](auto R) { return launch_fill_r<decltype(R)::value>(a, s); });
 }
 
 }  // namespace dfm

@@ -7,11 +7,11 @@
 //   news_gamma_kernel       a_t = S Cov(z_{t+1}, z_{t*+1}) S' lam_i* for t < T from Gamma_t = Var(z_t)               [S][T][r]
 //   news_cov_panel_kernel   c_ti = lam_i' a_t (+ R_i* on the target cell) on the new vintage's cells, NaN elsewhere  [S][T][N]
 //   news_impact_kernel      w, the news I and the per-series impacts sum_t w I                                       [S][N]
-// The two cell kernels use the geometry of simsmooth.hip: one workgroup owns a pass replicate's rows (a chunk of them for the
-// covariance panel, all of them for the impacts, which are summed over t in registers and then across the workgroup's row groups
-// in LDS in a fixed order: no atomics, results do not depend on scheduling), stages the r-vectors of its rows in LDS, keeps the
-// loadings of its two columns in registers and moves 16 bytes per lane where N is even.  blockIdx.x is the pass replicate: the G
-// targets of a replicate run next to each other, so the panels they share come from L2 / the Infinity Cache.
+// The two cell kernels: one workgroup owns a pass replicate's rows (a chunk of them for the covariance panel, all of them for the
+// impacts, which are summed over t in registers and then across the workgroup's row groups in LDS in a fixed order: no atomics,
+// results do not depend on scheduling), stages the r-vectors of its rows in LDS, keeps the loadings of its two columns in
+// registers and moves 16 bytes per lane where N is even.  blockIdx.x is the pass replicate: the G targets of a replicate run next
+// to each other, so the panels they share come from L2 / the Infinity Cache.
 #include "dfm_kernels.h"
 
 namespace dfm {
@@ -180,13 +180,13 @@ __global__ __launch_bounds__(kNwMaxThreads) void news_cov_panel_kernel(NwArgs a)
     const long long j = a.j0 + s;
     const size_t b = (size_t)(j / a.G);
     const int gi = (int)(j % a.G);
-    const int t0 = c * a.RC, t1 = t0 + a.RC < T ? t0 + a.RC : T;
+    const int t0 = c * a.geo.RC, t1 = t0 + a.geo.RC < T ? t0 + a.geo.RC : T;
     const double* AV = a.av + (size_t)s * T * r;
     for (int e = tid; e < (t1 - t0) * r; e += blockDim.x) sav[e] = AV[(size_t)t0 * r + e];
     __syncthreads();
-    const int jj = tid % a.NPB, gr = tid / a.NPB;
-    if (gr >= a.GR) return;
-    const int i0 = 2 * (sb * a.NPB + jj);
+    const int jj = tid % a.geo.NPB, gr = tid / a.geo.NPB;
+    if (gr >= a.geo.G) return;
+    const int i0 = 2 * (sb * a.geo.NPB + jj);
     if (i0 >= N) return;
     const bool two = i0 + 1 < N;
     double l0[RB], l1[RB];
@@ -213,10 +213,10 @@ __global__ __launch_bounds__(kNwMaxThreads) void news_cov_panel_kernel(NwArgs a)
     };
     double nx0, nx1;
     load(t0 + gr, nx0, nx1);
-    for (int t = t0 + gr; t < t1; t += a.GR) {
+    for (int t = t0 + gr; t < t1; t += a.geo.G) {
         const double* av = sav + (size_t)(t - t0) * r;
         const double x0 = nx0, x1 = nx1;
-        load(t + a.GR, nx0, nx1);
+        load(t + a.geo.G, nx0, nx1);
         double m0 = 0.0, m1 = 0.0;
 #pragma unroll
         for (int q = 0; q < RB; ++q)
@@ -245,15 +245,15 @@ __global__ __launch_bounds__(kNwMaxThreads) void news_cov_panel_kernel(NwArgs a)
 template <int RB, bool VEC>
 __global__ __launch_bounds__(kNwMaxThreads) void news_impact_kernel(NwArgs a) {
     extern __shared__ __attribute__((aligned(16))) double sgr[];
-    double* sred = sgr + (size_t)a.RC * a.r;                 // [GR][NPB][2] per-row-group sums
+    double* sred = sgr + (size_t)a.geo.RC * a.r;             // [G][NPB][2] per-row-group sums
     const int r = a.r, N = a.N, T = a.T, tid = threadIdx.x;
     const int s = blockIdx.x, sb = blockIdx.y;
     const long long j = a.j0 + s;
     const size_t b = (size_t)(j / a.G);
     const int gi = (int)(j % a.G);
-    const int jj = tid % a.NPB, gr = tid / a.NPB;
-    const int i0 = 2 * (sb * a.NPB + jj);
-    const bool act = gr < a.GR && i0 < N;
+    const int jj = tid % a.geo.NPB, gr = tid / a.geo.NPB;
+    const int i0 = 2 * (sb * a.geo.NPB + jj);
+    const bool act = gr < a.geo.G && i0 < N;
     const bool two = i0 + 1 < N;
     double l0[RB], l1[RB];
     double ir0 = 0.0, ir1 = 0.0, sc0 = 1.0, sc1 = 1.0, mu0 = 0.0, mu1 = 0.0, sd0 = 1.0, sd1 = 1.0;
@@ -277,12 +277,12 @@ __global__ __launch_bounds__(kNwMaxThreads) void news_impact_kernel(NwArgs a) {
     const double* G = a.g + (size_t)s * T * r;
     const bool want_news = a.news != nullptr && gi == 0;
     double acc0 = 0.0, acc1 = 0.0;
-    for (int t0 = 0; t0 < T; t0 += a.RC) {
-        const int t1 = t0 + a.RC < T ? t0 + a.RC : T;
+    for (int t0 = 0; t0 < T; t0 += a.geo.RC) {
+        const int t1 = t0 + a.geo.RC < T ? t0 + a.geo.RC : T;
         for (int e = tid; e < (t1 - t0) * r; e += blockDim.x) sgr[e] = G[(size_t)t0 * r + e];
         __syncthreads();
         if (act)
-            for (int t = t0 + gr; t < t1; t += a.GR) {
+            for (int t = t0 + gr; t < t1; t += a.geo.G) {
                 const double* gt = sgr + (size_t)(t - t0) * r;
                 const size_t cb = (b * T + t) * N + i0, cs = ((size_t)s * T + t) * N + i0, cx = (b * a.TH + t) * N + i0;
                 double xn0, xn1 = 0.0, xo0, xo1 = 0.0, c0, c1 = 0.0, xr0, xr1 = 0.0;
@@ -324,15 +324,15 @@ __global__ __launch_bounds__(kNwMaxThreads) void news_impact_kernel(NwArgs a) {
         __syncthreads();
     }
     if (act) {
-        sred[((size_t)gr * a.NPB + jj) * 2] = acc0;
-        sred[((size_t)gr * a.NPB + jj) * 2 + 1] = acc1;
+        sred[((size_t)gr * a.geo.NPB + jj) * 2] = acc0;
+        sred[((size_t)gr * a.geo.NPB + jj) * 2 + 1] = acc1;
     }
     __syncthreads();
     if (act && gr == 0) {
         double s0 = 0.0, s1 = 0.0;
-        for (int q = 0; q < a.GR; ++q) {
-            s0 += sred[((size_t)q * a.NPB + jj) * 2];
-            s1 += sred[((size_t)q * a.NPB + jj) * 2 + 1];
+        for (int q = 0; q < a.geo.G; ++q) {
+            s0 += sred[((size_t)q * a.geo.NPB + jj) * 2];
+            s1 += sred[((size_t)q * a.geo.NPB + jj) * 2 + 1];
         }
         a.impact[(size_t)j * N + i0] = s0;
         if (two) a.impact[(size_t)j * N + i0 + 1] = s1;
@@ -364,73 +364,42 @@ hipError_t launch_news_gamma(const NwArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
-// Column pairs per workgroup (NPB), rows per pass over them (GR) and per LDS chunk (RC): GR x NPB lanes rounded up to whole
-// waves, GR chosen so that the fewest lanes idle (N = 200: 5 x 100 of 512) -- the geometry of simsmooth.hip's cell kernels.
-static int nw_geometry(NwArgs& a, int& threads) {
-    const int npair = (a.N + 1) / 2;
-    a.nsblk = (npair + 255) / 256;
-    a.NPB = (npair + a.nsblk - 1) / a.nsblk;
-    int best_g = 1;
-    double best = -1.0;
-    for (int g = 1; g * a.NPB <= kNwMaxThreads; ++g) {
-        const int th = (g * a.NPB + 63) / 64 * 64;
-        if (th > kNwMaxThreads) break;
-        const double eff = (double)(g * a.NPB) / th;
-        if (eff > best + 1e-9) { best = eff; best_g = g; }
-    }
-    a.GR = best_g;
-    threads = (a.GR * a.NPB + 63) / 64 * 64;
-    int rc = a.GR * 8;
-    const int cap = (int)(kNwLds / ((size_t)a.r * sizeof(double)));
-    if (rc > cap) rc = cap;
-    if (rc > a.T) rc = a.T;
-    if (rc < 1) rc = 1;
-    a.RC = rc;
-    a.nchunk = (a.T + rc - 1) / rc;
-    return a.nchunk <= 65535 && a.nsblk <= 65535 ? 0 : -1;
+// Both cell kernels: column pairs in lanes, r doubles per staged row, T rows (a 3-D / 2-D grid: its y and z extents are checked).
+static bool nw_cells(NwArgs& a) {
+    if (a.r < 1 || a.r > 32 || a.S < 1) return false;
+    a.geo = cell_geometry((a.N + 1) / 2, a.r, a.T, kNwMaxThreads, kNwLds);
+    return a.geo.nchunk <= 65535 && a.geo.nsblk <= 65535;
 }
 
-static bool al16(const void* q) { return ((uintptr_t)q & 15) == 0; }
-
 template <int RB>
-static hipError_t launch_cov_rb(const NwArgs& a, int threads, bool vec, hipStream_t s) {
-    const dim3 grid((unsigned)a.S, (unsigned)a.nchunk, (unsigned)a.nsblk);
-    const size_t lds = (size_t)a.RC * a.r * sizeof(double);
-    if (vec) hipLaunchKernelGGL((news_cov_panel_kernel<RB, true>), grid, dim3(threads), lds, s, a);
-    else hipLaunchKernelGGL((news_cov_panel_kernel<RB, false>), grid, dim3(threads), lds, s, a);
+static hipError_t launch_cov_rb(const NwArgs& a, bool vec, hipStream_t s) {
+    const dim3 grid((unsigned)a.S, (unsigned)a.geo.nchunk, (unsigned)a.geo.nsblk), block(a.geo.threads);
+    const size_t lds = (size_t)a.geo.RC * a.r * sizeof(double);
+    if (vec) hipLaunchKernelGGL((news_cov_panel_kernel<RB, true>), grid, block, lds, s, a);
+    else hipLaunchKernelGGL((news_cov_panel_kernel<RB, false>), grid, block, lds, s, a);
     return hipGetLastError();
 }
 
 hipError_t launch_news_cov_panel(NwArgs a, hipStream_t s) {
-    if (a.r < 1 || a.r > 32 || a.S < 1) return hipErrorInvalidValue;
-    int threads = 0;
-    if (nw_geometry(a, threads)) return hipErrorInvalidValue;
+    if (!nw_cells(a)) return hipErrorInvalidValue;
     const bool vec = (a.N & 1) == 0 && al16(a.newp) && al16(a.cp);
-    if (a.r <= 4) return launch_cov_rb<4>(a, threads, vec, s);
-    if (a.r <= 8) return launch_cov_rb<8>(a, threads, vec, s);
-    if (a.r <= 16) return launch_cov_rb<16>(a, threads, vec, s);
-    return launch_cov_rb<32>(a, threads, vec, s);
+    return dispatch_r_bucket(a.r, [&](auto RB) { return launch_cov_rb<decltype(RB)::value>(a, vec, s); });
 }
 
 template <int RB>
-static hipError_t launch_impact_rb(const NwArgs& a, int threads, bool vec, hipStream_t s) {
-    const dim3 grid((unsigned)a.S, (unsigned)a.nsblk);
-    const size_t lds = ((size_t)a.RC * a.r + (size_t)2 * a.GR * a.NPB) * sizeof(double);
-    if (vec) hipLaunchKernelGGL((news_impact_kernel<RB, true>), grid, dim3(threads), lds, s, a);
-    else hipLaunchKernelGGL((news_impact_kernel<RB, false>), grid, dim3(threads), lds, s, a);
+static hipError_t launch_impact_rb(const NwArgs& a, bool vec, hipStream_t s) {
+    const dim3 grid((unsigned)a.S, (unsigned)a.geo.nsblk), block(a.geo.threads);
+    const size_t lds = ((size_t)a.geo.RC * a.r + (size_t)2 * a.geo.G * a.geo.NPB) * sizeof(double);
+    if (vec) hipLaunchKernelGGL((news_impact_kernel<RB, true>), grid, block, lds, s, a);
+    else hipLaunchKernelGGL((news_impact_kernel<RB, false>), grid, block, lds, s, a);
     return hipGetLastError();
 }
 
 hipError_t launch_news_impact(NwArgs a, hipStream_t s) {
-    if (a.r < 1 || a.r > 32 || a.S < 1) return hipErrorInvalidValue;
-    int threads = 0;
-    if (nw_geometry(a, threads)) return hipErrorInvalidValue;
+    if (!nw_cells(a)) return hipErrorInvalidValue;
     const bool vec = (a.N & 1) == 0 && al16(a.newp) && al16(a.oldp) && al16(a.cp) && al16(a.xrev) &&
                      (a.weight == nullptr || al16(a.weight)) && (a.news == nullptr || al16(a.news));
-    if (a.r <= 4) return launch_impact_rb<4>(a, threads, vec, s);
-    if (a.r <= 8) return launch_impact_rb<8>(a, threads, vec, s);
-    if (a.r <= 16) return launch_impact_rb<16>(a, threads, vec, s);
-    return launch_impact_rb<32>(a, threads, vec, s);
+    return dispatch_r_bucket(a.r, [&](auto RB) { return launch_impact_rb<decltype(RB)::value>(a, vec, s); });
 }
 
 }  // namespace dfm

@@ -14,48 +14,19 @@
 // pairs, stages the chunk's f rows in LDS, keeps its two rows of loadings in registers, draws one Philox counter per pair of
 // cells and moves 16 bytes per lane where N is even.  blockIdx.x is the pass replicate: the D draws of a replicate run next to
 // each other, so the panel chunk every one of them reads comes from L2 / the Infinity Cache and HBM sees the writes.
-#include <utility>
-
 #include "dfm_kernels.h"
 #include "dfm_philox.h"
+#include "dfm_smallmat.h"
 
 namespace dfm {
 
 constexpr int kSsTC = 32;                     // rows per chunk of the companion recursion (normals and L_Q eta staged in LDS)
 constexpr int kSsMaxThreads = 512;            // cell kernels
 constexpr size_t kSsLds = 32 * 1024;          // cell kernels: f rows staged per workgroup
-constexpr double kSsPsdTol = 1e-12;           // PSD root: a pivot <= this x trace zeroes its column
 enum : uint64_t { kSsZ0 = 1, kSsEta = 2, kSsEpsPlus = 3, kSsEps = 4 };
 
 __device__ __forceinline__ uint64_t ss_key(uint64_t seed, int64_t first_draw, int d) {
     return seed ^ (0x9E3779B97F4A7C15ull * (uint64_t)(first_draw + d + 1));
-}
-
-// Lower root L L' = M (n <= 32, lower triangle of M read) by Cholesky; a column whose pivot is <= kSsPsdTol trace(M) is zero, so a
-// positive semi-definite M has a root too.  L: LDS [n][n]; every thread of the workgroup takes part.
-__device__ void ss_psd_root(const double* M, int n, double* L) {
-    const int tid = threadIdx.x;
-    double tr = 0.0;
-    for (int i = 0; i < n; ++i) tr += M[i * n + i];
-    const double tol = kSsPsdTol * tr;
-    for (int e = tid; e < n * n; e += blockDim.x) L[e] = 0.0;
-    __syncthreads();
-    for (int j = 0; j < n; ++j) {
-        double dj = M[j * n + j];
-        for (int m = 0; m < j; ++m) dj -= L[j * n + m] * L[j * n + m];
-        const bool keep = dj > tol;
-        const double ljj = keep ? sqrt(dj) : 0.0;
-        for (int i = j + tid; i < n; i += blockDim.x) {
-            if (i == j) {
-                L[j * n + j] = ljj;
-            } else {
-                double v = M[i * n + j];
-                for (int m = 0; m < j; ++m) v -= L[i * n + m] * L[j * n + m];
-                L[i * n + j] = keep ? v / ljj : 0.0;
-            }
-        }
-        __syncthreads();
-    }
 }
 
 // One workgroup per replicate b: the roots of P0 and Q, once for all D draws.
@@ -63,10 +34,10 @@ __global__ __launch_bounds__(64) void simsmooth_prep_kernel(SsArgs a) {
     __shared__ double L[32 * 32];
     const size_t b = blockIdx.x;
     const int r = a.r, k = a.r * a.p;
-    ss_psd_root(a.P0 + b * k * k, k, L);
+    psd_root(a.P0 + b * k * k, k, L, kPsdTol);
     for (int e = threadIdx.x; e < k * k; e += blockDim.x) a.LP0[b * k * k + e] = L[e];
     __syncthreads();
-    ss_psd_root(a.Q + b * r * r, r, L);
+    psd_root(a.Q + b * r * r, r, L, kPsdTol);
     for (int e = threadIdx.x; e < r * r; e += blockDim.x) a.LQ[b * r * r + e] = L[e];
 }
 
@@ -204,13 +175,13 @@ __device__ __forceinline__ void ss_cells(const SsArgs& a) {
     const long long j = a.j0 + s;
     const size_t b = (size_t)(j / a.D);
     const int d = (int)(j % a.D);
-    const int t0 = c * a.RC, t1 = t0 + a.RC < rows ? t0 + a.RC : rows;
+    const int t0 = c * a.geo.RC, t1 = t0 + a.geo.RC < rows ? t0 + a.geo.RC : rows;
     const double* F = a.f_draw + (size_t)j * TH * r;
     for (int e = tid; e < (t1 - t0) * r; e += blockDim.x) sfr[e] = F[(size_t)t0 * r + e];
     __syncthreads();
-    const int jj = tid % a.NPB, gr = tid / a.NPB;
-    if (gr >= a.G) return;
-    const int i0 = 2 * (sb * a.NPB + jj);
+    const int jj = tid % a.geo.NPB, gr = tid / a.geo.NPB;
+    if (gr >= a.geo.G) return;
+    const int i0 = 2 * (sb * a.geo.NPB + jj);
     if (i0 >= N) return;
     const bool two = i0 + 1 < N;                             // (VEC: N even, always)
     double l0[RB], l1[RB];
@@ -241,10 +212,10 @@ __device__ __forceinline__ void ss_cells(const SsArgs& a) {
     };
     double nx0, nx1;                                          // the next row's cells, in flight while this row is computed
     load(t0 + gr, nx0, nx1);
-    for (int t = t0 + gr; t < t1; t += a.G) {
+    for (int t = t0 + gr; t < t1; t += a.geo.G) {
         const double* f = sfr + (size_t)(t - t0) * r;
         const double x0 = nx0, x1 = nx1;
-        load(t + a.G, nx0, nx1);
+        load(t + a.geo.G, nx0, nx1);
         double m0 = 0.0, m1 = 0.0;
 #pragma unroll
         for (int q = 0; q < RB; ++q)
@@ -304,58 +275,29 @@ hipError_t launch_simsmooth_finish(const SsArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
-// Column pairs per workgroup (NPB), rows per pass over them (G) and per workgroup (RC): G x NPB lanes rounded up to whole waves,
-// G chosen so that the fewest lanes idle (N = 200: 5 x 100 of 512).
-static int ss_geometry(SsArgs& a, int rows, int& threads) {
-    const int npair = (a.N + 1) / 2;
-    a.nsblk = (npair + 255) / 256;
-    a.NPB = (npair + a.nsblk - 1) / a.nsblk;
-    int bestG = 1;
-    double best = -1.0;
-    for (int G = 1; G * a.NPB <= kSsMaxThreads; ++G) {
-        const int th = (G * a.NPB + 63) / 64 * 64;
-        if (th > kSsMaxThreads) break;
-        const double eff = (double)(G * a.NPB) / th;
-        if (eff > best + 1e-9) { best = eff; bestG = G; }
-    }
-    a.G = bestG;
-    threads = (a.G * a.NPB + 63) / 64 * 64;
-    int rc = a.G * 8;
-    const int cap = (int)(kSsLds / ((size_t)a.r * sizeof(double)));
-    if (rc > cap) rc = cap;
-    if (rc > rows) rc = rows;
-    if (rc < 1) rc = 1;
-    a.RC = rc;
-    a.nchunk = (rows + rc - 1) / rc;
-    return a.nchunk <= 65535 && a.nsblk <= 65535 ? 0 : -1;
-}
-
 template <bool FILL, int RB>
-static hipError_t launch_cells_rb(const SsArgs& a, int threads, bool vec, hipStream_t s) {
-    const dim3 grid((unsigned)a.S, (unsigned)a.nchunk, (unsigned)a.nsblk);
-    const size_t lds = (size_t)a.RC * a.r * sizeof(double);
+static hipError_t launch_cells_rb(const SsArgs& a, bool vec, hipStream_t s) {
+    const dim3 grid((unsigned)a.S, (unsigned)a.geo.nchunk, (unsigned)a.geo.nsblk), block(a.geo.threads);
+    const size_t lds = (size_t)a.geo.RC * a.r * sizeof(double);
     if (vec) {
-        if constexpr (FILL) hipLaunchKernelGGL((simsmooth_fill_kernel<RB, true>), grid, dim3(threads), lds, s, a);
-        else hipLaunchKernelGGL((simsmooth_diff_kernel<RB, true>), grid, dim3(threads), lds, s, a);
+        if constexpr (FILL) hipLaunchKernelGGL((simsmooth_fill_kernel<RB, true>), grid, block, lds, s, a);
+        else hipLaunchKernelGGL((simsmooth_diff_kernel<RB, true>), grid, block, lds, s, a);
     } else {
-        if constexpr (FILL) hipLaunchKernelGGL((simsmooth_fill_kernel<RB, false>), grid, dim3(threads), lds, s, a);
-        else hipLaunchKernelGGL((simsmooth_diff_kernel<RB, false>), grid, dim3(threads), lds, s, a);
+        if constexpr (FILL) hipLaunchKernelGGL((simsmooth_fill_kernel<RB, false>), grid, block, lds, s, a);
+        else hipLaunchKernelGGL((simsmooth_diff_kernel<RB, false>), grid, block, lds, s, a);
     }
     return hipGetLastError();
 }
 
+// A lane per column pair; a staged row is f_t (cell_geometry, dfm_cellgeom.h); a 3-D grid: its y and z extents are checked.
 template <bool FILL>
 static hipError_t launch_cells(SsArgs a, hipStream_t s) {
     if (a.r < 1 || a.r > 32 || a.S < 1) return hipErrorInvalidValue;
-    int threads = 0;
-    if (ss_geometry(a, FILL ? a.T + a.H : a.T, threads)) return hipErrorInvalidValue;
-    auto al16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
+    a.geo = cell_geometry((a.N + 1) / 2, a.r, FILL ? a.T + a.H : a.T, kSsMaxThreads, kSsLds);
+    if (a.geo.nchunk > 65535 || a.geo.nsblk > 65535) return hipErrorInvalidValue;
     const double* out = FILL ? a.x_draw : a.diff;
     const bool vec = (a.N & 1) == 0 && al16(a.panel) && al16(out);
-    if (a.r <= 4) return launch_cells_rb<FILL, 4>(a, threads, vec, s);
-    if (a.r <= 8) return launch_cells_rb<FILL, 8>(a, threads, vec, s);
-    if (a.r <= 16) return launch_cells_rb<FILL, 16>(a, threads, vec, s);
-    return launch_cells_rb<FILL, 32>(a, threads, vec, s);
+    return dispatch_r_bucket(a.r, [&](auto RB) { return launch_cells_rb<FILL, decltype(RB)::value>(a, vec, s); });
 }
 
 hipError_t launch_simsmooth_diff(SsArgs a, hipStream_t s) { return launch_cells<false>(a, s); }

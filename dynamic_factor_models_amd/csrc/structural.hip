@@ -8,11 +8,10 @@
 //   sv_shock_kernel     etahat_t = f_t - sum_j A_j f_{t-j} and u_t = S^-1 etahat_t, all t at once
 //   sv_path_kernel      the r + 1 contribution chains c^(k)_t = sum_j A_j c^(k)_{t-j} + S e_k u_kt, one lane per (chain, state
 //                       component): (r + 1) r p busy lanes per dependent row instead of r
-//   sv_hd_fill_kernel   streams hd [B][r+1][T][N] = sd_i lam_i' c^(k)_t with the geometry of forecast_fill_kernel
+//   sv_hd_fill_kernel   streams hd [B][r+1][T][N] = sd_i lam_i' c^(k)_t, a chunk of rows and a block of series per workgroup
 // The tables are stored shock-major, Th[h][k][m] = (Theta_h)_mk, so that a lane's dot product reads consecutive addresses.
-#include <utility>
-
 #include "dfm_kernels.h"
+#include "dfm_smallmat.h"
 
 namespace dfm {
 
@@ -22,39 +21,8 @@ constexpr size_t kSvFillLds = 48 * 1024;      // both fill kernels: Theta rows /
 constexpr int kSvPathMaxThreads = 1024;       // sv_path_kernel
 constexpr size_t kSvPathLds = 48 * 1024;
 constexpr int kSvShockRows = 32;              // sv_shock_kernel: rows per workgroup
-constexpr double kSvPsdTol = 1e-12;           // PSD root: a pivot <= this x trace zeroes its column
 constexpr double kSvPivTol = 1e-12;           // Ln: a pivot <= this x max|Ln| raises the status bit
 constexpr int kSvStatusBit = 16;
-
-// Lower root L L' = M (n <= 32, lower triangle of M read), the zero-column rule of simsmooth.hip's ss_psd_root.  Returns the
-// number of zero columns.  M, L: LDS [n][n]; every thread of the workgroup takes part.
-__device__ int sv_psd_root(const double* M, int n, double* L) {
-    const int tid = threadIdx.x;
-    double tr = 0.0;
-    for (int i = 0; i < n; ++i) tr += M[i * n + i];
-    const double tol = kSvPsdTol * tr;
-    for (int e = tid; e < n * n; e += blockDim.x) L[e] = 0.0;
-    __syncthreads();
-    int dropped = 0;
-    for (int j = 0; j < n; ++j) {
-        double dj = M[j * n + j];
-        for (int m = 0; m < j; ++m) dj -= L[j * n + m] * L[j * n + m];
-        const bool keep = dj > tol;
-        dropped += keep ? 0 : 1;
-        const double ljj = keep ? sqrt(dj) : 0.0;
-        for (int i = j + tid; i < n; i += blockDim.x) {
-            if (i == j) {
-                L[j * n + j] = ljj;
-            } else {
-                double v = M[i * n + j];
-                for (int m = 0; m < j; ++m) v -= L[i * n + m] * L[j * n + m];
-                L[i * n + j] = keep ? v / ljj : 0.0;
-            }
-        }
-        __syncthreads();
-    }
-    return dropped;
-}
 
 // One workgroup per replicate.  LDS: A [r][r p], a ring of p + 1 Theta matrices, Ln, M = Ln Q Ln' (or Q), its root L, and X
 // (Ln Q, then S^-1, then the right-hand side L of Ln S = L).
@@ -87,7 +55,7 @@ __global__ __launch_bounds__(256) void sv_prep_kernel(SvArgs a) {
         }
         __syncthreads();
     }
-    const int dropped = sv_psd_root(sM, r, sL);
+    const int dropped = psd_root(sM, r, sL, kPsdTol);
     if (a.need_pd && dropped && tid == 0) atomicOr(a.status, kSvStatusBit);
     // S^-1 = L^-1 Ln by forward substitution, a column per thread (a zero pivot leaves a zero row)
     if (a.Sinv) {
@@ -179,14 +147,14 @@ __global__ __launch_bounds__(kSvIrfLanes) void sv_irf_fill_kernel(SvArgs a) {
     constexpr int RR = R * R;
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int tid = threadIdx.x, H = a.H, N = a.N;
-    const int s = (int)(blockIdx.x % (unsigned)a.nsblk);
-    const size_t b = blockIdx.x / (unsigned)a.nsblk;
+    const int s = (int)(blockIdx.x % (unsigned)a.geo.nsblk);
+    const size_t b = blockIdx.x / (unsigned)a.geo.nsblk;
     const bool hasc = a.Thc != nullptr, wantV = a.fevd != nullptr, unit = a.scale != nullptr;
     double* sT = sm;
-    double* sTc = sm + (size_t)a.RC * RR;
-    double* sSc = sm + (size_t)a.RC * RR * (hasc ? 2 : 1);
-    const int i0 = (s * a.NPB + tid) * SP;
-    const bool live = tid < a.NPB && i0 < N;                     // (SP = 2 only for even N: i0 + 1 < N)
+    double* sTc = sm + (size_t)a.geo.RC * RR;
+    double* sSc = sm + (size_t)a.geo.RC * RR * (hasc ? 2 : 1);
+    const int i0 = (s * a.geo.NPB + tid) * SP;
+    const bool live = tid < a.geo.NPB && i0 < N;                     // (SP = 2 only for even N: i0 + 1 < N)
     double lam[SP][R], ssq[SP][R], sdv[SP], Rv[SP];
     bool cm[SP];
 #pragma unroll
@@ -199,8 +167,8 @@ __global__ __launch_bounds__(kSvIrfLanes) void sv_irf_fill_kernel(SvArgs a) {
         cm[q] = a.cum != nullptr && a.cum[live ? i0 + q : 0] != 0;
     }
     if (tid < R) sSc[tid] = unit ? a.scale[b * R + tid] : 1.0;
-    for (int h0 = 0; h0 < H; h0 += a.RC) {
-        const int nh = H - h0 < a.RC ? H - h0 : a.RC;
+    for (int h0 = 0; h0 < H; h0 += a.geo.RC) {
+        const int nh = H - h0 < a.geo.RC ? H - h0 : a.geo.RC;
         __syncthreads();
         for (int e = tid; e < nh * RR; e += blockDim.x) {
             sT[e] = a.Th[(b * H + h0) * RR + e];
@@ -341,15 +309,15 @@ __global__ __launch_bounds__(kSvFillMaxThreads) void sv_hd_fill_kernel(SvArgs a)
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int T = a.T, N = a.N, tid = threadIdx.x;
     unsigned blk = blockIdx.x;
-    const int s = (int)(blk % (unsigned)a.nsblk); blk /= (unsigned)a.nsblk;
-    const int c = (int)(blk % (unsigned)a.nchunk);
-    const size_t bk = blk / (unsigned)a.nchunk, b = bk / (R + 1);       // bk = b (r + 1) + slot
-    const int t0 = c * a.RC, t1 = t0 + a.RC < T ? t0 + a.RC : T, nt = t1 - t0;
+    const int s = (int)(blk % (unsigned)a.geo.nsblk); blk /= (unsigned)a.geo.nsblk;
+    const int c = (int)(blk % (unsigned)a.geo.nchunk);
+    const size_t bk = blk / (unsigned)a.geo.nchunk, b = bk / (R + 1);       // bk = b (r + 1) + slot
+    const int t0 = c * a.geo.RC, t1 = t0 + a.geo.RC < T ? t0 + a.geo.RC : T, nt = t1 - t0;
     for (int e = tid; e < nt * R; e += blockDim.x) sm[e] = a.C[(bk * T + t0) * R + e];
     __syncthreads();
-    const int j = tid % a.NPB, g = tid / a.NPB;
-    if (g >= a.G) return;
-    const int i0 = (s * a.NPB + j) * SP;
+    const int j = tid % a.geo.NPB, g = tid / a.geo.NPB;
+    if (g >= a.geo.G) return;
+    const int i0 = (s * a.geo.NPB + j) * SP;
     if (i0 >= N) return;                                    // (SP = 2 only for even N: i0 + 1 < N)
     double lam[SP][R];
 #pragma unroll
@@ -359,7 +327,7 @@ __global__ __launch_bounds__(kSvFillMaxThreads) void sv_hd_fill_kernel(SvArgs a)
 #pragma unroll
         for (int k = 0; k < R; ++k) lam[q][k] = sd * a.Lam[bi * R + k];
     }
-    for (int t = t0 + g; t < t1; t += a.G) {
+    for (int t = t0 + g; t < t1; t += a.geo.G) {
         const double* cr = sm + (size_t)(t - t0) * R;
         double x[SP];
 #pragma unroll
@@ -385,126 +353,58 @@ hipError_t launch_sv_shock(const SvArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
-// Chains per workgroup (CP, each r p lanes wide) and rows staged between two write-outs (TC, under the LDS cap).
-static void path_geometry(int r, int p, SvArgs& a, int& threads, int& groups, size_t& lds) {
-    const int k = r * p;
-    int cp = kSvPathMaxThreads / k;
-    if (cp > r + 1) cp = r + 1;
-    a.CP = cp;
-    groups = (r + 1 + cp - 1) / cp;
-    const int words = (int)(kSvPathLds / sizeof(double)) - 2 * cp * k;
-    int tc = words / (cp * r + r);
-    a.TC = tc > 32 ? 32 : (tc < 1 ? 1 : tc);
-    threads = (cp * k + 63) / 64 * 64;
-    lds = ((size_t)2 * cp * k + (size_t)a.TC * (cp * r + r)) * sizeof(double);
-}
-
 hipError_t launch_sv_path(SvArgs a, hipStream_t s) {
-    int threads = 0, groups = 0;
-    size_t lds = 0;
-    path_geometry(a.r, a.p, a, threads, groups, lds);
-    hipLaunchKernelGGL(sv_path_kernel, dim3((unsigned)a.B, (unsigned)groups), dim3(threads), lds, s, a);
+    const PathGeom g = path_geometry(a.r, a.p, kSvPathMaxThreads, kSvPathLds);
+    a.CP = g.CP;
+    a.TC = g.TC;
+    hipLaunchKernelGGL(sv_path_kernel, dim3((unsigned)a.B, (unsigned)g.groups), dim3(g.threads), g.lds, s, a);
     return hipGetLastError();
 }
-
-// sv_irf_fill_kernel: series blocks of at most kSvIrfLanes lanes and the rows of the Theta tables (one, or two with cum) per chunk.
-static void irf_geometry(int N, int R, int SP, int H, bool hasc, SvArgs& a, int& threads) {
-    const int lanes = (N + SP - 1) / SP;
-    a.nsblk = (lanes + kSvIrfLanes - 1) / kSvIrfLanes;
-    a.NPB = (lanes + a.nsblk - 1) / a.nsblk;
-    threads = (a.NPB + 63) / 64 * 64;
-    const size_t row_bytes = (size_t)R * R * (hasc ? 2 : 1) * sizeof(double);
-    int rc = (int)((kSvFillLds - 32 * sizeof(double)) / row_bytes);
-    if (rc > H) rc = H;
-    a.RC = rc;
-    a.nchunk = (H + rc - 1) / rc;
-    a.G = 1;
-}
-
-// sv_hd_fill_kernel: forecast.hip's fill_geometry with R doubles per staged row.
-static void hd_geometry(int N, int R, int SP, int T, SvArgs& a, int& threads) {
-    const int lanes = (N + SP - 1) / SP;
-    a.nsblk = (lanes + 255) / 256;
-    a.NPB = (lanes + a.nsblk - 1) / a.nsblk;
-    int bestG = 1;
-    double best = -1.0;
-    for (int G = 1; G * a.NPB <= kSvFillMaxThreads; ++G) {
-        const int th = (G * a.NPB + 63) / 64 * 64;
-        if (th > kSvFillMaxThreads) break;
-        const double eff = (double)(G * a.NPB) / th;
-        if (eff > best + 1e-9) { best = eff; bestG = G; }
-    }
-    a.G = bestG;
-    threads = (a.G * a.NPB + 63) / 64 * 64;
-    int rc = a.G * 8;
-    const int cap = (int)(kSvFillLds / ((size_t)R * sizeof(double)));
-    if (rc > cap) rc = cap;
-    if (rc > T) rc = T;
-    a.RC = rc;
-    a.nchunk = (T + rc - 1) / rc;
-}
-
-static bool al16(const void* q) { return ((uintptr_t)q & 15) == 0; }
 
 template <int R>
 static hipError_t launch_irf_r(SvArgs a, hipStream_t s) {
     const int SP = ((a.N & 1) == 0 && R <= 16 && al16(a.irf) && al16(a.fevd)) ? 2 : 1;
     const bool hasc = a.Thc != nullptr;
-    int threads = 0;
-    irf_geometry(a.N, R, SP, a.H, hasc, a, threads);
-    const size_t lds = ((size_t)a.RC * R * R * (hasc ? 2 : 1) + 32) * sizeof(double);
-    const size_t blocks = (size_t)a.B * a.nsblk;
+    a.geo = irf_geometry(a.N, R, SP, a.H, hasc, kSvIrfLanes, kSvFillLds);
+    const size_t lds = ((size_t)a.geo.RC * R * R * (hasc ? 2 : 1) + 32) * sizeof(double);
+    const size_t blocks = (size_t)a.B * a.geo.nsblk;
     if (blocks > 0x7fffffffu) return hipErrorInvalidValue;
     if constexpr (R <= 16) {
         if (SP == 2) {
-            hipLaunchKernelGGL((sv_irf_fill_kernel<R, 2>), dim3((unsigned)blocks), dim3(threads), lds, s, a);
+            hipLaunchKernelGGL((sv_irf_fill_kernel<R, 2>), dim3((unsigned)blocks), dim3(a.geo.threads), lds, s, a);
             return hipGetLastError();
         }
     }
-    hipLaunchKernelGGL((sv_irf_fill_kernel<R, 1>), dim3((unsigned)blocks), dim3(threads), lds, s, a);
+    hipLaunchKernelGGL((sv_irf_fill_kernel<R, 1>), dim3((unsigned)blocks), dim3(a.geo.threads), lds, s, a);
     return hipGetLastError();
 }
 
+// A lane per SP series; a staged row is one row of a contribution path (cell_geometry, dfm_cellgeom.h).
 template <int R>
 static hipError_t launch_hd_r(SvArgs a, hipStream_t s) {
     const int SP = ((a.N & 1) == 0 && R <= 16 && al16(a.hd)) ? 2 : 1;
-    int threads = 0;
-    hd_geometry(a.N, R, SP, a.T, a, threads);
-    const size_t lds = (size_t)a.RC * R * sizeof(double);
-    const size_t blocks = (size_t)a.B * (R + 1) * a.nchunk * a.nsblk;
+    a.geo = cell_geometry((a.N + SP - 1) / SP, R, a.T, kSvFillMaxThreads, kSvFillLds);
+    const size_t lds = (size_t)a.geo.RC * R * sizeof(double);
+    const size_t blocks = (size_t)a.B * (R + 1) * a.geo.nchunk * a.geo.nsblk;
     if (blocks > 0x7fffffffu) return hipErrorInvalidValue;
     if constexpr (R <= 16) {
         if (SP == 2) {
-            hipLaunchKernelGGL((sv_hd_fill_kernel<R, 2>), dim3((unsigned)blocks), dim3(threads), lds, s, a);
+            hipLaunchKernelGGL((sv_hd_fill_kernel<R, 2>), dim3((unsigned)blocks), dim3(a.geo.threads), lds, s, a);
             return hipGetLastError();
         }
     }
-    hipLaunchKernelGGL((sv_hd_fill_kernel<R, 1>), dim3((unsigned)blocks), dim3(threads), lds, s, a);
+    hipLaunchKernelGGL((sv_hd_fill_kernel<R, 1>), dim3((unsigned)blocks), dim3(a.geo.threads), lds, s, a);
     return hipGetLastError();
-}
-
-template <int... Rs>
-static hipError_t launch_irf_dispatch(const SvArgs& a, hipStream_t s, std::integer_sequence<int, Rs...>) {
-    hipError_t e = hipErrorInvalidValue;
-    (void)((a.r == Rs + 1 ? (e = launch_irf_r<Rs + 1>(a, s), true) : false) || ...);
-    return e;
-}
-
-template <int... Rs>
-static hipError_t launch_hd_dispatch(const SvArgs& a, hipStream_t s, std::integer_sequence<int, Rs...>) {
-    hipError_t e = hipErrorInvalidValue;
-    (void)((a.r == Rs + 1 ? (e = launch_hd_r<Rs + 1>(a, s), true) : false) || ...);
-    return e;
 }
 
 hipError_t launch_sv_irf_fill(SvArgs a, hipStream_t s) {
     if (a.r < 1 || a.r > 32 || a.H < 1) return hipErrorInvalidValue;
-    return launch_irf_dispatch(a, s, std::make_integer_sequence<int, 32>{});
+    return dispatch_r_exact(a.r, hipErrorInvalidValue, [&](auto R) { return launch_irf_r<decltype(R)::value>(a, s); });
 }
 
 hipError_t launch_sv_hd_fill(SvArgs a, hipStream_t s) {
     if (a.r < 1 || a.r > 32 || a.T < 1) return hipErrorInvalidValue;
-    return launch_hd_dispatch(a, s, std::make_integer_sequence<int, 32>{});
+    return dispatch_r_exact(a.r, hipErrorInvalidValue, [&](auto R) { return launch_hd_r<decltype(R)::value>(a, s); });
 }
 
 }  // namespace dfm

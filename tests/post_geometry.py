@@ -1,12 +1,15 @@
 """Launch geometry of the post-estimation cell kernels, restated in plain Python, and the case table of
-tests/test_gpu_post_geometry.py.  Test infrastructure only: the C++ in csrc/forecast.hip, csrc/simsmooth.hip and csrc/news.hip
-stays the authority, and tests/test_post_geometry_cpu.py pins this restatement to the numbers those sources state.
+tests/test_gpu_post_geometry.py.  Test infrastructure only: cell_geometry of csrc/dfm_cellgeom.h stays the authority, and
+tests/test_post_geometry_cpu.py holds this restatement against that function, compiled for the host
+(tests/host/cellgeom_host.cpp), over the case tables and a sweep of every call site's inputs.
 
-The five cell kernels (forecast_fill_kernel, simsmooth_diff_kernel / simsmooth_fill_kernel, news_cov_panel_kernel,
-news_impact_kernel) share one geometry: a workgroup owns one replicate (pass replicate), a chunk of RC rows and a block of NPB
-lanes, each lane one series (SP = 1) or one pair of adjacent series; G row groups of NPB lanes are rounded up to whole waves.
-The host entry points stage every array 256-byte aligned, so the 16-byte path (SP = 2 / VEC) is taken exactly when N is even
-(and, for the forecast, R <= 16)."""
+The cell kernels (forecast_fill_kernel, simsmooth_diff_kernel / simsmooth_fill_kernel, news_cov_panel_kernel,
+news_impact_kernel, sv_hd_fill_kernel) share one geometry: a workgroup owns one replicate (pass replicate), a chunk of RC rows
+and a block of NPB lanes, each lane one series (SP = 1) or one pair of adjacent series; G row groups of NPB lanes are rounded up
+to whole waves.  The host entry points stage every array 256-byte aligned, so the 16-byte path (SP = 2 / VEC) is taken exactly
+when N is even (and, for the forecast, R <= 16)."""
+import os
+import subprocess
 
 FC_MAX_THREADS = 512                 # forecast.hip kFcFillMaxThreads
 FC_LDS = 48 * 1024                   # forecast.hip kFcFillLds
@@ -15,9 +18,14 @@ SS_LDS = 32 * 1024                   # simsmooth.hip kSsLds
 NW_MAX_THREADS = 512                 # news.hip kNwMaxThreads
 NW_LDS = 32 * 1024                   # news.hip kNwLds
 
+GEOM_FIELDS = ("NPB", "G", "RC", "nchunk", "nsblk", "threads")       # struct CellGeom
 
-def _best_g(npb, max_threads):
-    """The row-group count that idles the fewest lanes: the loop shared by fill_geometry, ss_geometry and nw_geometry."""
+
+def cell_geometry(lanes, row_doubles, rows, max_threads, lds_bytes):
+    """cell_geometry of dfm_cellgeom.h, the one restatement: blocks of at most 256 lanes, the row-group count G that idles the
+    fewest lanes of the workgroup's whole waves, RC = max(1, min(8 G, LDS cap, rows)) rows per chunk."""
+    nsblk = (lanes + 255) // 256
+    npb = (lanes + nsblk - 1) // nsblk
     best, best_g = -1.0, 1
     g = 1
     while g * npb <= max_threads:
@@ -28,73 +36,53 @@ def _best_g(npb, max_threads):
         if eff > best + 1e-9:
             best, best_g = eff, g
         g += 1
-    return best_g, (best_g * npb + 63) // 64 * 64
+    rc = max(1, min(8 * best_g, lds_bytes // (8 * row_doubles), rows))
+    return dict(NPB=npb, G=best_g, RC=rc, nchunk=(rows + rc - 1) // rc, nsblk=nsblk, threads=(best_g * npb + 63) // 64 * 64)
 
 
-def _summary(kernel, lanes, npb, nsblk, g, rc, rows, cap, threads, grid, **extra):
-    nchunk = (rows + rc - 1) // rc
-    return dict(kernel=kernel, nsblk=nsblk, NPB=npb, G=g, RC=rc, rows=rows, nchunk=nchunk, threads=threads, grid=grid,
-                cap=cap, idle_last=nsblk * npb > lanes, cap_binds=rc < 8 * g and rc < rows,
-                partial_last=nchunk > 1 and rows % rc != 0, **extra)
+def _summary(kernel, call, grid, **extra):
+    """One kernel's launch: `call` = the arguments of cell_geometry at its call site."""
+    lanes, row_doubles, rows, _, lds_bytes = call
+    g = cell_geometry(*call)
+    return dict(g, kernel=kernel, rows=rows, grid=grid(g), cap=lds_bytes // (8 * row_doubles), call=call,
+                idle_last=g["nsblk"] * g["NPB"] > lanes, cap_binds=g["RC"] < 8 * g["G"] and g["RC"] < rows,
+                partial_last=g["nchunk"] > 1 and rows % g["RC"] != 0, **extra)
 
 
 def forecast_fill(B, N, r, T, H):
-    """forecast.hip launch_fill_r (SP: even N and R <= 16 with 16-byte aligned pointers, lines 229-245) and fill_geometry
-    (lines 202-226) for forecast_fill_kernel<R, SP> over TH = T + H rows; the bucket is R = r itself (launch_fill_dispatch).
-    The grid is one-dimensional: B * nchunk * nsblk workgroups."""
+    """forecast.hip launch_fill_r (SP: even N and R <= 16 with 16-byte aligned pointers) for forecast_fill_kernel<R, SP> over
+    T + H rows of R + R (R + 1) / 2 staged doubles; the bucket is R = r itself.  The grid is one-dimensional: B * nchunk * nsblk
+    workgroups."""
     sp = 2 if N % 2 == 0 and r <= 16 else 1
-    th_rows = T + H
-    lanes = (N + sp - 1) // sp
-    nsblk = (lanes + 255) // 256
-    npb = (lanes + nsblk - 1) // nsblk
-    g, threads = _best_g(npb, FC_MAX_THREADS)
-    cap = FC_LDS // ((r + r * (r + 1) // 2) * 8)
-    rc = min(max(min(g * 8, cap), 1), th_rows)
-    nchunk = (th_rows + rc - 1) // rc
-    return _summary("forecast_fill_kernel", lanes, npb, nsblk, g, rc, th_rows, cap, threads, (B * nchunk * nsblk, 1, 1),
-                    SP=sp, R=r, vec=sp == 2)
-
-
-def _pair_geometry(N, r, rows, max_threads, lds):
-    """ss_geometry (simsmooth.hip lines 307-331) = nw_geometry (news.hip lines 367-391): column pairs per block, G, RC."""
-    npair = (N + 1) // 2
-    nsblk = (npair + 255) // 256
-    npb = (npair + nsblk - 1) // nsblk
-    g, threads = _best_g(npb, max_threads)
-    cap = lds // (r * 8)
-    rc = max(min(g * 8, cap, rows), 1)
-    return npair, nsblk, npb, g, threads, cap, rc
+    call = ((N + sp - 1) // sp, r + r * (r + 1) // 2, T + H, FC_MAX_THREADS, FC_LDS)
+    return _summary("forecast_fill_kernel", call, lambda g: (B * g["nchunk"] * g["nsblk"], 1, 1), SP=sp, R=r, vec=sp == 2)
 
 
 def rb_bucket(r):
-    """The loadings register bucket of launch_cells (simsmooth.hip lines 355-358), launch_news_cov_panel and
-    launch_news_impact (news.hip lines 409-412, 430-433)."""
+    """The loadings register bucket of launch_cells (simsmooth.hip), launch_news_cov_panel and launch_news_impact (news.hip):
+    dispatch_r_bucket of dfm_cellgeom.h."""
     return 4 if r <= 4 else 8 if r <= 8 else 16 if r <= 16 else 32
 
 
 def simsmooth_cells(B, D, N, r, T, H, fill):
-    """simsmooth.hip launch_cells<FILL> (lines 347-359) with ss_geometry: rows = T (difference kernel) or T + H (fill
-    kernel); grid (B D, nchunk, nsblk) for a call of at most 8192 pass replicates."""
-    rows = T + H if fill else T
-    npair, nsblk, npb, g, threads, cap, rc = _pair_geometry(N, r, rows, SS_MAX_THREADS, SS_LDS)
-    nchunk = (rows + rc - 1) // rc
+    """simsmooth.hip launch_cells<FILL>: column pairs, r doubles per row, rows = T (difference kernel) or T + H (fill kernel);
+    grid (B D, nchunk, nsblk) for a call of at most 8192 pass replicates."""
+    call = ((N + 1) // 2, r, T + H if fill else T, SS_MAX_THREADS, SS_LDS)
     name = "simsmooth_fill_kernel" if fill else "simsmooth_diff_kernel"
-    return _summary(name, npair, npb, nsblk, g, rc, rows, cap, threads, (B * D, nchunk, nsblk), RB=rb_bucket(r),
-                    vec=N % 2 == 0)
+    return _summary(name, call, lambda g: (B * D, g["nchunk"], g["nsblk"]), RB=rb_bucket(r), vec=N % 2 == 0)
 
 
 def news_cells(B, G, N, r, T, impact):
-    """news.hip nw_geometry with launch_news_cov_panel (grid (B G, nchunk, nsblk)) or launch_news_impact (grid (B G, nsblk):
-    one workgroup walks all T rows, RC at a time)."""
-    npair, nsblk, npb, g, threads, cap, rc = _pair_geometry(N, r, T, NW_MAX_THREADS, NW_LDS)
-    nchunk = (T + rc - 1) // rc
+    """news.hip launch_news_cov_panel (grid (B G, nchunk, nsblk)) or launch_news_impact (grid (B G, nsblk): one workgroup walks
+    all T rows, RC at a time): column pairs, r doubles per row, T rows."""
+    call = ((N + 1) // 2, r, T, NW_MAX_THREADS, NW_LDS)
     name = "news_impact_kernel" if impact else "news_cov_panel_kernel"
-    grid = (B * G, nsblk, 1) if impact else (B * G, nchunk, nsblk)
-    return _summary(name, npair, npb, nsblk, g, rc, T, cap, threads, grid, RB=rb_bucket(r), vec=N % 2 == 0)
+    grid = (lambda g: (B * G, g["nsblk"], 1)) if impact else (lambda g: (B * G, g["nchunk"], g["nsblk"]))
+    return _summary(name, call, grid, RB=rb_bucket(r), vec=N % 2 == 0)
 
 
 def news_gamma_kb(r, p):
-    """launch_news_gamma (news.hip lines 356-365): news_gamma_kernel<KB, NT> with KB >= k = r p."""
+    """launch_news_gamma (news.hip): news_gamma_kernel<KB, NT> with KB >= k = r p."""
     k = r * p
     return 8 if k <= 8 else 16 if k <= 16 else 32
 
@@ -223,3 +211,25 @@ def missing_classes(cases=None):
         for fam, s in classes(case_dict(row)).items():
             hit[fam] |= s
     return {fam: sorted(REQUIRED[fam] - hit[fam]) for fam in REQUIRED}
+
+
+# ------------------------------------------------------------------------------------------------------------- the host check
+SWEEP_N = range(1, 1101)
+SWEEP_R = (1, 4, 5, 8, 9, 16, 17, 20, 32)
+SWEEP_ROWS = (1, 7, 8, 39, 40, 41, 400)
+
+
+def build_cellgeom_host(directory):
+    """tests/host/cellgeom_host.cpp, which includes csrc/dfm_cellgeom.h and nothing else of the library, compiled with g++."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = os.path.join(str(directory), "cellgeom_host")
+    subprocess.run(["g++", "-O1", "-std=c++17", "-o", exe, os.path.join(root, "tests", "host", "cellgeom_host.cpp")], check=True)
+    return exe
+
+
+def ask_cellgeom_host(exe, requests):
+    """One process for all `requests` ((kind, int, ..) with kind = cell | irf | path): the printed fields of each, as int tuples."""
+    text = "".join(" ".join(map(str, q)) + "\n" for q in requests)
+    out = subprocess.run([exe], input=text, capture_output=True, text=True, check=True).stdout.splitlines()
+    assert len(out) == len(requests)
+    return [tuple(map(int, line.split())) for line in out]

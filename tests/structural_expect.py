@@ -5,19 +5,7 @@ import numpy as np
 
 from oracle import kalman_oracle as ko
 from oracle import varp_oracle as vo
-
-
-def psd_root(M):
-    """Lower root with the zero-column rule of dfm_simsmooth_batch: a pivot <= 1e-12 trace gives a zero column."""
-    n = M.shape[0]
-    L = np.zeros((n, n))
-    tol = 1e-12 * np.trace(M)
-    for j in range(n):
-        d = M[j, j] - L[j, :j] @ L[j, :j]
-        if d > tol:
-            L[j, j] = np.sqrt(d)
-            L[j + 1:, j] = (M[j + 1:, j] - L[j + 1:, :j] @ L[j, :j]) / L[j, j]
-    return L
+from tests.simsmooth_expect import psd_root      # lower root with the zero-column rule: a pivot <= 1e-12 trace gives a zero column
 
 
 def impact(Lam, Q, named=None):

@@ -1,6 +1,7 @@
 """Launch geometry of the structural kernels (csrc/structural.hip) restated in plain Python, and the case table of
 tests/test_gpu_structural.py.  Test infrastructure only: the C++ stays the authority, and tests/test_structural_cpu.py pins this
-restatement to the constants and numbers the source states."""
+restatement to the constants the source states and to the functions of csrc/dfm_cellgeom.h, compiled for the host."""
+from tests.post_geometry import cell_geometry
 
 IRF_LANES = 128                      # structural.hip kSvIrfLanes
 FILL_MAX_THREADS = 512               # kSvFillMaxThreads
@@ -10,39 +11,25 @@ PATH_LDS = 48 * 1024                 # kSvPathLds
 
 
 def irf_fill(B, N, r, H, cum, aligned=True):
-    """launch_irf_r / irf_geometry: sv_irf_fill_kernel<R, SP>, one workgroup per (replicate, series block), RC Theta rows per
-    LDS chunk (two tables with cum)."""
+    """launch_irf_r / irf_geometry (dfm_cellgeom.h): sv_irf_fill_kernel<R, SP>, one workgroup per (replicate, series block), RC
+    Theta rows per LDS chunk (two tables with cum)."""
     sp = 2 if N % 2 == 0 and r <= 16 and aligned else 1
     lanes = (N + sp - 1) // sp
     nsblk = (lanes + IRF_LANES - 1) // IRF_LANES
     npb = (lanes + nsblk - 1) // nsblk
     rc = min((FILL_LDS - 32 * 8) // (r * r * (2 if cum else 1) * 8), H)
-    return dict(SP=sp, nsblk=nsblk, NPB=npb, threads=(npb + 63) // 64 * 64, RC=rc, nchunk=(H + rc - 1) // rc, grid=B * nsblk)
+    return dict(SP=sp, nsblk=nsblk, NPB=npb, G=1, threads=(npb + 63) // 64 * 64, RC=rc, nchunk=(H + rc - 1) // rc, grid=B * nsblk)
 
 
 def hd_fill(B, N, r, T, aligned=True):
-    """launch_hd_r / hd_geometry: sv_hd_fill_kernel<R, SP> with forecast.hip's fill geometry over B (r + 1) slabs of T rows."""
+    """launch_hd_r: sv_hd_fill_kernel<R, SP> with cell_geometry (r doubles per staged row) over B (r + 1) slabs of T rows."""
     sp = 2 if N % 2 == 0 and r <= 16 and aligned else 1
-    lanes = (N + sp - 1) // sp
-    nsblk = (lanes + 255) // 256
-    npb = (lanes + nsblk - 1) // nsblk
-    best, g = -1.0, 1
-    G = 1
-    while G * npb <= FILL_MAX_THREADS:
-        th = (G * npb + 63) // 64 * 64
-        if th > FILL_MAX_THREADS:
-            break
-        if G * npb / th > best + 1e-9:
-            best, g = G * npb / th, G
-        G += 1
-    rc = min(g * 8, FILL_LDS // (r * 8), T)
-    nchunk = (T + rc - 1) // rc
-    return dict(SP=sp, nsblk=nsblk, NPB=npb, G=g, threads=(g * npb + 63) // 64 * 64, RC=rc, nchunk=nchunk,
-                grid=B * (r + 1) * nchunk * nsblk)
+    g = cell_geometry((N + sp - 1) // sp, r, T, FILL_MAX_THREADS, FILL_LDS)
+    return dict(g, SP=sp, grid=B * (r + 1) * g["nchunk"] * g["nsblk"])
 
 
 def path(r, p):
-    """path_geometry: CP chains of r p lanes per workgroup, TC rows staged between two write-outs."""
+    """path_geometry (dfm_cellgeom.h): CP chains of r p lanes per workgroup, TC rows staged between two write-outs."""
     k = r * p
     cp = min(PATH_MAX_THREADS // k, r + 1)
     tc = (PATH_LDS // 8 - 2 * cp * k) // (cp * r + r)

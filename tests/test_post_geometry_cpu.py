@@ -1,13 +1,49 @@
 """CPU checks of tests/post_geometry.py: the plain-Python restatement of the post-estimation kernels' launch geometry against the
-numbers the sources state, and the GPU case table (tests/test_gpu_post_geometry.py) against the coverage classes it must hit for
-each kernel family."""
+numbers the sources state and against cell_geometry of csrc/dfm_cellgeom.h itself, compiled for the host
+(tests/host/cellgeom_host.cpp), and the GPU case table (tests/test_gpu_post_geometry.py) against the coverage classes it must
+hit for each kernel family."""
+import itertools
+
 import pytest
 
 from tests import post_geometry as pg
 
 
-def test_forecast_fill_geometry_matches_the_sources():
-    # forecast.hip fill_geometry / DESIGN.md section 10: N = 200, SP = 2 gives 5 x 100 of 512; N = 139 gives 3 x 139 of 448
+@pytest.fixture(scope="module")
+def host_exe(tmp_path_factory):
+    return pg.build_cellgeom_host(tmp_path_factory.mktemp("cellgeom"))
+
+
+def _check_cells(host_exe, geos):
+    """Every summary of `geos` against the host function at the summary's own call-site arguments, field for field."""
+    calls = sorted({g["call"] for g in geos})
+    host = dict(zip(calls, pg.ask_cellgeom_host(host_exe, [("cell",) + c for c in calls])))
+    bad = [(g["kernel"], g["call"], host[g["call"]]) for g in geos if tuple(g[f] for f in pg.GEOM_FIELDS) != host[g["call"]]]
+    assert not bad, bad[:5]
+    return len(calls)
+
+
+def test_case_table_geometries_match_the_host_function(host_exe):
+    geos = [g for row in pg.CASES for fam in pg.geometries(pg.case_dict(row)).values() for g in fam]
+    assert len(geos) == 5 * len(pg.CASES) and _check_cells(host_exe, geos) > len(pg.CASES)
+
+
+@pytest.mark.parametrize("family", ["forecast", "simsmooth", "news"])
+def test_geometry_sweep_matches_the_host_function(host_exe, family):
+    """N = 1..1100 x r x rows at each family's own call-site arguments (lanes, staged doubles per row, thread and LDS caps)."""
+    one = dict(forecast=lambda N, r, rows: pg.forecast_fill(1, N, r, rows, 0),
+               simsmooth=lambda N, r, rows: pg.simsmooth_cells(1, 1, N, r, rows, 0, fill=True),
+               news=lambda N, r, rows: pg.news_cells(1, 1, N, r, rows, impact=False))[family]
+    geos = [one(N, r, rows) for N, r, rows in itertools.product(pg.SWEEP_N, pg.SWEEP_R, pg.SWEEP_ROWS)]
+    n = _check_cells(host_exe, geos)
+    # the sweep reaches both sides of every branch of the function
+    assert n > 10000 and {1, 2, 3} <= {g["nsblk"] for g in geos} and {1, 2, 5, 64} <= {g["G"] for g in geos}
+    assert any(g["cap_binds"] for g in geos) and any(g["RC"] == 8 * g["G"] for g in geos) and any(g["RC"] == g["rows"] for g in geos)
+    assert any(g["partial_last"] for g in geos) and any(g["threads"] > g["G"] * g["NPB"] for g in geos)
+
+
+def test_forecast_fill_launch_matches_the_sources():
+    # cell_geometry / DESIGN.md section 10: N = 200, SP = 2 gives 5 x 100 of 512; N = 139 gives 3 x 139 of 448
     g = pg.forecast_fill(1, 200, 8, 500, 0)
     assert (g["SP"], g["nsblk"], g["G"], g["NPB"], g["threads"]) == (2, 1, 5, 100, 512)
     g = pg.forecast_fill(1, 139, 8, 500, 0)
@@ -22,7 +58,7 @@ def test_forecast_fill_geometry_matches_the_sources():
 
 
 def test_pair_geometry_matches_the_sources():
-    # simsmooth.hip ss_geometry: N = 200 gives 5 x 100 of 512; news.hip nw_geometry is the same
+    # column pairs: N = 200 gives 5 x 100 of 512 in simsmooth.hip and in news.hip
     for g in (pg.simsmooth_cells(1, 1, 200, 8, 500, 0, fill=False), pg.news_cells(1, 1, 200, 8, 500, impact=False)):
         assert (g["nsblk"], g["G"], g["NPB"], g["threads"], g["RC"]) == (1, 5, 100, 512, 40)
     # N = 514: 257 pairs in 2 blocks of 129, the last lane of block 1 idle

@@ -3,6 +3,7 @@ tests/structural_expect.py against the reference-style impulse_response and agai
 library decides without a device, the api's refusals, the binding of dynamic_factor_models_amd/structural.py against a call
 recorder and _lib.SYMBOLS, and tests/structural_geometry.py against csrc/structural.hip.  No kernel is launched here."""
 import ctypes
+import itertools
 import os
 import re
 
@@ -11,6 +12,7 @@ import pytest
 import torch
 
 from dynamic_factor_models_amd import _lib, api, kalman, structural
+from tests import post_geometry as pg
 from tests import structural_expect as se
 from tests import structural_geometry as sg
 
@@ -129,7 +131,7 @@ def test_geometry_restatement_matches_the_source():
     assert (g["SP"], g["nsblk"], g["NPB"]) == (1, 2, 100)
     assert sg.irf_fill(2, 60, 32, 41, False)["RC"] == 5 and sg.irf_fill(2, 1025, 32, 12, True)["RC"] == 2
     assert sg.irf_fill(2, 200, 17, 2, False)["SP"] == 1 and sg.irf_fill(2, 200, 16, 2, False)["SP"] == 2
-    # hd_geometry is forecast.hip's: N = 200 gives 5 x 100 of 512, N = 139 gives 3 x 139 of 448
+    # launch_hd_r uses cell_geometry: N = 200 gives 5 x 100 of 512, N = 139 gives 3 x 139 of 448
     g = sg.hd_fill(1, 200, 8, 500)
     assert (g["SP"], g["G"], g["NPB"], g["threads"], g["RC"]) == (2, 5, 100, 512, 40)
     g = sg.hd_fill(1, 139, 8, 222)
@@ -140,6 +142,37 @@ def test_geometry_restatement_matches_the_source():
     for r, p in [(1, 1), (1, 12), (1, 32), (8, 4), (20, 1), (32, 1), (16, 2), (3, 2)]:
         g = sg.path(r, p)
         assert g["lds"] <= sg.PATH_LDS and g["TC"] >= 1 and g["CP"] * r * p <= sg.PATH_MAX_THREADS
+
+
+@pytest.fixture(scope="module")
+def host_exe(tmp_path_factory):
+    return pg.build_cellgeom_host(tmp_path_factory.mktemp("cellgeom"))
+
+
+def test_geometry_restatement_matches_the_host_functions(host_exe):
+    """irf_fill, hd_fill and path against irf_geometry, cell_geometry and path_geometry of csrc/dfm_cellgeom.h compiled for the host,
+    field for field: the rows of IRF_CASES, then N = 1..1100 x r x (H, with and without the cumulated table | T), and every (r, p)."""
+    irf_q = [(c["N"], c["r"], c["H"], c["cum"], not c["misaligned"]) for c in map(sg.irf_case, sg.IRF_CASES)]
+    irf_q += [(N, r, H, cum, True) for N, r, H, cum in itertools.product(pg.SWEEP_N, pg.SWEEP_R, (1, 2, 12, 41), (False, True))]
+    hd_q = list(itertools.product(pg.SWEEP_N, pg.SWEEP_R, pg.SWEEP_ROWS))
+    path_q = [(r, p) for r in range(1, 33) for p in range(1, 33) if r * p <= 32]
+    want, req = [], []
+    for N, r, H, cum, aligned in irf_q:
+        g = sg.irf_fill(1, N, r, H, cum, aligned)
+        want.append(tuple(g[f] for f in pg.GEOM_FIELDS))
+        req.append(("irf", N, r, g["SP"], H, int(cum), sg.IRF_LANES, sg.FILL_LDS))
+    for N, r, T in hd_q:
+        g = sg.hd_fill(1, N, r, T)
+        want.append(tuple(g[f] for f in pg.GEOM_FIELDS))
+        req.append(("cell", (N + g["SP"] - 1) // g["SP"], r, T, sg.FILL_MAX_THREADS, sg.FILL_LDS))
+    for r, p in path_q:
+        g = sg.path(r, p)
+        want.append((g["CP"], g["TC"], g["groups"], g["threads"], g["lds"]))
+        req.append(("path", r, p, sg.PATH_MAX_THREADS, sg.PATH_LDS))
+    got = pg.ask_cellgeom_host(host_exe, req)
+    bad = [(q, w, g) for q, w, g in zip(req, want, got) if w != g]
+    assert not bad, bad[:5]
+    assert len(path_q) == sum(32 // r for r in range(1, 33)) and {q[3] for q in req if q[0] == "irf"} == {1, 2}
 
 
 # ------------------------------------------------------------------------------------------------------------ status codes
