@@ -45,6 +45,7 @@ _SS_ARGS = [c_vp] + [c_int] * 7 + [c_vp] * 9 + [ctypes.c_uint64, ctypes.c_int64,
 _NW_ARGS = [c_vp] + [c_int] * 5 + [c_vp] * 10 + [c_int] + [c_vp] * 6 + [c_uint]
 _IRF_ARGS = [c_vp] + [c_int] * 5 + [c_vp] * 9 + [c_uint]
 _HD_ARGS = [c_vp] + [c_int] * 5 + [c_vp] * 13 + [c_uint]
+_FT_ARGS = [c_vp] + [c_int] * 7 + [c_vp] * 20 + [c_uint]
 _ARPASS_ARGS = [c_vp, c_int, c_int, c_int, c_int, c_int, c_int] + [c_vp] * 11 + [c_uint]
 _AREM_ARGS = [c_vp, c_int, c_int, c_int, c_int, c_int, c_int] + [c_vp] * 8 + [c_int, ctypes.c_double] + [c_vp] * 4 + [c_uint]
 _MFPASS_ARGS = [c_vp, c_int, c_int, c_int, c_int, c_int, c_int] + [c_vp] * 11 + [c_uint]
@@ -105,6 +106,8 @@ SYMBOLS = {
     "dfm_irf_batch": (c_int, _IRF_ARGS),
     "dfm_histdecomp_batch_dev": (c_int, _HD_ARGS),
     "dfm_histdecomp_batch": (c_int, _HD_ARGS),
+    "dfm_filter_batch_dev": (c_int, _FT_ARGS),
+    "dfm_filter_batch": (c_int, _FT_ARGS),
     "dfm_ks_pass_ar_batch_dev": (c_int, _ARPASS_ARGS),
     "dfm_ks_pass_ar_batch": (c_int, _ARPASS_ARGS),
     "dfm_em_ar_batch_dev": (c_int, _AREM_ARGS),

@@ -494,6 +494,129 @@ def forecast(m: DFMModel, H: int, *, through: Optional[int] = None, quantiles=No
     return out
 
 
+# ----------------------------------------------------------------------------- filtered states and out-of-sample evaluation
+def _filter_setup(m: DFMModel, through, quantiles):
+    """The checks filter_states and evaluate_forecasts share (no device is touched): (through, quantiles or None)."""
+    if m.em_params is None:
+        raise ValueError("the model has not been estimated: run estimate(m, Parametric()) first")
+    if m.nfac_o != 0:
+        raise ValueError("the filter needs nfac_o = 0")
+    through = m.lastperiod if through is None else int(through)
+    if not (m.lastperiod <= through <= m.T):
+        raise ValueError(f"through must lie in lastperiod..T ({m.lastperiod}..{m.T})")
+    qs = None
+    if quantiles is not None:
+        qs = np.atleast_1d(np.asarray(quantiles, dtype=np.float64))
+        if getattr(m, "replicates", None) is None:
+            raise ValueError("quantile bands need bootstrap replicates: estimate(m, Parametric(), nrep=...) first")
+        if qs.size < 1 or not np.all((qs > 0.0) & (qs <= 1.0)):
+            raise ValueError("quantiles must lie in (0, 1]")
+    return through, qs
+
+
+def _filter_run(m: DFMModel, through, H, t0, want, band_of, qs, ctx):
+    """One dfm_filter_batch call at the fit and, for bands, one over the bootstrap replicates' parameter sets on the same panel
+    followed by dfm_quantile_bands over band_of(outputs) [B, ...]."""
+    ep = m.em_params
+    Lam, R, Q = ep["Lam"], ep["R"], ep["Q"]
+    A = ep["Avar"] if "Avar" in ep else ep["A"]
+    cols, z, mu, sd = _forecast_inputs(m, through)
+    if Lam.shape[0] != cols.size:
+        raise ValueError("m.em_params does not match the model's series (was the model changed after estimate?)")
+    ctx, own = _own(ctx)
+    try:
+        def run(Lb, Rb, Ab, Qb, m0, P0b, w):
+            B = Lb.shape[0]
+            rep = lambda a: np.ascontiguousarray(np.broadcast_to(a, (B,) + a.shape))
+            return ctx.filter_batch_host(rep(z), Lb, Rb, Ab, Qb, m0, P0b, H=H, t0=t0, mean=rep(mu), sd=rep(sd), want=w,
+                                         may_have_missing=bool(np.isnan(z).any()))
+        o = run(Lam[None], R[None], A[None], Q[None], ep["mu0"][None], ep["P0"][None], want)
+        bands = None
+        if qs is not None:
+            rp = m.replicates["params"]
+            x = band_of(run(rp["Lam"], rp["R"], rp["A"], rp["Q"], rp["mu0"], rp["P0"], band_of.want))
+            bands = ctx.quantile_bands_host(np.ascontiguousarray(x.reshape(x.shape[0], -1)), qs).reshape((qs.size,) + x.shape[1:])
+    finally:
+        if own:
+            ctx.close()
+    return cols, o, bands
+
+
+def _unpack(Pp, k):
+    il = np.tril_indices(k)                                             # packed lower, row-major (include/dfm_hip.h)
+    cov = np.empty((Pp.shape[0], k, k))
+    cov[:, il[0], il[1]] = Pp
+    cov[:, il[1], il[0]] = Pp
+    return cov
+
+
+def filter_states(m: DFMModel, *, through: Optional[int] = None, quantiles=None, ctx=None) -> dict:
+    """What the parametric fit (`estimate(m, Parametric())`, nfac_o = 0) knew at every period: the Kalman filter's predicted and
+    filtered factors and the one-step prediction errors of the panel.  The parameters (m.em_params) are held fixed over the sample.
+    Window, series, standardisation and `through` as `forecast`.  One dfm_filter_batch call on the GPU.  Returns a dict:
+      rows            1-based periods initperiod .. through
+      cols            column indices (0-based) of m.data: the series estimate() used
+      factor_pred     [rows, r] E[f_t | rows before t], factor_pred_cov [rows, r, r] its variance
+      factor_filt     [rows, r] E[f_t | rows up to t],  factor_filt_cov [rows, r, r]
+      state_pred, state_filt   [rows, r p] the whole companion state (equal to the factors for factor_lags = 1)
+      loglik_t        [rows] log density of each row's observed cells given the rows before it; loglik their sum
+      x_pred          [rows, cols] one-step prediction of every cell, data units
+      error           [rows, cols] x - x_pred in data units, NaN on a missing cell
+      error_std       [rows, cols] the standardised innovation (mean 0, variance 1 under the model), NaN on a missing cell
+    `quantiles` (needs m.replicates): bands [nq, rows, cols] of x_pred over the bootstrap replicates' parameter sets
+    (dfm_quantile_bands).  `m` is not modified."""
+    through, qs = _filter_setup(m, through, quantiles)
+    band_of = lambda o: o["xpred"]
+    band_of.want = ("xpred",)
+    want = ("z_pred", "P_pred", "z_filt", "P_filt", "loglik_t", "xpred", "verr", "vstd")
+    cols, o, bands = _filter_run(m, through, 0, 0, want, band_of, qs, ctx)
+    r = m.em_params["Lam"].shape[1]
+    k = o["z_pred"].shape[2]
+    Pp, Pf = _unpack(o["P_pred"][0], k), _unpack(o["P_filt"][0], k)
+    out = dict(rows=np.arange(m.initperiod, through + 1), cols=cols, factor_pred=o["z_pred"][0][:, :r],
+               factor_pred_cov=Pp[:, :r, :r], factor_filt=o["z_filt"][0][:, :r], factor_filt_cov=Pf[:, :r, :r],
+               state_pred=o["z_pred"][0], state_filt=o["z_filt"][0], loglik_t=o["loglik_t"][0],
+               loglik=float(o["loglik_t"][0].sum()), x_pred=o["xpred"][0], error=o["verr"][0], error_std=o["vstd"][0])
+    if bands is not None:
+        out["quantiles"] = qs
+        out["bands"] = bands
+    return out
+
+
+def evaluate_forecasts(m: DFMModel, H: int, *, first_origin: Optional[int] = None, through: Optional[int] = None, quantiles=None,
+                       ctx=None) -> dict:
+    """The pseudo-out-of-sample record of the parametric fit: the h-step forecast error of every series at every origin, h = 1..H,
+    with the fit held fixed (the data flow is evaluated, not re-estimation), summarised per horizon and series.  Origins are the
+    1-based periods first_origin .. through - h (default first_origin: the middle of the window initperiod..through); the
+    forecast made at origin t uses rows initperiod..t only.  One dfm_filter_batch call on the GPU.  Returns a dict:
+      horizons   1 .. H
+      cols       column indices (0-based) of m.data: the series estimate() used
+      msfe       [H, cols] mean squared forecast error in data units, NaN where no origin has its target observed
+      rmsfe      its square root
+      relative   [H, cols] msfe over the MSFE of the unconditional-mean forecast on the same cells (< 1: the model helps)
+      count      [H, cols] origins averaged
+    `quantiles` (needs m.replicates): bands [nq, H, cols] of msfe over the bootstrap replicates' parameter sets.  `m` is not
+    modified."""
+    H = int(H)
+    if H < 1:
+        raise ValueError("H must be >= 1")
+    through, qs = _filter_setup(m, through, quantiles)
+    rows = through - m.initperiod + 1
+    first_origin = m.initperiod + rows // 2 if first_origin is None else int(first_origin)
+    if not (m.initperiod <= first_origin <= through):
+        raise ValueError(f"first_origin must lie in initperiod..through ({m.initperiod}..{through})")
+    band_of = lambda o: o["msfe"]
+    band_of.want = ("msfe",)
+    cols, o, bands = _filter_run(m, through, H, first_origin - m.initperiod, ("msfe", "msfe0", "cnt"), band_of, qs, ctx)
+    msfe, msfe0 = o["msfe"][0], o["msfe0"][0]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        out = dict(horizons=np.arange(1, H + 1), cols=cols, msfe=msfe, rmsfe=np.sqrt(msfe), relative=msfe / msfe0, count=o["cnt"][0])
+    if bands is not None:
+        out["quantiles"] = qs
+        out["bands"] = bands
+    return out
+
+
 # ----------------------------------------------------------------------------- structural analysis of the parametric fit
 def _structural_checks(m: DFMModel):
     if m.em_params is None:

@@ -157,6 +157,8 @@ struct dfm_handle {
                                            // parameters, u / a vectors, smoothed means and (no weight) covariance panels
     DevBlock sv;                           // dfm_irf_batch_dev / dfm_histdecomp_batch_dev: named / cum, S, S^-1, the Theta tables, shocks and
                                            // contribution paths, and the pass outputs the caller does not take
+    DevBlock ft;                           // dfm_filter_batch_dev: the padded loadings, the collapse's per-period arrays, the moments the
+                                           // caller does not take and the evaluation's running sums
     std::vector<int> sv_idx;               // host copy of named / cum while their upload is in flight
     const double* odd_panel_src = nullptr; int odd_panel_dims[3] = {0, 0, 0};   // the panel whose padded copy h->odd holds (odd_pad keep_panel)
     std::string prof_file;                 // DFM_PF_PROF_FILE with DFM_SCAN_ABL=256: phase stamps of the fused pass
@@ -169,11 +171,11 @@ struct dfm_handle {
 };
 
 enum KernelId { K_COLLAPSE = 0, K_RECURSION, K_MSTEP_STATS, K_MSTEP_SOLVE, K_PCA, K_SYNTH, K_PAD,
-                K_COLLAPSE_DMA, K_GRAM, K_COV, K_MEANSCAN, K_PFILL, K_COLLAPSE_MFMA, K_ALS, K_OLS, K_BOOT, K_QUANT, K_COLLAPSE_WIDE, K_EM_UPDATE, K_CHOW, K_MSTEP_MFMA, K_GRAM_XX, K_PASS_FUSED, K_FC_TAIL, K_FC_FILL, K_FC_PAD, K_SS_PREP, K_SS_EXPAND, K_SS_PATH, K_SS_DIFF, K_SS_FINISH, K_SS_FILL, K_NW_REVISE, K_NW_GATHER, K_NW_GAMMA, K_NW_COV, K_NW_IMPACT, K_MF_TABLE, K_MF_MOMENTS, K_MF_SOLVE, K_SV_PREP, K_SV_IRF_FILL, K_SV_SHOCK, K_SV_PATH, K_SV_HD_FILL, K_COUNT };
+                K_COLLAPSE_DMA, K_GRAM, K_COV, K_MEANSCAN, K_PFILL, K_COLLAPSE_MFMA, K_ALS, K_OLS, K_BOOT, K_QUANT, K_COLLAPSE_WIDE, K_EM_UPDATE, K_CHOW, K_MSTEP_MFMA, K_GRAM_XX, K_PASS_FUSED, K_FC_TAIL, K_FC_FILL, K_FC_PAD, K_SS_PREP, K_SS_EXPAND, K_SS_PATH, K_SS_DIFF, K_SS_FINISH, K_SS_FILL, K_NW_REVISE, K_NW_GATHER, K_NW_GAMMA, K_NW_COV, K_NW_IMPACT, K_MF_TABLE, K_MF_MOMENTS, K_MF_SOLVE, K_SV_PREP, K_SV_IRF_FILL, K_SV_SHOCK, K_SV_PATH, K_SV_HD_FILL, K_FT_FILTER, K_FT_FILL, K_FT_EVAL, K_COUNT };
 static const char* const kKernelNames[K_COUNT] = {"collapse_kernel", "recursion_kernel", "mstep_lam_kernel",
                                                   "mstep_solve_kernel", "pca_kernel", "synth_kernel",
                                                   "pad_params_kernel", "collapse_dma_kernel", "gram_kernel",
-                                                  "cov_kernel", "meanscan_kernel", "pfill_kernel", "collapse_mfma_kernel", "als_kernel", "ols_kernel", "var_boot_kernel", "quantile_kernel", "collapse_wide_kernel", "em_update_kernel", "chow_kernel", "mstep_mfma_kernel", "gram_xx_kernel", "pass_fused_kernel", "forecast_tail_kernel", "forecast_fill_kernel", "forecast_pad_kernel", "simsmooth_prep_kernel", "simsmooth_expand_kernel", "simsmooth_path_kernel", "simsmooth_diff_kernel", "simsmooth_finish_kernel", "simsmooth_fill_kernel", "news_revise_kernel", "news_gather_kernel", "news_gamma_kernel", "news_cov_panel_kernel", "news_impact_kernel", "mf_table_kernel", "mf_moments_kernel", "mf_solve_kernel", "sv_prep_kernel", "sv_irf_fill_kernel", "sv_shock_kernel", "sv_path_kernel", "sv_hd_fill_kernel"};
+                                                  "cov_kernel", "meanscan_kernel", "pfill_kernel", "collapse_mfma_kernel", "als_kernel", "ols_kernel", "var_boot_kernel", "quantile_kernel", "collapse_wide_kernel", "em_update_kernel", "chow_kernel", "mstep_mfma_kernel", "gram_xx_kernel", "pass_fused_kernel", "forecast_tail_kernel", "forecast_fill_kernel", "forecast_pad_kernel", "simsmooth_prep_kernel", "simsmooth_expand_kernel", "simsmooth_path_kernel", "simsmooth_diff_kernel", "simsmooth_finish_kernel", "simsmooth_fill_kernel", "news_revise_kernel", "news_gather_kernel", "news_gamma_kernel", "news_cov_panel_kernel", "news_impact_kernel", "mf_table_kernel", "mf_moments_kernel", "mf_solve_kernel", "sv_prep_kernel", "sv_irf_fill_kernel", "sv_shock_kernel", "sv_path_kernel", "sv_hd_fill_kernel", "filter_kernel", "filter_fill_kernel", "filter_eval_kernel"};
 
 namespace dfm { int handle_device(const dfm_handle* h) { return h->device; } }   // (probe.hip)
 
@@ -1678,7 +1680,7 @@ int dfm_destroy(dfm_handle* h) {
     for (auto e : h->ev_sub) hipEventDestroy(e);
     if (h->ev_fork) hipEventDestroy(h->ev_fork);
     if (h->ev_join) hipEventDestroy(h->ev_join);
-    for (DevBlock* b : {&h->ws, &h->odd, &h->fc, &h->ss, &h->nw, &h->sv}) b->release();
+    for (DevBlock* b : {&h->ws, &h->odd, &h->fc, &h->ss, &h->nw, &h->sv, &h->ft}) b->release();
     if (h->status_dev) hipFree(h->status_dev);
     if (h->own_stream && h->stream) hipStreamDestroy(h->stream);
     delete h;
@@ -1837,7 +1839,7 @@ int dfm_ks_pass_batch_dev(dfm_handle* h, int B, int T, int N, int r, const doubl
 // declared balanced, 2 = the PCA start's subspace iteration did not converge, 4 = a bounded wait between the waves of the
 // one-launch pass ran out (its outputs are invalid even where the log-likelihood happens to be finite), 8 = dfm_news_batch: a cell
 // of the old vintage is observed where the new one is missing, 16 = dfm_irf_batch / dfm_histdecomp_batch: a zero pivot in
-// Lam[named, :] or (decomposition) in the root of Q.  Every synchronising
+// Lam[named, :] or (decomposition) in the root of Q, 32 = dfm_filter_batch: a replicate's update failed.  Every synchronising
 // entry point goes through here; device-pointer callers get the same check from dfm_synchronize / dfm_check_status.
 static int status_check(dfm_handle* h) {
     if (!h->status_dev) return 0;
@@ -1848,6 +1850,7 @@ static int status_check(dfm_handle* h) {
     if (st & 8) return fail(h, DFM_E_VINTAGE, "news: a cell observed in the old vintage is missing in the new one%s");
     if (st & 1) return fail(h, DFM_E_MISSING, "panel contains NaN but DFM_F_MAY_HAVE_MISSING was not set%s");
     if (st & 16) return fail(h, DFM_E_NUMERIC, "structural identification: Lam[named, :] is singular, or Q is not positive definite where S^-1 is needed%s");
+    if (st & 32) return fail(h, DFM_E_NUMERIC, "filter: a replicate's update met a non-finite value or a matrix that is not positive semi-definite (NaN from that period on)%s");
     if (st & 2) return fail(h, DFM_E_NUMERIC, "PCA subspace iteration did not converge (near-degenerate spectrum at the cut)%s");
     return 0;
 }
@@ -2906,5 +2909,107 @@ int dfm_news_batch(dfm_handle* h, int B, int T, int N, int r, int p, const doubl
     int rc = st.finish(news_run(h, B, T, N, r, p, H, xo_d, xn_d, lam_d, R_d, A_d, Q_d, mu_d, P0_d, mean_d, sd_d, G, target_t, target_i, y_d,
                                 imp_d, news_d, w_d, ll_d, flags));
     if (rc == 0) rc = post_check(h, ll_host.data(), (int)n_ll);
+    return rc;
+}
+
+
+// ---- filtered states, prediction errors and out-of-sample evaluation (filter.hip) -------------------------------------------------
+// One forward pass, outside enqueue_pass: the loadings padded to pad_r(r) columns (pad_params_kernel), collapse_kernel into arrays
+// of h->ft (this one collapse route only), filter_kernel, then filter_fill_kernel and filter_eval_kernel for the outputs the caller
+// takes.  The moments the later kernels read (z_pred / P_pred for the fill, z_filt for the evaluation) live in h->ft when the
+// caller does not take them.  The parameters are the same at every origin.
+static int filter_check(dfm_handle* h, int B, int T, int N, int r, int p, int H, int t0, const double* panel, const double* Lam,
+                        const double* R, const double* Avar, const double* Q, const double* mu0, const double* P0,
+                        const double* mean, const double* sd) {
+    if (int rc = check_dims(h, B, T, N, r)) return rc;
+    if (H < 0) return fail(h, DFM_E_DIMS, "H must be >= 0%s");
+    if (t0 < 0 || t0 >= T) return fail(h, DFM_E_DIMS, "t0 (the first origin) must lie in [0, T)%s");
+    if (p < 1) return fail(h, DFM_E_DIMS, "number of factor lags must be >= 1%s");
+    if (r * p > DFM_MAX_R) return fail(h, DFM_E_R_UNSUPPORTED, "r * p > DFM_MAX_R (32)%s");
+    if (!panel || !Lam || !R || !Avar || !Q || !mu0 || !P0) return fail(h, DFM_E_NULL, "required pointer is NULL%s");
+    if ((mean == nullptr) != (sd == nullptr)) return fail(h, DFM_E_NULL, "mean and sd must both be given or both be NULL%s");
+    return check_general_n(h, N, r);
+}
+
+int dfm_filter_batch_dev(dfm_handle* h, int B, int T, int N, int r, int p, int H, int t0, const double* panel,
+                         const double* Lam, const double* R, const double* Avar, const double* Q, const double* mu0,
+                         const double* P0, const double* mean, const double* sd, double* z_pred, double* P_pred,
+                         double* z_filt, double* P_filt, double* loglik_t, double* xpred, double* verr, double* vstd,
+                         double* msfe, double* msfe0, int* cnt, unsigned flags) {
+    if (int rc = filter_check(h, B, T, N, r, p, H, t0, panel, Lam, R, Avar, Q, mu0, P0, mean, sd)) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const int Rp = pad_r(r), k = r * p;
+    const size_t d = sizeof(double), rr = (size_t)Rp * Rp, npR = (size_t)Rp * (Rp + 1) / 2, kk = (size_t)k * (k + 1) / 2, BT = (size_t)B * T;
+    const bool miss = (flags & DFM_F_MAY_HAVE_MISSING) != 0;
+    const bool fill = xpred || verr || vstd, eval = H > 0 && (msfe || msfe0 || cnt);
+    size_t off = 0;
+    const size_t o_lam = r != Rp ? take(off, (size_t)B * N * Rp * d) : (size_t)-1,
+                 o_pad = r != Rp ? take(off, (3 * B * rr + (size_t)B * Rp) * d) : (size_t)-1,      // pad_params_kernel's other outputs (unused)
+                 o_b = take(off, BT * Rp * d), o_s = take(off, BT * d), o_ld = take(off, BT * d), o_n = take(off, BT * sizeof(int)),
+                 o_ct = miss ? take(off, BT * npR * d) : (size_t)-1, o_cf = take(off, B * rr * d), o_lf = take(off, (size_t)B * d),
+                 o_zp = (!z_pred && fill) ? take(off, BT * k * d) : (size_t)-1,
+                 o_pp = (!P_pred && vstd) ? take(off, BT * kk * d) : (size_t)-1,
+                 o_zf = (!z_filt && eval) ? take(off, BT * k * d) : (size_t)-1,
+                 o_acc = eval ? take(off, (size_t)B * H * N * d) : (size_t)-1, o_acc0 = eval ? take(off, (size_t)B * H * N * d) : (size_t)-1,
+                 o_acn = eval ? take(off, (size_t)B * H * N * sizeof(int)) : (size_t)-1;
+    HIP_TRY(h, h->ft.grow(off));
+    const double* LamP = Lam;
+    if (r != Rp) {
+        double* pad = at<double>(h->ft, o_pad);
+        const size_t n = (size_t)B * N * Rp > B * rr ? (size_t)B * N * Rp : B * rr;
+        ProfScope ps(h, K_PAD);
+        // (A, Q, P0 and mu0 are read as if r wide -- in bounds of the caller's arrays, which are at least that large -- into `pad`)
+        hipLaunchKernelGGL(pad_params_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, B, N, r, Rp, Rp, Lam, Avar, Q,
+                           mu0, P0, at<double>(h->ft, o_lam), pad, pad + B * rr, pad + 3 * B * rr, pad + 2 * B * rr);
+        HIP_TRY(h, hipGetLastError());
+        LamP = at<double>(h->ft, o_lam);
+    }
+    CollapseArgs ca{};
+    ca.B = B; ca.T = T; ca.N = N; ca.panel = panel; ca.Lam = LamP; ca.Rv = R;
+    ca.bcol = at<double>(h->ft, o_b); ca.scol = at<double>(h->ft, o_s); ca.nobs = at<int>(h->ft, o_n); ca.ldrow = at<double>(h->ft, o_ld);
+    ca.Ct = at<double>(h->ft, o_ct); ca.Cfull = at<double>(h->ft, o_cf); ca.ldfull = at<double>(h->ft, o_lf);
+    ca.status = h->status_dev;
+    { ProfScope ps(h, K_COLLAPSE); HIP_TRY(h, launch_collapse(Rp, ca, h->stream)); }
+    FtArgs fa{};
+    fa.B = B; fa.T = T; fa.N = N; fa.r = r; fa.p = p; fa.Rp = Rp; fa.H = H; fa.t0 = t0;
+    fa.panel = panel; fa.Lam = Lam; fa.R = R; fa.A = Avar; fa.Q = Q; fa.mu0 = mu0; fa.P0 = P0; fa.mean = mean; fa.sd = sd;
+    fa.bcol = ca.bcol; fa.scol = ca.scol; fa.nobs = ca.nobs; fa.ldrow = ca.ldrow; fa.Ct = ca.Ct; fa.Cfull = ca.Cfull; fa.ldfull = ca.ldfull;
+    fa.z_pred = z_pred ? z_pred : at<double>(h->ft, o_zp); fa.P_pred = P_pred ? P_pred : at<double>(h->ft, o_pp);
+    fa.z_filt = z_filt ? z_filt : at<double>(h->ft, o_zf); fa.P_filt = P_filt; fa.loglik_t = loglik_t;
+    fa.xpred = xpred; fa.verr = verr; fa.vstd = vstd;
+    fa.msfe = eval ? msfe : nullptr; fa.msfe0 = eval ? msfe0 : nullptr; fa.cnt = eval ? cnt : nullptr;
+    fa.acc = at<double>(h->ft, o_acc); fa.acc0 = at<double>(h->ft, o_acc0); fa.acn = at<int>(h->ft, o_acn);
+    fa.status = h->status_dev;
+    { ProfScope ps(h, K_FT_FILTER); HIP_TRY(h, launch_filter(fa, h->stream)); }
+    if (fill) { ProfScope ps(h, K_FT_FILL); HIP_TRY(h, launch_filter_fill(fa, h->stream)); }
+    if (eval) { ProfScope ps(h, K_FT_EVAL); HIP_TRY(h, launch_filter_eval(fa, h->stream)); }
+    return 0;
+}
+
+int dfm_filter_batch(dfm_handle* h, int B, int T, int N, int r, int p, int H, int t0, const double* panel,
+                     const double* Lam, const double* R, const double* Avar, const double* Q, const double* mu0,
+                     const double* P0, const double* mean, const double* sd, double* z_pred, double* P_pred,
+                     double* z_filt, double* P_filt, double* loglik_t, double* xpred, double* verr, double* vstd,
+                     double* msfe, double* msfe0, int* cnt, unsigned flags) {
+    if (int rc = filter_check(h, B, T, N, r, p, H, t0, panel, Lam, R, Avar, Q, mu0, P0, mean, sd)) return rc;
+    if (int rc = status_epoch(h)) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t k = (size_t)r * p, kk = k * (k + 1) / 2, BT = (size_t)B * T, n_R = (size_t)B * N, n_x = BT * N, n_e = (size_t)B * H * N;
+    if (H == 0) { msfe = nullptr; msfe0 = nullptr; cnt = nullptr; }          // (left untouched)
+    HostStage st(h, 256);
+    double *x_d, *lam_d, *R_d, *A_d, *Q_d, *mu_d, *P0_d, *mean_d, *sd_d, *zp_d, *pp_d, *zf_d, *pf_d, *ll_d, *xp_d, *ve_d, *vs_d, *m_d, *m0_d;
+    int* cnt_d;
+    st.in(panel, n_x, x_d); st.in(Lam, (size_t)B * N * r, lam_d); st.in(R, n_R, R_d); st.in(Avar, (size_t)B * r * k, A_d);
+    st.in(Q, (size_t)B * r * r, Q_d); st.in(mu0, (size_t)B * k, mu_d); st.in(P0, (size_t)B * k * k, P0_d);
+    st.in(mean, mean ? n_R : 0, mean_d); st.in(sd, sd ? n_R : 0, sd_d);
+    st.out(z_pred, z_pred ? BT * k : 0, zp_d); st.out(P_pred, P_pred ? BT * kk : 0, pp_d);
+    st.out(z_filt, z_filt ? BT * k : 0, zf_d); st.out(P_filt, P_filt ? BT * kk : 0, pf_d);
+    st.out(loglik_t, loglik_t ? BT : 0, ll_d);
+    st.out(xpred, xpred ? n_x : 0, xp_d); st.out(verr, verr ? n_x : 0, ve_d); st.out(vstd, vstd ? n_x : 0, vs_d);
+    st.out(msfe, msfe ? n_e : 0, m_d); st.out(msfe0, msfe0 ? n_e : 0, m0_d); st.out(cnt, cnt ? n_e : 0, cnt_d);
+    if (int rc = st.begin()) return rc;
+    int rc = st.finish(dfm_filter_batch_dev(h, B, T, N, r, p, H, t0, x_d, lam_d, R_d, A_d, Q_d, mu_d, P0_d, mean_d, sd_d, zp_d, pp_d, zf_d,
+                                            pf_d, ll_d, xp_d, ve_d, vs_d, m_d, m0_d, cnt_d, flags));
+    if (rc == 0) rc = status_check(h);
     return rc;
 }

@@ -574,6 +574,31 @@ hipError_t launch_sv_shock(const SvArgs& a, hipStream_t s);
 hipError_t launch_sv_path(SvArgs a, hipStream_t s);
 hipError_t launch_sv_hd_fill(SvArgs a, hipStream_t s);
 
+// Filtered states, prediction errors and out-of-sample evaluation (filter.hip).  k = r p, kk = k (k + 1) / 2.
+struct FtArgs {
+    int B, T, N, r, p, Rp, H, t0;                 // Rp: width of the collapse's rows (pad_r(r))
+    const double* panel;                          // [B][T][N] (NaN = missing)
+    const double* Lam; const double* R;           // [B][N][r], [B][N]
+    const double* A; const double* Q;             // [B][r][k] = [A_1 .. A_p], [B][r][r]
+    const double* mu0; const double* P0;          // [B][k], [B][k][k]
+    const double* mean; const double* sd;         // [B][N] or both null
+    // launch_collapse's per-period arrays (CollapseArgs): Ct / ldrow are read only where nobs < N
+    const double* bcol; const double* scol; const int* nobs; const double* ldrow; const double* Ct; const double* Cfull;
+    const double* ldfull;
+    double* z_pred; double* P_pred;               // [B][T][k], [B][T][kk] (the fill reads them: never null when it runs)
+    double* z_filt; double* P_filt;               // [B][T][k] (the evaluation reads it), [B][T][kk] or null
+    double* loglik_t;                             // [B][T] or null
+    double* xpred; double* verr; double* vstd;    // [B][T][N] or null
+    double* msfe; double* msfe0; int* cnt;        // [B][H][N] or null
+    double* acc; double* acc0; int* acn;          // [B][H][N] each: the evaluation's running sums (scratch)
+    int* status;                                  // bit 32: a replicate's update failed
+    CellGeom geo;                                 // geometry of the fill (set by its launcher)
+};
+size_t filter_lds_bytes(int r, int k);            // filter_kernel's LDS
+hipError_t launch_filter(const FtArgs& a, hipStream_t s);
+hipError_t launch_filter_fill(FtArgs a, hipStream_t s);
+hipError_t launch_filter_eval(const FtArgs& a, hipStream_t s);
+
 // Device-side synthetic replicates (synth.hip); all arrays in the caller's layout (r).
 struct SynthArgs {
     int B, T, N, r;

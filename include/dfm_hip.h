@@ -569,6 +569,42 @@ int dfm_chow_batch_dev(dfm_handle* h, int S, int Tmax, int k, const double* y, c
 int dfm_chow_batch(dfm_handle* h, int S, int Tmax, int k, const double* y, const double* X, const int* Tlen,
                    int P, const int* prob_series, const int* prob_break, const int* prob_q, double* chow);
 
+/* --- filtered states, prediction errors and out-of-sample evaluation (csrc/filter.hip) -----------------
+ * dfm_filter_batch: what the model knew at time t.  Model, layouts and conventions are those of dfm_forecast_batch:
+ * x_t = Lam f_t + e_t, f_t = A_1 f_{t-1} + .. + A_p f_{t-p} + eta_t, state z_t = (f_t, .., f_{t-p+1}) of width k = r p <=
+ * DFM_MAX_R, mu0 / P0 the moments of z_0 (the period before panel row 0), NaN = missing cell, mean / sd [B][N] both given or
+ * both NULL.  ONE forward recursion in covariance form (no matrix but the r x r W_t = I + U' C_t U, eigenvalues >= 1, is
+ * factorised: Q, P_pred and C_t may be singular, so DFM_F_SINGULAR_Q is accepted and changes nothing) gives every origin.
+ * THE PARAMETERS ARE HELD FIXED OVER ALL ORIGINS: the evaluation measures the data flow through a given fit, not
+ * re-estimation (a caller who wants that batches expanding windows through dfm_em_batch and passes per-replicate parameters).
+ * Outputs, every one may be NULL (then it is not written, and not computed where nothing else needs it); kk = k (k + 1) / 2:
+ *   z_pred [B][T][k], P_pred [B][T][kk] packed lower   E, Var[z_t | x_0 .. x_{t-1}]
+ *   z_filt [B][T][k], P_filt [B][T][kk]                E, Var[z_t | x_0 .. x_t]
+ *   loglik_t [B][T]   log density of row t's observed cells given the rows before it; 0 for a row without observed cells
+ *   xpred [B][T][N]   mean_i + sd_i lam_i' f_{t|t-1}, on every cell
+ *   verr  [B][T][N]   x_ti - xpred in data units; NaN on a missing cell
+ *   vstd  [B][T][N]   (x_ti - lam_i' f_{t|t-1}) / sqrt(lam_i' P11_{t|t-1} lam_i + R_i) in model units; NaN on a missing cell
+ *   msfe  [B][H][N]   h = 1 .. H: the mean over the origins t = t0 .. T-1-h with x_{t+h,i} observed of
+ *                     sd_i^2 (x_{t+h,i} - lam_i' (M^h z_{t|t})[:r])^2, M the companion matrix; NaN where there is no such origin
+ *   msfe0 [B][H][N]   the same mean of sd_i^2 x_{t+h,i}^2: the unconditional-mean forecast, the benchmark
+ *   cnt   [B][H][N]   int32, the number of origins averaged
+ * H = 0: no evaluation -- msfe, msfe0 and cnt are left untouched whether NULL or not.  H < 0, t0 outside [0, T): DFM_E_DIMS.
+ * N beyond the register tiling of the collapse with missing cells (1024 for r <= 8, 512 for r <= 16, 256 beyond): DFM_E_DIMS.
+ * A NaN in the panel without DFM_F_MAY_HAVE_MISSING: DFM_E_MISSING.  A replicate whose update meets a non-finite value or a
+ * P_pred / W_t that is not positive semi-definite writes NaN from that period on; the outputs are written and the call (the
+ * host-pointer entry; dfm_check_status after the _dev entry) returns DFM_E_NUMERIC.  Sums over origins are taken in a fixed
+ * order: results are bit-identical from run to run. */
+int dfm_filter_batch_dev(dfm_handle* h, int B, int T, int N, int r, int p, int H, int t0, const double* panel,
+                         const double* Lam, const double* R, const double* Avar, const double* Q, const double* mu0,
+                         const double* P0, const double* mean, const double* sd, double* z_pred, double* P_pred,
+                         double* z_filt, double* P_filt, double* loglik_t, double* xpred, double* verr, double* vstd,
+                         double* msfe, double* msfe0, int* cnt, unsigned flags);
+int dfm_filter_batch(dfm_handle* h, int B, int T, int N, int r, int p, int H, int t0, const double* panel,
+                     const double* Lam, const double* R, const double* Avar, const double* Q, const double* mu0,
+                     const double* P0, const double* mean, const double* sd, double* z_pred, double* P_pred,
+                     double* z_filt, double* P_filt, double* loglik_t, double* xpred, double* verr, double* vstd,
+                     double* msfe, double* msfe0, int* cnt, unsigned flags);
+
 /* --- synthetic replicates generated on the device (SURVEY.md §8(d) DGP; no reference
  * counterpart -- the reference has no RNG).  Writes the standardised panel and the DGP parameters
  * rescaled to it.  Counter-based generator keyed by (seed, first_replicate + b). */

@@ -339,6 +339,50 @@ function forecast(h::Handle, z::Matrix{Float64}, params, H::Integer; nlag::Integ
             P = permutedims(P), loglik = ll[1])
 end
 
+# dfm_filter_batch for one replicate (include/dfm_hip.h); the parameters are held fixed over all origins.
+function filter_call(h::Handle, z::Matrix{Float64}, params, H::Integer, t0::Integer; nlag::Integer = 1, mean = nothing, sd = nothing)
+    (mean === nothing) == (sd === nothing) || error("mean and sd go together")
+    T, N = size(z); r = size(params.Lam, 2); k = r * nlag; kk = div(k * (k + 1), 2)
+    Av = hasproperty(params, :Avar) ? params.Avar : params.A
+    panel = to_c_panel(z)
+    Lam = permutedims(params.Lam); R = copy(params.R); AC = permutedims(Av); QC = permutedims(params.Q)
+    mu0 = copy(params.mu0); P0C = permutedims(params.P0)
+    meanC = mean === nothing ? C_NULL : Vector{Float64}(mean); sdC = sd === nothing ? C_NULL : Vector{Float64}(sd)
+    zp = Array{Float64}(undef, k, T); Pp = Array{Float64}(undef, kk, T); zf = Array{Float64}(undef, k, T); Pf = Array{Float64}(undef, kk, T)
+    ll = Array{Float64}(undef, T); xp = Array{Float64}(undef, N, T); ve = Array{Float64}(undef, N, T); vs = Array{Float64}(undef, N, T)
+    ms = Array{Float64}(undef, N, H); m0 = Array{Float64}(undef, N, H); cnt = Array{Cint}(undef, N, H)
+    flags = any(isnan, z) ? DFM_F_MAY_HAVE_MISSING : Cuint(0)
+    GC.@preserve panel Lam R AC QC mu0 P0C meanC sdC zp Pp zf Pf ll xp ve vs ms m0 cnt begin
+        rc = ccall((:dfm_filter_batch, LIB), Cint,
+                   (Ptr{Cvoid}, Cint, Cint, Cint, Cint, Cint, Cint, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                    Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                    Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cint}, Cuint),
+                   h.ptr, 1, T, N, r, nlag, H, t0, panel, Lam, R, AC, QC, mu0, P0C, meanC, sdC, zp, Pp, zf, Pf, ll, xp, ve, vs,
+                   H > 0 ? ms : C_NULL, H > 0 ? m0 : C_NULL, H > 0 ? cnt : C_NULL, flags)
+        check(h.ptr, rc)
+    end
+    return (zp = zp, Pp = Pp, zf = zf, Pf = Pf, ll = ll, xp = xp, ve = ve, vs = vs, ms = ms, m0 = m0, cnt = cnt)
+end
+
+"Predicted and filtered states, per-period log-likelihoods and one-step prediction errors (dfm_filter_batch; include/dfm_hip.h):
+z, params, nlag, mean, sd as `forecast`.  Rows 1..T: state_pred / state_filt (T x r nlag), P_pred / P_filt (packed lower per row),
+loglik_t, x_pred, error (data units) and error_std (NaN on missing cells)."
+function filter_states(h::Handle, z::Matrix{Float64}, params; nlag::Integer = 1, mean = nothing, sd = nothing)
+    o = filter_call(h, z, params, 0, 0; nlag = nlag, mean = mean, sd = sd)
+    return (state_pred = permutedims(o.zp), P_pred = permutedims(o.Pp), state_filt = permutedims(o.zf), P_filt = permutedims(o.Pf),
+            loglik_t = o.ll, x_pred = permutedims(o.xp), error = permutedims(o.ve), error_std = permutedims(o.vs))
+end
+
+"The pseudo-out-of-sample record with the fit held fixed (dfm_filter_batch; include/dfm_hip.h): origins first_origin..T-h (1-based
+rows of z), horizons h = 1..H.  Returns msfe, rmsfe, relative (msfe over the unconditional-mean forecast's) and count, each H x N."
+function evaluate_forecasts(h::Handle, z::Matrix{Float64}, params, H::Integer; first_origin::Integer = div(size(z, 1), 2) + 1,
+                            nlag::Integer = 1, mean = nothing, sd = nothing)
+    H >= 1 || error("H must be >= 1")
+    o = filter_call(h, z, params, H, first_origin - 1; nlag = nlag, mean = mean, sd = sd)
+    msfe = permutedims(o.ms)
+    return (msfe = msfe, rmsfe = sqrt.(msfe), relative = msfe ./ permutedims(o.m0), count = permutedims(o.cnt))
+end
+
 "Identified impulse responses and forecast-error variance shares of every series (dfm_irf_batch; include/dfm_hip.h): params as
 `forecast`; named = r distinct series (1-based; factor k is the common component of series named[k], their order the recursive
 ordering) or nothing (S = chol Q); cumulate = series (1-based) whose responses are cumulated; sd (length N) puts the responses
