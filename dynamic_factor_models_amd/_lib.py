@@ -42,6 +42,8 @@ _VPASS_ARGS = [c_vp, c_int, c_int, c_int, c_int, c_int] + [c_vp] * 10 + [c_uint]
 _VEM_ARGS = [c_vp, c_int, c_int, c_int, c_int, c_int] + [c_vp] * 7 + [c_int, ctypes.c_double] + [c_vp] * 4 + [c_uint]
 _FC_ARGS = [c_vp, c_int, c_int, c_int, c_int, c_int, c_int] + [c_vp] * 15 + [c_uint]
 _SS_ARGS = [c_vp] + [c_int] * 7 + [c_vp] * 9 + [ctypes.c_uint64, ctypes.c_int64, c_vp, c_vp, c_uint]
+_GB_ARGS = ([c_vp] + [c_int] * 5 + [c_vp] * 7 + [ctypes.c_double] * 6 + [c_vp] + [c_int] * 3
+            + [ctypes.c_uint64, ctypes.c_int64] + [c_vp] * 5 + [c_uint])
 _NW_ARGS = [c_vp] + [c_int] * 5 + [c_vp] * 10 + [c_int] + [c_vp] * 6 + [c_uint]
 _IRF_ARGS = [c_vp] + [c_int] * 5 + [c_vp] * 9 + [c_uint]
 _HD_ARGS = [c_vp] + [c_int] * 5 + [c_vp] * 13 + [c_uint]
@@ -100,6 +102,8 @@ SYMBOLS = {
     "dfm_forecast_batch": (c_int, _FC_ARGS),
     "dfm_simsmooth_batch_dev": (c_int, _SS_ARGS),
     "dfm_simsmooth_batch": (c_int, _SS_ARGS),
+    "dfm_gibbs_batch_dev": (c_int, _GB_ARGS),
+    "dfm_gibbs_batch": (c_int, _GB_ARGS),
     "dfm_news_batch_dev": (c_int, _NW_ARGS),
     "dfm_news_batch": (c_int, _NW_ARGS),
     "dfm_irf_batch_dev": (c_int, _IRF_ARGS),

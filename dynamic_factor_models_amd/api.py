@@ -829,6 +829,89 @@ def draw_paths(m: DFMModel, ndraws: int, H: int = 0, *, through: Optional[int] =
     return dict(rows=np.arange(m.initperiod, through + H + 1), cols=cols, factor=factor, x=x)
 
 
+def estimate_bayesian(m: DFMModel, ndraws: int, *, chains: int = 4, burn: int = 500, thin: int = 1, prior=None,
+                      seed: int = 20160415, keep_factors: bool = False, quantiles=None, ctx=None) -> dict:
+    """Bayesian estimation of the parametric model (`estimate(m, Parametric())` first, nfac_o = 0) by the Gibbs sampler of
+    include/dfm_hip.h: `chains` independent chains, all started at m.em_params, run as one batch on the GPU on the standardised
+    estimation window (rows initperiod..lastperiod, the series estimate() used).  Each chain runs `burn` sweeps and then keeps
+    `ndraws` sweeps, one in `thin`.  `prior`: a dict that overrides entries of bayes.default_prior(r) (tau_lam, nu_R, s_R,
+    tau_A, nu_Q, s_Q, A0).  mu0 and P0 stay at their EM values; the VAR block conditions on the first p drawn rows.
+    No rotation or scale normalisation is applied: the common component, R, forecasts and named-factor IRFs are identified,
+    Lam, A and Q one by one are not -- summarise those only through such functions.
+    Returns a dict:
+      params        dict(Lam, R, A, Q, mu0, P0), chains x ndraws flattened on the first axis (chain-major): the layout of
+                    m.replicates["params"], so `m.replicates = dict(params=out["params"])` turns the bands of forecast, draw_paths,
+                    structural_irf, historical_decomposition, news and evaluate_forecasts into posterior bands
+      rows, cols    1-based periods of the window, column indices (0-based) of m.data
+      R_mean [N], common_mean [rows, N]       posterior means in data units (sd_i^2 R_i; mean_i + sd_i lam_i' f_t)
+      quantiles, R_bands [nq, N], common_bands [nq, rows, N]    with `quantiles`
+      rhat_R [N], rhat_common [N]             split-R-hat across the chains of R_i and of the common component of the last period
+      factor        [chains x ndraws, rows, r] with keep_factors
+      prior, chains, ndraws
+    AR idiosyncratic terms and observed factors are refused.  `m` is not modified."""
+    from . import bayes
+    ndraws, chains, burn, thin = int(ndraws), int(chains), int(burn), int(thin)
+    if ndraws < 1 or chains < 1 or burn < 0 or thin < 1:
+        raise ValueError("ndraws >= 1, chains >= 1, burn >= 0 and thin >= 1 are required")
+    if m.em_params is None:
+        raise ValueError("the model has not been estimated: run estimate(m, Parametric()) first")
+    if m.nfac_o != 0:
+        raise ValueError("estimate_bayesian needs nfac_o = 0 (observed factors have no draws here)")
+    qs = None
+    if quantiles is not None:
+        qs = np.atleast_1d(np.asarray(quantiles, dtype=np.float64))
+        if qs.size < 1 or not np.all((qs > 0.0) & (qs <= 1.0)):
+            raise ValueError("quantiles must lie in (0, 1]")
+    ep = m.em_params
+    Lam, R, Q = ep["Lam"], ep["R"], ep["Q"]
+    A = ep["Avar"] if "Avar" in ep else ep["A"]
+    mu0, P0 = ep["mu0"], ep["P0"]
+    r = Lam.shape[1]
+    p = A.shape[1] // r
+    cols, z, mu, sd = _forecast_inputs(m, m.lastperiod)
+    if Lam.shape[0] != cols.size:
+        raise ValueError("m.em_params does not match the model's series (was the model changed after estimate?)")
+    if np.any(np.nan_to_num(np.asarray(m.uar_coef, dtype=np.float64)[cols]) != 0.0):
+        raise ValueError("estimate_bayesian has no AR idiosyncratic terms: the model carries uar_coef (estimate_ar_idio?)")
+    if z.shape[0] <= p:
+        raise ValueError("the window is not longer than the number of factor lags")
+    pr = bayes.check_prior(prior, r, p, chains)
+    n_sweeps = burn + (ndraws - 1) * thin + 1
+    from ._lib import DfmError
+    ctx, own = _own(ctx)
+    try:
+        rep = lambda a: np.ascontiguousarray(np.broadcast_to(a, (chains,) + a.shape))
+        args = (rep(z), rep(Lam), rep(R), rep(A), rep(Q), rep(mu0), rep(P0), pr, n_sweeps)
+        kw = dict(burn=burn, thin=thin, seed=int(seed), keep=("Lam", "R", "A", "Q", "f"), may_have_missing=bool(np.isnan(z).any()))
+        try:
+            _, d = ctx.gibbs_batch_host(*args, **kw)
+        except DfmError as err:                     # the information form inverts Q: as estimate(), retry in covariance form --
+            if err.code != -5 or "Gibbs sampler" in str(err):   # not for the sampler's own failures (a Cholesky of its
+                raise                                           # regressions, the Gamma cap), which that form cannot cure
+            _, d = ctx.gibbs_batch_host(*args, singular_q=True, **kw)
+    finally:
+        if own:
+            ctx.close()
+    flat = lambda a: a.reshape((chains * ndraws,) + a.shape[2:])
+    tile = lambda a: np.ascontiguousarray(np.broadcast_to(a, (chains * ndraws,) + a.shape))
+    params = dict(Lam=flat(d["Lam"]), R=flat(d["R"]), A=flat(d["A"]), Q=flat(d["Q"]), mu0=tile(mu0), P0=tile(P0))
+    Rd = d["R"] * sd ** 2                                               # [chains, ndraws, N], data units
+    last = bayes.common_component(d["Lam"], d["f"], mu, sd, rows=[z.shape[0] - 1])[:, :, 0, :]
+    out = dict(params=params, rows=np.arange(m.initperiod, m.lastperiod + 1), cols=cols, R_mean=Rd.mean(axis=(0, 1)),
+               rhat_R=bayes.split_rhat(Rd), rhat_common=bayes.split_rhat(last), prior=pr, chains=chains, ndraws=ndraws)
+    if qs is None:
+        out["common_mean"] = np.mean([bayes.common_component(d["Lam"][c], d["f"][c], mu, sd).mean(axis=0) for c in range(chains)], axis=0)
+    else:
+        cc = flat(bayes.common_component(d["Lam"], d["f"], mu, sd))
+        out["common_mean"] = cc.mean(axis=0)
+        out["quantiles"] = qs
+        out["R_bands"] = np.quantile(flat(Rd), qs, axis=0)
+        out["common_bands"] = np.quantile(cc, qs, axis=0)
+    if keep_factors:
+        out["factor"] = flat(d["f"])
+    return out
+
+
 def news(m: DFMModel, old, new, targets, *, groups=None, quantiles=None, ctx=None) -> dict:
     """News decomposition of the revision of nowcasts / forecasts between two data vintages (Banbura and Modugno 2014) from the
     parametric fit (`estimate(m, Parametric())`, nfac_o = 0), with one parameter set for both vintages.

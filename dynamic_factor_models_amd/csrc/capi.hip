@@ -159,6 +159,7 @@ struct dfm_handle {
                                            // contribution paths, and the pass outputs the caller does not take
     DevBlock ft;                           // dfm_filter_batch_dev: the padded loadings, the collapse's per-period arrays, the moments the
                                            // caller does not take and the evaluation's running sums
+    DevBlock gb;                           // dfm_gibbs_batch_dev: the sweep's factor path and the shared Gram roots of balanced panels
     std::vector<int> sv_idx;               // host copy of named / cum while their upload is in flight
     const double* odd_panel_src = nullptr; int odd_panel_dims[3] = {0, 0, 0};   // the panel whose padded copy h->odd holds (odd_pad keep_panel)
     std::string prof_file;                 // DFM_PF_PROF_FILE with DFM_SCAN_ABL=256: phase stamps of the fused pass
@@ -171,11 +172,11 @@ struct dfm_handle {
 };
 
 enum KernelId { K_COLLAPSE = 0, K_RECURSION, K_MSTEP_STATS, K_MSTEP_SOLVE, K_PCA, K_SYNTH, K_PAD,
-                K_COLLAPSE_DMA, K_GRAM, K_COV, K_MEANSCAN, K_PFILL, K_COLLAPSE_MFMA, K_ALS, K_OLS, K_BOOT, K_QUANT, K_COLLAPSE_WIDE, K_EM_UPDATE, K_CHOW, K_MSTEP_MFMA, K_GRAM_XX, K_PASS_FUSED, K_FC_TAIL, K_FC_FILL, K_FC_PAD, K_SS_PREP, K_SS_EXPAND, K_SS_PATH, K_SS_DIFF, K_SS_FINISH, K_SS_FILL, K_NW_REVISE, K_NW_GATHER, K_NW_GAMMA, K_NW_COV, K_NW_IMPACT, K_MF_TABLE, K_MF_MOMENTS, K_MF_SOLVE, K_SV_PREP, K_SV_IRF_FILL, K_SV_SHOCK, K_SV_PATH, K_SV_HD_FILL, K_FT_FILTER, K_FT_FILL, K_FT_EVAL, K_COUNT };
+                K_COLLAPSE_DMA, K_GRAM, K_COV, K_MEANSCAN, K_PFILL, K_COLLAPSE_MFMA, K_ALS, K_OLS, K_BOOT, K_QUANT, K_COLLAPSE_WIDE, K_EM_UPDATE, K_CHOW, K_MSTEP_MFMA, K_GRAM_XX, K_PASS_FUSED, K_FC_TAIL, K_FC_FILL, K_FC_PAD, K_SS_PREP, K_SS_EXPAND, K_SS_PATH, K_SS_DIFF, K_SS_FINISH, K_SS_FILL, K_NW_REVISE, K_NW_GATHER, K_NW_GAMMA, K_NW_COV, K_NW_IMPACT, K_MF_TABLE, K_MF_MOMENTS, K_MF_SOLVE, K_SV_PREP, K_SV_IRF_FILL, K_SV_SHOCK, K_SV_PATH, K_SV_HD_FILL, K_FT_FILTER, K_FT_FILL, K_FT_EVAL, K_GB_GRAM, K_GB_LOAD, K_GB_VAR, K_COUNT };
 static const char* const kKernelNames[K_COUNT] = {"collapse_kernel", "recursion_kernel", "mstep_lam_kernel",
                                                   "mstep_solve_kernel", "pca_kernel", "synth_kernel",
                                                   "pad_params_kernel", "collapse_dma_kernel", "gram_kernel",
-                                                  "cov_kernel", "meanscan_kernel", "pfill_kernel", "collapse_mfma_kernel", "als_kernel", "ols_kernel", "var_boot_kernel", "quantile_kernel", "collapse_wide_kernel", "em_update_kernel", "chow_kernel", "mstep_mfma_kernel", "gram_xx_kernel", "pass_fused_kernel", "forecast_tail_kernel", "forecast_fill_kernel", "forecast_pad_kernel", "simsmooth_prep_kernel", "simsmooth_expand_kernel", "simsmooth_path_kernel", "simsmooth_diff_kernel", "simsmooth_finish_kernel", "simsmooth_fill_kernel", "news_revise_kernel", "news_gather_kernel", "news_gamma_kernel", "news_cov_panel_kernel", "news_impact_kernel", "mf_table_kernel", "mf_moments_kernel", "mf_solve_kernel", "sv_prep_kernel", "sv_irf_fill_kernel", "sv_shock_kernel", "sv_path_kernel", "sv_hd_fill_kernel", "filter_kernel", "filter_fill_kernel", "filter_eval_kernel"};
+                                                  "cov_kernel", "meanscan_kernel", "pfill_kernel", "collapse_mfma_kernel", "als_kernel", "ols_kernel", "var_boot_kernel", "quantile_kernel", "collapse_wide_kernel", "em_update_kernel", "chow_kernel", "mstep_mfma_kernel", "gram_xx_kernel", "pass_fused_kernel", "forecast_tail_kernel", "forecast_fill_kernel", "forecast_pad_kernel", "simsmooth_prep_kernel", "simsmooth_expand_kernel", "simsmooth_path_kernel", "simsmooth_diff_kernel", "simsmooth_finish_kernel", "simsmooth_fill_kernel", "news_revise_kernel", "news_gather_kernel", "news_gamma_kernel", "news_cov_panel_kernel", "news_impact_kernel", "mf_table_kernel", "mf_moments_kernel", "mf_solve_kernel", "sv_prep_kernel", "sv_irf_fill_kernel", "sv_shock_kernel", "sv_path_kernel", "sv_hd_fill_kernel", "filter_kernel", "filter_fill_kernel", "filter_eval_kernel", "gibbs_gram_kernel", "gibbs_load_kernel", "gibbs_var_kernel"};
 
 namespace dfm { int handle_device(const dfm_handle* h) { return h->device; } }   // (probe.hip)
 
@@ -1680,7 +1681,7 @@ int dfm_destroy(dfm_handle* h) {
     for (auto e : h->ev_sub) hipEventDestroy(e);
     if (h->ev_fork) hipEventDestroy(h->ev_fork);
     if (h->ev_join) hipEventDestroy(h->ev_join);
-    for (DevBlock* b : {&h->ws, &h->odd, &h->fc, &h->ss, &h->nw, &h->sv, &h->ft}) b->release();
+    for (DevBlock* b : {&h->ws, &h->odd, &h->fc, &h->ss, &h->nw, &h->sv, &h->ft, &h->gb}) b->release();
     if (h->status_dev) hipFree(h->status_dev);
     if (h->own_stream && h->stream) hipStreamDestroy(h->stream);
     delete h;
@@ -1851,6 +1852,7 @@ static int status_check(dfm_handle* h) {
     if (st & 1) return fail(h, DFM_E_MISSING, "panel contains NaN but DFM_F_MAY_HAVE_MISSING was not set%s");
     if (st & 16) return fail(h, DFM_E_NUMERIC, "structural identification: Lam[named, :] is singular, or Q is not positive definite where S^-1 is needed%s");
     if (st & 32) return fail(h, DFM_E_NUMERIC, "filter: a replicate's update met a non-finite value or a matrix that is not positive semi-definite (NaN from that period on)%s");
+    if (st & 64) return fail(h, DFM_E_NUMERIC, "Gibbs sampler: a Cholesky factorisation failed or a Gamma draw was rejected 32 times%s");
     if (st & 2) return fail(h, DFM_E_NUMERIC, "PCA subspace iteration did not converge (near-degenerate spectrum at the cut)%s");
     return 0;
 }
@@ -2614,6 +2616,103 @@ int dfm_simsmooth_batch(dfm_handle* h, int B, int D, int T, int N, int r, int p,
     int rc = st.finish(simsmooth_run(h, B, D, T, N, r, p, H, x_d, lam_d, R_d, A_d, Q_d, mu_d, P0_d, mean_d, sd_d, seed, first_draw, f_d,
                                      xo_d, ll_d, flags));
     if (rc == 0) rc = post_check(h, ll_host.data(), (int)BD);
+    return rc;
+}
+
+
+// ---- Bayesian estimation: the Gibbs sampler (gibbs.hip) ------------------------------------------------------------------------
+// Sweep j: the factor path of every chain by dfm_simsmooth_batch_dev (D = 1, H = 0, first_draw = first_sweep + j) into h->gb, then
+// lam_i, R_i | f and A, Q | f in place in the caller's state.  Nothing waits between the sweeps; kept sweeps are copied behind the
+// sweep in stream order.
+static int gibbs_kept(int n_sweeps, int burn, int thin) { return n_sweeps > burn ? (n_sweeps - burn + thin - 1) / thin : 0; }
+
+static int gibbs_check(dfm_handle* h, int B, int T, int N, int r, int p, const double* panel, const double* mu0, const double* P0,
+                       const double* Lam, const double* R, const double* Avar, const double* Q, double tau_lam, double nu_R,
+                       double s_R, double tau_A, double nu_Q, double s_Q, int n_sweeps, int burn, int thin) {
+    if (int rc = check_dims(h, B, T, N, r)) return rc;
+    if (p < 1) return fail(h, DFM_E_DIMS, "number of factor lags must be >= 1%s");
+    if (r * p > DFM_MAX_R) return fail(h, DFM_E_R_UNSUPPORTED, "r * p > DFM_MAX_R (32)%s");
+    if (T <= p) return fail(h, DFM_E_DIMS, "T must be > p (the VAR block conditions on the first p drawn rows)%s");
+    if (n_sweeps < 1 || thin < 1 || burn < 0) return fail(h, DFM_E_DIMS, "n_sweeps >= 1, thin >= 1 and burn >= 0 are required%s");
+    if (!(tau_lam > 0.0) || !(nu_R >= 2.0) || !(s_R > 0.0) || !(tau_A > 0.0) || !(nu_Q >= (double)r + 1.0) || !(s_Q > 0.0))
+        return fail(h, DFM_E_DIMS, "prior: tau_lam, s_R, tau_A, s_Q > 0, nu_R >= 2 and nu_Q >= r + 1 are required%s");
+    if (!panel || !mu0 || !P0 || !Lam || !R || !Avar || !Q) return fail(h, DFM_E_NULL, "required pointer is NULL%s");
+    return 0;
+}
+
+int dfm_gibbs_batch_dev(dfm_handle* h, int B, int T, int N, int r, int p, const double* panel, const double* mu0, const double* P0,
+                        double* Lam, double* R, double* Avar, double* Q, double tau_lam, double nu_R, double s_R, double tau_A,
+                        double nu_Q, double s_Q, const double* A0, int n_sweeps, int burn, int thin, uint64_t seed,
+                        int64_t first_sweep, double* Lam_draw, double* R_draw, double* A_draw, double* Q_draw, double* f_draw,
+                        unsigned flags) {
+    if (int rc = gibbs_check(h, B, T, N, r, p, panel, mu0, P0, Lam, R, Avar, Q, tau_lam, nu_R, s_R, tau_A, nu_Q, s_Q, n_sweeps, burn,
+                             thin)) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t d = sizeof(double), k = (size_t)r * p;
+    const bool missing = (flags & DFM_F_MAY_HAVE_MISSING) != 0;
+    size_t off = 0;
+    const size_t o_f = take(off, (size_t)B * T * r * d), o_L = missing ? (size_t)-1 : take(off, (size_t)B * r * r * d);
+    HIP_TRY(h, h->gb.grow(off));
+    GbArgs a{};
+    a.B = B; a.T = T; a.N = N; a.r = r; a.p = p;
+    a.panel = panel; a.f = at<double>(h->gb, o_f); a.Lam = Lam; a.R = R; a.A = Avar; a.Q = Q; a.A0 = A0;
+    a.tau_lam = tau_lam; a.nu_R = nu_R; a.s_R = s_R; a.tau_A = tau_A; a.nu_Q = nu_Q; a.s_Q = s_Q;
+    a.seed = seed; a.missing = missing; a.Lsh = at<double>(h->gb, o_L); a.status = h->status_dev;
+    double* f = at<double>(h->gb, o_f);
+    const size_t K = (size_t)gibbs_kept(n_sweeps, burn, thin);
+    auto keep = [&](double* dst, const double* src, size_t per, size_t kk) {   // dst [B][K][per] <- src [B][per]
+        return dst ? hipMemcpy2DAsync(dst + kk * per, K * per * d, src, per * d, per * d, (size_t)B, hipMemcpyDeviceToDevice, h->stream)
+                   : hipSuccess;
+    };
+    for (int j = 0; j < n_sweeps; ++j) {
+        a.sweep = first_sweep + j;
+        if (int rc = dfm_simsmooth_batch_dev(h, B, 1, T, N, r, p, 0, panel, Lam, R, Avar, Q, mu0, P0, nullptr, nullptr, seed, a.sweep, f,
+                                             nullptr, flags)) return rc;
+        if (!missing) {
+            ProfScope ps(h, K_GB_GRAM);
+            HIP_TRY(h, launch_gibbs_gram(a, h->stream));
+        }
+        {
+            ProfScope ps(h, K_GB_LOAD);
+            HIP_TRY(h, launch_gibbs_load(a, h->stream));
+        }
+        {
+            ProfScope ps(h, K_GB_VAR);
+            HIP_TRY(h, launch_gibbs_var(a, h->stream));
+        }
+        if (j >= burn && (j - burn) % thin == 0) {
+            const size_t kk = (size_t)(j - burn) / thin;
+            HIP_TRY(h, keep(Lam_draw, Lam, (size_t)N * r, kk));
+            HIP_TRY(h, keep(R_draw, R, (size_t)N, kk));
+            HIP_TRY(h, keep(A_draw, Avar, (size_t)r * k, kk));
+            HIP_TRY(h, keep(Q_draw, Q, (size_t)r * r, kk));
+            HIP_TRY(h, keep(f_draw, f, (size_t)T * r, kk));
+        }
+    }
+    return 0;
+}
+
+int dfm_gibbs_batch(dfm_handle* h, int B, int T, int N, int r, int p, const double* panel, const double* mu0, const double* P0,
+                    double* Lam, double* R, double* Avar, double* Q, double tau_lam, double nu_R, double s_R, double tau_A,
+                    double nu_Q, double s_Q, const double* A0, int n_sweeps, int burn, int thin, uint64_t seed, int64_t first_sweep,
+                    double* Lam_draw, double* R_draw, double* A_draw, double* Q_draw, double* f_draw, unsigned flags) {
+    if (int rc = gibbs_check(h, B, T, N, r, p, panel, mu0, P0, Lam, R, Avar, Q, tau_lam, nu_R, s_R, tau_A, nu_Q, s_Q, n_sweeps, burn,
+                             thin)) return rc;
+    if (int rc = status_epoch(h)) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t k = (size_t)r * p, BK = (size_t)B * gibbs_kept(n_sweeps, burn, thin);
+    HostStage st(h, 256);
+    double *x_d, *mu_d, *P0_d, *lam_d, *R_d, *A_d, *Q_d, *A0_d, *ld_d, *rd_d, *ad_d, *qd_d, *fd_d;
+    st.in(panel, (size_t)B * T * N, x_d); st.in(mu0, (size_t)B * k, mu_d); st.in(P0, (size_t)B * k * k, P0_d);
+    st.inout(Lam, (size_t)B * N * r, lam_d); st.inout(R, (size_t)B * N, R_d); st.inout(Avar, (size_t)B * r * k, A_d);
+    st.inout(Q, (size_t)B * r * r, Q_d); st.in(A0, A0 ? (size_t)B * r * k : 0, A0_d);
+    st.out(Lam_draw, Lam_draw ? BK * N * r : 0, ld_d); st.out(R_draw, R_draw ? BK * N : 0, rd_d);
+    st.out(A_draw, A_draw ? BK * r * k : 0, ad_d); st.out(Q_draw, Q_draw ? BK * r * r : 0, qd_d);
+    st.out(f_draw, f_draw ? BK * T * r : 0, fd_d);
+    if (int rc = st.begin()) return rc;
+    int rc = st.finish(dfm_gibbs_batch_dev(h, B, T, N, r, p, x_d, mu_d, P0_d, lam_d, R_d, A_d, Q_d, tau_lam, nu_R, s_R, tau_A, nu_Q, s_Q,
+                                           A0_d, n_sweeps, burn, thin, seed, first_sweep, ld_d, rd_d, ad_d, qd_d, fd_d, flags));
+    if (rc == 0) rc = status_check(h);
     return rc;
 }
 

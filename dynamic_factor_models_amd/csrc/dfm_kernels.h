@@ -599,6 +599,24 @@ hipError_t launch_filter(const FtArgs& a, hipStream_t s);
 hipError_t launch_filter_fill(FtArgs a, hipStream_t s);
 hipError_t launch_filter_eval(const FtArgs& a, hipStream_t s);
 
+// One Gibbs sweep's parameter block "parameters | factor path" (gibbs.hip); chain b of B, the key of sweep `sweep`.
+struct GbArgs {
+    int B, T, N, r, p;
+    const double* panel;                          // [B][T][N] (NaN = missing)
+    const double* f;                              // [B][T][r]: the sweep's factor path
+    double* Lam; double* R;                       // [B][N][r], [B][N]: written by gibbs_load_kernel
+    double* A; double* Q;                         // [B][r][r p], [B][r][r]: written by gibbs_var_kernel
+    const double* A0;                             // [B][r][r p] prior mean of the VAR coefficients, or null (zero)
+    double tau_lam, nu_R, s_R, tau_A, nu_Q, s_Q;
+    uint64_t seed; int64_t sweep;
+    bool missing;                                 // DFM_F_MAY_HAVE_MISSING: a Gram matrix per series; else one per chain (Lsh)
+    double* Lsh;                                  // [B][r][r]: root of tau_lam I + F'F (gibbs_gram_kernel; balanced panels)
+    int* status;                                  // bit 64: a Cholesky failed or the gamma sampler ran into its cap
+};
+hipError_t launch_gibbs_gram(const GbArgs& a, hipStream_t s);
+hipError_t launch_gibbs_load(const GbArgs& a, hipStream_t s);
+hipError_t launch_gibbs_var(const GbArgs& a, hipStream_t s);
+
 // Device-side synthetic replicates (synth.hip); all arrays in the caller's layout (r).
 struct SynthArgs {
     int B, T, N, r;

@@ -304,6 +304,50 @@ int dfm_simsmooth_batch(dfm_handle* h, int B, int D, int T, int N, int r, int p,
                         const double* mu0, const double* P0, const double* mean, const double* sd,
                         uint64_t seed, int64_t first_draw, double* f_draw, double* x_draw, unsigned flags);
 
+/* --- Bayesian estimation: a batched Gibbs sampler ---------------------------------------------------------------------------
+ * The model, shapes and flags of dfm_simsmooth_batch (x_t = Lam f_t + e_t, e ~ N(0, diag R); VAR(p) factors with innovation
+ * covariance Q; NaN = missing; r p <= DFM_MAX_R); B independent chains.  mu0 [B][r p] and P0 [B][r p][r p] are inputs and stay
+ * fixed; the VAR block conditions on the first p drawn rows.  No stationarity truncation and no rotation or scale normalisation
+ * is applied: the posterior is proper through the priors, and the common component Lam f, R, forecasts and named-factor IRFs
+ * are well defined without one; Lam, A and Q individually are not identified.
+ * Priors (scalars per call, except A0 [B][r][r p], NULL = 0): lam_i | R_i ~ N(0, R_i / tau_lam I); R_i ~ IG(nu_R / 2, nu_R s_R / 2);
+ * vec(A') | Q ~ N(vec(A0'), Q (x) I / tau_A); Q ~ IW(s_Q I, nu_Q).  tau_lam, s_R, tau_A, s_Q > 0, nu_R >= 2, nu_Q >= r + 1.
+ * Lam [B][N][r], R [B][N], Avar [B][r][r p], Q [B][r][r] are the chain state: the start on entry, the state after the last sweep
+ * on return.  Sweep j = 0 .. n_sweeps-1 of chain b, key = seed ^ (0x9E3779B97F4A7C15 * (first_sweep + j + 1)), stream word 16 b + s:
+ *   1. f_1 .. f_T | X, state: dfm_simsmooth_batch_dev with D = 1, H = 0, first_draw = first_sweep + j (streams 1-4)
+ *   2. for series i over its observed rows O_i (n_i of them): S = tau_lam I + sum f f' = L L', m = S^-1 sum f x,
+ *      R_i = (nu_R s_R + sum x^2 - m' S m) / 2 / g, g ~ Gamma((nu_R + n_i) / 2, 1) from stream 6 (item i of N);
+ *      lam_i = m + sqrt(R_i) L^-T n, n = r normals of stream 5: idx = i ceil(r / 2) + k / 2, component k mod 2.  n_i = 0: the prior.
+ *   3. Y = rows p .. T-1 of f, Z their p lags (n = T - p rows): S = tau_A I + Z'Z = L L', M = S^-1 (tau_A A0' + Z'Y),
+ *      Psi = s_Q I + Y'Y + tau_A A0 A0' - M' S M = C C'; B_T lower triangular with B_T[j][j] = sqrt(2 Gamma((nu_Q + n - j) / 2))
+ *      from stream 9 (item j of r) and, below the diagonal, normals of stream 8: entry (j, c), c < j, is component e mod 2 of idx e / 2,
+ *      e = j (j - 1) / 2 + c;  G = C B_T^-T, Q = G G';  A' = M + L^-T E G', E [r p][r] normals of stream 7: idx = row ceil(r / 2) + k / 2.
+ * Gamma(a, 1), a >= 1, by Marsaglia and Tsang (2000): attempt k = 0, 1, .. of item i of n_items uses m = k n_items + i:
+ * z = first normal of the pair at idx 2 m, u = the 53-bit uniform at idx 2 m + 1 (as dfm_synth_panels_dev's R), d = a - 1/3,
+ * c = 1 / sqrt(9 d), v = (1 + c z)^3; accepted when v > 0 and log u < z^2 / 2 + d - d v + d log v; the draw is d v.  32 rejected
+ * attempts raise a status bit (DFM_E_NUMERIC), as does a failed Cholesky (every Cholesky of the sampler fails on a pivot
+ * <= 1e-12 trace, the rule of dfm_simsmooth_batch's roots, with or without DFM_F_MAY_HAVE_MISSING); a draw whose Cholesky failed leaves that part of the
+ * chain's state (lam_i and R_i of the series; A and Q) as it was, so a failure does not turn into NaN cells of later sweeps.
+ * Sweep j is kept when j >= burn and (j - burn) % thin == 0; K kept sweeps go to Lam_draw [B][K][N][r], R_draw [B][K][N],
+ * A_draw [B][K][r][r p], Q_draw [B][K][r][r], f_draw [B][K][T][r] (each may be NULL).  A call of n sweeps with first_sweep = k from
+ * the state k sweeps left equals the tail of one call of k + n sweeps bit for bit, and two runs agree bit for bit (no atomics
+ * on floating point).  Status: n_sweeps < 1, thin < 1, burn < 0, T <= p or a prior outside its condition: DFM_E_DIMS; a NULL
+ * panel, mu0, P0 or state: DFM_E_NULL; a shape the pass refuses: its status; a NaN panel without DFM_F_MAY_HAVE_MISSING:
+ * DFM_E_MISSING, a failed Cholesky or the gamma cap: DFM_E_NUMERIC (status-word bits: the host entry reports them,
+ * dfm_check_status after the "_dev" entry).  The sweeps are enqueued on the handle's stream without a wait between them.
+ * Allocates in the handle (kept for the next call): one [B][T][r] factor path and [B][r][r] roots, beside what
+ * dfm_simsmooth_batch_dev keeps. */
+int dfm_gibbs_batch_dev(dfm_handle* h, int B, int T, int N, int r, int p, const double* panel, const double* mu0,
+                        const double* P0, double* Lam, double* R, double* Avar, double* Q, double tau_lam, double nu_R,
+                        double s_R, double tau_A, double nu_Q, double s_Q, const double* A0, int n_sweeps, int burn, int thin,
+                        uint64_t seed, int64_t first_sweep, double* Lam_draw, double* R_draw, double* A_draw, double* Q_draw,
+                        double* f_draw, unsigned flags);
+int dfm_gibbs_batch(dfm_handle* h, int B, int T, int N, int r, int p, const double* panel, const double* mu0,
+                    const double* P0, double* Lam, double* R, double* Avar, double* Q, double tau_lam, double nu_R,
+                    double s_R, double tau_A, double nu_Q, double s_Q, const double* A0, int n_sweeps, int burn, int thin,
+                    uint64_t seed, int64_t first_sweep, double* Lam_draw, double* R_draw, double* A_draw, double* Q_draw,
+                    double* f_draw, unsigned flags);
+
 /* --- news decomposition of nowcast revisions (Banbura and Modugno 2014) -------------------------------------------------------
  * The model and conventions of dfm_forecast_batch; two vintages old / new [B][T][N] of the same standardised panel (a period the
  * old vintage did not have is all-NaN there).  Omega_old, Omega_new = their observed cells; Omega_old must be a subset of

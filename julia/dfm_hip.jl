@@ -463,6 +463,41 @@ function draw_paths(h::Handle, z::Matrix{Float64}, params, ndraws::Integer, H::I
     return (factor = permutedims(f, (3, 2, 1)), x = permutedims(x, (3, 2, 1)))
 end
 
+"Bayesian estimation by the Gibbs sampler (dfm_gibbs_batch; include/dfm_hip.h): z, params, nlag as `forecast`; `chains` chains
+start at params, run `burn` sweeps and keep `ndraws` sweeps each, one in `thin`.  prior = (tau_lam, nu_R, s_R, tau_A, nu_Q, s_Q)
+with A0 (r x r nlag, the prior mean of [A_1 .. A_p]) or nothing for zero.  mu0 and P0 stay fixed.  Returns the kept draws with
+chains x ndraws on the first axis (chain-major): Lam (. x N x r), R (. x N), A (. x r x r nlag), Q (. x r x r), factor (. x T x r).
+Lam, A and Q are not identified one by one (no rotation or scale normalisation): use them through the common component,
+forecasts or named-factor IRFs."
+function estimate_bayesian(h::Handle, z::Matrix{Float64}, params, ndraws::Integer; nlag::Integer = 1, chains::Integer = 4,
+                           burn::Integer = 500, thin::Integer = 1, seed::Integer = 20160415, first_sweep::Integer = 0,
+                           prior = (tau_lam = 1.0, nu_R = 4.0, s_R = 0.25, tau_A = 1.0, nu_Q = size(params.Lam, 2) + 2.0, s_Q = 0.5),
+                           A0 = nothing, singular_q::Bool = false)
+    T, N = size(z); r = size(params.Lam, 2); k = r * nlag; B = Int(chains); K = Int(ndraws)
+    Av = hasproperty(params, :Avar) ? params.Avar : params.A
+    rep(a) = repeat(a, outer = (ntuple(_ -> 1, ndims(a))..., B))
+    panel = rep(to_c_panel(z)[:, :, 1])
+    Lam = rep(permutedims(params.Lam)); R = rep(copy(params.R)); AC = rep(permutedims(Av)); QC = rep(permutedims(params.Q))
+    mu0 = rep(copy(params.mu0)); P0C = rep(permutedims(params.P0))
+    A0C = A0 === nothing ? C_NULL : rep(permutedims(Matrix{Float64}(A0)))
+    n_sweeps = burn + (K - 1) * thin + 1
+    Ld = Array{Float64}(undef, r, N, K, B); Rd = Array{Float64}(undef, N, K, B); Ad = Array{Float64}(undef, k, r, K, B)
+    Qd = Array{Float64}(undef, r, r, K, B); fd = Array{Float64}(undef, r, T, K, B)
+    flags = (any(isnan, z) ? DFM_F_MAY_HAVE_MISSING : Cuint(0)) | (singular_q ? DFM_F_SINGULAR_Q : Cuint(0))
+    GC.@preserve panel Lam R AC QC mu0 P0C A0C Ld Rd Ad Qd fd begin
+        rc = ccall((:dfm_gibbs_batch, LIB), Cint,
+                   (Ptr{Cvoid}, Cint, Cint, Cint, Cint, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                    Ptr{Float64}, Ptr{Float64}, Cdouble, Cdouble, Cdouble, Cdouble, Cdouble, Cdouble, Ptr{Float64}, Cint, Cint,
+                    Cint, UInt64, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cuint),
+                   h.ptr, B, T, N, r, nlag, panel, mu0, P0C, Lam, R, AC, QC, prior.tau_lam, prior.nu_R, prior.s_R, prior.tau_A,
+                   prior.nu_Q, prior.s_Q, A0C, n_sweeps, burn, thin, UInt64(seed), Int64(first_sweep), Ld, Rd, Ad, Qd, fd, flags)
+        check(h.ptr, rc)
+    end
+    flat(a, perm) = (p = permutedims(a, perm); reshape(permutedims(p, (2, 1, 3:ndims(p)...)), :, size(p)[3:end]...))
+    return (Lam = flat(Ld, (4, 3, 2, 1)), R = flat(Rd, (3, 2, 1)), A = flat(Ad, (4, 3, 2, 1)), Q = flat(Qd, (4, 3, 2, 1)),
+            factor = flat(fd, (4, 3, 2, 1)))
+end
+
 "News decomposition of the revision of G target cells between two vintages (dfm_news_batch; include/dfm_hip.h): zold / znew
 are T x N (NaN = missing, standardised; every cell of zold observed in znew), params, nlag, mean / sd as `forecast`; targets =
 G (row, column) pairs, 1-based, rows past T are forecasts.  Returns yhat (3 x G: old, revised old, new), impact (G x N), news
