@@ -46,6 +46,8 @@ _GB_ARGS = ([c_vp] + [c_int] * 5 + [c_vp] * 7 + [ctypes.c_double] * 6 + [c_vp] +
             + [ctypes.c_uint64, ctypes.c_int64] + [c_vp] * 5 + [c_uint])
 _NW_ARGS = [c_vp] + [c_int] * 5 + [c_vp] * 10 + [c_int] + [c_vp] * 6 + [c_uint]
 _IRF_ARGS = [c_vp] + [c_int] * 5 + [c_vp] * 9 + [c_uint]
+_SG_ARGS = ([c_vp] + [c_int] * 5 + [c_vp] * 7 + [c_int, c_vp, c_int, c_int, ctypes.c_uint64, ctypes.c_int64] + [c_vp] * 6
+            + [c_uint])
 _HD_ARGS = [c_vp] + [c_int] * 5 + [c_vp] * 13 + [c_uint]
 _FT_ARGS = [c_vp] + [c_int] * 7 + [c_vp] * 20 + [c_uint]
 _ARPASS_ARGS = [c_vp, c_int, c_int, c_int, c_int, c_int, c_int] + [c_vp] * 11 + [c_uint]
@@ -108,6 +110,8 @@ SYMBOLS = {
     "dfm_news_batch": (c_int, _NW_ARGS),
     "dfm_irf_batch_dev": (c_int, _IRF_ARGS),
     "dfm_irf_batch": (c_int, _IRF_ARGS),
+    "dfm_signirf_batch_dev": (c_int, _SG_ARGS),
+    "dfm_signirf_batch": (c_int, _SG_ARGS),
     "dfm_histdecomp_batch_dev": (c_int, _HD_ARGS),
     "dfm_histdecomp_batch": (c_int, _HD_ARGS),
     "dfm_filter_batch_dev": (c_int, _FT_ARGS),

@@ -714,6 +714,115 @@ def structural_irf(m: DFMModel, H: int, *, named=None, cumulate=None, unit_effec
     return out
 
 
+def structural_irf_signs(m: DFMModel, H: int, restrictions, *, candidates: int = 1000, keep: Optional[int] = None, named=None,
+                         cumulate=None, fevd: bool = False, quantiles=None, seed: int = 20160415, ctx=None) -> dict:
+    """Impulse responses identified by sign restrictions, from the parametric fit (`estimate(m, Parametric())`, nfac_o = 0);
+    definitions in include/dfm_hip.h (dfm_signirf_batch).  `candidates` rotations of the base impact matrix (chol(Q), or the
+    named-factor one with `named`) are drawn uniformly on the GPU; those whose responses carry the required signs are accepted.
+
+    `restrictions`: rows (series, shock, h0, h1, sign): the response of column `series` of m.data to shock `shock` (0-based) is
+    positive (sign = 1) or negative (sign = -1) at every horizon h0..h1 (0 = impact), cumulated responses for the series in
+    `cumulate`.  A shock column all of whose rows hold with the signs reversed is flipped, so a shock is identified up to what the
+    restrictions say and no further.  `keep`: how many accepted draws to return (default: all of them; the candidate stream is a
+    pure function of `seed`, so a second call over the same candidates is exact).  Returns a dict:
+      cols             column indices of m.data: the series estimate() used
+      irf              [n_kept, len(cols), H, r] in data units (draw, series, horizon, shock)
+      fevd             [n_kept, len(cols), H, r + 1] or None
+      impact           [n_kept, r, r] the impact matrices S Rot D of the kept draws
+      accepted_share   accepted candidates / candidates
+      candidates_used  the number of candidates drawn; candidate_index [n_kept]: which of them the kept draws are
+    `quantiles` (needs m.replicates -- bootstrap replicates or Gibbs draws -- and named, as structural_irf): one batched call runs
+    `candidates` rotations on every replicate's parameters and keeps `keep or 1` draws of each; the pointwise bands
+    [nq, len(cols), H, r] over the pooled kept draws come from dfm_quantile_bands; replicates_without_a_draw counts the replicates
+    none of whose candidates was accepted.  No accepted draw at all raises ValueError.  Zero and narrative restrictions,
+    AR-idiosyncratic and mixed-frequency fits are out of scope.  `m` is not modified."""
+    H, M = int(H), int(candidates)
+    if H < 1:
+        raise ValueError("H must be >= 1")
+    if M < 1:
+        raise ValueError("candidates must be >= 1")
+    if keep is not None and int(keep) < 1:
+        raise ValueError("keep must be >= 1")
+    _structural_checks(m)
+    qs = None
+    if quantiles is not None:
+        if named is None:
+            raise ValueError("quantile bands need named series: the replicates are not in a common rotation otherwise")
+        if getattr(m, "replicates", None) is None:
+            raise ValueError("quantile bands need bootstrap replicates: estimate(m, Parametric(), nrep=...) first")
+        qs = np.atleast_1d(np.asarray(quantiles, dtype=np.float64))
+        if qs.size < 1 or not np.all((qs > 0.0) & (qs <= 1.0)):
+            raise ValueError("quantiles must lie in (0, 1]")
+    ep = m.em_params
+    Lam, R, Q = ep["Lam"], ep["R"], ep["Q"]
+    A = ep["Avar"] if "Avar" in ep else ep["A"]
+    N, r = Lam.shape
+    cols, _, _, sd = _forecast_inputs(m, m.lastperiod)
+    if N != cols.size:
+        raise ValueError("m.em_params does not match the model's series (was the model changed after estimate?)")
+    nm = None if named is None else _to_cols(named, cols, "named")
+    if nm is not None and (nm.size != r or np.unique(nm).size != r):
+        raise ValueError(f"named must be {r} distinct series")
+    cum = None
+    if cumulate is not None:
+        cum = np.zeros(N, dtype=np.int32)
+        cum[_to_cols(cumulate, cols, "cumulate")] = 1
+    rs = np.asarray(restrictions, dtype=np.int64)
+    if rs.size == 0:
+        rs = rs.reshape(0, 5)
+    if rs.ndim != 2 or rs.shape[1] != 5:
+        raise ValueError("restrictions must be (series, shock, h0, h1, sign) rows")
+    rs = rs.copy()
+    if rs.shape[0]:
+        rs[:, 0] = _to_cols(rs[:, 0], cols, "restrictions")
+        if np.any(rs[:, 1] < 0) or np.any(rs[:, 1] >= r):
+            raise ValueError(f"restrictions: the shock must lie in 0..{r - 1}")
+        if np.any(rs[:, 2] < 0) or np.any(rs[:, 3] < rs[:, 2]) or np.any(rs[:, 3] >= H):
+            raise ValueError(f"restrictions: need 0 <= h0 <= h1 < H = {H}")
+        if np.any(np.abs(rs[:, 4]) != 1):
+            raise ValueError("restrictions: the sign must be +1 or -1")
+    ctx, own = _own(ctx)
+    try:
+        def run(Lb, Ab, Qb, Rb, K, want_S, want_irf, want_fevd):
+            B = Lb.shape[0]
+            sdb = np.ascontiguousarray(np.broadcast_to(sd, (B, N)))
+            return ctx.signirf_batch_host(Lb, Ab, Qb, Rb, H, rs, M, K, seed=seed, sd=sdb, named=nm, cum=cum, want_S=want_S,
+                                          want_irf=want_irf, want_fevd=want_fevd)
+        none = "no candidate satisfied the restrictions: accepted share 0 of {} candidates{}"
+        if keep is None:                                  # count first, then keep them all: the same candidates, exactly
+            n = int(run(Lam[None], A[None], Q[None], R[None], 1, False, False, False)["n_accept"][0])
+            if n == 0:
+                raise ValueError(none.format(M, ""))
+            o = run(Lam[None], A[None], Q[None], R[None], n, True, True, fevd)
+        else:
+            o = run(Lam[None], A[None], Q[None], R[None], int(keep), True, True, fevd)
+            n = int(o["n_accept"][0])
+            if n == 0:
+                raise ValueError(none.format(M, ""))
+        nk = min(n, o["cand"].shape[1])
+        bands = without = None
+        if qs is not None:
+            rp = m.replicates["params"]
+            ob = run(rp["Lam"], rp["A"], rp["Q"], rp["R"], int(keep) if keep is not None else 1, False, True, False)
+            got = ob["cand"] >= 0
+            if not got.any():
+                raise ValueError(none.format(M, " in any replicate"))
+            pooled = np.ascontiguousarray(ob["irf"][got])        # [draws, r, H, N]
+            bands = ctx.quantile_bands_host(pooled.reshape(pooled.shape[0], -1), qs).reshape(qs.size, r, H, N)
+            without = int((ob["n_accept"] == 0).sum())
+    finally:
+        if own:
+            ctx.close()
+    out = dict(cols=cols, irf=np.ascontiguousarray(o["irf"][0, :nk].transpose(0, 3, 2, 1)),
+               fevd=None if o["fevd"] is None else np.ascontiguousarray(o["fevd"][0, :nk].transpose(0, 3, 2, 1)),
+               impact=o["S"][0, :nk].copy(), accepted_share=n / M, candidates_used=M, candidate_index=o["cand"][0, :nk].copy())
+    if bands is not None:
+        out["quantiles"] = qs
+        out["bands"] = np.ascontiguousarray(bands.transpose(0, 3, 2, 1))
+        out["replicates_without_a_draw"] = without
+    return out
+
+
 def historical_decomposition(m: DFMModel, *, named=None, through: Optional[int] = None, ctx=None) -> dict:
     """Which shocks drove every series through the sample: the contribution of each identified factor shock and of the initial
     condition to the common component of every cell, from the parametric fit (`estimate(m, Parametric())`, nfac_o = 0);

@@ -156,7 +156,8 @@ struct dfm_handle {
     DevBlock nw;                           // dfm_news_batch_dev: targets, the revised old panel, one forecast's xhat, the slice's pass
                                            // parameters, u / a vectors, smoothed means and (no weight) covariance panels
     DevBlock sv;                           // dfm_irf_batch_dev / dfm_histdecomp_batch_dev: named / cum, S, S^-1, the Theta tables, shocks and
-                                           // contribution paths, and the pass outputs the caller does not take
+                                           // contribution paths, and the pass outputs the caller does not take; dfm_signirf_batch_dev:
+                                           // the restrictions, their table, mask, counts, rotations and the kept slots' tables
     DevBlock ft;                           // dfm_filter_batch_dev: the padded loadings, the collapse's per-period arrays, the moments the
                                            // caller does not take and the evaluation's running sums
     DevBlock gb;                           // dfm_gibbs_batch_dev: the sweep's factor path and the shared Gram roots of balanced panels
@@ -172,11 +173,11 @@ struct dfm_handle {
 };
 
 enum KernelId { K_COLLAPSE = 0, K_RECURSION, K_MSTEP_STATS, K_MSTEP_SOLVE, K_PCA, K_SYNTH, K_PAD,
-                K_COLLAPSE_DMA, K_GRAM, K_COV, K_MEANSCAN, K_PFILL, K_COLLAPSE_MFMA, K_ALS, K_OLS, K_BOOT, K_QUANT, K_COLLAPSE_WIDE, K_EM_UPDATE, K_CHOW, K_MSTEP_MFMA, K_GRAM_XX, K_PASS_FUSED, K_FC_TAIL, K_FC_FILL, K_FC_PAD, K_SS_PREP, K_SS_EXPAND, K_SS_PATH, K_SS_DIFF, K_SS_FINISH, K_SS_FILL, K_NW_REVISE, K_NW_GATHER, K_NW_GAMMA, K_NW_COV, K_NW_IMPACT, K_MF_TABLE, K_MF_MOMENTS, K_MF_SOLVE, K_SV_PREP, K_SV_IRF_FILL, K_SV_SHOCK, K_SV_PATH, K_SV_HD_FILL, K_FT_FILTER, K_FT_FILL, K_FT_EVAL, K_GB_GRAM, K_GB_LOAD, K_GB_VAR, K_COUNT };
+                K_COLLAPSE_DMA, K_GRAM, K_COV, K_MEANSCAN, K_PFILL, K_COLLAPSE_MFMA, K_ALS, K_OLS, K_BOOT, K_QUANT, K_COLLAPSE_WIDE, K_EM_UPDATE, K_CHOW, K_MSTEP_MFMA, K_GRAM_XX, K_PASS_FUSED, K_FC_TAIL, K_FC_FILL, K_FC_PAD, K_SS_PREP, K_SS_EXPAND, K_SS_PATH, K_SS_DIFF, K_SS_FINISH, K_SS_FILL, K_NW_REVISE, K_NW_GATHER, K_NW_GAMMA, K_NW_COV, K_NW_IMPACT, K_MF_TABLE, K_MF_MOMENTS, K_MF_SOLVE, K_SV_PREP, K_SV_IRF_FILL, K_SV_SHOCK, K_SV_PATH, K_SV_HD_FILL, K_FT_FILTER, K_FT_FILL, K_FT_EVAL, K_GB_GRAM, K_GB_LOAD, K_GB_VAR, K_SV_SIGN_TABLE, K_SV_SIGN, K_SV_SIGN_KEEP, K_COUNT };
 static const char* const kKernelNames[K_COUNT] = {"collapse_kernel", "recursion_kernel", "mstep_lam_kernel",
                                                   "mstep_solve_kernel", "pca_kernel", "synth_kernel",
                                                   "pad_params_kernel", "collapse_dma_kernel", "gram_kernel",
-                                                  "cov_kernel", "meanscan_kernel", "pfill_kernel", "collapse_mfma_kernel", "als_kernel", "ols_kernel", "var_boot_kernel", "quantile_kernel", "collapse_wide_kernel", "em_update_kernel", "chow_kernel", "mstep_mfma_kernel", "gram_xx_kernel", "pass_fused_kernel", "forecast_tail_kernel", "forecast_fill_kernel", "forecast_pad_kernel", "simsmooth_prep_kernel", "simsmooth_expand_kernel", "simsmooth_path_kernel", "simsmooth_diff_kernel", "simsmooth_finish_kernel", "simsmooth_fill_kernel", "news_revise_kernel", "news_gather_kernel", "news_gamma_kernel", "news_cov_panel_kernel", "news_impact_kernel", "mf_table_kernel", "mf_moments_kernel", "mf_solve_kernel", "sv_prep_kernel", "sv_irf_fill_kernel", "sv_shock_kernel", "sv_path_kernel", "sv_hd_fill_kernel", "filter_kernel", "filter_fill_kernel", "filter_eval_kernel", "gibbs_gram_kernel", "gibbs_load_kernel", "gibbs_var_kernel"};
+                                                  "cov_kernel", "meanscan_kernel", "pfill_kernel", "collapse_mfma_kernel", "als_kernel", "ols_kernel", "var_boot_kernel", "quantile_kernel", "collapse_wide_kernel", "em_update_kernel", "chow_kernel", "mstep_mfma_kernel", "gram_xx_kernel", "pass_fused_kernel", "forecast_tail_kernel", "forecast_fill_kernel", "forecast_pad_kernel", "simsmooth_prep_kernel", "simsmooth_expand_kernel", "simsmooth_path_kernel", "simsmooth_diff_kernel", "simsmooth_finish_kernel", "simsmooth_fill_kernel", "news_revise_kernel", "news_gather_kernel", "news_gamma_kernel", "news_cov_panel_kernel", "news_impact_kernel", "mf_table_kernel", "mf_moments_kernel", "mf_solve_kernel", "sv_prep_kernel", "sv_irf_fill_kernel", "sv_shock_kernel", "sv_path_kernel", "sv_hd_fill_kernel", "filter_kernel", "filter_fill_kernel", "filter_eval_kernel", "gibbs_gram_kernel", "gibbs_load_kernel", "gibbs_var_kernel", "sv_sign_table_kernel", "sv_sign_kernel", "sv_sign_keep_kernel"};
 
 namespace dfm { int handle_device(const dfm_handle* h) { return h->device; } }   // (probe.hip)
 
@@ -2795,6 +2796,157 @@ int dfm_irf_batch(dfm_handle* h, int B, int N, int r, int p, int H, const double
     st.out(irf, n_o * r, irf_d); st.out(fevd, fevd ? n_o * (r + 1) : 0, fv_d);
     if (int rc = st.begin()) return rc;
     int rc = st.finish(dfm_irf_batch_dev(h, B, N, r, p, H, lam_d, A_d, Q_d, R_d, sd_d, named, cum, irf_d, fv_d, flags));
+    if (rc == 0) rc = status_check(h);
+    return rc;
+}
+
+// ---- sign-restricted impulse responses (signirf.hip) ----------------------------------------------------------------------------
+// The restrictions as the kernels read them: the distinct restricted series, and the rows (index into that list, h0, h1, sign)
+// sorted by shock with the first row of every shock.
+struct SignPlan {
+    std::vector<int> ser, gs, rows;
+    int HT = 1;
+};
+static SignPlan sign_plan(int r, int G, const int* restr) {
+    SignPlan sp;
+    sp.gs.assign((size_t)r + 1, 0);
+    for (int k = 0; k < r; ++k) {
+        for (int g = 0; g < G; ++g) {
+            const int* q = restr + 5 * g;
+            if (q[1] != k) continue;
+            size_t s = 0;
+            while (s < sp.ser.size() && sp.ser[s] != q[0]) ++s;
+            if (s == sp.ser.size()) sp.ser.push_back(q[0]);
+            const int row[4] = {(int)s, q[2], q[3], q[4]};
+            sp.rows.insert(sp.rows.end(), row, row + 4);
+            if (q[3] + 1 > sp.HT) sp.HT = q[3] + 1;
+        }
+        sp.gs[k + 1] = (int)sp.rows.size() / 4;
+    }
+    return sp;
+}
+
+// Sizes and restrictions first (they are decided before the handle is looked at), then the handle and the required pointers.
+// *sp: the plan of the restrictions, built once per call.
+static int signirf_check(dfm_handle* h, int B, int N, int r, int p, int H, const double* Lam, const double* Avar, const double* Q,
+                         const double* R, const int* named, int G, const int* restr, int M, int K, const int* n_accept,
+                         const int* cand_out, const double* fevd, unsigned flags, SignPlan* sp) {
+    if (H < 1) return fail(h, DFM_E_DIMS, "H must be >= 1%s");
+    if (M < 1 || K < 1 || G < 0) return fail(h, DFM_E_DIMS, "need M >= 1, K >= 1 and G >= 0%s");
+    if (G > 0 && !restr) return fail(h, DFM_E_NULL, "G > 0 restrictions but restr is NULL%s");
+    for (int g = 0; g < G; ++g) {
+        const int* q = restr + 5 * g;
+        if (q[0] < 0 || q[0] >= N || q[1] < 0 || q[1] >= r || q[2] < 0 || q[3] < q[2] || q[3] >= H || (q[4] != 1 && q[4] != -1))
+            return fail(h, DFM_E_DIMS, "a restriction (series, shock, h0, h1, sign) is out of range%s");
+    }
+    if (r >= 1 && r <= DFM_MAX_R) {
+        *sp = sign_plan(r, G, restr);
+        if (dfm::sign_table_bytes((int)sp->ser.size(), sp->HT, r) > dfm::kSgTabLds)
+            return fail(h, DFM_E_DIMS, "the table of restricted responses (distinct series x (max h1 + 1) x r doubles) exceeds 48 KB%s");
+    }
+    if (int rc = sv_check(h, B, 1, N, r, p, named, 0)) return rc;
+    if ((long long)B * M > 0x7fffffffLL || (long long)B * K > 0x7fffffffLL) return fail(h, DFM_E_DIMS, "B * M and B * K must be < 2^31%s");
+    if (flags & DFM_SV_UNIT_EFFECT) return fail(h, DFM_E_NULL, "DFM_SV_UNIT_EFFECT: a rotated shock has no named series to normalise on%s");
+    if (!Lam || !Avar || !Q || !n_accept || !cand_out || (fevd && !R)) return fail(h, DFM_E_NULL, "required pointer is NULL%s");
+    return 0;
+}
+
+// The checked call on device pointers: what both entries run.
+static int signirf_run(dfm_handle* h, int B, int N, int r, int p, int H, const double* Lam, const double* Avar, const double* Q,
+                       const double* R, const double* sd, const int* named, const int* cum, int G, const SignPlan& sp, int M, int K,
+                       uint64_t seed, int64_t first_cand, int* n_accept, int* mask_out, int* cand_out, double* S_out, double* irf,
+                       double* fevd) {
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t d = sizeof(double), rr = (size_t)r * r, BK = (size_t)B * K;
+    bool any_cum = false;
+    if (cum)
+        for (int i = 0; i < N; ++i) any_cum = any_cum || cum[i] != 0;
+    if (!any_cum) cum = nullptr;
+    const int nS = (int)sp.ser.size();
+    const bool fill = irf || fevd;
+    // the host integers, in the order they lie at the start of h->sv: named | cum | ser | gs | rows
+    std::vector<int>& ix = h->sv_idx;
+    ix.clear();
+    const size_t i_named = ix.size(); if (named) ix.insert(ix.end(), named, named + r);
+    const size_t i_cum = ix.size();   if (cum) ix.insert(ix.end(), cum, cum + N);
+    const size_t i_ser = ix.size();   ix.insert(ix.end(), sp.ser.begin(), sp.ser.end());
+    const size_t i_gs = ix.size();    ix.insert(ix.end(), sp.gs.begin(), sp.gs.end());
+    const size_t i_rows = ix.size();  ix.insert(ix.end(), sp.rows.begin(), sp.rows.end());
+    size_t off = 0;
+    const size_t o_ix = take(off, ix.size() * sizeof(int)), o_S = take(off, B * rr * d), o_Th = take(off, (size_t)B * H * rr * d),
+                 o_Thc = cum ? take(off, (size_t)B * H * rr * d) : (size_t)-1, o_tab = take(off, (size_t)B * nS * sp.HT * r * d + 8),
+                 o_mask = mask_out ? (size_t)-1 : take(off, (size_t)B * M * sizeof(int)),
+                 o_wcnt = take(off, (size_t)B * ((M + 63) / 64) * sizeof(int)), o_rot = take(off, (size_t)B * M * rr * d),
+                 o_ThK = fill ? take(off, BK * H * rr * d) : (size_t)-1, o_ThcK = (fill && cum) ? take(off, BK * H * rr * d) : (size_t)-1;
+    HIP_TRY(h, h->sv.grow(off));
+    int* ixd = at<int>(h->sv, o_ix);
+    HIP_TRY(h, hipMemcpyAsync(ixd, ix.data(), ix.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    SvArgs a{};
+    a.B = B; a.N = N; a.r = r; a.p = p; a.H = H; a.T = 0;
+    a.Lam = Lam; a.R = fevd ? R : nullptr; a.A = Avar; a.Q = Q; a.sd = sd;
+    a.named = named ? ixd + i_named : nullptr; a.cum = cum ? ixd + i_cum : nullptr;
+    a.status = h->status_dev;
+    a.S = at<double>(h->sv, o_S); a.Th = at<double>(h->sv, o_Th); a.Thc = at<double>(h->sv, o_Thc);
+    {
+        ProfScope ps(h, K_SV_PREP);
+        HIP_TRY(h, launch_sv_prep(a, h->stream));
+    }
+    SgArgs g{};
+    g.B = B; g.N = N; g.r = r; g.H = H; g.M = M; g.K = K; g.nS = nS; g.HT = sp.HT; g.G = G;
+    g.Lam = Lam; g.sd = sd; g.cum = a.cum; g.ser = ixd + i_ser; g.gs = ixd + i_gs; g.rows = ixd + i_rows;
+    g.S = a.S; g.Th = a.Th; g.Thc = a.Thc; g.tab = at<double>(h->sv, o_tab);
+    g.seed = seed; g.first_cand = first_cand;
+    g.mask = mask_out ? mask_out : at<int>(h->sv, o_mask); g.wcnt = at<int>(h->sv, o_wcnt); g.rot = at<double>(h->sv, o_rot);
+    g.n_accept = n_accept; g.cand_out = cand_out; g.S_out = S_out;
+    g.ThK = at<double>(h->sv, o_ThK); g.ThcK = at<double>(h->sv, o_ThcK);
+    if (nS > 0) {
+        ProfScope ps(h, K_SV_SIGN_TABLE);
+        HIP_TRY(h, launch_sv_sign_table(g, h->stream));
+    }
+    {
+        ProfScope ps(h, K_SV_SIGN);
+        HIP_TRY(h, launch_sv_sign(g, h->stream));
+    }
+    {
+        ProfScope ps(h, K_SV_SIGN_KEEP);
+        HIP_TRY(h, launch_sv_sign_keep(g, h->stream));
+    }
+    if (!fill) return 0;
+    a.B = B; a.slots = K; a.Th = g.ThK; a.Thc = g.ThcK; a.irf = irf; a.fevd = fevd;
+    ProfScope ps(h, K_SV_IRF_FILL);
+    HIP_TRY(h, launch_sv_irf_fill(a, h->stream));
+    return 0;
+}
+
+int dfm_signirf_batch_dev(dfm_handle* h, int B, int N, int r, int p, int H, const double* Lam, const double* Avar, const double* Q,
+                          const double* R, const double* sd, const int* named, const int* cum, int G, const int* restr, int M, int K,
+                          uint64_t seed, int64_t first_cand, int* n_accept, int* mask_out, int* cand_out, double* S_out, double* irf,
+                          double* fevd, unsigned flags) {
+    SignPlan sp;
+    if (int rc = signirf_check(h, B, N, r, p, H, Lam, Avar, Q, R, named, G, restr, M, K, n_accept, cand_out, fevd, flags, &sp)) return rc;
+    return signirf_run(h, B, N, r, p, H, Lam, Avar, Q, R, sd, named, cum, G, sp, M, K, seed, first_cand, n_accept, mask_out, cand_out,
+                       S_out, irf, fevd);
+}
+
+int dfm_signirf_batch(dfm_handle* h, int B, int N, int r, int p, int H, const double* Lam, const double* Avar, const double* Q,
+                      const double* R, const double* sd, const int* named, const int* cum, int G, const int* restr, int M, int K,
+                      uint64_t seed, int64_t first_cand, int* n_accept, int* mask_out, int* cand_out, double* S_out, double* irf,
+                      double* fevd, unsigned flags) {
+    SignPlan sp;
+    if (int rc = signirf_check(h, B, N, r, p, H, Lam, Avar, Q, R, named, G, restr, M, K, n_accept, cand_out, fevd, flags, &sp)) return rc;
+    if (int rc = status_epoch(h)) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t n_R = (size_t)B * N, BK = (size_t)B * K, n_o = BK * H * N;
+    HostStage st(h, 256);
+    double *lam_d, *A_d, *Q_d, *R_d, *sd_d, *S_d, *irf_d, *fv_d;
+    int *na_d, *mk_d, *cd_d;
+    st.in(Lam, n_R * r, lam_d); st.in(Avar, (size_t)B * r * r * p, A_d); st.in(Q, (size_t)B * r * r, Q_d);
+    st.in(R, R ? n_R : 0, R_d); st.in(sd, sd ? n_R : 0, sd_d);
+    st.out(n_accept, (size_t)B, na_d); st.out(mask_out, mask_out ? (size_t)B * M : 0, mk_d); st.out(cand_out, BK, cd_d);
+    st.out(S_out, S_out ? BK * r * r : 0, S_d); st.out(irf, irf ? n_o * r : 0, irf_d); st.out(fevd, fevd ? n_o * (r + 1) : 0, fv_d);
+    if (int rc = st.begin()) return rc;
+    int rc = st.finish(signirf_run(h, B, N, r, p, H, lam_d, A_d, Q_d, R_d, sd_d, named, cum, G, sp, M, K, seed, first_cand, na_d, mk_d,
+                                   cd_d, S_d, irf_d, fv_d));
     if (rc == 0) rc = status_check(h);
     return rc;
 }

@@ -567,12 +567,40 @@ struct SvArgs {
     double* C;                                    // [B][r+1][T][r] contribution paths, slot r = the initial condition
     double* hd;                                   // [B][r+1][T][N]
     CellGeom geo; int CP, TC;                     // geometry (set by the launchers)
+    int slots;                                    // sv_irf_fill_kernel: tables and outputs per replicate (signirf.hip: K kept slots;
+                                                  // Th, Thc, irf, fevd are then [B slots][..]); 0 or 1: one, the plain entries
 };
 hipError_t launch_sv_prep(const SvArgs& a, hipStream_t s);
 hipError_t launch_sv_irf_fill(SvArgs a, hipStream_t s);
 hipError_t launch_sv_shock(const SvArgs& a, hipStream_t s);
 hipError_t launch_sv_path(SvArgs a, hipStream_t s);
 hipError_t launch_sv_hd_fill(SvArgs a, hipStream_t s);
+
+// Sign-restricted impulse responses (signirf.hip): M candidate rotations per replicate, the first K accepted ones kept.
+constexpr size_t kSgTabLds = 48 * 1024;           // sv_sign_kernel: the replicate's table of restricted responses, at most
+struct SgArgs {
+    int B, N, r, H, M, K;
+    int nS, HT, G;                                // distinct restricted series, horizons in the table (max h1 + 1), restrictions
+    const double* Lam; const double* sd;          // [B][N][r], [B][N] or null
+    const int* cum;                               // device [N] or null
+    const int* ser;                               // device [nS]: the distinct restricted series
+    const int* gs;                                // device [r+1]: the restrictions of shock k are rows gs[k] .. gs[k+1] - 1
+    const int* rows;                              // device [G][4]: (index into ser, h0, h1, sign), sorted by shock
+    const double* S;                              // [B][r][r] base impact matrix (sv_prep_kernel)
+    const double* Th; const double* Thc;          // [B][H][r][r] shock-major tables of sv_prep_kernel; Thc null: nothing cumulated
+    double* tab;                                  // [B][nS][HT][r] a_{i,h} = sd_i lam_i' Theta_h (Theta^c_h where cum[i])
+    uint64_t seed; int64_t first_cand;
+    int* mask;                                    // [B][M] 1 = accepted
+    int* wcnt;                                    // [B][ceil(M / 64)] accepted candidates of each group of 64
+    double* rot;                                  // [B][M][r][r] Rot D of the accepted candidates (r > 8: of every candidate)
+    int* n_accept; int* cand_out;                 // [B], [B][K]
+    double* S_out;                                // [B][K][r][r] or null
+    double* ThK; double* ThcK;                    // [B][K][H][r][r] tables of the kept slots, NaN where empty (null: not wanted)
+};
+size_t sign_table_bytes(int nS, int HT, int r);
+hipError_t launch_sv_sign_table(const SgArgs& a, hipStream_t s);
+hipError_t launch_sv_sign(const SgArgs& a, hipStream_t s);
+hipError_t launch_sv_sign_keep(const SgArgs& a, hipStream_t s);
 
 // Filtered states, prediction errors and out-of-sample evaluation (filter.hip).  k = r p, kk = k (k + 1) / 2.
 struct FtArgs {

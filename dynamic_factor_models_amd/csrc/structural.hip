@@ -2,7 +2,8 @@
 // dfm_histdecomp_batch, capi.hip).  Model  x_t = Lam f_t + e_t,  f_t = A_1 f_{t-1} + .. + A_p f_{t-p} + eta_t,  Var eta = Q,
 // eta_t = S u_t with Var u = I.  Identification (include/dfm_hip.h): S = Ln^-1 chol(Ln Q Ln') with Ln = Lam[named, :], or chol(Q).
 //   sv_prep_kernel      one workgroup per replicate: S, S^-1, the unit-effect scales and the tables Theta_h = Psi_h S, Theta^c_h
-//   sv_irf_fill_kernel  streams irf [B][r][H][N] and fevd [B][r+1][H][N]: a workgroup owns a replicate and a block of series, a lane
+//   sv_irf_fill_kernel  streams irf [B][r][H][N] and fevd [B][r+1][H][N]: a workgroup owns a replicate (or one of its SvArgs::slots
+//                       kept rotations, signirf.hip) and a block of series, a lane
 //                       one series (or two adjacent ones, 16-byte stores), walks h in order with the Theta rows staged in LDS
 //                       (every lane reads the same address: a broadcast) and the r running sums of squares in registers
 //   sv_shock_kernel     etahat_t = f_t - sum_j A_j f_{t-j} and u_t = S^-1 etahat_t, all t at once
@@ -148,8 +149,9 @@ __global__ __launch_bounds__(kSvIrfLanes) void sv_irf_fill_kernel(SvArgs a) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int tid = threadIdx.x, H = a.H, N = a.N;
     const int s = (int)(blockIdx.x % (unsigned)a.geo.nsblk);
-    const size_t b = blockIdx.x / (unsigned)a.geo.nsblk;
-    const bool hasc = a.Thc != nullptr, wantV = a.fevd != nullptr, unit = a.scale != nullptr;
+    const size_t sl = blockIdx.x / (unsigned)a.geo.nsblk;             // tables and outputs: the slot; parameters: its replicate
+    const size_t b = a.slots > 1 ? sl / (unsigned)a.slots : sl;
+    const bool hasc = a.Thc != nullptr, wantV = a.fevd != nullptr, wantI = a.irf != nullptr, unit = a.scale != nullptr;
     double* sT = sm;
     double* sTc = sm + (size_t)a.geo.RC * RR;
     double* sSc = sm + (size_t)a.geo.RC * RR * (hasc ? 2 : 1);
@@ -171,8 +173,8 @@ __global__ __launch_bounds__(kSvIrfLanes) void sv_irf_fill_kernel(SvArgs a) {
         const int nh = H - h0 < a.geo.RC ? H - h0 : a.geo.RC;
         __syncthreads();
         for (int e = tid; e < nh * RR; e += blockDim.x) {
-            sT[e] = a.Th[(b * H + h0) * RR + e];
-            if (hasc) sTc[e] = a.Thc[(b * H + h0) * RR + e];
+            sT[e] = a.Th[(sl * H + h0) * RR + e];
+            if (hasc) sTc[e] = a.Thc[(sl * H + h0) * RR + e];
         }
         __syncthreads();
         if (!live) continue;
@@ -194,7 +196,8 @@ __global__ __launch_bounds__(kSvIrfLanes) void sv_irf_fill_kernel(SvArgs a) {
                     tot[q] += ssq[q][k];
                     x[q] = unit ? sdv[q] * v / sSc[k] : sdv[q] * v;
                 }
-                const size_t o = ((b * R + k) * H + h) * N + i0;
+                if (!wantI) continue;
+                const size_t o = ((sl * R + k) * H + h) * N + i0;
                 if constexpr (SP == 2) *reinterpret_cast<double2*>(a.irf + o) = double2{x[0], x[1]};
                 else a.irf[o] = x[0];
             }
@@ -210,7 +213,7 @@ __global__ __launch_bounds__(kSvIrfLanes) void sv_irf_fill_kernel(SvArgs a) {
                 double x[SP];
 #pragma unroll
                 for (int q = 0; q < SP; ++q) x[q] = (k < R ? ssq[q][k < R ? k : 0] : idio[q]) * inv[q];
-                const size_t o = ((b * (R + 1) + k) * H + h) * N + i0;
+                const size_t o = ((sl * (R + 1) + k) * H + h) * N + i0;
                 if constexpr (SP == 2) *reinterpret_cast<double2*>(a.fevd + o) = double2{x[0], x[1]};
                 else a.fevd[o] = x[0];
             }
@@ -367,7 +370,7 @@ static hipError_t launch_irf_r(SvArgs a, hipStream_t s) {
     const bool hasc = a.Thc != nullptr;
     a.geo = irf_geometry(a.N, R, SP, a.H, hasc, kSvIrfLanes, kSvFillLds);
     const size_t lds = ((size_t)a.geo.RC * R * R * (hasc ? 2 : 1) + 32) * sizeof(double);
-    const size_t blocks = (size_t)a.B * a.geo.nsblk;
+    const size_t blocks = (size_t)a.B * (a.slots > 1 ? a.slots : 1) * a.geo.nsblk;
     if (blocks > 0x7fffffffu) return hipErrorInvalidValue;
     if constexpr (R <= 16) {
         if (SP == 2) {

@@ -1,7 +1,8 @@
-"""Binding of the structural entries of include/dfm_hip.h (csrc/structural.hip): dfm_irf_batch[_dev] and
-dfm_histdecomp_batch[_dev].  The functions take a DfmContext; importing this module (kalman.py does) also attaches them to
-DfmContext as irf_batch, irf_batch_host, histdecomp_batch and histdecomp_batch_host, with the marshalling conventions of
-forecast_batch(_host): device tensors in and out on torch's current stream, or NumPy through the host-pointer entries.
+"""Binding of the structural entries of include/dfm_hip.h (csrc/structural.hip, csrc/signirf.hip): dfm_irf_batch[_dev],
+dfm_histdecomp_batch[_dev] and dfm_signirf_batch[_dev].  The functions take a DfmContext; importing this module (kalman.py does)
+also attaches them to DfmContext as irf_batch, irf_batch_host, histdecomp_batch, histdecomp_batch_host, signirf_batch and
+signirf_batch_host, with the marshalling conventions of forecast_batch(_host): device tensors in and out on torch's current
+stream, or NumPy through the host-pointer entries.
 """
 from __future__ import annotations
 
@@ -67,6 +68,73 @@ def _histdecomp(ctx, be, panel, params, sd, named, want_shocks, may_have_missing
     return dict(hd=hd, shocks=shocks, f=f, loglik=ll)
 
 
+def _restrictions(restrictions):
+    """The restrictions as a host int32 [G, 5] array of (series, shock, h0, h1, sign) rows; none: G = 0 and no array."""
+    if restrictions is None:
+        return 0, None
+    a = np.asarray(restrictions, dtype=np.int64)
+    if a.size == 0:
+        return 0, None
+    if a.ndim != 2 or a.shape[1] != 5:
+        raise ValueError("restrictions must be (series, shock, h0, h1, sign) rows")
+    if np.any(np.abs(a[:, 4]) != 1):
+        raise ValueError("the sign of a restriction must be +1 or -1")
+    return a.shape[0], np.ascontiguousarray(a, dtype=np.int32)
+
+
+def _signirf(ctx, be, Lam, Avar, Q, R, H, restrictions, candidates, keep, seed, first_cand, sd, named, cum, want_mask, want_S,
+             want_irf, want_fevd):
+    Lam, Avar, Q = be.inp(Lam), be.inp(Avar), be.inp(Q)
+    B, N, r = Lam.shape
+    p = Avar.shape[2] // r
+    H, M, K = int(H), int(candidates), int(keep)
+    if H < 1:
+        raise ValueError("H must be >= 1")
+    if M < 1 or K < 1:
+        raise ValueError("candidates and keep must be >= 1")
+    if want_fevd and R is None:
+        raise ValueError("the variance decomposition needs R")
+    G, restr = _restrictions(restrictions)
+    R = None if R is None else be.inp(R)
+    sd = None if sd is None else be.inp(sd)
+    named = _index(named, r, "named", True)
+    cum = _index(cum, N, "cum", False)
+    n_accept = be.out(B, int32=True)
+    mask = be.out(B, M, int32=True) if want_mask else None
+    cand = be.out(B, K, int32=True)
+    S = be.out(B, K, r, r) if want_S else None
+    irf = be.out(B, K, r, H, N) if want_irf else None
+    fevd = be.out(B, K, r + 1, H, N) if want_fevd else None
+    be.sync()
+    rc = getattr(ctx._lib, "dfm_signirf_batch" + be.suffix)(
+        ctx._h, B, N, r, p, H, be.ptr(Lam, "Lam", (B, N, r)), be.ptr(Avar, "Avar", (B, r, r * p)), be.ptr(Q, "Q", (B, r, r)),
+        be.ptr(R, "R", (B, N)), be.ptr(sd, "sd", (B, N)), _k._ptr(named), _k._ptr(cum), G, _k._ptr(restr), M, K,
+        int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_cand), be.raw(n_accept), None if mask is None else be.raw(mask), be.raw(cand),
+        be.ptr(S, "S_out"), be.ptr(irf, "irf"), be.ptr(fevd, "fevd"), 0)
+    _k._check(ctx._h, rc)
+    return dict(n_accept=n_accept, mask=mask, cand=cand, S=S, irf=irf, fevd=fevd)
+
+
+def signirf_batch(ctx, Lam, Avar, Q, R, H: int, restrictions, candidates: int, keep: int = 1, seed: int = 0, first_cand: int = 0,
+                  sd=None, named=None, cum=None, want_mask: bool = False, want_S: bool = True, want_irf: bool = True,
+                  want_fevd: bool = False):
+    """dfm_signirf_batch_dev (device tensors, torch's current stream): `candidates` Haar rotations of the base impact matrix per
+    replicate, those whose responses satisfy the sign `restrictions` ((series, shock, h0, h1, sign) rows, host side) accepted, the
+    first `keep` accepted ones written out.  Inputs as irf_batch.  Returns dict(n_accept [B] int32, mask [B,candidates] int32 or
+    None, cand [B,keep] int32 (-1: empty slot), S [B,keep,r,r], irf [B,keep,r,H,N], fevd [B,keep,r+1,H,N]; None when not asked
+    for; NaN in empty slots).  Candidates first_cand .. first_cand + candidates - 1 of the stream of `seed`."""
+    return _signirf(ctx, _k._Torch(ctx, Lam), Lam, Avar, Q, R, H, restrictions, candidates, keep, seed, first_cand, sd, named, cum,
+                    want_mask, want_S, want_irf, want_fevd)
+
+
+def signirf_batch_host(ctx, Lam, Avar, Q, R, H: int, restrictions, candidates: int, keep: int = 1, seed: int = 0,
+                       first_cand: int = 0, sd=None, named=None, cum=None, want_mask: bool = False, want_S: bool = True,
+                       want_irf: bool = True, want_fevd: bool = False):
+    """dfm_signirf_batch (host pointers; what Julia's ccall binds): NumPy in / out, same dict as signirf_batch."""
+    return _signirf(ctx, _k._NP, Lam, Avar, Q, R, H, restrictions, candidates, keep, seed, first_cand, sd, named, cum, want_mask,
+                    want_S, want_irf, want_fevd)
+
+
 def irf_batch(ctx, Lam, Avar, Q, R, H: int, sd=None, named=None, cum=None, unit_effect: bool = False, want_fevd: bool = True):
     """dfm_irf_batch_dev (device tensors, torch's current stream): identified impulse responses irf [B,r,H,N] and forecast-error
     variance shares fevd [B,r+1,H,N] (None when not asked for) of every series.  Lam [B,N,r], Avar [B,r,r p], Q [B,r,r], R [B,N];
@@ -96,5 +164,5 @@ def histdecomp_batch_host(ctx, panel, Lam, R, Avar, Q, mu0, P0, sd=None, named=N
     return _histdecomp(ctx, _k._NP, panel, (Lam, R, Avar, Q, mu0, P0), sd, named, want_shocks, may_have_missing, singular_q)
 
 
-for _f in (irf_batch, irf_batch_host, histdecomp_batch, histdecomp_batch_host):
+for _f in (irf_batch, irf_batch_host, histdecomp_batch, histdecomp_batch_host, signirf_batch, signirf_batch_host):
     setattr(_k.DfmContext, _f.__name__, _f)

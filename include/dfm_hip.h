@@ -439,6 +439,59 @@ int dfm_histdecomp_batch(dfm_handle* h, int B, int T, int N, int r, int p, const
                          const double* sd, const int* named, double* hd, double* shocks, double* f_out, double* loglik,
                          unsigned flags);
 
+/* --- sign-restricted structural IRFs: batched rotation draws -------------------------------------------------------------------
+ * The model, `named`, `cum`, `sd`, the base impact matrix S and the tables Theta_h = Psi_h S are those of dfm_irf_batch, with
+ * 1 <= r p <= DFM_MAX_R: S = chol(Q), or Ln^-1 chol(Ln Q Ln') with `named`.  Every S Rot with Rot orthogonal has S Rot (S Rot)' =
+ * S S' and is an impact matrix too; M candidate rotations per replicate are drawn uniformly (Haar), those whose responses carry
+ * the required signs are accepted, and the first K accepted ones of every replicate are kept and written out.
+ *
+ * Restrictions: `restr` is a HOST int[G][5] shared by every replicate, row g = (series i, shock k, h0, h1, sign) with
+ * 0 <= i < N, 0 <= k < r, 0 <= h0 <= h1 < H, sign = +1 or -1.  Row g asks that sign * resp_i,k(h) > 0 for every h0 <= h <= h1,
+ * resp being the response as it is output (cumulated where cum[i]).  G = 0 is allowed: every candidate is then accepted (but
+ * for the pivot rule of step 4).
+ *
+ * Candidate m of replicate b, m = 0 .. M-1:
+ *   1. key = seed ^ (0x9E3779B97F4A7C15 * (first_cand + m + 1)), the key of dfm_simsmooth_batch, with stream word 16 b + 10
+ *      (streams 1-9 are taken).
+ *   2. Z [r][r] of standard normals: entry e = row r + col is component e mod 2 of the pair at index e / 2 (normal2, as the
+ *      other streams use it).
+ *   3. Rot = the orthogonal factor of Z = Rot U with U upper triangular and a POSITIVE diagonal.  That factor is unique and is
+ *      the Haar draw.  (The library: Gram-Schmidt by columns, every column orthogonalised twice.)
+ *   4. A pivot |U_jj| <= 1e-12 max|Z| rejects the candidate.
+ *   5. For every shock column k that has restrictions: if all its rows hold the column stays; if all its rows hold with every
+ *      sign reversed the column is flipped (Rot e_k -> -Rot e_k); otherwise the candidate is rejected.  Columns without
+ *      restrictions are never flipped.
+ *   6. The impact matrix of an accepted candidate is S_m = S Rot D, D the diagonal of flips.
+ * A candidate's result is a pure function of (seed, first_cand + m, b) and the inputs: it depends on neither M, K nor the launch
+ * geometry, and candidates [k, k + M) of one call equal those of a call with first_cand = k.
+ *
+ * Outputs ("slot" s = 0 .. K-1 of replicate b holds its s-th accepted candidate, in candidate order):
+ *   n_accept [B] int32            accepted among the M candidates
+ *   mask_out [B][M] int32         1 accepted, 0 not (may be NULL)
+ *   cand_out [B][K] int32         candidate index m (into mask_out) of the first min(K, n_accept[b]) accepted candidates; -1 behind
+ *   S_out [B][K][r][r]            S_m of the kept slots (may be NULL)
+ *   irf [B][K][r][H][N]           sd_i lam_i' Psi_h S_m e_k, cumulated where cum[i] (may be NULL): what dfm_irf_batch with
+ *                                 named = NULL gives for the rotated set (Lam S_m, S_m^-1 A_j S_m, I)
+ *   fevd [B][K][r+1][H][N]        dfm_irf_batch's definition with Theta_h Rot D in place of Theta_h (may be NULL; needs R)
+ * Empty slots hold NaN in every double output.
+ * Status: sizes and `restr` are checked before the handle.  H < 1, M < 1, K < 1, G < 0, a restr entry out of range, a named entry
+ * out of range or repeated: DFM_E_DIMS; G > 0 with restr NULL, n_accept or cand_out NULL, a NULL input: DFM_E_NULL; r p >
+ * DFM_MAX_R: DFM_E_R_UNSUPPORTED.  DFM_SV_UNIT_EFFECT is refused with DFM_E_NULL, the code that flag gets without named series:
+ * a rotated shock has no named series to normalise on.  A singular Ln gives status bit 16 and DFM_E_NUMERIC, as dfm_irf_batch.
+ * A rank-deficient Q is accepted.  The per-replicate table of restricted responses (the r-vectors sd_i lam_i' Theta_h of the
+ * distinct restricted series i and h <= max h1) lives in LDS: (distinct restricted series) x (max h1 + 1) x r x 8 bytes must not
+ * exceed 48 KB (49152), else DFM_E_DIMS.  B M and B K must be < 2^31 (DFM_E_DIMS).
+ * Allocates in the handle (kept for the next call): S, the Theta tables, the mask when mask_out is NULL, one r x r rotation per
+ * candidate ([B][M][r][r]) and the kept slots' tables [B][K][H][r][r].  Outputs must not overlap the inputs. */
+int dfm_signirf_batch_dev(dfm_handle* h, int B, int N, int r, int p, int H, const double* Lam, const double* Avar,
+                          const double* Q, const double* R, const double* sd, const int* named, const int* cum, int G,
+                          const int* restr, int M, int K, uint64_t seed, int64_t first_cand, int* n_accept, int* mask_out,
+                          int* cand_out, double* S_out, double* irf, double* fevd, unsigned flags);
+int dfm_signirf_batch(dfm_handle* h, int B, int N, int r, int p, int H, const double* Lam, const double* Avar, const double* Q,
+                      const double* R, const double* sd, const int* named, const int* cum, int G, const int* restr, int M,
+                      int K, uint64_t seed, int64_t first_cand, int* n_accept, int* mask_out, int* cand_out, double* S_out,
+                      double* irf, double* fevd, unsigned flags);
+
 /* --- AR idiosyncratic terms --------------------------------------------------------
  *   x_it = lam_i' f_t + e_it,   e_it = rho_i1 e_i,t-1 + .. + rho_iq e_i,t-q + eps_it,  eps_it ~ N(0, sig2_i)
  * with rho [B][N][q] / sig2 [B][N] in the role of the reference's uar_coef / uar_ser^2 (AR(n_uarlag) of the loading

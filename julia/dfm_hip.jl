@@ -410,6 +410,44 @@ function structural_irf(h::Handle, params, H::Integer; nlag::Integer = 1, named 
     return (irf = irf, fevd = fevd)              # the C layout [k][h][i] is column-major N x H x r as it stands
 end
 
+"Impulse responses identified by sign restrictions (dfm_signirf_batch; include/dfm_hip.h): params, nlag, named, cumulate, sd as
+`structural_irf`; restrictions = rows (series, shock, h0, h1, sign) with series and shock 1-based and horizons 0-based (0 = impact);
+`candidates` Haar rotations of the base impact matrix are drawn on the GPU from `seed` (candidates first_cand, first_cand + 1, ..),
+the first `keep` accepted ones are returned.  Returns n_accept, mask (candidates), cand (keep; 0-based candidate index, -1 = empty
+slot), impact (r x r x keep), irf (N x H x r x keep) and fevd (N x H x (r+1) x keep); empty slots hold NaN."
+function structural_irf_signs(h::Handle, params, H::Integer, restrictions; candidates::Integer = 1000, keep::Integer = 1,
+                              nlag::Integer = 1, named = nothing, cumulate = nothing, sd = nothing, seed::Integer = 20160415,
+                              first_cand::Integer = 0)
+    N, r = size(params.Lam)
+    Av = hasproperty(params, :Avar) ? params.Avar : params.A
+    Lam = permutedims(params.Lam); R = copy(params.R); AC = permutedims(Av); QC = permutedims(params.Q)
+    sdC = sd === nothing ? C_NULL : Vector{Float64}(sd)
+    namedC = named === nothing ? C_NULL : Vector{Cint}(named .- 1)
+    cumC = C_NULL
+    if cumulate !== nothing
+        cumC = zeros(Cint, N); cumC[cumulate] .= 1
+    end
+    G = length(restrictions)
+    restrC = G == 0 ? C_NULL : Matrix{Cint}(undef, 5, G)         # column g = row g of the C array [G][5]
+    for (g, q) in enumerate(restrictions)
+        restrC[:, g] .= (q[1] - 1, q[2] - 1, q[3], q[4], q[5])
+    end
+    M = Int(candidates); K = Int(keep)
+    nacc = Vector{Cint}(undef, 1); mask = Vector{Cint}(undef, M); cand = Vector{Cint}(undef, K)
+    S = Array{Float64}(undef, r, r, K); irf = Array{Float64}(undef, N, H, r, K); fevd = Array{Float64}(undef, N, H, r + 1, K)
+    GC.@preserve Lam R AC QC sdC namedC cumC restrC nacc mask cand S irf fevd begin
+        rc = ccall((:dfm_signirf_batch, LIB), Cint,
+                   (Ptr{Cvoid}, Cint, Cint, Cint, Cint, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                    Ptr{Float64}, Ptr{Cint}, Ptr{Cint}, Cint, Ptr{Cint}, Cint, Cint, UInt64, Int64, Ptr{Cint}, Ptr{Cint},
+                    Ptr{Cint}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cuint),
+                   h.ptr, 1, N, r, nlag, H, Lam, AC, QC, R, sdC, namedC, cumC, G, restrC, M, K, UInt64(seed), Int64(first_cand),
+                   nacc, mask, cand, S, irf, fevd, Cuint(0))
+        check(h.ptr, rc)
+    end
+    # the C layouts [s][i][k] and [s][k][h][i] are column-major (k, i, s) and (i, h, k, s): the impact matrices are transposed back
+    return (n_accept = Int(nacc[1]), mask = mask, cand = cand, impact = permutedims(S, (2, 1, 3)), irf = irf, fevd = fevd)
+end
+
 "Historical decomposition (dfm_histdecomp_batch; include/dfm_hip.h): z, params, nlag, sd, singular_q as `forecast`, named as
 `structural_irf`.  Returns contributions (T x N x (r+1): the last slot is the initial condition), shocks (T x r), factor
 (T x r) and loglik."
