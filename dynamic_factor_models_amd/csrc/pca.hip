@@ -644,7 +644,7 @@ __device__ __forceinline__ void spd_solve_lds(double* M, double* Bs, int r, int 
 //              matrix, 4 partial matrices per matrix meet in LDS -- one barrier for both;
 //   residual, Cholesky of G (thread 0), V = Y L^-T per row.
 // Same arithmetic, start and stopping rule as the generic loop; leaves the orthonormal basis in V (global), returns whether
-// the residual test fired.  sH / sG: R x R LDS matrices of the caller; red: >= 32 doubles.
+// the result is accepted (an exit fired, or max_iter ran out with the best residual under 1e-10).  sH / sG: R x R LDS matrices of the caller; red: >= 32 doubles.
 template <int R>
 __device__ __forceinline__ bool pca_iterate_lds(const PcaArgs& a, const double* __restrict__ S, double* V, double* Y, int N,
                                                 int r, double* sH, double* sG, double* red) {
@@ -801,9 +801,10 @@ __device__ __forceinline__ bool pca_iterate_lds(const PcaArgs& a, const double* 
         const double rel = sqrt(pr[0] / pr[1]);
         orthonormalise();
         if (rel <= 1e-14) { converged = true; break; }
-        if (rel < 0.5 * best) { best = rel; stall = 0; }
+        if (rel < best) { best = rel; stall = 0; }             // (the stopping rule: see the generic loop of pca_kernel)
         else if (++stall >= 8 && best < 1e-10) { converged = true; break; }
     }
+    if (best < 1e-10) converged = true;                         // max_iter ran out on a residual the result is still accepted at
     // H = V'S V of the FINAL basis for the Rayleigh-Ritz step of the caller, still from LDS (the caller's generic product
     // reads V from global memory: 0.31 ms per replicate, as long as the whole iteration)
     apply_S_lds();
@@ -905,8 +906,13 @@ __global__ __launch_bounds__(NT, (NT == kPcaFastThreads ? 4 : 1)) void pca_kerne
         converged = pca_iterate_lds<R>(a, S, V, Y, N, r, sH, sG, sred);
     } else {
     orthonormalise();
-    // iterate until the invariant-subspace residual ||S V - V (V'S V)||_F / ||S V||_F reaches the fp64
-    // floor (or stops improving): the Ritz vectors taken afterwards are then exact to roundoff / gap
+    // iterate until the invariant-subspace residual rel = ||S V - V (V'S V)||_F / ||S V||_F reaches the fp64 floor: the Ritz
+    // vectors taken afterwards are then exact to roundoff / gap.  Two exits: rel <= 1e-14, or eight iterations in a row that set
+    // NO NEW MINIMUM of rel with the minimum under 1e-10 -- the residual has stopped improving, which happens at the roundoff floor
+    // only (a wide state's floor can lie above 1e-14).  Slow progress is not a stall: with the cut in the noise bulk of the spectrum
+    // the rate lambda_{r+1} / lambda_r is 0.94 .. 0.98 and hardly an iteration halves the residual; a counter of such iterations left
+    // at rel ~ 5e-11, i.e. 2e-8 .. 2e-7 from the reference in Lam, A, Q and F.  max_iter running out with the minimum under 1e-10
+    // is accepted (that level is what the result was accepted at before); above it, status bit 1 (value 2) below.
     double best = 1e300;
     int stall = 0;
     for (int it = 0; it < a.max_iter; ++it) {
@@ -926,13 +932,15 @@ __global__ __launch_bounds__(NT, (NT == kPcaFastThreads ? 4 : 1)) void pca_kerne
         const double rel = sqrt(part[0] / part[1]);
         orthonormalise();
         if (rel <= 1e-14) { converged = true; break; }
-        if (rel < 0.5 * best) { best = rel; stall = 0; }
+        if (rel < best) { best = rel; stall = 0; }
         else if (++stall >= 8 && best < 1e-10) { converged = true; break; }
     }
+    if (best < 1e-10) converged = true;
     }
     if (a.stop_after == 1) return;
-    // max_iter exhausted above the tolerance (near-degenerate spectrum at the cut: the rate is lambda_{r+1} / lambda_r):
-    // the basis is NOT the reference's svd-based pca_score (dfm_functions.ipynb:179-183) -- say so instead of returning it
+    // max_iter exhausted with the best residual still >= 1e-10 (near-degenerate spectrum at the cut: the rate is
+    // lambda_{r+1} / lambda_r): the basis is NOT the reference's svd-based pca_score (dfm_functions.ipynb:179-183) -- say so
+    // instead of returning it
     if (!converged && tid == 0 && a.status) atomicOr(a.status, 2);
     // Rayleigh-Ritz: H = V'SV, H = W Theta W', V <- V W (descending), sign rule of the oracle
     if constexpr (!(NT == kPcaFastThreads && R <= 8)) {       // (the fast path left H in sH)
