@@ -10,7 +10,9 @@
 // + 8 FMAs per lane instead of 64.
 //
 // Outputs are exactly cov_body's (same tables, same bookkeeping of the fixed points, same P_smooth rows), written through
-// Cov8Dst so that they can live in global memory (cov_wave_kernel: drop-in for cov_kernel) or in LDS (pass_fused.hip).
+// Cov8Dst so that they can live in global memory (cov_wave_kernel: drop-in for cov_kernel) or on chip (pass_fused.hip: the
+// steady matrices, P_T, the scalars and G_e of the first KEEP steps in an LDS park of the wave, Z_e / J_e of those steps in the
+// caller's registers -- Cov8Dst::gpark).
 // The reference has no counterpart (dfm_functions.ipynb:21-23 declares `Parametric` only).
 #pragma once
 #include "dfm_cov.h"
@@ -34,15 +36,20 @@ struct Cov8Dst {                 // every matrix row-major [8][8] = indexed by t
     int* fill;                   // [2]
     double* PsInf;               // [64]
     double* SP11; double* SU; double* P0s;   // EM covariance sums [64] each, or null
+    // On-chip hand-over (pass_fused.hip), null elsewhere: entries e < KEEP leave only G_e, at gpark + e * 64 -- their Z_e, J_e
+    // stay in the caller's registers (cov_grid's Zk / Jk) -- and entries e >= KEEP go to tab_over as ever (tab_cap = 0).
+    double* gpark = nullptr;
+    double* PT_g = nullptr;      // a second copy of P_T (global: the EM update reads it) when PT itself is on chip, or null
 };
 
 // R x R threads (one wave at R = 8, a workgroup of 256 / 1024 threads at R = 16 / 32), replicate b.  G: the thread grid with
 // l, i, j (and, R >= 16, its LDS exchange buffers) set.  Cel = element (i, j) of C = Lam' R^-1 Lam, ldfull = sum_i log R_i.
 // wsm: 4 tiles of R x kTileStride<R> doubles of LDS private to the replicate.  NLEV = levels of the scan's carry tree;
 // KEEP = transient steps whose Z_e, J_e stay in registers.  Matrices of Cov8Dst: row-major [R][R], element l = R i + j.
+// Zk, Jk: element (i, j) of Z_e, J_e of the first KEEP steps on return (zero for e >= E).
 template <int R, int NLEV, int KEEP>
 __device__ __forceinline__ void cov_grid(const FastArgs& a, int b, double Cel, double ldfull, double* wsm, const Cov8Dst& o,
-                                         Grid<R>& G) {
+                                         Grid<R>& G, double (&Zk)[KEEP], double (&Jk)[KEEP]) {
     constexpr int TS = kTileStride<R>, RR = R * R, RT = R * kTileStride<R>;
     const int lane = G.l, i = G.i, j = G.j;                  // ("lane" = thread of the grid)
     double* L0 = wsm;
@@ -85,7 +92,6 @@ __device__ __forceinline__ void cov_grid(const FastArgs& a, int b, double Cel, d
     int E = 0;
     // Z_e, J_e of the first KEEP steps stay in registers for the backward sweep (one element per lane each): read
     // back from the table they cost a global round trip per distinct step -- 5 to 8 us each beside streaming waves
-    double Zk[KEEP], Jk[KEEP];
 #pragma unroll
     for (int u = 0; u < KEEP; ++u) { Zk[u] = 0.0; Jk[u] = 0.0; }
     double Zlast = 0.0, Jlast = 0.0, Glast = 0.0;               // entry E - 1 = the steady matrices
@@ -101,8 +107,12 @@ __device__ __forceinline__ void cov_grid(const FastArgs& a, int b, double Cel, d
         const double Gm = dot_rows<R>(LPT, L0, i, j);           // G = Psi' Z   (Z symmetric to rounding)
         const double Omf_new = (Qi - tmp) + Cel;                // Om_p + C
         const bool gsame = G.all_true(close_enough(Omf_new, Omf));
-        double* te = (e < o.tab_cap ? o.tab : o.tab_over) + (size_t)e * 3 * RR;
-        te[lane] = Z; te[RR + lane] = Jr; te[2 * RR + lane] = Gm;
+        if (o.gpark && e < KEEP) {                              // (uniform)
+            o.gpark[(size_t)e * RR + lane] = Gm;
+        } else {
+            double* te = (e < o.tab_cap ? o.tab : o.tab_over) + (size_t)e * 3 * RR;
+            te[lane] = Z; te[RR + lane] = Jr; te[2 * RR + lane] = Gm;
+        }
 #pragma unroll
         for (int u = 0; u < KEEP; ++u) {
             Zk[u] = (u == e) ? Z : Zk[u];
@@ -122,6 +132,7 @@ __device__ __forceinline__ void cov_grid(const FastArgs& a, int b, double Cel, d
     double Ps = Omf;
     const double detOmT = G.sweep_inverse(Ps);                  // P_T
     o.PT[lane] = Ps;
+    if (o.PT_g) o.PT_g[lane] = Ps;
     if (lane == 0) {
         const double sum_ldz = -(detprod.log_value() + (double)(T - E) * log(detM_last));
         const double LD = log(detOmT) + log(detP0) + (double)T * log(detQ) - sum_ldz;
@@ -186,7 +197,9 @@ __device__ __forceinline__ void cov_grid(const FastArgs& a, int b, double Cel, d
     if (lane == 0) { o.fill[0] = fill_lo; o.fill[1] = fill_hi; }
     if (o.SP11) { o.SP11[lane] = SP; o.SU[lane] = SU; }
 
-    // ---------------- steady Z, J, G and the powers G^(L 2^k), J^(L 2^k) for the chunk carries ------------------
+    // ---------------- steady Z, J, G and the powers G^(L 2^k), J^(L 2^k), k < NLEV, for the chunk carries -------
+    // (NLEV = 1: M^L alone -- all that scan_reg / scan_seq of pass_fused.hip read; the doubling levels serve the Kogge-Stone
+    //  carries of meanscan_kernel and of the diagnostics scan)
     {
         const double Zs = Zlast, Js = Jlast, Gs = Glast;
         o.stead[lane] = Zs;
@@ -214,14 +227,26 @@ __device__ __forceinline__ void cov_grid(const FastArgs& a, int b, double Cel, d
         }
     }
 }
+template <int R, int NLEV, int KEEP>
+__device__ __forceinline__ void cov_grid(const FastArgs& a, int b, double Cel, double ldfull, double* wsm, const Cov8Dst& o,
+                                         Grid<R>& G) {
+    double Zk[KEEP], Jk[KEEP];
+    cov_grid<R, NLEV, KEEP>(a, b, Cel, ldfull, wsm, o, G, Zk, Jk);
+}
 
 // ONE wave (64 lanes) per replicate at R = 8 (pass_fused.hip, cov_wave_kernel).  wsm: kCov8ScratchDoubles doubles of LDS.
 template <int NLEV>
 __device__ __forceinline__ void cov_wave8(const FastArgs& a, int b, double Cel, double ldfull, double* wsm, const Cov8Dst& o,
-                                          int lane) {
+                                          int lane, double (&Zk)[kCov8Keep], double (&Jk)[kCov8Keep]) {
     Grid<8> G;
     G.l = lane; G.i = lane >> 3; G.j = lane & 7; G.prow = nullptr; G.red = nullptr; G.tt = nullptr;
-    cov_grid<8, NLEV, kCov8Keep>(a, b, Cel, ldfull, wsm, o, G);
+    cov_grid<8, NLEV, kCov8Keep>(a, b, Cel, ldfull, wsm, o, G, Zk, Jk);
+}
+template <int NLEV>
+__device__ __forceinline__ void cov_wave8(const FastArgs& a, int b, double Cel, double ldfull, double* wsm, const Cov8Dst& o,
+                                          int lane) {
+    double Zk[kCov8Keep], Jk[kCov8Keep];
+    cov_wave8<NLEV>(a, b, Cel, ldfull, wsm, o, lane, Zk, Jk);
 }
 
 // Gram matrix C = Lam' R^-1 Lam and sum log R of replicate b by ONE wave (lane l owns series {2l, 2l+1} + 128 q, q < NDR),

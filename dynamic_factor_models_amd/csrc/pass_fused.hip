@@ -11,8 +11,11 @@
 //   the next ncov waves  COV     Gram matrix C = Lam' R^-1 Lam, the data-independent covariance recursion (dfm_cov8.h: one
 //                                wave per replicate, element per lane), the transient rows of P_smooth, then the fixed-point
 //                                rows of P_smooth (pure stores).  Nothing here depends on the panel, so these waves run
-//                                AHEAD of the stream (replicates j, j + ncov, ... each); their tables go to the
-//                                per-replicate workspace in global memory (L2-resident: written and read by the same CU).
+//                                AHEAD of the stream (replicates j, j + ncov, ... each).  The tables the scan needs stay ON
+//                                CHIP: Z_e, J_e of the transient in the wave's registers, G_e, the steady matrices, P_T and
+//                                the scalars in an LDS park of the wave, until the scan of replicate j - 1 has released the
+//                                single LDS table set; the wave then writes the set itself and raises tab_ready.
+//   one wave             FILL    the fixed-point rows of P_smooth of all but the last replicates (pure stores).
 //   the last 4 waves     SCAN    the time-parallel mean recursion (dfm_scan.h, the algorithm of meanscan_kernel) with
 //                                b_t / w_t in LDS: f_smooth, log-likelihood.  Its internal barriers are 4-wave barriers on
 //                                an LDS counter.
@@ -85,8 +88,23 @@ constexpr int kPfR = 8;
 #define DFM_PF_ECAP 8
 #endif
 constexpr int kPfEcap = DFM_PF_ECAP;                                  // transient covariance steps staged in LDS (later ones: global tab)
-constexpr int kPfNst = stead_mats(kPfR);                    // steady Z, J, G + the carry powers (256 scan threads)
+constexpr int kPfNst = stead_mats(kPfR);                    // steady Z, J, G + the carry powers (256 scan threads): the global layout
 constexpr int kPfNlev = scan_levels(kPfR);
+static_assert(kPfEcap == kCov8Keep, "the covariance wave keeps Z_e, J_e of exactly the staged transient steps in registers");
+// Steady matrices of the LDS table set and of the covariance waves' parks: Z, J, G, then G^(L 2^k), then J^(L 2^k), k < kPfNlevTab.
+// scan_reg / scan_seq read M^L only (their carries run sequentially); the doubling levels serve the Kogge-Stone carries of
+// scan_lds, which exists in the diagnostics build alone.
+#ifdef DFM_DIAG
+constexpr int kPfNlevTab = kPfNlev;
+#else
+constexpr int kPfNlevTab = 1;
+#endif
+constexpr int kPfGL = 3;                                    // index of G^L
+constexpr int kPfJL = 3 + kPfNlevTab;                       // index of J^L: producer (cov_grid<.., kPfNlevTab, ..>) and consumers
+constexpr int kPfNstTab = 3 + 2 * kPfNlevTab;               // steady matrices; P_T follows them
+// park of one covariance wave (doubles): [kPfNstTab] steady matrices, P_T, [kPfEcap] G_e, then xi0 [8], llc, E
+constexpr int kParkG = (kPfNstTab + 1) * 64, kParkXi0 = kParkG + kPfEcap * 64, kParkLlc = kParkXi0 + 8, kParkE = kParkLlc + 1,
+              kParkDoubles = kParkXi0 + 16;
 constexpr int kPfScanWaves = kScanThreads / 64;             // 4
 constexpr int kPfMaxCov = 2;
 // (development A/B: -DDFM_PF_DEFER=n.  Round 4, with the non-temporal panel stream: 1 -> 0.2064 ms, 2 -> 0.2044, 3 -> 0.2015, 4 -> 0.1955 at
@@ -103,10 +121,10 @@ constexpr unsigned kPfLdsLimit = 160u * 1024u;
 // flags (unsigned, LDS): monotone counters
 constexpr int kFBtReady = 0;      // [2] arrivals of stream waves per b_t buffer
 constexpr int kFScanDone = 2;     // replicates (local index) whose scan is complete
-constexpr int kFCovDone = 3;      // [kPfMaxCov] replicates finished by each covariance wave
+constexpr int kFCovDone = 3;      // [kPfMaxCov] replicates handed over by each covariance wave (diagnostic: nobody waits on it)
 constexpr int kFScanBar = 5;      // arrivals at the scan waves' barrier
 constexpr int kFAbort = 6;
-constexpr int kFTabReady = 7;     // replicates whose tables the mover has put into the LDS table set
+constexpr int kFTabReady = 7;     // replicates whose tables their covariance wave has put into the LDS table set
 constexpr int kFScanArrive = 8;   // scan_reg: scan waves that have finished their part of a replicate (4 per replicate)
 constexpr int kFStreamWaits = 9;  // 1 while stream wave 0 waits for a b_t buffer, i.e. for the scan: the scan is then the critical path
 constexpr int kFCount = 64;
@@ -204,10 +222,11 @@ __device__ __forceinline__ void pf_fill_rows(double* Prep, int lo, int hi, int n
 // byte offsets into the dynamic LDS of pass_fused_kernel (computed by the host)
 struct PfLds {
     unsigned flags;   // kFCount unsigned
-    unsigned smat;    // [kPfNst + 1][64] doubles: steady matrices, then P_T        (scan staging)
+    unsigned smat;    // [kPfNstTab + 1][64] doubles: steady matrices, then P_T     (scan staging)
     unsigned ctab;    // [kPfEcap][3][64] doubles: Z_e, J_e, G_e                     (scan staging)
     unsigned misc;    // kMiscDoubles doubles
     unsigned covws;   // ncov x kCov8ScratchDoubles doubles
+    unsigned park;    // ncov x kParkDoubles doubles: a covariance wave's finished tables until the table set is free
     unsigned sa, sb;  // [32][8] doubles each (carry scan)
     unsigned bt;      // nbuf x [T4][8] doubles: b_t, then w_t
     unsigned bt_stride;   // doubles between the b_t buffers
@@ -217,6 +236,9 @@ struct PfLds {
     int nt;           // non-temporal hint on the panel stream (dma16f)
 };
 
+#if defined(DFM_PF_FALLBACK_LDS) && !defined(DFM_DIAG)
+#error "scan_lds needs every carry power in the table set: build with -DDFM_DIAG"
+#endif
 #if defined(DFM_DIAG) || defined(DFM_PF_FALLBACK_LDS)   // the round-2 scan: A/B against scan_reg in the diagnostics build only (DFM_SCAN_ABL bit 9); production: scan_reg, scan_seq
 // ------------------------------------------------------------------------------------------------------------------
 // The scan of one replicate, b_t in LDS, tables staged in LDS.  Called by the 4 scan waves (tid 0 .. 255); `sync` is their
@@ -398,7 +420,7 @@ __device__ __forceinline__ void scan_reg(const FastArgs& a, int b, int tid, cons
     auto mark = [&](int k) {
         if (pslot && tid == 0) pslot[k] = (double)__builtin_amdgcn_s_memrealtime();
     };
-    constexpr int R = kPfR, NLEV = kPfNlev, NST = kPfNst, LM = kRegL;
+    constexpr int R = kPfR, NST = kPfNstTab, LM = kRegL;
     const int c = tid / R, i = tid % R, lane = tid & 63;
     const int T = a.T, r = a.r, L = a.L;
     const int ts = E - 1;                                     // <= kPfEcap
@@ -461,7 +483,7 @@ __device__ __forceinline__ void scan_reg(const FastArgs& a, int b, int tid, cons
     double v = xi;
     {
         double ML[R];
-        load_xperm<R>(ML, s_mat + 3 * R * R, i);              // G^L
+        load_xperm<R>(ML, s_mat + kPfGL * R * R, i);          // G^L
         for (int k0 = 0; k0 <= wlo; k0 += 8) {                // (uniform: blocks of 8 chunks up to this wave's own)
             double ek[8];
 #pragma unroll
@@ -524,7 +546,7 @@ __device__ __forceinline__ void scan_reg(const FastArgs& a, int b, int tid, cons
     double vb = 0.0;
     if (wlo < clast) {                                        // (uniform) this wave has a group below the top chunk
         double JL[R];
-        load_xperm<R>(JL, s_mat + (size_t)(3 + NLEV) * R * R, i);   // J^L
+        load_xperm<R>(JL, s_mat + (size_t)kPfJL * R * R, i);        // J^L
         vb = sEb[clast * R + i];
         for (int k0 = clast - 1; k0 > wlo; k0 -= 8) {         // chunks k0, k0 - 1, .. (those above c apply)
             double ek[8];
@@ -602,7 +624,7 @@ __device__ __forceinline__ void scan_reg(const FastArgs& a, int b, int tid, cons
 __device__ __forceinline__ void scan_seq(const FastArgs& a, int b, int tid, double* bt, const double* s_tab, const double* tab_over,
                                          const double* s_mat, const double* xi0p, const double* llcp, int E, const double* ssum, int nseg,
                                          unsigned* arrive, unsigned arrive_last, unsigned* scan_done, unsigned done_value) {
-    constexpr int R = kPfR, NST = kPfNst;
+    constexpr int R = kPfR, NST = kPfNstTab;
     const int lane = tid & 63, i = tid % R, c = tid / R;
     const int T = a.T, r = a.r;
     const int ts = E - 1;
@@ -754,7 +776,7 @@ __global__ __launch_bounds__(kPfMaxThreads) void pass_fused_kernel(CollapseArgs 
     const int N = a.N, T = a.T, B = a.B;
     const int G = (int)gridDim.x;
     const int nrep_wg = (B - (int)blockIdx.x + G - 1) / G;   // replicates of this workgroup
-    // P_smooth fills deferred to the tail (see the mover)
+    // P_smooth fills deferred to the tail (see the fill wave)
 #ifdef DFM_DIAG   // DFM_SCAN_ABL bits 12-14 = count + 1
     const int ndefer = (fa.P_smooth == nullptr) ? 0 : (((fa.abl >> 12) & 7) ? ((fa.abl >> 12) & 7) - 1 : kPfDeferDefault);
 #else
@@ -793,15 +815,22 @@ __global__ __launch_bounds__(kPfMaxThreads) void pass_fused_kernel(CollapseArgs 
         // lane roles of v_mfma_f64_4x4x4 (collapse_mfma.hip)
         const int K = lane >> 4, blk = (lane >> 2) & 3, q = lane & 3;
         const int g = blk >> 1, h = blk & 1;
-        int tq = (T + nsw - 1) / nsw;
+        // Segments are whole row blocks: T is cut into units of lcm(4, m) rows (m rows: the period after which a row starts on
+        // a 128-byte boundary again) and the waves get balanced unit counts, the first ones one more.  Only the last block of
+        // the last segment can be partial -- <= 3 repeated rows per replicate, not per wave.
+        int unit;
         {
             unsigned gg = rowB & 127u;
             gg = gg == 0 ? 128u : (gg & (~gg + 1u));
-            const int m = (int)(128u / gg);
-            tq = ((tq + m - 1) / m) * m;                         // segments start on 128-byte boundaries
+            const int m = (int)(128u / gg);                      // 1, 2, 4, 8 or 16
+            unit = m < 4 ? 4 : m;
         }
-        const int ta = (wave * tq < T) ? wave * tq : T;
-        const int tb = (ta + tq < T) ? ta + tq : T;
+        const int nunit = (T + unit - 1) / unit;
+        const int ubase = nunit / nsw, urem = nunit % nsw;
+        const int ua = wave * ubase + (wave < urem ? wave : urem);
+        const int ub = ua + ubase + (wave < urem ? 1 : 0);
+        const int ta = (ua * unit < T) ? ua * unit : T;
+        const int tb = (ub * unit < T) ? ub * unit : T;
         const int nrows = tb - ta;
         const int nblk = (nrows + 3) / 4;
         const unsigned ringB = NS * SB;
@@ -971,12 +1000,12 @@ __global__ __launch_bounds__(kPfMaxThreads) void pass_fused_kernel(CollapseArgs 
             // ---- the deferred P_smooth fills: the panel is through, HBM is idle but for the last scan's outputs ----------
             if (ndefer > 0) {
                 wait_vmf<0>();
-                const int nact = (T + tq - 1) / tq;               // stream waves that own periods (they all get here)
+                const int nact = nunit < nsw ? nunit : nsw;       // stream waves that own periods (they all get here)
                 const int npr = fa.r * (fa.r + 1) / 2;
                 double* ps = reinterpret_cast<double*>(const_cast<char*>(ring));   // this wave's ring is free now
                 for (int j = (nrep - ndefer > 0 ? nrep - ndefer : 0); j < nrep; ++j) {
                     const int b = (int)blockIdx.x + j * G;
-                    // (the covariance wave of replicate j published these long ago; the mover has raised tab_ready past j)
+                    // (the covariance wave of replicate j published these before it raised tab_ready past j)
                     if (!pf_wait_ge(flags + kFTabReady, (unsigned)(j + 1), flags + kFAbort)) break;
                     const int flo = __builtin_amdgcn_readfirstlane(ld_dev(fa.fill + 2 * b));
                     const int fhi = __builtin_amdgcn_readfirstlane(ld_dev(fa.fill + 2 * b + 1));
@@ -1006,14 +1035,30 @@ __global__ __launch_bounds__(kPfMaxThreads) void pass_fused_kernel(CollapseArgs 
         }
     } else if (wave < nsw + ncov) {
         // ================= COV: Gram matrix, covariance recursion, transient rows of P_smooth -- ahead of the stream ====
+        // Hand-over.  The wave that computed the tables of local replicate j keeps them on chip -- Z_e, J_e of the transient in
+        // registers, everything else in its LDS park -- until the scan of replicate j - 1 has released the single LDS table set,
+        // copies them into the set, raises tab_ready to j + 1, and only then starts replicate j + ncov.  Nothing the scan needs
+        // takes a round trip through global memory (19.5 KB out and 19.5 KB back per replicate, the second leg 50-100 us after
+        // the first, when the stream had turned L2 over ten times).
+        // No deadlock: the wave of replicate j waits for scan j - 1 only; scan j - 1 needs the tables of j - 1, which the other
+        // covariance wave (the same one if ncov = 1) wrote after scan j - 2, and b_t of j - 1, for which the stream waits on
+        // scan j - 1 - nbuf at the latest -- every wait points at a strictly smaller replicate, and replicate 0 waits for nothing.
+        // Slack (recorded timeline, B = 1024 at the headline shape: a replicate streams in ~47 us, a chain takes ~50 us): the wave
+        // hands replicate j over when scan j - 1 ends, its chain for j + 2 ends ~50 us later, and scan j + 2 can start when scan
+        // j + 1 ends, two stream periods (~94 us) after scan j - 1: ~44 us to spare.  On a box whose chain takes 90 us it is ~4 us;
+        // beyond that the scans wait for the chains -- as they did before, when a wave had to finish a chain per 94 us as well.
         const int cw = wave - nsw;
         double* ws = reinterpret_cast<double*>(smem + ly.covws) + (size_t)cw * kCov8ScratchDoubles;
         double* Cs = ws + 5 * kCov8TileDoubles;                  // Gram matrix
+        double* park = reinterpret_cast<double*>(smem + ly.park) + (size_t)cw * kParkDoubles;
+        double* s_mat = reinterpret_cast<double*>(smem + ly.smat);
+        double* s_tab = reinterpret_cast<double*>(smem + ly.ctab);
         // a latency chain (ahead of the stream after the first replicates).  (Round 3: dropping to priority 0 after the
         // workgroup's first replicate -- the only one whose chain somebody waits for -- measured neutral: the stream's first
         // two rounds are slower because the covariance waves' work shares the CU, not because of their priority.)
         __builtin_amdgcn_s_setprio(2);
-        for (int b = (int)blockIdx.x + cw * G; b < B; b += ncov * G) {
+        int j = cw;
+        for (int b = (int)blockIdx.x + cw * G; b < B; b += ncov * G, j += ncov) {
             stamp(b, 6);
             const double ld = gram_mfma8<STEPS, NDR>(fa.Lam + (size_t)b * N * R, fa.Rv + (size_t)b * N, N, lane, Cs,
                                                      prof ? a.scol + (size_t)b * T + 36 : nullptr);   // (null in the production build)
@@ -1022,86 +1067,69 @@ __global__ __launch_bounds__(kPfMaxThreads) void pass_fused_kernel(CollapseArgs 
             wave_lds_sync();
             __builtin_amdgcn_sched_barrier(0);
             Cov8Dst o;
-            o.tab = fa.tab + (size_t)b * T * 3 * 64; o.tab_cap = T; o.tab_over = o.tab;
-            o.stead = fa.stead + (size_t)b * kPfNst * 64;
-            o.PT = fa.PT + (size_t)b * 64; o.xi0 = fa.xi0 + (size_t)b * 8; o.llc = fa.llc + b; o.E = fa.E + b;
+            o.tab = nullptr; o.tab_cap = 0; o.tab_over = fa.tab + (size_t)b * T * 3 * 64;   // entries e >= kPfEcap only (slow Riccati)
+            o.gpark = park + kParkG;
+            o.stead = park;
+            o.PT = park + kPfNstTab * 64; o.xi0 = park + kParkXi0; o.llc = park + kParkLlc;
+            o.E = reinterpret_cast<int*>(park + kParkE);
             o.fill = fa.fill + 2 * b; o.PsInf = fa.PsInf + (size_t)b * 64;
             o.SP11 = fa.SP11 ? fa.SP11 + (size_t)b * 64 : nullptr;
             o.SU = fa.SP11 ? fa.SU + (size_t)b * 64 : nullptr;
             o.P0s = fa.SP11 ? fa.P0s + (size_t)b * 64 : nullptr;
+            o.PT_g = fa.SP11 ? fa.PT + (size_t)b * 64 : nullptr;  // (the EM update behind the pass reads P_T)
             stamp(b, 7);                                          // Gram done
-            cov_wave8<kPfNlev>(fa, b, Cel, ld, ws, o, lane);
+            double Zk[kCov8Keep], Jk[kCov8Keep];
+            cov_wave8<kPfNlevTab>(fa, b, Cel, ld, ws, o, lane, Zk, Jk);
             wave_lds_sync();
             stamp(b, 8);                                          // covariance recursion done
-            // the tables are complete: the scan of this replicate may start (its waves also write the fixed-point rows
-            // of P_smooth -- 144 KB of pure stores that would hold this latency chain up for 15 us)
-            pf_signal(flags + kFCovDone + cw, lane);
-        }
-    } else if (wave == nsw + ncov) {
-        // ================= MOVER: tables of replicate j from the workspace into LDS, one replicate ahead of the scan =====
-        // Under the streaming load a global round trip of this CU takes 5-8 us (its requests queue behind the DMA loads), and
-        // the scan group needed two of them per replicate on its critical path.  This wave takes them off it: as soon as a
-        // covariance wave has published replicate j it loads the tables into REGISTERS (one matrix element per lane: 32
-        // matrices = 64 VGPRs), waits for the scan of replicate j - 1 to release the single LDS table set, writes it and
-        // raises tab_ready.  It also writes the fixed-point rows of P_smooth (144 KB of pure stores per replicate).
-        double* s_mat = reinterpret_cast<double*>(smem + ly.smat);
-        double* s_tab = reinterpret_cast<double*>(smem + ly.ctab);
-        double* s_ps = misc + kMiscPs;
-        const int nfix0 = kPfEcap < T ? kPfEcap : T;
-        __builtin_amdgcn_s_setprio(1);
-        int b = blockIdx.x;
-        for (int j = 0; b < B; b += G, ++j) {
-            if (!pf_wait_ge(flags + kFCovDone + (j % ncov), (unsigned)(j / ncov + 1), flags + kFAbort)) break;
-            stamp(b, 4);
-            const double* stead = fa.stead + (size_t)b * kPfNst * 64;
-            const double* tab = fa.tab + (size_t)b * T * 3 * 64;
-            double ms[kPfNst + 1], mt[kPfEcap * 3];
-#pragma unroll
-            for (int k = 0; k < kPfNst; ++k) ms[k] = stead[k * 64 + lane];
-            ms[kPfNst] = fa.PT[(size_t)b * 64 + lane];
-#pragma unroll
-            for (int k = 0; k < kPfEcap * 3; ++k) mt[k] = (k < nfix0 * 3) ? tab[k * 64 + lane] : 0.0;
-            // one batch: every load is issued before the first one is consumed (a round trip is 5-8 us here)
-            const int Ev = ld_dev(fa.E + b);
-            // xi0 [8] then llc: adjacent in neither array, so two loads under lane predicates folded into one select
-            const double xiv = ld_dev(fa.xi0 + (size_t)b * R + (lane & 7));
-            const double llv = ld_dev(fa.llc + b);
-            const int npr = fa.r * (fa.r + 1) / 2;
-            int flo = 0, fhi = 0;
-            double psv = 0.0;
-            if (fa.P_smooth) {
-                flo = ld_dev(fa.fill + 2 * b);
-                fhi = ld_dev(fa.fill + 2 * b + 1);
-                int ri = 0;                                       // packed (caller's r) copy of P_s,inf
-                const int lv = lane < npr ? lane : 0;
-                while ((ri + 1) * (ri + 2) / 2 <= lv) ++ri;
-                psv = ld_dev(fa.PsInf + (size_t)b * 64 + ri * R + (lv - ri * (ri + 1) / 2));
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            const int E = __builtin_amdgcn_readfirstlane(Ev);
-            const double xl = lane < R ? xiv : llv;
-            const int fill_lo = __builtin_amdgcn_readfirstlane(flo), fill_hi = __builtin_amdgcn_readfirstlane(fhi);
             // the LDS table set is free once the scan of the previous replicate is complete
             if (j >= 1) {
                 if (!pf_wait_ge(flags + kFScanDone, (unsigned)j, flags + kFAbort)) break;
             }
+            stamp(b, 4);
 #pragma unroll
-            for (int k = 0; k <= kPfNst; ++k) s_mat[k * 64 + lane] = ms[k];
+            for (int k = 0; k <= kPfNstTab; ++k) s_mat[k * 64 + lane] = park[k * 64 + lane];
 #pragma unroll
-            for (int k = 0; k < kPfEcap * 3; ++k) s_tab[k * 64 + lane] = mt[k];
-            if (lane <= R) misc[kMiscXi0 + lane] = xl;            // xi0 [8], then llc
-            if (lane == 0) misc[kMiscE] = (double)E;
-            pf_signal(flags + kFTabReady, lane);
-            stamp(b, 5);
-            // rows [lo, hi) of P_smooth equal the backward fixed point: fire-and-forget 16-byte stores.  The fills of the
-            // workgroup's LAST replicates are left to the stream waves, who write them once their last row has been issued:
-            // HBM is the bottleneck while the panel streams and idle during the scan-only tail of the kernel
-            if (fill_hi > fill_lo && j < nrep_wg - ndefer) {
-                if (lane < npr) s_ps[lane] = psv;
-                wave_lds_sync();
-                pf_fill_rows(fa.P_smooth + (size_t)b * T * npr, fill_lo, fill_hi, npr, s_ps, lane, 0, 1);
-                wave_lds_sync();
+            for (int e = 0; e < kPfEcap; ++e) {                   // (entries past the transient are never read)
+                s_tab[(3 * e) * 64 + lane] = Zk[e];
+                s_tab[(3 * e + 1) * 64 + lane] = Jk[e];
+                s_tab[(3 * e + 2) * 64 + lane] = park[kParkG + e * 64 + lane];
             }
+            if (lane <= R) misc[kMiscXi0 + lane] = park[kParkXi0 + lane];   // xi0 [8], then llc
+            if (lane == 0) misc[kMiscE] = (double)o.E[0];
+            // fill / PsInf (global) and the set are visible to the workgroup before tab_ready moves.  The counter is at j here:
+            // replicate j - 1 was handed over before scan j - 1 could end.
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+            if (lane == 0) {
+                __hip_atomic_store(flags + kFTabReady, (unsigned)(j + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                __hip_atomic_fetch_add(flags + kFCovDone + cw, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            }
+            wave_lds_sync();                                      // the park is read out before the next chain writes it
+            stamp(b, 5);
+        }
+    } else if (wave == nsw + ncov) {
+        // ================= FILL: the fixed-point rows of P_smooth, all but the workgroup's last replicates ==============
+        // Rows [lo, hi) of P_smooth equal the backward fixed point: 144 KB of fire-and-forget 16-byte stores per replicate, which
+        // would hold a covariance wave's latency chain up for 15 us.  They are written when the tables of the replicate have been
+        // handed over.  The fills of the workgroup's LAST replicates are left to the stream waves, who write them once their last
+        // row has been issued: HBM is the bottleneck while the panel streams and idle during the scan-only tail of the kernel.
+        double* s_ps = misc + kMiscPs;
+        __builtin_amdgcn_s_setprio(1);
+        const int npr = fa.r * (fa.r + 1) / 2;
+        int b = blockIdx.x;
+        for (int j = 0; j < nrep_wg - ndefer && fa.P_smooth != nullptr; b += G, ++j) {
+            if (!pf_wait_ge(flags + kFTabReady, (unsigned)(j + 1), flags + kFAbort)) break;
+            const int fill_lo = __builtin_amdgcn_readfirstlane(ld_dev(fa.fill + 2 * b));
+            const int fill_hi = __builtin_amdgcn_readfirstlane(ld_dev(fa.fill + 2 * b + 1));
+            if (fill_hi <= fill_lo) continue;
+            int ri = 0;                                           // packed (caller's r) copy of P_s,inf
+            const int lv = lane < npr ? lane : 0;
+            while ((ri + 1) * (ri + 2) / 2 <= lv) ++ri;
+            const double psv = ld_dev(fa.PsInf + (size_t)b * 64 + ri * R + (lv - ri * (ri + 1) / 2));
+            if (lane < npr) s_ps[lane] = psv;
+            wave_lds_sync();
+            pf_fill_rows(fa.P_smooth + (size_t)b * T * npr, fill_lo, fill_hi, npr, s_ps, lane, 0, 1);
+            wave_lds_sync();
         }
     } else if (wave < nsw + ncov + 1 + kPfScanWaves) {
         // ================= SCAN: the mean recursion of every replicate, one behind the stream ==========================
@@ -1189,10 +1217,11 @@ static PfLds pf_layout(int T, int N, int nsw, int ncov, int nbuf) {
     unsigned off = 0;
     auto take = [&](unsigned bytes) { const unsigned at = off; off += (bytes + 255u) & ~255u; return at; };
     l.flags = take(kFCount * 4);
-    l.smat = take((kPfNst + 1) * 64 * 8);
+    l.smat = take((kPfNstTab + 1) * 64 * 8);
     l.ctab = take(kPfEcap * 3 * 64 * 8);
     l.misc = take(kMiscDoubles * 8);
     l.covws = take((unsigned)ncov * kCov8ScratchDoubles * 8);
+    l.park = take((unsigned)ncov * kParkDoubles * 8);
     l.sa = take(32 * 8 * 8);
     l.sb = take(32 * 8 * 8);
     const unsigned btb = (unsigned)((T + 3) / 4 * 4) * 8 * 8;
@@ -1209,7 +1238,7 @@ static PfLds pf_layout(int T, int N, int nsw, int ncov, int nbuf) {
 static PfLds pf_pick(int T, int N, int want_nsw, int want_ncov) {
     int ncov = want_ncov > 0 ? want_ncov : kPfMaxCov;
     if (ncov > kPfMaxCov) ncov = kPfMaxCov;
-    int cap = kPfMaxWaves - kPfScanWaves - 1 - ncov;        // one mover wave
+    int cap = kPfMaxWaves - kPfScanWaves - 1 - ncov;        // one fill wave
     // default: one stream wave per SIMD -- a second one on a SIMD is starved by the oldest-first arbitration (its segment
     // ends 20 us after the others') and the per-CU streaming rate is the same with 4 rings as with 5 (measured: B = 1024
     // 0.233 vs 0.245 ms, B = 8192 1.62 vs 1.68 ms)
