@@ -197,6 +197,14 @@ int hip_fail(dfm_handle* h, hipError_t e, const char* where) {
         if (_e != hipSuccess) return hip_fail(h, _e, #expr); \
     } while (0)
 
+// The element-wise kernels of this file: one thread per element, 256 per block, on h->stream.  n = threads wanted (>= 1).
+template <class... KArgs, class... Args>
+int launch_1d(dfm_handle* h, void (*kernel)(KArgs...), size_t n, Args... args) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, static_cast<KArgs>(args)...);
+    HIP_TRY(h, hipGetLastError());
+    return 0;
+}
+
 struct ProfScope {  // records an event pair around one kernel launch when profiling is on
     dfm_handle* h; int idx = -1; hipStream_t st;
     ProfScope(dfm_handle* h_, int kid, hipStream_t st_ = nullptr) : h(h_), st(st_ ? st_ : h_->stream) {
@@ -507,6 +515,18 @@ __global__ void pad_params_kernel(int B, int N, int r, int Rp, int Rl, const dou
 struct PaddedParams {
     const double *Lam, *A, *Q, *mu0, *P0;
 };
+// The buffers of one planned call.  Lam .. P0: the parameters in the layout the kernels read (padded, or the companion form), which
+// an EM run updates in place; fsm, Psm, llbuf, active: what the E-steps of an EM plan write (null for a plain pass).  model_bufs points
+// all of them into the workspace; a driver whose layout is the caller's points them at the caller's arrays instead.
+struct ModelBufs {
+    double *Lam, *A, *Q, *mu0, *P0, *fsm, *Psm, *llbuf;
+    int* active;
+    PaddedParams pp() const { return PaddedParams{Lam, A, Q, mu0, P0}; }
+};
+ModelBufs model_bufs(dfm_handle* h, const Plan& p) {
+    return ModelBufs{at<double>(h, p.LamP), at<double>(h, p.AP), at<double>(h, p.QP), at<double>(h, p.mu0P), at<double>(h, p.P0P),
+                     at<double>(h, p.fsm), at<double>(h, p.Psm), at<double>(h, p.llbuf), at<int>(h, p.active)};
+}
 
 int pad_params(dfm_handle* h, const Plan& p, int B, int N, int r, const double* Lam, const double* A,
                const double* Q, const double* mu0, const double* P0, PaddedParams* out) {
@@ -515,15 +535,9 @@ int pad_params(dfm_handle* h, const Plan& p, int B, int N, int r, const double* 
         return 0;
     }
     const size_t n = (size_t)B * N * p.Rp > (size_t)B * p.Rp * p.Rp ? (size_t)B * N * p.Rp : (size_t)B * p.Rp * p.Rp;
-    const int threads = 256;
-    const unsigned blocks = (unsigned)((n + threads - 1) / threads);
-    hipLaunchKernelGGL(pad_params_kernel, dim3(blocks), dim3(threads), 0, h->stream, B, N, r, p.Rp, p.Rc ? p.Rc : p.Rp, Lam, A, Q,
-                       mu0, P0, at<double>(h, p.LamP), at<double>(h, p.AP), at<double>(h, p.QP),
-                       at<double>(h, p.mu0P), at<double>(h, p.P0P));
-    HIP_TRY(h, hipGetLastError());
-    *out = PaddedParams{at<double>(h, p.LamP), at<double>(h, p.AP), at<double>(h, p.QP), at<double>(h, p.mu0P),
-                        at<double>(h, p.P0P)};
-    return 0;
+    const ModelBufs mb = model_bufs(h, p);
+    *out = mb.pp();
+    return launch_1d(h, pad_params_kernel, n, B, N, r, p.Rp, p.Rc ? p.Rc : p.Rp, Lam, A, Q, mu0, P0, mb.Lam, mb.A, mb.Q, mb.mu0, mb.P0);
 }
 
 
@@ -562,14 +576,17 @@ int odd_pad(dfm_handle* h, int B, int T, int N, int r, const double* panel, cons
     out->panel = static_cast<double*>(h->odd.p);
     out->Lam = out->panel + al(n_panel);
     out->R = out->Lam + al(n_lam);
-    auto grid = [](size_t n) { return dim3((unsigned)((n + 255) / 256)); };
     const bool same = keep_panel && h->odd_panel_src == panel && h->odd_panel_dims[0] == B && h->odd_panel_dims[1] == T && h->odd_panel_dims[2] == N;
-    if (!same) hipLaunchKernelGGL(pad_last_col_kernel, grid(n_panel), dim3(256), 0, h->stream, (size_t)B * T, N, panel, out->panel);
+    if (!same)
+        if (int rc = launch_1d(h, pad_last_col_kernel, n_panel, (size_t)B * T, N, panel, out->panel)) return rc;
     h->odd_panel_src = panel; h->odd_panel_dims[0] = B; h->odd_panel_dims[1] = T; h->odd_panel_dims[2] = N;
-    hipLaunchKernelGGL(copy_series_rows_kernel, grid(n_lam), dim3(256), 0, h->stream, (size_t)B, N, N + 1, r, 0.0, Lam, out->Lam);
-    hipLaunchKernelGGL(copy_series_rows_kernel, grid(n_R), dim3(256), 0, h->stream, (size_t)B, N, N + 1, 1, 1.0, R, out->R);
-    HIP_TRY(h, hipGetLastError());
-    return 0;
+    if (int rc = launch_1d(h, copy_series_rows_kernel, n_lam, (size_t)B, N, N + 1, r, 0.0, Lam, out->Lam)) return rc;
+    return launch_1d(h, copy_series_rows_kernel, n_R, (size_t)B, N, N + 1, 1, 1.0, R, out->R);
+}
+// ... and, after an EM run on the padded problem, the N series' loadings and variances back into the caller's arrays
+int odd_unpad(dfm_handle* h, int B, int N, int r, const OddPad& o, double* Lam, double* R) {
+    if (int rc = launch_1d(h, copy_series_rows_kernel, (size_t)B * N * r, (size_t)B, N + 1, N, r, 0.0, o.Lam, Lam)) return rc;
+    return launch_1d(h, copy_series_rows_kernel, (size_t)B * N, (size_t)B, N + 1, N, 1, 0.0, o.R, R);
 }
 
 struct EmOpts {          // all-null for a plain pass
@@ -625,10 +642,12 @@ bool pipe_eligible(const dfm_handle* h, int B, int N, int r, unsigned flags) {
 template <class Body>
 int pipe_run(dfm_handle* h, int B, size_t slot_bytes, Body body) {
     const int Bs = pipe_sub(h), S = (B + Bs - 1) / Bs;
-    const size_t slot = (slot_bytes + 255) & ~(size_t)255;
-    if (int rc = ensure_ws(h, 2 * slot + (size_t)B * sizeof(int))) return rc;
+    size_t off = 0;
+    take(off, slot_bytes);
+    const size_t slot = take(off, slot_bytes), o_agg = take(off, (size_t)B * sizeof(int));   // slots at 0 and `slot`, then the flags
+    if (int rc = ensure_ws(h, off)) return rc;
     char* base = static_cast<char*>(h->ws.p);
-    int* agg = reinterpret_cast<int*>(base + 2 * slot);       // chunk_fail of every replicate (dfm_chunk_fallbacks)
+    int* agg = reinterpret_cast<int*>(base + o_agg);          // chunk_fail of every replicate (dfm_chunk_fallbacks)
     hipStream_t main = h->stream;
     HIP_TRY(h, hipEventRecord(h->ev_fork, main));
     HIP_TRY(h, hipStreamWaitEvent(h->post, h->ev_fork, 0));
@@ -1006,31 +1025,24 @@ __global__ void copy_block_kernel(size_t nb, int rs, int cs, int rd, int cd, con
     dst[tid] = src[(b * rs + i) * cs + j];
 }
 int copy_block(dfm_handle* h, size_t nb, int rs, int cs, int rd, int cd, const double* src, double* dst) {
-    const size_t n = nb * rd * cd;
-    hipLaunchKernelGGL(copy_block_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, nb, rs, cs,
-                       rd, cd, src, dst);
-    HIP_TRY(h, hipGetLastError());
-    return 0;
+    return launch_1d(h, copy_block_kernel, nb * rd * cd, nb, rs, cs, rd, cd, src, dst);
 }
 
-// One EM iteration on PADDED, writable device parameters (Lam [B][N][Rp], A/Q/P0 [B][Rp][Rp], mu0 [B][Rp]).
-int em_iteration(dfm_handle* h, const Plan& p, int B, int T, int N, const double* panel, double* LamP,
-                 double* Rv, double* AP, double* QP, double* mu0P, double* P0P, double* fsm, double* Psm,
-                 double* loglik, EmOpts eo) {
+// One EM iteration on PADDED, writable device parameters (mb.Lam [B][N][Rp], A/Q/P0 [B][Rp][Rp], mu0 [B][Rp]).
+int em_iteration(dfm_handle* h, const Plan& p, int B, int T, int N, const double* panel, const ModelBufs& mb, double* Rv,
+                 const EmOpts& eo) {
     const int Rp = p.Rc ? p.Rc : p.Rp;          // width of the loadings (narrower than the state for a companion model)
-    PaddedParams pp{LamP, AP, QP, mu0P, P0P};
-    eo.A_out = AP; eo.Q_out = QP; eo.mu0_out = mu0P; eo.P0_out = P0P;
     h->defer_em = p.ms_mfma && p.Rp <= 8 && !h->opt.no_defer_em;  // the transition M-step rides in the loadings step's launch
     h->have_deferred_em = false;
-    const int rc_pass = enqueue_pass(h, p, B, T, N, Rp, panel, pp, Rv, fsm, Psm, loglik, &eo);
+    const int rc_pass = enqueue_pass(h, p, B, T, N, Rp, panel, mb.pp(), Rv, mb.fsm, mb.Psm, mb.llbuf, &eo);
     h->defer_em = false;
     if (rc_pass) return rc_pass;
     MstepArgs ma;
     ma.B = B; ma.T = T; ma.N = N; ma.r = Rp;
-    ma.panel = panel; ma.fsm = fsm; ma.Psm = Psm;
+    ma.panel = panel; ma.fsm = mb.fsm; ma.Psm = mb.Psm;
     ma.S11 = at<double>(h, p.S11); ma.S11inv = at<double>(h, p.Sxf);
     ma.Dmiss = mstep_needs_dmiss(Rp, N) ? at<double>(h, p.Dmiss) : nullptr;
-    ma.active = eo.active; ma.Lam_out = LamP; ma.R_out = Rv; ma.lam_stride = Rp; ma.min_cells = 1;
+    ma.active = eo.active; ma.Lam_out = mb.Lam; ma.R_out = Rv; ma.lam_stride = Rp; ma.min_cells = 1;
     if (p.ms_mfma) {   // balanced panel: second panel read on the matrix pipe
         ProfScope ps(h, K_MSTEP_MFMA);
         HIP_TRY(h, launch_mstep_mfma(Rp, ma, p.ms_wpr, at<double>(h, p.ms_ws), h->stream, h->have_deferred_em ? &h->deferred_em : nullptr));
@@ -1054,12 +1066,13 @@ int em_iteration(dfm_handle* h, const Plan& p, int B, int T, int N, const double
     return 0;
 }
 
-// The loop of every EM driver: iterations k_first .. k_end - 1 of a run of max_iter, one(eo) enqueues iteration eo.k.  With
-// bookkeeping (loglik_path; iters and the device flags `active` go with it) a run that starts at 0 gets its path NaN-filled and its
-// counts zeroed, and with poll && tol > 0 the loop stops launching once no replicate of this batch is active.
+// The loop of every EM driver: iterations k_first .. k_end - 1 of a run of max_iter, one(eo) enqueues iteration eo.k; the transition
+// M-step of every iteration writes mb's parameters, and mb.active are the device flags.  With bookkeeping (loglik_path; iters and the
+// flags go with it) a run that starts at 0 gets its path NaN-filled and its counts zeroed, and with poll && tol > 0 the loop stops
+// launching once no replicate of this batch is active.
 template <class One>
-int em_loop(dfm_handle* h, int B, int k_first, int k_end, int max_iter, double tol, double* loglik_path, int* iters, int* active,
-            bool poll, One one) {
+int em_loop(dfm_handle* h, int B, int k_first, int k_end, int max_iter, double tol, double* loglik_path, int* iters,
+            const ModelBufs& mb, bool poll, One one) {
     if (loglik_path && k_first == 0) {
         HIP_TRY(h, hipMemsetAsync(loglik_path, 0xFF, (size_t)B * max_iter * sizeof(double), h->stream));  // NaN
         HIP_TRY(h, hipMemsetAsync(iters, 0, (size_t)B * sizeof(int), h->stream));
@@ -1068,10 +1081,11 @@ int em_loop(dfm_handle* h, int B, int k_first, int k_end, int max_iter, double t
     std::vector<int> act_host(stop_early ? (size_t)B : 0);
     for (int k = k_first; k < k_end; ++k) {
         EmOpts eo;
-        eo.active = active; eo.iters = iters; eo.ll_path = loglik_path; eo.k = k; eo.max_iter = max_iter; eo.tol = tol;
+        eo.A_out = mb.A; eo.Q_out = mb.Q; eo.mu0_out = mb.mu0; eo.P0_out = mb.P0;
+        eo.active = mb.active; eo.iters = iters; eo.ll_path = loglik_path; eo.k = k; eo.max_iter = max_iter; eo.tol = tol;
         if (int rc = one(eo)) return rc;
         if (stop_early && k + 1 < k_end) {
-            HIP_TRY(h, hipMemcpyAsync(act_host.data(), active, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+            HIP_TRY(h, hipMemcpyAsync(act_host.data(), mb.active, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
             HIP_TRY(h, hipStreamSynchronize(h->stream));
             bool any = false;
             for (int b = 0; b < B; ++b) any = any || act_host[b] != 0;
@@ -1080,6 +1094,37 @@ int em_loop(dfm_handle* h, int B, int k_first, int k_end, int max_iter, double t
     }
     return 0;
 }
+
+// The results of an EM run from the plan's layout into the caller's.  r = the caller's factor count, a_cols = columns of its A (r; r p
+// of a VAR(p)), kw = width of its mu0 / P0 (r; the companion state's k), rows = periods of the smoother outputs.  What mb already
+// points at the caller's array is not copied: the E-steps or the M-step wrote it in place.  Lam = null: the loadings are not mb's
+// to give back (the driver's series step keeps them in the caller's array).
+int unpad_results(dfm_handle* h, const Plan& p, int B, int N, int rows, int r, int a_cols, int kw, const ModelBufs& mb, double* Lam,
+                  double* A, double* Q, double* mu0, double* P0, double* f_smooth, double* P_smooth) {
+    const int Rk = p.Rp, Rl = p.Rc ? p.Rc : p.Rp;            // state width; loadings width, which the smoother outputs share
+    const int np = r * (r + 1) / 2, npl = Rl * (Rl + 1) / 2;
+    if (Lam && Lam != mb.Lam) if (int rc = copy_block(h, (size_t)B * N, 1, Rl, 1, r, mb.Lam, Lam)) return rc;
+    if (A != mb.A) {
+        if (int rc = copy_block(h, B, Rk, Rk, r, a_cols, mb.A, A)) return rc;
+        if (int rc = copy_block(h, B, Rk, Rk, r, r, mb.Q, Q)) return rc;
+        if (int rc = copy_block(h, B, Rk, Rk, kw, kw, mb.P0, P0)) return rc;
+        if (int rc = copy_block(h, B, 1, Rk, 1, kw, mb.mu0, mu0)) return rc;
+    }
+    if (f_smooth && f_smooth != mb.fsm) if (int rc = copy_block(h, (size_t)B * rows, 1, Rl, 1, r, mb.fsm, f_smooth)) return rc;
+    if (P_smooth && P_smooth != mb.Psm) if (int rc = copy_block(h, (size_t)B * rows, 1, npl, 1, np, mb.Psm, P_smooth)) return rc;
+    return 0;
+}
+
+// ---- the model drivers ---------------------------------------------------------------------------------------------------------
+// Every driver below (em_run, varp_run, the AR pair, the mixed-frequency pair, obs_em_run) is the same procedure around its own
+// series step:
+//   1. check the arguments                     check_dims / check_em_n / check_general_n, ar_check, mf_check
+//   2. plan the call                           make_plan
+//   3. size the workspace                      arrays behind the plan: off = p.total, then take(off, bytes); ensure_ws(h, off)
+//   4. embed the caller's parameters           model_bufs, then pad_params (padded layout) or companion_pad (companion form)
+//   5. run the pass, or the EM loop            enqueue_pass; em_loop around em_iteration or the family's own iteration
+//   6. cut the results into the caller's layout   unpad_results (and odd_unpad after a run on a panel that odd_pad widened)
+// The AR and the mixed-frequency model have a pass and an EM driver: ar_plan / mf_plan do steps 2 and 3 for both.
 
 // Shared driver of dfm_em_step_batch_dev (max_iter = 1, no bookkeeping), dfm_em_batch_dev (iterations 0 .. max_iter-1,
 // stops launching once no replicate of THIS batch is active) and dfm_em_iterate_batch_dev (iteration k_first only, the
@@ -1100,11 +1145,7 @@ int em_run(dfm_handle* h, int B, int T, int N, int r, const double* panel, doubl
         // (the appended series is missing in EVERY period: the padded problem has missing cells whatever the caller said about N)
         if (int rc = em_run(h, B, T, N + 1, r, o.panel, o.Lam, o.R, A, Q, mu0, P0, max_iter, tol, loglik_path, iters, loglik_single,
                             f_smooth, P_smooth, flags | DFM_F_MAY_HAVE_MISSING, k_first, k_count, active_ext)) return rc;
-        const size_t n_lam = (size_t)B * N * r, n_R = (size_t)B * N;
-        hipLaunchKernelGGL(copy_series_rows_kernel, dim3((unsigned)((n_lam + 255) / 256)), dim3(256), 0, h->stream, (size_t)B, N + 1, N, r, 0.0, o.Lam, Lam);
-        hipLaunchKernelGGL(copy_series_rows_kernel, dim3((unsigned)((n_R + 255) / 256)), dim3(256), 0, h->stream, (size_t)B, N + 1, N, 1, 0.0, o.R, R);
-        HIP_TRY(h, hipGetLastError());
-        return 0;
+        return odd_unpad(h, B, N, r, o, Lam, R);
     }
     if (pipe_eligible(h, B, N, r, flags)) {     // sub-batches as EM runs of their own on two streams (pipe_run)
         const Plan ps = make_plan(h->opt, pipe_sub(h), T, N, r, flags, true, false);
@@ -1121,46 +1162,27 @@ int em_run(dfm_handle* h, int B, int T, int N, int r, const double* panel, doubl
     // M-step by em_update_kernel; panels with missing cells: recursion_kernel does both
     const Plan p = make_plan(h->opt, B, T, N, r, flags, true, fast);
     if (int rc = ensure_ws(h, p.total)) return rc;
-    const int Rp = p.Rp, Rl = p.Rc ? p.Rc : p.Rp;            // state width, loadings width
-    const size_t np = (size_t)r * (r + 1) / 2, npp = (size_t)Rl * (Rl + 1) / 2;
-    const bool padded = (r != Rp);
-    double *LamP = Lam, *AP = A, *QP = Q, *mu0P = mu0, *P0P = P0;
-    if (padded) {
+    ModelBufs mb = model_bufs(h, p);
+    if (r != p.Rp) {
         PaddedParams pp;
         if (int rc = pad_params(h, p, B, N, r, Lam, A, Q, mu0, P0, &pp)) return rc;
-        LamP = at<double>(h, p.LamP); AP = at<double>(h, p.AP); QP = at<double>(h, p.QP);
-        mu0P = at<double>(h, p.mu0P); P0P = at<double>(h, p.P0P);
+    } else {   // the caller's layout is the plan's: the EM updates its arrays in place, and the E-steps write its smoother outputs
+        mb.Lam = Lam; mb.A = A; mb.Q = Q; mb.mu0 = mu0; mb.P0 = P0;
+        if (f_smooth) mb.fsm = f_smooth;
+        if (P_smooth) mb.Psm = P_smooth;
     }
-    // smoother outputs of the E-steps: straight into the caller's buffers when layouts coincide
-    double* fsm = (!padded && f_smooth) ? f_smooth : at<double>(h, p.fsm);
-    double* Psm = (!padded && P_smooth) ? P_smooth : at<double>(h, p.Psm);
     // balanced panels with the loadings step on the matrix pipe: nothing in the EM reads the per-period smoothed covariances
     // (the M-step works from their sums, cov_kernel's SP11 / SU) -- unless the caller asked for them, the E-steps do not
     // write them (0.15 GB of stores per iteration at config 2, 0.86 GB at config 4)
-    if (!P_smooth && (p.ms_mfma || p.ms_wide)) Psm = nullptr;
-    double* llbuf = loglik_single ? loglik_single : at<double>(h, p.llbuf);
-    const bool book = loglik_path != nullptr;                // (dfm_em_step_batch_dev: none)
-    int* active = book ? (active_ext ? active_ext : at<int>(h, p.active)) : nullptr;
+    if (!P_smooth && (p.ms_mfma || p.ms_wide)) mb.Psm = nullptr;
+    if (loglik_single) mb.llbuf = loglik_single;
+    // no bookkeeping without a path (dfm_em_step_batch_dev); active_ext: the caller owns the flags and decides when to stop
+    mb.active = loglik_path ? (active_ext ? active_ext : mb.active) : nullptr;
     const int k_end = k_count < 0 ? max_iter : (k_first + k_count < max_iter ? k_first + k_count : max_iter);
-    // (active_ext: the caller owns the flags and decides when to stop)
-    if (int rc = em_loop(h, B, k_first, k_end, max_iter, tol, loglik_path, iters, active, !active_ext, [&](const EmOpts& eo) {
-            return em_iteration(h, p, B, T, N, panel, LamP, R, AP, QP, mu0P, P0P, fsm, Psm, llbuf, eo);
+    if (int rc = em_loop(h, B, k_first, k_end, max_iter, tol, loglik_path, iters, mb, !active_ext, [&](const EmOpts& eo) {
+            return em_iteration(h, p, B, T, N, panel, mb, R, eo);
         })) return rc;
-    if (padded) {
-        if (int rc = copy_block(h, (size_t)B * N, 1, Rl, 1, r, LamP, Lam)) return rc;
-        if (int rc = copy_block(h, B, Rp, Rp, r, r, AP, A)) return rc;
-        if (int rc = copy_block(h, B, Rp, Rp, r, r, QP, Q)) return rc;
-        if (int rc = copy_block(h, B, Rp, Rp, r, r, P0P, P0)) return rc;
-        if (int rc = copy_block(h, B, 1, Rp, 1, r, mu0P, mu0)) return rc;
-        if (f_smooth) if (int rc = copy_block(h, (size_t)B * T, 1, Rl, 1, r, fsm, f_smooth)) return rc;
-        if (P_smooth) if (int rc = copy_block(h, (size_t)B * T, 1, (int)npp, 1, (int)np, Psm, P_smooth)) return rc;
-    } else {
-        if (f_smooth && fsm != f_smooth)
-            HIP_TRY(h, hipMemcpyAsync(f_smooth, fsm, (size_t)B * T * r * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-        if (P_smooth && Psm != P_smooth)
-            HIP_TRY(h, hipMemcpyAsync(P_smooth, Psm, (size_t)B * T * np * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    }
-    return 0;
+    return unpad_results(h, p, B, N, T, r, r, r, mb, Lam, A, Q, mu0, P0, f_smooth, P_smooth);
 }
 
 // ---- VAR(p) factor dynamics in companion form ---------------------------------------------
@@ -1195,6 +1217,16 @@ __global__ void companion_pad_kernel(int B, int N, int r, int k, int ka, int Rc,
     }
 }
 
+// The caller's VAR parameters (Avar [B][r][ka], Q [B][r][r], mu0 [B][k], P0 [B][k][k]) into mb's companion form, and its loadings
+// Lam [B][N][r] into mb.Lam at the plan's loadings width -- Lam = null: the family's own loadings kernel fills mb.Lam.
+int companion_pad(dfm_handle* h, const Plan& p, int B, int N, int r, int k, int ka, const double* Lam, const double* Avar,
+                  const double* Q, const double* mu0, const double* P0, const ModelBufs& mb) {
+    const int Rk = p.Rp, Rc = p.Rc ? p.Rc : p.Rp;
+    const size_t nl = Lam ? (size_t)B * N * Rc : 0, nm = (size_t)B * Rk * Rk;
+    return launch_1d(h, companion_pad_kernel, nl > nm ? nl : nm, B, N, r, k, ka, Rc, Rk, Lam, Avar, Q, mu0, P0, mb.Lam, mb.A, mb.Q,
+                     mb.mu0, mb.P0);
+}
+
 int varp_run(dfm_handle* h, int B, int T, int N, int r, int nlag, const double* panel, double* Lam, double* R,
              double* Avar, double* Q, double* mu0, double* P0, int max_iter, double tol, double* loglik_path, int* iters,
              double* loglik_single, double* f_smooth, double* P_smooth, unsigned flags, bool em) {
@@ -1215,46 +1247,22 @@ int varp_run(dfm_handle* h, int B, int T, int N, int r, int nlag, const double* 
         if (int rc = odd_pad(h, B, T, N, r, panel, Lam, R, &o)) return rc;
         if (int rc = varp_run(h, B, T, N + 1, r, nlag, o.panel, o.Lam, o.R, Avar, Q, mu0, P0, max_iter, tol, loglik_path, iters, loglik_single,
                               f_smooth, P_smooth, flags, em)) return rc;
-        if (em) {
-            const size_t n_lam = (size_t)B * N * r, n_R = (size_t)B * N;
-            hipLaunchKernelGGL(copy_series_rows_kernel, dim3((unsigned)((n_lam + 255) / 256)), dim3(256), 0, h->stream, (size_t)B, N + 1, N, r, 0.0, o.Lam, Lam);
-            hipLaunchKernelGGL(copy_series_rows_kernel, dim3((unsigned)((n_R + 255) / 256)), dim3(256), 0, h->stream, (size_t)B, N + 1, N, 1, 0.0, o.R, R);
-            HIP_TRY(h, hipGetLastError());
-        }
-        return 0;
+        return em ? odd_unpad(h, B, N, r, o, Lam, R) : 0;
     }
     Companion comp;                                           // loadings on the first block only, pad_r(r) wide
     comp.Rc = pad_r(r); comp.rl = r; comp.kdim = k; comp.qsing = (flags & DFM_F_SINGULAR_Q) ? 1 : 0; comp.table = comp_tab_ok;
     const Plan p = make_plan(h->opt, B, T, N, k, flags | DFM_F_SINGULAR_Q, em, false, comp);
     if (int rc = ensure_ws(h, p.total)) return rc;
-    const int Rk = p.Rp, Rc = p.Rc;
-    double *LamP = at<double>(h, p.LamP), *AP = at<double>(h, p.AP), *QP = at<double>(h, p.QP),
-           *mu0P = at<double>(h, p.mu0P), *P0P = at<double>(h, p.P0P);
-    {
-        const size_t n = (size_t)B * N * Rc > (size_t)B * Rk * Rk ? (size_t)B * N * Rc : (size_t)B * Rk * Rk;
-        hipLaunchKernelGGL(companion_pad_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, B, N, r, k, k,
-                           Rc, Rk, Lam, Avar, Q, mu0, P0, LamP, AP, QP, mu0P, P0P);
-        HIP_TRY(h, hipGetLastError());
-    }
-    PaddedParams pp{LamP, AP, QP, mu0P, P0P};
+    ModelBufs mb = model_bufs(h, p);
+    if (int rc = companion_pad(h, p, B, N, r, k, k, Lam, Avar, Q, mu0, P0, mb)) return rc;
     if (!em)   // plain pass: smoothed moments of f_t = z_t[:r] straight into the caller's layout
-        return enqueue_pass(h, p, B, T, N, r, panel, pp, R, f_smooth, P_smooth, loglik_single, nullptr);
-    const size_t np = (size_t)r * (r + 1) / 2, npc = (size_t)Rc * (Rc + 1) / 2;
-    double* fsm = at<double>(h, p.fsm);
-    double* Psm = at<double>(h, p.Psm);
-    double* llbuf = loglik_single ? loglik_single : at<double>(h, p.llbuf);
-    int* active = loglik_path ? at<int>(h, p.active) : nullptr;
-    if (int rc = em_loop(h, B, 0, max_iter, max_iter, tol, loglik_path, iters, active, true, [&](const EmOpts& eo) {
-            return em_iteration(h, p, B, T, N, panel, LamP, R, AP, QP, mu0P, P0P, fsm, Psm, llbuf, eo);
+        return enqueue_pass(h, p, B, T, N, r, panel, mb.pp(), R, f_smooth, P_smooth, loglik_single, nullptr);
+    if (loglik_single) mb.llbuf = loglik_single;
+    if (!loglik_path) mb.active = nullptr;
+    if (int rc = em_loop(h, B, 0, max_iter, max_iter, tol, loglik_path, iters, mb, true, [&](const EmOpts& eo) {
+            return em_iteration(h, p, B, T, N, panel, mb, R, eo);
         })) return rc;
-    if (int rc = copy_block(h, (size_t)B * N, 1, Rc, 1, r, LamP, Lam)) return rc;
-    if (int rc = copy_block(h, B, Rk, Rk, r, k, AP, Avar)) return rc;
-    if (int rc = copy_block(h, B, Rk, Rk, r, r, QP, Q)) return rc;
-    if (int rc = copy_block(h, B, Rk, Rk, k, k, P0P, P0)) return rc;
-    if (int rc = copy_block(h, B, 1, Rk, 1, k, mu0P, mu0)) return rc;
-    if (f_smooth) if (int rc = copy_block(h, (size_t)B * T, 1, Rc, 1, r, fsm, f_smooth)) return rc;
-    if (P_smooth) if (int rc = copy_block(h, (size_t)B * T, 1, (int)npc, 1, (int)np, Psm, P_smooth)) return rc;
-    return 0;
+    return unpad_results(h, p, B, N, T, r, k, k, mb, Lam, Avar, Q, mu0, P0, f_smooth, P_smooth);
 }
 
 // ---- AR idiosyncratic terms by quasi-differencing ----------------------------------------------
@@ -1282,46 +1290,58 @@ __global__ void ar_loadings_kernel(int B, int N, int r, int q, int Rk, const dou
     LamK[tid] = v;
 }
 
-int ar_pass_run(dfm_handle* h, int B, int T, int N, int r, int nlag, int q, const double* panel, const double* Lam,
-                const double* sig2, const double* rho, const double* Avar, const double* Q, const double* mu0,
-                const double* P0, double* f_smooth, double* P_smooth, double* loglik, unsigned flags) {
+int ar_check(dfm_handle* h, int B, int T, int N, int r, int nlag, int q, bool em) {
     if (!h) return DFM_E_NULL;
     if (nlag < 1 || q < 0) return fail(h, DFM_E_DIMS, "need p >= 1 factor lags and q >= 0 idiosyncratic lags%s");
     if (int rc = check_dims(h, B, T, N, r)) return rc;
-    if (T <= q) return fail(h, DFM_E_DIMS, "T must exceed the number of idiosyncratic lags%s");
+    if (!em && T <= q) return fail(h, DFM_E_DIMS, "T must exceed the number of idiosyncratic lags%s");
+    if (em && T <= q + 1) return fail(h, DFM_E_DIMS, "T must exceed the number of idiosyncratic lags by at least 2%s");
     const int m = nlag > q + 1 ? nlag : q + 1, k = r * m;
     if (k > DFM_MAX_R) return fail(h, DFM_E_R_UNSUPPORTED, "r * max(p, q + 1) > DFM_MAX_R (32)%s");
-    if (int rc = check_general_n(h, N, k)) return rc;
+    if (em && !mstep_ar_supported(r, q)) return fail(h, DFM_E_R_UNSUPPORTED, "joint AR estimation needs r <= 8 and q <= 4%s");
+    return check_general_n(h, N, k);
+}
+
+// The plan of a pass on the T - q quasi-differenced periods (the observation loads on q + 1 blocks of the k-wide state) and, behind
+// it, the quasi-differenced panel xq and (EM) the moments of the series CM-steps (mstep_ar.hip)
+struct ArPlan { Plan p; ModelBufs mb; int k; double *xq, *mws; };
+int ar_plan(dfm_handle* h, int B, int T, int N, int r, int nlag, int q, unsigned flags, bool em, ArPlan* s) {
+    const int Tq = T - q;
+    s->k = r * (nlag > q + 1 ? nlag : q + 1);
+    s->p = make_plan(h->opt, B, Tq, N, s->k, flags | DFM_F_SINGULAR_Q, em, false, lag_blocks(s->k, r, nlag, flags));
+    size_t off = s->p.total;
+    const size_t xoff = take(off, (size_t)B * Tq * N * sizeof(double));
+    const size_t moff = em ? take(off, mstep_ar_workspace(B, T, N, r, q, s->p.Rp)) : (size_t)-1;
+    if (int rc = ensure_ws(h, off)) return rc;
+    s->mb = model_bufs(h, s->p);
+    s->xq = at<double>(h, xoff); s->mws = at<double>(h, moff);
+    return 0;
+}
+// The series side of one pass at the current rho: the quasi-differenced panel (q > 0; *xin = what the pass reads) and the loadings
+// on the lag blocks
+int ar_prepare(dfm_handle* h, const ArPlan& s, int B, int T, int N, int r, int q, const double* panel, const double* Lam,
+               const double* rho, const double** xin) {
+    *xin = panel;
+    if (q > 0) {
+        if (int rc = launch_1d(h, quasi_diff_kernel, (size_t)B * (T - q) * N, B, T, N, q, panel, rho, s.xq)) return rc;
+        *xin = s.xq;
+    }
+    return launch_1d(h, ar_loadings_kernel, (size_t)B * N * s.p.Rp, B, N, r, q, s.p.Rp, Lam, rho, s.mb.Lam);
+}
+
+int ar_pass_run(dfm_handle* h, int B, int T, int N, int r, int nlag, int q, const double* panel, const double* Lam,
+                const double* sig2, const double* rho, const double* Avar, const double* Q, const double* mu0,
+                const double* P0, double* f_smooth, double* P_smooth, double* loglik, unsigned flags) {
+    if (int rc = ar_check(h, B, T, N, r, nlag, q, false)) return rc;
     if (!panel || !Lam || !sig2 || (q > 0 && !rho) || !Avar || !Q || !mu0 || !P0 || !f_smooth || !loglik)
         return fail(h, DFM_E_NULL, "required pointer is NULL%s");
     HIP_TRY(h, hipSetDevice(h->device));
-    const int Tq = T - q;
-    const Plan p = make_plan(h->opt, B, Tq, N, k, flags | DFM_F_SINGULAR_Q, false, false, lag_blocks(k, r, nlag, flags));
-    const size_t xoff = (p.total + 255) & ~(size_t)255;
-    if (int rc = ensure_ws(h, xoff + (size_t)B * Tq * N * sizeof(double))) return rc;
-    const int Rk = p.Rp;
-    double *LamP = at<double>(h, p.LamP), *AP = at<double>(h, p.AP), *QP = at<double>(h, p.QP),
-           *mu0P = at<double>(h, p.mu0P), *P0P = at<double>(h, p.P0P), *xq = at<double>(h, xoff);
-    const double* xin = panel;
-    if (q > 0) {
-        const size_t n = (size_t)B * Tq * N;
-        hipLaunchKernelGGL(quasi_diff_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, B, T, N, q, panel,
-                           rho, xq);
-        HIP_TRY(h, hipGetLastError());
-        xin = xq;
-    }
-    {
-        const size_t n = (size_t)B * N * Rk;
-        hipLaunchKernelGGL(ar_loadings_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, B, N, r, q, Rk, Lam,
-                           rho, LamP);
-        HIP_TRY(h, hipGetLastError());
-        const size_t nm = (size_t)B * Rk * Rk;
-        hipLaunchKernelGGL(companion_pad_kernel, dim3((unsigned)((nm + 255) / 256)), dim3(256), 0, h->stream, B, N, r, k,
-                           r * nlag, Rk, Rk, (const double*)nullptr, Avar, Q, mu0, P0, LamP, AP, QP, mu0P, P0P);
-        HIP_TRY(h, hipGetLastError());
-    }
-    PaddedParams pp{LamP, AP, QP, mu0P, P0P};
-    return enqueue_pass(h, p, B, Tq, N, r, xin, pp, sig2, f_smooth, P_smooth, loglik, nullptr);
+    ArPlan s;
+    if (int rc = ar_plan(h, B, T, N, r, nlag, q, flags, false, &s)) return rc;
+    const double* xin;
+    if (int rc = ar_prepare(h, s, B, T, N, r, q, panel, Lam, rho, &xin)) return rc;
+    if (int rc = companion_pad(h, s.p, B, N, r, s.k, r * nlag, nullptr, Avar, Q, mu0, P0, s.mb)) return rc;
+    return enqueue_pass(h, s.p, B, T - q, N, r, xin, s.mb.pp(), sig2, f_smooth, P_smooth, loglik, nullptr);
 }
 
 // Joint estimation with AR(q) idiosyncratic terms by ECM (oracle/ar_oracle.py em_ar).  Per iteration: quasi-difference the
@@ -1330,68 +1350,27 @@ int ar_pass_run(dfm_handle* h, int B, int T, int N, int r, int nlag, int q, cons
 int ar_em_run(dfm_handle* h, int B, int T, int N, int r, int nlag, int q, const double* panel, double* Lam, double* sig2,
               double* rho, double* Avar, double* Q, double* mu0, double* P0, int max_iter, double tol, double* loglik_path,
               int* iters, double* f_smooth, double* P_smooth, unsigned flags) {
-    if (!h) return DFM_E_NULL;
-    if (nlag < 1 || q < 0) return fail(h, DFM_E_DIMS, "need p >= 1 factor lags and q >= 0 idiosyncratic lags%s");
-    if (int rc = check_dims(h, B, T, N, r)) return rc;
-    if (T <= q + 1) return fail(h, DFM_E_DIMS, "T must exceed the number of idiosyncratic lags by at least 2%s");
-    const int m = nlag > q + 1 ? nlag : q + 1, k = r * m;
-    if (k > DFM_MAX_R) return fail(h, DFM_E_R_UNSUPPORTED, "r * max(p, q + 1) > DFM_MAX_R (32)%s");
-    if (!mstep_ar_supported(r, q)) return fail(h, DFM_E_R_UNSUPPORTED, "joint AR estimation needs r <= 8 and q <= 4%s");
-    if (int rc = check_general_n(h, N, k)) return rc;
+    if (int rc = ar_check(h, B, T, N, r, nlag, q, true)) return rc;
     if (!panel || !Lam || !sig2 || (q > 0 && !rho) || !Avar || !Q || !mu0 || !P0 || !loglik_path || !iters)
         return fail(h, DFM_E_NULL, "required pointer is NULL%s");
     if (max_iter < 1) return fail(h, DFM_E_DIMS, "max_iter must be >= 1%s");
     HIP_TRY(h, hipSetDevice(h->device));
-    const int Tq = T - q;
-    const Plan p = make_plan(h->opt, B, Tq, N, k, flags | DFM_F_SINGULAR_Q, true, false, lag_blocks(k, r, nlag, flags));   // (the observation loads on q + 1 blocks)
-    const size_t xoff = (p.total + 255) & ~(size_t)255;
-    const int Rk = p.Rp;
-    const size_t moff = (xoff + (size_t)B * Tq * N * sizeof(double) + 255) & ~(size_t)255;   // the series CM-steps' moments (mstep_ar.hip)
-    if (int rc = ensure_ws(h, moff + mstep_ar_workspace(B, T, N, r, q, Rk))) return rc;
-    double *LamP = at<double>(h, p.LamP), *AP = at<double>(h, p.AP), *QP = at<double>(h, p.QP),
-           *mu0P = at<double>(h, p.mu0P), *P0P = at<double>(h, p.P0P), *xq = at<double>(h, xoff), *mws = at<double>(h, moff);
-    {
-        const size_t nm = (size_t)B * Rk * Rk;
-        hipLaunchKernelGGL(companion_pad_kernel, dim3((unsigned)((nm + 255) / 256)), dim3(256), 0, h->stream, B, N, r, k,
-                           r * nlag, Rk, Rk, (const double*)nullptr, Avar, Q, mu0, P0, LamP, AP, QP, mu0P, P0P);
-        HIP_TRY(h, hipGetLastError());
-    }
-    double* fsm = at<double>(h, p.fsm);
-    double* Psm = at<double>(h, p.Psm);
-    double* llbuf = at<double>(h, p.llbuf);
-    int* active = at<int>(h, p.active);
-    const size_t np = (size_t)r * (r + 1) / 2, npk = (size_t)Rk * (Rk + 1) / 2;
-    PaddedParams pp{LamP, AP, QP, mu0P, P0P};
-    if (int rc = em_loop(h, B, 0, max_iter, max_iter, tol, loglik_path, iters, active, true, [&](EmOpts eo) -> int {
-        const double* xin = panel;
-        if (q > 0) {
-            const size_t n = (size_t)B * Tq * N;
-            hipLaunchKernelGGL(quasi_diff_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, B, T, N, q, panel,
-                               rho, xq);
-            HIP_TRY(h, hipGetLastError());
-            xin = xq;
-        }
-        {
-            const size_t n = (size_t)B * N * Rk;
-            hipLaunchKernelGGL(ar_loadings_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, B, N, r, q, Rk, Lam,
-                               rho, LamP);
-            HIP_TRY(h, hipGetLastError());
-        }
-        eo.A_out = AP; eo.Q_out = QP; eo.mu0_out = mu0P; eo.P0_out = P0P;
-        if (int rc = enqueue_pass(h, p, B, Tq, N, Rk, xin, pp, sig2, fsm, Psm, llbuf, &eo)) return rc;
-        ArMstepArgs ma;
-        ma.B = B; ma.T = T; ma.N = N; ma.r = r; ma.q = q; ma.Rk = Rk;
-        ma.panel = panel; ma.zsm = fsm; ma.Psm = Psm; ma.active = active; ma.Lam = Lam; ma.rho = rho; ma.sig2 = sig2;
-        { ProfScope ps(h, K_MSTEP_STATS); HIP_TRY(h, launch_mstep_ar(ma, mws, h->stream)); }
+    ArPlan s;
+    if (int rc = ar_plan(h, B, T, N, r, nlag, q, flags, true, &s)) return rc;
+    const Plan& p = s.p;
+    const ModelBufs& mb = s.mb;
+    if (int rc = companion_pad(h, p, B, N, r, s.k, r * nlag, nullptr, Avar, Q, mu0, P0, mb)) return rc;
+    ArMstepArgs ma;
+    ma.B = B; ma.T = T; ma.N = N; ma.r = r; ma.q = q; ma.Rk = p.Rp;
+    ma.panel = panel; ma.zsm = mb.fsm; ma.Psm = mb.Psm; ma.active = mb.active; ma.Lam = Lam; ma.rho = rho; ma.sig2 = sig2;
+    if (int rc = em_loop(h, B, 0, max_iter, max_iter, tol, loglik_path, iters, mb, true, [&](const EmOpts& eo) -> int {
+        const double* xin;
+        if (int rc = ar_prepare(h, s, B, T, N, r, q, panel, Lam, rho, &xin)) return rc;
+        if (int rc = enqueue_pass(h, p, B, T - q, N, p.Rp, xin, mb.pp(), sig2, mb.fsm, mb.Psm, mb.llbuf, &eo)) return rc;
+        { ProfScope ps(h, K_MSTEP_STATS); HIP_TRY(h, launch_mstep_ar(ma, s.mws, h->stream)); }
         return 0;
     })) return rc;
-    if (int rc = copy_block(h, B, Rk, Rk, r, r * nlag, AP, Avar)) return rc;
-    if (int rc = copy_block(h, B, Rk, Rk, r, r, QP, Q)) return rc;
-    if (int rc = copy_block(h, B, Rk, Rk, k, k, P0P, P0)) return rc;
-    if (int rc = copy_block(h, B, 1, Rk, 1, k, mu0P, mu0)) return rc;
-    if (f_smooth) if (int rc = copy_block(h, (size_t)B * Tq, 1, Rk, 1, r, fsm, f_smooth)) return rc;
-    if (P_smooth) if (int rc = copy_block(h, (size_t)B * Tq, 1, (int)npk, 1, (int)np, Psm, P_smooth)) return rc;
-    return 0;
+    return unpad_results(h, p, B, N, T - q, r, r * nlag, s.k, mb, nullptr, Avar, Q, mu0, P0, f_smooth, P_smooth);
 }
 
 // ---- mixed frequency (mstep_mf.hip; tests/mf_expect.py) ---------------------------------------------------------------------
@@ -1446,6 +1425,40 @@ int mf_check(dfm_handle* h, int B, int T, int N, int r, int nlag, int L) {
     return check_general_n(h, N, k);
 }
 
+// The weights on the host (finite; EM: dealt into classes), the plan of a pass on the k-wide state (the observation loads on L
+// blocks) and, for the EM, behind it: the series step's table and moments, then the class weights and the tile lists
+struct MfPlan { Plan p; ModelBufs mb; int k; MfClasses mc; double *mws, *Wc; int *tile_class, *tile_series; };
+int mf_plan(dfm_handle* h, int B, int T, int N, int r, int nlag, int L, const double* W, unsigned flags, bool em, MfPlan* s) {
+    std::vector<double> Wh((size_t)N * L);
+    HIP_TRY(h, hipMemcpyAsync(Wh.data(), W, Wh.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (em) {
+        if (int rc = mf_classes(h, N, L, Wh, &s->mc)) return rc;
+    } else {
+        for (double w : Wh)
+            if (!isfinite(w)) return fail(h, DFM_E_DIMS, "mixed frequency: a weight is not finite%s");
+    }
+    const MfClasses& mc = s->mc;
+    s->k = r * (nlag > L ? nlag : L);
+    s->p = make_plan(h->opt, B, T, N, s->k, flags | DFM_F_SINGULAR_Q, em, false, lag_blocks(s->k, r, nlag, flags));
+    size_t off = s->p.total;
+    const size_t none = (size_t)-1;
+    const size_t moff = em ? take(off, mstep_mf_workspace(B, T, N, r, mc.C)) : none;
+    const size_t woff = em ? take(off, mc.Wc.size() * sizeof(double)) : none;
+    const size_t coff = em ? take(off, mc.tile_class.size() * sizeof(int)) : none;
+    const size_t soff = em ? take(off, mc.tile_series.size() * sizeof(int)) : none;
+    if (int rc = ensure_ws(h, off)) return rc;
+    s->mb = model_bufs(h, s->p);
+    s->mws = at<double>(h, moff); s->Wc = at<double>(h, woff); s->tile_class = at<int>(h, coff); s->tile_series = at<int>(h, soff);
+    if (em) {
+        HIP_TRY(h, hipMemcpyAsync(s->Wc, mc.Wc.data(), mc.Wc.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(s->tile_class, mc.tile_class.data(), mc.tile_class.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(s->tile_series, mc.tile_series.data(), mc.tile_series.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));         // (the host vectors need not outlive this call)
+    }
+    return 0;
+}
+
 int mf_pass_run(dfm_handle* h, int B, int T, int N, int r, int nlag, int L, const double* panel, const double* Lam, const double* R,
                 const double* W, const double* Avar, const double* Q, const double* mu0, const double* P0, double* f_smooth,
                 double* P_smooth, double* loglik, unsigned flags) {
@@ -1453,26 +1466,11 @@ int mf_pass_run(dfm_handle* h, int B, int T, int N, int r, int nlag, int L, cons
     if (!panel || !Lam || !R || !W || !Avar || !Q || !mu0 || !P0 || !f_smooth || !loglik)
         return fail(h, DFM_E_NULL, "required pointer is NULL%s");
     HIP_TRY(h, hipSetDevice(h->device));
-    std::vector<double> Wh((size_t)N * L);
-    HIP_TRY(h, hipMemcpyAsync(Wh.data(), W, Wh.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    for (double w : Wh)
-        if (!isfinite(w)) return fail(h, DFM_E_DIMS, "mixed frequency: a weight is not finite%s");
-    const int m = nlag > L ? nlag : L, k = r * m;
-    const Plan p = make_plan(h->opt, B, T, N, k, flags | DFM_F_SINGULAR_Q, false, false, lag_blocks(k, r, nlag, flags));
-    if (int rc = ensure_ws(h, p.total)) return rc;
-    const int Rk = p.Rp;
-    double *LamP = at<double>(h, p.LamP), *AP = at<double>(h, p.AP), *QP = at<double>(h, p.QP),
-           *mu0P = at<double>(h, p.mu0P), *P0P = at<double>(h, p.P0P);
-    HIP_TRY(h, launch_mf_loadings(B, N, r, L, Rk, Lam, W, LamP, h->stream));
-    {
-        const size_t nm = (size_t)B * Rk * Rk;
-        hipLaunchKernelGGL(companion_pad_kernel, dim3((unsigned)((nm + 255) / 256)), dim3(256), 0, h->stream, B, N, r, k,
-                           r * nlag, Rk, Rk, (const double*)nullptr, Avar, Q, mu0, P0, LamP, AP, QP, mu0P, P0P);
-        HIP_TRY(h, hipGetLastError());
-    }
-    PaddedParams pp{LamP, AP, QP, mu0P, P0P};
-    return enqueue_pass(h, p, B, T, N, r, panel, pp, R, f_smooth, P_smooth, loglik, nullptr);
+    MfPlan s;
+    if (int rc = mf_plan(h, B, T, N, r, nlag, L, W, flags, false, &s)) return rc;
+    HIP_TRY(h, launch_mf_loadings(B, N, r, L, s.p.Rp, Lam, W, s.mb.Lam, h->stream));
+    if (int rc = companion_pad(h, s.p, B, N, r, s.k, r * nlag, nullptr, Avar, Q, mu0, P0, s.mb)) return rc;
+    return enqueue_pass(h, s.p, B, T, N, r, panel, s.mb.pp(), R, f_smooth, P_smooth, loglik, nullptr);
 }
 
 int mf_run(dfm_handle* h, int B, int T, int N, int r, int nlag, int L, const double* panel, double* Lam, double* R, const double* W,
@@ -1484,61 +1482,25 @@ int mf_run(dfm_handle* h, int B, int T, int N, int r, int nlag, int L, const dou
         return fail(h, DFM_E_NULL, "required pointer is NULL%s");
     if (max_iter < 1) return fail(h, DFM_E_DIMS, "max_iter must be >= 1%s");
     HIP_TRY(h, hipSetDevice(h->device));
-    MfClasses mc;
-    {
-        std::vector<double> Wh((size_t)N * L);
-        HIP_TRY(h, hipMemcpyAsync(Wh.data(), W, Wh.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        if (int rc = mf_classes(h, N, L, Wh, &mc)) return rc;
-    }
-    const int m = nlag > L ? nlag : L, k = r * m;
-    const Plan p = make_plan(h->opt, B, T, N, k, flags | DFM_F_SINGULAR_Q, true, false, lag_blocks(k, r, nlag, flags));   // (the observation loads on L blocks)
-    // behind the pass's plan: the series step's table and moments, then the class weights and the tile lists
-    size_t off = (p.total + 255) & ~(size_t)255;
-    const size_t moff = take(off, mstep_mf_workspace(B, T, N, r, mc.C));
-    const size_t woff = take(off, mc.Wc.size() * sizeof(double));
-    const size_t coff = take(off, mc.tile_class.size() * sizeof(int));
-    const size_t soff = take(off, mc.tile_series.size() * sizeof(int));
-    if (int rc = ensure_ws(h, off)) return rc;
-    HIP_TRY(h, hipMemcpyAsync(at<double>(h, woff), mc.Wc.data(), mc.Wc.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(at<int>(h, coff), mc.tile_class.data(), mc.tile_class.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(at<int>(h, soff), mc.tile_series.data(), mc.tile_series.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));             // (the host vectors go out of scope with this call)
+    MfPlan s;
+    if (int rc = mf_plan(h, B, T, N, r, nlag, L, W, flags, true, &s)) return rc;
+    const Plan& p = s.p;
+    const ModelBufs& mb = s.mb;
     const int Rk = p.Rp;
-    double *LamP = at<double>(h, p.LamP), *AP = at<double>(h, p.AP), *QP = at<double>(h, p.QP),
-           *mu0P = at<double>(h, p.mu0P), *P0P = at<double>(h, p.P0P), *mws = at<double>(h, moff);
-    {
-        const size_t nm = (size_t)B * Rk * Rk;
-        hipLaunchKernelGGL(companion_pad_kernel, dim3((unsigned)((nm + 255) / 256)), dim3(256), 0, h->stream, B, N, r, k,
-                           r * nlag, Rk, Rk, (const double*)nullptr, Avar, Q, mu0, P0, LamP, AP, QP, mu0P, P0P);
-        HIP_TRY(h, hipGetLastError());
-    }
-    double* fsm = at<double>(h, p.fsm);
-    double* Psm = at<double>(h, p.Psm);
-    double* llbuf = at<double>(h, p.llbuf);
-    int* active = at<int>(h, p.active);
-    const size_t np = (size_t)r * (r + 1) / 2, npk = (size_t)Rk * (Rk + 1) / 2;
-    PaddedParams pp{LamP, AP, QP, mu0P, P0P};
+    if (int rc = companion_pad(h, p, B, N, r, s.k, r * nlag, nullptr, Avar, Q, mu0, P0, mb)) return rc;
     MfMstepArgs ma;
-    ma.B = B; ma.T = T; ma.N = N; ma.r = r; ma.L = L; ma.Rk = Rk; ma.C = mc.C; ma.VW = mstep_mf_row_width(r); ma.ntiles = mc.ntiles;
-    ma.panel = panel; ma.zsm = fsm; ma.Psm = Psm; ma.active = active; ma.Wc = at<double>(h, woff);
-    ma.tile_class = at<int>(h, coff); ma.tile_series = at<int>(h, soff); ma.Lam = Lam; ma.R = R;
-    if (int rc = em_loop(h, B, 0, max_iter, max_iter, tol, loglik_path, iters, active, true, [&](EmOpts eo) -> int {
-        { ProfScope ps(h, K_PAD); HIP_TRY(h, launch_mf_loadings(B, N, r, L, Rk, Lam, W, LamP, h->stream)); }
-        eo.A_out = AP; eo.Q_out = QP; eo.mu0_out = mu0P; eo.P0_out = P0P;
-        if (int rc = enqueue_pass(h, p, B, T, N, Rk, panel, pp, R, fsm, Psm, llbuf, &eo)) return rc;
-        { ProfScope ps(h, K_MF_TABLE); HIP_TRY(h, launch_mf_table(ma, mws, h->stream)); }
-        { ProfScope ps(h, K_MF_MOMENTS); HIP_TRY(h, launch_mf_moments(ma, mws, h->stream)); }
-        { ProfScope ps(h, K_MF_SOLVE); HIP_TRY(h, launch_mf_solve(ma, mws, h->stream)); }
+    ma.B = B; ma.T = T; ma.N = N; ma.r = r; ma.L = L; ma.Rk = Rk; ma.C = s.mc.C; ma.VW = mstep_mf_row_width(r); ma.ntiles = s.mc.ntiles;
+    ma.panel = panel; ma.zsm = mb.fsm; ma.Psm = mb.Psm; ma.active = mb.active; ma.Wc = s.Wc;
+    ma.tile_class = s.tile_class; ma.tile_series = s.tile_series; ma.Lam = Lam; ma.R = R;
+    if (int rc = em_loop(h, B, 0, max_iter, max_iter, tol, loglik_path, iters, mb, true, [&](const EmOpts& eo) -> int {
+        { ProfScope ps(h, K_PAD); HIP_TRY(h, launch_mf_loadings(B, N, r, L, Rk, Lam, W, mb.Lam, h->stream)); }
+        if (int rc = enqueue_pass(h, p, B, T, N, Rk, panel, mb.pp(), R, mb.fsm, mb.Psm, mb.llbuf, &eo)) return rc;
+        { ProfScope ps(h, K_MF_TABLE); HIP_TRY(h, launch_mf_table(ma, s.mws, h->stream)); }
+        { ProfScope ps(h, K_MF_MOMENTS); HIP_TRY(h, launch_mf_moments(ma, s.mws, h->stream)); }
+        { ProfScope ps(h, K_MF_SOLVE); HIP_TRY(h, launch_mf_solve(ma, s.mws, h->stream)); }
         return 0;
     })) return rc;
-    if (int rc = copy_block(h, B, Rk, Rk, r, r * nlag, AP, Avar)) return rc;
-    if (int rc = copy_block(h, B, Rk, Rk, r, r, QP, Q)) return rc;
-    if (int rc = copy_block(h, B, Rk, Rk, k, k, P0P, P0)) return rc;
-    if (int rc = copy_block(h, B, 1, Rk, 1, k, mu0P, mu0)) return rc;
-    if (f_smooth) if (int rc = copy_block(h, (size_t)B * T, 1, Rk, 1, r, fsm, f_smooth)) return rc;
-    if (P_smooth) if (int rc = copy_block(h, (size_t)B * T, 1, (int)npk, 1, (int)np, Psm, P_smooth)) return rc;
-    return 0;
+    return unpad_results(h, p, B, N, T, r, r * nlag, s.k, mb, nullptr, Avar, Q, mu0, P0, f_smooth, P_smooth);
 }
 
 // ---- observed factors (mstep_obs.hip, oracle/obs_oracle.py em_obs) ------------------------------------
@@ -1561,42 +1523,34 @@ int obs_em_run(dfm_handle* h, int B, int T, int N, int ru, int ro, const double*
     if (max_iter < 1) return fail(h, DFM_E_DIMS, "max_iter must be >= 1%s");
     HIP_TRY(h, hipSetDevice(h->device));
     const Plan p = make_plan(h->opt, B, T, N, ru, flags, true, fast);
-    const size_t yoff = (p.total + 255) & ~(size_t)255;
-    // wide joint regression: z [B][T][Re] | Var z [B][T][NPe] | LamAug [B][N][Re] | S11, S11inv [B][Re][Re] | Dmiss [B][N][NPe]
+    // behind the plan: the residual panel y, then for the wide joint regression
+    // z [B][T][Re] | Var z [B][T][NPe] | LamAug [B][N][Re] | S11, S11inv [B][Re][Re] | Dmiss [B][N][NPe]
     const int Re = wide_obs ? mstep_obs_wide_width(ro, ru) : 0;
     const size_t NPe = (size_t)Re * (Re + 1) / 2;
-    size_t woff = (yoff + (size_t)B * T * N * sizeof(double) + 255) & ~(size_t)255, wend = woff;
-    auto wtake = [&](size_t bytes) { const size_t o = wend; wend = (wend + bytes + 255) & ~(size_t)255; return o; };
-    const size_t o_z = wide_obs ? wtake((size_t)B * T * Re * sizeof(double)) : 0;
-    const size_t o_v = wide_obs ? wtake((size_t)B * T * NPe * sizeof(double)) : 0;
-    const size_t o_l = wide_obs ? wtake((size_t)B * N * Re * sizeof(double)) : 0;
-    const size_t o_s = wide_obs ? wtake((size_t)B * Re * Re * sizeof(double)) : 0;
-    const size_t o_i = wide_obs ? wtake((size_t)B * Re * Re * sizeof(double)) : 0;
-    const size_t o_d = wide_obs ? wtake((size_t)B * N * NPe * sizeof(double)) : 0;
-    if (int rc = ensure_ws(h, wend)) return rc;
+    size_t off = p.total;
+    const size_t yoff = take(off, (size_t)B * T * N * sizeof(double));
+    const size_t o_z = wide_obs ? take(off, (size_t)B * T * Re * sizeof(double)) : 0;
+    const size_t o_v = wide_obs ? take(off, (size_t)B * T * NPe * sizeof(double)) : 0;
+    const size_t o_l = wide_obs ? take(off, (size_t)B * N * Re * sizeof(double)) : 0;
+    const size_t o_s = wide_obs ? take(off, (size_t)B * Re * Re * sizeof(double)) : 0;
+    const size_t o_i = wide_obs ? take(off, (size_t)B * Re * Re * sizeof(double)) : 0;
+    const size_t o_d = wide_obs ? take(off, (size_t)B * N * NPe * sizeof(double)) : 0;
+    if (int rc = ensure_ws(h, off)) return rc;
     const int Rp = p.Rp, Rl = p.Rc ? p.Rc : p.Rp;            // state width, loadings width
-    const bool padded = (ru != Rp);
-    double *LamP = at<double>(h, p.LamP), *y = at<double>(h, yoff);
-    double *AP = A, *QP = Q, *mu0P = mu0, *P0P = P0;
-    if (padded) {
-        AP = at<double>(h, p.AP); QP = at<double>(h, p.QP); mu0P = at<double>(h, p.mu0P); P0P = at<double>(h, p.P0P);
-        const size_t n = (size_t)B * Rp * Rp;                 // (N = 0: the loadings are embedded by launch_obs_residual)
-        hipLaunchKernelGGL(pad_params_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, B, 0, ru, Rp, Rl,
-                           (const double*)nullptr, A, Q, mu0, P0, (double*)nullptr, AP, QP, mu0P, P0P);
-        HIP_TRY(h, hipGetLastError());
+    double* y = at<double>(h, yoff);
+    ModelBufs mb = model_bufs(h, p);                          // (mb.Lam: the padded Lam_u, embedded by launch_obs_residual)
+    if (ru != Rp) {                                           // (N = 0: no loadings)
+        if (int rc = launch_1d(h, pad_params_kernel, (size_t)B * Rp * Rp, B, 0, ru, Rp, Rl, nullptr, A, Q, mu0, P0, nullptr, mb.A, mb.Q,
+                               mb.mu0, mb.P0)) return rc;
+    } else {
+        mb.A = A; mb.Q = Q; mb.mu0 = mu0; mb.P0 = P0;
     }
-    double* fsm = at<double>(h, p.fsm);
-    double* Psm = at<double>(h, p.Psm);
-    double* llbuf = at<double>(h, p.llbuf);
-    int* active = at<int>(h, p.active);
     ObsArgs oa;
     oa.B = B; oa.T = T; oa.N = N; oa.ro = ro; oa.ru = ru; oa.Rl = Rl;
-    oa.panel = panel; oa.G = G; oa.fsm = fsm; oa.Psm = Psm; oa.active = active; oa.Lam = Lam; oa.R = R;
-    PaddedParams pp{LamP, AP, QP, mu0P, P0P};
-    if (int rc = em_loop(h, B, 0, max_iter, max_iter, tol, loglik_path, iters, active, true, [&](EmOpts eo) -> int {
-        { ProfScope ps(h, K_PAD); HIP_TRY(h, launch_obs_residual(oa, y, LamP, h->stream)); }
-        eo.A_out = AP; eo.Q_out = QP; eo.mu0_out = mu0P; eo.P0_out = P0P;
-        if (int rc = enqueue_pass(h, p, B, T, N, Rl, y, pp, R, fsm, Psm, llbuf, &eo)) return rc;
+    oa.panel = panel; oa.G = G; oa.fsm = mb.fsm; oa.Psm = mb.Psm; oa.active = mb.active; oa.Lam = Lam; oa.R = R;
+    if (int rc = em_loop(h, B, 0, max_iter, max_iter, tol, loglik_path, iters, mb, true, [&](const EmOpts& eo) -> int {
+        { ProfScope ps(h, K_PAD); HIP_TRY(h, launch_obs_residual(oa, y, mb.Lam, h->stream)); }
+        if (int rc = enqueue_pass(h, p, B, T, N, Rl, y, mb.pp(), R, mb.fsm, mb.Psm, mb.llbuf, &eo)) return rc;
         if (!wide_obs) {
             ProfScope ps(h, K_MSTEP_STATS);
             HIP_TRY(h, launch_mstep_obs(oa, h->stream));
@@ -1607,7 +1561,7 @@ int obs_em_run(dfm_handle* h, int B, int T, int N, int ru, int ro, const double*
             ma.B = B; ma.T = T; ma.N = N; ma.r = Re;
             ma.panel = panel; ma.fsm = z; ma.Psm = Vz; ma.S11 = at<double>(h, o_s); ma.S11inv = at<double>(h, o_i);
             ma.Dmiss = at<double>(h, o_d);
-            ma.active = active; ma.Lam_out = LamAug; ma.R_out = R; ma.lam_stride = Re;
+            ma.active = mb.active; ma.Lam_out = LamAug; ma.R_out = R; ma.lam_stride = Re;
             ma.min_cells = ro + ru + 1;                       // (as mstep_obs_kernel and the oracle: too few cells for the joint regression)
             HIP_TRY(h, hipMemsetAsync(ma.Dmiss, 0, (size_t)B * N * NPe * sizeof(double), h->stream));
             { ProfScope ps(h, K_MSTEP_STATS); HIP_TRY(h, launch_mstep_lam(Re, ma, h->stream)); }
@@ -1615,16 +1569,7 @@ int obs_em_run(dfm_handle* h, int B, int T, int N, int ru, int ro, const double*
         }
         return 0;
     })) return rc;
-    const size_t np = (size_t)ru * (ru + 1) / 2, npl = (size_t)Rl * (Rl + 1) / 2;
-    if (padded) {
-        if (int rc = copy_block(h, B, Rp, Rp, ru, ru, AP, A)) return rc;
-        if (int rc = copy_block(h, B, Rp, Rp, ru, ru, QP, Q)) return rc;
-        if (int rc = copy_block(h, B, Rp, Rp, ru, ru, P0P, P0)) return rc;
-        if (int rc = copy_block(h, B, 1, Rp, 1, ru, mu0P, mu0)) return rc;
-    }
-    if (f_smooth) if (int rc = copy_block(h, (size_t)B * T, 1, Rl, 1, ru, fsm, f_smooth)) return rc;
-    if (P_smooth) if (int rc = copy_block(h, (size_t)B * T, 1, (int)npl, 1, (int)np, Psm, P_smooth)) return rc;
-    return 0;
+    return unpad_results(h, p, B, N, T, ru, ru, ru, mb, nullptr, A, Q, mu0, P0, f_smooth, P_smooth);
 }
 
 }  // namespace
@@ -2414,10 +2359,9 @@ int dfm_standardize_batch_dev(dfm_handle* h, int B, int T, int N, double* panel,
 // P_out in the T + H row layout).  p > 1: the panel with H all-missing rows appended goes into xhat, the companion pass runs on it
 // as a (T + H)-row panel with missing cells straight into f_out / P_out (the smoothed moments of the empty rows are the forecast
 // moments), forecast_fill_kernel rewrites xhat in place.
-int dfm_forecast_batch_dev(dfm_handle* h, int B, int T, int N, int r, int p, int H, const double* panel, const double* Lam,
-                           const double* R, const double* Avar, const double* Q, const double* mu0, const double* P0,
-                           const double* mean, const double* sd, double* xhat, double* xvar, double* common, double* f_out,
-                           double* P_out, double* loglik, unsigned flags) {
+static int forecast_check(dfm_handle* h, int B, int T, int N, int r, int p, int H, const double* panel, const double* Lam,
+                          const double* R, const double* Avar, const double* Q, const double* mu0, const double* P0,
+                          const double* mean, const double* sd, const double* xhat, const double* f_out) {
     if (int rc = check_dims(h, B, T, N, r)) return rc;
     if (H < 0) return fail(h, DFM_E_DIMS, "H must be >= 0%s");
     if (p < 1) return fail(h, DFM_E_DIMS, "number of factor lags must be >= 1%s");
@@ -2425,6 +2369,13 @@ int dfm_forecast_batch_dev(dfm_handle* h, int B, int T, int N, int r, int p, int
     if (!panel || !Lam || !R || !Avar || !Q || !mu0 || !P0 || !xhat || !f_out)
         return fail(h, DFM_E_NULL, "required pointer is NULL%s");
     if ((mean == nullptr) != (sd == nullptr)) return fail(h, DFM_E_NULL, "mean and sd must both be given or both be NULL%s");
+    return 0;
+}
+int dfm_forecast_batch_dev(dfm_handle* h, int B, int T, int N, int r, int p, int H, const double* panel, const double* Lam,
+                           const double* R, const double* Avar, const double* Q, const double* mu0, const double* P0,
+                           const double* mean, const double* sd, double* xhat, double* xvar, double* common, double* f_out,
+                           double* P_out, double* loglik, unsigned flags) {
+    if (int rc = forecast_check(h, B, T, N, r, p, H, panel, Lam, R, Avar, Q, mu0, P0, mean, sd, xhat, f_out)) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     const size_t d = sizeof(double), np = (size_t)r * (r + 1) / 2, TH = (size_t)T + H;
     const bool needP = xvar != nullptr || P_out != nullptr;
@@ -2475,13 +2426,7 @@ int dfm_forecast_batch(dfm_handle* h, int B, int T, int N, int r, int p, int H, 
                        const double* R, const double* Avar, const double* Q, const double* mu0, const double* P0,
                        const double* mean, const double* sd, double* xhat, double* xvar, double* common, double* f_out,
                        double* P_out, double* loglik, unsigned flags) {
-    if (int rc = check_dims(h, B, T, N, r)) return rc;
-    if (H < 0) return fail(h, DFM_E_DIMS, "H must be >= 0%s");
-    if (p < 1) return fail(h, DFM_E_DIMS, "number of factor lags must be >= 1%s");
-    if (r * p > DFM_MAX_R) return fail(h, DFM_E_R_UNSUPPORTED, "r * p > DFM_MAX_R (32)%s");
-    if (!panel || !Lam || !R || !Avar || !Q || !mu0 || !P0 || !xhat || !f_out)
-        return fail(h, DFM_E_NULL, "required pointer is NULL%s");
-    if ((mean == nullptr) != (sd == nullptr)) return fail(h, DFM_E_NULL, "mean and sd must both be given or both be NULL%s");
+    if (int rc = forecast_check(h, B, T, N, r, p, H, panel, Lam, R, Avar, Q, mu0, P0, mean, sd, xhat, f_out)) return rc;
     if (int rc = status_epoch(h)) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     const size_t k = (size_t)r * p, np = (size_t)r * (r + 1) / 2, TH = (size_t)T + H, n_R = (size_t)B * N, n_x = (size_t)B * TH * N;
@@ -3210,9 +3155,8 @@ int dfm_filter_batch_dev(dfm_handle* h, int B, int T, int N, int r, int p, int H
         const size_t n = (size_t)B * N * Rp > B * rr ? (size_t)B * N * Rp : B * rr;
         ProfScope ps(h, K_PAD);
         // (A, Q, P0 and mu0 are read as if r wide -- in bounds of the caller's arrays, which are at least that large -- into `pad`)
-        hipLaunchKernelGGL(pad_params_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, B, N, r, Rp, Rp, Lam, Avar, Q,
-                           mu0, P0, at<double>(h->ft, o_lam), pad, pad + B * rr, pad + 3 * B * rr, pad + 2 * B * rr);
-        HIP_TRY(h, hipGetLastError());
+        if (int rc = launch_1d(h, pad_params_kernel, n, B, N, r, Rp, Rp, Lam, Avar, Q, mu0, P0, at<double>(h->ft, o_lam), pad,
+                               pad + B * rr, pad + 3 * B * rr, pad + 2 * B * rr)) return rc;
         LamP = at<double>(h->ft, o_lam);
     }
     CollapseArgs ca{};
