@@ -49,6 +49,7 @@ _IRF_ARGS = [c_vp] + [c_int] * 5 + [c_vp] * 9 + [c_uint]
 _SG_ARGS = ([c_vp] + [c_int] * 5 + [c_vp] * 7 + [c_int, c_vp, c_int, c_int, ctypes.c_uint64, ctypes.c_int64] + [c_vp] * 6
             + [c_uint])
 _HD_ARGS = [c_vp] + [c_int] * 5 + [c_vp] * 13 + [c_uint]
+_PX_ARGS = [c_vp] + [c_int] * 6 + [c_vp] * 10 + [c_int] * 3 + [ctypes.c_uint64, ctypes.c_int64] + [c_vp] * 7 + [c_uint]
 _FT_ARGS = [c_vp] + [c_int] * 7 + [c_vp] * 20 + [c_uint]
 _ARPASS_ARGS = [c_vp, c_int, c_int, c_int, c_int, c_int, c_int] + [c_vp] * 11 + [c_uint]
 _AREM_ARGS = [c_vp, c_int, c_int, c_int, c_int, c_int, c_int] + [c_vp] * 8 + [c_int, ctypes.c_double] + [c_vp] * 4 + [c_uint]
@@ -112,6 +113,8 @@ SYMBOLS = {
     "dfm_irf_batch": (c_int, _IRF_ARGS),
     "dfm_signirf_batch_dev": (c_int, _SG_ARGS),
     "dfm_signirf_batch": (c_int, _SG_ARGS),
+    "dfm_proxyirf_batch_dev": (c_int, _PX_ARGS),
+    "dfm_proxyirf_batch": (c_int, _PX_ARGS),
     "dfm_histdecomp_batch_dev": (c_int, _HD_ARGS),
     "dfm_histdecomp_batch": (c_int, _HD_ARGS),
     "dfm_filter_batch_dev": (c_int, _FT_ARGS),

@@ -823,6 +823,129 @@ def structural_irf_signs(m: DFMModel, H: int, restrictions, *, candidates: int =
     return out
 
 
+_QUANTILE_MAX_DRAWS = 16384          # dfm_quantile_bands: draws per call, at most
+
+
+def structural_irf_proxy(m: DFMModel, H: int, instrument, *, norm, draws: int = 0, block: Optional[int] = None, cumulate=None,
+                         unit_effect: bool = False, fevd: bool = True, quantiles=None, parameter_draws: bool = False,
+                         seed: int = 20160415, ctx=None) -> dict:
+    """Impulse responses to ONE structural shock identified by an external instrument (proxy SVAR), from the parametric fit
+    (`estimate(m, Parametric())`, nfac_o = 0); definitions in include/dfm_hip.h (dfm_proxyirf_batch).  The instrument is
+    correlated with the shock of interest and with no other; the covariance of the factor-VAR innovations with it gives the
+    shock's impact column.  No ordering, no named series: the answer does not depend on the rotation the fit sits in.
+
+    `instrument`: one entry per row of m.data, NaN where it does not exist; the estimation window's rows are used.  `norm`: a
+    column index of m.data; the shock is signed so that this series rises on impact, and with `unit_effect` it rises by one data
+    unit.  `cumulate`: column indices of the series that entered in differences.  `draws`: moving block bootstrap draws of the
+    instrument moment (blocks of `block` usable periods; the default block length is ceil(n ** (1/3)) for n usable periods), drawn
+    on the GPU as a pure function of `seed`.  Returns a dict:
+      cols           column indices of m.data: the series estimate() used
+      irf            [len(cols), H] in data units
+      fevd           [len(cols), H] share of the forecast-error variance due to the shock (None if not asked for)
+      impact         [r] the impact column in the fit's own rotation
+      relevance      the squared correlation of the instrument with the identified shock under the model's Q
+      shock          [window rows] the identified unit-variance shock (zero in the first factor_lags rows)
+      first_stage_F  the F statistic of the regression of the instrument on the factor innovations over the usable periods
+    `quantiles` (needs draws >= 1): pointwise bands [nq, len(cols), H] by dfm_quantile_bands over the block draws of the point
+    estimate, or with `parameter_draws=True` (needs m.replicates) over `draws` block draws of every replicate pooled; replicates x
+    draws may not exceed 16384.  Q must be positive definite for the identification; a numeric failure of the pass is retried once
+    in covariance form.  The historical decomposition under the identified shock, several instruments, weak-instrument-robust
+    sets, AR-idiosyncratic and mixed-frequency fits are out of scope.  `m` is not modified."""
+    H, D = int(H), int(draws)
+    if H < 1:
+        raise ValueError("H must be >= 1")
+    if D < 0:
+        raise ValueError("draws must be >= 0")
+    _structural_checks(m)
+    qs = None
+    if quantiles is not None:
+        if D < 1:
+            raise ValueError("quantile bands need draws >= 1")
+        qs = np.atleast_1d(np.asarray(quantiles, dtype=np.float64))
+        if qs.size < 1 or not np.all((qs > 0.0) & (qs <= 1.0)):
+            raise ValueError("quantiles must lie in (0, 1]")
+    if parameter_draws and getattr(m, "replicates", None) is None:
+        raise ValueError("parameter draws need bootstrap replicates: estimate(m, Parametric(), nrep=...) first")
+    nrep = m.replicates["params"]["Lam"].shape[0] if parameter_draws else 1
+    if qs is not None and nrep * D > _QUANTILE_MAX_DRAWS:
+        raise ValueError(f"quantile bands pool replicates x draws = {nrep} x {D} draws; at most {_QUANTILE_MAX_DRAWS} fit one call")
+    ep = m.em_params
+    Lam, R, Q = ep["Lam"], ep["R"], ep["Q"]
+    A = ep["Avar"] if "Avar" in ep else ep["A"]
+    N, r = Lam.shape
+    p = A.shape[1] // r
+    cols, z, _, sd = _forecast_inputs(m, m.lastperiod)
+    if N != cols.size:
+        raise ValueError("m.em_params does not match the model's series (was the model changed after estimate?)")
+    if np.any(np.nan_to_num(np.asarray(m.uar_coef, dtype=np.float64)[cols]) != 0.0):
+        raise ValueError("structural_irf_proxy has no AR idiosyncratic terms: the model carries uar_coef (estimate_ar_idio?)")
+    inst = np.asarray(instrument, dtype=np.float64).reshape(-1)
+    if inst.size != m.data.shape[0]:
+        raise ValueError(f"the instrument must have one entry per row of m.data ({m.data.shape[0]}), NaN where it does not exist")
+    zi = np.ascontiguousarray(inst[m.initperiod - 1:m.lastperiod])
+    used = np.nonzero(np.isfinite(zi[p:]))[0] + p
+    n = used.size
+    if n < r + 2:
+        raise ValueError(f"the instrument has {n} usable periods in the estimation window; at least r + 2 = {r + 2} are needed")
+    L = int(np.ceil(n ** (1.0 / 3.0) - 1e-12)) if block is None else int(block)
+    if not 1 <= L <= n:
+        raise ValueError(f"block must lie in 1..{n} (the usable periods)")
+    nrm = int(_to_cols(norm, cols, "norm")[0])
+    cum = None
+    if cumulate is not None:
+        cum = np.zeros(N, dtype=np.int32)
+        cum[_to_cols(cumulate, cols, "cumulate")] = 1
+    from ._lib import DfmError
+    ctx, own = _own(ctx)
+    try:
+        def run(Lb, Rb, Ab, Qb, m0, P0b, Dd, want_fevd, want_shock):
+            B = Lb.shape[0]
+            rep = lambda a: np.ascontiguousarray(np.broadcast_to(a, (B,) + a.shape))
+            call = lambda sq: ctx.proxyirf_batch_host(
+                rep(z), Lb, Rb, Ab, Qb, m0, P0b, H, zi, nrm, draws=Dd, block=L, seed=seed, sd=rep(sd), cum=cum,
+                unit_effect=unit_effect, want_fevd=want_fevd, want_shock=want_shock, may_have_missing=bool(np.isnan(z).any()),
+                singular_q=sq)
+            try:
+                return _numeric_retry(call)
+            except DfmError as err:
+                if err.code != -5:
+                    raise
+                text = str(err).split(": ", 2)[-1]
+                raise DfmError(err.code, f"{text}; identification by an instrument needs Q positive definite") from None
+        o = run(Lam[None], R[None], A[None], Q[None], ep["mu0"][None], ep["P0"][None], 0 if parameter_draws else D, fevd, True)
+        bands = None
+        if qs is not None:
+            if parameter_draws:
+                rp = m.replicates["params"]
+                pooled = run(rp["Lam"], rp["R"], rp["A"], rp["Q"], rp["mu0"], rp["P0"], D, False, False)["irf"][:, 1:]
+            else:
+                pooled = o["irf"][:, 1:]
+            pooled = pooled.reshape(-1, H * N)
+            pooled = np.ascontiguousarray(pooled[np.isfinite(pooled[:, 0])])
+            if pooled.shape[0] == 0:
+                raise ValueError("no block draw gave a finite response")
+            bands = ctx.quantile_bands_host(pooled, qs).reshape(qs.size, H, N)
+    finally:
+        if own:
+            ctx.close()
+    f = o["f"][0]
+    eta = f[p:].copy()
+    for j in range(p):
+        eta -= f[p - 1 - j:f.shape[0] - 1 - j] @ A[:, j * r:(j + 1) * r].T
+    X = np.column_stack([np.ones(n), eta[used - p]])
+    y = zi[used]
+    res = y - X @ np.linalg.lstsq(X, y, rcond=None)[0]
+    rss, tss = float(res @ res), float(((y - y.mean()) ** 2).sum())
+    F = ((tss - rss) / r) / (rss / (n - r - 1)) if rss > 0.0 else np.inf
+    out = dict(cols=cols, irf=np.ascontiguousarray(o["irf"][0, 0].T),
+               fevd=None if o["fevd"] is None else np.ascontiguousarray(o["fevd"][0, 0].T), impact=o["impact"][0, 0].copy(),
+               relevance=float(o["rel"][0, 0]), shock=o["shock"][0].copy(), first_stage_F=float(F))
+    if bands is not None:
+        out["quantiles"] = qs
+        out["bands"] = np.ascontiguousarray(bands.transpose(0, 2, 1))
+    return out
+
+
 def historical_decomposition(m: DFMModel, *, named=None, through: Optional[int] = None, ctx=None) -> dict:
     """Which shocks drove every series through the sample: the contribution of each identified factor shock and of the initial
     condition to the common component of every cell, from the parametric fit (`estimate(m, Parametric())`, nfac_o = 0);

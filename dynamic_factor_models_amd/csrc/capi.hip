@@ -157,11 +157,14 @@ struct dfm_handle {
                                            // parameters, u / a vectors, smoothed means and (no weight) covariance panels
     DevBlock sv;                           // dfm_irf_batch_dev / dfm_histdecomp_batch_dev: named / cum, S, S^-1, the Theta tables, shocks and
                                            // contribution paths, and the pass outputs the caller does not take; dfm_signirf_batch_dev:
-                                           // the restrictions, their table, mask, counts, rotations and the kept slots' tables
+                                           // the restrictions, their table, mask, counts, rotations and the kept slots' tables;
+                                           // dfm_proxyirf_batch_dev: cum, the used rows, the instrument, S, S^-1, the Theta tables, the row
+                                           // table, the slots' w and tables, the den table and the pass outputs the caller does not take
     DevBlock ft;                           // dfm_filter_batch_dev: the padded loadings, the collapse's per-period arrays, the moments the
                                            // caller does not take and the evaluation's running sums
     DevBlock gb;                           // dfm_gibbs_batch_dev: the sweep's factor path and the shared Gram roots of balanced panels
     std::vector<int> sv_idx;               // host copy of named / cum while their upload is in flight
+    std::vector<double> sv_z;              // dfm_proxyirf_batch_dev: host copy of the instrument while its upload is in flight
     const double* odd_panel_src = nullptr; int odd_panel_dims[3] = {0, 0, 0};   // the panel whose padded copy h->odd holds (odd_pad keep_panel)
     std::string prof_file;                 // DFM_PF_PROF_FILE with DFM_SCAN_ABL=256: phase stamps of the fused pass
     char err[512] = {0};
@@ -173,11 +176,11 @@ struct dfm_handle {
 };
 
 enum KernelId { K_COLLAPSE = 0, K_RECURSION, K_MSTEP_STATS, K_MSTEP_SOLVE, K_PCA, K_SYNTH, K_PAD,
-                K_COLLAPSE_DMA, K_GRAM, K_COV, K_MEANSCAN, K_PFILL, K_COLLAPSE_MFMA, K_ALS, K_OLS, K_BOOT, K_QUANT, K_COLLAPSE_WIDE, K_EM_UPDATE, K_CHOW, K_MSTEP_MFMA, K_GRAM_XX, K_PASS_FUSED, K_FC_TAIL, K_FC_FILL, K_FC_PAD, K_SS_PREP, K_SS_EXPAND, K_SS_PATH, K_SS_DIFF, K_SS_FINISH, K_SS_FILL, K_NW_REVISE, K_NW_GATHER, K_NW_GAMMA, K_NW_COV, K_NW_IMPACT, K_MF_TABLE, K_MF_MOMENTS, K_MF_SOLVE, K_SV_PREP, K_SV_IRF_FILL, K_SV_SHOCK, K_SV_PATH, K_SV_HD_FILL, K_FT_FILTER, K_FT_FILL, K_FT_EVAL, K_GB_GRAM, K_GB_LOAD, K_GB_VAR, K_SV_SIGN_TABLE, K_SV_SIGN, K_SV_SIGN_KEEP, K_COUNT };
+                K_COLLAPSE_DMA, K_GRAM, K_COV, K_MEANSCAN, K_PFILL, K_COLLAPSE_MFMA, K_ALS, K_OLS, K_BOOT, K_QUANT, K_COLLAPSE_WIDE, K_EM_UPDATE, K_CHOW, K_MSTEP_MFMA, K_GRAM_XX, K_PASS_FUSED, K_FC_TAIL, K_FC_FILL, K_FC_PAD, K_SS_PREP, K_SS_EXPAND, K_SS_PATH, K_SS_DIFF, K_SS_FINISH, K_SS_FILL, K_NW_REVISE, K_NW_GATHER, K_NW_GAMMA, K_NW_COV, K_NW_IMPACT, K_MF_TABLE, K_MF_MOMENTS, K_MF_SOLVE, K_SV_PREP, K_SV_IRF_FILL, K_SV_SHOCK, K_SV_PATH, K_SV_HD_FILL, K_FT_FILTER, K_FT_FILL, K_FT_EVAL, K_GB_GRAM, K_GB_LOAD, K_GB_VAR, K_SV_SIGN_TABLE, K_SV_SIGN, K_SV_SIGN_KEEP, K_PX_ROWS, K_PX_MOMENT, K_PX_SLOT_TABLE, K_PX_DEN, K_PX_FILL, K_PX_SHOCK, K_COUNT };
 static const char* const kKernelNames[K_COUNT] = {"collapse_kernel", "recursion_kernel", "mstep_lam_kernel",
                                                   "mstep_solve_kernel", "pca_kernel", "synth_kernel",
                                                   "pad_params_kernel", "collapse_dma_kernel", "gram_kernel",
-                                                  "cov_kernel", "meanscan_kernel", "pfill_kernel", "collapse_mfma_kernel", "als_kernel", "ols_kernel", "var_boot_kernel", "quantile_kernel", "collapse_wide_kernel", "em_update_kernel", "chow_kernel", "mstep_mfma_kernel", "gram_xx_kernel", "pass_fused_kernel", "forecast_tail_kernel", "forecast_fill_kernel", "forecast_pad_kernel", "simsmooth_prep_kernel", "simsmooth_expand_kernel", "simsmooth_path_kernel", "simsmooth_diff_kernel", "simsmooth_finish_kernel", "simsmooth_fill_kernel", "news_revise_kernel", "news_gather_kernel", "news_gamma_kernel", "news_cov_panel_kernel", "news_impact_kernel", "mf_table_kernel", "mf_moments_kernel", "mf_solve_kernel", "sv_prep_kernel", "sv_irf_fill_kernel", "sv_shock_kernel", "sv_path_kernel", "sv_hd_fill_kernel", "filter_kernel", "filter_fill_kernel", "filter_eval_kernel", "gibbs_gram_kernel", "gibbs_load_kernel", "gibbs_var_kernel", "sv_sign_table_kernel", "sv_sign_kernel", "sv_sign_keep_kernel"};
+                                                  "cov_kernel", "meanscan_kernel", "pfill_kernel", "collapse_mfma_kernel", "als_kernel", "ols_kernel", "var_boot_kernel", "quantile_kernel", "collapse_wide_kernel", "em_update_kernel", "chow_kernel", "mstep_mfma_kernel", "gram_xx_kernel", "pass_fused_kernel", "forecast_tail_kernel", "forecast_fill_kernel", "forecast_pad_kernel", "simsmooth_prep_kernel", "simsmooth_expand_kernel", "simsmooth_path_kernel", "simsmooth_diff_kernel", "simsmooth_finish_kernel", "simsmooth_fill_kernel", "news_revise_kernel", "news_gather_kernel", "news_gamma_kernel", "news_cov_panel_kernel", "news_impact_kernel", "mf_table_kernel", "mf_moments_kernel", "mf_solve_kernel", "sv_prep_kernel", "sv_irf_fill_kernel", "sv_shock_kernel", "sv_path_kernel", "sv_hd_fill_kernel", "filter_kernel", "filter_fill_kernel", "filter_eval_kernel", "gibbs_gram_kernel", "gibbs_load_kernel", "gibbs_var_kernel", "sv_sign_table_kernel", "sv_sign_kernel", "sv_sign_keep_kernel", "px_rows_kernel", "px_moment_kernel", "px_slot_table_kernel", "px_den_kernel", "px_fill_kernel", "px_shock_kernel"};
 
 namespace dfm { int handle_device(const dfm_handle* h) { return h->device; } }   // (probe.hip)
 
@@ -1786,7 +1789,7 @@ int dfm_ks_pass_batch_dev(dfm_handle* h, int B, int T, int N, int r, const doubl
 // declared balanced, 2 = the PCA start's subspace iteration did not converge, 4 = a bounded wait between the waves of the
 // one-launch pass ran out (its outputs are invalid even where the log-likelihood happens to be finite), 8 = dfm_news_batch: a cell
 // of the old vintage is observed where the new one is missing, 16 = dfm_irf_batch / dfm_histdecomp_batch: a zero pivot in
-// Lam[named, :] or (decomposition) in the root of Q, 32 = dfm_filter_batch: a replicate's update failed.  Every synchronising
+// Lam[named, :] or (decomposition, dfm_proxyirf_batch) in the root of Q, 32 = dfm_filter_batch: a replicate's update failed.  Every synchronising
 // entry point goes through here; device-pointer callers get the same check from dfm_synchronize / dfm_check_status.
 static int status_check(dfm_handle* h) {
     if (!h->status_dev) return 0;
@@ -2963,6 +2966,153 @@ int dfm_histdecomp_batch(dfm_handle* h, int B, int T, int N, int r, int p, const
     if (int rc = st.begin()) return rc;
     int rc = st.finish(dfm_histdecomp_batch_dev(h, B, T, N, r, p, x_d, lam_d, R_d, A_d, Q_d, mu_d, P0_d, sd_d, named, hd_d, u_d, f_d, ll_d,
                                                 flags));
+    if (rc == 0) rc = post_check(h, ll_host.data(), B);
+    if (rc == 0 && loglik) memcpy(loglik, ll_host.data(), (size_t)B * sizeof(double));
+    return rc;
+}
+
+// ---- impulse responses identified by an external instrument (proxy.hip) ----------------------------------------------------------
+// Sizes, norm and the instrument first (they are decided before the handle is looked at), then the handle and the required
+// pointers.  *U: the used rows {t : p <= t < T, z_t finite}, built once per call.
+static int proxyirf_check(dfm_handle* h, int B, int T, int N, int r, int p, int H, const double* panel, const double* Lam,
+                          const double* R, const double* Avar, const double* Q, const double* mu0, const double* P0, const double* z,
+                          int norm, int D, int L, int64_t first_draw, const double* impact, const double* rel, std::vector<int>* U) {
+    if (H < 1) return fail(h, DFM_E_DIMS, "H must be >= 1%s");
+    if (D < 0 || first_draw < 0) return fail(h, DFM_E_DIMS, "need D >= 0 and first_draw >= 0%s");
+    if (B < 1 || T < 1 || N < 1 || r < 1) return fail(h, DFM_E_DIMS, "B, T, N, r must be >= 1%s");
+    if (p < 1) return fail(h, DFM_E_DIMS, "number of factor lags must be >= 1%s");
+    if (r > DFM_MAX_R || (long long)r * p > DFM_MAX_R) return fail(h, DFM_E_R_UNSUPPORTED, "r * p > DFM_MAX_R (32)%s");
+    if (T < p + 1) return fail(h, DFM_E_DIMS, "T must be >= p + 1%s");
+    if (norm < 0 || norm >= N) return fail(h, DFM_E_DIMS, "norm lies outside [0, N)%s");
+    if ((long long)B * ((long long)D + 1) > 0x7fffffffLL) return fail(h, DFM_E_DIMS, "B * (D + 1) must be < 2^31%s");
+    if (L < 1) return fail(h, DFM_E_DIMS, "the block length L must be >= 1%s");
+    if (z) {
+        U->clear();
+        for (int t = p; t < T; ++t)
+            if (isfinite(z[t])) U->push_back(t);
+        const int n = (int)U->size();
+        if (n < r + 2) return fail(h, DFM_E_DIMS, "the instrument has fewer than r + 2 usable periods%s");
+        if (L > n) return fail(h, DFM_E_DIMS, "the block length L exceeds the number of usable periods%s");
+    }
+    if (!h) return DFM_E_NULL;
+    if (!panel || !Lam || !R || !Avar || !Q || !mu0 || !P0 || !z || !impact || !rel) return fail(h, DFM_E_NULL, "required pointer is NULL%s");
+    return 0;
+}
+
+// The checked call on device pointers (z and cum on the host): what both entries run.
+static int proxyirf_run(dfm_handle* h, int B, int T, int N, int r, int p, int H, const double* panel, const double* Lam,
+                        const double* R, const double* Avar, const double* Q, const double* mu0, const double* P0, const double* sd,
+                        const int* cum, const std::vector<int>& U, const double* z, int norm, int D, int L, uint64_t seed,
+                        int64_t first_draw, double* impact, double* rel, double* irf, double* fevd, double* shock, double* f_out,
+                        double* loglik, unsigned flags) {
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t d = sizeof(double), rr = (size_t)r * r, n_f = (size_t)B * T * r, BS = (size_t)B * ((size_t)D + 1);
+    const int n = (int)U.size();
+    bool any_cum = false;
+    if (cum)
+        for (int i = 0; i < N; ++i) any_cum = any_cum || cum[i] != 0;
+    if (!any_cum) cum = nullptr;
+    const bool fill = irf || fevd, unit = (flags & DFM_SV_UNIT_EFFECT) != 0;
+    // the host integers, in the order they lie at the start of h->sv: cum | U
+    std::vector<int>& ix = h->sv_idx;
+    ix.clear();
+    if (cum) ix.insert(ix.end(), cum, cum + N);
+    const size_t i_U = ix.size();
+    ix.insert(ix.end(), U.begin(), U.end());
+    h->sv_z.assign(z, z + T);
+    size_t off = 0;
+    const size_t o_ix = take(off, ix.size() * sizeof(int)), o_z = take(off, (size_t)T * d), o_S = take(off, B * rr * d),
+                 o_Si = take(off, B * rr * d), o_Th = take(off, (size_t)B * H * rr * d),
+                 o_Thc = cum ? take(off, (size_t)B * H * rr * d) : (size_t)-1, o_f = f_out ? (size_t)-1 : take(off, n_f * d),
+                 o_ll = loglik ? (size_t)-1 : take(off, (size_t)B * d), o_rows = take(off, (size_t)B * n * (r + 1) * d),
+                 o_w = take(off, BS * r * d), o_tk = fill ? take(off, BS * H * r * d) : (size_t)-1,
+                 o_tkc = (fill && cum) ? take(off, BS * H * r * d) : (size_t)-1,
+                 o_sc = (fill && unit) ? take(off, BS * d) : (size_t)-1, o_den = fevd ? take(off, (size_t)B * H * N * d) : (size_t)-1;
+    HIP_TRY(h, h->sv.grow(off));
+    int* ixd = at<int>(h->sv, o_ix);
+    HIP_TRY(h, hipMemcpyAsync(ixd, ix.data(), ix.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(at<double>(h->sv, o_z), h->sv_z.data(), (size_t)T * d, hipMemcpyHostToDevice, h->stream));
+    double* f = f_out ? f_out : at<double>(h->sv, o_f);
+    double* ll = loglik ? loglik : at<double>(h->sv, o_ll);
+    const unsigned pass_flags = flags & (DFM_F_MAY_HAVE_MISSING | DFM_F_SINGULAR_Q);
+    if (p == 1) {
+        if (int rc = dfm_ks_pass_batch_dev(h, B, T, N, r, panel, Lam, R, Avar, Q, mu0, P0, f, nullptr, ll, pass_flags)) return rc;
+    } else {
+        if (int rc = dfm_ks_pass_varp_batch_dev(h, B, T, N, r, p, panel, Lam, R, Avar, Q, mu0, P0, f, nullptr, ll, pass_flags)) return rc;
+    }
+    SvArgs a{};
+    a.B = B; a.N = N; a.r = r; a.p = p; a.H = H; a.T = T;
+    a.Lam = Lam; a.A = Avar; a.Q = Q; a.sd = sd;
+    a.need_pd = 1; a.status = h->status_dev;
+    a.S = at<double>(h->sv, o_S); a.Sinv = at<double>(h->sv, o_Si); a.Th = at<double>(h->sv, o_Th); a.Thc = at<double>(h->sv, o_Thc);
+    {
+        ProfScope ps(h, K_SV_PREP);
+        HIP_TRY(h, launch_sv_prep(a, h->stream));
+    }
+    PxArgs g{};
+    g.B = B; g.T = T; g.N = N; g.r = r; g.p = p; g.H = H; g.n = n; g.D = D; g.L = L; g.norm = norm; g.unit = unit ? 1 : 0;
+    g.Lam = Lam; g.sd = sd; g.A = Avar; g.cum = cum ? ixd : nullptr; g.U = ixd + i_U; g.z = at<double>(h->sv, o_z); g.f = f;
+    g.S = a.S; g.Sinv = a.Sinv; g.Th = a.Th; g.Thc = a.Thc;
+    g.seed = seed; g.first_draw = first_draw;
+    g.rows = at<double>(h->sv, o_rows); g.impact = impact; g.rel = rel; g.w = at<double>(h->sv, o_w);
+    g.tk = at<double>(h->sv, o_tk); g.tkc = at<double>(h->sv, o_tkc); g.scale = at<double>(h->sv, o_sc);
+    g.R = R; g.den = at<double>(h->sv, o_den); g.irf = irf; g.fevd = fevd; g.shock = shock;
+    {
+        ProfScope ps(h, K_PX_ROWS);
+        HIP_TRY(h, launch_px_rows(g, h->stream));
+    }
+    {
+        ProfScope ps(h, K_PX_MOMENT);
+        HIP_TRY(h, launch_px_moment(g, h->stream));
+    }
+    if (shock) {
+        ProfScope ps(h, K_PX_SHOCK);
+        HIP_TRY(h, launch_px_shock(g, h->stream));
+    }
+    if (!fill) return 0;
+    {
+        ProfScope ps(h, K_PX_SLOT_TABLE);
+        HIP_TRY(h, launch_px_slot_table(g, h->stream));
+    }
+    if (fevd) {
+        ProfScope ps(h, K_PX_DEN);
+        HIP_TRY(h, launch_px_den(g, h->stream));
+    }
+    ProfScope ps(h, K_PX_FILL);
+    HIP_TRY(h, launch_px_fill(g, h->stream));
+    return 0;
+}
+
+int dfm_proxyirf_batch_dev(dfm_handle* h, int B, int T, int N, int r, int p, int H, const double* panel, const double* Lam,
+                           const double* R, const double* Avar, const double* Q, const double* mu0, const double* P0,
+                           const double* sd, const int* cum, const double* z, int norm, int D, int L, uint64_t seed,
+                           int64_t first_draw, double* impact, double* rel, double* irf, double* fevd, double* shock,
+                           double* f_out, double* loglik, unsigned flags) {
+    std::vector<int> U;
+    if (int rc = proxyirf_check(h, B, T, N, r, p, H, panel, Lam, R, Avar, Q, mu0, P0, z, norm, D, L, first_draw, impact, rel, &U)) return rc;
+    return proxyirf_run(h, B, T, N, r, p, H, panel, Lam, R, Avar, Q, mu0, P0, sd, cum, U, z, norm, D, L, seed, first_draw, impact, rel,
+                        irf, fevd, shock, f_out, loglik, flags);
+}
+
+int dfm_proxyirf_batch(dfm_handle* h, int B, int T, int N, int r, int p, int H, const double* panel, const double* Lam,
+                       const double* R, const double* Avar, const double* Q, const double* mu0, const double* P0, const double* sd,
+                       const int* cum, const double* z, int norm, int D, int L, uint64_t seed, int64_t first_draw, double* impact,
+                       double* rel, double* irf, double* fevd, double* shock, double* f_out, double* loglik, unsigned flags) {
+    std::vector<int> U;
+    if (int rc = proxyirf_check(h, B, T, N, r, p, H, panel, Lam, R, Avar, Q, mu0, P0, z, norm, D, L, first_draw, impact, rel, &U)) return rc;
+    if (int rc = status_epoch(h)) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t k = (size_t)r * p, n_R = (size_t)B * N, n_f = (size_t)B * T * r, BS = (size_t)B * ((size_t)D + 1), n_o = BS * H * N;
+    std::vector<double> ll_host((size_t)B);                     // (checked before the caller's loglik, which is optional, is written)
+    HostStage st(h, 256);
+    double *x_d, *lam_d, *R_d, *A_d, *Q_d, *mu_d, *P0_d, *sd_d, *im_d, *rel_d, *irf_d, *fv_d, *u_d, *f_d, *ll_d;
+    st.in(panel, (size_t)B * T * N, x_d); st.in(Lam, n_R * r, lam_d); st.in(R, n_R, R_d); st.in(Avar, (size_t)B * r * k, A_d);
+    st.in(Q, (size_t)B * r * r, Q_d); st.in(mu0, (size_t)B * k, mu_d); st.in(P0, (size_t)B * k * k, P0_d); st.in(sd, sd ? n_R : 0, sd_d);
+    st.out(impact, BS * r, im_d); st.out(rel, BS, rel_d); st.out(irf, irf ? n_o : 0, irf_d); st.out(fevd, fevd ? n_o : 0, fv_d);
+    st.out(shock, shock ? (size_t)B * T : 0, u_d); st.out(f_out, f_out ? n_f : 0, f_d); st.out(ll_host.data(), (size_t)B, ll_d);
+    if (int rc = st.begin()) return rc;
+    int rc = st.finish(proxyirf_run(h, B, T, N, r, p, H, x_d, lam_d, R_d, A_d, Q_d, mu_d, P0_d, sd_d, cum, U, z, norm, D, L, seed,
+                                    first_draw, im_d, rel_d, irf_d, fv_d, u_d, f_d, ll_d, flags));
     if (rc == 0) rc = post_check(h, ll_host.data(), B);
     if (rc == 0 && loglik) memcpy(loglik, ll_host.data(), (size_t)B * sizeof(double));
     return rc;

@@ -602,6 +602,41 @@ hipError_t launch_sv_sign_table(const SgArgs& a, hipStream_t s);
 hipError_t launch_sv_sign(const SgArgs& a, hipStream_t s);
 hipError_t launch_sv_sign_keep(const SgArgs& a, hipStream_t s);
 
+// Impulse responses identified by an external instrument (proxy.hip): slot 0 = the sample, slots 1 .. D = moving block draws of
+// the n used rows.  S = chol(Q), S^-1 and the tables Theta_h = Psi_h S come from sv_prep_kernel with named = null.
+constexpr int kPxLanes = 256;                     // px_moment_kernel: slots per workgroup, one per lane
+constexpr size_t kPxTabLds = 48 * 1024;           // px_moment_kernel: a row table up to this size sits in LDS; a larger one is read
+                                                  // from global memory (through L2)
+struct PxArgs {
+    int B, T, N, r, p, H, n, D, L, norm, unit;    // n used rows, D block draws of length L; unit: DFM_SV_UNIT_EFFECT
+    const double* Lam; const double* sd;          // [B][N][r], [B][N] or null
+    const double* A;                              // [B][r][r p]
+    const int* cum;                               // device [N] or null
+    const int* U;                                 // device [n]: the used rows, increasing
+    const double* z;                              // device [T]: the instrument (NaN where not used)
+    const double* f;                              // [B][T][r] smoothed factors
+    const double* S; const double* Sinv;          // [B][r][r] (sv_prep_kernel)
+    const double* Th; const double* Thc;          // [B][H][r][r] shock-major; Thc null: nothing cumulated
+    uint64_t seed; int64_t first_draw;
+    double* rows;                                 // [B][n][r+1]: etahat and z of the used rows
+    double* impact; double* rel;                  // [B][D+1][r], [B][D+1]
+    double* w;                                    // [B][D+1][r]: S^-1 hvec, a unit vector (NaN for a NaN slot)
+    double* tk; double* tkc;                      // [B][D+1][H][r]: Theta_h w and the cumulated form (tkc null: nothing cumulated)
+    double* scale;                                // [B][D+1]: the unit-effect divisor of the slot (null: no unit effect)
+    const double* R;                              // [B][N] (the den table and fevd)
+    double* den;                                  // [B][H][N]: sum_k num_k + idio of dfm_irf_batch (null: no fevd)
+    double* irf; double* fevd;                    // [B][D+1][H][N] or null
+    double* shock;                                // [B][T] or null
+    CellGeom geo;                                 // geometry of the fill (set by its launcher)
+};
+size_t proxy_row_stride(int r);                   // doubles per row of the table in LDS: r + 1 rounded up to an odd number
+hipError_t launch_px_rows(const PxArgs& a, hipStream_t s);
+hipError_t launch_px_moment(const PxArgs& a, hipStream_t s);
+hipError_t launch_px_slot_table(const PxArgs& a, hipStream_t s);
+hipError_t launch_px_den(const PxArgs& a, hipStream_t s);
+hipError_t launch_px_fill(PxArgs a, hipStream_t s);
+hipError_t launch_px_shock(const PxArgs& a, hipStream_t s);
+
 // Filtered states, prediction errors and out-of-sample evaluation (filter.hip).  k = r p, kk = k (k + 1) / 2.
 struct FtArgs {
     int B, T, N, r, p, Rp, H, t0;                 // Rp: width of the collapse's rows (pad_r(r))

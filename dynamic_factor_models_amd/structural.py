@@ -1,7 +1,7 @@
-"""Binding of the structural entries of include/dfm_hip.h (csrc/structural.hip, csrc/signirf.hip): dfm_irf_batch[_dev],
-dfm_histdecomp_batch[_dev] and dfm_signirf_batch[_dev].  The functions take a DfmContext; importing this module (kalman.py does)
-also attaches them to DfmContext as irf_batch, irf_batch_host, histdecomp_batch, histdecomp_batch_host, signirf_batch and
-signirf_batch_host, with the marshalling conventions of forecast_batch(_host): device tensors in and out on torch's current
+"""Binding of the structural entries of include/dfm_hip.h (csrc/structural.hip, csrc/signirf.hip, csrc/proxy.hip):
+dfm_irf_batch[_dev], dfm_histdecomp_batch[_dev], dfm_signirf_batch[_dev] and dfm_proxyirf_batch[_dev].  The functions take a
+DfmContext; importing this module (kalman.py does) also attaches them to DfmContext as irf_batch, irf_batch_host, histdecomp_batch,
+histdecomp_batch_host, signirf_batch, signirf_batch_host, proxyirf_batch and proxyirf_batch_host, with the marshalling conventions of forecast_batch(_host): device tensors in and out on torch's current
 stream, or NumPy through the host-pointer entries.
 """
 from __future__ import annotations
@@ -115,6 +115,65 @@ def _signirf(ctx, be, Lam, Avar, Q, R, H, restrictions, candidates, keep, seed, 
     return dict(n_accept=n_accept, mask=mask, cand=cand, S=S, irf=irf, fevd=fevd)
 
 
+def _proxyirf(ctx, be, panel, params, H, instrument, norm, draws, block, seed, first_draw, sd, cum, unit_effect, want_irf, want_fevd,
+              want_shock, may_have_missing, singular_q):
+    panel, params, dims, _, shapes = _k._model(_k._VARP, be, panel, params)
+    B, T, N, r, p = dims
+    H, D, L, norm, first_draw = int(H), int(draws), int(block), int(norm), int(first_draw)
+    if H < 1:
+        raise ValueError("H must be >= 1")
+    if D < 0 or first_draw < 0:
+        raise ValueError("draws and first_draw must be >= 0")
+    if not 0 <= norm < N:
+        raise ValueError(f"norm must be a series index in 0..{N - 1}")
+    z = np.ascontiguousarray(np.asarray(instrument, dtype=np.float64).reshape(-1))
+    if z.size != T:
+        raise ValueError(f"the instrument must have {T} entries, one per period")
+    n = int(np.isfinite(z[p:]).sum())
+    if n < r + 2:
+        raise ValueError(f"the instrument has {n} usable periods; at least r + 2 = {r + 2} are needed")
+    if not 1 <= L <= n:
+        raise ValueError(f"block must lie in 1..{n} (the usable periods)")
+    sd = None if sd is None else be.inp(sd)
+    cum = _index(cum, N, "cum", False)
+    flags = _k._flags(may_have_missing, singular_q, be, panel) | (_lib.DFM_SV_UNIT_EFFECT if unit_effect else 0)
+    impact, rel = be.out(B, D + 1, r), be.out(B, D + 1)
+    irf = be.out(B, D + 1, H, N) if want_irf else None
+    fevd = be.out(B, D + 1, H, N) if want_fevd else None
+    shock = be.out(B, T) if want_shock else None
+    f, ll = be.out(B, T, r), be.out(B)
+    be.sync()
+    rc = getattr(ctx._lib, "dfm_proxyirf_batch" + be.suffix)(
+        ctx._h, B, T, N, r, p, H, be.ptr(panel, "panel"), *_k._ptrs(be, _k._VARP, params, shapes), be.ptr(sd, "sd", (B, N)),
+        _k._ptr(cum), _k._ptr(z), norm, D, L, int(seed) & 0xFFFFFFFFFFFFFFFF, first_draw, be.ptr(impact, "impact"),
+        be.ptr(rel, "rel"), be.ptr(irf, "irf"), be.ptr(fevd, "fevd"), be.ptr(shock, "shock"), be.ptr(f, "f_out"),
+        be.ptr(ll, "loglik"), flags)
+    _k._check(ctx._h, rc)
+    return dict(impact=impact, rel=rel, irf=irf, fevd=fevd, shock=shock, f=f, loglik=ll)
+
+
+def proxyirf_batch(ctx, panel, Lam, R, Avar, Q, mu0, P0, H: int, instrument, norm: int, draws: int = 0, block: int = 1,
+                   seed: int = 0, first_draw: int = 0, sd=None, cum=None, unit_effect: bool = False, want_irf: bool = True,
+                   want_fevd: bool = False, want_shock: bool = True, may_have_missing: Optional[bool] = None,
+                   singular_q: bool = False):
+    """dfm_proxyirf_batch_dev (device tensors, torch's current stream): the shock identified by the external `instrument` (host
+    side, one entry per period, NaN = not available), signed by series `norm`; slot 0 is the sample, slots 1 .. draws are moving
+    block draws (length `block`) of the instrument moment.  Parameters as histdecomp_batch, cum as irf_batch.  Returns dict(impact
+    [B,draws+1,r], rel [B,draws+1], irf [B,draws+1,H,N], fevd [B,draws+1,H,N], shock [B,T], f [B,T,r], loglik [B]; None when not
+    asked for).  Draws first_draw .. first_draw + draws - 1 of the stream of `seed`."""
+    return _proxyirf(ctx, _k._Torch(ctx, panel), panel, (Lam, R, Avar, Q, mu0, P0), H, instrument, norm, draws, block, seed,
+                     first_draw, sd, cum, unit_effect, want_irf, want_fevd, want_shock, may_have_missing, singular_q)
+
+
+def proxyirf_batch_host(ctx, panel, Lam, R, Avar, Q, mu0, P0, H: int, instrument, norm: int, draws: int = 0, block: int = 1,
+                        seed: int = 0, first_draw: int = 0, sd=None, cum=None, unit_effect: bool = False, want_irf: bool = True,
+                        want_fevd: bool = False, want_shock: bool = True, may_have_missing: Optional[bool] = None,
+                        singular_q: bool = False):
+    """dfm_proxyirf_batch (host pointers; what Julia's ccall binds): NumPy in / out, same dict as proxyirf_batch."""
+    return _proxyirf(ctx, _k._NP, panel, (Lam, R, Avar, Q, mu0, P0), H, instrument, norm, draws, block, seed, first_draw, sd, cum,
+                     unit_effect, want_irf, want_fevd, want_shock, may_have_missing, singular_q)
+
+
 def signirf_batch(ctx, Lam, Avar, Q, R, H: int, restrictions, candidates: int, keep: int = 1, seed: int = 0, first_cand: int = 0,
                   sd=None, named=None, cum=None, want_mask: bool = False, want_S: bool = True, want_irf: bool = True,
                   want_fevd: bool = False):
@@ -164,5 +223,6 @@ def histdecomp_batch_host(ctx, panel, Lam, R, Avar, Q, mu0, P0, sd=None, named=N
     return _histdecomp(ctx, _k._NP, panel, (Lam, R, Avar, Q, mu0, P0), sd, named, want_shocks, may_have_missing, singular_q)
 
 
-for _f in (irf_batch, irf_batch_host, histdecomp_batch, histdecomp_batch_host, signirf_batch, signirf_batch_host):
+for _f in (irf_batch, irf_batch_host, histdecomp_batch, histdecomp_batch_host, signirf_batch, signirf_batch_host, proxyirf_batch,
+           proxyirf_batch_host):
     setattr(_k.DfmContext, _f.__name__, _f)

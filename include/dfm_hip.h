@@ -492,6 +492,65 @@ int dfm_signirf_batch(dfm_handle* h, int B, int N, int r, int p, int H, const do
                       int K, uint64_t seed, int64_t first_cand, int* n_accept, int* mask_out, int* cand_out, double* S_out,
                       double* irf, double* fevd, unsigned flags);
 
+/* --- structural IRFs identified by an external instrument (proxy SVAR): batched block draws ---------------------------------------
+ * The model, sd, cum and the smoother pass are those of dfm_histdecomp_batch, with 1 <= r p <= DFM_MAX_R and Q positive definite.
+ * An instrument z_t is correlated with ONE structural shock and with none of the others; the covariance of the factor-VAR
+ * innovations with z_t then is that shock's impact column up to scale.  No ordering, no named series, no rotation search.  The
+ * sampling error of the instrument moment is judged by a moving block bootstrap of the used rows (D draws of block length L per
+ * replicate); parameter uncertainty is the replicate axis.
+ *
+ * Inputs: panel [B][T][N], Lam, R, Avar, Q, mu0, P0, sd (may be NULL) and cum (HOST int[N], may be NULL) as dfm_histdecomp_batch /
+ * dfm_irf_batch.  z: HOST double[T] in both entries, shared by every replicate as cum is; NaN = not available in that period.
+ * norm: series index, 0 <= norm < N; the identified shock is signed so that the impact response of series norm is non-negative.
+ * D >= 0 block draws per replicate, L the block length, seed, first_draw >= 0.
+ *
+ * Replicate b:
+ *   1. the smoother pass exactly as dfm_histdecomp_batch_dev calls it (caller's flags, no P_smooth)
+ *   2. for t >= p: etahat_t = f_t|T - sum_j A_j f_{t-j|T}
+ *   3. used rows U = {t : p <= t < T, z_t finite} in increasing order, n = |U| (the same for every replicate)
+ *   4. slots s = 0 .. D.  Slot 0 is the sample itself: src(j) = U[j], j = 0 .. n-1.  Slot 1 + d is block draw g = first_draw + d:
+ *      key = seed ^ (0x9E3779B97F4A7C15 * (g + 1)), the key of dfm_simsmooth_batch, stream word 16 b + 11 (streams 1-10 are
+ *      taken); nb = ceil(n / L) blocks; block k takes component k mod 4 of Philox::block(key, k / 4, stream) as a 32-bit word w;
+ *      its start is s_k = (uint64(w) * (n - L + 1)) >> 32 (integer arithmetic); src(j) = U[s_{j / L} + j mod L], the last block cut
+ *      at n.  A draw is a pure function of (seed, g, b), the inputs and L: it depends on neither D nor the launch geometry, and
+ *      draws [k, k + D) of one call equal those of a call with first_draw = k.
+ *   5. moments of a slot: zbar = (1/n) sum_j z_src(j); m = (1/n) sum_j etahat_src(j) (z_src(j) - zbar), an r-vector;
+ *      v = (1/n) sum_j (z_src(j) - zbar)^2
+ *   6. impact vector: gq = Q^-1 m through the Cholesky root of Q (a pivot <= 1e-12 trace raises status bit 16, which the host
+ *      entry reports as DFM_E_NUMERIC, as dfm_histdecomp_batch does); kappa = m' gq.  If kappa > 0 is false every output of the
+ *      slot is NaN.  Otherwise hvec = m / sqrt(kappa), so that hvec' Q^-1 hvec = 1: the one-standard-deviation shock.  hvec is
+ *      replaced by -hvec where lam_norm' hvec < 0.
+ *        impact [B][D+1][r] = hvec;  rel [B][D+1] = kappa / v (under the model's Q the squared correlation of the instrument with
+ *        the identified shock)
+ *   7. responses, h = 0 .. H-1:
+ *        irf [B][D+1][H][N] = sd_i lam_i' Psi_h hvec, with Psi^c_h = sum_{j<=h} Psi_j where cum[i].  Flag DFM_SV_UNIT_EFFECT divides
+ *          the slot by the impact response of series norm in output units (a true division: that response is exactly 1 at
+ *          h = 0); a zero impact response gives a NaN slot of irf.
+ *        fevd [B][D+1][H][N] = num / (den + idio), always from the unit-variance shock: num = sum_{j<=h} (lam_i' Psi_j hvec)^2,
+ *          den = sum_{j<=h} lam_i' Psi_j Q Psi_j' lam_i (dfm_irf_batch's sum_k num_k, since S S' = Q), idio as in dfm_irf_batch;
+ *          cumulated forms where cum[i]
+ *      Each of irf and fevd may be NULL.
+ *   8. shock [B][T] (may be NULL): slot 0's series u_t = hvec' Q^-1 etahat_t for t >= p, zero before
+ *   9. f_out [B][T][r] and loglik [B] are optional, as in dfm_histdecomp_batch
+ * Invariance: under Lam -> Lam M^-1, A_j -> M A_j M^-1, Q -> M Q M', mu0 -> M mu0, P0 -> M P0 M' (blockwise for the companion
+ * state) impact -> M impact, f_out -> f_out M', and rel, irf, fevd, shock do not change: the answer does not depend on the
+ * rotation the fit sits in.
+ * Status: sizes, norm and z are checked before the handle.  H < 1, T < p + 1, D < 0, first_draw < 0, norm out of range, n < r + 2,
+ * L < 1, L > n, B (D + 1) >= 2^31: DFM_E_DIMS; a NULL required pointer (impact and rel are required): DFM_E_NULL; r p > DFM_MAX_R:
+ * DFM_E_R_UNSUPPORTED; the rest as the pass.
+ * Allocates in the handle (kept for the next call): S, S^-1, the Theta tables, the row table [B][n][r+1], one r-vector and (with irf
+ * or fevd) one [H][r] table per slot, with fevd a [B][H][N] table, and the pass outputs the caller does not take.
+ * dfm_workspace_bytes does not count them.  Outputs must not overlap the inputs. */
+int dfm_proxyirf_batch_dev(dfm_handle* h, int B, int T, int N, int r, int p, int H, const double* panel, const double* Lam,
+                           const double* R, const double* Avar, const double* Q, const double* mu0, const double* P0,
+                           const double* sd, const int* cum, const double* z, int norm, int D, int L, uint64_t seed,
+                           int64_t first_draw, double* impact, double* rel, double* irf, double* fevd, double* shock,
+                           double* f_out, double* loglik, unsigned flags);
+int dfm_proxyirf_batch(dfm_handle* h, int B, int T, int N, int r, int p, int H, const double* panel, const double* Lam,
+                       const double* R, const double* Avar, const double* Q, const double* mu0, const double* P0, const double* sd,
+                       const int* cum, const double* z, int norm, int D, int L, uint64_t seed, int64_t first_draw, double* impact,
+                       double* rel, double* irf, double* fevd, double* shock, double* f_out, double* loglik, unsigned flags);
+
 /* --- AR idiosyncratic terms --------------------------------------------------------
  *   x_it = lam_i' f_t + e_it,   e_it = rho_i1 e_i,t-1 + .. + rho_iq e_i,t-q + eps_it,  eps_it ~ N(0, sig2_i)
  * with rho [B][N][q] / sig2 [B][N] in the role of the reference's uar_coef / uar_ser^2 (AR(n_uarlag) of the loading

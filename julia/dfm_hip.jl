@@ -448,6 +448,49 @@ function structural_irf_signs(h::Handle, params, H::Integer, restrictions; candi
     return (n_accept = Int(nacc[1]), mask = mask, cand = cand, impact = permutedims(S, (2, 1, 3)), irf = irf, fevd = fevd)
 end
 
+"Impulse responses to one shock identified by an external instrument (dfm_proxyirf_batch; include/dfm_hip.h): z, params, nlag,
+sd, singular_q as `historical_decomposition`, cumulate as `structural_irf`; instrument = one entry per row of z, NaN where it does
+not exist; norm = the series (1-based) whose impact response is made non-negative (exactly 1 with unit_effect); draws moving block
+draws of the instrument moment with blocks of `block` usable periods (default ceil(n^(1/3))), a pure function of (seed,
+first_draw + draw index).  Slot 1 is the sample, slots 2 .. draws + 1 the block draws.  Returns impact (r x (draws+1)), relevance
+(draws+1), irf and fevd (N x H x (draws+1)), shock (T), factor (T x r) and loglik."
+function structural_irf_proxy(h::Handle, z::Matrix{Float64}, params, H::Integer, instrument; norm::Integer, draws::Integer = 0,
+                              block = nothing, nlag::Integer = 1, cumulate = nothing, sd = nothing, unit_effect::Bool = false,
+                              seed::Integer = 20160415, first_draw::Integer = 0, singular_q::Bool = false)
+    T, N = size(z); r = size(params.Lam, 2)
+    length(instrument) == T || error("the instrument must have one entry per row of z")
+    Av = hasproperty(params, :Avar) ? params.Avar : params.A
+    panel = to_c_panel(z)
+    Lam = permutedims(params.Lam); R = copy(params.R); AC = permutedims(Av); QC = permutedims(params.Q)
+    mu0 = copy(params.mu0); P0C = permutedims(params.P0)
+    sdC = sd === nothing ? C_NULL : Vector{Float64}(sd)
+    cumC = C_NULL
+    if cumulate !== nothing
+        cumC = zeros(Cint, N); cumC[cumulate] .= 1
+    end
+    zC = Vector{Float64}(instrument)
+    n = count(isfinite, zC[nlag + 1:end])
+    L = block === nothing ? max(1, ceil(Int, n^(1 / 3) - 1e-12)) : Int(block)
+    D1 = Int(draws) + 1
+    impact = Array{Float64}(undef, r, D1); rel = Vector{Float64}(undef, D1)
+    irf = Array{Float64}(undef, N, H, D1); fevd = Array{Float64}(undef, N, H, D1)
+    u = Vector{Float64}(undef, T); f = Array{Float64}(undef, r, T); ll = Array{Float64}(undef, 1)
+    flags = (any(isnan, z) ? DFM_F_MAY_HAVE_MISSING : Cuint(0)) | (singular_q ? DFM_F_SINGULAR_Q : Cuint(0)) |
+            (unit_effect ? DFM_SV_UNIT_EFFECT : Cuint(0))
+    GC.@preserve panel Lam R AC QC mu0 P0C sdC cumC zC impact rel irf fevd u f ll begin
+        rc = ccall((:dfm_proxyirf_batch, LIB), Cint,
+                   (Ptr{Cvoid}, Cint, Cint, Cint, Cint, Cint, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                    Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cint}, Ptr{Float64}, Cint, Cint, Cint, UInt64,
+                    Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                    Cuint),
+                   h.ptr, 1, T, N, r, nlag, H, panel, Lam, R, AC, QC, mu0, P0C, sdC, cumC, zC, norm - 1, Int(draws), L,
+                   UInt64(seed), Int64(first_draw), impact, rel, irf, fevd, u, f, ll, flags)
+        check(h.ptr, rc)
+    end
+    # the C layouts [s][c] and [s][h][i] are column-major (c, s) and (i, h, s) as they stand
+    return (impact = impact, relevance = rel, irf = irf, fevd = fevd, shock = u, factor = permutedims(f), loglik = ll[1])
+end
+
 "Historical decomposition (dfm_histdecomp_batch; include/dfm_hip.h): z, params, nlag, sd, singular_q as `forecast`, named as
 `structural_irf`.  Returns contributions (T x N x (r+1): the last slot is the initial condition), shocks (T x r), factor
 (T x r) and loglik."
