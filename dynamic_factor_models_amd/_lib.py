@@ -55,6 +55,7 @@ _ARPASS_ARGS = [c_vp, c_int, c_int, c_int, c_int, c_int, c_int] + [c_vp] * 11 + 
 _AREM_ARGS = [c_vp, c_int, c_int, c_int, c_int, c_int, c_int] + [c_vp] * 8 + [c_int, ctypes.c_double] + [c_vp] * 4 + [c_uint]
 _MFPASS_ARGS = [c_vp, c_int, c_int, c_int, c_int, c_int, c_int] + [c_vp] * 11 + [c_uint]
 _MFEM_ARGS = [c_vp, c_int, c_int, c_int, c_int, c_int, c_int] + [c_vp] * 8 + [c_int, ctypes.c_double] + [c_vp] * 4 + [c_uint]
+_MFBEM_ARGS = [c_vp, c_int, c_int, c_int, c_int, c_int, c_int] + [c_vp] * 9 + [c_int, ctypes.c_double] + [c_vp] * 4 + [c_uint]
 _OBSEM_ARGS = [c_vp, c_int, c_int, c_int, c_int, c_int] + [c_vp] * 8 + [c_int, ctypes.c_double] + [c_vp] * 4 + [c_uint]
 _PCA_ARGS = [c_vp, c_int, c_int, c_int, c_int] + [c_vp] * 8
 c_ll = ctypes.c_longlong
@@ -127,6 +128,8 @@ SYMBOLS = {
     "dfm_ks_pass_mf_batch": (c_int, _MFPASS_ARGS),
     "dfm_em_mf_batch_dev": (c_int, _MFEM_ARGS),
     "dfm_em_mf_batch": (c_int, _MFEM_ARGS),
+    "dfm_em_mf_blocks_batch_dev": (c_int, _MFBEM_ARGS),
+    "dfm_em_mf_blocks_batch": (c_int, _MFBEM_ARGS),
     "dfm_em_obs_batch_dev": (c_int, _OBSEM_ARGS),
     "dfm_em_obs_batch": (c_int, _OBSEM_ARGS),
     "dfm_pca_init_batch_dev": (c_int, _PCA_ARGS),

@@ -1332,10 +1332,103 @@ def _mf_start(ctx, z, W, r, p):
     return dict(Lam=Lam, R=R, Avar=Avar, Q=0.5 * (Q + Q.T), mu0=np.zeros(r * m), P0=0.5 * (P0 + P0.T))
 
 
+def mf_blocks(membership, factors) -> np.ndarray:
+    """The `free` matrix of a block structure (Banbura and Modugno 2014).  membership [N][G] (boolean): which series belong to
+    which block -- a column of all True is a global block; factors [G]: the factor count of each block.  Returns free
+    [N][sum(factors)] (boolean, True = the loading is estimated), the columns in block order: block g's factors load on its own
+    series only, every other loading is fixed (at 0 in estimate_mixed_frequency's start)."""
+    mem = np.asarray(membership)
+    fac = np.asarray(factors)
+    if mem.ndim != 2 or fac.ndim != 1 or fac.shape[0] != mem.shape[1] or mem.shape[1] < 1:
+        raise ValueError("mf_blocks: membership must be [N][G] and factors [G]")
+    if fac.dtype.kind not in "iu" or np.any(fac < 1):
+        raise ValueError("mf_blocks: every block needs a whole number >= 1 of factors")
+    mem = mem != 0
+    if not mem.any(axis=1).all():
+        raise ValueError(f"mf_blocks: series {np.nonzero(~mem.any(axis=1))[0].tolist()} belong to no block")
+    if not mem.any(axis=0).all():
+        raise ValueError(f"mf_blocks: blocks {np.nonzero(~mem.any(axis=0))[0].tolist()} have no series")
+    return np.ascontiguousarray(np.repeat(mem, fac, axis=1))
+
+
+def _mf_free(blocks, N: int, r: int) -> np.ndarray:
+    """blocks= of estimate_mixed_frequency as a free [N][r] boolean matrix: the matrix itself, or (membership, factors)."""
+    if isinstance(blocks, (tuple, list)) and len(blocks) == 2 and np.ndim(blocks[0]) == 2:
+        free = mf_blocks(*blocks)
+    else:
+        free = np.asarray(blocks)
+        if free.ndim != 2:
+            raise ValueError("blocks: a free [N][r] matrix or (membership [N][G], factors [G])")
+        free = np.ascontiguousarray(free != 0)
+    if free.shape[0] != N:
+        raise ValueError(f"blocks: {free.shape[0]} rows for {N} series")
+    if free.shape[1] != r:
+        raise ValueError(f"blocks: {free.shape[1]} factor columns, but r = {r}")
+    return free
+
+
+def _mf_block_runs(free):
+    """Maximal runs of equal adjacent columns of free -- the blocks, as far as the start needs them: [(first, past the last, members)]."""
+    runs, c0 = [], 0
+    for c in range(1, free.shape[1] + 1):
+        if c == free.shape[1] or not np.array_equal(free[:, c], free[:, c0]):
+            runs.append((c0, c, free[:, c0]))
+            c0 = c
+    return runs
+
+
+def _mf_blocks_start(ctx, z, W, free, p):
+    """Block-wise start of the EM with fixed loadings: for each block in order (a run of equal columns of free), the first principal
+    components (pca_start) of the block's fully observed MONTHLY series after the factors of the earlier blocks are projected
+    out; every series regresses on its FREE aggregated factors only, its fixed loadings start at 0; VAR(p), P0 and the variance
+    floor as _mf_start."""
+    T, N = z.shape
+    r = free.shape[1]
+    L = W.shape[1]
+    m = max(p, L)
+    monthly = (W[:, 0] == 1.0) & np.all(W[:, 1:] == 0.0, axis=1)
+    full = ~np.isnan(z).any(axis=0)
+    F = np.zeros((T, 0))
+    for c0, c1, member in _mf_block_runs(free):
+        sel = monthly & full & member
+        if not sel.any():
+            raise ValueError(f"blocks: factor columns {c0}..{c1 - 1} have no fully observed monthly series to start from")
+        zb = z[:, sel]
+        if F.shape[1]:
+            zb = zb - F @ np.linalg.lstsq(F, zb, rcond=None)[0]
+        F = np.hstack([F, pca_start(ctx, zb, c1 - c0)])
+    Flag = np.stack([np.vstack([np.zeros((l, r)), F[:T - l]]) for l in range(L)])       # [L, T, r]: f_{t-l}
+    Lam = np.zeros((N, r)); R = np.ones(N)
+    for i in range(N):
+        fr = np.nonzero(free[i])[0]
+        g = np.tensordot(W[i], Flag, axes=1)[:, fr]
+        o = ~np.isnan(z[:, i]); o[:L - 1] = False
+        if o.sum() < len(fr) + 1:
+            continue
+        lam = np.linalg.lstsq(g[o], z[o, i], rcond=None)[0] if len(fr) else np.zeros(0)
+        Lam[i, fr] = lam
+        R[i] = max(np.mean((z[o, i] - g[o] @ lam) ** 2), 0.05)
+    Z = np.hstack([F[p - 1 - l:T - l] for l in range(p)])
+    Y, Xl = F[p:], Z[:-1]
+    Avar = np.linalg.solve(Xl.T @ Xl, Xl.T @ Y).T
+    e = Y - Xl @ Avar.T
+    Q = e.T @ e / (T - p)
+    Zm = np.hstack([F[m - 1 - l:T - l] for l in range(m)])
+    P0 = Zm.T @ Zm / Zm.shape[0] + 1e-3 * np.eye(r * m)
+    return dict(Lam=Lam, R=R, Avar=Avar, Q=0.5 * (Q + Q.T), mu0=np.zeros(r * m), P0=0.5 * (P0 + P0.T))
+
+
 def estimate_mixed_frequency(x, weights, r: int, p: int, *, max_em_iter: int = 50, tol_em: float = 1e-6, nrep: int = 0,
-                             seed: int = 20160415, ctx=None) -> dict:
+                             seed: int = 20160415, blocks=None, ctx=None) -> dict:
     """Maximum likelihood of the mixed-frequency DFM by EM (include/dfm_hip.h: dfm_em_mf_batch): monthly factors f_t with
     VAR(p) dynamics, series i loading on sum_l w_il f_{t-l}.
+
+    blocks (None: every loading is estimated, nothing below applies): a block structure of the loadings (dfm_em_mf_blocks_batch) --
+    either a free [N][r] matrix (nonzero = estimated, zero = fixed at its starting value, which is 0) or (membership [N][G],
+    factors [G]) as mf_blocks takes them; r must equal the number of factor columns.  The factor VAR stays unrestricted.  The start
+    is block-wise (`_mf_blocks_start`; a block without a fully observed monthly series is a ValueError), the bootstrap replicates
+    run under the same mask, and the returned dict gains `free`.  forecast_mixed takes such a fit as it is.  A SINGLE-frequency
+    block model is this call with all weights "m".
 
     x [T, N] is the MONTHLY panel in data units: a quarterly series sits in the third month of each quarter and is NaN elsewhere.
     `weights`: the [N][L] array, or a list of "m" / "q_flow" / "q_avg" (mf_weights).  Every series is standardised with its own
@@ -1352,22 +1445,29 @@ def estimate_mixed_frequency(x, weights, r: int, p: int, *, max_em_iter: int = 5
         mu = np.nansum(x, axis=0) / n
     z, sd = standardize_data(x)
     sd = np.asarray(sd).reshape(N)
+    free = None if blocks is None else _mf_free(blocks, N, int(r))
     ctx, own = _own(ctx)
     try:
-        start = _mf_start(ctx, z, W, int(r), int(p))
+        start = _mf_start(ctx, z, W, int(r), int(p)) if free is None else _mf_blocks_start(ctx, z, W, free, int(p))
         keys = ("Lam", "R", "Avar", "Q", "mu0", "P0")
 
         def run(panels, st, **kw):
             args = [panels, st["Lam"], st["R"], W, st["Avar"], st["Q"], st["mu0"], st["P0"]]
+            em = ctx.em_mf_batch_host
+            if free is not None:
+                args.insert(4, free)
+                em = ctx.em_mf_blocks_batch_host
             try:
-                return ctx.em_mf_batch_host(*args, max_iter=max_em_iter, tol=tol_em, may_have_missing=True, **kw)
+                return em(*args, max_iter=max_em_iter, tol=tol_em, may_have_missing=True, **kw)
             except DfmError as err:                 # the information form inverts Q: as estimate(), retry in covariance form
                 if err.code != -5:
                     raise
-                return ctx.em_mf_batch_host(*args, max_iter=max_em_iter, tol=tol_em, may_have_missing=True, singular_q=True, **kw)
+                return em(*args, max_iter=max_em_iter, tol=tol_em, may_have_missing=True, singular_q=True, **kw)
         est, path, iters, f, _ = run(z[None], {k: start[k][None] for k in keys})
         out = {k: est[k][0] for k in keys}
         out.update(W=W, mean=mu, sd=sd, loglik_path=path[0], iters=int(iters[0]), f_smooth=f[0], start=start)
+        if free is not None:
+            out["free"] = free
         if nrep > 0:
             LamK, M, Qk = _mf_expanded(out["Lam"], W, out["Avar"], out["Q"])
             k = M.shape[0]

@@ -176,11 +176,11 @@ struct dfm_handle {
 };
 
 enum KernelId { K_COLLAPSE = 0, K_RECURSION, K_MSTEP_STATS, K_MSTEP_SOLVE, K_PCA, K_SYNTH, K_PAD,
-                K_COLLAPSE_DMA, K_GRAM, K_COV, K_MEANSCAN, K_PFILL, K_COLLAPSE_MFMA, K_ALS, K_OLS, K_BOOT, K_QUANT, K_COLLAPSE_WIDE, K_EM_UPDATE, K_CHOW, K_MSTEP_MFMA, K_GRAM_XX, K_PASS_FUSED, K_FC_TAIL, K_FC_FILL, K_FC_PAD, K_SS_PREP, K_SS_EXPAND, K_SS_PATH, K_SS_DIFF, K_SS_FINISH, K_SS_FILL, K_NW_REVISE, K_NW_GATHER, K_NW_GAMMA, K_NW_COV, K_NW_IMPACT, K_MF_TABLE, K_MF_MOMENTS, K_MF_SOLVE, K_SV_PREP, K_SV_IRF_FILL, K_SV_SHOCK, K_SV_PATH, K_SV_HD_FILL, K_FT_FILTER, K_FT_FILL, K_FT_EVAL, K_GB_GRAM, K_GB_LOAD, K_GB_VAR, K_SV_SIGN_TABLE, K_SV_SIGN, K_SV_SIGN_KEEP, K_PX_ROWS, K_PX_MOMENT, K_PX_SLOT_TABLE, K_PX_DEN, K_PX_FILL, K_PX_SHOCK, K_COUNT };
+                K_COLLAPSE_DMA, K_GRAM, K_COV, K_MEANSCAN, K_PFILL, K_COLLAPSE_MFMA, K_ALS, K_OLS, K_BOOT, K_QUANT, K_COLLAPSE_WIDE, K_EM_UPDATE, K_CHOW, K_MSTEP_MFMA, K_GRAM_XX, K_PASS_FUSED, K_FC_TAIL, K_FC_FILL, K_FC_PAD, K_SS_PREP, K_SS_EXPAND, K_SS_PATH, K_SS_DIFF, K_SS_FINISH, K_SS_FILL, K_NW_REVISE, K_NW_GATHER, K_NW_GAMMA, K_NW_COV, K_NW_IMPACT, K_MF_TABLE, K_MF_MOMENTS, K_MF_SOLVE, K_SV_PREP, K_SV_IRF_FILL, K_SV_SHOCK, K_SV_PATH, K_SV_HD_FILL, K_FT_FILTER, K_FT_FILL, K_FT_EVAL, K_GB_GRAM, K_GB_LOAD, K_GB_VAR, K_SV_SIGN_TABLE, K_SV_SIGN, K_SV_SIGN_KEEP, K_PX_ROWS, K_PX_MOMENT, K_PX_SLOT_TABLE, K_PX_DEN, K_PX_FILL, K_PX_SHOCK, K_MF_SOLVE_BLOCKS, K_COUNT };
 static const char* const kKernelNames[K_COUNT] = {"collapse_kernel", "recursion_kernel", "mstep_lam_kernel",
                                                   "mstep_solve_kernel", "pca_kernel", "synth_kernel",
                                                   "pad_params_kernel", "collapse_dma_kernel", "gram_kernel",
-                                                  "cov_kernel", "meanscan_kernel", "pfill_kernel", "collapse_mfma_kernel", "als_kernel", "ols_kernel", "var_boot_kernel", "quantile_kernel", "collapse_wide_kernel", "em_update_kernel", "chow_kernel", "mstep_mfma_kernel", "gram_xx_kernel", "pass_fused_kernel", "forecast_tail_kernel", "forecast_fill_kernel", "forecast_pad_kernel", "simsmooth_prep_kernel", "simsmooth_expand_kernel", "simsmooth_path_kernel", "simsmooth_diff_kernel", "simsmooth_finish_kernel", "simsmooth_fill_kernel", "news_revise_kernel", "news_gather_kernel", "news_gamma_kernel", "news_cov_panel_kernel", "news_impact_kernel", "mf_table_kernel", "mf_moments_kernel", "mf_solve_kernel", "sv_prep_kernel", "sv_irf_fill_kernel", "sv_shock_kernel", "sv_path_kernel", "sv_hd_fill_kernel", "filter_kernel", "filter_fill_kernel", "filter_eval_kernel", "gibbs_gram_kernel", "gibbs_load_kernel", "gibbs_var_kernel", "sv_sign_table_kernel", "sv_sign_kernel", "sv_sign_keep_kernel", "px_rows_kernel", "px_moment_kernel", "px_slot_table_kernel", "px_den_kernel", "px_fill_kernel", "px_shock_kernel"};
+                                                  "cov_kernel", "meanscan_kernel", "pfill_kernel", "collapse_mfma_kernel", "als_kernel", "ols_kernel", "var_boot_kernel", "quantile_kernel", "collapse_wide_kernel", "em_update_kernel", "chow_kernel", "mstep_mfma_kernel", "gram_xx_kernel", "pass_fused_kernel", "forecast_tail_kernel", "forecast_fill_kernel", "forecast_pad_kernel", "simsmooth_prep_kernel", "simsmooth_expand_kernel", "simsmooth_path_kernel", "simsmooth_diff_kernel", "simsmooth_finish_kernel", "simsmooth_fill_kernel", "news_revise_kernel", "news_gather_kernel", "news_gamma_kernel", "news_cov_panel_kernel", "news_impact_kernel", "mf_table_kernel", "mf_moments_kernel", "mf_solve_kernel", "sv_prep_kernel", "sv_irf_fill_kernel", "sv_shock_kernel", "sv_path_kernel", "sv_hd_fill_kernel", "filter_kernel", "filter_fill_kernel", "filter_eval_kernel", "gibbs_gram_kernel", "gibbs_load_kernel", "gibbs_var_kernel", "sv_sign_table_kernel", "sv_sign_kernel", "sv_sign_keep_kernel", "px_rows_kernel", "px_moment_kernel", "px_slot_table_kernel", "px_den_kernel", "px_fill_kernel", "px_shock_kernel", "mf_solve_blocks_kernel"};
 
 namespace dfm { int handle_device(const dfm_handle* h) { return h->device; } }   // (probe.hip)
 
@@ -1476,9 +1476,11 @@ int mf_pass_run(dfm_handle* h, int B, int T, int N, int r, int nlag, int L, cons
     return enqueue_pass(h, s.p, B, T, N, r, panel, s.mb.pp(), R, f_smooth, P_smooth, loglik, nullptr);
 }
 
+// free_mask [N][r] (device bytes, or null = every loading estimated): the series solve with fixed loadings, mstep_mf_blocks.hip;
+// nothing else of the iteration looks at it
 int mf_run(dfm_handle* h, int B, int T, int N, int r, int nlag, int L, const double* panel, double* Lam, double* R, const double* W,
            double* Avar, double* Q, double* mu0, double* P0, int max_iter, double tol, double* loglik_path, int* iters,
-           double* f_smooth, double* P_smooth, unsigned flags) {
+           double* f_smooth, double* P_smooth, unsigned flags, const unsigned char* free_mask = nullptr) {
     if (int rc = mf_check(h, B, T, N, r, nlag, L)) return rc;
     if (!mstep_mf_supported(r, L)) return fail(h, DFM_E_R_UNSUPPORTED, "mixed-frequency estimation needs r <= 8%s");
     if (!panel || !Lam || !R || !W || !Avar || !Q || !mu0 || !P0 || !loglik_path || !iters)
@@ -1500,7 +1502,8 @@ int mf_run(dfm_handle* h, int B, int T, int N, int r, int nlag, int L, const dou
         if (int rc = enqueue_pass(h, p, B, T, N, Rk, panel, mb.pp(), R, mb.fsm, mb.Psm, mb.llbuf, &eo)) return rc;
         { ProfScope ps(h, K_MF_TABLE); HIP_TRY(h, launch_mf_table(ma, s.mws, h->stream)); }
         { ProfScope ps(h, K_MF_MOMENTS); HIP_TRY(h, launch_mf_moments(ma, s.mws, h->stream)); }
-        { ProfScope ps(h, K_MF_SOLVE); HIP_TRY(h, launch_mf_solve(ma, s.mws, h->stream)); }
+        if (free_mask) { ProfScope ps(h, K_MF_SOLVE_BLOCKS); HIP_TRY(h, launch_mf_solve_blocks(ma, free_mask, s.mws, h->stream)); }
+        else { ProfScope ps(h, K_MF_SOLVE); HIP_TRY(h, launch_mf_solve(ma, s.mws, h->stream)); }
         return 0;
     })) return rc;
     return unpad_results(h, p, B, N, T, r, r * nlag, s.k, mb, nullptr, Avar, Q, mu0, P0, f_smooth, P_smooth);
@@ -2021,10 +2024,19 @@ int dfm_em_mf_batch_dev(dfm_handle* h, int B, int T, int N, int r, int p, int L,
                   flags);
 }
 
-// host entry points: em = false is the pass (loglik_path = loglik [B], iters unused)
+int dfm_em_mf_blocks_batch_dev(dfm_handle* h, int B, int T, int N, int r, int p, int L, const double* panel, double* Lam, double* R,
+                               const double* W, const void* free_mask, double* Avar, double* Q, double* mu0, double* P0,
+                               int max_iter, double tol, double* loglik_path, int* iters, double* f_smooth, double* P_smooth,
+                               unsigned flags) {
+    return mf_run(h, B, T, N, r, p, L, panel, Lam, R, W, Avar, Q, mu0, P0, max_iter, tol, loglik_path, iters, f_smooth, P_smooth,
+                  flags, static_cast<const unsigned char*>(free_mask));
+}
+
+// host entry points: em = false is the pass (loglik_path = loglik [B], iters unused).  free_mask (EM only, may be NULL) is staged
+// LAST and takes no space when it is NULL: the block of a call without one is laid out as it always was
 static int mf_host(dfm_handle* h, int B, int T, int N, int r, int p, int L, const double* panel, double* Lam, double* R,
                    const double* W, double* Avar, double* Q, double* mu0, double* P0, int max_iter, double tol, double* loglik_path,
-                   int* iters, double* f_smooth, double* P_smooth, unsigned flags, bool em) {
+                   int* iters, double* f_smooth, double* P_smooth, unsigned flags, bool em, const unsigned char* free_mask = nullptr) {
     if (int rc = mf_check(h, B, T, N, r, p, L)) return rc;
     if (!panel || !Lam || !R || !W || !Avar || !Q || !mu0 || !P0 || !loglik_path || (em && !iters) || (!em && !f_smooth))
         return fail(h, DFM_E_NULL, "required pointer is NULL%s");
@@ -2035,13 +2047,15 @@ static int mf_host(dfm_handle* h, int B, int T, int N, int r, int p, int L, cons
     HostStage st(h);
     double *x_d, *lam_d, *R_d, *w_d, *A_d, *Q_d, *mu_d, *P0_d, *f_d, *P_d, *ll_d;
     int* it_d;
+    unsigned char* m_d;
     st.in(panel, (size_t)B * T * N, x_d); st.inout(Lam, (size_t)B * N * r, lam_d, em); st.inout(R, (size_t)B * N, R_d, em);
     st.in(W, (size_t)N * L, w_d); st.inout(Avar, (size_t)B * r * r * p, A_d, em); st.inout(Q, (size_t)B * r * r, Q_d, em);
     st.inout(mu0, (size_t)B * k, mu_d, em); st.inout(P0, (size_t)B * k * k, P0_d, em);
     st.out(f_smooth, (size_t)B * T * r, f_d); st.out(P_smooth, (size_t)B * T * np, P_d);
     st.out(loglik_path, (size_t)B * (em ? max_iter : 1), ll_d); st.out(iters, (size_t)B, it_d);
+    st.in(free_mask, free_mask ? (size_t)N * r : 0, m_d);
     if (int rc = st.begin()) return rc;
-    int rc = st.finish(em ? mf_run(h, B, T, N, r, p, L, x_d, lam_d, R_d, w_d, A_d, Q_d, mu_d, P0_d, max_iter, tol, ll_d, it_d, f_d, P_d, flags)
+    int rc = st.finish(em ? mf_run(h, B, T, N, r, p, L, x_d, lam_d, R_d, w_d, A_d, Q_d, mu_d, P0_d, max_iter, tol, ll_d, it_d, f_d, P_d, flags, m_d)
                           : mf_pass_run(h, B, T, N, r, p, L, x_d, lam_d, R_d, w_d, A_d, Q_d, mu_d, P0_d, f_d, P_d, ll_d, flags));
     if (rc == 0) rc = post_check(h, loglik_path, B, em ? (size_t)max_iter : 1);
     return rc;
@@ -2060,6 +2074,14 @@ int dfm_em_mf_batch(dfm_handle* h, int B, int T, int N, int r, int p, int L, con
                     int* iters, double* f_smooth, double* P_smooth, unsigned flags) {
     return mf_host(h, B, T, N, r, p, L, panel, Lam, R, W, Avar, Q, mu0, P0, max_iter, tol, loglik_path, iters, f_smooth, P_smooth,
                    flags, true);
+}
+
+int dfm_em_mf_blocks_batch(dfm_handle* h, int B, int T, int N, int r, int p, int L, const double* panel, double* Lam, double* R,
+                           const double* W, const void* free_mask, double* Avar, double* Q, double* mu0, double* P0,
+                           int max_iter, double tol, double* loglik_path, int* iters, double* f_smooth, double* P_smooth,
+                           unsigned flags) {
+    return mf_host(h, B, T, N, r, p, L, panel, Lam, R, W, Avar, Q, mu0, P0, max_iter, tol, loglik_path, iters, f_smooth, P_smooth,
+                   flags, true, static_cast<const unsigned char*>(free_mask));
 }
 
 // ---- observed factors ------------------------------------------------------------------------------------------------

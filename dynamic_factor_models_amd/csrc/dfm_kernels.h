@@ -294,6 +294,8 @@ hipError_t launch_mf_loadings(int B, int N, int r, int L, int Rk, const double* 
 hipError_t launch_mf_table(const MfMstepArgs& a, double* ws, hipStream_t s);
 hipError_t launch_mf_moments(const MfMstepArgs& a, double* ws, hipStream_t s);
 hipError_t launch_mf_solve(const MfMstepArgs& a, double* ws, hipStream_t s);
+// The solve with fixed loadings (mstep_mf_blocks.hip): free_mask [N][r] bytes, nonzero = estimated; a fixed entry of Lam is not written
+hipError_t launch_mf_solve_blocks(const MfMstepArgs& a, const unsigned char* free_mask, double* ws, hipStream_t s);
 // V[b][t][tt16] = [vec(E f f' + P) of the leading r states (packed lower), zeros to ntm16 | f_t (Rp columns), zeros] (mstep_miss.hip)
 hipError_t launch_mmw_vec(const double* fsm, const double* Psm, const int* active, int B, int T, int r, int Rp, int ntm16, int tt16,
                           double* V, hipStream_t s);

@@ -55,13 +55,16 @@ class _Numpy:
     def out(self, *shape, int32=False):
         return np.empty(shape, dtype=np.int32 if int32 else np.float64)
 
+    def inp_bytes(self, a):
+        return None if a is None else np.ascontiguousarray(np.asarray(a) != 0, dtype=np.uint8)
+
     def has_nan(self, panel):
         return bool(np.isnan(panel).any())
 
     def ptr(self, a, name=None, shape=None):
         return _ptr(a)
 
-    raw = ptr
+    raw = ptr_bytes = ptr
 
     def sync(self):
         pass
@@ -79,7 +82,7 @@ class _Torch:
     def inp(self, t):
         return t
 
-    upd = inp
+    upd = inp_bytes = inp
 
     def out(self, *shape, int32=False):
         return self.torch.empty(shape, dtype=self.torch.int32 if int32 else self.torch.float64, device=self.panel.device)
@@ -91,6 +94,16 @@ class _Torch:
     def ptr(self, t, name, shape=None):
         """As _ptr: None and a zero-size tensor (rho with q = 0) give null, unchecked."""
         return None if t is None or 0 in t.shape else self.ctx._dev(t, name, shape)
+
+    def ptr_bytes(self, t, name, shape=None):
+        """A mask: a contiguous uint8 tensor on the device (None: null)."""
+        if t is None:
+            return None
+        if not isinstance(t, self.torch.Tensor) or not t.is_cuda or t.dtype != self.torch.uint8 or not t.is_contiguous():
+            raise TypeError(f"{name}: expected a contiguous uint8 tensor on the HIP device")
+        if shape is not None and tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{name}: shape {tuple(t.shape)} != expected {tuple(shape)}")
+        return ctypes.c_void_p(t.data_ptr())
 
     def raw(self, t):
         return ctypes.c_void_p(t.data_ptr())
@@ -104,10 +117,11 @@ _NP = _Numpy()
 
 # ---------------------------------------------------------------------- the four model families
 # infix: dfm_ks_pass<infix>_batch[_dev] and dfm_em<infix>_batch[_dev];  names: the parameter arrays after the panel, in call order;
-# readonly: those EM does not update (the host EM neither copies nor returns them);  geom(B, T, N, r, *arrays) gives, from the
+# readonly: those EM does not update (the host EM neither copies nor returns them);  bytes: those that are byte masks, not float64
+# (always read only; None passes as null);  geom(B, T, N, r, *arrays) gives, from the
 # arrays' shapes, (the extra integer arguments, the rows of f_smooth / P_smooth, the expected shape of each array); k in it is
 # the state width.
-_Family = namedtuple("_Family", "infix names readonly geom")
+_Family = namedtuple("_Family", "infix names readonly geom bytes", defaults=((),))
 
 
 def _geom_plain(B, T, N, r, Lam, R, A, Q, mu0, P0):
@@ -133,10 +147,16 @@ def _geom_mf(B, T, N, r, Lam, R, W, Avar, Q, mu0, P0):
     return (p, L), T, ((B, N, r), (B, N), (N, L), (B, r, r * p), (B, r, r), (B, k), (B, k, k))
 
 
+def _geom_mf_blocks(B, T, N, r, Lam, R, W, free, Avar, Q, mu0, P0):
+    extra, rows, sh = _geom_mf(B, T, N, r, Lam, R, W, Avar, Q, mu0, P0)
+    return extra, rows, sh[:3] + ((N, r),) + sh[3:]
+
+
 _PLAIN = _Family("", ("Lam", "R", "A", "Q", "mu0", "P0"), (), _geom_plain)
 _VARP = _Family("_varp", ("Lam", "R", "Avar", "Q", "mu0", "P0"), (), _geom_varp)
 _AR = _Family("_ar", ("Lam", "sig2", "rho", "Avar", "Q", "mu0", "P0"), (), _geom_ar)
 _MF = _Family("_mf", ("Lam", "R", "W", "Avar", "Q", "mu0", "P0"), ("W",), _geom_mf)
+_MF_BLOCKS = _Family("_mf_blocks", ("Lam", "R", "W", "free", "Avar", "Q", "mu0", "P0"), ("W", "free"), _geom_mf_blocks, ("free",))
 # Differences between the public wrappers that nobody chose.  They are kept as they were; the next change can decide them:
 #  - want_P exists on ks_pass_batch_host only; the varp / ar / mf host passes always return P_smooth;
 #  - ks_pass_batch_multi_host has no singular_q and never sets DFM_F_SINGULAR_Q (em_obs_batch_host: neither);
@@ -147,7 +167,8 @@ def _model(fam, be, panel, params, update=False):
     """The panel and the parameter arrays of family `fam` as backend `be` takes them (update: EM will write the parameters), and
     what their shapes say: (panel, params, (B, T, N, r, *extra integers), output rows, expected shapes)."""
     panel = be.inp(panel)
-    params = [(be.upd if update and n not in fam.readonly else be.inp)(a) for n, a in zip(fam.names, params)]
+    params = [(be.inp_bytes if n in fam.bytes else be.upd if update and n not in fam.readonly else be.inp)(a)
+              for n, a in zip(fam.names, params)]
     B, T, N = panel.shape
     r = params[0].shape[2]
     extra, rows, shapes = fam.geom(B, T, N, r, *params)
@@ -155,7 +176,7 @@ def _model(fam, be, panel, params, update=False):
 
 
 def _ptrs(be, fam, arrays, shapes):
-    return [be.ptr(a, n, s) for a, n, s in zip(arrays, fam.names, shapes)]
+    return [(be.ptr_bytes if n in fam.bytes else be.ptr)(a, n, s) for a, n, s in zip(arrays, fam.names, shapes)]
 
 
 def _pass_out(be, B, rows, r, want_P=True):
@@ -703,6 +724,22 @@ class DfmContext:
         """Host-pointer entry (what Julia's ccall binds).  Returns (params dict, loglik_path, iters, f_smooth, P_smooth);
         inputs are not modified."""
         return self._em(_MF, _NP, panel, (Lam, R, W, Avar, Q, mu0, P0), max_iter, tol, True, True, may_have_missing,
+                        singular_q)
+
+    def em_mf_blocks_batch_dev(self, panel, Lam, R, W, free, Avar, Q, mu0, P0, max_iter: int = 10, tol: float = 0.0,
+                               want_smooth: bool = True, want_P: bool = True, may_have_missing: Optional[bool] = None,
+                               singular_q: bool = False):
+        """em_mf_batch with fixed loadings (include/dfm_hip.h, the blocks twin of dfm_em_mf_batch_dev).  free [N,r]: a uint8
+        device tensor, nonzero = estimated; a fixed entry of Lam keeps the value it has on entry; the mask is read only.  None:
+        em_mf_batch itself.  Returns (loglik_path [B,max_iter], iters [B], f_smooth [B,T,r] or None, P_smooth or None)."""
+        return self._em(_MF_BLOCKS, _Torch(self, panel), panel, (Lam, R, W, free, Avar, Q, mu0, P0), max_iter, tol, want_smooth,
+                        want_P, may_have_missing, singular_q)[1:]
+
+    def em_mf_blocks_batch_host(self, panel, Lam, R, W, free, Avar, Q, mu0, P0, max_iter: int = 10, tol: float = 0.0,
+                                may_have_missing: Optional[bool] = None, singular_q: bool = False):
+        """Host-pointer entry (what Julia's ccall binds); free [N,r]: any array, nonzero = estimated.  Returns (params dict,
+        loglik_path, iters, f_smooth, P_smooth); inputs are not modified."""
+        return self._em(_MF_BLOCKS, _NP, panel, (Lam, R, W, free, Avar, Q, mu0, P0), max_iter, tol, True, True, may_have_missing,
                         singular_q)
 
     # ------------------------------------------------------------------ PCA initialisation / synthetic panels

@@ -624,6 +624,25 @@ int dfm_em_mf_batch(dfm_handle* h, int B, int T, int N, int r, int p, int L, con
                     const double* W, double* Avar, double* Q, double* mu0, double* P0, int max_iter, double tol,
                     double* loglik_path, int* iters, double* f_smooth, double* P_smooth, unsigned flags);
 
+/* The same EM with BLOCK-STRUCTURED loadings: some loadings are FIXED, the rest estimated (Banbura and Modugno 2014: a global
+ * factor loads on every series, a "real" or "survey" factor on its own block only).  free_mask [N][r] (unsigned char, one matrix for
+ * the whole batch; void* here so that every binding passes its byte array as it is): nonzero = estimated, zero = fixed.  A fixed loading keeps, bit for bit, the value it has in Lam on entry -- 0 for
+ * a block structure, 1 for a normalisation -- in every replicate and iteration.  Steps (1) and (2) are those of dfm_em_mf_batch
+ * (the factor VAR stays unrestricted over all r factors); in step (3), with F the free and X the fixed coordinates of series i,
+ * k_i = |F|, and G_i, b_i as above,
+ *   lam_F = G_FF^-1 (b_F - G_FX lam_X)  (Cholesky of G_FF),   R_i = (sum_t x_it^2 - 2 lam_i' b_i + lam_i' G_i lam_i) / n_i  (whole lam_i).
+ * A series with n_i < k_i + 1 observed cells, or whose G_FF is not positive definite, keeps lam_i and R_i; a series with k_i = 0
+ * and n_i >= 1 updates R_i only.  free_mask == NULL is dfm_em_mf_batch itself.  The _dev entry reads the mask on the device and
+ * never copies it back.  Limits, flags and status codes are those of dfm_em_mf_batch. */
+int dfm_em_mf_blocks_batch_dev(dfm_handle* h, int B, int T, int N, int r, int p, int L, const double* panel, double* Lam, double* R,
+                               const double* W, const void* free_mask, double* Avar, double* Q, double* mu0, double* P0,
+                               int max_iter, double tol, double* loglik_path, int* iters, double* f_smooth, double* P_smooth,
+                               unsigned flags);
+int dfm_em_mf_blocks_batch(dfm_handle* h, int B, int T, int N, int r, int p, int L, const double* panel, double* Lam, double* R,
+                           const double* W, const void* free_mask, double* Avar, double* Q, double* mu0, double* P0,
+                           int max_iter, double tol, double* loglik_path, int* iters, double* f_smooth, double* P_smooth,
+                           unsigned flags);
+
 /* --- OBSERVED factors ------------------------------------------------------------------------------
  *   x_it = lam_o,i' g_t + lam_u,i' f_t + e_it,   e_it ~ N(0, R_i),     f_t = A f_{t-1} + eta_t,  eta_t ~ N(0, Q)
  * The reference's DFMModel has `nfac_o` observed factors in front of the `nfac_u` estimated ones (`factor` is T x nfac_t,

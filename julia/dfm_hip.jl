@@ -703,6 +703,49 @@ function em_mf(h::Handle, z::Matrix{Float64}, W::Matrix{Float64}, Lam::Matrix{Fl
             loglik = path[1:kk], iters = kk, factor = permutedims(f))
 end
 
+"em_mf with FIXED loadings (dfm_em_mf_blocks_batch; include/dfm_hip.h): `free` is N x r, true / nonzero = estimated; a fixed loading
+keeps the value it has in Lam (0 for a block structure, 1 for a normalisation).  Arguments and result otherwise as em_mf."
+function em_mf_blocks(h::Handle, z::Matrix{Float64}, W::Matrix{Float64}, free::AbstractMatrix, Lam::Matrix{Float64}, R::Vector{Float64},
+                      Avar::Matrix{Float64}, Q::Matrix{Float64}, mu0::Vector{Float64}, P0::Matrix{Float64}; max_iter::Integer = 50,
+                      tol::Real = 1e-6, singular_q::Bool = false)
+    T, N = size(z); r = size(Lam, 2); L = size(W, 2); p = div(size(Avar, 2), r)
+    size(free) == (N, r) || error("free: $(size(free)) for $N series and $r factors")
+    panel = to_c_panel(z)
+    LamC = permutedims(Lam); Rc = copy(R); WC = permutedims(W); AC = permutedims(Avar); QC = permutedims(Q)
+    freeC = Matrix{UInt8}(permutedims(free .!= 0))
+    mu = copy(mu0); P0C = permutedims(P0)
+    path = Array{Float64}(undef, max_iter); iters = Array{Cint}(undef, 1)
+    f = Array{Float64}(undef, r, T); np = div(r * (r + 1), 2); P = Array{Float64}(undef, np, T)
+    flags = (any(isnan, z) ? DFM_F_MAY_HAVE_MISSING : Cuint(0)) | (singular_q ? DFM_F_SINGULAR_Q : Cuint(0))
+    GC.@preserve panel LamC Rc WC freeC AC QC mu P0C path iters f P begin
+        rc = ccall((:dfm_em_mf_blocks_batch, LIB), Cint,
+                   (Ptr{Cvoid}, Cint, Cint, Cint, Cint, Cint, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                    Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cint, Cdouble, Ptr{Float64}, Ptr{Cint},
+                    Ptr{Float64}, Ptr{Float64}, Cuint),
+                   h.ptr, 1, T, N, r, p, L, panel, LamC, Rc, WC, freeC, AC, QC, mu, P0C, max_iter, tol, path, iters, f, P, flags)
+        check(h.ptr, rc)
+    end
+    kk = Int(iters[1])
+    return (Lam = permutedims(LamC), R = Rc, Avar = permutedims(AC), Q = permutedims(QC), mu0 = mu, P0 = permutedims(P0C),
+            loglik = path[1:kk], iters = kk, factor = permutedims(f))
+end
+
+"The device-pointer twin (dfm_em_mf_blocks_batch_dev) for arrays that already live on the GPU, row-major as the C interface has them:
+B replicates, parameters updated in place, `free` N x r bytes read only (C_NULL: every loading estimated); f / P may be C_NULL.
+Enqueues on the handle's stream and returns; the caller synchronises."
+function em_mf_blocks_dev!(h::Handle, B::Integer, T::Integer, N::Integer, r::Integer, p::Integer, L::Integer, panel::Ptr{Float64},
+                           Lam::Ptr{Float64}, R::Ptr{Float64}, W::Ptr{Float64}, free::Ptr{Cvoid}, Avar::Ptr{Float64}, Q::Ptr{Float64},
+                           mu0::Ptr{Float64}, P0::Ptr{Float64}, max_iter::Integer, tol::Real, path::Ptr{Float64}, iters::Ptr{Cint},
+                           f::Ptr{Float64}, P::Ptr{Float64}, flags::Cuint)
+    rc = ccall((:dfm_em_mf_blocks_batch_dev, LIB), Cint,
+               (Ptr{Cvoid}, Cint, Cint, Cint, Cint, Cint, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cint, Cdouble, Ptr{Float64}, Ptr{Cint},
+                Ptr{Float64}, Ptr{Float64}, Cuint),
+               h.ptr, B, T, N, r, p, L, panel, Lam, R, W, free, Avar, Q, mu0, P0, max_iter, tol, path, iters, f, P, flags)
+    check(h.ptr, rc)
+    return nothing
+end
+
 "Smoother pass of the mixed-frequency model (dfm_ks_pass_mf_batch): arguments as em_mf; returns the smoothed monthly factors, their
 packed covariances and the log-likelihood."
 function ks_pass_mf(h::Handle, z::Matrix{Float64}, W::Matrix{Float64}, Lam::Matrix{Float64}, R::Vector{Float64}, Avar::Matrix{Float64},
