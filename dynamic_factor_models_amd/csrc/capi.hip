@@ -66,6 +66,7 @@ struct RouteOpts {
                                            // per-series loads are dependent round trips, ~5 us each beside the collapse)
     int pass_fused = 1;                    // the balanced pass at Rp = 8 as ONE launch (pass_fused.hip); DFM_PASS_FUSED=0: two launches
     int pass_nsw = 0;                      // DFM_PASS_NSW: stream waves per workgroup of that launch (0 = automatic)
+    bool pf_wpark = true;                  // DFM_PF_WPARK=0 (route): the stream waves of that launch load their own weights (no hand-over by the fill wave)
     bool wide_old = false;                 // DFM_WIDE_OLD=1: Rp = 32 balanced collapse by collapse_wide_kernel + gram_wide_kernel
     bool collapse_miss_old = false;        // DFM_COLLAPSE_MISS_OLD=1: register-streamed collapse_kernel for panels with missing cells
     bool narrow_tab_off = false;           // DFM_NARROW_TAB=0 (diagnostics build): r <= 4 on the 8-wide state through collapse_kernel<4> + chunk_bridge_kernel
@@ -108,6 +109,7 @@ RouteOpts route_opts_from_env() {
     o.mstep_miss_mode = num(route_env("DFM_MSTEP_MISS"), 1);
     o.pass_fused = num(route_env("DFM_PASS_FUSED"), 1);
     o.pass_nsw = num(diag_env("DFM_PASS_NSW"), 0);
+    o.pf_wpark = !off(route_env("DFM_PF_WPARK"));
     o.pass_ncov = num(diag_env("DFM_PASS_NCOV"), 0);
     o.gram_xx_valu = on(diag_env("DFM_GRAM_XX_VALU"));
     o.collapse_miss_old = on(diag_env("DFM_COLLAPSE_MISS_OLD"));
@@ -779,7 +781,7 @@ int enqueue_pass_fast(dfm_handle* h, const Plan& p, int B, int T, int N, int out
             ca.scol = at<double>(h, p.scol);                      // workspace dump below (diagnostics)
             if (const char* f = diag_env("DFM_PF_PROF_FILE")) h->prof_file = f;
         }
-        { ProfScope ps(h, K_PASS_FUSED); HIP_TRY(h, launch_pass_fused(ca, fa, h->opt.pass_nsw, h->opt.pass_ncov, h->num_cu, h->stream)); }
+        { ProfScope ps(h, K_PASS_FUSED); HIP_TRY(h, launch_pass_fused(ca, fa, h->opt.pass_nsw, h->opt.pass_ncov, h->opt.pf_wpark, h->num_cu, h->stream)); }
         if ((h->opt.scan_abl & 256) && !h->prof_file.empty()) {       // diagnostics: dump the stamps of this pass (synchronises)
             std::vector<double> st((size_t)B * T);
             HIP_TRY(h, hipStreamSynchronize(h->stream));

@@ -18,7 +18,7 @@ extern thread_local const char* t_launched_kernel;
 // Environment switches of the library, in two classes.
 //   route_env: selects among PRODUCTION kernels that compute the same result to rounding (the one-launch pass or the two-launch
 //              pass, one wave or a lane group per replicate, ...): what the test-suite uses to cover every fallback, and tuning
-//              knobs (DFM_NUM_CU).  Ten names since round 6: DFM_FORCE_GENERAL, DFM_PASS_FUSED, DFM_NO_CHUNK, DFM_NO_PAIR,
+//              knobs (DFM_NUM_CU).  Eleven names: DFM_FORCE_GENERAL, DFM_PASS_FUSED, DFM_PF_WPARK, DFM_NO_CHUNK, DFM_NO_PAIR,
 //              DFM_MSTEP_MISS, DFM_TILE_NC, DFM_NUM_CU -- which kernel runs, never what it computes -- and DFM_CHUNK_W, DFM_TILE_W,
 //              DFM_CHUNK_TOL, which set the warm-up and the boundary tolerance of the time-chunked recursions (a replicate that misses the
 //              tolerance is redone sequentially: accuracy knobs).
@@ -377,8 +377,10 @@ hipError_t launch_pfill(int Rpad, const FastArgs& a, hipStream_t s);   // the P_
 // one-wave-per-replicate covariance recursion as a drop-in for launch_cov (Rp = 8, Cfull / ldfull from gram_kernel).
 bool pass_fused_supported(int Rpad, int T, int N);
 int pass_fused_pick_nsw(int T, int N, int want);            // stream waves per workgroup that fit the 160 KB of LDS (diagnostic)
+int pass_fused_pick_nbuf(int T, int N);                     // b_t buffers of that layout (diagnostic)
+bool pass_fused_pick_wpark(int T, int N);                   // the weight hand-over's route rule at that shape (diagnostic)
 // nsw / ncov: stream / covariance waves per workgroup (0 = as many as fit)
-hipError_t launch_pass_fused(const CollapseArgs& a, const FastArgs& fa, int nsw, int ncov, int num_cu, hipStream_t s);
+hipError_t launch_pass_fused(const CollapseArgs& a, const FastArgs& fa, int nsw, int ncov, bool wpark, int num_cu, hipStream_t s);
 hipError_t launch_cov_wave(const FastArgs& a, hipStream_t s);
 // the element-per-thread covariance recursion for Rp = 16 / 32 (a workgroup of Rp x Rp threads per replicate; Cfull / ldfull
 // from the Gram kernel): what launch_cov runs for those widths unless DFM_COV_ROWS=1

@@ -7,7 +7,10 @@
 //                                v_mfma_f64_4x4x4): wave w streams segment w of the replicate's T periods.  b_t goes to
 //                                one of two LDS arrays [T][8] instead of HBM, sum_t s_t to an LDS slot.  While the scan
 //                                waves work on replicate j the stream waves are already filling the other array with
-//                                replicate j + 1, so HBM never waits for the (latency-bound) scan.
+//                                replicate j + 1, so HBM never waits for the (latency-bound) scan.  Their weights (lam / R in
+//                                the MFMA operand layout, 1 / R by column) come from the fill wave through a park in the
+//                                b_t buffer they are about to fill, read with ds_read at the replicate boundary: no global
+//                                load, no vmcnt(0), the ring stays in flight (pf_wpark_rule; else they load their own).
 //   the next ncov waves  COV     Gram matrix C = Lam' R^-1 Lam, the data-independent covariance recursion (dfm_cov8.h: one
 //                                wave per replicate, element per lane), the transient rows of P_smooth, then the fixed-point
 //                                rows of P_smooth (pure stores).  Nothing here depends on the panel, so these waves run
@@ -15,7 +18,10 @@
 //                                CHIP: Z_e, J_e of the transient in the wave's registers, G_e, the steady matrices, P_T and
 //                                the scalars in an LDS park of the wave, until the scan of replicate j - 1 has released the
 //                                single LDS table set; the wave then writes the set itself and raises tab_ready.
-//   one wave             FILL    the fixed-point rows of P_smooth of all but the last replicates (pure stores).
+//   one wave             FILL    the fixed-point rows of P_smooth of all but the last replicates (pure stores); the stream
+//                                waves' weights of replicate j + 1, loaded while the scan of j - 1 still holds the buffer and
+//                                parked in its highest rows once that scan is done (w_ready; the stream waves count w_taken
+//                                before they store b_t over the park).
 //   the last 4 waves     SCAN    the time-parallel mean recursion (dfm_scan.h, the algorithm of meanscan_kernel) with
 //                                b_t / w_t in LDS: f_smooth, log-likelihood.  Its internal barriers are 4-wave barriers on
 //                                an LDS counter.
@@ -23,7 +29,7 @@
 // Against the two-launch pass (fused collapse launch + meanscan_kernel): no b_t round trip through HBM (33 MB written,
 // read back), no w_t scratch (33 MB + 33 MB), no second launch whose ~55 us of dependent scans ran behind the stream
 // instead of beside it, and the covariance recursion no longer holds 128 wide waves resident for 125 us.
-// Synchronisation: monotone counters in LDS (bt_ready[buffer], scan_done, cov_done[wave]); every wait is BOUNDED (a wait
+// Synchronisation: monotone counters in LDS (bt_ready[buffer], scan_done, cov_done[wave], w_ready, w_taken); every wait is BOUNDED (a wait
 // that does not end sets bit 2 of the status word and the whole workgroup drains).  No inter-workgroup communication.
 // The reference has no counterpart (dfm_functions.ipynb:21-23 declares `Parametric` only).
 #include <stdlib.h>
@@ -46,6 +52,7 @@ namespace dfm {
 namespace {
 
 using lds_char_ptr_f = __attribute__((address_space(3))) char*;
+using lds_double_ptr_f = __attribute__((address_space(3))) double*;
 
 // nt: the non-temporal hint on the panel stream.  The panel is read ONCE per pass; with the hint its lines do not displace the
 // rest of the pass's working set from the 256-MB Infinity Cache -- the outputs (P_smooth, f_smooth: 180 MB per 1024 replicates),
@@ -76,6 +83,13 @@ __device__ __forceinline__ void dma16f(const void* gsrc, unsigned lds_dst, bool 
             : "v"(gsrc), "s"(lds_dst)
             : "memory");
     }
+}
+// The lane id from the hardware (all lanes active), opaque to the compiler: what is derived from it is derived where it is asked
+// for, not kept -- or spilled -- from the top of the kernel (see the stream role of pass_fused_kernel).
+__device__ __forceinline__ int pf_fresh_lane() {
+    int l;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+    return l;
 }
 template <int K>
 __device__ __forceinline__ void wait_vmf() {
@@ -127,6 +141,8 @@ constexpr int kFAbort = 6;
 constexpr int kFTabReady = 7;     // replicates whose tables their covariance wave has put into the LDS table set
 constexpr int kFScanArrive = 8;   // scan_reg: scan waves that have finished their part of a replicate (4 per replicate)
 constexpr int kFStreamWaits = 9;  // 1 while stream wave 0 waits for a b_t buffer, i.e. for the scan: the scan is then the critical path
+constexpr int kFWReady = 10;      // weight hand-over: local replicates whose stream weights the fill wave has parked in their b_t buffer
+constexpr int kFWTaken = 11;      // weight hand-over: reads of a park by the stream waves that own periods (one per wave and replicate)
 constexpr int kFCount = 64;
 
 // misc doubles (LDS)
@@ -144,6 +160,10 @@ __device__ __forceinline__ unsigned ld_flag(const unsigned* f) {
     return __builtin_amdgcn_readfirstlane(__hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
 }
 // Bounded wait until *f >= target (counters are monotone).  false: the workgroup is draining (time-out somewhere).
+// kLdsOnly: what the waiter reads or writes behind the flag is in LDS and nothing else -- a wave's LDS operations execute in
+// program order, so an lgkmcnt wait stands in for the acquire fence.  The stream waves use it where their ring's DMAs are in
+// flight: no vmcnt wait may come between two counted ones.
+template <bool kLdsOnly = false>
 __device__ __forceinline__ bool pf_wait_ge(const unsigned* f, unsigned target, unsigned* abortf) {
     unsigned spins = 0;
     for (;;) {
@@ -157,7 +177,8 @@ __device__ __forceinline__ bool pf_wait_ge(const unsigned* f, unsigned target, u
             }
         }
     }
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    if constexpr (kLdsOnly) wait_lgkmf();
+    else __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     return true;
 }
 // everything this wave wrote (LDS and global) is visible to the workgroup before the counter moves
@@ -234,6 +255,8 @@ struct PfLds {
     unsigned total;
     int nsw, ncov, nbuf;
     int nt;           // non-temporal hint on the panel stream (dma16f)
+    int wpark;        // 1: the stream waves' weights come from the fill wave through a park in the b_t buffer (pf_wpark_rule)
+    unsigned wpark_off;   // doubles from the start of a b_t buffer to its park: the buffer's highest rows
 };
 
 #if defined(DFM_PF_FALLBACK_LDS) && !defined(DFM_DIAG)
@@ -691,6 +714,60 @@ __device__ __forceinline__ void scan_seq(const FastArgs& a, int b, int tid, doub
 }
 
 // ------------------------------------------------------------------------------------------------------------------
+// The weights of one replicate in the collapse's operand layout -- ONE text for everyone who forms them (the stream waves on the
+// route without the hand-over, the fill wave that parks them for the stream waves, gram_mfma8 through pf_weight): the values are
+// bit-identical whoever computes them.  Lane (K, g, h, q) gets Bw[s] = lam_c,4h+q / R_c for the series c = 8 s + 4 g + K (0 for a
+// clamped last step) and rown[jq][e] = 1 / R of its own column pair 2 lane + 128 jq + e (0 past N).  They depend on the lane
+// only, not on the wave.  pf_weights_issue puts every load in flight (no per-load address registers: constant offsets off one
+// base); pf_weights_finish waits for them -- vmcnt(0): whatever else the wave has in flight lands too -- and forms the values.
+// ------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ double pf_weight(double lam, double rv) { return lam * fast_rcp(rv); }
+
+template <int STEPS, int NQ>
+__device__ __forceinline__ void pf_weights_issue(const double* __restrict__ Lg, const double* __restrict__ Rg, int N, int lane,
+                                                 double (&Bw)[STEPS], double (&rv)[STEPS], double (&rown)[NQ][2]) {
+    constexpr int R = 8, CS = 8;
+    const int K = lane >> 4, blk = (lane >> 2) & 3, q = lane & 3;
+    const int g = blk >> 1, h = blk & 1;
+    const bool tail_clamp = (STEPS - 1) * CS + 4 * g + K >= N;
+    const int clast = tail_clamp ? N - 1 : (STEPS - 1) * CS + 4 * g + K;
+    const double* __restrict__ Lq = Lg + (4 * g + K) * R + 4 * h + q;
+    const double* __restrict__ Rq = Rg + (4 * g + K);
+#pragma unroll
+    for (int s = 0; s + 1 < STEPS; ++s) {
+        Bw[s] = Lq[s * CS * R];
+        rv[s] = Rq[s * CS];
+    }
+    Bw[STEPS - 1] = Lg[(size_t)clast * R + 4 * h + q];
+    rv[STEPS - 1] = Rg[clast];
+#pragma unroll
+    for (int jq = 0; jq < NQ; ++jq)
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const int c = 2 * lane + 128 * jq + e;
+            rown[jq][e] = Rg[c < N ? c : N - 1];
+        }
+    __builtin_amdgcn_sched_barrier(0);                    // all loads in flight before the first use
+}
+template <int STEPS, int NQ>
+__device__ __forceinline__ void pf_weights_finish(int N, int lane, double (&Bw)[STEPS], double (&rv)[STEPS], double (&rown)[NQ][2]) {
+    constexpr int CS = 8;
+    const int K = lane >> 4, g = (lane >> 3) & 1;
+    const bool tail_clamp = (STEPS - 1) * CS + 4 * g + K >= N;
+    wait_vmf<0>();
+#pragma unroll
+    for (int s = 0; s + 1 < STEPS; ++s) Bw[s] = pf_weight(Bw[s], rv[s]);
+    Bw[STEPS - 1] = tail_clamp ? 0.0 : pf_weight(Bw[STEPS - 1], rv[STEPS - 1]);
+#pragma unroll
+    for (int jq = 0; jq < NQ; ++jq)
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const int c = 2 * lane + 128 * jq + e;
+            rown[jq][e] = (c < N) ? fast_rcp(rown[jq][e]) : 0.0;
+        }
+}
+
+// ------------------------------------------------------------------------------------------------------------------
 // Gram matrix C = Lam' R^-1 Lam of one replicate by ONE wave on the fp64 matrix pipe, in the collapse's own operand layout:
 // lane (K, g, h, q) holds W[c][4 h + q] = lam_c,4h+q / R_c for the series c = 8 s + 4 g + K (the B operands of the stream
 // waves).  Rows i = 4 p + (0..3) of Lam' play the part of the 4 periods of a row block: the A operand of block p is
@@ -741,7 +818,7 @@ __device__ __forceinline__ double gram_mfma8(const double* __restrict__ Lg, cons
     double D0 = 0.0, D1 = 0.0;
 #pragma unroll
     for (int s = 0; s < STEPS; ++s) {
-        const double w = (s == STEPS - 1 && tail_clamp) ? 0.0 : raw[s] * fast_rcp(rv[s]);   // the stream waves' weights exactly
+        const double w = (s == STEPS - 1 && tail_clamp) ? 0.0 : pf_weight(raw[s], rv[s]);   // the stream waves' weights exactly
         const double other = xor_lane<4>(raw[s]);
         const double a0 = h == 0 ? raw[s] : other;           // lam_c,q
         const double a1 = h == 0 ? other : raw[s];           // lam_c,4+q
@@ -812,9 +889,6 @@ __global__ __launch_bounds__(kPfMaxThreads) void pass_fused_kernel(CollapseArgs 
         // never drains at a replicate boundary.  Every block issues exactly 4 x NDR DMA instructions (rows past the
         // segment repeat its last row), which keeps the counted vmcnt wait valid across boundaries.
         const unsigned rowB = (unsigned)N * 8u;
-        // lane roles of v_mfma_f64_4x4x4 (collapse_mfma.hip)
-        const int K = lane >> 4, blk = (lane >> 2) & 3, q = lane & 3;
-        const int g = blk >> 1, h = blk & 1;
         // Segments are whole row blocks: T is cut into units of lcm(4, m) rows (m rows: the period after which a row starts on
         // a 128-byte boundary again) and the waves get balanced unit counts, the first ones one more.  Only the last block of
         // the last segment can be partial -- <= 3 repeated rows per replicate, not per wave.
@@ -837,170 +911,191 @@ __global__ __launch_bounds__(kPfMaxThreads) void pass_fused_kernel(CollapseArgs 
         const char* ring = smem + ly.ring + (size_t)wave * ringB;
         const unsigned ring_lds =
             __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lds_char_ptr_f)(smem)) + ly.ring + (unsigned)wave * ringB;
-        const unsigned lane16 = 16u * lane;
-        bool pact[NDR];                                          // lane moves 16 bytes of piece p of a row
-#pragma unroll
-        for (int p = 0; p < NDR; ++p) pact[p] = lane16 + 1024u * p < rowB;
-        const unsigned lane_off = (unsigned)q * SB + (unsigned)(4 * g + K) * 8u;
-        const bool tail_clamp = (STEPS - 1) * CS + 4 * g + K >= N;
-        const unsigned last_off = tail_clamp ? (unsigned)q * SB + (unsigned)(N - 1) * 8u : lane_off + (unsigned)(STEPS - 1) * (CS * 8u);
         const int nrep = (B - (int)blockIdx.x + G - 1) / G;      // replicates of this workgroup
         const int gtot = nrep * nblk;                            // row blocks of this wave
 
         double Bw[STEPS];                                        // B operands: lam_cf / R_c for c = s CS + 4 g + K, f = 4 h + q
         double rown[NQ][2];                                      // 1 / R of the lane's own 16-byte column pairs (s_t pass)
-        // block k of local replicate jj into ring block `bslot`: 4 rows x NDR DMA instructions, always
-        auto issue_block = [&](int jj, int k, int bslot) {
-            const char* seg = reinterpret_cast<const char*>(a.panel + ((size_t)((int)blockIdx.x + jj * G) * T + ta) * N);
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr) {
-                int ri = 4 * k + rr;
-                ri = ri < nrows ? ri : nrows - 1;
-                const char* src = seg + (size_t)ri * rowB + lane16;
-                const unsigned dst = __builtin_amdgcn_readfirstlane(ring_lds + (unsigned)(bslot * 4 + rr) * SB);
-#pragma unroll
-                for (int p = 0; p < NDR; ++p) {
-                    if (pact[p]) dma16f(src + 1024 * p, dst + 1024u * p, dma_nt);
-                }
-            }
-        };
-        // weights of replicate bb: loads off one base pointer with constant offsets (no per-load address registers),
-        // reciprocal by v_rcp_f64 + two Newton steps.  Ends with vmcnt(0): the ring blocks in flight have landed too.
-        auto load_weights = [&](int bb) {
-            const double* __restrict__ Lq = a.Lam + (size_t)bb * N * R + (4 * g + K) * R + 4 * h + q;
-            const double* __restrict__ Rq = a.Rv + (size_t)bb * N + (4 * g + K);
-            const int clast = tail_clamp ? N - 1 : (STEPS - 1) * CS + 4 * g + K;
-            double rv[STEPS];
-#pragma unroll
-            for (int s = 0; s + 1 < STEPS; ++s) {
-                Bw[s] = Lq[s * CS * R];
-                rv[s] = Rq[s * CS];
-            }
-            Bw[STEPS - 1] = a.Lam[(size_t)bb * N * R + (size_t)clast * R + 4 * h + q];
-            rv[STEPS - 1] = a.Rv[(size_t)bb * N + clast];
-            const double* __restrict__ Rg = a.Rv + (size_t)bb * N;
-#pragma unroll
-            for (int jq = 0; jq < NQ; ++jq)
-#pragma unroll
-                for (int e = 0; e < 2; ++e) {
-                    const int c = 2 * lane + 128 * jq + e;
-                    rown[jq][e] = Rg[c < N ? c : N - 1];
-                }
-            __builtin_amdgcn_sched_barrier(0);                    // all loads in flight before the first use
-            wait_vmf<0>();
-#pragma unroll
-            for (int s = 0; s + 1 < STEPS; ++s) Bw[s] *= fast_rcp(rv[s]);
-            Bw[STEPS - 1] = tail_clamp ? 0.0 : Bw[STEPS - 1] * fast_rcp(rv[STEPS - 1]);
-#pragma unroll
-            for (int jq = 0; jq < NQ; ++jq)
-#pragma unroll
-                for (int e = 0; e < 2; ++e) {
-                    const int c = 2 * lane + 128 * jq + e;
-                    rown[jq][e] = (c < N) ? fast_rcp(rown[jq][e]) : 0.0;
-                }
-        };
+        // Hand-over (ly.wpark): the fill wave has parked Bw / rown of local replicate j in the highest rows of the b_t buffer that
+        // replicate j fills -- [STEPS][64] doubles of Bw, lane-major, then 1 / R of the N columns; rows >= prow0.  A stream wave reads its values with ds_read
+        // at the boundary, so its ring stays in flight.  Block kpark is the wave's first one with a row inside the park: before it
+        // stores there every stream wave that owns periods must have taken its weights (kFWTaken).
+        const bool wpark = ly.wpark != 0;
+        const int nact = nunit < nsw ? nunit : nsw;             // stream waves that own periods
+        const int prow0 = (int)(ly.wpark_off / 8u);
+        const int kpark = prow0 > ta ? (prow0 - ta) / 4 : 0;
 
         if (gtot > 0) {
-            // prologue: the first NB blocks
             int ij = 0, ik = 0;                                  // next block to issue
             auto advance_issue = [&]() { ++ik; if (ik == nblk) { ik = 0; ++ij; } };
-#pragma unroll
-            for (int u = 0; u < NB; ++u) {
-                if (u < gtot) { issue_block(ij, ik, u); advance_issue(); }
-            }
             int bslot = 0;
-            double qa[NQ][2];
             double* bt = bt0;
             int buf = 0;
             int gidx = 0;
-            for (int j = 0; j < nrep; ++j) {
-                const int b = (int)blockIdx.x + j * G;
-                if (wave == 0) stamp(b, 0);
-                load_weights(b);                                  // (drains the vm counter)
-                buf = nbuf == 2 ? (j & 1) : 0;
-                bt = bt0 + (size_t)buf * ly.bt_stride;
-                // the b_t buffer is free once the scan of the replicate that used it last is complete
-                if (j >= nbuf) {
-                    const bool must_wait = wave == 0 && (int)(ld_flag(flags + kFScanDone) - (unsigned)(j - nbuf + 1)) < 0;
-                    if (must_wait && lane == 0) __hip_atomic_store(flags + kFStreamWaits, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    if (!pf_wait_ge(flags + kFScanDone, (unsigned)(j - nbuf + 1), flags + kFAbort)) { wait_vmf<0>(); return; }
-                    if (must_wait && lane == 0) __hip_atomic_store(flags + kFStreamWaits, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                }
-                if (wave == 0) stamp(b, 1);
-                stamp(b, 32 + wave);                              // per-wave segment start / end (diagnostics)
+            // The replicate loop exists twice in the binary, one text: with the hand-over (kWp) it holds no VGPR-returning global
+            // load at all, so the compiler's own wait-count insertion has nothing to wait for in it -- with the other route's
+            // loads in the same loop it put a vmcnt(0) in front of the park reads.  false: the workgroup is draining.
+            auto replicates = [&](auto kWpTag) -> bool {
+                constexpr bool kWp = decltype(kWpTag)::value;
+                for (int j = 0; j < nrep; ++j) {
+                    const int b = (int)blockIdx.x + j * G;
+                    // Everything a lane derives from its id is derived HERE, per replicate, from a lane id the compiler cannot trace
+                    // back to threadIdx: nothing of it is live across the boundary.  What the block loop keeps in registers used to
+                    // be spilled across the replicate loop and reloaded at this point, and a scratch reload is a vmcnt(0) wait --
+                    // the drain of the ring the weight hand-over exists to avoid.
+                    const int lane = pf_fresh_lane();
+                    // lane roles of v_mfma_f64_4x4x4 (collapse_mfma.hip)
+                    const int K = lane >> 4, blk = (lane >> 2) & 3, q = lane & 3;
+                    const int g = blk >> 1, h = blk & 1;
+                    const unsigned lane16 = 16u * lane;
+                    bool pact[NDR];                                          // lane moves 16 bytes of piece p of a row
 #pragma unroll
-                for (int jq = 0; jq < NQ; ++jq) { qa[jq][0] = 0.0; qa[jq][1] = 0.0; }
-                for (int k = 0; k < nblk; ++k, ++gidx) {
-                    const int r0 = k * 4;
-                    const bool full = r0 + 4 <= nrows;           // (wave-uniform)
-                    // rows of this block have landed once at most the DMAs of the NB - 1 YOUNGER blocks are outstanding
-                    // (one in-order vmcnt counter per wave); at the tail of the sequence there are fewer younger blocks
-                    if (gidx + NB - 1 < gtot) wait_vmf<((NB - 1) * 4 * NDR <= 63 ? (NB - 1) * 4 * NDR : 63)>();
-                    else wait_vmf<0>();
-                    const char* blkbase = ring + (unsigned)bslot * 4u * SB;
-                    const char* pa = blkbase + lane_off;
-                    double xa[STEPS];
+                    for (int p = 0; p < NDR; ++p) pact[p] = lane16 + 1024u * p < rowB;
+                    const unsigned lane_off = (unsigned)q * SB + (unsigned)(4 * g + K) * 8u;
+                    const bool tail_clamp = (STEPS - 1) * CS + 4 * g + K >= N;
+                    const unsigned last_off = tail_clamp ? (unsigned)q * SB + (unsigned)(N - 1) * 8u : lane_off + (unsigned)(STEPS - 1) * (CS * 8u);
+                    // block k of local replicate jj into ring block `bslot`: 4 rows x NDR DMA instructions, always
+                    auto issue_block = [&](int jj, int k, int bslot) {
+                        const char* seg = reinterpret_cast<const char*>(a.panel + ((size_t)((int)blockIdx.x + jj * G) * T + ta) * N);
 #pragma unroll
-                    for (int s = 0; s + 1 < STEPS; ++s) xa[s] = *reinterpret_cast<const double*>(pa + s * (CS * 8));
-                    xa[STEPS - 1] = *reinterpret_cast<const double*>(blkbase + last_off);
-                    const char* pq = blkbase + lane16;
-                    double2 xq[4][NQ];
+                        for (int rr = 0; rr < 4; ++rr) {
+                            int ri = 4 * k + rr;
+                            ri = ri < nrows ? ri : nrows - 1;
+                            const char* src = seg + (size_t)ri * rowB + lane16;
+                            const unsigned dst = __builtin_amdgcn_readfirstlane(ring_lds + (unsigned)(bslot * 4 + rr) * SB);
 #pragma unroll
-                    for (int rr = 0; rr < 4; ++rr)
-#pragma unroll
-                        for (int jq = 0; jq < NQ; ++jq)
-                            xq[rr][jq] = pact[jq] ? *reinterpret_cast<const double2*>(pq + (unsigned)rr * SB + 1024u * jq)
-                                                  : make_double2(0.0, 0.0);
-                    wait_lgkmf();                                        // the reads are done before the slots are re-armed
-                    if (ij < nrep) { issue_block(ij, ik, bslot); advance_issue(); }
-                    double D = 0.0, D2 = 0.0;                            // two accumulators: half the dependent MFMA chain
-#pragma unroll
-                    for (int s = 0; s < STEPS; ++s) {
-                        if ((s & 1) == 0) D = __builtin_amdgcn_mfma_f64_4x4x4f64(xa[s], Bw[s], D, 0, 0, 0);
-                        else D2 = __builtin_amdgcn_mfma_f64_4x4x4f64(xa[s], Bw[s], D2, 0, 0, 0);
-                    }
-                    D += D2;
-#pragma unroll
-                    for (int rr = 0; rr < 4; ++rr) {
-                        if (full || r0 + rr < nrows) {                   // wave-uniform: rows past the segment repeat its last row
-#pragma unroll
-                            for (int jq = 0; jq < NQ; ++jq) {
-                                qa[jq][0] = fma(xq[rr][jq].x, xq[rr][jq].x, qa[jq][0]);
-                                qa[jq][1] = fma(xq[rr][jq].y, xq[rr][jq].y, qa[jq][1]);
+                            for (int p = 0; p < NDR; ++p) {
+                                if (pact[p]) dma16f(src + 1024 * p, dst + 1024u * p, dma_nt);
                             }
                         }
+                    };
+                    // weights of replicate bb by this wave itself (the route without the hand-over).  Ends with vmcnt(0): the ring blocks in
+                    // flight have landed too, and nothing new is issued until the weights are back.
+                    auto load_weights = [&](int bb) {
+                        double rv[STEPS];
+                        pf_weights_issue<STEPS, NQ>(a.Lam + (size_t)bb * N * R, a.Rv + (size_t)bb * N, N, lane, Bw, rv, rown);
+                        pf_weights_finish<STEPS, NQ>(N, lane, Bw, rv, rown);
+                    };
+                    if (j == 0) {                                     // prologue: the first NB blocks
+#pragma unroll
+                        for (int u = 0; u < NB; ++u) {
+                            if (u < gtot) { issue_block(ij, ik, u); advance_issue(); }
+                        }
                     }
-                    D += xor_lane<8>(D);                                 // fold the two series groups
-                    // lane (K = period, g = 0, h, q) holds factor 4 h + q of period r0 + K: the even-q lane stores (f, f + 1)
-                    const double hi = xor_lane<1>(D);
-                    const int t = ta + r0 + K;
-                    if (g == 0 && (q & 1) == 0 && t < tb)
-                        *reinterpret_cast<double2*>(&bt[(size_t)t * R + 4 * h + q]) = make_double2(D, hi);
-                    bslot = (bslot + 1 == NB) ? 0 : bslot + 1;
-                }
-                double sp = 0.0;
+                    if (wave == 0) stamp(b, 0);
+                    if constexpr (!kWp) load_weights(b);                      // (drains the vm counter)
+                    buf = nbuf == 2 ? (j & 1) : 0;
+                    bt = bt0 + (size_t)buf * ly.bt_stride;
+                    // the b_t buffer is free once the scan of the replicate that used it last is complete.  With the hand-over the
+                    // fill wave has waited for that scan before it parked the weights: w_ready >= j + 1 says both.
+                    if (kWp || j >= nbuf) {
+                        const bool must_wait = wave == 0 && j >= nbuf && (int)(ld_flag(flags + kFScanDone) - (unsigned)(j - nbuf + 1)) < 0;
+                        if (must_wait && lane == 0) __hip_atomic_store(flags + kFStreamWaits, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        if constexpr (kWp) {
+                            if (!pf_wait_ge<true>(flags + kFWReady, (unsigned)(j + 1), flags + kFAbort)) { wait_vmf<0>(); return false; }
+                        } else {
+                            if (!pf_wait_ge(flags + kFScanDone, (unsigned)(j - nbuf + 1), flags + kFAbort)) { wait_vmf<0>(); return false; }
+                        }
+                        if (must_wait && lane == 0) __hip_atomic_store(flags + kFStreamWaits, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    }
+                    if constexpr (kWp) {                              // no vmcnt wait here: the blocks in flight stay in flight
+                        const lds_double_ptr_f pk = (lds_double_ptr_f)(bt + ly.wpark_off) + lane;
 #pragma unroll
-                for (int jq = 0; jq < NQ; ++jq)
+                        for (int s = 0; s < STEPS; ++s) Bw[s] = pk[s * 64];
 #pragma unroll
-                    for (int e = 0; e < 2; ++e) sp = fma(qa[jq][e], rown[jq][e], sp);
-                sp = wave_allsum(sp);
-                if (lane == 0) {
-                    misc[kMiscSsum + buf * 8 + wave] = sp;
-                    if (sp != sp) atomicOr(a.status, 1);             // NaN in the panel on the balanced path
+                        for (int jq = 0; jq < NQ; ++jq) {             // 1 / R by column: the lane's own pairs, 0 past N
+                            const lds_double_ptr_f pr = pk + STEPS * 64 + lane + 128 * jq;
+                            rown[jq][0] = pact[jq] ? pr[0] : 0.0;
+                            rown[jq][1] = pact[jq] ? pr[1] : 0.0;
+                        }
+                        wait_lgkmf();                                 // the values are in registers before the count moves
+                        __builtin_amdgcn_wave_barrier();
+                        if (lane == 0) __hip_atomic_fetch_add(flags + kFWTaken, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    }
+                    if (wave == 0) stamp(b, 1);
+                    stamp(b, 32 + wave);                              // per-wave segment start / end (diagnostics)
+                    double qa[NQ][2];
+#pragma unroll
+                    for (int jq = 0; jq < NQ; ++jq) { qa[jq][0] = 0.0; qa[jq][1] = 0.0; }
+                    for (int k = 0; k < nblk; ++k, ++gidx) {
+                        const int r0 = k * 4;
+                        const bool full = r0 + 4 <= nrows;           // (wave-uniform)
+                        // from this block on the wave's b_t rows lie in the park of this replicate: everybody has read it?
+                        if (kWp && k == kpark) {
+                            if (!pf_wait_ge<true>(flags + kFWTaken, (unsigned)(nact * (j + 1)), flags + kFAbort)) { wait_vmf<0>(); return false; }
+                        }
+                        // rows of this block have landed once at most the DMAs of the NB - 1 YOUNGER blocks are outstanding
+                        // (one in-order vmcnt counter per wave); at the tail of the sequence there are fewer younger blocks
+                        if (gidx + NB - 1 < gtot) wait_vmf<((NB - 1) * 4 * NDR <= 63 ? (NB - 1) * 4 * NDR : 63)>();
+                        else wait_vmf<0>();
+                        const char* blkbase = ring + (unsigned)bslot * 4u * SB;
+                        const char* pa = blkbase + lane_off;
+                        double xa[STEPS];
+#pragma unroll
+                        for (int s = 0; s + 1 < STEPS; ++s) xa[s] = *reinterpret_cast<const double*>(pa + s * (CS * 8));
+                        xa[STEPS - 1] = *reinterpret_cast<const double*>(blkbase + last_off);
+                        const char* pq = blkbase + lane16;
+                        double2 xq[4][NQ];
+#pragma unroll
+                        for (int rr = 0; rr < 4; ++rr)
+#pragma unroll
+                            for (int jq = 0; jq < NQ; ++jq)
+                                xq[rr][jq] = pact[jq] ? *reinterpret_cast<const double2*>(pq + (unsigned)rr * SB + 1024u * jq)
+                                                      : make_double2(0.0, 0.0);
+                        wait_lgkmf();                                        // the reads are done before the slots are re-armed
+                        if (ij < nrep) { issue_block(ij, ik, bslot); advance_issue(); }
+                        double D = 0.0, D2 = 0.0;                            // two accumulators: half the dependent MFMA chain
+#pragma unroll
+                        for (int s = 0; s < STEPS; ++s) {
+                            if ((s & 1) == 0) D = __builtin_amdgcn_mfma_f64_4x4x4f64(xa[s], Bw[s], D, 0, 0, 0);
+                            else D2 = __builtin_amdgcn_mfma_f64_4x4x4f64(xa[s], Bw[s], D2, 0, 0, 0);
+                        }
+                        D += D2;
+#pragma unroll
+                        for (int rr = 0; rr < 4; ++rr) {
+                            if (full || r0 + rr < nrows) {                   // wave-uniform: rows past the segment repeat its last row
+#pragma unroll
+                                for (int jq = 0; jq < NQ; ++jq) {
+                                    qa[jq][0] = fma(xq[rr][jq].x, xq[rr][jq].x, qa[jq][0]);
+                                    qa[jq][1] = fma(xq[rr][jq].y, xq[rr][jq].y, qa[jq][1]);
+                                }
+                            }
+                        }
+                        D += xor_lane<8>(D);                                 // fold the two series groups
+                        // lane (K = period, g = 0, h, q) holds factor 4 h + q of period r0 + K: the even-q lane stores (f, f + 1)
+                        const double hi = xor_lane<1>(D);
+                        const int t = ta + r0 + K;
+                        if (g == 0 && (q & 1) == 0 && t < tb)
+                            *reinterpret_cast<double2*>(&bt[(size_t)t * R + 4 * h + q]) = make_double2(D, hi);
+                        bslot = (bslot + 1 == NB) ? 0 : bslot + 1;
+                    }
+                    double sp = 0.0;
+#pragma unroll
+                    for (int jq = 0; jq < NQ; ++jq)
+#pragma unroll
+                        for (int e = 0; e < 2; ++e) sp = fma(qa[jq][e], rown[jq][e], sp);
+                    sp = wave_allsum(sp);
+                    if (lane == 0) {
+                        misc[kMiscSsum + buf * 8 + wave] = sp;
+                        if (sp != sp) atomicOr(a.status, 1);             // NaN in the panel on the balanced path
+                    }
+                    // this wave's part of b_t is in LDS.  (The release waits for the LDS writes only in effect: the DMAs in
+                    // flight belong to the next replicate, so no full vmcnt wait here -- an explicit lgkmcnt wait instead.)
+                    wait_lgkmf();
+                    __builtin_amdgcn_wave_barrier();
+                    if (lane == 0) __hip_atomic_fetch_add(flags + kFBtReady + buf, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    if (wave == 0) stamp(b, 2);
+                    if (wave == nsw - 1) stamp(b, 3);
+                    stamp(b, 24 + wave);
                 }
-                // this wave's part of b_t is in LDS.  (The release waits for the LDS writes only in effect: the DMAs in
-                // flight belong to the next replicate, so no full vmcnt wait here -- an explicit lgkmcnt wait instead.)
-                wait_lgkmf();
-                __builtin_amdgcn_wave_barrier();
-                if (lane == 0) __hip_atomic_fetch_add(flags + kFBtReady + buf, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                if (wave == 0) stamp(b, 2);
-                if (wave == nsw - 1) stamp(b, 3);
-                stamp(b, 24 + wave);
-            }
+                return true;
+            };
+            if (!(wpark ? replicates(std::true_type{}) : replicates(std::false_type{}))) return;
             // ---- the deferred P_smooth fills: the panel is through, HBM is idle but for the last scan's outputs ----------
             if (ndefer > 0) {
                 wait_vmf<0>();
-                const int nact = nunit < nsw ? nunit : nsw;       // stream waves that own periods (they all get here)
+                const int lane = pf_fresh_lane();                 // (not the kernel's own: that one would be reloaded from scratch in the loop above)
+                // (nact: the stream waves that own periods -- they all get here)
                 const int npr = fa.r * (fa.r + 1) / 2;
                 double* ps = reinterpret_cast<double*>(const_cast<char*>(ring));   // this wave's ring is free now
                 for (int j = (nrep - ndefer > 0 ? nrep - ndefer : 0); j < nrep; ++j) {
@@ -1108,16 +1203,51 @@ __global__ __launch_bounds__(kPfMaxThreads) void pass_fused_kernel(CollapseArgs 
             stamp(b, 5);
         }
     } else if (wave == nsw + ncov) {
-        // ================= FILL: the fixed-point rows of P_smooth, all but the workgroup's last replicates ==============
+        // ================= FILL: the fixed-point rows of P_smooth, all but the workgroup's last replicates; the weight parks ====
         // Rows [lo, hi) of P_smooth equal the backward fixed point: 144 KB of fire-and-forget 16-byte stores per replicate, which
         // would hold a covariance wave's latency chain up for 15 us.  They are written when the tables of the replicate have been
         // handed over.  The fills of the workgroup's LAST replicates are left to the stream waves, who write them once their last
         // row has been issued: HBM is the bottleneck while the panel streams and idle during the scan-only tail of the kernel.
+        //
+        // Weight hand-over (ly.wpark).  This wave also forms the stream waves' weights of every local replicate jn (pf_weights_*:
+        // they depend on the lane only) and parks them in the highest rows of the b_t buffer jn & 1, the one replicate jn fills.
+        // That buffer is free once the scan of replicate jn - 2 is complete -- the stream of jn - 2 consumed its own park before it
+        // stored over it, the scan has read the rows -- and stays free until the stream of jn, which waits for w_ready >= jn + 1
+        // and therefore no longer for the scan itself.  The loads of jn are in flight while this wave waits for that scan: the
+        // round trip is off everybody's path, and one wave fetches Lam and R per replicate instead of four.  (W_0 and W_1 need no
+        // wait; they are parked one after the other, not from one batch of loads: two replicates' raw values are 216 registers.)
+        // No deadlock: the park of jn waits for scan jn - 2; the fill of replicate j for the tables of j, which their covariance
+        // wave publishes after scan j - 1; the stream of jn for the park of jn; scan j for the stream of j and the tables of j.
+        // This wave parks jn = j + 1 BEFORE it waits for the tables of j, so the park of jn never waits for anything of replicate
+        // jn - 1 or later: every wait points at a strictly smaller replicate, and replicates 0 and 1 wait for nothing.
         double* s_ps = misc + kMiscPs;
         __builtin_amdgcn_s_setprio(1);
         const int npr = fa.r * (fa.r + 1) / 2;
-        int b = blockIdx.x;
-        for (int j = 0; j < nrep_wg - ndefer && fa.P_smooth != nullptr; b += G, ++j) {
+        const bool wpark = ly.wpark != 0;
+        const int nfill = fa.P_smooth != nullptr ? nrep_wg - ndefer : 0;
+        for (int j = wpark ? -1 : 0; j < (wpark ? nrep_wg : nfill); ++j) {
+            const int jn = j + 1;
+            if (wpark && jn < nrep_wg) {
+                const int bn = (int)blockIdx.x + jn * G;
+                double Bw[STEPS], rv[STEPS], rown[NQ][2];
+                pf_weights_issue<STEPS, NQ>(fa.Lam + (size_t)bn * N * R, fa.Rv + (size_t)bn * N, N, lane, Bw, rv, rown);
+                if (jn >= 2) {
+                    if (!pf_wait_ge(flags + kFScanDone, (unsigned)(jn - 1), flags + kFAbort)) break;
+                }
+                pf_weights_finish<STEPS, NQ>(N, lane, Bw, rv, rown);
+                const lds_double_ptr_f pk = (lds_double_ptr_f)(bt0 + (size_t)(jn & 1) * ly.bt_stride + ly.wpark_off) + lane;
+#pragma unroll
+                for (int s = 0; s < STEPS; ++s) pk[s * 64] = Bw[s];
+#pragma unroll
+                for (int jq = 0; jq < NQ; ++jq) {                 // 1 / R by column (N is even: a pair lies inside N or past it)
+                    const lds_double_ptr_f pr = pk + STEPS * 64 + lane + 128 * jq;
+                    if (2 * lane + 128 * jq < N) { pr[0] = rown[jq][0]; pr[1] = rown[jq][1]; }
+                }
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");   // the park is written before the counter moves
+                if (lane == 0) __hip_atomic_store(flags + kFWReady, (unsigned)(jn + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            }
+            if (j < 0 || j >= nfill) continue;
+            const int b = (int)blockIdx.x + j * G;
             if (!pf_wait_ge(flags + kFTabReady, (unsigned)(j + 1), flags + kFAbort)) break;
             const int fill_lo = __builtin_amdgcn_readfirstlane(ld_dev(fa.fill + 2 * b));
             const int fill_hi = __builtin_amdgcn_readfirstlane(ld_dev(fa.fill + 2 * b + 1));
@@ -1208,10 +1338,23 @@ __global__ __launch_bounds__(kPfMaxThreads) void pass_fused_kernel(CollapseArgs 
             if (tid == 0) stamp(b, 22);
         }
     }
-    if (lane == 0 && ld_flag(flags + kFAbort) != 0) atomicOr(a.status, 4);   // a bounded wait ran out
+    // (a fresh lane id: the kernel's own would be kept in scratch across the stream waves' replicate loop and reloaded in it)
+    if (pf_fresh_lane() == 0 && ld_flag(flags + kFAbort) != 0) atomicOr(a.status, 4);   // a bounded wait ran out
 }
 
 // ------------------------------------------------------------------------------------------------------------------
+// The route rule of the weight hand-over, in one place: the fill wave parks the stream waves' weights in the b_t buffer of the
+// replicate that will use them iff there are two buffers (with one, the buffer is free only when the stream already waits for it)
+// and the park -- [STEPS][64] doubles of lam / R in lane order, then 1 / R of the N columns -- fits the buffer's [T4][8] doubles.
+// DFM_PF_WPARK=0 (route) turns it off.
+static bool pf_wpark_rule(int T, int N, int nbuf, bool enabled, unsigned* off_doubles) {
+    const unsigned steps = (unsigned)(N + 7) / 8;
+    const unsigned park = steps * 64u + (unsigned)N, rows = (unsigned)((T + 3) / 4 * 4) * 8u;   // (N is even: so is the offset)
+    const bool use = enabled && nbuf == 2 && park <= rows;
+    if (off_doubles) *off_doubles = use ? rows - park : 0u;
+    return use;
+}
+
 static PfLds pf_layout(int T, int N, int nsw, int ncov, int nbuf) {
     PfLds l;
     unsigned off = 0;
@@ -1230,12 +1373,13 @@ static PfLds pf_layout(int T, int N, int nsw, int ncov, int nbuf) {
     l.ring = take((unsigned)nsw * 8u * pf_slot_bytes(N));
     l.total = off;
     l.nsw = nsw; l.ncov = ncov; l.nbuf = nbuf; l.nt = 0;
+    l.wpark = 0; l.wpark_off = 0;                             // (pf_pick decides)
     return l;
 }
 
 // Stream waves, covariance waves and b_t buffers that fit 160 KB of LDS and 12 waves: double-buffered b_t with as many
 // stream waves as fit (at least 3), else one buffer (the stream then waits for the scan of the previous replicate).
-static PfLds pf_pick(int T, int N, int want_nsw, int want_ncov) {
+static PfLds pf_pick(int T, int N, int want_nsw, int want_ncov, bool wpark = true) {
     int ncov = want_ncov > 0 ? want_ncov : kPfMaxCov;
     if (ncov > kPfMaxCov) ncov = kPfMaxCov;
     int cap = kPfMaxWaves - kPfScanWaves - 1 - ncov;        // one fill wave
@@ -1247,8 +1391,11 @@ static PfLds pf_pick(int T, int N, int want_nsw, int want_ncov) {
     while (cap > 1 && T / cap < 8) --cap;                     // keep segments a few row blocks long
     for (int nbuf = 2; nbuf >= 1; --nbuf) {
         for (int nsw = cap; nsw >= (nbuf == 2 ? (cap < 3 ? cap : 3) : 1); --nsw) {
-            const PfLds l = pf_layout(T, N, nsw, ncov, nbuf);
-            if (l.total <= kPfLdsLimit) return l;
+            PfLds l = pf_layout(T, N, nsw, ncov, nbuf);
+            if (l.total <= kPfLdsLimit) {
+                l.wpark = pf_wpark_rule(T, N, nbuf, wpark, &l.wpark_off) ? 1 : 0;
+                return l;
+            }
         }
     }
     PfLds none = pf_layout(T, N, 1, ncov, 1);
@@ -1256,6 +1403,8 @@ static PfLds pf_pick(int T, int N, int want_nsw, int want_ncov) {
 }
 
 int pass_fused_pick_nsw(int T, int N, int want) { return pf_pick(T, N, want, 0).nsw; }
+int pass_fused_pick_nbuf(int T, int N) { return pf_pick(T, N, 0, 0).nbuf; }
+bool pass_fused_pick_wpark(int T, int N) { return pf_pick(T, N, 0, 0).wpark != 0; }
 
 // Rp = 8, the shapes of the MFMA collapse (even N, 8N <= 4096, ceil(N / 8) <= 32 steps), T below the LDS limit
 bool pass_fused_supported(int Rpad, int T, int N) {
@@ -1270,8 +1419,8 @@ bool pass_fused_supported(int Rpad, int T, int N) {
 }
 
 template <int STEPS, int NDR>
-static hipError_t launch_pf_one(const CollapseArgs& a, const FastArgs& fa, int nsw, int ncov, int num_cu, hipStream_t s) {
-    PfLds ly = pf_pick(a.T, a.N, nsw, ncov);
+static hipError_t launch_pf_one(const CollapseArgs& a, const FastArgs& fa, int nsw, int ncov, bool wpark, int num_cu, hipStream_t s) {
+    PfLds ly = pf_pick(a.T, a.N, nsw, ncov, wpark);
     if (ly.total > kPfLdsLimit) return hipErrorInvalidValue;
     ly.nt = stream_nt_hint((size_t)a.B * a.T * a.N * sizeof(double)) ? 1 : 0;
     static LdsOptIn attr_done;
@@ -1288,7 +1437,7 @@ static hipError_t launch_pf_one(const CollapseArgs& a, const FastArgs& fa, int n
 }
 
 template <int S>
-static hipError_t launch_pf_pick(const CollapseArgs& a, const FastArgs& fa, int nsw, int ncov, int num_cu, hipStream_t s, int steps) {
+static hipError_t launch_pf_pick(const CollapseArgs& a, const FastArgs& fa, int nsw, int ncov, bool wpark, int num_cu, hipStream_t s, int steps) {
     if constexpr (S > 32) {
         return hipErrorInvalidValue;
     } else {
@@ -1298,18 +1447,18 @@ static hipError_t launch_pf_pick(const CollapseArgs& a, const FastArgs& fa, int 
         if (steps == S) {
             const int ndr = (a.N * 8 + 1023) / 1024;
             constexpr int lo = (8 * (S - 1) * 8 + 8 + 1023) / 1024, hi = (8 * S * 8 + 1023) / 1024;
-            if constexpr (lo <= 1 && 1 <= hi) { if (ndr == 1) return launch_pf_one<S, 1>(a, fa, nsw, ncov, num_cu, s); }
-            if constexpr (lo <= 2 && 2 <= hi) { if (ndr == 2) return launch_pf_one<S, 2>(a, fa, nsw, ncov, num_cu, s); }
-            if constexpr (lo <= 3 && 3 <= hi) { if (ndr == 3) return launch_pf_one<S, 3>(a, fa, nsw, ncov, num_cu, s); }
-            if constexpr (lo <= 4 && 4 <= hi) { if (ndr == 4) return launch_pf_one<S, 4>(a, fa, nsw, ncov, num_cu, s); }
+            if constexpr (lo <= 1 && 1 <= hi) { if (ndr == 1) return launch_pf_one<S, 1>(a, fa, nsw, ncov, wpark, num_cu, s); }
+            if constexpr (lo <= 2 && 2 <= hi) { if (ndr == 2) return launch_pf_one<S, 2>(a, fa, nsw, ncov, wpark, num_cu, s); }
+            if constexpr (lo <= 3 && 3 <= hi) { if (ndr == 3) return launch_pf_one<S, 3>(a, fa, nsw, ncov, wpark, num_cu, s); }
+            if constexpr (lo <= 4 && 4 <= hi) { if (ndr == 4) return launch_pf_one<S, 4>(a, fa, nsw, ncov, wpark, num_cu, s); }
             return hipErrorInvalidValue;
         }
-        return launch_pf_pick<S + 1>(a, fa, nsw, ncov, num_cu, s, steps);
+        return launch_pf_pick<S + 1>(a, fa, nsw, ncov, wpark, num_cu, s, steps);
     }
 }
 
-hipError_t launch_pass_fused(const CollapseArgs& a, const FastArgs& fa, int nsw, int ncov, int num_cu, hipStream_t s) {
-    return launch_pf_pick<1>(a, fa, nsw, ncov, num_cu, s, (a.N + 7) / 8);
+hipError_t launch_pass_fused(const CollapseArgs& a, const FastArgs& fa, int nsw, int ncov, bool wpark, int num_cu, hipStream_t s) {
+    return launch_pf_pick<1>(a, fa, nsw, ncov, wpark, num_cu, s, (a.N + 7) / 8);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
