@@ -16,6 +16,7 @@
 // f64 matrix pipe (ar_moments_kernel), then four lanes per series for the solves (ar_solve_kernel); the two-sweep kernel with a
 // thread per series (mstep_ar_kernel: 4.3 ms per 1024 replicates at the Stock-Watson shape) is kept in the diagnostics library.
 // The reference has no counterpart of the joint estimation (dfm_functions.ipynb:21-23 declares `Parametric` only).
+#include "dfm_argeom.h"
 #include "dfm_kernels.h"
 
 namespace dfm {
@@ -254,22 +255,14 @@ namespace {
 
 typedef double ar_v4 __attribute__((ext_vector_type(4)));
 
-template <int R, int Q1>
-struct ArGeo {
-    static constexpr int K1 = R * Q1, NPR = K1 * (K1 + 1) / 2, NTM = (NPR + 15) / 16, NZF = (K1 + 15) / 16;
-    static constexpr int TT = NTM + Q1 * NZF, TPW = (TT + 3) / 4;
-    static constexpr int SGW = TPW <= 6 ? 3 : (TPW <= 9 ? 2 : 1);
-    static constexpr int NXX = Q1 * (Q1 + 1) / 2;
-};
-constexpr int kArTC = 128;                                     // periods per staged chunk of the panel block
-constexpr int kArPF = 3;                                       // B operands in flight: steps ahead
+// (ArGeo<R, Q1>, kArTC, kArPF, the tiles of a wave and the workspace arithmetic: dfm_argeom.h)
 
 template <int R, int Q1, int W>
 __device__ __forceinline__ void ar_mom_body(const ArMstepArgs& a, const double* __restrict__ V, double* __restrict__ OUT,
                                             double* __restrict__ SM, int ntm16, int VW, int Ns, double* Xs) {
     using G = ArGeo<R, Q1>;
     constexpr int Q = Q1 - 1, TPW = G::TPW, SGW = G::SGW, SW = 16 * SGW;
-    constexpr int NT = (G::TT - W * TPW) < TPW ? ((G::TT - W * TPW) > 0 ? (G::TT - W * TPW) : 0) : TPW;   // tiles of this wave
+    constexpr int NT = ar_wave_tiles(G::TT, TPW, W);               // tiles of this wave
     const int b = blockIdx.y, i0 = (int)blockIdx.x * SW;
     const int T = a.T, N = a.N, Tq = T - Q;
     const int tid = threadIdx.x, lane = tid & 63, k4 = lane >> 4, c16 = lane & 15;
@@ -398,7 +391,7 @@ __global__ __launch_bounds__(256) void ar_solve_kernel(ArMstepArgs a, const doub
     constexpr int Q = Q1 - 1, NE = Q1 * Q1, NU = Q1 * (Q1 + 1) / 2, NUL = (NU + 3) / 4;
     const int b = blockIdx.y;
     const int lane4 = (int)threadIdx.x & 3;
-    const int i = (int)blockIdx.x * 64 + ((int)threadIdx.x >> 2);
+    const int i = (int)blockIdx.x * kArSolveSeries + ((int)threadIdx.x >> 2);
     if (a.active && a.active[b] == 0) return;
     const int N = a.N;
     const bool live = i < N;
@@ -517,21 +510,11 @@ __global__ __launch_bounds__(256) void ar_solve_kernel(ArMstepArgs a, const doub
     a.sig2[(size_t)b * N + i] = sig / (double)n;
 }
 
-// V | OUT | SM (doubles) of the moment form; Ns = N rounded up to 16
-static size_t ar_ws_doubles(int B, int T, int N, int r, int q, int Rk, size_t* oV = nullptr, size_t* oOUT = nullptr, int* pVW = nullptr,
-                            int* pntm16 = nullptr, int* pNs = nullptr, int* pTT = nullptr) {
-    const int k1 = r * (q + 1), npr = k1 * (k1 + 1) / 2, ntm = (npr + 15) / 16, nzf = (k1 + 15) / 16;
-    const int VW = 16 * ntm + 16 * ((Rk + 15) / 16), Ns = (N + 15) & ~15, TT = ntm + (q + 1) * nzf;
-    const size_t nV = (size_t)B * (T - q) * VW, nOUT = (size_t)B * 16 * TT * Ns, nSM = (size_t)B * 16 * Ns;
-    if (oV) *oV = nV;
-    if (oOUT) *oOUT = nOUT;
-    if (pVW) *pVW = VW;
-    if (pntm16) *pntm16 = 16 * ntm;
-    if (pNs) *pNs = Ns;
-    if (pTT) *pTT = TT;
-    return nV + nOUT + nSM;
+// V | OUT | SM (doubles) of the moment form: ar_ws_geometry (dfm_argeom.h)
+size_t mstep_ar_workspace(int B, int T, int N, int r, int q, int Rk) {
+    const ArWs w = ar_ws_geometry(B, T, N, r, q, Rk);
+    return (w.nV + w.nOUT + w.nSM) * sizeof(double) + 256;
 }
-size_t mstep_ar_workspace(int B, int T, int N, int r, int q, int Rk) { return ar_ws_doubles(B, T, N, r, q, Rk) * sizeof(double) + 256; }
 
 template <int R, int Q1>
 static hipError_t launch_ar_rq(const ArMstepArgs& a, double* ws, hipStream_t s) {
@@ -548,17 +531,16 @@ static hipError_t launch_ar_rq(const ArMstepArgs& a, double* ws, hipStream_t s) 
 #endif
         if (ws == nullptr) return hipErrorInvalidValue;
         using G = ArGeo<R, Q1>;
-        size_t nV = 0, nOUT = 0;
-        int VW = 0, ntm16 = 0, Ns = 0, TT = 0;
-        ar_ws_doubles(a.B, a.T, a.N, a.r, a.q, a.Rk, &nV, &nOUT, &VW, &ntm16, &Ns, &TT);
-        double *V = ws, *OUT = V + nV, *SM = OUT + nOUT;
+        const ArWs w = ar_ws_geometry(a.B, a.T, a.N, a.r, a.q, a.Rk);
+        const int VW = w.VW, ntm16 = w.ntm16, Ns = w.Ns;
+        double *V = ws, *OUT = V + w.nV, *SM = OUT + w.nOUT;
         hipError_t e = launch_mmw_vec(a.zsm, a.Psm, a.active, a.B, a.T - a.q, G::K1, a.Rk, ntm16, VW, V, s);
         if (e != hipSuccess) return e;
         constexpr int SW = 16 * G::SGW;
         const size_t lds = (size_t)(kArTC + Q1 - 1) * SW * sizeof(double);
-        hipLaunchKernelGGL((ar_moments_kernel<R, Q1>), dim3((a.N + SW - 1) / SW, a.B), dim3(256), lds, s, a, (const double*)V, OUT, SM, ntm16, VW, Ns);
+        hipLaunchKernelGGL((ar_moments_kernel<R, Q1>), dim3(ar_moment_blocks<R, Q1>(a.N), a.B), dim3(256), lds, s, a, (const double*)V, OUT, SM, ntm16, VW, Ns);
         if ((e = hipGetLastError()) != hipSuccess) return e;
-        hipLaunchKernelGGL((ar_solve_kernel<R, Q1>), dim3((a.N + 63) / 64, a.B), dim3(256), 0, s, a, (const double*)OUT, (const double*)SM, Ns);
+        hipLaunchKernelGGL((ar_solve_kernel<R, Q1>), dim3(ar_solve_blocks(a.N), a.B), dim3(256), 0, s, a, (const double*)OUT, (const double*)SM, Ns);
         return hipGetLastError();
     }
 }
