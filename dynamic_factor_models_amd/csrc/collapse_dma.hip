@@ -26,30 +26,6 @@
 
 namespace dfm {
 
-using lds_char_ptr = __attribute__((address_space(3))) char*;
-
-// One LDS-DMA: every active lane moves 16 B from its own global address to lds_dst + 16 * lane.
-// M0 carries the wave-uniform LDS byte address; it is compiler-reserved, so it is saved and
-// restored inside the statement (cdna_hip_programming.md §5.7).  hipcc does not count this load.
-__device__ __forceinline__ void dma16(const void* gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %2\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, off\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(gsrc), "s"(lds_dst)
-        : "memory");
-}
-
-template <int K>
-__device__ __forceinline__ void wait_vmcnt() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"i"(K) : "memory");
-}
-__device__ __forceinline__ void wait_lgkm0() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-
 // OPT bits (tuning, measured with scripts/microbench/colbw.hip): 1 = wave segments start on 128-byte
 // boundaries (rows per wave rounded to a multiple of 128 / gcd(8N, 128)); 2 = the first ring fill is
 // issued before the loading weights are fetched; 4 = no filler DMAs past the end of the segment (the
@@ -182,7 +158,7 @@ __global__ __launch_bounds__(256) void collapse_dma_kernel(CollapseArgs a) {
                 xs[rr][j] = act[j] ? *reinterpret_cast<const double2*>(ring + o) : make_double2(0.0, 0.0);
             }
         }
-        wait_lgkm0();   // the reads are done before their pieces are re-armed
+        wait_lgkmcnt0();   // the reads are done before their pieces are re-armed
         {
             int done_rows = r0 + RB;
             done_rows = done_rows < nrows ? done_rows : nrows;

@@ -33,26 +33,6 @@
 
 namespace dfm {
 
-using lds_char_ptr_m = __attribute__((address_space(3))) char*;
-
-__device__ __forceinline__ void dma16m(const void* gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %2\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, off\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(gsrc), "s"(lds_dst)
-        : "memory");
-}
-template <int K>
-__device__ __forceinline__ void wait_vm() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"i"(K) : "memory");
-}
-__device__ __forceinline__ void wait_lgkm() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-
 #ifdef DFM_MFMA_BENCH_ONLY      // scripts/microbench/colbw.hip: only the headline shape, with the ablation variants
 constexpr bool kMfmaBench = true;
 #else
@@ -201,7 +181,7 @@ __global__ __launch_bounds__(256, ((STEPS * MfmaGeo<R>::NINST <= 25 && !FUSE) ? 
     const unsigned ringB = NS * SB;
     const char* ring = smem + (size_t)wave * ringB;
     const unsigned ring_lds =
-        __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lds_char_ptr_m)(smem)) + (unsigned)wave * ringB;
+        __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lds_char_ptr)(smem)) + (unsigned)wave * ringB;
     const unsigned lane16 = 16u * lane;
     bool pact[NDR];                                          // lane moves 16 bytes of piece p of a row
 #pragma unroll
@@ -213,7 +193,7 @@ __global__ __launch_bounds__(256, ((STEPS * MfmaGeo<R>::NINST <= 25 && !FUSE) ? 
         const unsigned dst = __builtin_amdgcn_readfirstlane(ring_lds + (unsigned)slot * SB);
 #pragma unroll
         for (int p = 0; p < NDR; ++p) {
-            if (pact[p]) dma16m(src + 1024 * p, dst + 1024u * p);
+            if (pact[p]) dma16(src + 1024 * p, dst + 1024u * p);
         }
     };
     // B operands: W[c][f] = lam_cf / R_c for c = s CS + 4 g + K, f = 4 (h + FPI m) + q.  All loads first
@@ -320,10 +300,10 @@ __global__ __launch_bounds__(256, ((STEPS * MfmaGeo<R>::NINST <= 25 && !FUSE) ? 
             // younger than the DMAs this block needs (re-arm of iteration bk - NB): the deferred stores issued
             // behind the re-arms of iterations bk - NB .. bk - 1 (NB of them once the queue is primed) and the
             // re-arms of iterations bk - NB + 1 .. bk - 1
-            if (bk >= kDefer + NB) wait_vm<(KW + NB * G::NINST <= 63 ? KW + NB * G::NINST : 63)>();
-            else wait_vm<(KW <= 63 ? KW : 63)>();
+            if (bk >= kDefer + NB) wait_vmcnt<(KW + NB * G::NINST <= 63 ? KW + NB * G::NINST : 63)>();
+            else wait_vmcnt<(KW <= 63 ? KW : 63)>();
         } else {
-            wait_vm<0>();
+            wait_vmcnt<0>();
         }
         const unsigned long long s1 = now();
         const char* blkbase = ring + (unsigned)bslot * 4u * SB;
@@ -340,7 +320,7 @@ __global__ __launch_bounds__(256, ((STEPS * MfmaGeo<R>::NINST <= 25 && !FUSE) ? 
             for (int j = 0; j < NQ; ++j)
                 xq[rr][j] = pact[j] ? *reinterpret_cast<const double2*>(pq + (unsigned)rr * SB + 1024u * j)
                                     : make_double2(0.0, 0.0);
-        wait_lgkm();                                         // the reads are done before the slots are re-armed
+        wait_lgkmcnt0();                                     // the reads are done before the slots are re-armed
         const unsigned long long s2 = now();
         if constexpr (MODE == 0) {
 #pragma unroll
@@ -452,7 +432,7 @@ __global__ __launch_bounds__(256, ((STEPS * MfmaGeo<R>::NINST <= 25 && !FUSE) ? 
 #pragma unroll
     for (int dq = kDefer - 1; dq >= 0; --dq) store_pending(dq);   // the last kDefer row blocks
     const unsigned long long t_loop_end = now();
-    wait_vm<0>();
+    wait_vmcnt<0>();
     // s = sum_t sum_i x_it^2 / R_i over this wave's periods
     double sp = 0.0;
     {

@@ -41,26 +41,6 @@ namespace dfm {
 
 namespace {
 
-using lds_char_ptr_x = __attribute__((address_space(3))) char*;
-
-__device__ __forceinline__ void dma16x(const void* gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %2\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, off\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(gsrc), "s"(lds_dst)
-        : "memory");
-}
-template <int K>
-__device__ __forceinline__ void wait_vmx() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"i"(K) : "memory");
-}
-__device__ __forceinline__ void wait_lgkmx() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-
 __host__ __device__ inline unsigned miss_slot_bytes(int N) {
     unsigned sb = (unsigned)N * 8u;
     while ((sb & 255u) != 64u && (sb & 255u) != 192u) sb += 16u;
@@ -128,7 +108,7 @@ __global__ __launch_bounds__(256, 2) void collapse_miss_kernel(CollapseArgs a, u
     double* Wt = reinterpret_cast<double*>(smem + 4 * ringB);
     double* Rt = Wt + (size_t)(N + 1) * R;
     int* idx = reinterpret_cast<int*>(Rt + (N + 2)) + (size_t)wave * (N8 + 8);
-    const unsigned ring_lds = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lds_char_ptr_x)(smem)) + (unsigned)wave * ringB;
+    const unsigned ring_lds = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lds_char_ptr)(smem)) + (unsigned)wave * ringB;
     const unsigned lane16 = 16u * lane;
     bool pact[NDR];
 #pragma unroll
@@ -151,7 +131,7 @@ __global__ __launch_bounds__(256, 2) void collapse_miss_kernel(CollapseArgs a, u
             const unsigned dst = __builtin_amdgcn_readfirstlane(ring_lds + (unsigned)(bslot * 4 + rr) * SB);
 #pragma unroll
             for (int p = 0; p < NDR; ++p) {
-                if (pact[p]) dma16x(src + 1024 * p, dst + 1024u * p);
+                if (pact[p]) dma16(src + 1024 * p, dst + 1024u * p);
             }
         }
     };
@@ -231,8 +211,8 @@ __global__ __launch_bounds__(256, 2) void collapse_miss_kernel(CollapseArgs a, u
     int bslot = 0;
     for (int k = 0; k < nblk; ++k) {
         const int r0 = k * 4;
-        if (k + NB - 1 < nblk) wait_vmx<((NB - 1) * 4 * NDR <= 63 ? (NB - 1) * 4 * NDR : 63)>();
-        else wait_vmx<0>();
+        if (k + NB - 1 < nblk) wait_vmcnt<((NB - 1) * 4 * NDR <= 63 ? (NB - 1) * 4 * NDR : 63)>();
+        else wait_vmcnt<0>();
         const char* blkbase = ring + (unsigned)bslot * 4u * SB;
         const char* pa = blkbase + lane_off;
         double xa[STEPS];
@@ -247,7 +227,7 @@ __global__ __launch_bounds__(256, 2) void collapse_miss_kernel(CollapseArgs a, u
             for (int jq = 0; jq < NQ; ++jq)
                 xq[rr][jq] = pact[jq] ? *reinterpret_cast<const double2*>(pq + (unsigned)rr * SB + 1024u * jq)
                                       : make_double2(0.0, 0.0);
-        wait_lgkmx();                                            // the reads are done before the slots are re-armed
+        wait_lgkmcnt0();                                         // the reads are done before the slots are re-armed
         if (k + NB < nblk) issue_block(k + NB, bslot);
         // b_t over the observed cells: NaN operands -> 0
         double D = 0.0, D2 = 0.0;
@@ -373,7 +353,7 @@ __global__ __launch_bounds__(256, 2) void collapse_miss_kernel(CollapseArgs a, u
             if (canon && t < tb && obs) {                        // doubles 8, 9 of the row: s_t, n_t log 2 pi + sum of log R over the observed
                 double* sl = obs_row(t) + 8;
                 if (ridx < 4) sl[0] = red[0];
-                else sl[1] = (double)(N - nm) * 1.8378770664093454835606594728112 + (ldfull - red[0]);
+                else sl[1] = (double)(N - nm) * kLog2Pi + (ldfull - red[0]);
             } else if (canon && t < tb) {
                 if (ridx < 4) {
                     a.scol[(size_t)b * T + t] = red[0];

@@ -29,58 +29,9 @@
 #include "dfm_gram.h"
 #include "dfm_kernels.h"
 
-// cache-policy modifiers of the streaming LDS-DMA loads (development A/B: -DDFM_DMA_MOD='" nt"', '" sc1"', ...); default: none
-#ifndef DFM_DMA_MOD
-#define DFM_DMA_MOD ""
-#endif
-
 namespace dfm {
 
 namespace {
-
-using lds_char_ptr_w = __attribute__((address_space(3))) char*;
-using lds_cvd_ptr_w = const volatile __attribute__((address_space(3))) double*;
-// one ds_read_b64 (never merged into ds_read2_b64, never moved relative to other volatile accesses) of LDS byte address a
-__device__ __forceinline__ double lds_read64(unsigned a) { return *(lds_cvd_ptr_w)(size_t)a; }
-typedef double w2_v4 __attribute__((ext_vector_type(4)));
-typedef double w2_v2 __attribute__((ext_vector_type(2)));
-typedef unsigned w2_u4 __attribute__((ext_vector_type(4)));
-typedef unsigned w2_u2 __attribute__((ext_vector_type(2)));
-using lds_cv2_ptr_w = const __attribute__((address_space(3))) w2_v2*;
-using lds_cu4_ptr_w = const __attribute__((address_space(3))) w2_u4*;
-using lds_cu2_ptr_w = const __attribute__((address_space(3))) w2_u2*;
-using lds_cu1_ptr_w = const __attribute__((address_space(3))) unsigned*;
-
-__device__ __forceinline__ void dma16w(const void* gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %2\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, off" DFM_DMA_MOD "\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(gsrc), "s"(lds_dst)
-        : "memory");
-}
-// the PANEL rows of collapse_wide2_kernel (development A/B: -DDFM_W2_PANEL_MOD='" nt"' puts a modifier on them alone -- the W / R
-// tables of a replicate are re-read from L2 by every CU of its XCD and must stay cacheable)
-#ifndef DFM_W2_PANEL_MOD
-#define DFM_W2_PANEL_MOD DFM_DMA_MOD
-#endif
-__device__ __forceinline__ void dma16wp(const void* gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %2\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, off" DFM_W2_PANEL_MOD "\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(gsrc), "s"(lds_dst)
-        : "memory");
-}
-__device__ __forceinline__ void wait_all_w() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 constexpr int kW2R = 32;          // padded factors (widest; the kernels are templates in R = 16 | 32, the stage layout is R = 32's)
 #ifndef DFM_W2_ROWS
@@ -167,7 +118,7 @@ __global__ __launch_bounds__(kPrepThreads) void wide_prep_kernel(CollapseArgs a,
     const int tile = wave % NTILE, sl = wave / NTILE;
     const int it = tile / (R / 16), jt = tile % (R / 16);
     const int k4 = lane >> 4, c16 = lane & 15;
-    w2_v4 acc = {0.0, 0.0, 0.0, 0.0};
+    v4d acc = {0.0, 0.0, 0.0, 0.0};
     const int steps = (N + 3) / 4;
     const int sps = (steps + NSL - 1) / NSL;
     const int s_lo = sl * sps, s_hi = (s_lo + sps < steps) ? s_lo + sps : steps;
@@ -232,7 +183,7 @@ __global__ __launch_bounds__(kW2Threads) void collapse_wide2_kernel(CollapseArgs
     const int nch = (N + kW2Chunk - 1) / kW2Chunk;
     double* redS = reinterpret_cast<double*>(smem + kW2NBuf * kW2StageB);   // [2][8]: s_t partials of the waves, by tile parity
     volatile int* itemq = reinterpret_cast<volatile int*>(redS + 16);       // [kW2Ring]: published items (-1 = the queue is empty)
-    const unsigned itemq_lds = (unsigned)(size_t)(lds_char_ptr_w)(smem) + kW2NBuf * kW2StageB + 16 * 8;
+    const unsigned itemq_lds = (unsigned)(size_t)(lds_char_ptr)(smem) + kW2NBuf * kW2StageB + 16 * 8;
     unsigned long long* stamps = reinterpret_cast<unsigned long long*>(redS + 32);   // DIAG, abl & 256: [64 stages][4] of workgroup 0, wave 0
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -288,7 +239,7 @@ __global__ __launch_bounds__(kW2Threads) void collapse_wide2_kernel(CollapseArgs
         __builtin_amdgcn_s_setprio(3);                        // few instructions, all on the critical path of the stream
         const unsigned rowB = (unsigned)N * 8u;
         const unsigned wbytes = (unsigned)N * R * 8u;
-        const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lds_char_ptr_w)(smem));
+        const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lds_char_ptr)(smem));
         auto issue_dma = [&](int b, int t0, int ch, int bsel) {
             if (abl & 32) return;                             // (diagnostics: compute only)
             const char* Xb = reinterpret_cast<const char*>(a.panel + (size_t)b * T * N);
@@ -304,7 +255,7 @@ __global__ __launch_bounds__(kW2Threads) void collapse_wide2_kernel(CollapseArgs
                 t = t < T ? t : T - 1;
                 const char* src = Xb + (size_t)t * rowB + colB;
                 const unsigned dst = __builtin_amdgcn_readfirstlane(sbase + (unsigned)(pw * 8 + k) * kW2GroupB);
-                if (act) dma16wp(src, dst);
+                if (act) dma16_w2_panel(src, dst);
             }
 #pragma unroll
             for (int u = 0; u < GEO::WPieces; ++u) {   // past the end of W -- the last, partial stage -- the lanes re-read its last 16 bytes; those rows only ever meet a zeroed A
@@ -312,14 +263,14 @@ __global__ __launch_bounds__(kW2Threads) void collapse_wide2_kernel(CollapseArgs
                 const unsigned dst = __builtin_amdgcn_readfirstlane(sbase + kW2PanelB + (unsigned)(GEO::WPieces * pw + u) * 1024u);
                 unsigned oo = o < wbytes ? o : wbytes - 16u;
                 if (lamd) oo ^= (oo & 256u) >> 1;           // odd series (256-byte rows): 16-byte unit u <- u ^ 8, i.e. byte offset ^ 128
-                dma16w(Wb + oo, dst);
+                dma16_mod(Wb + oo, dst);
             }
             if (pw == 0) {                  // 1 / R of the stage's 32 series (the table is padded with zeros to a whole stage)
                 const unsigned dst = __builtin_amdgcn_readfirstlane(sbase + kW2PanelB + kW2WB);
-                if (lane < 16) dma16w(Rb + (size_t)ch * (kW2Chunk * 8u) + 16u * lane, dst);
+                if (lane < 16) dma16_mod(Rb + (size_t)ch * (kW2Chunk * 8u) + 16u * lane, dst);
                 if (MISS) {                 // ... and log R (the table follows the 1 / R table of the whole batch)
                     const char* Lb = Rb + (size_t)B * npad * 8u;
-                    if (lane < 16) dma16w(Lb + (size_t)ch * (kW2Chunk * 8u) + 16u * lane, dst + kW2Chunk * 8u);
+                    if (lane < 16) dma16_mod(Lb + (size_t)ch * (kW2Chunk * 8u) + 16u * lane, dst + kW2Chunk * 8u);
                 }
             }
         };
@@ -341,9 +292,9 @@ __global__ __launch_bounds__(kW2Threads) void collapse_wide2_kernel(CollapseArgs
         }
         int bsel = 0;
         while (more) {
-            if (!v1) wait_all_w();
-            else if (pw == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(GEO::PerStage + (MISS ? 2 : 1)) : "memory");
-            else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(GEO::PerStage) : "memory");
+            if (!v1) wait_vmcnt<0>();
+            else if (pw == 0) wait_vmcnt<GEO::PerStage + (MISS ? 2 : 1)>();
+            else wait_vmcnt<GEO::PerStage>();
             __syncthreads();                                  // stage q has landed; every consumer is done with stage q - 1
             const bool v2 = ikk >= 0;                         // stage q + 2 exists: into the buffer stage q - 1 used
             if (v2) issue_next(bsel == 0 ? 2 : bsel - 1);
@@ -363,7 +314,7 @@ __global__ __launch_bounds__(kW2Threads) void collapse_wide2_kernel(CollapseArgs
         }
     };
     const int k4 = lane >> 4, c16 = lane & 15;
-    const unsigned ldsc = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lds_char_ptr_w)(smem));
+    const unsigned ldsc = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lds_char_ptr)(smem));
     int ci = 0, ch = 0, bsel = 0, cb = 0, ctile = 0;          // consume cursor
     bool more;
     {
@@ -371,9 +322,8 @@ __global__ __launch_bounds__(kW2Threads) void collapse_wide2_kernel(CollapseArgs
         more = kk0 >= 0;
         if (more) decode(kk0, cb, ctile);
     }
-    typedef double w2_v4 __attribute__((ext_vector_type(4)));
-    w2_v4 acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};   // factors 0..15: even / odd steps
-    w2_v4 accb = {0.0, 0.0, 0.0, 0.0};                                // NX == 4: factors 16..31
+    v4d acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};   // factors 0..15: even / odd steps
+    v4d accb = {0.0, 0.0, 0.0, 0.0};                                // NX == 4: factors 16..31
     double acc4[N4 > 0 ? N4 : 1];
 #pragma unroll
     for (int x = 0; x < (N4 > 0 ? N4 : 1); ++x) acc4[x] = 0.0;
@@ -393,7 +343,7 @@ __global__ __launch_bounds__(kW2Threads) void collapse_wide2_kernel(CollapseArgs
 
     // finished tile: its results wait in registers / redS until the next barrier has passed
     int pend_b = -1, pend_t0 = 0, pend_par = 0, pend_tile = 0;
-    w2_v4 pacc = {0.0, 0.0, 0.0, 0.0}, paccb = {0.0, 0.0, 0.0, 0.0};
+    v4d pacc = {0.0, 0.0, 0.0, 0.0}, paccb = {0.0, 0.0, 0.0, 0.0};
     double pacc4[N4 > 0 ? N4 : 1];
     auto flush_pending = [&]() {
         if (pend_b < 0) return;
@@ -479,7 +429,7 @@ __global__ __launch_bounds__(kW2Threads) void collapse_wide2_kernel(CollapseArgs
             pacc = acc0 + acc1; paccb = accb;
 #pragma unroll
             for (int x = 0; x < (N4 > 0 ? N4 : 1); ++x) { pacc4[x] = acc4[x]; acc4[x] = 0.0; }
-            acc0 = w2_v4{0.0, 0.0, 0.0, 0.0}; acc1 = acc0; accb = acc0;
+            acc0 = v4d{0.0, 0.0, 0.0, 0.0}; acc1 = acc0; accb = acc0;
             if (MISS) {                                       // per period: fold the four series classes k4 of the row
                 qs += __shfl_xor(qs, 16, 64); qs += __shfl_xor(qs, 32, 64);
                 nmis += __shfl_xor(nmis, 16, 64); nmis += __shfl_xor(nmis, 32, 64);
@@ -653,13 +603,13 @@ __global__ __launch_bounds__(kCtThreads) void ct_miss_wide2_kernel(CollapseArgs 
     const double* __restrict__ X = a.panel + (size_t)b * T * N;
     const char* __restrict__ Wb = reinterpret_cast<const char*>(Wall + (size_t)b * N * R);
     const int nch = npad / SS;
-    const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lds_char_ptr_w)(smem));
+    const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lds_char_ptr)(smem));
     const unsigned wbytes = (unsigned)N * R * 8u;
     auto issue = [&](int ch, int buf) {                        // wave w moves piece w of stage ch: ONE global_load_lds_dwordx4
         unsigned o = (unsigned)ch * (SS * R * 8u) + (unsigned)wave * 1024u + 16u * lane;
         o = o < wbytes ? o : wbytes - 16u;                    // the last stage may be partial: its rows past N are never selected
         const unsigned dst = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)buf * kStageB + (unsigned)wave * kPieceB);
-        dma16w(Wb + o, dst);
+        dma16_mod(Wb + o, dst);
     };
 #pragma unroll
     for (int u = 0; u < NBUF - 1; ++u)
@@ -719,7 +669,7 @@ __global__ __launch_bounds__(kCtThreads) void ct_miss_wide2_kernel(CollapseArgs 
                 default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
             }
         }
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");     // everybody's piece has landed; every wave is done with stage ch - 1
+        lds_barrier();                                                      // everybody's piece has landed; every wave is done with stage ch - 1
         if (ch + NBUF - 1 < nch) issue(ch + NBUF - 1, (ch + NBUF - 1) % NBUF);   // into the buffer stage ch - 1 used (ch = 0: a fresh one)
         if (!mine) continue;
         const char* st = smem + (size_t)(ch % NBUF) * kStageB;
@@ -789,7 +739,7 @@ __global__ __launch_bounds__(kCtThreads) void ct_miss_wide2_kernel(CollapseArgs 
                 const int jj = 4 * bi + x, kk = 4 * bj + y;
                 if (act && slot == 0 && kk <= jj && jj < ctr) Cs[jj * (jj + 1) / 2 + kk] = cfv[x][y] - e;
             }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_lgkmcnt0();
         __builtin_amdgcn_wave_barrier();
         if (a.Ct == nullptr) {                                // the caller promised a balanced panel: flag it, keep valid memory
             if (lane == 0) atomicOr(a.status, 1);
@@ -797,7 +747,7 @@ __global__ __launch_bounds__(kCtThreads) void ct_miss_wide2_kernel(CollapseArgs 
             double* Co = a.Ct + ((size_t)b * T + (t0 + tw0 + pp)) * NPo;      // (NPo is even: rows are 16-byte aligned)
             for (int v = 2 * lane; v < NPo; v += 128) *reinterpret_cast<double2*>(Co + v) = *reinterpret_cast<const double2*>(Cs + v);
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");        // (the row is read before the next period overwrites it)
+        wait_lgkmcnt0();                                          // (the row is read before the next period overwrites it)
         __builtin_amdgcn_wave_barrier();
     }
     (void)NPfull;
@@ -853,7 +803,7 @@ __global__ __launch_bounds__(64 * kCsWaves) void ct_miss_slice_kernel(CollapseAr
     double* Cs = Cfp + NPe + (size_t)wave * NPe;
     unsigned short* list = reinterpret_cast<unsigned short*>(Cfp + (size_t)(1 + kCsWaves) * NPe) + (size_t)wave * lcap;
     int* next_t = reinterpret_cast<int*>(reinterpret_cast<unsigned short*>(Cfp + (size_t)(1 + kCsWaves) * NPe) + (size_t)kCsWaves * lcap);   // (lcap is a multiple of 8: aligned)
-    const unsigned list0 = (unsigned)(size_t)(lds_char_ptr_w)(reinterpret_cast<char*>(list));
+    const unsigned list0 = (unsigned)(size_t)(lds_char_ptr)(reinterpret_cast<char*>(list));
     {
         const int pr = rb / 2;                                // 16-byte pieces per row
         const double* Vb = Vall + ((size_t)b * N + s0) * R;
@@ -891,7 +841,7 @@ __global__ __launch_bounds__(64 * kCsWaves) void ct_miss_slice_kernel(CollapseAr
 #else
     const unsigned offr = 8u * BH * ba, offc = 8u * BW * bc;
 #endif
-    const unsigned vs0 = (unsigned)(size_t)(lds_char_ptr_w)(Vs);
+    const unsigned vs0 = (unsigned)(size_t)(lds_char_ptr)(Vs);
     const double* __restrict__ X = a.panel + (size_t)b * T * N + s0;
     const int* __restrict__ nobs = a.nobs + (size_t)b * T;
     constexpr int XU = 8;                                     // panel loads in flight per lane (512 series per batch)
@@ -946,22 +896,22 @@ __global__ __launch_bounds__(64 * kCsWaves) void ct_miss_slice_kernel(CollapseAr
             }
         }
         if (lane < SPT) list[n + lane] = (unsigned short)ns;
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_lgkmcnt0();
         __builtin_amdgcn_wave_barrier();
         // ---- SPT series per trip, the same for every lane: their indices in one broadcast read, their rows in 2 SPT reads issued
         // together (the empty statements pin that order: left alone, the compiler re-uses one register set and waits per series)
         for (int e0 = 0; e0 < n; e0 += SPT) {
             unsigned idx[SPT];
             if (SPT == 8) {
-                const w2_u4 L = *(lds_cu4_ptr_w)(size_t)(list0 + 2u * (unsigned)e0);
+                const v4u L = *(lds_cu4_ptr)(size_t)(list0 + 2u * (unsigned)e0);
 #pragma unroll
                 for (int k = 0; k < 4; ++k) { idx[2 * k] = L[k] & 0xffffu; idx[2 * k + 1] = L[k] >> 16; }
             } else if (SPT == 4) {
-                const w2_u2 L = *(lds_cu2_ptr_w)(size_t)(list0 + 2u * (unsigned)e0);
+                const v2u L = *(lds_cu2_ptr)(size_t)(list0 + 2u * (unsigned)e0);
 #pragma unroll
                 for (int k = 0; k < 2; ++k) { idx[2 * k] = L[k] & 0xffffu; idx[2 * k + 1] = L[k] >> 16; }
             } else {
-                const unsigned L = *(lds_cu1_ptr_w)(size_t)(list0 + 2u * (unsigned)e0);
+                const unsigned L = *(lds_cu1_ptr)(size_t)(list0 + 2u * (unsigned)e0);
                 idx[0] = L & 0xffffu; idx[SPT - 1] = L >> 16;
             }
             double vr[SPT][BH], vc[SPT][BW];
@@ -970,12 +920,12 @@ __global__ __launch_bounds__(64 * kCsWaves) void ct_miss_slice_kernel(CollapseAr
                 const unsigned ra = idx[k] * (unsigned)recB + vs0;
 #pragma unroll
                 for (int x = 0; x < BH; x += 2) {
-                    const w2_v2 d = *(lds_cv2_ptr_w)(size_t)(ra + offr + 8u * x);
+                    const v2d d = *(lds_cv2_ptr)(size_t)(ra + offr + 8u * x);
                     vr[k][x] = d[0]; vr[k][x + 1] = d[1];
                 }
 #pragma unroll
                 for (int y = 0; y < BW; y += 2) {
-                    const w2_v2 d = *(lds_cv2_ptr_w)(size_t)(ra + offc + 8u * y);
+                    const v2d d = *(lds_cv2_ptr)(size_t)(ra + offc + 8u * y);
                     vc[k][y] = d[0]; vc[k][y + 1] = d[1];
                 }
             }
@@ -1005,7 +955,7 @@ __global__ __launch_bounds__(64 * kCsWaves) void ct_miss_slice_kernel(CollapseAr
                 const int q = BH * ba + x, kk = BW * bc + y;
                 if (act && kk <= q && q < ctr) Cs[q * (q + 1) / 2 + kk] = E[x][y];
             }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_lgkmcnt0();
         __builtin_amdgcn_wave_barrier();
         if (even) {                                           // (rows are 16-byte aligned)
 #pragma unroll
@@ -1025,7 +975,7 @@ __global__ __launch_bounds__(64 * kCsWaves) void ct_miss_slice_kernel(CollapseAr
         } else {
             for (int v = lane; v < NPo; v += 64) Co[v] = (first ? Cfp[v] : Co[v]) - Cs[v];
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // (the row is read before the next period overwrites it)
+        wait_lgkmcnt0();                                        // (the row is read before the next period overwrites it)
         __builtin_amdgcn_wave_barrier();
     }
 }

@@ -8,7 +8,6 @@
 
 namespace dfm {
 
-constexpr double kLog2PiF = 1.8378770664093454835606594728112;
 constexpr int kScanThreads = 256;   // meanscan workgroup: 256 / R lane groups = time chunks
 __host__ __device__ constexpr int cov_threads(int R) { (void)R; return 64; }
 // levels of the carry scan over the 256 / R chunks, and matrices kept per replicate in `stead`:
@@ -215,7 +214,7 @@ __device__ __forceinline__ void cov_body(const FastArgs& a, int wave_first, doub
         for (int j = 0; j < R; ++j) a.PT[mo + j] = Ps[j];
         if (i == 0) {
             const double LD = log(detOmT) + log(detP0) + (double)T * log(detQ) - sum_ldz;
-            a.llc[b] = (double)a.N * (double)T * kLog2PiF + (double)T * (CPL2 > 0 ? ldfull_b : a.ldfull[b]) + LD + q0;
+            a.llc[b] = (double)a.N * (double)T * kLog2Pi + (double)T * (CPL2 > 0 ? ldfull_b : a.ldfull[b]) + LD + q0;
             a.E[b] = E;
         }
     }

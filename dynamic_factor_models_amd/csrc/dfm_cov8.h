@@ -136,7 +136,7 @@ __device__ __forceinline__ void cov_grid(const FastArgs& a, int b, double Cel, d
     if (lane == 0) {
         const double sum_ldz = -(detprod.log_value() + (double)(T - E) * log(detM_last));
         const double LD = log(detOmT) + log(detP0) + (double)T * log(detQ) - sum_ldz;
-        o.llc[0] = (double)a.N * (double)T * kLog2PiF + (double)T * ldfull + LD + q0;
+        o.llc[0] = (double)a.N * (double)T * kLog2Pi + (double)T * ldfull + LD + q0;
         o.E[0] = E;
     }
 

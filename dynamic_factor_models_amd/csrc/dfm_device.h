@@ -3,9 +3,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dfm_lds.h"   // LDS aliases, the LDS-DMA statement, counted waits, the LDS-only barrier
+
 namespace dfm {
 
 constexpr int kWave = 64;
+constexpr double kLog2Pi = 1.8378770664093454835606594728112;
 
 // "hipFuncSetAttribute(MaxDynamicSharedMemorySize) done" per DEVICE: the attribute belongs to the function on the current
 // device, and the multi-GPU library object (multi.hip) launches the same kernels from one process on several devices, from
@@ -34,6 +37,12 @@ __device__ __forceinline__ double dpp_mov(double v) {
     int lo = __double2loint(v), hi = __double2hiint(v);
     lo = __builtin_amdgcn_mov_dpp(lo, CTRL, 0xF, 0xF, true);
     hi = __builtin_amdgcn_mov_dpp(hi, CTRL, 0xF, 0xF, true);
+    return __hiloint2double(hi, lo);
+}
+// value of lane `src` (wave-uniform) in every lane: two v_readlane, the result lives in SGPRs
+__device__ __forceinline__ double uniform_lane(double v, int src) {
+    const int lo = __builtin_amdgcn_readlane(__double2loint(v), src);
+    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), src);
     return __hiloint2double(hi, lo);
 }
 constexpr int kDppXor1 = 0xB1;         // quad_perm [1,0,3,2]

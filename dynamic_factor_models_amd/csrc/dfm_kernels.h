@@ -32,7 +32,7 @@ inline const char* diag_env(const char* name) { return getenv(name); }
 inline const char* diag_env(const char*) { return nullptr; }
 #endif
 
-// Non-temporal hint on a kernel's ONE-PASS panel stream (pass_fused.hip dma16f, mstep_mfma.hip): on for batches whose panels are
+// Non-temporal hint on a kernel's ONE-PASS panel stream (dfm_lds.h dma16_stream: pass_fused.hip, mstep_mfma.hip): on for batches whose panels are
 // <= 2 GiB, where part of the pass's working set survives in the 256-MB Infinity Cache between launches (measured gains up to
 // B = 4096 at the C2 shape, a loss at 8192).  DFM_DMA_NT=0 | 1 (diagnostics build) overrides.
 inline bool stream_nt_hint(size_t panel_bytes) {

@@ -151,4 +151,32 @@ __device__ inline int psd_root(const double* M, int n, double* L, double tol_rel
     return dropped;
 }
 
+// ---- 16 x 16 matrices on the fp64 matrix pipe (recursion_mbf16.hip, recursion_comp.hip): one v4d per lane in the D layout of
+// v_mfma_f64_16x16x4_f64 -- lane l = 16 g + c holds rows 4 g .. 4 g + 3 of column c.
+__device__ __forceinline__ v4d mm1(double a, double b, v4d acc) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0); }
+__device__ __forceinline__ double row_sum16(double v) {          // sum over the 16 lanes of a row group, in every lane of it
+    v += xor_lane<1>(v); v += xor_lane<2>(v); v += xor_lane<4>(v); v += xor_lane<8>(v);
+    return v;
+}
+__device__ __forceinline__ double col_sum4(double v) {           // sum over the 4 row groups (lanes c, c + 16, c + 32, c + 48)
+    v += xor_lane<16>(v); v += xor_lane<32>(v);
+    return v;
+}
+// sqrt(x) and 1 / sqrt(x) of a positive, normal x: v_rsq_f64 refined by two Newton steps, the root by one correction (a pivot of an
+// SPD matrix: no scaling, no fix-up -- the IEEE sqrt + division pair is ~35 instructions on a chain that is nothing but such pivots)
+__device__ __forceinline__ void fast_sqrt_rsqrt(double x, double& s, double& r) {
+    r = __builtin_amdgcn_rsq(x);
+    r = fma(0.5 * r, fma(-x * r, r, 1.0), r);
+    r = fma(0.5 * r, fma(-x * r, r, 1.0), r);
+    s = x * r;
+    s = fma(0.5 * r, fma(-s, s, x), s);
+}
+// x[q], q run-time: selects, no indexing.  The operands are PRVALUES -- unary plus: `q == 0 ? x[0] : x[1]` on lvalues is an lvalue, clang
+// emits a select of ADDRESSES and one load, the array then stays in scratch memory behind a dynamic offset, and every pick is a scratch
+// round trip behind an s_waitcnt vmcnt(0).
+__device__ __forceinline__ double pick4(const double (&x)[4], int q) {
+    const double a0 = +x[0], a1 = +x[1], a2 = +x[2], a3 = +x[3];
+    return q == 0 ? +a0 : q == 1 ? +a1 : q == 2 ? +a2 : +a3;
+}
+
 }  // namespace dfm

@@ -22,7 +22,6 @@
 namespace dfm {
 
 namespace {
-typedef double eu_v4 __attribute__((ext_vector_type(4)));
 }
 
 template <int R>
@@ -53,7 +52,7 @@ __global__ __launch_bounds__(R * R) void em_update_grid_kernel(EmUpdArgs a) {
         const int k4 = lane >> 4, c16 = lane & 15;
         const int steps = (T + 3) / 4, sps = (steps + NSL - 1) / NSL;
         const int s_lo = sl * sps, s_hi = (s_lo + sps < steps) ? s_lo + sps : steps;
-        eu_v4 a11 = {0.0, 0.0, 0.0, 0.0}, a10 = {0.0, 0.0, 0.0, 0.0};
+        v4d a11 = {0.0, 0.0, 0.0, 0.0}, a10 = {0.0, 0.0, 0.0, 0.0};
         for (int s0 = s_lo; s0 < s_hi; s0 += 8) {
             double av[8], bv[8], pv[8];
 #pragma unroll

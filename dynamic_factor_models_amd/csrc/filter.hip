@@ -219,7 +219,7 @@ __global__ __launch_bounds__(64) void filter_kernel(FtArgs a) {
                 }
                 double q = 0.0;
                 for (int i = 0; i < r; ++i) q += stv[i];
-                ll = -0.5 * ((double)n * 1.8378770664093454835606594728112 + (part ? a.ldrow[bt] : a.ldfull[b]) + a.scol[bt] + q);
+                ll = -0.5 * ((double)n * kLog2Pi + (part ? a.ldrow[bt] : a.ldfull[b]) + a.scol[bt] + q);
                 __syncthreads();
                 for (int e = tid; e < k * k; e += 64) {
                     const int i = e / k, j = e % k;

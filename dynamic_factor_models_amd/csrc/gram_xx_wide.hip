@@ -18,24 +18,6 @@ namespace dfm {
 
 namespace {
 
-using lds_char_ptr_gx = __attribute__((address_space(3))) char*;
-using lds_cvd_ptr_gx = const volatile __attribute__((address_space(3))) double*;
-__device__ __forceinline__ double lds_read64g(unsigned a) { return *(lds_cvd_ptr_gx)(size_t)a; }
-typedef double gx_v4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void dma16gx(const void* gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %2\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, off\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(gsrc), "s"(lds_dst)
-        : "memory");
-}
-
 constexpr int kGxSer = 128;                               // series per block
 constexpr int kGxPer = 16;                                // periods per stage
 constexpr int kGxSteps = kGxPer / 4;
@@ -70,7 +52,7 @@ __global__ __launch_bounds__(kGxThreads) void gram_xx_wide_kernel(PcaArgs a, int
         // ---- producers: rows 4 p .. 4 p + 3 of both blocks of a stage, one DMA per row (lane l = series 2 l, 2 l + 1 of the block)
         const int pw = wave - kGxCompute;
         __builtin_amdgcn_s_setprio(3);
-        const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lds_char_ptr_gx)(smem));
+        const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lds_char_ptr)(smem));
         const bool acti = si + 2 * lane < N, actj = sj + 2 * lane < N;   // (lane 0 is active in both: every DMA is issued)
         auto issue = [&](int st, int bsel) {
             const unsigned sbase = lds0 + (unsigned)bsel * kGxStageB;
@@ -82,16 +64,16 @@ __global__ __launch_bounds__(kGxThreads) void gram_xx_wide_kernel(PcaArgs a, int
                 const char* rowp = reinterpret_cast<const char*>(X + (size_t)t * N);
                 const unsigned dsti = __builtin_amdgcn_readfirstlane(sbase + (unsigned)row * kGxRowB);
                 const unsigned dstj = __builtin_amdgcn_readfirstlane(sbase + kGxBlockB + (unsigned)row * kGxRowB);
-                if (acti) dma16gx(rowp + (size_t)(si + 2 * lane) * 8, dsti);
-                if (actj) dma16gx(rowp + (size_t)(sj + 2 * lane) * 8, dstj);
+                if (acti) dma16(rowp + (size_t)(si + 2 * lane) * 8, dsti);
+                if (actj) dma16(rowp + (size_t)(sj + 2 * lane) * 8, dstj);
             }
         };
         issue(0, 0);
         if (nst > 1) issue(1, 1);
         int bsel = 0;
         for (int q = 0; q < nst; ++q) {
-            if (q + 1 < nst) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kGxPerStage) : "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            if (q + 1 < nst) wait_vmcnt<kGxPerStage>();
+            else wait_vmcnt<0>();
             __syncthreads();                                  // stage q has landed; every consumer is done with stage q - 1
             if (q + 2 < nst) issue(q + 2, bsel == 0 ? 2 : bsel - 1);
             bsel = bsel == 2 ? 0 : bsel + 1;
@@ -101,12 +83,12 @@ __global__ __launch_bounds__(kGxThreads) void gram_xx_wide_kernel(PcaArgs a, int
 
     // ---- consumers: wave w = rows 16 w .. 16 w + 15 of block bi, all 8 column tiles of block bj
     const int k4 = lane >> 4, c16 = lane & 15;
-    const unsigned ldsc = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lds_char_ptr_gx)(smem));
+    const unsigned ldsc = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lds_char_ptr)(smem));
     const unsigned a_off = (unsigned)k4 * kGxRowB + (unsigned)(16 * wave + c16) * 8u;
     const unsigned b_off = kGxBlockB + (unsigned)k4 * kGxRowB + (unsigned)c16 * 8u;
-    gx_v4 acc[8];
+    v4d acc[8];
 #pragma unroll
-    for (int ct = 0; ct < 8; ++ct) acc[ct] = gx_v4{0.0, 0.0, 0.0, 0.0};
+    for (int ct = 0; ct < 8; ++ct) acc[ct] = v4d{0.0, 0.0, 0.0, 0.0};
     int bsel = 0;
     for (int q = 0; q < nst; ++q) {
         __syncthreads();
@@ -115,9 +97,9 @@ __global__ __launch_bounds__(kGxThreads) void gram_xx_wide_kernel(PcaArgs a, int
         double av[kGxSteps], bv[kGxSteps][8];
 #pragma unroll
         for (int s = 0; s < kGxSteps; ++s) {
-            av[s] = lds_read64g(stg + a_off + (unsigned)s * (4 * kGxRowB));
+            av[s] = lds_read64(stg + a_off + (unsigned)s * (4 * kGxRowB));
 #pragma unroll
-            for (int ct = 0; ct < 8; ++ct) bv[s][ct] = lds_read64g(stg + b_off + (unsigned)s * (4 * kGxRowB) + (unsigned)ct * 128u);
+            for (int ct = 0; ct < 8; ++ct) bv[s][ct] = lds_read64(stg + b_off + (unsigned)s * (4 * kGxRowB) + (unsigned)ct * 128u);
         }
 #pragma unroll
         for (int s = 0; s < kGxSteps; ++s) {

@@ -92,7 +92,6 @@ __device__ __forceinline__ bool chol_solve_packed(const double (&S)[R * (R + 1) 
 // (its 64 series as 4 row tiles, the NP packed entries as ET = ceil(NP / 16) column tiles; 0 / 1 operands are exact in fp64, so the sums
 // are the same numbers in another order); the NP mod 16 entries beyond the full tiles stay with the VALU.  The A operands (the lanes' own NaN tests, as bytes) and the B operands (E_t, already in
 // the LDS tile) arrive by 4 + ET LDS reads per block.  The VALU keeps Sxf, Sxx and the counts.
-typedef double mx_v4 __attribute__((ext_vector_type(4)));
 template <int R, int CPL, bool REGD, bool MX = false>
 __global__ __launch_bounds__(256, (MX ? 2 : 1)) void mstep_lam_kernel(MstepArgs a) {
     constexpr int NP = R * (R + 1) / 2;
@@ -137,11 +136,11 @@ __global__ __launch_bounds__(256, (MX ? 2 : 1)) void mstep_lam_kernel(MstepArgs 
     __shared__ unsigned char mkS[MX ? UN * 256 : 1];          // MX: the group's NaN tests, [period][series]
     __shared__ double Dl[MX ? 64 * (NP + 1) : 1];             // MX: a wave's sums on their way back to the lanes that own the series
     static_assert(!MX || UN % 4 == 0, "blocks of 4 periods");
-    mx_v4 macc[MX ? 4 : 1][MX ? ET : 1];
+    v4d macc[MX ? 4 : 1][MX ? ET : 1];
 #pragma unroll
     for (int st = 0; st < (MX ? 4 : 1); ++st)
 #pragma unroll
-        for (int et = 0; et < (MX ? ET : 1); ++et) macc[st][et] = mx_v4{0.0, 0.0, 0.0, 0.0};
+        for (int et = 0; et < (MX ? ET : 1); ++et) macc[st][et] = v4d{0.0, 0.0, 0.0, 0.0};
     const int mlane = tid & 63, mk4 = mlane >> 4, mc16 = mlane & 15, mwave = tid >> 6;
     const int ngroups = (T + UN - 1) / UN;
     double xn[UN][CPL], mn[NLD];
@@ -186,7 +185,7 @@ __global__ __launch_bounds__(256, (MX ? 2 : 1)) void mstep_lam_kernel(MstepArgs 
         }
         // (workgroup barriers that order LDS traffic only: __syncthreads() also drains the vector-memory counter, i.e. it would
         // wait for the rows of the next group that are requested in between)
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        lds_barrier();
         if (g + 1 < ngroups) issue(g + 1);
         // E_t = f_t f_t' + P_t once per period, in place of P_t in the tile: it is the same for every series (every lane of every
         // wave used to recompute the 36 products for each of its missing cells -- half of the masked update's instructions)
@@ -201,7 +200,7 @@ __global__ __launch_bounds__(256, (MX ? 2 : 1)) void mstep_lam_kernel(MstepArgs 
                 mb[UN * R + e] = fma(mb[u * R + i], mb[u * R + jj], mb[UN * R + e]);
             }
         }
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        lds_barrier();
         if constexpr (MX) {
             // the masked update of the group's UN periods on the matrix pipe (see the head of the kernel); periods past the sample: 0
 #pragma unroll
@@ -209,7 +208,7 @@ __global__ __launch_bounds__(256, (MX ? 2 : 1)) void mstep_lam_kernel(MstepArgs 
                 const double x = xv[u][0];
                 mkS[u * 256 + tid] = (t0 + u < T && tid < N && x != x) ? 1 : 0;
             }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // (the wave reads back its own columns: LDS serves a wave in order)
+            wait_lgkmcnt0();                                     // (the wave reads back its own columns: LDS serves a wave in order)
 #pragma unroll
             for (int blk = 0; blk < UN / 4; ++blk) {
                 const int u = 4 * blk + mk4;
@@ -303,7 +302,7 @@ __global__ __launch_bounds__(256, (MX ? 2 : 1)) void mstep_lam_kernel(MstepArgs 
                             const int e = 16 * et + mc16;
                             if (e < NP) Dl[(16 * st + mk4 + 4 * v) * (NP + 1) + e] = macc[st][et][v];
                         }
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                wait_lgkmcnt0();
 #pragma unroll
                 for (int v = 0; v < 16 * ET; ++v) dm[0][v] = Dl[mlane * (NP + 1) + v];
             }

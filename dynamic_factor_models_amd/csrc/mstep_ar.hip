@@ -253,7 +253,6 @@ __global__ __launch_bounds__(256) void mstep_ar_kernel(ArMstepArgs a) {
 // series-fastest so that ar_solve_kernel (a thread per series: the r x r and q x q solves of the old kernel) reads it coalesced.
 namespace {
 
-typedef double ar_v4 __attribute__((ext_vector_type(4)));
 
 // (ArGeo<R, Q1>, kArTC, kArPF, the tiles of a wave and the workspace arithmetic: dfm_argeom.h)
 
@@ -268,11 +267,11 @@ __device__ __forceinline__ void ar_mom_body(const ArMstepArgs& a, const double* 
     const int tid = threadIdx.x, lane = tid & 63, k4 = lane >> 4, c16 = lane & 15;
     const double* xb = a.panel + (size_t)b * T * N;
     const double* Vb = V + (size_t)b * Tq * VW;
-    ar_v4 acc[SGW][NT > 0 ? NT : 1];
+    v4d acc[SGW][NT > 0 ? NT : 1];
 #pragma unroll
     for (int g = 0; g < SGW; ++g)
 #pragma unroll
-        for (int x = 0; x < (NT > 0 ? NT : 1); ++x) acc[g][x] = ar_v4{0.0, 0.0, 0.0, 0.0};
+        for (int x = 0; x < (NT > 0 ? NT : 1); ++x) acc[g][x] = v4d{0.0, 0.0, 0.0, 0.0};
     double xx[SGW][G::NXX], nn[SGW];
 #pragma unroll
     for (int g = 0; g < SGW; ++g) {

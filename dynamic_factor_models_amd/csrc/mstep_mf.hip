@@ -24,7 +24,6 @@ namespace dfm {
 
 namespace {
 
-typedef double mf_v4 __attribute__((ext_vector_type(4)));
 
 constexpr int kMfU = 4;                                        // matrix steps (of 4 periods) loaded together, one group ahead
 
@@ -102,9 +101,9 @@ __global__ __launch_bounds__(256) void mf_moments_kernel(MfMstepArgs a, const do
     const double* __restrict__ xb = a.panel + (size_t)b * T * N + xcol;
     const size_t vstride = (size_t)a.C * VW;
     const double* __restrict__ Vb = V + ((size_t)b * T * a.C + cls) * VW + c16;
-    mf_v4 acc[TT];
+    v4d acc[TT];
 #pragma unroll
-    for (int x = 0; x < TT; ++x) acc[x] = mf_v4{0.0, 0.0, 0.0, 0.0};
+    for (int x = 0; x < TT; ++x) acc[x] = v4d{0.0, 0.0, 0.0, 0.0};
     double nn = 0.0, sxx = 0.0;
     double xq[kMfU], bq[kMfU][TT];
     auto load = [&](int g) {

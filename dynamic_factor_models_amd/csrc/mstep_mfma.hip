@@ -21,35 +21,6 @@
 
 namespace dfm {
 
-using lds_char_ptr_ms = __attribute__((address_space(3))) char*;
-__device__ __forceinline__ void dma16s(const void* gsrc, unsigned lds_dst, bool nt) {   // nt: see pass_fused.hip dma16f
-    unsigned keep;
-    if (nt) {
-        asm volatile(
-            "s_mov_b32 %0, m0\n\t"
-            "s_mov_b32 m0, %2\n\t"
-            "s_nop 0\n\t"
-            "global_load_lds_dwordx4 %1, off nt\n\t"
-            "s_mov_b32 m0, %0"
-            : "=&s"(keep)
-            : "v"(gsrc), "s"(lds_dst)
-            : "memory");
-    } else {
-        asm volatile(
-            "s_mov_b32 %0, m0\n\t"
-            "s_mov_b32 m0, %2\n\t"
-            "s_nop 0\n\t"
-            "global_load_lds_dwordx4 %1, off\n\t"
-            "s_mov_b32 m0, %0"
-            : "=&s"(keep)
-            : "v"(gsrc), "s"(lds_dst)
-            : "memory");
-    }
-}
-template <int K>
-__device__ __forceinline__ void wait_vms() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"i"(K) : "memory");
-}
 
 template <int R>
 struct MsGeo {
@@ -113,7 +84,7 @@ __global__ __launch_bounds__(256, 2) void mstep_mfma_kernel(MstepArgs a, unsigne
     const unsigned ringB = NS * SB + NB * FB;                // period slots, then the factor blocks of the NB row blocks
     const char* ring = smem + (size_t)wave * ringB;
     const unsigned ring_lds =
-        __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lds_char_ptr_ms)(smem)) + (unsigned)wave * ringB;
+        __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lds_char_ptr)(smem)) + (unsigned)wave * ringB;
     const unsigned lane16 = 16u * lane;
     bool pact[NDR];
 #pragma unroll
@@ -123,7 +94,7 @@ __global__ __launch_bounds__(256, 2) void mstep_mfma_kernel(MstepArgs a, unsigne
         const unsigned dst = __builtin_amdgcn_readfirstlane(ring_lds + (unsigned)slot * SB);
 #pragma unroll
         for (int p = 0; p < NDR; ++p)
-            if (pact[p]) dma16s(src + 1024 * p, dst + 1024u * p, dma_nt != 0);
+            if (pact[p]) dma16_stream(src + 1024 * p, dst + 1024u * p, dma_nt != 0);
     };
     // the factors of row block j (periods 4j .. 4j+3, R doubles each, contiguous) ride the same DMA stream into the
     // block's slot of the factor ring -- every load of the steady state is an LDS-DMA, so one counted vmcnt orders them
@@ -131,7 +102,7 @@ __global__ __launch_bounds__(256, 2) void mstep_mfma_kernel(MstepArgs a, unsigne
     auto issue_f = [&](int j, int bslot_) {
         const unsigned dst = __builtin_amdgcn_readfirstlane(ring_lds + NS * SB + (unsigned)bslot_ * FB);
         const int row = 4 * j + (int)(lane16 / (8u * R));
-        if (lane16 < FB && row < nrows) dma16s(fbytes + (size_t)j * FB + lane16, dst, false);   // (the factors were just written: they are wanted in cache)
+        if (lane16 < FB && row < nrows) dma16(fbytes + (size_t)j * FB + lane16, dst);           // (the factors were just written: they are wanted in cache)
     };
     int issued = 0;
     if (nrows > 0) {
@@ -165,9 +136,9 @@ __global__ __launch_bounds__(256, 2) void mstep_mfma_kernel(MstepArgs a, unsigne
         const int r0 = bk * 4;
         if constexpr (MODE <= 1) {
             constexpr int KW = (NB - 1) * (4 * NDR + 1);   // the row blocks issued after this one: periods + factors
-            wait_vms<(KW <= 63 ? KW : 63)>();
+            wait_vmcnt<(KW <= 63 ? KW : 63)>();
         } else {
-            wait_vms<0>();
+            wait_vmcnt<0>();
         }
         const char* blkbase = ring + (unsigned)bslot * 4u * SB;
         const char* pa = blkbase + lane_off;
@@ -183,7 +154,7 @@ __global__ __launch_bounds__(256, 2) void mstep_mfma_kernel(MstepArgs a, unsigne
             for (int j = 0; j < NQ; ++j)
                 xq[rr][j] = pact[j] ? *reinterpret_cast<const double2*>(pq + (unsigned)rr * SB + 1024u * j) : make_double2(0.0, 0.0);
         const double fb = *reinterpret_cast<const double*>(ring + NS * SB + (unsigned)bslot * FB + ((unsigned)K * R + (unsigned)(fcol < R ? fcol : 0)) * 8u);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_lgkmcnt0();
         if constexpr (MODE == 0) {
 #pragma unroll
             for (int rr = 0; rr < 4; ++rr) issue_row(issued + rr, bslot * 4 + rr);
@@ -232,7 +203,7 @@ __global__ __launch_bounds__(256, 2) void mstep_mfma_kernel(MstepArgs a, unsigne
             bslot = (bslot + 1 == NB) ? 0 : bslot + 1;
         }
     }
-    wait_vms<0>();
+    wait_vmcnt<0>();
     // partial sums of this segment: fold the duplicate... (each (series, factor) lives in exactly one lane) and store
     double* ps = part_sxf + ((size_t)b * wpr + segi) * (size_t)N * R;
 #pragma unroll

@@ -29,23 +29,8 @@ namespace dfm {
 
 namespace {
 
-using lds_char_ptr_mm = __attribute__((address_space(3))) char*;
 using lds_cvd_ptr_mm = const __attribute__((address_space(3))) double*;   // (not volatile: a "memory" clobber follows every barrier)
 __device__ __forceinline__ double lds_read64mm(unsigned a) { return *(lds_cvd_ptr_mm)(size_t)a; }
-typedef double mm_v4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void dma16mm(const void* gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %2\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, off\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(gsrc), "s"(lds_dst)
-        : "memory");
-}
 
 constexpr int kMmWaves = 8;
 // s_waitcnt vmcnt(n) for a wave-uniform n known only at run time (the immediate must be a constant): n in 0 .. 12
@@ -158,9 +143,7 @@ __global__ __launch_bounds__(256) void mmw_vec_kernel(MstepArgs a, double* __res
 // two counters and the one that is not chosen exits at once (no host round trip).
 constexpr int kMlKP = 16, kMlSer = 128, kMlMaxU = 4, kMlWaves = 16;
 
-typedef double mm_v2 __attribute__((ext_vector_type(2)));
-using lds_cv2_ptr_mm = const __attribute__((address_space(3))) mm_v2*;
-__device__ __forceinline__ mm_v2 lds_read128mm(unsigned a) { return *(lds_cv2_ptr_mm)(size_t)a; }
+__device__ __forceinline__ v2d lds_read128mm(unsigned a) { return *(lds_cv2_ptr)(size_t)a; }
 
 __device__ __forceinline__ bool list_route(const unsigned* share, unsigned thr_pct) {
     return (unsigned long long)share[0] * 100ull <= (unsigned long long)share[1] * (unsigned long long)thr_pct;
@@ -200,7 +183,7 @@ __global__ __launch_bounds__(64 * kMlWaves) void mstep_miss_list_kernel(MstepArg
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int k4 = lane >> 4, c16 = lane & 15;
-    const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lds_char_ptr_mm)(smem));
+    const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lds_char_ptr)(smem));
     const int nst = (T + KP - 1) / KP;
     const int tt16 = g.tt16;
     const int ND = KP * (1 + g.nv);
@@ -245,22 +228,22 @@ __global__ __launch_bounds__(64 * kMlWaves) void mstep_miss_list_kernel(MstepArg
                     const unsigned dst = sbase + (cdU[u] & 0xffffu);
                     const unsigned pc = cdU[u] >> 24;
                     if (pc == 0) {
-                        if (okP) dma16mm(Xl + (size_t)t * rowXB, dst);
+                        if (okP) dma16(Xl + (size_t)t * rowXB, dst);
                     } else {
                         const unsigned o = 1024u * (pc - 1u);
-                        if (o + 16u * (unsigned)lane < g.vrowB) dma16mm(Vl + ((size_t)t * g.vrowB + o), dst);
+                        if (o + 16u * (unsigned)lane < g.vrowB) dma16(Vl + ((size_t)t * g.vrowB + o), dst);
                     }
                 }
             }
         };
-        mm_v2 acc[8][NR];
+        v2d acc[8][NR];
 #pragma unroll
         for (int j = 0; j < 8; ++j)
 #pragma unroll
-            for (int k = 0; k < NR; ++k) acc[j][k] = mm_v2{0.0, 0.0};
-        mm_v4 accf[NTF];
+            for (int k = 0; k < NR; ++k) acc[j][k] = v2d{0.0, 0.0};
+        v4d accf[NTF];
 #pragma unroll
-        for (int x = 0; x < NTF; ++x) accf[x] = mm_v4{0.0, 0.0, 0.0, 0.0};
+        for (int x = 0; x < NTF; ++x) accf[x] = v4d{0.0, 0.0, 0.0, 0.0};
         double qs = 0.0, nc = 0.0;
         const int sw = s0 + 8 * wave;                         // the walk's first series
         const int sd = s0 + 16 * dt;                          // the dense tile's first series
@@ -315,13 +298,13 @@ __global__ __launch_bounds__(64 * kMlWaves) void mstep_miss_list_kernel(MstepArg
             for (int j = 0; j < 8; ++j) {
                 unsigned m = (unsigned)(bal[j >> 2] >> (16 * (j & 3))) & 0xffffu;
                 if (m) {
-                    mm_v2 cur[NR];
+                    v2d cur[NR];
                     unsigned ad = vb + (unsigned)__builtin_ctz(m) * g.vstride;
                     m &= m - 1u;
 #pragma unroll
                     for (int k = 0; k < NR; ++k) cur[k] = lds_read128mm(ad + 1024u * (unsigned)k);
                     while (m) {
-                        mm_v2 nx[NR];
+                        v2d nx[NR];
                         ad = vb + (unsigned)__builtin_ctz(m) * g.vstride;
                         m &= m - 1u;
 #pragma unroll
@@ -343,7 +326,7 @@ __global__ __launch_bounds__(64 * kMlWaves) void mstep_miss_list_kernel(MstepArg
 #pragma unroll
                 for (int k = 0; k < NR; ++k) {
                     const int col = 128 * k + 2 * lane;
-                    if (col < g.ntm16) *reinterpret_cast<mm_v2*>(orow + col) = acc[j][k];
+                    if (col < g.ntm16) *reinterpret_cast<v2d*>(orow + col) = acc[j][k];
                 }
             }
         }
@@ -402,7 +385,7 @@ __global__ __launch_bounds__(64 * kMmWaves) void mstep_miss_kernel(MstepArgs a, 
     const int tile0 = cgi * g.tpw;
     const int ntile = (g.tt - tile0 < g.tpw) ? g.tt - tile0 : g.tpw;   // tiles of this wave
     const int k4 = lane >> 4, c16 = lane & 15;
-    const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lds_char_ptr_mm)(smem));
+    const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lds_char_ptr)(smem));
     const int nst = (T + KP - 1) / KP;
     const int tt16 = g.tt * 16;
     const int ND = KP * (1 + g.nv);
@@ -436,17 +419,17 @@ __global__ __launch_bounds__(64 * kMmWaves) void mstep_miss_kernel(MstepArgs a, 
                 if (piece == 0) {
                     const int ser = s0 + 2 * lane;
                     const unsigned dst = __builtin_amdgcn_readfirstlane(sbase + (unsigned)per * g.pstride);
-                    if (2 * lane < g.ser && ser < N) dma16mm(Xb + ((size_t)t * N + ser) * 8, dst);
+                    if (2 * lane < g.ser && ser < N) dma16(Xb + ((size_t)t * N + ser) * 8, dst);
                 } else {
                     const unsigned o = 1024u * (unsigned)(piece - 1) + 16u * (unsigned)lane;
                     const unsigned dst = __builtin_amdgcn_readfirstlane(sbase + g.panelB + (unsigned)per * g.vstride + 1024u * (unsigned)(piece - 1));
-                    if (o < g.vrowB) dma16mm(Vb + (size_t)t * g.vrowB + o, dst);
+                    if (o < g.vrowB) dma16(Vb + (size_t)t * g.vrowB + o, dst);
                 }
             }
         };
-        mm_v4 acc[TPW];
+        v4d acc[TPW];
 #pragma unroll
-        for (int x = 0; x < TPW; ++x) acc[x] = mm_v4{0.0, 0.0, 0.0, 0.0};
+        for (int x = 0; x < TPW; ++x) acc[x] = v4d{0.0, 0.0, 0.0, 0.0};
         double qs = 0.0, nc = 0.0;
         const bool ser_ok = s0 + 16 * sgi + c16 < N;
         const unsigned a_off = (unsigned)k4 * g.pstride + (unsigned)(16 * sgi + c16) * 8u;

@@ -29,41 +29,6 @@ namespace dfm {
 
 namespace {
 
-using lds_char_ptr_mw = __attribute__((address_space(3))) char*;
-using lds_cvd_ptr_mw = const volatile __attribute__((address_space(3))) double*;
-__device__ __forceinline__ double lds_read64m(unsigned a) { return *(lds_cvd_ptr_mw)(size_t)a; }
-typedef double mw_v4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void dma16mw(const void* gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %2\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, off\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(gsrc), "s"(lds_dst)
-        : "memory");
-}
-
-// the PANEL rows (development A/B: -DDFM_MW_PANEL_MOD='" nt"'); the factor rows are re-read by the 8 series blocks of a replicate
-#ifndef DFM_MW_PANEL_MOD
-#define DFM_MW_PANEL_MOD ""
-#endif
-__device__ __forceinline__ void dma16mwp(const void* gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %2\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, off" DFM_MW_PANEL_MOD "\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(gsrc), "s"(lds_dst)
-        : "memory");
-}
-
 constexpr int kMwR = 32;
 constexpr int kMwSer = 128;                              // series per item: 8 consumer waves x 16
 constexpr int kMwPer = 32;                               // periods per stage
@@ -94,7 +59,7 @@ __global__ __launch_bounds__(kMwThreads) void mstep_wide_kernel(MstepArgs a, dou
     const int N = a.N, T = a.T, B = a.B;
     const int nst = (T + kMwPer - 1) / kMwPer;                // stages per item
     volatile int* itemq = reinterpret_cast<volatile int*>(smem + kMwNBuf * kMwStageB);
-    const unsigned itemq_lds = (unsigned)(size_t)(lds_char_ptr_mw)(smem) + kMwNBuf * kMwStageB;
+    const unsigned itemq_lds = (unsigned)(size_t)(lds_char_ptr)(smem) + kMwNBuf * kMwStageB;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int xcd = (int)blockIdx.x & 7;
@@ -140,7 +105,7 @@ __global__ __launch_bounds__(kMwThreads) void mstep_wide_kernel(MstepArgs a, dou
         // row h of the piece rotated by 8 h units of 16 bytes).  Lane 0 of a row DMA is always active: 10 DMAs per stage, always.
         const int pw = wave - kMwCompute;
         __builtin_amdgcn_s_setprio(3);
-        const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lds_char_ptr_mw)(smem));
+        const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lds_char_ptr)(smem));
         auto issue_dma = [&](int b, int sb, int st, int bsel) {
             const char* Xb = reinterpret_cast<const char*>(a.panel + (size_t)b * T * N);
             const char* Fb = reinterpret_cast<const char*>(a.fsm + (size_t)b * T * rd);
@@ -155,7 +120,7 @@ __global__ __launch_bounds__(kMwThreads) void mstep_wide_kernel(MstepArgs a, dou
                 t = t < T ? t : T - 1;
                 const char* src = Xb + ((size_t)t * N + ser) * 8;
                 const unsigned dst = __builtin_amdgcn_readfirstlane(sbase + (unsigned)row * kMwRowB);
-                if (act) dma16mwp(src, dst);
+                if (act) dma16_mw_panel(src, dst);
             }
 #pragma unroll
             for (int u = 0; u < GEO::FPieces; ++u) {
@@ -175,7 +140,7 @@ __global__ __launch_bounds__(kMwThreads) void mstep_wide_kernel(MstepArgs a, dou
                     src = Fb + (o < lim ? o : lim);
                 }
                 const unsigned dst = __builtin_amdgcn_readfirstlane(sbase + kMwPanelB + (unsigned)piece * 1024u);
-                dma16mw(src, dst);
+                dma16(src, dst);
             }
         };
         int ii = 0, ist = 0, ikk = read_item(0);
@@ -191,8 +156,8 @@ __global__ __launch_bounds__(kMwThreads) void mstep_wide_kernel(MstepArgs a, dou
         }
         int bsel = 0;
         while (more) {
-            if (!v1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(GEO::PerStage) : "memory");
+            if (!v1) wait_vmcnt<0>();
+            else wait_vmcnt<GEO::PerStage>();
             __syncthreads();
             const bool v2 = ikk >= 0;
             if (v2) issue_next(bsel == 0 ? 2 : bsel - 1);
@@ -206,10 +171,10 @@ __global__ __launch_bounds__(kMwThreads) void mstep_wide_kernel(MstepArgs a, dou
 
     // ---- consumer waves
     const int k4 = lane >> 4, c16 = lane & 15;
-    const unsigned ldsc = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lds_char_ptr_mw)(smem));
+    const unsigned ldsc = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lds_char_ptr)(smem));
     int ci = 0, st = 0, bsel = 0, ckk = read_item(0);
     bool more = ckk >= 0;
-    mw_v4 acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0}, accb = {0.0, 0.0, 0.0, 0.0};
+    v4d acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0}, accb = {0.0, 0.0, 0.0, 0.0};
     double acc4[N4 > 0 ? N4 : 1];
 #pragma unroll
     for (int x = 0; x < (N4 > 0 ? N4 : 1); ++x) acc4[x] = 0.0;
@@ -236,11 +201,11 @@ __global__ __launch_bounds__(kMwThreads) void mstep_wide_kernel(MstepArgs a, dou
         {
             double av[kMwSteps], bv[kMwSteps], bvb[NX == 4 ? kMwSteps : 1], b4v[N4 > 0 ? N4 : 1][kMwSteps];
             auto load_step = [&](int s) {
-                av[s] = lds_read64m(stg + a_off + (unsigned)s * (4 * kMwRowB));
-                bv[s] = lds_read64m(stg + b16 + (unsigned)s * (4u * (unsigned)(rd * 8)));
-                if (NX == 4) bvb[NX == 4 ? s : 0] = lds_read64m(stg + b16b + (unsigned)s * 1024u);
+                av[s] = lds_read64(stg + a_off + (unsigned)s * (4 * kMwRowB));
+                bv[s] = lds_read64(stg + b16 + (unsigned)s * (4u * (unsigned)(rd * 8)));
+                if (NX == 4) bvb[NX == 4 ? s : 0] = lds_read64(stg + b16b + (unsigned)s * 1024u);
 #pragma unroll
-                for (int x = 0; x < N4; ++x) b4v[x][s] = lds_read64m(stg + b4[x] + (unsigned)s * 1024u);
+                for (int x = 0; x < N4; ++x) b4v[x][s] = lds_read64(stg + b4[x] + (unsigned)s * 1024u);
             };
 #pragma unroll
             for (int s = 0; s < 4; ++s) load_step(s);
@@ -259,7 +224,7 @@ __global__ __launch_bounds__(kMwThreads) void mstep_wide_kernel(MstepArgs a, dou
         }
         bsel = bsel == 2 ? 0 : bsel + 1;
         if (++st == nst) {                                    // the item is complete: Sxf rows and Sxx of its series
-            const mw_v4 accs = acc0 + acc1;
+            const v4d accs = acc0 + acc1;
             double* out = sxf + ((size_t)b * N + s0 + 16 * wave) * rd;
 #pragma unroll
             for (int v = 0; v < 4; ++v) {                     // 16x16x4: D[(l / 16) + 4 v][l % 16] -> series k4 + 4 v, factor c16
@@ -279,7 +244,7 @@ __global__ __launch_bounds__(kMwThreads) void mstep_wide_kernel(MstepArgs a, dou
             qs += __shfl_xor(qs, 16, 64);
             qs += __shfl_xor(qs, 32, 64);
             if (k4 == 0 && ser_ok) sxx[(size_t)b * N + s0 + 16 * wave + c16] = qs;
-            acc0 = mw_v4{0.0, 0.0, 0.0, 0.0}; acc1 = acc0; accb = acc0;
+            acc0 = v4d{0.0, 0.0, 0.0, 0.0}; acc1 = acc0; accb = acc0;
 #pragma unroll
             for (int x = 0; x < (N4 > 0 ? N4 : 1); ++x) acc4[x] = 0.0;
             qs = 0.0;

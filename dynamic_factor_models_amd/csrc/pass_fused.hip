@@ -42,48 +42,10 @@
 #include "dfm_kernels.h"
 #include "dfm_scan.h"
 
-// cache-policy modifiers of the streaming LDS-DMA loads (development A/B: -DDFM_DMA_MOD='" nt"', '" sc1"', ...); default: none
-#ifndef DFM_DMA_MOD
-#define DFM_DMA_MOD ""
-#endif
-
 namespace dfm {
 
 namespace {
 
-using lds_char_ptr_f = __attribute__((address_space(3))) char*;
-using lds_double_ptr_f = __attribute__((address_space(3))) double*;
-
-// nt: the non-temporal hint on the panel stream.  The panel is read ONCE per pass; with the hint its lines do not displace the
-// rest of the pass's working set from the 256-MB Infinity Cache -- the outputs (P_smooth, f_smooth: 180 MB per 1024 replicates),
-// which the next pass or the M-step behind this one overwrites or reads again, and the covariance tables.  Measured in one
-// process (profiles/r04/ab_dma_nt_*.txt): +12 % at B = 512, +13..15 % at 1024, +8 % at 1536, +6 % at 2048, +1 % at 4096, -2 % at
-// 8192 (nothing of a 6.6-GB batch stays on chip, and the hint costs the L2 its write-combining of neighbouring rows): the
-// launcher sets it for batches whose panels are <= 2 GiB.
-__device__ __forceinline__ void dma16f(const void* gsrc, unsigned lds_dst, bool nt) {
-    unsigned keep;
-    if (nt) {                                                  // (wave-uniform)
-        asm volatile(
-            "s_mov_b32 %0, m0\n\t"
-            "s_mov_b32 m0, %2\n\t"
-            "s_nop 0\n\t"
-            "global_load_lds_dwordx4 %1, off nt\n\t"
-            "s_mov_b32 m0, %0"
-            : "=&s"(keep)
-            : "v"(gsrc), "s"(lds_dst)
-            : "memory");
-    } else {
-        asm volatile(
-            "s_mov_b32 %0, m0\n\t"
-            "s_mov_b32 m0, %2\n\t"
-            "s_nop 0\n\t"
-            "global_load_lds_dwordx4 %1, off" DFM_DMA_MOD "\n\t"
-            "s_mov_b32 m0, %0"
-            : "=&s"(keep)
-            : "v"(gsrc), "s"(lds_dst)
-            : "memory");
-    }
-}
 // The lane id from the hardware (all lanes active), opaque to the compiler: what is derived from it is derived where it is asked
 // for, not kept -- or spilled -- from the top of the kernel (see the stream role of pass_fused_kernel).
 __device__ __forceinline__ int pf_fresh_lane() {
@@ -91,11 +53,6 @@ __device__ __forceinline__ int pf_fresh_lane() {
     asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
     return l;
 }
-template <int K>
-__device__ __forceinline__ void wait_vmf() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"i"(K) : "memory");
-}
-__device__ __forceinline__ void wait_lgkmf() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
 constexpr int kPfR = 8;
 #ifndef DFM_PF_ECAP
@@ -177,7 +134,7 @@ __device__ __forceinline__ bool pf_wait_ge(const unsigned* f, unsigned target, u
             }
         }
     }
-    if constexpr (kLdsOnly) wait_lgkmf();
+    if constexpr (kLdsOnly) wait_lgkmcnt0();
     else __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     return true;
 }
@@ -254,7 +211,7 @@ struct PfLds {
     unsigned ring;    // nsw x 8 slots x SB bytes
     unsigned total;
     int nsw, ncov, nbuf;
-    int nt;           // non-temporal hint on the panel stream (dma16f)
+    int nt;           // non-temporal hint on the panel stream (dma16_stream)
     int wpark;        // 1: the stream waves' weights come from the fill wave through a park in the b_t buffer (pf_wpark_rule)
     unsigned wpark_off;   // doubles from the start of a b_t buffer to its park: the buffer's highest rows
 };
@@ -754,7 +711,7 @@ __device__ __forceinline__ void pf_weights_finish(int N, int lane, double (&Bw)[
     constexpr int CS = 8;
     const int K = lane >> 4, g = (lane >> 3) & 1;
     const bool tail_clamp = (STEPS - 1) * CS + 4 * g + K >= N;
-    wait_vmf<0>();
+    wait_vmcnt<0>();
 #pragma unroll
     for (int s = 0; s + 1 < STEPS; ++s) Bw[s] = pf_weight(Bw[s], rv[s]);
     Bw[STEPS - 1] = tail_clamp ? 0.0 : pf_weight(Bw[STEPS - 1], rv[STEPS - 1]);
@@ -804,7 +761,7 @@ __device__ __forceinline__ double gram_mfma8(const double* __restrict__ Lg, cons
     // with its use (a full round trip per step -- 5 to 8 us each beside the streaming waves)
     __builtin_amdgcn_sched_barrier(0);
     if (tstamp) {                                                // diagnostics: when the batch of loads has landed
-        wait_vmf<0>();
+        wait_vmcnt<0>();
         if (lane == 0) *tstamp = (double)__builtin_amdgcn_s_memrealtime();
     }
     double ld = 0.0;
@@ -910,7 +867,7 @@ __global__ __launch_bounds__(kPfMaxThreads) void pass_fused_kernel(CollapseArgs 
         const unsigned ringB = NS * SB;
         const char* ring = smem + ly.ring + (size_t)wave * ringB;
         const unsigned ring_lds =
-            __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lds_char_ptr_f)(smem)) + ly.ring + (unsigned)wave * ringB;
+            __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lds_char_ptr)(smem)) + ly.ring + (unsigned)wave * ringB;
         const int nrep = (B - (int)blockIdx.x + G - 1) / G;      // replicates of this workgroup
         const int gtot = nrep * nblk;                            // row blocks of this wave
 
@@ -965,7 +922,7 @@ __global__ __launch_bounds__(kPfMaxThreads) void pass_fused_kernel(CollapseArgs 
                             const unsigned dst = __builtin_amdgcn_readfirstlane(ring_lds + (unsigned)(bslot * 4 + rr) * SB);
 #pragma unroll
                             for (int p = 0; p < NDR; ++p) {
-                                if (pact[p]) dma16f(src + 1024 * p, dst + 1024u * p, dma_nt);
+                                if (pact[p]) dma16_stream(src + 1024 * p, dst + 1024u * p, dma_nt);
                             }
                         }
                     };
@@ -992,23 +949,23 @@ __global__ __launch_bounds__(kPfMaxThreads) void pass_fused_kernel(CollapseArgs 
                         const bool must_wait = wave == 0 && j >= nbuf && (int)(ld_flag(flags + kFScanDone) - (unsigned)(j - nbuf + 1)) < 0;
                         if (must_wait && lane == 0) __hip_atomic_store(flags + kFStreamWaits, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                         if constexpr (kWp) {
-                            if (!pf_wait_ge<true>(flags + kFWReady, (unsigned)(j + 1), flags + kFAbort)) { wait_vmf<0>(); return false; }
+                            if (!pf_wait_ge<true>(flags + kFWReady, (unsigned)(j + 1), flags + kFAbort)) { wait_vmcnt<0>(); return false; }
                         } else {
-                            if (!pf_wait_ge(flags + kFScanDone, (unsigned)(j - nbuf + 1), flags + kFAbort)) { wait_vmf<0>(); return false; }
+                            if (!pf_wait_ge(flags + kFScanDone, (unsigned)(j - nbuf + 1), flags + kFAbort)) { wait_vmcnt<0>(); return false; }
                         }
                         if (must_wait && lane == 0) __hip_atomic_store(flags + kFStreamWaits, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                     }
                     if constexpr (kWp) {                              // no vmcnt wait here: the blocks in flight stay in flight
-                        const lds_double_ptr_f pk = (lds_double_ptr_f)(bt + ly.wpark_off) + lane;
+                        const lds_double_ptr pk = (lds_double_ptr)(bt + ly.wpark_off) + lane;
 #pragma unroll
                         for (int s = 0; s < STEPS; ++s) Bw[s] = pk[s * 64];
 #pragma unroll
                         for (int jq = 0; jq < NQ; ++jq) {             // 1 / R by column: the lane's own pairs, 0 past N
-                            const lds_double_ptr_f pr = pk + STEPS * 64 + lane + 128 * jq;
+                            const lds_double_ptr pr = pk + STEPS * 64 + lane + 128 * jq;
                             rown[jq][0] = pact[jq] ? pr[0] : 0.0;
                             rown[jq][1] = pact[jq] ? pr[1] : 0.0;
                         }
-                        wait_lgkmf();                                 // the values are in registers before the count moves
+                        wait_lgkmcnt0();                              // the values are in registers before the count moves
                         __builtin_amdgcn_wave_barrier();
                         if (lane == 0) __hip_atomic_fetch_add(flags + kFWTaken, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                     }
@@ -1022,12 +979,12 @@ __global__ __launch_bounds__(kPfMaxThreads) void pass_fused_kernel(CollapseArgs 
                         const bool full = r0 + 4 <= nrows;           // (wave-uniform)
                         // from this block on the wave's b_t rows lie in the park of this replicate: everybody has read it?
                         if (kWp && k == kpark) {
-                            if (!pf_wait_ge<true>(flags + kFWTaken, (unsigned)(nact * (j + 1)), flags + kFAbort)) { wait_vmf<0>(); return false; }
+                            if (!pf_wait_ge<true>(flags + kFWTaken, (unsigned)(nact * (j + 1)), flags + kFAbort)) { wait_vmcnt<0>(); return false; }
                         }
                         // rows of this block have landed once at most the DMAs of the NB - 1 YOUNGER blocks are outstanding
                         // (one in-order vmcnt counter per wave); at the tail of the sequence there are fewer younger blocks
-                        if (gidx + NB - 1 < gtot) wait_vmf<((NB - 1) * 4 * NDR <= 63 ? (NB - 1) * 4 * NDR : 63)>();
-                        else wait_vmf<0>();
+                        if (gidx + NB - 1 < gtot) wait_vmcnt<((NB - 1) * 4 * NDR <= 63 ? (NB - 1) * 4 * NDR : 63)>();
+                        else wait_vmcnt<0>();
                         const char* blkbase = ring + (unsigned)bslot * 4u * SB;
                         const char* pa = blkbase + lane_off;
                         double xa[STEPS];
@@ -1042,7 +999,7 @@ __global__ __launch_bounds__(kPfMaxThreads) void pass_fused_kernel(CollapseArgs 
                             for (int jq = 0; jq < NQ; ++jq)
                                 xq[rr][jq] = pact[jq] ? *reinterpret_cast<const double2*>(pq + (unsigned)rr * SB + 1024u * jq)
                                                       : make_double2(0.0, 0.0);
-                        wait_lgkmf();                                        // the reads are done before the slots are re-armed
+                        wait_lgkmcnt0();                                     // the reads are done before the slots are re-armed
                         if (ij < nrep) { issue_block(ij, ik, bslot); advance_issue(); }
                         double D = 0.0, D2 = 0.0;                            // two accumulators: half the dependent MFMA chain
 #pragma unroll
@@ -1081,7 +1038,7 @@ __global__ __launch_bounds__(kPfMaxThreads) void pass_fused_kernel(CollapseArgs 
                     }
                     // this wave's part of b_t is in LDS.  (The release waits for the LDS writes only in effect: the DMAs in
                     // flight belong to the next replicate, so no full vmcnt wait here -- an explicit lgkmcnt wait instead.)
-                    wait_lgkmf();
+                    wait_lgkmcnt0();
                     __builtin_amdgcn_wave_barrier();
                     if (lane == 0) __hip_atomic_fetch_add(flags + kFBtReady + buf, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                     if (wave == 0) stamp(b, 2);
@@ -1093,7 +1050,7 @@ __global__ __launch_bounds__(kPfMaxThreads) void pass_fused_kernel(CollapseArgs 
             if (!(wpark ? replicates(std::true_type{}) : replicates(std::false_type{}))) return;
             // ---- the deferred P_smooth fills: the panel is through, HBM is idle but for the last scan's outputs ----------
             if (ndefer > 0) {
-                wait_vmf<0>();
+                wait_vmcnt<0>();
                 const int lane = pf_fresh_lane();                 // (not the kernel's own: that one would be reloaded from scratch in the loop above)
                 // (nact: the stream waves that own periods -- they all get here)
                 const int npr = fa.r * (fa.r + 1) / 2;
@@ -1235,12 +1192,12 @@ __global__ __launch_bounds__(kPfMaxThreads) void pass_fused_kernel(CollapseArgs 
                     if (!pf_wait_ge(flags + kFScanDone, (unsigned)(jn - 1), flags + kFAbort)) break;
                 }
                 pf_weights_finish<STEPS, NQ>(N, lane, Bw, rv, rown);
-                const lds_double_ptr_f pk = (lds_double_ptr_f)(bt0 + (size_t)(jn & 1) * ly.bt_stride + ly.wpark_off) + lane;
+                const lds_double_ptr pk = (lds_double_ptr)(bt0 + (size_t)(jn & 1) * ly.bt_stride + ly.wpark_off) + lane;
 #pragma unroll
                 for (int s = 0; s < STEPS; ++s) pk[s * 64] = Bw[s];
 #pragma unroll
                 for (int jq = 0; jq < NQ; ++jq) {                 // 1 / R by column (N is even: a pair lies inside N or past it)
-                    const lds_double_ptr_f pr = pk + STEPS * 64 + lane + 128 * jq;
+                    const lds_double_ptr pr = pk + STEPS * 64 + lane + 128 * jq;
                     if (2 * lane + 128 * jq < N) { pr[0] = rown[jq][0]; pr[1] = rown[jq][1]; }
                 }
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");   // the park is written before the counter moves

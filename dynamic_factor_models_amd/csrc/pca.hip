@@ -80,7 +80,6 @@ __global__ __launch_bounds__(kPcaThreads) void gram_xx_kernel(PcaArgs a) {
 // 16 k + j; D[(l / 16) + 4 v][l % 16] in register v of lane l.
 constexpr int kGxThreads = 512;
 constexpr int kGxPB = 32;                     // periods per LDS block
-typedef double gx_v4 __attribute__((ext_vector_type(4)));
 
 template <int MAXP>
 __global__ __launch_bounds__(kGxThreads) void gram_xx_mfma_kernel(PcaArgs a) {
@@ -104,9 +103,9 @@ __global__ __launch_bounds__(kGxThreads) void gram_xx_mfma_kernel(PcaArgs a) {
         while (rem >= NT - bi) { rem -= NT - bi; ++bi; }
         tbi[m] = bi; tbj[m] = bi + rem;
     }
-    gx_v4 acc[MAXP];
+    v4d acc[MAXP];
 #pragma unroll
-    for (int m = 0; m < MAXP; ++m) acc[m] = gx_v4{0.0, 0.0, 0.0, 0.0};
+    for (int m = 0; m < MAXP; ++m) acc[m] = v4d{0.0, 0.0, 0.0, 0.0};
     const int nblk = (T + kGxPB - 1) / kGxPB;
     const int per_thread = (kGxPB * ld + kGxThreads - 1) / kGxThreads;   // LDS doubles each thread stages per block
     // element e of a block: row e / ld, column e % ld
@@ -185,19 +184,6 @@ __global__ __launch_bounds__(kGxThreads) void gram_xx_mfma_kernel(PcaArgs a) {
 // barrier; nothing else moves the panel.  Row stride = 128 bytes (mod 256): the four k-rows of an MFMA step on distinct banks.
 // Columns >= N of the buffers stay zero (zeroed once: the DMAs never write them); the rows of a partial last block are zeroed.
 namespace {
-using lds_char_ptr_gx = __attribute__((address_space(3))) char*;
-__device__ __forceinline__ void dma16gx(const void* gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %2\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, off\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(gsrc), "s"(lds_dst)
-        : "memory");
-}
 __host__ __device__ inline int gx_dma_ld(int N) { const int NT = (N + 15) / 16; return NT * 16 + ((NT & 1) ? 0 : 16); }
 }  // namespace
 
@@ -224,11 +210,11 @@ __global__ __launch_bounds__(kGxThreads) void gram_xx_dma_kernel(PcaArgs a) {
         while (rem >= NT - bi) { rem -= NT - bi; ++bi; }
         tbi[m] = bi; tbj[m] = bi + rem;
     }
-    gx_v4 acc[MAXP];
+    v4d acc[MAXP];
 #pragma unroll
-    for (int m = 0; m < MAXP; ++m) acc[m] = gx_v4{0.0, 0.0, 0.0, 0.0};
+    for (int m = 0; m < MAXP; ++m) acc[m] = v4d{0.0, 0.0, 0.0, 0.0};
     const int nblk = (T + kGxPB - 1) / kGxPB;
-    const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lds_char_ptr_gx)(gx_lds));
+    const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lds_char_ptr)(gx_lds));
     const unsigned bufB = (unsigned)kGxPB * ldB;
     for (int e = tid; e < 2 * kGxPB * ld; e += kGxThreads) gx_lds[e] = 0.0;
     __syncthreads();
@@ -240,7 +226,7 @@ __global__ __launch_bounds__(kGxThreads) void gram_xx_dma_kernel(PcaArgs a) {
                 const char* src = X + (size_t)t * rowB + 16u * (unsigned)lane;
                 const unsigned dst = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)sel * bufB + (unsigned)rr * ldB);
                 for (int pc = 0; pc < npiece; ++pc)
-                    if (16u * (unsigned)lane + 1024u * (unsigned)pc < rowB) dma16gx(src + 1024 * pc, dst + 1024u * (unsigned)pc);
+                    if (16u * (unsigned)lane + 1024u * (unsigned)pc < rowB) dma16(src + 1024 * pc, dst + 1024u * (unsigned)pc);
             } else {                                             // past the sample: a zero row
                 double* row = gx_lds + (size_t)sel * kGxPB * ld + (size_t)rr * ld;
                 for (int c = lane; c < N; c += 64) row[c] = 0.0;
@@ -248,7 +234,7 @@ __global__ __launch_bounds__(kGxThreads) void gram_xx_dma_kernel(PcaArgs a) {
         }
     };
     issue(0, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vmcnt<0>();
     __syncthreads();
     for (int blk = 0; blk < nblk; ++blk) {
         const double* cur = gx_lds + (size_t)(blk & 1) * kGxPB * ld;
@@ -265,7 +251,7 @@ __global__ __launch_bounds__(kGxThreads) void gram_xx_dma_kernel(PcaArgs a) {
                 for (int kk = 0; kk < kGxPB / 4; ++kk) acc[m] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[kk], bv[kk], acc[m], 0, 0, 0);
             }
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // this wave's rows of the next block have landed
+        wait_vmcnt<0>();                                         // this wave's rows of the next block have landed
         __syncthreads();
     }
 #pragma unroll
@@ -353,7 +339,6 @@ __device__ __forceinline__ void chol_lds(double* G, int r) {
 // iteration and four in the tail.)
 template <int R, int NT>
 __device__ __forceinline__ void tall_gram_mfma(double* M, const double* A, const double* Bm, int n, double* part) {
-    typedef double tg_v4 __attribute__((ext_vector_type(4)));
     constexpr int CT = R >= 16 ? R / 16 : 1, NW = NT / 64, NTILE = CT * CT, NSL = NW / NTILE;
     static_assert(NSL >= 1, "one wave per tile at least");
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, k4 = lane >> 4, c16 = lane & 15;
@@ -361,7 +346,7 @@ __device__ __forceinline__ void tall_gram_mfma(double* M, const double* A, const
     const int steps = (n + 3) / 4, sps = (steps + NSL - 1) / NSL;
     const int s_lo = sl * sps, s_hi = s_lo + sps < steps ? s_lo + sps : steps;
     const int pa = 16 * pt + c16, pb = 16 * qt + c16;
-    tg_v4 acc = {0.0, 0.0, 0.0, 0.0};
+    v4d acc = {0.0, 0.0, 0.0, 0.0};
     for (int s0 = s_lo; s0 < s_hi; s0 += 8) {
         double av[8], bv[8];
 #pragma unroll
@@ -864,15 +849,14 @@ __global__ __launch_bounds__(NT, (NT == kPcaFastThreads ? 4 : 1)) void pca_kerne
     // Y <- S V on the matrix pipe: wave w takes the row tiles w, w + NT / 64, ...; per step of 4 columns of S one load of A
     // (S[k][row] = S[row][k]: 128 contiguous bytes per k) and one of B per 16-column tile of V, 8 steps in flight.  (The VALU
     // form -- thread = row, 32 loads of V per 32 FMAs -- took 5 ms per iteration at config 4: 13 GFLOP/s per CU.)
-    typedef double pca_v4 __attribute__((ext_vector_type(4)));
     auto apply_S = [&]() {
         constexpr int CT = R >= 16 ? R / 16 : 1;
         const int lane = tid & 63, wave = tid >> 6, k4 = lane >> 4, c16 = lane & 15;
         const int nrt = (N + 15) / 16, steps = (N + 3) / 4;
         for (int rt = wave; rt < nrt; rt += NT / 64) {
-            pca_v4 acc[CT];
+            v4d acc[CT];
 #pragma unroll
-            for (int ct = 0; ct < CT; ++ct) acc[ct] = pca_v4{0.0, 0.0, 0.0, 0.0};
+            for (int ct = 0; ct < CT; ++ct) acc[ct] = v4d{0.0, 0.0, 0.0, 0.0};
             const int row = 16 * rt + c16, rowc = row < N ? row : N - 1;
             for (int s0 = 0; s0 < steps; s0 += 8) {
                 double av[8], bv[CT][8];
@@ -1040,9 +1024,9 @@ __global__ __launch_bounds__(NT, (NT == kPcaFastThreads ? 4 : 1)) void pca_kerne
                 const int lane = tid & 63, wave = tid >> 6, k4 = lane >> 4, c16 = lane & 15;
                 const int ntt = (T + 15) / 16, steps = (N + 3) / 4;
                 for (int tt = wave; tt < ntt; tt += NT / 64) {
-                    pca_v4 acc[CT];
+                    v4d acc[CT];
 #pragma unroll
-                    for (int ct = 0; ct < CT; ++ct) acc[ct] = pca_v4{0.0, 0.0, 0.0, 0.0};
+                    for (int ct = 0; ct < CT; ++ct) acc[ct] = v4d{0.0, 0.0, 0.0, 0.0};
                     const int trow = 16 * tt + c16, trc = trow < T ? trow : T - 1;
                     for (int s0 = 0; s0 < steps; s0 += 8) {
                         double av[8], bv[CT][8];
@@ -1077,9 +1061,9 @@ __global__ __launch_bounds__(NT, (NT == kPcaFastThreads ? 4 : 1)) void pca_kerne
             const int lane = tid & 63, wave = tid >> 6, k4 = lane >> 4, c16 = lane & 15;
             const int ntt = (T + 15) / 16, steps = (N + 3) / 4;
             for (int tt = wave; tt < ntt; tt += NT / 64) {
-                pca_v4 acc[CT];
+                v4d acc[CT];
 #pragma unroll
-                for (int ct = 0; ct < CT; ++ct) acc[ct] = pca_v4{0.0, 0.0, 0.0, 0.0};
+                for (int ct = 0; ct < CT; ++ct) acc[ct] = v4d{0.0, 0.0, 0.0, 0.0};
                 const int trow = 16 * tt + c16, trc = trow < T ? trow : T - 1;
                 for (int s0 = 0; s0 < steps; s0 += 8) {
                     double av[8], bv[CT][8];

@@ -9,12 +9,12 @@
 
 #include <hip/hip_runtime.h>
 
+#include "dfm_lds.h"
+
 struct dfm_handle;
 namespace dfm { int handle_device(const dfm_handle* h); }   // capi.hip
 
 namespace {
-
-using lds_ptr = __attribute__((address_space(3))) char*;
 
 template <int NSLOT>
 __global__ __launch_bounds__(256) void probe_read_kernel(const char* __restrict__ base, size_t seg, double* out) {
@@ -23,15 +23,13 @@ __global__ __launch_bounds__(256) void probe_read_kernel(const char* __restrict_
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const size_t wg = (size_t)blockIdx.x * 4 + wave;
     const char* src = base + wg * seg + 16 * lane;
-    const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lds_ptr)smem) + wave * NSLOT * 1024;
+    const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(dfm::lds_char_ptr)smem) + wave * NSLOT * 1024;
     const int npiece = (int)(seg / 1024);
     auto issue = [&](int piece, int slot) {
         const int pc = piece < npiece ? piece : npiece - 1;
         const char* g = src + (size_t)pc * 1024;
         const unsigned dst = __builtin_amdgcn_readfirstlane(lds0 + slot * 1024);
-        unsigned keep;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(g), "s"(dst) : "memory");
+        dfm::dma16(g, dst);
     };
 #pragma unroll
     for (int s = 0; s < NSLOT; ++s) issue(s, s);
@@ -39,11 +37,11 @@ __global__ __launch_bounds__(256) void probe_read_kernel(const char* __restrict_
     int slot = 0;
     constexpr int HALF = NSLOT / 2;
     for (int p0 = 0; p0 < npiece; p0 += HALF) {
-        asm volatile("s_waitcnt vmcnt(%0)" ::"i"(NSLOT - HALF) : "memory");
+        dfm::wait_vmcnt<NSLOT - HALF>();
         double2 v[HALF];
 #pragma unroll
         for (int u = 0; u < HALF; ++u) v[u] = *reinterpret_cast<const double2*>(smem + (wave * NSLOT + slot + u) * 1024 + 16 * lane);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        dfm::wait_lgkmcnt0();
 #pragma unroll
         for (int u = 0; u < HALF; ++u) issue(p0 + NSLOT + u, slot + u);
 #pragma unroll
@@ -51,7 +49,7 @@ __global__ __launch_bounds__(256) void probe_read_kernel(const char* __restrict_
         slot += HALF;
         if (slot == NSLOT) slot = 0;
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    dfm::wait_vmcnt<0>();
     if (acc == 1.2345e300) out[0] = acc;
 }
 

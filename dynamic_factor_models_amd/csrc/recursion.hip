@@ -26,7 +26,6 @@
 
 namespace dfm {
 
-constexpr double kLog2Pi = 1.8378770664093454835606594728112;
 constexpr int CH = 8;                 // periods per prefetch chunk
 
 template <int R>

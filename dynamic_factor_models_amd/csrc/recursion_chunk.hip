@@ -42,7 +42,6 @@ namespace dfm {
 
 namespace {
 
-constexpr double kLog2PiC = 1.8378770664093454835606594728112;
 constexpr int kCstStride = 320;     // doubles per replicate in chunk_cst
 constexpr int kOffK = 0, kOffKT = 64, kOffQPhi = 128, kOffPhi = 192, kOffM0 = 256, kOffXi0 = 292, kOffLdc = 300, kOffQ0 = 301;
 constexpr int kTermStride = 96;     // P_T (36) f_T (8) P_0 (36) f_0 (8)
@@ -140,7 +139,6 @@ struct LdsAcc {
 // ---- one period's row of a chunk-major table (rows of 64 double2, lane = chunk) into the wave's LDS stage by LDS-DMA: nothing
 // lands in a VGPR until the arithmetic asks for it (the 46 doubles of a period held beside the step's 100 live matrix entries
 // cost ~500 VGPR <-> AGPR moves per step).  NROWS loads of 16 bytes per lane; lds_dst, base wave-uniform.
-using lds_cptr = __attribute__((address_space(3))) char*;
 #define DFM_CK_DMA_ROW                                   \
     "s_nop 0\n\t"                                        \
     "global_load_lds_dwordx4 %1, %2\n\t"                 \
@@ -179,21 +177,19 @@ __device__ __forceinline__ void dma_rows(const double2* base, unsigned voff, uns
 // a workgroup-scope fence (s_waitcnt).  __threadfence() is agent scope: buffer_wbl2 + buffer_inv -- the XCD's L2 writes back every dirty
 // line it holds (all the outputs the batch has just stored) once per fence and replicate.
 __device__ __forceinline__ void wave_mem_fence() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup"); }
-__device__ __forceinline__ void wait_dma() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-__device__ __forceinline__ void wait_lds_reads() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
 // the observation stage: 23 rows of 64 double2 (lane = chunk), as the table has them: doubles 0..35 of a lane's period C_t (packed),
 // 36..43 b_t, 44 s_t, 45 n_t log 2 pi + log det R_t
 struct StageObs {
     const double* st;   // stage + 2 * lane
-    __device__ __forceinline__ void ready() const { wait_dma(); }
+    __device__ __forceinline__ void ready() const { wait_vmcnt<0>(); }
     __device__ __forceinline__ double at(int e) const { return st[(e >> 1) * 128 + (e & 1)]; }
     __device__ __forceinline__ double c(int p) const { return at(p); }
     __device__ __forceinline__ double b(int i) const { return at(chunk::NP + i); }
 };
 struct StageZw {
     const double* st;
-    __device__ __forceinline__ void ready() const { wait_dma(); }
+    __device__ __forceinline__ void ready() const { wait_vmcnt<0>(); }
     __device__ __forceinline__ double z(int p) const { return st[(p >> 1) * 128 + (p & 1)]; }
     __device__ __forceinline__ double w(int i) const { return st[((chunk::NP + i) >> 1) * 128 + (i & 1)]; }
 };
@@ -271,7 +267,7 @@ __global__ __launch_bounds__(64) void chunk_bridge_kernel(RecursionArgs a) {
 #pragma unroll
         for (int i = 0; i < RC; ++i) v[NP + i] = a.bcol[bt * RC + i];
         v[NP + R] = a.scol[bt];
-        v[NP + R + 1] = (double)n * kLog2PiC + (n == a.N ? a.ldfull[b] : a.ldrow[bt]);
+        v[NP + R + 1] = (double)n * kLog2Pi + (n == a.N ? a.ldfull[b] : a.ldrow[bt]);
     }
     double2* dst = reinterpret_cast<double2*>(a.chunk_obs) + ((size_t)b * L + slot) * kObsRows * 64 + lane;
 #pragma unroll
@@ -310,7 +306,7 @@ __global__ __launch_bounds__(64) void chunk_unbridge_kernel(RecursionArgs a, dou
     } else {
         nobs[bt] = a.N;
         if (t == 0) {
-            ldfull[b] = v[NP + R + 1] - (double)a.N * kLog2PiC;
+            ldfull[b] = v[NP + R + 1] - (double)a.N * kLog2Pi;
 #pragma unroll
             for (int i = 0; i < RC; ++i)
 #pragma unroll
@@ -356,7 +352,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
     double* stage = csm;
     const double* stl = stage + 2 * lane;                          // (both tables' stage: rows of 64 double2, lane = chunk)
     const double* sto = stl;
-    const unsigned stage_lds = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lds_cptr)(reinterpret_cast<char*>(stage)));
+    const unsigned stage_lds = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lds_char_ptr)(reinterpret_cast<char*>(stage)));
     double* acc10 = csm + 2 * 64 * kObsRows;
     double* acc11 = acc10 + 64 * kAccSlots;
     if constexpr (EM) {
@@ -415,7 +411,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
             for (int j = 0; j <= i; ++j) m[pidx(i, j)] = qf[8 * i + j] + ob.c(pidx(i, j));
             xi[i] = ob.b(i);
         }
-        wait_lds_reads();
+        wait_lgkmcnt0();
         issue_obs(-W);
     }
     LogProd lp;
@@ -453,7 +449,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
             ssum += counted ? st_s : 0.0;
             ldnsum += counted ? st_l : 0.0;
         }
-        wait_lds_reads();                                          // the stage is re-armed: its reads are done
+        wait_lgkmcnt0();                                           // the stage is re-armed: its reads are done
         if (u + 1 < NS) issue_obs(u + 1 - W);
         if (u == ucap) {                                           // (wave-uniform) the top lane has just taken period T - 1
             const cdp ph = launder(cst + kOffPhi);
@@ -520,7 +516,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
         const int src = lane + sh < 64 ? lane + sh : 63;
         dma_rows<kScrRows>(scr + (size_t)slot * kScrRows * 64, (unsigned)src * 16u, stage_lds);
     };
-    wait_lds_reads();
+    wait_lgkmcnt0();
     issue_zw(NS - 1);
     for (int u = 0; u < NS; ++u) {
         const int d = NS - 1 - u;
@@ -545,7 +541,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
         } else {
             bwd_step(P, f, StageZw{stl}, ktrow, NoAcc{});
         }
-        wait_lds_reads();
+        wait_lgkmcnt0();
         if (u + 1 < NS) issue_zw(d - 1);
         if (counted) {
             if (t >= 1) store_row(t - 1, P, f);

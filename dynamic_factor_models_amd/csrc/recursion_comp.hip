@@ -36,33 +36,11 @@ namespace dfm {
 
 namespace {
 
-typedef double c16 __attribute__((ext_vector_type(4)));
-constexpr double kLog2PiC4 = 1.8378770664093454835606594728112;
 constexpr int kDppShr4 = 0x114, kDppShl12 = 0x10C, kDppShl4 = 0x104, kDppShr12 = 0x11C;   // row_shr:n = lane l <- l - n, row_shl:n = lane l <- l + n (0 outside the row)
 
-__device__ __forceinline__ c16 cm1(double a, double b, c16 acc) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0); }
-__device__ __forceinline__ double crd(double v, int lane) {
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane), hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double crow16(double v) { v += xor_lane<1>(v); v += xor_lane<2>(v); v += xor_lane<4>(v); v += xor_lane<8>(v); return v; }
-__device__ __forceinline__ double ccol4(double v) { v += xor_lane<16>(v); v += xor_lane<32>(v); return v; }
-// (the operands are PRVALUES -- unary plus: `q == 0 ? x[0] : x[1]` on lvalues is an lvalue, clang emits a select of ADDRESSES and one load,
-// the array then stays in scratch memory behind a dynamic offset, and every pick is a scratch round trip behind an s_waitcnt vmcnt(0))
-__device__ __forceinline__ double cpick(const double (&x)[4], int q) {
-    const double a0 = +x[0], a1 = +x[1], a2 = +x[2], a3 = +x[3];
-    return q == 0 ? +a0 : q == 1 ? +a1 : q == 2 ? +a2 : +a3;
-}
 __device__ __forceinline__ double cpick44(const double (&W)[4][4], int i, int j) {   // W[i][j], i and j run-time (selects, no indexing)
-    const double r0 = cpick(W[0], j), r1 = cpick(W[1], j), r2 = cpick(W[2], j), r3 = cpick(W[3], j);
+    const double r0 = pick4(W[0], j), r1 = pick4(W[1], j), r2 = pick4(W[2], j), r3 = pick4(W[3], j);
     return i == 0 ? +r0 : i == 1 ? +r1 : i == 2 ? +r2 : +r3;
-}
-__device__ __forceinline__ void csqrt(double x, double& s, double& r) {   // sqrt and 1 / sqrt of a positive normal x (recursion_mbf16.hip)
-    r = __builtin_amdgcn_rsq(x);
-    r = fma(0.5 * r, fma(-x * r, r, 1.0), r);
-    r = fma(0.5 * r, fma(-x * r, r, 1.0), r);
-    s = x * r;
-    s = fma(0.5 * r, fma(-s, s, x), s);
 }
 // inverse of a symmetric positive definite 4 x 4 matrix (wave-uniform values, every lane the same): Cholesky, triangular inverse,
 // Li' Li.  Returns det; ok = false when a pivot is not positive.
@@ -77,7 +55,7 @@ __device__ __forceinline__ double inv4(const double (&S)[4][4], double (&Inv)[4]
         ok = ok && (d > 0.0);
         det *= (d > 0.0 ? d : 1.0);
         double ljj;
-        csqrt(d > 0.0 ? d : 1.0, ljj, iL[j]);
+        fast_sqrt_rsqrt(d > 0.0 ? d : 1.0, ljj, iL[j]);
         L[j][j] = ljj;
 #pragma unroll
         for (int i = j + 1; i < 4; ++i) {
@@ -165,7 +143,7 @@ __global__ __launch_bounds__(64) void recursion_comp_kernel(RecursionArgs a) {
     const double ldfull = a.ldfull[b];
     double* slot0 = a.ZJtab + (size_t)b * (T + 1) * kSlot;
     const bool em = a.S11 != nullptr;
-    const c16 zero = {0.0, 0.0, 0.0, 0.0};
+    const v4d zero = {0.0, 0.0, 0.0, 0.0};
     const double* Ag = a.A + (size_t)b * RR;
     const double* Qg = a.Q + (size_t)b * RR;
     bool okall = true;
@@ -197,7 +175,7 @@ __global__ __launch_bounds__(64) void recursion_comp_kernel(RecursionArgs a) {
         sQP[e] = s;
     }
     wave_lds_sync();
-    c16 PQP[NT][NT];                                               // Phi' Qi Phi
+    v4d PQP[NT][NT];                                               // Phi' Qi Phi
     double cbr[NT], cbc[NT][4];                                    // Base's constant block row / block column (see the head of the file)
 #pragma unroll
     for (int ti = 0; ti < NT; ++ti)
@@ -233,7 +211,7 @@ __global__ __launch_bounds__(64) void recursion_comp_kernel(RecursionArgs a) {
         wave_lds_sync();
         okall = lds_spd_inverse(sS, k, lane, detP0) && okall;
     }
-    c16 Om[NT][NT];
+    v4d Om[NT][NT];
 #pragma unroll
     for (int ti = 0; ti < NT; ++ti)
 #pragma unroll
@@ -252,12 +230,12 @@ __global__ __launch_bounds__(64) void recursion_comp_kernel(RecursionArgs a) {
             qq = xi_l * mug[lane];
         }
         if (lane < 32) sXi[0][lane] = lane < k ? xi_l : 0.0;
-        qq = crow16(qq); qq = ccol4(qq);
+        qq = row_sum16(qq); qq = col_sum4(qq);
         q0 = qq;                                                   // mu0' P0^-1 mu0
     }
     wave_lds_sync();
     // the replicate's full collapsed observation (periods without a missing cell)
-    c16 Cfl[NT][NT];
+    v4d Cfl[NT][NT];
 #pragma unroll
     for (int ti = 0; ti < NT; ++ti)
 #pragma unroll
@@ -270,7 +248,7 @@ __global__ __launch_bounds__(64) void recursion_comp_kernel(RecursionArgs a) {
 
     // M_dd^-1 [c][k4] in the lanes of the first four columns (the A operand of "M_dd^-1 padded")
     auto wsel = [&](const double (&W)[4][4]) -> double {
-        const double r0 = cpick(W[0], k4), r1 = cpick(W[1], k4), r2 = cpick(W[2], k4), r3 = cpick(W[3], k4);
+        const double r0 = pick4(W[0], k4), r1 = pick4(W[1], k4), r2 = pick4(W[2], k4), r3 = pick4(W[3], k4);
         const double x = c == 0 ? +r0 : c == 1 ? +r1 : c == 2 ? +r2 : +r3;
         return c < 4 ? x : 0.0;
     };
@@ -280,7 +258,7 @@ __global__ __launch_bounds__(64) void recursion_comp_kernel(RecursionArgs a) {
     double acc = 0.0;                                              // sum_t (n log 2 pi + ld + s) - sum_t xi_d' M_dd^-1 xi_d
     int cur = 0;
     // the period's collapsed observation a step ahead (vector loads: see recursion_mbf16.hip)
-    struct ObsIn { int nt; double s, ld, bl; c16 C[NT][NT]; };
+    struct ObsIn { int nt; double s, ld, bl; v4d C[NT][NT]; };
     auto fetch_obs = [&](int t) {
         ObsIn o;
         t = t < T ? t : T - 1;
@@ -306,7 +284,7 @@ __global__ __launch_bounds__(64) void recursion_comp_kernel(RecursionArgs a) {
         const double* xi = sXi[cur];
         double* xin = sXi[cur ^ 1];
         // M = Om_f + Phi' Qi Phi; its pivot block M_dd and the strip of the d rows
-        c16 M[NT][NT];
+        v4d M[NT][NT];
 #pragma unroll
         for (int ti = 0; ti < NT; ++ti)
 #pragma unroll
@@ -332,7 +310,7 @@ __global__ __launch_bounds__(64) void recursion_comp_kernel(RecursionArgs a) {
             for (int i = 0; i < 4; ++i)
 #pragma unroll
                 for (int j = 0; j <= i; ++j) {
-                    const double pv = crd(dsel, 16 * i + 4 * vd + j);
+                    const double pv = uniform_lane(dsel, 16 * i + 4 * vd + j);
                     Mdd[i][j] = pv; Mdd[j][i] = pv;
                 }
         }
@@ -354,7 +332,7 @@ __global__ __launch_bounds__(64) void recursion_comp_kernel(RecursionArgs a) {
             for (int q = 0; q < 4; ++q) s = fma(Mdi[i][q], xd[q], s);
             z[i] = s;
         }
-        acc += (double)ob.nt * kLog2PiC4 + ((ob.nt == N) ? ldfull : ob.ld) + ob.s - (xd[0] * z[0] + xd[1] * z[1] + xd[2] * z[2] + xd[3] * z[3]);
+        acc += (double)ob.nt * kLog2Pi + ((ob.nt == N) ? ldfull : ob.ld) + ob.s - (xd[0] * z[0] + xd[1] * z[1] + xd[2] * z[2] + xd[3] * z[3]);
         // U in column-operand form: ucol[t] = U[16 t + c][k4]  (the d strip moved 4 columns right under the constant block)
         double ucol[NT];
 #pragma unroll
@@ -368,14 +346,14 @@ __global__ __launch_bounds__(64) void recursion_comp_kernel(RecursionArgs a) {
         const double ws = wsel(Mdi);
         double rrow[NT];
 #pragma unroll
-        for (int tj = 0; tj < NT; ++tj) rrow[tj] = cm1(ws, ucol[tj], zero)[0];
+        for (int tj = 0; tj < NT; ++tj) rrow[tj] = mm1(ws, ucol[tj], zero)[0];
         // Om_p = Base - (U M_dd^-1) U';  Om_f' = Om_p + C
         const bool full = ob.nt == N || !haveCt;
 #pragma unroll
         for (int ti = 0; ti < NT; ++ti)
 #pragma unroll
             for (int tj = 0; tj < NT; ++tj) {
-                c16 base;
+                v4d base;
 #pragma unroll
                 for (int v = 0; v < 4; ++v) {
                     double val;
@@ -389,14 +367,14 @@ __global__ __launch_bounds__(64) void recursion_comp_kernel(RecursionArgs a) {
                     }
                     base[v] = (ri(ti, v) < k && cj(tj) < k) ? val : 0.0;
                 }
-                const c16 op = cm1(-rrow[ti], ucol[tj], base);
+                const v4d op = mm1(-rrow[ti], ucol[tj], base);
 #pragma unroll
                 for (int v = 0; v < 4; ++v) Om[ti][tj][v] = op[v] + (full ? Cfl[ti][tj][v] : ob.C[ti][tj][v]);
             }
         // xi_p = [0; xi_a] - U z;  xi_f' = xi_p + b
 #pragma unroll
         for (int tj = 0; tj < NT; ++tj) {
-            const double uz = ccol4(ucol[tj] * cpick(z, k4));
+            const double uz = col_sum4(ucol[tj] * pick4(z, k4));
             const int i = cj(tj);
             if (k4 == 0) xin[i] = (i < k) ? ((i >= 4 ? xi[i - 4] : 0.0) - uz) : 0.0;
         }
@@ -408,7 +386,7 @@ __global__ __launch_bounds__(64) void recursion_comp_kernel(RecursionArgs a) {
 #pragma unroll
             for (int tj = 0; tj < NT; ++tj) sl[64 * tj + lane] = -rrow[tj];
             if (c < 4) sl[128 + 4 * c + k4] = ws;                 // M_dd^-1 row-major
-            if (c == 4) sl[144 + k4] = cpick(z, k4);
+            if (c == 4) sl[144 + k4] = pick4(z, k4);
         }
         cur ^= 1;
         wave_lds_sync();
@@ -426,7 +404,7 @@ __global__ __launch_bounds__(64) void recursion_comp_kernel(RecursionArgs a) {
             }
     wave_lds_sync();
     okall = lds_spd_inverse(sS, k, lane, detOT) && okall;
-    c16 V[NT][NT];
+    v4d V[NT][NT];
 #pragma unroll
     for (int ti = 0; ti < NT; ++ti)
 #pragma unroll
@@ -446,7 +424,7 @@ __global__ __launch_bounds__(64) void recursion_comp_kernel(RecursionArgs a) {
             qq = ml * xi[lane];
         }
         if (lane < 32) sM[0][lane] = lane < k ? ml : 0.0;
-        qq = crow16(qq); qq = ccol4(qq);
+        qq = row_sum16(qq); qq = col_sum4(qq);
         qT = qq;                                                   // xi_T' Om_T^-1 xi_T
     }
     wave_lds_sync();
@@ -462,7 +440,7 @@ __global__ __launch_bounds__(64) void recursion_comp_kernel(RecursionArgs a) {
 #endif
     // =================================================== backward ==========================================================
     const int r = a.r, rl = a.rl > 0 ? a.rl : R, npr = r * (r + 1) / 2;
-    c16 S11[NT][NT], S10[NT][NT], VT[NT][NT];
+    v4d S11[NT][NT], S10[NT][NT], VT[NT][NT];
 #pragma unroll
     for (int ti = 0; ti < NT; ++ti)
 #pragma unroll
@@ -550,11 +528,11 @@ __global__ __launch_bounds__(64) void recursion_comp_kernel(RecursionArgs a) {
         double gv[NT];
 #pragma unroll
         for (int tj = 0; tj < NT; ++tj) {
-            c16 ac = zero;
+            v4d ac = zero;
 #pragma unroll
             for (int tk = 0; tk < NT; ++tk)
 #pragma unroll
-                for (int s = 0; s < 4; ++s) ac = cm1(gcs[tk][s], V[tk][tj][s], ac);
+                for (int s = 0; s < 4; ++s) ac = mm1(gcs[tk][s], V[tk][tj][s], ac);
             gv[tj] = ac[0];
         }
         // md = g + G m;  Vdd = M_dd^-1 + (G V) G'
@@ -563,20 +541,20 @@ __global__ __launch_bounds__(64) void recursion_comp_kernel(RecursionArgs a) {
             double gm = 0.0;
 #pragma unroll
             for (int tj = 0; tj < NT; ++tj) gm = fma(sc.g[tj], mcol[tj], gm);
-            gm = crow16(gm);
+            gm = row_sum16(gm);
 #pragma unroll
-            for (int q = 0; q < 4; ++q) md[q] = sc.z[q] + crd(gm, 16 * q);
+            for (int q = 0; q < 4; ++q) md[q] = sc.z[q] + uniform_lane(gm, 16 * q);
             double part[4] = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
             for (int tj = 0; tj < NT; ++tj) {
                 const double g0 = sc.g[tj], g1 = xor_lane<16>(g0), g2 = xor_lane<32>(g0), g3 = xor_lane<48>(g0);   // G[k4 ^ x][j]
                 const double gq[4] = {g0, g1, g2, g3};
 #pragma unroll
-                for (int qp = 0; qp < 4; ++qp) part[qp] = fma(gv[tj], cpick(gq, qp ^ k4), part[qp]);
+                for (int qp = 0; qp < 4; ++qp) part[qp] = fma(gv[tj], pick4(gq, qp ^ k4), part[qp]);
             }
 #pragma unroll
             for (int qp = 0; qp < 4; ++qp) {
-                vdd[qp] = crow16(part[qp]) + sc.mdr[qp];
+                vdd[qp] = row_sum16(part[qp]) + sc.mdr[qp];
             }
         }
         // ---- GV in column form (LDS transposition): cs0[ti][v] = GV[q'][i], cs1 = GV[q'][i + 4], q' = c - 4 vd, in the lanes of block column db
@@ -587,7 +565,7 @@ __global__ __launch_bounds__(64) void recursion_comp_kernel(RecursionArgs a) {
         // (what does not depend on the register index, outside the register loop; LDS reads unconditional at a valid address, then selected:
         // a read under a lane-divergent condition is a branch region of its own -- the loop was bound by what it issues)
         const double* gvrow = sGV + (c & 3) * 32;
-        const double md_l = cpick(md, c & 3);
+        const double md_l = pick4(md, c & 3);
         double mprev_t[NT];
 #pragma unroll
         for (int tj = 0; tj < NT; ++tj) {
@@ -597,7 +575,7 @@ __global__ __launch_bounds__(64) void recursion_comp_kernel(RecursionArgs a) {
         }
         // S10 += Cov(s_t, s_{t-1} | X) + m_t m_{t-1}',  Cov = [V[:, 4:], V G']
         // new state: V moved one block up-left, block row / column db from GV, block (db, db) = Vdd;  m' = (m[4:], md)
-        c16 Vn[NT][NT];
+        v4d Vn[NT][NT];
 #pragma unroll
         for (int ti = 0; ti < NT; ++ti)
 #pragma unroll
@@ -635,7 +613,7 @@ __global__ __launch_bounds__(64) void recursion_comp_kernel(RecursionArgs a) {
             const double gl = c < 12 ? g0s : g1s;
             const int j = cj(tj);
             double rowv = j < ka ? gl : 0.0;
-            if (tj == td && qp_l >= 0) rowv = cpick(vdd, qp_l);
+            if (tj == td && qp_l >= 0) rowv = pick4(vdd, qp_l);
 #pragma unroll
             for (int ti = 0; ti < NT; ++ti)
 #pragma unroll
@@ -648,7 +626,7 @@ __global__ __launch_bounds__(64) void recursion_comp_kernel(RecursionArgs a) {
             for (int tj = 0; tj < NT; ++tj) V[ti][tj] = Vn[ti][tj];
         {
             const double ml4 = m[(lane & 31) + 4 < 32 ? (lane & 31) + 4 : 31];
-            const double mdl = cpick(md, (lane - ka) & 3);
+            const double mdl = pick4(md, (lane - ka) & 3);
             if (lane < 32) mn[lane] = lane < ka ? ml4 : (lane < k ? mdl : 0.0);
         }
         mc ^= 1;

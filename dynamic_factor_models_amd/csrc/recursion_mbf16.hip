@@ -34,45 +34,15 @@ namespace dfm {
 
 namespace {
 
-typedef double m16 __attribute__((ext_vector_type(4)));
 constexpr int K16 = 16, KK16 = 256;
-constexpr double kLog2PiM = 1.8378770664093454835606594728112;
 // per-period scratch (the replicate's ZJtab slot of 512 doubles): [0, 256) P_p, lane-major (lane l: doubles 4 l .. 4 l + 3);
 // [256, 272) W row-major; [272, 276) u; [288, 304) m_p.  Slot T: [0, 256) S11 (full 16 x 16, row-major) for the epilogue kernel.
 constexpr int kSlot = 2 * KK16, kOffW = 256, kOffU = 272, kOffMp = 288;
 
-__device__ __forceinline__ m16 mm4(const m16& a, const m16& b, m16 acc) {   // acc + Left Right (a: A operand of Left, b: Right in D layout)
+__device__ __forceinline__ v4d mm4(const v4d& a, const v4d& b, v4d acc) {   // acc + Left Right (a: A operand of Left, b: Right in D layout)
 #pragma unroll
     for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s], b[s], acc, 0, 0, 0);
     return acc;
-}
-__device__ __forceinline__ m16 mm1(double a, double b, m16 acc) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0); }
-__device__ __forceinline__ double rdlane(double v, int lane) {
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane), hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double row_sum16(double v) {          // sum over the 16 lanes of a row group, in every lane of it
-    v += xor_lane<1>(v); v += xor_lane<2>(v); v += xor_lane<4>(v); v += xor_lane<8>(v);
-    return v;
-}
-__device__ __forceinline__ double col_sum4(double v) {           // sum over the 4 row groups (lanes c, c + 16, c + 32, c + 48)
-    v += xor_lane<16>(v); v += xor_lane<32>(v);
-    return v;
-}
-// sqrt(x) and 1 / sqrt(x) of a positive, normal x: v_rsq_f64 refined by two Newton steps, the root by one correction (a pivot of an
-// SPD matrix: no scaling, no fix-up -- the IEEE sqrt + division pair is ~35 instructions on a chain that is nothing but such pivots)
-__device__ __forceinline__ void fast_sqrt_rsqrt(double x, double& s, double& r) {
-    r = __builtin_amdgcn_rsq(x);
-    r = fma(0.5 * r, fma(-x * r, r, 1.0), r);
-    r = fma(0.5 * r, fma(-x * r, r, 1.0), r);
-    s = x * r;
-    s = fma(0.5 * r, fma(-s, s, x), s);
-}
-// (PRVALUE operands -- unary plus: a conditional on array lvalues is an lvalue, i.e. a select of addresses + one load: the array stays in
-// scratch memory and every pick is a scratch round trip behind s_waitcnt vmcnt(0); recursion_comp.hip cpick)
-__device__ __forceinline__ double pick4(const double (&x)[4], int q) {
-    const double a0 = +x[0], a1 = +x[1], a2 = +x[2], a3 = +x[3];
-    return q == 0 ? +a0 : q == 1 ? +a1 : q == 2 ? +a2 : +a3;
 }
 
 // the wave-uniform 4 x 4 algebra of one period (see the head of the file).  In: P11 (symmetric, full), C (symmetric, full), e0 = b - C mp1.
@@ -208,7 +178,7 @@ __global__ __launch_bounds__(64) void recursion_mbf16_kernel(RecursionArgs a) {
     const bool em = a.S11 != nullptr;
 
     // ---- constants: A in both operand layouts, Q; the replicate's full Gram matrix (periods without a missing cell) ---------------
-    m16 dA, aA, dQ, pf;
+    v4d dA, aA, dQ, pf;
     {
         const double* Ag = a.A + (size_t)b * KK16;
         const double* Qg = a.Q + (size_t)b * KK16;
@@ -221,7 +191,7 @@ __global__ __launch_bounds__(64) void recursion_mbf16_kernel(RecursionArgs a) {
             pf[v] = 0.5 * (Pg[(k4 + 4 * v) * K16 + c] + Pg[c * K16 + k4 + 4 * v]);
         }
     }
-    const m16 P0m = pf;
+    const v4d P0m = pf;
     double Cf[4][4];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
@@ -235,7 +205,7 @@ __global__ __launch_bounds__(64) void recursion_mbf16_kernel(RecursionArgs a) {
         const double x = c == 0 ? r0 : c == 1 ? r1 : c == 2 ? r2 : r3;
         return c < 4 ? x : 0.0;
     };
-    const m16 zero = {0.0, 0.0, 0.0, 0.0};
+    const v4d zero = {0.0, 0.0, 0.0, 0.0};
 
     // =================================================== forward ===========================================================
     LogProd detprod;
@@ -273,8 +243,8 @@ __global__ __launch_bounds__(64) void recursion_mbf16_kernel(RecursionArgs a) {
             }
         }
         // P_p = A (P_f A') + Q;  m_p = A m_f
-        const m16 X = mm4(pf, aA, zero);
-        const m16 pp = mm4(aA, X, dQ);
+        const v4d X = mm4(pf, aA, zero);
+        const v4d pp = mm4(aA, X, dQ);
         {
             const double mfc = vmf[c];
             double y[4];
@@ -292,7 +262,7 @@ __global__ __launch_bounds__(64) void recursion_mbf16_kernel(RecursionArgs a) {
             mp1[i] = vmp[i];
 #pragma unroll
             for (int j = 0; j <= i; ++j) {
-                const double pv = rdlane(pp[0], 16 * i + j);
+                const double pv = uniform_lane(pp[0], 16 * i + j);
                 P11[i][j] = pv; P11[j][i] = pv;
             }
         }
@@ -307,7 +277,7 @@ __global__ __launch_bounds__(64) void recursion_mbf16_kernel(RecursionArgs a) {
         okall = update4(P11, C, e, up) && okall;
         // P_f = P_p - P1 W P1'  (two rank-4 instructions);  m_f = m_p + P1 u
         const double ws = wsel(up.W);
-        const m16 WP = mm1(ws, pp[0], zero);                      // rows 0..3: W P1'
+        const v4d WP = mm1(ws, pp[0], zero);                      // rows 0..3: W P1'
         pf = mm1(-WP[0], pp[0], pp);
         {
             const double pu = col_sum4(pp[0] * pick4(up.u, k4));   // (P1 u)[c]
@@ -332,14 +302,14 @@ __global__ __launch_bounds__(64) void recursion_mbf16_kernel(RecursionArgs a) {
         // what the backward sweep reads back
         {
             double* sl = slot0 + (size_t)t * kSlot;
-            *reinterpret_cast<m16*>(sl + 4 * lane) = pp;
+            *reinterpret_cast<v4d*>(sl + 4 * lane) = pp;
             if (c < 4) sl[kOffW + 4 * c + k4] = ws;
             if (c == 4) sl[kOffU + k4] = pick4(up.u, k4);
             if (lane < K16) sl[kOffMp + lane] = vmp[lane];
         }
         wave_lds_sync();
     }
-    const double ll = okall ? -0.5 * (nsum * kLog2PiM + ldsum + detprod.log_value() + qsum + ssum) : __builtin_nan("");
+    const double ll = okall ? -0.5 * (nsum * kLog2Pi + ldsum + detprod.log_value() + qsum + ssum) : __builtin_nan("");
     if (lane == 0) {
         a.loglik[b] = ll;
         if (a.ncov) a.ncov[b] = T;
@@ -348,16 +318,16 @@ __global__ __launch_bounds__(64) void recursion_mbf16_kernel(RecursionArgs a) {
 
     // =================================================== backward ==========================================================
     const int r = a.r, rl = a.rl > 0 ? a.rl : K16, npr = r * (r + 1) / 2;
-    m16 Nn = zero, ImNPn = zero, S11 = zero, S10 = zero, VT = zero;
+    v4d Nn = zero, ImNPn = zero, S11 = zero, S10 = zero, VT = zero;
     double snext[4] = {0.0, 0.0, 0.0, 0.0}, sTrow[4] = {0.0, 0.0, 0.0, 0.0}, sTc = 0.0;
     if (lane < K16) vr[lane] = 0.0;
     wave_lds_sync();
-    struct SlotIn { m16 pp; double W[16], u[4], ws, mpr[4]; };
+    struct SlotIn { v4d pp; double W[16], u[4], ws, mpr[4]; };
     auto fetch_slot = [&](int t) {
         SlotIn o;
         const double* sl = slot0 + (size_t)(t > 0 ? t : 0) * kSlot;
         const double* su = sl;
-        o.pp = *reinterpret_cast<const m16*>(sl + 4 * lane);
+        o.pp = *reinterpret_cast<const v4d*>(sl + 4 * lane);
 #pragma unroll
         for (int q = 0; q < 16; ++q) o.W[q] = su[kOffW + q];
 #pragma unroll
@@ -369,7 +339,7 @@ __global__ __launch_bounds__(64) void recursion_mbf16_kernel(RecursionArgs a) {
     for (int t = T - 1; t >= 0; --t) {
         const SlotIn sc_ = snx;
         snx = fetch_slot(t - 1);                                   // (the slot of the next step: its round trip under this step's products)
-        const m16 pp = sc_.pp;
+        const v4d pp = sc_.pp;
         double W[4][4], u[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -387,7 +357,7 @@ __global__ __launch_bounds__(64) void recursion_mbf16_kernel(RecursionArgs a) {
             const double z = row_sum16(pp[0] * y);                 // (P1' A' r)[k4], in every lane of row group k4
             double zq[4];
 #pragma unroll
-            for (int q = 0; q < 4; ++q) zq[q] = rdlane(z, 16 * q);
+            for (int q = 0; q < 4; ++q) zq[q] = uniform_lane(z, 16 * q);
             double corr = 0.0;
             if (c < 4) {
                 const double w0 = c == 0 ? +W[0][0] : c == 1 ? +W[1][0] : c == 2 ? +W[2][0] : +W[3][0];
@@ -400,25 +370,25 @@ __global__ __launch_bounds__(64) void recursion_mbf16_kernel(RecursionArgs a) {
             if (k4 == 0) vr[c] = y + corr;
         }
         // N_{t-1} = E W E' + D' (A' N A) D,  D = I - P1 W E'
-        const m16 NA = mm4(Nn, dA, zero);
-        const m16 M = mm4(NA, dA, zero);
-        const m16 PW = mm1(pp[0], ws, zero);                       // P1 W (columns 0..3)
-        m16 Tm = M;
+        const v4d NA = mm4(Nn, dA, zero);
+        const v4d M = mm4(NA, dA, zero);
+        const v4d PW = mm1(pp[0], ws, zero);                       // P1 W (columns 0..3)
+        v4d Tm = M;
         {
-            const m16 MPW = mm4(M, PW, zero);
+            const v4d MPW = mm4(M, PW, zero);
 #pragma unroll
             for (int v = 0; v < 4; ++v) Tm[v] -= MPW[v];
         }
-        const m16 PT = mm4(pp, Tm, zero);
-        const m16 WPT = mm1(ws, PT[0], zero);                      // rows 0..3: W P1' T
+        const v4d PT = mm4(pp, Tm, zero);
+        const v4d WPT = mm1(ws, PT[0], zero);                      // rows 0..3: W P1' T
         Nn = Tm;
         Nn[0] = Nn[0] - WPT[0] + ws;                               // (+ E W E': ws is W[c][k4] = W[k4][c] in the lanes of columns 0..3, 0 elsewhere)
         wave_lds_sync();
         // s_t|T = m_p + P_p r,  V_t = P_p - P_p N P_p
-        const m16 NP = mm4(Nn, pp, zero);
-        m16 V = pp;
+        const v4d NP = mm4(Nn, pp, zero);
+        v4d V = pp;
         {
-            const m16 PNP = mm4(NP, pp, zero);
+            const v4d PNP = mm4(NP, pp, zero);
 #pragma unroll
             for (int v = 0; v < 4; ++v) V[v] -= PNP[v];
         }
@@ -453,10 +423,10 @@ __global__ __launch_bounds__(64) void recursion_mbf16_kernel(RecursionArgs a) {
                 for (int v = 0; v < 4; ++v) sTrow[v] = srow[v];
             } else {
                 // Cov(s_{t+1}, s_t | X) = (I - P_p,t+1 N_t) A P_f,t  with  P_f,t = P_p - P1 W P1'
-                const m16 WP = mm1(ws, pp[0], zero);
-                const m16 pft = mm1(-WP[0], pp[0], pp);
-                const m16 APf = mm4(aA, pft, zero);
-                const m16 Cv = mm4(ImNPn, APf, zero);
+                const v4d WP = mm1(ws, pp[0], zero);
+                const v4d pft = mm1(-WP[0], pp[0], pp);
+                const v4d APf = mm4(aA, pft, zero);
+                const v4d Cv = mm4(ImNPn, APf, zero);
 #pragma unroll
                 for (int v = 0; v < 4; ++v) S10[v] += fma(snext[v], sc, Cv[v]);
             }
@@ -479,12 +449,12 @@ __global__ __launch_bounds__(64) void recursion_mbf16_kernel(RecursionArgs a) {
         if (k4 == 0) vy[c] = y;
         wave_lds_sync();
     }
-    const m16 NA0 = mm4(Nn, dA, zero);
-    const m16 N0 = mm4(NA0, dA, zero);                             // A' N A
-    const m16 NP0 = mm4(N0, P0m, zero);
-    m16 P0s = P0m;
+    const v4d NA0 = mm4(Nn, dA, zero);
+    const v4d N0 = mm4(NA0, dA, zero);                             // A' N A
+    const v4d NP0 = mm4(N0, P0m, zero);
+    v4d P0s = P0m;
     {
-        const m16 PNP = mm4(NP0, P0m, zero);
+        const v4d PNP = mm4(NP0, P0m, zero);
 #pragma unroll
         for (int v = 0; v < 4; ++v) P0s[v] -= PNP[v];
     }
@@ -504,8 +474,8 @@ __global__ __launch_bounds__(64) void recursion_mbf16_kernel(RecursionArgs a) {
     }
     const double f0c = vs[c];
     {
-        const m16 AP0 = mm4(aA, P0m, zero);                        // L_0 P_0 = A P0
-        const m16 Cv = mm4(ImNPn, AP0, zero);                      // Cov(s_1, s_0 | X)
+        const v4d AP0 = mm4(aA, P0m, zero);                        // L_0 P_0 = A P0
+        const v4d Cv = mm4(ImNPn, AP0, zero);                      // Cov(s_1, s_0 | X)
 #pragma unroll
         for (int v = 0; v < 4; ++v) S10[v] += fma(snext[v], f0c, Cv[v]);
     }

@@ -27,11 +27,7 @@
 namespace dfm {
 
 namespace {
-constexpr double kLog2PiP = 1.8378770664093454835606594728112;
 constexpr int kPairChunk = 8;
-// workgroup barrier that orders LDS traffic only: __syncthreads() also drains the vector-memory counter, i.e. it would
-// wait for the prefetch of the next chunk at every chunk
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 }  // namespace
 
 __global__ __launch_bounds__(128, 2) void recursion_pair_kernel(RecursionArgs a) {
@@ -250,7 +246,7 @@ __global__ __launch_bounds__(128, 2) void recursion_pair_kernel(RecursionArgs a)
             const double qd = G.sum_i(G.sum_j(part)) - xch[4 * RR + 0];
             const double ssum = xch[4 * RR + 1], nsum = xch[4 * RR + 2], ldsum = xch[4 * RR + 3];
             const double LD = log(detOmT) + log(detP0) + (double)T * log(detQ) + detprod.log_value();
-            const double ll = -0.5 * (nsum * kLog2PiP + ldsum + LD + ssum + qd);
+            const double ll = -0.5 * (nsum * kLog2Pi + ldsum + LD + ssum + qd);
             if (lane == 0) {
                 a.loglik[b] = ll;
                 if (a.ncov) a.ncov[b] = e + 1;

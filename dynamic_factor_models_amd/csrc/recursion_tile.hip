@@ -48,8 +48,6 @@ namespace dfm {
 
 namespace {
 
-typedef double v4d __attribute__((ext_vector_type(4)));
-
 constexpr int kRt = 32;
 constexpr int kRtTile = 256;                       // doubles of one tile: [2 register pairs][64 lanes] double2
 constexpr int kRtBufA = 0;                         // exchange 1: Z | P_s | prologue operands        (4 tiles)
@@ -59,7 +57,6 @@ constexpr int kRtPraw = kRtXk + 4 * kRtTile;       // [2][4][32] published pivot
 constexpr int kRtPD = kRtPraw + 2 * 128;           // [2][16]    raw pivot block
 constexpr int kRtRed = kRtPD + 32;                 // [64]
 constexpr int kRtLds = kRtRed + 64;
-constexpr double kLog2PiT = 1.8378770664093454835606594728112;
 constexpr int kRtCh = 2;                           // periods per prefetch chunk
 
 struct RtCtx {
@@ -67,11 +64,6 @@ struct RtCtx {
     int lane, w, I, J, q, c;
     int pp;                                        // pivot exchanges so far (buffer parity)
 };
-
-// Barrier of the workgroup's four waves that waits for this wave's LDS traffic ONLY.  __syncthreads() also drains vmcnt: every
-// one of the ~9 barriers of a period would then wait for the table stores (8 KB per wave and period) and for the prefetch of the
-// next chunk -- HBM round trips inside a chain whose steps are a few hundred cycles (the lesson of recursion_pair.hip).
-__device__ __forceinline__ void rt_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 __device__ __forceinline__ void st_tile(double* buf, int tile, int lane, const v4d& m) {
     double2* p = reinterpret_cast<double2*>(buf + tile * kRtTile);
@@ -131,7 +123,7 @@ __device__ __forceinline__ double rt_sweep_inverse(RtCtx& x, v4d& m, int npiv) {
                 }
                 praw[q * 32 + 16 * J + c] = val;
             }
-            rt_barrier();
+            lds_barrier();
             // D = L diag(d) L' (unit lower L) -- every lane, redundantly (the values are wave-uniform) -- and T~ = D^-1 R~ for the
             // lane's column by two substitutions.  No explicit D^-1: the pivot columns of R~ are -I, so the same solve leaves -D^-1
             // in the pivot block.  (A first version inverted D by 2 x 2 blocks and multiplied: ~90 fp64 instructions on a chain
@@ -356,7 +348,7 @@ __global__ __launch_bounds__(256, CH ? 2 : 1) void recursion_tile_kernel(Recursi
     const double detP0 = rt_sweep_inverse(x, Omf, npiv);
     st_tile(bufA, w, lane, Ael);
     st_tile(bufB, w, lane, Qi);
-    rt_barrier();
+    lds_barrier();
     v4d KtY0, KtY1, Phi;
     {
         const v4d A0i = ld_tile(bufA, tY0, lane), A1i = ld_tile(bufA, tY1, lane);   // A as Y: tiles (kb, I)
@@ -366,17 +358,17 @@ __global__ __launch_bounds__(256, CH ? 2 : 1) void recursion_tile_kernel(Recursi
         const v4d Kt = mm_tn(A0i, A1i, Q0j, Q1j, nks, zero4);                       // K' = A'Qi
         const v4d Km = mm_tn(Q0i, Q1i, A0j, A1j, nks, zero4);                       // K  = Qi A
         st_tile(Xk, w, lane, Kt);
-        rt_barrier();                                                             // (bufA / bufB are read; Xk is complete)
+        lds_barrier();                                                            // (bufA / bufB are read; Xk is complete)
         st_tile(bufB, w, lane, Km);
-        rt_barrier();
+        lds_barrier();
         const v4d K0i = ld_tile(bufB, tY0, lane), K1i = ld_tile(bufB, tY1, lane);
         Phi = mm_tn(K0i, K1i, A0j, A1j, nks, zero4);                                // Phi = K'A
         KtY0 = ld_tile(Xk, tY0, lane); KtY1 = ld_tile(Xk, tY1, lane);               // K' as Y: constant for the whole kernel
         st_tile(bufA, w, lane, Omf);
-        rt_barrier();                                                             // (K' tiles are read before column 31 is patched)
+        lds_barrier();                                                            // (K' tiles are read before column 31 is patched)
     }
     put_c31(Xk, mu0v);
-    rt_barrier();
+    lds_barrier();
     double xi[4];                                              // (column-31 lanes) xi_t, rows of this wave's row block
     double qacc = 0.0;                                         // (column-31 lanes) mu0'xi_0 - xi_T'f_T - sum_t xi_t'w_t
     {
@@ -391,7 +383,7 @@ __global__ __launch_bounds__(256, CH ? 2 : 1) void recursion_tile_kernel(Recursi
 #pragma unroll
         for (int v = 0; v < 4; ++v) { xi[v] = 0.0; Omf[v] = Qi[v] + Cf[v]; }
     }
-    rt_barrier();                                           // (every wave has read Xk before the next patch)
+    lds_barrier();                                          // (every wave has read Xk before the next patch)
     put_c31(Xk, xi);
 
     // ---------------- forward sweep (t = T: the terminal inverse P_T = Om_f,T^-1 and f_T = P_T xi_T) ----------------------
@@ -437,7 +429,7 @@ __global__ __launch_bounds__(256, CH ? 2 : 1) void recursion_tile_kernel(Recursi
                 RT_TOCK(p_inv);
                 RT_TICK(p_p1);
                 st_tile(bufA, w, lane, Z);
-                rt_barrier();                                 // E1: Z in LDS; column 31 of Xk holds xi_t
+                lds_barrier();                                // E1: Z in LDS; column 31 of Xk holds xi_t
                 const v4d ZY0 = ld_tile(bufA, tY0, lane), ZY1 = ld_tile(bufA, tY1, lane);
                 const v4d X0 = ld_tile(Xk, tX0, lane), X1 = ld_tile(Xk, tX1, lane);
                 const v4d Jaug = mm_tn(ZY0, ZY1, X0, X1, nks, zero4);          // [J | w] = Z'[K' | xi]
@@ -464,7 +456,7 @@ __global__ __launch_bounds__(256, CH ? 2 : 1) void recursion_tile_kernel(Recursi
                     }
                     RT_TOCK(p_p1);
                     RT_TICK(p_p2);
-                    rt_barrier();                             // E2: [J | w] in LDS
+                    lds_barrier();                            // E2: [J | w] in LDS
                     const v4d JX0 = ld_tile(bufB, tX0, lane), JX1 = ld_tile(bufB, tX1, lane);
                     const v4d prod = mm_tn(KtY0, KtY1, JX0, JX1, nks, zero4);  // K [J | w]
                     const bool full = (cn[s] == N);
@@ -497,7 +489,7 @@ __global__ __launch_bounds__(256, CH ? 2 : 1) void recursion_tile_kernel(Recursi
     // ---------------- log-likelihood, EM bookkeeping ------------------------------------------------------------------
     {
         if (c31) sm[kRtRed + 4 * I + q] = qacc;
-        rt_barrier();
+        lds_barrier();
         if (tid == 0) {
             double qd = 0.0;
 #pragma unroll
@@ -507,10 +499,10 @@ __global__ __launch_bounds__(256, CH ? 2 : 1) void recursion_tile_kernel(Recursi
                 double LD = detprod.log_value();
                 if (first) LD += log(detP0) + (double)T * log(detQ);
                 if (lastc) LD += log(detOmT);
-                part[0] = nsum * kLog2PiT + ldsum + LD + ssum + qd;
+                part[0] = nsum * kLog2Pi + ldsum + LD + ssum + qd;
             } else {
                 const double LD = log(detOmT) + log(detP0) + (double)T * log(detQ) + detprod.log_value();
-                const double ll = -0.5 * (nsum * kLog2PiT + ldsum + LD + ssum + qd);
+                const double ll = -0.5 * (nsum * kLog2Pi + ldsum + LD + ssum + qd);
                 a.loglik[b] = ll;
                 if (a.ncov) a.ncov[b] = T;
                 if (a.active) em_record(a, b, ll, em_decide(a, b, ll));   // EM bookkeeping (dfm_em_epilogue.h); tile_mstep_kernel reads active
@@ -579,7 +571,7 @@ __global__ __launch_bounds__(256, CH ? 2 : 1) void recursion_tile_kernel(Recursi
             if (t <= tl && t >= s0) {                            // (uniform)
                 const bool own = !CH || t < e0;
                 st_tile(bufA, w, lane, Ps);
-                rt_barrier();                                 // E3
+                lds_barrier();                                // E3
                 const v4d PY0 = ld_tile(bufA, tY0, lane), PY1 = ld_tile(bufA, tY1, lane);
                 const v4d U = mm_tn(PY0, PY1, jx0[s], jx1[s], nks, zero4);      // U = P_s J' = Cov(f_t+1, f_t | X)
                 load_bwd_x(s, t - 2);
@@ -589,7 +581,7 @@ __global__ __launch_bounds__(256, CH ? 2 : 1) void recursion_tile_kernel(Recursi
                     for (int v = 0; v < 4; ++v) Uaug[v] = fs[v];                // column 31 := f_t+1
                 }
                 st_tile(bufB, w, lane, Uaug);
-                rt_barrier();                                 // E4
+                lds_barrier();                                // E4
                 const v4d UX0 = ld_tile(bufB, tX0, lane), UX1 = ld_tile(bufB, tX1, lane);
                 v4d Pn = mm_tn(jy0[s], jy1[s], UX0, UX1, nks, zc[s]);           // Z + J [U | f_t+1]
                 if (c31) {
@@ -683,9 +675,6 @@ constexpr int kT1Phi = 128;                        // two matrices in the regist
 constexpr int kT1Qi = kT1Phi + 4 * kRtTile;
 constexpr int kT1Cf = kT1Qi + 4 * kRtTile;         // (end of the constants: the stage starts here)
 
-// the wave's own LDS writes are visible to its later reads (one in-order queue): only the compiler must not move them
-__device__ __forceinline__ void t1_lds_fence() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-
 __device__ __forceinline__ void t1_ld_g(const double* tab, int lane, M32& m) {
 #pragma unroll
     for (int I = 0; I < 2; ++I)
@@ -758,10 +747,6 @@ __device__ __forceinline__ void t1_mm0(const M32& Y, const M32& X, int nks, M32&
     out.t[0][0] = a00; out.t[0][1] = a01; out.t[1][0] = a10; out.t[1][1] = a11;
 }
 
-__device__ __forceinline__ double t1_readlane(double x, int l) {
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(x), l), __builtin_amdgcn_readlane(__double2loint(x), l));
-}
-
 // rt_sweep_inverse in one wave: the pivot block D comes out of the registers by v_readlane (the pivot is unrolled: constant lanes),
 // the four pivot rows of the lane's two columns through 512 bytes of LDS, the A operand is the lane's own published value
 __device__ __forceinline__ double t1_sweep_inverse(double* praw, M32& m, int npiv, int q, int c) {
@@ -775,13 +760,13 @@ __device__ __forceinline__ double t1_sweep_inverse(double* praw, M32& m, int npi
             val[0] = m.t[Ik][0][vk];
             val[1] = m.t[Ik][1][vk];
             const double vd = val[Ik];
-            const double D00 = t1_readlane(vd, ck), D10 = t1_readlane(vd, 16 + ck), D20 = t1_readlane(vd, 32 + ck), D30 = t1_readlane(vd, 48 + ck);
-            const double D11 = t1_readlane(vd, 16 + ck + 1), D21 = t1_readlane(vd, 32 + ck + 1), D31 = t1_readlane(vd, 48 + ck + 1);
-            const double D22 = t1_readlane(vd, 32 + ck + 2), D32 = t1_readlane(vd, 48 + ck + 2), D33 = t1_readlane(vd, 48 + ck + 3);
+            const double D00 = uniform_lane(vd, ck), D10 = uniform_lane(vd, 16 + ck), D20 = uniform_lane(vd, 32 + ck), D30 = uniform_lane(vd, 48 + ck);
+            const double D11 = uniform_lane(vd, 16 + ck + 1), D21 = uniform_lane(vd, 32 + ck + 1), D31 = uniform_lane(vd, 48 + ck + 1);
+            const double D22 = uniform_lane(vd, 32 + ck + 2), D32 = uniform_lane(vd, 48 + ck + 2), D33 = uniform_lane(vd, 48 + ck + 3);
             if (inblk) val[Ik] = (c - ck == q) ? -1.0 : 0.0;
             praw[c * 4 + q] = val[0];
             praw[(16 + c) * 4 + q] = val[1];
-            t1_lds_fence();
+            wait_lgkmcnt0();
             const double2* pr = reinterpret_cast<const double2*>(praw);
             const double2 pa0 = pr[c * 2], pb0 = pr[c * 2 + 1], pa1 = pr[(16 + c) * 2], pb1 = pr[(16 + c) * 2 + 1];
             const double i0 = fast_rcp3(D00);
@@ -810,7 +795,7 @@ __device__ __forceinline__ double t1_sweep_inverse(double* praw, M32& m, int npi
                 const double tq0 = fma(-l30, tq3, fma(-l20, tq2, fma(-l10, tq1, p0 * i0)));
                 tq[J] = -((q & 2) ? ((q & 1) ? tq3 : tq2) : ((q & 1) ? tq1 : tq0));
             }
-            t1_lds_fence();                                      // (the rows are read before the next pivot publishes its own)
+            wait_lgkmcnt0();                                     // (the rows are read before the next pivot publishes its own)
             m.t[Ik][0][vk] = 0.0;                                // pivot rows ...
             m.t[Ik][1][vk] = 0.0;
 #pragma unroll
@@ -831,25 +816,6 @@ __device__ __forceinline__ double t1_sweep_inverse(double* praw, M32& m, int npi
             for (int v = 0; v < 4; ++v) m.t[I][J][v] = (16 * J + c < lim && 16 * I + q + 4 * v < lim) ? -m.t[I][J][v] : m.t[I][J][v];
     return det;
 }
-}  // namespace
-
-namespace {
-using t1_lds_cptr = __attribute__((address_space(3))) char*;
-// One LDS-DMA instruction: lane l copies 16 bytes from gbase + voff to LDS byte lds_dst + 16 l -- nothing lands in a VGPR until the
-// arithmetic asks for it.  gbase, lds_dst wave-uniform.  t1_dma16: lanes 0 .. 15 only (a 256-byte row).
-__device__ __forceinline__ void t1_dma(const void* gbase, unsigned voff, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(gbase), "s"(lds_dst) : "memory");
-}
-__device__ __forceinline__ void t1_dma16(const void* gbase, unsigned voff, unsigned lds_dst) {
-    unsigned keep;
-    unsigned long long ex;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b64 %1, exec\n\ts_mov_b32 m0, %4\n\ts_mov_b64 exec, 0xffff\n\tglobal_load_lds_dwordx4 %2, %3\n\t"
-                 "s_mov_b64 exec, %1\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep), "=&s"(ex) : "v"(voff), "s"(gbase), "s"(lds_dst) : "memory");
-}
-__device__ __forceinline__ void t1_wait_vm() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 constexpr int kT1QiC = kT1Qi;                      // Qi, plus Cfull where the lane's element lies outside the C_t block
 // LDS of a wave: the pivot rows, Phi, QiC, and ONE stage [rows area: a packed C_t / Z row in whole KBs of DMA (nR of them) | a 32-vector
@@ -890,7 +856,7 @@ __global__ __launch_bounds__(64, (EM ? 1 : DFM_T1_OCC)) void recursion_tile1_ker
     const bool c31 = (c == 15);                                // column 31 lives in the tiles (., 1) of these lanes
     const int stgB = t1_rows_kb(a.ct_r, rs) * 128, stgZ = stgB + 32, stgOne = stgZ + 1;   // the stage: rows | 32-vector | zero, one
     double* praw = sm + kT1Praw;
-    const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(t1_lds_cptr)(reinterpret_cast<char*>(sm)));
+    const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lds_char_ptr)(reinterpret_cast<char*>(sm)));
     int zero_v;                                                // a zero the compiler cannot see through: per-lane (vector) loads of
     asm volatile("v_mov_b32 %0, 0" : "=v"(zero_v));            // wave-uniform scalars -- their waits are vmcnt's, not the LDS queue's
 
@@ -966,9 +932,9 @@ __global__ __launch_bounds__(64, (EM ? 1 : DFM_T1_OCC)) void recursion_tile1_ker
         for (int k = 0; k < nZ; ++k) {                           // (uniform)
             unsigned vo = (unsigned)lane * 16u + ((unsigned)k << 10);
             vo = vo < rowZB - 16u ? vo : rowZB - 16u;
-            t1_dma(ent, vo, dst + ((unsigned)k << 10));
+            dma16_base(ent, vo, dst + ((unsigned)k << 10));
         }
-        t1_dma16(vsrc, (unsigned)(lane & 15) * 16u, dst + 8u * (unsigned)stgB);
+        dma16_base_row16(vsrc, (unsigned)(lane & 15) * 16u, dst + 8u * (unsigned)stgB);
     };
     auto get_packed = [&](const double* stg, M32& Zm) {
         const char* sb = reinterpret_cast<const char*>(stg);
@@ -1045,7 +1011,7 @@ __global__ __launch_bounds__(64, (EM ? 1 : DFM_T1_OCC)) void recursion_tile1_ker
                     if (!((cinm >> (8 * I + 4 * J + v)) & 1u)) Qi.t[I][J][v] += Cf.t[I][J][v];
         t1_st_s(sm + kT1QiC, lane, Qi);
         if (lane < 2) sm[kT1Stg + stgZ + lane] = (double)lane;   // the zero, the one
-        t1_lds_fence();
+        wait_lgkmcnt0();
     }
 
     // ---------------- forward sweep ----------------------------------------------------------------------------------------
@@ -1062,10 +1028,10 @@ __global__ __launch_bounds__(64, (EM ? 1 : DFM_T1_OCC)) void recursion_tile1_ker
             for (int k = 0; k < nC; ++k) {                       // (uniform)
                 unsigned vo = (unsigned)lane * 16u + ((unsigned)k << 10);
                 vo = vo < rowB - 16u ? vo : rowB - 16u;
-                t1_dma(src, vo, dst + ((unsigned)k << 10));
+                dma16_base(src, vo, dst + ((unsigned)k << 10));
             }
         }
-        t1_dma16(bcol + (size_t)t * R, (unsigned)(lane & 15) * 16u, dst + 8u * (unsigned)stgB);
+        dma16_base_row16(bcol + (size_t)t * R, (unsigned)(lane & 15) * 16u, dst + 8u * (unsigned)stgB);
     };
     auto load_scal = [&](int t) {
         t = t < T ? t : T - 1;
@@ -1129,7 +1095,7 @@ __global__ __launch_bounds__(64, (EM ? 1 : DFM_T1_OCC)) void recursion_tile1_ker
             t1_mm0(Kt, Jaug, nks, prod);                         // K [J | w]
             RT_TOCK(p_p1);
             RT_TICK(p_p2);
-            t1_wait_vm();                                        // the stage holds period t (issued a period ago)
+            wait_vmcnt<0>();                                     // the stage holds period t (issued a period ago)
             const bool full = (cn == N);
             const double* stg = sm + kT1Stg;
             M32 QiL;
@@ -1171,7 +1137,7 @@ __global__ __launch_bounds__(64, (EM ? 1 : DFM_T1_OCC)) void recursion_tile1_ker
                 nsum += (double)cn;
                 ldsum += full ? a.ldfull[b] : cl;
             }
-            t1_lds_fence();                                      // (the stage is read)
+            wait_lgkmcnt0();                                     // (the stage is read)
             RT_TOCK(p_p2);
             RT_TICK(p_p3);
             if (t >= s0) {                                       // (uniform; warm-up periods leave no entry)
@@ -1197,7 +1163,7 @@ __global__ __launch_bounds__(64, (EM ? 1 : DFM_T1_OCC)) void recursion_tile1_ker
         if (lane == 15) {
             double LD = detprod.log_value();                     // (the last chunk's includes det Om_f,T)
             if (first) LD += ldet0;
-            part[0] = nsum * kLog2PiT + ldsum + LD + ssum + qd;
+            part[0] = nsum * kLog2Pi + ldsum + LD + ssum + qd;
         }
     }
 
@@ -1238,7 +1204,7 @@ __global__ __launch_bounds__(64, (EM ? 1 : DFM_T1_OCC)) void recursion_tile1_ker
         }
     };
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");   // (the wave reads back its own table and w_t stores: one CU, one write-through L1)
-    t1_lds_fence();
+    wait_lgkmcnt0();
     auto issue_bwd = [&](int t) {
         t = t > s0 ? t : s0;
         dma_packed(tab_ent(t), w_ent(t), lds0 + 8u * (unsigned)kT1Stg);
@@ -1250,14 +1216,14 @@ __global__ __launch_bounds__(64, (EM ? 1 : DFM_T1_OCC)) void recursion_tile1_ker
         const double* ent = lastc ? ZJ + (size_t)T * 2 * RR : xZJ + (size_t)(Wk - 1) * 2 * RR;
         const double* fv = lastc ? ent + RR : xw + (size_t)(Wk - 1) * R;
         dma_packed(ent, fv, lds0 + 8u * (unsigned)kT1Stg);
-        t1_wait_vm();
+        wait_vmcnt<0>();
         const double* stg = sm + kT1Stg;
         get_packed(stg, Ps);
 #pragma unroll
         for (int I = 0; I < 2; ++I)
 #pragma unroll
             for (int v = 0; v < 4; ++v) fs[I][v] = stg[stgB + 16 * I + q + 4 * v];
-        t1_lds_fence();
+        wait_lgkmcnt0();
         issue_bwd(tl);
     }
     M32 SP, SU;
@@ -1273,7 +1239,7 @@ __global__ __launch_bounds__(64, (EM ? 1 : DFM_T1_OCC)) void recursion_tile1_ker
     for (int t = tl; t >= s0; --t) {
         const bool own = t < e0;
         RT_TICK(q_w);
-        t1_wait_vm();                                            // the stage holds step t
+        wait_vmcnt<0>();                                         // the stage holds step t
         const double* stg = sm + kT1Stg;
         M32 zc, jt, U, Pn;
         double wv[2][4];
@@ -1282,7 +1248,7 @@ __global__ __launch_bounds__(64, (EM ? 1 : DFM_T1_OCC)) void recursion_tile1_ker
         for (int I = 0; I < 2; ++I)
 #pragma unroll
             for (int v = 0; v < 4; ++v) wv[I][v] = stg[stgB + 16 * I + q + 4 * v];
-        t1_lds_fence();                                          // (the stage is read: re-arm it)
+        wait_lgkmcnt0();                                         // (the stage is read: re-arm it)
         issue_bwd(t - 1);
         if (pend >= 0) emit(pend, Ps, fs);
         RT_TOCK(q_w);
@@ -1471,7 +1437,7 @@ __device__ __forceinline__ bool rt_all(RtCtx& x, bool pred, int& par) {
     double* fl = x.sm + kRtRed + 8 * (par & 1);
     par ^= 1;
     if (x.lane == 0) fl[x.w] = wv ? 1.0 : 0.0;
-    rt_barrier();
+    lds_barrier();
     return fl[0] != 0.0 && fl[1] != 0.0 && fl[2] != 0.0 && fl[3] != 0.0;
 }
 // element (i, j) of a matrix st_tile() left in an LDS tile buffer
@@ -1524,7 +1490,7 @@ __global__ __launch_bounds__(256, 1) void cov_tile_kernel(FastArgs a, int rstate
     st_tile(bufA, w, lane, Ael);
     st_tile(bufB, w, lane, Qi);
     if (tid < R) sm[kRtRed + 16 + tid] = mu0t;
-    rt_barrier();
+    lds_barrier();
     v4d KtY0, KtY1, Phi;
     {
         const v4d A0i = ld_tile(bufA, tY0, lane), A1i = ld_tile(bufA, tY1, lane);
@@ -1534,14 +1500,14 @@ __global__ __launch_bounds__(256, 1) void cov_tile_kernel(FastArgs a, int rstate
         const v4d Kt = mm_tn(A0i, A1i, Q0j, Q1j, nks, zero4);                       // K' = A'Qi
         const v4d Km = mm_tn(Q0i, Q1i, A0j, A1j, nks, zero4);                       // K  = Qi A
         st_tile(Xk, w, lane, Kt);
-        rt_barrier();
+        lds_barrier();
         st_tile(bufB, w, lane, Km);
-        rt_barrier();
+        lds_barrier();
         const v4d K0i = ld_tile(bufB, tY0, lane), K1i = ld_tile(bufB, tY1, lane);
         Phi = mm_tn(K0i, K1i, A0j, A1j, nks, zero4);                                // Phi = K'A
         KtY0 = ld_tile(Xk, tY0, lane); KtY1 = ld_tile(Xk, tY1, lane);               // K' as Y: constant
         st_tile(bufA, w, lane, Omf);
-        rt_barrier();
+        lds_barrier();
     }
     double q0 = 0.0;
     if (w == 0) {                                              // xi_0 = Om_f,0 mu0 and mu0'xi_0: one row per lane (lanes 32.. idle)
@@ -1568,14 +1534,14 @@ __global__ __launch_bounds__(256, 1) void cov_tile_kernel(FastArgs a, int rstate
         for (int v = 0; v < 4; ++v) Z[v] = Omf[v] + Phi[v];
         const double detM = rt_sweep_inverse(x, Z, npiv);       // (its barriers: every wave is done with bufA / bufB of the last step)
         st_tile(bufA, w, lane, Z);
-        rt_barrier();
+        lds_barrier();
         const v4d ZY0 = ld_tile(bufA, tY0, lane), ZY1 = ld_tile(bufA, tY1, lane);
         const v4d ZX0 = ld_tile(bufA, tX0, lane), ZX1 = ld_tile(bufA, tX1, lane);
         const v4d X0 = ld_tile(Xk, tX0, lane), X1 = ld_tile(Xk, tX1, lane);
         const v4d Jm = mm_tn(ZY0, ZY1, X0, X1, nks, zero4);    // J = Z K'
         const v4d Gm = mm_tn(KtY0, KtY1, ZX0, ZX1, nks, zero4);   // G = K Z
         st_tile(bufB, w, lane, Jm);
-        rt_barrier();
+        lds_barrier();
         const v4d JX0 = ld_tile(bufB, tX0, lane), JX1 = ld_tile(bufB, tX1, lane);
         const v4d KJ = mm_tn(KtY0, KtY1, JX0, JX1, nks, zero4);
         v4d Omn;
@@ -1607,7 +1573,7 @@ __global__ __launch_bounds__(256, 1) void cov_tile_kernel(FastArgs a, int rstate
     if (tid == 0) {
         const double sum_ldz = -(detprod.log_value() + (double)(T - E) * log(detM_last));
         const double LD = log(detOmT) + log(detP0) + (double)T * log(detQ) - sum_ldz;
-        a.llc[b] = (double)a.N * (double)T * kLog2PiF + (double)T * a.ldfull[b] + LD + q0;
+        a.llc[b] = (double)a.N * (double)T * kLog2Pi + (double)T * a.ldfull[b] + LD + q0;
         a.E[b] = E;
     }
 
@@ -1647,7 +1613,7 @@ __global__ __launch_bounds__(256, 1) void cov_tile_kernel(FastArgs a, int rstate
             st_tile(Xk, w, lane, Gc);                            // (K' is done with)
         }
         st_tile(bufA, w, lane, Ps);
-        rt_barrier();
+        lds_barrier();
         if (reload) {
             GX0 = ld_tile(Xk, tX0, lane); GX1 = ld_tile(Xk, tX1, lane);
             GY0 = ld_tile(Xk, tY0, lane); GY1 = ld_tile(Xk, tY1, lane);
@@ -1655,7 +1621,7 @@ __global__ __launch_bounds__(256, 1) void cov_tile_kernel(FastArgs a, int rstate
         const v4d PY0 = ld_tile(bufA, tY0, lane), PY1 = ld_tile(bufA, tY1, lane);
         const v4d U = mm_tn(PY0, PY1, GX0, GX1, nks, zero4);   // U = P_s J'
         st_tile(bufB, w, lane, U);
-        rt_barrier();
+        lds_barrier();
         const v4d UX0 = ld_tile(bufB, tX0, lane), UX1 = ld_tile(bufB, tX1, lane);
         const v4d Psn = mm_tn(GY0, GY1, UX0, UX1, nks, Zc);    // Z + J U
         bool same = true;
@@ -1691,12 +1657,12 @@ __global__ __launch_bounds__(256, 1) void cov_tile_kernel(FastArgs a, int rstate
         auto square2 = [&]() {
             st_tile(bufA, w, lane, MG);
             st_tile(bufB, w, lane, MJ);
-            rt_barrier();
+            lds_barrier();
             const v4d gY0 = ld_tile(bufA, tY0, lane), gY1 = ld_tile(bufA, tY1, lane), gX0 = ld_tile(bufA, tX0, lane), gX1 = ld_tile(bufA, tX1, lane);
             const v4d jY0 = ld_tile(bufB, tY0, lane), jY1 = ld_tile(bufB, tY1, lane), jX0 = ld_tile(bufB, tX0, lane), jX1 = ld_tile(bufB, tX1, lane);
             MG = mm_tn(jY0, jY1, gX0, gX1, nks, zero4);        // J'G = G G
             MJ = mm_tn(gY0, gY1, jX0, jX1, nks, zero4);        // G'J = J J
-            rt_barrier();                                      // (the buffers are free again)
+            lds_barrier();                                     // (the buffers are free again)
         };
         for (int l = 1; l < a.L; l <<= 1) square2();             // M^L
 #pragma unroll 1

@@ -32,7 +32,6 @@ namespace dfm {
 
 namespace {
 
-constexpr double kLog2PiW = 1.8378770664093454835606594728112;
 // periods per prefetch chunk at Rp = 8: 8 when the batch leaves at most one wave per SIMD (the deeper prefetch hides more of
 // the chain's memory latency: 0.86 vs 1.07 ms per 1024 replicates), 4 beyond that -- 212 instead of 310 registers, so TWO
 // waves share a SIMD and fill each other's waits (B = 2048: 1.26 ms with chunks of 4, 1.72 ms in two rounds of chunks of 8)
@@ -287,7 +286,7 @@ __global__ __launch_bounds__(R * R, (R == 16 ? DFM_WG16_WAVES : 1)) void recursi
         const double qd = G.sum_i(G.sum_j(part));
         const double LD = COV ? detprod.log_value()
                               : log(detOmT) + log(detP0) + (double)T * log(detQ) + detprod.log_value();   // sum_ldz = -log prod
-        const double ll = -0.5 * (nsum * kLog2PiW + ldsum + LD + ssum + qd);
+        const double ll = -0.5 * (nsum * kLog2Pi + ldsum + LD + ssum + qd);
         if (lane == 0) {
             a.loglik[b] = ll;
             if (a.ncov) a.ncov[b] = e + 1;

@@ -37,24 +37,6 @@ constexpr int kS3PF = 4;                           // operand prefetch distance 
 #define DFM_S3_PF1 8
 #endif
 constexpr int kS3PF1 = DFM_S3_PF1;                 // ... of the zero-state runs (no Z operand, no emission: registers to spare)
-typedef double s3_v4 __attribute__((ext_vector_type(4)));
-// workgroup barrier for data that travels through LDS only: __syncthreads() also waits for every outstanding global access
-// (vmcnt(0)) -- here that would be the prefetched operands of later steps and the asynchronous staging
-__device__ __forceinline__ void s3_barrier_lds() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-using s3_lds_ptr = __attribute__((address_space(3))) char*;
-// 64 lanes x 16 bytes, global -> LDS (1 KB back to back from byte address `lds_dst`), asynchronous: counted by vmcnt
-__device__ __forceinline__ void s3_dma16(const void* gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %2\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, off\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(gsrc), "s"(lds_dst)
-        : "memory");
-}
 
 template <int R>
 struct S3Geo {
@@ -96,7 +78,7 @@ __device__ __forceinline__ void load_aop(double (&A)[R / 16][R / 4], const doubl
 
 // Y = M X (+ Y0): X, Y in the D layout of the MFMA (X[it][v] = element (K + 4 v + 16 it, column j) of lane (K, j))
 template <int R>
-__device__ __forceinline__ void mm_step(const double (&A)[R / 16][R / 4], const s3_v4 (&X)[R / 16], s3_v4 (&Y)[R / 16]) {
+__device__ __forceinline__ void mm_step(const double (&A)[R / 16][R / 4], const v4d (&X)[R / 16], v4d (&Y)[R / 16]) {
 #pragma unroll
     for (int s = 0; s < R / 4; ++s) {
 #pragma unroll
@@ -157,7 +139,7 @@ __global__ __launch_bounds__(S3Geo<R>::NT, (R == 16 ? 4 : 1)) void meanscan_mfma
     stamp();
 
     constexpr int NW = kS3Threads / 64;
-    const unsigned lds_dsm = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(s3_lds_ptr)dsm);
+    const unsigned lds_dsm = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lds_char_ptr)dsm);
     // carry powers of one direction -> LDS (row stride kS3PS), ASYNCHRONOUSLY: 1-KB LDS-DMA pieces dealt to the waves; the 16 bytes
     // of lane l of piece i are LDS doubles 128 i + 2 l, 128 i + 2 l + 1 = columns (c, c + 1) of row (level k, r) -- c = R is the
     // padding pair, it re-reads the row's last pair.  The carry scan waits for them (vmcnt(0) + barrier) a whole phase later; the
@@ -173,10 +155,9 @@ __global__ __launch_bounds__(S3Geo<R>::NT, (R == 16 ? 4 : 1)) void meanscan_mfma
             const int krc = kr < kS3Lev * R ? kr : kS3Lev * R - 1;
             const double* src = src0 + (size_t)krc * R + (col < R ? col : R - 2);
             const unsigned dst = __builtin_amdgcn_readfirstlane(lds_dsm + (unsigned)(S3Lds::oPow * 8 + 1024 * i));
-            if (byte < bytes) s3_dma16(src, dst);
+            if (byte < bytes) dma16(src, dst);
         }
     };
-    auto powers_landed = [&]() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); };   // (then a barrier: every wave's pieces)
     // ---- forward transient, steps 0 .. ts - 1 (time-varying Z_t, G_t: 8 KB each per step): the chain xi_(t+1) = G_t xi_t + b_t on
     // the even waves, w_t = Z_t xi_t (off the chain) on the odd ones, step t on waves 2 t and 2 t + 1 (mod NW) -- every wave
     // fetches the one matrix of its first step NOW, all at once, and the one of its next step as soon as it has used the last
@@ -207,8 +188,8 @@ __global__ __launch_bounds__(S3Geo<R>::NT, (R == 16 ? 4 : 1)) void meanscan_mfma
         // ---- P_smooth rows inside the fixed-point range: fire-and-forget stores (unless pfill_kernel wrote them)
         fill_psmooth_rows(a, b, tid, kS3Threads, s_ps);
     }
-    if (a.abl & 2) { powers_landed(); return; }
-    s3_barrier_lds();
+    if (a.abl & 2) { wait_vmcnt<0>(); return; }
+    lds_barrier();
 
     stamp();   // 1: staging done
     double dot = 0.0;                                         // lane part of sum_t xi_t' w_t
@@ -228,7 +209,7 @@ __global__ __launch_bounds__(S3Geo<R>::NT, (R == 16 ? 4 : 1)) void meanscan_mfma
             tn += NW / 2;
             preload_fwd(tn);
         }
-        s3_barrier_lds();
+        lds_barrier();
     }
 
     stamp();   // 2: forward transient done
@@ -251,7 +232,7 @@ __global__ __launch_bounds__(S3Geo<R>::NT, (R == 16 ? 4 : 1)) void meanscan_mfma
         auto step_t = [&](int j) { return FWD ? t0 + j : t0 - j; };
         auto valid_t = [&](int j) { const int t = step_t(j); return j < L && t >= ts && t < T; };
         // operands of step j in the D layout
-        auto load_u = [&](s3_v4 (&U)[NIO], int j) {
+        auto load_u = [&](v4d (&U)[NIO], int j) {
             int t = step_t(j);
             t = t < ts ? ts : (t >= T ? T - 1 : t);           // (a row that exists; the step is skipped when invalid)
             const double2* p;
@@ -271,10 +252,10 @@ __global__ __launch_bounds__(S3Geo<R>::NT, (R == 16 ? 4 : 1)) void meanscan_mfma
                 U[io][0] = x.x; U[io][1] = x.y; U[io][2] = y.x; U[io][3] = y.y;
             }
         };
-        auto run = [&](s3_v4 (&X)[NIO], auto emit_tag) {
+        auto run = [&](v4d (&X)[NIO], auto emit_tag) {
             constexpr bool EMIT = decltype(emit_tag)::value;
             constexpr int PF = (EMIT || R < 32) ? kS3PF : kS3PF1;
-            s3_v4 cur[PF][NIO];                                 // ring of operands, PF steps ahead (slot u refilled once consumed)
+            v4d cur[PF][NIO];                                   // ring of operands, PF steps ahead (slot u refilled once consumed)
 #pragma unroll
             for (int u = 0; u < PF; ++u) load_u(cur[u], u);
             for (int j0 = 0; j0 < L; j0 += PF) {
@@ -285,9 +266,9 @@ __global__ __launch_bounds__(S3Geo<R>::NT, (R == 16 ? 4 : 1)) void meanscan_mfma
                         const bool ok = valid_t(j);
                         const int t = step_t(j);
                         if constexpr (EMIT && FWD) {          // w_t = Z xi_t, xi_t' w_t
-                            s3_v4 W[NIO];
+                            v4d W[NIO];
 #pragma unroll
-                            for (int io = 0; io < NIO; ++io) W[io] = s3_v4{0.0, 0.0, 0.0, 0.0};
+                            for (int io = 0; io < NIO; ++io) W[io] = v4d{0.0, 0.0, 0.0, 0.0};
                             mm_step<R>(AZ, X, W);
                             if (ok) {
                                 double2* q = wch + ((size_t)(wave * L + j) * NPc) * 64 + lane;
@@ -300,7 +281,7 @@ __global__ __launch_bounds__(S3Geo<R>::NT, (R == 16 ? 4 : 1)) void meanscan_mfma
                                 }
                             }
                         }
-                        s3_v4 Y[NIO];
+                        v4d Y[NIO];
 #pragma unroll
                         for (int io = 0; io < NIO; ++io) Y[io] = cur[u][io];
                         load_u(cur[u], j + PF);
@@ -330,14 +311,14 @@ __global__ __launch_bounds__(S3Geo<R>::NT, (R == 16 ? 4 : 1)) void meanscan_mfma
                 }
             }
         };
-        auto from_vec = [&](s3_v4 (&X)[NIO], const double* vsrc, bool take) {
+        auto from_vec = [&](v4d (&X)[NIO], const double* vsrc, bool take) {
 #pragma unroll
             for (int io = 0; io < NIO; ++io)
 #pragma unroll
                 for (int v = 0; v < 4; ++v) X[io][v] = take ? vsrc[s3_pi<R>(K, v, io)] : 0.0;
         };
         // phase 1: chunk 0 from the true start (its end state then carries the head through the scan), the others from zero
-        s3_v4 X[NIO];
+        v4d X[NIO];
         from_vec(X, s_vec + head, ch == 0);
         run(X, std::false_type{});
         stamp();   // 3 / 7: phase 1 done
@@ -349,14 +330,14 @@ __global__ __launch_bounds__(S3Geo<R>::NT, (R == 16 ? 4 : 1)) void meanscan_mfma
                 for (int v = 0; v < 4; ++v) s_P[ch * kS3PS + K + 4 * v + 16 * io] = X[io][v];
         };
         put_state();
-        powers_landed();
+        wait_vmcnt<0>();                                           // the powers have landed (then a barrier: every wave's pieces)
         __syncthreads();
 #pragma unroll 1
         for (int k = 0; k < kS3Lev; ++k) {
             double AP[NIO][R / 4];
             load_aop<R>(AP, s_pow + (size_t)k * R * kS3PS, kS3PS, K, j16);
             const int src = ch - (1 << k);
-            s3_v4 Bv[NIO];                                     // the state 2^k columns to the left, as the B operand (= D layout)
+            v4d Bv[NIO];                                       // the state 2^k columns to the left, as the B operand (= D layout)
 #pragma unroll
             for (int io = 0; io < NIO; ++io)
 #pragma unroll
@@ -435,7 +416,7 @@ __global__ __launch_bounds__(S3Geo<R>::NT, (R == 16 ? 4 : 1)) void meanscan_mfma
                 kn += NW;
                 preload_bwd(kn);
             }
-            s3_barrier_lds();
+            lds_barrier();
         }
         if (ts == 0 && wave == 0 && cg == 0 && a.f0s) a.f0s[(size_t)b * R + i32] = s_vec[3 * R + i32];
     }
