@@ -1,7 +1,8 @@
-// dfm_cellgeom.h -- launch geometry of the post-estimation cell kernels (forecast.hip, simsmooth.hip, news.hip, structural.hip) and
-// the two dispatchers their launchers share.  Plain C++17 with no HIP include: the launchers call it, the kernels read the CellGeom
-// it returns through their argument struct, and tests/host/cellgeom_host.cpp compiles it for the CPU, where
-// tests/test_post_geometry_cpu.py and tests/test_structural_cpu.py hold the Python restatement of tests/post_geometry.py and
+// dfm_cellgeom.h -- launch geometry of the post-estimation cell kernels (forecast.hip, filter.hip, simsmooth.hip, news.hip,
+// structural.hip, proxy.hip), the rule for their 16-byte cell path (cell_vec, cell_sp) and the two dispatchers their launchers
+// share.  Plain C++17 with no HIP include: the launchers call it, the kernels read the CellGeom it returns through their argument
+// struct, and tests/host/cellgeom_host.cpp compiles it for the CPU, where tests/test_post_geometry_cpu.py, tests/test_filter_cpu.py
+// and tests/test_structural_cpu.py hold the Python restatements of tests/post_geometry.py, tests/filter_expect.py and
 // tests/structural_geometry.py against it.
 #pragma once
 #include <stddef.h>
@@ -21,6 +22,14 @@ struct CellGeom {
 constexpr int kCellBlockLanes = 256;          // lanes of one series block, at most
 
 inline bool al16(const void* q) { return ((uintptr_t)q & 15) == 0; }
+
+// The 16-byte cell path: N even and every pointer the kernel moves cells through 16-byte aligned (a null pointer -- an output not
+// asked for -- counts as aligned).  cell_vec: the VEC of the pair kernels.  cell_sp: the series per lane of the SP kernels, two on
+// that path while the loadings' register bucket RB is at most 16.
+template <class... P>
+inline bool cell_vec(int N, const P*... ptrs) { return (N & 1) == 0 && (al16(ptrs) && ...); }
+template <class... P>
+inline int cell_sp(int N, int RB, const P*... ptrs) { return RB <= 16 && cell_vec(N, ptrs...) ? 2 : 1; }
 
 // A cell kernel streams a [rows][N] output from loadings in registers and rows of row_doubles doubles staged in LDS.  `lanes` (one
 // series or one pair of series each) are split into blocks of at most 256; the workgroup is G x NPB lanes rounded up to whole

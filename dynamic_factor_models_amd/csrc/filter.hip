@@ -12,6 +12,7 @@
 //             loglik_t = -1/2 [n_t log 2 pi + ld_t + log det W + s_t - 2 b_t' f_p + f_p' C_t f_p - a' P11 G^-1 a]
 // Nothing but W is factorised: Q, P_p and C_t may be singular.  filter_fill_kernel streams the prediction errors of every cell,
 // filter_eval_kernel the h-step forecast errors of every origin and their means over origins.
+#include "dfm_cell.h"
 #include "dfm_kernels.h"
 #include "dfm_smallmat.h"
 
@@ -282,80 +283,53 @@ template <int RB, int SP>
 __global__ __launch_bounds__(kFtFillMaxThreads) void filter_fill_kernel(FtArgs a) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int r = a.r, k = a.r * a.p, T = a.T, tid = threadIdx.x, np = r * (r + 1) / 2, kk = k * (k + 1) / 2;
-    unsigned blk = blockIdx.x;
-    const int s = (int)(blk % (unsigned)a.geo.nsblk); blk /= (unsigned)a.geo.nsblk;
-    const int c = (int)(blk % (unsigned)a.geo.nchunk);
-    const size_t b = blk / (unsigned)a.geo.nchunk;
-    const int t0 = c * a.geo.RC, t1 = t0 + a.geo.RC < T ? t0 + a.geo.RC : T, nt = t1 - t0;
+    const CellChunk ch = cell_chunk(a.geo, blockIdx.x, T);
+    const size_t b = ch.outer;
+    const int t0 = ch.t0, t1 = ch.t1;
     double* sf = sm;
     double* sP = sm + (size_t)a.geo.RC * r;
     const bool wantStd = a.vstd != nullptr, needX = a.verr != nullptr || wantStd;
-    for (int e = tid; e < nt * r; e += blockDim.x) sf[e] = a.z_pred[(b * T + t0 + e / r) * k + e % r];
-    if (wantStd)
-        for (int e = tid; e < nt * np; e += blockDim.x) sP[e] = a.P_pred[(b * T + t0 + e / np) * kk + e % np];
+    cell_stage(sf, a.z_pred + (b * T + t0) * k, t1 - t0, r, k);
+    if (wantStd) cell_stage(sP, a.P_pred + (b * T + t0) * kk, t1 - t0, np, kk);
     __syncthreads();
-    const int j = tid % a.geo.NPB, g = tid / a.geo.NPB;
-    if (g >= a.geo.G) return;
-    const int i0 = (s * a.geo.NPB + j) * SP;
-    if (i0 >= a.N) return;                                  // (SP = 2 only for even N: i0 + 1 < N)
+    const CellLane ln = cell_lane<SP>(a.geo, tid, ch.s, a.N);
+    if (!ln.live) return;
+    const int i0 = ln.i0;
     const bool scale = a.mean != nullptr;
-    double lam[SP][RB], Rv[SP], mu[SP], sd[SP];
+    CellLam<SP, RB> lam;
+    lam.load(a.Lam, b, a.N, i0, r);
+    double Rv[SP], mu[SP], sd[SP];
 #pragma unroll
     for (int q = 0; q < SP; ++q) {
         const size_t bi = b * a.N + i0 + q;
-#pragma unroll
-        for (int m = 0; m < RB; ++m) lam[q][m] = m < r ? a.Lam[bi * r + m] : 0.0;
         Rv[q] = wantStd ? a.R[bi] : 0.0;
         mu[q] = scale ? a.mean[bi] : 0.0;
         sd[q] = scale ? a.sd[bi] : 1.0;
     }
-    for (int t = t0 + g; t < t1; t += a.geo.G) {
+    for (int t = t0 + ln.g; t < t1; t += a.geo.G) {
         const double* f = sf + (size_t)(t - t0) * r;
         const double* P = sP + (size_t)(t - t0) * np;
         const size_t o = (b * T + t) * a.N + i0;
         double x[SP];
 #pragma unroll
         for (int q = 0; q < SP; ++q) x[q] = 0.0;
-        if (needX) {
-            if constexpr (SP == 2) {
-                const double2 v = *reinterpret_cast<const double2*>(a.panel + o);
-                x[0] = v.x; x[1] = v.y;
-            } else {
-                x[0] = a.panel[o];
-            }
-        }
+        if (needX) cell_ld<SP>(a.panel + o, x);
         double xp[SP], ve[SP], vs[SP];
 #pragma unroll
         for (int q = 0; q < SP; ++q) {
-            double m = 0.0;
-#pragma unroll
-            for (int l = 0; l < RB; ++l)
-                if (l < r) m += lam[q][l] * f[l];
+            const double m = lam.dot(q, f, r);
             double qf = 0.0;
             if (wantStd) {
-#pragma unroll
-                for (int jj = 0; jj < RB; ++jj)
-                    if (jj < r) {
-                        double u = 0.0;
-#pragma unroll
-                        for (int l = 0; l < jj; ++l) u += P[jj * (jj + 1) / 2 + l] * lam[q][l];
-                        qf += lam[q][jj] * (P[jj * (jj + 1) / 2 + jj] * lam[q][jj] + 2.0 * u);
-                    }
+                DFM_CELL_QUAD(qf, lam.l[q], P, RB, r)
             }
             const double e = x[q] - m;                      // NaN on a missing cell
             xp[q] = scale ? mu[q] + sd[q] * m : m;
             ve[q] = scale ? sd[q] * e : e;
             vs[q] = e / sqrt(qf + Rv[q]);
         }
-        if constexpr (SP == 2) {
-            if (a.xpred) *reinterpret_cast<double2*>(a.xpred + o) = double2{xp[0], xp[1]};
-            if (a.verr) *reinterpret_cast<double2*>(a.verr + o) = double2{ve[0], ve[1]};
-            if (wantStd) *reinterpret_cast<double2*>(a.vstd + o) = double2{vs[0], vs[1]};
-        } else {
-            if (a.xpred) a.xpred[o] = xp[0];
-            if (a.verr) a.verr[o] = ve[0];
-            if (wantStd) a.vstd[o] = vs[0];
-        }
+        if (a.xpred) cell_st<SP>(a.xpred + o, xp);
+        if (a.verr) cell_st<SP>(a.verr + o, ve);
+        if (wantStd) cell_st<SP>(a.vstd + o, vs);
     }
 }
 
@@ -366,19 +340,11 @@ hipError_t launch_filter_fill(FtArgs a, hipStream_t s) {
     return dispatch_r_bucket(a.r, [&](auto RBc) -> hipError_t {
         constexpr int RB = decltype(RBc)::value;
         const int r = a.r;
-        const int SP = ((a.N & 1) == 0 && RB <= 16 && al16(a.panel) && al16(a.xpred) && al16(a.verr) && al16(a.vstd)) ? 2 : 1;
+        const int SP = cell_sp(a.N, RB, a.panel, a.xpred, a.verr, a.vstd);
         a.geo = cell_geometry((a.N + SP - 1) / SP, r + r * (r + 1) / 2, a.T, kFtFillMaxThreads, kFtFillLds);
         const size_t lds = (size_t)a.geo.RC * (r + r * (r + 1) / 2) * sizeof(double);
-        const size_t blocks = (size_t)a.B * a.geo.nchunk * a.geo.nsblk;
-        if (blocks > 0x7fffffffu) return hipErrorInvalidValue;
-        if constexpr (RB <= 16) {
-            if (SP == 2) {
-                hipLaunchKernelGGL((filter_fill_kernel<RB, 2>), dim3((unsigned)blocks), dim3(a.geo.threads), lds, s, a);
-                return hipGetLastError();
-            }
-        }
-        hipLaunchKernelGGL((filter_fill_kernel<RB, 1>), dim3((unsigned)blocks), dim3(a.geo.threads), lds, s, a);
-        return hipGetLastError();
+        return cell_launch_sp<RB>(filter_fill_kernel<RB, 1>, filter_fill_kernel<RB, cell_sp_max(RB)>, SP,
+                                  (size_t)a.B * a.geo.nchunk * a.geo.nsblk, a.geo.threads, lds, s, a);
     });
 }
 
@@ -402,9 +368,8 @@ __global__ __launch_bounds__(256) void filter_eval_kernel(FtArgs a) {
     for (int e = tid; e < r * k; e += blockDim.x) sA[e] = a.A[b * r * k + e];
     const int i = s * 256 + tid;
     const bool own = i < N;
-    double lam[RB];
-#pragma unroll
-    for (int m = 0; m < RB; ++m) lam[m] = (own && m < r) ? a.Lam[(b * N + i) * r + m] : 0.0;
+    CellLam<1, RB> lam;
+    lam.load(a.Lam, b, N, i, r, own ? 1 : 0);
     const int last = T - 2;                        // the last origin that has a row behind it
     bool first = true;
     for (int c0 = a.t0; c0 <= last; c0 += kFtEvalChunk) {
@@ -436,11 +401,7 @@ __global__ __launch_bounds__(256) void filter_eval_kernel(FtArgs a) {
                     if (th >= T) break;
                     const double x = a.panel[(b * T + th) * N + i];
                     if (x == x) {
-                        double m = 0.0;
-#pragma unroll
-                        for (int l = 0; l < RB; ++l)
-                            if (l < r) m += lam[l] * nxt[o * k + l];
-                        const double e = x - m;
+                        const double e = x - lam.dot(0, nxt + o * k, r);
                         s1 += e * e;
                         s0 += x * x;
                         ++n;

@@ -12,6 +12,7 @@
 // At r <= 8 (K = 8 + 36) the VALU does them in the shadow of the stores: one workgroup owns a replicate's chunk of rows and a
 // block of series, stages the chunk's f_t / P_t rows in LDS (every lane of a wave reads the same address: a broadcast), keeps its
 // series' loadings in registers and writes 16 bytes per lane (two adjacent series) when N is even.
+#include "dfm_cell.h"
 #include "dfm_kernels.h"
 
 namespace dfm {
@@ -94,15 +95,13 @@ __global__ __launch_bounds__(kFcFillMaxThreads) void forecast_fill_kernel(FcFill
     constexpr int NP = R * (R + 1) / 2;
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int TH = a.T + a.H, tid = threadIdx.x;
-    unsigned blk = blockIdx.x;
-    const int s = (int)(blk % (unsigned)a.geo.nsblk); blk /= (unsigned)a.geo.nsblk;
-    const int c = (int)(blk % (unsigned)a.geo.nchunk);
-    const size_t b = blk / (unsigned)a.geo.nchunk;
-    const int t0 = c * a.geo.RC, t1 = t0 + a.geo.RC < TH ? t0 + a.geo.RC : TH, nt = t1 - t0;
+    const CellChunk ch = cell_chunk(a.geo, blockIdx.x, TH);
+    const size_t b = ch.outer;
+    const int t0 = ch.t0, t1 = ch.t1, nt = t1 - t0;
     double* sf = sm;
     double* sP = sm + (size_t)a.geo.RC * R;
     const bool loadP = a.Ph != nullptr, wantVar = a.xvar != nullptr;
-    const bool copy = s == 0 && a.f_out != nullptr;
+    const bool copy = ch.s == 0 && a.f_out != nullptr;
     // the chunk's factor rows (contiguous in both sources); series block 0 also writes them to the caller's T + H row layout
     for (int e = tid; e < nt * R; e += blockDim.x) {
         const int t = t0 + e / R, k = e % R;
@@ -118,33 +117,26 @@ __global__ __launch_bounds__(kFcFillMaxThreads) void forecast_fill_kernel(FcFill
             if (copy && a.P_out) a.P_out[(b * TH + t) * NP + k] = v;
         }
     __syncthreads();
-    const int j = tid % a.geo.NPB, g = tid / a.geo.NPB;
-    if (g >= a.geo.G) return;
-    const int i0 = (s * a.geo.NPB + j) * SP;
-    if (i0 >= a.N) return;                                  // (SP = 2 only for even N: i0 + 1 < N)
+    const CellLane ln = cell_lane<SP>(a.geo, tid, ch.s, a.N);
+    if (!ln.live) return;
+    const int i0 = ln.i0;
     const bool scale = a.mean != nullptr;
-    double lam[SP][R], Rv[SP], mu[SP], sd[SP];
+    CellLam<SP, R> lam;
+    lam.load(a.Lam, b, a.N, i0, R);
+    double Rv[SP], mu[SP], sd[SP];
 #pragma unroll
     for (int q = 0; q < SP; ++q) {
         const size_t bi = b * a.N + i0 + q;
-#pragma unroll
-        for (int k = 0; k < R; ++k) lam[q][k] = a.Lam[bi * R + k];
         Rv[q] = wantVar ? a.R[bi] : 0.0;
         mu[q] = scale ? a.mean[bi] : 0.0;
         sd[q] = scale ? a.sd[bi] : 1.0;
     }
-    for (int t = t0 + g; t < t1; t += a.geo.G) {
+    for (int t = t0 + ln.g; t < t1; t += a.geo.G) {
         const double* f = sf + (size_t)(t - t0) * R;
         const double* P = sP + (size_t)(t - t0) * NP;
         double x[SP];
         if (t < a.T) {
-            const double* px = a.panel + (b * a.panel_rows + t) * a.N + i0;
-            if constexpr (SP == 2) {
-                const double2 v = *reinterpret_cast<const double2*>(px);
-                x[0] = v.x; x[1] = v.y;
-            } else {
-                x[0] = px[0];
-            }
+            cell_ld<SP>(a.panel + (b * a.panel_rows + t) * a.N + i0, x);
         } else {
 #pragma unroll
             for (int q = 0; q < SP; ++q) x[q] = __builtin_nan("");
@@ -152,18 +144,10 @@ __global__ __launch_bounds__(kFcFillMaxThreads) void forecast_fill_kernel(FcFill
         double xh[SP], xv[SP], cm[SP];
 #pragma unroll
         for (int q = 0; q < SP; ++q) {
-            double m = 0.0;
-#pragma unroll
-            for (int k = 0; k < R; ++k) m += lam[q][k] * f[k];
+            const double m = lam.dot(q, f, R);
             double qf = 0.0;
             if (wantVar) {
-#pragma unroll
-                for (int jj = 0; jj < R; ++jj) {
-                    double u = 0.0;
-#pragma unroll
-                    for (int kk = 0; kk < jj; ++kk) u += P[jj * (jj + 1) / 2 + kk] * lam[q][kk];
-                    qf += lam[q][jj] * (P[jj * (jj + 1) / 2 + jj] * lam[q][jj] + 2.0 * u);
-                }
+                DFM_CELL_QUAD(qf, lam.l[q], P, R, R)
             }
             const bool obs = x[q] == x[q];
             cm[q] = scale ? mu[q] + sd[q] * m : m;
@@ -171,15 +155,9 @@ __global__ __launch_bounds__(kFcFillMaxThreads) void forecast_fill_kernel(FcFill
             xv[q] = obs ? 0.0 : (scale ? sd[q] * sd[q] * (qf + Rv[q]) : qf + Rv[q]);
         }
         const size_t o = (b * TH + t) * a.N + i0;
-        if constexpr (SP == 2) {
-            *reinterpret_cast<double2*>(a.xhat + o) = double2{xh[0], xh[1]};
-            if (wantVar) *reinterpret_cast<double2*>(a.xvar + o) = double2{xv[0], xv[1]};
-            if (a.common) *reinterpret_cast<double2*>(a.common + o) = double2{cm[0], cm[1]};
-        } else {
-            a.xhat[o] = xh[0];
-            if (wantVar) a.xvar[o] = xv[0];
-            if (a.common) a.common[o] = cm[0];
-        }
+        cell_st<SP>(a.xhat + o, xh);
+        if (wantVar) cell_st<SP>(a.xvar + o, xv);
+        if (a.common) cell_st<SP>(a.common + o, cm);
     }
 }
 
@@ -200,19 +178,11 @@ hipError_t launch_forecast_pad(int B, int T, int H, int N, const double* panel, 
 // A lane per SP series; a staged row is f_t and the packed P_t (cell_geometry, dfm_cellgeom.h).
 template <int R>
 static hipError_t launch_fill_r(FcFillArgs a, hipStream_t s) {
-    const int SP = ((a.N & 1) == 0 && R <= 16 && al16(a.panel) && al16(a.xhat) && al16(a.xvar) && al16(a.common)) ? 2 : 1;
+    const int SP = cell_sp(a.N, R, a.panel, a.xhat, a.xvar, a.common);
     a.geo = cell_geometry((a.N + SP - 1) / SP, R + R * (R + 1) / 2, a.T + a.H, kFcFillMaxThreads, kFcFillLds);
     const size_t lds = (size_t)a.geo.RC * (R + R * (R + 1) / 2) * sizeof(double);
-    const size_t blocks = (size_t)a.B * a.geo.nchunk * a.geo.nsblk;
-    if (blocks > 0x7fffffffu) return hipErrorInvalidValue;
-    if constexpr (R <= 16) {
-        if (SP == 2) {
-            hipLaunchKernelGGL((forecast_fill_kernel<R, 2>), dim3((unsigned)blocks), dim3(a.geo.threads), lds, s, a);
-            return hipGetLastError();
-        }
-    }
-    hipLaunchKernelGGL((forecast_fill_kernel<R, 1>), dim3((unsigned)blocks), dim3(a.geo.threads), lds, s, a);
-    return hipGetLastError();
+    return cell_launch_sp<R>(forecast_fill_kernel<R, 1>, forecast_fill_kernel<R, cell_sp_max(R)>, SP,
+                             (size_t)a.B * a.geo.nchunk * a.geo.nsblk, a.geo.threads, lds, s, a);
 }
 
 hipError_t launch_forecast_fill(const FcFillArgs& a, hipStream_t s) {

@@ -12,6 +12,7 @@
 // results do not depend on scheduling), stages the r-vectors of its rows in LDS, keeps the loadings of its two columns in
 // registers and moves 16 bytes per lane where N is even.  blockIdx.x is the pass replicate: the G targets of a replicate run next
 // to each other, so the panels they share come from L2 / the Infinity Cache.
+#include "dfm_cell.h"
 #include "dfm_kernels.h"
 
 namespace dfm {
@@ -176,67 +177,39 @@ template <int RB, bool VEC>
 __global__ __launch_bounds__(kNwMaxThreads) void news_cov_panel_kernel(NwArgs a) {
     extern __shared__ __attribute__((aligned(16))) double sav[];
     const int r = a.r, N = a.N, T = a.T, tid = threadIdx.x;
-    const int s = blockIdx.x, c = blockIdx.y, sb = blockIdx.z;
+    const int s = blockIdx.x;
+    const CellChunk ch = cell_chunk(a.geo, blockIdx.z, blockIdx.y, s, T);
     const long long j = a.j0 + s;
     const size_t b = (size_t)(j / a.G);
     const int gi = (int)(j % a.G);
-    const int t0 = c * a.geo.RC, t1 = t0 + a.geo.RC < T ? t0 + a.geo.RC : T;
-    const double* AV = a.av + (size_t)s * T * r;
-    for (int e = tid; e < (t1 - t0) * r; e += blockDim.x) sav[e] = AV[(size_t)t0 * r + e];
+    const int t0 = ch.t0, t1 = ch.t1;
+    cell_stage(sav, a.av + ((size_t)s * T + t0) * r, (t1 - t0) * r);
     __syncthreads();
-    const int jj = tid % a.geo.NPB, gr = tid / a.geo.NPB;
-    if (gr >= a.geo.G) return;
-    const int i0 = 2 * (sb * a.geo.NPB + jj);
-    if (i0 >= N) return;
-    const bool two = i0 + 1 < N;
-    double l0[RB], l1[RB];
-#pragma unroll
-    for (int q = 0; q < RB; ++q) {
-        l0[q] = q < r ? a.Lam[(b * N + i0) * r + q] : 0.0;
-        l1[q] = (q < r && two) ? a.Lam[(b * N + i0 + 1) * r + q] : 0.0;
-    }
+    const CellLane ln = cell_lane<2>(a.geo, tid, ch.s, N);
+    if (!ln.live) return;
+    const int i0 = ln.i0, gr = ln.g;
+    const bool two = ln.n == 2;
+    CellLam<2, RB> lam;
+    lam.load(a.Lam, b, N, i0, r, ln.n);
     const int ts = a.tgt[2 * gi], is = a.tgt[2 * gi + 1];
     const double radd = a.R[b * N + is];
     const double qnan = __longlong_as_double(0x7FF8000000000000ll);
-    auto load = [&](int t, double& x0, double& x1) {
-        x0 = qnan; x1 = qnan;
-        if (t < t1) {
-            const double* px = a.newp + (b * T + t) * N + i0;
-            if constexpr (VEC) {
-                const double2 v = *reinterpret_cast<const double2*>(px);
-                x0 = v.x; x1 = v.y;
-            } else {
-                x0 = px[0];
-                if (two) x1 = px[1];
-            }
-        }
-    };
-    double nx0, nx1;
-    load(t0 + gr, nx0, nx1);
+    const double* px = a.newp + b * T * N + i0;
+    double nx[2];                                             // the next row's cells, in flight while this row is computed
+    cell_prefetch_pair<VEC>(px + (size_t)(t0 + gr) * N, t0 + gr < t1, two, nx);
     for (int t = t0 + gr; t < t1; t += a.geo.G) {
         const double* av = sav + (size_t)(t - t0) * r;
-        const double x0 = nx0, x1 = nx1;
-        load(t + a.geo.G, nx0, nx1);
-        double m0 = 0.0, m1 = 0.0;
-#pragma unroll
-        for (int q = 0; q < RB; ++q)
-            if (q < r) {
-                const double v = av[q];
-                m0 = fma(l0[q], v, m0);
-                m1 = fma(l1[q], v, m1);
-            }
+        const double x0 = nx[0], x1 = nx[1];
+        cell_prefetch_pair<VEC>(px + (size_t)(t + a.geo.G) * N, t + a.geo.G < t1, two, nx);
+        double m[2];
+        lam.dots(av, r, m);
+        double m0 = m[0], m1 = m[1];
         if (t == ts) {
             if (i0 == is) m0 += radd;
             if (i0 + 1 == is) m1 += radd;
         }
-        const double y0 = x0 == x0 ? m0 : qnan, y1 = x1 == x1 ? m1 : qnan;
-        double* out = a.cp + ((size_t)s * T + t) * N + i0;
-        if constexpr (VEC) {
-            *reinterpret_cast<double2*>(out) = double2{y0, y1};
-        } else {
-            out[0] = y0;
-            if (two) out[1] = y1;
-        }
+        const double y[2] = {x0 == x0 ? m0 : qnan, x1 == x1 ? m1 : qnan};
+        cell_st_pair<VEC>(a.cp + ((size_t)s * T + t) * N + i0, two, y);
     }
 }
 
@@ -251,21 +224,15 @@ __global__ __launch_bounds__(kNwMaxThreads) void news_impact_kernel(NwArgs a) {
     const long long j = a.j0 + s;
     const size_t b = (size_t)(j / a.G);
     const int gi = (int)(j % a.G);
-    const int jj = tid % a.geo.NPB, gr = tid / a.geo.NPB;
-    const int i0 = 2 * (sb * a.geo.NPB + jj);
-    const bool act = gr < a.geo.G && i0 < N;
+    const CellLane ln = cell_lane<2>(a.geo, tid, sb, N);     // (an idle lane stays for the barriers)
+    const int jj = tid % a.geo.NPB, gr = ln.g, i0 = ln.i0;
+    const bool act = ln.live;
     const bool two = i0 + 1 < N;
-    double l0[RB], l1[RB];
+    CellLam<2, RB> lam;
+    lam.load(a.Lam, b, N, i0, r, ln.n);
     double ir0 = 0.0, ir1 = 0.0, sc0 = 1.0, sc1 = 1.0, mu0 = 0.0, mu1 = 0.0, sd0 = 1.0, sd1 = 1.0;
     const bool scale = a.mean != nullptr;
-#pragma unroll
-    for (int q = 0; q < RB; ++q) { l0[q] = 0.0; l1[q] = 0.0; }
     if (act) {
-#pragma unroll
-        for (int q = 0; q < RB; ++q) {
-            l0[q] = q < r ? a.Lam[(b * N + i0) * r + q] : 0.0;
-            l1[q] = (q < r && two) ? a.Lam[(b * N + i0 + 1) * r + q] : 0.0;
-        }
         ir0 = a.R[b * N + i0];
         ir1 = two ? a.R[b * N + i0 + 1] : 1.0;
         if (scale) {
@@ -279,47 +246,28 @@ __global__ __launch_bounds__(kNwMaxThreads) void news_impact_kernel(NwArgs a) {
     double acc0 = 0.0, acc1 = 0.0;
     for (int t0 = 0; t0 < T; t0 += a.geo.RC) {
         const int t1 = t0 + a.geo.RC < T ? t0 + a.geo.RC : T;
-        for (int e = tid; e < (t1 - t0) * r; e += blockDim.x) sgr[e] = G[(size_t)t0 * r + e];
+        cell_stage(sgr, G + (size_t)t0 * r, (t1 - t0) * r);
         __syncthreads();
         if (act)
             for (int t = t0 + gr; t < t1; t += a.geo.G) {
                 const double* gt = sgr + (size_t)(t - t0) * r;
                 const size_t cb = (b * T + t) * N + i0, cs = ((size_t)s * T + t) * N + i0, cx = (b * a.TH + t) * N + i0;
-                double xn0, xn1 = 0.0, xo0, xo1 = 0.0, c0, c1 = 0.0, xr0, xr1 = 0.0;
-                if constexpr (VEC) {
-                    const double2 vn = *reinterpret_cast<const double2*>(a.newp + cb);
-                    const double2 vo = *reinterpret_cast<const double2*>(a.oldp + cb);
-                    const double2 vc = *reinterpret_cast<const double2*>(a.cp + cs);
-                    const double2 vx = *reinterpret_cast<const double2*>(a.xrev + cx);
-                    xn0 = vn.x; xn1 = vn.y; xo0 = vo.x; xo1 = vo.y; c0 = vc.x; c1 = vc.y; xr0 = vx.x; xr1 = vx.y;
-                } else {
-                    xn0 = a.newp[cb]; xo0 = a.oldp[cb]; c0 = a.cp[cs]; xr0 = a.xrev[cx];
-                    if (two) { xn1 = a.newp[cb + 1]; xo1 = a.oldp[cb + 1]; c1 = a.cp[cs + 1]; xr1 = a.xrev[cx + 1]; }
-                }
-                double m0 = 0.0, m1 = 0.0;
-#pragma unroll
-                for (int q = 0; q < RB; ++q)
-                    if (q < r) {
-                        const double v = gt[q];
-                        m0 = fma(l0[q], v, m0);
-                        m1 = fma(l1[q], v, m1);
-                    }
-                const bool on0 = xn0 == xn0, on1 = two && xn1 == xn1;
-                const double w0 = on0 ? sc0 * ((c0 - m0) / ir0) : 0.0, w1 = on1 ? sc1 * ((c1 - m1) / ir1) : 0.0;
-                const double n0 = (on0 && xo0 != xo0) ? (scale ? mu0 + sd0 * xn0 : xn0) - xr0 : 0.0;
-                const double n1 = (on1 && xo1 != xo1) ? (scale ? mu1 + sd1 * xn1 : xn1) - xr1 : 0.0;
-                acc0 = fma(w0, n0, acc0);
-                acc1 = fma(w1, n1, acc1);
-                if (a.weight) {
-                    double* pw = a.weight + ((size_t)j * T + t) * N + i0;
-                    if constexpr (VEC) *reinterpret_cast<double2*>(pw) = double2{w0, w1};
-                    else { pw[0] = w0; if (two) pw[1] = w1; }
-                }
-                if (want_news) {
-                    double* pn = a.news + cb;
-                    if constexpr (VEC) *reinterpret_cast<double2*>(pn) = double2{n0, n1};
-                    else { pn[0] = n0; if (two) pn[1] = n1; }
-                }
+                double xn[2] = {0.0, 0.0}, xo[2] = {0.0, 0.0}, cv[2] = {0.0, 0.0}, xr[2] = {0.0, 0.0};
+                cell_ld_pair<VEC>(a.newp + cb, two, xn);
+                cell_ld_pair<VEC>(a.oldp + cb, two, xo);
+                cell_ld_pair<VEC>(a.cp + cs, two, cv);
+                cell_ld_pair<VEC>(a.xrev + cx, two, xr);
+                double m[2];
+                lam.dots(gt, r, m);
+                const double m0 = m[0], m1 = m[1];
+                const bool on0 = xn[0] == xn[0], on1 = two && xn[1] == xn[1];
+                const double w[2] = {on0 ? sc0 * ((cv[0] - m0) / ir0) : 0.0, on1 ? sc1 * ((cv[1] - m1) / ir1) : 0.0};
+                const double n[2] = {(on0 && xo[0] != xo[0]) ? (scale ? mu0 + sd0 * xn[0] : xn[0]) - xr[0] : 0.0,
+                                     (on1 && xo[1] != xo[1]) ? (scale ? mu1 + sd1 * xn[1] : xn[1]) - xr[1] : 0.0};
+                acc0 = fma(w[0], n[0], acc0);
+                acc1 = fma(w[1], n[1], acc1);
+                if (a.weight) cell_st_pair<VEC>(a.weight + ((size_t)j * T + t) * N + i0, two, w);
+                if (want_news) cell_st_pair<VEC>(a.news + cb, two, n);
             }
         __syncthreads();
     }
@@ -373,32 +321,27 @@ static bool nw_cells(NwArgs& a) {
 
 template <int RB>
 static hipError_t launch_cov_rb(const NwArgs& a, bool vec, hipStream_t s) {
-    const dim3 grid((unsigned)a.S, (unsigned)a.geo.nchunk, (unsigned)a.geo.nsblk), block(a.geo.threads);
+    const dim3 grid((unsigned)a.S, (unsigned)a.geo.nchunk, (unsigned)a.geo.nsblk);
     const size_t lds = (size_t)a.geo.RC * a.r * sizeof(double);
-    if (vec) hipLaunchKernelGGL((news_cov_panel_kernel<RB, true>), grid, block, lds, s, a);
-    else hipLaunchKernelGGL((news_cov_panel_kernel<RB, false>), grid, block, lds, s, a);
-    return hipGetLastError();
+    return cell_launch_vec(news_cov_panel_kernel<RB, false>, news_cov_panel_kernel<RB, true>, vec, grid, a.geo.threads, lds, s, a);
 }
 
 hipError_t launch_news_cov_panel(NwArgs a, hipStream_t s) {
     if (!nw_cells(a)) return hipErrorInvalidValue;
-    const bool vec = (a.N & 1) == 0 && al16(a.newp) && al16(a.cp);
+    const bool vec = cell_vec(a.N, a.newp, a.cp);
     return dispatch_r_bucket(a.r, [&](auto RB) { return launch_cov_rb<decltype(RB)::value>(a, vec, s); });
 }
 
 template <int RB>
 static hipError_t launch_impact_rb(const NwArgs& a, bool vec, hipStream_t s) {
-    const dim3 grid((unsigned)a.S, (unsigned)a.geo.nsblk), block(a.geo.threads);
+    const dim3 grid((unsigned)a.S, (unsigned)a.geo.nsblk);
     const size_t lds = ((size_t)a.geo.RC * a.r + (size_t)2 * a.geo.G * a.geo.NPB) * sizeof(double);
-    if (vec) hipLaunchKernelGGL((news_impact_kernel<RB, true>), grid, block, lds, s, a);
-    else hipLaunchKernelGGL((news_impact_kernel<RB, false>), grid, block, lds, s, a);
-    return hipGetLastError();
+    return cell_launch_vec(news_impact_kernel<RB, false>, news_impact_kernel<RB, true>, vec, grid, a.geo.threads, lds, s, a);
 }
 
 hipError_t launch_news_impact(NwArgs a, hipStream_t s) {
     if (!nw_cells(a)) return hipErrorInvalidValue;
-    const bool vec = (a.N & 1) == 0 && al16(a.newp) && al16(a.oldp) && al16(a.cp) && al16(a.xrev) &&
-                     (a.weight == nullptr || al16(a.weight)) && (a.news == nullptr || al16(a.news));
+    const bool vec = cell_vec(a.N, a.newp, a.oldp, a.cp, a.xrev, a.weight, a.news);
     return dispatch_r_bucket(a.r, [&](auto RB) { return launch_impact_rb<decltype(RB)::value>(a, vec, s); });
 }
 

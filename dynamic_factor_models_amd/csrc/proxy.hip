@@ -17,6 +17,7 @@
 //                         workgroup ids are remapped so that the slots of a replicate run on one XCD
 //   px_shock_kernel       u_t = w_0' S^-1 etahat_t of slot 0, all t at once
 // No atomics; every sum runs in a fixed order, so two identical calls agree bit for bit.
+#include "dfm_cell.h"
 #include "dfm_kernels.h"
 #include "dfm_philox.h"
 
@@ -239,15 +240,16 @@ __global__ __launch_bounds__(kPxFillLanes) void px_fill_kernel(PxArgs a) {
     const bool hasc = a.tkc != nullptr, wantV = a.fevd != nullptr, wantI = a.irf != nullptr;
     double* sT = sm;                                                 // [RC][RB], columns r .. RB - 1 zero
     double* sTc = sm + (size_t)a.geo.RC * RB;
-    const int i0 = (s * a.geo.NPB + tid) * SP;
-    const bool live = tid < a.geo.NPB && i0 < N;                     // (SP = 2 only for even N: i0 + 1 < N)
-    double lam[SP][RB], ssq[SP], sdv[SP];
+    const CellLane ln = cell_lane<SP>(a.geo, tid, s, N);             // (G = 1: an idle lane stays for the barriers)
+    const int i0 = ln.i0;
+    const bool live = ln.live;
+    CellLam<SP, RB> lam;
+    lam.load(a.Lam, b, N, i0, r, ln.n);
+    double ssq[SP], sdv[SP];
     bool cm[SP];
 #pragma unroll
     for (int q = 0; q < SP; ++q) {
         const size_t bi = b * N + (live ? i0 + q : 0);
-#pragma unroll
-        for (int m = 0; m < RB; ++m) lam[q][m] = m < r ? a.Lam[bi * r + m] : 0.0;
         ssq[q] = 0.0;
         sdv[q] = a.sd ? a.sd[bi] : 1.0;
         cm[q] = a.cum != nullptr && a.cum[live ? i0 + q : 0] != 0;
@@ -271,13 +273,9 @@ __global__ __launch_bounds__(kPxFillLanes) void px_fill_kernel(PxArgs a) {
 #pragma unroll
             for (int u = 0; u < kPxDenAhead; ++u) {
                 const int h = h0 + hq + u;
-                const size_t od = (b * H + (h < H ? h : H - 1)) * N + i0;
-                if constexpr (SP == 2) {
-                    const double2 v = wantV ? *reinterpret_cast<const double2*>(a.den + od) : double2{0.0, 0.0};
-                    dn[u][0] = v.x; dn[u][1] = v.y;
-                } else {
-                    dn[u][0] = wantV ? a.den[od] : 0.0;
-                }
+#pragma unroll
+                for (int q = 0; q < SP; ++q) dn[u][q] = 0.0;
+                if (wantV) cell_ld<SP>(a.den + (b * H + (h < H ? h : H - 1)) * N + i0, dn[u]);
             }
 #pragma unroll
             for (int u = 0; u < kPxDenAhead; ++u) {
@@ -287,20 +285,16 @@ __global__ __launch_bounds__(kPxFillLanes) void px_fill_kernel(PxArgs a) {
 #pragma unroll
                 for (int q = 0; q < SP; ++q) {
                     const double* Tq = (cm[q] ? sTc : sT) + (size_t)hh * RB;
-                    double v = 0.0;
-#pragma unroll
-                    for (int m = 0; m < RB; ++m) v = fma(lam[q][m], Tq[m], v);
+                    const double v = lam.dot(q, Tq, RB);          // (the staged rows are zero beyond r, as the loadings are)
                     ssq[q] = fma(v, v, ssq[q]);
                     x[q] = unit ? sdv[q] * v / sc : sdv[q] * v;
                 }
                 const size_t o = (sl * H + h) * N + i0;
-                if (wantI) {
-                    if constexpr (SP == 2) *reinterpret_cast<double2*>(a.irf + o) = double2{x[0], x[1]};
-                    else a.irf[o] = x[0];
-                }
+                if (wantI) cell_st<SP>(a.irf + o, x);
                 if (!wantV) continue;
-                if constexpr (SP == 2) *reinterpret_cast<double2*>(a.fevd + o) = double2{ssq[0] * dn[u][0], ssq[1] * dn[u][1]};
-                else a.fevd[o] = ssq[0] * dn[u][0];
+#pragma unroll
+                for (int q = 0; q < SP; ++q) x[q] = ssq[q] * dn[u][q];
+                cell_st<SP>(a.fevd + o, x);
             }
         }
     }
@@ -384,20 +378,12 @@ hipError_t launch_px_den(const PxArgs& a, hipStream_t s) {
 // (two with the cumulated table), which the geometry's r x r rows bound from above.
 template <int RB>
 static hipError_t launch_fill_rb(PxArgs a, hipStream_t s) {
-    const int SP = ((a.N & 1) == 0 && RB <= 16 && al16(a.irf) && al16(a.fevd)) ? 2 : 1;
+    const int SP = cell_sp(a.N, RB, a.irf, a.fevd);
     const bool hasc = a.tkc != nullptr;
     a.geo = irf_geometry(a.N, RB, SP, a.H, hasc, kPxFillLanes, kPxFillLds);
     const size_t lds = (size_t)a.geo.RC * RB * (hasc ? 2 : 1) * sizeof(double);
-    const size_t blocks = (size_t)a.B * (a.D + 1) * a.geo.nsblk;
-    if (blocks > 0x7fffffffu) return hipErrorInvalidValue;
-    if constexpr (RB <= 16) {
-        if (SP == 2) {
-            hipLaunchKernelGGL((px_fill_kernel<RB, 2>), dim3((unsigned)blocks), dim3(a.geo.threads), lds, s, a);
-            return hipGetLastError();
-        }
-    }
-    hipLaunchKernelGGL((px_fill_kernel<RB, 1>), dim3((unsigned)blocks), dim3(a.geo.threads), lds, s, a);
-    return hipGetLastError();
+    return cell_launch_sp<RB>(px_fill_kernel<RB, 1>, px_fill_kernel<RB, cell_sp_max(RB)>, SP,
+                              (size_t)a.B * (a.D + 1) * a.geo.nsblk, a.geo.threads, lds, s, a);
 }
 
 hipError_t launch_px_fill(PxArgs a, hipStream_t s) {

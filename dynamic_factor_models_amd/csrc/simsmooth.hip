@@ -14,6 +14,7 @@
 // pairs, stages the chunk's f rows in LDS, keeps its two rows of loadings in registers, draws one Philox counter per pair of
 // cells and moves 16 bytes per lane where N is even.  blockIdx.x is the pass replicate: the D draws of a replicate run next to
 // each other, so the panel chunk every one of them reads comes from L2 / the Infinity Cache and HBM sees the writes.
+#include "dfm_cell.h"
 #include "dfm_kernels.h"
 #include "dfm_philox.h"
 #include "dfm_smallmat.h"
@@ -171,80 +172,52 @@ __device__ __forceinline__ void ss_cells(const SsArgs& a) {
     extern __shared__ __attribute__((aligned(16))) double sfr[];
     const int r = a.r, N = a.N, T = a.T, TH = a.T + a.H, tid = threadIdx.x;
     const int rows = FILL ? TH : T;
-    const int s = blockIdx.x, c = blockIdx.y, sb = blockIdx.z;
+    const int s = blockIdx.x;
+    const CellChunk ch = cell_chunk(a.geo, blockIdx.z, blockIdx.y, s, rows);
     const long long j = a.j0 + s;
     const size_t b = (size_t)(j / a.D);
     const int d = (int)(j % a.D);
-    const int t0 = c * a.geo.RC, t1 = t0 + a.geo.RC < rows ? t0 + a.geo.RC : rows;
-    const double* F = a.f_draw + (size_t)j * TH * r;
-    for (int e = tid; e < (t1 - t0) * r; e += blockDim.x) sfr[e] = F[(size_t)t0 * r + e];
+    const int t0 = ch.t0, t1 = ch.t1;
+    cell_stage(sfr, a.f_draw + ((size_t)j * TH + t0) * r, (t1 - t0) * r);
     __syncthreads();
-    const int jj = tid % a.geo.NPB, gr = tid / a.geo.NPB;
-    if (gr >= a.geo.G) return;
-    const int i0 = 2 * (sb * a.geo.NPB + jj);
-    if (i0 >= N) return;
-    const bool two = i0 + 1 < N;                             // (VEC: N even, always)
-    double l0[RB], l1[RB];
-#pragma unroll
-    for (int q = 0; q < RB; ++q) {
-        l0[q] = q < r ? a.Lam[(b * N + i0) * r + q] : 0.0;
-        l1[q] = (q < r && two) ? a.Lam[(b * N + i0 + 1) * r + q] : 0.0;
-    }
+    const CellLane ln = cell_lane<2>(a.geo, tid, ch.s, N);
+    if (!ln.live) return;
+    const int i0 = ln.i0, gr = ln.g;
+    const bool two = ln.n == 2;                              // (VEC: N even, always)
+    CellLam<2, RB> lam;
+    lam.load(a.Lam, b, N, i0, r, ln.n);
     const double sr0 = sqrt(a.R[b * N + i0]), sr1 = two ? sqrt(a.R[b * N + i0 + 1]) : 0.0;
     const bool scale = FILL && a.mean != nullptr;
     const double mu0 = scale ? a.mean[b * N + i0] : 0.0, mu1 = (scale && two) ? a.mean[b * N + i0 + 1] : 0.0;
     const double sd0 = scale ? a.sd[b * N + i0] : 1.0, sd1 = (scale && two) ? a.sd[b * N + i0 + 1] : 1.0;
     const uint64_t key = ss_key(a.seed, a.first_draw, d), stream = 16 * b + (FILL ? kSsEps : kSsEpsPlus);
     const uint64_t hN = (uint64_t)(N + 1) / 2;
-    const double qnan = __longlong_as_double(0x7FF8000000000000ll);
-    auto load = [&](int t, double& x0, double& x1) {
-        x0 = qnan; x1 = qnan;
-        if (t < T && t < t1) {
-            const double* px = a.panel + (b * T + t) * N + i0;
-            if constexpr (VEC) {
-                const double2 v = *reinterpret_cast<const double2*>(px);
-                x0 = v.x; x1 = v.y;
-            } else {
-                x0 = px[0];
-                if (two) x1 = px[1];
-            }
-        }
-    };
-    double nx0, nx1;                                          // the next row's cells, in flight while this row is computed
-    load(t0 + gr, nx0, nx1);
+    const double* px = a.panel + b * T * N + i0;
+    double nx[2];                                             // the next row's cells, in flight while this row is computed
+    cell_prefetch_pair<VEC>(px + (size_t)(t0 + gr) * N, t0 + gr < T && t0 + gr < t1, two, nx);
     for (int t = t0 + gr; t < t1; t += a.geo.G) {
         const double* f = sfr + (size_t)(t - t0) * r;
-        const double x0 = nx0, x1 = nx1;
-        load(t + a.geo.G, nx0, nx1);
-        double m0 = 0.0, m1 = 0.0;
-#pragma unroll
-        for (int q = 0; q < RB; ++q)
-            if (q < r) {
-                const double fq = f[q];
-                m0 = fma(l0[q], fq, m0);
-                m1 = fma(l1[q], fq, m1);
-            }
+        const double x0 = nx[0], x1 = nx[1];
+        const int tn = t + a.geo.G;
+        cell_prefetch_pair<VEC>(px + (size_t)tn * N, tn < T && tn < t1, two, nx);
+        double m[2];
+        lam.dots(f, r, m);
+        const double m0 = m[0], m1 = m[1];
         const bool o0 = x0 == x0, o1 = x1 == x1;
-        double y0, y1;
+        double y[2];
         if constexpr (!FILL) {
             double e0 = 0.0, e1 = 0.0;
             if (o0 || o1) normal2(key, stream, (uint64_t)t * hN + (uint64_t)(i0 / 2), e0, e1);
-            y0 = o0 ? x0 - (m0 + sr0 * e0) : x0;
-            y1 = o1 ? x1 - (m1 + sr1 * e1) : x1;
+            y[0] = o0 ? x0 - (m0 + sr0 * e0) : x0;
+            y[1] = o1 ? x1 - (m1 + sr1 * e1) : x1;
         } else {
             double e0 = 0.0, e1 = 0.0;
             if (!o0 || (two && !o1)) normal2(key, stream, (uint64_t)t * hN + (uint64_t)(i0 / 2), e0, e1);
             const double v0 = o0 ? x0 : m0 + sr0 * e0, v1 = o1 ? x1 : m1 + sr1 * e1;
-            y0 = scale ? mu0 + sd0 * v0 : v0;
-            y1 = scale ? mu1 + sd1 * v1 : v1;
+            y[0] = scale ? mu0 + sd0 * v0 : v0;
+            y[1] = scale ? mu1 + sd1 * v1 : v1;
         }
-        double* out = FILL ? a.x_draw + ((size_t)j * TH + t) * N + i0 : a.diff + ((size_t)s * T + t) * N + i0;
-        if constexpr (VEC) {
-            *reinterpret_cast<double2*>(out) = double2{y0, y1};
-        } else {
-            out[0] = y0;
-            if (two) out[1] = y1;
-        }
+        cell_st_pair<VEC>(FILL ? a.x_draw + ((size_t)j * TH + t) * N + i0 : a.diff + ((size_t)s * T + t) * N + i0, two, y);
     }
 }
 
@@ -277,16 +250,12 @@ hipError_t launch_simsmooth_finish(const SsArgs& a, hipStream_t s) {
 
 template <bool FILL, int RB>
 static hipError_t launch_cells_rb(const SsArgs& a, bool vec, hipStream_t s) {
-    const dim3 grid((unsigned)a.S, (unsigned)a.geo.nchunk, (unsigned)a.geo.nsblk), block(a.geo.threads);
+    const dim3 grid((unsigned)a.S, (unsigned)a.geo.nchunk, (unsigned)a.geo.nsblk);
     const size_t lds = (size_t)a.geo.RC * a.r * sizeof(double);
-    if (vec) {
-        if constexpr (FILL) hipLaunchKernelGGL((simsmooth_fill_kernel<RB, true>), grid, block, lds, s, a);
-        else hipLaunchKernelGGL((simsmooth_diff_kernel<RB, true>), grid, block, lds, s, a);
-    } else {
-        if constexpr (FILL) hipLaunchKernelGGL((simsmooth_fill_kernel<RB, false>), grid, block, lds, s, a);
-        else hipLaunchKernelGGL((simsmooth_diff_kernel<RB, false>), grid, block, lds, s, a);
-    }
-    return hipGetLastError();
+    if constexpr (FILL)
+        return cell_launch_vec(simsmooth_fill_kernel<RB, false>, simsmooth_fill_kernel<RB, true>, vec, grid, a.geo.threads, lds, s, a);
+    else
+        return cell_launch_vec(simsmooth_diff_kernel<RB, false>, simsmooth_diff_kernel<RB, true>, vec, grid, a.geo.threads, lds, s, a);
 }
 
 // A lane per column pair; a staged row is f_t (cell_geometry, dfm_cellgeom.h); a 3-D grid: its y and z extents are checked.
@@ -295,8 +264,7 @@ static hipError_t launch_cells(SsArgs a, hipStream_t s) {
     if (a.r < 1 || a.r > 32 || a.S < 1) return hipErrorInvalidValue;
     a.geo = cell_geometry((a.N + 1) / 2, a.r, FILL ? a.T + a.H : a.T, kSsMaxThreads, kSsLds);
     if (a.geo.nchunk > 65535 || a.geo.nsblk > 65535) return hipErrorInvalidValue;
-    const double* out = FILL ? a.x_draw : a.diff;
-    const bool vec = (a.N & 1) == 0 && al16(a.panel) && al16(out);
+    const bool vec = cell_vec(a.N, a.panel, FILL ? a.x_draw : a.diff);
     return dispatch_r_bucket(a.r, [&](auto RB) { return launch_cells_rb<FILL, decltype(RB)::value>(a, vec, s); });
 }
 

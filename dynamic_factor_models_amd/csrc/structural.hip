@@ -11,6 +11,7 @@
 //                       component): (r + 1) r p busy lanes per dependent row instead of r
 //   sv_hd_fill_kernel   streams hd [B][r+1][T][N] = sd_i lam_i' c^(k)_t, a chunk of rows and a block of series per workgroup
 // The tables are stored shock-major, Th[h][k][m] = (Theta_h)_mk, so that a lane's dot product reads consecutive addresses.
+#include "dfm_cell.h"
 #include "dfm_kernels.h"
 #include "dfm_smallmat.h"
 
@@ -155,15 +156,18 @@ __global__ __launch_bounds__(kSvIrfLanes) void sv_irf_fill_kernel(SvArgs a) {
     double* sT = sm;
     double* sTc = sm + (size_t)a.geo.RC * RR;
     double* sSc = sm + (size_t)a.geo.RC * RR * (hasc ? 2 : 1);
-    const int i0 = (s * a.geo.NPB + tid) * SP;
-    const bool live = tid < a.geo.NPB && i0 < N;                     // (SP = 2 only for even N: i0 + 1 < N)
-    double lam[SP][R], ssq[SP][R], sdv[SP], Rv[SP];
+    const CellLane ln = cell_lane<SP>(a.geo, tid, s, N);             // (G = 1: an idle lane stays for the barriers)
+    const int i0 = ln.i0;
+    const bool live = ln.live;
+    CellLam<SP, R> lam;
+    lam.load(a.Lam, b, N, i0, R, ln.n);
+    double ssq[SP][R], sdv[SP], Rv[SP];
     bool cm[SP];
 #pragma unroll
     for (int q = 0; q < SP; ++q) {
         const size_t bi = b * N + (live ? i0 + q : 0);
 #pragma unroll
-        for (int k = 0; k < R; ++k) { lam[q][k] = a.Lam[bi * R + k]; ssq[q][k] = 0.0; }
+        for (int k = 0; k < R; ++k) ssq[q][k] = 0.0;
         sdv[q] = a.sd ? a.sd[bi] : 1.0;
         Rv[q] = wantV ? a.R[bi] : 0.0;
         cm[q] = a.cum != nullptr && a.cum[live ? i0 + q : 0] != 0;
@@ -172,10 +176,8 @@ __global__ __launch_bounds__(kSvIrfLanes) void sv_irf_fill_kernel(SvArgs a) {
     for (int h0 = 0; h0 < H; h0 += a.geo.RC) {
         const int nh = H - h0 < a.geo.RC ? H - h0 : a.geo.RC;
         __syncthreads();
-        for (int e = tid; e < nh * RR; e += blockDim.x) {
-            sT[e] = a.Th[(sl * H + h0) * RR + e];
-            if (hasc) sTc[e] = a.Thc[(sl * H + h0) * RR + e];
-        }
+        cell_stage(sT, a.Th + (sl * H + h0) * RR, nh * RR);
+        if (hasc) cell_stage(sTc, a.Thc + (sl * H + h0) * RR, nh * RR);
         __syncthreads();
         if (!live) continue;
         for (int hh = 0; hh < nh; ++hh) {
@@ -189,17 +191,12 @@ __global__ __launch_bounds__(kSvIrfLanes) void sv_irf_fill_kernel(SvArgs a) {
                 double x[SP];
 #pragma unroll
                 for (int q = 0; q < SP; ++q) {
-                    double v = 0.0;
-#pragma unroll
-                    for (int m = 0; m < R; ++m) v = fma(lam[q][m], Tq[q][k * R + m], v);
+                    const double v = lam.dot(q, Tq[q] + k * R, R);
                     ssq[q][k] = fma(v, v, ssq[q][k]);
                     tot[q] += ssq[q][k];
                     x[q] = unit ? sdv[q] * v / sSc[k] : sdv[q] * v;
                 }
-                if (!wantI) continue;
-                const size_t o = ((sl * R + k) * H + h) * N + i0;
-                if constexpr (SP == 2) *reinterpret_cast<double2*>(a.irf + o) = double2{x[0], x[1]};
-                else a.irf[o] = x[0];
+                if (wantI) cell_st<SP>(a.irf + ((sl * R + k) * H + h) * N + i0, x);
             }
             if (!wantV) continue;
             double idio[SP], inv[SP];
@@ -213,9 +210,7 @@ __global__ __launch_bounds__(kSvIrfLanes) void sv_irf_fill_kernel(SvArgs a) {
                 double x[SP];
 #pragma unroll
                 for (int q = 0; q < SP; ++q) x[q] = (k < R ? ssq[q][k < R ? k : 0] : idio[q]) * inv[q];
-                const size_t o = ((sl * (R + 1) + k) * H + h) * N + i0;
-                if constexpr (SP == 2) *reinterpret_cast<double2*>(a.fevd + o) = double2{x[0], x[1]};
-                else a.fevd[o] = x[0];
+                cell_st<SP>(a.fevd + ((sl * (R + 1) + k) * H + h) * N + i0, x);
             }
         }
     }
@@ -311,38 +306,22 @@ template <int R, int SP>
 __global__ __launch_bounds__(kSvFillMaxThreads) void sv_hd_fill_kernel(SvArgs a) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int T = a.T, N = a.N, tid = threadIdx.x;
-    unsigned blk = blockIdx.x;
-    const int s = (int)(blk % (unsigned)a.geo.nsblk); blk /= (unsigned)a.geo.nsblk;
-    const int c = (int)(blk % (unsigned)a.geo.nchunk);
-    const size_t bk = blk / (unsigned)a.geo.nchunk, b = bk / (R + 1);       // bk = b (r + 1) + slot
-    const int t0 = c * a.geo.RC, t1 = t0 + a.geo.RC < T ? t0 + a.geo.RC : T, nt = t1 - t0;
-    for (int e = tid; e < nt * R; e += blockDim.x) sm[e] = a.C[(bk * T + t0) * R + e];
+    const CellChunk ch = cell_chunk(a.geo, blockIdx.x, T);
+    const size_t bk = ch.outer, b = bk / (R + 1);                           // bk = b (r + 1) + slot
+    const int t0 = ch.t0, t1 = ch.t1;
+    cell_stage(sm, a.C + (bk * T + t0) * R, (t1 - t0) * R);
     __syncthreads();
-    const int j = tid % a.geo.NPB, g = tid / a.geo.NPB;
-    if (g >= a.geo.G) return;
-    const int i0 = (s * a.geo.NPB + j) * SP;
-    if (i0 >= N) return;                                    // (SP = 2 only for even N: i0 + 1 < N)
-    double lam[SP][R];
-#pragma unroll
-    for (int q = 0; q < SP; ++q) {
-        const size_t bi = b * N + i0 + q;
-        const double sd = a.sd ? a.sd[bi] : 1.0;
-#pragma unroll
-        for (int k = 0; k < R; ++k) lam[q][k] = sd * a.Lam[bi * R + k];
-    }
-    for (int t = t0 + g; t < t1; t += a.geo.G) {
+    const CellLane ln = cell_lane<SP>(a.geo, tid, ch.s, N);
+    if (!ln.live) return;
+    const int i0 = ln.i0;
+    CellLam<SP, R> lam;                                                     // sd_i lam_i
+    lam.load(a.Lam, b, N, i0, R, SP, a.sd);
+    for (int t = t0 + ln.g; t < t1; t += a.geo.G) {
         const double* cr = sm + (size_t)(t - t0) * R;
         double x[SP];
 #pragma unroll
-        for (int q = 0; q < SP; ++q) {
-            double v = 0.0;
-#pragma unroll
-            for (int k = 0; k < R; ++k) v = fma(lam[q][k], cr[k], v);
-            x[q] = v;
-        }
-        const size_t o = (bk * T + t) * N + i0;
-        if constexpr (SP == 2) *reinterpret_cast<double2*>(a.hd + o) = double2{x[0], x[1]};
-        else a.hd[o] = x[0];
+        for (int q = 0; q < SP; ++q) x[q] = lam.dot(q, cr, R);
+        cell_st<SP>(a.hd + (bk * T + t) * N + i0, x);
     }
 }
 
@@ -366,38 +345,22 @@ hipError_t launch_sv_path(SvArgs a, hipStream_t s) {
 
 template <int R>
 static hipError_t launch_irf_r(SvArgs a, hipStream_t s) {
-    const int SP = ((a.N & 1) == 0 && R <= 16 && al16(a.irf) && al16(a.fevd)) ? 2 : 1;
+    const int SP = cell_sp(a.N, R, a.irf, a.fevd);
     const bool hasc = a.Thc != nullptr;
     a.geo = irf_geometry(a.N, R, SP, a.H, hasc, kSvIrfLanes, kSvFillLds);
     const size_t lds = ((size_t)a.geo.RC * R * R * (hasc ? 2 : 1) + 32) * sizeof(double);
-    const size_t blocks = (size_t)a.B * (a.slots > 1 ? a.slots : 1) * a.geo.nsblk;
-    if (blocks > 0x7fffffffu) return hipErrorInvalidValue;
-    if constexpr (R <= 16) {
-        if (SP == 2) {
-            hipLaunchKernelGGL((sv_irf_fill_kernel<R, 2>), dim3((unsigned)blocks), dim3(a.geo.threads), lds, s, a);
-            return hipGetLastError();
-        }
-    }
-    hipLaunchKernelGGL((sv_irf_fill_kernel<R, 1>), dim3((unsigned)blocks), dim3(a.geo.threads), lds, s, a);
-    return hipGetLastError();
+    return cell_launch_sp<R>(sv_irf_fill_kernel<R, 1>, sv_irf_fill_kernel<R, cell_sp_max(R)>, SP,
+                             (size_t)a.B * (a.slots > 1 ? a.slots : 1) * a.geo.nsblk, a.geo.threads, lds, s, a);
 }
 
 // A lane per SP series; a staged row is one row of a contribution path (cell_geometry, dfm_cellgeom.h).
 template <int R>
 static hipError_t launch_hd_r(SvArgs a, hipStream_t s) {
-    const int SP = ((a.N & 1) == 0 && R <= 16 && al16(a.hd)) ? 2 : 1;
+    const int SP = cell_sp(a.N, R, a.hd);
     a.geo = cell_geometry((a.N + SP - 1) / SP, R, a.T, kSvFillMaxThreads, kSvFillLds);
     const size_t lds = (size_t)a.geo.RC * R * sizeof(double);
-    const size_t blocks = (size_t)a.B * (R + 1) * a.geo.nchunk * a.geo.nsblk;
-    if (blocks > 0x7fffffffu) return hipErrorInvalidValue;
-    if constexpr (R <= 16) {
-        if (SP == 2) {
-            hipLaunchKernelGGL((sv_hd_fill_kernel<R, 2>), dim3((unsigned)blocks), dim3(a.geo.threads), lds, s, a);
-            return hipGetLastError();
-        }
-    }
-    hipLaunchKernelGGL((sv_hd_fill_kernel<R, 1>), dim3((unsigned)blocks), dim3(a.geo.threads), lds, s, a);
-    return hipGetLastError();
+    return cell_launch_sp<R>(sv_hd_fill_kernel<R, 1>, sv_hd_fill_kernel<R, cell_sp_max(R)>, SP,
+                             (size_t)a.B * (R + 1) * a.geo.nchunk * a.geo.nsblk, a.geo.threads, lds, s, a);
 }
 
 hipError_t launch_sv_irf_fill(SvArgs a, hipStream_t s) {

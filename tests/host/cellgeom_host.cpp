@@ -4,6 +4,8 @@
 //   cell lanes row_doubles rows max_threads lds_bytes      ->  NPB G RC nchunk nsblk threads
 //   irf  N R SP H hasc max_lanes lds_bytes                 ->  NPB G RC nchunk nsblk threads
 //   path r p max_threads lds_bytes                         ->  CP TC groups threads lds
+//   sp   N RB aligned                                      ->  SP   (cell_sp with one pointer, 16 or 8 bytes off a 16-byte line, and
+//                                                               a null one beside it, which counts as aligned)
 // A line it cannot read ends the run with exit status 1.
 #include <cstdio>
 #include <cstring>
@@ -25,6 +27,10 @@ int main() {
         } else if (!strcmp(kind, "path") && n == 4) {
             const dfm::PathGeom g = dfm::path_geometry((int)v[0], (int)v[1], (int)v[2], (size_t)v[3]);
             printf("%d %d %d %d %zu\n", g.CP, g.TC, g.groups, g.threads, g.lds);
+        } else if (!strcmp(kind, "sp") && n == 3) {
+            alignas(16) static double cells[4];
+            const double* none = nullptr;
+            printf("%d\n", dfm::cell_sp((int)v[0], (int)v[1], v[2] != 0 ? cells + 2 : cells + 1, none));
         } else {
             return 1;
         }

@@ -49,11 +49,11 @@ def _summary(kernel, call, grid, **extra):
                 partial_last=g["nchunk"] > 1 and rows % g["RC"] != 0, **extra)
 
 
-def forecast_fill(B, N, r, T, H):
+def forecast_fill(B, N, r, T, H, aligned=True):
     """forecast.hip launch_fill_r (SP: even N and R <= 16 with 16-byte aligned pointers) for forecast_fill_kernel<R, SP> over
     T + H rows of R + R (R + 1) / 2 staged doubles; the bucket is R = r itself.  The grid is one-dimensional: B * nchunk * nsblk
     workgroups."""
-    sp = 2 if N % 2 == 0 and r <= 16 else 1
+    sp = 2 if N % 2 == 0 and r <= 16 and aligned else 1
     call = ((N + sp - 1) // sp, r + r * (r + 1) // 2, T + H, FC_MAX_THREADS, FC_LDS)
     return _summary("forecast_fill_kernel", call, lambda g: (B * g["nchunk"] * g["nsblk"], 1, 1), SP=sp, R=r, vec=sp == 2)
 
@@ -228,8 +228,19 @@ def build_cellgeom_host(directory):
 
 
 def ask_cellgeom_host(exe, requests):
-    """One process for all `requests` ((kind, int, ..) with kind = cell | irf | path): the printed fields of each, as int tuples."""
+    """One process for all `requests` ((kind, int, ..) with kind = cell | irf | path | sp): the printed fields of each, as int
+    tuples."""
     text = "".join(" ".join(map(str, q)) + "\n" for q in requests)
     out = subprocess.run([exe], input=text, capture_output=True, text=True, check=True).stdout.splitlines()
     assert len(out) == len(requests)
     return [tuple(map(int, line.split())) for line in out]
+
+
+def check_sp_rule(exe, restated, bucket=lambda r: r):
+    """`restated(N, r, aligned)`, a launcher's SP as a test module restates it, against cell_sp of dfm_cellgeom.h at the launcher's
+    register bucket: N in SWEEP_N, r in SWEEP_R, aligned and misaligned.  Returns the set of SP values seen."""
+    q = [(N, r, al) for N in SWEEP_N for r in SWEEP_R for al in (1, 0)]
+    got = ask_cellgeom_host(exe, [("sp", N, bucket(r), al) for N, r, al in q])
+    bad = [(x, g[0], restated(x[0], x[1], bool(x[2]))) for x, g in zip(q, got) if g[0] != restated(x[0], x[1], bool(x[2]))]
+    assert not bad, bad[:5]
+    return {g[0] for g in got}

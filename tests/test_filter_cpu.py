@@ -89,6 +89,13 @@ def test_collapsed_update_equals_the_textbook_update(kind):
     assert abs(ll - ell) <= 1e-12 * max(1.0, abs(ell))
 
 
+def test_fill_sp_rule_matches_cell_sp(tmp_path):
+    """fill_launch's SP against cell_sp of csrc/dfm_cellgeom.h, compiled for the host, at the fill's register bucket."""
+    exe = fe.pg.build_cellgeom_host(tmp_path)
+    seen = fe.pg.check_sp_rule(exe, lambda N, r, al: fe.fill_launch(1, N, r, 20, aligned=al)["SP"], bucket=fe.pg.rb_bucket)
+    assert seen == {1, 2}
+
+
 def test_gpu_case_table_reaches_every_launch_class():
     assert fe.missing_classes() == set()
     names = [c[0] for c in fe.CASES]

@@ -42,6 +42,11 @@ def test_geometry_sweep_matches_the_host_function(host_exe, family):
     assert any(g["partial_last"] for g in geos) and any(g["threads"] > g["G"] * g["NPB"] for g in geos)
 
 
+def test_sp_rule_matches_cell_sp(host_exe):
+    """forecast_fill's SP (the bucket is R = r itself) against cell_sp, the one rule every SP launcher calls."""
+    assert pg.check_sp_rule(host_exe, lambda N, r, al: pg.forecast_fill(1, N, r, 40, 0, aligned=al)["SP"]) == {1, 2}
+
+
 def test_forecast_fill_launch_matches_the_sources():
     # cell_geometry / DESIGN.md section 10: N = 200, SP = 2 gives 5 x 100 of 512; N = 139 gives 3 x 139 of 448
     g = pg.forecast_fill(1, 200, 8, 500, 0)

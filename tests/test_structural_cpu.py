@@ -175,6 +175,12 @@ def test_geometry_restatement_matches_the_host_functions(host_exe):
     assert len(path_q) == sum(32 // r for r in range(1, 33)) and {q[3] for q in req if q[0] == "irf"} == {1, 2}
 
 
+def test_sp_rule_matches_cell_sp(host_exe):
+    """The SP of irf_fill and hd_fill (the bucket is R = r itself) against cell_sp of csrc/dfm_cellgeom.h."""
+    assert pg.check_sp_rule(host_exe, lambda N, r, al: sg.irf_fill(1, N, r, 12, False, aligned=al)["SP"]) == {1, 2}
+    assert pg.check_sp_rule(host_exe, lambda N, r, al: sg.hd_fill(1, N, r, 40, aligned=al)["SP"]) == {1, 2}
+
+
 # ------------------------------------------------------------------------------------------------------------ status codes
 def test_status_codes_without_a_device():
     lib = _lib.load()
