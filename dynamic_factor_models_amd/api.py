@@ -1856,7 +1856,7 @@ def bootstrap_irf_bands(varm: VARModel, H: int, ndraws: int = 10000, quantiles=(
     return dict(point=impulse_response(varm, range(varm.ns), H), bands=bands, draws=draws)
 
 
-def _ar_model_inputs(m: DFMModel):
+def _ar_model_inputs(m: DFMModel, through: Optional[int] = None):
     """The parametric model with AR(n_uarlag) idiosyncratic terms assembled from what the reference's own estimator leaves
     in the model (`estimate!(m)`):
 
@@ -1868,6 +1868,8 @@ def _ar_model_inputs(m: DFMModel):
     dfm_ks_pass_ar_batch (quasi-differenced observation equation, state (f_t .. f_{t-m+1}), m = max(p, n_uarlag + 1),
     nfac_u * m <= 32; likelihood conditional on the first n_uarlag window rows).  z_q ~ N(0, stationary covariance of
     the companion VAR) -- or the sample second moment of the stacked factor estimates when the VAR is not stable.
+    `through` (1-based, default lastperiod): the panel x holds rows initperiod..through; everything else -- c_i, mu_f, P0 -- comes
+    from the estimation window initperiod..lastperiod whatever `through` is.
     Returns (inputs dict for the library, column indices used, factor mean mu_f, series intercepts c_i)."""
     if m.nfac_o != 0:
         raise NotImplementedError("observed factors (nfac_o > 0) are not supported (non-functional in the reference too)")
@@ -1893,7 +1895,8 @@ def _ar_model_inputs(m: DFMModel):
     Asum = sum(Avar[:, l * r:(l + 1) * r] for l in range(p))
     mu_f = np.linalg.solve(np.eye(r) - Asum, c_f)
     c_i = np.nanmean(Y - F @ lam.T, axis=0)                              # intercept of the loading regression (:396-400)
-    x = Y - c_i - lam @ mu_f
+    Yx = Y if through is None else m.data[m.initperiod - 1:through][:, cols]
+    x = Yx - c_i - lam @ mu_f
     M = np.zeros((k, k)); M[:r, :r * p] = Avar
     M[r:, :k - r] = np.eye(k - r)
     Qk = np.zeros((k, k)); Qk[:r, :r] = var.seps
@@ -1960,6 +1963,61 @@ def estimate_ar_idio(m: DFMModel, *, max_em_iter: int = 20, tol_em: float = 1e-6
     var.seps = est["Q"][0]
     _fill_matrices(var)
     return path[0, :int(iters[0])].copy()
+
+
+def forecast_ar_idio(m: DFMModel, H: int, *, through: Optional[int] = None, ctx=None) -> dict:
+    """Nowcasts and H-step forecasts of the panel from the model with AR(n_uarlag) idiosyncratic terms, after
+    `estimate(m, NonParametric())`, optionally followed by `estimate_ar_idio(m)` (`_ar_model_inputs`: whatever loadings, `uar_coef`,
+    `uar_ser` and factor VAR the model holds).  What `forecast` gives for the parametric fit, with the idiosyncratic persistence
+    kept: one to four steps ahead rho_i e_iT is often the larger part of a series' forecast.
+
+    Parameters, the series intercepts c_i and the factor mean mu_f come from the estimation window; the state conditions on rows
+    initperiod..`through` (1-based, lastperiod <= through <= m.T, default lastperiod) -- rows after lastperiod are the ragged edge
+    a nowcast is for.  The q = n_uarlag idiosyncratic terms before the first output row have the window's sample variance of
+    Y - c_i - F lam_i.  One dfm_forecast_ar_batch call on the GPU.  Returns a dict (data units):
+      rows        1-based periods initperiod + q .. through + H (the last H are the forecast horizon)
+      cols        column indices (0-based) of m.data: the series `_ar_model_inputs` used
+      x           [rows, cols] observed cells as they are, every other cell E[x_ti | X] = common + idio
+      x_sd        [rows, cols] 0 on observed cells, sqrt(lam_i' P_t lam_i + V_ti) elsewhere -- the two variances added, without
+                  the cross-period covariance of the factor estimation error (include/dfm_hip.h; within a few per cent of exact)
+      common      [rows, cols] c_i + lam_i' (mu_f + E[f_t - mu_f | X])
+      idio        [rows, cols] E[e_ti | X]: the residual on an observed cell, the AR(q) smoother's mean elsewhere
+      factor      [rows, r] E[f_t | X] (with the factor mean mu_f, which is returned too), factor_cov [rows, r, r] = Var[f_t | X]
+      loglik      log-likelihood of rows initperiod + q .. through, conditional on the first q rows
+      inputs      the arrays handed to the library (those of `_ar_model_inputs`, v0 and mean), for the parity test
+    `m` is not modified."""
+    H = int(H)
+    if H < 0:
+        raise ValueError("H must be >= 0")
+    q = int(m.n_uarlag)
+    if not (1 <= q <= 4):
+        raise ValueError("forecast_ar_idio needs 1 <= n_uarlag <= 4")
+    through = m.lastperiod if through is None else int(through)
+    if not (m.lastperiod <= through <= m.T):
+        raise ValueError(f"through must lie in lastperiod..T ({m.lastperiod}..{m.T})")
+    inputs, cols, mu_f, c_i = _ar_model_inputs(m, through)
+    r = m.nfac_u
+    win = slice(m.initperiod - 1, m.lastperiod)
+    v0 = np.nanvar(m.data[win][:, cols] - c_i - m.factor[win] @ inputs["Lam"].T, axis=0)
+    mean = c_i + inputs["Lam"] @ mu_f
+    x = inputs["x"]
+    ctx, own = _own(ctx)
+    try:
+        o = ctx.forecast_ar_batch_host(x[None], inputs["Lam"][None], inputs["sig2"][None], inputs["rho"][None],
+                                       inputs["Avar"][None], inputs["Q"][None], inputs["mu0"][None], inputs["P0"][None], H,
+                                       v0=v0[None], mean=mean[None], sd=np.ones((1, cols.size)),
+                                       may_have_missing=bool(np.isnan(x).any()))
+    finally:
+        if own:
+            ctx.close()
+    il = np.tril_indices(r)                                             # packed lower, row-major (include/dfm_hip.h)
+    Pp = o["P"][0]
+    cov = np.empty((Pp.shape[0], r, r))
+    cov[:, il[0], il[1]] = Pp
+    cov[:, il[1], il[0]] = Pp
+    return dict(rows=np.arange(m.initperiod + q, through + H + 1), cols=cols, x=o["xhat"][0], x_sd=np.sqrt(o["xvar"][0]),
+                common=o["common"][0], idio=o["idio"][0], factor=o["f"][0] + mu_f, factor_cov=cov, loglik=float(o["loglik"][0]),
+                mu_f=mu_f, inputs=dict(inputs, v0=v0, mean=mean))
 
 
 def amengual_watson_test(m: DFMModel, nper: int = 4, *, ctx=None):

@@ -76,6 +76,7 @@ struct RouteOpts {
     int mstep_miss_mode = 1;               // DFM_MSTEP_MISS (route): loadings step with missing cells on the matrix pipe (mstep_miss.hip): 0 = never
                                            // (mstep_lam_kernel), 1 = where mstep_lam_kernel keeps its per-series accumulators in global memory
                                            // (Rp > 8 or N > 256), 2 = wherever supported
+    size_t fcar_msg_cap = (size_t)4 << 30;     // DFM_FCAR_MSG_BYTES=n (route): cap of the message buffer of dfm_forecast_ar_batch, which slices its replicates over it (4 GiB)
     bool odd_pad8 = true;                  // DFM_ODD_PAD8=0 (diagnostics build): odd N at states up to 8 wide stays on collapse_kernel
 };
 
@@ -122,6 +123,7 @@ RouteOpts route_opts_from_env() {
     o.tile_w = pos(route_env("DFM_TILE_W"));
     o.wide_old = on(diag_env("DFM_WIDE_OLD"));
     o.cov_wave = on(diag_env("DFM_COV_WAVE"));
+    if (const char* v = route_env("DFM_FCAR_MSG_BYTES")) { if (atoll(v) > 0) o.fcar_msg_cap = (size_t)atoll(v); }
     return o;
 }
 }  // namespace
@@ -152,7 +154,8 @@ struct dfm_handle {
     dfm::EmUpdArgs deferred_em;
     DevBlock odd;                          // panel / loadings / R with one all-missing series appended (odd N beyond the tilings, odd_pad)
     DevBlock fc;                           // dfm_forecast_batch_dev: the pass's T-row moments, the forecast tail, P and loglik when the
-                                           // caller does not take them (beside h->ws: the pass itself may reallocate that)
+                                           // caller does not take them (beside h->ws: the pass itself may reallocate that);
+                                           // dfm_forecast_ar_batch_dev: the padded panel, P and loglik likewise, one slice's messages
     DevBlock ss;                           // dfm_simsmooth_batch_dev: roots, the slice's pass parameters, smoothed means, logliks and
                                            // (no x_draw) difference panels -- beside h->ws for the same reason
     DevBlock nw;                           // dfm_news_batch_dev: targets, the revised old panel, one forecast's xhat, the slice's pass
@@ -178,11 +181,11 @@ struct dfm_handle {
 };
 
 enum KernelId { K_COLLAPSE = 0, K_RECURSION, K_MSTEP_STATS, K_MSTEP_SOLVE, K_PCA, K_SYNTH, K_PAD,
-                K_COLLAPSE_DMA, K_GRAM, K_COV, K_MEANSCAN, K_PFILL, K_COLLAPSE_MFMA, K_ALS, K_OLS, K_BOOT, K_QUANT, K_COLLAPSE_WIDE, K_EM_UPDATE, K_CHOW, K_MSTEP_MFMA, K_GRAM_XX, K_PASS_FUSED, K_FC_TAIL, K_FC_FILL, K_FC_PAD, K_SS_PREP, K_SS_EXPAND, K_SS_PATH, K_SS_DIFF, K_SS_FINISH, K_SS_FILL, K_NW_REVISE, K_NW_GATHER, K_NW_GAMMA, K_NW_COV, K_NW_IMPACT, K_MF_TABLE, K_MF_MOMENTS, K_MF_SOLVE, K_SV_PREP, K_SV_IRF_FILL, K_SV_SHOCK, K_SV_PATH, K_SV_HD_FILL, K_FT_FILTER, K_FT_FILL, K_FT_EVAL, K_GB_GRAM, K_GB_LOAD, K_GB_VAR, K_SV_SIGN_TABLE, K_SV_SIGN, K_SV_SIGN_KEEP, K_PX_ROWS, K_PX_MOMENT, K_PX_SLOT_TABLE, K_PX_DEN, K_PX_FILL, K_PX_SHOCK, K_MF_SOLVE_BLOCKS, K_COUNT };
+                K_COLLAPSE_DMA, K_GRAM, K_COV, K_MEANSCAN, K_PFILL, K_COLLAPSE_MFMA, K_ALS, K_OLS, K_BOOT, K_QUANT, K_COLLAPSE_WIDE, K_EM_UPDATE, K_CHOW, K_MSTEP_MFMA, K_GRAM_XX, K_PASS_FUSED, K_FC_TAIL, K_FC_FILL, K_FC_PAD, K_SS_PREP, K_SS_EXPAND, K_SS_PATH, K_SS_DIFF, K_SS_FINISH, K_SS_FILL, K_NW_REVISE, K_NW_GATHER, K_NW_GAMMA, K_NW_COV, K_NW_IMPACT, K_MF_TABLE, K_MF_MOMENTS, K_MF_SOLVE, K_SV_PREP, K_SV_IRF_FILL, K_SV_SHOCK, K_SV_PATH, K_SV_HD_FILL, K_FT_FILTER, K_FT_FILL, K_FT_EVAL, K_GB_GRAM, K_GB_LOAD, K_GB_VAR, K_SV_SIGN_TABLE, K_SV_SIGN, K_SV_SIGN_KEEP, K_PX_ROWS, K_PX_MOMENT, K_PX_SLOT_TABLE, K_PX_DEN, K_PX_FILL, K_PX_SHOCK, K_MF_SOLVE_BLOCKS, K_FCAR_BACK, K_FCAR_FWD, K_COUNT };
 static const char* const kKernelNames[K_COUNT] = {"collapse_kernel", "recursion_kernel", "mstep_lam_kernel",
                                                   "mstep_solve_kernel", "pca_kernel", "synth_kernel",
                                                   "pad_params_kernel", "collapse_dma_kernel", "gram_kernel",
-                                                  "cov_kernel", "meanscan_kernel", "pfill_kernel", "collapse_mfma_kernel", "als_kernel", "ols_kernel", "var_boot_kernel", "quantile_kernel", "collapse_wide_kernel", "em_update_kernel", "chow_kernel", "mstep_mfma_kernel", "gram_xx_kernel", "pass_fused_kernel", "forecast_tail_kernel", "forecast_fill_kernel", "forecast_pad_kernel", "simsmooth_prep_kernel", "simsmooth_expand_kernel", "simsmooth_path_kernel", "simsmooth_diff_kernel", "simsmooth_finish_kernel", "simsmooth_fill_kernel", "news_revise_kernel", "news_gather_kernel", "news_gamma_kernel", "news_cov_panel_kernel", "news_impact_kernel", "mf_table_kernel", "mf_moments_kernel", "mf_solve_kernel", "sv_prep_kernel", "sv_irf_fill_kernel", "sv_shock_kernel", "sv_path_kernel", "sv_hd_fill_kernel", "filter_kernel", "filter_fill_kernel", "filter_eval_kernel", "gibbs_gram_kernel", "gibbs_load_kernel", "gibbs_var_kernel", "sv_sign_table_kernel", "sv_sign_kernel", "sv_sign_keep_kernel", "px_rows_kernel", "px_moment_kernel", "px_slot_table_kernel", "px_den_kernel", "px_fill_kernel", "px_shock_kernel", "mf_solve_blocks_kernel"};
+                                                  "cov_kernel", "meanscan_kernel", "pfill_kernel", "collapse_mfma_kernel", "als_kernel", "ols_kernel", "var_boot_kernel", "quantile_kernel", "collapse_wide_kernel", "em_update_kernel", "chow_kernel", "mstep_mfma_kernel", "gram_xx_kernel", "pass_fused_kernel", "forecast_tail_kernel", "forecast_fill_kernel", "forecast_pad_kernel", "simsmooth_prep_kernel", "simsmooth_expand_kernel", "simsmooth_path_kernel", "simsmooth_diff_kernel", "simsmooth_finish_kernel", "simsmooth_fill_kernel", "news_revise_kernel", "news_gather_kernel", "news_gamma_kernel", "news_cov_panel_kernel", "news_impact_kernel", "mf_table_kernel", "mf_moments_kernel", "mf_solve_kernel", "sv_prep_kernel", "sv_irf_fill_kernel", "sv_shock_kernel", "sv_path_kernel", "sv_hd_fill_kernel", "filter_kernel", "filter_fill_kernel", "filter_eval_kernel", "gibbs_gram_kernel", "gibbs_load_kernel", "gibbs_var_kernel", "sv_sign_table_kernel", "sv_sign_kernel", "sv_sign_keep_kernel", "px_rows_kernel", "px_moment_kernel", "px_slot_table_kernel", "px_den_kernel", "px_fill_kernel", "px_shock_kernel", "mf_solve_blocks_kernel", "forecast_ar_back_kernel", "forecast_ar_fwd_kernel"};
 
 namespace dfm { int handle_device(const dfm_handle* h) { return h->device; } }   // (probe.hip)
 
@@ -2473,6 +2476,98 @@ int dfm_forecast_batch(dfm_handle* h, int B, int T, int N, int r, int p, int H, 
     return rc;
 }
 
+
+// ---- nowcasts and forecasts with AR idiosyncratic terms (forecast_ar.hip) -----------------------------------------------------
+// The panel with H all-missing rows appended goes into h->fc (xhat has q rows too few to hold it), the AR pass runs on its T + H
+// rows straight into f_out / P_out (quasi-differencing a NaN row gives NaN rows: the smoothed moments of the empty rows are the
+// forecast moments), then per slice of replicates the backward kernel leaves its messages in h->fc and the forward kernel writes
+// the cells.  A slice is as many replicates as fit the cap of the message buffer (RouteOpts::fcar_msg_cap), at least one: the
+// buffer does not grow with B.
+static int forecast_ar_check(dfm_handle* h, int B, int T, int N, int r, int p, int q, int H, const double* panel, const double* Lam,
+                             const double* sig2, const double* rho, const double* Avar, const double* Q, const double* mu0,
+                             const double* P0, const double* mean, const double* sd, const double* xhat, const double* f_out) {
+    if (int rc = check_dims(h, B, T, N, r)) return rc;
+    if (H < 0) return fail(h, DFM_E_DIMS, "H must be >= 0%s");
+    if (p < 1) return fail(h, DFM_E_DIMS, "number of factor lags must be >= 1%s");
+    if (q < 1) return fail(h, DFM_E_DIMS, "number of idiosyncratic lags must be >= 1 (q = 0 is dfm_forecast_batch)%s");
+    if (T <= q) return fail(h, DFM_E_DIMS, "T must exceed the number of idiosyncratic lags%s");
+    if (q > 4) return fail(h, DFM_E_R_UNSUPPORTED, "forecasts with AR idiosyncratic terms need q <= 4%s");
+    if ((long long)T + H > 0x7fffffffLL) return fail(h, DFM_E_DIMS, "T + H must be < 2^31%s");
+    if (int rc = ar_check(h, B, T + H, N, r, p, q, false)) return rc;
+    if (!panel || !Lam || !sig2 || !rho || !Avar || !Q || !mu0 || !P0 || !xhat || !f_out)
+        return fail(h, DFM_E_NULL, "required pointer is NULL%s");
+    if ((mean == nullptr) != (sd == nullptr)) return fail(h, DFM_E_NULL, "mean and sd must both be given or both be NULL%s");
+    return 0;
+}
+
+int dfm_forecast_ar_batch_dev(dfm_handle* h, int B, int T, int N, int r, int p, int q, int H, const double* panel, const double* Lam,
+                              const double* sig2, const double* rho, const double* Avar, const double* Q, const double* mu0,
+                              const double* P0, const double* v0, const double* mean, const double* sd, double* xhat, double* xvar,
+                              double* common, double* idio, double* f_out, double* P_out, double* loglik, unsigned flags) {
+    if (int rc = forecast_ar_check(h, B, T, N, r, p, q, H, panel, Lam, sig2, rho, Avar, Q, mu0, P0, mean, sd, xhat, f_out)) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t d = sizeof(double), np = (size_t)r * (r + 1) / 2, TH = (size_t)T + H, n = TH - q;
+    const size_t per = forecast_ar_msg_bytes((int)n, N, q);
+    size_t Sl = h->opt.fcar_msg_cap / per;
+    if (Sl < 1) Sl = 1;
+    if (Sl > (size_t)B) Sl = (size_t)B;
+    size_t off = 0;
+    const size_t o_x = take(off, (size_t)B * TH * N * d), o_P = (!P_out && xvar) ? take(off, (size_t)B * n * np * d) : (size_t)-1,
+                 o_ll = loglik ? (size_t)-1 : take(off, (size_t)B * d), o_msg = take(off, Sl * per),
+                 o_last = take(off, Sl * N * sizeof(int));
+    HIP_TRY(h, h->fc.grow(off));
+    double* xpad = at<double>(h->fc, o_x);
+    double* Pbuf = P_out ? P_out : at<double>(h->fc, o_P);
+    {
+        ProfScope ps(h, K_FC_PAD);
+        HIP_TRY(h, launch_forecast_pad(B, T, H, N, panel, xpad, !(flags & DFM_F_MAY_HAVE_MISSING), h->status_dev, h->stream));
+    }
+    if (int rc = ar_pass_run(h, B, (int)TH, N, r, p, q, xpad, Lam, sig2, rho, Avar, Q, mu0, P0, f_out, Pbuf,
+                             loglik ? loglik : at<double>(h->fc, o_ll), flags | DFM_F_MAY_HAVE_MISSING)) return rc;
+    FcArArgs a{};
+    a.n = (int)n; a.N = N; a.r = r; a.q = q;
+    a.panel = xpad; a.f = f_out; a.P = xvar ? Pbuf : nullptr;
+    a.Lam = Lam; a.sig2 = sig2; a.rho = rho; a.v0 = v0; a.mean = mean; a.sd = sd;
+    a.msg = at<double>(h->fc, o_msg); a.last = at<int>(h->fc, o_last);
+    a.xhat = xhat; a.xvar = xvar; a.common = common; a.idio = idio;
+    for (size_t b0 = 0; b0 < (size_t)B; b0 += Sl) {
+        a.b0 = (int)b0; a.S = (int)((size_t)B - b0 < Sl ? (size_t)B - b0 : Sl);
+        {
+            ProfScope ps(h, K_FCAR_BACK);
+            HIP_TRY(h, launch_forecast_ar_back(a, h->stream));
+        }
+        {
+            ProfScope ps(h, K_FCAR_FWD);
+            HIP_TRY(h, launch_forecast_ar_fwd(a, h->stream));
+        }
+    }
+    return 0;
+}
+
+int dfm_forecast_ar_batch(dfm_handle* h, int B, int T, int N, int r, int p, int q, int H, const double* panel, const double* Lam,
+                          const double* sig2, const double* rho, const double* Avar, const double* Q, const double* mu0,
+                          const double* P0, const double* v0, const double* mean, const double* sd, double* xhat, double* xvar,
+                          double* common, double* idio, double* f_out, double* P_out, double* loglik, unsigned flags) {
+    if (int rc = forecast_ar_check(h, B, T, N, r, p, q, H, panel, Lam, sig2, rho, Avar, Q, mu0, P0, mean, sd, xhat, f_out)) return rc;
+    if (int rc = status_epoch(h)) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t m = (size_t)(p > q + 1 ? p : q + 1), k = (size_t)r * m, np = (size_t)r * (r + 1) / 2, n = (size_t)T + H - q,
+                 n_R = (size_t)B * N, n_x = (size_t)B * n * N;
+    std::vector<double> ll_host((size_t)B);                     // (checked before the caller's loglik, which is optional, is written)
+    HostStage st(h, 256);
+    double *x_d, *lam_d, *R_d, *rho_d, *A_d, *Q_d, *mu_d, *P0_d, *v0_d, *mean_d, *sd_d, *xh_d, *xv_d, *cm_d, *id_d, *f_d, *P_d, *ll_d;
+    st.in(panel, (size_t)B * T * N, x_d); st.in(Lam, (size_t)B * N * r, lam_d); st.in(sig2, n_R, R_d); st.in(rho, n_R * q, rho_d);
+    st.in(Avar, (size_t)B * r * r * p, A_d); st.in(Q, (size_t)B * r * r, Q_d); st.in(mu0, (size_t)B * k, mu_d); st.in(P0, (size_t)B * k * k, P0_d);
+    st.in(v0, v0 ? n_R : 0, v0_d); st.in(mean, mean ? n_R : 0, mean_d); st.in(sd, sd ? n_R : 0, sd_d);
+    st.out(xhat, n_x, xh_d); st.out(xvar, xvar ? n_x : 0, xv_d); st.out(common, common ? n_x : 0, cm_d); st.out(idio, idio ? n_x : 0, id_d);
+    st.out(f_out, (size_t)B * n * r, f_d); st.out(P_out, P_out ? (size_t)B * n * np : 0, P_d); st.out(ll_host.data(), (size_t)B, ll_d);
+    if (int rc = st.begin()) return rc;
+    int rc = st.finish(dfm_forecast_ar_batch_dev(h, B, T, N, r, p, q, H, x_d, lam_d, R_d, rho_d, A_d, Q_d, mu_d, P0_d, v0_d, mean_d, sd_d,
+                                                 xh_d, xv_d, cm_d, id_d, f_d, P_d, ll_d, flags));
+    if (rc == 0) rc = post_check(h, ll_host.data(), B);
+    if (rc == 0 && loglik) memcpy(loglik, ll_host.data(), (size_t)B * sizeof(double));
+    return rc;
+}
 
 // ---- posterior draws of factor and panel paths: the simulation smoother (simsmooth.hip) --------------------------------------
 // Per slice of at most kSsSlice pass replicates j = b D + d: expand the parameters (mu0 = 0), simulate f+ into f_draw, stream the

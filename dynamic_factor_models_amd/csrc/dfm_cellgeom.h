@@ -1,5 +1,6 @@
 // dfm_cellgeom.h -- launch geometry of the post-estimation cell kernels (forecast.hip, filter.hip, simsmooth.hip, news.hip,
-// structural.hip, proxy.hip), the rule for their 16-byte cell path (cell_vec, cell_sp) and the two dispatchers their launchers
+// structural.hip, proxy.hip) and of the series recursions of forecast_ar.hip (series_geometry; tests/host/seriesgeom_host.cpp,
+// tests/test_forecast_ar_cpu.py), the rule for the 16-byte cell path (cell_vec, cell_sp) and the two dispatchers the launchers
 // share.  Plain C++17 with no HIP include: the launchers call it, the kernels read the CellGeom it returns through their argument
 // struct, and tests/host/cellgeom_host.cpp compiles it for the CPU, where tests/test_post_geometry_cpu.py, tests/test_filter_cpu.py
 // and tests/test_structural_cpu.py hold the Python restatements of tests/post_geometry.py, tests/filter_expect.py and
@@ -49,6 +50,27 @@ inline CellGeom cell_geometry(int lanes, int row_doubles, int rows, int max_thre
     }
     g.threads = (g.G * g.NPB + 63) / 64 * 64;
     int rc = g.G * 8;
+    const int cap = (int)(lds_bytes / ((size_t)row_doubles * sizeof(double)));
+    if (rc > cap) rc = cap;
+    if (rc > rows) rc = rows;
+    if (rc < 1) rc = 1;
+    g.RC = rc;
+    g.nchunk = (rows + rc - 1) / rc;
+    return g;
+}
+
+// The series recursions of forecast_ar.hip: ONE lane per series and one row group (every lane walks every row, in order), so a
+// workgroup is a series block of at most 256 lanes in whole waves and owns all the rows of its replicate; it stages them in LDS
+// kSeriesChunkRows at a time, fewer under the LDS cap or when there are no more.  rows >= 1.
+constexpr int kSeriesChunkRows = 32;
+
+inline CellGeom series_geometry(int N, int row_doubles, int rows, size_t lds_bytes) {
+    CellGeom g;
+    g.nsblk = (N + kCellBlockLanes - 1) / kCellBlockLanes;
+    g.NPB = (N + g.nsblk - 1) / g.nsblk;
+    g.G = 1;
+    g.threads = (g.NPB + 63) / 64 * 64;
+    int rc = kSeriesChunkRows;
     const int cap = (int)(lds_bytes / ((size_t)row_doubles * sizeof(double)));
     if (rc > cap) rc = cap;
     if (rc > rows) rc = rows;

@@ -18,10 +18,10 @@ extern thread_local const char* t_launched_kernel;
 // Environment switches of the library, in two classes.
 //   route_env: selects among PRODUCTION kernels that compute the same result to rounding (the one-launch pass or the two-launch
 //              pass, one wave or a lane group per replicate, ...): what the test-suite uses to cover every fallback, and tuning
-//              knobs (DFM_NUM_CU).  Eleven names: DFM_FORCE_GENERAL, DFM_PASS_FUSED, DFM_PF_WPARK, DFM_NO_CHUNK, DFM_NO_PAIR,
-//              DFM_MSTEP_MISS, DFM_TILE_NC, DFM_NUM_CU -- which kernel runs, never what it computes -- and DFM_CHUNK_W, DFM_TILE_W,
-//              DFM_CHUNK_TOL, which set the warm-up and the boundary tolerance of the time-chunked recursions (a replicate that misses the
-//              tolerance is redone sequentially: accuracy knobs).
+//              knobs (DFM_NUM_CU).  Twelve names: DFM_FORCE_GENERAL, DFM_PASS_FUSED, DFM_PF_WPARK, DFM_NO_CHUNK, DFM_NO_PAIR,
+//              DFM_MSTEP_MISS, DFM_TILE_NC, DFM_NUM_CU, DFM_FCAR_MSG_BYTES -- which kernel runs or how a call is sliced, never what it
+//              computes -- and DFM_CHUNK_W, DFM_TILE_W, DFM_CHUNK_TOL, which set the warm-up and the boundary tolerance of the
+//              time-chunked recursions (a replicate that misses the tolerance is redone sequentially: accuracy knobs).
 //   diag_env:  ablations (some produce WRONG results on purpose: stream-only, compute-only, skipped stages), phase stamps, the
 //              *_OLD kernels kept for A/B.  Read only by a library built with -DDFM_DIAG (`python -m
 //              dynamic_factor_models_amd.build --diag`); the default libdfmhip.so ignores them.
@@ -495,6 +495,23 @@ struct FcFillArgs {
 hipError_t launch_forecast_fill(const FcFillArgs& a, hipStream_t s);
 hipError_t launch_forecast_pad(int B, int T, int H, int N, const double* panel, double* out, bool check_nan, int* status,
                                hipStream_t s);
+
+// The series side of the forecasts with AR(q) idiosyncratic terms (forecast_ar.hip): one launch covers the S replicates b0 ..
+// b0 + S - 1 of the call, whose messages fill the slice buffer.
+struct FcArArgs {
+    int b0, S, n, N, r, q;                        // n = T + H - q output rows (panel rows q .. T + H - 1)
+    const double* panel;                          // [B][n + q][N]: the panel with its H all-missing rows
+    const double* f; const double* P;             // [B][n][r], [B][n][r(r+1)/2] (P is read only with xvar)
+    const double* Lam; const double* sig2; const double* rho;   // [B][N][r], [B][N], [B][N][q]
+    const double* v0;                             // [B][N] variance of the q terms before output row 0, or null (sig2)
+    const double* mean; const double* sd;         // [B][N] or both null
+    double* msg; int* last;                       // [S][q + q(q+1)/2][n][N] backward messages, [S][N] last observed row (-1: none)
+    double* xhat; double* xvar; double* common; double* idio;   // [B][n][N]; all but xhat may be null
+    CellGeom geo;                                 // geometry (set by the launcher)
+};
+hipError_t launch_forecast_ar_back(const FcArArgs& a, hipStream_t s);
+hipError_t launch_forecast_ar_fwd(const FcArArgs& a, hipStream_t s);
+size_t forecast_ar_msg_bytes(int n, int N, int q);   // the messages of ONE replicate
 
 // Posterior draws of factor and panel paths, Durbin-Koopman simulation smoother (simsmooth.hip).  Pass replicate j = b D + d;
 // a call runs its B D pass replicates in slices j0 .. j0 + S - 1.

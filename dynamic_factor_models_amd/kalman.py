@@ -901,3 +901,4 @@ class DfmContext:
 from . import structural  # noqa: E402,F401  (attaches the structural entries to DfmContext)
 from . import filtering  # noqa: E402,F401  (attaches the filter entries to DfmContext)
 from . import gibbs  # noqa: E402,F401  (attaches the Gibbs sampler's entries to DfmContext)
+from . import forecasting_ar  # noqa: E402,F401  (attaches the forecast entries of the AR-idiosyncratic model to DfmContext)

@@ -630,6 +630,37 @@ function ks_pass_ar(h::Handle, x::Matrix{Float64}, Lam::Matrix{Float64}, sig2::V
     return (factor = permutedims(f), P = permutedims(P), loglik = ll[1])
 end
 
+"Nowcasts and H-step forecasts of the panel with AR(q) idiosyncratic terms (dfm_forecast_ar_batch; include/dfm_hip.h): arguments
+as ks_pass_ar (1 <= q <= 4); v0 (length N, default sig2) is the variance of the q idiosyncratic terms before the first output row,
+mean / sd (length N, both or neither) put the cells into data units.  Rows q+1..T+H: x = observed cells as they are and
+E[x_ti | X] = common + idio elsewhere, xvar (0 on observed cells; the factor and idiosyncratic variances added, not exact), common,
+idio, factor (T+H-q x r), P (packed lower per row), loglik (conditional on the first q rows)."
+function forecast_ar(h::Handle, x::Matrix{Float64}, Lam::Matrix{Float64}, sig2::Vector{Float64}, rho::Matrix{Float64},
+                     Avar::Matrix{Float64}, Q::Matrix{Float64}, mu0::Vector{Float64}, P0::Matrix{Float64}, H::Integer;
+                     v0 = nothing, mean = nothing, sd = nothing, singular_q::Bool = false)
+    (mean === nothing) == (sd === nothing) || error("mean and sd go together")
+    T, N = size(x); r = size(Lam, 2); q = size(rho, 2); p = div(size(Avar, 2), r); n = T + H - q
+    panel = to_c_panel(x)
+    LamC = permutedims(Lam); rhoC = permutedims(rho); AC = permutedims(Avar); QC = permutedims(Q); P0C = permutedims(P0)
+    v0C = v0 === nothing ? C_NULL : Vector{Float64}(v0)
+    meanC = mean === nothing ? C_NULL : Vector{Float64}(mean); sdC = sd === nothing ? C_NULL : Vector{Float64}(sd)
+    xhat = Array{Float64}(undef, N, n); xvar = Array{Float64}(undef, N, n); common = Array{Float64}(undef, N, n)
+    idio = Array{Float64}(undef, N, n)
+    f = Array{Float64}(undef, r, n); np = div(r * (r + 1), 2); P = Array{Float64}(undef, np, n); ll = Array{Float64}(undef, 1)
+    flags = (any(isnan, x) ? DFM_F_MAY_HAVE_MISSING : Cuint(0)) | (singular_q ? DFM_F_SINGULAR_Q : Cuint(0))
+    GC.@preserve panel LamC sig2 rhoC AC QC mu0 P0C v0C meanC sdC xhat xvar common idio f P ll begin
+        rc = ccall((:dfm_forecast_ar_batch, LIB), Cint,
+                   (Ptr{Cvoid}, Cint, Cint, Cint, Cint, Cint, Cint, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                    Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                    Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cuint),
+                   h.ptr, 1, T, N, r, p, q, H, panel, LamC, sig2, rhoC, AC, QC, mu0, P0C, v0C, meanC, sdC, xhat, xvar, common, idio,
+                   f, P, ll, flags)
+        check(h.ptr, rc)
+    end
+    return (x = permutedims(xhat), xvar = permutedims(xvar), common = permutedims(common), idio = permutedims(idio),
+            factor = permutedims(f), P = permutedims(P), loglik = ll[1])
+end
+
 "Joint ECM estimation with AR(q) idiosyncratic terms (dfm_em_ar_batch; include/dfm_hip.h): the re-estimation of the
 reference's `lambda`, `uar_coef`, `uar_ser` (dfm_functions.ipynb:391-415) and factor VAR inside the parametric model.
 Arguments as ks_pass_ar (the start: what `estimate!(m)` left in the model).  Returns the updated parameters, the
