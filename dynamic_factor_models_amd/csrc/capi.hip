@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "dfm_kernels.h"
+#include "dfm_msgeom.h"
 
 using namespace dfm;
 
@@ -372,11 +373,8 @@ Plan make_plan(const RouteOpts& o, int B, int T, int N, int r, unsigned flags, b
         p.active = take(off, (size_t)B * sizeof(int));
         if (mstep_needs_dmiss(Rp, N)) p.Dmiss = take(off, (size_t)B * N * np * d);
         if (fast && mstep_mfma_supported(Rp, N)) {
-            int w = (256 * 12) / B;
-            w = w < 1 ? 1 : (w > 8 ? 8 : w);
-            while (w > 1 && T / w < 8) --w;
-            p.ms_wpr = w;
-            p.ms_ws = take(off, mstep_mfma_workspace(B, N, Rp, w));
+            p.ms_wpr = ms_wpr(B, T);
+            p.ms_ws = take(off, mstep_mfma_workspace(B, N, Rp, p.ms_wpr));
         }
         if (fast && mstep_wide_supported(Rp, N)) p.mw_ws = take(off, mstep_wide_workspace(B, N, Rp));
         // (sized for loadings as wide as the state, whatever a companion model narrows them to)

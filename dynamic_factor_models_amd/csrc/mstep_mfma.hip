@@ -18,22 +18,10 @@
 #include "dfm_gram.h"
 #include "dfm_em_update.h"
 #include "dfm_kernels.h"
+#include "dfm_msgeom.h"
 
 namespace dfm {
 
-
-template <int R>
-struct MsGeo {
-    static constexpr int NFG = (R + 3) / 4;                 // factor groups of 4
-    static constexpr int FPI = NFG < 4 ? NFG : 4;
-    static constexpr int NCG = 4 / FPI;                     // series groups per instruction
-    static constexpr int CS = 4 * NCG;                      // series per step
-};
-__host__ __device__ inline unsigned ms_slot_bytes(int N) {   // as collapse_mfma.hip: 4 consecutive slots 64 B apart mod 256
-    unsigned sb = (unsigned)N * 8u;
-    while ((sb & 255u) != 64u && (sb & 255u) != 192u) sb += 16u;
-    return sb;
-}
 
 template <int R, int STEPS, int NDR>
 __global__ __launch_bounds__(256, 2) void mstep_mfma_kernel(MstepArgs a, unsigned SB, int wpr, double* part_sxf, double* part_sxx, EmUpdArgs ua,
@@ -66,16 +54,8 @@ __global__ __launch_bounds__(256, 2) void mstep_mfma_kernel(MstepArgs a, unsigne
     const int K = lane >> 4, blk = (lane >> 2) & 3, q = lane & 3;
     const int g = blk / G::FPI, h = blk % G::FPI;
 
-    int tq = (T + wpr - 1) / wpr;
-    {
-        unsigned gg = rowB & 127u;
-        gg = gg == 0 ? 128u : (gg & (~gg + 1u));
-        const int m = (int)(128u / gg);
-        tq = ((tq + m - 1) / m) * m;
-    }
-    const int ta = (segi * tq < T) ? segi * tq : T;
-    const int tb = (ta + tq < T) ? ta + tq : T;
-    const int nrows = tb - ta;
+    const MsSeg sg = ms_segment(N, T, wpr, segi);
+    const int ta = sg.ta, nrows = sg.nrows;
     const int nblk = (nrows + 3) / 4;
     const char* __restrict__ seg = reinterpret_cast<const char*>(a.panel + ((size_t)b * T + ta) * N);
     const double* __restrict__ fseg = a.fsm + ((size_t)b * T + ta) * R;
@@ -270,8 +250,6 @@ __global__ __launch_bounds__(256, 8) void mstep_finish_kernel(MstepArgs a, int w
 }
 
 // ---------------------------------------------------------------------------------------------
-constexpr int kMsMaxSteps = 32;
-
 template <int R, int STEPS, int NDR>
 static hipError_t launch_ms_one(const MstepArgs& a, int wpr, double* pf, double* px, hipStream_t s, const EmUpdArgs* ua) {
     const unsigned SB = ms_slot_bytes(a.N);
@@ -287,8 +265,8 @@ static hipError_t launch_ms_one(const MstepArgs& a, int wpr, double* pf, double*
     }
     EmUpdArgs u0;
     memset(&u0, 0, sizeof(u0));
-    const int nfront = ua ? (a.B + 3) / 4 : 0;                // transition M-step waves in front of the streaming workgroups
-    hipLaunchKernelGGL((mstep_mfma_kernel<R, STEPS, NDR>), dim3((a.B * wpr + 3) / 4 + nfront), dim3(256), lds, s, a, SB, wpr, pf, px, ua ? *ua : u0,
+    const int nfront = ua ? ms_front_blocks(a.B) : 0;         // transition M-step waves in front of the streaming workgroups
+    hipLaunchKernelGGL((mstep_mfma_kernel<R, STEPS, NDR>), dim3(ms_stream_blocks(a.B, wpr) + nfront), dim3(256), lds, s, a, SB, wpr, pf, px, ua ? *ua : u0,
                        (ua && ua->k == 0) ? -nfront : nfront, stream_nt_hint((size_t)a.B * a.T * a.N * sizeof(double)) ? 1 : 0);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
@@ -302,8 +280,8 @@ static hipError_t launch_ms_pick(const MstepArgs& a, int wpr, double* pf, double
         return hipErrorInvalidValue;
     } else {
         if (steps == S) {
-            const int ndr = (a.N * 8 + 1023) / 1024;
-            constexpr int lo = (MsGeo<R>::CS * (S - 1) * 8 + 8 + 1023) / 1024, hi = (MsGeo<R>::CS * S * 8 + 1023) / 1024;
+            const int ndr = ms_ndr(a.N);
+            constexpr int lo = ms_ndr_lo(MsGeo<R>::CS, S), hi = ms_ndr_hi(MsGeo<R>::CS, S);
             if constexpr (lo <= 1 && 1 <= hi) { if (ndr == 1) return launch_ms_one<R, S, 1>(a, wpr, pf, px, s, ua); }
             if constexpr (lo <= 2 && 2 <= hi) { if (ndr == 2) return launch_ms_one<R, S, 2>(a, wpr, pf, px, s, ua); }
             if constexpr (lo <= 3 && 3 <= hi) { if (ndr == 3) return launch_ms_one<R, S, 3>(a, wpr, pf, px, s, ua); }
@@ -315,19 +293,14 @@ static hipError_t launch_ms_pick(const MstepArgs& a, int wpr, double* pf, double
 }
 
 // balanced panels, Rp in {4, 8} (the shapes of the fused E-step), even N, ceil(N / CS) <= 32, 8N <= 4096
-bool mstep_mfma_supported(int Rpad, int N) {
-    if ((N & 1) != 0 || N * 8 > 4096 || N < 4) return false;
-    if (Rpad == 4) return (N + MsGeo<4>::CS - 1) / MsGeo<4>::CS <= kMsMaxSteps;
-    if (Rpad == 8) return (N + MsGeo<8>::CS - 1) / MsGeo<8>::CS <= kMsMaxSteps;
-    return false;
-}
+bool mstep_mfma_supported(int Rpad, int N) { return ms_supported(Rpad, N); }
 size_t mstep_mfma_workspace(int B, int N, int Rpad, int wpr) { return (size_t)B * wpr * ((size_t)N * Rpad + N) * sizeof(double); }
 
 hipError_t launch_mstep_mfma(int Rpad, const MstepArgs& a, int wpr, double* workspace, hipStream_t s, const EmUpdArgs* ua) {
     double* pf = workspace;
     double* px = workspace + (size_t)a.B * wpr * a.N * Rpad;
-    if (Rpad == 4) return launch_ms_pick<4, 1>(a, wpr, pf, px, s, (a.N + MsGeo<4>::CS - 1) / MsGeo<4>::CS, ua);
-    if (Rpad == 8) return launch_ms_pick<8, 1>(a, wpr, pf, px, s, (a.N + MsGeo<8>::CS - 1) / MsGeo<8>::CS, ua);
+    if (Rpad == 4) return launch_ms_pick<4, 1>(a, wpr, pf, px, s, ms_steps(a.N, MsGeo<4>::CS), ua);
+    if (Rpad == 8) return launch_ms_pick<8, 1>(a, wpr, pf, px, s, ms_steps(a.N, MsGeo<8>::CS), ua);
     return hipErrorInvalidValue;
 }
 

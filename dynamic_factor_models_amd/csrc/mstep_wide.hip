@@ -24,16 +24,14 @@
 
 #include "dfm_gram.h"
 #include "dfm_kernels.h"
+#include "dfm_msgeom.h"
 
 namespace dfm {
 
 namespace {
 
 constexpr int kMwR = 32;
-constexpr int kMwSer = 128;                              // series per item: 8 consumer waves x 16
-constexpr int kMwPer = 32;                               // periods per stage
-constexpr int kMwSteps = kMwPer / 4;
-constexpr int kMwNBuf = 3;
+constexpr int kMwSteps = kMwPer / 4;                     // (kMwSer series per item, kMwPer periods per stage, kMwNBuf stage buffers: dfm_msgeom.h)
 constexpr unsigned kMwRowB = 1152;                       // LDS bytes between the panel rows of a stage (1024 + 128)
 constexpr unsigned kMwPanelB = kMwPer * kMwRowB;         // 36864
 constexpr unsigned kMwFB = kMwPer * kMwR * 8;            // 8192 (R = 32; R = 16 uses half of it)
@@ -57,7 +55,7 @@ __global__ __launch_bounds__(kMwThreads) void mstep_wide_kernel(MstepArgs a, dou
     constexpr int N4 = NX < 4 ? NX : 0;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int N = a.N, T = a.T, B = a.B;
-    const int nst = (T + kMwPer - 1) / kMwPer;                // stages per item
+    const int nst = mw_stages(T);                             // stages per item
     volatile int* itemq = reinterpret_cast<volatile int*>(smem + kMwNBuf * kMwStageB);
     const unsigned itemq_lds = (unsigned)(size_t)(lds_char_ptr)(smem) + kMwNBuf * kMwStageB;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -297,10 +295,7 @@ __global__ __launch_bounds__(256) void mstep_finish_wide_kernel(MstepArgs a, con
 }
 
 // Rp = 16 | 32 with an even N; narrower states (computed 16 wide) where mstep_mfma's 4-KB row ring ends
-bool mstep_wide_supported(int Rpad, int N) {
-    if ((N & 1) != 0 || N < 2) return false;
-    return Rpad == 32 || Rpad == 16 || (Rpad >= 2 && Rpad <= 8 && N * 8 > 4096);
-}
+bool mstep_wide_supported(int Rpad, int N) { return mw_supported(Rpad, N); }
 // Sxf [B][N][Rp] | Sxx [B][N] | 8 queue counters
 size_t mstep_wide_workspace(int B, int N, int Rpad) { return ((size_t)B * N * Rpad + (size_t)B * N) * sizeof(double) + 64; }
 
@@ -327,14 +322,10 @@ hipError_t launch_mstep_wide(const MstepArgs& a, double* ws, int Rpad, int r, in
     int* ctr = reinterpret_cast<int*>(sxx + (size_t)a.B * a.N);
     hipError_t e = hipMemsetAsync(ctr, 0, 32, s);
     if (e != hipSuccess) return e;
-    const int nsb = (a.N + kMwSer - 1) / kMwSer;
+    const int nsb = mw_nsb(a.N);
     const size_t lds = (size_t)kMwNBuf * kMwStageB + kMwRing * sizeof(int) + 32;
-    const int xcd_map = a.B >= 16;
-    const long long NI = (long long)a.B * nsb;
-    int G = num_cu > 0 ? num_cu : 256;
-    G = (G / 8) * 8;
-    if (G < 8) G = 8;
-    if (!xcd_map && NI < G) G = (int)NI;
+    const int xcd_map = mw_xcd_map(a.B);
+    const int G = mw_grid(a.B, nsb, num_cu);
     if (Rpad <= 16) {
         e = launch_mw<16, 0>(a, sxf, sxx, ctr, G, lds, nsb, xcd_map, s, Rpad);
         if (e != hipSuccess) return e;
@@ -347,7 +338,7 @@ hipError_t launch_mstep_wide(const MstepArgs& a, double* ws, int Rpad, int r, in
         }
         return hipGetLastError();
     }
-    const int nx = r <= 16 ? 1 : (r + 3 - 16) / 4;
+    const int nx = mw_nx(r);
     switch (nx) {
         case 1: e = launch_mw<32, 1>(a, sxf, sxx, ctr, G, lds, nsb, xcd_map, s); break;
         case 2: e = launch_mw<32, 2>(a, sxf, sxx, ctr, G, lds, nsb, xcd_map, s); break;
