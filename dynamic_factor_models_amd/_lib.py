@@ -52,6 +52,7 @@ _HD_ARGS = [c_vp] + [c_int] * 5 + [c_vp] * 13 + [c_uint]
 _PX_ARGS = [c_vp] + [c_int] * 6 + [c_vp] * 10 + [c_int] * 3 + [ctypes.c_uint64, ctypes.c_int64] + [c_vp] * 7 + [c_uint]
 _FT_ARGS = [c_vp] + [c_int] * 7 + [c_vp] * 20 + [c_uint]
 _FCAR_ARGS = [c_vp] + [c_int] * 7 + [c_vp] * 18 + [c_uint]
+_SSAR_ARGS = [c_vp] + [c_int] * 8 + [c_vp] * 11 + [ctypes.c_uint64, ctypes.c_int64, c_vp, c_vp, c_uint]
 _ARPASS_ARGS = [c_vp, c_int, c_int, c_int, c_int, c_int, c_int] + [c_vp] * 11 + [c_uint]
 _AREM_ARGS = [c_vp, c_int, c_int, c_int, c_int, c_int, c_int] + [c_vp] * 8 + [c_int, ctypes.c_double] + [c_vp] * 4 + [c_uint]
 _MFPASS_ARGS = [c_vp, c_int, c_int, c_int, c_int, c_int, c_int] + [c_vp] * 11 + [c_uint]
@@ -127,6 +128,8 @@ SYMBOLS = {
     "dfm_em_ar_batch": (c_int, _AREM_ARGS),
     "dfm_forecast_ar_batch_dev": (c_int, _FCAR_ARGS),
     "dfm_forecast_ar_batch": (c_int, _FCAR_ARGS),
+    "dfm_simsmooth_ar_batch_dev": (c_int, _SSAR_ARGS),
+    "dfm_simsmooth_ar_batch": (c_int, _SSAR_ARGS),
     "dfm_ks_pass_mf_batch_dev": (c_int, _MFPASS_ARGS),
     "dfm_ks_pass_mf_batch": (c_int, _MFPASS_ARGS),
     "dfm_em_mf_batch_dev": (c_int, _MFEM_ARGS),

@@ -1028,7 +1028,7 @@ def draw_paths(m: DFMModel, ndraws: int, H: int = 0, *, through: Optional[int] =
     if Lam.shape[0] != cols.size:
         raise ValueError("m.em_params does not match the model's series (was the model changed after estimate?)")
     if np.any(np.nan_to_num(np.asarray(m.uar_coef, dtype=np.float64)[cols]) != 0.0):
-        raise ValueError("draw_paths has no AR idiosyncratic terms: the model carries uar_coef (estimate_ar_idio?)")
+        raise ValueError("draw_paths has no AR idiosyncratic terms: the model carries uar_coef -- draw_paths_ar_idio draws from it")
     if z.shape[0] < A.shape[1] // Lam.shape[1]:
         raise ValueError("the window is shorter than the number of factor lags")
     from ._lib import DfmError
@@ -2018,6 +2018,80 @@ def forecast_ar_idio(m: DFMModel, H: int, *, through: Optional[int] = None, ctx=
     return dict(rows=np.arange(m.initperiod + q, through + H + 1), cols=cols, x=o["xhat"][0], x_sd=np.sqrt(o["xvar"][0]),
                 common=o["common"][0], idio=o["idio"][0], factor=o["f"][0] + mu_f, factor_cov=cov, loglik=float(o["loglik"][0]),
                 mu_f=mu_f, inputs=dict(inputs, v0=v0, mean=mean))
+
+
+def draw_paths_ar_idio(m: DFMModel, ndraws: int, H: int = 0, *, through: Optional[int] = None, seed: int = 20160415,
+                       first_draw: int = 0, quantiles=None, ctx=None) -> dict:
+    """Joint draws of the factor path and of the panel's missing and future cells from the model with AR(n_uarlag) idiosyncratic
+    terms: the counterpart of `forecast_ar_idio`, which gives the marginal moments only -- a fan chart of a series, the probability
+    of an event over several cells.  The AR model's horizon errors are strongly correlated along time; the draws carry that.
+
+    Model, window, `through`, v0 and the data units exactly as `forecast_ar_idio`.  One dfm_simsmooth_ar_batch call on the GPU
+    (include/dfm_hip.h: a simulation smoother; the random stream is a pure function of `seed` and the draw's index first_draw + d,
+    so draws [k, k + n) equal those of a call with first_draw = k).  The draws are independent, with mean `forecast_ar_idio`'s x
+    and the joint covariance of its error: exact posterior draws when the only missing cells are the ragged edge and the horizon;
+    with interior gaps they carry the pass's quasi-differencing convention.  Returns a dict (data units):
+      rows        1-based periods initperiod + q .. through + H
+      cols        column indices (0-based) of m.data: the series `_ar_model_inputs` used
+      factor      [ndraws, rows, r] factor paths (with the factor mean mu_f)
+      x           [ndraws, rows, cols] observed cells as they are, every other cell drawn
+      x_sd        [rows, cols] sample standard deviation of the draws (ndraws >= 2, else 0): 0 on observed cells, elsewhere the
+                  companion of `forecast_ar_idio`'s x_sd that includes the cross-period covariance of the factor estimation error
+      bands       [nq, rows, cols] pointwise nearest-rank quantiles of x (dfm_quantile_bands), with `quantiles`
+    `m` is not modified."""
+    ndraws, H, first_draw = int(ndraws), int(H), int(first_draw)
+    if ndraws < 1:
+        raise ValueError("ndraws must be >= 1")
+    if H < 0:
+        raise ValueError("H must be >= 0")
+    if first_draw < 0:
+        raise ValueError("first_draw must be >= 0")
+    q = int(m.n_uarlag)
+    if not (1 <= q <= 4):
+        raise ValueError("draw_paths_ar_idio needs 1 <= n_uarlag <= 4")
+    qs = None
+    if quantiles is not None:
+        qs = np.atleast_1d(np.asarray(quantiles, dtype=np.float64))
+        if qs.size == 0 or np.any(~(qs >= 0.0)) or np.any(~(qs <= 1.0)):
+            raise ValueError("quantiles must lie in [0, 1]")
+        if ndraws > _QUANTILE_MAX_DRAWS:
+            raise ValueError(f"bands need ndraws <= {_QUANTILE_MAX_DRAWS}")
+    through = m.lastperiod if through is None else int(through)
+    if not (m.lastperiod <= through <= m.T):
+        raise ValueError(f"through must lie in lastperiod..T ({m.lastperiod}..{m.T})")
+    inputs, cols, mu_f, c_i = _ar_model_inputs(m, through)
+    win = slice(m.initperiod - 1, m.lastperiod)
+    v0 = np.nanvar(m.data[win][:, cols] - c_i - m.factor[win] @ inputs["Lam"].T, axis=0)
+    mean = c_i + inputs["Lam"] @ mu_f
+    x = inputs["x"]
+    from ._lib import DfmError
+    ctx, own = _own(ctx)
+    try:
+        args = (x[None], inputs["Lam"][None], inputs["sig2"][None], inputs["rho"][None], inputs["Avar"][None], inputs["Q"][None],
+                inputs["mu0"][None], inputs["P0"][None], ndraws, H)
+        kw = dict(v0=v0[None], seed=int(seed), first_draw=first_draw, mean=mean[None], sd=np.ones((1, cols.size)),
+                  may_have_missing=bool(np.isnan(x).any()))
+        try:
+            o = ctx.simsmooth_ar_batch_host(*args, **kw)
+        except DfmError as err:                     # the information form inverts Q: as draw_paths, retry in covariance form
+            if err.code != -5:
+                raise
+            o = ctx.simsmooth_ar_batch_host(*args, singular_q=True, **kw)
+        xd = o["x"][0]
+        xr = m.data[m.initperiod - 1 + q:through][:, cols]              # observed cells: the data itself, not mean + z
+        obs = ~np.isnan(xr)
+        xd[:, :xr.shape[0], :][:, obs] = xr[obs]
+        bands = None if qs is None else ctx.quantile_bands_host(xd.reshape(ndraws, -1), qs).reshape((qs.size,) + xd.shape[1:])
+    finally:
+        if own:
+            ctx.close()
+    x_sd = xd.std(axis=0, ddof=1) if ndraws > 1 else np.zeros(xd.shape[1:])
+    x_sd[:xr.shape[0]][obs] = 0.0
+    out = dict(rows=np.arange(m.initperiod + q, through + H + 1), cols=cols, factor=o["f"][0] + mu_f, x=xd, x_sd=x_sd,
+               mu_f=mu_f, inputs=dict(inputs, v0=v0, mean=mean))
+    if bands is not None:
+        out["quantiles"], out["bands"] = qs, bands
+    return out
 
 
 def amengual_watson_test(m: DFMModel, nper: int = 4, *, ctx=None):

@@ -77,7 +77,7 @@ struct RouteOpts {
     int mstep_miss_mode = 1;               // DFM_MSTEP_MISS (route): loadings step with missing cells on the matrix pipe (mstep_miss.hip): 0 = never
                                            // (mstep_lam_kernel), 1 = where mstep_lam_kernel keeps its per-series accumulators in global memory
                                            // (Rp > 8 or N > 256), 2 = wherever supported
-    size_t fcar_msg_cap = (size_t)4 << 30;     // DFM_FCAR_MSG_BYTES=n (route): cap of the message buffer of dfm_forecast_ar_batch, which slices its replicates over it (4 GiB)
+    size_t fcar_msg_cap = (size_t)4 << 30;     // DFM_FCAR_MSG_BYTES=n (route): cap of the message buffer of dfm_forecast_ar_batch and dfm_simsmooth_ar_batch, which slice their replicates over it (4 GiB)
     bool odd_pad8 = true;                  // DFM_ODD_PAD8=0 (diagnostics build): odd N at states up to 8 wide stays on collapse_kernel
 };
 
@@ -158,7 +158,8 @@ struct dfm_handle {
                                            // caller does not take them (beside h->ws: the pass itself may reallocate that);
                                            // dfm_forecast_ar_batch_dev: the padded panel, P and loglik likewise, one slice's messages
     DevBlock ss;                           // dfm_simsmooth_batch_dev: roots, the slice's pass parameters, smoothed means, logliks and
-                                           // (no x_draw) difference panels -- beside h->ws for the same reason
+                                           // (no x_draw) difference panels -- beside h->ws for the same reason;
+                                           // dfm_simsmooth_ar_batch_dev: the same, the difference panels always, one slice's messages
     DevBlock nw;                           // dfm_news_batch_dev: targets, the revised old panel, one forecast's xhat, the slice's pass
                                            // parameters, u / a vectors, smoothed means and (no weight) covariance panels
     DevBlock sv;                           // dfm_irf_batch_dev / dfm_histdecomp_batch_dev: named / cum, S, S^-1, the Theta tables, shocks and
@@ -182,11 +183,11 @@ struct dfm_handle {
 };
 
 enum KernelId { K_COLLAPSE = 0, K_RECURSION, K_MSTEP_STATS, K_MSTEP_SOLVE, K_PCA, K_SYNTH, K_PAD,
-                K_COLLAPSE_DMA, K_GRAM, K_COV, K_MEANSCAN, K_PFILL, K_COLLAPSE_MFMA, K_ALS, K_OLS, K_BOOT, K_QUANT, K_COLLAPSE_WIDE, K_EM_UPDATE, K_CHOW, K_MSTEP_MFMA, K_GRAM_XX, K_PASS_FUSED, K_FC_TAIL, K_FC_FILL, K_FC_PAD, K_SS_PREP, K_SS_EXPAND, K_SS_PATH, K_SS_DIFF, K_SS_FINISH, K_SS_FILL, K_NW_REVISE, K_NW_GATHER, K_NW_GAMMA, K_NW_COV, K_NW_IMPACT, K_MF_TABLE, K_MF_MOMENTS, K_MF_SOLVE, K_SV_PREP, K_SV_IRF_FILL, K_SV_SHOCK, K_SV_PATH, K_SV_HD_FILL, K_FT_FILTER, K_FT_FILL, K_FT_EVAL, K_GB_GRAM, K_GB_LOAD, K_GB_VAR, K_SV_SIGN_TABLE, K_SV_SIGN, K_SV_SIGN_KEEP, K_PX_ROWS, K_PX_MOMENT, K_PX_SLOT_TABLE, K_PX_DEN, K_PX_FILL, K_PX_SHOCK, K_MF_SOLVE_BLOCKS, K_FCAR_BACK, K_FCAR_FWD, K_COUNT };
+                K_COLLAPSE_DMA, K_GRAM, K_COV, K_MEANSCAN, K_PFILL, K_COLLAPSE_MFMA, K_ALS, K_OLS, K_BOOT, K_QUANT, K_COLLAPSE_WIDE, K_EM_UPDATE, K_CHOW, K_MSTEP_MFMA, K_GRAM_XX, K_PASS_FUSED, K_FC_TAIL, K_FC_FILL, K_FC_PAD, K_SS_PREP, K_SS_EXPAND, K_SS_PATH, K_SS_DIFF, K_SS_FINISH, K_SS_FILL, K_NW_REVISE, K_NW_GATHER, K_NW_GAMMA, K_NW_COV, K_NW_IMPACT, K_MF_TABLE, K_MF_MOMENTS, K_MF_SOLVE, K_SV_PREP, K_SV_IRF_FILL, K_SV_SHOCK, K_SV_PATH, K_SV_HD_FILL, K_FT_FILTER, K_FT_FILL, K_FT_EVAL, K_GB_GRAM, K_GB_LOAD, K_GB_VAR, K_SV_SIGN_TABLE, K_SV_SIGN, K_SV_SIGN_KEEP, K_PX_ROWS, K_PX_MOMENT, K_PX_SLOT_TABLE, K_PX_DEN, K_PX_FILL, K_PX_SHOCK, K_MF_SOLVE_BLOCKS, K_FCAR_BACK, K_FCAR_FWD, K_SSAR_PARAMS, K_SSAR_EXPAND, K_SSAR_DIFF, K_SSAR_FWD, K_SSAR_FINISH, K_COUNT };
 static const char* const kKernelNames[K_COUNT] = {"collapse_kernel", "recursion_kernel", "mstep_lam_kernel",
                                                   "mstep_solve_kernel", "pca_kernel", "synth_kernel",
                                                   "pad_params_kernel", "collapse_dma_kernel", "gram_kernel",
-                                                  "cov_kernel", "meanscan_kernel", "pfill_kernel", "collapse_mfma_kernel", "als_kernel", "ols_kernel", "var_boot_kernel", "quantile_kernel", "collapse_wide_kernel", "em_update_kernel", "chow_kernel", "mstep_mfma_kernel", "gram_xx_kernel", "pass_fused_kernel", "forecast_tail_kernel", "forecast_fill_kernel", "forecast_pad_kernel", "simsmooth_prep_kernel", "simsmooth_expand_kernel", "simsmooth_path_kernel", "simsmooth_diff_kernel", "simsmooth_finish_kernel", "simsmooth_fill_kernel", "news_revise_kernel", "news_gather_kernel", "news_gamma_kernel", "news_cov_panel_kernel", "news_impact_kernel", "mf_table_kernel", "mf_moments_kernel", "mf_solve_kernel", "sv_prep_kernel", "sv_irf_fill_kernel", "sv_shock_kernel", "sv_path_kernel", "sv_hd_fill_kernel", "filter_kernel", "filter_fill_kernel", "filter_eval_kernel", "gibbs_gram_kernel", "gibbs_load_kernel", "gibbs_var_kernel", "sv_sign_table_kernel", "sv_sign_kernel", "sv_sign_keep_kernel", "px_rows_kernel", "px_moment_kernel", "px_slot_table_kernel", "px_den_kernel", "px_fill_kernel", "px_shock_kernel", "mf_solve_blocks_kernel", "forecast_ar_back_kernel", "forecast_ar_fwd_kernel"};
+                                                  "cov_kernel", "meanscan_kernel", "pfill_kernel", "collapse_mfma_kernel", "als_kernel", "ols_kernel", "var_boot_kernel", "quantile_kernel", "collapse_wide_kernel", "em_update_kernel", "chow_kernel", "mstep_mfma_kernel", "gram_xx_kernel", "pass_fused_kernel", "forecast_tail_kernel", "forecast_fill_kernel", "forecast_pad_kernel", "simsmooth_prep_kernel", "simsmooth_expand_kernel", "simsmooth_path_kernel", "simsmooth_diff_kernel", "simsmooth_finish_kernel", "simsmooth_fill_kernel", "news_revise_kernel", "news_gather_kernel", "news_gamma_kernel", "news_cov_panel_kernel", "news_impact_kernel", "mf_table_kernel", "mf_moments_kernel", "mf_solve_kernel", "sv_prep_kernel", "sv_irf_fill_kernel", "sv_shock_kernel", "sv_path_kernel", "sv_hd_fill_kernel", "filter_kernel", "filter_fill_kernel", "filter_eval_kernel", "gibbs_gram_kernel", "gibbs_load_kernel", "gibbs_var_kernel", "sv_sign_table_kernel", "sv_sign_kernel", "sv_sign_keep_kernel", "px_rows_kernel", "px_moment_kernel", "px_slot_table_kernel", "px_den_kernel", "px_fill_kernel", "px_shock_kernel", "mf_solve_blocks_kernel", "forecast_ar_back_kernel", "forecast_ar_fwd_kernel", "simsmooth_ar_params_kernel", "simsmooth_ar_expand_kernel", "simsmooth_ar_diff_kernel", "simsmooth_ar_fwd_kernel", "simsmooth_ar_finish_kernel"};
 
 namespace dfm { int handle_device(const dfm_handle* h) { return h->device; } }   // (probe.hip)
 
@@ -2681,6 +2682,153 @@ int dfm_simsmooth_batch(dfm_handle* h, int B, int D, int T, int N, int r, int p,
     if (int rc = st.begin()) return rc;
     int rc = st.finish(simsmooth_run(h, B, D, T, N, r, p, H, x_d, lam_d, R_d, A_d, Q_d, mu_d, P0_d, mean_d, sd_d, seed, first_draw, f_d,
                                      xo_d, ll_d, flags));
+    if (rc == 0) rc = post_check(h, ll_host.data(), (int)BD);
+    return rc;
+}
+
+// ---- posterior path draws with AR idiosyncratic terms (simsmooth_ar.hip) ------------------------------------------------------
+// The factor side runs the kernels above on the state of m = max(p, q + 1) lags (Avar padded with zero blocks), with T = n output
+// rows and no horizon of its own: the horizon rows are rows of the path.  Per slice of pass replicates j = b D + d: expand the
+// parameters (mu0 = 0; rho by simsmooth_ar_expand_kernel), f+ into f_draw, the difference panels, the AR pass on them into g, then
+// (x_draw) the backward messages of forecast_ar_back_kernel on (difference panel, g) and the assembling forward kernel, and
+// f_draw += g behind it.  A slice is min(kSsSlice, fcar_msg_cap / one replicate's messages) pass replicates, at least one;
+// everything of a slice lives in h->ss (the difference panels too: x_draw has q rows per replicate fewer, and a workgroup of the
+// forward kernel would write cells of x_draw that another one's difference panel still holds).
+static int simsmooth_ar_check(dfm_handle* h, int B, int D, int T, int N, int r, int p, int q, int H, const double* panel,
+                              const double* Lam, const double* sig2, const double* rho, const double* Avar, const double* Q,
+                              const double* mu0, const double* P0, const double* mean, const double* sd, const double* f_draw) {
+    if (!h) return DFM_E_NULL;
+    if (D < 1) return fail(h, DFM_E_DIMS, "D (draws per replicate) must be >= 1%s");
+    if (!f_draw) return fail(h, DFM_E_NULL, "required pointer is NULL%s");
+    if (int rc = forecast_ar_check(h, B, T, N, r, p, q, H, panel, Lam, sig2, rho, Avar, Q, mu0, P0, mean, sd, f_draw, f_draw)) return rc;
+    if ((long long)B * D > 0x7fffffffLL) return fail(h, DFM_E_DIMS, "B * D must be < 2^31%s");
+    return 0;
+}
+
+// ll_all: [B D] device log-likelihoods of the difference panels (the host entry checks them), or null (h->ss, per slice)
+static int simsmooth_ar_run(dfm_handle* h, int B, int D, int T, int N, int r, int p, int q, int H, const double* panel,
+                            const double* Lam, const double* sig2, const double* rho, const double* Avar, const double* Q,
+                            const double* mu0, const double* P0, const double* v0, const double* mean, const double* sd,
+                            uint64_t seed, int64_t first_draw, double* f_draw, double* x_draw, double* ll_all, unsigned flags) {
+    HIP_TRY(h, hipSetDevice(h->device));
+    const int m = p > q + 1 ? p : q + 1;
+    const size_t d = sizeof(double), k = (size_t)r * m, TH = (size_t)T + H, n = TH - q;
+    const long long BD = (long long)B * D;
+    const size_t per = forecast_ar_msg_bytes((int)n, N, q);
+    size_t Sl = h->opt.fcar_msg_cap / per;
+    if (Sl > (size_t)kSsSlice) Sl = kSsSlice;
+    if (Sl < 1) Sl = 1;
+    const int Smax = (int)(BD < (long long)Sl ? BD : (long long)Sl);
+    size_t off = 0;
+    const size_t o_LP0 = take(off, (size_t)B * k * k * d), o_LQ = take(off, (size_t)B * r * r * d),
+                 o_Ap = p < m ? take(off, (size_t)B * r * k * d) : (size_t)-1,
+                 o_L = take(off, (size_t)Smax * N * r * d), o_R = take(off, (size_t)Smax * N * d),
+                 o_rho = take(off, (size_t)Smax * N * q * d), o_A = take(off, (size_t)Smax * r * k * d),
+                 o_Q = take(off, (size_t)Smax * r * r * d), o_m = take(off, (size_t)Smax * k * d),
+                 o_P = take(off, (size_t)Smax * k * k * d), o_g = take(off, (size_t)Smax * n * r * d),
+                 o_ll = ll_all ? (size_t)-1 : take(off, (size_t)Smax * d), o_x = take(off, (size_t)Smax * TH * N * d),
+                 o_msg = x_draw ? take(off, (size_t)Smax * per) : (size_t)-1,
+                 o_last = x_draw ? take(off, (size_t)Smax * N * sizeof(int)) : (size_t)-1;
+    HIP_TRY(h, h->ss.grow(off));
+    const double* Am = Avar;
+    if (p < m) {
+        ProfScope ps(h, K_SSAR_PARAMS);
+        HIP_TRY(h, launch_simsmooth_ar_params(B, r, p, m, Avar, at<double>(h->ss, o_Ap), h->stream));
+        Am = at<double>(h->ss, o_Ap);
+    }
+    // the factor side: the plain model's kernels on m lags and n rows
+    SsArgs a{};
+    a.B = B; a.D = D; a.T = (int)n; a.N = N; a.r = r; a.p = m; a.H = 0;
+    a.Lam = Lam; a.R = sig2; a.A = Am; a.Q = Q; a.mu0 = mu0; a.P0 = P0;
+    a.seed = seed; a.first_draw = first_draw; a.f_draw = f_draw;
+    a.LP0 = at<double>(h->ss, o_LP0); a.LQ = at<double>(h->ss, o_LQ);
+    a.eLam = at<double>(h->ss, o_L); a.eR = at<double>(h->ss, o_R); a.eA = at<double>(h->ss, o_A); a.eQ = at<double>(h->ss, o_Q);
+    a.emu0 = at<double>(h->ss, o_m); a.eP0 = at<double>(h->ss, o_P);
+    double* erho = at<double>(h->ss, o_rho);
+    double* g = at<double>(h->ss, o_g);
+    double* diff = at<double>(h->ss, o_x);
+    // the series side: the generator and the assembling forward kernel read the caller's parameters, the backward kernel the slice's
+    SsArArgs gen{};
+    gen.n = (int)n; gen.N = N; gen.r = r; gen.q = q;
+    gen.Lam = Lam; gen.sig2 = sig2; gen.rho = rho; gen.v0 = v0; gen.mean = mean; gen.sd = sd;
+    gen.f = g; gen.msg = at<double>(h->ss, o_msg); gen.last = at<int>(h->ss, o_last);
+    gen.dr.D = D; gen.dr.T = T; gen.dr.k = (int)k; gen.dr.seed = seed; gen.dr.first_draw = first_draw;
+    gen.dr.X = panel; gen.dr.fplus = f_draw; gen.dr.mu0 = mu0; gen.dr.LP0 = a.LP0; gen.dr.diff = diff; gen.dr.x_draw = x_draw;
+    gen.dr.check_nan = (flags & DFM_F_MAY_HAVE_MISSING) ? 0 : 1; gen.dr.status = h->status_dev;
+    FcArArgs back{};
+    back.n = (int)n; back.N = N; back.r = r; back.q = q;
+    back.panel = diff; back.f = g; back.Lam = a.eLam; back.sig2 = a.eR; back.rho = erho;
+    back.msg = gen.msg; back.last = gen.last;
+    {
+        ProfScope ps(h, K_SS_PREP);
+        HIP_TRY(h, launch_simsmooth_prep(a, h->stream));
+    }
+    for (long long j0 = 0; j0 < BD; j0 += Smax) {
+        const int S = (int)(BD - j0 < Smax ? BD - j0 : Smax);
+        a.j0 = j0; a.S = S;
+        gen.dr.j0 = j0; gen.S = S; back.b0 = 0; back.S = S;
+        double* ll = ll_all ? ll_all + j0 : at<double>(h->ss, o_ll);
+        {
+            ProfScope ps(h, K_SS_EXPAND);
+            HIP_TRY(h, launch_simsmooth_expand(a, h->stream));
+        }
+        {
+            ProfScope ps(h, K_SSAR_EXPAND);
+            HIP_TRY(h, launch_simsmooth_ar_expand(S, j0, D, (size_t)N * q, rho, erho, h->stream));
+        }
+        {
+            ProfScope ps(h, K_SS_PATH);
+            HIP_TRY(h, launch_simsmooth_path(a, h->stream));
+        }
+        {
+            ProfScope ps(h, K_SSAR_DIFF);
+            HIP_TRY(h, launch_simsmooth_ar_diff(gen, h->stream));
+        }
+        if (int rc = ar_pass_run(h, S, (int)TH, N, r, m, q, diff, a.eLam, a.eR, erho, a.eA, a.eQ, a.emu0, a.eP0, g, nullptr, ll,
+                                 flags | DFM_F_MAY_HAVE_MISSING)) return rc;
+        if (x_draw) {
+            {
+                ProfScope ps(h, K_FCAR_BACK);
+                HIP_TRY(h, launch_forecast_ar_back(back, h->stream));
+            }
+            ProfScope ps(h, K_SSAR_FWD);
+            HIP_TRY(h, launch_simsmooth_ar_fwd(gen, h->stream));
+        }
+        {
+            ProfScope ps(h, K_SSAR_FINISH);
+            HIP_TRY(h, launch_simsmooth_ar_finish((size_t)S * n * r, g, f_draw + (size_t)j0 * n * r, h->stream));
+        }
+    }
+    return 0;
+}
+
+int dfm_simsmooth_ar_batch_dev(dfm_handle* h, int B, int D, int T, int N, int r, int p, int q, int H, const double* panel,
+                               const double* Lam, const double* sig2, const double* rho, const double* Avar, const double* Q,
+                               const double* mu0, const double* P0, const double* v0, const double* mean, const double* sd,
+                               uint64_t seed, int64_t first_draw, double* f_draw, double* x_draw, unsigned flags) {
+    if (int rc = simsmooth_ar_check(h, B, D, T, N, r, p, q, H, panel, Lam, sig2, rho, Avar, Q, mu0, P0, mean, sd, f_draw)) return rc;
+    return simsmooth_ar_run(h, B, D, T, N, r, p, q, H, panel, Lam, sig2, rho, Avar, Q, mu0, P0, v0, mean, sd, seed, first_draw, f_draw,
+                            x_draw, nullptr, flags);
+}
+
+int dfm_simsmooth_ar_batch(dfm_handle* h, int B, int D, int T, int N, int r, int p, int q, int H, const double* panel,
+                           const double* Lam, const double* sig2, const double* rho, const double* Avar, const double* Q,
+                           const double* mu0, const double* P0, const double* v0, const double* mean, const double* sd,
+                           uint64_t seed, int64_t first_draw, double* f_draw, double* x_draw, unsigned flags) {
+    if (int rc = simsmooth_ar_check(h, B, D, T, N, r, p, q, H, panel, Lam, sig2, rho, Avar, Q, mu0, P0, mean, sd, f_draw)) return rc;
+    if (int rc = status_epoch(h)) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t m = (size_t)(p > q + 1 ? p : q + 1), k = (size_t)r * m, n = (size_t)T + H - q, BD = (size_t)B * D, n_R = (size_t)B * N;
+    std::vector<double> ll_host(BD);
+    HostStage st(h, 256);
+    double *x_d, *lam_d, *R_d, *rho_d, *A_d, *Q_d, *mu_d, *P0_d, *v0_d, *mean_d, *sd_d, *f_d, *xo_d, *ll_d;
+    st.in(panel, (size_t)B * T * N, x_d); st.in(Lam, (size_t)B * N * r, lam_d); st.in(sig2, n_R, R_d); st.in(rho, n_R * q, rho_d);
+    st.in(Avar, (size_t)B * r * r * p, A_d); st.in(Q, (size_t)B * r * r, Q_d); st.in(mu0, (size_t)B * k, mu_d); st.in(P0, (size_t)B * k * k, P0_d);
+    st.in(v0, v0 ? n_R : 0, v0_d); st.in(mean, mean ? n_R : 0, mean_d); st.in(sd, sd ? n_R : 0, sd_d);
+    st.out(f_draw, BD * n * r, f_d); st.out(x_draw, x_draw ? BD * n * N : 0, xo_d); st.out(ll_host.data(), BD, ll_d);
+    if (int rc = st.begin()) return rc;
+    int rc = st.finish(simsmooth_ar_run(h, B, D, T, N, r, p, q, H, x_d, lam_d, R_d, rho_d, A_d, Q_d, mu_d, P0_d, v0_d, mean_d, sd_d, seed,
+                                        first_draw, f_d, xo_d, ll_d, flags));
     if (rc == 0) rc = post_check(h, ll_host.data(), (int)BD);
     return rc;
 }

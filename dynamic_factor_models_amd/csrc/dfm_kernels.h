@@ -496,6 +496,22 @@ hipError_t launch_forecast_fill(const FcFillArgs& a, hipStream_t s);
 hipError_t launch_forecast_pad(int B, int T, int H, int N, const double* panel, double* out, bool check_nan, int* status,
                                hipStream_t s);
 
+// The path draws of the same model (simsmooth_ar.hip; dfm_simsmooth_ar_batch): what the two kernels that walk the simulated series
+// read beside FcArArgs (SsArArgs, below).  There the launch covers the pass replicates j0 .. j0 + S - 1 (j = b D + d), Lam / sig2 /
+// rho / v0 / mean / sd are the caller's [B] arrays, and f, msg, last are the slice's ([S]: the smoothed mean g of the difference
+// panels).  A struct of its own: grown by these fields, FcArArgs cost two instances of forecast_ar_fwd_kernel a wave per SIMD.
+struct SsArDraw {
+    int D, T, k;                                  // draws per replicate, panel rows, k = r max(p, q + 1)
+    long long j0;
+    uint64_t seed; int64_t first_draw;
+    const double* X;                              // [B][T][N] the caller's panel (NaN = missing)
+    const double* fplus;                          // [B D][n][r] the simulated factor path (f_draw before g joins)
+    const double* mu0; const double* LP0;         // [B][k], [B][k][k] (lower PSD root of P0)
+    double* diff;                                 // [S][n + q][N] difference panels of the slice
+    double* x_draw;                               // [B D][n][N]
+    int check_nan; int* status;                   // a NaN in X raises bit 1 of *status (no DFM_F_MAY_HAVE_MISSING)
+};
+
 // The series side of the forecasts with AR(q) idiosyncratic terms (forecast_ar.hip): one launch covers the S replicates b0 ..
 // b0 + S - 1 of the call, whose messages fill the slice buffer.
 struct FcArArgs {
@@ -512,6 +528,13 @@ struct FcArArgs {
 hipError_t launch_forecast_ar_back(const FcArArgs& a, hipStream_t s);
 hipError_t launch_forecast_ar_fwd(const FcArArgs& a, hipStream_t s);
 size_t forecast_ar_msg_bytes(int n, int N, int q);   // the messages of ONE replicate
+struct SsArArgs : FcArArgs { SsArDraw dr; };
+hipError_t launch_simsmooth_ar_diff(const SsArArgs& a, hipStream_t s);      // simsmooth_ar.hip
+hipError_t launch_simsmooth_ar_fwd(const SsArArgs& a, hipStream_t s);       // forecast_ar.hip: the forward kernel's text
+// A_pad [B][r][r m] = [A_1 .. A_p 0 ..]; erho [S][N][q] = rho of replicate (j0 + s) / D
+hipError_t launch_simsmooth_ar_params(int B, int r, int p, int m, const double* Avar, double* Apad, hipStream_t s);
+hipError_t launch_simsmooth_ar_expand(int S, long long j0, int D, size_t per, const double* src, double* dst, hipStream_t s);
+hipError_t launch_simsmooth_ar_finish(size_t n, const double* g, double* f_draw, hipStream_t s);   // f_draw += g
 
 // Posterior draws of factor and panel paths, Durbin-Koopman simulation smoother (simsmooth.hip).  Pass replicate j = b D + d;
 // a call runs its B D pass replicates in slices j0 .. j0 + S - 1.

@@ -1,5 +1,5 @@
 // dfm_philox.h -- Philox4x32-10 counter-based generator (Salmon et al. 2011): every number is a pure function
-// of (key, counter), so results do not depend on the launch geometry.  Shared by synth.hip, boot.hip and simsmooth.hip.
+// of (key, counter), so results do not depend on the launch geometry.  Shared by synth.hip, boot.hip, simsmooth.hip and dfm_fcar.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -28,32 +28,12 @@
 //
 // Messages: q + q (q + 1) / 2 doubles per cell, component-major -- msg[((b' NC + c) n + t) N + i], b' the replicate inside the
 // slice -- so the lanes' stores of one component at one row are contiguous.  capi.hip slices the replicates over the buffer.
-#include "dfm_cell.h"
-#include "dfm_kernels.h"
+#include "dfm_fcar.h"
 
 namespace dfm {
 
 constexpr size_t kFcArLds = 48 * 1024;
 constexpr double kFcArPivotTol = 0x1p-44;   // a pivot of the message's L D L' below this share of its diagonal entry is rounding noise
-
-// The lane's series: loadings, AR coefficients, innovation variance.  An idle lane (behind the block's last series) walks series
-// N - 1 beside the others and stores nothing: it stays for the barriers.
-template <int Q, int RB>
-struct FcArSeries {
-    CellLam<1, RB> lam;
-    double rho[Q], sig2;
-    int i;
-    bool live;
-    __device__ __forceinline__ void load(const FcArArgs& a, size_t b, const CellLane& ln) {
-        live = ln.live;
-        i = live ? ln.i0 : a.N - 1;
-        lam.load(a.Lam, b, a.N, i, a.r);
-        const size_t bi = b * a.N + i;
-#pragma unroll
-        for (int l = 0; l < Q; ++l) rho[l] = a.rho[bi * Q + l];
-        sig2 = a.sig2[bi];
-    }
-};
 
 template <int Q, int RB>
 __global__ __launch_bounds__(kCellBlockLanes) void forecast_ar_back_kernel(FcArArgs a) {
@@ -135,21 +115,35 @@ __global__ __launch_bounds__(kCellBlockLanes) void forecast_ar_back_kernel(FcArA
     if (se.live) a.last[bl * N + se.i] = last;
 }
 
-template <int Q, int RB>
-__global__ __launch_bounds__(kCellBlockLanes) void forecast_ar_fwd_kernel(FcArArgs a) {
+// DRAW (simsmooth_ar_fwd_kernel; dfm_simsmooth_ar_batch): the same filter on the difference panel D = X - x+ of pass replicate
+// j = j0 + bl, which is not read but formed again -- the lane re-runs the e+ recursion of simsmooth_ar_diff_kernel from its counters
+// (SsArIdio) on the staged f+ rows -- with a.f the smoothed mean g of D; the cell written is the draw, x_draw = mean + sd (lam' (f+ + g)
+// + e+ + ehat*) off the observed cells.  Parameters are those of replicate j / D, f / msg / last the slice's.
+template <int Q, int RB, bool DRAW>
+__device__ __forceinline__ void fc_ar_fwd(const FcArArgs& a, const SsArDraw* dr) {
     constexpr int NC = Q + Q * (Q + 1) / 2;
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int n = a.n, N = a.N, r = a.r, np = r * (r + 1) / 2, tid = threadIdx.x;
     const int s = (int)(blockIdx.x % (unsigned)a.geo.nsblk);
-    const size_t bl = blockIdx.x / (unsigned)a.geo.nsblk, b = (size_t)a.b0 + bl;
-    const bool wantVar = a.xvar != nullptr, scale = a.mean != nullptr;
+    const size_t bl = blockIdx.x / (unsigned)a.geo.nsblk;
+    const size_t j = DRAW ? (size_t)dr->j0 + bl : 0;                             // pass replicate (DRAW)
+    const size_t b = DRAW ? j / (size_t)dr->D : (size_t)a.b0 + bl;               // the parameters' replicate
+    const size_t bf = DRAW ? bl : b;                                              // the replicate of the f / P rows
+    const bool wantVar = !DRAW && a.xvar != nullptr, scale = a.mean != nullptr;
     double* sf = sm;
-    double* sP = sm + (size_t)a.geo.RC * r;
+    double* sP = sm + (size_t)a.geo.RC * r;                                       // (DRAW: the f+ rows)
     FcArSeries<Q, RB> se;
     se.load(a, b, cell_lane<1>(a.geo, tid, s, N));
     const size_t bi = b * N + se.i;
     const double mu = scale ? a.mean[bi] : 0.0, sd = scale ? a.sd[bi] : 1.0;
     const int last = a.last[bl * N + se.i];
+    SsArIdio<Q, RB> gen;
+    if constexpr (DRAW) {
+        double* sz = sm + (size_t)a.geo.RC * 2 * r;
+        const uint64_t key = ssar_key(dr->seed, dr->first_draw, (int)(j % (size_t)dr->D));
+        ssar_stage_z(*dr, b, key, Q * r, sz, sz + 32);
+        gen.start(a, *dr, se, b, key, sz, s * a.geo.NPB);
+    }
     double av[Q], P[Q][Q];
     {
         const double v0 = a.v0 ? a.v0[bi] : se.sig2;
@@ -160,18 +154,22 @@ __global__ __launch_bounds__(kCellBlockLanes) void forecast_ar_fwd_kernel(FcArAr
             for (int j = 0; j < Q; ++j) P[i][j] = i == j ? v0 : 0.0;
         }
     }
-    const double* xcol = a.panel + (b * (size_t)(n + Q) + Q) * N + se.i;
+    // output row t of the lane's series: xcol[t N] for t < nx (DRAW: the caller's T-row panel, NaN behind it)
+    const double* xcol = DRAW ? dr->X + (b * (size_t)dr->T + Q) * N + se.i : a.panel + (b * (size_t)(n + Q) + Q) * N + se.i;
+    const int nx = DRAW ? dr->T - Q : n;
     const double* mcol = a.msg + bl * NC * (size_t)n * N + se.i;
     double xn = xcol[0];
     for (int ck = 0; ck < a.geo.nchunk; ++ck) {
         const int t0 = ck * a.geo.RC, t1 = t0 + a.geo.RC < n ? t0 + a.geo.RC : n;
         __syncthreads();
-        cell_stage(sf, a.f + (b * n + t0) * r, (t1 - t0) * r);
-        if (wantVar) cell_stage(sP, a.P + (b * n + t0) * np, (t1 - t0) * np);
+        cell_stage(sf, a.f + (bf * n + t0) * r, (t1 - t0) * r);
+        if (wantVar) cell_stage(sP, a.P + (bf * n + t0) * np, (t1 - t0) * np);
+        if constexpr (DRAW) cell_stage(sP, dr->fplus + (j * n + t0) * r, (t1 - t0) * r);
         __syncthreads();
         for (int t = t0; t < t1; ++t) {
             const double x = xn;
-            if (t + 1 < n) xn = xcol[(size_t)(t + 1) * N];
+            if (t + 1 < nx) xn = xcol[(size_t)(t + 1) * N];
+            else if constexpr (DRAW) xn = __longlong_as_double(0x7FF8000000000000ll);
             const bool obs = x == x;
             const bool need = !obs && t < last;
             // the message of the rows behind t, where there is one
@@ -188,7 +186,12 @@ __global__ __launch_bounds__(kCellBlockLanes) void forecast_ar_fwd_kernel(FcArAr
                 const double* Pt = sP + (size_t)(t - t0) * np;
                 DFM_CELL_QUAD(qf, se.lam.l[0], Pt, RB, r)
             }
-            const double u = obs ? x - m : 0.0;
+            double mp = 0.0, ep = 0.0;
+            if constexpr (DRAW) {
+                mp = se.lam.dot(0, sP + (size_t)(t - t0) * r, r);
+                ep = gen.step(se, t);
+            }
+            const double u = obs ? (DRAW ? x - (mp + ep) : x) - m : 0.0;
             // predict
             double rP[Q], an[Q], Pn[Q][Q];
             an[0] = 0.0;
@@ -288,7 +291,13 @@ __global__ __launch_bounds__(kCellBlockLanes) void forecast_ar_fwd_kernel(FcArAr
                     }
                 }
             }
-            if (se.live) {
+            if constexpr (DRAW) {
+                if (se.live) {
+                    const double v = obs ? x : (mp + m) + (ep + eh);
+                    const double xd[1] = {scale ? mu + sd * v : v};
+                    cell_st<1>(dr->x_draw + (j * n + t) * N + se.i, xd);
+                }
+            } else if (se.live) {
                 const double cm = scale ? mu + sd * m : m;
                 const double e = obs ? u : eh;
                 const double id[1] = {scale ? sd * e : e};
@@ -309,39 +318,55 @@ __global__ __launch_bounds__(kCellBlockLanes) void forecast_ar_fwd_kernel(FcArAr
     }
 }
 
-// Both kernels on the geometry of series_geometry (dfm_cellgeom.h): a staged row is f_t (backward), f_t and the packed P_t (forward).
 template <int Q, int RB>
-static hipError_t launch_fc_ar_q(FcArArgs a, bool back, hipStream_t s) {
-    const int np = a.r * (a.r + 1) / 2, row = back ? a.r : a.r + (a.xvar ? np : 0);
-    a.geo = series_geometry(a.N, row, a.n, kFcArLds);
-    const size_t blocks = (size_t)a.S * a.geo.nsblk, lds = (size_t)a.geo.RC * row * sizeof(double);
+__global__ __launch_bounds__(kCellBlockLanes) void forecast_ar_fwd_kernel(FcArArgs a) { fc_ar_fwd<Q, RB, false>(a, nullptr); }
+template <int Q, int RB>
+__global__ __launch_bounds__(kCellBlockLanes) void simsmooth_ar_fwd_kernel(SsArArgs a) { fc_ar_fwd<Q, RB, true>(a, &a.dr); }
+
+// The kernels on the geometry of series_geometry (dfm_cellgeom.h): a staged row is f_t (backward), f_t and the packed P_t
+// (forward), g_t and f+_t with the z+ tail behind the chunk (draw).
+enum FcArKind { kFcArBack, kFcArFwd, kFcArDraw };
+
+template <int Q, int RB, class Args>
+static hipError_t launch_fc_ar_q(Args a, FcArKind kind, hipStream_t s) {
+    const int np = a.r * (a.r + 1) / 2;
+    const int row = kind == kFcArBack ? a.r : kind == kFcArDraw ? 2 * a.r : a.r + (a.xvar ? np : 0);
+    const size_t tail = kind == kFcArDraw ? kSsArLdsTail * sizeof(double) : 0;
+    a.geo = series_geometry(a.N, row, a.n, kFcArLds - tail);
+    const size_t blocks = (size_t)a.S * a.geo.nsblk, lds = (size_t)a.geo.RC * row * sizeof(double) + tail;
     if (blocks > 0x7fffffffu) return hipErrorInvalidValue;
-    void (*k)(FcArArgs) = forecast_ar_fwd_kernel<Q, RB>;
-    if (back) k = forecast_ar_back_kernel<Q, RB>;
-    hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(a.geo.threads), lds, s, a);
+    if constexpr (std::is_same_v<Args, SsArArgs>) {
+        hipLaunchKernelGGL((simsmooth_ar_fwd_kernel<Q, RB>), dim3((unsigned)blocks), dim3(a.geo.threads), lds, s, a);
+    } else {
+        void (*k)(FcArArgs) = forecast_ar_fwd_kernel<Q, RB>;
+        if (kind == kFcArBack) k = forecast_ar_back_kernel<Q, RB>;
+        hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(a.geo.threads), lds, s, a);
+    }
     return hipGetLastError();
 }
 
-template <int Q>
-static hipError_t launch_fc_ar_r(const FcArArgs& a, bool back, hipStream_t s) {
-    if (a.r <= 4) return launch_fc_ar_q<Q, 4>(a, back, s);
-    if (a.r <= 8) return launch_fc_ar_q<Q, 8>(a, back, s);
-    return launch_fc_ar_q<Q, 16>(a, back, s);
+template <int Q, class Args>
+static hipError_t launch_fc_ar_r(const Args& a, FcArKind kind, hipStream_t s) {
+    if (a.r <= 4) return launch_fc_ar_q<Q, 4>(a, kind, s);
+    if (a.r <= 8) return launch_fc_ar_q<Q, 8>(a, kind, s);
+    return launch_fc_ar_q<Q, 16>(a, kind, s);
 }
 
-static hipError_t launch_fc_ar(const FcArArgs& a, bool back, hipStream_t s) {
+template <class Args>
+static hipError_t launch_fc_ar(const Args& a, FcArKind kind, hipStream_t s) {
     if (a.r < 1 || a.r > 16 || a.n < 1 || a.S < 1) return hipErrorInvalidValue;
     switch (a.q) {
-        case 1: return launch_fc_ar_r<1>(a, back, s);
-        case 2: return launch_fc_ar_r<2>(a, back, s);
-        case 3: return launch_fc_ar_r<3>(a, back, s);
-        case 4: return launch_fc_ar_r<4>(a, back, s);
+        case 1: return launch_fc_ar_r<1>(a, kind, s);
+        case 2: return launch_fc_ar_r<2>(a, kind, s);
+        case 3: return launch_fc_ar_r<3>(a, kind, s);
+        case 4: return launch_fc_ar_r<4>(a, kind, s);
     }
     return hipErrorInvalidValue;
 }
 
-hipError_t launch_forecast_ar_back(const FcArArgs& a, hipStream_t s) { return launch_fc_ar(a, true, s); }
-hipError_t launch_forecast_ar_fwd(const FcArArgs& a, hipStream_t s) { return launch_fc_ar(a, false, s); }
+hipError_t launch_forecast_ar_back(const FcArArgs& a, hipStream_t s) { return launch_fc_ar(a, kFcArBack, s); }
+hipError_t launch_forecast_ar_fwd(const FcArArgs& a, hipStream_t s) { return launch_fc_ar(a, kFcArFwd, s); }
+hipError_t launch_simsmooth_ar_fwd(const SsArArgs& a, hipStream_t s) { return launch_fc_ar(a, kFcArDraw, s); }
 
 size_t forecast_ar_msg_bytes(int n, int N, int q) {
     return (size_t)(q + q * (q + 1) / 2) * (size_t)n * N * sizeof(double);

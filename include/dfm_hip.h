@@ -624,6 +624,48 @@ int dfm_forecast_ar_batch(dfm_handle* h, int B, int T, int N, int r, int p, int 
                           double* xhat, double* xvar, double* common, double* idio, double* f_out, double* P_out,
                           double* loglik, unsigned flags);
 
+/* Joint posterior draws of the factor path and of the panel's missing and horizon cells from the same model
+ * (csrc/simsmooth_ar.hip): what dfm_simsmooth_batch is to dfm_forecast_batch, for dfm_forecast_ar_batch.  Inputs and conventions as
+ * dfm_forecast_ar_batch, D draws per replicate; outputs have its n = T + H - q rows (panel rows q .. T+H-1).  m = max(p, q + 1),
+ * k = r m.  Draw d of replicate b (simulation smoother of Durbin and Koopman 2002; every n below is a fresh N(0, 1)):
+ *   1. State.  z+ = mu0 + L_P0 n: the state mu0 / P0 describe, lags f_{q-1} .. f_{q-m} in 0-based panel rows.
+ *   2. Factor path.  f+_t = sum_j A_j f+_{t-j} + L_Q n_t for the n output rows, horizon included.
+ *   3. Pre-sample terms, l = 1 .. q: e+_{q-l,i} = X_{q-l,i} - lam_i' f+_{q-l} where that panel cell is observed, sqrt(v0_i) n where it
+ *      is missing (v0 NULL: sig2_i).
+ *   4. Series path.  e+_ti = sum_l rho_il e+_{t-l,i} + sqrt(sig2_i) n_ti and x+_ti = lam_i' f+_t + e+_ti over the n output rows.
+ *   5. Difference panel, T + H rows: rows < q are 0 where X is observed and NaN where it is not; rows q .. T-1 are X - x+ (NaN where
+ *      X is NaN); the H horizon rows are NaN.
+ *   6. Smoothed difference.  g, ehat* are what dfm_forecast_ar_batch computes on that panel with H = 0 extra rows, mu0 = 0 and the
+ *      caller's other parameters and v0: the AR pass's f_smooth, and the per-series smoother's mean of the residuals D - lam' g.
+ *   7. Outputs.  f_draw_t = f+_t + g_t                                                                              [B][D][n][r]
+ *      x_draw (may be NULL) = mean_i + sd_i X_ti on an observed cell (bit for bit X_ti when mean / sd are NULL), and
+ *      mean_i + sd_i (lam_i' f_draw_t + e+_ti + ehat*_ti) on every other cell                                       [B][D][n][N]
+ * Exactness.  xhat of dfm_forecast_ar_batch is an affine map of the observed cells, so the draws are independent with mean xhat
+ * and the joint covariance of xhat's error.  They are exact posterior draws on panels whose only missing cells are ragged-edge and
+ * horizon cells, given rows 0 .. q-1 -- there the draws' variance is the exact form xvar of dfm_forecast_ar_batch leaves out.
+ * With interior gaps they carry the pass's quasi-differencing convention (a quasi-difference is missing when any of its q + 1
+ * cells is): mean and covariance are then those of xhat's error, not of the exact posterior.  Cells before a
+ * series' first q consecutive observed output rows carry the v0 prior.
+ * Random stream (part of the contract, as in dfm_simsmooth_batch): Philox4x32-10, Box-Muller on two 53-bit uniforms; key =
+ * seed ^ (0x9E3779B97F4A7C15 (first_draw + d + 1)), stream word 16 b + s, element c of a pair is component c mod 2 at idx:
+ *   s = 1  z+, idx = c / 2, c < k                     s = 2  eta of output row t, idx = t ceil(r/2) + c / 2
+ *   s = 3  eps+ of output row t, idx = t ceil(N/2) + i / 2, c = i
+ *   s = 5  pre-sample term l of series i, idx = (l - 1) ceil(N/2) + i / 2, c = i
+ * Roots by the rule of dfm_simsmooth_batch (DFM_F_SINGULAR_Q works).  Draws [k, k + D) of a call equal those of a call with
+ * first_draw = k.  An index depends on neither the missing cells nor the launch geometry nor the slicing.
+ * Status: as dfm_forecast_ar_batch (f_draw in the place of xhat and f_out), plus D < 1: DFM_E_DIMS; B D >= 2^31: DFM_E_DIMS.
+ * Allocates in the handle (kept for the next call): the roots and, for one slice of min(8192, DFM_FCAR_MSG_BYTES / one replicate's
+ * messages) pass replicates (at least one), the pass parameters, g, the difference panels [T+H][N] and (x_draw) the backward
+ * messages.  Results do not depend on the slicing.  Outputs must not overlap the inputs. */
+int dfm_simsmooth_ar_batch_dev(dfm_handle* h, int B, int D, int T, int N, int r, int p, int q, int H, const double* panel,
+                               const double* Lam, const double* sig2, const double* rho, const double* Avar, const double* Q,
+                               const double* mu0, const double* P0, const double* v0, const double* mean, const double* sd,
+                               uint64_t seed, int64_t first_draw, double* f_draw, double* x_draw, unsigned flags);
+int dfm_simsmooth_ar_batch(dfm_handle* h, int B, int D, int T, int N, int r, int p, int q, int H, const double* panel,
+                           const double* Lam, const double* sig2, const double* rho, const double* Avar, const double* Q,
+                           const double* mu0, const double* P0, const double* v0, const double* mean, const double* sd,
+                           uint64_t seed, int64_t first_draw, double* f_draw, double* x_draw, unsigned flags);
+
 /* --- MIXED FREQUENCY: monthly factors, quarterly series (Mariano and Murasawa 2003; Banbura and Modugno 2014) ---------------
  *   x_it = lam_i' g_it + e_it,   g_it = sum_{l<L} w_il f_{t-l},   e_it ~ N(0, R_i),
  *   f_t  = A_1 f_{t-1} + .. + A_p f_{t-p} + eta_t,   eta_t ~ N(0, Q)

@@ -661,6 +661,35 @@ function forecast_ar(h::Handle, x::Matrix{Float64}, Lam::Matrix{Float64}, sig2::
             factor = permutedims(f), P = permutedims(P), loglik = ll[1])
 end
 
+"Joint posterior draws of the factor path and of the missing / future cells with AR(q) idiosyncratic terms
+(dfm_simsmooth_ar_batch; include/dfm_hip.h): arguments as forecast_ar; ndraws independent draws over rows q+1..T+H by the
+simulation smoother, a pure function of (seed, first_draw + draw index), with mean `forecast_ar`'s x and the joint covariance of
+its error (exact posterior draws when the only missing cells are ragged-edge and horizon cells).  Returns factor
+(ndraws x (T+H-q) x r) and x (ndraws x (T+H-q) x N: observed cells as given)."
+function draw_paths_ar(h::Handle, x::Matrix{Float64}, Lam::Matrix{Float64}, sig2::Vector{Float64}, rho::Matrix{Float64},
+                       Avar::Matrix{Float64}, Q::Matrix{Float64}, mu0::Vector{Float64}, P0::Matrix{Float64}, ndraws::Integer,
+                       H::Integer = 0; v0 = nothing, mean = nothing, sd = nothing, seed::Integer = 20160415,
+                       first_draw::Integer = 0, singular_q::Bool = false)
+    (mean === nothing) == (sd === nothing) || error("mean and sd go together")
+    T, N = size(x); r = size(Lam, 2); q = size(rho, 2); p = div(size(Avar, 2), r); n = T + H - q
+    panel = to_c_panel(x)
+    LamC = permutedims(Lam); rhoC = permutedims(rho); AC = permutedims(Avar); QC = permutedims(Q); P0C = permutedims(P0)
+    v0C = v0 === nothing ? C_NULL : Vector{Float64}(v0)
+    meanC = mean === nothing ? C_NULL : Vector{Float64}(mean); sdC = sd === nothing ? C_NULL : Vector{Float64}(sd)
+    f = Array{Float64}(undef, r, n, ndraws); xd = Array{Float64}(undef, N, n, ndraws)
+    flags = (any(isnan, x) ? DFM_F_MAY_HAVE_MISSING : Cuint(0)) | (singular_q ? DFM_F_SINGULAR_Q : Cuint(0))
+    GC.@preserve panel LamC sig2 rhoC AC QC mu0 P0C v0C meanC sdC f xd begin
+        rc = ccall((:dfm_simsmooth_ar_batch, LIB), Cint,
+                   (Ptr{Cvoid}, Cint, Cint, Cint, Cint, Cint, Cint, Cint, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                    Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                    Ptr{Float64}, UInt64, Int64, Ptr{Float64}, Ptr{Float64}, Cuint),
+                   h.ptr, 1, ndraws, T, N, r, p, q, H, panel, LamC, sig2, rhoC, AC, QC, mu0, P0C, v0C, meanC, sdC, UInt64(seed),
+                   Int64(first_draw), f, xd, flags)
+        check(h.ptr, rc)
+    end
+    return (factor = permutedims(f, (3, 2, 1)), x = permutedims(xd, (3, 2, 1)))
+end
+
 "Joint ECM estimation with AR(q) idiosyncratic terms (dfm_em_ar_batch; include/dfm_hip.h): the re-estimation of the
 reference's `lambda`, `uar_coef`, `uar_ser` (dfm_functions.ipynb:391-415) and factor VAR inside the parametric model.
 Arguments as ks_pass_ar (the start: what `estimate!(m)` left in the model).  Returns the updated parameters, the
