@@ -44,6 +44,8 @@ _FC_ARGS = [c_vp, c_int, c_int, c_int, c_int, c_int, c_int] + [c_vp] * 15 + [c_u
 _SS_ARGS = [c_vp] + [c_int] * 7 + [c_vp] * 9 + [ctypes.c_uint64, ctypes.c_int64, c_vp, c_vp, c_uint]
 _GB_ARGS = ([c_vp] + [c_int] * 5 + [c_vp] * 7 + [ctypes.c_double] * 6 + [c_vp] + [c_int] * 3
             + [ctypes.c_uint64, ctypes.c_int64] + [c_vp] * 5 + [c_uint])
+_GBAR_ARGS = ([c_vp] + [c_int] * 6 + [c_vp] * 8 + [ctypes.c_double] * 7 + [c_vp] + [c_int] * 3
+              + [ctypes.c_uint64, ctypes.c_int64] + [c_vp] * 6 + [c_uint])
 _NW_ARGS = [c_vp] + [c_int] * 5 + [c_vp] * 10 + [c_int] + [c_vp] * 6 + [c_uint]
 _IRF_ARGS = [c_vp] + [c_int] * 5 + [c_vp] * 9 + [c_uint]
 _SG_ARGS = ([c_vp] + [c_int] * 5 + [c_vp] * 7 + [c_int, c_vp, c_int, c_int, ctypes.c_uint64, ctypes.c_int64] + [c_vp] * 6
@@ -130,6 +132,8 @@ SYMBOLS = {
     "dfm_forecast_ar_batch": (c_int, _FCAR_ARGS),
     "dfm_simsmooth_ar_batch_dev": (c_int, _SSAR_ARGS),
     "dfm_simsmooth_ar_batch": (c_int, _SSAR_ARGS),
+    "dfm_gibbs_ar_batch_dev": (c_int, _GBAR_ARGS),
+    "dfm_gibbs_ar_batch": (c_int, _GBAR_ARGS),
     "dfm_ks_pass_mf_batch_dev": (c_int, _MFPASS_ARGS),
     "dfm_ks_pass_mf_batch": (c_int, _MFPASS_ARGS),
     "dfm_em_mf_batch_dev": (c_int, _MFEM_ARGS),

@@ -1104,7 +1104,7 @@ def estimate_bayesian(m: DFMModel, ndraws: int, *, chains: int = 4, burn: int = 
     if Lam.shape[0] != cols.size:
         raise ValueError("m.em_params does not match the model's series (was the model changed after estimate?)")
     if np.any(np.nan_to_num(np.asarray(m.uar_coef, dtype=np.float64)[cols]) != 0.0):
-        raise ValueError("estimate_bayesian has no AR idiosyncratic terms: the model carries uar_coef (estimate_ar_idio?)")
+        raise ValueError("estimate_bayesian has no AR idiosyncratic terms: the model carries uar_coef (estimate_bayesian_ar_idio?)")
     if z.shape[0] <= p:
         raise ValueError("the window is not longer than the number of factor lags")
     pr = bayes.check_prior(prior, r, p, chains)
@@ -2021,7 +2021,7 @@ def forecast_ar_idio(m: DFMModel, H: int, *, through: Optional[int] = None, ctx=
 
 
 def draw_paths_ar_idio(m: DFMModel, ndraws: int, H: int = 0, *, through: Optional[int] = None, seed: int = 20160415,
-                       first_draw: int = 0, quantiles=None, ctx=None) -> dict:
+                       first_draw: int = 0, quantiles=None, params=None, ctx=None) -> dict:
     """Joint draws of the factor path and of the panel's missing and future cells from the model with AR(n_uarlag) idiosyncratic
     terms: the counterpart of `forecast_ar_idio`, which gives the marginal moments only -- a fan chart of a series, the probability
     of an event over several cells.  The AR model's horizon errors are strongly correlated along time; the draws carry that.
@@ -2038,6 +2038,10 @@ def draw_paths_ar_idio(m: DFMModel, ndraws: int, H: int = 0, *, through: Optiona
       x_sd        [rows, cols] sample standard deviation of the draws (ndraws >= 2, else 0): 0 on observed cells, elsewhere the
                   companion of `forecast_ar_idio`'s x_sd that includes the cross-period covariance of the factor estimation error
       bands       [nq, rows, cols] pointwise nearest-rank quantiles of x (dfm_quantile_bands), with `quantiles`
+    `params` (default None: the model's own parameters): the `params` of `estimate_bayesian_ar_idio` -- dict(Lam, sig2, rho, Avar,
+    Q, mu0, P0) with S parameter sets on the first axis.  Every set is one replicate of the same dfm_simsmooth_ar_batch call with
+    `ndraws` draws each, and factor / x hold S x ndraws draws (set-major), so x_sd and bands carry the parameter uncertainty as
+    well.  The data units (c_i, mu_f) and v0 stay those of the model.
     `m` is not modified."""
     ndraws, H, first_draw = int(ndraws), int(H), int(first_draw)
     if ndraws < 1:
@@ -2064,12 +2068,26 @@ def draw_paths_ar_idio(m: DFMModel, ndraws: int, H: int = 0, *, through: Optiona
     v0 = np.nanvar(m.data[win][:, cols] - c_i - m.factor[win] @ inputs["Lam"].T, axis=0)
     mean = c_i + inputs["Lam"] @ mu_f
     x = inputs["x"]
+    names = ("Lam", "sig2", "rho", "Avar", "Q", "mu0", "P0")
+    S, sets = 1, [inputs[k][None] for k in names]
+    if params is not None:
+        lost = [k for k in names if k not in params]
+        if lost:
+            raise ValueError(f"params lacks {lost}")
+        sets = [np.ascontiguousarray(params[k], dtype=np.float64) for k in names]
+        S = sets[0].shape[0] if sets[0].ndim == 3 else 0
+        for k, a in zip(names, sets):
+            if S < 1 or a.shape != (S,) + inputs[k].shape:
+                raise ValueError(f"params[{k!r}] must be [S, ...] with the model's own shape {inputs[k].shape} behind S >= 1")
+        if qs is not None and S * ndraws > _QUANTILE_MAX_DRAWS:
+            raise ValueError(f"bands need S x ndraws <= {_QUANTILE_MAX_DRAWS}")
+    total = S * ndraws
+    rep = lambda a: np.ascontiguousarray(np.broadcast_to(a, (S,) + a.shape))
     from ._lib import DfmError
     ctx, own = _own(ctx)
     try:
-        args = (x[None], inputs["Lam"][None], inputs["sig2"][None], inputs["rho"][None], inputs["Avar"][None], inputs["Q"][None],
-                inputs["mu0"][None], inputs["P0"][None], ndraws, H)
-        kw = dict(v0=v0[None], seed=int(seed), first_draw=first_draw, mean=mean[None], sd=np.ones((1, cols.size)),
+        args = (rep(x), *sets, ndraws, H)
+        kw = dict(v0=rep(v0), seed=int(seed), first_draw=first_draw, mean=rep(mean), sd=np.ones((S, cols.size)),
                   may_have_missing=bool(np.isnan(x).any()))
         try:
             o = ctx.simsmooth_ar_batch_host(*args, **kw)
@@ -2077,20 +2095,107 @@ def draw_paths_ar_idio(m: DFMModel, ndraws: int, H: int = 0, *, through: Optiona
             if err.code != -5:
                 raise
             o = ctx.simsmooth_ar_batch_host(*args, singular_q=True, **kw)
-        xd = o["x"][0]
+        xd = o["x"].reshape((total,) + o["x"].shape[2:])
+        fd = o["f"].reshape((total,) + o["f"].shape[2:])
         xr = m.data[m.initperiod - 1 + q:through][:, cols]              # observed cells: the data itself, not mean + z
         obs = ~np.isnan(xr)
         xd[:, :xr.shape[0], :][:, obs] = xr[obs]
-        bands = None if qs is None else ctx.quantile_bands_host(xd.reshape(ndraws, -1), qs).reshape((qs.size,) + xd.shape[1:])
+        bands = None if qs is None else ctx.quantile_bands_host(xd.reshape(total, -1), qs).reshape((qs.size,) + xd.shape[1:])
     finally:
         if own:
             ctx.close()
-    x_sd = xd.std(axis=0, ddof=1) if ndraws > 1 else np.zeros(xd.shape[1:])
+    x_sd = xd.std(axis=0, ddof=1) if total > 1 else np.zeros(xd.shape[1:])
     x_sd[:xr.shape[0]][obs] = 0.0
-    out = dict(rows=np.arange(m.initperiod + q, through + H + 1), cols=cols, factor=o["f"][0] + mu_f, x=xd, x_sd=x_sd,
+    out = dict(rows=np.arange(m.initperiod + q, through + H + 1), cols=cols, factor=fd + mu_f, x=xd, x_sd=x_sd,
                mu_f=mu_f, inputs=dict(inputs, v0=v0, mean=mean))
     if bands is not None:
         out["quantiles"], out["bands"] = qs, bands
+    return out
+
+
+def estimate_bayesian_ar_idio(m: DFMModel, ndraws: int, *, chains: int = 4, burn: int = 500, thin: int = 1, prior=None,
+                              seed: int = 20160415, keep_factors: bool = False, quantiles=None, ctx=None) -> dict:
+    """Bayesian estimation of the model with AR(n_uarlag) idiosyncratic terms by the Gibbs sampler of include/dfm_hip.h
+    (dfm_gibbs_ar_batch), after `estimate(m, NonParametric())`, optionally followed by `estimate_ar_idio(m)`: `chains` independent
+    chains, all started at the parameters the model holds (`_ar_model_inputs`), run as one batch on the GPU on the window rows
+    initperiod..lastperiod.  Each chain runs `burn` sweeps and then keeps `ndraws` sweeps, one in `thin`.  `prior`: a dict that
+    overrides entries of bayes.default_prior_ar(r) (tau_lam, nu_R, s_R, tau_rho, tau_A, nu_Q, s_Q, A0).  mu0 and P0 stay at their
+    start values, and so does the series mean  mean_i = c_i + lam_i' mu_f  (c_i the intercept of the loading regression, mu_f the
+    factor VAR's mean): it is FIXED at the start values, the sampler draws deviations from it.  The series block conditions on the
+    first q output rows, the VAR block on the first p drawn rows; A is not truncated to the stationary region, rho_i is.
+    No rotation or scale normalisation is applied: rho, sig2, the common component and forecasts are identified, Lam, A and Q one
+    by one are not.  Returns a dict:
+      params        dict(Lam, sig2, rho, Avar, Q, mu0, P0), chains x ndraws flattened on the first axis (chain-major): hand it to
+                    `draw_paths_ar_idio(m, ..., params=out["params"])` for fan charts with parameter uncertainty
+      rows, cols    1-based periods initperiod + q .. lastperiod, column indices (0-based) of m.data
+      sig2_mean [N], rho_mean [N, q], persistence_mean [N] (sum_l rho_il), common_mean [rows, N] (mean_i + lam_i' f_t)
+      quantiles, sig2_bands [nq, N], persistence_bands [nq, N], common_bands [nq, rows, N]    with `quantiles`
+      rhat_sig2 [N], rhat_persistence [N], rhat_common [N]    split-R-hat across the chains (common: of the last period)
+      factor        [chains x ndraws, rows, r] (with the factor mean mu_f) with keep_factors
+      prior, chains, ndraws, mu_f
+    `m` is not modified."""
+    from . import bayes
+    ndraws, chains, burn, thin = int(ndraws), int(chains), int(burn), int(thin)
+    if ndraws < 1 or chains < 1 or burn < 0 or thin < 1:
+        raise ValueError("ndraws >= 1, chains >= 1, burn >= 0 and thin >= 1 are required")
+    q = int(m.n_uarlag)
+    if not (1 <= q <= 4):
+        raise ValueError("estimate_bayesian_ar_idio needs 1 <= n_uarlag <= 4")
+    if m.nfac_u > 8:
+        raise ValueError("estimate_bayesian_ar_idio needs nfac_u <= 8")
+    qs = None
+    if quantiles is not None:
+        qs = np.atleast_1d(np.asarray(quantiles, dtype=np.float64))
+        if qs.size < 1 or not np.all((qs > 0.0) & (qs <= 1.0)):
+            raise ValueError("quantiles must lie in (0, 1]")
+    inputs, cols, mu_f, c_i = _ar_model_inputs(m)
+    names = ("Lam", "sig2", "rho", "Avar", "Q", "mu0", "P0")
+    x = inputs["x"]
+    r = inputs["Lam"].shape[1]
+    p = inputs["Avar"].shape[1] // r
+    if x.shape[0] - q <= p:
+        raise ValueError("the window is not longer than n_uarlag plus the number of factor lags")
+    pr = bayes.check_prior_ar(prior, r, p, chains)
+    mean = c_i + inputs["Lam"] @ mu_f
+    n_sweeps = burn + (ndraws - 1) * thin + 1
+    from ._lib import DfmError
+    ctx, own = _own(ctx)
+    try:
+        rep = lambda a: np.ascontiguousarray(np.broadcast_to(a, (chains,) + a.shape))
+        args = (rep(x), *[rep(inputs[k]) for k in names], pr, n_sweeps)
+        kw = dict(burn=burn, thin=thin, seed=int(seed), keep=("Lam", "sig2", "rho", "A", "Q", "f"),
+                  may_have_missing=bool(np.isnan(x).any()))
+        try:
+            _, d = ctx.gibbs_ar_batch_host(*args, **kw)
+        except DfmError as err:                     # as estimate_bayesian: the covariance form, but not for the sampler's own failures
+            if err.code != -5 or "Gibbs sampler" in str(err):
+                raise
+            _, d = ctx.gibbs_ar_batch_host(*args, singular_q=True, **kw)
+    finally:
+        if own:
+            ctx.close()
+    flat = lambda a: a.reshape((chains * ndraws,) + a.shape[2:])
+    tile = lambda a: np.ascontiguousarray(np.broadcast_to(a, (chains * ndraws,) + a.shape))
+    params = dict(Lam=flat(d["Lam"]), sig2=flat(d["sig2"]), rho=flat(d["rho"]), Avar=flat(d["A"]), Q=flat(d["Q"]),
+                  mu0=tile(inputs["mu0"]), P0=tile(inputs["P0"]))
+    pers = d["rho"].sum(axis=3)                                         # [chains, ndraws, N]
+    last = bayes.common_component(d["Lam"], d["f"], mean, 1.0, rows=[d["f"].shape[2] - 1])[:, :, 0, :]
+    out = dict(params=params, rows=np.arange(m.initperiod + q, m.lastperiod + 1), cols=cols, sig2_mean=d["sig2"].mean(axis=(0, 1)),
+               rho_mean=d["rho"].mean(axis=(0, 1)), persistence_mean=pers.mean(axis=(0, 1)), rhat_sig2=bayes.split_rhat(d["sig2"]),
+               rhat_persistence=bayes.split_rhat(pers), rhat_common=bayes.split_rhat(last), prior=pr, chains=chains, ndraws=ndraws,
+               mu_f=mu_f)
+    if qs is None:
+        out["common_mean"] = np.mean([bayes.common_component(d["Lam"][c], d["f"][c], mean, 1.0).mean(axis=0) for c in range(chains)],
+                                     axis=0)
+    else:
+        cc = flat(bayes.common_component(d["Lam"], d["f"], mean, 1.0))
+        out["common_mean"] = cc.mean(axis=0)
+        out["quantiles"] = qs
+        out["sig2_bands"] = np.quantile(flat(d["sig2"]), qs, axis=0)
+        out["persistence_bands"] = np.quantile(flat(pers), qs, axis=0)
+        out["common_bands"] = np.quantile(cc, qs, axis=0)
+    if keep_factors:
+        out["factor"] = flat(d["f"]) + mu_f
     return out
 
 

@@ -37,6 +37,25 @@ def check_prior(prior, r: int, p: int, chains: int) -> dict:
     return pr
 
 
+def default_prior_ar(r: int) -> dict:
+    """default_prior plus rho_i ~ N(0, I / tau_rho) truncated to the stationary region, tau_rho = 4 (sd 0.5 per coefficient): a
+    prior-only series is then stationary with probability 0.96 / 0.82 / 0.65 / 0.49 for q = 1 .. 4, so the sampler's 32 attempts
+    fail with probability <= 6e-10; tau_rho = 1 at q = 4 gives 0.09 and does reach the cap."""
+    return dict(default_prior(r), tau_rho=4.0)
+
+
+def check_prior_ar(prior, r: int, p: int, chains: int) -> dict:
+    """check_prior for the model with AR idiosyncratic terms (api.estimate_bayesian_ar_idio): default_prior_ar, and tau_rho > 0."""
+    pr = dict(prior or {})
+    unknown = set(pr) - set(PRIOR_KEYS) - {"tau_rho"}
+    if unknown:
+        raise ValueError(f"unknown prior entries: {sorted(unknown)}")
+    tau_rho = pr.pop("tau_rho", default_prior_ar(r)["tau_rho"])
+    if not tau_rho > 0:
+        raise ValueError("prior: tau_rho must be > 0")
+    return dict(check_prior(pr, r, p, chains), tau_rho=float(tau_rho))
+
+
 def split_rhat(x: np.ndarray) -> np.ndarray:
     """Split-R-hat of Gelman et al. (2013) for draws x [chains, K, ...]: every chain is cut into two halves, and the pooled
     variance estimate of the 2 chains sequences is compared with their mean within-sequence variance.  NaN with fewer than 4

@@ -170,6 +170,7 @@ struct dfm_handle {
     DevBlock ft;                           // dfm_filter_batch_dev: the padded loadings, the collapse's per-period arrays, the moments the
                                            // caller does not take and the evaluation's running sums
     DevBlock gb;                           // dfm_gibbs_batch_dev: the sweep's factor path and the shared Gram roots of balanced panels
+                                           // dfm_gibbs_ar_batch_dev: the sweep's [B][T - q][r] factor path
     std::vector<int> sv_idx;               // host copy of named / cum while their upload is in flight
     std::vector<double> sv_z;              // dfm_proxyirf_batch_dev: host copy of the instrument while its upload is in flight
     const double* odd_panel_src = nullptr; int odd_panel_dims[3] = {0, 0, 0};   // the panel whose padded copy h->odd holds (odd_pad keep_panel)
@@ -183,11 +184,11 @@ struct dfm_handle {
 };
 
 enum KernelId { K_COLLAPSE = 0, K_RECURSION, K_MSTEP_STATS, K_MSTEP_SOLVE, K_PCA, K_SYNTH, K_PAD,
-                K_COLLAPSE_DMA, K_GRAM, K_COV, K_MEANSCAN, K_PFILL, K_COLLAPSE_MFMA, K_ALS, K_OLS, K_BOOT, K_QUANT, K_COLLAPSE_WIDE, K_EM_UPDATE, K_CHOW, K_MSTEP_MFMA, K_GRAM_XX, K_PASS_FUSED, K_FC_TAIL, K_FC_FILL, K_FC_PAD, K_SS_PREP, K_SS_EXPAND, K_SS_PATH, K_SS_DIFF, K_SS_FINISH, K_SS_FILL, K_NW_REVISE, K_NW_GATHER, K_NW_GAMMA, K_NW_COV, K_NW_IMPACT, K_MF_TABLE, K_MF_MOMENTS, K_MF_SOLVE, K_SV_PREP, K_SV_IRF_FILL, K_SV_SHOCK, K_SV_PATH, K_SV_HD_FILL, K_FT_FILTER, K_FT_FILL, K_FT_EVAL, K_GB_GRAM, K_GB_LOAD, K_GB_VAR, K_SV_SIGN_TABLE, K_SV_SIGN, K_SV_SIGN_KEEP, K_PX_ROWS, K_PX_MOMENT, K_PX_SLOT_TABLE, K_PX_DEN, K_PX_FILL, K_PX_SHOCK, K_MF_SOLVE_BLOCKS, K_FCAR_BACK, K_FCAR_FWD, K_SSAR_PARAMS, K_SSAR_EXPAND, K_SSAR_DIFF, K_SSAR_FWD, K_SSAR_FINISH, K_COUNT };
+                K_COLLAPSE_DMA, K_GRAM, K_COV, K_MEANSCAN, K_PFILL, K_COLLAPSE_MFMA, K_ALS, K_OLS, K_BOOT, K_QUANT, K_COLLAPSE_WIDE, K_EM_UPDATE, K_CHOW, K_MSTEP_MFMA, K_GRAM_XX, K_PASS_FUSED, K_FC_TAIL, K_FC_FILL, K_FC_PAD, K_SS_PREP, K_SS_EXPAND, K_SS_PATH, K_SS_DIFF, K_SS_FINISH, K_SS_FILL, K_NW_REVISE, K_NW_GATHER, K_NW_GAMMA, K_NW_COV, K_NW_IMPACT, K_MF_TABLE, K_MF_MOMENTS, K_MF_SOLVE, K_SV_PREP, K_SV_IRF_FILL, K_SV_SHOCK, K_SV_PATH, K_SV_HD_FILL, K_FT_FILTER, K_FT_FILL, K_FT_EVAL, K_GB_GRAM, K_GB_LOAD, K_GB_VAR, K_SV_SIGN_TABLE, K_SV_SIGN, K_SV_SIGN_KEEP, K_PX_ROWS, K_PX_MOMENT, K_PX_SLOT_TABLE, K_PX_DEN, K_PX_FILL, K_PX_SHOCK, K_MF_SOLVE_BLOCKS, K_FCAR_BACK, K_FCAR_FWD, K_SSAR_PARAMS, K_SSAR_EXPAND, K_SSAR_DIFF, K_SSAR_FWD, K_SSAR_FINISH, K_GB_AR_SERIES, K_COUNT };
 static const char* const kKernelNames[K_COUNT] = {"collapse_kernel", "recursion_kernel", "mstep_lam_kernel",
                                                   "mstep_solve_kernel", "pca_kernel", "synth_kernel",
                                                   "pad_params_kernel", "collapse_dma_kernel", "gram_kernel",
-                                                  "cov_kernel", "meanscan_kernel", "pfill_kernel", "collapse_mfma_kernel", "als_kernel", "ols_kernel", "var_boot_kernel", "quantile_kernel", "collapse_wide_kernel", "em_update_kernel", "chow_kernel", "mstep_mfma_kernel", "gram_xx_kernel", "pass_fused_kernel", "forecast_tail_kernel", "forecast_fill_kernel", "forecast_pad_kernel", "simsmooth_prep_kernel", "simsmooth_expand_kernel", "simsmooth_path_kernel", "simsmooth_diff_kernel", "simsmooth_finish_kernel", "simsmooth_fill_kernel", "news_revise_kernel", "news_gather_kernel", "news_gamma_kernel", "news_cov_panel_kernel", "news_impact_kernel", "mf_table_kernel", "mf_moments_kernel", "mf_solve_kernel", "sv_prep_kernel", "sv_irf_fill_kernel", "sv_shock_kernel", "sv_path_kernel", "sv_hd_fill_kernel", "filter_kernel", "filter_fill_kernel", "filter_eval_kernel", "gibbs_gram_kernel", "gibbs_load_kernel", "gibbs_var_kernel", "sv_sign_table_kernel", "sv_sign_kernel", "sv_sign_keep_kernel", "px_rows_kernel", "px_moment_kernel", "px_slot_table_kernel", "px_den_kernel", "px_fill_kernel", "px_shock_kernel", "mf_solve_blocks_kernel", "forecast_ar_back_kernel", "forecast_ar_fwd_kernel", "simsmooth_ar_params_kernel", "simsmooth_ar_expand_kernel", "simsmooth_ar_diff_kernel", "simsmooth_ar_fwd_kernel", "simsmooth_ar_finish_kernel"};
+                                                  "cov_kernel", "meanscan_kernel", "pfill_kernel", "collapse_mfma_kernel", "als_kernel", "ols_kernel", "var_boot_kernel", "quantile_kernel", "collapse_wide_kernel", "em_update_kernel", "chow_kernel", "mstep_mfma_kernel", "gram_xx_kernel", "pass_fused_kernel", "forecast_tail_kernel", "forecast_fill_kernel", "forecast_pad_kernel", "simsmooth_prep_kernel", "simsmooth_expand_kernel", "simsmooth_path_kernel", "simsmooth_diff_kernel", "simsmooth_finish_kernel", "simsmooth_fill_kernel", "news_revise_kernel", "news_gather_kernel", "news_gamma_kernel", "news_cov_panel_kernel", "news_impact_kernel", "mf_table_kernel", "mf_moments_kernel", "mf_solve_kernel", "sv_prep_kernel", "sv_irf_fill_kernel", "sv_shock_kernel", "sv_path_kernel", "sv_hd_fill_kernel", "filter_kernel", "filter_fill_kernel", "filter_eval_kernel", "gibbs_gram_kernel", "gibbs_load_kernel", "gibbs_var_kernel", "sv_sign_table_kernel", "sv_sign_kernel", "sv_sign_keep_kernel", "px_rows_kernel", "px_moment_kernel", "px_slot_table_kernel", "px_den_kernel", "px_fill_kernel", "px_shock_kernel", "mf_solve_blocks_kernel", "forecast_ar_back_kernel", "forecast_ar_fwd_kernel", "simsmooth_ar_params_kernel", "simsmooth_ar_expand_kernel", "simsmooth_ar_diff_kernel", "simsmooth_ar_fwd_kernel", "simsmooth_ar_finish_kernel", "gibbs_ar_series_kernel"};
 
 namespace dfm { int handle_device(const dfm_handle* h) { return h->device; } }   // (probe.hip)
 
@@ -1808,7 +1809,7 @@ static int status_check(dfm_handle* h) {
     if (st & 1) return fail(h, DFM_E_MISSING, "panel contains NaN but DFM_F_MAY_HAVE_MISSING was not set%s");
     if (st & 16) return fail(h, DFM_E_NUMERIC, "structural identification: Lam[named, :] is singular, or Q is not positive definite where S^-1 is needed%s");
     if (st & 32) return fail(h, DFM_E_NUMERIC, "filter: a replicate's update met a non-finite value or a matrix that is not positive semi-definite (NaN from that period on)%s");
-    if (st & 64) return fail(h, DFM_E_NUMERIC, "Gibbs sampler: a Cholesky factorisation failed or a Gamma draw was rejected 32 times%s");
+    if (st & 64) return fail(h, DFM_E_NUMERIC, "Gibbs sampler: a Cholesky factorisation failed, or a Gamma draw or a stationary rho draw was rejected 32 times%s");
     if (st & 2) return fail(h, DFM_E_NUMERIC, "PCA subspace iteration did not converge (near-degenerate spectrum at the cut)%s");
     return 0;
 }
@@ -2926,6 +2927,105 @@ int dfm_gibbs_batch(dfm_handle* h, int B, int T, int N, int r, int p, const doub
     if (int rc = st.begin()) return rc;
     int rc = st.finish(dfm_gibbs_batch_dev(h, B, T, N, r, p, x_d, mu_d, P0_d, lam_d, R_d, A_d, Q_d, tau_lam, nu_R, s_R, tau_A, nu_Q, s_Q,
                                            A0_d, n_sweeps, burn, thin, seed, first_sweep, ld_d, rd_d, ad_d, qd_d, fd_d, flags));
+    if (rc == 0) rc = status_check(h);
+    return rc;
+}
+
+
+// ---- Bayesian estimation with AR idiosyncratic terms (gibbs_ar.hip) -----------------------------------------------------------
+// Sweep j: the factor path of every chain by dfm_simsmooth_ar_batch_dev (D = 1, H = 0, v0 / mean / sd / x_draw NULL, first_draw =
+// first_sweep + j) into h->gb, then rho_i, sig2_i, lam_i | f (gibbs_ar_series_kernel) and A, Q | f (gibbs_var_kernel on the n = T - q
+// rows of the path) in place in the caller's state.  Nothing waits between the sweeps; kept sweeps are copied behind the sweep.
+static int gibbs_ar_check(dfm_handle* h, int B, int T, int N, int r, int p, int q, const double* panel, const double* mu0,
+                          const double* P0, const double* Lam, const double* sig2, const double* rho, const double* Avar,
+                          const double* Q, double tau_lam, double nu_R, double s_R, double tau_rho, double tau_A, double nu_Q,
+                          double s_Q, int n_sweeps, int burn, int thin) {
+    if (int rc = check_dims(h, B, T, N, r)) return rc;
+    if (p < 1) return fail(h, DFM_E_DIMS, "number of factor lags must be >= 1%s");
+    if (q < 1) return fail(h, DFM_E_DIMS, "number of idiosyncratic lags must be >= 1 (q = 0 is dfm_gibbs_batch)%s");
+    if (n_sweeps < 1 || thin < 1 || burn < 0) return fail(h, DFM_E_DIMS, "n_sweeps >= 1, thin >= 1 and burn >= 0 are required%s");
+    if (!(tau_lam > 0.0) || !(nu_R >= 2.0) || !(s_R > 0.0) || !(tau_rho > 0.0) || !(tau_A > 0.0) || !(nu_Q >= (double)r + 1.0) ||
+        !(s_Q > 0.0))
+        return fail(h, DFM_E_DIMS, "prior: tau_lam, s_R, tau_rho, tau_A, s_Q > 0, nu_R >= 2 and nu_Q >= r + 1 are required%s");
+    const int m = p > q + 1 ? p : q + 1;
+    if (q > 4 || r > 8 || (long long)r * m > DFM_MAX_R)
+        return fail(h, DFM_E_R_UNSUPPORTED, "the Gibbs sampler with AR idiosyncratic terms needs q <= 4, r <= 8 and r max(p, q + 1) <= 32%s");
+    if ((long long)T - q <= p) return fail(h, DFM_E_DIMS, "T - q must be > p (the VAR block conditions on the first p drawn rows)%s");
+    if (!panel || !mu0 || !P0 || !Lam || !sig2 || !rho || !Avar || !Q) return fail(h, DFM_E_NULL, "required pointer is NULL%s");
+    return 0;
+}
+
+int dfm_gibbs_ar_batch_dev(dfm_handle* h, int B, int T, int N, int r, int p, int q, const double* panel, const double* mu0,
+                           const double* P0, double* Lam, double* sig2, double* rho, double* Avar, double* Q, double tau_lam,
+                           double nu_R, double s_R, double tau_rho, double tau_A, double nu_Q, double s_Q, const double* A0,
+                           int n_sweeps, int burn, int thin, uint64_t seed, int64_t first_sweep, double* Lam_draw,
+                           double* sig2_draw, double* rho_draw, double* A_draw, double* Q_draw, double* f_draw, unsigned flags) {
+    if (int rc = gibbs_ar_check(h, B, T, N, r, p, q, panel, mu0, P0, Lam, sig2, rho, Avar, Q, tau_lam, nu_R, s_R, tau_rho, tau_A, nu_Q,
+                                s_Q, n_sweeps, burn, thin)) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t d = sizeof(double), k = (size_t)r * p, n = (size_t)T - q;
+    HIP_TRY(h, h->gb.grow((size_t)B * n * r * d));
+    double* f = at<double>(h->gb, 0);
+    GbArArgs sa{};
+    sa.B = B; sa.n = (int)n; sa.N = N; sa.r = r; sa.q = q;
+    sa.panel = panel; sa.f = f; sa.Lam = Lam; sa.sig2 = sig2; sa.rho = rho;
+    sa.tau_lam = tau_lam; sa.nu_R = nu_R; sa.s_R = s_R; sa.tau_rho = tau_rho; sa.seed = seed; sa.status = h->status_dev;
+    GbArgs a{};                                             // gibbs_var_kernel on the path's n rows
+    a.B = B; a.T = (int)n; a.N = N; a.r = r; a.p = p;
+    a.f = f; a.A = Avar; a.Q = Q; a.A0 = A0; a.tau_A = tau_A; a.nu_Q = nu_Q; a.s_Q = s_Q; a.seed = seed; a.status = h->status_dev;
+    const size_t K = (size_t)gibbs_kept(n_sweeps, burn, thin);
+    auto keep = [&](double* dst, const double* src, size_t per, size_t kk) {   // dst [B][K][per] <- src [B][per]
+        return dst ? hipMemcpy2DAsync(dst + kk * per, K * per * d, src, per * d, per * d, (size_t)B, hipMemcpyDeviceToDevice, h->stream)
+                   : hipSuccess;
+    };
+    for (int j = 0; j < n_sweeps; ++j) {
+        a.sweep = sa.sweep = first_sweep + j;
+        if (int rc = dfm_simsmooth_ar_batch_dev(h, B, 1, T, N, r, p, q, 0, panel, Lam, sig2, rho, Avar, Q, mu0, P0, nullptr, nullptr,
+                                                nullptr, seed, a.sweep, f, nullptr, flags)) return rc;
+        {
+            ProfScope ps(h, K_GB_AR_SERIES);
+            HIP_TRY(h, launch_gibbs_ar_series(sa, h->stream));
+        }
+        {
+            ProfScope ps(h, K_GB_VAR);
+            HIP_TRY(h, launch_gibbs_var(a, h->stream));
+        }
+        if (j >= burn && (j - burn) % thin == 0) {
+            const size_t kk = (size_t)(j - burn) / thin;
+            HIP_TRY(h, keep(Lam_draw, Lam, (size_t)N * r, kk));
+            HIP_TRY(h, keep(sig2_draw, sig2, (size_t)N, kk));
+            HIP_TRY(h, keep(rho_draw, rho, (size_t)N * q, kk));
+            HIP_TRY(h, keep(A_draw, Avar, (size_t)r * k, kk));
+            HIP_TRY(h, keep(Q_draw, Q, (size_t)r * r, kk));
+            HIP_TRY(h, keep(f_draw, f, n * r, kk));
+        }
+    }
+    return 0;
+}
+
+int dfm_gibbs_ar_batch(dfm_handle* h, int B, int T, int N, int r, int p, int q, const double* panel, const double* mu0,
+                       const double* P0, double* Lam, double* sig2, double* rho, double* Avar, double* Q, double tau_lam, double nu_R,
+                       double s_R, double tau_rho, double tau_A, double nu_Q, double s_Q, const double* A0, int n_sweeps, int burn,
+                       int thin, uint64_t seed, int64_t first_sweep, double* Lam_draw, double* sig2_draw, double* rho_draw,
+                       double* A_draw, double* Q_draw, double* f_draw, unsigned flags) {
+    if (int rc = gibbs_ar_check(h, B, T, N, r, p, q, panel, mu0, P0, Lam, sig2, rho, Avar, Q, tau_lam, nu_R, s_R, tau_rho, tau_A, nu_Q,
+                                s_Q, n_sweeps, burn, thin)) return rc;
+    if (int rc = status_epoch(h)) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t m = (size_t)(p > q + 1 ? p : q + 1), km = (size_t)r * m, k = (size_t)r * p, n = (size_t)T - q,
+                 BK = (size_t)B * gibbs_kept(n_sweeps, burn, thin);
+    HostStage st(h, 256);
+    double *x_d, *mu_d, *P0_d, *lam_d, *s2_d, *rho_d, *A_d, *Q_d, *A0_d, *ld_d, *sd_d, *rd_d, *ad_d, *qd_d, *fd_d;
+    st.in(panel, (size_t)B * T * N, x_d); st.in(mu0, (size_t)B * km, mu_d); st.in(P0, (size_t)B * km * km, P0_d);
+    st.inout(Lam, (size_t)B * N * r, lam_d); st.inout(sig2, (size_t)B * N, s2_d); st.inout(rho, (size_t)B * N * q, rho_d);
+    st.inout(Avar, (size_t)B * r * k, A_d); st.inout(Q, (size_t)B * r * r, Q_d); st.in(A0, A0 ? (size_t)B * r * k : 0, A0_d);
+    st.out(Lam_draw, Lam_draw ? BK * N * r : 0, ld_d); st.out(sig2_draw, sig2_draw ? BK * N : 0, sd_d);
+    st.out(rho_draw, rho_draw ? BK * N * q : 0, rd_d); st.out(A_draw, A_draw ? BK * r * k : 0, ad_d);
+    st.out(Q_draw, Q_draw ? BK * r * r : 0, qd_d); st.out(f_draw, f_draw ? BK * n * r : 0, fd_d);
+    if (int rc = st.begin()) return rc;
+    int rc = st.finish(dfm_gibbs_ar_batch_dev(h, B, T, N, r, p, q, x_d, mu_d, P0_d, lam_d, s2_d, rho_d, A_d, Q_d, tau_lam, nu_R, s_R, tau_rho,
+                                              tau_A, nu_Q, s_Q, A0_d, n_sweeps, burn, thin, seed, first_sweep, ld_d, sd_d, rd_d, ad_d, qd_d,
+                                              fd_d, flags));
     if (rc == 0) rc = status_check(h);
     return rc;
 }

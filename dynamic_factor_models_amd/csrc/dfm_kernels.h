@@ -724,6 +724,20 @@ hipError_t launch_gibbs_gram(const GbArgs& a, hipStream_t s);
 hipError_t launch_gibbs_load(const GbArgs& a, hipStream_t s);
 hipError_t launch_gibbs_var(const GbArgs& a, hipStream_t s);
 
+// The series block "rho_i, sig2_i, lam_i | factor path" of one sweep of dfm_gibbs_ar_batch (gibbs_ar.hip); chain b of B.  Output
+// row t = 0 .. n-1 is panel row t + q; the first q panel rows are never read here.
+struct GbArArgs {
+    int B, n, N, r, q;
+    const double* panel;                          // [B][n + q][N] (NaN = missing)
+    const double* f;                              // [B][n][r]: the sweep's factor path
+    double* Lam; double* sig2; double* rho;       // [B][N][r], [B][N], [B][N][q]: read on entry, written in place
+    double tau_lam, nu_R, s_R, tau_rho;
+    uint64_t seed; int64_t sweep;
+    int* status;                                  // bit 64: a Cholesky failed, the gamma sampler or the rho sampler ran into its cap
+    CellGeom geo;                                 // geometry (set by the launcher)
+};
+hipError_t launch_gibbs_ar_series(const GbArArgs& a, hipStream_t s);
+
 // Device-side synthetic replicates (synth.hip); all arrays in the caller's layout (r).
 struct SynthArgs {
     int B, T, N, r;

@@ -10,41 +10,14 @@
 // Gamma(a, 1), a >= 1, is Marsaglia and Tsang (2000): attempt k of item i of n uses counter m = k n + i -- z = first normal of
 // normal2(2 m), u = uniform1(2 m + 1); 32 rejected attempts raise the status bit.  No floating-point atomics: every sum runs over
 // t in one fixed order, so two runs agree bit for bit.
-#include "dfm_kernels.h"
-#include "dfm_philox.h"
+#include "dfm_gibbs.h"
 #include "dfm_smallmat.h"
 
 namespace dfm {
 
-constexpr int kGbFailBit = 64;                // status word: a Cholesky failed or the gamma sampler ran into its cap
 constexpr int kGbTC = 64;                     // gibbs_load_kernel / gibbs_gram_kernel: f rows staged per chunk
 constexpr int kGbVarTC = 32;                  // gibbs_var_kernel: rows per chunk (behind the p lag rows)
-constexpr int kGbGammaCap = 32;               // attempts of one Gamma draw
 constexpr int kGbThreads = 256;
-enum : uint64_t { kGbLamN = 5, kGbRGam = 6, kGbVarE = 7, kGbBartN = 8, kGbBartG = 9 };
-
-__device__ __forceinline__ uint64_t gb_key(uint64_t seed, int64_t sweep) {
-    return seed ^ (0x9E3779B97F4A7C15ull * (uint64_t)(sweep + 1));
-}
-__device__ __forceinline__ double gb_uniform1(uint64_t key, uint64_t stream, uint64_t idx) {
-    uint32_t o[4];
-    Philox::block(key, idx, stream, o);
-    return u01(o[0], o[1]);
-}
-// Gamma(a, 1), a >= 1; item `item` of n_items on stream word `word`
-__device__ __forceinline__ double gb_gamma(uint64_t key, uint64_t word, int item, int n_items, double a, bool& capped) {
-    const double d = a - 1.0 / 3.0, c = 1.0 / sqrt(9.0 * d);
-    for (int k = 0; k < kGbGammaCap; ++k) {
-        const uint64_t m = (uint64_t)k * (uint64_t)n_items + (uint64_t)item;
-        double z, z1;
-        normal2(key, word, 2 * m, z, z1);
-        const double u = gb_uniform1(key, word, 2 * m + 1);
-        const double t = 1.0 + c * z, v = t * t * t;
-        if (v > 0.0 && log(u) < 0.5 * z * z + d - d * v + d * log(v)) return d * v;
-    }
-    capped = true;
-    return d;
-}
 
 // One workgroup per chain: L L' = tau_lam I + F'F over all T rows (what every series of a balanced panel shares).
 __global__ __launch_bounds__(kGbThreads) void gibbs_gram_kernel(GbArgs a) {

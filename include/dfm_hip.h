@@ -666,6 +666,57 @@ int dfm_simsmooth_ar_batch(dfm_handle* h, int B, int D, int T, int N, int r, int
                            const double* mu0, const double* P0, const double* v0, const double* mean, const double* sd,
                            uint64_t seed, int64_t first_draw, double* f_draw, double* x_draw, unsigned flags);
 
+/* Bayesian estimation of the same model: a batched Gibbs sampler (csrc/gibbs_ar.hip), what dfm_gibbs_batch is to dfm_simsmooth_batch,
+ * for dfm_simsmooth_ar_batch.  B independent chains; shapes, flags and m = max(p, q + 1) as dfm_ks_pass_ar_batch.  mu0 [B][r m] and
+ * P0 [B][r m][r m] are inputs and stay fixed.  The chain state is Lam [B][N][r], sig2 [B][N], rho [B][N][q], Avar [B][r][r p],
+ * Q [B][r][r]: the start on entry, the state after the last sweep on return.
+ * Priors (scalars per call, except A0 [B][r][r p], NULL = 0): lam_i | sig2_i ~ N(0, sig2_i / tau_lam I); sig2_i ~ IG(nu_R / 2,
+ * nu_R s_R / 2); rho_i ~ N(0, I / tau_rho) truncated to the stationary region (NOT scaled by sig2_i); vec(A') | Q ~ N(vec(A0'),
+ * Q (x) I / tau_A); Q ~ IW(s_Q I, nu_Q).  tau_lam, s_R, tau_rho, tau_A, s_Q > 0, nu_R >= 2, nu_Q >= r + 1.
+ * Sweep j = 0 .. n_sweeps-1 of chain b, key = seed ^ (0x9E3779B97F4A7C15 * (first_sweep + j + 1)), stream word 16 b + s.  Rows are
+ * the n = T - q output rows (panel rows q .. T-1): X_t, F_t.  U_i = { t : q <= t < n, cells t, t-1, .. t-q of series i all observed }
+ * (the AR pass's convention applied to the output rows), n_i = |U_i|.
+ *   1. F = f_draw of dfm_simsmooth_ar_batch_dev with D = 1, H = 0, v0 / mean / sd / x_draw NULL, first_draw = first_sweep + j
+ *      (streams 1, 2, 3, 5).
+ *   2. rho_i | lam_i, sig2_i, F:  e_t = X_ti - lam_i' F_t, w_t = (e_t-1, .., e_t-q);  S = tau_rho I + sum_{U_i} w w' / sig2_i = L L',
+ *      y = L^-1 sum_{U_i} w e_t / sig2_i.  A candidate is L^-T (y + n), n = q normals of stream 11: attempt k = 0, 1, .. of series i
+ *      uses idx = (k N + i) ceil(q / 2) + l / 2, component l mod 2.  The first stationary candidate is the draw.  Stationarity is
+ *      the step-down (Levinson) recursion: for k = q .. 1, kappa = phi_k; not stationary unless |kappa| < 1; then phi_j <-
+ *      (phi_j + kappa phi_{k-j}) / (1 - kappa^2) for j < k.  32 rejected attempts raise a status bit (DFM_E_NUMERIC) and leave
+ *      rho_i as it was.
+ *   3. (sig2_i, lam_i) | rho_i, F with the new rho_i:  x~_t = X_t - sum_l rho_il X_t-l, f~_t = F_t - sum_l rho_il F_t-l over U_i;
+ *      S = tau_lam I + sum f~ f~' = L L', y = L^-1 sum f~ x~;  sig2_i = (nu_R s_R + sum x~^2 - y'y) / 2 / g, g ~ Gamma((nu_R + n_i) / 2, 1)
+ *      from stream 6 (item i of N);  lam_i = L^-T (y + sqrt(sig2_i) n), n = r normals of stream 10: idx = i ceil(r / 2) + k / 2,
+ *      component k mod 2.  n_i = 0 gives the priors, in step 2 as well.
+ *   4. A, Q | F: step 3 of dfm_gibbs_batch on the n rows of F (streams 7, 8, 9); it conditions on the first p drawn rows.
+ * Stream 5 is NOT reused for the loadings: dfm_simsmooth_ar_batch spends it on the pre-sample terms with overlapping indices.
+ * Gamma draws, their cap and the Cholesky rule (a pivot <= 1e-12 trace fails) as dfm_gibbs_batch: a failed block leaves its own
+ * part of the series' state unchanged (rho_i; or lam_i and sig2_i; or A and Q) and raises the bit.
+ * Approximations.  Steps 2-3 condition on the first q output rows of each series, as step 4 and dfm_gibbs_batch's VAR block
+ * condition on the first p: the path step uses those q quasi-differences, the series step does not.  No stationarity truncation is
+ * applied to A.  Lam, A and Q are not identified (no rotation or scale normalisation); rho, sig2, the common component and
+ * forecasts are.  Interior gaps carry the pass's quasi-differencing convention (see dfm_simsmooth_ar_batch).
+ * Sweep j is kept when j >= burn and (j - burn) % thin == 0; K kept sweeps go to Lam_draw [B][K][N][r], sig2_draw [B][K][N],
+ * rho_draw [B][K][N][q], A_draw [B][K][r][r p], Q_draw [B][K][r][r], f_draw [B][K][n][r] (each may be NULL).  A call of n sweeps
+ * with first_sweep = k from the state k sweeps left equals the tail of one call of k + n sweeps bit for bit, and two runs agree
+ * bit for bit (no atomics on floating point; every sum runs over t in ascending order).
+ * Status: n_sweeps < 1, thin < 1, burn < 0, q < 1, T - q <= p or a prior outside its condition: DFM_E_DIMS; q > 4, r > 8 or
+ * r m > 32: DFM_E_R_UNSUPPORTED (the limits of dfm_em_ar_batch); a NULL panel, mu0, P0 or state: DFM_E_NULL; a NaN panel without
+ * DFM_F_MAY_HAVE_MISSING: DFM_E_MISSING; a failed Cholesky, the Gamma cap or the rho cap: DFM_E_NUMERIC (status-word bits: the host
+ * entry reports them, dfm_check_status after the "_dev" entry).  The sweeps are enqueued on the handle's stream without a wait
+ * between them.  Allocates in the handle (kept for the next call): one [B][n][r] factor path, beside what
+ * dfm_simsmooth_ar_batch_dev keeps. */
+int dfm_gibbs_ar_batch_dev(dfm_handle* h, int B, int T, int N, int r, int p, int q, const double* panel, const double* mu0,
+                           const double* P0, double* Lam, double* sig2, double* rho, double* Avar, double* Q, double tau_lam,
+                           double nu_R, double s_R, double tau_rho, double tau_A, double nu_Q, double s_Q, const double* A0,
+                           int n_sweeps, int burn, int thin, uint64_t seed, int64_t first_sweep, double* Lam_draw,
+                           double* sig2_draw, double* rho_draw, double* A_draw, double* Q_draw, double* f_draw, unsigned flags);
+int dfm_gibbs_ar_batch(dfm_handle* h, int B, int T, int N, int r, int p, int q, const double* panel, const double* mu0,
+                       const double* P0, double* Lam, double* sig2, double* rho, double* Avar, double* Q, double tau_lam,
+                       double nu_R, double s_R, double tau_rho, double tau_A, double nu_Q, double s_Q, const double* A0,
+                       int n_sweeps, int burn, int thin, uint64_t seed, int64_t first_sweep, double* Lam_draw,
+                       double* sig2_draw, double* rho_draw, double* A_draw, double* Q_draw, double* f_draw, unsigned flags);
+
 /* --- MIXED FREQUENCY: monthly factors, quarterly series (Mariano and Murasawa 2003; Banbura and Modugno 2014) ---------------
  *   x_it = lam_i' g_it + e_it,   g_it = sum_{l<L} w_il f_{t-l},   e_it ~ N(0, R_i),
  *   f_t  = A_1 f_{t-1} + .. + A_p f_{t-p} + eta_t,   eta_t ~ N(0, Q)

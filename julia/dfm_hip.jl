@@ -579,6 +579,43 @@ function estimate_bayesian(h::Handle, z::Matrix{Float64}, params, ndraws::Intege
             factor = flat(fd, (4, 3, 2, 1)))
 end
 
+"Bayesian estimation of the model with AR(q) idiosyncratic terms by its Gibbs sampler (dfm_gibbs_ar_batch; include/dfm_hip.h):
+z is T x N (NaN = missing, in deviations from the series means), params has Lam (N x r), sig2 (N), rho (N x q), Avar (r x r nlag),
+Q, mu0 (r m) and P0 (r m x r m), m = max(nlag, q + 1), as the AR pass takes them.  `chains` chains start at params, run `burn`
+sweeps and keep `ndraws` sweeps each, one in `thin`.  prior = (tau_lam, nu_R, s_R, tau_rho, tau_A, nu_Q, s_Q) with A0 or nothing.
+Returns the kept draws with chains x ndraws on the first axis (chain-major): Lam, sig2, rho (. x N x q), A, Q and factor
+(. x T - q x r).  rho, sig2, the common component and forecasts are identified; Lam, A and Q one by one are not."
+function estimate_bayesian_ar(h::Handle, z::Matrix{Float64}, params, ndraws::Integer; nlag::Integer = 1, chains::Integer = 4,
+                              burn::Integer = 500, thin::Integer = 1, seed::Integer = 20160415, first_sweep::Integer = 0,
+                              prior = (tau_lam = 1.0, nu_R = 4.0, s_R = 0.25, tau_rho = 4.0, tau_A = 1.0,
+                                       nu_Q = size(params.Lam, 2) + 2.0, s_Q = 0.5),
+                              A0 = nothing, singular_q::Bool = false)
+    T, N = size(z); r = size(params.Lam, 2); q = size(params.rho, 2); k = r * nlag; B = Int(chains); K = Int(ndraws); n = T - q
+    rep(a) = repeat(a, outer = (ntuple(_ -> 1, ndims(a))..., B))
+    panel = rep(to_c_panel(z)[:, :, 1])
+    Lam = rep(permutedims(params.Lam)); S2 = rep(copy(params.sig2)); Rho = rep(permutedims(params.rho))
+    AC = rep(permutedims(params.Avar)); QC = rep(permutedims(params.Q)); mu0 = rep(copy(params.mu0)); P0C = rep(permutedims(params.P0))
+    A0C = A0 === nothing ? C_NULL : rep(permutedims(Matrix{Float64}(A0)))
+    n_sweeps = burn + (K - 1) * thin + 1
+    Ld = Array{Float64}(undef, r, N, K, B); Sd = Array{Float64}(undef, N, K, B); Rd = Array{Float64}(undef, q, N, K, B)
+    Ad = Array{Float64}(undef, k, r, K, B); Qd = Array{Float64}(undef, r, r, K, B); fd = Array{Float64}(undef, r, n, K, B)
+    flags = (any(isnan, z) ? DFM_F_MAY_HAVE_MISSING : Cuint(0)) | (singular_q ? DFM_F_SINGULAR_Q : Cuint(0))
+    GC.@preserve panel Lam S2 Rho AC QC mu0 P0C A0C Ld Sd Rd Ad Qd fd begin
+        rc = ccall((:dfm_gibbs_ar_batch, LIB), Cint,
+                   (Ptr{Cvoid}, Cint, Cint, Cint, Cint, Cint, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                    Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cdouble, Cdouble, Cdouble, Cdouble, Cdouble, Cdouble, Cdouble,
+                    Ptr{Float64}, Cint, Cint, Cint, UInt64, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                    Ptr{Float64}, Ptr{Float64}, Cuint),
+                   h.ptr, B, T, N, r, nlag, q, panel, mu0, P0C, Lam, S2, Rho, AC, QC, prior.tau_lam, prior.nu_R, prior.s_R,
+                   prior.tau_rho, prior.tau_A, prior.nu_Q, prior.s_Q, A0C, n_sweeps, burn, thin, UInt64(seed), Int64(first_sweep),
+                   Ld, Sd, Rd, Ad, Qd, fd, flags)
+        check(h.ptr, rc)
+    end
+    flat(a, perm) = (p = permutedims(a, perm); reshape(permutedims(p, (2, 1, 3:ndims(p)...)), :, size(p)[3:end]...))
+    return (Lam = flat(Ld, (4, 3, 2, 1)), sig2 = flat(Sd, (3, 2, 1)), rho = flat(Rd, (4, 3, 2, 1)), A = flat(Ad, (4, 3, 2, 1)),
+            Q = flat(Qd, (4, 3, 2, 1)), factor = flat(fd, (4, 3, 2, 1)))
+end
+
 "News decomposition of the revision of G target cells between two vintages (dfm_news_batch; include/dfm_hip.h): zold / znew
 are T x N (NaN = missing, standardised; every cell of zold observed in znew), params, nlag, mean / sd as `forecast`; targets =
 G (row, column) pairs, 1-based, rows past T are forecasts.  Returns yhat (3 x G: old, revised old, new), impact (G x N), news
