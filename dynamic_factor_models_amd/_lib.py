@@ -54,6 +54,7 @@ _HD_ARGS = [c_vp] + [c_int] * 5 + [c_vp] * 13 + [c_uint]
 _PX_ARGS = [c_vp] + [c_int] * 6 + [c_vp] * 10 + [c_int] * 3 + [ctypes.c_uint64, ctypes.c_int64] + [c_vp] * 7 + [c_uint]
 _FT_ARGS = [c_vp] + [c_int] * 7 + [c_vp] * 20 + [c_uint]
 _FCAR_ARGS = [c_vp] + [c_int] * 7 + [c_vp] * 18 + [c_uint]
+_FTAR_ARGS = [c_vp] + [c_int] * 8 + [c_vp] * 22 + [c_uint]
 _SSAR_ARGS = [c_vp] + [c_int] * 8 + [c_vp] * 11 + [ctypes.c_uint64, ctypes.c_int64, c_vp, c_vp, c_uint]
 _ARPASS_ARGS = [c_vp, c_int, c_int, c_int, c_int, c_int, c_int] + [c_vp] * 11 + [c_uint]
 _AREM_ARGS = [c_vp, c_int, c_int, c_int, c_int, c_int, c_int] + [c_vp] * 8 + [c_int, ctypes.c_double] + [c_vp] * 4 + [c_uint]
@@ -130,6 +131,8 @@ SYMBOLS = {
     "dfm_em_ar_batch": (c_int, _AREM_ARGS),
     "dfm_forecast_ar_batch_dev": (c_int, _FCAR_ARGS),
     "dfm_forecast_ar_batch": (c_int, _FCAR_ARGS),
+    "dfm_filter_ar_batch_dev": (c_int, _FTAR_ARGS),
+    "dfm_filter_ar_batch": (c_int, _FTAR_ARGS),
     "dfm_simsmooth_ar_batch_dev": (c_int, _SSAR_ARGS),
     "dfm_simsmooth_ar_batch": (c_int, _SSAR_ARGS),
     "dfm_gibbs_ar_batch_dev": (c_int, _GBAR_ARGS),

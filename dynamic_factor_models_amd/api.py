@@ -2199,6 +2199,134 @@ def estimate_bayesian_ar_idio(m: DFMModel, ndraws: int, *, chains: int = 4, burn
     return out
 
 
+_AR_PARAM_NAMES = ("Lam", "sig2", "rho", "Avar", "Q", "mu0", "P0")
+
+
+def _filter_ar_setup(m: DFMModel, through, params, who):
+    """The checks and inputs filter_states_ar_idio and evaluate_forecasts_ar_idio share (no device is touched): q, through, the
+    panel, the parameter sets [S, ...] (the model's own as one set without `params`), cols, mu_f and the data-unit mean."""
+    q = int(m.n_uarlag)
+    if not (1 <= q <= 4):
+        raise ValueError(f"{who} needs 1 <= n_uarlag <= 4")
+    through = m.lastperiod if through is None else int(through)
+    if not (m.lastperiod <= through <= m.T):
+        raise ValueError(f"through must lie in lastperiod..T ({m.lastperiod}..{m.T})")
+    inputs, cols, mu_f, c_i = _ar_model_inputs(m, through)
+    sets = [inputs[k][None] for k in _AR_PARAM_NAMES]
+    if params is not None:
+        lost = [k for k in _AR_PARAM_NAMES if k not in params]
+        if lost:
+            raise ValueError(f"params lacks {lost}")
+        sets = [np.ascontiguousarray(params[k], dtype=np.float64) for k in _AR_PARAM_NAMES]
+        S = sets[0].shape[0] if sets[0].ndim == 3 else 0
+        for k, a in zip(_AR_PARAM_NAMES, sets):
+            if S < 1 or a.shape != (S,) + inputs[k].shape:
+                raise ValueError(f"params[{k!r}] must be [S, ...] with the model's own shape {inputs[k].shape} behind S >= 1")
+    mean = c_i + inputs["Lam"] @ mu_f
+    return q, through, inputs, sets, cols, mu_f, mean
+
+
+def filter_states_ar_idio(m: DFMModel, *, through: Optional[int] = None, params=None, ctx=None) -> dict:
+    """What the model with AR(n_uarlag) idiosyncratic terms knew at every period: the Kalman filter's predicted and filtered
+    factors, the per-period log-likelihood and the one-step prediction errors of the panel -- the diagnostics of the fit that
+    `forecast_ar_idio` forecasts from.  Inputs, window, `through` and the data units (mean_i = c_i + lam_i' mu_f, sd = 1) exactly
+    as `forecast_ar_idio`; the parameters are held fixed over the sample.  One dfm_filter_ar_batch call on the GPU.  Returns a dict:
+      rows            1-based periods initperiod + q .. through
+      cols            column indices (0-based) of m.data: the series `_ar_model_inputs` used
+      factor_pred     [rows, r] E[f_t | rows before t] (with the factor mean mu_f), factor_pred_cov [rows, r, r] its variance
+      factor_filt     [rows, r] E[f_t | rows up to t],  factor_filt_cov [rows, r, r]
+      state_pred, state_filt   [rows, r m] the whole state (f_t, .., f_{t-m+1}), m = max(p, q + 1), in deviations from mu_f
+      loglik_t        [rows] log density of each row's observed quasi-differences given the rows before it; loglik their sum, the
+                      log-likelihood of `forecast_ar_idio` (conditional on the first q rows)
+      x_pred          [rows, cols] one-step prediction of every cell whose q lags are observed (NaN elsewhere), data units
+      error           [rows, cols] x - x_pred, NaN where the cell or one of its lags is missing
+      error_std       [rows, cols] the standardised innovation (mean 0, variance 1 under the model), NaN likewise
+    `params` (default None: the model's own parameters): ONE parameter set in the layout of `estimate_bayesian_ar_idio`'s `params`
+    (S = 1 on the first axis).  `m` is not modified."""
+    q, through, inputs, sets, cols, mu_f, mean = _filter_ar_setup(m, through, params, "filter_states_ar_idio")
+    if sets[0].shape[0] != 1:
+        raise ValueError("filter_states_ar_idio takes one parameter set (S = 1); evaluate_forecasts_ar_idio takes several")
+    x = inputs["x"]
+    want = ("z_pred", "P_pred", "z_filt", "P_filt", "loglik_t", "xpred", "verr", "vstd")
+    ctx, own = _own(ctx)
+    try:
+        o = ctx.filter_ar_batch_host(x[None], *sets, H=0, mean=mean[None], sd=np.ones((1, cols.size)), want=want,
+                                     may_have_missing=bool(np.isnan(x).any()))
+    finally:
+        if own:
+            ctx.close()
+    r = m.nfac_u
+    k = o["z_pred"].shape[2]
+    Pp, Pf = _unpack(o["P_pred"][0], k), _unpack(o["P_filt"][0], k)
+    return dict(rows=np.arange(m.initperiod + q, through + 1), cols=cols, factor_pred=o["z_pred"][0][:, :r] + mu_f,
+                factor_pred_cov=Pp[:, :r, :r], factor_filt=o["z_filt"][0][:, :r] + mu_f, factor_filt_cov=Pf[:, :r, :r],
+                state_pred=o["z_pred"][0], state_filt=o["z_filt"][0], loglik_t=o["loglik_t"][0],
+                loglik=float(o["loglik_t"][0].sum()), x_pred=o["xpred"][0], error=o["verr"][0], error_std=o["vstd"][0], mu_f=mu_f,
+                inputs=dict(inputs, mean=mean))
+
+
+def evaluate_forecasts_ar_idio(m: DFMModel, H: int, *, first_origin: Optional[int] = None, through: Optional[int] = None,
+                               params=None, quantiles=None, ctx=None) -> dict:
+    """The pseudo-out-of-sample record of the model with AR(n_uarlag) idiosyncratic terms: the h-step forecast error of every
+    series at every origin, h = 1..H, with the fit held fixed, summarised per horizon and series -- and beside it the record of
+    the factor-only forecast from the same filtered state on the same origins, so that `gain` says what the idiosyncratic
+    persistence buys.  Inputs, window, `through` and the data units as `forecast_ar_idio`.  Origins are the 1-based periods
+    first_origin .. through - h (default first_origin: the middle of the rows initperiod + q .. through) at which the series' last
+    q cells and its target cell are observed; the forecast made at origin t uses rows initperiod..t only.  One dfm_filter_ar_batch
+    call on the GPU.  Returns a dict:
+      horizons     1 .. H
+      cols         column indices (0-based) of m.data: the series `_ar_model_inputs` used
+      msfe         [H, cols] mean squared forecast error, NaN where no origin qualifies;  rmsfe its square root
+      msfe_common  [H, cols] the same of the factor-only forecast c_i + lam_i' f_{t+h|t}
+      gain         [H, cols] msfe / msfe_common (< 1: the idiosyncratic term helps)
+      relative     [H, cols] msfe over the MSFE of the unconditional-mean forecast on the same cells (< 1: the model helps)
+      count        [H, cols] origins averaged
+    `params`: the `params` of `estimate_bayesian_ar_idio` -- S parameter sets on the first axis, run as S replicates of the one
+    call; the record above is then that of the first set, and with `quantiles` (needs `params`: `estimate_ar_idio` has no
+    replicates) bands [nq, H, cols] of msfe and gain_bands of gain over the sets (dfm_quantile_bands).  `m` is not modified."""
+    H = int(H)
+    if H < 1:
+        raise ValueError("H must be >= 1")
+    qs = None
+    if quantiles is not None:
+        if params is None:
+            raise ValueError("quantile bands need parameter sets: params=estimate_bayesian_ar_idio(...)['params']")
+        qs = np.atleast_1d(np.asarray(quantiles, dtype=np.float64))
+        if qs.size < 1 or not np.all((qs > 0.0) & (qs <= 1.0)):
+            raise ValueError("quantiles must lie in (0, 1]")
+    q, through, inputs, sets, cols, mu_f, mean = _filter_ar_setup(m, through, params, "evaluate_forecasts_ar_idio")
+    first = m.initperiod + q
+    rows = through - first + 1
+    first_origin = first + rows // 2 if first_origin is None else int(first_origin)
+    if not (first <= first_origin <= through):
+        raise ValueError(f"first_origin must lie in initperiod + n_uarlag..through ({first}..{through})")
+    S = sets[0].shape[0]
+    if qs is not None and S > _QUANTILE_MAX_DRAWS:
+        raise ValueError(f"bands need at most {_QUANTILE_MAX_DRAWS} parameter sets")
+    x = inputs["x"]
+    rep = lambda a: np.ascontiguousarray(np.broadcast_to(a, (S,) + a.shape))
+    ctx, own = _own(ctx)
+    try:
+        o = ctx.filter_ar_batch_host(rep(x), *sets, H=H, t0=first_origin - m.initperiod, mean=rep(mean), sd=np.ones((S, cols.size)),
+                                     want=("msfe", "msfe_common", "msfe0", "cnt"), may_have_missing=bool(np.isnan(x).any()))
+        bands = gbands = None
+        if qs is not None:
+            with np.errstate(invalid="ignore", divide="ignore"):
+                g = o["msfe"] / o["msfe_common"]
+            band = lambda a: ctx.quantile_bands_host(np.ascontiguousarray(a.reshape(S, -1)), qs).reshape((qs.size,) + a.shape[1:])
+            bands, gbands = band(o["msfe"]), band(g)
+    finally:
+        if own:
+            ctx.close()
+    msfe, msfec, msfe0 = o["msfe"][0], o["msfe_common"][0], o["msfe0"][0]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        out = dict(horizons=np.arange(1, H + 1), cols=cols, msfe=msfe, rmsfe=np.sqrt(msfe), msfe_common=msfec, gain=msfe / msfec,
+                   relative=msfe / msfe0, count=o["cnt"][0])
+    if bands is not None:
+        out["quantiles"], out["bands"], out["gain_bands"] = qs, bands, gbands
+    return out
+
+
 def amengual_watson_test(m: DFMModel, nper: int = 4, *, ctx=None):
     """`amengual_watson_test(m, nper)` -- dfm_functions.ipynb:734-768: the number of DYNAMIC factors.  Every
     included series is regressed on [1, lags 1..p of the r estimated static factors], p = the factor VAR's

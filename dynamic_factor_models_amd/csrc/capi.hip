@@ -168,7 +168,8 @@ struct dfm_handle {
                                            // dfm_proxyirf_batch_dev: cum, the used rows, the instrument, S, S^-1, the Theta tables, the row
                                            // table, the slots' w and tables, the den table and the pass outputs the caller does not take
     DevBlock ft;                           // dfm_filter_batch_dev: the padded loadings, the collapse's per-period arrays, the moments the
-                                           // caller does not take and the evaluation's running sums
+                                           // caller does not take and the evaluation's running sums;
+                                           // dfm_filter_ar_batch_dev: the same, with the quasi-differenced panel and its loadings
     DevBlock gb;                           // dfm_gibbs_batch_dev: the sweep's factor path and the shared Gram roots of balanced panels
                                            // dfm_gibbs_ar_batch_dev: the sweep's [B][T - q][r] factor path
     std::vector<int> sv_idx;               // host copy of named / cum while their upload is in flight
@@ -184,11 +185,11 @@ struct dfm_handle {
 };
 
 enum KernelId { K_COLLAPSE = 0, K_RECURSION, K_MSTEP_STATS, K_MSTEP_SOLVE, K_PCA, K_SYNTH, K_PAD,
-                K_COLLAPSE_DMA, K_GRAM, K_COV, K_MEANSCAN, K_PFILL, K_COLLAPSE_MFMA, K_ALS, K_OLS, K_BOOT, K_QUANT, K_COLLAPSE_WIDE, K_EM_UPDATE, K_CHOW, K_MSTEP_MFMA, K_GRAM_XX, K_PASS_FUSED, K_FC_TAIL, K_FC_FILL, K_FC_PAD, K_SS_PREP, K_SS_EXPAND, K_SS_PATH, K_SS_DIFF, K_SS_FINISH, K_SS_FILL, K_NW_REVISE, K_NW_GATHER, K_NW_GAMMA, K_NW_COV, K_NW_IMPACT, K_MF_TABLE, K_MF_MOMENTS, K_MF_SOLVE, K_SV_PREP, K_SV_IRF_FILL, K_SV_SHOCK, K_SV_PATH, K_SV_HD_FILL, K_FT_FILTER, K_FT_FILL, K_FT_EVAL, K_GB_GRAM, K_GB_LOAD, K_GB_VAR, K_SV_SIGN_TABLE, K_SV_SIGN, K_SV_SIGN_KEEP, K_PX_ROWS, K_PX_MOMENT, K_PX_SLOT_TABLE, K_PX_DEN, K_PX_FILL, K_PX_SHOCK, K_MF_SOLVE_BLOCKS, K_FCAR_BACK, K_FCAR_FWD, K_SSAR_PARAMS, K_SSAR_EXPAND, K_SSAR_DIFF, K_SSAR_FWD, K_SSAR_FINISH, K_GB_AR_SERIES, K_COUNT };
+                K_COLLAPSE_DMA, K_GRAM, K_COV, K_MEANSCAN, K_PFILL, K_COLLAPSE_MFMA, K_ALS, K_OLS, K_BOOT, K_QUANT, K_COLLAPSE_WIDE, K_EM_UPDATE, K_CHOW, K_MSTEP_MFMA, K_GRAM_XX, K_PASS_FUSED, K_FC_TAIL, K_FC_FILL, K_FC_PAD, K_SS_PREP, K_SS_EXPAND, K_SS_PATH, K_SS_DIFF, K_SS_FINISH, K_SS_FILL, K_NW_REVISE, K_NW_GATHER, K_NW_GAMMA, K_NW_COV, K_NW_IMPACT, K_MF_TABLE, K_MF_MOMENTS, K_MF_SOLVE, K_SV_PREP, K_SV_IRF_FILL, K_SV_SHOCK, K_SV_PATH, K_SV_HD_FILL, K_FT_FILTER, K_FT_FILL, K_FT_EVAL, K_GB_GRAM, K_GB_LOAD, K_GB_VAR, K_SV_SIGN_TABLE, K_SV_SIGN, K_SV_SIGN_KEEP, K_PX_ROWS, K_PX_MOMENT, K_PX_SLOT_TABLE, K_PX_DEN, K_PX_FILL, K_PX_SHOCK, K_MF_SOLVE_BLOCKS, K_FCAR_BACK, K_FCAR_FWD, K_SSAR_PARAMS, K_SSAR_EXPAND, K_SSAR_DIFF, K_SSAR_FWD, K_SSAR_FINISH, K_GB_AR_SERIES, K_FTAR_FILTER, K_FTAR_FILL, K_FTAR_EVAL, K_COUNT };
 static const char* const kKernelNames[K_COUNT] = {"collapse_kernel", "recursion_kernel", "mstep_lam_kernel",
                                                   "mstep_solve_kernel", "pca_kernel", "synth_kernel",
                                                   "pad_params_kernel", "collapse_dma_kernel", "gram_kernel",
-                                                  "cov_kernel", "meanscan_kernel", "pfill_kernel", "collapse_mfma_kernel", "als_kernel", "ols_kernel", "var_boot_kernel", "quantile_kernel", "collapse_wide_kernel", "em_update_kernel", "chow_kernel", "mstep_mfma_kernel", "gram_xx_kernel", "pass_fused_kernel", "forecast_tail_kernel", "forecast_fill_kernel", "forecast_pad_kernel", "simsmooth_prep_kernel", "simsmooth_expand_kernel", "simsmooth_path_kernel", "simsmooth_diff_kernel", "simsmooth_finish_kernel", "simsmooth_fill_kernel", "news_revise_kernel", "news_gather_kernel", "news_gamma_kernel", "news_cov_panel_kernel", "news_impact_kernel", "mf_table_kernel", "mf_moments_kernel", "mf_solve_kernel", "sv_prep_kernel", "sv_irf_fill_kernel", "sv_shock_kernel", "sv_path_kernel", "sv_hd_fill_kernel", "filter_kernel", "filter_fill_kernel", "filter_eval_kernel", "gibbs_gram_kernel", "gibbs_load_kernel", "gibbs_var_kernel", "sv_sign_table_kernel", "sv_sign_kernel", "sv_sign_keep_kernel", "px_rows_kernel", "px_moment_kernel", "px_slot_table_kernel", "px_den_kernel", "px_fill_kernel", "px_shock_kernel", "mf_solve_blocks_kernel", "forecast_ar_back_kernel", "forecast_ar_fwd_kernel", "simsmooth_ar_params_kernel", "simsmooth_ar_expand_kernel", "simsmooth_ar_diff_kernel", "simsmooth_ar_fwd_kernel", "simsmooth_ar_finish_kernel", "gibbs_ar_series_kernel"};
+                                                  "cov_kernel", "meanscan_kernel", "pfill_kernel", "collapse_mfma_kernel", "als_kernel", "ols_kernel", "var_boot_kernel", "quantile_kernel", "collapse_wide_kernel", "em_update_kernel", "chow_kernel", "mstep_mfma_kernel", "gram_xx_kernel", "pass_fused_kernel", "forecast_tail_kernel", "forecast_fill_kernel", "forecast_pad_kernel", "simsmooth_prep_kernel", "simsmooth_expand_kernel", "simsmooth_path_kernel", "simsmooth_diff_kernel", "simsmooth_finish_kernel", "simsmooth_fill_kernel", "news_revise_kernel", "news_gather_kernel", "news_gamma_kernel", "news_cov_panel_kernel", "news_impact_kernel", "mf_table_kernel", "mf_moments_kernel", "mf_solve_kernel", "sv_prep_kernel", "sv_irf_fill_kernel", "sv_shock_kernel", "sv_path_kernel", "sv_hd_fill_kernel", "filter_kernel", "filter_fill_kernel", "filter_eval_kernel", "gibbs_gram_kernel", "gibbs_load_kernel", "gibbs_var_kernel", "sv_sign_table_kernel", "sv_sign_kernel", "sv_sign_keep_kernel", "px_rows_kernel", "px_moment_kernel", "px_slot_table_kernel", "px_den_kernel", "px_fill_kernel", "px_shock_kernel", "mf_solve_blocks_kernel", "forecast_ar_back_kernel", "forecast_ar_fwd_kernel", "simsmooth_ar_params_kernel", "simsmooth_ar_expand_kernel", "simsmooth_ar_diff_kernel", "simsmooth_ar_fwd_kernel", "simsmooth_ar_finish_kernel", "gibbs_ar_series_kernel", "filter_ar_kernel", "filter_ar_fill_kernel", "filter_ar_eval_kernel"};
 
 namespace dfm { int handle_device(const dfm_handle* h) { return h->device; } }   // (probe.hip)
 
@@ -3720,6 +3721,108 @@ int dfm_filter_batch(dfm_handle* h, int B, int T, int N, int r, int p, int H, in
     if (int rc = st.begin()) return rc;
     int rc = st.finish(dfm_filter_batch_dev(h, B, T, N, r, p, H, t0, x_d, lam_d, R_d, A_d, Q_d, mu_d, P0_d, mean_d, sd_d, zp_d, pp_d, zf_d,
                                             pf_d, ll_d, xp_d, ve_d, vs_d, m_d, m0_d, cnt_d, flags));
+    if (rc == 0) rc = status_check(h);
+    return rc;
+}
+
+// ---- the same for the model with AR idiosyncratic terms (filter_ar.hip) -----------------------------------------------------------
+// As ar_pass_run prepares its pass: quasi_diff_kernel and ar_loadings_kernel (loadings on q + 1 lag blocks, pad_r(k) wide: the width
+// of the AR pass's plan) into h->ft, collapse_kernel at that width on the quasi-differenced panel, then filter_ar_kernel and, for the
+// outputs the caller takes, filter_ar_fill_kernel and filter_ar_eval_kernel -- both read the panel itself.
+static int filter_ar_check(dfm_handle* h, int B, int T, int N, int r, int p, int q, int H, int t0, const double* panel,
+                           const double* Lam, const double* sig2, const double* rho, const double* Avar, const double* Q,
+                           const double* mu0, const double* P0, const double* mean, const double* sd) {
+    if (int rc = check_dims(h, B, T, N, r)) return rc;
+    if (H < 0) return fail(h, DFM_E_DIMS, "H must be >= 0%s");
+    if (p < 1) return fail(h, DFM_E_DIMS, "number of factor lags must be >= 1%s");
+    if (q < 1) return fail(h, DFM_E_DIMS, "number of idiosyncratic lags must be >= 1 (q = 0 is dfm_filter_batch)%s");
+    if (T <= q) return fail(h, DFM_E_DIMS, "T must exceed the number of idiosyncratic lags%s");
+    if (t0 < q || t0 >= T) return fail(h, DFM_E_DIMS, "t0 (the first origin) must lie in [q, T)%s");
+    if (q > 4) return fail(h, DFM_E_R_UNSUPPORTED, "the filter with AR idiosyncratic terms needs q <= 4%s");
+    if (int rc = ar_check(h, B, T, N, r, p, q, false)) return rc;
+    if (!panel || !Lam || !sig2 || !rho || !Avar || !Q || !mu0 || !P0) return fail(h, DFM_E_NULL, "required pointer is NULL%s");
+    if ((mean == nullptr) != (sd == nullptr)) return fail(h, DFM_E_NULL, "mean and sd must both be given or both be NULL%s");
+    return 0;
+}
+
+int dfm_filter_ar_batch_dev(dfm_handle* h, int B, int T, int N, int r, int p, int q, int H, int t0, const double* panel,
+                            const double* Lam, const double* sig2, const double* rho, const double* Avar, const double* Q,
+                            const double* mu0, const double* P0, const double* mean, const double* sd, double* z_pred,
+                            double* P_pred, double* z_filt, double* P_filt, double* loglik_t, double* xpred, double* verr,
+                            double* vstd, double* msfe, double* msfe_common, double* msfe0, int* cnt, unsigned flags) {
+    if (int rc = filter_ar_check(h, B, T, N, r, p, q, H, t0, panel, Lam, sig2, rho, Avar, Q, mu0, P0, mean, sd)) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const int m = p > q + 1 ? p : q + 1, k = r * m, w = r * (q + 1), Rp = pad_r(k), n = T - q;
+    const size_t d = sizeof(double), rr = (size_t)Rp * Rp, npR = (size_t)Rp * (Rp + 1) / 2, kk = (size_t)k * (k + 1) / 2, Bn = (size_t)B * n;
+    const bool miss = (flags & DFM_F_MAY_HAVE_MISSING) != 0;
+    const bool fill = xpred || verr || vstd, eval = H > 0 && (msfe || msfe_common || msfe0 || cnt);
+    const size_t n_e = (size_t)B * H * N;
+    size_t off = 0;
+    const size_t o_xq = take(off, Bn * N * d), o_lam = take(off, (size_t)B * N * Rp * d),
+                 o_b = take(off, Bn * Rp * d), o_s = take(off, Bn * d), o_ld = take(off, Bn * d), o_n = take(off, Bn * sizeof(int)),
+                 o_ct = miss ? take(off, Bn * npR * d) : (size_t)-1, o_cf = take(off, B * rr * d), o_lf = take(off, (size_t)B * d),
+                 o_zp = (!z_pred && fill) ? take(off, Bn * k * d) : (size_t)-1,
+                 o_pp = (!P_pred && vstd) ? take(off, Bn * kk * d) : (size_t)-1,
+                 o_zf = (!z_filt && eval) ? take(off, Bn * k * d) : (size_t)-1,
+                 o_acc = eval ? take(off, n_e * d) : (size_t)-1, o_accc = eval ? take(off, n_e * d) : (size_t)-1,
+                 o_acc0 = eval ? take(off, n_e * d) : (size_t)-1, o_acn = eval ? take(off, n_e * sizeof(int)) : (size_t)-1;
+    HIP_TRY(h, h->ft.grow(off));
+    double* xq = at<double>(h->ft, o_xq);
+    double* LamK = at<double>(h->ft, o_lam);
+    if (int rc = launch_1d(h, quasi_diff_kernel, Bn * N, B, T, N, q, panel, rho, xq)) return rc;
+    if (int rc = launch_1d(h, ar_loadings_kernel, (size_t)B * N * Rp, B, N, r, q, Rp, Lam, rho, LamK)) return rc;
+    CollapseArgs ca{};
+    ca.B = B; ca.T = n; ca.N = N; ca.panel = xq; ca.Lam = LamK; ca.Rv = sig2;
+    ca.kreal = w;                                               // (the loadings' columns w .. Rp - 1 are zero: as enqueue_pass at kdim)
+    ca.bcol = at<double>(h->ft, o_b); ca.scol = at<double>(h->ft, o_s); ca.nobs = at<int>(h->ft, o_n); ca.ldrow = at<double>(h->ft, o_ld);
+    ca.Ct = at<double>(h->ft, o_ct); ca.Cfull = at<double>(h->ft, o_cf); ca.ldfull = at<double>(h->ft, o_lf);
+    ca.status = h->status_dev;
+    { ProfScope ps(h, K_COLLAPSE); HIP_TRY(h, launch_collapse(Rp, ca, h->stream)); }
+    FtArArgs fa{};
+    fa.B = B; fa.T = T; fa.N = N; fa.r = r; fa.p = p; fa.q = q; fa.k = k; fa.w = w; fa.Rp = Rp; fa.H = H; fa.t0 = t0;
+    fa.panel = panel; fa.Lam = Lam; fa.sig2 = sig2; fa.rho = rho; fa.A = Avar; fa.Q = Q; fa.mu0 = mu0; fa.P0 = P0; fa.mean = mean; fa.sd = sd;
+    fa.bcol = ca.bcol; fa.scol = ca.scol; fa.nobs = ca.nobs; fa.ldrow = ca.ldrow; fa.Ct = ca.Ct; fa.Cfull = ca.Cfull; fa.ldfull = ca.ldfull;
+    fa.z_pred = z_pred ? z_pred : at<double>(h->ft, o_zp); fa.P_pred = P_pred ? P_pred : at<double>(h->ft, o_pp);
+    fa.z_filt = z_filt ? z_filt : at<double>(h->ft, o_zf); fa.P_filt = P_filt; fa.loglik_t = loglik_t;
+    fa.xpred = xpred; fa.verr = verr; fa.vstd = vstd;
+    fa.msfe = eval ? msfe : nullptr; fa.msfe_common = eval ? msfe_common : nullptr; fa.msfe0 = eval ? msfe0 : nullptr;
+    fa.cnt = eval ? cnt : nullptr;
+    fa.acc = at<double>(h->ft, o_acc); fa.accc = at<double>(h->ft, o_accc); fa.acc0 = at<double>(h->ft, o_acc0);
+    fa.acn = at<int>(h->ft, o_acn);
+    fa.status = h->status_dev;
+    { ProfScope ps(h, K_FTAR_FILTER); HIP_TRY(h, launch_filter_ar(fa, h->stream)); }
+    if (fill) { ProfScope ps(h, K_FTAR_FILL); HIP_TRY(h, launch_filter_ar_fill(fa, h->stream)); }
+    if (eval) { ProfScope ps(h, K_FTAR_EVAL); HIP_TRY(h, launch_filter_ar_eval(fa, h->stream)); }
+    return 0;
+}
+
+int dfm_filter_ar_batch(dfm_handle* h, int B, int T, int N, int r, int p, int q, int H, int t0, const double* panel,
+                        const double* Lam, const double* sig2, const double* rho, const double* Avar, const double* Q,
+                        const double* mu0, const double* P0, const double* mean, const double* sd, double* z_pred,
+                        double* P_pred, double* z_filt, double* P_filt, double* loglik_t, double* xpred, double* verr,
+                        double* vstd, double* msfe, double* msfe_common, double* msfe0, int* cnt, unsigned flags) {
+    if (int rc = filter_ar_check(h, B, T, N, r, p, q, H, t0, panel, Lam, sig2, rho, Avar, Q, mu0, P0, mean, sd)) return rc;
+    if (int rc = status_epoch(h)) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t m = (size_t)(p > q + 1 ? p : q + 1), k = (size_t)r * m, kk = k * (k + 1) / 2, Bn = (size_t)B * (T - q),
+                 n_R = (size_t)B * N, n_x = Bn * N, n_e = (size_t)B * H * N;
+    if (H == 0) { msfe = nullptr; msfe_common = nullptr; msfe0 = nullptr; cnt = nullptr; }          // (left untouched)
+    HostStage st(h, 256);
+    double *x_d, *lam_d, *R_d, *rho_d, *A_d, *Q_d, *mu_d, *P0_d, *mean_d, *sd_d, *zp_d, *pp_d, *zf_d, *pf_d, *ll_d, *xp_d, *ve_d, *vs_d,
+        *m_d, *mc_d, *m0_d;
+    int* cnt_d;
+    st.in(panel, (size_t)B * T * N, x_d); st.in(Lam, (size_t)B * N * r, lam_d); st.in(sig2, n_R, R_d); st.in(rho, n_R * q, rho_d);
+    st.in(Avar, (size_t)B * r * r * p, A_d); st.in(Q, (size_t)B * r * r, Q_d); st.in(mu0, (size_t)B * k, mu_d);
+    st.in(P0, (size_t)B * k * k, P0_d); st.in(mean, mean ? n_R : 0, mean_d); st.in(sd, sd ? n_R : 0, sd_d);
+    st.out(z_pred, z_pred ? Bn * k : 0, zp_d); st.out(P_pred, P_pred ? Bn * kk : 0, pp_d);
+    st.out(z_filt, z_filt ? Bn * k : 0, zf_d); st.out(P_filt, P_filt ? Bn * kk : 0, pf_d);
+    st.out(loglik_t, loglik_t ? Bn : 0, ll_d);
+    st.out(xpred, xpred ? n_x : 0, xp_d); st.out(verr, verr ? n_x : 0, ve_d); st.out(vstd, vstd ? n_x : 0, vs_d);
+    st.out(msfe, msfe ? n_e : 0, m_d); st.out(msfe_common, msfe_common ? n_e : 0, mc_d); st.out(msfe0, msfe0 ? n_e : 0, m0_d);
+    st.out(cnt, cnt ? n_e : 0, cnt_d);
+    if (int rc = st.begin()) return rc;
+    int rc = st.finish(dfm_filter_ar_batch_dev(h, B, T, N, r, p, q, H, t0, x_d, lam_d, R_d, rho_d, A_d, Q_d, mu_d, P0_d, mean_d, sd_d, zp_d,
+                                               pp_d, zf_d, pf_d, ll_d, xp_d, ve_d, vs_d, m_d, mc_d, m0_d, cnt_d, flags));
     if (rc == 0) rc = status_check(h);
     return rc;
 }

@@ -1,5 +1,5 @@
-// dfm_cell.h -- the text the post-estimation cell kernels share (forecast.hip, filter.hip, structural.hip, proxy.hip, simsmooth.hip,
-// news.hip).  A cell kernel writes a [rows][N] panel from per-series loadings held in registers and per-row vectors staged in LDS
+// dfm_cell.h -- the text the post-estimation cell kernels share (forecast.hip, filter.hip, filter_ar.hip, structural.hip, proxy.hip,
+// simsmooth.hip, news.hip).  A cell kernel writes a [rows][N] panel from per-series loadings held in registers and per-row vectors staged in LDS
 // (DESIGN.md section 10).  No kernels here: the chunk decode, the row staging, the lane map, the loadings holder with its dot
 // product, the packed quadratic form, the 16-byte-or-scalar cell I/O and the twin launchers, each written once.  The first part is
 // plain C++ behind DFM_CELL_FN, so that tests/host/cell_host.cpp compiles the holder and the quadratic form for the CPU.

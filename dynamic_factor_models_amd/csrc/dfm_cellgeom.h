@@ -1,5 +1,5 @@
-// dfm_cellgeom.h -- launch geometry of the post-estimation cell kernels (forecast.hip, filter.hip, simsmooth.hip, news.hip,
-// structural.hip, proxy.hip) and of the series recursions of forecast_ar.hip (series_geometry; tests/host/seriesgeom_host.cpp,
+// dfm_cellgeom.h -- launch geometry of the post-estimation cell kernels (forecast.hip, filter.hip, filter_ar.hip, simsmooth.hip,
+// news.hip, structural.hip, proxy.hip) and of the series recursions of forecast_ar.hip (series_geometry; tests/host/seriesgeom_host.cpp,
 // tests/test_forecast_ar_cpu.py), the rule for the 16-byte cell path (cell_vec, cell_sp) and the two dispatchers the launchers
 // share.  Plain C++17 with no HIP include: the launchers call it, the kernels read the CellGeom it returns through their argument
 // struct, and tests/host/cellgeom_host.cpp compiles it for the CPU, where tests/test_post_geometry_cpu.py, tests/test_filter_cpu.py
@@ -78,6 +78,17 @@ inline CellGeom series_geometry(int N, int row_doubles, int rows, size_t lds_byt
     g.RC = rc;
     g.nchunk = (rows + rc - 1) / rc;
     return g;
+}
+
+// filter_ar_fill_kernel (filter_ar.hip), a cell kernel of the model with AR(q) idiosyncratic terms: the observation loads on the
+// first w = r (q + 1) entries of the state, so a staged row is the first w of z_pred and the packed leading w x w block of P_pred;
+// the loadings' register bucket is dispatch_r_bucket's of w, and SP follows cell_sp at it.  tests/host/filter_ar_geom_host.cpp.
+constexpr int kFtArFillMaxThreads = 512;
+constexpr size_t kFtArFillLds = 48 * 1024;
+
+inline int filter_ar_row_doubles(int w) { return w + w * (w + 1) / 2; }
+inline CellGeom filter_ar_fill_geometry(int N, int SP, int w, int rows) {
+    return cell_geometry((N + SP - 1) / SP, filter_ar_row_doubles(w), rows, kFtArFillMaxThreads, kFtArFillLds);
 }
 
 // sv_irf_fill_kernel: series blocks of at most max_lanes lanes of SP series and the rows of the Theta tables (one, or two with the

@@ -13,15 +13,11 @@
 // Nothing but W is factorised: Q, P_p and C_t may be singular.  filter_fill_kernel streams the prediction errors of every cell,
 // filter_eval_kernel the h-step forecast errors of every origin and their means over origins.
 #include "dfm_cell.h"
+#include "dfm_filter.h"
 #include "dfm_kernels.h"
 #include "dfm_smallmat.h"
 
 namespace dfm {
-
-constexpr int kFtFillMaxThreads = 512;
-constexpr size_t kFtFillLds = 48 * 1024;
-constexpr int kFtEvalChunk = 64;                  // origins whose states a workgroup of the evaluation advances together
-constexpr int kFtFailBit = 32;
 
 // ---- the recursion: one wave per replicate, every matrix in LDS ---------------------------------------------------------------
 // LDS (doubles): A r k | Q r r | P k k | Pp k k | X r k (A P, then C U, then S G^-1 C) | U r r | Y r (r+1) ([a | C_t]) |
@@ -30,37 +26,6 @@ __host__ __device__ inline size_t filter_lds_doubles(int r, int k) {
     return (size_t)2 * r * k + (size_t)2 * r * r + (size_t)2 * k * k + (size_t)3 * r * (r + 1) + (size_t)2 * k + (size_t)2 * r;
 }
 size_t filter_lds_bytes(int r, int k) { return filter_lds_doubles(r, k) * sizeof(double); }
-
-// Lower root L L' = M (leading n x n block of a matrix with rows ld apart, lower triangle read) of one wave's workgroup, as
-// psd_root: a pivot <= tol_rel trace(M) gives a zero column.  Returns 1 when a pivot is below -tol_rel trace(M) or not finite
-// (M is not positive semi-definite), else 0.  L: [n][n].
-__device__ inline int filter_root(const double* M, int ld, int n, double* L, double tol_rel) {
-    const int tid = threadIdx.x;
-    double tr = 0.0;
-    for (int i = 0; i < n; ++i) tr += M[i * ld + i];
-    const double tol = tol_rel * tr;
-    for (int e = tid; e < n * n; e += blockDim.x) L[e] = 0.0;
-    __syncthreads();
-    int bad = (tr == tr && fabs(tr) <= 1.79e308) ? 0 : 1;
-    for (int j = 0; j < n; ++j) {
-        double dj = M[j * ld + j];
-        for (int m = 0; m < j; ++m) dj -= L[j * n + m] * L[j * n + m];
-        const bool keep = dj > tol;
-        if (!(dj >= -tol)) bad = 1;
-        const double ljj = keep ? sqrt(dj) : 0.0;
-        for (int i = j + tid; i < n; i += blockDim.x) {
-            if (i == j) {
-                L[j * n + j] = ljj;
-            } else {
-                double v = M[i * ld + j];
-                for (int m = 0; m < j; ++m) v -= L[i * n + m] * L[j * n + m];
-                L[i * n + j] = keep ? v / ljj : 0.0;
-            }
-        }
-        __syncthreads();
-    }
-    return bad;
-}
 
 __global__ __launch_bounds__(64) void filter_kernel(FtArgs a) {
     extern __shared__ __attribute__((aligned(16))) double sm[];

@@ -902,5 +902,6 @@ from . import structural  # noqa: E402,F401  (attaches the structural entries to
 from . import filtering  # noqa: E402,F401  (attaches the filter entries to DfmContext)
 from . import gibbs  # noqa: E402,F401  (attaches the Gibbs sampler's entries to DfmContext)
 from . import forecasting_ar  # noqa: E402,F401  (attaches the forecast entries of the AR-idiosyncratic model to DfmContext)
+from . import filtering_ar  # noqa: E402,F401  (attaches its filter entries)
 from . import simsmooth_ar  # noqa: E402,F401  (attaches its path-draw entries)
 from . import gibbs_ar  # noqa: E402,F401  (attaches the Gibbs sampler's entries of the AR-idiosyncratic model)

@@ -911,6 +911,54 @@ int dfm_filter_batch(dfm_handle* h, int B, int T, int N, int r, int p, int H, in
                      double* z_filt, double* P_filt, double* loglik_t, double* xpred, double* verr, double* vstd,
                      double* msfe, double* msfe0, int* cnt, unsigned flags);
 
+/* dfm_filter_ar_batch (csrc/filter_ar.hip): the same for the model with AR(q) idiosyncratic terms -- what dfm_filter_batch is to
+ * dfm_forecast_batch, for dfm_forecast_ar_batch.  Model, inputs and conventions are those of dfm_ks_pass_ar_batch (1 <= q <= 4):
+ * m = max(p, q + 1), state z_t = (f_t, .., f_{t-m+1}) of width k = r m <= DFM_MAX_R, the quasi-differenced rows
+ * y_t = x_t - sum_l rho_l x_{t-l} = LamK z_t + eps_t for the panel rows t = q .. T-1 (a cell of y is missing when x_ti or one of its
+ * q lags is), mu0 / P0 used exactly as the pass uses them (loglik_t summed over the rows is the pass's loglik), mean / sd as
+ * dfm_filter_batch.  ONE forward recursion in covariance form, with the observation loading on the first w = r (q + 1) entries of
+ * the state (only the w x w W_t = I + U' C_t U is factorised), gives every origin; THE PARAMETERS ARE HELD FIXED OVER ALL ORIGINS.
+ * All outputs have n = T - q rows, the panel rows q .. T-1 (the pass's convention).  Every output may be NULL; kk = k (k + 1) / 2:
+ *   z_pred [B][n][k], P_pred [B][n][kk] packed lower   E, Var[z_t | y rows before t]
+ *   z_filt [B][n][k], P_filt [B][n][kk]                E, Var[z_t | y rows through t]
+ *   loglik_t [B][n]   log density of row t's observed y cells given the rows before it; 0 for a row without observed cells
+ *   xpred [B][n][N]   mean_i + sd_i (lamK_i' z_pred[t] + sum_l rho_il x_{t-l,i}): the one-step prediction of x, defined where x_ti
+ *                     itself is missing; NaN where a lag is missing
+ *   verr  [B][n][N]   sd_i (y_ti - lamK_i' z_pred[t]) = x - xpred in data units; NaN where y_ti is missing
+ *   vstd  [B][n][N]   (y_ti - lamK_i' z_pred[t]) / sqrt(lamK_i' P_pred[:w,:w] lamK_i + sig2_i); NaN where y_ti is missing
+ *   msfe, msfe_common, msfe0 [B][H][N]   h = 1 .. H: the mean over the qualifying origins of sd_i^2 (x_{t+h,i} - full)^2,
+ *                     sd_i^2 (x_{t+h,i} - common)^2 and sd_i^2 x_{t+h,i}^2 (x in model units); NaN without such an origin
+ *   cnt   [B][H][N]   int32, the origins averaged -- the same for all three
+ * The forecast at origin t (a panel row) of a series whose cells t, t-1, .., t-q+1 are all observed:
+ *   e_{t-l|t} = x_{t-l,i} - lam_i' z_{t|t}[block l], l = 0 .. q-1;  f_{t+h|t} = (M^h z_{t|t})[:r], M the companion matrix;
+ *   e_{t+h|t} = sum_l rho_il e_{t+h-l|t} (the AR(q) recursion run forward);
+ *   full = lam_i' f_{t+h|t} + e_{t+h|t},  common = lam_i' f_{t+h|t} (the factor-only forecast from the same state).
+ * On a balanced panel `full` is the exact E[x_{t+h,i} | x_0 .. x_t] of the likelihood, which is conditional on the first q rows.
+ * With missing cells the information set is the pass's own: a missing cell removes q + 1 quasi-differenced cells -- the convention
+ * of the pass's likelihood.  Qualifying origins are t = t0 .. T-1-h with the cells t .. t-q+1 and t+h of series i observed; an
+ * origin whose last q cells are not all observed needs lags the state does not hold, and is not evaluated and not counted.
+ * msfe / msfe_common says what the idiosyncratic persistence buys, per series and horizon.
+ * H = 0: no evaluation -- msfe, msfe_common, msfe0 and cnt are left untouched whether NULL or not.
+ * Status: H < 0, q < 1, T <= q, t0 outside [q, T): DFM_E_DIMS (q = 0 is dfm_filter_batch); q > 4, or r max(p, q + 1) > DFM_MAX_R:
+ * DFM_E_R_UNSUPPORTED; a NULL required input, mean without sd: DFM_E_NULL; a NaN in the panel without DFM_F_MAY_HAVE_MISSING:
+ * DFM_E_MISSING; N beyond the collapse's register tiling at the state's width, as the pass: DFM_E_DIMS.  A replicate whose update
+ * meets a non-finite value or a P_pred / W_t that is not positive semi-definite writes NaN from that period on; the outputs are
+ * written and the call (the host-pointer entry; dfm_check_status after the _dev entry) returns DFM_E_NUMERIC.  Sums over origins
+ * are taken in a fixed order: results are bit-identical from run to run.
+ * Allocates in the handle (kept for the next call): the quasi-differenced panel [B][n][N], the loadings on the lag blocks, the
+ * collapse's per-period arrays, the moments the caller does not take and the evaluation's running sums.  dfm_workspace_bytes does
+ * not count them.  Outputs must not overlap the inputs. */
+int dfm_filter_ar_batch_dev(dfm_handle* h, int B, int T, int N, int r, int p, int q, int H, int t0, const double* panel,
+                            const double* Lam, const double* sig2, const double* rho, const double* Avar, const double* Q,
+                            const double* mu0, const double* P0, const double* mean, const double* sd, double* z_pred,
+                            double* P_pred, double* z_filt, double* P_filt, double* loglik_t, double* xpred, double* verr,
+                            double* vstd, double* msfe, double* msfe_common, double* msfe0, int* cnt, unsigned flags);
+int dfm_filter_ar_batch(dfm_handle* h, int B, int T, int N, int r, int p, int q, int H, int t0, const double* panel,
+                        const double* Lam, const double* sig2, const double* rho, const double* Avar, const double* Q,
+                        const double* mu0, const double* P0, const double* mean, const double* sd, double* z_pred,
+                        double* P_pred, double* z_filt, double* P_filt, double* loglik_t, double* xpred, double* verr,
+                        double* vstd, double* msfe, double* msfe_common, double* msfe0, int* cnt, unsigned flags);
+
 /* --- synthetic replicates generated on the device (SURVEY.md §8(d) DGP; no reference
  * counterpart -- the reference has no RNG).  Writes the standardised panel and the DGP parameters
  * rescaled to it.  Counter-based generator keyed by (seed, first_replicate + b). */

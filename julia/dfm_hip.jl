@@ -698,6 +698,60 @@ function forecast_ar(h::Handle, x::Matrix{Float64}, Lam::Matrix{Float64}, sig2::
             factor = permutedims(f), P = permutedims(P), loglik = ll[1])
 end
 
+# dfm_filter_ar_batch for one replicate (include/dfm_hip.h); the parameters are held fixed over all origins.  t0: a 0-based panel row.
+function filter_ar_call(h::Handle, x::Matrix{Float64}, Lam::Matrix{Float64}, sig2::Vector{Float64}, rho::Matrix{Float64},
+                        Avar::Matrix{Float64}, Q::Matrix{Float64}, mu0::Vector{Float64}, P0::Matrix{Float64}, H::Integer, t0::Integer;
+                        mean = nothing, sd = nothing, singular_q::Bool = false)
+    (mean === nothing) == (sd === nothing) || error("mean and sd go together")
+    T, N = size(x); r = size(Lam, 2); q = size(rho, 2); p = div(size(Avar, 2), r); n = T - q
+    k = r * max(p, q + 1); kk = div(k * (k + 1), 2)
+    panel = to_c_panel(x)
+    LamC = permutedims(Lam); rhoC = permutedims(rho); AC = permutedims(Avar); QC = permutedims(Q); P0C = permutedims(P0)
+    meanC = mean === nothing ? C_NULL : Vector{Float64}(mean); sdC = sd === nothing ? C_NULL : Vector{Float64}(sd)
+    zp = Array{Float64}(undef, k, n); Pp = Array{Float64}(undef, kk, n); zf = Array{Float64}(undef, k, n); Pf = Array{Float64}(undef, kk, n)
+    ll = Array{Float64}(undef, n); xp = Array{Float64}(undef, N, n); ve = Array{Float64}(undef, N, n); vs = Array{Float64}(undef, N, n)
+    ms = Array{Float64}(undef, N, H); mc = Array{Float64}(undef, N, H); m0 = Array{Float64}(undef, N, H); cnt = Array{Cint}(undef, N, H)
+    flags = (any(isnan, x) ? DFM_F_MAY_HAVE_MISSING : Cuint(0)) | (singular_q ? DFM_F_SINGULAR_Q : Cuint(0))
+    GC.@preserve panel LamC sig2 rhoC AC QC mu0 P0C meanC sdC zp Pp zf Pf ll xp ve vs ms mc m0 cnt begin
+        rc = ccall((:dfm_filter_ar_batch, LIB), Cint,
+                   (Ptr{Cvoid}, Cint, Cint, Cint, Cint, Cint, Cint, Cint, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                    Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                    Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                    Ptr{Float64}, Ptr{Cint}, Cuint),
+                   h.ptr, 1, T, N, r, p, q, H, t0, panel, LamC, sig2, rhoC, AC, QC, mu0, P0C, meanC, sdC, zp, Pp, zf, Pf, ll, xp, ve, vs,
+                   H > 0 ? ms : C_NULL, H > 0 ? mc : C_NULL, H > 0 ? m0 : C_NULL, H > 0 ? cnt : C_NULL, flags)
+        check(h.ptr, rc)
+    end
+    return (zp = zp, Pp = Pp, zf = zf, Pf = Pf, ll = ll, xp = xp, ve = ve, vs = vs, ms = ms, mc = mc, m0 = m0, cnt = cnt)
+end
+
+"Predicted and filtered states, per-period log-likelihoods and one-step prediction errors of the model with AR(q) idiosyncratic
+terms (dfm_filter_ar_batch; include/dfm_hip.h): arguments as forecast_ar.  Rows q+1..T: state_pred / state_filt (T-q x r max(p, q+1)),
+P_pred / P_filt (packed lower per row), loglik_t (its sum is ks_pass_ar's loglik), x_pred (NaN where a lag is missing), error (data
+units) and error_std (NaN where the cell or one of its q lags is missing)."
+function filter_ar(h::Handle, x::Matrix{Float64}, Lam::Matrix{Float64}, sig2::Vector{Float64}, rho::Matrix{Float64},
+                   Avar::Matrix{Float64}, Q::Matrix{Float64}, mu0::Vector{Float64}, P0::Matrix{Float64};
+                   mean = nothing, sd = nothing, singular_q::Bool = false)
+    o = filter_ar_call(h, x, Lam, sig2, rho, Avar, Q, mu0, P0, 0, size(rho, 2); mean = mean, sd = sd, singular_q = singular_q)
+    return (state_pred = permutedims(o.zp), P_pred = permutedims(o.Pp), state_filt = permutedims(o.zf), P_filt = permutedims(o.Pf),
+            loglik_t = o.ll, x_pred = permutedims(o.xp), error = permutedims(o.ve), error_std = permutedims(o.vs))
+end
+
+"The pseudo-out-of-sample record of the model with AR(q) idiosyncratic terms, the fit held fixed (dfm_filter_ar_batch;
+include/dfm_hip.h): origins first_origin..T-h (1-based rows of x, first_origin > q) whose last q cells and target are observed,
+horizons h = 1..H.  Returns msfe, rmsfe, msfe_common (the factor-only forecast from the same state), gain (msfe ./ msfe_common),
+relative (msfe over the unconditional-mean forecast's) and count, each H x N."
+function evaluate_forecasts_ar(h::Handle, x::Matrix{Float64}, Lam::Matrix{Float64}, sig2::Vector{Float64}, rho::Matrix{Float64},
+                               Avar::Matrix{Float64}, Q::Matrix{Float64}, mu0::Vector{Float64}, P0::Matrix{Float64}, H::Integer;
+                               first_origin::Integer = size(rho, 2) + div(size(x, 1) - size(rho, 2), 2) + 1,
+                               mean = nothing, sd = nothing, singular_q::Bool = false)
+    H >= 1 || error("H must be >= 1")
+    o = filter_ar_call(h, x, Lam, sig2, rho, Avar, Q, mu0, P0, H, first_origin - 1; mean = mean, sd = sd, singular_q = singular_q)
+    msfe = permutedims(o.ms); msfec = permutedims(o.mc)
+    return (msfe = msfe, rmsfe = sqrt.(msfe), msfe_common = msfec, gain = msfe ./ msfec, relative = msfe ./ permutedims(o.m0),
+            count = permutedims(o.cnt))
+end
+
 "Joint posterior draws of the factor path and of the missing / future cells with AR(q) idiosyncratic terms
 (dfm_simsmooth_ar_batch; include/dfm_hip.h): arguments as forecast_ar; ndraws independent draws over rows q+1..T+H by the
 simulation smoother, a pure function of (seed, first_draw + draw index), with mean `forecast_ar`'s x and the joint covariance of
