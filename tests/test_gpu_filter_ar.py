@@ -2,7 +2,9 @@
 tests/filter_ar_expect.py at the project's 1e-9 x max(1, scale), NaN positions and counts exactly: the case table of
 filter_ar_expect.CASES, one panel of missing patterns, kernels this entry does not share (the AR pass, dfm_filter_batch at rho = 0,
 dfm_forecast_ar_batch on a truncated panel), every optional output left out in turn, the two entries, repeated calls, the status
-codes, a failed replicate, and the two api functions on the Stock-Watson panel."""
+codes, a failed replicate, and the two api functions on the Stock-Watson panel.  The table of tests/ar_post_geometry.py
+(tests/test_gpu_ar_post_geometry.py) adds r > 8, state widths that are no power of two, every reachable instance of the fill and of the
+evaluation, and 64 and 65 evaluation origins."""
 import ctypes
 import os
 

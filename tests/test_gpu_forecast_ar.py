@@ -4,7 +4,9 @@ conditioning of the idiosyncratic process on its residuals -- at 1e-9, section 1
 bit for bit, xvar on them is exactly 0.  The case table (forecast_ar_expect.CASES) holds the smallest shapes that reach every
 branch: q = 1 .. 4, p below / at / above q + 1, r = 1 and 8 (k = 32), one / two / three series blocks with full and ragged last
 waves, T = q + 1, a horizon longer than a staged chunk, every missing-cell pattern of apply_pattern in one panel;
-tests/test_forecast_ar_cpu.py checks that table's coverage and conditioning without a device."""
+tests/test_forecast_ar_cpu.py checks that table's coverage and conditioning without a device.  Branches, not kernel instances:
+the table of tests/ar_post_geometry.py (tests/test_gpu_ar_post_geometry.py) runs every reachable (Q, RB) instance of the two kernels
+and every edge of their staged chunks."""
 import ctypes
 import os
 

@@ -3,6 +3,8 @@ at 1e-9.  Every sweep is compared on its own: the model's sweep j starts from th
 compounds.  The case table is tests/gibbs_ar_cases.py; tests/test_gibbs_ar_cpu.py asserts that no accept of it is decided within
 1e-6 of its boundary, so no series is left out of a comparison.  Then: continuation, repeatability, burn / thin, NULL outputs, the
 device entry, the rho cap, every status code, and api.estimate_bayesian_ar_idio with its draws handed to api.draw_paths_ar_idio.
+That table reaches the sampler's branches; the table of tests/ar_post_geometry.py (tests/test_gpu_ar_post_geometry.py) runs every
+(Q, RB) instance of gibbs_ar_series_kernel, three series blocks and the edges of its staged chunks.
 
 The api test's figures are measured, not chosen: the expectation model, run on the CPU on the same stream
 from the same start (scripts/gibbs_ar_api_bound.py: the Stock-Watson panel, 2 chains, 4 + 6 sweeps, about two minutes), gives

@@ -4,7 +4,9 @@ series for step 6) at 1e-9 x scale, the bound of tests/test_gpu_simsmooth.py and
 are bit for bit.  The case table (simsmooth_ar_expect.CASES; its coverage is checked in tests/test_simsmooth_ar_cpu.py, which
 also shows that the restatement has the exact posterior mean and joint covariance) holds the smallest shapes that reach every
 branch: q = 1 .. 4, p below / at / above q + 1, r = 1, 4 and 8 with k = 32, N = 1, 64, 65 and 257 (two series blocks), T = q + 1,
-H = 0, 1 and 41 (longer than a staged chunk), B = 1 and 3, D = 1 and 5, every missing-cell class of apply_pattern."""
+H = 0, 1 and 41 (longer than a staged chunk), B = 1 and 3, D = 1 and 5, every missing-cell class of apply_pattern.  Branches, not
+kernel instances: the table of tests/ar_post_geometry.py (tests/test_gpu_ar_post_geometry.py) runs every reachable (Q, RB) instance of
+the kernels, three series blocks and every edge of their staged chunks."""
 import ctypes
 import os
 
