@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "dfm_kernels.h"
+#include "dfm_mfgeom.h"
 #include "dfm_msgeom.h"
 
 using namespace dfm;
@@ -1386,42 +1387,15 @@ int ar_em_run(dfm_handle* h, int B, int T, int N, int r, int nlag, int q, const 
 // x_it = lam_i' sum_{l<L} w_il f_{t-l} + e_it with known weights W [N][L] shared by the batch: a sibling of the AR model above without
 // quasi-differencing and without a rho step.  Loadings [w_i0 lam_i, .., w_i,L-1 lam_i, 0..] on the companion state of
 // m = max(p, L) lags, the pass and the restricted transition step as ar_em_run, then the series step from a per-class table.
-struct MfClasses {
-    int C = 0, ntiles = 0;
-    std::vector<double> Wc;            // [C][L]
-    std::vector<int> tile_class, tile_series;
-};
-// the distinct rows of W (exact comparison) and the series dealt into class-pure tiles of 16 (index lists, -1 = padding)
+using MfClasses = MfDeal;
+// the distinct rows of W (exact comparison) and the series dealt into class-pure tiles of 16 (index lists, -1 = padding):
+// dfm_mfgeom.h mf_deal
 int mf_classes(dfm_handle* h, int N, int L, const std::vector<double>& W, MfClasses* mc) {
-    std::vector<int> cls(N);
-    for (int i = 0; i < N; ++i) {
-        for (int l = 0; l < L; ++l)
-            if (!isfinite(W[(size_t)i * L + l])) return fail(h, DFM_E_DIMS, "mixed frequency: a weight is not finite%s");
-        int c = 0;
-        for (; c < mc->C; ++c) {
-            bool same = true;
-            for (int l = 0; l < L; ++l) same = same && mc->Wc[(size_t)c * L + l] == W[(size_t)i * L + l];
-            if (same) break;
-        }
-        if (c == mc->C) {
-            if (mc->C == kMfMaxClasses) return fail(h, DFM_E_DIMS, "mixed frequency: more than 8 distinct weight vectors%s");
-            mc->Wc.insert(mc->Wc.end(), W.begin() + (size_t)i * L, W.begin() + (size_t)(i + 1) * L);
-            ++mc->C;
-        }
-        cls[i] = c;
+    switch (mf_deal(N, L, W.data(), mc)) {
+        case kMfDealOk: return 0;
+        case kMfDealNotFinite: return fail(h, DFM_E_DIMS, "mixed frequency: a weight is not finite%s");
+        default: return fail(h, DFM_E_DIMS, "mixed frequency: more than 8 distinct weight vectors%s");
     }
-    for (int c = 0; c < mc->C; ++c) {
-        int fill = 0;
-        for (int i = 0; i < N; ++i) {
-            if (cls[i] != c) continue;
-            if (fill == 0) mc->tile_class.push_back(c);
-            mc->tile_series.push_back(i);
-            fill = (fill + 1) & 15;
-        }
-        while (fill) { mc->tile_series.push_back(-1); fill = (fill + 1) & 15; }
-    }
-    mc->ntiles = (int)mc->tile_class.size();
-    return 0;
 }
 
 int mf_check(dfm_handle* h, int B, int T, int N, int r, int nlag, int L) {

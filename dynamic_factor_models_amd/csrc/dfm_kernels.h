@@ -270,7 +270,7 @@ size_t mstep_ar_workspace(int B, int T, int N, int r, int q, int Rk);
 hipError_t launch_mstep_ar(const ArMstepArgs& a, double* ws, hipStream_t s);
 // Series block of the EM iteration of the mixed-frequency model (mstep_mf.hip): x_it = lam_i' sum_l w_il f_{t-l} + e_it with known
 // weights in C <= kMfMaxClasses distinct classes; the series dealt by index into tiles of 16 of one class each.
-constexpr int kMfMaxClasses = 8, kMfMaxLags = 5;
+// (kMfMaxClasses = 8, kMfMaxLags = 5, the row of the table and the grids: dfm_mfgeom.h)
 struct MfMstepArgs {
     int B, T, N, r, L, Rk, C;   // Rk: padded state width (r max(p, L) <= Rk)
     int VW;                     // mstep_mf_row_width(r): columns of a class row of the table

@@ -19,6 +19,7 @@
 //   mf_solve_kernel    a thread per series: the r x r Cholesky solve and R_i, with the n_i < r + 1 rule.
 // mf_loadings_kernel expands the loadings for the E-step: LamK[i] = [w_i0 lam_i, .., w_i,L-1 lam_i, 0..].
 #include "dfm_kernels.h"
+#include "dfm_mfgeom.h"
 
 namespace dfm {
 
@@ -48,7 +49,7 @@ __global__ __launch_bounds__(256) void mf_table_kernel(MfMstepArgs a, double* __
     const int e = (int)blockIdx.x * 256 + (int)threadIdx.x;
     if (e >= a.T * VW) return;
     const int t = e / VW, col = e - t * VW;
-    const int np = r * (r + 1) / 2, ng16 = VW - 16;
+    const int np = mf_vech_cols(r), ng16 = mf_mean_col0(VW);
     const size_t npk = (size_t)Rk * (Rk + 1) / 2;
     const double* __restrict__ zt = a.zsm + ((size_t)b * a.T + t) * Rk;
     const double* __restrict__ Pt = a.Psm + ((size_t)b * a.T + t) * npk;
@@ -91,7 +92,7 @@ __global__ __launch_bounds__(256) void mf_moments_kernel(MfMstepArgs a, const do
                                                          double* __restrict__ SM) {
     const int b = blockIdx.y;
     if (a.active && a.active[b] == 0) return;
-    const int tile = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6);
+    const int tile = (int)blockIdx.x * kMfWaves + ((int)threadIdx.x >> 6);
     if (tile >= a.ntiles) return;
     const int lane = (int)threadIdx.x & 63, k4 = lane >> 4, c16 = lane & 15;
     const int T = a.T, N = a.N, VW = 16 * TT;
@@ -116,7 +117,7 @@ __global__ __launch_bounds__(256) void mf_moments_kernel(MfMstepArgs a, const do
             for (int x = 0; x < TT; ++x) bq[u][x] = Vb[(size_t)t * vstride + 16 * x];
         }
     };
-    const int ng = (T + 15) / 16;
+    const int ng = mf_groups(T);
     load(0);
     for (int g = 0; g < ng; ++g) {
         double xv[kMfU], bv[kMfU][TT];
@@ -172,9 +173,9 @@ __global__ __launch_bounds__(256) void mf_solve_kernel(MfMstepArgs a, const doub
     double G[R][R], Lc[R][R], bv[R], y[R];
 #pragma unroll
     for (int c = 0; c < R; ++c) {
-        bv[c] = o[VW - 16 + c];
+        bv[c] = o[mf_mean_col(VW, c)];
 #pragma unroll
-        for (int d = 0; d <= c; ++d) { G[c][d] = o[c * (c + 1) / 2 + d]; G[d][c] = G[c][d]; }
+        for (int d = 0; d <= c; ++d) { G[c][d] = o[mf_vech_col(c, d)]; G[d][c] = G[c][d]; }
     }
     bool pd = true;
 #pragma unroll
@@ -223,7 +224,7 @@ __global__ __launch_bounds__(256) void mf_solve_kernel(MfMstepArgs a, const doub
 }
 
 bool mstep_mf_supported(int r, int L) { return r >= 1 && r <= 8 && L >= 1 && L <= kMfMaxLags; }
-int mstep_mf_row_width(int r) { return 16 * ((r * (r + 1) / 2 + 15) / 16) + 16; }
+int mstep_mf_row_width(int r) { return mf_row_width(r); }
 // V [B][T][C][VW] | OUT [B][N][VW] | SM [B][2][N]
 size_t mstep_mf_workspace(int B, int T, int N, int r, int C) {
     const size_t VW = (size_t)mstep_mf_row_width(r);
@@ -232,15 +233,14 @@ size_t mstep_mf_workspace(int B, int T, int N, int r, int C) {
 
 hipError_t launch_mf_loadings(int B, int N, int r, int L, int Rk, const double* Lam, const double* W, double* LamK, hipStream_t s) {
     note_kernel("mf_loadings_kernel");
-    const size_t n = (size_t)B * N * Rk;
-    hipLaunchKernelGGL(mf_loadings_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, B, N, r, L, Rk, Lam, W, LamK);
+    hipLaunchKernelGGL(mf_loadings_kernel, dim3((unsigned)mf_loadings_blocks(B, N, Rk)), dim3(kMfBlock), 0, s, B, N, r, L, Rk, Lam, W, LamK);
     return hipGetLastError();
 }
 
 hipError_t launch_mf_table(const MfMstepArgs& a, double* ws, hipStream_t s) {
     note_kernel("mf_table_kernel");
     if (!ws || a.VW != mstep_mf_row_width(a.r) || a.C < 1 || a.C > kMfMaxClasses || a.r * a.L > a.Rk) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(mf_table_kernel, dim3((a.T * a.VW + 255) / 256, a.B), dim3(256), 0, s, a, ws);
+    hipLaunchKernelGGL(mf_table_kernel, dim3(mf_table_blocks(a.T, a.VW), a.B), dim3(kMfBlock), 0, s, a, ws);
     return hipGetLastError();
 }
 
@@ -250,8 +250,8 @@ hipError_t launch_mf_moments(const MfMstepArgs& a, double* ws, hipStream_t s) {
     const double* V = ws;
     double* OUT = ws + (size_t)a.B * a.T * a.C * a.VW;
     double* SM = OUT + (size_t)a.B * a.N * a.VW;
-    const dim3 grid((a.ntiles + 3) / 4, a.B), block(256);
-    switch (a.VW / 16) {
+    const dim3 grid(mf_moment_blocks(a.ntiles), a.B), block(kMfBlock);
+    switch (mf_row_tiles(a.VW)) {
         case 2: hipLaunchKernelGGL(mf_moments_kernel<2>, grid, block, 0, s, a, V, OUT, SM); break;
         case 3: hipLaunchKernelGGL(mf_moments_kernel<3>, grid, block, 0, s, a, V, OUT, SM); break;
         case 4: hipLaunchKernelGGL(mf_moments_kernel<4>, grid, block, 0, s, a, V, OUT, SM); break;
@@ -262,7 +262,7 @@ hipError_t launch_mf_moments(const MfMstepArgs& a, double* ws, hipStream_t s) {
 
 template <int R>
 static hipError_t launch_mf_solve_r(const MfMstepArgs& a, const double* OUT, const double* SM, hipStream_t s) {
-    hipLaunchKernelGGL(mf_solve_kernel<R>, dim3((a.N + 255) / 256, a.B), dim3(256), 0, s, a, OUT, SM);
+    hipLaunchKernelGGL(mf_solve_kernel<R>, dim3(mf_solve_blocks(a.N), a.B), dim3(kMfBlock), 0, s, a, OUT, SM);
     return hipGetLastError();
 }
 hipError_t launch_mf_solve(const MfMstepArgs& a, double* ws, hipStream_t s) {

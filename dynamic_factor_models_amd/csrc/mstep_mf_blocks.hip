@@ -9,6 +9,7 @@
 // the factor of G_FF sits in the free rows and columns, the substituted pivots are exactly 1 and the solution's fixed entries
 // exactly 0; lam_X is put back before the sums of R_i.  Only free entries of Lam are stored.
 #include "dfm_kernels.h"
+#include "dfm_mfgeom.h"
 
 namespace dfm {
 
@@ -34,11 +35,11 @@ __global__ __launch_bounds__(256) void mf_solve_blocks_kernel(MfMstepArgs a, con
     double G[R][R], Lc[R][R], bv[R], y[R], lx[R];
 #pragma unroll
     for (int c = 0; c < R; ++c) {
-        bv[c] = o[VW - 16 + c];
+        bv[c] = o[mf_mean_col(VW, c)];
         const double l = lam[c];                               // (read whole: a load under the lane's bit would split the row's loads)
         lx[c] = (fr >> c) & 1u ? 0.0 : l;                      // lam_X, zero on the free coordinates
 #pragma unroll
-        for (int d = 0; d <= c; ++d) { G[c][d] = o[c * (c + 1) / 2 + d]; G[d][c] = G[c][d]; }
+        for (int d = 0; d <= c; ++d) { G[c][d] = o[mf_vech_col(c, d)]; G[d][c] = G[c][d]; }
     }
     // the substituted system: entry (q, j) is G[q][j] where both are free, the identity elsewhere
     auto free2 = [&](int q, int j) { return ((fr >> q) & (fr >> j) & 1u) != 0u; };
@@ -97,7 +98,7 @@ __global__ __launch_bounds__(256) void mf_solve_blocks_kernel(MfMstepArgs a, con
 template <int R>
 static hipError_t launch_mf_solve_blocks_r(const MfMstepArgs& a, const unsigned char* free_mask, const double* OUT, const double* SM,
                                            hipStream_t s) {
-    hipLaunchKernelGGL(mf_solve_blocks_kernel<R>, dim3((a.N + 255) / 256, a.B), dim3(256), 0, s, a, free_mask, OUT, SM);
+    hipLaunchKernelGGL(mf_solve_blocks_kernel<R>, dim3(mf_solve_blocks(a.N), a.B), dim3(kMfBlock), 0, s, a, free_mask, OUT, SM);
     return hipGetLastError();
 }
 hipError_t launch_mf_solve_blocks(const MfMstepArgs& a, const unsigned char* free_mask, double* ws, hipStream_t s) {

@@ -742,7 +742,9 @@ int dfm_ks_pass_mf_batch(dfm_handle* h, int B, int T, int N, int r, int p, int L
  * symmetrised, mu0 / P0 = smoothed moments of z_0; (3) per series, over its n_i observed periods,
  *   G_i = sum_t E[g_it g_it'],  b_i = sum_t x_it E[g_it],  lam_i = G_i^-1 b_i,  R_i = (sum_t x_it^2 - 2 lam_i' b_i + lam_i' G_i lam_i) / n_i
  * with E[g_it] and E[g_it g_it'] read from the smoothed mean and covariance of z_t (L <= m: every lag is inside the state).  A
- * series with fewer than r + 1 observed cells keeps lam_i and R_i.  Parameters are updated in place; loglik_path [B][max_iter]
+ * series with fewer than r + 1 observed cells keeps lam_i and R_i.  So does a series whose G_i is not positive definite (its
+ * Cholesky factorisation meets a pivot <= 0: an all-zero weight row gives G_i = 0 exactly).  Parameters are updated in place;
+ * loglik_path [B][max_iter]
  * (the likelihood at the parameters ENTERING each iteration, NaN past convergence, non-decreasing), iters and tol as
  * dfm_em_batch; f_smooth / P_smooth (may be NULL): the last E-step.  The distinct rows of W (compared exactly) are the weight
  * CLASSES; the aggregated moments are tabulated once per period and class, so a panel may hold at most 8 classes (else

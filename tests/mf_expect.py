@@ -80,6 +80,10 @@ def em_step_mf(x, Lam, R, W, Avar, Q, mu0, P0):
         w = W[i]
         G = np.einsum("l,tlcmd,m->cd", w, Eb[o], w)
         b = np.einsum("l,tlc->tc", w, zb[o]).T @ x[o, i]
+        try:                                                       # a G_i that is not positive definite keeps lam_i and R_i
+            np.linalg.cholesky(G)
+        except np.linalg.LinAlgError:
+            continue
         lam = np.linalg.solve(G, b)
         Lam_new[i] = lam
         R_new[i] = ((x[o, i] ** 2).sum() - 2.0 * lam @ b + lam @ G @ lam) / n

@@ -139,6 +139,34 @@ def test_em_mf_tol_bookkeeping_and_thin_series():
     assert 2 <= len(path) < 60
 
 
+def test_a_series_whose_g_is_not_positive_definite_is_kept():
+    """An all-zero weight row makes G_i = 0 exactly (the rule of include/dfm_hip.h: dfm_em_mf_batch): the series keeps lam_i and
+    R_i, every other series and the transition step are what they are without the rule -- the zero row loads on nothing, so the
+    pass is the pass of the panel without that series -- and tests/mf_blocks_expect.py states the same rule."""
+    from tests import mf_blocks_expect as mb
+    x, W, st = me.synth_mf(3, 10, 4, 60, 2, 1, "q_avg", missing=0.05)
+    z = 4                                                        # a monthly series with every cell it had
+    assert (~np.isnan(x[:, z])).sum() >= 3
+    W0 = W.copy(); W0[z] = 0.0
+    new, ll, _ = me.em_step_mf(x, W=W0, **st)
+    assert np.array_equal(new["Lam"][z], st["Lam"][z]) and new["R"][z] == st["R"][z]
+    rest = np.arange(W.shape[0]) != z
+    sub = dict(st, Lam=st["Lam"][rest], R=st["R"][rest])
+    ref, _, _ = me.em_step_mf(x[:, rest], W=W[rest], **sub)
+    for k in KEYS:
+        got = new[k][rest] if k in ("Lam", "R") else new[k]
+        assert np.abs(got - ref[k]).max() <= 1e-12 * max(1.0, np.abs(ref[k]).max()), k
+    assert np.all(new["Lam"][rest] != st["Lam"][rest]) and np.isfinite(ll)
+    blk, _, _ = mb.em_step_mf_blocks(x, W=W0, free=np.ones_like(st["Lam"], bool), **st)
+    for k in KEYS:
+        assert np.abs(blk[k] - new[k]).max() <= 1e-12 * max(1.0, np.abs(new[k]).max()), k
+    assert np.array_equal(blk["Lam"][z], st["Lam"][z]) and blk["R"][z] == st["R"][z]
+    with pytest.raises(np.linalg.LinAlgError):                  # the model's test is the Cholesky attempt: a zero pivot fails it
+        np.linalg.cholesky(np.zeros((2, 2)))
+    _, path, _ = me.em_mf(x, st, W0, max_iter=4)
+    assert np.all(np.diff(path) >= 0.0)
+
+
 # ---- the C interface, stated three times -------------------------------------------------------------------------------------
 def test_header_ctypes_table_and_julia_ccalls_agree():
     from dynamic_factor_models_amd import _lib
