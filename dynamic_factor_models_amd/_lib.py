@@ -47,6 +47,7 @@ _GB_ARGS = ([c_vp] + [c_int] * 5 + [c_vp] * 7 + [ctypes.c_double] * 6 + [c_vp] +
 _GBAR_ARGS = ([c_vp] + [c_int] * 6 + [c_vp] * 8 + [ctypes.c_double] * 7 + [c_vp] + [c_int] * 3
               + [ctypes.c_uint64, ctypes.c_int64] + [c_vp] * 6 + [c_uint])
 _NW_ARGS = [c_vp] + [c_int] * 5 + [c_vp] * 10 + [c_int] + [c_vp] * 6 + [c_uint]
+_NWAR_ARGS = [c_vp] + [c_int] * 6 + [c_vp] * 12 + [c_int] + [c_vp] * 6 + [c_uint]
 _IRF_ARGS = [c_vp] + [c_int] * 5 + [c_vp] * 9 + [c_uint]
 _SG_ARGS = ([c_vp] + [c_int] * 5 + [c_vp] * 7 + [c_int, c_vp, c_int, c_int, ctypes.c_uint64, ctypes.c_int64] + [c_vp] * 6
             + [c_uint])
@@ -137,6 +138,8 @@ SYMBOLS = {
     "dfm_simsmooth_ar_batch": (c_int, _SSAR_ARGS),
     "dfm_gibbs_ar_batch_dev": (c_int, _GBAR_ARGS),
     "dfm_gibbs_ar_batch": (c_int, _GBAR_ARGS),
+    "dfm_news_ar_batch_dev": (c_int, _NWAR_ARGS),
+    "dfm_news_ar_batch": (c_int, _NWAR_ARGS),
     "dfm_ks_pass_mf_batch_dev": (c_int, _MFPASS_ARGS),
     "dfm_ks_pass_mf_batch": (c_int, _MFPASS_ARGS),
     "dfm_em_mf_batch_dev": (c_int, _MFEM_ARGS),

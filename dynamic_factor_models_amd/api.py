@@ -1213,7 +1213,7 @@ def news(m: DFMModel, old, new, targets, *, groups=None, quantiles=None, ctx=Non
                 raise ValueError(f"groups[{name!r}] must list columns estimate() used")
             gsum[name] = np.asarray(idx)
     if np.any(np.nan_to_num(np.asarray(m.uar_coef, dtype=np.float64)[cols]) != 0.0):
-        raise ValueError("news has no AR idiosyncratic terms: the model carries uar_coef (estimate_ar_idio?)")
+        raise ValueError("news has no AR idiosyncratic terms: the model carries uar_coef (news_ar_idio is the call for it)")
     qs = None
     if quantiles is not None:
         qs = np.atleast_1d(np.asarray(quantiles, dtype=np.float64))
@@ -2324,6 +2324,125 @@ def evaluate_forecasts_ar_idio(m: DFMModel, H: int, *, first_origin: Optional[in
                    relative=msfe / msfe0, count=o["cnt"][0])
     if bands is not None:
         out["quantiles"], out["bands"], out["gain_bands"] = qs, bands, gbands
+    return out
+
+
+def news_ar_idio(m: DFMModel, old, new, targets, *, groups=None, params=None, quantiles=None, ctx=None) -> dict:
+    """News decomposition of the revision of nowcasts / forecasts between two data vintages from the model with AR(n_uarlag)
+    idiosyncratic terms: what `news` gives for the parametric fit, with the effect of a release on its OWN series' nowcast through
+    the idiosyncratic persistence kept.  After `estimate(m, NonParametric())`, optionally `estimate_ar_idio(m)`.
+
+    `old` / `new` / `targets` / `groups` as in `news`; units, v0 and mean as in `forecast_ar_idio`; parameters, c_i and mu_f come from
+    the estimation window, the vintages cover rows initperiod .. their last row.  The vintages must be EDGE-SHAPED on the series
+    used: each series observed on window rows 0 .. L with no gap, L >= 2 n_uarlag - 1 in old, old's cells a subset of new's.  Any
+    other pattern is a ValueError that names the first offending column and the condition it breaks (drop that series, or trim the
+    rows): with an interior gap the decomposition would not add up.  The first n_uarlag window rows are
+    conditioning values: a target there is refused, a revision there moves y_rev - y_old and has no weight.
+    `params`: the dict of `estimate_bayesian_ar_idio` (S parameter sets); each runs as one replicate of the same
+    dfm_news_ar_batch call, behind the point estimate, and with `quantiles` nearest-rank bands over them give impact_bands
+    [nq, G, cols] and revision_bands [nq, G].  Returns the keys of `news` (data units) with rows = initperiod + n_uarlag .. the
+    last row of the vintages, and inputs (the arrays handed to the library: old, new, the parameters, v0, mean, sd, targets).
+    `m` is not modified."""
+    from . import news_ar as _na
+    q = int(m.n_uarlag)
+    if not (1 <= q <= 4):
+        raise ValueError("news_ar_idio needs 1 <= n_uarlag <= 4")
+    ncol = m.data.shape[1]
+
+    def vintage(v, name):
+        if np.isscalar(v) and float(v) == int(v):
+            t = int(v)
+            if not (m.initperiod <= t <= m.T):
+                raise ValueError(f"{name} vintage: through must lie in initperiod..T ({m.initperiod}..{m.T})")
+            return np.asarray(m.data[:t], dtype=np.float64)
+        x = np.asarray(v, dtype=np.float64)
+        if x.ndim != 2 or x.shape[1] != ncol or x.shape[0] < m.initperiod:
+            raise ValueError(f"{name} vintage: an array shaped like m.data ([rows >= initperiod, {ncol}]) or a 1-based row")
+        return x
+    xo, xn = vintage(old, "old"), vintage(new, "new")
+    last = max(xo.shape[0], xn.shape[0])
+    padr = lambda x: np.vstack([x, np.full((last - x.shape[0], ncol), np.nan)])
+    xo, xn = padr(xo), padr(xn)
+    tg = list(targets) if targets is not None else []
+    if len(tg) < 1:
+        raise ValueError("at least one target (column, period) is needed")
+    inputs, cols, mu_f, c_i = _ar_model_inputs(m)
+    pos = {int(c): j for j, c in enumerate(cols)}
+    pairs = []
+    for c, per in tg:
+        if int(c) not in pos:
+            raise ValueError(f"target column {c} is not one of the series the model uses")
+        if int(per) < m.initperiod + q:
+            raise ValueError(f"target period {per} lies before initperiod + n_uarlag ({m.initperiod + q}): the first n_uarlag "
+                             "window rows are conditioning values")
+        pairs.append((int(per) - m.initperiod, pos[int(c)]))
+    gsum = None
+    if groups is not None:
+        gsum = {}
+        for name, gc in dict(groups).items():
+            idx = [pos.get(int(c), -1) for c in np.atleast_1d(gc)]
+            if len(idx) < 1 or min(idx) < 0:
+                raise ValueError(f"groups[{name!r}] must list columns the model uses")
+            gsum[name] = np.asarray(idx)
+    sets = [inputs[k][None] for k in _AR_PARAM_NAMES]
+    if params is not None:
+        lost = [k for k in _AR_PARAM_NAMES if k not in params]
+        if lost:
+            raise ValueError(f"params lacks {lost}")
+        extra = [np.ascontiguousarray(params[k], dtype=np.float64) for k in _AR_PARAM_NAMES]
+        S = extra[0].shape[0] if extra[0].ndim == 3 else 0
+        for k, a in zip(_AR_PARAM_NAMES, extra):
+            if S < 1 or a.shape != (S,) + inputs[k].shape:
+                raise ValueError(f"params[{k!r}] must be [S, ...] with the model's own shape {inputs[k].shape} behind S >= 1")
+        sets = [np.concatenate([a, b]) for a, b in zip(sets, extra)]    # replicate 0: the point estimate
+    qs = None
+    if quantiles is not None:
+        qs = np.atleast_1d(np.asarray(quantiles, dtype=np.float64))
+        if params is None:
+            raise ValueError("quantile bands need parameter sets: params=estimate_bayesian_ar_idio(m, ...)['params']")
+        if qs.size < 1 or not np.all((qs > 0.0) & (qs <= 1.0)):
+            raise ValueError("quantiles must lie in (0, 1]")
+        if sets[0].shape[0] - 1 > _QUANTILE_MAX_DRAWS:
+            raise ValueError(f"bands need at most {_QUANTILE_MAX_DRAWS} parameter sets")
+    mean = c_i + inputs["Lam"] @ mu_f
+    zo, zn = xo[m.initperiod - 1:, cols] - mean, xn[m.initperiod - 1:, cols] - mean
+    _na.check_args(zn.shape[0], q, pairs)
+    why = _na.edge_shape_error(zo, zn, q, cols=cols)
+    if why is not None:
+        raise ValueError("vintage: " + why)
+    win = slice(m.initperiod - 1, m.lastperiod)
+    v0 = np.nanvar(m.data[win][:, cols] - c_i - m.factor[win] @ inputs["Lam"].T, axis=0)
+    B = sets[0].shape[0]
+    rep = lambda a: np.ascontiguousarray(np.broadcast_to(a, (B,) + a.shape))
+    sd = np.ones(cols.size)
+    from ._lib import DfmError
+    ctx, own = _own(ctx)
+    try:
+        args = (rep(zo), rep(zn), *sets, pairs)
+        kw = dict(v0=rep(v0), mean=rep(mean), sd=rep(sd), may_have_missing=bool(np.isnan(zn).any()))
+        try:
+            o = ctx.news_ar_batch_host(*args, **kw)
+        except DfmError as err:                     # the information form inverts Q: as estimate(), retry in covariance form
+            if err.code != -5:
+                raise
+            o = ctx.news_ar_batch_host(*args, singular_q=True, **kw)
+        bands = None
+        if qs is not None:
+            bands = (ctx.quantile_bands_host(o["impact"][1:], qs),
+                     ctx.quantile_bands_host(o["yhat"][1:, 2] - o["yhat"][1:, 0], qs))
+    finally:
+        if own:
+            ctx.close()
+    y = o["yhat"][0]
+    out = dict(rows=np.arange(m.initperiod + q, last + 1), cols=cols, y_old=y[0], y_rev=y[1], y_new=y[2], revision=y[2] - y[0],
+               data_revision=y[1] - y[0], news_effect=y[2] - y[1], impact=o["impact"][0], news=o["news"][0],
+               weight=o["weight"][0],
+               inputs=dict({k: a[0] for k, a in zip(_AR_PARAM_NAMES, sets)}, old=zo, new=zn, v0=v0, mean=mean, sd=sd, targets=pairs))
+    if gsum is not None:
+        out["groups"] = {name: out["impact"][:, idx].sum(axis=1) for name, idx in gsum.items()}
+    if bands is not None:
+        out["quantiles"] = qs
+        out["impact_bands"], out["revision_bands"] = bands
     return out
 
 

@@ -163,6 +163,8 @@ struct dfm_handle {
                                            // dfm_simsmooth_ar_batch_dev: the same, the difference panels always, one slice's messages
     DevBlock nw;                           // dfm_news_batch_dev: targets, the revised old panel, one forecast's xhat, the slice's pass
                                            // parameters, u / a vectors, smoothed means and (no weight) covariance panels
+                                           // dfm_news_ar_batch_dev: the same on the output rows of the AR forecasts, with rho,
+                                           // the u / d vectors of news_ar_rec_kernel and the whole smoothed state of the slice
     DevBlock sv;                           // dfm_irf_batch_dev / dfm_histdecomp_batch_dev: named / cum, S, S^-1, the Theta tables, shocks and
                                            // contribution paths, and the pass outputs the caller does not take; dfm_signirf_batch_dev:
                                            // the restrictions, their table, mask, counts, rotations and the kept slots' tables;
@@ -186,11 +188,11 @@ struct dfm_handle {
 };
 
 enum KernelId { K_COLLAPSE = 0, K_RECURSION, K_MSTEP_STATS, K_MSTEP_SOLVE, K_PCA, K_SYNTH, K_PAD,
-                K_COLLAPSE_DMA, K_GRAM, K_COV, K_MEANSCAN, K_PFILL, K_COLLAPSE_MFMA, K_ALS, K_OLS, K_BOOT, K_QUANT, K_COLLAPSE_WIDE, K_EM_UPDATE, K_CHOW, K_MSTEP_MFMA, K_GRAM_XX, K_PASS_FUSED, K_FC_TAIL, K_FC_FILL, K_FC_PAD, K_SS_PREP, K_SS_EXPAND, K_SS_PATH, K_SS_DIFF, K_SS_FINISH, K_SS_FILL, K_NW_REVISE, K_NW_GATHER, K_NW_GAMMA, K_NW_COV, K_NW_IMPACT, K_MF_TABLE, K_MF_MOMENTS, K_MF_SOLVE, K_SV_PREP, K_SV_IRF_FILL, K_SV_SHOCK, K_SV_PATH, K_SV_HD_FILL, K_FT_FILTER, K_FT_FILL, K_FT_EVAL, K_GB_GRAM, K_GB_LOAD, K_GB_VAR, K_SV_SIGN_TABLE, K_SV_SIGN, K_SV_SIGN_KEEP, K_PX_ROWS, K_PX_MOMENT, K_PX_SLOT_TABLE, K_PX_DEN, K_PX_FILL, K_PX_SHOCK, K_MF_SOLVE_BLOCKS, K_FCAR_BACK, K_FCAR_FWD, K_SSAR_PARAMS, K_SSAR_EXPAND, K_SSAR_DIFF, K_SSAR_FWD, K_SSAR_FINISH, K_GB_AR_SERIES, K_FTAR_FILTER, K_FTAR_FILL, K_FTAR_EVAL, K_COUNT };
+                K_COLLAPSE_DMA, K_GRAM, K_COV, K_MEANSCAN, K_PFILL, K_COLLAPSE_MFMA, K_ALS, K_OLS, K_BOOT, K_QUANT, K_COLLAPSE_WIDE, K_EM_UPDATE, K_CHOW, K_MSTEP_MFMA, K_GRAM_XX, K_PASS_FUSED, K_FC_TAIL, K_FC_FILL, K_FC_PAD, K_SS_PREP, K_SS_EXPAND, K_SS_PATH, K_SS_DIFF, K_SS_FINISH, K_SS_FILL, K_NW_REVISE, K_NW_GATHER, K_NW_GAMMA, K_NW_COV, K_NW_IMPACT, K_MF_TABLE, K_MF_MOMENTS, K_MF_SOLVE, K_SV_PREP, K_SV_IRF_FILL, K_SV_SHOCK, K_SV_PATH, K_SV_HD_FILL, K_FT_FILTER, K_FT_FILL, K_FT_EVAL, K_GB_GRAM, K_GB_LOAD, K_GB_VAR, K_SV_SIGN_TABLE, K_SV_SIGN, K_SV_SIGN_KEEP, K_PX_ROWS, K_PX_MOMENT, K_PX_SLOT_TABLE, K_PX_DEN, K_PX_FILL, K_PX_SHOCK, K_MF_SOLVE_BLOCKS, K_FCAR_BACK, K_FCAR_FWD, K_SSAR_PARAMS, K_SSAR_EXPAND, K_SSAR_DIFF, K_SSAR_FWD, K_SSAR_FINISH, K_GB_AR_SERIES, K_FTAR_FILTER, K_FTAR_FILL, K_FTAR_EVAL, K_NWAR_REVISE, K_NWAR_REC, K_NWAR_QC, K_NWAR_IMPACT, K_COUNT };
 static const char* const kKernelNames[K_COUNT] = {"collapse_kernel", "recursion_kernel", "mstep_lam_kernel",
                                                   "mstep_solve_kernel", "pca_kernel", "synth_kernel",
                                                   "pad_params_kernel", "collapse_dma_kernel", "gram_kernel",
-                                                  "cov_kernel", "meanscan_kernel", "pfill_kernel", "collapse_mfma_kernel", "als_kernel", "ols_kernel", "var_boot_kernel", "quantile_kernel", "collapse_wide_kernel", "em_update_kernel", "chow_kernel", "mstep_mfma_kernel", "gram_xx_kernel", "pass_fused_kernel", "forecast_tail_kernel", "forecast_fill_kernel", "forecast_pad_kernel", "simsmooth_prep_kernel", "simsmooth_expand_kernel", "simsmooth_path_kernel", "simsmooth_diff_kernel", "simsmooth_finish_kernel", "simsmooth_fill_kernel", "news_revise_kernel", "news_gather_kernel", "news_gamma_kernel", "news_cov_panel_kernel", "news_impact_kernel", "mf_table_kernel", "mf_moments_kernel", "mf_solve_kernel", "sv_prep_kernel", "sv_irf_fill_kernel", "sv_shock_kernel", "sv_path_kernel", "sv_hd_fill_kernel", "filter_kernel", "filter_fill_kernel", "filter_eval_kernel", "gibbs_gram_kernel", "gibbs_load_kernel", "gibbs_var_kernel", "sv_sign_table_kernel", "sv_sign_kernel", "sv_sign_keep_kernel", "px_rows_kernel", "px_moment_kernel", "px_slot_table_kernel", "px_den_kernel", "px_fill_kernel", "px_shock_kernel", "mf_solve_blocks_kernel", "forecast_ar_back_kernel", "forecast_ar_fwd_kernel", "simsmooth_ar_params_kernel", "simsmooth_ar_expand_kernel", "simsmooth_ar_diff_kernel", "simsmooth_ar_fwd_kernel", "simsmooth_ar_finish_kernel", "gibbs_ar_series_kernel", "filter_ar_kernel", "filter_ar_fill_kernel", "filter_ar_eval_kernel"};
+                                                  "cov_kernel", "meanscan_kernel", "pfill_kernel", "collapse_mfma_kernel", "als_kernel", "ols_kernel", "var_boot_kernel", "quantile_kernel", "collapse_wide_kernel", "em_update_kernel", "chow_kernel", "mstep_mfma_kernel", "gram_xx_kernel", "pass_fused_kernel", "forecast_tail_kernel", "forecast_fill_kernel", "forecast_pad_kernel", "simsmooth_prep_kernel", "simsmooth_expand_kernel", "simsmooth_path_kernel", "simsmooth_diff_kernel", "simsmooth_finish_kernel", "simsmooth_fill_kernel", "news_revise_kernel", "news_gather_kernel", "news_gamma_kernel", "news_cov_panel_kernel", "news_impact_kernel", "mf_table_kernel", "mf_moments_kernel", "mf_solve_kernel", "sv_prep_kernel", "sv_irf_fill_kernel", "sv_shock_kernel", "sv_path_kernel", "sv_hd_fill_kernel", "filter_kernel", "filter_fill_kernel", "filter_eval_kernel", "gibbs_gram_kernel", "gibbs_load_kernel", "gibbs_var_kernel", "sv_sign_table_kernel", "sv_sign_kernel", "sv_sign_keep_kernel", "px_rows_kernel", "px_moment_kernel", "px_slot_table_kernel", "px_den_kernel", "px_fill_kernel", "px_shock_kernel", "mf_solve_blocks_kernel", "forecast_ar_back_kernel", "forecast_ar_fwd_kernel", "simsmooth_ar_params_kernel", "simsmooth_ar_expand_kernel", "simsmooth_ar_diff_kernel", "simsmooth_ar_fwd_kernel", "simsmooth_ar_finish_kernel", "gibbs_ar_series_kernel", "filter_ar_kernel", "filter_ar_fill_kernel", "filter_ar_eval_kernel", "news_ar_revise_kernel", "news_ar_rec_kernel", "news_ar_qc_kernel", "news_ar_impact_kernel"};
 
 namespace dfm { int handle_device(const dfm_handle* h) { return h->device; } }   // (probe.hip)
 
@@ -3594,6 +3596,179 @@ int dfm_news_batch(dfm_handle* h, int B, int T, int N, int r, int p, const doubl
     if (int rc = st.begin()) return rc;
     int rc = st.finish(news_run(h, B, T, N, r, p, H, xo_d, xn_d, lam_d, R_d, A_d, Q_d, mu_d, P0_d, mean_d, sd_d, G, target_t, target_i, y_d,
                                 imp_d, news_d, w_d, ll_d, flags));
+    if (rc == 0) rc = post_check(h, ll_host.data(), (int)n_ll);
+    return rc;
+}
+
+// ---- news decomposition with AR idiosyncratic terms (news_ar.hip) ------------------------------------------------------------------
+// As news_run, on the output rows of dfm_forecast_ar_batch_dev: the vintage check and the revised old panel, the three forecasts
+// (old, new, then the revised old panel, whose xhat stays in h->nw for the news), then the B G weight passes in slices of at most
+// kNwSlice pass replicates j = b G + g.  A slice: expand the parameters (mu0 = 0; the state has m = max(p, q + 1) lags, Avar padded
+// with zero blocks), the u / Gamma recursion, the covariance panels -- which ARE quasi-differenced cells -- the inner part of the AR
+// pass over them (no quasi_diff_kernel) with the whole smoothed state kept (the rows t < q need E[f_{t-l}] before output row 0),
+// the impacts.  With weight the covariance panels of a slice live in that slice's part of weight.
+static int news_ar_check(dfm_handle* h, int B, int T, int N, int r, int p, int q, const double* oldp, const double* newp,
+                         const double* Lam, const double* sig2, const double* rho, const double* Avar, const double* Q,
+                         const double* mu0, const double* P0, const double* mean, const double* sd, int G, const int* target_t,
+                         const int* target_i, const double* yhat, const double* impact, int* H) {
+    if (int rc = check_dims(h, B, T, N, r)) return rc;
+    if (G < 1) return fail(h, DFM_E_DIMS, "G (targets) must be >= 1%s");
+    if (p < 1) return fail(h, DFM_E_DIMS, "number of factor lags must be >= 1%s");
+    if (q < 1) return fail(h, DFM_E_DIMS, "number of idiosyncratic lags must be >= 1 (q = 0 is dfm_news_batch)%s");
+    if (q > 4) return fail(h, DFM_E_R_UNSUPPORTED, "news with AR idiosyncratic terms needs q <= 4%s");
+    if (T <= 2 * q) return fail(h, DFM_E_DIMS, "T must exceed 2 q (q conditioning rows, q rows that fix the idiosyncratic state)%s");
+    if ((long long)B * G > 0x7fffffffLL) return fail(h, DFM_E_DIMS, "B * G must be < 2^31%s");
+    if (!oldp || !newp || !Lam || !sig2 || !rho || !Avar || !Q || !mu0 || !P0 || !target_t || !target_i || !yhat || !impact)
+        return fail(h, DFM_E_NULL, "required pointer is NULL%s");
+    if ((mean == nullptr) != (sd == nullptr)) return fail(h, DFM_E_NULL, "mean and sd must both be given or both be NULL%s");
+    int tmax = 0;
+    for (int g = 0; g < G; ++g) {
+        if (target_t[g] < q || target_t[g] > 0x3fffffff || target_i[g] < 0 || target_i[g] >= N)
+            return fail(h, DFM_E_DIMS, "a target lies outside [q, T + H) x [0, N)%s");
+        if (target_t[g] > tmax) tmax = target_t[g];
+    }
+    *H = tmax + 1 > T ? tmax + 1 - T : 0;
+    return ar_check(h, B, T + *H, N, r, p, q, false);
+}
+
+// The AR pass's inner part over S panels of ns rows that are quasi-differenced already; g [S][ns][Rp] takes the whole smoothed
+// state (out_r = Rp, as ar_em_run takes it).  ar_plan's room for a quasi-differenced panel stays unused.
+static int news_ar_pass(dfm_handle* h, int S, int ns, int N, int r, int m, int q, const double* qc, const double* Lam,
+                        const double* sig2, const double* rho, const double* Avar, const double* Q, const double* mu0,
+                        const double* P0, double* g, double* ll, unsigned flags) {
+    ArPlan s;
+    if (int rc = ar_plan(h, S, ns + q, N, r, m, q, flags, false, &s)) return rc;
+    if (int rc = launch_1d(h, ar_loadings_kernel, (size_t)S * N * s.p.Rp, S, N, r, q, s.p.Rp, Lam, rho, s.mb.Lam)) return rc;
+    if (int rc = companion_pad(h, s.p, S, N, r, s.k, r * m, nullptr, Avar, Q, mu0, P0, s.mb)) return rc;
+    return enqueue_pass(h, s.p, S, ns, N, s.p.Rp, qc, s.mb.pp(), sig2, g, nullptr, ll, nullptr);
+}
+
+// ll_all: [3 B + B G] device log-likelihoods (the three forecasts, then the weight passes; the host entry checks them), or null
+static int news_ar_run(dfm_handle* h, int B, int T, int N, int r, int p, int q, int H, const double* oldp, const double* newp,
+                       const double* Lam, const double* sig2, const double* rho, const double* Avar, const double* Q,
+                       const double* mu0, const double* P0, const double* v0, const double* mean, const double* sd, int G,
+                       const int* target_t, const int* target_i, double* yhat, double* impact, double* news, double* weight,
+                       double* ll_all, unsigned flags) {
+    HIP_TRY(h, hipSetDevice(h->device));
+    const int m = p > q + 1 ? p : q + 1, Rp = pad_r(r * m), w = (q + 1) * r;
+    const size_t d = sizeof(double), k = (size_t)r * m, TH = (size_t)T + H, n = TH - q, ns = (size_t)T - q;
+    const long long BG = (long long)B * G;
+    const int Smax = (int)(BG < kNwSlice ? BG : kNwSlice);
+    size_t off = 0;
+    const size_t o_t = take(off, (size_t)2 * G * sizeof(int)), o_rev = take(off, (size_t)B * T * N * d),
+                 o_x = take(off, (size_t)B * n * N * d), o_f = take(off, (size_t)B * n * r * d),
+                 o_Ap = p < m ? take(off, (size_t)B * r * k * d) : (size_t)-1,
+                 o_L = take(off, (size_t)Smax * N * r * d), o_R = take(off, (size_t)Smax * N * d),
+                 o_rho = take(off, (size_t)Smax * N * q * d), o_A = take(off, (size_t)Smax * r * k * d),
+                 o_Q = take(off, (size_t)Smax * r * r * d), o_m = take(off, (size_t)Smax * k * d),
+                 o_P = take(off, (size_t)Smax * k * k * d), o_u = take(off, (size_t)Smax * ns * (k + 1) * d),
+                 o_dv = take(off, (size_t)Smax * ns * (w + 1) * d), o_g = take(off, (size_t)Smax * ns * Rp * d),
+                 o_ll = ll_all ? (size_t)-1 : take(off, (size_t)(B > Smax ? B : Smax) * d),
+                 o_c = weight ? (size_t)-1 : take(off, (size_t)Smax * ns * N * d);
+    HIP_TRY(h, h->nw.grow(off));
+    int* tgt = at<int>(h->nw, o_t);
+    {
+        std::vector<int> tg((size_t)2 * G);                   // (a pageable source: staged before the call returns); output rows
+        for (int g = 0; g < G; ++g) { tg[2 * g] = target_t[g] - q; tg[2 * g + 1] = target_i[g]; }
+        HIP_TRY(h, hipMemcpyAsync(tgt, tg.data(), tg.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    }
+    NwArArgs a{};
+    a.B = B; a.T = T; a.N = N; a.r = r; a.q = q; a.k = (int)k; a.ka = r * p; a.G = G; a.n = (int)n; a.ns = (int)ns; a.Rp = Rp;
+    a.oldp = oldp; a.newp = newp; a.Lam = Lam; a.sig2 = sig2; a.rho = rho; a.A = Avar; a.Q = Q; a.P0 = P0; a.mean = mean; a.sd = sd;
+    a.tgt = tgt; a.rev = at<double>(h->nw, o_rev); a.xrev = at<double>(h->nw, o_x); a.impact = impact; a.news = news; a.weight = weight;
+    a.status = h->status_dev; a.u = at<double>(h->nw, o_u); a.dv = at<double>(h->nw, o_dv); a.g = at<double>(h->nw, o_g);
+    {
+        ProfScope ps(h, K_NWAR_REVISE);
+        HIP_TRY(h, launch_news_ar_revise(a, h->stream));
+    }
+    NwArgs ga{};                                              // news_gather_kernel on the forecasts' n output rows
+    ga.B = B; ga.G = G; ga.N = N; ga.TH = (int)n; ga.tgt = tgt; ga.yhat = yhat;
+    // old, new, revised old: the last one's xhat stays in o_x for the news
+    const struct { const double* panel; unsigned fl; int which; } runs[3] = {
+        {oldp, flags | DFM_F_MAY_HAVE_MISSING, 0}, {newp, flags, 2}, {a.rev, flags | DFM_F_MAY_HAVE_MISSING, 1}};
+    for (const auto& run : runs) {
+        double* ll = ll_all ? ll_all + (size_t)run.which * B : at<double>(h->nw, o_ll);
+        if (int rc = dfm_forecast_ar_batch_dev(h, B, T, N, r, p, q, H, run.panel, Lam, sig2, rho, Avar, Q, mu0, P0, v0, mean, sd,
+                                               at<double>(h->nw, o_x), nullptr, nullptr, nullptr, at<double>(h->nw, o_f), nullptr, ll,
+                                               run.fl)) return rc;
+        ProfScope ps(h, K_NW_GATHER);
+        HIP_TRY(h, launch_news_gather(ga, at<double>(h->nw, o_x), run.which, h->stream));
+    }
+    const double* Am = Avar;
+    if (p < m) {
+        ProfScope ps(h, K_SSAR_PARAMS);
+        HIP_TRY(h, launch_simsmooth_ar_params(B, r, p, m, Avar, at<double>(h->nw, o_Ap), h->stream));
+        Am = at<double>(h->nw, o_Ap);
+    }
+    SsArgs e{};
+    e.B = B; e.D = G; e.T = (int)ns; e.N = N; e.r = r; e.p = m;
+    e.Lam = Lam; e.R = sig2; e.A = Am; e.Q = Q; e.mu0 = mu0; e.P0 = P0;
+    e.eLam = at<double>(h->nw, o_L); e.eR = at<double>(h->nw, o_R); e.eA = at<double>(h->nw, o_A); e.eQ = at<double>(h->nw, o_Q); e.emu0 = at<double>(h->nw, o_m); e.eP0 = at<double>(h->nw, o_P);
+    double* erho = at<double>(h->nw, o_rho);
+    for (long long j0 = 0; j0 < BG; j0 += Smax) {
+        const int S = (int)(BG - j0 < Smax ? BG - j0 : Smax);
+        a.j0 = j0; a.S = S; e.j0 = j0; e.S = S;
+        a.qc = weight ? weight + (size_t)j0 * ns * N : at<double>(h->nw, o_c);
+        double* ll = ll_all ? ll_all + (size_t)3 * B + j0 : at<double>(h->nw, o_ll);
+        {
+            ProfScope ps(h, K_SS_EXPAND);
+            HIP_TRY(h, launch_simsmooth_expand(e, h->stream));
+        }
+        {
+            ProfScope ps(h, K_SSAR_EXPAND);
+            HIP_TRY(h, launch_simsmooth_ar_expand(S, j0, G, (size_t)N * q, rho, erho, h->stream));
+        }
+        {
+            ProfScope ps(h, K_NWAR_REC);
+            HIP_TRY(h, launch_news_ar_rec(a, h->stream));
+        }
+        {
+            ProfScope ps(h, K_NWAR_QC);
+            HIP_TRY(h, launch_news_ar_qc(a, h->stream));
+        }
+        if (int rc = news_ar_pass(h, S, (int)ns, N, r, m, q, a.qc, e.eLam, e.eR, erho, e.eA, e.eQ, e.emu0, e.eP0, at<double>(h->nw, o_g), ll,
+                                  flags)) return rc;
+        ProfScope ps(h, K_NWAR_IMPACT);
+        HIP_TRY(h, launch_news_ar_impact(a, h->stream));
+    }
+    return 0;
+}
+
+int dfm_news_ar_batch_dev(dfm_handle* h, int B, int T, int N, int r, int p, int q, const double* old_panel, const double* new_panel,
+                          const double* Lam, const double* sig2, const double* rho, const double* Avar, const double* Q,
+                          const double* mu0, const double* P0, const double* v0, const double* mean, const double* sd, int G,
+                          const int* target_t, const int* target_i, double* yhat, double* impact, double* news, double* weight,
+                          unsigned flags) {
+    int H = 0;
+    if (int rc = news_ar_check(h, B, T, N, r, p, q, old_panel, new_panel, Lam, sig2, rho, Avar, Q, mu0, P0, mean, sd, G, target_t,
+                               target_i, yhat, impact, &H)) return rc;
+    return news_ar_run(h, B, T, N, r, p, q, H, old_panel, new_panel, Lam, sig2, rho, Avar, Q, mu0, P0, v0, mean, sd, G, target_t,
+                       target_i, yhat, impact, news, weight, nullptr, flags);
+}
+
+int dfm_news_ar_batch(dfm_handle* h, int B, int T, int N, int r, int p, int q, const double* old_panel, const double* new_panel,
+                      const double* Lam, const double* sig2, const double* rho, const double* Avar, const double* Q,
+                      const double* mu0, const double* P0, const double* v0, const double* mean, const double* sd, int G,
+                      const int* target_t, const int* target_i, double* yhat, double* impact, double* news, double* weight,
+                      unsigned flags) {
+    int H = 0;
+    if (int rc = news_ar_check(h, B, T, N, r, p, q, old_panel, new_panel, Lam, sig2, rho, Avar, Q, mu0, P0, mean, sd, G, target_t,
+                               target_i, yhat, impact, &H)) return rc;
+    if (int rc = status_epoch(h)) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t m = (size_t)(p > q + 1 ? p : q + 1), k = (size_t)r * m, BG = (size_t)B * G, n_panel = (size_t)B * T * N,
+                 n_R = (size_t)B * N, n_s = (size_t)B * (T - q) * N, n_ll = (size_t)3 * B + BG;
+    std::vector<double> ll_host(n_ll);
+    HostStage st(h, 256);
+    double *xo_d, *xn_d, *lam_d, *R_d, *rho_d, *A_d, *Q_d, *mu_d, *P0_d, *v0_d, *mean_d, *sd_d, *y_d, *imp_d, *news_d, *w_d, *ll_d;
+    st.in(old_panel, n_panel, xo_d); st.in(new_panel, n_panel, xn_d); st.in(Lam, n_R * r, lam_d); st.in(sig2, n_R, R_d);
+    st.in(rho, n_R * q, rho_d); st.in(Avar, (size_t)B * r * r * p, A_d); st.in(Q, (size_t)B * r * r, Q_d); st.in(mu0, (size_t)B * k, mu_d);
+    st.in(P0, (size_t)B * k * k, P0_d); st.in(v0, v0 ? n_R : 0, v0_d); st.in(mean, mean ? n_R : 0, mean_d); st.in(sd, sd ? n_R : 0, sd_d);
+    st.out(yhat, (size_t)B * 3 * G, y_d); st.out(impact, BG * N, imp_d); st.out(news, news ? n_s : 0, news_d);
+    st.out(weight, weight ? (size_t)G * n_s : 0, w_d); st.out(ll_host.data(), n_ll, ll_d);
+    if (int rc = st.begin()) return rc;
+    int rc = st.finish(news_ar_run(h, B, T, N, r, p, q, H, xo_d, xn_d, lam_d, R_d, rho_d, A_d, Q_d, mu_d, P0_d, v0_d, mean_d, sd_d, G,
+                                   target_t, target_i, y_d, imp_d, news_d, w_d, ll_d, flags));
     if (rc == 0) rc = post_check(h, ll_host.data(), (int)n_ll);
     return rc;
 }

@@ -592,6 +592,33 @@ hipError_t launch_news_gamma(const NwArgs& a, hipStream_t s);
 hipError_t launch_news_cov_panel(NwArgs a, hipStream_t s);
 hipError_t launch_news_impact(NwArgs a, hipStream_t s);
 
+// The same for the model with AR(q) idiosyncratic terms (news_ar.hip).  Rows are output rows t = 0 .. (panel rows q ..), as in
+// FcArArgs: ns = T - q of them in the sample, n = T + H - q in the forecasts; the state is k = r max(p, q + 1) wide.
+struct NwArArgs {
+    int B, T, N, r, q, k, ka, G, n, ns, Rp;       // ka = r p: columns of A; Rp: row stride of g (the pass's padded state)
+    const double* oldp; const double* newp;       // [B][T][N] (NaN = missing)
+    const double* Lam; const double* sig2; const double* rho;   // [B][N][r], [B][N], [B][N][q]
+    const double* A; const double* Q; const double* P0;         // [B][r][ka], [B][r][r], [B][k][k]
+    const double* mean; const double* sd;         // [B][N] or both null
+    const int* tgt;                               // device [G][2] = (t* - q, i*): the target's OUTPUT row and series
+    double* rev;                                  // [B][T][N] revised old panel
+    const double* xrev;                           // [B][n][N] xhat of the revised-old run
+    double* impact;                               // [B][G][N]
+    double* news;                                 // [B][ns][N] or null
+    double* weight;                               // [B][G][ns][N] or null
+    int* status;                                  // bit 8: a vintage is not edge-shaped, or a cell of old is missing in new
+    long long j0; int S;                          // the slice
+    double* u;                                    // [S][ns][k + 1] u_t and psi_{t* - t} of the rows t <= min(t*, ns - 1)
+    double* dv;                                   // [S][ns][(q + 1) r + 1] d_t on the observed lag blocks, psi_{t* - t} (0 behind t*)
+    double* qc;                                   // [S][ns][N] covariance panels (may alias the slice's part of weight)
+    const double* g;                              // [S][ns][Rp] E_0[z | qc] of the covariance panels
+    CellGeom geo;                                 // geometry of the cell kernels (set by their launchers)
+};
+hipError_t launch_news_ar_revise(const NwArArgs& a, hipStream_t s);
+hipError_t launch_news_ar_rec(const NwArArgs& a, hipStream_t s);
+hipError_t launch_news_ar_qc(const NwArArgs& a, hipStream_t s);
+hipError_t launch_news_ar_impact(const NwArArgs& a, hipStream_t s);
+
 // Structural analysis of the factor VAR: identified impulse responses, variance and historical decompositions (structural.hip).
 struct SvArgs {
     int B, N, r, p, H, T;

@@ -905,3 +905,4 @@ from . import forecasting_ar  # noqa: E402,F401  (attaches the forecast entries 
 from . import filtering_ar  # noqa: E402,F401  (attaches its filter entries)
 from . import simsmooth_ar  # noqa: E402,F401  (attaches its path-draw entries)
 from . import gibbs_ar  # noqa: E402,F401  (attaches the Gibbs sampler's entries of the AR-idiosyncratic model)
+from . import news_ar  # noqa: E402,F401  (attaches its news entries)

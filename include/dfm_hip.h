@@ -385,6 +385,42 @@ int dfm_news_batch(dfm_handle* h, int B, int T, int N, int r, int p, const doubl
                    const double* P0, const double* mean, const double* sd, int G, const int* target_t,
                    const int* target_i, double* yhat, double* impact, double* news, double* weight, unsigned flags);
 
+/* --- news decomposition with AR(q) idiosyncratic terms -------------------------------------------------------------------------
+ * The same question for the model, symbols and output-row convention of dfm_forecast_ar_batch (below): 1 <= q <= 4, the output
+ * rows are panel rows q .. T + H - 1, n_s = T - q of them in the sample; v0, mean, sd as in that call.  Vintages and targets as in
+ * dfm_news_batch: old / new [B][T][N], targets (target_t[g], target_i[g]) in PANEL rows with q <= t* < T + H, H derived from them.
+ *   yhat[b][w][g]   = xhat of dfm_forecast_ar_batch at the target, conditioned on old (w = 0), revised old (1), new (2)  [B][3][G]
+ *   news[b][t][i]   = I = x_new - E[x | revised old] on the news cells of output row t, 0 elsewhere      (may be NULL) [B][T-q][N]
+ *   weight[b][g][t][i] = d y_new / d x on the cells of new in output row t (data units), 0 elsewhere     (may be NULL) [B][G][T-q][N]
+ *   impact[b][g][i] = sum_t w I of series i; sum_i impact = yhat[2] - yhat[1]                                          [B][G][N]
+ * The first q panel rows are conditioning values: the model is that of the cells behind them given them.  A revision there moves
+ * yhat[1] - yhat[0] and carries no weight.
+ * Both vintages must be EDGE-SHAPED: in every replicate and series the observed panel rows are exactly 0 .. L_i, with
+ * L_i >= 2 q - 1 in old (hence in new, since every cell of old must be observed in new).  Anything else -- an interior gap, a late
+ * start, a series with fewer than 2 q observed rows or none -- is DFM_E_VINTAGE (the status-word bit of dfm_news_batch: the host
+ * entry reports it, dfm_check_status after the "_dev" entry), because the decomposition would not add up: the AR pass
+ * quasi-differences one interior NaN into q + 1 NaN rows, so its factor estimate is no projection on the observed cells, and
+ * y_new - y_rev - sum w I was measured at up to 4.5e-2 on revisions of 6e-2 with a single interior gap; a series with fewer than
+ * q observed output rows brings v0 in and leaves 1e-8 .. 1e-6.  On edge-shaped vintages the identity holds to rounding.
+ * The weights come from one pass per (b, g): the covariance of every quasi-differenced cell with the target is written as a panel
+ * (NaN where the quasi-differenced new vintage is NaN), the inner part of the AR pass runs on it with mu0 = 0 and the caller's
+ * flags, and the adjoint of the quasi-difference turns its residuals into weights.
+ * Status: q < 1, T <= 2 q, G < 1, a target outside [q, T + H) x [0, N): DFM_E_DIMS; q > 4 and what dfm_ks_pass_ar_batch refuses
+ * at T + H rows: DFM_E_R_UNSUPPORTED / its status; a NULL required pointer, mean without sd: DFM_E_NULL; a NaN in new without
+ * DFM_F_MAY_HAVE_MISSING: DFM_E_MISSING; a non-finite pass: DFM_E_NUMERIC (host entry).  target_t / target_i are HOST arrays in
+ * both entries.  Outputs must not overlap the inputs.  Allocates in the handle as dfm_news_batch does, per slice of at most 8192
+ * pass replicates.  Out of scope: vintages that are not edge-shaped, re-estimation between vintages, exact xvar, q > 4. */
+int dfm_news_ar_batch_dev(dfm_handle* h, int B, int T, int N, int r, int p, int q, const double* old_panel,
+                          const double* new_panel, const double* Lam, const double* sig2, const double* rho, const double* Avar,
+                          const double* Q, const double* mu0, const double* P0, const double* v0, const double* mean,
+                          const double* sd, int G, const int* target_t, const int* target_i, double* yhat, double* impact,
+                          double* news, double* weight, unsigned flags);
+int dfm_news_ar_batch(dfm_handle* h, int B, int T, int N, int r, int p, int q, const double* old_panel, const double* new_panel,
+                      const double* Lam, const double* sig2, const double* rho, const double* Avar, const double* Q,
+                      const double* mu0, const double* P0, const double* v0, const double* mean, const double* sd, int G,
+                      const int* target_t, const int* target_i, double* yhat, double* impact, double* news, double* weight,
+                      unsigned flags);
+
 /* --- structural IRFs, variance and historical decompositions of the panel ---------------------------------------------------
  * The model of dfm_forecast_batch: x_t = Lam f_t + e_t, f_t = A_1 f_{t-1} + .. + A_p f_{t-p} + eta_t, Var eta = Q, with
  * 1 <= r p <= DFM_MAX_R.  The structural shocks are eta_t = S u_t with Var u = I.

@@ -698,6 +698,37 @@ function forecast_ar(h::Handle, x::Matrix{Float64}, Lam::Matrix{Float64}, sig2::
             factor = permutedims(f), P = permutedims(P), loglik = ll[1])
 end
 
+"News decomposition of the revision of G target cells between two vintages under the model with AR(q) idiosyncratic terms
+(dfm_news_ar_batch; include/dfm_hip.h): xold / xnew are T x N (NaN = missing) and EDGE-SHAPED -- each series observed on rows
+1..L with no gap, L >= 2q in xold, every cell of xold observed in xnew; anything else is DFM_E_VINTAGE.  Parameters, v0, mean / sd
+as forecast_ar; targets = G (row, column) pairs, 1-based, row > q, rows past T are forecasts.  Returns yhat (3 x G: old, revised
+old, new), impact (G x N), news (T-q x N) and weight (G x T-q x N) over rows q+1..T, in data units with mean / sd."
+function news_ar(h::Handle, xold::Matrix{Float64}, xnew::Matrix{Float64}, Lam::Matrix{Float64}, sig2::Vector{Float64},
+                 rho::Matrix{Float64}, Avar::Matrix{Float64}, Q::Matrix{Float64}, mu0::Vector{Float64}, P0::Matrix{Float64},
+                 targets; v0 = nothing, mean = nothing, sd = nothing, singular_q::Bool = false)
+    (mean === nothing) == (sd === nothing) || error("mean and sd go together")
+    size(xold) == size(xnew) || error("xold and xnew must have the same size")
+    T, N = size(xnew); r = size(Lam, 2); q = size(rho, 2); p = div(size(Avar, 2), r); G = length(targets); ns = T - q
+    po = to_c_panel(xold); pn = to_c_panel(xnew)
+    LamC = permutedims(Lam); rhoC = permutedims(rho); AC = permutedims(Avar); QC = permutedims(Q); P0C = permutedims(P0)
+    v0C = v0 === nothing ? C_NULL : Vector{Float64}(v0)
+    meanC = mean === nothing ? C_NULL : Vector{Float64}(mean); sdC = sd === nothing ? C_NULL : Vector{Float64}(sd)
+    tt = Cint[t - 1 for (t, _) in targets]; ti = Cint[i - 1 for (_, i) in targets]
+    yhat = Array{Float64}(undef, G, 3); impact = Array{Float64}(undef, N, G); nw = Array{Float64}(undef, N, ns)
+    w = Array{Float64}(undef, N, ns, G)
+    flags = (any(isnan, xnew) ? DFM_F_MAY_HAVE_MISSING : Cuint(0)) | (singular_q ? DFM_F_SINGULAR_Q : Cuint(0))
+    GC.@preserve po pn LamC sig2 rhoC AC QC mu0 P0C v0C meanC sdC tt ti yhat impact nw w begin
+        rc = ccall((:dfm_news_ar_batch, LIB), Cint,
+                   (Ptr{Cvoid}, Cint, Cint, Cint, Cint, Cint, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                    Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                    Cint, Ptr{Cint}, Ptr{Cint}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cuint),
+                   h.ptr, 1, T, N, r, p, q, po, pn, LamC, sig2, rhoC, AC, QC, mu0, P0C, v0C, meanC, sdC, G, tt, ti, yhat, impact, nw,
+                   w, flags)
+        check(h.ptr, rc)
+    end
+    return (yhat = permutedims(yhat), impact = permutedims(impact), news = permutedims(nw), weight = permutedims(w, (3, 2, 1)))
+end
+
 # dfm_filter_ar_batch for one replicate (include/dfm_hip.h); the parameters are held fixed over all origins.  t0: a 0-based panel row.
 function filter_ar_call(h::Handle, x::Matrix{Float64}, Lam::Matrix{Float64}, sig2::Vector{Float64}, rho::Matrix{Float64},
                         Avar::Matrix{Float64}, Q::Matrix{Float64}, mu0::Vector{Float64}, P0::Matrix{Float64}, H::Integer, t0::Integer;
