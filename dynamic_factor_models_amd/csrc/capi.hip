@@ -170,9 +170,10 @@ struct dfm_handle {
                                            // the restrictions, their table, mask, counts, rotations and the kept slots' tables;
                                            // dfm_proxyirf_batch_dev: cum, the used rows, the instrument, S, S^-1, the Theta tables, the row
                                            // table, the slots' w and tables, the den table and the pass outputs the caller does not take
-    DevBlock ft;                           // dfm_filter_batch_dev: the padded loadings, the collapse's per-period arrays, the moments the
-                                           // caller does not take and the evaluation's running sums;
-                                           // dfm_filter_ar_batch_dev: the same, with the quasi-differenced panel and its loadings
+    DevBlock ft;                           // the two filter drivers: each one's own arrays first (dfm_filter_batch_dev: the padded loadings;
+                                           // dfm_filter_ar_batch_dev: the quasi-differenced panel, its loadings and the fourth running sum),
+                                           // then what filter_carve lays out for both: the collapse's per-period arrays, the moments the
+                                           // caller does not take and the evaluation's running sums
     DevBlock gb;                           // dfm_gibbs_batch_dev: the sweep's factor path and the shared Gram roots of balanced panels
                                            // dfm_gibbs_ar_batch_dev: the sweep's [B][T - q][r] factor path
     std::vector<int> sv_idx;               // host copy of named / cum while their upload is in flight
@@ -3792,6 +3793,34 @@ static int filter_check(dfm_handle* h, int B, int T, int N, int r, int p, int H,
     return check_general_n(h, N, r);
 }
 
+// What both filter drivers carve from h->ft behind their own arrays (`off`: the bytes those take), from the dimensions, inputs and
+// caller's outputs already in `fa`: the collapse's per-period arrays over the n rows (into `ca` and `fa`), the moments the later
+// kernels read and the caller does not take, and the evaluation's running sums.  Grows h->ft to the total.
+static int filter_carve(dfm_handle* h, size_t off, bool miss, bool fill, bool eval, CollapseArgs& ca, FtCells& fa) {
+    const size_t d = sizeof(double), B = (size_t)fa.B, Bn = B * fa.n, k = (size_t)fa.k, kk = k * (k + 1) / 2, Rp = (size_t)fa.Rp,
+                 n_e = B * fa.H * fa.N;
+    const size_t o_b = take(off, Bn * Rp * d), o_s = take(off, Bn * d), o_ld = take(off, Bn * d), o_n = take(off, Bn * sizeof(int)),
+                 o_ct = miss ? take(off, Bn * (Rp * (Rp + 1) / 2) * d) : (size_t)-1, o_cf = take(off, B * Rp * Rp * d),
+                 o_lf = take(off, B * d),
+                 o_zp = (!fa.z_pred && fill) ? take(off, Bn * k * d) : (size_t)-1,
+                 o_pp = (!fa.P_pred && fa.vstd) ? take(off, Bn * kk * d) : (size_t)-1,
+                 o_zf = (!fa.z_filt && eval) ? take(off, Bn * k * d) : (size_t)-1,
+                 o_acc = eval ? take(off, n_e * d) : (size_t)-1, o_acc0 = eval ? take(off, n_e * d) : (size_t)-1,
+                 o_acn = eval ? take(off, n_e * sizeof(int)) : (size_t)-1;
+    HIP_TRY(h, h->ft.grow(off));
+    ca.B = fa.B; ca.T = fa.n; ca.N = fa.N;
+    ca.bcol = at<double>(h->ft, o_b); ca.scol = at<double>(h->ft, o_s); ca.nobs = at<int>(h->ft, o_n); ca.ldrow = at<double>(h->ft, o_ld);
+    ca.Ct = at<double>(h->ft, o_ct); ca.Cfull = at<double>(h->ft, o_cf); ca.ldfull = at<double>(h->ft, o_lf);
+    ca.status = h->status_dev;
+    fa.bcol = ca.bcol; fa.scol = ca.scol; fa.nobs = ca.nobs; fa.ldrow = ca.ldrow; fa.Ct = ca.Ct; fa.Cfull = ca.Cfull; fa.ldfull = ca.ldfull;
+    if (!fa.z_pred) fa.z_pred = at<double>(h->ft, o_zp);
+    if (!fa.P_pred) fa.P_pred = at<double>(h->ft, o_pp);
+    if (!fa.z_filt) fa.z_filt = at<double>(h->ft, o_zf);
+    fa.acc = at<double>(h->ft, o_acc); fa.acc0 = at<double>(h->ft, o_acc0); fa.acn = at<int>(h->ft, o_acn);
+    fa.status = h->status_dev;
+    return 0;
+}
+
 int dfm_filter_batch_dev(dfm_handle* h, int B, int T, int N, int r, int p, int H, int t0, const double* panel,
                          const double* Lam, const double* R, const double* Avar, const double* Q, const double* mu0,
                          const double* P0, const double* mean, const double* sd, double* z_pred, double* P_pred,
@@ -3799,21 +3828,21 @@ int dfm_filter_batch_dev(dfm_handle* h, int B, int T, int N, int r, int p, int H
                          double* msfe, double* msfe0, int* cnt, unsigned flags) {
     if (int rc = filter_check(h, B, T, N, r, p, H, t0, panel, Lam, R, Avar, Q, mu0, P0, mean, sd)) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
-    const int Rp = pad_r(r), k = r * p;
-    const size_t d = sizeof(double), rr = (size_t)Rp * Rp, npR = (size_t)Rp * (Rp + 1) / 2, kk = (size_t)k * (k + 1) / 2, BT = (size_t)B * T;
+    const int Rp = pad_r(r);
+    const size_t d = sizeof(double), rr = (size_t)Rp * Rp;
     const bool miss = (flags & DFM_F_MAY_HAVE_MISSING) != 0;
     const bool fill = xpred || verr || vstd, eval = H > 0 && (msfe || msfe0 || cnt);
+    FtArgs fa{};
+    fa.B = B; fa.n = T; fa.N = N; fa.r = r; fa.p = p; fa.k = r * p; fa.w = r; fa.Rp = Rp; fa.H = H; fa.t0 = t0;
+    fa.panel = panel; fa.Lam = Lam; fa.R = R; fa.A = Avar; fa.Q = Q; fa.mu0 = mu0; fa.P0 = P0; fa.mean = mean; fa.sd = sd;
+    fa.z_pred = z_pred; fa.P_pred = P_pred; fa.z_filt = z_filt; fa.P_filt = P_filt; fa.loglik_t = loglik_t;
+    fa.xpred = xpred; fa.verr = verr; fa.vstd = vstd;
+    fa.msfe = eval ? msfe : nullptr; fa.msfe0 = eval ? msfe0 : nullptr; fa.cnt = eval ? cnt : nullptr;
     size_t off = 0;
     const size_t o_lam = r != Rp ? take(off, (size_t)B * N * Rp * d) : (size_t)-1,
-                 o_pad = r != Rp ? take(off, (3 * B * rr + (size_t)B * Rp) * d) : (size_t)-1,      // pad_params_kernel's other outputs (unused)
-                 o_b = take(off, BT * Rp * d), o_s = take(off, BT * d), o_ld = take(off, BT * d), o_n = take(off, BT * sizeof(int)),
-                 o_ct = miss ? take(off, BT * npR * d) : (size_t)-1, o_cf = take(off, B * rr * d), o_lf = take(off, (size_t)B * d),
-                 o_zp = (!z_pred && fill) ? take(off, BT * k * d) : (size_t)-1,
-                 o_pp = (!P_pred && vstd) ? take(off, BT * kk * d) : (size_t)-1,
-                 o_zf = (!z_filt && eval) ? take(off, BT * k * d) : (size_t)-1,
-                 o_acc = eval ? take(off, (size_t)B * H * N * d) : (size_t)-1, o_acc0 = eval ? take(off, (size_t)B * H * N * d) : (size_t)-1,
-                 o_acn = eval ? take(off, (size_t)B * H * N * sizeof(int)) : (size_t)-1;
-    HIP_TRY(h, h->ft.grow(off));
+                 o_pad = r != Rp ? take(off, (3 * B * rr + (size_t)B * Rp) * d) : (size_t)-1;      // pad_params_kernel's other outputs (unused)
+    CollapseArgs ca{};
+    if (int rc = filter_carve(h, off, miss, fill, eval, ca, fa)) return rc;
     const double* LamP = Lam;
     if (r != Rp) {
         double* pad = at<double>(h->ft, o_pad);
@@ -3824,22 +3853,8 @@ int dfm_filter_batch_dev(dfm_handle* h, int B, int T, int N, int r, int p, int H
                                pad + B * rr, pad + 3 * B * rr, pad + 2 * B * rr)) return rc;
         LamP = at<double>(h->ft, o_lam);
     }
-    CollapseArgs ca{};
-    ca.B = B; ca.T = T; ca.N = N; ca.panel = panel; ca.Lam = LamP; ca.Rv = R;
-    ca.bcol = at<double>(h->ft, o_b); ca.scol = at<double>(h->ft, o_s); ca.nobs = at<int>(h->ft, o_n); ca.ldrow = at<double>(h->ft, o_ld);
-    ca.Ct = at<double>(h->ft, o_ct); ca.Cfull = at<double>(h->ft, o_cf); ca.ldfull = at<double>(h->ft, o_lf);
-    ca.status = h->status_dev;
+    ca.panel = panel; ca.Lam = LamP; ca.Rv = R;
     { ProfScope ps(h, K_COLLAPSE); HIP_TRY(h, launch_collapse(Rp, ca, h->stream)); }
-    FtArgs fa{};
-    fa.B = B; fa.T = T; fa.N = N; fa.r = r; fa.p = p; fa.Rp = Rp; fa.H = H; fa.t0 = t0;
-    fa.panel = panel; fa.Lam = Lam; fa.R = R; fa.A = Avar; fa.Q = Q; fa.mu0 = mu0; fa.P0 = P0; fa.mean = mean; fa.sd = sd;
-    fa.bcol = ca.bcol; fa.scol = ca.scol; fa.nobs = ca.nobs; fa.ldrow = ca.ldrow; fa.Ct = ca.Ct; fa.Cfull = ca.Cfull; fa.ldfull = ca.ldfull;
-    fa.z_pred = z_pred ? z_pred : at<double>(h->ft, o_zp); fa.P_pred = P_pred ? P_pred : at<double>(h->ft, o_pp);
-    fa.z_filt = z_filt ? z_filt : at<double>(h->ft, o_zf); fa.P_filt = P_filt; fa.loglik_t = loglik_t;
-    fa.xpred = xpred; fa.verr = verr; fa.vstd = vstd;
-    fa.msfe = eval ? msfe : nullptr; fa.msfe0 = eval ? msfe0 : nullptr; fa.cnt = eval ? cnt : nullptr;
-    fa.acc = at<double>(h->ft, o_acc); fa.acc0 = at<double>(h->ft, o_acc0); fa.acn = at<int>(h->ft, o_acn);
-    fa.status = h->status_dev;
     { ProfScope ps(h, K_FT_FILTER); HIP_TRY(h, launch_filter(fa, h->stream)); }
     if (fill) { ProfScope ps(h, K_FT_FILL); HIP_TRY(h, launch_filter_fill(fa, h->stream)); }
     if (eval) { ProfScope ps(h, K_FT_EVAL); HIP_TRY(h, launch_filter_eval(fa, h->stream)); }
@@ -3902,43 +3917,29 @@ int dfm_filter_ar_batch_dev(dfm_handle* h, int B, int T, int N, int r, int p, in
     if (int rc = filter_ar_check(h, B, T, N, r, p, q, H, t0, panel, Lam, sig2, rho, Avar, Q, mu0, P0, mean, sd)) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     const int m = p > q + 1 ? p : q + 1, k = r * m, w = r * (q + 1), Rp = pad_r(k), n = T - q;
-    const size_t d = sizeof(double), rr = (size_t)Rp * Rp, npR = (size_t)Rp * (Rp + 1) / 2, kk = (size_t)k * (k + 1) / 2, Bn = (size_t)B * n;
+    const size_t d = sizeof(double), Bn = (size_t)B * n;
     const bool miss = (flags & DFM_F_MAY_HAVE_MISSING) != 0;
     const bool fill = xpred || verr || vstd, eval = H > 0 && (msfe || msfe_common || msfe0 || cnt);
-    const size_t n_e = (size_t)B * H * N;
+    FtArArgs fa{};
+    fa.B = B; fa.n = n; fa.N = N; fa.r = r; fa.p = p; fa.q = q; fa.k = k; fa.w = w; fa.Rp = Rp; fa.H = H; fa.t0 = t0;
+    fa.panel = panel; fa.Lam = Lam; fa.sig2 = sig2; fa.rho = rho; fa.A = Avar; fa.Q = Q; fa.mu0 = mu0; fa.P0 = P0; fa.mean = mean; fa.sd = sd;
+    fa.z_pred = z_pred; fa.P_pred = P_pred; fa.z_filt = z_filt; fa.P_filt = P_filt; fa.loglik_t = loglik_t;
+    fa.xpred = xpred; fa.verr = verr; fa.vstd = vstd;
+    fa.msfe = eval ? msfe : nullptr; fa.msfe_common = eval ? msfe_common : nullptr; fa.msfe0 = eval ? msfe0 : nullptr;
+    fa.cnt = eval ? cnt : nullptr;
     size_t off = 0;
     const size_t o_xq = take(off, Bn * N * d), o_lam = take(off, (size_t)B * N * Rp * d),
-                 o_b = take(off, Bn * Rp * d), o_s = take(off, Bn * d), o_ld = take(off, Bn * d), o_n = take(off, Bn * sizeof(int)),
-                 o_ct = miss ? take(off, Bn * npR * d) : (size_t)-1, o_cf = take(off, B * rr * d), o_lf = take(off, (size_t)B * d),
-                 o_zp = (!z_pred && fill) ? take(off, Bn * k * d) : (size_t)-1,
-                 o_pp = (!P_pred && vstd) ? take(off, Bn * kk * d) : (size_t)-1,
-                 o_zf = (!z_filt && eval) ? take(off, Bn * k * d) : (size_t)-1,
-                 o_acc = eval ? take(off, n_e * d) : (size_t)-1, o_accc = eval ? take(off, n_e * d) : (size_t)-1,
-                 o_acc0 = eval ? take(off, n_e * d) : (size_t)-1, o_acn = eval ? take(off, n_e * sizeof(int)) : (size_t)-1;
-    HIP_TRY(h, h->ft.grow(off));
+                 o_accc = eval ? take(off, (size_t)B * H * N * d) : (size_t)-1;
+    CollapseArgs ca{};
+    if (int rc = filter_carve(h, off, miss, fill, eval, ca, fa)) return rc;
+    fa.accc = at<double>(h->ft, o_accc);
     double* xq = at<double>(h->ft, o_xq);
     double* LamK = at<double>(h->ft, o_lam);
     if (int rc = launch_1d(h, quasi_diff_kernel, Bn * N, B, T, N, q, panel, rho, xq)) return rc;
     if (int rc = launch_1d(h, ar_loadings_kernel, (size_t)B * N * Rp, B, N, r, q, Rp, Lam, rho, LamK)) return rc;
-    CollapseArgs ca{};
-    ca.B = B; ca.T = n; ca.N = N; ca.panel = xq; ca.Lam = LamK; ca.Rv = sig2;
+    ca.panel = xq; ca.Lam = LamK; ca.Rv = sig2;
     ca.kreal = w;                                               // (the loadings' columns w .. Rp - 1 are zero: as enqueue_pass at kdim)
-    ca.bcol = at<double>(h->ft, o_b); ca.scol = at<double>(h->ft, o_s); ca.nobs = at<int>(h->ft, o_n); ca.ldrow = at<double>(h->ft, o_ld);
-    ca.Ct = at<double>(h->ft, o_ct); ca.Cfull = at<double>(h->ft, o_cf); ca.ldfull = at<double>(h->ft, o_lf);
-    ca.status = h->status_dev;
     { ProfScope ps(h, K_COLLAPSE); HIP_TRY(h, launch_collapse(Rp, ca, h->stream)); }
-    FtArArgs fa{};
-    fa.B = B; fa.T = T; fa.N = N; fa.r = r; fa.p = p; fa.q = q; fa.k = k; fa.w = w; fa.Rp = Rp; fa.H = H; fa.t0 = t0;
-    fa.panel = panel; fa.Lam = Lam; fa.sig2 = sig2; fa.rho = rho; fa.A = Avar; fa.Q = Q; fa.mu0 = mu0; fa.P0 = P0; fa.mean = mean; fa.sd = sd;
-    fa.bcol = ca.bcol; fa.scol = ca.scol; fa.nobs = ca.nobs; fa.ldrow = ca.ldrow; fa.Ct = ca.Ct; fa.Cfull = ca.Cfull; fa.ldfull = ca.ldfull;
-    fa.z_pred = z_pred ? z_pred : at<double>(h->ft, o_zp); fa.P_pred = P_pred ? P_pred : at<double>(h->ft, o_pp);
-    fa.z_filt = z_filt ? z_filt : at<double>(h->ft, o_zf); fa.P_filt = P_filt; fa.loglik_t = loglik_t;
-    fa.xpred = xpred; fa.verr = verr; fa.vstd = vstd;
-    fa.msfe = eval ? msfe : nullptr; fa.msfe_common = eval ? msfe_common : nullptr; fa.msfe0 = eval ? msfe0 : nullptr;
-    fa.cnt = eval ? cnt : nullptr;
-    fa.acc = at<double>(h->ft, o_acc); fa.accc = at<double>(h->ft, o_accc); fa.acc0 = at<double>(h->ft, o_acc0);
-    fa.acn = at<int>(h->ft, o_acn);
-    fa.status = h->status_dev;
     { ProfScope ps(h, K_FTAR_FILTER); HIP_TRY(h, launch_filter_ar(fa, h->stream)); }
     if (fill) { ProfScope ps(h, K_FTAR_FILL); HIP_TRY(h, launch_filter_ar_fill(fa, h->stream)); }
     if (eval) { ProfScope ps(h, K_FTAR_EVAL); HIP_TRY(h, launch_filter_ar_eval(fa, h->stream)); }

@@ -708,55 +708,49 @@ hipError_t launch_px_den(const PxArgs& a, hipStream_t s);
 hipError_t launch_px_fill(PxArgs a, hipStream_t s);
 hipError_t launch_px_shock(const PxArgs& a, hipStream_t s);
 
-// Filtered states, prediction errors and out-of-sample evaluation (filter.hip).  k = r p, kk = k (k + 1) / 2.
-struct FtArgs {
-    int B, T, N, r, p, Rp, H, t0;                 // Rp: width of the collapse's rows (pad_r(r))
-    const double* panel;                          // [B][T][N] (NaN = missing)
-    const double* Lam; const double* R;           // [B][N][r], [B][N]
-    const double* A; const double* Q;             // [B][r][k] = [A_1 .. A_p], [B][r][r]
-    const double* mu0; const double* P0;          // [B][k], [B][k][k]
-    const double* mean; const double* sd;         // [B][N] or both null
-    // launch_collapse's per-period arrays (CollapseArgs): Ct / ldrow are read only where nobs < N
-    const double* bcol; const double* scol; const int* nobs; const double* ldrow; const double* Ct; const double* Cfull;
-    const double* ldfull;
-    double* z_pred; double* P_pred;               // [B][T][k], [B][T][kk] (the fill reads them: never null when it runs)
-    double* z_filt; double* P_filt;               // [B][T][k] (the evaluation reads it), [B][T][kk] or null
-    double* loglik_t;                             // [B][T] or null
-    double* xpred; double* verr; double* vstd;    // [B][T][N] or null
-    double* msfe; double* msfe0; int* cnt;        // [B][H][N] or null
-    double* acc; double* acc0; int* acn;          // [B][H][N] each: the evaluation's running sums (scratch)
-    int* status;                                  // bit 32: a replicate's update failed
-    CellGeom geo;                                 // geometry of the fill (set by its launcher)
-};
-size_t filter_lds_bytes(int r, int k);            // filter_kernel's LDS
-hipError_t launch_filter(const FtArgs& a, hipStream_t s);
-hipError_t launch_filter_fill(FtArgs a, hipStream_t s);
-hipError_t launch_filter_eval(const FtArgs& a, hipStream_t s);
-
-// The same for the model with AR(q) idiosyncratic terms (filter_ar.hip).  m = max(p, q + 1), k = r m (the state), w = r (q + 1)
-// (the width the quasi-differenced observation loads on), n = T - q output rows (panel rows q .. T-1), kk = k (k + 1) / 2.
-struct FtArArgs {
-    int B, T, N, r, p, q, k, w, Rp, H, t0;        // T: panel rows; Rp: width of the collapse's rows (pad_r(k)); t0: a panel row >= q
-    const double* panel;                          // [B][T][N] (NaN = missing): the panel itself, not its quasi-differences
-    const double* Lam; const double* sig2;        // [B][N][r], [B][N]
-    const double* rho;                            // [B][N][q]
+// Filtered states, prediction errors and out-of-sample evaluation: the plain parametric fit (filter.hip) and the fit with AR(q)
+// idiosyncratic terms (filter_ar.hip).  Plain: the state has width k = r p, the observation loads on its first w = r entries and
+// the n = T output rows are the panel's.  AR: m = max(p, q + 1), k = r m, w = r (q + 1) (the width the quasi-differenced
+// observation loads on), n = T - q output rows (panel rows q .. T-1).  kk = k (k + 1) / 2.
+// What the forward recursion reads and writes (filter_recursion, dfm_filter.h):
+struct FtRec {
+    int B, n, N, r, p, k, w, Rp;                  // Rp: width of the collapse's rows (pad_r(r); AR: pad_r(k))
     const double* A; const double* Q;             // [B][r][r p] = [A_1 .. A_p], [B][r][r]
     const double* mu0; const double* P0;          // [B][k], [B][k][k]
-    const double* mean; const double* sd;         // [B][N] or both null
-    // launch_collapse's per-period arrays over the n quasi-differenced rows: Ct / ldrow are read only where nobs < N
+    // launch_collapse's per-period arrays (CollapseArgs) over the n rows: Ct / ldrow are read only where nobs < N
     const double* bcol; const double* scol; const int* nobs; const double* ldrow; const double* Ct; const double* Cfull;
     const double* ldfull;
     double* z_pred; double* P_pred;               // [B][n][k], [B][n][kk] (the fill reads them: never null when it runs)
     double* z_filt; double* P_filt;               // [B][n][k] (the evaluation reads it), [B][n][kk] or null
     double* loglik_t;                             // [B][n] or null
-    double* xpred; double* verr; double* vstd;    // [B][n][N] or null
-    double* msfe; double* msfe_common; double* msfe0; int* cnt;   // [B][H][N] or null
-    double* acc; double* accc; double* acc0; int* acn;            // [B][H][N] each: the evaluation's running sums (scratch)
     int* status;                                  // bit 32: a replicate's update failed
+};
+// ... and what the fill and evaluation kernels of both fits take beyond that
+struct FtCells : FtRec {
+    int H, t0;                                    // t0: the first origin, a panel row (AR: >= q)
+    const double* panel;                          // [B][T][N] (NaN = missing): the panel itself (AR: not its quasi-differences)
+    const double* Lam;                            // [B][N][r]
+    const double* mean; const double* sd;         // [B][N] or both null
+    double* xpred; double* verr; double* vstd;    // [B][n][N] or null
+    double* msfe; double* msfe0; int* cnt;        // [B][H][N] or null
+    double* acc; double* acc0; int* acn;          // [B][H][N] each: the evaluation's running sums (scratch)
     CellGeom geo;                                 // geometry of the fill (set by its launcher)
 };
+struct FtArgs : FtCells {
+    const double* R;                              // [B][N]
+};
+struct FtArArgs : FtCells {
+    int q;
+    const double* sig2; const double* rho;        // [B][N], [B][N][q]
+    double* msfe_common;                          // [B][H][N] or null
+    double* accc;                                 // [B][H][N]: its running sum (scratch)
+};
+size_t filter_lds_bytes(int r, int k);            // filter_kernel's LDS
 size_t filter_ar_lds_bytes(int r, int k, int w);  // filter_ar_kernel's LDS
-hipError_t launch_filter_ar(const FtArArgs& a, hipStream_t s);
+hipError_t launch_filter(const FtRec& a, hipStream_t s);
+hipError_t launch_filter_fill(FtArgs a, hipStream_t s);
+hipError_t launch_filter_eval(const FtArgs& a, hipStream_t s);
+hipError_t launch_filter_ar(const FtRec& a, hipStream_t s);
 hipError_t launch_filter_ar_fill(FtArArgs a, hipStream_t s);
 hipError_t launch_filter_ar_eval(const FtArArgs& a, hipStream_t s);
 

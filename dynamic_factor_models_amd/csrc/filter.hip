@@ -4,13 +4,9 @@
 // Model  x_t = Lam f_t + e_t, e_t ~ N(0, diag R),  f_t = A_1 f_{t-1} + .. + A_p f_{t-p} + eta_t, eta_t ~ N(0, Q); state
 // z_t = (f_t, .., f_{t-p+1}) of width k = r p, companion matrix M (top r rows [A_1 .. A_p], shifts below).  The collapse
 // (collapse.hip) has reduced row t to  b_t = sum lam_i x_ti / R_i,  C_t = sum lam_i lam_i' / R_i,  s_t = sum x_ti^2 / R_i,
-// n_t and ld_t = sum log R_i over its observed cells.  filter_kernel runs the forward recursion in covariance form:
-//   predict   z_p = M z,  P_p = M P M' + Qc          (only the top r rows are products; the rest are shifts)
-//   update    S = P_p[:, :r], P11 = S[:r] = U U' (zero columns for zero pivots), W = I + U' C_t U (SPD, eigenvalues >= 1),
-//             G^-1 = I - C_t U W^-1 U',  a = b_t - C_t f_p
-//             z = z_p + S G^-1 a,   P = P_p - S (G^-1 C_t) S'
-//             loglik_t = -1/2 [n_t log 2 pi + ld_t + log det W + s_t - 2 b_t' f_p + f_p' C_t f_p - a' P11 G^-1 a]
-// Nothing but W is factorised: Q, P_p and C_t may be singular.  filter_fill_kernel streams the prediction errors of every cell,
+// n_t and ld_t = sum log R_i over its observed cells.  filter_kernel runs the forward recursion in covariance form, the text of
+// dfm_filter.h (filter_recursion) with its three widths folded into one: the observation loads on f_t, the first w = r entries of
+// the state, and A has no zero columns (ka = k).  filter_fill_kernel streams the prediction errors of every cell,
 // filter_eval_kernel the h-step forecast errors of every origin and their means over origins.
 #include "dfm_cell.h"
 #include "dfm_filter.h"
@@ -19,225 +15,15 @@
 
 namespace dfm {
 
-// ---- the recursion: one wave per replicate, every matrix in LDS ---------------------------------------------------------------
-// LDS (doubles): A r k | Q r r | P k k | Pp k k | X r k (A P, then C U, then S G^-1 C) | U r r | Y r (r+1) ([a | C_t]) |
-// W r (r+1) (W, then W^-1 U' Y) | Lw r (r+1) (root of W, then G^-1 Y) | z k | zp k | bv r | tv r
-__host__ __device__ inline size_t filter_lds_doubles(int r, int k) {
-    return (size_t)2 * r * k + (size_t)2 * r * r + (size_t)2 * k * k + (size_t)3 * r * (r + 1) + (size_t)2 * k + (size_t)2 * r;
-}
-size_t filter_lds_bytes(int r, int k) { return filter_lds_doubles(r, k) * sizeof(double); }
+// ---- the recursion: filter_recursion (dfm_filter.h) at k = ka = r p, w = r ----------------------------------------------------
+size_t filter_lds_bytes(int r, int k) { return filter_ar_lds_doubles(r, k, r) * sizeof(double); }
 
-__global__ __launch_bounds__(64) void filter_kernel(FtArgs a) {
-    extern __shared__ __attribute__((aligned(16))) double sm[];
-    const int r = a.r, k = a.r * a.p, T = a.T, N = a.N, Rp = a.Rp, tid = threadIdx.x, r1 = r + 1;
-    const int kk = k * (k + 1) / 2, npR = Rp * (Rp + 1) / 2;
-    const size_t b = blockIdx.x;
-    double* sA = sm;
-    double* sQ = sA + r * k;
-    double* sP = sQ + r * r;
-    double* sPp = sP + k * k;
-    double* sX = sPp + k * k;
-    double* sU = sX + r * k;
-    double* sY = sU + r * r;
-    double* sW = sY + r * r1;
-    double* sL = sW + r * r1;
-    double* sz = sL + r * r1;
-    double* szp = sz + k;
-    double* sbv = szp + k;
-    double* stv = sbv + r;
-    for (int e = tid; e < r * k; e += 64) sA[e] = a.A[b * r * k + e];
-    for (int e = tid; e < r * r; e += 64) sQ[e] = a.Q[b * r * r + e];
-    for (int e = tid; e < k * k; e += 64) {       // (lower triangle read, as the packed outputs are)
-        const int i = e / k, j = e % k;
-        sP[e] = i >= j ? a.P0[b * k * k + e] : a.P0[b * k * k + j * k + i];
-    }
-    for (int e = tid; e < k; e += 64) sz[e] = a.mu0[b * k + e];
-    __syncthreads();
-    const double nan = __builtin_nan("");
-    bool dead = false;
-    for (int t = 0; t < T; ++t) {
-        const size_t bt = b * T + t;
-        double ll = 0.0;
-        if (!dead) {
-            // ---- predict
-            for (int e = tid; e < k; e += 64) {
-                double v;
-                if (e < r) {
-                    v = 0.0;
-                    for (int l = 0; l < k; ++l) v = fma(sA[e * k + l], sz[l], v);
-                } else {
-                    v = sz[e - r];
-                }
-                szp[e] = v;
-            }
-            for (int e = tid; e < r * k; e += 64) {
-                const int i = e / k, j = e % k;
-                double v = 0.0;
-                for (int l = 0; l < k; ++l) v = fma(sA[i * k + l], sP[l * k + j], v);
-                sX[e] = v;
-            }
-            __syncthreads();
-            for (int e = tid; e < k * k; e += 64) {
-                const int i = e / k, j = e % k;
-                if (j > i) continue;
-                double v;
-                if (i < r) {                      // (then j < r)
-                    double vij = sQ[i * r + j], vji = sQ[j * r + i];
-                    for (int l = 0; l < k; ++l) {
-                        vij = fma(sX[i * k + l], sA[j * k + l], vij);
-                        vji = fma(sX[j * k + l], sA[i * k + l], vji);
-                    }
-                    v = 0.5 * (vij + vji);
-                } else if (j < r) {
-                    v = sX[j * k + (i - r)];
-                } else {
-                    v = sP[(i - r) * k + (j - r)];
-                }
-                sPp[i * k + j] = v;
-                sPp[j * k + i] = v;
-            }
-            __syncthreads();
-            // ---- update
-            const int n = a.nobs[bt];
-            if (n > 0) {
-                const bool part = n < N;
-                for (int e = tid; e < r * r; e += 64) {
-                    const int i = e / r, j = e % r, hi = i > j ? i : j, lo = i > j ? j : i;
-                    sY[i * r1 + 1 + j] = part ? a.Ct[bt * npR + hi * (hi + 1) / 2 + lo] : a.Cfull[b * Rp * Rp + hi * Rp + lo];
-                }
-                for (int e = tid; e < r; e += 64) sbv[e] = a.bcol[bt * Rp + e];
-                int bad = filter_root(sPp, k, r, sU, kPsdTol);      // (its barriers also publish Y and bv)
-                for (int e = tid; e < r; e += 64) {
-                    double v = sbv[e];
-                    for (int j = 0; j < r; ++j) v = fma(-sY[e * r1 + 1 + j], szp[j], v);
-                    sY[e * r1] = v;                                 // a = b_t - C_t f_p
-                }
-                for (int e = tid; e < r * r; e += 64) {             // C U
-                    const int i = e / r, j = e % r;
-                    double v = 0.0;
-                    for (int l = j; l < r; ++l) v = fma(sY[i * r1 + 1 + l], sU[l * r + j], v);
-                    sX[e] = v;
-                }
-                __syncthreads();
-                for (int e = tid; e < r * r; e += 64) {             // W = I + U' C U (lower triangle, mirrored)
-                    const int i = e / r, j = e % r;
-                    if (j > i) continue;
-                    double v = i == j ? 1.0 : 0.0;
-                    for (int l = i; l < r; ++l) v = fma(sU[l * r + i], sX[l * r + j], v);
-                    sW[i * r + j] = v;
-                    sW[j * r + i] = v;
-                }
-                __syncthreads();
-                bad |= filter_root(sW, r, r, sL, 0.0);
-                // the r + 1 columns of Y = [a | C]: Y2 = W^-1 U' Y, a lane per column
-                for (int e = tid; e < r * r1; e += 64) {
-                    const int i = e / r1, c = e % r1;
-                    double v = 0.0;
-                    for (int l = i; l < r; ++l) v = fma(sU[l * r + i], sY[l * r1 + c], v);
-                    sW[i * r1 + c] = v;
-                }
-                __syncthreads();
-                if (tid < r1) {
-                    const int c = tid;
-                    for (int i = 0; i < r; ++i) {
-                        double v = sW[i * r1 + c];
-                        for (int m = 0; m < i; ++m) v = fma(-sL[i * r + m], sW[m * r1 + c], v);
-                        sW[i * r1 + c] = v / sL[i * r + i];
-                    }
-                    for (int i = r - 1; i >= 0; --i) {
-                        double v = sW[i * r1 + c];
-                        for (int m = i + 1; m < r; ++m) v = fma(-sL[m * r + i], sW[m * r1 + c], v);
-                        sW[i * r1 + c] = v / sL[i * r + i];
-                    }
-                }
-                if (tid < r) stv[tid] = 2.0 * log(sL[tid * r + tid]);   // log det W, term by term
-                __syncthreads();
-                // G^-1 Y = Y - (C U) Y2 into the root's place: column 0 = G^-1 a, columns 1 .. r = G^-1 C
-                for (int e = tid; e < r * r1; e += 64) {
-                    const int i = e / r1, c = e % r1;
-                    double v = sY[e];
-                    for (int l = 0; l < r; ++l) v = fma(-sX[i * r + l], sW[l * r1 + c], v);
-                    sL[e] = v;
-                }
-                __syncthreads();
-                // log-likelihood terms of row i, and z = z_p + S G^-1 a
-                if (tid < r) {
-                    const int i = tid;
-                    double cf = 0.0, pg = 0.0;
-                    for (int j = 0; j < r; ++j) {
-                        cf = fma(sY[i * r1 + 1 + j], szp[j], cf);
-                        pg = fma(sPp[i * k + j], sL[j * r1], pg);
-                    }
-                    stv[i] += szp[i] * (cf - 2.0 * sbv[i]) - sY[i * r1] * pg;
-                }
-                for (int e = tid; e < k; e += 64) {
-                    double v = szp[e];
-                    for (int j = 0; j < r; ++j) v = fma(sPp[e * k + j], sL[j * r1], v);
-                    sz[e] = v;
-                }
-                __syncthreads();
-                // S (G^-1 C) with G^-1 C symmetrised, then P = P_p - (S G^-1 C) S' on the lower triangle, mirrored
-                for (int e = tid; e < k * r; e += 64) {
-                    const int i = e / r, j = e % r;
-                    double v = 0.0;
-                    for (int l = 0; l < r; ++l) v = fma(sPp[i * k + l], 0.5 * (sL[l * r1 + 1 + j] + sL[j * r1 + 1 + l]), v);
-                    sX[e] = v;
-                }
-                double q = 0.0;
-                for (int i = 0; i < r; ++i) q += stv[i];
-                ll = -0.5 * ((double)n * kLog2Pi + (part ? a.ldrow[bt] : a.ldfull[b]) + a.scol[bt] + q);
-                __syncthreads();
-                for (int e = tid; e < k * k; e += 64) {
-                    const int i = e / k, j = e % k;
-                    if (j > i) continue;
-                    double v = sPp[i * k + j];
-                    for (int l = 0; l < r; ++l) v = fma(-sX[i * r + l], sPp[j * k + l], v);
-                    sP[i * k + j] = v;
-                    sP[j * k + i] = v;
-                }
-                bool fin = ll == ll && fabs(ll) <= 1.79e308;
-                for (int e = tid; e < k; e += 64) fin = fin && sz[e] == sz[e] && fabs(sz[e]) <= 1.79e308;
-                if (bad || __any(!fin)) dead = true;
-            } else {
-                for (int e = tid; e < k * k; e += 64) sP[e] = sPp[e];
-                for (int e = tid; e < k; e += 64) sz[e] = szp[e];
-                bool fin = true;
-                for (int e = tid; e < k; e += 64) fin = fin && szp[e] == szp[e] && fabs(szp[e]) <= 1.79e308;
-                if (__any(!fin)) dead = true;
-            }
-            __syncthreads();
-            if (dead && tid == 0) atomicOr(a.status, kFtFailBit);
-        }
-        // ---- the period's outputs (NaN from the failed period on)
-        for (int e = tid; e < k; e += 64) {
-            if (a.z_pred) a.z_pred[bt * k + e] = dead ? nan : szp[e];
-            if (a.z_filt) a.z_filt[bt * k + e] = dead ? nan : sz[e];
-        }
-        if (a.P_pred || a.P_filt)
-            for (int e = tid; e < k * k; e += 64) {
-                const int i = e / k, j = e % k;
-                if (j > i) continue;
-                const size_t o = bt * kk + i * (i + 1) / 2 + j;
-                if (a.P_pred) a.P_pred[o] = dead ? nan : sPp[e];
-                if (a.P_filt) a.P_filt[o] = dead ? nan : sP[e];
-            }
-        if (a.loglik_t && tid == 0) a.loglik_t[bt] = dead ? nan : ll;
-        __syncthreads();
-    }
-}
+__global__ __launch_bounds__(64) void filter_kernel(FtRec a) { filter_recursion<false>(a); }
 
-hipError_t launch_filter(const FtArgs& a, hipStream_t s) {
-    const size_t lds = filter_lds_bytes(a.r, a.r * a.p);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
+hipError_t launch_filter(const FtRec& a, hipStream_t s) {
+    if (a.k != a.r * a.p || a.w != a.r) return hipErrorInvalidValue;       // (the widths filter_recursion<false> takes as given)
     static LdsOptIn attr_done;
-    if (!attr_done && lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&filter_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           160 * 1024);
-        if (e != hipSuccess) return e;
-        attr_done = true;
-    }
-    hipLaunchKernelGGL(filter_kernel, dim3((unsigned)a.B), dim3(64), lds, s, a);
-    return hipGetLastError();
+    return launch_filter_recursion(filter_kernel, attr_done, a, s);
 }
 
 // ---- the panel-sized outputs ------------------------------------------------------------------------------------------------------
@@ -247,7 +33,7 @@ hipError_t launch_filter(const FtArgs& a, hipStream_t s) {
 template <int RB, int SP>
 __global__ __launch_bounds__(kFtFillMaxThreads) void filter_fill_kernel(FtArgs a) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
-    const int r = a.r, k = a.r * a.p, T = a.T, tid = threadIdx.x, np = r * (r + 1) / 2, kk = k * (k + 1) / 2;
+    const int r = a.r, k = a.r * a.p, T = a.n, tid = threadIdx.x, np = r * (r + 1) / 2, kk = k * (k + 1) / 2;
     const CellChunk ch = cell_chunk(a.geo, blockIdx.x, T);
     const size_t b = ch.outer;
     const int t0 = ch.t0, t1 = ch.t1;
@@ -306,7 +92,7 @@ hipError_t launch_filter_fill(FtArgs a, hipStream_t s) {
         constexpr int RB = decltype(RBc)::value;
         const int r = a.r;
         const int SP = cell_sp(a.N, RB, a.panel, a.xpred, a.verr, a.vstd);
-        a.geo = cell_geometry((a.N + SP - 1) / SP, r + r * (r + 1) / 2, a.T, kFtFillMaxThreads, kFtFillLds);
+        a.geo = cell_geometry((a.N + SP - 1) / SP, r + r * (r + 1) / 2, a.n, kFtFillMaxThreads, kFtFillLds);
         const size_t lds = (size_t)a.geo.RC * (r + r * (r + 1) / 2) * sizeof(double);
         return cell_launch_sp<RB>(filter_fill_kernel<RB, 1>, filter_fill_kernel<RB, cell_sp_max(RB)>, SP,
                                   (size_t)a.B * a.geo.nchunk * a.geo.nsblk, a.geo.threads, lds, s, a);
@@ -323,7 +109,7 @@ hipError_t launch_filter_fill(FtArgs a, hipStream_t s) {
 template <int RB>
 __global__ __launch_bounds__(256) void filter_eval_kernel(FtArgs a) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
-    const int r = a.r, k = a.r * a.p, T = a.T, N = a.N, H = a.H, tid = threadIdx.x;
+    const int r = a.r, k = a.r * a.p, T = a.n, N = a.N, H = a.H, tid = threadIdx.x;
     const int nsblk = (N + 255) / 256;
     const int s = blockIdx.x % nsblk;
     const size_t b = blockIdx.x / nsblk;
@@ -345,17 +131,7 @@ __global__ __launch_bounds__(256) void filter_eval_kernel(FtArgs a) {
         double* nxt = buf1;
         for (int h = 1; h <= H; ++h) {
             __syncthreads();
-            for (int e = tid; e < no * k; e += blockDim.x) {
-                const int o = e / k, m = e % k;
-                double v;
-                if (m < r) {
-                    v = 0.0;
-                    for (int l = 0; l < k; ++l) v = fma(sA[m * k + l], cur[o * k + l], v);
-                } else {
-                    v = cur[o * k + m - r];
-                }
-                nxt[e] = v;
-            }
+            filter_eval_step(sA, k, cur, nxt, no, r, k);
             __syncthreads();
             if (own) {
                 const size_t ai = (b * H + (h - 1)) * N + i;

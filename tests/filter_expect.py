@@ -10,8 +10,8 @@ from tests.simsmooth_expect import psd_root      # lower root with the zero-colu
 from tests.structural_expect import KEYS, synth  # noqa: F401  (the oracle's synthetic panels and parameters)
 
 LOG2PI = float(np.log(2.0 * np.pi))
-FT_MAX_THREADS = 512                 # filter.hip kFtFillMaxThreads
-FT_LDS = 48 * 1024                   # filter.hip kFtFillLds
+FT_MAX_THREADS = 512                 # dfm_filter.h kFtFillMaxThreads
+FT_LDS = 48 * 1024                   # dfm_filter.h kFtFillLds
 
 
 def companion(A, Q):

@@ -1,5 +1,5 @@
 """CPU tests of the filter family (include/dfm_hip.h dfm_filter_batch): the expectation model of tests/filter_expect.py against the
-oracles, the collapsed update of csrc/filter.hip restated in NumPy against the textbook update, the launch classes the GPU case
+oracles, the collapsed update of csrc/dfm_filter.h restated in NumPy against the textbook update, the launch classes the GPU case
 table reaches, and the argument checks, signatures and Julia names that need no device."""
 import os
 
