@@ -82,6 +82,60 @@ __device__ __forceinline__ void dma16_base_row16(const void* gbase, unsigned vof
                  : "=&s"(keep), "=&s"(ex) : "v"(voff), "s"(gbase), "s"(lds_dst) : "memory");
 }
 
+// One ring BLOCK of LDS-DMAs in one statement: 4 rows x NDR pieces of 1 KB.  Row k comes from the wave-uniform pointer rk and
+// lands at lds_dst + k * slot_stride; piece p of a row is the instruction's immediate offset 1024 p, which the hardware adds to
+// the global AND to the LDS address.  Lane l moves the 16 bytes at voff (= 16 l) of its piece.  M0 is saved and restored ONCE and
+// walks the slots by addition; exec changes ONCE, for the last piece of every row, which only the lanes of last_mask move (a row
+// need not fill its last KB).  Two pieces: up the rows with the full-width piece, back down with the last one.  One piece: up
+// the rows under the mask.  The s_nop behind each write of M0 covers the hazard between that write and the load that reads M0
+// (cdna_hip_programming.md §5.7); behind the first write the save of exec stands in that place.  vmcnt counts exactly 4 NDR
+// loads per statement; their order inside the block is free, the kernels' counted waits are block-granular.
+// PRECONDITION: all 64 lanes active on entry (a wave-uniform call site).  The full-width pieces go out under the exec they find
+// and the last pieces under last_mask itself, not under its intersection with the caller's exec.
+#define DFM_GLDS_(MOD, R, P) "global_load_lds_dwordx4 %2, " R " offset:" P MOD "\n\t"
+#define DFM_M0_UP_ "s_add_u32 m0, m0, %8\n\ts_nop 0\n\t"
+#define DFM_M0_DOWN_ "s_sub_u32 m0, m0, %8\n\ts_nop 0\n\t"
+#define DFM_BLOCK_ROWS1_(MOD)                                                                                               \
+    "s_mov_b64 exec, %9\n\t"                                                                                                \
+    DFM_GLDS_(MOD, "%3", "0") DFM_M0_UP_ DFM_GLDS_(MOD, "%4", "0") DFM_M0_UP_ DFM_GLDS_(MOD, "%5", "0") DFM_M0_UP_          \
+    DFM_GLDS_(MOD, "%6", "0")
+#define DFM_BLOCK_ROWS2_(MOD)                                                                                               \
+    DFM_GLDS_(MOD, "%3", "0") DFM_M0_UP_ DFM_GLDS_(MOD, "%4", "0") DFM_M0_UP_ DFM_GLDS_(MOD, "%5", "0") DFM_M0_UP_          \
+    DFM_GLDS_(MOD, "%6", "0")                                                                                               \
+    "s_mov_b64 exec, %9\n\t"                                                                                                \
+    DFM_GLDS_(MOD, "%6", "1024") DFM_M0_DOWN_ DFM_GLDS_(MOD, "%5", "1024") DFM_M0_DOWN_ DFM_GLDS_(MOD, "%4", "1024")        \
+    DFM_M0_DOWN_ DFM_GLDS_(MOD, "%3", "1024")
+#define DFM_LDS_DMA_BLOCK(ROWS, voff, r0, r1, r2, r3, lds_dst, slot_stride, last_mask)                                      \
+    do {                                                                                                                    \
+        unsigned keep_m0_;                                                                                                  \
+        unsigned long long keep_ex_;                                                                                        \
+        asm volatile(                                                                                                       \
+            "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %7\n\ts_mov_b64 %1, exec\n\t"                                                \
+            ROWS                                                                                                            \
+            "s_mov_b64 exec, %1\n\ts_mov_b32 m0, %0"                                                                        \
+            : "=&s"(keep_m0_), "=&s"(keep_ex_)                                                                              \
+            : "v"(voff), "s"(r0), "s"(r1), "s"(r2), "s"(r3), "s"(lds_dst), "s"(slot_stride), "s"(last_mask)                 \
+            : "memory", "scc");                                                                                             \
+    } while (0)
+#define DFM_LDS_DMA_BLOCK_NDR(MOD, ...)                                                       \
+    do {                                                                                      \
+        if constexpr (NDR == 1) DFM_LDS_DMA_BLOCK(DFM_BLOCK_ROWS1_(MOD), __VA_ARGS__);        \
+        else DFM_LDS_DMA_BLOCK(DFM_BLOCK_ROWS2_(MOD), __VA_ARGS__);                           \
+    } while (0)
+// nt: the panel stream's non-temporal hint (dma16_stream above), chosen once per block
+template <int NDR>
+__device__ __forceinline__ void dma16_block_stream(unsigned voff, const void* r0, const void* r1, const void* r2, const void* r3,
+                                                   unsigned lds_dst, unsigned slot_stride, unsigned long long last_mask, bool nt) {
+    static_assert(NDR == 1 || NDR == 2, "rows of at most 2 KB (the MFMA collapse: N <= 256); a longer row needs its own ROWS text");
+    if (nt) DFM_LDS_DMA_BLOCK_NDR(" nt", voff, r0, r1, r2, r3, lds_dst, slot_stride, last_mask);      // (wave-uniform)
+    else DFM_LDS_DMA_BLOCK_NDR(DFM_DMA_MOD, voff, r0, r1, r2, r3, lds_dst, slot_stride, last_mask);
+}
+// the lanes that move 16 bytes of the last piece of a row of row_bytes (a multiple of 16)
+__device__ __forceinline__ unsigned long long dma16_last_mask(unsigned row_bytes) {
+    const unsigned nl = ((row_bytes + 1023u) % 1024u + 1u) / 16u;    // 1 .. 64 lanes
+    return nl >= 64u ? ~0ull : (1ull << nl) - 1ull;
+}
+
 // at most K vector-memory operations of this wave (LDS-DMAs among them) still in flight; K = 0: all have landed
 template <int K>
 __device__ __forceinline__ void wait_vmcnt() {

@@ -11,6 +11,9 @@
 //                                the MFMA operand layout, 1 / R by column) come from the fill wave through a park in the
 //                                b_t buffer they are about to fill, read with ds_read at the replicate boundary: no global
 //                                load, no vmcnt(0), the ring stays in flight (pf_wpark_rule; else they load their own).
+//                                A ring block (4 rows x NDR pieces) is issued as ONE statement (dfm_lds.h dma16_block_stream)
+//                                off one running scalar pointer: a wave issues ~210 instructions per block, not ~360, and
+//                                the stream waves were issue-bound (docs/HISTORY.md A.16).
 //   the next ncov waves  COV     Gram matrix C = Lam' R^-1 Lam, the data-independent covariance recursion (dfm_cov8.h: one
 //                                wave per replicate, element per lane), the transient rows of P_smooth, then the fixed-point
 //                                rows of P_smooth (pure stores).  Nothing here depends on the panel, so these waves run
@@ -884,7 +887,20 @@ __global__ __launch_bounds__(kPfMaxThreads) void pass_fused_kernel(CollapseArgs 
 
         if (gtot > 0) {
             int ij = 0, ik = 0;                                  // next block to issue
-            auto advance_issue = [&]() { ++ik; if (ik == nblk) { ik = 0; ++ij; } };
+            // ... and its first row: ONE running scalar pointer, advanced by a block per issue and formed anew only where the
+            // sequence moves to the next replicate -- nothing of a block's addresses is computed from (replicate, block, row).
+            auto seg_base = [&](int jj) { return reinterpret_cast<const char*>(a.panel + ((size_t)((int)blockIdx.x + jj * G) * T + ta) * N); };
+            const char* isrc = seg_base(0);
+            const size_t blkB = 4 * (size_t)rowB;
+            const int kclamp = (nrows & 3) != 0 ? nblk - 1 : -1;       // the one block of a segment whose last rows repeat:
+            const unsigned clamp1 = (nrows & 3) > 1 ? rowB : 0u;       // its rows 1 and 2 (row 3 repeats row 2), as byte offsets
+            const unsigned clamp2 = (nrows & 3) > 2 ? 2u * rowB : clamp1;
+            const unsigned long long last_mask = dma16_last_mask(rowB);
+            auto advance_issue = [&]() {
+                ++ik;
+                isrc += blkB;
+                if (ik == nblk) { ik = 0; ++ij; isrc = seg_base(ij); }
+            };
             int bslot = 0;
             double* bt = bt0;
             int buf = 0;
@@ -907,24 +923,20 @@ __global__ __launch_bounds__(kPfMaxThreads) void pass_fused_kernel(CollapseArgs 
                     const unsigned lane16 = 16u * lane;
                     bool pact[NDR];                                          // lane moves 16 bytes of piece p of a row
 #pragma unroll
-                    for (int p = 0; p < NDR; ++p) pact[p] = lane16 + 1024u * p < rowB;
+                    for (int p = 0; p < NDR; ++p) pact[p] = p + 1 < NDR || lane16 + 1024u * p < rowB;   // (only a row's last piece is partial)
                     const unsigned lane_off = (unsigned)q * SB + (unsigned)(4 * g + K) * 8u;
                     const bool tail_clamp = (STEPS - 1) * CS + 4 * g + K >= N;
                     const unsigned last_off = tail_clamp ? (unsigned)q * SB + (unsigned)(N - 1) * 8u : lane_off + (unsigned)(STEPS - 1) * (CS * 8u);
                     // block k of local replicate jj into ring block `bslot`: 4 rows x NDR DMA instructions, always
-                    auto issue_block = [&](int jj, int k, int bslot) {
-                        const char* seg = reinterpret_cast<const char*>(a.panel + ((size_t)((int)blockIdx.x + jj * G) * T + ta) * N);
-#pragma unroll
-                        for (int rr = 0; rr < 4; ++rr) {
-                            int ri = 4 * k + rr;
-                            ri = ri < nrows ? ri : nrows - 1;
-                            const char* src = seg + (size_t)ri * rowB + lane16;
-                            const unsigned dst = __builtin_amdgcn_readfirstlane(ring_lds + (unsigned)(bslot * 4 + rr) * SB);
-#pragma unroll
-                            for (int p = 0; p < NDR; ++p) {
-                                if (pact[p]) dma16_stream(src + 1024 * p, dst + 1024u * p, dma_nt);
-                            }
-                        }
+                    // (the block is the one at the issue cursor: isrc is its first row.)  One statement per block -- dma16_block_stream:
+                    // constant row strides off the running pointer; the clamp to the segment's last row only in block kclamp.
+                    auto issue_block = [&](int k, int bslot) {
+                        const bool cl = k == kclamp;                         // (wave-uniform)
+                        const char* r1 = isrc + (cl ? clamp1 : rowB);
+                        const char* r2 = isrc + (cl ? clamp2 : 2u * rowB);
+                        const char* r3 = isrc + (cl ? clamp2 : 3u * rowB);
+                        const unsigned dst = __builtin_amdgcn_readfirstlane(ring_lds + (unsigned)bslot * 4u * SB);
+                        dma16_block_stream<NDR>(lane16, isrc, r1, r2, r3, dst, SB, last_mask, dma_nt);
                     };
                     // weights of replicate bb by this wave itself (the route without the hand-over).  Ends with vmcnt(0): the ring blocks in
                     // flight have landed too, and nothing new is issued until the weights are back.
@@ -936,7 +948,7 @@ __global__ __launch_bounds__(kPfMaxThreads) void pass_fused_kernel(CollapseArgs 
                     if (j == 0) {                                     // prologue: the first NB blocks
 #pragma unroll
                         for (int u = 0; u < NB; ++u) {
-                            if (u < gtot) { issue_block(ij, ik, u); advance_issue(); }
+                            if (u < gtot) { issue_block(ik, u); advance_issue(); }
                         }
                     }
                     if (wave == 0) stamp(b, 0);
@@ -994,13 +1006,18 @@ __global__ __launch_bounds__(kPfMaxThreads) void pass_fused_kernel(CollapseArgs 
                         const char* pq = blkbase + lane16;
                         double2 xq[4][NQ];
 #pragma unroll
-                        for (int rr = 0; rr < 4; ++rr)
+                        for (int rr = 0; rr < 4; ++rr) {
 #pragma unroll
-                            for (int jq = 0; jq < NQ; ++jq)
-                                xq[rr][jq] = pact[jq] ? *reinterpret_cast<const double2*>(pq + (unsigned)rr * SB + 1024u * jq)
-                                                      : make_double2(0.0, 0.0);
+                            for (int jq = 0; jq + 1 < NQ; ++jq) xq[rr][jq] = *reinterpret_cast<const double2*>(pq + (unsigned)rr * SB + 1024u * jq);
+                            xq[rr][NQ - 1] = make_double2(0.0, 0.0);
+                        }
+                        if (pact[NQ - 1]) {                                  // the last pieces of the four rows under one exec mask
+#pragma unroll
+                            for (int rr = 0; rr < 4; ++rr)
+                                xq[rr][NQ - 1] = *reinterpret_cast<const double2*>(pq + (unsigned)rr * SB + 1024u * (NQ - 1));
+                        }
                         wait_lgkmcnt0();                                     // the reads are done before the slots are re-armed
-                        if (ij < nrep) { issue_block(ij, ik, bslot); advance_issue(); }
+                        if (ij < nrep) { issue_block(ik, bslot); advance_issue(); }
                         double D = 0.0, D2 = 0.0;                            // two accumulators: half the dependent MFMA chain
 #pragma unroll
                         for (int s = 0; s < STEPS; ++s) {
@@ -1008,14 +1025,20 @@ __global__ __launch_bounds__(kPfMaxThreads) void pass_fused_kernel(CollapseArgs 
                             else D2 = __builtin_amdgcn_mfma_f64_4x4x4f64(xa[s], Bw[s], D2, 0, 0, 0);
                         }
                         D += D2;
+                        auto square_row = [&](int rr) {
 #pragma unroll
-                        for (int rr = 0; rr < 4; ++rr) {
-                            if (full || r0 + rr < nrows) {                   // wave-uniform: rows past the segment repeat its last row
+                            for (int jq = 0; jq < NQ; ++jq) {
+                                qa[jq][0] = fma(xq[rr][jq].x, xq[rr][jq].x, qa[jq][0]);
+                                qa[jq][1] = fma(xq[rr][jq].y, xq[rr][jq].y, qa[jq][1]);
+                            }
+                        };
+                        if (full) {                                          // (wave-uniform) one branch per block, not one per row
 #pragma unroll
-                                for (int jq = 0; jq < NQ; ++jq) {
-                                    qa[jq][0] = fma(xq[rr][jq].x, xq[rr][jq].x, qa[jq][0]);
-                                    qa[jq][1] = fma(xq[rr][jq].y, xq[rr][jq].y, qa[jq][1]);
-                                }
+                            for (int rr = 0; rr < 4; ++rr) square_row(rr);
+                        } else {
+#pragma unroll
+                            for (int rr = 0; rr < 4; ++rr) {
+                                if (r0 + rr < nrows) square_row(rr);         // rows past the segment repeat its last row
                             }
                         }
                         D += xor_lane<8>(D);                                 // fold the two series groups
