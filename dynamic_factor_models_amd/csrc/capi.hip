@@ -239,6 +239,14 @@ struct ProfScope {  // records an event pair around one kernel launch when profi
         if (dfm::t_launched_kernel) h->events[idx].name = dfm::t_launched_kernel;
     }
 };
+// One kernel launch on h->stream under its ProfScope: HIP_TRY(h, expr) with kernel kid's event pair around it (h->err quotes expr
+// as HIP_TRY does).  A launch on another stream, or a scope that holds more than the launch, still writes its ProfScope out.
+#define HIP_LAUNCH(h, kid, expr)                           \
+    do {                                                   \
+        ProfScope ps(h, kid);                              \
+        hipError_t _e = (expr);                            \
+        if (_e != hipSuccess) return hip_fail(h, _e, #expr); \
+    } while (0)
 
 int pad_r(int r) { return pow2_ge(r) < 2 ? 2 : pow2_ge(r); }
 
@@ -767,14 +775,14 @@ int enqueue_pass_fast(dfm_handle* h, const Plan& p, int B, int T, int N, int out
         ua.active = em->active; ua.iters = em->iters; ua.ll_path = em->ll_path; ua.k = em->k; ua.max_iter = em->max_iter;
         ua.tol = em->tol;
         if (h->defer_em) { h->deferred_em = ua; h->have_deferred_em = true; return 0; }
-        { ProfScope ps(h, K_EM_UPDATE); HIP_TRY(h, launch_em_update(p.Rp, ua, h->stream)); }
+        HIP_LAUNCH(h, K_EM_UPDATE, launch_em_update(p.Rp, ua, h->stream));
         return 0;
     };
     if (h->opt.no_side) {   // diagnostics: everything in order on the main stream
-        if (!fuse_gram) { ProfScope ps(h, K_GRAM); HIP_TRY(h, run_gram(h->stream)); }
-        { ProfScope ps(h, K_COV); HIP_TRY(h, launch_cov(p.Rp, fa, h->stream)); }
-        { ProfScope ps(h, use_wide ? K_COLLAPSE_WIDE : use_mfma ? K_COLLAPSE_MFMA : K_COLLAPSE_DMA); HIP_TRY(h, run_collapse(ca, h->stream)); }
-        { ProfScope ps(h, K_MEANSCAN); HIP_TRY(h, launch_meanscan(p.Rp, fa, h->stream)); }
+        if (!fuse_gram) HIP_LAUNCH(h, K_GRAM, run_gram(h->stream));
+        HIP_LAUNCH(h, K_COV, launch_cov(p.Rp, fa, h->stream));
+        HIP_LAUNCH(h, use_wide ? K_COLLAPSE_WIDE : use_mfma ? K_COLLAPSE_MFMA : K_COLLAPSE_DMA, run_collapse(ca, h->stream));
+        HIP_LAUNCH(h, K_MEANSCAN, launch_meanscan(p.Rp, fa, h->stream));
         return em_update();
     }
     // Measured on MI355X (profiles/r01): every cross-stream event edge costs 7-25 us, more than the
@@ -789,7 +797,7 @@ int enqueue_pass_fast(dfm_handle* h, const Plan& p, int B, int T, int N, int out
             ca.scol = at<double>(h, p.scol);                      // workspace dump below (diagnostics)
             if (const char* f = diag_env("DFM_PF_PROF_FILE")) h->prof_file = f;
         }
-        { ProfScope ps(h, K_PASS_FUSED); HIP_TRY(h, launch_pass_fused(ca, fa, h->opt.pass_nsw, h->opt.pass_ncov, h->opt.pf_wpark, h->num_cu, h->stream)); }
+        HIP_LAUNCH(h, K_PASS_FUSED, launch_pass_fused(ca, fa, h->opt.pass_nsw, h->opt.pass_ncov, h->opt.pf_wpark, h->num_cu, h->stream));
         if ((h->opt.scan_abl & 256) && !h->prof_file.empty()) {       // diagnostics: dump the stamps of this pass (synchronises)
             std::vector<double> st((size_t)B * T);
             HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -809,12 +817,12 @@ int enqueue_pass_fast(dfm_handle* h, const Plan& p, int B, int T, int N, int out
         // ONE stream, two launches: [Gram + covariance workgroups + P_smooth fill | streaming collapse] -> scan.
         // The covariance waves sit at the front of the collapse grid (resident first, no cross-stream events).
         if (h->opt.fused_gram) { fa.Lam = pp.Lam; fa.Rv = Rv; }   // the covariance workgroups compute their Gram matrices themselves
-        else { ProfScope ps(h, K_GRAM); HIP_TRY(h, run_gram(h->stream)); }
+        else HIP_LAUNCH(h, K_GRAM, run_gram(h->stream));
         ca.fuse_cov = &fa;
-        { ProfScope ps(h, K_COLLAPSE_MFMA); HIP_TRY(h, launch_collapse_dma(p.Rp, ca, h->stream, cvariant)); }
+        HIP_LAUNCH(h, K_COLLAPSE_MFMA, launch_collapse_dma(p.Rp, ca, h->stream, cvariant));
         ca.fuse_cov = nullptr;
         if (P_smooth) fa.abl |= 1;
-        { ProfScope ps(h, K_MEANSCAN); HIP_TRY(h, launch_meanscan(p.Rp, fa, h->stream)); }
+        HIP_LAUNCH(h, K_MEANSCAN, launch_meanscan(p.Rp, fa, h->stream));
         return em_update();
     }
     // Wide states (collapse_wide2), DFM_WIDE_SUB = n > 1 (diagnostics; default off): the batch in n sub-batches, each a complete
@@ -842,10 +850,10 @@ int enqueue_pass_fast(dfm_handle* h, const Plan& p, int B, int T, int N, int out
             return c;
         };
         auto sub_ws = [&](int s_) { return reinterpret_cast<double*>(reinterpret_cast<char*>(Wwide) + (size_t)s_ * slice); };
-        for (int s_ = 0; s_ < Sw; ++s_) { ProfScope ps(h, K_GRAM); HIP_TRY(h, launch_wide_prep(sub_args(s_), sub_ws(s_), p.Rp, h->stream, p.r)); }
+        for (int s_ = 0; s_ < Sw; ++s_) HIP_LAUNCH(h, K_GRAM, launch_wide_prep(sub_args(s_), sub_ws(s_), p.Rp, h->stream, p.r));
         HIP_TRY(h, hipEventRecord(h->ev_fork, h->stream));
         HIP_TRY(h, hipStreamWaitEvent(h->side, h->ev_fork, 0));
-        { ProfScope ps(h, K_COV); HIP_TRY(h, launch_cov(p.Rp, fa, h->stream)); }      // resident before the collapse fills the CUs
+        HIP_LAUNCH(h, K_COV, launch_cov(p.Rp, fa, h->stream));      // resident before the collapse fills the CUs
         HIP_TRY(h, hipEventRecord(h->ev_sub[Sw], h->stream));                         // covariance tables done
         for (int s_ = 0; s_ < Sw; ++s_) {
             { ProfScope ps(h, K_COLLAPSE_WIDE, h->side); HIP_TRY(h, launch_collapse_wide2(sub_args(s_), sub_ws(s_), p.Rp, p.r, h->num_cu, h->side)); }
@@ -863,7 +871,7 @@ int enqueue_pass_fast(dfm_handle* h, const Plan& p, int B, int T, int N, int out
             HIP_TRY(h, hipStreamWaitEvent(h->stream, h->ev_sub[s_], 0));
             FastArgs fs = fa;
             fs.b0 = sub_lo(s_); fs.B = sub_lo(s_ + 1) - sub_lo(s_);
-            { ProfScope ps(h, K_MEANSCAN); HIP_TRY(h, launch_meanscan(p.Rp, fs, h->stream)); }
+            HIP_LAUNCH(h, K_MEANSCAN, launch_meanscan(p.Rp, fs, h->stream));
         }
         if (fill) HIP_TRY(h, hipStreamWaitEvent(h->stream, h->ev_post, 0));
         return em_update();
@@ -872,10 +880,10 @@ int enqueue_pass_fast(dfm_handle* h, const Plan& p, int B, int T, int N, int out
         // The covariance kernel (128 waves, 224 VGPRs each) must be resident BEFORE the streaming collapse fills
         // every CU, or it waits for the collapse to drain (measured: 285 us instead of 90).  It therefore goes
         // first on the caller's stream, and the collapse is the forked work: its queue starts ~6 us later.
-        if (!fuse_gram || use_wide2) { ProfScope ps(h, K_GRAM); HIP_TRY(h, run_gram(h->stream)); }   // 12 us, alone
+        if (!fuse_gram || use_wide2) HIP_LAUNCH(h, K_GRAM, run_gram(h->stream));   // 12 us, alone
         HIP_TRY(h, hipEventRecord(h->ev_fork, h->stream));
         HIP_TRY(h, hipStreamWaitEvent(h->side, h->ev_fork, 0));
-        { ProfScope ps(h, K_COV); HIP_TRY(h, (h->opt.cov_wave && p.Rp == 8 && !fuse_gram) ? launch_cov_wave(fa, h->stream) : launch_cov(p.Rp, fa, h->stream)); }
+        HIP_LAUNCH(h, K_COV, (h->opt.cov_wave && p.Rp == 8 && !fuse_gram) ? launch_cov_wave(fa, h->stream) : launch_cov(p.Rp, fa, h->stream));
         { ProfScope ps(h, use_wide ? K_COLLAPSE_WIDE : use_mfma ? K_COLLAPSE_MFMA : K_COLLAPSE_DMA, h->side); HIP_TRY(h, run_collapse(ca, h->side)); }
         HIP_TRY(h, hipEventRecord(h->ev_join, h->side));
         const bool fill = !h->opt.no_pfill && P_smooth;
@@ -904,7 +912,7 @@ int enqueue_pass_fast(dfm_handle* h, const Plan& p, int B, int T, int N, int out
             fa.abl |= 1;
         }
         HIP_TRY(h, hipStreamWaitEvent(h->stream, h->ev_join, 0));
-        { ProfScope ps(h, K_MEANSCAN); HIP_TRY(h, launch_meanscan(p.Rp, fa, h->stream)); }
+        HIP_LAUNCH(h, K_MEANSCAN, launch_meanscan(p.Rp, fa, h->stream));
         if (fill_late) HIP_TRY(h, hipStreamWaitEvent(h->stream, h->ev_post, 0));
         return em_update();
     }
@@ -925,7 +933,7 @@ int enqueue_pass_fast(dfm_handle* h, const Plan& p, int B, int T, int N, int out
         const int b0 = (int)((long long)B * s / S), b1 = (int)((long long)B * (s + 1) / S);
         CollapseArgs cs = ca;
         cs.b0 = b0; cs.B = b1 - b0;
-        { ProfScope ps(h, use_mfma ? K_COLLAPSE_MFMA : K_COLLAPSE_DMA); HIP_TRY(h, launch_collapse_dma(p.Rp, cs, h->stream, cvariant)); }
+        HIP_LAUNCH(h, use_mfma ? K_COLLAPSE_MFMA : K_COLLAPSE_DMA, launch_collapse_dma(p.Rp, cs, h->stream, cvariant));
         HIP_TRY(h, hipEventRecord(h->ev_sub[s], h->stream));
         HIP_TRY(h, hipStreamWaitEvent(h->post, h->ev_sub[s], 0));
         FastArgs fs = fa;
@@ -999,7 +1007,7 @@ int enqueue_pass(dfm_handle* h, const Plan& p, int B, int T, int N, int out_r, c
             ca.lam_w = p.Rc;
             ca.obs_chunk = at<double>(h, p.ck_rows);
             ca.obs_table = at<double>(h, p.ck_obs); ca.obs_L = recursion_chunk_len(T);
-            { ProfScope ps(h, K_COLLAPSE); HIP_TRY(h, launch_collapse_miss(ca, h->num_cu, h->stream)); }
+            HIP_LAUNCH(h, K_COLLAPSE, launch_collapse_miss(ca, h->num_cu, h->stream));
             RecursionArgs ua = ra;
             ua.chunk_obs = at<double>(h, p.ck_obs);
             ua.chunk_fail = nullptr;                              // (no flags: every replicate)
@@ -1010,20 +1018,20 @@ int enqueue_pass(dfm_handle* h, const Plan& p, int B, int T, int N, int out_r, c
             ca.obs_chunk = at<double>(h, p.ck_rows);
             ca.obs_table = ra.chunk_obs; ca.obs_L = recursion_chunk_len(T);
             ra.chunk_obs_ready = 1;
-            ProfScope ps(h, K_COLLAPSE); HIP_TRY(h, launch_collapse_miss(ca, h->num_cu, h->stream));
+            HIP_LAUNCH(h, K_COLLAPSE, launch_collapse_miss(ca, h->num_cu, h->stream));
         } else
-        if (!h->opt.collapse_miss_old && collapse_miss_supported(Rcol, N)) { ProfScope ps(h, K_COLLAPSE); HIP_TRY(h, launch_collapse_miss(ca, h->num_cu, h->stream)); }
+        if (!h->opt.collapse_miss_old && collapse_miss_supported(Rcol, N)) HIP_LAUNCH(h, K_COLLAPSE, launch_collapse_miss(ca, h->num_cu, h->stream));
         else if (p.Wwide != (size_t)-1 && N > collapse_max_n(Rcol)) {   // Rp = 32 beyond the register tiling (config 4 with missing cells)
             double* W = at<double>(h, p.Wwide);
             double* V = at<double>(h, p.Vwide);
-            { ProfScope ps(h, K_GRAM); HIP_TRY(h, launch_wide_prep(ca, W, 32, h->stream, 0, V)); }
-            { ProfScope ps(h, K_COLLAPSE_WIDE); HIP_TRY(h, launch_collapse_wide2(ca, W, 32, p.r, h->num_cu, h->stream)); }
-            { ProfScope ps(h, K_COLLAPSE); HIP_TRY(h, launch_ct_miss_wide(ca, W, p.r, h->stream, V)); }
-        } else { ProfScope ps(h, K_COLLAPSE); HIP_TRY(h, launch_collapse(Rcol, ca, h->stream)); }
+            HIP_LAUNCH(h, K_GRAM, launch_wide_prep(ca, W, 32, h->stream, 0, V));
+            HIP_LAUNCH(h, K_COLLAPSE_WIDE, launch_collapse_wide2(ca, W, 32, p.r, h->num_cu, h->stream));
+            HIP_LAUNCH(h, K_COLLAPSE, launch_ct_miss_wide(ca, W, p.r, h->stream, V));
+        } else HIP_LAUNCH(h, K_COLLAPSE, launch_collapse(Rcol, ca, h->stream));
     }
     h->ck_fail_dev = nullptr; h->ck_fail_n = 0;
     if (chunked || (tiled && recursion_tile_writes_fail(ra))) { h->ck_fail_dev = ra.chunk_fail; h->ck_fail_n = B; }
-    { ProfScope ps(h, K_RECURSION); HIP_TRY(h, launch_recursion(p.Rp, ra, h->stream)); }
+    HIP_LAUNCH(h, K_RECURSION, launch_recursion(p.Rp, ra, h->stream));
     return 0;
 }
 
@@ -1063,19 +1071,17 @@ int em_iteration(dfm_handle* h, const Plan& p, int B, int T, int N, const double
         return 0;
     }
     if (p.ms_wide) {   // ... Rp = 32 (config 4): the same on the streaming machinery of its collapse
-        ProfScope ps(h, K_MSTEP_MFMA);
-        HIP_TRY(h, launch_mstep_wide(ma, at<double>(h, p.mw_ws), Rp, p.r, h->num_cu, h->stream));
+        HIP_LAUNCH(h, K_MSTEP_MFMA, launch_mstep_wide(ma, at<double>(h, p.mw_ws), Rp, p.r, h->num_cu, h->stream));
         return 0;
     }
     if (p.ms_miss) {   // panels with missing cells: both contractions of the loadings step as one product per replicate on the matrix pipe
         const int rl = p.Rc ? (p.rl ? p.rl : Rp) : (p.r < Rp ? p.r : Rp);     // the loadings' factor count
-        ProfScope ps(h, K_MSTEP_STATS);
-        HIP_TRY(h, launch_mstep_miss(ma, at<double>(h, p.mm_ws), Rp, rl, h->num_cu, h->stream));
+        HIP_LAUNCH(h, K_MSTEP_STATS, launch_mstep_miss(ma, at<double>(h, p.mm_ws), Rp, rl, h->num_cu, h->stream));
         return 0;
     }
     if (ma.Dmiss)
         HIP_TRY(h, hipMemsetAsync(ma.Dmiss, 0, (size_t)B * N * (Rp * (Rp + 1) / 2) * sizeof(double), h->stream));
-    { ProfScope ps(h, K_MSTEP_STATS); HIP_TRY(h, launch_mstep_lam(Rp, ma, h->stream)); }
+    HIP_LAUNCH(h, K_MSTEP_STATS, launch_mstep_lam(Rp, ma, h->stream));
     return 0;
 }
 
@@ -1380,7 +1386,7 @@ int ar_em_run(dfm_handle* h, int B, int T, int N, int r, int nlag, int q, const 
         const double* xin;
         if (int rc = ar_prepare(h, s, B, T, N, r, q, panel, Lam, rho, &xin)) return rc;
         if (int rc = enqueue_pass(h, p, B, T - q, N, p.Rp, xin, mb.pp(), sig2, mb.fsm, mb.Psm, mb.llbuf, &eo)) return rc;
-        { ProfScope ps(h, K_MSTEP_STATS); HIP_TRY(h, launch_mstep_ar(ma, s.mws, h->stream)); }
+        HIP_LAUNCH(h, K_MSTEP_STATS, launch_mstep_ar(ma, s.mws, h->stream));
         return 0;
     })) return rc;
     return unpad_results(h, p, B, N, T - q, r, r * nlag, s.k, mb, nullptr, Avar, Q, mu0, P0, f_smooth, P_smooth);
@@ -1481,12 +1487,12 @@ int mf_run(dfm_handle* h, int B, int T, int N, int r, int nlag, int L, const dou
     ma.panel = panel; ma.zsm = mb.fsm; ma.Psm = mb.Psm; ma.active = mb.active; ma.Wc = s.Wc;
     ma.tile_class = s.tile_class; ma.tile_series = s.tile_series; ma.Lam = Lam; ma.R = R;
     if (int rc = em_loop(h, B, 0, max_iter, max_iter, tol, loglik_path, iters, mb, true, [&](const EmOpts& eo) -> int {
-        { ProfScope ps(h, K_PAD); HIP_TRY(h, launch_mf_loadings(B, N, r, L, Rk, Lam, W, mb.Lam, h->stream)); }
+        HIP_LAUNCH(h, K_PAD, launch_mf_loadings(B, N, r, L, Rk, Lam, W, mb.Lam, h->stream));
         if (int rc = enqueue_pass(h, p, B, T, N, Rk, panel, mb.pp(), R, mb.fsm, mb.Psm, mb.llbuf, &eo)) return rc;
-        { ProfScope ps(h, K_MF_TABLE); HIP_TRY(h, launch_mf_table(ma, s.mws, h->stream)); }
-        { ProfScope ps(h, K_MF_MOMENTS); HIP_TRY(h, launch_mf_moments(ma, s.mws, h->stream)); }
-        if (free_mask) { ProfScope ps(h, K_MF_SOLVE_BLOCKS); HIP_TRY(h, launch_mf_solve_blocks(ma, free_mask, s.mws, h->stream)); }
-        else { ProfScope ps(h, K_MF_SOLVE); HIP_TRY(h, launch_mf_solve(ma, s.mws, h->stream)); }
+        HIP_LAUNCH(h, K_MF_TABLE, launch_mf_table(ma, s.mws, h->stream));
+        HIP_LAUNCH(h, K_MF_MOMENTS, launch_mf_moments(ma, s.mws, h->stream));
+        if (free_mask) HIP_LAUNCH(h, K_MF_SOLVE_BLOCKS, launch_mf_solve_blocks(ma, free_mask, s.mws, h->stream));
+        else HIP_LAUNCH(h, K_MF_SOLVE, launch_mf_solve(ma, s.mws, h->stream));
         return 0;
     })) return rc;
     return unpad_results(h, p, B, N, T, r, r * nlag, s.k, mb, nullptr, Avar, Q, mu0, P0, f_smooth, P_smooth);
@@ -1538,14 +1544,13 @@ int obs_em_run(dfm_handle* h, int B, int T, int N, int ru, int ro, const double*
     oa.B = B; oa.T = T; oa.N = N; oa.ro = ro; oa.ru = ru; oa.Rl = Rl;
     oa.panel = panel; oa.G = G; oa.fsm = mb.fsm; oa.Psm = mb.Psm; oa.active = mb.active; oa.Lam = Lam; oa.R = R;
     if (int rc = em_loop(h, B, 0, max_iter, max_iter, tol, loglik_path, iters, mb, true, [&](const EmOpts& eo) -> int {
-        { ProfScope ps(h, K_PAD); HIP_TRY(h, launch_obs_residual(oa, y, mb.Lam, h->stream)); }
+        HIP_LAUNCH(h, K_PAD, launch_obs_residual(oa, y, mb.Lam, h->stream));
         if (int rc = enqueue_pass(h, p, B, T, N, Rl, y, mb.pp(), R, mb.fsm, mb.Psm, mb.llbuf, &eo)) return rc;
         if (!wide_obs) {
-            ProfScope ps(h, K_MSTEP_STATS);
-            HIP_TRY(h, launch_mstep_obs(oa, h->stream));
+            HIP_LAUNCH(h, K_MSTEP_STATS, launch_mstep_obs(oa, h->stream));
         } else {
             double *z = at<double>(h, o_z), *Vz = at<double>(h, o_v), *LamAug = at<double>(h, o_l);
-            { ProfScope ps(h, K_PAD); HIP_TRY(h, launch_obs_augment(oa, Re, z, Vz, LamAug, at<double>(h, o_s), at<double>(h, o_i), h->stream)); }
+            HIP_LAUNCH(h, K_PAD, launch_obs_augment(oa, Re, z, Vz, LamAug, at<double>(h, o_s), at<double>(h, o_i), h->stream));
             MstepArgs ma;
             ma.B = B; ma.T = T; ma.N = N; ma.r = Re;
             ma.panel = panel; ma.fsm = z; ma.Psm = Vz; ma.S11 = at<double>(h, o_s); ma.S11inv = at<double>(h, o_i);
@@ -1553,12 +1558,105 @@ int obs_em_run(dfm_handle* h, int B, int T, int N, int ru, int ro, const double*
             ma.active = mb.active; ma.Lam_out = LamAug; ma.R_out = R; ma.lam_stride = Re;
             ma.min_cells = ro + ru + 1;                       // (as mstep_obs_kernel and the oracle: too few cells for the joint regression)
             HIP_TRY(h, hipMemsetAsync(ma.Dmiss, 0, (size_t)B * N * NPe * sizeof(double), h->stream));
-            { ProfScope ps(h, K_MSTEP_STATS); HIP_TRY(h, launch_mstep_lam(Re, ma, h->stream)); }
+            HIP_LAUNCH(h, K_MSTEP_STATS, launch_mstep_lam(Re, ma, h->stream));
             if (int rc = copy_block(h, (size_t)B * N, 1, Re, 1, ro + ru, LamAug, Lam)) return rc;   // (inactive replicates: their own values back)
         }
         return 0;
     })) return rc;
     return unpad_results(h, p, B, N, T, ru, ru, ru, mb, nullptr, A, Q, mu0, P0, f_smooth, P_smooth);
+}
+
+// ---- what the post-estimation drivers share, plain and AR-idiosyncratic (q = 0: the plain model) -----------------------------
+// Lags of the state: the factors' p, and at least q + 1 where the series' AR terms read q lags of the factors.
+int state_lags(int p, int q) { return p > q + 1 ? p : q + 1; }
+
+// The model parameters of a host-pointer entry on the device.  stage_model declares them to the entry's HostStage in the order
+// every _dev twin takes them -- Lam, R | sig2, [rho], Avar, Q, mu0, P0, [v0], mean, sd; rho and v0 with q > 0 only -- with the
+// element counts of (B, N, r, p, q).  `md` receives the pointers at st.begin(): it lives where the entry's other pointers do.
+struct ModelDev { double *Lam, *R, *rho, *A, *Q, *mu0, *P0, *v0, *mean, *sd; };
+void stage_model(HostStage& st, ModelDev& md, int B, int N, int r, int p, int q, const double* Lam, const double* R, const double* rho,
+                 const double* Avar, const double* Q, const double* mu0, const double* P0, const double* v0, const double* mean,
+                 const double* sd) {
+    const size_t n_R = (size_t)B * N, k = (size_t)r * state_lags(p, q);
+    md = ModelDev{};
+    st.in(Lam, n_R * r, md.Lam); st.in(R, n_R, md.R);
+    if (q) st.in(rho, n_R * q, md.rho);
+    st.in(Avar, (size_t)B * r * r * p, md.A); st.in(Q, (size_t)B * r * r, md.Q); st.in(mu0, (size_t)B * k, md.mu0);
+    st.in(P0, (size_t)B * k * k, md.P0);
+    if (q) st.in(v0, v0 ? n_R : 0, md.v0);
+    st.in(mean, mean ? n_R : 0, md.mean); st.in(sd, sd ? n_R : 0, md.sd);
+}
+
+// The expanded parameters of one slice of at most Smax pass replicates (simsmooth_expand_kernel; rho by
+// simsmooth_ar_expand_kernel) on a state of k: the constructor takes their room at `off` of a driver's block, in the order eLam,
+// eR, [erho], eA, eQ, emu0, eP0; once the block has grown, point() writes them into the SsArgs and returns erho (q = 0: null).
+struct SliceParams {
+    size_t L, R, rho, A, Q, m, P;
+    SliceParams(size_t& off, int Smax, int N, int r, size_t k, int q) {
+        const size_t S = (size_t)Smax, d = sizeof(double);
+        L = take(off, S * N * r * d); R = take(off, S * N * d);
+        rho = q ? take(off, S * N * q * d) : (size_t)-1;
+        A = take(off, S * r * k * d); Q = take(off, S * r * r * d); m = take(off, S * k * d); P = take(off, S * k * k * d);
+    }
+    double* point(const DevBlock& b, SsArgs& e) const {
+        e.eLam = at<double>(b, L); e.eR = at<double>(b, R); e.eA = at<double>(b, A); e.eQ = at<double>(b, Q);
+        e.emu0 = at<double>(b, m); e.eP0 = at<double>(b, P);
+        return at<double>(b, rho);
+    }
+};
+
+// The AR drivers run the plain model's kernels on m = state_lags(p, q) lags: *Am = Avar with zero blocks appended to m lags
+// (simsmooth_ar_params_kernel into Apad, which the driver planned for p < m), or the caller's Avar where p = m.
+int pad_avar(dfm_handle* h, int B, int r, int p, int m, const double* Avar, double* Apad, const double** Am) {
+    *Am = Avar;
+    if (p < m) {
+        HIP_LAUNCH(h, K_SSAR_PARAMS, launch_simsmooth_ar_params(B, r, p, m, Avar, Apad, h->stream));
+        *Am = Apad;
+    }
+    return 0;
+}
+
+// The target loop of both news checks: rows in [t_lo, 2^30), series in [0, N); *H = the horizon the targets need.
+bool news_targets(int T, int N, int G, const int* target_t, const int* target_i, int t_lo, int* H) {
+    int tmax = 0;
+    for (int g = 0; g < G; ++g) {
+        if (target_t[g] < t_lo || target_t[g] > 0x3fffffff || target_i[g] < 0 || target_i[g] >= N) return false;
+        if (target_t[g] > tmax) tmax = target_t[g];
+    }
+    *H = tmax + 1 > T ? tmax + 1 - T : 0;
+    return true;
+}
+
+// The targets as (row - shift, series) pairs at tgt [G][2] of the device (shift = q: output rows of the AR forecasts).
+int news_stage_targets(dfm_handle* h, int G, const int* target_t, const int* target_i, int shift, int* tgt) {
+    std::vector<int> tg((size_t)2 * G);                       // (a pageable source: staged before the call returns)
+    for (int g = 0; g < G; ++g) { tg[2 * g] = target_t[g] - shift; tg[2 * g + 1] = target_i[g]; }
+    HIP_TRY(h, hipMemcpyAsync(tgt, tg.data(), tg.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    return 0;
+}
+
+// The three conditional means of both news drivers -- old, new, then the revised old panel `rev`, whose xhat stays behind for the
+// impacts: forecast(panel, loglik, flags) runs one into xhat, news_gather_kernel (ga) picks the targets out of it.  The logliks go
+// to ll_all [3][B] (old, revised, new), else all to ll_own.
+template <class Forecast>
+int news_forecasts(dfm_handle* h, int B, const NwArgs& ga, const double* oldp, const double* newp, const double* rev,
+                   const double* xhat, double* ll_all, double* ll_own, unsigned flags, Forecast forecast) {
+    const struct { const double* panel; unsigned fl; int which; } runs[3] = {
+        {oldp, flags | DFM_F_MAY_HAVE_MISSING, 0}, {newp, flags, 2}, {rev, flags | DFM_F_MAY_HAVE_MISSING, 1}};
+    for (const auto& run : runs) {
+        if (int rc = forecast(run.panel, ll_all ? ll_all + (size_t)run.which * B : ll_own, run.fl)) return rc;
+        HIP_LAUNCH(h, K_NW_GATHER, launch_news_gather(ga, xhat, run.which, h->stream));
+    }
+    return 0;
+}
+
+// The tail of a Gibbs sweep, for both samplers: sweep j is kept when it is past the burn-in and on the thinning grid, as slot
+// (j - burn) / thin of K; gibbs_keep copies one parameter of it, dst [B][K][per] <- src [B][per], behind the sweep (dst null: not wanted).
+bool gibbs_kept_slot(int j, int burn, int thin) { return j >= burn && (j - burn) % thin == 0; }
+hipError_t gibbs_keep(dfm_handle* h, double* dst, const double* src, size_t per, size_t kk, size_t K, int B) {
+    const size_t d = sizeof(double);
+    return dst ? hipMemcpy2DAsync(dst + kk * per, K * per * d, src, per * d, per * d, (size_t)B, hipMemcpyDeviceToDevice, h->stream)
+               : hipSuccess;
 }
 
 }  // namespace
@@ -1948,7 +2046,7 @@ static int ar_host(dfm_handle* h, int B, int T, int N, int r, int p, int q, cons
     if (int rc = check_dims(h, B, T, N, r)) return rc;
     if (p < 1 || q < 0 || T <= q + (em ? 1 : 0))
         return fail(h, DFM_E_DIMS, em ? "need p >= 1, 0 <= q < T - 1%s" : "need p >= 1, 0 <= q < T%s");
-    const int m = p > q + 1 ? p : q + 1;
+    const int m = state_lags(p, q);
     if (r * m > DFM_MAX_R) return fail(h, DFM_E_R_UNSUPPORTED, "r * max(p, q + 1) > DFM_MAX_R (32)%s");
     if (!panel || !Lam || !sig2 || (q > 0 && !rho) || !Avar || !Q || !mu0 || !P0 || !loglik_path || (em ? !iters : !f_smooth))
         return fail(h, DFM_E_NULL, "required pointer is NULL%s");
@@ -2124,8 +2222,8 @@ int dfm_pca_init_batch_dev(dfm_handle* h, int B, int T, int N, int r, const doub
     pa.S = at<double>(h, oS); pa.V = at<double>(h, oV); pa.Y = at<double>(h, oY); pa.F = at<double>(h, oF);
     pa.Lam = Lam; pa.Rv = R; pa.A = A; pa.Q = Q; pa.mu0 = mu0; pa.P0 = P0; pa.factors = factors;
     pa.status = h->status_dev;
-    { ProfScope ps(h, K_GRAM_XX); HIP_TRY(h, launch_gram_xx(pa, h->stream, h->opt.gram_xx_valu ? 1 : 0)); }
-    { ProfScope ps(h, K_PCA); HIP_TRY(h, launch_pca(Rp, pa, h->stream)); }
+    HIP_LAUNCH(h, K_GRAM_XX, launch_gram_xx(pa, h->stream, h->opt.gram_xx_valu ? 1 : 0));
+    HIP_LAUNCH(h, K_PCA, launch_pca(Rp, pa, h->stream));
     return 0;
 }
 
@@ -2167,7 +2265,7 @@ int dfm_synth_panels_dev(dfm_handle* h, uint64_t seed, int64_t first_replicate, 
     sa.panel = panel; sa.Lam = Lam; sa.R = R; sa.A = A; sa.Q = Q; sa.mu0 = mu0; sa.P0 = P0;
     sa.fscratch = at<double>(h, oF);
     sa.colstats = at<double>(h, oC);
-    { ProfScope ps(h, K_SYNTH); HIP_TRY(h, launch_synth(sa, h->stream)); }
+    HIP_LAUNCH(h, K_SYNTH, launch_synth(sa, h->stream));
     return 0;
 }
 
@@ -2191,7 +2289,7 @@ int dfm_als_batch_dev(dfm_handle* h, int B, int T, int N, int r, const double* z
     a.B = B; a.T = T; a.N = N; a.rmax = r; a.z = z; a.z_stride = z_stride; a.r_each = r_each; a.F = F; a.Lam = Lam;
     a.nt_min = nt_min; a.max_iter = max_iter; a.tol = tol; a.ssr_path = ssr_path; a.path_cap = ssr_path ? path_cap : 0;
     a.iters = iters; a.ssr = ssr; a.R2 = R2;
-    { ProfScope ps(h, K_ALS); HIP_TRY(h, launch_als(Rp, a, h->stream)); }
+    HIP_LAUNCH(h, K_ALS, launch_als(Rp, a, h->stream));
     return 0;
 }
 
@@ -2226,7 +2324,7 @@ int dfm_ols_batch_dev(dfm_handle* h, int P, int T, int K, const double* X, long 
     memset(&a, 0, sizeof(a));
     a.P = P; a.T = T; a.K = K; a.X = X; a.x_stride = x_stride; a.y = y; a.y_stride = y_stride; a.y_inc = y_inc;
     a.nt_min = nt_min; a.beta = beta; a.resid = resid; a.ssr = ssr; a.tss = tss; a.nobs = nobs;
-    { ProfScope ps(h, K_OLS); HIP_TRY(h, launch_ols(K > 32 ? 64 : pad_r(K), a, h->stream)); }
+    HIP_LAUNCH(h, K_OLS, launch_ols(K > 32 ? 64 : pad_r(K), a, h->stream));
     return 0;
 }
 
@@ -2294,7 +2392,7 @@ int dfm_quantile_bands_dev(dfm_handle* h, int B, int S, int nq, const double* x,
     HIP_TRY(h, hipSetDevice(h->device));
     QuantArgs a;
     a.B = B; a.S = S; a.nq = nq; a.x = x; a.q = q; a.out = out;
-    { ProfScope ps(h, K_QUANT); HIP_TRY(h, launch_quantiles(a, h->stream)); }
+    HIP_LAUNCH(h, K_QUANT, launch_quantiles(a, h->stream));
     return 0;
 }
 
@@ -2323,7 +2421,7 @@ int dfm_chow_batch_dev(dfm_handle* h, int S, int Tmax, int k, const double* y, c
     ChowArgs a;
     a.S = S; a.Tmax = Tmax; a.k = k; a.P = P; a.y = y; a.X = X; a.Tlen = Tlen; a.prob_series = prob_series;
     a.prob_break = prob_break; a.prob_q = prob_q; a.chow = chow;
-    { ProfScope ps(h, K_CHOW); HIP_TRY(h, launch_chow(a, h->stream)); }
+    HIP_LAUNCH(h, K_CHOW, launch_chow(a, h->stream));
     return 0;
 }
 
@@ -2402,8 +2500,7 @@ int dfm_forecast_batch_dev(dfm_handle* h, int B, int T, int N, int r, int p, int
                                            loglik ? loglik : at<double>(h->fc, o_ll), flags)) return rc;
         if (H) {
             FcTailArgs ta{B, T, H, r, fsm, Psm, Avar, Q, ft, Pt};
-            ProfScope ps(h, K_FC_TAIL);
-            HIP_TRY(h, launch_forecast_tail(ta, h->stream));
+            HIP_LAUNCH(h, K_FC_TAIL, launch_forecast_tail(ta, h->stream));
         }
         fa.panel = panel; fa.panel_rows = T;
         fa.fh = fsm; fa.Ph = needP ? Psm : nullptr; fa.Th = T; fa.ft = ft; fa.Pt = Pt;
@@ -2414,10 +2511,7 @@ int dfm_forecast_batch_dev(dfm_handle* h, int B, int T, int N, int r, int p, int
         const size_t o_P = (!P_out && xvar) ? take(off, (size_t)B * TH * np * d) : (size_t)-1, o_ll = take(off, (size_t)B * d);
         HIP_TRY(h, h->fc.grow(off));
         if (o_P != (size_t)-1) Pbuf = at<double>(h->fc, o_P);
-        {
-            ProfScope ps(h, K_FC_PAD);
-            HIP_TRY(h, launch_forecast_pad(B, T, H, N, panel, xhat, !(flags & DFM_F_MAY_HAVE_MISSING), h->status_dev, h->stream));
-        }
+        HIP_LAUNCH(h, K_FC_PAD, launch_forecast_pad(B, T, H, N, panel, xhat, !(flags & DFM_F_MAY_HAVE_MISSING), h->status_dev, h->stream));
         if (int rc = dfm_ks_pass_varp_batch_dev(h, B, (int)TH, N, r, p, xhat, Lam, R, Avar, Q, mu0, P0, f_out, Pbuf,
                                                 loglik ? loglik : at<double>(h->fc, o_ll),
                                                 flags | DFM_F_MAY_HAVE_MISSING)) return rc;
@@ -2425,8 +2519,7 @@ int dfm_forecast_batch_dev(dfm_handle* h, int B, int T, int N, int r, int p, int
         fa.fh = f_out; fa.Ph = xvar ? Pbuf : nullptr; fa.Th = (int)TH; fa.ft = nullptr; fa.Pt = nullptr;
         fa.f_out = nullptr; fa.P_out = nullptr;
     }
-    ProfScope ps(h, K_FC_FILL);
-    HIP_TRY(h, launch_forecast_fill(fa, h->stream));
+    HIP_LAUNCH(h, K_FC_FILL, launch_forecast_fill(fa, h->stream));
     return 0;
 }
 
@@ -2437,18 +2530,18 @@ int dfm_forecast_batch(dfm_handle* h, int B, int T, int N, int r, int p, int H, 
     if (int rc = forecast_check(h, B, T, N, r, p, H, panel, Lam, R, Avar, Q, mu0, P0, mean, sd, xhat, f_out)) return rc;
     if (int rc = status_epoch(h)) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
-    const size_t k = (size_t)r * p, np = (size_t)r * (r + 1) / 2, TH = (size_t)T + H, n_R = (size_t)B * N, n_x = (size_t)B * TH * N;
+    const size_t np = (size_t)r * (r + 1) / 2, TH = (size_t)T + H, n_x = (size_t)B * TH * N;
     std::vector<double> ll_host((size_t)B);                     // (checked before the caller's loglik, which is optional, is written)
     HostStage st(h, 256);
-    double *x_d, *lam_d, *R_d, *A_d, *Q_d, *mu_d, *P0_d, *mean_d, *sd_d, *xh_d, *xv_d, *cm_d, *f_d, *P_d, *ll_d;
-    st.in(panel, (size_t)B * T * N, x_d); st.in(Lam, (size_t)B * N * r, lam_d); st.in(R, n_R, R_d); st.in(Avar, (size_t)B * r * k, A_d);
-    st.in(Q, (size_t)B * r * r, Q_d); st.in(mu0, (size_t)B * k, mu_d); st.in(P0, (size_t)B * k * k, P0_d);
-    st.in(mean, mean ? n_R : 0, mean_d); st.in(sd, sd ? n_R : 0, sd_d);
+    ModelDev md;
+    double *x_d, *xh_d, *xv_d, *cm_d, *f_d, *P_d, *ll_d;
+    st.in(panel, (size_t)B * T * N, x_d);
+    stage_model(st, md, B, N, r, p, 0, Lam, R, nullptr, Avar, Q, mu0, P0, nullptr, mean, sd);
     st.out(xhat, n_x, xh_d); st.out(xvar, xvar ? n_x : 0, xv_d); st.out(common, common ? n_x : 0, cm_d);
     st.out(f_out, (size_t)B * TH * r, f_d); st.out(P_out, P_out ? (size_t)B * TH * np : 0, P_d); st.out(ll_host.data(), (size_t)B, ll_d);
     if (int rc = st.begin()) return rc;
-    int rc = st.finish(dfm_forecast_batch_dev(h, B, T, N, r, p, H, x_d, lam_d, R_d, A_d, Q_d, mu_d, P0_d, mean_d, sd_d, xh_d, xv_d, cm_d,
-                                              f_d, P_d, ll_d, flags));
+    int rc = st.finish(dfm_forecast_batch_dev(h, B, T, N, r, p, H, x_d, md.Lam, md.R, md.A, md.Q, md.mu0, md.P0, md.mean, md.sd, xh_d, xv_d,
+                                              cm_d, f_d, P_d, ll_d, flags));
     if (rc == 0) rc = post_check(h, ll_host.data(), B);
     if (rc == 0 && loglik) memcpy(loglik, ll_host.data(), (size_t)B * sizeof(double));
     return rc;
@@ -2496,10 +2589,7 @@ int dfm_forecast_ar_batch_dev(dfm_handle* h, int B, int T, int N, int r, int p, 
     HIP_TRY(h, h->fc.grow(off));
     double* xpad = at<double>(h->fc, o_x);
     double* Pbuf = P_out ? P_out : at<double>(h->fc, o_P);
-    {
-        ProfScope ps(h, K_FC_PAD);
-        HIP_TRY(h, launch_forecast_pad(B, T, H, N, panel, xpad, !(flags & DFM_F_MAY_HAVE_MISSING), h->status_dev, h->stream));
-    }
+    HIP_LAUNCH(h, K_FC_PAD, launch_forecast_pad(B, T, H, N, panel, xpad, !(flags & DFM_F_MAY_HAVE_MISSING), h->status_dev, h->stream));
     if (int rc = ar_pass_run(h, B, (int)TH, N, r, p, q, xpad, Lam, sig2, rho, Avar, Q, mu0, P0, f_out, Pbuf,
                              loglik ? loglik : at<double>(h->fc, o_ll), flags | DFM_F_MAY_HAVE_MISSING)) return rc;
     FcArArgs a{};
@@ -2510,14 +2600,8 @@ int dfm_forecast_ar_batch_dev(dfm_handle* h, int B, int T, int N, int r, int p, 
     a.xhat = xhat; a.xvar = xvar; a.common = common; a.idio = idio;
     for (size_t b0 = 0; b0 < (size_t)B; b0 += Sl) {
         a.b0 = (int)b0; a.S = (int)((size_t)B - b0 < Sl ? (size_t)B - b0 : Sl);
-        {
-            ProfScope ps(h, K_FCAR_BACK);
-            HIP_TRY(h, launch_forecast_ar_back(a, h->stream));
-        }
-        {
-            ProfScope ps(h, K_FCAR_FWD);
-            HIP_TRY(h, launch_forecast_ar_fwd(a, h->stream));
-        }
+        HIP_LAUNCH(h, K_FCAR_BACK, launch_forecast_ar_back(a, h->stream));
+        HIP_LAUNCH(h, K_FCAR_FWD, launch_forecast_ar_fwd(a, h->stream));
     }
     return 0;
 }
@@ -2529,19 +2613,18 @@ int dfm_forecast_ar_batch(dfm_handle* h, int B, int T, int N, int r, int p, int 
     if (int rc = forecast_ar_check(h, B, T, N, r, p, q, H, panel, Lam, sig2, rho, Avar, Q, mu0, P0, mean, sd, xhat, f_out)) return rc;
     if (int rc = status_epoch(h)) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
-    const size_t m = (size_t)(p > q + 1 ? p : q + 1), k = (size_t)r * m, np = (size_t)r * (r + 1) / 2, n = (size_t)T + H - q,
-                 n_R = (size_t)B * N, n_x = (size_t)B * n * N;
+    const size_t np = (size_t)r * (r + 1) / 2, n = (size_t)T + H - q, n_x = (size_t)B * n * N;
     std::vector<double> ll_host((size_t)B);                     // (checked before the caller's loglik, which is optional, is written)
     HostStage st(h, 256);
-    double *x_d, *lam_d, *R_d, *rho_d, *A_d, *Q_d, *mu_d, *P0_d, *v0_d, *mean_d, *sd_d, *xh_d, *xv_d, *cm_d, *id_d, *f_d, *P_d, *ll_d;
-    st.in(panel, (size_t)B * T * N, x_d); st.in(Lam, (size_t)B * N * r, lam_d); st.in(sig2, n_R, R_d); st.in(rho, n_R * q, rho_d);
-    st.in(Avar, (size_t)B * r * r * p, A_d); st.in(Q, (size_t)B * r * r, Q_d); st.in(mu0, (size_t)B * k, mu_d); st.in(P0, (size_t)B * k * k, P0_d);
-    st.in(v0, v0 ? n_R : 0, v0_d); st.in(mean, mean ? n_R : 0, mean_d); st.in(sd, sd ? n_R : 0, sd_d);
+    ModelDev md;
+    double *x_d, *xh_d, *xv_d, *cm_d, *id_d, *f_d, *P_d, *ll_d;
+    st.in(panel, (size_t)B * T * N, x_d);
+    stage_model(st, md, B, N, r, p, q, Lam, sig2, rho, Avar, Q, mu0, P0, v0, mean, sd);
     st.out(xhat, n_x, xh_d); st.out(xvar, xvar ? n_x : 0, xv_d); st.out(common, common ? n_x : 0, cm_d); st.out(idio, idio ? n_x : 0, id_d);
     st.out(f_out, (size_t)B * n * r, f_d); st.out(P_out, P_out ? (size_t)B * n * np : 0, P_d); st.out(ll_host.data(), (size_t)B, ll_d);
     if (int rc = st.begin()) return rc;
-    int rc = st.finish(dfm_forecast_ar_batch_dev(h, B, T, N, r, p, q, H, x_d, lam_d, R_d, rho_d, A_d, Q_d, mu_d, P0_d, v0_d, mean_d, sd_d,
-                                                 xh_d, xv_d, cm_d, id_d, f_d, P_d, ll_d, flags));
+    int rc = st.finish(dfm_forecast_ar_batch_dev(h, B, T, N, r, p, q, H, x_d, md.Lam, md.R, md.rho, md.A, md.Q, md.mu0, md.P0, md.v0, md.mean,
+                                                 md.sd, xh_d, xv_d, cm_d, id_d, f_d, P_d, ll_d, flags));
     if (rc == 0) rc = post_check(h, ll_host.data(), B);
     if (rc == 0 && loglik) memcpy(loglik, ll_host.data(), (size_t)B * sizeof(double));
     return rc;
@@ -2587,49 +2670,29 @@ static int simsmooth_run(dfm_handle* h, int B, int D, int T, int N, int r, int p
     const long long BD = (long long)B * D;
     const int Smax = (int)(BD < kSsSlice ? BD : kSsSlice);
     size_t off = 0;
-    const size_t o_LP0 = take(off, (size_t)B * k * k * d), o_LQ = take(off, (size_t)B * r * r * d),
-                 o_L = take(off, (size_t)Smax * N * r * d), o_R = take(off, (size_t)Smax * N * d),
-                 o_A = take(off, (size_t)Smax * r * k * d), o_Q = take(off, (size_t)Smax * r * r * d),
-                 o_m = take(off, (size_t)Smax * k * d), o_P = take(off, (size_t)Smax * k * k * d),
-                 o_g = take(off, (size_t)Smax * T * r * d), o_ll = ll_all ? (size_t)-1 : take(off, (size_t)Smax * d),
+    const size_t o_LP0 = take(off, (size_t)B * k * k * d), o_LQ = take(off, (size_t)B * r * r * d);
+    const SliceParams sp(off, Smax, N, r, k, 0);
+    const size_t o_g = take(off, (size_t)Smax * T * r * d), o_ll = ll_all ? (size_t)-1 : take(off, (size_t)Smax * d),
                  o_x = x_draw ? (size_t)-1 : take(off, (size_t)Smax * T * N * d);
     HIP_TRY(h, h->ss.grow(off));
     SsArgs a{};
     a.B = B; a.D = D; a.T = T; a.N = N; a.r = r; a.p = p; a.H = H;
     a.panel = panel; a.Lam = Lam; a.R = R; a.A = Avar; a.Q = Q; a.mu0 = mu0; a.P0 = P0; a.mean = mean; a.sd = sd;
     a.seed = seed; a.first_draw = first_draw; a.f_draw = f_draw; a.x_draw = x_draw;
-    a.LP0 = at<double>(h->ss, o_LP0); a.LQ = at<double>(h->ss, o_LQ);
-    a.eLam = at<double>(h->ss, o_L); a.eR = at<double>(h->ss, o_R); a.eA = at<double>(h->ss, o_A); a.eQ = at<double>(h->ss, o_Q); a.emu0 = at<double>(h->ss, o_m); a.eP0 = at<double>(h->ss, o_P); a.g = at<double>(h->ss, o_g);
-    {
-        ProfScope ps(h, K_SS_PREP);
-        HIP_TRY(h, launch_simsmooth_prep(a, h->stream));
-    }
+    a.LP0 = at<double>(h->ss, o_LP0); a.LQ = at<double>(h->ss, o_LQ); a.g = at<double>(h->ss, o_g);
+    sp.point(h->ss, a);
+    HIP_LAUNCH(h, K_SS_PREP, launch_simsmooth_prep(a, h->stream));
     for (long long j0 = 0; j0 < BD; j0 += Smax) {
         const int S = (int)(BD - j0 < Smax ? BD - j0 : Smax);
         a.j0 = j0; a.S = S;
         a.diff = x_draw ? x_draw + (size_t)j0 * TH * N : at<double>(h->ss, o_x);
         double* ll = ll_all ? ll_all + j0 : at<double>(h->ss, o_ll);
-        {
-            ProfScope ps(h, K_SS_EXPAND);
-            HIP_TRY(h, launch_simsmooth_expand(a, h->stream));
-        }
-        {
-            ProfScope ps(h, K_SS_PATH);
-            HIP_TRY(h, launch_simsmooth_path(a, h->stream));
-        }
-        {
-            ProfScope ps(h, K_SS_DIFF);
-            HIP_TRY(h, launch_simsmooth_diff(a, h->stream));
-        }
+        HIP_LAUNCH(h, K_SS_EXPAND, launch_simsmooth_expand(a, h->stream));
+        HIP_LAUNCH(h, K_SS_PATH, launch_simsmooth_path(a, h->stream));
+        HIP_LAUNCH(h, K_SS_DIFF, launch_simsmooth_diff(a, h->stream));
         if (int rc = slice_pass(h, S, T, N, r, p, a.diff, a, at<double>(h->ss, o_g), ll, flags)) return rc;
-        {
-            ProfScope ps(h, K_SS_FINISH);
-            HIP_TRY(h, launch_simsmooth_finish(a, h->stream));
-        }
-        if (x_draw) {
-            ProfScope ps(h, K_SS_FILL);
-            HIP_TRY(h, launch_simsmooth_fill(a, h->stream));
-        }
+        HIP_LAUNCH(h, K_SS_FINISH, launch_simsmooth_finish(a, h->stream));
+        if (x_draw) HIP_LAUNCH(h, K_SS_FILL, launch_simsmooth_fill(a, h->stream));
     }
     return 0;
 }
@@ -2650,17 +2713,17 @@ int dfm_simsmooth_batch(dfm_handle* h, int B, int D, int T, int N, int r, int p,
     if (int rc = simsmooth_check(h, B, D, T, N, r, p, H, panel, Lam, R, Avar, Q, mu0, P0, mean, sd, f_draw)) return rc;
     if (int rc = status_epoch(h)) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
-    const size_t k = (size_t)r * p, TH = (size_t)T + H, BD = (size_t)B * D, n_R = (size_t)B * N;
+    const size_t TH = (size_t)T + H, BD = (size_t)B * D;
     std::vector<double> ll_host(BD);
     HostStage st(h, 256);
-    double *x_d, *lam_d, *R_d, *A_d, *Q_d, *mu_d, *P0_d, *mean_d, *sd_d, *f_d, *xo_d, *ll_d;
-    st.in(panel, (size_t)B * T * N, x_d); st.in(Lam, (size_t)B * N * r, lam_d); st.in(R, n_R, R_d); st.in(Avar, (size_t)B * r * k, A_d);
-    st.in(Q, (size_t)B * r * r, Q_d); st.in(mu0, (size_t)B * k, mu_d); st.in(P0, (size_t)B * k * k, P0_d);
-    st.in(mean, mean ? n_R : 0, mean_d); st.in(sd, sd ? n_R : 0, sd_d);
+    ModelDev md;
+    double *x_d, *f_d, *xo_d, *ll_d;
+    st.in(panel, (size_t)B * T * N, x_d);
+    stage_model(st, md, B, N, r, p, 0, Lam, R, nullptr, Avar, Q, mu0, P0, nullptr, mean, sd);
     st.out(f_draw, BD * TH * r, f_d); st.out(x_draw, x_draw ? BD * TH * N : 0, xo_d); st.out(ll_host.data(), BD, ll_d);
     if (int rc = st.begin()) return rc;
-    int rc = st.finish(simsmooth_run(h, B, D, T, N, r, p, H, x_d, lam_d, R_d, A_d, Q_d, mu_d, P0_d, mean_d, sd_d, seed, first_draw, f_d,
-                                     xo_d, ll_d, flags));
+    int rc = st.finish(simsmooth_run(h, B, D, T, N, r, p, H, x_d, md.Lam, md.R, md.A, md.Q, md.mu0, md.P0, md.mean, md.sd, seed, first_draw,
+                                     f_d, xo_d, ll_d, flags));
     if (rc == 0) rc = post_check(h, ll_host.data(), (int)BD);
     return rc;
 }
@@ -2690,7 +2753,7 @@ static int simsmooth_ar_run(dfm_handle* h, int B, int D, int T, int N, int r, in
                             const double* mu0, const double* P0, const double* v0, const double* mean, const double* sd,
                             uint64_t seed, int64_t first_draw, double* f_draw, double* x_draw, double* ll_all, unsigned flags) {
     HIP_TRY(h, hipSetDevice(h->device));
-    const int m = p > q + 1 ? p : q + 1;
+    const int m = state_lags(p, q);
     const size_t d = sizeof(double), k = (size_t)r * m, TH = (size_t)T + H, n = TH - q;
     const long long BD = (long long)B * D;
     const size_t per = forecast_ar_msg_bytes((int)n, N, q);
@@ -2700,30 +2763,22 @@ static int simsmooth_ar_run(dfm_handle* h, int B, int D, int T, int N, int r, in
     const int Smax = (int)(BD < (long long)Sl ? BD : (long long)Sl);
     size_t off = 0;
     const size_t o_LP0 = take(off, (size_t)B * k * k * d), o_LQ = take(off, (size_t)B * r * r * d),
-                 o_Ap = p < m ? take(off, (size_t)B * r * k * d) : (size_t)-1,
-                 o_L = take(off, (size_t)Smax * N * r * d), o_R = take(off, (size_t)Smax * N * d),
-                 o_rho = take(off, (size_t)Smax * N * q * d), o_A = take(off, (size_t)Smax * r * k * d),
-                 o_Q = take(off, (size_t)Smax * r * r * d), o_m = take(off, (size_t)Smax * k * d),
-                 o_P = take(off, (size_t)Smax * k * k * d), o_g = take(off, (size_t)Smax * n * r * d),
+                 o_Ap = p < m ? take(off, (size_t)B * r * k * d) : (size_t)-1;
+    const SliceParams sp(off, Smax, N, r, k, q);
+    const size_t o_g = take(off, (size_t)Smax * n * r * d),
                  o_ll = ll_all ? (size_t)-1 : take(off, (size_t)Smax * d), o_x = take(off, (size_t)Smax * TH * N * d),
                  o_msg = x_draw ? take(off, (size_t)Smax * per) : (size_t)-1,
                  o_last = x_draw ? take(off, (size_t)Smax * N * sizeof(int)) : (size_t)-1;
     HIP_TRY(h, h->ss.grow(off));
-    const double* Am = Avar;
-    if (p < m) {
-        ProfScope ps(h, K_SSAR_PARAMS);
-        HIP_TRY(h, launch_simsmooth_ar_params(B, r, p, m, Avar, at<double>(h->ss, o_Ap), h->stream));
-        Am = at<double>(h->ss, o_Ap);
-    }
+    const double* Am;
+    if (int rc = pad_avar(h, B, r, p, m, Avar, at<double>(h->ss, o_Ap), &Am)) return rc;
     // the factor side: the plain model's kernels on m lags and n rows
     SsArgs a{};
     a.B = B; a.D = D; a.T = (int)n; a.N = N; a.r = r; a.p = m; a.H = 0;
     a.Lam = Lam; a.R = sig2; a.A = Am; a.Q = Q; a.mu0 = mu0; a.P0 = P0;
     a.seed = seed; a.first_draw = first_draw; a.f_draw = f_draw;
     a.LP0 = at<double>(h->ss, o_LP0); a.LQ = at<double>(h->ss, o_LQ);
-    a.eLam = at<double>(h->ss, o_L); a.eR = at<double>(h->ss, o_R); a.eA = at<double>(h->ss, o_A); a.eQ = at<double>(h->ss, o_Q);
-    a.emu0 = at<double>(h->ss, o_m); a.eP0 = at<double>(h->ss, o_P);
-    double* erho = at<double>(h->ss, o_rho);
+    double* erho = sp.point(h->ss, a);
     double* g = at<double>(h->ss, o_g);
     double* diff = at<double>(h->ss, o_x);
     // the series side: the generator and the assembling forward kernel read the caller's parameters, the backward kernel the slice's
@@ -2738,45 +2793,23 @@ static int simsmooth_ar_run(dfm_handle* h, int B, int D, int T, int N, int r, in
     back.n = (int)n; back.N = N; back.r = r; back.q = q;
     back.panel = diff; back.f = g; back.Lam = a.eLam; back.sig2 = a.eR; back.rho = erho;
     back.msg = gen.msg; back.last = gen.last;
-    {
-        ProfScope ps(h, K_SS_PREP);
-        HIP_TRY(h, launch_simsmooth_prep(a, h->stream));
-    }
+    HIP_LAUNCH(h, K_SS_PREP, launch_simsmooth_prep(a, h->stream));
     for (long long j0 = 0; j0 < BD; j0 += Smax) {
         const int S = (int)(BD - j0 < Smax ? BD - j0 : Smax);
         a.j0 = j0; a.S = S;
         gen.dr.j0 = j0; gen.S = S; back.b0 = 0; back.S = S;
         double* ll = ll_all ? ll_all + j0 : at<double>(h->ss, o_ll);
-        {
-            ProfScope ps(h, K_SS_EXPAND);
-            HIP_TRY(h, launch_simsmooth_expand(a, h->stream));
-        }
-        {
-            ProfScope ps(h, K_SSAR_EXPAND);
-            HIP_TRY(h, launch_simsmooth_ar_expand(S, j0, D, (size_t)N * q, rho, erho, h->stream));
-        }
-        {
-            ProfScope ps(h, K_SS_PATH);
-            HIP_TRY(h, launch_simsmooth_path(a, h->stream));
-        }
-        {
-            ProfScope ps(h, K_SSAR_DIFF);
-            HIP_TRY(h, launch_simsmooth_ar_diff(gen, h->stream));
-        }
+        HIP_LAUNCH(h, K_SS_EXPAND, launch_simsmooth_expand(a, h->stream));
+        HIP_LAUNCH(h, K_SSAR_EXPAND, launch_simsmooth_ar_expand(S, j0, D, (size_t)N * q, rho, erho, h->stream));
+        HIP_LAUNCH(h, K_SS_PATH, launch_simsmooth_path(a, h->stream));
+        HIP_LAUNCH(h, K_SSAR_DIFF, launch_simsmooth_ar_diff(gen, h->stream));
         if (int rc = ar_pass_run(h, S, (int)TH, N, r, m, q, diff, a.eLam, a.eR, erho, a.eA, a.eQ, a.emu0, a.eP0, g, nullptr, ll,
                                  flags | DFM_F_MAY_HAVE_MISSING)) return rc;
         if (x_draw) {
-            {
-                ProfScope ps(h, K_FCAR_BACK);
-                HIP_TRY(h, launch_forecast_ar_back(back, h->stream));
-            }
-            ProfScope ps(h, K_SSAR_FWD);
-            HIP_TRY(h, launch_simsmooth_ar_fwd(gen, h->stream));
+            HIP_LAUNCH(h, K_FCAR_BACK, launch_forecast_ar_back(back, h->stream));
+            HIP_LAUNCH(h, K_SSAR_FWD, launch_simsmooth_ar_fwd(gen, h->stream));
         }
-        {
-            ProfScope ps(h, K_SSAR_FINISH);
-            HIP_TRY(h, launch_simsmooth_ar_finish((size_t)S * n * r, g, f_draw + (size_t)j0 * n * r, h->stream));
-        }
+        HIP_LAUNCH(h, K_SSAR_FINISH, launch_simsmooth_ar_finish((size_t)S * n * r, g, f_draw + (size_t)j0 * n * r, h->stream));
     }
     return 0;
 }
@@ -2797,17 +2830,17 @@ int dfm_simsmooth_ar_batch(dfm_handle* h, int B, int D, int T, int N, int r, int
     if (int rc = simsmooth_ar_check(h, B, D, T, N, r, p, q, H, panel, Lam, sig2, rho, Avar, Q, mu0, P0, mean, sd, f_draw)) return rc;
     if (int rc = status_epoch(h)) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
-    const size_t m = (size_t)(p > q + 1 ? p : q + 1), k = (size_t)r * m, n = (size_t)T + H - q, BD = (size_t)B * D, n_R = (size_t)B * N;
+    const size_t n = (size_t)T + H - q, BD = (size_t)B * D;
     std::vector<double> ll_host(BD);
     HostStage st(h, 256);
-    double *x_d, *lam_d, *R_d, *rho_d, *A_d, *Q_d, *mu_d, *P0_d, *v0_d, *mean_d, *sd_d, *f_d, *xo_d, *ll_d;
-    st.in(panel, (size_t)B * T * N, x_d); st.in(Lam, (size_t)B * N * r, lam_d); st.in(sig2, n_R, R_d); st.in(rho, n_R * q, rho_d);
-    st.in(Avar, (size_t)B * r * r * p, A_d); st.in(Q, (size_t)B * r * r, Q_d); st.in(mu0, (size_t)B * k, mu_d); st.in(P0, (size_t)B * k * k, P0_d);
-    st.in(v0, v0 ? n_R : 0, v0_d); st.in(mean, mean ? n_R : 0, mean_d); st.in(sd, sd ? n_R : 0, sd_d);
+    ModelDev md;
+    double *x_d, *f_d, *xo_d, *ll_d;
+    st.in(panel, (size_t)B * T * N, x_d);
+    stage_model(st, md, B, N, r, p, q, Lam, sig2, rho, Avar, Q, mu0, P0, v0, mean, sd);
     st.out(f_draw, BD * n * r, f_d); st.out(x_draw, x_draw ? BD * n * N : 0, xo_d); st.out(ll_host.data(), BD, ll_d);
     if (int rc = st.begin()) return rc;
-    int rc = st.finish(simsmooth_ar_run(h, B, D, T, N, r, p, q, H, x_d, lam_d, R_d, rho_d, A_d, Q_d, mu_d, P0_d, v0_d, mean_d, sd_d, seed,
-                                        first_draw, f_d, xo_d, ll_d, flags));
+    int rc = st.finish(simsmooth_ar_run(h, B, D, T, N, r, p, q, H, x_d, md.Lam, md.R, md.rho, md.A, md.Q, md.mu0, md.P0, md.v0, md.mean, md.sd,
+                                        seed, first_draw, f_d, xo_d, ll_d, flags));
     if (rc == 0) rc = post_check(h, ll_host.data(), (int)BD);
     return rc;
 }
@@ -2853,33 +2886,20 @@ int dfm_gibbs_batch_dev(dfm_handle* h, int B, int T, int N, int r, int p, const 
     a.seed = seed; a.missing = missing; a.Lsh = at<double>(h->gb, o_L); a.status = h->status_dev;
     double* f = at<double>(h->gb, o_f);
     const size_t K = (size_t)gibbs_kept(n_sweeps, burn, thin);
-    auto keep = [&](double* dst, const double* src, size_t per, size_t kk) {   // dst [B][K][per] <- src [B][per]
-        return dst ? hipMemcpy2DAsync(dst + kk * per, K * per * d, src, per * d, per * d, (size_t)B, hipMemcpyDeviceToDevice, h->stream)
-                   : hipSuccess;
-    };
     for (int j = 0; j < n_sweeps; ++j) {
         a.sweep = first_sweep + j;
         if (int rc = dfm_simsmooth_batch_dev(h, B, 1, T, N, r, p, 0, panel, Lam, R, Avar, Q, mu0, P0, nullptr, nullptr, seed, a.sweep, f,
                                              nullptr, flags)) return rc;
-        if (!missing) {
-            ProfScope ps(h, K_GB_GRAM);
-            HIP_TRY(h, launch_gibbs_gram(a, h->stream));
-        }
-        {
-            ProfScope ps(h, K_GB_LOAD);
-            HIP_TRY(h, launch_gibbs_load(a, h->stream));
-        }
-        {
-            ProfScope ps(h, K_GB_VAR);
-            HIP_TRY(h, launch_gibbs_var(a, h->stream));
-        }
-        if (j >= burn && (j - burn) % thin == 0) {
+        if (!missing) HIP_LAUNCH(h, K_GB_GRAM, launch_gibbs_gram(a, h->stream));
+        HIP_LAUNCH(h, K_GB_LOAD, launch_gibbs_load(a, h->stream));
+        HIP_LAUNCH(h, K_GB_VAR, launch_gibbs_var(a, h->stream));
+        if (gibbs_kept_slot(j, burn, thin)) {
             const size_t kk = (size_t)(j - burn) / thin;
-            HIP_TRY(h, keep(Lam_draw, Lam, (size_t)N * r, kk));
-            HIP_TRY(h, keep(R_draw, R, (size_t)N, kk));
-            HIP_TRY(h, keep(A_draw, Avar, (size_t)r * k, kk));
-            HIP_TRY(h, keep(Q_draw, Q, (size_t)r * r, kk));
-            HIP_TRY(h, keep(f_draw, f, (size_t)T * r, kk));
+            HIP_TRY(h, gibbs_keep(h, Lam_draw, Lam, (size_t)N * r, kk, K, B));
+            HIP_TRY(h, gibbs_keep(h, R_draw, R, (size_t)N, kk, K, B));
+            HIP_TRY(h, gibbs_keep(h, A_draw, Avar, (size_t)r * k, kk, K, B));
+            HIP_TRY(h, gibbs_keep(h, Q_draw, Q, (size_t)r * r, kk, K, B));
+            HIP_TRY(h, gibbs_keep(h, f_draw, f, (size_t)T * r, kk, K, B));
         }
     }
     return 0;
@@ -2925,7 +2945,7 @@ static int gibbs_ar_check(dfm_handle* h, int B, int T, int N, int r, int p, int 
     if (!(tau_lam > 0.0) || !(nu_R >= 2.0) || !(s_R > 0.0) || !(tau_rho > 0.0) || !(tau_A > 0.0) || !(nu_Q >= (double)r + 1.0) ||
         !(s_Q > 0.0))
         return fail(h, DFM_E_DIMS, "prior: tau_lam, s_R, tau_rho, tau_A, s_Q > 0, nu_R >= 2 and nu_Q >= r + 1 are required%s");
-    const int m = p > q + 1 ? p : q + 1;
+    const int m = state_lags(p, q);
     if (q > 4 || r > 8 || (long long)r * m > DFM_MAX_R)
         return fail(h, DFM_E_R_UNSUPPORTED, "the Gibbs sampler with AR idiosyncratic terms needs q <= 4, r <= 8 and r max(p, q + 1) <= 32%s");
     if ((long long)T - q <= p) return fail(h, DFM_E_DIMS, "T - q must be > p (the VAR block conditions on the first p drawn rows)%s");
@@ -2952,30 +2972,20 @@ int dfm_gibbs_ar_batch_dev(dfm_handle* h, int B, int T, int N, int r, int p, int
     a.B = B; a.T = (int)n; a.N = N; a.r = r; a.p = p;
     a.f = f; a.A = Avar; a.Q = Q; a.A0 = A0; a.tau_A = tau_A; a.nu_Q = nu_Q; a.s_Q = s_Q; a.seed = seed; a.status = h->status_dev;
     const size_t K = (size_t)gibbs_kept(n_sweeps, burn, thin);
-    auto keep = [&](double* dst, const double* src, size_t per, size_t kk) {   // dst [B][K][per] <- src [B][per]
-        return dst ? hipMemcpy2DAsync(dst + kk * per, K * per * d, src, per * d, per * d, (size_t)B, hipMemcpyDeviceToDevice, h->stream)
-                   : hipSuccess;
-    };
     for (int j = 0; j < n_sweeps; ++j) {
         a.sweep = sa.sweep = first_sweep + j;
         if (int rc = dfm_simsmooth_ar_batch_dev(h, B, 1, T, N, r, p, q, 0, panel, Lam, sig2, rho, Avar, Q, mu0, P0, nullptr, nullptr,
                                                 nullptr, seed, a.sweep, f, nullptr, flags)) return rc;
-        {
-            ProfScope ps(h, K_GB_AR_SERIES);
-            HIP_TRY(h, launch_gibbs_ar_series(sa, h->stream));
-        }
-        {
-            ProfScope ps(h, K_GB_VAR);
-            HIP_TRY(h, launch_gibbs_var(a, h->stream));
-        }
-        if (j >= burn && (j - burn) % thin == 0) {
+        HIP_LAUNCH(h, K_GB_AR_SERIES, launch_gibbs_ar_series(sa, h->stream));
+        HIP_LAUNCH(h, K_GB_VAR, launch_gibbs_var(a, h->stream));
+        if (gibbs_kept_slot(j, burn, thin)) {
             const size_t kk = (size_t)(j - burn) / thin;
-            HIP_TRY(h, keep(Lam_draw, Lam, (size_t)N * r, kk));
-            HIP_TRY(h, keep(sig2_draw, sig2, (size_t)N, kk));
-            HIP_TRY(h, keep(rho_draw, rho, (size_t)N * q, kk));
-            HIP_TRY(h, keep(A_draw, Avar, (size_t)r * k, kk));
-            HIP_TRY(h, keep(Q_draw, Q, (size_t)r * r, kk));
-            HIP_TRY(h, keep(f_draw, f, n * r, kk));
+            HIP_TRY(h, gibbs_keep(h, Lam_draw, Lam, (size_t)N * r, kk, K, B));
+            HIP_TRY(h, gibbs_keep(h, sig2_draw, sig2, (size_t)N, kk, K, B));
+            HIP_TRY(h, gibbs_keep(h, rho_draw, rho, (size_t)N * q, kk, K, B));
+            HIP_TRY(h, gibbs_keep(h, A_draw, Avar, (size_t)r * k, kk, K, B));
+            HIP_TRY(h, gibbs_keep(h, Q_draw, Q, (size_t)r * r, kk, K, B));
+            HIP_TRY(h, gibbs_keep(h, f_draw, f, n * r, kk, K, B));
         }
     }
     return 0;
@@ -2990,7 +3000,7 @@ int dfm_gibbs_ar_batch(dfm_handle* h, int B, int T, int N, int r, int p, int q, 
                                 s_Q, n_sweeps, burn, thin)) return rc;
     if (int rc = status_epoch(h)) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
-    const size_t m = (size_t)(p > q + 1 ? p : q + 1), km = (size_t)r * m, k = (size_t)r * p, n = (size_t)T - q,
+    const size_t m = (size_t)state_lags(p, q), km = (size_t)r * m, k = (size_t)r * p, n = (size_t)T - q,
                  BK = (size_t)B * gibbs_kept(n_sweeps, burn, thin);
     HostStage st(h, 256);
     double *x_d, *mu_d, *P0_d, *lam_d, *s2_d, *rho_d, *A_d, *Q_d, *A0_d, *ld_d, *sd_d, *rd_d, *ad_d, *qd_d, *fd_d;
@@ -3062,12 +3072,8 @@ int dfm_irf_batch_dev(dfm_handle* h, int B, int N, int r, int p, int H, const do
     a.status = h->status_dev;
     a.S = at<double>(h->sv, o_S); a.scale = at<double>(h->sv, o_sc); a.Th = at<double>(h->sv, o_Th); a.Thc = at<double>(h->sv, o_Thc);
     a.irf = irf; a.fevd = fevd;
-    {
-        ProfScope ps(h, K_SV_PREP);
-        HIP_TRY(h, launch_sv_prep(a, h->stream));
-    }
-    ProfScope ps(h, K_SV_IRF_FILL);
-    HIP_TRY(h, launch_sv_irf_fill(a, h->stream));
+    HIP_LAUNCH(h, K_SV_PREP, launch_sv_prep(a, h->stream));
+    HIP_LAUNCH(h, K_SV_IRF_FILL, launch_sv_irf_fill(a, h->stream));
     return 0;
 }
 
@@ -3178,10 +3184,7 @@ static int signirf_run(dfm_handle* h, int B, int N, int r, int p, int H, const d
     a.named = named ? ixd + i_named : nullptr; a.cum = cum ? ixd + i_cum : nullptr;
     a.status = h->status_dev;
     a.S = at<double>(h->sv, o_S); a.Th = at<double>(h->sv, o_Th); a.Thc = at<double>(h->sv, o_Thc);
-    {
-        ProfScope ps(h, K_SV_PREP);
-        HIP_TRY(h, launch_sv_prep(a, h->stream));
-    }
+    HIP_LAUNCH(h, K_SV_PREP, launch_sv_prep(a, h->stream));
     SgArgs g{};
     g.B = B; g.N = N; g.r = r; g.H = H; g.M = M; g.K = K; g.nS = nS; g.HT = sp.HT; g.G = G;
     g.Lam = Lam; g.sd = sd; g.cum = a.cum; g.ser = ixd + i_ser; g.gs = ixd + i_gs; g.rows = ixd + i_rows;
@@ -3190,22 +3193,12 @@ static int signirf_run(dfm_handle* h, int B, int N, int r, int p, int H, const d
     g.mask = mask_out ? mask_out : at<int>(h->sv, o_mask); g.wcnt = at<int>(h->sv, o_wcnt); g.rot = at<double>(h->sv, o_rot);
     g.n_accept = n_accept; g.cand_out = cand_out; g.S_out = S_out;
     g.ThK = at<double>(h->sv, o_ThK); g.ThcK = at<double>(h->sv, o_ThcK);
-    if (nS > 0) {
-        ProfScope ps(h, K_SV_SIGN_TABLE);
-        HIP_TRY(h, launch_sv_sign_table(g, h->stream));
-    }
-    {
-        ProfScope ps(h, K_SV_SIGN);
-        HIP_TRY(h, launch_sv_sign(g, h->stream));
-    }
-    {
-        ProfScope ps(h, K_SV_SIGN_KEEP);
-        HIP_TRY(h, launch_sv_sign_keep(g, h->stream));
-    }
+    if (nS > 0) HIP_LAUNCH(h, K_SV_SIGN_TABLE, launch_sv_sign_table(g, h->stream));
+    HIP_LAUNCH(h, K_SV_SIGN, launch_sv_sign(g, h->stream));
+    HIP_LAUNCH(h, K_SV_SIGN_KEEP, launch_sv_sign_keep(g, h->stream));
     if (!fill) return 0;
     a.B = B; a.slots = K; a.Th = g.ThK; a.Thc = g.ThcK; a.irf = irf; a.fevd = fevd;
-    ProfScope ps(h, K_SV_IRF_FILL);
-    HIP_TRY(h, launch_sv_irf_fill(a, h->stream));
+    HIP_LAUNCH(h, K_SV_IRF_FILL, launch_sv_irf_fill(a, h->stream));
     return 0;
 }
 
@@ -3272,20 +3265,10 @@ int dfm_histdecomp_batch_dev(dfm_handle* h, int B, int T, int N, int r, int p, c
     a.need_pd = 1; a.status = h->status_dev;
     a.S = at<double>(h->sv, o_S); a.Sinv = at<double>(h->sv, o_Si);
     a.f = f; a.u = shocks ? shocks : at<double>(h->sv, o_u); a.C = at<double>(h->sv, o_C); a.hd = hd;
-    {
-        ProfScope ps(h, K_SV_PREP);
-        HIP_TRY(h, launch_sv_prep(a, h->stream));
-    }
-    {
-        ProfScope ps(h, K_SV_SHOCK);
-        HIP_TRY(h, launch_sv_shock(a, h->stream));
-    }
-    {
-        ProfScope ps(h, K_SV_PATH);
-        HIP_TRY(h, launch_sv_path(a, h->stream));
-    }
-    ProfScope ps(h, K_SV_HD_FILL);
-    HIP_TRY(h, launch_sv_hd_fill(a, h->stream));
+    HIP_LAUNCH(h, K_SV_PREP, launch_sv_prep(a, h->stream));
+    HIP_LAUNCH(h, K_SV_SHOCK, launch_sv_shock(a, h->stream));
+    HIP_LAUNCH(h, K_SV_PATH, launch_sv_path(a, h->stream));
+    HIP_LAUNCH(h, K_SV_HD_FILL, launch_sv_hd_fill(a, h->stream));
     return 0;
 }
 
@@ -3388,10 +3371,7 @@ static int proxyirf_run(dfm_handle* h, int B, int T, int N, int r, int p, int H,
     a.Lam = Lam; a.A = Avar; a.Q = Q; a.sd = sd;
     a.need_pd = 1; a.status = h->status_dev;
     a.S = at<double>(h->sv, o_S); a.Sinv = at<double>(h->sv, o_Si); a.Th = at<double>(h->sv, o_Th); a.Thc = at<double>(h->sv, o_Thc);
-    {
-        ProfScope ps(h, K_SV_PREP);
-        HIP_TRY(h, launch_sv_prep(a, h->stream));
-    }
+    HIP_LAUNCH(h, K_SV_PREP, launch_sv_prep(a, h->stream));
     PxArgs g{};
     g.B = B; g.T = T; g.N = N; g.r = r; g.p = p; g.H = H; g.n = n; g.D = D; g.L = L; g.norm = norm; g.unit = unit ? 1 : 0;
     g.Lam = Lam; g.sd = sd; g.A = Avar; g.cum = cum ? ixd : nullptr; g.U = ixd + i_U; g.z = at<double>(h->sv, o_z); g.f = f;
@@ -3400,29 +3380,13 @@ static int proxyirf_run(dfm_handle* h, int B, int T, int N, int r, int p, int H,
     g.rows = at<double>(h->sv, o_rows); g.impact = impact; g.rel = rel; g.w = at<double>(h->sv, o_w);
     g.tk = at<double>(h->sv, o_tk); g.tkc = at<double>(h->sv, o_tkc); g.scale = at<double>(h->sv, o_sc);
     g.R = R; g.den = at<double>(h->sv, o_den); g.irf = irf; g.fevd = fevd; g.shock = shock;
-    {
-        ProfScope ps(h, K_PX_ROWS);
-        HIP_TRY(h, launch_px_rows(g, h->stream));
-    }
-    {
-        ProfScope ps(h, K_PX_MOMENT);
-        HIP_TRY(h, launch_px_moment(g, h->stream));
-    }
-    if (shock) {
-        ProfScope ps(h, K_PX_SHOCK);
-        HIP_TRY(h, launch_px_shock(g, h->stream));
-    }
+    HIP_LAUNCH(h, K_PX_ROWS, launch_px_rows(g, h->stream));
+    HIP_LAUNCH(h, K_PX_MOMENT, launch_px_moment(g, h->stream));
+    if (shock) HIP_LAUNCH(h, K_PX_SHOCK, launch_px_shock(g, h->stream));
     if (!fill) return 0;
-    {
-        ProfScope ps(h, K_PX_SLOT_TABLE);
-        HIP_TRY(h, launch_px_slot_table(g, h->stream));
-    }
-    if (fevd) {
-        ProfScope ps(h, K_PX_DEN);
-        HIP_TRY(h, launch_px_den(g, h->stream));
-    }
-    ProfScope ps(h, K_PX_FILL);
-    HIP_TRY(h, launch_px_fill(g, h->stream));
+    HIP_LAUNCH(h, K_PX_SLOT_TABLE, launch_px_slot_table(g, h->stream));
+    if (fevd) HIP_LAUNCH(h, K_PX_DEN, launch_px_den(g, h->stream));
+    HIP_LAUNCH(h, K_PX_FILL, launch_px_fill(g, h->stream));
     return 0;
 }
 
@@ -3482,13 +3446,7 @@ static int news_check(dfm_handle* h, int B, int T, int N, int r, int p, const do
     if (!oldp || !newp || !Lam || !R || !Avar || !Q || !mu0 || !P0 || !target_t || !target_i || !yhat || !impact)
         return fail(h, DFM_E_NULL, "required pointer is NULL%s");
     if ((mean == nullptr) != (sd == nullptr)) return fail(h, DFM_E_NULL, "mean and sd must both be given or both be NULL%s");
-    int tmax = 0;
-    for (int g = 0; g < G; ++g) {
-        if (target_t[g] < 0 || target_t[g] > 0x3fffffff || target_i[g] < 0 || target_i[g] >= N)
-            return fail(h, DFM_E_DIMS, "a target lies outside [0, T + H) x [0, N)%s");
-        if (target_t[g] > tmax) tmax = target_t[g];
-    }
-    *H = tmax + 1 > T ? tmax + 1 - T : 0;
+    if (!news_targets(T, N, G, target_t, target_i, 0, H)) return fail(h, DFM_E_DIMS, "a target lies outside [0, T + H) x [0, N)%s");
     return 0;
 }
 
@@ -3503,64 +3461,41 @@ static int news_run(dfm_handle* h, int B, int T, int N, int r, int p, int H, con
     const int Smax = (int)(BG < kNwSlice ? BG : kNwSlice);
     size_t off = 0;
     const size_t o_t = take(off, (size_t)2 * G * sizeof(int)), o_rev = take(off, (size_t)B * T * N * d),
-                 o_x = take(off, (size_t)B * TH * N * d), o_f = take(off, (size_t)B * TH * r * d),
-                 o_L = take(off, (size_t)Smax * N * r * d), o_R = take(off, (size_t)Smax * N * d),
-                 o_A = take(off, (size_t)Smax * r * k * d), o_Q = take(off, (size_t)Smax * r * r * d),
-                 o_m = take(off, (size_t)Smax * k * d), o_P = take(off, (size_t)Smax * k * k * d),
-                 o_u = take(off, (size_t)Smax * T * k * d), o_av = take(off, (size_t)Smax * T * r * d),
+                 o_x = take(off, (size_t)B * TH * N * d), o_f = take(off, (size_t)B * TH * r * d);
+    const SliceParams sp(off, Smax, N, r, k, 0);
+    const size_t o_u = take(off, (size_t)Smax * T * k * d), o_av = take(off, (size_t)Smax * T * r * d),
                  o_g = take(off, (size_t)Smax * T * r * d),
                  o_ll = ll_all ? (size_t)-1 : take(off, (size_t)(B > Smax ? B : Smax) * d),
                  o_c = weight ? (size_t)-1 : take(off, (size_t)Smax * T * N * d);
     HIP_TRY(h, h->nw.grow(off));
     int* tgt = at<int>(h->nw, o_t);
-    {
-        std::vector<int> tg((size_t)2 * G);                   // (a pageable source: staged before the call returns)
-        for (int g = 0; g < G; ++g) { tg[2 * g] = target_t[g]; tg[2 * g + 1] = target_i[g]; }
-        HIP_TRY(h, hipMemcpyAsync(tgt, tg.data(), tg.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    }
+    double *xhat = at<double>(h->nw, o_x), *fbuf = at<double>(h->nw, o_f);
+    if (int rc = news_stage_targets(h, G, target_t, target_i, 0, tgt)) return rc;
     NwArgs a{};
     a.B = B; a.T = T; a.N = N; a.r = r; a.p = p; a.G = G; a.TH = (int)TH;
     a.oldp = oldp; a.newp = newp; a.Lam = Lam; a.R = R; a.A = Avar; a.P0 = P0; a.Q = Q; a.mean = mean; a.sd = sd;
-    a.tgt = tgt; a.rev = at<double>(h->nw, o_rev); a.xrev = at<double>(h->nw, o_x); a.yhat = yhat; a.impact = impact; a.news = news; a.weight = weight;
+    a.tgt = tgt; a.rev = at<double>(h->nw, o_rev); a.xrev = xhat; a.yhat = yhat; a.impact = impact; a.news = news; a.weight = weight;
     a.status = h->status_dev; a.u = at<double>(h->nw, o_u); a.av = at<double>(h->nw, o_av); a.g = at<double>(h->nw, o_g);
-    {
-        ProfScope ps(h, K_NW_REVISE);
-        HIP_TRY(h, launch_news_revise(a, h->stream));
-    }
-    // old, new, revised old: the last one's xhat stays in o_x for the impacts
-    const struct { const double* panel; unsigned fl; int which; } runs[3] = {
-        {oldp, flags | DFM_F_MAY_HAVE_MISSING, 0}, {newp, flags, 2}, {a.rev, flags | DFM_F_MAY_HAVE_MISSING, 1}};
-    for (const auto& run : runs) {
-        double* ll = ll_all ? ll_all + (size_t)run.which * B : at<double>(h->nw, o_ll);
-        if (int rc = dfm_forecast_batch_dev(h, B, T, N, r, p, H, run.panel, Lam, R, Avar, Q, mu0, P0, mean, sd, at<double>(h->nw, o_x), nullptr,
-                                            nullptr, at<double>(h->nw, o_f), nullptr, ll, run.fl)) return rc;
-        ProfScope ps(h, K_NW_GATHER);
-        HIP_TRY(h, launch_news_gather(a, at<double>(h->nw, o_x), run.which, h->stream));
-    }
+    HIP_LAUNCH(h, K_NW_REVISE, launch_news_revise(a, h->stream));
+    if (int rc = news_forecasts(h, B, a, oldp, newp, a.rev, xhat, ll_all, at<double>(h->nw, o_ll), flags,
+                                [&](const double* panel, double* ll, unsigned fl) {
+        return dfm_forecast_batch_dev(h, B, T, N, r, p, H, panel, Lam, R, Avar, Q, mu0, P0, mean, sd, xhat, nullptr, nullptr, fbuf,
+                                      nullptr, ll, fl);
+    })) return rc;
     SsArgs e{};
     e.B = B; e.D = G; e.T = T; e.N = N; e.r = r; e.p = p;
     e.Lam = Lam; e.R = R; e.A = Avar; e.Q = Q; e.mu0 = mu0; e.P0 = P0;
-    e.eLam = at<double>(h->nw, o_L); e.eR = at<double>(h->nw, o_R); e.eA = at<double>(h->nw, o_A); e.eQ = at<double>(h->nw, o_Q); e.emu0 = at<double>(h->nw, o_m); e.eP0 = at<double>(h->nw, o_P);
+    sp.point(h->nw, e);
     for (long long j0 = 0; j0 < BG; j0 += Smax) {
         const int S = (int)(BG - j0 < Smax ? BG - j0 : Smax);
         a.j0 = j0; a.S = S; e.j0 = j0; e.S = S;
         a.cp = weight ? weight + (size_t)j0 * T * N : at<double>(h->nw, o_c);
         double* ll = ll_all ? ll_all + (size_t)3 * B + j0 : at<double>(h->nw, o_ll);
-        {
-            ProfScope ps(h, K_SS_EXPAND);
-            HIP_TRY(h, launch_simsmooth_expand(e, h->stream));
-        }
-        {
-            ProfScope ps(h, K_NW_GAMMA);
-            HIP_TRY(h, launch_news_gamma(a, h->stream));
-        }
-        {
-            ProfScope ps(h, K_NW_COV);
-            HIP_TRY(h, launch_news_cov_panel(a, h->stream));
-        }
+        HIP_LAUNCH(h, K_SS_EXPAND, launch_simsmooth_expand(e, h->stream));
+        HIP_LAUNCH(h, K_NW_GAMMA, launch_news_gamma(a, h->stream));
+        HIP_LAUNCH(h, K_NW_COV, launch_news_cov_panel(a, h->stream));
         if (int rc = slice_pass(h, S, T, N, r, p, a.cp, e, at<double>(h->nw, o_g), ll, flags)) return rc;
-        ProfScope ps(h, K_NW_IMPACT);
-        HIP_TRY(h, launch_news_impact(a, h->stream));
+        HIP_LAUNCH(h, K_NW_IMPACT, launch_news_impact(a, h->stream));
     }
     return 0;
 }
@@ -3585,18 +3520,18 @@ int dfm_news_batch(dfm_handle* h, int B, int T, int N, int r, int p, const doubl
                             impact, &H)) return rc;
     if (int rc = status_epoch(h)) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
-    const size_t k = (size_t)r * p, BG = (size_t)B * G, n_panel = (size_t)B * T * N, n_R = (size_t)B * N, n_ll = (size_t)3 * B + BG;
+    const size_t BG = (size_t)B * G, n_panel = (size_t)B * T * N, n_ll = (size_t)3 * B + BG;
     std::vector<double> ll_host(n_ll);
     HostStage st(h, 256);
-    double *xo_d, *xn_d, *lam_d, *R_d, *A_d, *Q_d, *mu_d, *P0_d, *mean_d, *sd_d, *y_d, *imp_d, *news_d, *w_d, *ll_d;
-    st.in(old_panel, n_panel, xo_d); st.in(new_panel, n_panel, xn_d); st.in(Lam, (size_t)B * N * r, lam_d); st.in(R, n_R, R_d);
-    st.in(Avar, (size_t)B * r * k, A_d); st.in(Q, (size_t)B * r * r, Q_d); st.in(mu0, (size_t)B * k, mu_d); st.in(P0, (size_t)B * k * k, P0_d);
-    st.in(mean, mean ? n_R : 0, mean_d); st.in(sd, sd ? n_R : 0, sd_d);
+    ModelDev md;
+    double *xo_d, *xn_d, *y_d, *imp_d, *news_d, *w_d, *ll_d;
+    st.in(old_panel, n_panel, xo_d); st.in(new_panel, n_panel, xn_d);
+    stage_model(st, md, B, N, r, p, 0, Lam, R, nullptr, Avar, Q, mu0, P0, nullptr, mean, sd);
     st.out(yhat, (size_t)B * 3 * G, y_d); st.out(impact, BG * N, imp_d); st.out(news, news ? n_panel : 0, news_d);
     st.out(weight, weight ? BG * T * N : 0, w_d); st.out(ll_host.data(), n_ll, ll_d);
     if (int rc = st.begin()) return rc;
-    int rc = st.finish(news_run(h, B, T, N, r, p, H, xo_d, xn_d, lam_d, R_d, A_d, Q_d, mu_d, P0_d, mean_d, sd_d, G, target_t, target_i, y_d,
-                                imp_d, news_d, w_d, ll_d, flags));
+    int rc = st.finish(news_run(h, B, T, N, r, p, H, xo_d, xn_d, md.Lam, md.R, md.A, md.Q, md.mu0, md.P0, md.mean, md.sd, G, target_t,
+                                target_i, y_d, imp_d, news_d, w_d, ll_d, flags));
     if (rc == 0) rc = post_check(h, ll_host.data(), (int)n_ll);
     return rc;
 }
@@ -3622,13 +3557,7 @@ static int news_ar_check(dfm_handle* h, int B, int T, int N, int r, int p, int q
     if (!oldp || !newp || !Lam || !sig2 || !rho || !Avar || !Q || !mu0 || !P0 || !target_t || !target_i || !yhat || !impact)
         return fail(h, DFM_E_NULL, "required pointer is NULL%s");
     if ((mean == nullptr) != (sd == nullptr)) return fail(h, DFM_E_NULL, "mean and sd must both be given or both be NULL%s");
-    int tmax = 0;
-    for (int g = 0; g < G; ++g) {
-        if (target_t[g] < q || target_t[g] > 0x3fffffff || target_i[g] < 0 || target_i[g] >= N)
-            return fail(h, DFM_E_DIMS, "a target lies outside [q, T + H) x [0, N)%s");
-        if (target_t[g] > tmax) tmax = target_t[g];
-    }
-    *H = tmax + 1 > T ? tmax + 1 - T : 0;
+    if (!news_targets(T, N, G, target_t, target_i, q, H)) return fail(h, DFM_E_DIMS, "a target lies outside [q, T + H) x [0, N)%s");
     return ar_check(h, B, T + *H, N, r, p, q, false);
 }
 
@@ -3651,86 +3580,54 @@ static int news_ar_run(dfm_handle* h, int B, int T, int N, int r, int p, int q, 
                        const int* target_t, const int* target_i, double* yhat, double* impact, double* news, double* weight,
                        double* ll_all, unsigned flags) {
     HIP_TRY(h, hipSetDevice(h->device));
-    const int m = p > q + 1 ? p : q + 1, Rp = pad_r(r * m), w = (q + 1) * r;
+    const int m = state_lags(p, q), Rp = pad_r(r * m), w = (q + 1) * r;
     const size_t d = sizeof(double), k = (size_t)r * m, TH = (size_t)T + H, n = TH - q, ns = (size_t)T - q;
     const long long BG = (long long)B * G;
     const int Smax = (int)(BG < kNwSlice ? BG : kNwSlice);
     size_t off = 0;
     const size_t o_t = take(off, (size_t)2 * G * sizeof(int)), o_rev = take(off, (size_t)B * T * N * d),
                  o_x = take(off, (size_t)B * n * N * d), o_f = take(off, (size_t)B * n * r * d),
-                 o_Ap = p < m ? take(off, (size_t)B * r * k * d) : (size_t)-1,
-                 o_L = take(off, (size_t)Smax * N * r * d), o_R = take(off, (size_t)Smax * N * d),
-                 o_rho = take(off, (size_t)Smax * N * q * d), o_A = take(off, (size_t)Smax * r * k * d),
-                 o_Q = take(off, (size_t)Smax * r * r * d), o_m = take(off, (size_t)Smax * k * d),
-                 o_P = take(off, (size_t)Smax * k * k * d), o_u = take(off, (size_t)Smax * ns * (k + 1) * d),
+                 o_Ap = p < m ? take(off, (size_t)B * r * k * d) : (size_t)-1;
+    const SliceParams sp(off, Smax, N, r, k, q);
+    const size_t o_u = take(off, (size_t)Smax * ns * (k + 1) * d),
                  o_dv = take(off, (size_t)Smax * ns * (w + 1) * d), o_g = take(off, (size_t)Smax * ns * Rp * d),
                  o_ll = ll_all ? (size_t)-1 : take(off, (size_t)(B > Smax ? B : Smax) * d),
                  o_c = weight ? (size_t)-1 : take(off, (size_t)Smax * ns * N * d);
     HIP_TRY(h, h->nw.grow(off));
     int* tgt = at<int>(h->nw, o_t);
-    {
-        std::vector<int> tg((size_t)2 * G);                   // (a pageable source: staged before the call returns); output rows
-        for (int g = 0; g < G; ++g) { tg[2 * g] = target_t[g] - q; tg[2 * g + 1] = target_i[g]; }
-        HIP_TRY(h, hipMemcpyAsync(tgt, tg.data(), tg.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    }
+    double *xhat = at<double>(h->nw, o_x), *fbuf = at<double>(h->nw, o_f);
+    if (int rc = news_stage_targets(h, G, target_t, target_i, q, tgt)) return rc;       // (output rows)
     NwArArgs a{};
     a.B = B; a.T = T; a.N = N; a.r = r; a.q = q; a.k = (int)k; a.ka = r * p; a.G = G; a.n = (int)n; a.ns = (int)ns; a.Rp = Rp;
     a.oldp = oldp; a.newp = newp; a.Lam = Lam; a.sig2 = sig2; a.rho = rho; a.A = Avar; a.Q = Q; a.P0 = P0; a.mean = mean; a.sd = sd;
-    a.tgt = tgt; a.rev = at<double>(h->nw, o_rev); a.xrev = at<double>(h->nw, o_x); a.impact = impact; a.news = news; a.weight = weight;
+    a.tgt = tgt; a.rev = at<double>(h->nw, o_rev); a.xrev = xhat; a.impact = impact; a.news = news; a.weight = weight;
     a.status = h->status_dev; a.u = at<double>(h->nw, o_u); a.dv = at<double>(h->nw, o_dv); a.g = at<double>(h->nw, o_g);
-    {
-        ProfScope ps(h, K_NWAR_REVISE);
-        HIP_TRY(h, launch_news_ar_revise(a, h->stream));
-    }
+    HIP_LAUNCH(h, K_NWAR_REVISE, launch_news_ar_revise(a, h->stream));
     NwArgs ga{};                                              // news_gather_kernel on the forecasts' n output rows
     ga.B = B; ga.G = G; ga.N = N; ga.TH = (int)n; ga.tgt = tgt; ga.yhat = yhat;
-    // old, new, revised old: the last one's xhat stays in o_x for the news
-    const struct { const double* panel; unsigned fl; int which; } runs[3] = {
-        {oldp, flags | DFM_F_MAY_HAVE_MISSING, 0}, {newp, flags, 2}, {a.rev, flags | DFM_F_MAY_HAVE_MISSING, 1}};
-    for (const auto& run : runs) {
-        double* ll = ll_all ? ll_all + (size_t)run.which * B : at<double>(h->nw, o_ll);
-        if (int rc = dfm_forecast_ar_batch_dev(h, B, T, N, r, p, q, H, run.panel, Lam, sig2, rho, Avar, Q, mu0, P0, v0, mean, sd,
-                                               at<double>(h->nw, o_x), nullptr, nullptr, nullptr, at<double>(h->nw, o_f), nullptr, ll,
-                                               run.fl)) return rc;
-        ProfScope ps(h, K_NW_GATHER);
-        HIP_TRY(h, launch_news_gather(ga, at<double>(h->nw, o_x), run.which, h->stream));
-    }
-    const double* Am = Avar;
-    if (p < m) {
-        ProfScope ps(h, K_SSAR_PARAMS);
-        HIP_TRY(h, launch_simsmooth_ar_params(B, r, p, m, Avar, at<double>(h->nw, o_Ap), h->stream));
-        Am = at<double>(h->nw, o_Ap);
-    }
+    if (int rc = news_forecasts(h, B, ga, oldp, newp, a.rev, xhat, ll_all, at<double>(h->nw, o_ll), flags,
+                                [&](const double* panel, double* ll, unsigned fl) {
+        return dfm_forecast_ar_batch_dev(h, B, T, N, r, p, q, H, panel, Lam, sig2, rho, Avar, Q, mu0, P0, v0, mean, sd, xhat, nullptr,
+                                         nullptr, nullptr, fbuf, nullptr, ll, fl);
+    })) return rc;
+    const double* Am;
+    if (int rc = pad_avar(h, B, r, p, m, Avar, at<double>(h->nw, o_Ap), &Am)) return rc;
     SsArgs e{};
     e.B = B; e.D = G; e.T = (int)ns; e.N = N; e.r = r; e.p = m;
     e.Lam = Lam; e.R = sig2; e.A = Am; e.Q = Q; e.mu0 = mu0; e.P0 = P0;
-    e.eLam = at<double>(h->nw, o_L); e.eR = at<double>(h->nw, o_R); e.eA = at<double>(h->nw, o_A); e.eQ = at<double>(h->nw, o_Q); e.emu0 = at<double>(h->nw, o_m); e.eP0 = at<double>(h->nw, o_P);
-    double* erho = at<double>(h->nw, o_rho);
+    double* erho = sp.point(h->nw, e);
     for (long long j0 = 0; j0 < BG; j0 += Smax) {
         const int S = (int)(BG - j0 < Smax ? BG - j0 : Smax);
         a.j0 = j0; a.S = S; e.j0 = j0; e.S = S;
         a.qc = weight ? weight + (size_t)j0 * ns * N : at<double>(h->nw, o_c);
         double* ll = ll_all ? ll_all + (size_t)3 * B + j0 : at<double>(h->nw, o_ll);
-        {
-            ProfScope ps(h, K_SS_EXPAND);
-            HIP_TRY(h, launch_simsmooth_expand(e, h->stream));
-        }
-        {
-            ProfScope ps(h, K_SSAR_EXPAND);
-            HIP_TRY(h, launch_simsmooth_ar_expand(S, j0, G, (size_t)N * q, rho, erho, h->stream));
-        }
-        {
-            ProfScope ps(h, K_NWAR_REC);
-            HIP_TRY(h, launch_news_ar_rec(a, h->stream));
-        }
-        {
-            ProfScope ps(h, K_NWAR_QC);
-            HIP_TRY(h, launch_news_ar_qc(a, h->stream));
-        }
+        HIP_LAUNCH(h, K_SS_EXPAND, launch_simsmooth_expand(e, h->stream));
+        HIP_LAUNCH(h, K_SSAR_EXPAND, launch_simsmooth_ar_expand(S, j0, G, (size_t)N * q, rho, erho, h->stream));
+        HIP_LAUNCH(h, K_NWAR_REC, launch_news_ar_rec(a, h->stream));
+        HIP_LAUNCH(h, K_NWAR_QC, launch_news_ar_qc(a, h->stream));
         if (int rc = news_ar_pass(h, S, (int)ns, N, r, m, q, a.qc, e.eLam, e.eR, erho, e.eA, e.eQ, e.emu0, e.eP0, at<double>(h->nw, o_g), ll,
                                   flags)) return rc;
-        ProfScope ps(h, K_NWAR_IMPACT);
-        HIP_TRY(h, launch_news_ar_impact(a, h->stream));
+        HIP_LAUNCH(h, K_NWAR_IMPACT, launch_news_ar_impact(a, h->stream));
     }
     return 0;
 }
@@ -3757,19 +3654,18 @@ int dfm_news_ar_batch(dfm_handle* h, int B, int T, int N, int r, int p, int q, c
                                target_i, yhat, impact, &H)) return rc;
     if (int rc = status_epoch(h)) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
-    const size_t m = (size_t)(p > q + 1 ? p : q + 1), k = (size_t)r * m, BG = (size_t)B * G, n_panel = (size_t)B * T * N,
-                 n_R = (size_t)B * N, n_s = (size_t)B * (T - q) * N, n_ll = (size_t)3 * B + BG;
+    const size_t BG = (size_t)B * G, n_panel = (size_t)B * T * N, n_s = (size_t)B * (T - q) * N, n_ll = (size_t)3 * B + BG;
     std::vector<double> ll_host(n_ll);
     HostStage st(h, 256);
-    double *xo_d, *xn_d, *lam_d, *R_d, *rho_d, *A_d, *Q_d, *mu_d, *P0_d, *v0_d, *mean_d, *sd_d, *y_d, *imp_d, *news_d, *w_d, *ll_d;
-    st.in(old_panel, n_panel, xo_d); st.in(new_panel, n_panel, xn_d); st.in(Lam, n_R * r, lam_d); st.in(sig2, n_R, R_d);
-    st.in(rho, n_R * q, rho_d); st.in(Avar, (size_t)B * r * r * p, A_d); st.in(Q, (size_t)B * r * r, Q_d); st.in(mu0, (size_t)B * k, mu_d);
-    st.in(P0, (size_t)B * k * k, P0_d); st.in(v0, v0 ? n_R : 0, v0_d); st.in(mean, mean ? n_R : 0, mean_d); st.in(sd, sd ? n_R : 0, sd_d);
+    ModelDev md;
+    double *xo_d, *xn_d, *y_d, *imp_d, *news_d, *w_d, *ll_d;
+    st.in(old_panel, n_panel, xo_d); st.in(new_panel, n_panel, xn_d);
+    stage_model(st, md, B, N, r, p, q, Lam, sig2, rho, Avar, Q, mu0, P0, v0, mean, sd);
     st.out(yhat, (size_t)B * 3 * G, y_d); st.out(impact, BG * N, imp_d); st.out(news, news ? n_s : 0, news_d);
     st.out(weight, weight ? (size_t)G * n_s : 0, w_d); st.out(ll_host.data(), n_ll, ll_d);
     if (int rc = st.begin()) return rc;
-    int rc = st.finish(news_ar_run(h, B, T, N, r, p, q, H, xo_d, xn_d, lam_d, R_d, rho_d, A_d, Q_d, mu_d, P0_d, v0_d, mean_d, sd_d, G,
-                                   target_t, target_i, y_d, imp_d, news_d, w_d, ll_d, flags));
+    int rc = st.finish(news_ar_run(h, B, T, N, r, p, q, H, xo_d, xn_d, md.Lam, md.R, md.rho, md.A, md.Q, md.mu0, md.P0, md.v0, md.mean, md.sd,
+                                   G, target_t, target_i, y_d, imp_d, news_d, w_d, ll_d, flags));
     if (rc == 0) rc = post_check(h, ll_host.data(), (int)n_ll);
     return rc;
 }
@@ -3854,10 +3750,10 @@ int dfm_filter_batch_dev(dfm_handle* h, int B, int T, int N, int r, int p, int H
         LamP = at<double>(h->ft, o_lam);
     }
     ca.panel = panel; ca.Lam = LamP; ca.Rv = R;
-    { ProfScope ps(h, K_COLLAPSE); HIP_TRY(h, launch_collapse(Rp, ca, h->stream)); }
-    { ProfScope ps(h, K_FT_FILTER); HIP_TRY(h, launch_filter(fa, h->stream)); }
-    if (fill) { ProfScope ps(h, K_FT_FILL); HIP_TRY(h, launch_filter_fill(fa, h->stream)); }
-    if (eval) { ProfScope ps(h, K_FT_EVAL); HIP_TRY(h, launch_filter_eval(fa, h->stream)); }
+    HIP_LAUNCH(h, K_COLLAPSE, launch_collapse(Rp, ca, h->stream));
+    HIP_LAUNCH(h, K_FT_FILTER, launch_filter(fa, h->stream));
+    if (fill) HIP_LAUNCH(h, K_FT_FILL, launch_filter_fill(fa, h->stream));
+    if (eval) HIP_LAUNCH(h, K_FT_EVAL, launch_filter_eval(fa, h->stream));
     return 0;
 }
 
@@ -3869,22 +3765,22 @@ int dfm_filter_batch(dfm_handle* h, int B, int T, int N, int r, int p, int H, in
     if (int rc = filter_check(h, B, T, N, r, p, H, t0, panel, Lam, R, Avar, Q, mu0, P0, mean, sd)) return rc;
     if (int rc = status_epoch(h)) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
-    const size_t k = (size_t)r * p, kk = k * (k + 1) / 2, BT = (size_t)B * T, n_R = (size_t)B * N, n_x = BT * N, n_e = (size_t)B * H * N;
+    const size_t k = (size_t)r * p, kk = k * (k + 1) / 2, BT = (size_t)B * T, n_x = BT * N, n_e = (size_t)B * H * N;
     if (H == 0) { msfe = nullptr; msfe0 = nullptr; cnt = nullptr; }          // (left untouched)
     HostStage st(h, 256);
-    double *x_d, *lam_d, *R_d, *A_d, *Q_d, *mu_d, *P0_d, *mean_d, *sd_d, *zp_d, *pp_d, *zf_d, *pf_d, *ll_d, *xp_d, *ve_d, *vs_d, *m_d, *m0_d;
+    ModelDev md;
+    double *x_d, *zp_d, *pp_d, *zf_d, *pf_d, *ll_d, *xp_d, *ve_d, *vs_d, *m_d, *m0_d;
     int* cnt_d;
-    st.in(panel, n_x, x_d); st.in(Lam, (size_t)B * N * r, lam_d); st.in(R, n_R, R_d); st.in(Avar, (size_t)B * r * k, A_d);
-    st.in(Q, (size_t)B * r * r, Q_d); st.in(mu0, (size_t)B * k, mu_d); st.in(P0, (size_t)B * k * k, P0_d);
-    st.in(mean, mean ? n_R : 0, mean_d); st.in(sd, sd ? n_R : 0, sd_d);
+    st.in(panel, n_x, x_d);
+    stage_model(st, md, B, N, r, p, 0, Lam, R, nullptr, Avar, Q, mu0, P0, nullptr, mean, sd);
     st.out(z_pred, z_pred ? BT * k : 0, zp_d); st.out(P_pred, P_pred ? BT * kk : 0, pp_d);
     st.out(z_filt, z_filt ? BT * k : 0, zf_d); st.out(P_filt, P_filt ? BT * kk : 0, pf_d);
     st.out(loglik_t, loglik_t ? BT : 0, ll_d);
     st.out(xpred, xpred ? n_x : 0, xp_d); st.out(verr, verr ? n_x : 0, ve_d); st.out(vstd, vstd ? n_x : 0, vs_d);
     st.out(msfe, msfe ? n_e : 0, m_d); st.out(msfe0, msfe0 ? n_e : 0, m0_d); st.out(cnt, cnt ? n_e : 0, cnt_d);
     if (int rc = st.begin()) return rc;
-    int rc = st.finish(dfm_filter_batch_dev(h, B, T, N, r, p, H, t0, x_d, lam_d, R_d, A_d, Q_d, mu_d, P0_d, mean_d, sd_d, zp_d, pp_d, zf_d,
-                                            pf_d, ll_d, xp_d, ve_d, vs_d, m_d, m0_d, cnt_d, flags));
+    int rc = st.finish(dfm_filter_batch_dev(h, B, T, N, r, p, H, t0, x_d, md.Lam, md.R, md.A, md.Q, md.mu0, md.P0, md.mean, md.sd, zp_d, pp_d,
+                                            zf_d, pf_d, ll_d, xp_d, ve_d, vs_d, m_d, m0_d, cnt_d, flags));
     if (rc == 0) rc = status_check(h);
     return rc;
 }
@@ -3916,7 +3812,7 @@ int dfm_filter_ar_batch_dev(dfm_handle* h, int B, int T, int N, int r, int p, in
                             double* vstd, double* msfe, double* msfe_common, double* msfe0, int* cnt, unsigned flags) {
     if (int rc = filter_ar_check(h, B, T, N, r, p, q, H, t0, panel, Lam, sig2, rho, Avar, Q, mu0, P0, mean, sd)) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
-    const int m = p > q + 1 ? p : q + 1, k = r * m, w = r * (q + 1), Rp = pad_r(k), n = T - q;
+    const int m = state_lags(p, q), k = r * m, w = r * (q + 1), Rp = pad_r(k), n = T - q;
     const size_t d = sizeof(double), Bn = (size_t)B * n;
     const bool miss = (flags & DFM_F_MAY_HAVE_MISSING) != 0;
     const bool fill = xpred || verr || vstd, eval = H > 0 && (msfe || msfe_common || msfe0 || cnt);
@@ -3939,10 +3835,10 @@ int dfm_filter_ar_batch_dev(dfm_handle* h, int B, int T, int N, int r, int p, in
     if (int rc = launch_1d(h, ar_loadings_kernel, (size_t)B * N * Rp, B, N, r, q, Rp, Lam, rho, LamK)) return rc;
     ca.panel = xq; ca.Lam = LamK; ca.Rv = sig2;
     ca.kreal = w;                                               // (the loadings' columns w .. Rp - 1 are zero: as enqueue_pass at kdim)
-    { ProfScope ps(h, K_COLLAPSE); HIP_TRY(h, launch_collapse(Rp, ca, h->stream)); }
-    { ProfScope ps(h, K_FTAR_FILTER); HIP_TRY(h, launch_filter_ar(fa, h->stream)); }
-    if (fill) { ProfScope ps(h, K_FTAR_FILL); HIP_TRY(h, launch_filter_ar_fill(fa, h->stream)); }
-    if (eval) { ProfScope ps(h, K_FTAR_EVAL); HIP_TRY(h, launch_filter_ar_eval(fa, h->stream)); }
+    HIP_LAUNCH(h, K_COLLAPSE, launch_collapse(Rp, ca, h->stream));
+    HIP_LAUNCH(h, K_FTAR_FILTER, launch_filter_ar(fa, h->stream));
+    if (fill) HIP_LAUNCH(h, K_FTAR_FILL, launch_filter_ar_fill(fa, h->stream));
+    if (eval) HIP_LAUNCH(h, K_FTAR_EVAL, launch_filter_ar_eval(fa, h->stream));
     return 0;
 }
 
@@ -3954,16 +3850,14 @@ int dfm_filter_ar_batch(dfm_handle* h, int B, int T, int N, int r, int p, int q,
     if (int rc = filter_ar_check(h, B, T, N, r, p, q, H, t0, panel, Lam, sig2, rho, Avar, Q, mu0, P0, mean, sd)) return rc;
     if (int rc = status_epoch(h)) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
-    const size_t m = (size_t)(p > q + 1 ? p : q + 1), k = (size_t)r * m, kk = k * (k + 1) / 2, Bn = (size_t)B * (T - q),
-                 n_R = (size_t)B * N, n_x = Bn * N, n_e = (size_t)B * H * N;
+    const size_t k = (size_t)r * state_lags(p, q), kk = k * (k + 1) / 2, Bn = (size_t)B * (T - q), n_x = Bn * N, n_e = (size_t)B * H * N;
     if (H == 0) { msfe = nullptr; msfe_common = nullptr; msfe0 = nullptr; cnt = nullptr; }          // (left untouched)
     HostStage st(h, 256);
-    double *x_d, *lam_d, *R_d, *rho_d, *A_d, *Q_d, *mu_d, *P0_d, *mean_d, *sd_d, *zp_d, *pp_d, *zf_d, *pf_d, *ll_d, *xp_d, *ve_d, *vs_d,
-        *m_d, *mc_d, *m0_d;
+    ModelDev md;
+    double *x_d, *zp_d, *pp_d, *zf_d, *pf_d, *ll_d, *xp_d, *ve_d, *vs_d, *m_d, *mc_d, *m0_d;
     int* cnt_d;
-    st.in(panel, (size_t)B * T * N, x_d); st.in(Lam, (size_t)B * N * r, lam_d); st.in(sig2, n_R, R_d); st.in(rho, n_R * q, rho_d);
-    st.in(Avar, (size_t)B * r * r * p, A_d); st.in(Q, (size_t)B * r * r, Q_d); st.in(mu0, (size_t)B * k, mu_d);
-    st.in(P0, (size_t)B * k * k, P0_d); st.in(mean, mean ? n_R : 0, mean_d); st.in(sd, sd ? n_R : 0, sd_d);
+    st.in(panel, (size_t)B * T * N, x_d);
+    stage_model(st, md, B, N, r, p, q, Lam, sig2, rho, Avar, Q, mu0, P0, nullptr, mean, sd);   // (this entry takes no v0)
     st.out(z_pred, z_pred ? Bn * k : 0, zp_d); st.out(P_pred, P_pred ? Bn * kk : 0, pp_d);
     st.out(z_filt, z_filt ? Bn * k : 0, zf_d); st.out(P_filt, P_filt ? Bn * kk : 0, pf_d);
     st.out(loglik_t, loglik_t ? Bn : 0, ll_d);
@@ -3971,8 +3865,8 @@ int dfm_filter_ar_batch(dfm_handle* h, int B, int T, int N, int r, int p, int q,
     st.out(msfe, msfe ? n_e : 0, m_d); st.out(msfe_common, msfe_common ? n_e : 0, mc_d); st.out(msfe0, msfe0 ? n_e : 0, m0_d);
     st.out(cnt, cnt ? n_e : 0, cnt_d);
     if (int rc = st.begin()) return rc;
-    int rc = st.finish(dfm_filter_ar_batch_dev(h, B, T, N, r, p, q, H, t0, x_d, lam_d, R_d, rho_d, A_d, Q_d, mu_d, P0_d, mean_d, sd_d, zp_d,
-                                               pp_d, zf_d, pf_d, ll_d, xp_d, ve_d, vs_d, m_d, mc_d, m0_d, cnt_d, flags));
+    int rc = st.finish(dfm_filter_ar_batch_dev(h, B, T, N, r, p, q, H, t0, x_d, md.Lam, md.R, md.rho, md.A, md.Q, md.mu0, md.P0, md.mean, md.sd,
+                                               zp_d, pp_d, zf_d, pf_d, ll_d, xp_d, ve_d, vs_d, m_d, mc_d, m0_d, cnt_d, flags));
     if (rc == 0) rc = status_check(h);
     return rc;
 }

@@ -112,7 +112,8 @@ def test_the_launchers_say_what_the_restatement_says():
                  "if (r <= 16) return f(std::integral_constant<int, 16>{});", "return f(std::integral_constant<int, 32>{});"):
         assert line in cg, line
     # the sweep: the gram kernel only without the flag; the pass's admission
-    assert "if (!missing) {\n            ProfScope ps(h, K_GB_GRAM);" in capi
+    assert "if (!missing) HIP_LAUNCH(h, K_GB_GRAM, launch_gibbs_gram(a, h->stream));" in capi
+    assert capi.count("launch_gibbs_gram(") == 1
     assert "int collapse_max_n(int Rpad) { return Rpad <= 8 ? 1024 : Rpad <= 16 ? 512 : 256; }" in src("collapse.hip")
     assert "if (plain && pad_r(r) == 32 && (collapse_wide2_supported(32, N) || collapse_wide2_supported(32, N + 1))) return 0;" in capi
     assert "if (N > collapse_max_n(pad_r(r)))" in capi
