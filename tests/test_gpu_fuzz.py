@@ -186,10 +186,11 @@ def test_dispatch_edges_of_the_sequential_path(ctx, B, N, T, r, why):
 
 
 def test_companion_state_32_wide_with_large_lds(ctx):
-    """r = 8, VAR(4), T = 700: Grid<32> with more than 64 KB of dynamic LDS (tiles + period index)."""
+    """r = 8, VAR(4), T = 760: Grid<32> with more than 64 KB of dynamic LDS (tiles + period index: 62 528 + 4 T bytes, the opt-in of
+    launch_wave_cov_ch is first taken at T = 753; tests/test_gpu_varp_routes.py runs both sides of that edge)."""
     import torch
     from oracle import varp_oracle as vo
-    B, N, T, r, p = 2, 40, 700, 8, 4
+    B, N, T, r, p = 2, 40, 760, 8, 4
     keys = ("Lam", "R", "Avar", "Q", "mu0", "P0")
     xs = [vo.synth_varp(b, N, T, r, p, missing=0.05) for b in range(B)]
     qs = [vo.varp_init(np.nan_to_num(x), r, p)[0] for x in xs]
