@@ -57,6 +57,8 @@ _FT_ARGS = [c_vp] + [c_int] * 7 + [c_vp] * 20 + [c_uint]
 _FCAR_ARGS = [c_vp] + [c_int] * 7 + [c_vp] * 18 + [c_uint]
 _FTAR_ARGS = [c_vp] + [c_int] * 8 + [c_vp] * 22 + [c_uint]
 _SSAR_ARGS = [c_vp] + [c_int] * 8 + [c_vp] * 11 + [ctypes.c_uint64, ctypes.c_int64, c_vp, c_vp, c_uint]
+_SIM_ARGS = [c_vp] + [c_int] * 6 + [c_vp] * 7 + [ctypes.c_uint64, ctypes.c_int64, c_vp, c_vp, c_uint]
+_SIMAR_ARGS = [c_vp] + [c_int] * 7 + [c_vp] * 9 + [ctypes.c_uint64, ctypes.c_int64, c_vp, c_vp, c_uint]
 _ARPASS_ARGS = [c_vp, c_int, c_int, c_int, c_int, c_int, c_int] + [c_vp] * 11 + [c_uint]
 _AREM_ARGS = [c_vp, c_int, c_int, c_int, c_int, c_int, c_int] + [c_vp] * 8 + [c_int, ctypes.c_double] + [c_vp] * 4 + [c_uint]
 _MFPASS_ARGS = [c_vp, c_int, c_int, c_int, c_int, c_int, c_int] + [c_vp] * 11 + [c_uint]
@@ -136,6 +138,10 @@ SYMBOLS = {
     "dfm_filter_ar_batch": (c_int, _FTAR_ARGS),
     "dfm_simsmooth_ar_batch_dev": (c_int, _SSAR_ARGS),
     "dfm_simsmooth_ar_batch": (c_int, _SSAR_ARGS),
+    "dfm_simulate_batch_dev": (c_int, _SIM_ARGS),
+    "dfm_simulate_batch": (c_int, _SIM_ARGS),
+    "dfm_simulate_ar_batch_dev": (c_int, _SIMAR_ARGS),
+    "dfm_simulate_ar_batch": (c_int, _SIMAR_ARGS),
     "dfm_gibbs_ar_batch_dev": (c_int, _GBAR_ARGS),
     "dfm_gibbs_ar_batch": (c_int, _GBAR_ARGS),
     "dfm_news_ar_batch_dev": (c_int, _NWAR_ARGS),

@@ -150,7 +150,7 @@ def drop_missing_col(A: np.ndarray):
 # ----------------------------------------------------------------------------- estimate!(m, ::Parametric)
 def estimate(m: DFMModel, method: EstimationMethod = None, *, max_em_iter: int = 50, tol_em: float = 1e-6,
              factor_lags: Optional[int] = None, ctx=None, lam_constr_f=None, lam_constr_fl=None,
-             nrep: int = 0, seed: int = 20160415, ngpu: int = 1):
+             nrep: int = 0, seed: int = 20160415, ngpu: int = 1, draws: Optional[str] = None):
     """`estimate!(m::DFMModel, ::Parametric; max_em_iter, tol_em)`: PCA-initialised EM for the exact
     Gaussian state-space DFM  x_t = Lam f_t + e_t,  f_t = A f_{t-1} + eta_t  on the standardised
     estimation window (rows initperiod..lastperiod, series with inclcode == 1), fitted with the HIP
@@ -170,7 +170,13 @@ def estimate(m: DFMModel, method: EstimationMethod = None, *, max_em_iter: int =
     parametric-bootstrap replicates of the standardised window are drawn from the fitted model (the window's own missing
     pattern; NumPy generator seeded with `seed`) and re-estimated by EM in ONE batched call on `ngpu` GPUs of this node
     (dfm_em_batch_multi: replicates sharded over the GPUs, one RCCL all-gather of {loglik, active} per EM iteration);
-    the replicate estimates land in `m.replicates`.  Needs factor_lags = 1.
+    the replicate estimates land in `m.replicates`.  That host generator serves factor_lags = 1 and is the default there.
+    `draws="device"` (the default, and the only way, for factor_lags > 1): the panels are drawn on the device from the point
+    estimate by dfm_simulate_batch (the random stream of dfm_simsmooth_batch, key `seed`, draw b = replicate b; the window's NaN
+    pattern) and re-estimated from the point estimate where they lie, in one dfm_em_varp_batch_dev call (dfm_em_batch_dev at
+    factor_lags = 1) on one GPU; a fit that needed the covariance-form recursion re-estimates in it too.  `m.replicates` has the
+    same keys either way; with factor_lags > 1 params["A"] = params["Avar"] = [A_1 .. A_p], which is what every band-producing
+    function reads.
     `NonParametric()` runs the reference's own estimator (ALS, loadings, VAR) on the HIP kernels of als.hip:
     see estimate_nonparametric below."""
     method = Parametric() if method is None else method
@@ -188,8 +194,15 @@ def estimate(m: DFMModel, method: EstimationMethod = None, *, max_em_iter: int =
     nlag = m.n_factorlag if factor_lags is None else int(factor_lags)
     if nlag < 1 or r * nlag > 32:
         raise ValueError("need 1 <= factor_lags and nfac_u * factor_lags <= 32 (DFM_MAX_R)")
-    if nrep and nlag != 1:
-        raise ValueError("bootstrap replicates (nrep > 0) need factor_lags = 1")
+    if draws not in (None, "host", "device"):
+        raise ValueError('draws must be "host", "device" or None (host at factor_lags = 1, device beyond)')
+    dev_draws = draws == "device" or (draws is None and nlag > 1)
+    if nrep and nlag > 1 and not dev_draws:
+        raise ValueError('the host generator of bootstrap panels serves factor_lags = 1 only: draws="device"')
+    if nrep and nlag > 1 and int(ngpu) > 1:
+        raise ValueError("bootstrap replicates with factor_lags > 1 run on one GPU (there is no multi-GPU VAR(p) EM): ngpu = 1")
+    if nrep and dev_draws and int(ngpu) > 1:
+        raise ValueError('draws="device" re-estimates the replicates on one GPU: ngpu = 1')
     incl = m.inclcode == 1
     xdata = m.data[m.initperiod - 1:m.lastperiod, :][:, incl]           # :335-336
     z, sd = standardize_data(xdata)                                     # :339
@@ -209,6 +222,7 @@ def estimate(m: DFMModel, method: EstimationMethod = None, *, max_em_iter: int =
         from .kalman import DfmContext
         ctx = DfmContext()                                              # raises without a HIP device
     try:
+        used_singular_q = False
         p0, F0 = ctx.pca_init_batch_host(xbal[None, :, :], r)          # pca_score (:179-183) + OLS start, on the GPU
         F0 = F0[0]
         Lam = np.empty((N, r)); R = np.empty(N)
@@ -223,7 +237,6 @@ def estimate(m: DFMModel, method: EstimationMethod = None, *, max_em_iter: int =
             from ._lib import DfmError
             args = (z[None], start["Lam"], start["R"], start["A"], start["Q"], start["mu0"], start["P0"])
             kw = dict(max_iter=max_em_iter, tol=tol_em, may_have_missing=bool((~obs).any()))
-            used_singular_q = False
             try:
                 params, path, iters, f, P = ctx.em_batch_host(*args, **kw)
             except DfmError as err:
@@ -253,6 +266,7 @@ def estimate(m: DFMModel, method: EstimationMethod = None, *, max_em_iter: int =
                 if err.code != -5:
                     raise
                 params, path, iters, f, P = ctx.em_varp_batch_host(*vargs, singular_q=True, **vkw)
+                used_singular_q = True
             params = dict(params)
             params["A"] = params["Avar"]
     finally:
@@ -290,9 +304,16 @@ def estimate(m: DFMModel, method: EstimationMethod = None, *, max_em_iter: int =
     var.betahat[:] = 0.0
     c0 = 1 if var.withconst else 0
     var.betahat[c0:c0 + ka, :] = A[:, :ka].T
-    if nrep:
+    if nrep and dev_draws:
+        c, own = _own(None if own_ctx else ctx)
+        try:
+            m.replicates = _bootstrap_replicates_device(c, z, params, nlag, int(nrep), int(seed), max_em_iter, tol_em, used_singular_q)
+        finally:
+            if own:
+                c.close()
+    elif nrep:
         m.replicates = _bootstrap_replicates(z, params, int(nrep), int(seed), int(ngpu), max_em_iter, tol_em,
-                                             singular_q=(nlag == 1 and used_singular_q))
+                                             singular_q=used_singular_q)
     return m.loglik_path
 
 
@@ -395,6 +416,44 @@ def _bootstrap_replicates(z, params, nrep, seed, ngpu, max_em_iter, tol_em, sing
                                                                  rep(P0), max_iter=max_em_iter, tol=tol_em,
                                                                  singular_q=singular_q)
     return dict(params=new, loglik_path=path, iters=iters, iterations=ran, panels=panels)
+
+
+def _em_resident(em, panels, start, names, nrep, max_em_iter, tol_em, singular_q, sync, **kw):
+    """One EM call on resident panels [nrep, T, N], every replicate started from `start` (name -> device tensor [1, ...]): the
+    updated parameters, log-likelihood paths and iteration counts on the host.  The device entries only enqueue, so a replicate
+    whose first log-likelihood is not finite is what the host entries report as DFM_E_NUMERIC: like the point estimate, the call
+    is then run once more in covariance form."""
+    for sq in ((True,) if singular_q else (False, True)):
+        P = [start[k].expand(nrep, *start[k].shape[1:]).contiguous() for k in names]
+        path, iters = em(panels, *P, max_iter=max_em_iter, tol=tol_em, singular_q=sq, **kw)[:2]
+        sync()
+        path, iters = path.cpu().numpy(), iters.cpu().numpy()
+        if np.isfinite(path[:, 0]).all():
+            break
+    else:
+        from ._lib import DfmError
+        raise DfmError(-5, "bootstrap replicates: non-finite log-likelihood (Q or P0 not positive definite?)")
+    return {k: a.cpu().numpy() for k, a in zip(names, P)}, path, iters
+
+
+def _bootstrap_replicates_device(ctx, z, params, nlag, nrep, seed, max_em_iter, tol_em, singular_q=False):
+    """`nrep` parametric-bootstrap panels drawn on the device from the fitted model on the standardised window z (NaN where z is
+    NaN: dfm_simulate_batch, replicate b = draw b of seed `seed`), re-estimated from the point estimate where they lie
+    (dfm_em_varp_batch_dev; dfm_em_batch_dev at factor_lags = 1).  The keys of _bootstrap_replicates."""
+    torch = ctx._torch
+    names = ("Lam", "R", "A" if nlag == 1 else "Avar", "Q", "mu0", "P0")
+    dev = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64), device=f"cuda:{ctx.device}")
+    start = {k: dev(params[k][:1]) for k in names}
+    miss = bool(np.isnan(z).any())
+    sim = ctx.simulate_batch(*(start[k] for k in names), D=nrep, T=z.shape[0], mask_panel=dev(z[None]) if miss else None,
+                             seed=seed, want_f=False)
+    panels = sim["x"][0]
+    em = ctx.em_batch if nlag == 1 else ctx.em_varp_batch
+    new, path, iters = _em_resident(em, panels, start, names, nrep, max_em_iter, tol_em, singular_q, ctx.synchronize,
+                                    may_have_missing=miss)
+    if nlag > 1:
+        new["A"] = new["Avar"]
+    return dict(params=new, loglik_path=path, iters=iters, iterations=int(iters.max()), panels=panels.cpu().numpy())
 
 
 # ----------------------------------------------------------------------------- nowcasts and forecasts of the panel
@@ -1059,6 +1118,41 @@ def draw_paths(m: DFMModel, ndraws: int, H: int = 0, *, through: Optional[int] =
     obs = ~np.isnan(xr)
     x[..., :xr.shape[0], :][..., obs] = xr[obs]
     return dict(rows=np.arange(m.initperiod, through + H + 1), cols=cols, factor=factor, x=x)
+
+
+def simulate(m: DFMModel, ndraws: int, *, seed: int = 20160415, masked: bool = True, ctx=None) -> dict:
+    """`ndraws` panels simulated from the parametric fit (`estimate(m, Parametric())`, nfac_o = 0) over the estimation window, for
+    Monte-Carlo work that is not a bootstrap: the size of a test under the fitted model, the sampling spread of a statistic.
+    One dfm_simulate_batch call on the GPU (the random stream of `draw_paths`' unconditional step: draw d of `seed`).
+    Returns a dict:
+      rows        1-based periods initperiod .. lastperiod
+      cols        column indices (0-based) of m.data: the series estimate() used
+      x           [ndraws, rows, cols] data units (window mean + s.d. times the simulated standardised cell); `masked`: NaN where
+                  the window's own cell is missing, else balanced
+      factor      [ndraws, rows, r] the simulated factor paths (the model's standardised factor units)
+    `m` is not modified."""
+    ndraws = int(ndraws)
+    if ndraws < 1:
+        raise ValueError("ndraws must be >= 1")
+    if m.em_params is None:
+        raise ValueError("the model has not been estimated: run estimate(m, Parametric()) first")
+    if m.nfac_o != 0:
+        raise ValueError("simulate needs nfac_o = 0 (observed factors have no model to draw from)")
+    ep = m.em_params
+    A = ep["Avar"] if "Avar" in ep else ep["A"]
+    cols, z, mu, sd = _forecast_inputs(m, m.lastperiod)
+    if ep["Lam"].shape[0] != cols.size:
+        raise ValueError("m.em_params does not match the model's series (was the model changed after estimate?)")
+    if z.shape[0] < A.shape[1] // ep["Lam"].shape[1]:
+        raise ValueError("the window is shorter than the number of factor lags")
+    ctx, own = _own(ctx)
+    try:
+        o = ctx.simulate_batch_host(ep["Lam"][None], ep["R"][None], A[None], ep["Q"][None], ep["mu0"][None], ep["P0"][None], ndraws,
+                                    T=z.shape[0], mask_panel=z[None] if masked and np.isnan(z).any() else None, seed=int(seed))
+    finally:
+        if own:
+            ctx.close()
+    return dict(rows=np.arange(m.initperiod, m.lastperiod + 1), cols=cols, x=mu + sd * o["x"][0], factor=o["f"][0])
 
 
 def estimate_bayesian(m: DFMModel, ndraws: int, *, chains: int = 4, burn: int = 500, thin: int = 1, prior=None,
@@ -1930,7 +2024,32 @@ def smooth_factors_ar_idio(m: DFMModel, *, ctx=None):
     return dict(loglik=float(ll[0]), factor=factor, P=P[0], series=cols, inputs=inputs, mu_f=mu_f)
 
 
-def estimate_ar_idio(m: DFMModel, *, max_em_iter: int = 20, tol_em: float = 1e-6, ctx=None):
+def _ar_v0(m: DFMModel, cols, c_i, Lam):
+    """The variance of the q idiosyncratic terms before the first output row: the window's sample variance of Y - c_i - F lam_i."""
+    win = slice(m.initperiod - 1, m.lastperiod)
+    return np.nanvar(m.data[win][:, cols] - c_i - m.factor[win] @ Lam.T, axis=0)
+
+
+def _bootstrap_replicates_ar(ctx, m: DFMModel, x, cols, est, nrep, seed, max_em_iter, tol_em):
+    """`nrep` parametric-bootstrap panels of the AR-idiosyncratic fit `est` (the parameters dfm_em_ar_batch returned, [1, ...]),
+    drawn on the device conditional on the first n_uarlag rows of the window panel x (dfm_simulate_ar_batch: replicate b = draw b
+    of seed `seed`, the panel's NaN pattern, the v0 of forecast_ar_idio at the fitted model) and re-estimated from the fit where
+    they lie, in one dfm_em_ar_batch_dev call."""
+    torch = ctx._torch
+    dev = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64), device=f"cuda:{ctx.device}")
+    _, _, _, c_i = _ar_model_inputs(m)                       # the intercepts of the model as the fit left it
+    v0 = _ar_v0(m, cols, c_i, est["Lam"][0])
+    start = {k: dev(est[k][:1]) for k in _AR_PARAM_NAMES}
+    sim = ctx.simulate_ar_batch(*(start[k] for k in _AR_PARAM_NAMES), D=nrep, panel=dev(x[None]), v0=dev(v0[None]), seed=seed,
+                                want_f=False)
+    panels = sim["x"][0]
+    new, path, iters = _em_resident(ctx.em_ar_batch, panels, start, _AR_PARAM_NAMES, nrep, max_em_iter, tol_em, False,
+                                    ctx.synchronize, may_have_missing=bool(np.isnan(x).any()))
+    return dict(params=new, loglik_path=path, iters=iters, panels=panels.cpu().numpy(), v0=v0,
+                fit={k: np.array(est[k][:1]) for k in _AR_PARAM_NAMES})
+
+
+def estimate_ar_idio(m: DFMModel, *, max_em_iter: int = 20, tol_em: float = 1e-6, nrep: int = 0, seed: int = 20160415, ctx=None):
     """JOINT estimation of the parametric model with AR(n_uarlag) idiosyncratic terms -- the
     re-estimation of `lambda`, `uar_coef`, `uar_ser` and the factor VAR that the reference's two-step estimator
     (:391-415, :444-468) never does.  Started from `estimate(m, NonParametric())` (`_ar_model_inputs`: the reference's own
@@ -1939,7 +2058,19 @@ def estimate_ar_idio(m: DFMModel, *, max_em_iter: int = 20, tol_em: float = 1e-6
     factor mean stay at their two-step values.  Mutates m IN PLACE like the reference's estimators: `lambda`, `uar_coef`,
     `uar_ser` of the series used, `factor` (smoothed, rows initperiod + n_uarlag .. lastperiod), `factor_var_model`
     (`betahat` slope rows, `seps`, `M`, `Q`, `G` through `fill_matrices`).  Returns the log-likelihood path (conditional on
-    the first n_uarlag window rows; non-decreasing)."""
+    the first n_uarlag window rows; non-decreasing).
+    `nrep` > 0: after the fit, `nrep` parametric-bootstrap replicates of the window panel are drawn on the device from the fitted
+    model, conditional on the panel's first n_uarlag rows -- what the likelihood conditions on -- with its NaN pattern and the
+    pre-sample variance v0 of `forecast_ar_idio` (dfm_simulate_ar_batch: the random stream of dfm_simsmooth_ar_batch, key `seed`,
+    draw b = replicate b), and re-estimated from the fit in ONE dfm_em_ar_batch_dev call.  They land in
+    `m.replicates_ar = dict(params, loglik_path, iters, panels, v0, fit)`; `params` (name -> [nrep, ...], the layout of
+    `estimate_bayesian_ar_idio`'s) is what `forecast_ar_idio`, `filter_states_ar_idio`, `evaluate_forecasts_ar_idio`,
+    `news_ar_idio` and `draw_paths_ar_idio` take as `params=`.  Needs 1 <= n_uarlag <= 4."""
+    nrep = int(nrep)
+    if nrep < 0:
+        raise ValueError("nrep must be >= 0")
+    if nrep and not (1 <= int(m.n_uarlag) <= 4):
+        raise ValueError("bootstrap replicates (nrep > 0) need 1 <= n_uarlag <= 4")
     inputs, cols, mu_f, _ = _ar_model_inputs(m)
     var = m.factor_var_model
     r, p, q = m.nfac_u, var.nlag, m.n_uarlag
@@ -1948,24 +2079,26 @@ def estimate_ar_idio(m: DFMModel, *, max_em_iter: int = 20, tol_em: float = 1e-6
         est, path, iters, f, _ = ctx.em_ar_batch_host(inputs["x"][None], inputs["Lam"][None], inputs["sig2"][None],
                                                       inputs["rho"][None], inputs["Avar"][None], inputs["Q"][None],
                                                       inputs["mu0"][None], inputs["P0"][None], max_iter=max_em_iter, tol=tol_em)
+        m.lambda_[cols] = est["Lam"][0]
+        m.uar_coef[cols] = est["rho"][0]
+        m.uar_ser[cols] = np.sqrt(est["sig2"][0])
+        m.factor[m.initperiod - 1 + q:m.lastperiod] = f[0] + mu_f
+        c0 = 1 if var.withconst else 0
+        A = est["Avar"][0]
+        var.betahat[c0:c0 + r * p] = A.T
+        if var.withconst:                                        # the factor mean is held: c_f = (I - sum A_l) mu_f
+            var.betahat[0] = (np.eye(r) - sum(A[:, l * r:(l + 1) * r] for l in range(p))) @ mu_f
+        var.seps = est["Q"][0]
+        _fill_matrices(var)
+        if nrep:
+            m.replicates_ar = _bootstrap_replicates_ar(ctx, m, inputs["x"], cols, est, nrep, int(seed), max_em_iter, tol_em)
     finally:
         if own:
             ctx.close()
-    m.lambda_[cols] = est["Lam"][0]
-    m.uar_coef[cols] = est["rho"][0]
-    m.uar_ser[cols] = np.sqrt(est["sig2"][0])
-    m.factor[m.initperiod - 1 + q:m.lastperiod] = f[0] + mu_f
-    c0 = 1 if var.withconst else 0
-    A = est["Avar"][0]
-    var.betahat[c0:c0 + r * p] = A.T
-    if var.withconst:                                            # the factor mean is held: c_f = (I - sum A_l) mu_f
-        var.betahat[0] = (np.eye(r) - sum(A[:, l * r:(l + 1) * r] for l in range(p))) @ mu_f
-    var.seps = est["Q"][0]
-    _fill_matrices(var)
     return path[0, :int(iters[0])].copy()
 
 
-def forecast_ar_idio(m: DFMModel, H: int, *, through: Optional[int] = None, ctx=None) -> dict:
+def forecast_ar_idio(m: DFMModel, H: int, *, through: Optional[int] = None, params=None, quantiles=None, ctx=None) -> dict:
     """Nowcasts and H-step forecasts of the panel from the model with AR(n_uarlag) idiosyncratic terms, after
     `estimate(m, NonParametric())`, optionally followed by `estimate_ar_idio(m)` (`_ar_model_inputs`: whatever loadings, `uar_coef`,
     `uar_ser` and factor VAR the model holds).  What `forecast` gives for the parametric fit, with the idiosyncratic persistence
@@ -1985,7 +2118,10 @@ def forecast_ar_idio(m: DFMModel, H: int, *, through: Optional[int] = None, ctx=
       factor      [rows, r] E[f_t | X] (with the factor mean mu_f, which is returned too), factor_cov [rows, r, r] = Var[f_t | X]
       loglik      log-likelihood of rows initperiod + q .. through, conditional on the first q rows
       inputs      the arrays handed to the library (those of `_ar_model_inputs`, v0 and mean), for the parity test
-    `m` is not modified."""
+    `quantiles` (needs `params`: S parameter sets on the first axis, `m.replicates_ar["params"]` of `estimate_ar_idio(nrep=...)`
+    or `estimate_bayesian_ar_idio`'s): every set runs in ONE batched call on the same panel, and dfm_quantile_bands over the sets'
+    horizon rows gives bands [nq, H, len(cols)] (nearest rank) -- the PARAMETER uncertainty of the point forecast only, as in
+    `forecast`; the point forecast stays that of the model's own parameters.  `m` is not modified."""
     H = int(H)
     if H < 0:
         raise ValueError("H must be >= 0")
@@ -1995,10 +2131,23 @@ def forecast_ar_idio(m: DFMModel, H: int, *, through: Optional[int] = None, ctx=
     through = m.lastperiod if through is None else int(through)
     if not (m.lastperiod <= through <= m.T):
         raise ValueError(f"through must lie in lastperiod..T ({m.lastperiod}..{m.T})")
+    qs = None
+    if quantiles is not None:
+        if params is None:
+            raise ValueError("quantile bands need parameter sets: params=m.replicates_ar['params'] of estimate_ar_idio(nrep=...)")
+        if H < 1:
+            raise ValueError("quantile bands need H >= 1")
+        qs = np.atleast_1d(np.asarray(quantiles, dtype=np.float64))
+        if qs.size < 1 or not np.all((qs > 0.0) & (qs <= 1.0)):
+            raise ValueError("quantiles must lie in (0, 1]")
+    elif params is not None:
+        raise ValueError("params serve the quantile bands: give quantiles= with them")
     inputs, cols, mu_f, c_i = _ar_model_inputs(m, through)
+    sets = None if params is None else _ar_param_sets(inputs, params)
+    if sets is not None and sets[0].shape[0] > _QUANTILE_MAX_DRAWS:
+        raise ValueError(f"bands need at most {_QUANTILE_MAX_DRAWS} parameter sets")
     r = m.nfac_u
-    win = slice(m.initperiod - 1, m.lastperiod)
-    v0 = np.nanvar(m.data[win][:, cols] - c_i - m.factor[win] @ inputs["Lam"].T, axis=0)
+    v0 = _ar_v0(m, cols, c_i, inputs["Lam"])
     mean = c_i + inputs["Lam"] @ mu_f
     x = inputs["x"]
     ctx, own = _own(ctx)
@@ -2007,6 +2156,13 @@ def forecast_ar_idio(m: DFMModel, H: int, *, through: Optional[int] = None, ctx=
                                        inputs["Avar"][None], inputs["Q"][None], inputs["mu0"][None], inputs["P0"][None], H,
                                        v0=v0[None], mean=mean[None], sd=np.ones((1, cols.size)),
                                        may_have_missing=bool(np.isnan(x).any()))
+        bands = None
+        if qs is not None:
+            S = sets[0].shape[0]
+            rep = lambda a: np.ascontiguousarray(np.broadcast_to(a, (S,) + a.shape))
+            ob = ctx.forecast_ar_batch_host(rep(x), *sets, H, v0=rep(v0), mean=rep(mean), sd=np.ones((S, cols.size)), want=(),
+                                            may_have_missing=bool(np.isnan(x).any()))
+            bands = ctx.quantile_bands_host(ob["xhat"][:, -H:, :], qs)
     finally:
         if own:
             ctx.close()
@@ -2015,9 +2171,45 @@ def forecast_ar_idio(m: DFMModel, H: int, *, through: Optional[int] = None, ctx=
     cov = np.empty((Pp.shape[0], r, r))
     cov[:, il[0], il[1]] = Pp
     cov[:, il[1], il[0]] = Pp
-    return dict(rows=np.arange(m.initperiod + q, through + H + 1), cols=cols, x=o["xhat"][0], x_sd=np.sqrt(o["xvar"][0]),
-                common=o["common"][0], idio=o["idio"][0], factor=o["f"][0] + mu_f, factor_cov=cov, loglik=float(o["loglik"][0]),
-                mu_f=mu_f, inputs=dict(inputs, v0=v0, mean=mean))
+    out = dict(rows=np.arange(m.initperiod + q, through + H + 1), cols=cols, x=o["xhat"][0], x_sd=np.sqrt(o["xvar"][0]),
+               common=o["common"][0], idio=o["idio"][0], factor=o["f"][0] + mu_f, factor_cov=cov, loglik=float(o["loglik"][0]),
+               mu_f=mu_f, inputs=dict(inputs, v0=v0, mean=mean))
+    if bands is not None:
+        out["quantiles"] = qs
+        out["bands"] = bands
+    return out
+
+
+def simulate_ar_idio(m: DFMModel, ndraws: int, *, seed: int = 20160415, masked: bool = True, ctx=None) -> dict:
+    """`ndraws` panels simulated from the model with AR(n_uarlag) idiosyncratic terms the model holds (`_ar_model_inputs`, as
+    `forecast_ar_idio`), over the estimation window: what `simulate` is for the parametric fit.  One dfm_simulate_ar_batch call on
+    the GPU.  `masked` (default): the draws are conditional on the window's first q = n_uarlag rows, which they repeat, and carry
+    the window's NaN pattern -- the panels a bootstrap of `estimate_ar_idio` re-estimates; masked=False: every cell of every row is
+    simulated, the q idiosyncratic terms before row initperiod + q with the variance v0 of `forecast_ar_idio`.  Returns a dict:
+      rows        1-based periods initperiod .. lastperiod
+      cols        column indices (0-based) of m.data: the series `_ar_model_inputs` used
+      x           [ndraws, rows, cols] data units
+      factor      [ndraws, rows from initperiod + q, r] the simulated factor paths, with the factor mean mu_f
+    `m` is not modified."""
+    ndraws = int(ndraws)
+    if ndraws < 1:
+        raise ValueError("ndraws must be >= 1")
+    q = int(m.n_uarlag)
+    if not (1 <= q <= 4):
+        raise ValueError("simulate_ar_idio needs 1 <= n_uarlag <= 4")
+    inputs, cols, mu_f, c_i = _ar_model_inputs(m)
+    if inputs["x"].shape[0] <= q:
+        raise ValueError("the window must be longer than n_uarlag")
+    v0 = _ar_v0(m, cols, c_i, inputs["Lam"])
+    mean = c_i + inputs["Lam"] @ mu_f
+    ctx, own = _own(ctx)
+    try:
+        o = ctx.simulate_ar_batch_host(*(inputs[k][None] for k in _AR_PARAM_NAMES), ndraws, T=inputs["x"].shape[0],
+                                       panel=inputs["x"][None] if masked else None, v0=v0[None], seed=int(seed))
+    finally:
+        if own:
+            ctx.close()
+    return dict(rows=np.arange(m.initperiod, m.lastperiod + 1), cols=cols, x=o["x"][0] + mean, factor=o["f"][0] + mu_f)
 
 
 def draw_paths_ar_idio(m: DFMModel, ndraws: int, H: int = 0, *, through: Optional[int] = None, seed: int = 20160415,
@@ -2202,6 +2394,19 @@ def estimate_bayesian_ar_idio(m: DFMModel, ndraws: int, *, chains: int = 4, burn
 _AR_PARAM_NAMES = ("Lam", "sig2", "rho", "Avar", "Q", "mu0", "P0")
 
 
+def _ar_param_sets(inputs, params):
+    """`params` (name -> [S, ...] in the layout of _AR_PARAM_NAMES) checked against the model's own shapes: the S sets as arrays."""
+    lost = [k for k in _AR_PARAM_NAMES if k not in params]
+    if lost:
+        raise ValueError(f"params lacks {lost}")
+    sets = [np.ascontiguousarray(params[k], dtype=np.float64) for k in _AR_PARAM_NAMES]
+    S = sets[0].shape[0] if sets[0].ndim == 3 else 0
+    for k, a in zip(_AR_PARAM_NAMES, sets):
+        if S < 1 or a.shape != (S,) + inputs[k].shape:
+            raise ValueError(f"params[{k!r}] must be [S, ...] with the model's own shape {inputs[k].shape} behind S >= 1")
+    return sets
+
+
 def _filter_ar_setup(m: DFMModel, through, params, who):
     """The checks and inputs filter_states_ar_idio and evaluate_forecasts_ar_idio share (no device is touched): q, through, the
     panel, the parameter sets [S, ...] (the model's own as one set without `params`), cols, mu_f and the data-unit mean."""
@@ -2212,16 +2417,7 @@ def _filter_ar_setup(m: DFMModel, through, params, who):
     if not (m.lastperiod <= through <= m.T):
         raise ValueError(f"through must lie in lastperiod..T ({m.lastperiod}..{m.T})")
     inputs, cols, mu_f, c_i = _ar_model_inputs(m, through)
-    sets = [inputs[k][None] for k in _AR_PARAM_NAMES]
-    if params is not None:
-        lost = [k for k in _AR_PARAM_NAMES if k not in params]
-        if lost:
-            raise ValueError(f"params lacks {lost}")
-        sets = [np.ascontiguousarray(params[k], dtype=np.float64) for k in _AR_PARAM_NAMES]
-        S = sets[0].shape[0] if sets[0].ndim == 3 else 0
-        for k, a in zip(_AR_PARAM_NAMES, sets):
-            if S < 1 or a.shape != (S,) + inputs[k].shape:
-                raise ValueError(f"params[{k!r}] must be [S, ...] with the model's own shape {inputs[k].shape} behind S >= 1")
+    sets = [inputs[k][None] for k in _AR_PARAM_NAMES] if params is None else _ar_param_sets(inputs, params)
     mean = c_i + inputs["Lam"] @ mu_f
     return q, through, inputs, sets, cols, mu_f, mean
 

@@ -189,11 +189,11 @@ struct dfm_handle {
 };
 
 enum KernelId { K_COLLAPSE = 0, K_RECURSION, K_MSTEP_STATS, K_MSTEP_SOLVE, K_PCA, K_SYNTH, K_PAD,
-                K_COLLAPSE_DMA, K_GRAM, K_COV, K_MEANSCAN, K_PFILL, K_COLLAPSE_MFMA, K_ALS, K_OLS, K_BOOT, K_QUANT, K_COLLAPSE_WIDE, K_EM_UPDATE, K_CHOW, K_MSTEP_MFMA, K_GRAM_XX, K_PASS_FUSED, K_FC_TAIL, K_FC_FILL, K_FC_PAD, K_SS_PREP, K_SS_EXPAND, K_SS_PATH, K_SS_DIFF, K_SS_FINISH, K_SS_FILL, K_NW_REVISE, K_NW_GATHER, K_NW_GAMMA, K_NW_COV, K_NW_IMPACT, K_MF_TABLE, K_MF_MOMENTS, K_MF_SOLVE, K_SV_PREP, K_SV_IRF_FILL, K_SV_SHOCK, K_SV_PATH, K_SV_HD_FILL, K_FT_FILTER, K_FT_FILL, K_FT_EVAL, K_GB_GRAM, K_GB_LOAD, K_GB_VAR, K_SV_SIGN_TABLE, K_SV_SIGN, K_SV_SIGN_KEEP, K_PX_ROWS, K_PX_MOMENT, K_PX_SLOT_TABLE, K_PX_DEN, K_PX_FILL, K_PX_SHOCK, K_MF_SOLVE_BLOCKS, K_FCAR_BACK, K_FCAR_FWD, K_SSAR_PARAMS, K_SSAR_EXPAND, K_SSAR_DIFF, K_SSAR_FWD, K_SSAR_FINISH, K_GB_AR_SERIES, K_FTAR_FILTER, K_FTAR_FILL, K_FTAR_EVAL, K_NWAR_REVISE, K_NWAR_REC, K_NWAR_QC, K_NWAR_IMPACT, K_COUNT };
+                K_COLLAPSE_DMA, K_GRAM, K_COV, K_MEANSCAN, K_PFILL, K_COLLAPSE_MFMA, K_ALS, K_OLS, K_BOOT, K_QUANT, K_COLLAPSE_WIDE, K_EM_UPDATE, K_CHOW, K_MSTEP_MFMA, K_GRAM_XX, K_PASS_FUSED, K_FC_TAIL, K_FC_FILL, K_FC_PAD, K_SS_PREP, K_SS_EXPAND, K_SS_PATH, K_SS_DIFF, K_SS_FINISH, K_SS_FILL, K_NW_REVISE, K_NW_GATHER, K_NW_GAMMA, K_NW_COV, K_NW_IMPACT, K_MF_TABLE, K_MF_MOMENTS, K_MF_SOLVE, K_SV_PREP, K_SV_IRF_FILL, K_SV_SHOCK, K_SV_PATH, K_SV_HD_FILL, K_FT_FILTER, K_FT_FILL, K_FT_EVAL, K_GB_GRAM, K_GB_LOAD, K_GB_VAR, K_SV_SIGN_TABLE, K_SV_SIGN, K_SV_SIGN_KEEP, K_PX_ROWS, K_PX_MOMENT, K_PX_SLOT_TABLE, K_PX_DEN, K_PX_FILL, K_PX_SHOCK, K_MF_SOLVE_BLOCKS, K_FCAR_BACK, K_FCAR_FWD, K_SSAR_PARAMS, K_SSAR_EXPAND, K_SSAR_DIFF, K_SSAR_FWD, K_SSAR_FINISH, K_GB_AR_SERIES, K_FTAR_FILTER, K_FTAR_FILL, K_FTAR_EVAL, K_NWAR_REVISE, K_NWAR_REC, K_NWAR_QC, K_NWAR_IMPACT, K_SIM_CELLS, K_SIMAR_CELLS, K_COUNT };
 static const char* const kKernelNames[K_COUNT] = {"collapse_kernel", "recursion_kernel", "mstep_lam_kernel",
                                                   "mstep_solve_kernel", "pca_kernel", "synth_kernel",
                                                   "pad_params_kernel", "collapse_dma_kernel", "gram_kernel",
-                                                  "cov_kernel", "meanscan_kernel", "pfill_kernel", "collapse_mfma_kernel", "als_kernel", "ols_kernel", "var_boot_kernel", "quantile_kernel", "collapse_wide_kernel", "em_update_kernel", "chow_kernel", "mstep_mfma_kernel", "gram_xx_kernel", "pass_fused_kernel", "forecast_tail_kernel", "forecast_fill_kernel", "forecast_pad_kernel", "simsmooth_prep_kernel", "simsmooth_expand_kernel", "simsmooth_path_kernel", "simsmooth_diff_kernel", "simsmooth_finish_kernel", "simsmooth_fill_kernel", "news_revise_kernel", "news_gather_kernel", "news_gamma_kernel", "news_cov_panel_kernel", "news_impact_kernel", "mf_table_kernel", "mf_moments_kernel", "mf_solve_kernel", "sv_prep_kernel", "sv_irf_fill_kernel", "sv_shock_kernel", "sv_path_kernel", "sv_hd_fill_kernel", "filter_kernel", "filter_fill_kernel", "filter_eval_kernel", "gibbs_gram_kernel", "gibbs_load_kernel", "gibbs_var_kernel", "sv_sign_table_kernel", "sv_sign_kernel", "sv_sign_keep_kernel", "px_rows_kernel", "px_moment_kernel", "px_slot_table_kernel", "px_den_kernel", "px_fill_kernel", "px_shock_kernel", "mf_solve_blocks_kernel", "forecast_ar_back_kernel", "forecast_ar_fwd_kernel", "simsmooth_ar_params_kernel", "simsmooth_ar_expand_kernel", "simsmooth_ar_diff_kernel", "simsmooth_ar_fwd_kernel", "simsmooth_ar_finish_kernel", "gibbs_ar_series_kernel", "filter_ar_kernel", "filter_ar_fill_kernel", "filter_ar_eval_kernel", "news_ar_revise_kernel", "news_ar_rec_kernel", "news_ar_qc_kernel", "news_ar_impact_kernel"};
+                                                  "cov_kernel", "meanscan_kernel", "pfill_kernel", "collapse_mfma_kernel", "als_kernel", "ols_kernel", "var_boot_kernel", "quantile_kernel", "collapse_wide_kernel", "em_update_kernel", "chow_kernel", "mstep_mfma_kernel", "gram_xx_kernel", "pass_fused_kernel", "forecast_tail_kernel", "forecast_fill_kernel", "forecast_pad_kernel", "simsmooth_prep_kernel", "simsmooth_expand_kernel", "simsmooth_path_kernel", "simsmooth_diff_kernel", "simsmooth_finish_kernel", "simsmooth_fill_kernel", "news_revise_kernel", "news_gather_kernel", "news_gamma_kernel", "news_cov_panel_kernel", "news_impact_kernel", "mf_table_kernel", "mf_moments_kernel", "mf_solve_kernel", "sv_prep_kernel", "sv_irf_fill_kernel", "sv_shock_kernel", "sv_path_kernel", "sv_hd_fill_kernel", "filter_kernel", "filter_fill_kernel", "filter_eval_kernel", "gibbs_gram_kernel", "gibbs_load_kernel", "gibbs_var_kernel", "sv_sign_table_kernel", "sv_sign_kernel", "sv_sign_keep_kernel", "px_rows_kernel", "px_moment_kernel", "px_slot_table_kernel", "px_den_kernel", "px_fill_kernel", "px_shock_kernel", "mf_solve_blocks_kernel", "forecast_ar_back_kernel", "forecast_ar_fwd_kernel", "simsmooth_ar_params_kernel", "simsmooth_ar_expand_kernel", "simsmooth_ar_diff_kernel", "simsmooth_ar_fwd_kernel", "simsmooth_ar_finish_kernel", "gibbs_ar_series_kernel", "filter_ar_kernel", "filter_ar_fill_kernel", "filter_ar_eval_kernel", "news_ar_revise_kernel", "news_ar_rec_kernel", "news_ar_qc_kernel", "news_ar_impact_kernel", "simulate_cells_kernel", "simulate_ar_cells_kernel"};
 
 namespace dfm { int handle_device(const dfm_handle* h) { return h->device; } }   // (probe.hip)
 
@@ -2845,8 +2845,117 @@ int dfm_simsmooth_ar_batch(dfm_handle* h, int B, int D, int T, int N, int r, int
     return rc;
 }
 
+// ---- panels simulated from a given model (simulate.hip) -----------------------------------------------------------------------
+// x+ of the two smoothers above, written out: the roots once, then per slice of at most kSsSlice pass replicates j = b D + d the
+// factor path f+ (simsmooth_path_kernel, into f_sim or h->ss) and the cells.  No pass runs: no N limit of the pass applies.
+static int simulate_check(dfm_handle* h, int B, int D, int T, int N, int r, int p, int q, const double* Lam, const double* R,
+                          const double* rho, const double* Avar, const double* Q, const double* mu0, const double* P0,
+                          const double* x_sim) {
+    if (!h) return DFM_E_NULL;
+    if (B < 1 || T < 1 || N < 1 || r < 1) return fail(h, DFM_E_DIMS, "B, T, N, r must be >= 1%s");
+    if (D < 1) return fail(h, DFM_E_DIMS, "D (draws per replicate) must be >= 1%s");
+    if (p < 1) return fail(h, DFM_E_DIMS, "number of factor lags must be >= 1%s");
+    if (q < 0 || q > 4) return fail(h, DFM_E_DIMS, "number of idiosyncratic lags must be 1 .. 4%s");
+    if ((long long)r * (q ? state_lags(p, q) : p) > DFM_MAX_R)
+        return fail(h, DFM_E_DIMS, "state wider than DFM_MAX_R (32): r p, or r max(p, q + 1) with AR idiosyncratic terms%s");
+    if (T < p) return fail(h, DFM_E_DIMS, "T must be >= p%s");
+    if (T <= q) return fail(h, DFM_E_DIMS, "T must exceed the number of idiosyncratic lags%s");
+    if ((long long)B * D > 0x7fffffffLL) return fail(h, DFM_E_DIMS, "B * D must be < 2^31%s");
+    if (!Lam || !R || (q && !rho) || !Avar || !Q || !mu0 || !P0 || !x_sim) return fail(h, DFM_E_NULL, "required pointer is NULL%s");
+    return 0;
+}
 
-// ---- Bayesian estimation: the Gibbs sampler (gibbs.hip) ------------------------------------------------------------------------
+// q = 0: the plain model (R, mask = the mask panel); q > 0: AR idiosyncratic terms (R = sig2, mask = the panel).
+static int simulate_run(dfm_handle* h, int B, int D, int T, int N, int r, int p, int q, const double* mask, const double* Lam,
+                        const double* R, const double* rho, const double* Avar, const double* Q, const double* mu0,
+                        const double* P0, const double* v0, uint64_t seed, int64_t first_draw, double* x_sim, double* f_sim) {
+    HIP_TRY(h, hipSetDevice(h->device));
+    const int m = q ? state_lags(p, q) : p;
+    const size_t d = sizeof(double), k = (size_t)r * m, n = (size_t)T - q;
+    const long long BD = (long long)B * D;
+    const int Smax = (int)(BD < kSsSlice ? BD : kSsSlice);
+    size_t off = 0;
+    const size_t o_LP0 = take(off, (size_t)B * k * k * d), o_LQ = take(off, (size_t)B * r * r * d),
+                 o_Ap = p < m ? take(off, (size_t)B * r * k * d) : (size_t)-1,
+                 o_f = f_sim ? (size_t)-1 : take(off, (size_t)BD * n * r * d);
+    HIP_TRY(h, h->ss.grow(off));
+    const double* Am;
+    if (int rc = pad_avar(h, B, r, p, m, Avar, at<double>(h->ss, o_Ap), &Am)) return rc;
+    SsArgs a{};
+    a.B = B; a.D = D; a.T = (int)n; a.N = N; a.r = r; a.p = m; a.H = 0;
+    a.panel = mask; a.Lam = Lam; a.R = R; a.A = Am; a.Q = Q; a.mu0 = mu0; a.P0 = P0;
+    a.seed = seed; a.first_draw = first_draw; a.f_draw = f_sim ? f_sim : at<double>(h->ss, o_f); a.x_draw = x_sim;
+    a.LP0 = at<double>(h->ss, o_LP0); a.LQ = at<double>(h->ss, o_LQ);
+    SsArArgs gen{};
+    gen.n = (int)n; gen.N = N; gen.r = r; gen.q = q;
+    gen.Lam = Lam; gen.sig2 = R; gen.rho = rho; gen.v0 = v0;
+    gen.dr.D = D; gen.dr.T = T; gen.dr.k = (int)k; gen.dr.seed = seed; gen.dr.first_draw = first_draw;
+    gen.dr.X = mask; gen.dr.fplus = a.f_draw; gen.dr.mu0 = mu0; gen.dr.LP0 = a.LP0; gen.dr.x_draw = x_sim;
+    HIP_LAUNCH(h, K_SS_PREP, launch_simsmooth_prep(a, h->stream));
+    for (long long j0 = 0; j0 < BD; j0 += Smax) {
+        const int S = (int)(BD - j0 < Smax ? BD - j0 : Smax);
+        a.j0 = j0; a.S = S; gen.dr.j0 = j0; gen.S = S;
+        HIP_LAUNCH(h, K_SS_PATH, launch_simsmooth_path(a, h->stream));
+        if (q) HIP_LAUNCH(h, K_SIMAR_CELLS, launch_simulate_ar_cells(gen, h->stream));
+        else HIP_LAUNCH(h, K_SIM_CELLS, launch_simulate_cells(a, h->stream));
+    }
+    return 0;
+}
+
+static int simulate_host(dfm_handle* h, int B, int D, int T, int N, int r, int p, int q, const double* mask, const double* Lam,
+                         const double* R, const double* rho, const double* Avar, const double* Q, const double* mu0,
+                         const double* P0, const double* v0, uint64_t seed, int64_t first_draw, double* x_sim, double* f_sim) {
+    if (int rc = status_epoch(h)) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t BD = (size_t)B * D;
+    HostStage st(h, 256);
+    ModelDev md;
+    double *x_d, *xo_d, *f_d;
+    st.in(mask, mask ? (size_t)B * T * N : 0, x_d);
+    stage_model(st, md, B, N, r, p, q, Lam, R, rho, Avar, Q, mu0, P0, v0, nullptr, nullptr);
+    st.out(x_sim, BD * T * N, xo_d); st.out(f_sim, f_sim ? BD * (size_t)(T - q) * r : 0, f_d);
+    if (int rc = st.begin()) return rc;
+    return st.finish(simulate_run(h, B, D, T, N, r, p, q, x_d, md.Lam, md.R, md.rho, md.A, md.Q, md.mu0, md.P0, md.v0, seed, first_draw,
+                                  xo_d, f_d));
+}
+
+int dfm_simulate_batch_dev(dfm_handle* h, int B, int D, int T, int N, int r, int p, const double* mask_panel, const double* Lam,
+                           const double* R, const double* Avar, const double* Q, const double* mu0, const double* P0, uint64_t seed,
+                           int64_t first_draw, double* x_sim, double* f_sim, unsigned flags) {
+    (void)flags;
+    if (int rc = simulate_check(h, B, D, T, N, r, p, 0, Lam, R, nullptr, Avar, Q, mu0, P0, x_sim)) return rc;
+    return simulate_run(h, B, D, T, N, r, p, 0, mask_panel, Lam, R, nullptr, Avar, Q, mu0, P0, nullptr, seed, first_draw, x_sim, f_sim);
+}
+
+int dfm_simulate_batch(dfm_handle* h, int B, int D, int T, int N, int r, int p, const double* mask_panel, const double* Lam,
+                       const double* R, const double* Avar, const double* Q, const double* mu0, const double* P0, uint64_t seed,
+                       int64_t first_draw, double* x_sim, double* f_sim, unsigned flags) {
+    (void)flags;
+    if (int rc = simulate_check(h, B, D, T, N, r, p, 0, Lam, R, nullptr, Avar, Q, mu0, P0, x_sim)) return rc;
+    return simulate_host(h, B, D, T, N, r, p, 0, mask_panel, Lam, R, nullptr, Avar, Q, mu0, P0, nullptr, seed, first_draw, x_sim, f_sim);
+}
+
+int dfm_simulate_ar_batch_dev(dfm_handle* h, int B, int D, int T, int N, int r, int p, int q, const double* panel, const double* Lam,
+                              const double* sig2, const double* rho, const double* Avar, const double* Q, const double* mu0,
+                              const double* P0, const double* v0, uint64_t seed, int64_t first_draw, double* x_sim, double* f_sim,
+                              unsigned flags) {
+    (void)flags;
+    if (h && q < 1) return fail(h, DFM_E_DIMS, "number of idiosyncratic lags must be 1 .. 4%s");
+    if (int rc = simulate_check(h, B, D, T, N, r, p, q, Lam, sig2, rho, Avar, Q, mu0, P0, x_sim)) return rc;
+    return simulate_run(h, B, D, T, N, r, p, q, panel, Lam, sig2, rho, Avar, Q, mu0, P0, v0, seed, first_draw, x_sim, f_sim);
+}
+
+int dfm_simulate_ar_batch(dfm_handle* h, int B, int D, int T, int N, int r, int p, int q, const double* panel, const double* Lam,
+                          const double* sig2, const double* rho, const double* Avar, const double* Q, const double* mu0,
+                          const double* P0, const double* v0, uint64_t seed, int64_t first_draw, double* x_sim, double* f_sim,
+                          unsigned flags) {
+    (void)flags;
+    if (h && q < 1) return fail(h, DFM_E_DIMS, "number of idiosyncratic lags must be 1 .. 4%s");
+    if (int rc = simulate_check(h, B, D, T, N, r, p, q, Lam, sig2, rho, Avar, Q, mu0, P0, x_sim)) return rc;
+    return simulate_host(h, B, D, T, N, r, p, q, panel, Lam, sig2, rho, Avar, Q, mu0, P0, v0, seed, first_draw, x_sim, f_sim);
+}
+
+// ---- Bayesian estimation: the Gibbs sampler (gibbs.hip)------------------------------------------------------------------------
 // Sweep j: the factor path of every chain by dfm_simsmooth_batch_dev (D = 1, H = 0, first_draw = first_sweep + j) into h->gb, then
 // lam_i, R_i | f and A, Q | f in place in the caller's state.  Nothing waits between the sweeps; kept sweeps are copied behind the
 // sweep in stream order.

@@ -68,6 +68,8 @@ struct SsArIdio {
     // The q terms before output row 0: the residual of the observed panel cell against f+ (x+ equals X there), a N(0, v0) draw
     // where the cell is missing.
     // i0: the first series of the lane's block (lane tid stands at series i0 + tid, which is se.i on a live lane).
+    // HASX = false (simulate_ar_cells_kernel without a panel, simulate.hip): dr.X is null and every term is such a draw.
+    template <bool HASX = true>
     __device__ __forceinline__ void start(const FcArArgs& a, const SsArDraw& dr, const FcArSeries<Q, RB>& se, size_t b, uint64_t key_,
                                           const double* sz, int i0) {
         key = key_;
@@ -82,7 +84,8 @@ struct SsArIdio {
         const double sv0 = sqrt(a.v0 ? a.v0[b * a.N + se.i] : se.sig2);
 #pragma unroll
         for (int l = 1; l <= Q; ++l) {
-            const double x = dr.X[(b * dr.T + (Q - l)) * a.N + se.i];
+            double x = __longlong_as_double(0x7FF8000000000000ll);
+            if constexpr (HASX) x = dr.X[(b * dr.T + (Q - l)) * a.N + se.i];
             const bool obs = x == x;
             double z0 = 0.0, z1 = 0.0;
             if (__any(!obs)) normal2(key, 16 * b + kSsArPre, (uint64_t)(l - 1) * hN + (uint64_t)(se.i / 2), z0, z1);

@@ -562,6 +562,13 @@ hipError_t launch_simsmooth_diff(SsArgs a, hipStream_t s);
 hipError_t launch_simsmooth_finish(const SsArgs& a, hipStream_t s);
 hipError_t launch_simsmooth_fill(SsArgs a, hipStream_t s);
 
+// Panels simulated from a given model (simulate.hip; dfm_simulate_batch, dfm_simulate_ar_batch): x+ of the smoothers' step 1, written
+// out.  Both read f+ of the slice from f_draw / dr.fplus, [B D][rows][r] with H = 0, as simsmooth_path_kernel leaves it.
+//   plain: a.panel is the mask panel [B][T][N] or null (balanced), a.x_draw the output [B D][T][N]
+//   AR:    a.dr.X is the panel [B][T][N] or null, a.dr.x_draw the output [B D][T][N] (rows < q included; a.n = T - q)
+hipError_t launch_simulate_cells(SsArgs a, hipStream_t s);
+hipError_t launch_simulate_ar_cells(const SsArArgs& a, hipStream_t s);
+
 // News decomposition of nowcast revisions (news.hip).  Pass replicate j = b G + g (replicate b, target g); a call runs its B G
 // weight passes in slices j0 .. j0 + S - 1.
 struct NwArgs {

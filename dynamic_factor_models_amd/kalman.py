@@ -906,3 +906,4 @@ from . import filtering_ar  # noqa: E402,F401  (attaches its filter entries)
 from . import simsmooth_ar  # noqa: E402,F401  (attaches its path-draw entries)
 from . import gibbs_ar  # noqa: E402,F401  (attaches the Gibbs sampler's entries of the AR-idiosyncratic model)
 from . import news_ar  # noqa: E402,F401  (attaches its news entries)
+from . import simulate  # noqa: E402,F401  (attaches the simulated-panel entries of both models)

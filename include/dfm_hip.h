@@ -702,6 +702,42 @@ int dfm_simsmooth_ar_batch(dfm_handle* h, int B, int D, int T, int N, int r, int
                            const double* mu0, const double* P0, const double* v0, const double* mean, const double* sd,
                            uint64_t seed, int64_t first_draw, double* f_draw, double* x_draw, unsigned flags);
 
+/* Panels simulated from a given model (csrc/simulate.hip): the parametric bootstrap's replicate panels, and Monte-Carlo panels in
+ * general.  D draws per replicate b; the model, its parameters and their shapes are those of dfm_simsmooth_batch (plain) and
+ * dfm_simsmooth_ar_batch (AR idiosyncratic terms; m = max(p, q + 1), mu0 [B][r m], P0 [B][r m][r m]).  No pass runs, so no N limit
+ * of a pass applies: any N >= 1, and a state (r p, or r m) of at most DFM_MAX_R.
+ * The random stream is part of the contract and is the smoothers': no new stream.
+ *   dfm_simulate_batch.  x_sim[b][d] [T][N] is x+ of step 1 of dfm_simsmooth_batch for the same (seed, first_draw, b, d): z+_0 from
+ *     stream 1, eta from stream 2, eps+ from stream 3, same key and same roots (a rank-deficient Q or P0 is fine).  A cell is NaN
+ *     wherever mask_panel [B][T][N] is NaN; mask_panel is read for its NaN pattern only, and NULL means a balanced panel.
+ *     f_sim [B][D][T][r] (may be NULL) is f+.
+ *   dfm_simulate_ar_batch.  Rows q .. T-1 of x_sim[b][d] [T][N] are x+ of steps 1-4 of dfm_simsmooth_ar_batch with H = 0 (streams 1,
+ *     2, 3 and 5; the pre-sample terms are X - lam' f+ where the panel cell is observed and sqrt(v0) n where it is not; v0 NULL:
+ *     sig2), NaN where `panel` [B][T][N] is NaN.  Rows < q: with a panel, its own cells bit for bit (NaN stays NaN) -- a bootstrap
+ *     conditional on the first q rows, which is what the likelihood of dfm_em_ar_batch conditions on; with panel NULL every cell is
+ *     simulated: row q - l is lam_i' f+_{q-l} + e+_{q-l,i}, f+_{q-l} being lag block l - 1 of z+ and e+_{q-l,i} = sqrt(v0_i) n the
+ *     pre-sample term l of stream 5.  f_sim [B][D][T-q][r] (may be NULL) is f+ of the output rows.
+ * Draws [k, k + D) of a call equal the draws of a call with first_draw = k; an index depends on neither the mask nor the launch
+ * geometry nor the slicing (at most 8192 pass replicates b D + d per launch of the path kernel).
+ * Status: D < 1, T < p, T <= q, q outside 1..4, a state wider than DFM_MAX_R, B D >= 2^31: DFM_E_DIMS; x_sim or a parameter NULL:
+ * DFM_E_NULL.  flags: none defined, pass 0.
+ * Allocates in the handle (kept for the next call): the roots, Avar padded to m lags, and f+ [B D][rows][r] when f_sim is NULL.
+ * Outputs must not overlap the inputs. */
+int dfm_simulate_batch_dev(dfm_handle* h, int B, int D, int T, int N, int r, int p, const double* mask_panel, const double* Lam,
+                           const double* R, const double* Avar, const double* Q, const double* mu0, const double* P0, uint64_t seed,
+                           int64_t first_draw, double* x_sim, double* f_sim, unsigned flags);
+int dfm_simulate_batch(dfm_handle* h, int B, int D, int T, int N, int r, int p, const double* mask_panel, const double* Lam,
+                       const double* R, const double* Avar, const double* Q, const double* mu0, const double* P0, uint64_t seed,
+                       int64_t first_draw, double* x_sim, double* f_sim, unsigned flags);
+int dfm_simulate_ar_batch_dev(dfm_handle* h, int B, int D, int T, int N, int r, int p, int q, const double* panel, const double* Lam,
+                              const double* sig2, const double* rho, const double* Avar, const double* Q, const double* mu0,
+                              const double* P0, const double* v0, uint64_t seed, int64_t first_draw, double* x_sim, double* f_sim,
+                              unsigned flags);
+int dfm_simulate_ar_batch(dfm_handle* h, int B, int D, int T, int N, int r, int p, int q, const double* panel, const double* Lam,
+                          const double* sig2, const double* rho, const double* Avar, const double* Q, const double* mu0,
+                          const double* P0, const double* v0, uint64_t seed, int64_t first_draw, double* x_sim, double* f_sim,
+                          unsigned flags);
+
 /* Bayesian estimation of the same model: a batched Gibbs sampler (csrc/gibbs_ar.hip), what dfm_gibbs_batch is to dfm_simsmooth_batch,
  * for dfm_simsmooth_ar_batch.  B independent chains; shapes, flags and m = max(p, q + 1) as dfm_ks_pass_ar_batch.  mu0 [B][r m] and
  * P0 [B][r m][r m] are inputs and stay fixed.  The chain state is Lam [B][N][r], sig2 [B][N], rho [B][N][q], Avar [B][r][r p],

@@ -812,6 +812,81 @@ function draw_paths_ar(h::Handle, x::Matrix{Float64}, Lam::Matrix{Float64}, sig2
     return (factor = permutedims(f, (3, 2, 1)), x = permutedims(xd, (3, 2, 1)))
 end
 
+"Panels simulated from a given model (dfm_simulate_batch; include/dfm_hip.h): params, nlag as `forecast`; ndraws panels of T rows,
+draw d the x+ of `draw_paths`' unconditional step for the same (seed, first_draw + d).  `mask` (T x N, or nothing: balanced) is read
+for its NaN pattern only: a cell is NaN where it is.  Returns x (ndraws x T x N) and factor (ndraws x T x r)."
+function simulate(h::Handle, params, ndraws::Integer, T::Integer; nlag::Integer = 1, mask = nothing, seed::Integer = 20160415,
+                  first_draw::Integer = 0)
+    N, r = size(params.Lam)
+    mask === nothing || size(mask) == (T, N) || error("mask must be T x N")
+    Av = hasproperty(params, :Avar) ? params.Avar : params.A
+    maskC = mask === nothing ? C_NULL : to_c_panel(Matrix{Float64}(mask))
+    Lam = permutedims(params.Lam); R = copy(params.R); AC = permutedims(Av); QC = permutedims(params.Q)
+    mu0 = copy(params.mu0); P0C = permutedims(params.P0)
+    f = Array{Float64}(undef, r, T, ndraws); x = Array{Float64}(undef, N, T, ndraws)
+    GC.@preserve maskC Lam R AC QC mu0 P0C f x begin
+        rc = ccall((:dfm_simulate_batch, LIB), Cint,
+                   (Ptr{Cvoid}, Cint, Cint, Cint, Cint, Cint, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                    Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, UInt64, Int64, Ptr{Float64}, Ptr{Float64}, Cuint),
+                   h.ptr, 1, ndraws, T, N, r, nlag, maskC, Lam, R, AC, QC, mu0, P0C, UInt64(seed), Int64(first_draw), x, f, Cuint(0))
+        check(h.ptr, rc)
+    end
+    return (x = permutedims(x, (3, 2, 1)), factor = permutedims(f, (3, 2, 1)))
+end
+
+"The device-pointer twin (dfm_simulate_batch_dev) for arrays that already live on the GPU, row-major as the C interface has them:
+B replicates, D draws each; mask_panel and f_sim may be C_NULL.  Enqueues on the handle's stream and returns; the caller synchronises."
+function simulate_dev!(h::Handle, B::Integer, D::Integer, T::Integer, N::Integer, r::Integer, p::Integer, mask_panel::Ptr{Float64},
+                       Lam::Ptr{Float64}, R::Ptr{Float64}, Avar::Ptr{Float64}, Q::Ptr{Float64}, mu0::Ptr{Float64}, P0::Ptr{Float64},
+                       seed::Integer, first_draw::Integer, x_sim::Ptr{Float64}, f_sim::Ptr{Float64})
+    rc = ccall((:dfm_simulate_batch_dev, LIB), Cint,
+               (Ptr{Cvoid}, Cint, Cint, Cint, Cint, Cint, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, UInt64, Int64, Ptr{Float64}, Ptr{Float64}, Cuint),
+               h.ptr, B, D, T, N, r, p, mask_panel, Lam, R, Avar, Q, mu0, P0, UInt64(seed), Int64(first_draw), x_sim, f_sim, Cuint(0))
+    check(h.ptr, rc)
+    return nothing
+end
+
+"Panels simulated from the model with AR(q) idiosyncratic terms (dfm_simulate_ar_batch; include/dfm_hip.h): parameters as
+forecast_ar.  With a panel `x` (T x N) the draws repeat its first q rows and carry its NaN pattern -- the parametric bootstrap of
+`em_ar`, conditional on what its likelihood conditions on; with x = nothing every cell of the T rows is simulated.  Draw d is the
+x+ of `draw_paths_ar` for the same (seed, first_draw + d).  Returns x (ndraws x T x N) and factor (ndraws x (T-q) x r)."
+function simulate_ar(h::Handle, Lam::Matrix{Float64}, sig2::Vector{Float64}, rho::Matrix{Float64}, Avar::Matrix{Float64},
+                     Q::Matrix{Float64}, mu0::Vector{Float64}, P0::Matrix{Float64}, ndraws::Integer, T::Integer; x = nothing,
+                     v0 = nothing, seed::Integer = 20160415, first_draw::Integer = 0)
+    N, r = size(Lam); q = size(rho, 2); p = div(size(Avar, 2), r); n = T - q
+    x === nothing || size(x) == (T, N) || error("x must be T x N")
+    panel = x === nothing ? C_NULL : to_c_panel(Matrix{Float64}(x))
+    LamC = permutedims(Lam); rhoC = permutedims(rho); AC = permutedims(Avar); QC = permutedims(Q); P0C = permutedims(P0)
+    v0C = v0 === nothing ? C_NULL : Vector{Float64}(v0)
+    f = Array{Float64}(undef, r, n, ndraws); xs = Array{Float64}(undef, N, T, ndraws)
+    GC.@preserve panel LamC sig2 rhoC AC QC mu0 P0C v0C f xs begin
+        rc = ccall((:dfm_simulate_ar_batch, LIB), Cint,
+                   (Ptr{Cvoid}, Cint, Cint, Cint, Cint, Cint, Cint, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                    Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, UInt64, Int64, Ptr{Float64},
+                    Ptr{Float64}, Cuint),
+                   h.ptr, 1, ndraws, T, N, r, p, q, panel, LamC, sig2, rhoC, AC, QC, mu0, P0C, v0C, UInt64(seed), Int64(first_draw),
+                   xs, f, Cuint(0))
+        check(h.ptr, rc)
+    end
+    return (x = permutedims(xs, (3, 2, 1)), factor = permutedims(f, (3, 2, 1)))
+end
+
+"The device-pointer twin (dfm_simulate_ar_batch_dev): as simulate_dev!, with panel, v0 and f_sim allowed to be C_NULL."
+function simulate_ar_dev!(h::Handle, B::Integer, D::Integer, T::Integer, N::Integer, r::Integer, p::Integer, q::Integer,
+                          panel::Ptr{Float64}, Lam::Ptr{Float64}, sig2::Ptr{Float64}, rho::Ptr{Float64}, Avar::Ptr{Float64},
+                          Q::Ptr{Float64}, mu0::Ptr{Float64}, P0::Ptr{Float64}, v0::Ptr{Float64}, seed::Integer,
+                          first_draw::Integer, x_sim::Ptr{Float64}, f_sim::Ptr{Float64})
+    rc = ccall((:dfm_simulate_ar_batch_dev, LIB), Cint,
+               (Ptr{Cvoid}, Cint, Cint, Cint, Cint, Cint, Cint, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, UInt64, Int64, Ptr{Float64}, Ptr{Float64},
+                Cuint),
+               h.ptr, B, D, T, N, r, p, q, panel, Lam, sig2, rho, Avar, Q, mu0, P0, v0, UInt64(seed), Int64(first_draw), x_sim,
+               f_sim, Cuint(0))
+    check(h.ptr, rc)
+    return nothing
+end
+
 "Joint ECM estimation with AR(q) idiosyncratic terms (dfm_em_ar_batch; include/dfm_hip.h): the re-estimation of the
 reference's `lambda`, `uar_coef`, `uar_ser` (dfm_functions.ipynb:391-415) and factor VAR inside the parametric model.
 Arguments as ks_pass_ar (the start: what `estimate!(m)` left in the model).  Returns the updated parameters, the
