@@ -33,7 +33,7 @@ DFM_MULTI_F_FORCE_COMM = 1
  DFM_MULTI_LOGLIK, DFM_MULTI_LOGLIK_PATH, DFM_MULTI_ITERS, DFM_MULTI_PANEL) = range(12)
 ERRORS = {-1: "DFM_E_DIMS", -2: "DFM_E_R_UNSUPPORTED", -3: "DFM_E_NULL", -4: "DFM_E_MISSING",
           -5: "DFM_E_NUMERIC", -6: "DFM_E_NO_DEVICE", -7: "DFM_E_COMM",
-          -8: "DFM_E_VINTAGE"}
+          -8: "DFM_E_VINTAGE", -9: "DFM_E_WINDOW"}
 
 _PASS_ARGS = [c_vp, c_int, c_int, c_int, c_int] + [c_vp] * 10 + [c_uint]
 _EMSTEP_ARGS = [c_vp, c_int, c_int, c_int, c_int] + [c_vp] * 8 + [c_uint]
@@ -59,6 +59,7 @@ _FTAR_ARGS = [c_vp] + [c_int] * 8 + [c_vp] * 22 + [c_uint]
 _SSAR_ARGS = [c_vp] + [c_int] * 8 + [c_vp] * 11 + [ctypes.c_uint64, ctypes.c_int64, c_vp, c_vp, c_uint]
 _SIM_ARGS = [c_vp] + [c_int] * 6 + [c_vp] * 7 + [ctypes.c_uint64, ctypes.c_int64, c_vp, c_vp, c_uint]
 _SIMAR_ARGS = [c_vp] + [c_int] * 7 + [c_vp] * 9 + [ctypes.c_uint64, ctypes.c_int64, c_vp, c_vp, c_uint]
+_RW_ARGS = ([c_vp] + [c_int] * 9 + [c_vp] * 10 + [c_int, ctypes.c_double] + [c_vp] * 19 + [c_uint])
 _ARPASS_ARGS = [c_vp, c_int, c_int, c_int, c_int, c_int, c_int] + [c_vp] * 11 + [c_uint]
 _AREM_ARGS = [c_vp, c_int, c_int, c_int, c_int, c_int, c_int] + [c_vp] * 8 + [c_int, ctypes.c_double] + [c_vp] * 4 + [c_uint]
 _MFPASS_ARGS = [c_vp, c_int, c_int, c_int, c_int, c_int, c_int] + [c_vp] * 11 + [c_uint]
@@ -142,6 +143,8 @@ SYMBOLS = {
     "dfm_simulate_batch": (c_int, _SIM_ARGS),
     "dfm_simulate_ar_batch_dev": (c_int, _SIMAR_ARGS),
     "dfm_simulate_ar_batch": (c_int, _SIMAR_ARGS),
+    "dfm_rolling_eval_batch_dev": (c_int, _RW_ARGS),
+    "dfm_rolling_eval_batch": (c_int, _RW_ARGS),
     "dfm_gibbs_ar_batch_dev": (c_int, _GBAR_ARGS),
     "dfm_gibbs_ar_batch": (c_int, _GBAR_ARGS),
     "dfm_news_ar_batch_dev": (c_int, _NWAR_ARGS),

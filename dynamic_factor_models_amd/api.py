@@ -676,6 +676,96 @@ def evaluate_forecasts(m: DFMModel, H: int, *, first_origin: Optional[int] = Non
     return out
 
 
+def evaluate_forecasts_rolling(m: DFMModel, H: int, window: int, *, origins=None, step: int = 1, lags=None, start=None,
+                               max_em_iter: int = 50, tol_em: float = 1e-6, factor_lags: Optional[int] = None, ctx=None) -> dict:
+    """The rolling-window out-of-sample record, RE-ESTIMATED at every origin: what the model forecast when it only knew what was
+    known then.  Rows are initperiod..lastperiod of m.data in data units, the series those `estimate()` used.  At origin t (a 1-based
+    period) the vintage is the `window` rows ending at t, with series i known through t - lags[i] only (`lags`: publication lags per
+    column of m.data, default 0); it is standardised on its own visible cells, the EM runs on it from `start` for at most max_em_iter
+    iterations (tol_em as `estimate`; 0 iterations: the start's parameters on per-window standardisation), and the panel is forecast
+    h = 0..H rows past t (h = 0: the nowcast of the series not yet published).  One dfm_rolling_eval_batch call on the GPU: the
+    windows are the batch of the EM.  origins: increasing periods in initperiod + window - 1 .. lastperiod (default every `step`-th).
+    start: a dict with Lam, R, A or Avar, Q, mu0, P0 in standardised units, one set or one per origin (a leading axis), the loadings'
+    rows the series estimate() used or those of its own "cols" (column indices of m.data; the `params` and `cols` this function
+    returns make such a start), and optionally "sd": the s.d. of the sample those units belong to (absent: the windows' own units).
+    The default is m.em_params with the estimation window's s.d. -- LOOK-AHEAD IN THE START VALUES ONLY (the data of every window
+    are its own); pass the parameters of a fit on an earlier sample to avoid it.  factor_lags: p of the factor VAR, default the
+    start's.  A series with fewer than max(m.nt_min_factor_estimation, r + 1) visible cells in any window is dropped beforehand.
+    Returns a dict (data units):
+      origins    the 1-based periods, horizons 0 .. H, cols the column indices (0-based) of m.data that were used
+      forecast, variance   [origins, H+1, cols] mean and variance of the cell at origin + h given the vintage
+      error, error_std     [origins, H+1, cols] x - forecast and the same over its s.d.; NaN unless the target lies in the sample, is
+                           observed and was not visible in the vintage
+      msfe, rmsfe, relative, count   [H+1, cols] over the scored origins; relative = msfe over that of the vintage's own mean
+      params, iters, loglik_path     the windows' parameters (a dict, [origins, ..]), EM iterations and log-likelihood paths
+      mean, sd   [origins, cols] of each vintage's visible cells
+    `m` is not modified."""
+    H, W, step = int(H), int(window), int(step)
+    if H < 0:
+        raise ValueError("H must be >= 0")
+    if start is None and m.em_params is None:
+        raise ValueError("the model has not been estimated: run estimate(m, Parametric()) first, or pass start")
+    if m.nfac_o != 0:
+        raise ValueError("the rolling evaluation needs nfac_o = 0")
+    rows = m.lastperiod - m.initperiod + 1
+    if not (2 <= W <= rows):
+        raise ValueError(f"window must lie in 2..{rows} (the rows initperiod..lastperiod)")
+    if step < 1:
+        raise ValueError("step must be >= 1")
+    first = m.initperiod + W - 1
+    org = np.arange(first, m.lastperiod + 1, step) if origins is None else np.asarray(origins, dtype=np.int64).reshape(-1)
+    if org.size < 1 or org.min() < first or org.max() > m.lastperiod or np.any(np.diff(org) <= 0):
+        raise ValueError(f"origins must increase and lie in the first full window's end..lastperiod ({first}..{m.lastperiod})")
+    cols, _, _, sd_full = _forecast_inputs(m, m.lastperiod)
+    sp = dict(m.em_params, sd=sd_full) if start is None else dict(start)
+    if sp.get("cols") is not None:                                      # the start's own series: a subset of those estimate() used
+        scols = np.asarray(sp["cols"], dtype=np.int64).reshape(-1)
+        if not np.all(np.isin(scols, cols)) or np.unique(scols).size != scols.size:
+            raise ValueError("start['cols'] must be distinct series among those estimate() used")
+        cols = scols
+    Lam = np.asarray(sp["Lam"], dtype=np.float64)
+    A = np.asarray(sp["Avar"] if "Avar" in sp else sp["A"], dtype=np.float64)
+    one = Lam.ndim == 2                                                 # one start (no leading axis), or one per origin
+    lead = (lambda a: np.asarray(a, dtype=np.float64)[None]) if one else (lambda a: np.asarray(a, dtype=np.float64))
+    Lam, R, A, Q, mu0, P0 = (lead(a) for a in (Lam, sp["R"], A, sp["Q"], sp["mu0"], sp["P0"]))
+    r = Lam.shape[2]
+    p = A.shape[2] // r
+    if factor_lags is not None and int(factor_lags) != p:
+        raise ValueError(f"factor_lags = {int(factor_lags)} but the start has {p} lag(s)")
+    if Lam.shape[1] != cols.size or Lam.shape[0] not in (1, org.size):
+        raise ValueError("the start does not match the model's series, or has neither one set nor one per origin")
+    if W < p:
+        raise ValueError("window must be >= factor_lags")
+    lg = np.zeros(m.ns, dtype=np.int64) if lags is None else np.asarray(lags, dtype=np.int64).reshape(-1)
+    if lg.size != m.ns or np.any(lg < 0):
+        raise ValueError(f"lags must hold one integer >= 0 per column of m.data ({m.ns})")
+    lg = lg[cols]
+    min_obs = max(int(m.nt_min_factor_estimation), r + 1)
+    if np.any(lg > W - min_obs):
+        raise ValueError(f"a publication lag beyond window - {min_obs} leaves a series too few rows")
+    x = np.ascontiguousarray(m.data[m.initperiod - 1:m.lastperiod, :][:, cols], dtype=np.float64)
+    o0 = org - m.initperiod                                             # 0-based rows of x
+    cs = np.vstack([np.zeros((1, cols.size), dtype=np.int64), np.cumsum(~np.isnan(x), axis=0)])
+    vis = cs[o0[:, None] - lg[None, :] + 1, np.arange(cols.size)[None, :]] - cs[o0 - W + 1]      # [origins, cols] visible cells
+    keep = (vis >= min_obs).all(axis=0)
+    if keep.sum() < r:
+        raise ValueError("fewer series with enough visible cells in every window than factors")
+    sd_start = None if sp.get("sd") is None else np.ascontiguousarray(np.asarray(sp["sd"], dtype=np.float64).reshape(-1)[keep])
+    x, lg, cols = np.ascontiguousarray(x[:, keep]), lg[keep], cols[keep]
+    args = (x, o0, W, H, np.ascontiguousarray(Lam[:, keep]), np.ascontiguousarray(R[:, keep]), A, Q, mu0, P0)
+    kw = dict(lags=lg, sd_start=sd_start, min_obs=min_obs, max_iter=int(max_em_iter), tol=float(tol_em))
+    ctx, own = _own(ctx)
+    try:
+        o = _numeric_retry(lambda sq: ctx.rolling_eval_batch_host(*args, singular_q=sq, **kw))
+    finally:
+        if own:
+            ctx.close()
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return dict(origins=org, horizons=np.arange(H + 1), cols=cols, forecast=o["fc"], variance=o["fvar"], error=o["err"],
+                    error_std=o["err_std"], msfe=o["msfe"], rmsfe=np.sqrt(o["msfe"]), relative=o["msfe"] / o["msfe0"], count=o["cnt"],
+                    params=o["params"], iters=o["iters"], loglik_path=o["loglik_path"], mean=o["mean"], sd=o["sd"])
+
+
 # ----------------------------------------------------------------------------- structural analysis of the parametric fit
 def _structural_checks(m: DFMModel):
     if m.em_params is None:

@@ -176,6 +176,8 @@ struct dfm_handle {
                                            // caller does not take and the evaluation's running sums
     DevBlock gb;                           // dfm_gibbs_batch_dev: the sweep's factor path and the shared Gram roots of balanced panels
                                            // dfm_gibbs_ar_batch_dev: the sweep's [B][T - q][r] factor path
+    DevBlock rw;                           // dfm_rolling_eval_batch_dev: origins, lags, the running sums [H + 1][N], then one slice's windows,
+                                           // xhat, xvar, factor rows and logliks, and the slice's part of every output the caller does not take
     std::vector<int> sv_idx;               // host copy of named / cum while their upload is in flight
     std::vector<double> sv_z;              // dfm_proxyirf_batch_dev: host copy of the instrument while its upload is in flight
     const double* odd_panel_src = nullptr; int odd_panel_dims[3] = {0, 0, 0};   // the panel whose padded copy h->odd holds (odd_pad keep_panel)
@@ -189,11 +191,11 @@ struct dfm_handle {
 };
 
 enum KernelId { K_COLLAPSE = 0, K_RECURSION, K_MSTEP_STATS, K_MSTEP_SOLVE, K_PCA, K_SYNTH, K_PAD,
-                K_COLLAPSE_DMA, K_GRAM, K_COV, K_MEANSCAN, K_PFILL, K_COLLAPSE_MFMA, K_ALS, K_OLS, K_BOOT, K_QUANT, K_COLLAPSE_WIDE, K_EM_UPDATE, K_CHOW, K_MSTEP_MFMA, K_GRAM_XX, K_PASS_FUSED, K_FC_TAIL, K_FC_FILL, K_FC_PAD, K_SS_PREP, K_SS_EXPAND, K_SS_PATH, K_SS_DIFF, K_SS_FINISH, K_SS_FILL, K_NW_REVISE, K_NW_GATHER, K_NW_GAMMA, K_NW_COV, K_NW_IMPACT, K_MF_TABLE, K_MF_MOMENTS, K_MF_SOLVE, K_SV_PREP, K_SV_IRF_FILL, K_SV_SHOCK, K_SV_PATH, K_SV_HD_FILL, K_FT_FILTER, K_FT_FILL, K_FT_EVAL, K_GB_GRAM, K_GB_LOAD, K_GB_VAR, K_SV_SIGN_TABLE, K_SV_SIGN, K_SV_SIGN_KEEP, K_PX_ROWS, K_PX_MOMENT, K_PX_SLOT_TABLE, K_PX_DEN, K_PX_FILL, K_PX_SHOCK, K_MF_SOLVE_BLOCKS, K_FCAR_BACK, K_FCAR_FWD, K_SSAR_PARAMS, K_SSAR_EXPAND, K_SSAR_DIFF, K_SSAR_FWD, K_SSAR_FINISH, K_GB_AR_SERIES, K_FTAR_FILTER, K_FTAR_FILL, K_FTAR_EVAL, K_NWAR_REVISE, K_NWAR_REC, K_NWAR_QC, K_NWAR_IMPACT, K_SIM_CELLS, K_SIMAR_CELLS, K_COUNT };
+                K_COLLAPSE_DMA, K_GRAM, K_COV, K_MEANSCAN, K_PFILL, K_COLLAPSE_MFMA, K_ALS, K_OLS, K_BOOT, K_QUANT, K_COLLAPSE_WIDE, K_EM_UPDATE, K_CHOW, K_MSTEP_MFMA, K_GRAM_XX, K_PASS_FUSED, K_FC_TAIL, K_FC_FILL, K_FC_PAD, K_SS_PREP, K_SS_EXPAND, K_SS_PATH, K_SS_DIFF, K_SS_FINISH, K_SS_FILL, K_NW_REVISE, K_NW_GATHER, K_NW_GAMMA, K_NW_COV, K_NW_IMPACT, K_MF_TABLE, K_MF_MOMENTS, K_MF_SOLVE, K_SV_PREP, K_SV_IRF_FILL, K_SV_SHOCK, K_SV_PATH, K_SV_HD_FILL, K_FT_FILTER, K_FT_FILL, K_FT_EVAL, K_GB_GRAM, K_GB_LOAD, K_GB_VAR, K_SV_SIGN_TABLE, K_SV_SIGN, K_SV_SIGN_KEEP, K_PX_ROWS, K_PX_MOMENT, K_PX_SLOT_TABLE, K_PX_DEN, K_PX_FILL, K_PX_SHOCK, K_MF_SOLVE_BLOCKS, K_FCAR_BACK, K_FCAR_FWD, K_SSAR_PARAMS, K_SSAR_EXPAND, K_SSAR_DIFF, K_SSAR_FWD, K_SSAR_FINISH, K_GB_AR_SERIES, K_FTAR_FILTER, K_FTAR_FILL, K_FTAR_EVAL, K_NWAR_REVISE, K_NWAR_REC, K_NWAR_QC, K_NWAR_IMPACT, K_SIM_CELLS, K_SIMAR_CELLS, K_RW_WINDOW, K_RW_START, K_RW_SCORE, K_COUNT };
 static const char* const kKernelNames[K_COUNT] = {"collapse_kernel", "recursion_kernel", "mstep_lam_kernel",
                                                   "mstep_solve_kernel", "pca_kernel", "synth_kernel",
                                                   "pad_params_kernel", "collapse_dma_kernel", "gram_kernel",
-                                                  "cov_kernel", "meanscan_kernel", "pfill_kernel", "collapse_mfma_kernel", "als_kernel", "ols_kernel", "var_boot_kernel", "quantile_kernel", "collapse_wide_kernel", "em_update_kernel", "chow_kernel", "mstep_mfma_kernel", "gram_xx_kernel", "pass_fused_kernel", "forecast_tail_kernel", "forecast_fill_kernel", "forecast_pad_kernel", "simsmooth_prep_kernel", "simsmooth_expand_kernel", "simsmooth_path_kernel", "simsmooth_diff_kernel", "simsmooth_finish_kernel", "simsmooth_fill_kernel", "news_revise_kernel", "news_gather_kernel", "news_gamma_kernel", "news_cov_panel_kernel", "news_impact_kernel", "mf_table_kernel", "mf_moments_kernel", "mf_solve_kernel", "sv_prep_kernel", "sv_irf_fill_kernel", "sv_shock_kernel", "sv_path_kernel", "sv_hd_fill_kernel", "filter_kernel", "filter_fill_kernel", "filter_eval_kernel", "gibbs_gram_kernel", "gibbs_load_kernel", "gibbs_var_kernel", "sv_sign_table_kernel", "sv_sign_kernel", "sv_sign_keep_kernel", "px_rows_kernel", "px_moment_kernel", "px_slot_table_kernel", "px_den_kernel", "px_fill_kernel", "px_shock_kernel", "mf_solve_blocks_kernel", "forecast_ar_back_kernel", "forecast_ar_fwd_kernel", "simsmooth_ar_params_kernel", "simsmooth_ar_expand_kernel", "simsmooth_ar_diff_kernel", "simsmooth_ar_fwd_kernel", "simsmooth_ar_finish_kernel", "gibbs_ar_series_kernel", "filter_ar_kernel", "filter_ar_fill_kernel", "filter_ar_eval_kernel", "news_ar_revise_kernel", "news_ar_rec_kernel", "news_ar_qc_kernel", "news_ar_impact_kernel", "simulate_cells_kernel", "simulate_ar_cells_kernel"};
+                                                  "cov_kernel", "meanscan_kernel", "pfill_kernel", "collapse_mfma_kernel", "als_kernel", "ols_kernel", "var_boot_kernel", "quantile_kernel", "collapse_wide_kernel", "em_update_kernel", "chow_kernel", "mstep_mfma_kernel", "gram_xx_kernel", "pass_fused_kernel", "forecast_tail_kernel", "forecast_fill_kernel", "forecast_pad_kernel", "simsmooth_prep_kernel", "simsmooth_expand_kernel", "simsmooth_path_kernel", "simsmooth_diff_kernel", "simsmooth_finish_kernel", "simsmooth_fill_kernel", "news_revise_kernel", "news_gather_kernel", "news_gamma_kernel", "news_cov_panel_kernel", "news_impact_kernel", "mf_table_kernel", "mf_moments_kernel", "mf_solve_kernel", "sv_prep_kernel", "sv_irf_fill_kernel", "sv_shock_kernel", "sv_path_kernel", "sv_hd_fill_kernel", "filter_kernel", "filter_fill_kernel", "filter_eval_kernel", "gibbs_gram_kernel", "gibbs_load_kernel", "gibbs_var_kernel", "sv_sign_table_kernel", "sv_sign_kernel", "sv_sign_keep_kernel", "px_rows_kernel", "px_moment_kernel", "px_slot_table_kernel", "px_den_kernel", "px_fill_kernel", "px_shock_kernel", "mf_solve_blocks_kernel", "forecast_ar_back_kernel", "forecast_ar_fwd_kernel", "simsmooth_ar_params_kernel", "simsmooth_ar_expand_kernel", "simsmooth_ar_diff_kernel", "simsmooth_ar_fwd_kernel", "simsmooth_ar_finish_kernel", "gibbs_ar_series_kernel", "filter_ar_kernel", "filter_ar_fill_kernel", "filter_ar_eval_kernel", "news_ar_revise_kernel", "news_ar_rec_kernel", "news_ar_qc_kernel", "news_ar_impact_kernel", "simulate_cells_kernel", "simulate_ar_cells_kernel", "rolling_window_kernel", "rolling_start_kernel", "rolling_score_kernel"};
 
 namespace dfm { int handle_device(const dfm_handle* h) { return h->device; } }   // (probe.hip)
 
@@ -1714,7 +1716,7 @@ int dfm_destroy(dfm_handle* h) {
     for (auto e : h->ev_sub) hipEventDestroy(e);
     if (h->ev_fork) hipEventDestroy(h->ev_fork);
     if (h->ev_join) hipEventDestroy(h->ev_join);
-    for (DevBlock* b : {&h->ws, &h->odd, &h->fc, &h->ss, &h->nw, &h->sv, &h->ft, &h->gb}) b->release();
+    for (DevBlock* b : {&h->ws, &h->odd, &h->fc, &h->ss, &h->nw, &h->sv, &h->ft, &h->gb, &h->rw}) b->release();
     if (h->status_dev) hipFree(h->status_dev);
     if (h->own_stream && h->stream) hipStreamDestroy(h->stream);
     delete h;
@@ -1873,7 +1875,8 @@ int dfm_ks_pass_batch_dev(dfm_handle* h, int B, int T, int N, int r, const doubl
 // declared balanced, 2 = the PCA start's subspace iteration did not converge, 4 = a bounded wait between the waves of the
 // one-launch pass ran out (its outputs are invalid even where the log-likelihood happens to be finite), 8 = dfm_news_batch: a cell
 // of the old vintage is observed where the new one is missing, 16 = dfm_irf_batch / dfm_histdecomp_batch: a zero pivot in
-// Lam[named, :] or (decomposition, dfm_proxyirf_batch) in the root of Q, 32 = dfm_filter_batch: a replicate's update failed.  Every synchronising
+// Lam[named, :] or (decomposition, dfm_proxyirf_batch) in the root of Q, 32 = dfm_filter_batch: a replicate's update failed, 128 (kRwWindowBit) =
+// dfm_rolling_eval_batch: a thin or constant series in a window.  Every synchronising
 // entry point goes through here; device-pointer callers get the same check from dfm_synchronize / dfm_check_status.
 static int status_check(dfm_handle* h) {
     if (!h->status_dev) return 0;
@@ -1881,6 +1884,7 @@ static int status_check(dfm_handle* h) {
     HIP_TRY(h, hipMemcpy(&st, h->status_dev, sizeof(int), hipMemcpyDeviceToHost));
     if (st) HIP_TRY(h, hipMemset(h->status_dev, 0, sizeof(int)));      // reported once
     if (st & 4) return fail(h, DFM_E_NUMERIC, "one-launch pass: a bounded wait between its waves ran out (results invalid)%s");
+    if (st & kRwWindowBit) return fail(h, DFM_E_WINDOW, "rolling evaluation: a series of a window has fewer than min_obs visible cells, or they are all equal%s");
     if (st & 8) return fail(h, DFM_E_VINTAGE, "news: a cell observed in the old vintage is missing in the new one%s");
     if (st & 1) return fail(h, DFM_E_MISSING, "panel contains NaN but DFM_F_MAY_HAVE_MISSING was not set%s");
     if (st & 16) return fail(h, DFM_E_NUMERIC, "structural identification: Lam[named, :] is singular, or Q is not positive definite where S^-1 is needed%s");
@@ -2953,6 +2957,170 @@ int dfm_simulate_ar_batch(dfm_handle* h, int B, int D, int T, int N, int r, int 
     if (h && q < 1) return fail(h, DFM_E_DIMS, "number of idiosyncratic lags must be 1 .. 4%s");
     if (int rc = simulate_check(h, B, D, T, N, r, p, q, Lam, sig2, rho, Avar, Q, mu0, P0, x_sim)) return rc;
     return simulate_host(h, B, D, T, N, r, p, q, panel, Lam, sig2, rho, Avar, Q, mu0, P0, v0, seed, first_draw, x_sim, f_sim);
+}
+
+// ---- rolling-window out-of-sample evaluation, re-estimated at every origin (rolling.hip) ---------------------------------------
+// Per slice of at most kRwSlice windows: rolling_window_kernel (the standardised vintages and their statistics), the status word's
+// window bit (read here: no EM on a thin or constant series), rolling_start_kernel, the EM entry of the plain or the VAR(p) model in
+// place in the windows' parameters, dfm_forecast_batch_dev on the windows, rolling_score_kernel.  The slice's arrays live in h->rw
+// (beside h->ws and h->fc, which the entries it calls size for themselves); what the caller takes is written at its slice offset.
+constexpr int kRwSlice = 1024;
+
+static int rolling_check(dfm_handle* h, int T, int N, int r, int p, int W, int H, int O, int min_obs, int n_start, const double* x,
+                         const int* origins, const int* lags, const double* Lam_start, const double* R_start, const double* Avar_start,
+                         const double* Q_start, const double* mu0_start, const double* P0_start, int max_iter, const double* Lam,
+                         const double* R, const double* Avar, const double* Q, const double* mu0, const double* P0, unsigned flags) {
+    if (!h) return DFM_E_NULL;
+    if (T < 1 || N < 1 || r < 1 || p < 1 || O < 1) return fail(h, DFM_E_DIMS, "T, N, r, p, O must be >= 1%s");
+    if ((long long)r * p > DFM_MAX_R) return fail(h, DFM_E_DIMS, "r * p > DFM_MAX_R (32)%s");
+    if (W > T || W < 2 || W < p) return fail(h, DFM_E_DIMS, "need max(2, p) <= W <= T%s");
+    if (H < 0) return fail(h, DFM_E_DIMS, "H must be >= 0%s");
+    if (max_iter < 0) return fail(h, DFM_E_DIMS, "max_iter must be >= 0%s");
+    if (min_obs < r + 1) return fail(h, DFM_E_DIMS, "min_obs must be >= r + 1%s");
+    if (n_start != 1 && n_start != O) return fail(h, DFM_E_DIMS, "n_start must be 1 or O%s");
+    if (!x || !origins || !Lam_start || !R_start || !Avar_start || !Q_start || !mu0_start || !P0_start)
+        return fail(h, DFM_E_NULL, "required pointer is NULL%s");
+    if (max_iter > 0 && (!Lam || !R || !Avar || !Q || !mu0 || !P0))
+        return fail(h, DFM_E_NULL, "the windows' parameter arrays are required when max_iter > 0%s");
+    for (int b = 0; b < O; ++b)
+        if (origins[b] < W - 1 || origins[b] > T - 1 || (b && origins[b] <= origins[b - 1]))
+            return fail(h, DFM_E_DIMS, "origins must increase and lie in W - 1 .. T - 1%s");
+    bool lagged = false;
+    for (int i = 0; lags && i < N; ++i) {
+        if (lags[i] < 0 || lags[i] > W - min_obs) return fail(h, DFM_E_DIMS, "publication lags must lie in 0 .. W - min_obs%s");
+        lagged = lagged || lags[i] > 0;
+    }
+    if (lagged && !(flags & DFM_F_MAY_HAVE_MISSING))
+        return fail(h, DFM_E_MISSING, "publication lags leave NaN in the windows: DFM_F_MAY_HAVE_MISSING is needed%s");
+    return 0;
+}
+
+static int rolling_run(dfm_handle* h, int T, int N, int r, int p, int W, int H, int O, int min_obs, int n_start, const double* x,
+                       const int* origins, const int* lags, const double* Lam_start, const double* R_start, const double* Avar_start,
+                       const double* Q_start, const double* mu0_start, const double* P0_start, const double* sd_start, int max_iter,
+                       double tol, double* Lam, double* R, double* Avar, double* Q, double* mu0, double* P0, double* loglik_path,
+                       int* iters, double* win_mean, double* win_sd, int* win_nobs, double* windows, double* fc, double* fvar, double* err,
+                       double* err_std, double* msfe, double* msfe0, int* cnt, unsigned flags) {
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t d = sizeof(double), k = (size_t)r * p, H1 = (size_t)H + 1, TH = (size_t)W + H;
+    const size_t Smax = O < kRwSlice ? O : kRwSlice, SN = Smax * N;
+    size_t off = 0;
+    // an output the caller does not take has the slice's part here; (size_t)-1: the caller's array, at its slice offset
+    auto own = [&](const void* callers, size_t bytes) { return callers ? (size_t)-1 : take(off, bytes); };
+    const size_t o_org = take(off, (size_t)O * sizeof(int)), o_lag = lags ? take(off, (size_t)N * sizeof(int)) : (size_t)-1,
+                 o_sse = take(off, H1 * N * d), o_sse0 = take(off, H1 * N * d), o_cnt = take(off, H1 * N * sizeof(int)),
+                 o_win = own(windows, Smax * W * N * d), o_xh = take(off, Smax * TH * N * d), o_xv = take(off, Smax * TH * N * d),
+                 o_f = take(off, Smax * TH * r * d), o_ll = take(off, Smax * d),
+                 o_L = own(Lam, SN * r * d), o_R = own(R, SN * d), o_A = own(Avar, Smax * r * k * d), o_Q = own(Q, Smax * r * r * d),
+                 o_m = own(mu0, Smax * k * d), o_P = own(P0, Smax * k * k * d),
+                 o_path = max_iter ? own(loglik_path, Smax * max_iter * d) : (size_t)-1, o_it = own(iters, Smax * sizeof(int)),
+                 o_mean = own(win_mean, SN * d), o_sd = own(win_sd, SN * d), o_nobs = own(win_nobs, SN * sizeof(int));
+    HIP_TRY(h, h->rw.grow(off));
+    int* org_d = at<int>(h->rw, o_org);
+    HIP_TRY(h, hipMemcpyAsync(org_d, origins, (size_t)O * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    if (lags) HIP_TRY(h, hipMemcpyAsync(at<int>(h->rw, o_lag), lags, (size_t)N * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    RwArgs a{};
+    a.T = T; a.N = N; a.W = W; a.H = H; a.r = r; a.k = (int)k; a.min_obs = min_obs;
+    a.x = x; a.origins = org_d; a.lags = at<int>(h->rw, o_lag); a.status = h->status_dev;
+    a.n_start = n_start; a.sLam = Lam_start; a.sR = R_start; a.sA = Avar_start; a.sQ = Q_start; a.smu0 = mu0_start; a.sP0 = P0_start;
+    a.sd_start = sd_start;
+    a.xhat = at<double>(h->rw, o_xh); a.xvar = at<double>(h->rw, o_xv);
+    a.sse = at<double>(h->rw, o_sse); a.sse0 = at<double>(h->rw, o_sse0); a.cnt = at<int>(h->rw, o_cnt);
+    a.msfe = msfe; a.msfe0 = msfe0; a.cnt_out = cnt;
+    double *xhat = at<double>(h->rw, o_xh), *xvar = at<double>(h->rw, o_xv), *fbuf = at<double>(h->rw, o_f), *llbuf = at<double>(h->rw, o_ll);
+    for (int b0 = 0; b0 < O; b0 += kRwSlice) {
+        const int S = O - b0 < kRwSlice ? O - b0 : kRwSlice;
+        // the slice's part of an [O][per] array: the caller's, or the block's
+        auto part = [&](auto* callers, size_t o_own, size_t per) { return callers ? callers + (size_t)b0 * per : at<std::remove_pointer_t<decltype(callers)>>(h->rw, o_own); };
+        a.b0 = b0; a.S = S; a.first = b0 == 0; a.last = b0 + S == O;
+        a.win = part(windows, o_win, (size_t)W * N); a.mean = part(win_mean, o_mean, N); a.sd = part(win_sd, o_sd, N); a.nobs = part(win_nobs, o_nobs, N);
+        a.Lam = part(Lam, o_L, (size_t)N * r); a.R = part(R, o_R, N); a.A = part(Avar, o_A, r * k); a.Q = part(Q, o_Q, (size_t)r * r);
+        a.mu0 = part(mu0, o_m, k); a.P0 = part(P0, o_P, k * k);
+        a.fc = fc ? fc + (size_t)b0 * H1 * N : nullptr; a.fvar = fvar ? fvar + (size_t)b0 * H1 * N : nullptr;
+        a.err = err ? err + (size_t)b0 * H1 * N : nullptr; a.err_std = err_std ? err_std + (size_t)b0 * H1 * N : nullptr;
+        int* it = part(iters, o_it, 1);
+        HIP_LAUNCH(h, K_RW_WINDOW, launch_rolling_window(a, h->stream));
+        int st = 0;                                            // a thin or constant series: stop before the EM meets its window
+        HIP_TRY(h, hipMemcpyAsync(&st, h->status_dev, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        if (st & kRwWindowBit) return status_check(h);
+        HIP_LAUNCH(h, K_RW_START, launch_rolling_start(a, h->stream));
+        if (max_iter > 0) {
+            double* path = part(loglik_path, o_path, (size_t)max_iter);
+            if (int rc = p == 1 ? dfm_em_batch_dev(h, S, W, N, r, a.win, a.Lam, a.R, a.A, a.Q, a.mu0, a.P0, max_iter, tol, path, it, nullptr,
+                                                   nullptr, flags)
+                                : dfm_em_varp_batch_dev(h, S, W, N, r, p, a.win, a.Lam, a.R, a.A, a.Q, a.mu0, a.P0, max_iter, tol, path, it,
+                                                        nullptr, nullptr, flags)) return rc;
+        } else {
+            HIP_TRY(h, hipMemsetAsync(it, 0, (size_t)S * sizeof(int), h->stream));
+        }
+        if (int rc = dfm_forecast_batch_dev(h, S, W, N, r, p, H, a.win, a.Lam, a.R, a.A, a.Q, a.mu0, a.P0, a.mean, a.sd, xhat, xvar, nullptr,
+                                            fbuf, nullptr, llbuf, flags)) return rc;
+        HIP_LAUNCH(h, K_RW_SCORE, launch_rolling_score(a, h->stream));
+    }
+    return 0;
+}
+
+static int rolling_host(dfm_handle* h, int T, int N, int r, int p, int W, int H, int O, int min_obs, int n_start, const double* x,
+                        const int* origins, const int* lags, const double* Lam_start, const double* R_start, const double* Avar_start,
+                        const double* Q_start, const double* mu0_start, const double* P0_start, const double* sd_start, int max_iter,
+                        double tol, double* Lam, double* R, double* Avar, double* Q, double* mu0, double* P0, double* loglik_path,
+                        int* iters, double* win_mean, double* win_sd, int* win_nobs, double* windows, double* fc, double* fvar, double* err,
+                        double* err_std, double* msfe, double* msfe0, int* cnt, unsigned flags) {
+    if (int rc = status_epoch(h)) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t k = (size_t)r * p, nO = (size_t)O, ON = nO * N, n_fc = nO * (H + 1) * N, n_ms = (size_t)(H + 1) * N;
+    HostStage st(h, 256);
+    ModelDev sm, wm;
+    double *x_d, *sds_d, *path_d, *win_d, *fc_d, *fv_d, *er_d, *es_d, *ms_d, *m0_d;
+    int *it_d, *nobs_d, *cnt_d;
+    st.in(x, (size_t)T * N, x_d);
+    stage_model(st, sm, n_start, N, r, p, 0, Lam_start, R_start, nullptr, Avar_start, Q_start, mu0_start, P0_start, nullptr, nullptr, nullptr);
+    st.in(sd_start, sd_start ? (size_t)N : 0, sds_d);
+    // the windows' parameters and statistics: outputs only, each taking room only where the caller takes it
+    wm = ModelDev{};
+    st.out(Lam, Lam ? ON * r : 0, wm.Lam); st.out(R, R ? ON : 0, wm.R); st.out(Avar, Avar ? nO * r * k : 0, wm.A);
+    st.out(Q, Q ? nO * r * r : 0, wm.Q); st.out(mu0, mu0 ? nO * k : 0, wm.mu0); st.out(P0, P0 ? nO * k * k : 0, wm.P0);
+    st.out(loglik_path, loglik_path ? nO * max_iter : 0, path_d); st.out(iters, iters ? nO : 0, it_d);
+    st.out(win_mean, win_mean ? ON : 0, wm.mean); st.out(win_sd, win_sd ? ON : 0, wm.sd); st.out(win_nobs, win_nobs ? ON : 0, nobs_d);
+    st.out(windows, windows ? ON * W : 0, win_d);
+    st.out(fc, fc ? n_fc : 0, fc_d); st.out(fvar, fvar ? n_fc : 0, fv_d); st.out(err, err ? n_fc : 0, er_d);
+    st.out(err_std, err_std ? n_fc : 0, es_d); st.out(msfe, msfe ? n_ms : 0, ms_d); st.out(msfe0, msfe0 ? n_ms : 0, m0_d);
+    st.out(cnt, cnt ? n_ms : 0, cnt_d);
+    if (int rc = st.begin()) return rc;
+    int rc = st.finish(rolling_run(h, T, N, r, p, W, H, O, min_obs, n_start, x_d, origins, lags, sm.Lam, sm.R, sm.A, sm.Q, sm.mu0, sm.P0, sds_d,
+                                   max_iter, tol, wm.Lam, wm.R, wm.A, wm.Q, wm.mu0, wm.P0, path_d, it_d, wm.mean, wm.sd, nobs_d, win_d, fc_d, fv_d,
+                                   er_d, es_d, ms_d, m0_d, cnt_d, flags));
+    if (rc == 0) rc = status_check(h);
+    return rc;
+}
+
+int dfm_rolling_eval_batch_dev(dfm_handle* h, int T, int N, int r, int p, int W, int H, int O, int min_obs, int n_start,
+                               const double* x, const int* origins, const int* lags, const double* Lam_start,
+                               const double* R_start, const double* Avar_start, const double* Q_start, const double* mu0_start,
+                               const double* P0_start, const double* sd_start, int max_iter, double tol, double* Lam, double* R,
+                               double* Avar, double* Q, double* mu0, double* P0, double* loglik_path, int* iters,
+                               double* win_mean, double* win_sd, int* win_nobs, double* windows, double* fc, double* fvar, double* err,
+                               double* err_std, double* msfe, double* msfe0, int* cnt, unsigned flags) {
+    if (int rc = rolling_check(h, T, N, r, p, W, H, O, min_obs, n_start, x, origins, lags, Lam_start, R_start, Avar_start, Q_start, mu0_start,
+                               P0_start, max_iter, Lam, R, Avar, Q, mu0, P0, flags)) return rc;
+    return rolling_run(h, T, N, r, p, W, H, O, min_obs, n_start, x, origins, lags, Lam_start, R_start, Avar_start, Q_start, mu0_start, P0_start,
+                       sd_start, max_iter, tol, Lam, R, Avar, Q, mu0, P0, loglik_path, iters, win_mean, win_sd, win_nobs, windows, fc, fvar, err,
+                       err_std, msfe, msfe0, cnt, flags);
+}
+
+int dfm_rolling_eval_batch(dfm_handle* h, int T, int N, int r, int p, int W, int H, int O, int min_obs, int n_start,
+                           const double* x, const int* origins, const int* lags, const double* Lam_start,
+                           const double* R_start, const double* Avar_start, const double* Q_start, const double* mu0_start,
+                           const double* P0_start, const double* sd_start, int max_iter, double tol, double* Lam, double* R,
+                           double* Avar, double* Q, double* mu0, double* P0, double* loglik_path, int* iters,
+                           double* win_mean, double* win_sd, int* win_nobs, double* windows, double* fc, double* fvar, double* err,
+                           double* err_std, double* msfe, double* msfe0, int* cnt, unsigned flags) {
+    if (int rc = rolling_check(h, T, N, r, p, W, H, O, min_obs, n_start, x, origins, lags, Lam_start, R_start, Avar_start, Q_start, mu0_start,
+                               P0_start, max_iter, Lam, R, Avar, Q, mu0, P0, flags)) return rc;
+    return rolling_host(h, T, N, r, p, W, H, O, min_obs, n_start, x, origins, lags, Lam_start, R_start, Avar_start, Q_start, mu0_start, P0_start,
+                        sd_start, max_iter, tol, Lam, R, Avar, Q, mu0, P0, loglik_path, iters, win_mean, win_sd, win_nobs, windows, fc, fvar, err,
+                        err_std, msfe, msfe0, cnt, flags);
 }
 
 // ---- Bayesian estimation: the Gibbs sampler (gibbs.hip)------------------------------------------------------------------------

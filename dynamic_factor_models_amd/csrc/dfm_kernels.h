@@ -793,6 +793,31 @@ struct GbArArgs {
 };
 hipError_t launch_gibbs_ar_series(const GbArArgs& a, hipStream_t s);
 
+// Rolling-window out-of-sample evaluation (rolling.hip; dfm_rolling_eval_batch).  A call runs its O windows in slices b0 ..
+// b0 + S - 1; every array marked [S] is the slice's part (the driver offsets the caller's [O] arrays by b0).
+constexpr int kRwWindowBit = 128;                 // status word bit: a series of a window is thin or constant
+struct RwArgs {
+    int T, N, W, H, r, k;                         // panel rows, series, window rows, horizons, factors, state width r p
+    int b0, S, min_obs;
+    const double* x;                              // [T][N] the raw panel, data units (NaN = missing)
+    const int* origins; const int* lags;          // device [O], [N] (lags null: all 0)
+    double* win;                                  // [S][W][N] the standardised vintages
+    double* mean; double* sd; int* nobs;          // [S][N]
+    int* status;                                  // bit kRwWindowBit
+    int n_start;                                  // rolling_start_kernel: 1 = one start for every window, else one per window ([O])
+    const double *sLam, *sR, *sA, *sQ, *smu0, *sP0;   // the start, layouts of dfm_em_varp_batch
+    const double* sd_start;                       // [N] or null (no rescale)
+    double *Lam, *R, *A, *Q, *mu0, *P0;           // [S][..] the windows' parameters
+    const double* xhat; const double* xvar;       // rolling_score_kernel: [S][W + H][N] of the slice's forecasts
+    double *fc, *fvar, *err, *err_std;            // [S][H + 1][N], each may be null
+    double *sse, *sse0; int* cnt;                 // [H + 1][N] running sums over the origins scored so far
+    double *msfe, *msfe0; int* cnt_out;           // [H + 1][N], each may be null: written when last
+    int first, last;                              // the call's first / last slice: the sums start at zero / are divided
+};
+hipError_t launch_rolling_window(const RwArgs& a, hipStream_t s);
+hipError_t launch_rolling_start(const RwArgs& a, hipStream_t s);
+hipError_t launch_rolling_score(const RwArgs& a, hipStream_t s);
+
 // Device-side synthetic replicates (synth.hip); all arrays in the caller's layout (r).
 struct SynthArgs {
     int B, T, N, r;

@@ -907,3 +907,4 @@ from . import simsmooth_ar  # noqa: E402,F401  (attaches its path-draw entries)
 from . import gibbs_ar  # noqa: E402,F401  (attaches the Gibbs sampler's entries of the AR-idiosyncratic model)
 from . import news_ar  # noqa: E402,F401  (attaches its news entries)
 from . import simulate  # noqa: E402,F401  (attaches the simulated-panel entries of both models)
+from . import rolling  # noqa: E402,F401  (attaches the rolling-window evaluation entries)

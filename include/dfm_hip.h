@@ -47,7 +47,8 @@ enum {
     DFM_E_NUMERIC = -5,       /* non-finite log-likelihood in some replicate (non-PD Q/P0/...) */
     DFM_E_NO_DEVICE = -6,     /* no HIP device / extension not usable */
     DFM_E_COMM = -7,          /* multi-GPU entry points: RCCL could not be loaded or a collective failed */
-    DFM_E_VINTAGE = -8        /* dfm_news_batch: a cell observed in the old vintage is missing in the new one */
+    DFM_E_VINTAGE = -8,       /* dfm_news_batch: a cell observed in the old vintage is missing in the new one */
+    DFM_E_WINDOW = -9         /* dfm_rolling_eval_batch: a series of a window has too few visible cells, or they are all equal */
 };
 
 /* flags */
@@ -1032,6 +1033,52 @@ int dfm_filter_ar_batch(dfm_handle* h, int B, int T, int N, int r, int p, int q,
                         const double* mu0, const double* P0, const double* mean, const double* sd, double* z_pred,
                         double* P_pred, double* z_filt, double* P_filt, double* loglik_t, double* xpred, double* verr,
                         double* vstd, double* msfe, double* msfe_common, double* msfe0, int* cnt, unsigned flags);
+
+/* --- rolling-window out-of-sample evaluation, re-estimated at every origin (rolling.hip) ---------------
+ * x [T][N] is ONE raw panel in data units (NaN = missing).  origins [O]: 0-based rows o_0 < o_1 < .. < o_{O-1} with
+ * W - 1 <= o_b <= T - 1; lags [N]: publication lags lag_i >= 0 (NULL: all 0).  Both are HOST arrays in both entries.  Vintage b is
+ * rows o_b - W + 1 .. o_b of x; cell (t, i) is visible iff x_ti is observed and t <= o_b - lag_i, every other cell of the window is
+ * NaN.  Each window is standardised on its own visible cells (mean and population s.d., the reference's standardize_data):
+ * win_mean, win_sd [O][N], win_nobs [O][N] (int); windows [O][W][N] takes the standardised vintages themselves.  A series with fewer than min_obs visible cells in a window, or whose visible
+ * cells are all equal (s.d. 0), gives DFM_E_WINDOW: a status-word bit raised by rolling_window_kernel; the driver reads the word
+ * behind that kernel of every slice and stops there, so no EM runs on such a window (both entries return the code).
+ * Start: n_start = 1 or O parameter sets in standardised units, Lam_start [n_start][N][r], R_start [n_start][N], Avar_start
+ * [n_start][r][r p], Q_start [n_start][r][r], mu0_start [n_start][r p], P0_start [n_start][r p][r p] (the layouts of
+ * dfm_em_varp_batch; p = 1: those of dfm_em_batch).  sd_start [N] (may be NULL: no rescale) says which units the start's loadings are
+ * in: window b starts from Lam_i sd_start_i / win_sd_bi and R_i (sd_start_i / win_sd_bi)^2; Avar, Q, mu0, P0 are copied.
+ * EM: the windows are the batch of dfm_em_batch_dev (p = 1) or dfm_em_varp_batch_dev (p > 1) with T = W; max_iter, tol and flags
+ * mean what they mean there.  max_iter = 0: no EM, the forecasts are those of the start parameters and iters = 0 (the record of
+ * fixed parameters on per-window standardisation).  The windows' parameters Lam [O][N][r] .. P0 [O][r p][r p] are outputs (the EM runs
+ * in place in them), as are loglik_path [O][max_iter] (NaN past iters[b]) and iters [O].
+ * Forecasts: dfm_forecast_batch_dev on the windows with T = W, H, win_mean, win_sd.  For h = 0 .. H the target row is o_b + h:
+ * fc [O][H+1][N] = xhat_b[W-1+h], fvar [O][H+1][N] = xvar_b[W-1+h], data units, written for every target (an origin at T - 1 has
+ * real forecasts).  A target is SCORED iff its cell was not visible in vintage b (h >= 1; h = 0 where lag_i > 0: the nowcast),
+ * o_b + h < T and x is observed there: err = x - fc, err_std = err / sqrt(fvar) [O][H+1][N], NaN on every other target; err0 = x -
+ * win_mean[b][i] is the error of the unconditional-mean forecast of the same vintage.  msfe, msfe0 [H+1][N] are the means of err^2,
+ * err0^2 over the scored origins, cnt [H+1][N] (int) their number; NaN where cnt = 0.  The sums are taken in origin order by one
+ * lane per (h, i), no atomics: bit-identical from run to run.
+ * Every output may be NULL, except the six parameter arrays when max_iter > 0 (DFM_E_NULL).
+ * Status: W > T, W < max(2, p), H < 0, O < 1, origins out of range or not increasing, lag_i < 0 or lag_i > W - min_obs, min_obs <
+ * r + 1, n_start not 1 or O, r p > DFM_MAX_R, max_iter < 0: DFM_E_DIMS.  A lag > 0 without DFM_F_MAY_HAVE_MISSING: DFM_E_MISSING (its
+ * windows have NaN); a NaN in x without the flag: the pass's own DFM_E_MISSING (status word).  What the EM or the forecast entry
+ * refuses at (O, W, N, r, p): its status.
+ * The windows run in slices of at most 1024: one slice's windows, xhat, xvar and the EM's workspace are resident, so device memory
+ * does not grow with O (beyond the origins and what the caller takes); the running sums are continued slice after slice.
+ * Allocates in the handle (kept for the next call).  Outputs must not overlap the inputs. */
+int dfm_rolling_eval_batch_dev(dfm_handle* h, int T, int N, int r, int p, int W, int H, int O, int min_obs, int n_start,
+                               const double* x, const int* origins, const int* lags, const double* Lam_start,
+                               const double* R_start, const double* Avar_start, const double* Q_start, const double* mu0_start,
+                               const double* P0_start, const double* sd_start, int max_iter, double tol, double* Lam, double* R,
+                               double* Avar, double* Q, double* mu0, double* P0, double* loglik_path, int* iters,
+                               double* win_mean, double* win_sd, int* win_nobs, double* windows, double* fc, double* fvar, double* err,
+                               double* err_std, double* msfe, double* msfe0, int* cnt, unsigned flags);
+int dfm_rolling_eval_batch(dfm_handle* h, int T, int N, int r, int p, int W, int H, int O, int min_obs, int n_start,
+                           const double* x, const int* origins, const int* lags, const double* Lam_start,
+                           const double* R_start, const double* Avar_start, const double* Q_start, const double* mu0_start,
+                           const double* P0_start, const double* sd_start, int max_iter, double tol, double* Lam, double* R,
+                           double* Avar, double* Q, double* mu0, double* P0, double* loglik_path, int* iters,
+                           double* win_mean, double* win_sd, int* win_nobs, double* windows, double* fc, double* fvar, double* err,
+                           double* err_std, double* msfe, double* msfe0, int* cnt, unsigned flags);
 
 /* --- synthetic replicates generated on the device (SURVEY.md §8(d) DGP; no reference
  * counterpart -- the reference has no RNG).  Writes the standardised panel and the DGP parameters

@@ -383,6 +383,50 @@ function evaluate_forecasts(h::Handle, z::Matrix{Float64}, params, H::Integer; f
     return (msfe = msfe, rmsfe = sqrt.(msfe), relative = msfe ./ permutedims(o.m0), count = permutedims(o.cnt))
 end
 
+"The rolling-window out-of-sample record, re-estimated at every origin (dfm_rolling_eval_batch; include/dfm_hip.h): x is the RAW
+T x N panel (NaN = missing), origins increasing 1-based rows in W..T, lags the publication lags (length N) or nothing; start the
+parameters every window's EM starts from (Lam N x r, R, A or Avar r x (r nlag), Q, mu0, P0 as `em` / `em_varp` return them), in the
+units of sd_start (length N) or, with nothing, in each window's own.  max_iter = 0: no EM.  Returns forecast, variance, error,
+error_std (O x (H+1) x N, horizons 0..H), msfe, rmsfe, relative, count ((H+1) x N), mean, sd (O x N), iters, loglik (O x max_iter) and
+the windows' parameters Lam (O x N x r), R (O x N), A (O x r x r nlag), Q, mu0, P0."
+function evaluate_forecasts_rolling(h::Handle, x::Matrix{Float64}, start, H::Integer, W::Integer, origins::AbstractVector{<:Integer};
+                                    nlag::Integer = 1, lags = nothing, sd_start = nothing, min_obs::Integer = size(start.Lam, 2) + 1,
+                                    max_iter::Integer = 50, tol::Real = 1e-6, singular_q::Bool = false)
+    T, N = size(x); r = size(start.Lam, 2); k = r * nlag; O = length(origins); H1 = H + 1
+    Av = hasproperty(start, :Avar) ? start.Avar : start.A
+    panel = to_c_panel(x)
+    org = Vector{Cint}(origins .- 1)
+    lagC = lags === nothing ? C_NULL : Vector{Cint}(lags)
+    Lam0 = permutedims(start.Lam); R0 = copy(start.R); A0 = permutedims(Av); Q0 = permutedims(start.Q)
+    m0 = copy(start.mu0); P00 = permutedims(start.P0)
+    sdC = sd_start === nothing ? C_NULL : Vector{Float64}(sd_start)
+    Lam = Array{Float64}(undef, r, N, O); R = Array{Float64}(undef, N, O); A = Array{Float64}(undef, k, r, O)
+    Q = Array{Float64}(undef, r, r, O); mu0 = Array{Float64}(undef, k, O); P0 = Array{Float64}(undef, k, k, O)
+    path = Array{Float64}(undef, max(max_iter, 1), O); iters = Array{Cint}(undef, O)
+    wm = Array{Float64}(undef, N, O); ws = Array{Float64}(undef, N, O); wn = Array{Cint}(undef, N, O)
+    fc = Array{Float64}(undef, N, H1, O); fv = Array{Float64}(undef, N, H1, O); er = Array{Float64}(undef, N, H1, O)
+    es = Array{Float64}(undef, N, H1, O); ms = Array{Float64}(undef, N, H1); ms0 = Array{Float64}(undef, N, H1); cnt = Array{Cint}(undef, N, H1)
+    missing_cells = any(isnan, x) || (lags !== nothing && any(>(0), lags))
+    flags = (missing_cells ? DFM_F_MAY_HAVE_MISSING : Cuint(0)) | (singular_q ? DFM_F_SINGULAR_Q : Cuint(0))
+    GC.@preserve panel org lagC Lam0 R0 A0 Q0 m0 P00 sdC Lam R A Q mu0 P0 path iters wm ws wn fc fv er es ms ms0 cnt begin
+        rc = ccall((:dfm_rolling_eval_batch, LIB), Cint,
+                   (Ptr{Cvoid}, Cint, Cint, Cint, Cint, Cint, Cint, Cint, Cint, Cint, Ptr{Float64}, Ptr{Cint}, Ptr{Cint}, Ptr{Float64},
+                    Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cint, Cdouble, Ptr{Float64},
+                    Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cint}, Ptr{Float64},
+                    Ptr{Float64}, Ptr{Cint}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                    Ptr{Float64}, Ptr{Cint}, Cuint),
+                   h.ptr, T, N, r, nlag, W, H, O, min_obs, 1, panel, org, lagC, Lam0, R0, A0, Q0, m0, P00, sdC, max_iter, tol, Lam, R, A, Q,
+                   mu0, P0, max_iter > 0 ? path : C_NULL, iters, wm, ws, wn, C_NULL, fc, fv, er, es, ms, ms0, cnt, flags)
+        check(h.ptr, rc)
+    end
+    msfe = permutedims(ms)
+    return (forecast = permutedims(fc, (3, 2, 1)), variance = permutedims(fv, (3, 2, 1)), error = permutedims(er, (3, 2, 1)),
+            error_std = permutedims(es, (3, 2, 1)), msfe = msfe, rmsfe = sqrt.(msfe), relative = msfe ./ permutedims(ms0),
+            count = permutedims(cnt), mean = permutedims(wm), sd = permutedims(ws), iters = Vector{Int}(iters),
+            loglik = permutedims(path)[:, 1:max_iter], Lam = permutedims(Lam, (3, 2, 1)), R = permutedims(R),
+            A = permutedims(A, (3, 2, 1)), Q = permutedims(Q, (3, 2, 1)), mu0 = permutedims(mu0), P0 = permutedims(P0, (3, 2, 1)))
+end
+
 "Identified impulse responses and forecast-error variance shares of every series (dfm_irf_batch; include/dfm_hip.h): params as
 `forecast`; named = r distinct series (1-based; factor k is the common component of series named[k], their order the recursive
 ordering) or nothing (S = chol Q); cumulate = series (1-based) whose responses are cumulated; sd (length N) puts the responses
