@@ -24,6 +24,7 @@ Reference objects mirrored (file:line of dfm_functions.ipynb):
 """
 from __future__ import annotations
 
+from contextlib import contextmanager as _contextmanager     # (underscore: api's public names stay what they were)
 from dataclasses import dataclass, field
 from typing import Optional
 
@@ -218,11 +219,7 @@ def estimate(m: DFMModel, method: EstimationMethod = None, *, max_em_iter: int =
         raise ValueError("fewer fully observed series than factors: cannot initialise by PCA")
 
     own_ctx = ctx is None
-    if own_ctx:
-        from .kalman import DfmContext
-        ctx = DfmContext()                                              # raises without a HIP device
-    try:
-        used_singular_q = False
+    with _device(ctx) as ctx:                                           # raises without a HIP device
         p0, F0 = ctx.pca_init_batch_host(xbal[None, :, :], r)          # pca_score (:179-183) + OLS start, on the GPU
         F0 = F0[0]
         Lam = np.empty((N, r)); R = np.empty(N)
@@ -234,18 +231,11 @@ def estimate(m: DFMModel, method: EstimationMethod = None, *, max_em_iter: int =
             R[gap] = o["ssr"] / np.maximum(o["nobs"], 1)
         if nlag == 1:
             start = dict(Lam=Lam[None], R=R[None], A=p0["A"], Q=p0["Q"], mu0=p0["mu0"], P0=p0["P0"])
-            from ._lib import DfmError
             args = (z[None], start["Lam"], start["R"], start["A"], start["Q"], start["mu0"], start["P0"])
             kw = dict(max_iter=max_em_iter, tol=tol_em, may_have_missing=bool((~obs).any()))
-            try:
-                params, path, iters, f, P = ctx.em_batch_host(*args, **kw)
-            except DfmError as err:
-                # the information-form recursion inverts Q: a PCA start on fewer than 2r + 1 periods has a rank-deficient
-                # VAR residual covariance.  Run the covariance-form recursion (DFM_F_SINGULAR_Q) instead of failing.
-                if err.code != -5:
-                    raise
-                params, path, iters, f, P = ctx.em_batch_host(*args, singular_q=True, **kw)
-                used_singular_q = True
+            # the information-form recursion inverts Q: a PCA start on fewer than 2r + 1 periods has a rank-deficient
+            # VAR residual covariance.  Run the covariance-form recursion (DFM_F_SINGULAR_Q) instead of failing.
+            (params, path, iters, f, P), used_singular_q = _numeric_retry(lambda **sq: (ctx.em_batch_host(*args, **sq, **kw), bool(sq)))
         else:
             # VAR(p) start (oracle/varp_oracle.py varp_init): OLS of the PCA factors on their p lags without constant
             # (dfm_ols_batch), Q = residual covariance / (T - p), z_0 ~ N(0, second moment of the stacked lags)
@@ -257,21 +247,12 @@ def estimate(m: DFMModel, method: EstimationMethod = None, *, max_em_iter: int =
             e = o["resid"]
             Qv = e.T @ e / (T - nlag); Qv = 0.5 * (Qv + Qv.T)
             P0v = Z.T @ Z / Z.shape[0]; P0v = 0.5 * (P0v + P0v.T)
-            from ._lib import DfmError
             vargs = (z[None], Lam[None], R[None], Avar[None], Qv[None], np.zeros((1, r * nlag)), P0v[None])
             vkw = dict(max_iter=max_em_iter, tol=tol_em, may_have_missing=bool((~obs).any()))
-            try:
-                params, path, iters, f, P = ctx.em_varp_batch_host(*vargs, **vkw)
-            except DfmError as err:                     # r = 4: recursion_comp.hip inverts the r x r block Q (as above)
-                if err.code != -5:
-                    raise
-                params, path, iters, f, P = ctx.em_varp_batch_host(*vargs, singular_q=True, **vkw)
-                used_singular_q = True
+            # r = 4: recursion_comp.hip inverts the r x r block Q (as above)
+            (params, path, iters, f, P), used_singular_q = _numeric_retry(lambda **sq: (ctx.em_varp_batch_host(*vargs, **sq, **vkw), bool(sq)))
             params = dict(params)
             params["A"] = params["Avar"]
-    finally:
-        if own_ctx:
-            ctx.close()
     k = int(iters[0])
     f = f[0]
     Lam, R, A, Q = params["Lam"][0], params["R"][0], params["A"][0], params["Q"][0]
@@ -305,12 +286,8 @@ def estimate(m: DFMModel, method: EstimationMethod = None, *, max_em_iter: int =
     c0 = 1 if var.withconst else 0
     var.betahat[c0:c0 + ka, :] = A[:, :ka].T
     if nrep and dev_draws:
-        c, own = _own(None if own_ctx else ctx)
-        try:
+        with _device(None if own_ctx else ctx) as c:
             m.replicates = _bootstrap_replicates_device(c, z, params, nlag, int(nrep), int(seed), max_em_iter, tol_em, used_singular_q)
-        finally:
-            if own:
-                c.close()
     elif nrep:
         m.replicates = _bootstrap_replicates(z, params, int(nrep), int(seed), int(ngpu), max_em_iter, tol_em,
                                              singular_q=used_singular_q)
@@ -340,8 +317,7 @@ def _estimate_parametric_observed(m: DFMModel, max_em_iter, tol_em, ctx):
     if not enough.all():
         z = z[:, enough]
     T, N = z.shape
-    ctx, own = _own(ctx)
-    try:
+    with _device(ctx) as ctx:
         og = ctx.ols_batch_host(G, z, want_resid=True)                  # series on the observed factors, complete cases
         Lam_o = og["beta"]
         res = og["resid"]                                               # [T, N], NaN where the cell is missing
@@ -376,9 +352,6 @@ def _estimate_parametric_observed(m: DFMModel, max_em_iter, tol_em, ctx):
         m.fes.R2 = np.full(m.fes.ns, np.nan); m.fes.R2[np.nonzero(enough)[0]] = R2
         m.r2[cols] = R2
         estimate_var(m.factor_var_model, ctx=ctx)                       # VAR of (g, f) jointly: the reference's second stage
-    finally:
-        if own:
-            ctx.close()
     return m.loglik_path
 
 
@@ -473,6 +446,133 @@ def _forecast_inputs(m: DFMModel, through: int):
     return cols, (x - mu) / sd, mu, sd
 
 
+# ----------------------------------------------------------------------------- what the post-estimation calls share
+# One text for what the functions of the parametric fit and their _ar_idio counterparts have in common (docs/HISTORY.md A.17,
+# with the list of the differences between them that were kept as they were).
+def _own(ctx):
+    if ctx is not None:
+        return ctx, False
+    from .kalman import DfmContext
+    return DfmContext(), True                                           # raises without a HIP device
+
+
+@_contextmanager
+def _device(ctx):
+    """The context a function works on: `ctx` itself, which stays open, or with None a new one (_own), which is closed on the way
+    out, also when the body raises."""
+    ctx, own = _own(ctx)
+    try:
+        yield ctx
+    finally:
+        if own:
+            ctx.close()
+
+
+def _numeric_retry(call, unless=None):
+    """The information form inverts Q, so a numeric failure (DfmError code -5) of call() is answered once with
+    call(singular_q=True), the covariance form -- unless `unless(err)` says that this failure is not one that form can cure."""
+    from ._lib import DfmError
+    try:
+        return call()
+    except DfmError as err:
+        if err.code != -5 or (unless is not None and unless(err)):
+            raise
+        return call(singular_q=True)
+
+
+def _quantile_arg(quantiles, *needs, closed=False):
+    """`quantiles` as a float64 vector (None stays None), each in (0, 1] -- `closed`: in [0, 1] -- or ValueError.  `needs`:
+    (broken, message) pairs, the refusals a function has between reading the vector and checking its range (no replicates, no
+    horizon); the first broken one is raised."""
+    if quantiles is None:
+        return None
+    qs = np.atleast_1d(np.asarray(quantiles, dtype=np.float64))
+    for broken, message in needs:
+        if broken:
+            raise ValueError(message)
+    if closed:
+        if qs.size == 0 or np.any(~(qs >= 0.0)) or np.any(~(qs <= 1.0)):
+            raise ValueError("quantiles must lie in [0, 1]")
+    elif qs.size < 1 or not np.all((qs > 0.0) & (qs <= 1.0)):
+        raise ValueError("quantiles must lie in (0, 1]")
+    return qs
+
+
+_NEED_REPLICATES = "quantile bands need bootstrap replicates: estimate(m, Parametric(), nrep=...) first"
+
+
+def _need_fit(m: DFMModel):
+    """Refuses a model without a parametric fit."""
+    if m.em_params is None:
+        raise ValueError("the model has not been estimated: run estimate(m, Parametric()) first")
+
+
+def _through_arg(m: DFMModel, through):
+    """`through` (None: lastperiod) as a 1-based period in lastperiod..T, or ValueError."""
+    through = m.lastperiod if through is None else int(through)
+    if not (m.lastperiod <= through <= m.T):
+        raise ValueError(f"through must lie in lastperiod..T ({m.lastperiod}..{m.T})")
+    return through
+
+
+def _no_ar_terms(m: DFMModel, cols, who, hint):
+    """Refuses, in the name of function `who`, a model whose series carry AR idiosyncratic coefficients; `hint`: where to go."""
+    if np.any(np.nan_to_num(np.asarray(m.uar_coef, dtype=np.float64)[cols]) != 0.0):
+        raise ValueError(f"{who} has no AR idiosyncratic terms: the model carries uar_coef {hint}")
+
+
+def _plain_fit(m: DFMModel, through, who=None, hint=""):
+    """What a function of the parametric fit starts from: the parameters in m.em_params as (Lam, R, A, Q, mu0, P0) -- A is
+    [A_1 .. A_p], under whichever key estimate() left it -- and _forecast_inputs(m, through): cols, z, mu, sd.  Refuses a model
+    whose series no longer match the fit and, with `who`, one with AR idiosyncratic terms (_no_ar_terms)."""
+    ep = m.em_params
+    prm = (ep["Lam"], ep["R"], ep["Avar"] if "Avar" in ep else ep["A"], ep["Q"], ep["mu0"], ep["P0"])
+    cols, z, mu, sd = _forecast_inputs(m, through)
+    if prm[0].shape[0] != cols.size:
+        raise ValueError("m.em_params does not match the model's series (was the model changed after estimate?)")
+    if who is not None:
+        _no_ar_terms(m, cols, who, hint)
+    return prm, cols, z, mu, sd
+
+
+def _replicate_sets(m: DFMModel):
+    """The bootstrap replicates' (or posterior draws') parameter sets in the order of _plain_fit, [B, ...] each."""
+    rp = m.replicates["params"]
+    return rp["Lam"], rp["R"], rp["A"], rp["Q"], rp["mu0"], rp["P0"]
+
+
+def _rep(a, B):
+    """`a` for each of B replicates: [B, ...], C-ordered."""
+    return np.ascontiguousarray(np.broadcast_to(a, (B,) + a.shape))
+
+
+def _one(prm):
+    """One parameter set as a batch of one."""
+    return tuple(a[None] for a in prm)
+
+
+def _unpack(Pp, k):
+    """[rows, k (k + 1) / 2] packed lower triangles as full symmetric [rows, k, k]."""
+    il = np.tril_indices(k)                                             # packed lower, row-major (include/dfm_hip.h)
+    cov = np.empty((Pp.shape[0], k, k))
+    cov[:, il[0], il[1]] = Pp
+    cov[:, il[1], il[0]] = Pp
+    return cov
+
+
+def _horizon_bands(ctx, ob, H, qs):
+    """Bands [nq, H, cols] over the horizon rows of the replicates' point forecasts (dfm_quantile_bands)."""
+    return ctx.quantile_bands_host(ob["xhat"][:, -H:, :], qs)
+
+
+def _with_bands(out, qs, **bands):
+    """`out` with the quantiles and the band arrays behind them -- when bands were asked for."""
+    if qs is not None:
+        out["quantiles"] = qs
+        out.update(bands)
+    return out
+
+
 def forecast(m: DFMModel, H: int, *, through: Optional[int] = None, quantiles=None, ctx=None) -> dict:
     """Nowcasts and H-step forecasts of the panel from the parametric fit (`estimate(m, Parametric())`, nfac_o = 0).
 
@@ -493,120 +593,54 @@ def forecast(m: DFMModel, H: int, *, through: Optional[int] = None, quantiles=No
     H = int(H)
     if H < 0:
         raise ValueError("H must be >= 0")
-    if m.em_params is None:
-        raise ValueError("the model has not been estimated: run estimate(m, Parametric()) first")
+    _need_fit(m)
     if m.nfac_o != 0:
         raise ValueError("forecast needs nfac_o = 0 (the future values of observed factors are unknown)")
-    through = m.lastperiod if through is None else int(through)
-    if not (m.lastperiod <= through <= m.T):
-        raise ValueError(f"through must lie in lastperiod..T ({m.lastperiod}..{m.T})")
-    qs = None
-    if quantiles is not None:
-        qs = np.atleast_1d(np.asarray(quantiles, dtype=np.float64))
-        if getattr(m, "replicates", None) is None:
-            raise ValueError("quantile bands need bootstrap replicates: estimate(m, Parametric(), nrep=...) first")
-        if H < 1:
-            raise ValueError("quantile bands need H >= 1")
-        if qs.size < 1 or not np.all((qs > 0.0) & (qs <= 1.0)):
-            raise ValueError("quantiles must lie in (0, 1]")
-    ep = m.em_params
-    Lam, R, Q = ep["Lam"], ep["R"], ep["Q"]
-    A = ep["Avar"] if "Avar" in ep else ep["A"]
-    mu0, P0 = ep["mu0"], ep["P0"]
-    r = Lam.shape[1]
-    cols, z, mu, sd = _forecast_inputs(m, through)
-    if Lam.shape[0] != cols.size:
-        raise ValueError("m.em_params does not match the model's series (was the model changed after estimate?)")
-    from ._lib import DfmError
-    ctx, own = _own(ctx)
-    try:
-        def run(Lb, Rb, Ab, Qb, m0, P0b, **kw):
-            B = Lb.shape[0]
-            rep = lambda a: np.ascontiguousarray(np.broadcast_to(a, (B,) + a.shape))
-            args = (rep(z), Lb, Rb, Ab, Qb, m0, P0b, H)
-            kw.update(mean=rep(mu), sd=rep(sd), may_have_missing=bool(np.isnan(z).any()))
-            try:
-                return ctx.forecast_batch_host(*args, **kw)
-            except DfmError as err:                 # the information form inverts Q: as estimate(), retry in covariance form
-                if err.code != -5:
-                    raise
-                return ctx.forecast_batch_host(*args, singular_q=True, **kw)
-        o = run(Lam[None], R[None], A[None], Q[None], mu0[None], P0[None])
+    through = _through_arg(m, through)
+    qs = _quantile_arg(quantiles, (getattr(m, "replicates", None) is None, _NEED_REPLICATES), (H < 1, "quantile bands need H >= 1"))
+    prm, cols, z, mu, sd = _plain_fit(m, through)
+    with _device(ctx) as ctx:
+        def run(sets, **kw):                        # the information form inverts Q: as estimate(), retry in covariance form
+            B = sets[0].shape[0]
+            kw.update(mean=_rep(mu, B), sd=_rep(sd, B), may_have_missing=bool(np.isnan(z).any()))
+            return _numeric_retry(lambda **sq: ctx.forecast_batch_host(_rep(z, B), *sets, H, **sq, **kw))
+        o = run(_one(prm))
         bands = None
         if qs is not None:
-            rp = m.replicates["params"]
-            ob = run(rp["Lam"], rp["R"], rp["A"], rp["Q"], rp["mu0"], rp["P0"], want_var=False, want_common=False, want_P=False)
-            bands = ctx.quantile_bands_host(ob["xhat"][:, -H:, :], qs)
-    finally:
-        if own:
-            ctx.close()
-    il = np.tril_indices(r)                                             # packed lower, row-major (include/dfm_hip.h)
-    Pp = o["P"][0]
-    cov = np.empty((Pp.shape[0], r, r))
-    cov[:, il[0], il[1]] = Pp
-    cov[:, il[1], il[0]] = Pp
+            bands = _horizon_bands(ctx, run(_replicate_sets(m), want_var=False, want_common=False, want_P=False), H, qs)
     out = dict(rows=np.arange(m.initperiod, through + H + 1), cols=cols, x=o["xhat"][0], x_sd=np.sqrt(o["xvar"][0]),
-               common=o["common"][0], factor=o["f"][0], factor_cov=cov, loglik=float(o["loglik"][0]))
-    if bands is not None:
-        out["quantiles"] = qs
-        out["bands"] = bands
-    return out
+               common=o["common"][0], factor=o["f"][0], factor_cov=_unpack(o["P"][0], prm[0].shape[1]),
+               loglik=float(o["loglik"][0]))
+    return _with_bands(out, qs, bands=bands)
 
 
 # ----------------------------------------------------------------------------- filtered states and out-of-sample evaluation
 def _filter_setup(m: DFMModel, through, quantiles):
     """The checks filter_states and evaluate_forecasts share (no device is touched): (through, quantiles or None)."""
-    if m.em_params is None:
-        raise ValueError("the model has not been estimated: run estimate(m, Parametric()) first")
+    _need_fit(m)
     if m.nfac_o != 0:
         raise ValueError("the filter needs nfac_o = 0")
-    through = m.lastperiod if through is None else int(through)
-    if not (m.lastperiod <= through <= m.T):
-        raise ValueError(f"through must lie in lastperiod..T ({m.lastperiod}..{m.T})")
-    qs = None
-    if quantiles is not None:
-        qs = np.atleast_1d(np.asarray(quantiles, dtype=np.float64))
-        if getattr(m, "replicates", None) is None:
-            raise ValueError("quantile bands need bootstrap replicates: estimate(m, Parametric(), nrep=...) first")
-        if qs.size < 1 or not np.all((qs > 0.0) & (qs <= 1.0)):
-            raise ValueError("quantiles must lie in (0, 1]")
-    return through, qs
+    through = _through_arg(m, through)
+    return through, _quantile_arg(quantiles, (getattr(m, "replicates", None) is None, _NEED_REPLICATES))
+
+
+def _flat_bands(ctx, x, qs):
+    """Bands [nq, ...] of x [B, ...] over its first axis (dfm_quantile_bands takes the cells as one axis)."""
+    return ctx.quantile_bands_host(np.ascontiguousarray(x.reshape(x.shape[0], -1)), qs).reshape((qs.size,) + x.shape[1:])
 
 
 def _filter_run(m: DFMModel, through, H, t0, want, band_of, qs, ctx):
     """One dfm_filter_batch call at the fit and, for bands, one over the bootstrap replicates' parameter sets on the same panel
     followed by dfm_quantile_bands over band_of(outputs) [B, ...]."""
-    ep = m.em_params
-    Lam, R, Q = ep["Lam"], ep["R"], ep["Q"]
-    A = ep["Avar"] if "Avar" in ep else ep["A"]
-    cols, z, mu, sd = _forecast_inputs(m, through)
-    if Lam.shape[0] != cols.size:
-        raise ValueError("m.em_params does not match the model's series (was the model changed after estimate?)")
-    ctx, own = _own(ctx)
-    try:
-        def run(Lb, Rb, Ab, Qb, m0, P0b, w):
-            B = Lb.shape[0]
-            rep = lambda a: np.ascontiguousarray(np.broadcast_to(a, (B,) + a.shape))
-            return ctx.filter_batch_host(rep(z), Lb, Rb, Ab, Qb, m0, P0b, H=H, t0=t0, mean=rep(mu), sd=rep(sd), want=w,
+    prm, cols, z, mu, sd = _plain_fit(m, through)
+    with _device(ctx) as ctx:
+        def run(sets, w):
+            B = sets[0].shape[0]
+            return ctx.filter_batch_host(_rep(z, B), *sets, H=H, t0=t0, mean=_rep(mu, B), sd=_rep(sd, B), want=w,
                                          may_have_missing=bool(np.isnan(z).any()))
-        o = run(Lam[None], R[None], A[None], Q[None], ep["mu0"][None], ep["P0"][None], want)
-        bands = None
-        if qs is not None:
-            rp = m.replicates["params"]
-            x = band_of(run(rp["Lam"], rp["R"], rp["A"], rp["Q"], rp["mu0"], rp["P0"], band_of.want))
-            bands = ctx.quantile_bands_host(np.ascontiguousarray(x.reshape(x.shape[0], -1)), qs).reshape((qs.size,) + x.shape[1:])
-    finally:
-        if own:
-            ctx.close()
+        o = run(_one(prm), want)
+        bands = None if qs is None else _flat_bands(ctx, band_of(run(_replicate_sets(m), band_of.want)), qs)
     return cols, o, bands
-
-
-def _unpack(Pp, k):
-    il = np.tril_indices(k)                                             # packed lower, row-major (include/dfm_hip.h)
-    cov = np.empty((Pp.shape[0], k, k))
-    cov[:, il[0], il[1]] = Pp
-    cov[:, il[1], il[0]] = Pp
-    return cov
 
 
 def filter_states(m: DFMModel, *, through: Optional[int] = None, quantiles=None, ctx=None) -> dict:
@@ -636,10 +670,7 @@ def filter_states(m: DFMModel, *, through: Optional[int] = None, quantiles=None,
                factor_pred_cov=Pp[:, :r, :r], factor_filt=o["z_filt"][0][:, :r], factor_filt_cov=Pf[:, :r, :r],
                state_pred=o["z_pred"][0], state_filt=o["z_filt"][0], loglik_t=o["loglik_t"][0],
                loglik=float(o["loglik_t"][0].sum()), x_pred=o["xpred"][0], error=o["verr"][0], error_std=o["vstd"][0])
-    if bands is not None:
-        out["quantiles"] = qs
-        out["bands"] = bands
-    return out
+    return _with_bands(out, qs, bands=bands)
 
 
 def evaluate_forecasts(m: DFMModel, H: int, *, first_origin: Optional[int] = None, through: Optional[int] = None, quantiles=None,
@@ -670,10 +701,7 @@ def evaluate_forecasts(m: DFMModel, H: int, *, first_origin: Optional[int] = Non
     msfe, msfe0 = o["msfe"][0], o["msfe0"][0]
     with np.errstate(invalid="ignore", divide="ignore"):
         out = dict(horizons=np.arange(1, H + 1), cols=cols, msfe=msfe, rmsfe=np.sqrt(msfe), relative=msfe / msfe0, count=o["cnt"][0])
-    if bands is not None:
-        out["quantiles"] = qs
-        out["bands"] = bands
-    return out
+    return _with_bands(out, qs, bands=bands)
 
 
 def evaluate_forecasts_rolling(m: DFMModel, H: int, window: int, *, origins=None, step: int = 1, lags=None, start=None,
@@ -754,12 +782,8 @@ def evaluate_forecasts_rolling(m: DFMModel, H: int, window: int, *, origins=None
     x, lg, cols = np.ascontiguousarray(x[:, keep]), lg[keep], cols[keep]
     args = (x, o0, W, H, np.ascontiguousarray(Lam[:, keep]), np.ascontiguousarray(R[:, keep]), A, Q, mu0, P0)
     kw = dict(lags=lg, sd_start=sd_start, min_obs=min_obs, max_iter=int(max_em_iter), tol=float(tol_em))
-    ctx, own = _own(ctx)
-    try:
-        o = _numeric_retry(lambda sq: ctx.rolling_eval_batch_host(*args, singular_q=sq, **kw))
-    finally:
-        if own:
-            ctx.close()
+    with _device(ctx) as ctx:
+        o = _numeric_retry(lambda singular_q=False: ctx.rolling_eval_batch_host(*args, singular_q=singular_q, **kw))
     with np.errstate(invalid="ignore", divide="ignore"):
         return dict(origins=org, horizons=np.arange(H + 1), cols=cols, forecast=o["fc"], variance=o["fvar"], error=o["err"],
                     error_std=o["err_std"], msfe=o["msfe"], rmsfe=np.sqrt(o["msfe"]), relative=o["msfe"] / o["msfe0"], count=o["cnt"],
@@ -768,8 +792,7 @@ def evaluate_forecasts_rolling(m: DFMModel, H: int, window: int, *, origins=None
 
 # ----------------------------------------------------------------------------- structural analysis of the parametric fit
 def _structural_checks(m: DFMModel):
-    if m.em_params is None:
-        raise ValueError("the model has not been estimated: run estimate(m, Parametric()) first")
+    _need_fit(m)
     if m.nfac_o != 0:
         raise ValueError("structural analysis needs nfac_o = 0")
 
@@ -785,15 +808,30 @@ def _to_cols(idx, cols, what):
     return np.asarray(out, dtype=np.int32)
 
 
-def _numeric_retry(call):
-    """As forecast: the information form inverts Q, so a numeric failure is retried once in covariance form."""
-    from ._lib import DfmError
-    try:
-        return call(False)
-    except DfmError as err:
-        if err.code != -5:
-            raise
-        return call(True)
+def _named_arg(named, cols, r):
+    """`named` (None stays None) as r distinct positions in `cols`, or ValueError."""
+    nm = None if named is None else _to_cols(named, cols, "named")
+    if nm is not None and (nm.size != r or np.unique(nm).size != r):
+        raise ValueError(f"named must be {r} distinct series")
+    return nm
+
+
+def _cumulate_arg(cumulate, cols):
+    """`cumulate` (None stays None) as a 0 / 1 flag per series of `cols`."""
+    if cumulate is None:
+        return None
+    cum = np.zeros(cols.size, dtype=np.int32)
+    cum[_to_cols(cumulate, cols, "cumulate")] = 1
+    return cum
+
+
+def _structural_quantiles(m: DFMModel, quantiles, named):
+    """`quantiles` of structural_irf and structural_irf_signs: bands need named series and replicates, in that order."""
+    if quantiles is not None and named is None:
+        raise ValueError("quantile bands need named series: the replicates are not in a common rotation otherwise")
+    if quantiles is not None and getattr(m, "replicates", None) is None:
+        raise ValueError(_NEED_REPLICATES)
+    return _quantile_arg(quantiles)
 
 
 def structural_irf(m: DFMModel, H: int, *, named=None, cumulate=None, unit_effect: bool = False, fevd: bool = True,
@@ -817,50 +855,23 @@ def structural_irf(m: DFMModel, H: int, *, named=None, cumulate=None, unit_effec
     _structural_checks(m)
     if unit_effect and named is None:
         raise ValueError("unit_effect needs named series")
-    qs = None
-    if quantiles is not None:
-        if named is None:
-            raise ValueError("quantile bands need named series: the replicates are not in a common rotation otherwise")
-        if getattr(m, "replicates", None) is None:
-            raise ValueError("quantile bands need bootstrap replicates: estimate(m, Parametric(), nrep=...) first")
-        qs = np.atleast_1d(np.asarray(quantiles, dtype=np.float64))
-        if qs.size < 1 or not np.all((qs > 0.0) & (qs <= 1.0)):
-            raise ValueError("quantiles must lie in (0, 1]")
-    ep = m.em_params
-    Lam, R, Q = ep["Lam"], ep["R"], ep["Q"]
-    A = ep["Avar"] if "Avar" in ep else ep["A"]
+    qs = _structural_quantiles(m, quantiles, named)
+    (Lam, R, A, Q, _, _), cols, _, _, sd = _plain_fit(m, m.lastperiod)
     N, r = Lam.shape
-    cols, _, _, sd = _forecast_inputs(m, m.lastperiod)
-    if N != cols.size:
-        raise ValueError("m.em_params does not match the model's series (was the model changed after estimate?)")
-    nm = None if named is None else _to_cols(named, cols, "named")
-    if nm is not None and (nm.size != r or np.unique(nm).size != r):
-        raise ValueError(f"named must be {r} distinct series")
-    cum = None
-    if cumulate is not None:
-        cum = np.zeros(N, dtype=np.int32)
-        cum[_to_cols(cumulate, cols, "cumulate")] = 1
-    ctx, own = _own(ctx)
-    try:
-        def run(Lb, Ab, Qb, Rb, want_fevd):
-            B = Lb.shape[0]
-            sdb = np.ascontiguousarray(np.broadcast_to(sd, (B, N)))
-            return ctx.irf_batch_host(Lb, Ab, Qb, Rb, H, sd=sdb, named=nm, cum=cum, unit_effect=unit_effect, want_fevd=want_fevd)
-        o = run(Lam[None], A[None], Q[None], R[None], fevd)
+    nm = _named_arg(named, cols, r)
+    cum = _cumulate_arg(cumulate, cols)
+    with _device(ctx) as ctx:
+        def run(Lb, Rb, Ab, Qb, want_fevd):
+            return ctx.irf_batch_host(Lb, Ab, Qb, Rb, H, sd=_rep(sd, Lb.shape[0]), named=nm, cum=cum, unit_effect=unit_effect,
+                                      want_fevd=want_fevd)
+        o = run(Lam[None], R[None], A[None], Q[None], fevd)
         bands = None
         if qs is not None:
-            rp = m.replicates["params"]
-            ob = run(rp["Lam"], rp["A"], rp["Q"], rp["R"], False)
+            ob = run(*_replicate_sets(m)[:4], False)
             bands = ctx.quantile_bands_host(ob["irf"].reshape(ob["irf"].shape[0], -1), qs).reshape(qs.size, r, H, N)
-    finally:
-        if own:
-            ctx.close()
     out = dict(cols=cols, irf=np.ascontiguousarray(o["irf"][0].transpose(2, 1, 0)),
                fevd=None if o["fevd"] is None else np.ascontiguousarray(o["fevd"][0].transpose(2, 1, 0)))
-    if bands is not None:
-        out["quantiles"] = qs
-        out["bands"] = np.ascontiguousarray(bands.transpose(0, 3, 2, 1))
-    return out
+    return _with_bands(out, qs, bands=None if bands is None else np.ascontiguousarray(bands.transpose(0, 3, 2, 1)))
 
 
 def structural_irf_signs(m: DFMModel, H: int, restrictions, *, candidates: int = 1000, keep: Optional[int] = None, named=None,
@@ -893,29 +904,11 @@ def structural_irf_signs(m: DFMModel, H: int, restrictions, *, candidates: int =
     if keep is not None and int(keep) < 1:
         raise ValueError("keep must be >= 1")
     _structural_checks(m)
-    qs = None
-    if quantiles is not None:
-        if named is None:
-            raise ValueError("quantile bands need named series: the replicates are not in a common rotation otherwise")
-        if getattr(m, "replicates", None) is None:
-            raise ValueError("quantile bands need bootstrap replicates: estimate(m, Parametric(), nrep=...) first")
-        qs = np.atleast_1d(np.asarray(quantiles, dtype=np.float64))
-        if qs.size < 1 or not np.all((qs > 0.0) & (qs <= 1.0)):
-            raise ValueError("quantiles must lie in (0, 1]")
-    ep = m.em_params
-    Lam, R, Q = ep["Lam"], ep["R"], ep["Q"]
-    A = ep["Avar"] if "Avar" in ep else ep["A"]
+    qs = _structural_quantiles(m, quantiles, named)
+    (Lam, R, A, Q, _, _), cols, _, _, sd = _plain_fit(m, m.lastperiod)
     N, r = Lam.shape
-    cols, _, _, sd = _forecast_inputs(m, m.lastperiod)
-    if N != cols.size:
-        raise ValueError("m.em_params does not match the model's series (was the model changed after estimate?)")
-    nm = None if named is None else _to_cols(named, cols, "named")
-    if nm is not None and (nm.size != r or np.unique(nm).size != r):
-        raise ValueError(f"named must be {r} distinct series")
-    cum = None
-    if cumulate is not None:
-        cum = np.zeros(N, dtype=np.int32)
-        cum[_to_cols(cumulate, cols, "cumulate")] = 1
+    nm = _named_arg(named, cols, r)
+    cum = _cumulate_arg(cumulate, cols)
     rs = np.asarray(restrictions, dtype=np.int64)
     if rs.size == 0:
         rs = rs.reshape(0, 5)
@@ -930,46 +923,38 @@ def structural_irf_signs(m: DFMModel, H: int, restrictions, *, candidates: int =
             raise ValueError(f"restrictions: need 0 <= h0 <= h1 < H = {H}")
         if np.any(np.abs(rs[:, 4]) != 1):
             raise ValueError("restrictions: the sign must be +1 or -1")
-    ctx, own = _own(ctx)
-    try:
-        def run(Lb, Ab, Qb, Rb, K, want_S, want_irf, want_fevd):
-            B = Lb.shape[0]
-            sdb = np.ascontiguousarray(np.broadcast_to(sd, (B, N)))
-            return ctx.signirf_batch_host(Lb, Ab, Qb, Rb, H, rs, M, K, seed=seed, sd=sdb, named=nm, cum=cum, want_S=want_S,
-                                          want_irf=want_irf, want_fevd=want_fevd)
+    with _device(ctx) as ctx:
+        def run(sets, K, want_S, want_irf, want_fevd):
+            Lb, Rb, Ab, Qb = sets[:4]
+            return ctx.signirf_batch_host(Lb, Ab, Qb, Rb, H, rs, M, K, seed=seed, sd=_rep(sd, Lb.shape[0]), named=nm, cum=cum,
+                                          want_S=want_S, want_irf=want_irf, want_fevd=want_fevd)
         none = "no candidate satisfied the restrictions: accepted share 0 of {} candidates{}"
+        fit = (Lam[None], R[None], A[None], Q[None])
         if keep is None:                                  # count first, then keep them all: the same candidates, exactly
-            n = int(run(Lam[None], A[None], Q[None], R[None], 1, False, False, False)["n_accept"][0])
+            n = int(run(fit, 1, False, False, False)["n_accept"][0])
             if n == 0:
                 raise ValueError(none.format(M, ""))
-            o = run(Lam[None], A[None], Q[None], R[None], n, True, True, fevd)
+            o = run(fit, n, True, True, fevd)
         else:
-            o = run(Lam[None], A[None], Q[None], R[None], int(keep), True, True, fevd)
+            o = run(fit, int(keep), True, True, fevd)
             n = int(o["n_accept"][0])
             if n == 0:
                 raise ValueError(none.format(M, ""))
         nk = min(n, o["cand"].shape[1])
         bands = without = None
         if qs is not None:
-            rp = m.replicates["params"]
-            ob = run(rp["Lam"], rp["A"], rp["Q"], rp["R"], int(keep) if keep is not None else 1, False, True, False)
+            ob = run(_replicate_sets(m), int(keep) if keep is not None else 1, False, True, False)
             got = ob["cand"] >= 0
             if not got.any():
                 raise ValueError(none.format(M, " in any replicate"))
             pooled = np.ascontiguousarray(ob["irf"][got])        # [draws, r, H, N]
             bands = ctx.quantile_bands_host(pooled.reshape(pooled.shape[0], -1), qs).reshape(qs.size, r, H, N)
             without = int((ob["n_accept"] == 0).sum())
-    finally:
-        if own:
-            ctx.close()
     out = dict(cols=cols, irf=np.ascontiguousarray(o["irf"][0, :nk].transpose(0, 3, 2, 1)),
                fevd=None if o["fevd"] is None else np.ascontiguousarray(o["fevd"][0, :nk].transpose(0, 3, 2, 1)),
                impact=o["S"][0, :nk].copy(), accepted_share=n / M, candidates_used=M, candidate_index=o["cand"][0, :nk].copy())
-    if bands is not None:
-        out["quantiles"] = qs
-        out["bands"] = np.ascontiguousarray(bands.transpose(0, 3, 2, 1))
-        out["replicates_without_a_draw"] = without
-    return out
+    return _with_bands(out, qs, bands=None if bands is None else np.ascontiguousarray(bands.transpose(0, 3, 2, 1)),
+                       replicates_without_a_draw=without)
 
 
 _QUANTILE_MAX_DRAWS = 16384          # dfm_quantile_bands: draws per call, at most
@@ -1006,28 +991,18 @@ def structural_irf_proxy(m: DFMModel, H: int, instrument, *, norm, draws: int = 
     if D < 0:
         raise ValueError("draws must be >= 0")
     _structural_checks(m)
-    qs = None
-    if quantiles is not None:
-        if D < 1:
-            raise ValueError("quantile bands need draws >= 1")
-        qs = np.atleast_1d(np.asarray(quantiles, dtype=np.float64))
-        if qs.size < 1 or not np.all((qs > 0.0) & (qs <= 1.0)):
-            raise ValueError("quantiles must lie in (0, 1]")
+    if quantiles is not None and D < 1:
+        raise ValueError("quantile bands need draws >= 1")
+    qs = _quantile_arg(quantiles)
     if parameter_draws and getattr(m, "replicates", None) is None:
         raise ValueError("parameter draws need bootstrap replicates: estimate(m, Parametric(), nrep=...) first")
     nrep = m.replicates["params"]["Lam"].shape[0] if parameter_draws else 1
     if qs is not None and nrep * D > _QUANTILE_MAX_DRAWS:
         raise ValueError(f"quantile bands pool replicates x draws = {nrep} x {D} draws; at most {_QUANTILE_MAX_DRAWS} fit one call")
-    ep = m.em_params
-    Lam, R, Q = ep["Lam"], ep["R"], ep["Q"]
-    A = ep["Avar"] if "Avar" in ep else ep["A"]
-    N, r = Lam.shape
+    prm, cols, z, _, sd = _plain_fit(m, m.lastperiod, "structural_irf_proxy", "(estimate_ar_idio?)")
+    A = prm[2]
+    N, r = prm[0].shape
     p = A.shape[1] // r
-    cols, z, _, sd = _forecast_inputs(m, m.lastperiod)
-    if N != cols.size:
-        raise ValueError("m.em_params does not match the model's series (was the model changed after estimate?)")
-    if np.any(np.nan_to_num(np.asarray(m.uar_coef, dtype=np.float64)[cols]) != 0.0):
-        raise ValueError("structural_irf_proxy has no AR idiosyncratic terms: the model carries uar_coef (estimate_ar_idio?)")
     inst = np.asarray(instrument, dtype=np.float64).reshape(-1)
     if inst.size != m.data.shape[0]:
         raise ValueError(f"the instrument must have one entry per row of m.data ({m.data.shape[0]}), NaN where it does not exist")
@@ -1040,33 +1015,27 @@ def structural_irf_proxy(m: DFMModel, H: int, instrument, *, norm, draws: int = 
     if not 1 <= L <= n:
         raise ValueError(f"block must lie in 1..{n} (the usable periods)")
     nrm = int(_to_cols(norm, cols, "norm")[0])
-    cum = None
-    if cumulate is not None:
-        cum = np.zeros(N, dtype=np.int32)
-        cum[_to_cols(cumulate, cols, "cumulate")] = 1
+    cum = _cumulate_arg(cumulate, cols)
     from ._lib import DfmError
-    ctx, own = _own(ctx)
-    try:
-        def run(Lb, Rb, Ab, Qb, m0, P0b, Dd, want_fevd, want_shock):
-            B = Lb.shape[0]
-            rep = lambda a: np.ascontiguousarray(np.broadcast_to(a, (B,) + a.shape))
-            call = lambda sq: ctx.proxyirf_batch_host(
-                rep(z), Lb, Rb, Ab, Qb, m0, P0b, H, zi, nrm, draws=Dd, block=L, seed=seed, sd=rep(sd), cum=cum,
+    with _device(ctx) as ctx:
+        def run(sets, Dd, want_fevd, want_shock):
+            B = sets[0].shape[0]
+            call = lambda singular_q=False: ctx.proxyirf_batch_host(
+                _rep(z, B), *sets, H, zi, nrm, draws=Dd, block=L, seed=seed, sd=_rep(sd, B), cum=cum,
                 unit_effect=unit_effect, want_fevd=want_fevd, want_shock=want_shock, may_have_missing=bool(np.isnan(z).any()),
-                singular_q=sq)
+                singular_q=singular_q)
             try:
                 return _numeric_retry(call)
-            except DfmError as err:
+            except DfmError as err:                 # the covariance form failed too: say what the identification needs
                 if err.code != -5:
                     raise
                 text = str(err).split(": ", 2)[-1]
                 raise DfmError(err.code, f"{text}; identification by an instrument needs Q positive definite") from None
-        o = run(Lam[None], R[None], A[None], Q[None], ep["mu0"][None], ep["P0"][None], 0 if parameter_draws else D, fevd, True)
+        o = run(_one(prm), 0 if parameter_draws else D, fevd, True)
         bands = None
         if qs is not None:
             if parameter_draws:
-                rp = m.replicates["params"]
-                pooled = run(rp["Lam"], rp["R"], rp["A"], rp["Q"], rp["mu0"], rp["P0"], D, False, False)["irf"][:, 1:]
+                pooled = run(_replicate_sets(m), D, False, False)["irf"][:, 1:]
             else:
                 pooled = o["irf"][:, 1:]
             pooled = pooled.reshape(-1, H * N)
@@ -1074,9 +1043,6 @@ def structural_irf_proxy(m: DFMModel, H: int, instrument, *, norm, draws: int = 
             if pooled.shape[0] == 0:
                 raise ValueError("no block draw gave a finite response")
             bands = ctx.quantile_bands_host(pooled, qs).reshape(qs.size, H, N)
-    finally:
-        if own:
-            ctx.close()
     f = o["f"][0]
     eta = f[p:].copy()
     for j in range(p):
@@ -1089,10 +1055,7 @@ def structural_irf_proxy(m: DFMModel, H: int, instrument, *, norm, draws: int = 
     out = dict(cols=cols, irf=np.ascontiguousarray(o["irf"][0, 0].T),
                fevd=None if o["fevd"] is None else np.ascontiguousarray(o["fevd"][0, 0].T), impact=o["impact"][0, 0].copy(),
                relevance=float(o["rel"][0, 0]), shock=o["shock"][0].copy(), first_stage_F=float(F))
-    if bands is not None:
-        out["quantiles"] = qs
-        out["bands"] = np.ascontiguousarray(bands.transpose(0, 2, 1))
-    return out
+    return _with_bands(out, qs, bands=None if bands is None else np.ascontiguousarray(bands.transpose(0, 2, 1)))
 
 
 def historical_decomposition(m: DFMModel, *, named=None, through: Optional[int] = None, ctx=None) -> dict:
@@ -1110,27 +1073,12 @@ def historical_decomposition(m: DFMModel, *, named=None, through: Optional[int] 
       loglik         log-likelihood of the observed cells
     AR-idiosyncratic and mixed-frequency fits are out of scope.  `m` is not modified."""
     _structural_checks(m)
-    through = m.lastperiod if through is None else int(through)
-    if not (m.lastperiod <= through <= m.T):
-        raise ValueError(f"through must lie in lastperiod..T ({m.lastperiod}..{m.T})")
-    ep = m.em_params
-    Lam, R, Q = ep["Lam"], ep["R"], ep["Q"]
-    A = ep["Avar"] if "Avar" in ep else ep["A"]
-    r = Lam.shape[1]
-    cols, z, _, sd = _forecast_inputs(m, through)
-    if Lam.shape[0] != cols.size:
-        raise ValueError("m.em_params does not match the model's series (was the model changed after estimate?)")
-    nm = None if named is None else _to_cols(named, cols, "named")
-    if nm is not None and (nm.size != r or np.unique(nm).size != r):
-        raise ValueError(f"named must be {r} distinct series")
-    ctx, own = _own(ctx)
-    try:
-        o = _numeric_retry(lambda sq: ctx.histdecomp_batch_host(
-            z[None], Lam[None], R[None], A[None], Q[None], ep["mu0"][None], ep["P0"][None], sd=sd[None], named=nm,
-            may_have_missing=bool(np.isnan(z).any()), singular_q=sq))
-    finally:
-        if own:
-            ctx.close()
+    through = _through_arg(m, through)
+    prm, cols, z, _, sd = _plain_fit(m, through)
+    nm = _named_arg(named, cols, prm[0].shape[1])
+    with _device(ctx) as ctx:
+        o = _numeric_retry(lambda singular_q=False: ctx.histdecomp_batch_host(
+            z[None], *_one(prm), sd=sd[None], named=nm, may_have_missing=bool(np.isnan(z).any()), singular_q=singular_q))
     return dict(rows=np.arange(m.initperiod, through + 1), cols=cols,
                 contributions=np.ascontiguousarray(o["hd"][0].transpose(1, 2, 0)), shocks=o["shocks"][0], factor=o["f"][0],
                 loglik=float(o["loglik"][0]))
@@ -1160,50 +1108,21 @@ def draw_paths(m: DFMModel, ndraws: int, H: int = 0, *, through: Optional[int] =
         raise ValueError("H must be >= 0")
     if first_draw < 0:
         raise ValueError("first_draw must be >= 0")
-    if m.em_params is None:
-        raise ValueError("the model has not been estimated: run estimate(m, Parametric()) first")
+    _need_fit(m)
     if m.nfac_o != 0:
         raise ValueError("draw_paths needs nfac_o = 0 (observed factors have no draws here)")
-    through = m.lastperiod if through is None else int(through)
-    if not (m.lastperiod <= through <= m.T):
-        raise ValueError(f"through must lie in lastperiod..T ({m.lastperiod}..{m.T})")
+    through = _through_arg(m, through)
     if parameter_draws and getattr(m, "replicates", None) is None:
         raise ValueError("parameter draws need bootstrap replicates: estimate(m, Parametric(), nrep=...) first")
-    ep = m.em_params
-    Lam, R, Q = ep["Lam"], ep["R"], ep["Q"]
-    A = ep["Avar"] if "Avar" in ep else ep["A"]
-    mu0, P0 = ep["mu0"], ep["P0"]
-    cols, z, mu, sd = _forecast_inputs(m, through)
-    if Lam.shape[0] != cols.size:
-        raise ValueError("m.em_params does not match the model's series (was the model changed after estimate?)")
-    if np.any(np.nan_to_num(np.asarray(m.uar_coef, dtype=np.float64)[cols]) != 0.0):
-        raise ValueError("draw_paths has no AR idiosyncratic terms: the model carries uar_coef -- draw_paths_ar_idio draws from it")
-    if z.shape[0] < A.shape[1] // Lam.shape[1]:
+    prm, cols, z, mu, sd = _plain_fit(m, through, "draw_paths", "-- draw_paths_ar_idio draws from it")
+    if z.shape[0] < prm[2].shape[1] // prm[0].shape[1]:
         raise ValueError("the window is shorter than the number of factor lags")
-    from ._lib import DfmError
-    ctx, own = _own(ctx)
-    try:
-        def run(Lb, Rb, Ab, Qb, m0, P0b):
-            B = Lb.shape[0]
-            rep = lambda a: np.ascontiguousarray(np.broadcast_to(a, (B,) + a.shape))
-            args = (rep(z), Lb, Rb, Ab, Qb, m0, P0b, ndraws, H)
-            kw = dict(seed=int(seed), first_draw=first_draw, mean=rep(mu), sd=rep(sd), may_have_missing=bool(np.isnan(z).any()))
-            try:
-                return ctx.simsmooth_batch_host(*args, **kw)
-            except DfmError as err:                 # the information form inverts Q: as estimate(), retry in covariance form
-                if err.code != -5:
-                    raise
-                return ctx.simsmooth_batch_host(*args, singular_q=True, **kw)
-        if parameter_draws:
-            rp = m.replicates["params"]
-            o = run(rp["Lam"], rp["R"], rp["A"], rp["Q"], rp["mu0"], rp["P0"])
-            factor, x = o["f"], o["x"]
-        else:
-            o = run(Lam[None], R[None], A[None], Q[None], mu0[None], P0[None])
-            factor, x = o["f"][0], o["x"][0]
-    finally:
-        if own:
-            ctx.close()
+    sets = _replicate_sets(m) if parameter_draws else _one(prm)
+    B = sets[0].shape[0]
+    kw = dict(seed=int(seed), first_draw=first_draw, mean=_rep(mu, B), sd=_rep(sd, B), may_have_missing=bool(np.isnan(z).any()))
+    with _device(ctx) as ctx:                       # the information form inverts Q: as estimate(), retry in covariance form
+        o = _numeric_retry(lambda **sq: ctx.simsmooth_batch_host(_rep(z, B), *sets, ndraws, H, **sq, **kw))
+    factor, x = (o["f"], o["x"]) if parameter_draws else (o["f"][0], o["x"][0])
     xr = m.data[m.initperiod - 1:through, :][:, cols]                  # observed cells: the data itself, not mean + sd z
     obs = ~np.isnan(xr)
     x[..., :xr.shape[0], :][..., obs] = xr[obs]
@@ -1224,24 +1143,15 @@ def simulate(m: DFMModel, ndraws: int, *, seed: int = 20160415, masked: bool = T
     ndraws = int(ndraws)
     if ndraws < 1:
         raise ValueError("ndraws must be >= 1")
-    if m.em_params is None:
-        raise ValueError("the model has not been estimated: run estimate(m, Parametric()) first")
+    _need_fit(m)
     if m.nfac_o != 0:
         raise ValueError("simulate needs nfac_o = 0 (observed factors have no model to draw from)")
-    ep = m.em_params
-    A = ep["Avar"] if "Avar" in ep else ep["A"]
-    cols, z, mu, sd = _forecast_inputs(m, m.lastperiod)
-    if ep["Lam"].shape[0] != cols.size:
-        raise ValueError("m.em_params does not match the model's series (was the model changed after estimate?)")
-    if z.shape[0] < A.shape[1] // ep["Lam"].shape[1]:
+    prm, cols, z, mu, sd = _plain_fit(m, m.lastperiod)
+    if z.shape[0] < prm[2].shape[1] // prm[0].shape[1]:
         raise ValueError("the window is shorter than the number of factor lags")
-    ctx, own = _own(ctx)
-    try:
-        o = ctx.simulate_batch_host(ep["Lam"][None], ep["R"][None], A[None], ep["Q"][None], ep["mu0"][None], ep["P0"][None], ndraws,
-                                    T=z.shape[0], mask_panel=z[None] if masked and np.isnan(z).any() else None, seed=int(seed))
-    finally:
-        if own:
-            ctx.close()
+    with _device(ctx) as ctx:
+        o = ctx.simulate_batch_host(*_one(prm), ndraws, T=z.shape[0], mask_panel=z[None] if masked and np.isnan(z).any() else None,
+                                    seed=int(seed))
     return dict(rows=np.arange(m.initperiod, m.lastperiod + 1), cols=cols, x=mu + sd * o["x"][0], factor=o["f"][0])
 
 
@@ -1269,62 +1179,65 @@ def estimate_bayesian(m: DFMModel, ndraws: int, *, chains: int = 4, burn: int = 
     ndraws, chains, burn, thin = int(ndraws), int(chains), int(burn), int(thin)
     if ndraws < 1 or chains < 1 or burn < 0 or thin < 1:
         raise ValueError("ndraws >= 1, chains >= 1, burn >= 0 and thin >= 1 are required")
-    if m.em_params is None:
-        raise ValueError("the model has not been estimated: run estimate(m, Parametric()) first")
+    _need_fit(m)
     if m.nfac_o != 0:
         raise ValueError("estimate_bayesian needs nfac_o = 0 (observed factors have no draws here)")
-    qs = None
-    if quantiles is not None:
-        qs = np.atleast_1d(np.asarray(quantiles, dtype=np.float64))
-        if qs.size < 1 or not np.all((qs > 0.0) & (qs <= 1.0)):
-            raise ValueError("quantiles must lie in (0, 1]")
-    ep = m.em_params
-    Lam, R, Q = ep["Lam"], ep["R"], ep["Q"]
-    A = ep["Avar"] if "Avar" in ep else ep["A"]
-    mu0, P0 = ep["mu0"], ep["P0"]
-    r = Lam.shape[1]
-    p = A.shape[1] // r
-    cols, z, mu, sd = _forecast_inputs(m, m.lastperiod)
-    if Lam.shape[0] != cols.size:
-        raise ValueError("m.em_params does not match the model's series (was the model changed after estimate?)")
-    if np.any(np.nan_to_num(np.asarray(m.uar_coef, dtype=np.float64)[cols]) != 0.0):
-        raise ValueError("estimate_bayesian has no AR idiosyncratic terms: the model carries uar_coef (estimate_bayesian_ar_idio?)")
+    qs = _quantile_arg(quantiles)
+    prm, cols, z, mu, sd = _plain_fit(m, m.lastperiod, "estimate_bayesian", "(estimate_bayesian_ar_idio?)")
+    r = prm[0].shape[1]
+    p = prm[2].shape[1] // r
     if z.shape[0] <= p:
         raise ValueError("the window is not longer than the number of factor lags")
     pr = bayes.check_prior(prior, r, p, chains)
+    keep = ("Lam", "R", "A", "Q", "f")
+    d = _gibbs_chains(ctx, "gibbs_batch_host", z, prm, pr, chains, ndraws, burn, thin, seed, keep)
+    K = chains * ndraws
+    params = dict(Lam=_pooled(d["Lam"]), R=_pooled(d["R"]), A=_pooled(d["A"]), Q=_pooled(d["Q"]), mu0=_rep(prm[4], K), P0=_rep(prm[5], K))
+    return _bayes_summary(d, params, np.arange(m.initperiod, m.lastperiod + 1), cols, dict(R=d["R"] * sd ** 2), ("R",), mu, sd, pr,
+                          qs, keep_factors)
+
+
+def _gibbs_chains(ctx, entry, x, start, pr, chains, ndraws, burn, thin, seed, keep):
+    """`chains` chains of the Gibbs sampler behind `entry` (a host entry of the context), all started at `start` on panel x: the
+    kept draws, name -> [chains, ndraws, ...].  The information form inverts Q: as estimate(), a numeric failure is retried in
+    covariance form -- not the sampler's own failures (a Cholesky of its regressions, the Gamma cap), which that form cannot cure."""
     n_sweeps = burn + (ndraws - 1) * thin + 1
-    from ._lib import DfmError
-    ctx, own = _own(ctx)
-    try:
-        rep = lambda a: np.ascontiguousarray(np.broadcast_to(a, (chains,) + a.shape))
-        args = (rep(z), rep(Lam), rep(R), rep(A), rep(Q), rep(mu0), rep(P0), pr, n_sweeps)
-        kw = dict(burn=burn, thin=thin, seed=int(seed), keep=("Lam", "R", "A", "Q", "f"), may_have_missing=bool(np.isnan(z).any()))
-        try:
-            _, d = ctx.gibbs_batch_host(*args, **kw)
-        except DfmError as err:                     # the information form inverts Q: as estimate(), retry in covariance form --
-            if err.code != -5 or "Gibbs sampler" in str(err):   # not for the sampler's own failures (a Cholesky of its
-                raise                                           # regressions, the Gamma cap), which that form cannot cure
-            _, d = ctx.gibbs_batch_host(*args, singular_q=True, **kw)
-    finally:
-        if own:
-            ctx.close()
-    flat = lambda a: a.reshape((chains * ndraws,) + a.shape[2:])
-    tile = lambda a: np.ascontiguousarray(np.broadcast_to(a, (chains * ndraws,) + a.shape))
-    params = dict(Lam=flat(d["Lam"]), R=flat(d["R"]), A=flat(d["A"]), Q=flat(d["Q"]), mu0=tile(mu0), P0=tile(P0))
-    Rd = d["R"] * sd ** 2                                               # [chains, ndraws, N], data units
-    last = bayes.common_component(d["Lam"], d["f"], mu, sd, rows=[z.shape[0] - 1])[:, :, 0, :]
-    out = dict(params=params, rows=np.arange(m.initperiod, m.lastperiod + 1), cols=cols, R_mean=Rd.mean(axis=(0, 1)),
-               rhat_R=bayes.split_rhat(Rd), rhat_common=bayes.split_rhat(last), prior=pr, chains=chains, ndraws=ndraws)
+    args = (_rep(x, chains), *[_rep(a, chains) for a in start], pr, n_sweeps)
+    kw = dict(burn=burn, thin=thin, seed=int(seed), keep=keep, may_have_missing=bool(np.isnan(x).any()))
+    with _device(ctx) as ctx:
+        return _numeric_retry(lambda **sq: getattr(ctx, entry)(*args, **sq, **kw), unless=lambda err: "Gibbs sampler" in str(err))[1]
+
+
+def _pooled(a):
+    """Draws [chains, ndraws, ...] as [chains x ndraws, ...], chain-major."""
+    return a.reshape((a.shape[0] * a.shape[1],) + a.shape[2:])
+
+
+def _bayes_summary(d, params, rows, cols, stats, checked, mean, sd, pr, qs, keep_factors, mu_f=None):
+    """The returned dict of estimate_bayesian / estimate_bayesian_ar_idio from the chains' draws d (name -> [chains, ndraws, ...]).
+    stats: name -> draws in data units, each summarised as <name>_mean; those named in `checked` also as rhat_<name> and, with qs,
+    <name>_bands.  The common component is mean + sd lam_i' f_t (rhat_common: of the last period).  mu_f (the AR model): returned,
+    and added to the factors."""
+    from . import bayes
+    chains, ndraws = d["f"].shape[:2]
+    last = bayes.common_component(d["Lam"], d["f"], mean, sd, rows=[d["f"].shape[2] - 1])[:, :, 0, :]
+    out = dict(params=params, rows=rows, cols=cols)
+    out.update({k + "_mean": a.mean(axis=(0, 1)) for k, a in stats.items()})
+    out.update({"rhat_" + k: bayes.split_rhat(stats[k]) for k in checked})
+    out.update(rhat_common=bayes.split_rhat(last), prior=pr, chains=chains, ndraws=ndraws)
+    if mu_f is not None:
+        out["mu_f"] = mu_f
     if qs is None:
-        out["common_mean"] = np.mean([bayes.common_component(d["Lam"][c], d["f"][c], mu, sd).mean(axis=0) for c in range(chains)], axis=0)
+        out["common_mean"] = np.mean([bayes.common_component(d["Lam"][c], d["f"][c], mean, sd).mean(axis=0) for c in range(chains)],
+                                     axis=0)
     else:
-        cc = flat(bayes.common_component(d["Lam"], d["f"], mu, sd))
+        cc = _pooled(bayes.common_component(d["Lam"], d["f"], mean, sd))
         out["common_mean"] = cc.mean(axis=0)
         out["quantiles"] = qs
-        out["R_bands"] = np.quantile(flat(Rd), qs, axis=0)
+        out.update({k + "_bands": np.quantile(_pooled(stats[k]), qs, axis=0) for k in checked})
         out["common_bands"] = np.quantile(cc, qs, axis=0)
     if keep_factors:
-        out["factor"] = flat(d["f"])
+        out["factor"] = _pooled(d["f"]) if mu_f is None else _pooled(d["f"]) + mu_f
     return out
 
 
@@ -1347,10 +1260,33 @@ def news(m: DFMModel, old, new, targets, *, groups=None, quantiles=None, ctx=Non
     `quantiles` (needs m.replicates from estimate(..., nrep=...)): every bootstrap parameter set runs in the same batched call,
     and nearest-rank bands over the replicates give impact_bands [nq, G, cols] and revision_bands [nq, G].  `m` is not
     modified."""
-    if m.em_params is None:
-        raise ValueError("the model has not been estimated: run estimate(m, Parametric()) first")
+    _need_fit(m)
     if m.nfac_o != 0:
         raise ValueError("news needs nfac_o = 0 (observed factors have no news here)")
+    xo, xn, last = _vintages(m, old, new)
+    if np.any(~np.isnan(xo) & np.isnan(xn)):
+        raise ValueError("vintage: a cell observed in the old vintage is missing in the new one")
+    tg = _target_list(targets)
+    prm, cols, _, mu, sd = _plain_fit(m, m.lastperiod)
+    pos = {int(c): j for j, c in enumerate(cols)}
+    pairs = _news_targets(m, tg, pos, "estimate() used")
+    gsum = _news_groups(groups, pos, "estimate() used")
+    _no_ar_terms(m, cols, "news", "(news_ar_idio is the call for it)")
+    qs = _quantile_arg(quantiles, (getattr(m, "replicates", None) is None, _NEED_REPLICATES))
+    zo = (xo[m.initperiod - 1:, cols] - mu) / sd
+    zn = (xn[m.initperiod - 1:, cols] - mu) / sd
+    sets = _one(prm)
+    if qs is not None:                              # replicate 0: the point estimate; 1 ..: the bootstrap parameter sets
+        sets = [np.concatenate([a, b]) for a, b in zip(sets, _replicate_sets(m))]
+    B = sets[0].shape[0]
+    o, bands = _news_call(ctx, "news_batch_host", (_rep(zo, B), _rep(zn, B), *sets, pairs),
+                          dict(mean=_rep(mu, B), sd=_rep(sd, B), may_have_missing=bool(np.isnan(zn).any())), qs)
+    return _news_result(o, np.arange(m.initperiod, last + 1), cols, {}, gsum, qs, bands)
+
+
+def _vintages(m: DFMModel, old, new):
+    """The two vintages of news / news_ar_idio -- each an array shaped like m.data, or a 1-based row meaning "m.data through it" --
+    as float64 arrays padded with NaN rows to the same number of rows: (old, new, that number)."""
     ncol = m.data.shape[1]
 
     def vintage(v, name):
@@ -1366,76 +1302,64 @@ def news(m: DFMModel, old, new, targets, *, groups=None, quantiles=None, ctx=Non
     xo, xn = vintage(old, "old"), vintage(new, "new")
     last = max(xo.shape[0], xn.shape[0])
     padr = lambda x: np.vstack([x, np.full((last - x.shape[0], ncol), np.nan)])
-    xo, xn = padr(xo), padr(xn)
-    if np.any(~np.isnan(xo) & np.isnan(xn)):
-        raise ValueError("vintage: a cell observed in the old vintage is missing in the new one")
+    return padr(xo), padr(xn), last
+
+
+def _target_list(targets):
+    """`targets` as a list with at least one entry, or ValueError."""
     tg = list(targets) if targets is not None else []
     if len(tg) < 1:
         raise ValueError("at least one target (column, period) is needed")
-    ep = m.em_params
-    Lam, R, Q = ep["Lam"], ep["R"], ep["Q"]
-    A = ep["Avar"] if "Avar" in ep else ep["A"]
-    mu0, P0 = ep["mu0"], ep["P0"]
-    cols, _, mu, sd = _forecast_inputs(m, m.lastperiod)
-    if Lam.shape[0] != cols.size:
-        raise ValueError("m.em_params does not match the model's series (was the model changed after estimate?)")
-    pos = {int(c): j for j, c in enumerate(cols)}
-    tt, ti = [], []
+    return tg
+
+
+def _news_targets(m: DFMModel, tg, pos, used, q=0):
+    """(column of m.data, 1-based period) targets as (window row, position) pairs; pos: column -> position among the series `used`
+    (the message's words for them); q: the window's first q rows are conditioning values and no targets."""
+    pairs = []
     for c, per in tg:
         if int(c) not in pos:
-            raise ValueError(f"target column {c} is not one of the series estimate() used")
-        if int(per) < m.initperiod:
-            raise ValueError(f"target period {per} lies before initperiod ({m.initperiod})")
-        tt.append(int(per) - m.initperiod)
-        ti.append(pos[int(c)])
-    gsum = None
-    if groups is not None:
-        gsum = {}
-        for name, gc in dict(groups).items():
-            idx = [pos.get(int(c), -1) for c in np.atleast_1d(gc)]
-            if len(idx) < 1 or min(idx) < 0:
-                raise ValueError(f"groups[{name!r}] must list columns estimate() used")
-            gsum[name] = np.asarray(idx)
-    if np.any(np.nan_to_num(np.asarray(m.uar_coef, dtype=np.float64)[cols]) != 0.0):
-        raise ValueError("news has no AR idiosyncratic terms: the model carries uar_coef (news_ar_idio is the call for it)")
-    qs = None
-    if quantiles is not None:
-        qs = np.atleast_1d(np.asarray(quantiles, dtype=np.float64))
-        if getattr(m, "replicates", None) is None:
-            raise ValueError("quantile bands need bootstrap replicates: estimate(m, Parametric(), nrep=...) first")
-        if qs.size < 1 or not np.all((qs > 0.0) & (qs <= 1.0)):
-            raise ValueError("quantiles must lie in (0, 1]")
-    zo = (xo[m.initperiod - 1:, cols] - mu) / sd
-    zn = (xn[m.initperiod - 1:, cols] - mu) / sd
-    pairs = list(zip(tt, ti))
-    from ._lib import DfmError
-    ctx, own = _own(ctx)
-    try:
-        prm = [Lam[None], R[None], A[None], Q[None], mu0[None], P0[None]]
-        if qs is not None:                          # replicate 0: the point estimate; 1 ..: the bootstrap parameter sets
-            rp = m.replicates["params"]
-            prm = [np.concatenate([a, rp[k]]) for a, k in zip(prm, ("Lam", "R", "A", "Q", "mu0", "P0"))]
-        B = prm[0].shape[0]
-        rep = lambda a: np.ascontiguousarray(np.broadcast_to(a, (B,) + a.shape))
-        args = (rep(zo), rep(zn), *prm, pairs)
-        kw = dict(mean=rep(mu), sd=rep(sd), may_have_missing=bool(np.isnan(zn).any()))
-        try:
-            o = ctx.news_batch_host(*args, **kw)
-        except DfmError as err:                     # the information form inverts Q: as estimate(), retry in covariance form
-            if err.code != -5:
-                raise
-            o = ctx.news_batch_host(*args, singular_q=True, **kw)
+            raise ValueError(f"target column {c} is not one of the series {used}")
+        if int(per) < m.initperiod + q:
+            raise ValueError(f"target period {per} lies before initperiod ({m.initperiod})" if q == 0 else
+                             f"target period {per} lies before initperiod + n_uarlag ({m.initperiod + q}): the first n_uarlag "
+                             "window rows are conditioning values")
+        pairs.append((int(per) - m.initperiod, pos[int(c)]))
+    return pairs
+
+
+def _news_groups(groups, pos, used):
+    """`groups` (name -> columns of m.data; None stays None) as name -> positions among the series `used`."""
+    if groups is None:
+        return None
+    gsum = {}
+    for name, gc in dict(groups).items():
+        idx = [pos.get(int(c), -1) for c in np.atleast_1d(gc)]
+        if len(idx) < 1 or min(idx) < 0:
+            raise ValueError(f"groups[{name!r}] must list columns {used}")
+        gsum[name] = np.asarray(idx)
+    return gsum
+
+
+def _news_call(ctx, entry, args, kw, qs):
+    """One call of the news entry `entry` (a host entry of the context) with replicate 0 the point estimate -- the information form
+    inverts Q: as estimate(), retried in covariance form -- and, with qs, the nearest-rank bands of the impacts and of the revision
+    over the replicates behind it: (outputs, (impact_bands, revision_bands) or None)."""
+    with _device(ctx) as ctx:
+        o = _numeric_retry(lambda **sq: getattr(ctx, entry)(*args, **sq, **kw))
         bands = None
         if qs is not None:
             bands = (ctx.quantile_bands_host(o["impact"][1:], qs),
                      ctx.quantile_bands_host(o["yhat"][1:, 2] - o["yhat"][1:, 0], qs))
-    finally:
-        if own:
-            ctx.close()
+    return o, bands
+
+
+def _news_result(o, rows, cols, extra, gsum, qs, bands):
+    """The returned dict of news / news_ar_idio from replicate 0 of the outputs; `extra`: the entries that follow `weight`."""
     y = o["yhat"][0]
-    out = dict(rows=np.arange(m.initperiod, last + 1), cols=cols, y_old=y[0], y_rev=y[1], y_new=y[2], revision=y[2] - y[0],
+    out = dict(rows=rows, cols=cols, y_old=y[0], y_rev=y[1], y_new=y[2], revision=y[2] - y[0],
                data_revision=y[1] - y[0], news_effect=y[2] - y[1], impact=o["impact"][0], news=o["news"][0],
-               weight=o["weight"][0])
+               weight=o["weight"][0], **extra)
     if gsum is not None:
         out["groups"] = {name: out["impact"][:, idx].sum(axis=1) for name, idx in gsum.items()}
     if bands is not None:
@@ -1620,7 +1544,6 @@ def estimate_mixed_frequency(x, weights, r: int, p: int, *, max_em_iter: int = 5
     Avar [r, r p], Q, mu0, P0 (standardised units), W, mean, sd, loglik_path (NaN past convergence), iters, f_smooth [T, r],
     start (the parameters the EM started from); with nrep > 0 also `replicates`: parametric-bootstrap panels drawn from the fit
     with the panel's missing pattern and re-estimated from the point estimate in ONE batched call (params, loglik_path, iters)."""
-    from ._lib import DfmError
     x = np.asarray(x, dtype=np.float64)
     T, N = x.shape
     W = mf_weights(weights, N)
@@ -1630,8 +1553,7 @@ def estimate_mixed_frequency(x, weights, r: int, p: int, *, max_em_iter: int = 5
     z, sd = standardize_data(x)
     sd = np.asarray(sd).reshape(N)
     free = None if blocks is None else _mf_free(blocks, N, int(r))
-    ctx, own = _own(ctx)
-    try:
+    with _device(ctx) as ctx:
         start = _mf_start(ctx, z, W, int(r), int(p)) if free is None else _mf_blocks_start(ctx, z, W, free, int(p))
         keys = ("Lam", "R", "Avar", "Q", "mu0", "P0")
 
@@ -1641,12 +1563,8 @@ def estimate_mixed_frequency(x, weights, r: int, p: int, *, max_em_iter: int = 5
             if free is not None:
                 args.insert(4, free)
                 em = ctx.em_mf_blocks_batch_host
-            try:
-                return em(*args, max_iter=max_em_iter, tol=tol_em, may_have_missing=True, **kw)
-            except DfmError as err:                 # the information form inverts Q: as estimate(), retry in covariance form
-                if err.code != -5:
-                    raise
-                return em(*args, max_iter=max_em_iter, tol=tol_em, may_have_missing=True, singular_q=True, **kw)
+            # the information form inverts Q: as estimate(), retry in covariance form
+            return _numeric_retry(lambda **sq: em(*args, max_iter=max_em_iter, tol=tol_em, may_have_missing=True, **sq, **kw))
         est, path, iters, f, _ = run(z[None], {k: start[k][None] for k in keys})
         out = {k: est[k][0] for k in keys}
         out.update(W=W, mean=mu, sd=sd, loglik_path=path[0], iters=int(iters[0]), f_smooth=f[0], start=start)
@@ -1666,9 +1584,6 @@ def estimate_mixed_frequency(x, weights, r: int, p: int, *, max_em_iter: int = 5
             panels[:, np.isnan(z)] = np.nan
             rest, rpath, riters, _, _ = run(panels, {k: np.repeat(out[k][None], nrep, axis=0) for k in keys})
             out["replicates"] = dict(params=rest, loglik_path=rpath, iters=riters)
-    finally:
-        if own:
-            ctx.close()
     return out
 
 
@@ -1689,39 +1604,24 @@ def forecast_mixed(fit: dict, x, H: int, quantiles=None, *, ctx=None) -> dict:
     r = fit["Lam"].shape[1]
     if x.ndim != 2 or x.shape[1] != W.shape[0]:
         raise ValueError("x must be [T, N] with the fit's series")
-    qs = None
-    if quantiles is not None:
-        qs = np.atleast_1d(np.asarray(quantiles, dtype=np.float64))
-        if fit.get("replicates") is None:
-            raise ValueError("quantile bands need bootstrap replicates: estimate_mixed_frequency(..., nrep=...) first")
-        if H < 1:
-            raise ValueError("quantile bands need H >= 1")
-        if qs.size < 1 or not np.all((qs > 0.0) & (qs <= 1.0)):
-            raise ValueError("quantiles must lie in (0, 1]")
+    qs = _quantile_arg(quantiles, (fit.get("replicates") is None,
+                                   "quantile bands need bootstrap replicates: estimate_mixed_frequency(..., nrep=...) first"),
+                       (H < 1, "quantile bands need H >= 1"))
     z = (x - mu) / sd
-    ctx, own = _own(ctx)
-    try:
+    with _device(ctx) as ctx:
         def run(ps, **kw):
             B = ps["Lam"].shape[0]
             ex = [_mf_expanded(ps["Lam"][b], W, ps["Avar"][b], ps["Q"][b]) for b in range(B)]
-            rep = lambda a: np.ascontiguousarray(np.broadcast_to(a, (B,) + a.shape))
-            return ctx.forecast_batch_host(rep(z), np.stack([e[0] for e in ex]), ps["R"], np.stack([e[1] for e in ex]),
-                                           np.stack([e[2] for e in ex]), ps["mu0"], ps["P0"], H, mean=rep(mu), sd=rep(sd),
+            return ctx.forecast_batch_host(_rep(z, B), np.stack([e[0] for e in ex]), ps["R"], np.stack([e[1] for e in ex]),
+                                           np.stack([e[2] for e in ex]), ps["mu0"], ps["P0"], H, mean=_rep(mu, B), sd=_rep(sd, B),
                                            may_have_missing=True, singular_q=True, **kw)
         o = run({k: fit[k][None] for k in ("Lam", "R", "Avar", "Q", "mu0", "P0")}, want_P=False)
         bands = None
         if qs is not None:
-            ob = run(fit["replicates"]["params"], want_var=False, want_common=False, want_P=False)
-            bands = ctx.quantile_bands_host(ob["xhat"][:, -H:, :], qs)
-    finally:
-        if own:
-            ctx.close()
+            bands = _horizon_bands(ctx, run(fit["replicates"]["params"], want_var=False, want_common=False, want_P=False), H, qs)
     out = dict(x=o["xhat"][0], x_sd=np.sqrt(o["xvar"][0]), common=o["common"][0], factor=o["f"][0][:, :r],
                loglik=float(o["loglik"][0]))
-    if bands is not None:
-        out["quantiles"] = qs
-        out["bands"] = bands
-    return out
+    return _with_bands(out, qs, bands=bands)
 
 
 def _lagmat(X: np.ndarray, lags) -> np.ndarray:
@@ -1733,13 +1633,6 @@ def _lagmat(X: np.ndarray, lags) -> np.ndarray:
     for k, lag in enumerate(lags):
         out[lag:, nc * k: nc * (k + 1)] = X[: T - lag]
     return out
-
-
-def _own(ctx):
-    if ctx is not None:
-        return ctx, False
-    from .kalman import DfmContext
-    return DfmContext(), True                                           # raises without a HIP device
 
 
 def pca_start(ctx, z: np.ndarray, r: int) -> np.ndarray:
@@ -1762,14 +1655,10 @@ def estimate_factor(m: DFMModel, max_iter: int = 100000000, computeR2: bool = Tr
     z, _ = standardize_data(xdata)                                         # :339
     m.fes.tss = float(np.nansum(z * z))                                    # :342
     m.fes.nobs = int((~np.isnan(z)).sum())                                 # :343
-    ctx, own = _own(ctx)
-    try:
+    with _device(ctx) as ctx:
         F0 = pca_start(ctx, z, r)                                          # :345-348
         o = ctx.als_batch_host(z, F0[None], nt_min=m.nt_min_factor_estimation, max_iter=max_iter, tol=m.tol,
                                want_R2=computeR2)                          # :352-370 (+ :372-380)
-    finally:
-        if own:
-            ctx.close()
     m.factor[m.initperiod - 1:m.lastperiod, :] = o["F"][0]                 # :371
     m.fes.ssr = float(o["ssr"][0])                                         # :366
     if computeR2:
@@ -1793,8 +1682,7 @@ def _estimate_factor_observed(m: DFMModel, max_iter, computeR2, ctx):
     z, _ = standardize_data(m.data[w0:w1, :][:, m.inclcode == 1])          # :335-339
     T, N = z.shape
     m.fes.tss = float(np.nansum(z * z)); m.fes.nobs = int((~np.isnan(z)).sum())
-    ctx, own = _own(ctx)
-    try:
+    with _device(ctx) as ctx:
         res = ctx.ols_batch_host(G, z, want_resid=True)["resid"]           # start: PCA of what g does not explain
         F = pca_start(ctx, res, ru)
         ssr, it = 0.0, 0
@@ -1813,9 +1701,6 @@ def _estimate_factor_observed(m: DFMModel, max_iter, computeR2, ctx):
         if computeR2:                                                      # :372-380
             o = ctx.ols_batch_host(np.hstack([G, F]), z, nt_min=m.nt_min_factor_estimation, want_resid=False)
             m.fes.R2 = np.where(np.isnan(o["beta"][:, 0]), np.nan, 1.0 - o["ssr"] / o["tss"])
-    finally:
-        if own:
-            ctx.close()
     return None
 
 
@@ -1828,8 +1713,7 @@ def estimate_factor_loading(m: DFMModel, *, lam_constr=None, ctx=None):
     Y = m.data[m.initperiod - 1:m.lastperiod, :]
     T, r = F.shape
     X = np.column_stack([F, np.ones(T)])
-    ctx, own = _own(ctx)
-    try:
+    with _device(ctx) as ctx:
         o = ctx.ols_batch_host(X, Y, nt_min=m.nt_min_factorloading_estimation)
         ok = ~np.isnan(o["beta"][:, 0])
         r2 = 1.0 - o["ssr"] / o["tss"]
@@ -1855,9 +1739,6 @@ def estimate_factor_loading(m: DFMModel, *, lam_constr=None, ctx=None):
         hi = np.nonzero(ok & ~(r2 < 0.9999))[0]
         m.uar_coef[hi, :] = 0.0
         m.uar_ser[hi] = 0.0
-    finally:
-        if own:
-            ctx.close()
     return None
 
 
@@ -1870,12 +1751,8 @@ def estimate_var(varm: VARModel, compute_matrices: bool = True, *, ctx=None):
         x = np.column_stack([np.ones(T), x])
     rows_ok = ~np.isnan(x).any(axis=1) & ~np.isnan(yr).any(axis=1)         # the reference drops rows jointly (:455)
     Y = np.where(rows_ok[:, None], yr, np.nan)
-    ctx, own = _own(ctx)
-    try:
+    with _device(ctx) as ctx:
         o = ctx.ols_batch_host(x, Y, nt_min=0)
-    finally:
-        if own:
-            ctx.close()
     K = x.shape[1]
     varm.betahat = o["beta"].T.copy()
     e = o["resid"][rows_ok]
@@ -1905,15 +1782,11 @@ def estimate_nonparametric(m: DFMModel, *, ctx=None, lam_constr_f=None, lam_cons
     """`estimate!(m, NonParametric())` -- dfm_functions.ipynb:530-543."""
     if lam_constr_f is not None or lam_constr_fl is not None:
         raise NotImplementedError("loading constraints are not supported on the HIP path")
-    ctx, own = _own(ctx)
-    try:
+    with _device(ctx) as ctx:
         estimate_factor(m, lam_constr=lam_constr_f, ctx=ctx)
         estimate_factor_loading(m, lam_constr=lam_constr_fl, ctx=ctx)
         m.factor_var_model.y = m.factor
         estimate_var(m.factor_var_model, ctx=ctx)
-    finally:
-        if own:
-            ctx.close()
     return None
 
 
@@ -1940,8 +1813,7 @@ def estimate_factor_numbers(m: DFMModel, nfacs, *, ctx=None, with_aw: bool = Fal
     z, _ = standardize_data(xdata)
     T = z.shape[0]
     tss = float(np.nansum(z * z)); nobs = int((~np.isnan(z)).sum())
-    ctx, own = _own(ctx)
-    try:
+    with _device(ctx) as ctx:
         F0 = pca_start(ctx, z, rmax)                       # scores are nested: run r starts from the first r columns
         o = ctx.als_batch_host(z, np.repeat(F0[None], len(nfacs), axis=0), r_each=nfacs,
                                nt_min=m.nt_min_factor_estimation, tol=m.tol)
@@ -1970,9 +1842,6 @@ def estimate_factor_numbers(m: DFMModel, nfacs, *, ctx=None, with_aw: bool = Fal
                 aw[k - 1, col] = bai_ng_criterion(a["ssr"][b], meta[col][0], meta[col][1], k)
                 ssr_dyn[k - 1, col] = a["ssr"][b]
             out.update(aw_icp=aw, ssr_dynamic=ssr_dyn)
-    finally:
-        if own:
-            ctx.close()
     return out
 
 
@@ -2023,8 +1892,7 @@ def bootstrap_irf_bands(varm: VARModel, H: int, ndraws: int = 10000, quantiles=(
     resid[varm.nlag:] = varm.resid[rows]
     if not varm.withconst:
         raise NotImplementedError("bootstrap_irf_bands needs a VAR with constant (the reference's default)")
-    ctx, own = _own(ctx)
-    try:
+    with _device(ctx) as ctx:
         from .shard import replicate_range
         lo, hi = replicate_range(int(ndraws), world, rank)
         draws = ctx.var_bootstrap_irf_host(y, varm.betahat, resid, varm.nlag, H, hi - lo, seed=seed, first_draw=lo,
@@ -2034,9 +1902,6 @@ def bootstrap_irf_bands(varm: VARModel, H: int, ndraws: int = 10000, quantiles=(
                 raise ValueError("world > 1 needs a gather function")
             draws = np.asarray(gather(draws))
         bands = ctx.quantile_bands_host(draws, np.asarray(quantiles, float))
-    finally:
-        if own:
-            ctx.close()
     return dict(point=impulse_response(varm, range(varm.ns), H), bands=bands, draws=draws)
 
 
@@ -2102,16 +1967,20 @@ def smooth_factors_ar_idio(m: DFMModel, *, ctx=None):
     series (column indices used), inputs (the arrays handed to the library, for the parity test))."""
     inputs, cols, mu_f, _ = _ar_model_inputs(m)
     r, q = m.nfac_u, m.n_uarlag
-    ctx, own = _own(ctx)
-    try:
+    with _device(ctx) as ctx:
         f, P, ll = ctx.ks_pass_ar_batch_host(inputs["x"][None], inputs["Lam"][None], inputs["sig2"][None], inputs["rho"][None],
                                              inputs["Avar"][None], inputs["Q"][None], inputs["mu0"][None], inputs["P0"][None])
-    finally:
-        if own:
-            ctx.close()
     factor = np.full((m.T_all if hasattr(m, "T_all") else m.data.shape[0], r), np.nan)
     factor[m.initperiod - 1 + q:m.lastperiod] = f[0] + mu_f
     return dict(loglik=float(ll[0]), factor=factor, P=P[0], series=cols, inputs=inputs, mu_f=mu_f)
+
+
+def _ar_lags(m: DFMModel, who):
+    """q = n_uarlag, which the post-estimation entries of the AR model take in 1..4; `who` is refused otherwise."""
+    q = int(m.n_uarlag)
+    if not (1 <= q <= 4):
+        raise ValueError(f"{who} needs 1 <= n_uarlag <= 4")
+    return q
 
 
 def _ar_v0(m: DFMModel, cols, c_i, Lam):
@@ -2164,8 +2033,7 @@ def estimate_ar_idio(m: DFMModel, *, max_em_iter: int = 20, tol_em: float = 1e-6
     inputs, cols, mu_f, _ = _ar_model_inputs(m)
     var = m.factor_var_model
     r, p, q = m.nfac_u, var.nlag, m.n_uarlag
-    ctx, own = _own(ctx)
-    try:
+    with _device(ctx) as ctx:
         est, path, iters, f, _ = ctx.em_ar_batch_host(inputs["x"][None], inputs["Lam"][None], inputs["sig2"][None],
                                                       inputs["rho"][None], inputs["Avar"][None], inputs["Q"][None],
                                                       inputs["mu0"][None], inputs["P0"][None], max_iter=max_em_iter, tol=tol_em)
@@ -2182,9 +2050,6 @@ def estimate_ar_idio(m: DFMModel, *, max_em_iter: int = 20, tol_em: float = 1e-6
         _fill_matrices(var)
         if nrep:
             m.replicates_ar = _bootstrap_replicates_ar(ctx, m, inputs["x"], cols, est, nrep, int(seed), max_em_iter, tol_em)
-    finally:
-        if own:
-            ctx.close()
     return path[0, :int(iters[0])].copy()
 
 
@@ -2215,59 +2080,33 @@ def forecast_ar_idio(m: DFMModel, H: int, *, through: Optional[int] = None, para
     H = int(H)
     if H < 0:
         raise ValueError("H must be >= 0")
-    q = int(m.n_uarlag)
-    if not (1 <= q <= 4):
-        raise ValueError("forecast_ar_idio needs 1 <= n_uarlag <= 4")
-    through = m.lastperiod if through is None else int(through)
-    if not (m.lastperiod <= through <= m.T):
-        raise ValueError(f"through must lie in lastperiod..T ({m.lastperiod}..{m.T})")
-    qs = None
-    if quantiles is not None:
-        if params is None:
-            raise ValueError("quantile bands need parameter sets: params=m.replicates_ar['params'] of estimate_ar_idio(nrep=...)")
-        if H < 1:
-            raise ValueError("quantile bands need H >= 1")
-        qs = np.atleast_1d(np.asarray(quantiles, dtype=np.float64))
-        if qs.size < 1 or not np.all((qs > 0.0) & (qs <= 1.0)):
-            raise ValueError("quantiles must lie in (0, 1]")
-    elif params is not None:
+    q = _ar_lags(m, "forecast_ar_idio")
+    through = _through_arg(m, through)
+    if quantiles is not None and params is None:
+        raise ValueError("quantile bands need parameter sets: params=m.replicates_ar['params'] of estimate_ar_idio(nrep=...)")
+    if quantiles is not None and H < 1:
+        raise ValueError("quantile bands need H >= 1")
+    qs = _quantile_arg(quantiles)
+    if qs is None and params is not None:
         raise ValueError("params serve the quantile bands: give quantiles= with them")
     inputs, cols, mu_f, c_i = _ar_model_inputs(m, through)
     sets = None if params is None else _ar_param_sets(inputs, params)
     if sets is not None and sets[0].shape[0] > _QUANTILE_MAX_DRAWS:
         raise ValueError(f"bands need at most {_QUANTILE_MAX_DRAWS} parameter sets")
-    r = m.nfac_u
     v0 = _ar_v0(m, cols, c_i, inputs["Lam"])
     mean = c_i + inputs["Lam"] @ mu_f
     x = inputs["x"]
-    ctx, own = _own(ctx)
-    try:
-        o = ctx.forecast_ar_batch_host(x[None], inputs["Lam"][None], inputs["sig2"][None], inputs["rho"][None],
-                                       inputs["Avar"][None], inputs["Q"][None], inputs["mu0"][None], inputs["P0"][None], H,
-                                       v0=v0[None], mean=mean[None], sd=np.ones((1, cols.size)),
-                                       may_have_missing=bool(np.isnan(x).any()))
-        bands = None
-        if qs is not None:
+    with _device(ctx) as ctx:
+        def run(sets, **kw):
             S = sets[0].shape[0]
-            rep = lambda a: np.ascontiguousarray(np.broadcast_to(a, (S,) + a.shape))
-            ob = ctx.forecast_ar_batch_host(rep(x), *sets, H, v0=rep(v0), mean=rep(mean), sd=np.ones((S, cols.size)), want=(),
-                                            may_have_missing=bool(np.isnan(x).any()))
-            bands = ctx.quantile_bands_host(ob["xhat"][:, -H:, :], qs)
-    finally:
-        if own:
-            ctx.close()
-    il = np.tril_indices(r)                                             # packed lower, row-major (include/dfm_hip.h)
-    Pp = o["P"][0]
-    cov = np.empty((Pp.shape[0], r, r))
-    cov[:, il[0], il[1]] = Pp
-    cov[:, il[1], il[0]] = Pp
+            return ctx.forecast_ar_batch_host(_rep(x, S), *sets, H, v0=_rep(v0, S), mean=_rep(mean, S), sd=np.ones((S, cols.size)),
+                                              **kw, may_have_missing=bool(np.isnan(x).any()))
+        o = run([inputs[k][None] for k in _AR_PARAM_NAMES])
+        bands = None if qs is None else _horizon_bands(ctx, run(sets, want=()), H, qs)
     out = dict(rows=np.arange(m.initperiod + q, through + H + 1), cols=cols, x=o["xhat"][0], x_sd=np.sqrt(o["xvar"][0]),
-               common=o["common"][0], idio=o["idio"][0], factor=o["f"][0] + mu_f, factor_cov=cov, loglik=float(o["loglik"][0]),
-               mu_f=mu_f, inputs=dict(inputs, v0=v0, mean=mean))
-    if bands is not None:
-        out["quantiles"] = qs
-        out["bands"] = bands
-    return out
+               common=o["common"][0], idio=o["idio"][0], factor=o["f"][0] + mu_f, factor_cov=_unpack(o["P"][0], m.nfac_u),
+               loglik=float(o["loglik"][0]), mu_f=mu_f, inputs=dict(inputs, v0=v0, mean=mean))
+    return _with_bands(out, qs, bands=bands)
 
 
 def simulate_ar_idio(m: DFMModel, ndraws: int, *, seed: int = 20160415, masked: bool = True, ctx=None) -> dict:
@@ -2284,21 +2123,15 @@ def simulate_ar_idio(m: DFMModel, ndraws: int, *, seed: int = 20160415, masked: 
     ndraws = int(ndraws)
     if ndraws < 1:
         raise ValueError("ndraws must be >= 1")
-    q = int(m.n_uarlag)
-    if not (1 <= q <= 4):
-        raise ValueError("simulate_ar_idio needs 1 <= n_uarlag <= 4")
+    q = _ar_lags(m, "simulate_ar_idio")
     inputs, cols, mu_f, c_i = _ar_model_inputs(m)
     if inputs["x"].shape[0] <= q:
         raise ValueError("the window must be longer than n_uarlag")
     v0 = _ar_v0(m, cols, c_i, inputs["Lam"])
     mean = c_i + inputs["Lam"] @ mu_f
-    ctx, own = _own(ctx)
-    try:
+    with _device(ctx) as ctx:
         o = ctx.simulate_ar_batch_host(*(inputs[k][None] for k in _AR_PARAM_NAMES), ndraws, T=inputs["x"].shape[0],
                                        panel=inputs["x"][None] if masked else None, v0=v0[None], seed=int(seed))
-    finally:
-        if own:
-            ctx.close()
     return dict(rows=np.arange(m.initperiod, m.lastperiod + 1), cols=cols, x=o["x"][0] + mean, factor=o["f"][0] + mu_f)
 
 
@@ -2332,67 +2165,34 @@ def draw_paths_ar_idio(m: DFMModel, ndraws: int, H: int = 0, *, through: Optiona
         raise ValueError("H must be >= 0")
     if first_draw < 0:
         raise ValueError("first_draw must be >= 0")
-    q = int(m.n_uarlag)
-    if not (1 <= q <= 4):
-        raise ValueError("draw_paths_ar_idio needs 1 <= n_uarlag <= 4")
-    qs = None
-    if quantiles is not None:
-        qs = np.atleast_1d(np.asarray(quantiles, dtype=np.float64))
-        if qs.size == 0 or np.any(~(qs >= 0.0)) or np.any(~(qs <= 1.0)):
-            raise ValueError("quantiles must lie in [0, 1]")
-        if ndraws > _QUANTILE_MAX_DRAWS:
-            raise ValueError(f"bands need ndraws <= {_QUANTILE_MAX_DRAWS}")
-    through = m.lastperiod if through is None else int(through)
-    if not (m.lastperiod <= through <= m.T):
-        raise ValueError(f"through must lie in lastperiod..T ({m.lastperiod}..{m.T})")
+    q = _ar_lags(m, "draw_paths_ar_idio")
+    qs = _quantile_arg(quantiles, closed=True)
+    if qs is not None and ndraws > _QUANTILE_MAX_DRAWS:
+        raise ValueError(f"bands need ndraws <= {_QUANTILE_MAX_DRAWS}")
+    through = _through_arg(m, through)
     inputs, cols, mu_f, c_i = _ar_model_inputs(m, through)
-    win = slice(m.initperiod - 1, m.lastperiod)
-    v0 = np.nanvar(m.data[win][:, cols] - c_i - m.factor[win] @ inputs["Lam"].T, axis=0)
+    v0 = _ar_v0(m, cols, c_i, inputs["Lam"])
     mean = c_i + inputs["Lam"] @ mu_f
     x = inputs["x"]
-    names = ("Lam", "sig2", "rho", "Avar", "Q", "mu0", "P0")
-    S, sets = 1, [inputs[k][None] for k in names]
-    if params is not None:
-        lost = [k for k in names if k not in params]
-        if lost:
-            raise ValueError(f"params lacks {lost}")
-        sets = [np.ascontiguousarray(params[k], dtype=np.float64) for k in names]
-        S = sets[0].shape[0] if sets[0].ndim == 3 else 0
-        for k, a in zip(names, sets):
-            if S < 1 or a.shape != (S,) + inputs[k].shape:
-                raise ValueError(f"params[{k!r}] must be [S, ...] with the model's own shape {inputs[k].shape} behind S >= 1")
-        if qs is not None and S * ndraws > _QUANTILE_MAX_DRAWS:
-            raise ValueError(f"bands need S x ndraws <= {_QUANTILE_MAX_DRAWS}")
+    sets = [inputs[k][None] for k in _AR_PARAM_NAMES] if params is None else _ar_param_sets(inputs, params)
+    S = sets[0].shape[0]
+    if params is not None and qs is not None and S * ndraws > _QUANTILE_MAX_DRAWS:
+        raise ValueError(f"bands need S x ndraws <= {_QUANTILE_MAX_DRAWS}")
     total = S * ndraws
-    rep = lambda a: np.ascontiguousarray(np.broadcast_to(a, (S,) + a.shape))
-    from ._lib import DfmError
-    ctx, own = _own(ctx)
-    try:
-        args = (rep(x), *sets, ndraws, H)
-        kw = dict(v0=rep(v0), seed=int(seed), first_draw=first_draw, mean=rep(mean), sd=np.ones((S, cols.size)),
-                  may_have_missing=bool(np.isnan(x).any()))
-        try:
-            o = ctx.simsmooth_ar_batch_host(*args, **kw)
-        except DfmError as err:                     # the information form inverts Q: as draw_paths, retry in covariance form
-            if err.code != -5:
-                raise
-            o = ctx.simsmooth_ar_batch_host(*args, singular_q=True, **kw)
-        xd = o["x"].reshape((total,) + o["x"].shape[2:])
-        fd = o["f"].reshape((total,) + o["f"].shape[2:])
+    kw = dict(v0=_rep(v0, S), seed=int(seed), first_draw=first_draw, mean=_rep(mean, S), sd=np.ones((S, cols.size)),
+              may_have_missing=bool(np.isnan(x).any()))
+    with _device(ctx) as ctx:                       # the information form inverts Q: as draw_paths, retry in covariance form
+        o = _numeric_retry(lambda **sq: ctx.simsmooth_ar_batch_host(_rep(x, S), *sets, ndraws, H, **sq, **kw))
+        xd, fd = _pooled(o["x"]), _pooled(o["f"])
         xr = m.data[m.initperiod - 1 + q:through][:, cols]              # observed cells: the data itself, not mean + z
         obs = ~np.isnan(xr)
         xd[:, :xr.shape[0], :][:, obs] = xr[obs]
-        bands = None if qs is None else ctx.quantile_bands_host(xd.reshape(total, -1), qs).reshape((qs.size,) + xd.shape[1:])
-    finally:
-        if own:
-            ctx.close()
+        bands = None if qs is None else _flat_bands(ctx, xd, qs)
     x_sd = xd.std(axis=0, ddof=1) if total > 1 else np.zeros(xd.shape[1:])
     x_sd[:xr.shape[0]][obs] = 0.0
     out = dict(rows=np.arange(m.initperiod + q, through + H + 1), cols=cols, factor=fd + mu_f, x=xd, x_sd=x_sd,
                mu_f=mu_f, inputs=dict(inputs, v0=v0, mean=mean))
-    if bands is not None:
-        out["quantiles"], out["bands"] = qs, bands
-    return out
+    return _with_bands(out, qs, bands=bands)
 
 
 def estimate_bayesian_ar_idio(m: DFMModel, ndraws: int, *, chains: int = 4, burn: int = 500, thin: int = 1, prior=None,
@@ -2420,18 +2220,11 @@ def estimate_bayesian_ar_idio(m: DFMModel, ndraws: int, *, chains: int = 4, burn
     ndraws, chains, burn, thin = int(ndraws), int(chains), int(burn), int(thin)
     if ndraws < 1 or chains < 1 or burn < 0 or thin < 1:
         raise ValueError("ndraws >= 1, chains >= 1, burn >= 0 and thin >= 1 are required")
-    q = int(m.n_uarlag)
-    if not (1 <= q <= 4):
-        raise ValueError("estimate_bayesian_ar_idio needs 1 <= n_uarlag <= 4")
+    q = _ar_lags(m, "estimate_bayesian_ar_idio")
     if m.nfac_u > 8:
         raise ValueError("estimate_bayesian_ar_idio needs nfac_u <= 8")
-    qs = None
-    if quantiles is not None:
-        qs = np.atleast_1d(np.asarray(quantiles, dtype=np.float64))
-        if qs.size < 1 or not np.all((qs > 0.0) & (qs <= 1.0)):
-            raise ValueError("quantiles must lie in (0, 1]")
+    qs = _quantile_arg(quantiles)
     inputs, cols, mu_f, c_i = _ar_model_inputs(m)
-    names = ("Lam", "sig2", "rho", "Avar", "Q", "mu0", "P0")
     x = inputs["x"]
     r = inputs["Lam"].shape[1]
     p = inputs["Avar"].shape[1] // r
@@ -2439,46 +2232,14 @@ def estimate_bayesian_ar_idio(m: DFMModel, ndraws: int, *, chains: int = 4, burn
         raise ValueError("the window is not longer than n_uarlag plus the number of factor lags")
     pr = bayes.check_prior_ar(prior, r, p, chains)
     mean = c_i + inputs["Lam"] @ mu_f
-    n_sweeps = burn + (ndraws - 1) * thin + 1
-    from ._lib import DfmError
-    ctx, own = _own(ctx)
-    try:
-        rep = lambda a: np.ascontiguousarray(np.broadcast_to(a, (chains,) + a.shape))
-        args = (rep(x), *[rep(inputs[k]) for k in names], pr, n_sweeps)
-        kw = dict(burn=burn, thin=thin, seed=int(seed), keep=("Lam", "sig2", "rho", "A", "Q", "f"),
-                  may_have_missing=bool(np.isnan(x).any()))
-        try:
-            _, d = ctx.gibbs_ar_batch_host(*args, **kw)
-        except DfmError as err:                     # as estimate_bayesian: the covariance form, but not for the sampler's own failures
-            if err.code != -5 or "Gibbs sampler" in str(err):
-                raise
-            _, d = ctx.gibbs_ar_batch_host(*args, singular_q=True, **kw)
-    finally:
-        if own:
-            ctx.close()
-    flat = lambda a: a.reshape((chains * ndraws,) + a.shape[2:])
-    tile = lambda a: np.ascontiguousarray(np.broadcast_to(a, (chains * ndraws,) + a.shape))
-    params = dict(Lam=flat(d["Lam"]), sig2=flat(d["sig2"]), rho=flat(d["rho"]), Avar=flat(d["A"]), Q=flat(d["Q"]),
-                  mu0=tile(inputs["mu0"]), P0=tile(inputs["P0"]))
-    pers = d["rho"].sum(axis=3)                                         # [chains, ndraws, N]
-    last = bayes.common_component(d["Lam"], d["f"], mean, 1.0, rows=[d["f"].shape[2] - 1])[:, :, 0, :]
-    out = dict(params=params, rows=np.arange(m.initperiod + q, m.lastperiod + 1), cols=cols, sig2_mean=d["sig2"].mean(axis=(0, 1)),
-               rho_mean=d["rho"].mean(axis=(0, 1)), persistence_mean=pers.mean(axis=(0, 1)), rhat_sig2=bayes.split_rhat(d["sig2"]),
-               rhat_persistence=bayes.split_rhat(pers), rhat_common=bayes.split_rhat(last), prior=pr, chains=chains, ndraws=ndraws,
-               mu_f=mu_f)
-    if qs is None:
-        out["common_mean"] = np.mean([bayes.common_component(d["Lam"][c], d["f"][c], mean, 1.0).mean(axis=0) for c in range(chains)],
-                                     axis=0)
-    else:
-        cc = flat(bayes.common_component(d["Lam"], d["f"], mean, 1.0))
-        out["common_mean"] = cc.mean(axis=0)
-        out["quantiles"] = qs
-        out["sig2_bands"] = np.quantile(flat(d["sig2"]), qs, axis=0)
-        out["persistence_bands"] = np.quantile(flat(pers), qs, axis=0)
-        out["common_bands"] = np.quantile(cc, qs, axis=0)
-    if keep_factors:
-        out["factor"] = flat(d["f"]) + mu_f
-    return out
+    keep = ("Lam", "sig2", "rho", "A", "Q", "f")
+    d = _gibbs_chains(ctx, "gibbs_ar_batch_host", x, [inputs[k] for k in _AR_PARAM_NAMES], pr, chains, ndraws, burn, thin, seed, keep)
+    K = chains * ndraws
+    params = dict(Lam=_pooled(d["Lam"]), sig2=_pooled(d["sig2"]), rho=_pooled(d["rho"]), Avar=_pooled(d["A"]), Q=_pooled(d["Q"]),
+                  mu0=_rep(inputs["mu0"], K), P0=_rep(inputs["P0"], K))
+    stats = dict(sig2=d["sig2"], rho=d["rho"], persistence=d["rho"].sum(axis=3))        # [chains, ndraws, N (, q)]
+    return _bayes_summary(d, params, np.arange(m.initperiod + q, m.lastperiod + 1), cols, stats, ("sig2", "persistence"), mean, 1.0,
+                          pr, qs, keep_factors, mu_f=mu_f)
 
 
 _AR_PARAM_NAMES = ("Lam", "sig2", "rho", "Avar", "Q", "mu0", "P0")
@@ -2500,12 +2261,8 @@ def _ar_param_sets(inputs, params):
 def _filter_ar_setup(m: DFMModel, through, params, who):
     """The checks and inputs filter_states_ar_idio and evaluate_forecasts_ar_idio share (no device is touched): q, through, the
     panel, the parameter sets [S, ...] (the model's own as one set without `params`), cols, mu_f and the data-unit mean."""
-    q = int(m.n_uarlag)
-    if not (1 <= q <= 4):
-        raise ValueError(f"{who} needs 1 <= n_uarlag <= 4")
-    through = m.lastperiod if through is None else int(through)
-    if not (m.lastperiod <= through <= m.T):
-        raise ValueError(f"through must lie in lastperiod..T ({m.lastperiod}..{m.T})")
+    q = _ar_lags(m, who)
+    through = _through_arg(m, through)
     inputs, cols, mu_f, c_i = _ar_model_inputs(m, through)
     sets = [inputs[k][None] for k in _AR_PARAM_NAMES] if params is None else _ar_param_sets(inputs, params)
     mean = c_i + inputs["Lam"] @ mu_f
@@ -2534,13 +2291,9 @@ def filter_states_ar_idio(m: DFMModel, *, through: Optional[int] = None, params=
         raise ValueError("filter_states_ar_idio takes one parameter set (S = 1); evaluate_forecasts_ar_idio takes several")
     x = inputs["x"]
     want = ("z_pred", "P_pred", "z_filt", "P_filt", "loglik_t", "xpred", "verr", "vstd")
-    ctx, own = _own(ctx)
-    try:
+    with _device(ctx) as ctx:
         o = ctx.filter_ar_batch_host(x[None], *sets, H=0, mean=mean[None], sd=np.ones((1, cols.size)), want=want,
                                      may_have_missing=bool(np.isnan(x).any()))
-    finally:
-        if own:
-            ctx.close()
     r = m.nfac_u
     k = o["z_pred"].shape[2]
     Pp, Pf = _unpack(o["P_pred"][0], k), _unpack(o["P_filt"][0], k)
@@ -2573,13 +2326,9 @@ def evaluate_forecasts_ar_idio(m: DFMModel, H: int, *, first_origin: Optional[in
     H = int(H)
     if H < 1:
         raise ValueError("H must be >= 1")
-    qs = None
-    if quantiles is not None:
-        if params is None:
-            raise ValueError("quantile bands need parameter sets: params=estimate_bayesian_ar_idio(...)['params']")
-        qs = np.atleast_1d(np.asarray(quantiles, dtype=np.float64))
-        if qs.size < 1 or not np.all((qs > 0.0) & (qs <= 1.0)):
-            raise ValueError("quantiles must lie in (0, 1]")
+    if quantiles is not None and params is None:
+        raise ValueError("quantile bands need parameter sets: params=estimate_bayesian_ar_idio(...)['params']")
+    qs = _quantile_arg(quantiles)
     q, through, inputs, sets, cols, mu_f, mean = _filter_ar_setup(m, through, params, "evaluate_forecasts_ar_idio")
     first = m.initperiod + q
     rows = through - first + 1
@@ -2590,27 +2339,20 @@ def evaluate_forecasts_ar_idio(m: DFMModel, H: int, *, first_origin: Optional[in
     if qs is not None and S > _QUANTILE_MAX_DRAWS:
         raise ValueError(f"bands need at most {_QUANTILE_MAX_DRAWS} parameter sets")
     x = inputs["x"]
-    rep = lambda a: np.ascontiguousarray(np.broadcast_to(a, (S,) + a.shape))
-    ctx, own = _own(ctx)
-    try:
-        o = ctx.filter_ar_batch_host(rep(x), *sets, H=H, t0=first_origin - m.initperiod, mean=rep(mean), sd=np.ones((S, cols.size)),
-                                     want=("msfe", "msfe_common", "msfe0", "cnt"), may_have_missing=bool(np.isnan(x).any()))
+    with _device(ctx) as ctx:
+        o = ctx.filter_ar_batch_host(_rep(x, S), *sets, H=H, t0=first_origin - m.initperiod, mean=_rep(mean, S),
+                                     sd=np.ones((S, cols.size)), want=("msfe", "msfe_common", "msfe0", "cnt"),
+                                     may_have_missing=bool(np.isnan(x).any()))
         bands = gbands = None
         if qs is not None:
             with np.errstate(invalid="ignore", divide="ignore"):
                 g = o["msfe"] / o["msfe_common"]
-            band = lambda a: ctx.quantile_bands_host(np.ascontiguousarray(a.reshape(S, -1)), qs).reshape((qs.size,) + a.shape[1:])
-            bands, gbands = band(o["msfe"]), band(g)
-    finally:
-        if own:
-            ctx.close()
+            bands, gbands = _flat_bands(ctx, o["msfe"], qs), _flat_bands(ctx, g, qs)
     msfe, msfec, msfe0 = o["msfe"][0], o["msfe_common"][0], o["msfe0"][0]
     with np.errstate(invalid="ignore", divide="ignore"):
         out = dict(horizons=np.arange(1, H + 1), cols=cols, msfe=msfe, rmsfe=np.sqrt(msfe), msfe_common=msfec, gain=msfe / msfec,
                    relative=msfe / msfe0, count=o["cnt"][0])
-    if bands is not None:
-        out["quantiles"], out["bands"], out["gain_bands"] = qs, bands, gbands
-    return out
+    return _with_bands(out, qs, bands=bands, gain_bands=gbands)
 
 
 def news_ar_idio(m: DFMModel, old, new, targets, *, groups=None, params=None, quantiles=None, ctx=None) -> dict:
@@ -2630,106 +2372,32 @@ def news_ar_idio(m: DFMModel, old, new, targets, *, groups=None, params=None, qu
     last row of the vintages, and inputs (the arrays handed to the library: old, new, the parameters, v0, mean, sd, targets).
     `m` is not modified."""
     from . import news_ar as _na
-    q = int(m.n_uarlag)
-    if not (1 <= q <= 4):
-        raise ValueError("news_ar_idio needs 1 <= n_uarlag <= 4")
-    ncol = m.data.shape[1]
-
-    def vintage(v, name):
-        if np.isscalar(v) and float(v) == int(v):
-            t = int(v)
-            if not (m.initperiod <= t <= m.T):
-                raise ValueError(f"{name} vintage: through must lie in initperiod..T ({m.initperiod}..{m.T})")
-            return np.asarray(m.data[:t], dtype=np.float64)
-        x = np.asarray(v, dtype=np.float64)
-        if x.ndim != 2 or x.shape[1] != ncol or x.shape[0] < m.initperiod:
-            raise ValueError(f"{name} vintage: an array shaped like m.data ([rows >= initperiod, {ncol}]) or a 1-based row")
-        return x
-    xo, xn = vintage(old, "old"), vintage(new, "new")
-    last = max(xo.shape[0], xn.shape[0])
-    padr = lambda x: np.vstack([x, np.full((last - x.shape[0], ncol), np.nan)])
-    xo, xn = padr(xo), padr(xn)
-    tg = list(targets) if targets is not None else []
-    if len(tg) < 1:
-        raise ValueError("at least one target (column, period) is needed")
+    q = _ar_lags(m, "news_ar_idio")
+    xo, xn, last = _vintages(m, old, new)
+    tg = _target_list(targets)
     inputs, cols, mu_f, c_i = _ar_model_inputs(m)
     pos = {int(c): j for j, c in enumerate(cols)}
-    pairs = []
-    for c, per in tg:
-        if int(c) not in pos:
-            raise ValueError(f"target column {c} is not one of the series the model uses")
-        if int(per) < m.initperiod + q:
-            raise ValueError(f"target period {per} lies before initperiod + n_uarlag ({m.initperiod + q}): the first n_uarlag "
-                             "window rows are conditioning values")
-        pairs.append((int(per) - m.initperiod, pos[int(c)]))
-    gsum = None
-    if groups is not None:
-        gsum = {}
-        for name, gc in dict(groups).items():
-            idx = [pos.get(int(c), -1) for c in np.atleast_1d(gc)]
-            if len(idx) < 1 or min(idx) < 0:
-                raise ValueError(f"groups[{name!r}] must list columns the model uses")
-            gsum[name] = np.asarray(idx)
+    pairs = _news_targets(m, tg, pos, "the model uses", q)
+    gsum = _news_groups(groups, pos, "the model uses")
     sets = [inputs[k][None] for k in _AR_PARAM_NAMES]
-    if params is not None:
-        lost = [k for k in _AR_PARAM_NAMES if k not in params]
-        if lost:
-            raise ValueError(f"params lacks {lost}")
-        extra = [np.ascontiguousarray(params[k], dtype=np.float64) for k in _AR_PARAM_NAMES]
-        S = extra[0].shape[0] if extra[0].ndim == 3 else 0
-        for k, a in zip(_AR_PARAM_NAMES, extra):
-            if S < 1 or a.shape != (S,) + inputs[k].shape:
-                raise ValueError(f"params[{k!r}] must be [S, ...] with the model's own shape {inputs[k].shape} behind S >= 1")
-        sets = [np.concatenate([a, b]) for a, b in zip(sets, extra)]    # replicate 0: the point estimate
-    qs = None
-    if quantiles is not None:
-        qs = np.atleast_1d(np.asarray(quantiles, dtype=np.float64))
-        if params is None:
-            raise ValueError("quantile bands need parameter sets: params=estimate_bayesian_ar_idio(m, ...)['params']")
-        if qs.size < 1 or not np.all((qs > 0.0) & (qs <= 1.0)):
-            raise ValueError("quantiles must lie in (0, 1]")
-        if sets[0].shape[0] - 1 > _QUANTILE_MAX_DRAWS:
-            raise ValueError(f"bands need at most {_QUANTILE_MAX_DRAWS} parameter sets")
+    if params is not None:                          # replicate 0: the point estimate
+        sets = [np.concatenate([a, b]) for a, b in zip(sets, _ar_param_sets(inputs, params))]
+    qs = _quantile_arg(quantiles, (params is None, "quantile bands need parameter sets: params=estimate_bayesian_ar_idio(m, ...)['params']"))
+    if qs is not None and sets[0].shape[0] - 1 > _QUANTILE_MAX_DRAWS:
+        raise ValueError(f"bands need at most {_QUANTILE_MAX_DRAWS} parameter sets")
     mean = c_i + inputs["Lam"] @ mu_f
     zo, zn = xo[m.initperiod - 1:, cols] - mean, xn[m.initperiod - 1:, cols] - mean
     _na.check_args(zn.shape[0], q, pairs)
     why = _na.edge_shape_error(zo, zn, q, cols=cols)
     if why is not None:
         raise ValueError("vintage: " + why)
-    win = slice(m.initperiod - 1, m.lastperiod)
-    v0 = np.nanvar(m.data[win][:, cols] - c_i - m.factor[win] @ inputs["Lam"].T, axis=0)
+    v0 = _ar_v0(m, cols, c_i, inputs["Lam"])
     B = sets[0].shape[0]
-    rep = lambda a: np.ascontiguousarray(np.broadcast_to(a, (B,) + a.shape))
     sd = np.ones(cols.size)
-    from ._lib import DfmError
-    ctx, own = _own(ctx)
-    try:
-        args = (rep(zo), rep(zn), *sets, pairs)
-        kw = dict(v0=rep(v0), mean=rep(mean), sd=rep(sd), may_have_missing=bool(np.isnan(zn).any()))
-        try:
-            o = ctx.news_ar_batch_host(*args, **kw)
-        except DfmError as err:                     # the information form inverts Q: as estimate(), retry in covariance form
-            if err.code != -5:
-                raise
-            o = ctx.news_ar_batch_host(*args, singular_q=True, **kw)
-        bands = None
-        if qs is not None:
-            bands = (ctx.quantile_bands_host(o["impact"][1:], qs),
-                     ctx.quantile_bands_host(o["yhat"][1:, 2] - o["yhat"][1:, 0], qs))
-    finally:
-        if own:
-            ctx.close()
-    y = o["yhat"][0]
-    out = dict(rows=np.arange(m.initperiod + q, last + 1), cols=cols, y_old=y[0], y_rev=y[1], y_new=y[2], revision=y[2] - y[0],
-               data_revision=y[1] - y[0], news_effect=y[2] - y[1], impact=o["impact"][0], news=o["news"][0],
-               weight=o["weight"][0],
-               inputs=dict({k: a[0] for k, a in zip(_AR_PARAM_NAMES, sets)}, old=zo, new=zn, v0=v0, mean=mean, sd=sd, targets=pairs))
-    if gsum is not None:
-        out["groups"] = {name: out["impact"][:, idx].sum(axis=1) for name, idx in gsum.items()}
-    if bands is not None:
-        out["quantiles"] = qs
-        out["impact_bands"], out["revision_bands"] = bands
-    return out
+    o, bands = _news_call(ctx, "news_ar_batch_host", (_rep(zo, B), _rep(zn, B), *sets, pairs),
+                          dict(v0=_rep(v0, B), mean=_rep(mean, B), sd=_rep(sd, B), may_have_missing=bool(np.isnan(zn).any())), qs)
+    extra = dict(inputs=dict({k: a[0] for k, a in zip(_AR_PARAM_NAMES, sets)}, old=zo, new=zn, v0=v0, mean=mean, sd=sd, targets=pairs))
+    return _news_result(o, np.arange(m.initperiod + q, last + 1), cols, extra, gsum, qs, bands)
 
 
 def amengual_watson_test(m: DFMModel, nper: int = 4, *, ctx=None):
@@ -2745,8 +2413,7 @@ def amengual_watson_test(m: DFMModel, nper: int = 4, *, ctx=None):
     T_all, ns = est.shape
     nlag = m.factor_var_model.nlag
     x = np.column_stack([np.ones(T_all), _lagmat(m.factor, range(1, nlag + 1))])
-    ctx, own = _own(ctx)
-    try:
+    with _device(ctx) as ctx:
         # the reference keeps a series when it has at least nt_min rows MORE than regressors (:744)
         o = ctx.ols_batch_host(x, est, nt_min=x.shape[1] + m.nt_min_factor_estimation)
         res = o["resid"]                                                   # NaN where a row was not used
@@ -2757,9 +2424,6 @@ def amengual_watson_test(m: DFMModel, nper: int = 4, *, ctx=None):
         F0 = pca_start(ctx, z, r)
         a = ctx.als_batch_host(z, np.repeat(F0[None], r, axis=0), r_each=np.arange(1, r + 1),
                                nt_min=m.nt_min_factor_estimation, tol=m.tol)
-    finally:
-        if own:
-            ctx.close()
     aw = np.array([bai_ng_criterion(s, nobs, T, k + 1) for k, s in enumerate(a["ssr"])])
     return aw, a["ssr"].copy()
 
@@ -2790,12 +2454,8 @@ def break_tests(m: DFMModel, T_break: int, ccut: float = 0.15, q: int = 6, min_o
         n1 = int(np.floor(ccut * T))
         for tb in range(n1, T - n1 + 1):                                               # compute_qlr's HAC leg
             ps.append(s); pb.append(tb); pq.append(q); tag.append(1)
-    ctx, own = _own(ctx)
-    try:
+    with _device(ctx) as ctx:
         stat = ctx.chow_batch_host(ys, Xs, ps, pb, pq)
-    finally:
-        if own:
-            ctx.close()
     ps = np.asarray(ps); tag = np.asarray(tag)
     for s, i in enumerate(who):
         sel = ps == s

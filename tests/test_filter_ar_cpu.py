@@ -15,6 +15,7 @@ from dynamic_factor_models_amd import _lib, api, filtering_ar, kalman
 from oracle import ar_oracle as ao
 from tests import filter_ar_expect as fe
 from tests import forecast_ar_expect as fae
+from tests.api_calls import Recorder
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BALANCED = [(6, 14, 2, 1, 2, 4), (5, 12, 1, 2, 1, 3), (8, 16, 2, 2, 3, 5), (7, 15, 2, 3, 1, 4), (4, 14, 1, 1, 4, 3)]  # N, T, r, p, q, H
@@ -138,22 +139,6 @@ B, T, N, r, p, q, H, T0 = 2, 12, 6, 2, 2, 1, 3, 4
 K = r * max(p, q + 1)
 KK = K * (K + 1) // 2
 HANDLE = 0xD0F0
-
-
-class Recorder:
-    """Stands for the loaded library: every dfm_* attribute stores (name, args) and returns 0."""
-
-    def __init__(self):
-        self.calls = []
-
-    def __getattr__(self, name):
-        if not name.startswith("dfm_"):
-            raise AttributeError(name)
-
-        def fn(*args):
-            self.calls.append((name, args))
-            return 0
-        return fn
 
 
 class _OnDevice(torch.Tensor):

@@ -13,6 +13,7 @@ import torch
 
 from dynamic_factor_models_amd import _lib, api, forecasting_ar, kalman
 from tests import forecast_ar_expect as fe
+from tests.api_calls import Recorder
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BALANCED = [(6, 14, 2, 1, 2, 4), (5, 12, 1, 2, 1, 3), (8, 16, 2, 2, 3, 5), (30, 20, 2, 1, 2, 4)]      # N, T, r, p, q, H
@@ -147,22 +148,6 @@ def test_geometry_header_against_its_restatement(tmp_path):
 B, T, N, r, p, q, H = 2, 12, 6, 2, 2, 1, 3
 HANDLE = 0xD0F0
 NPK = r * (r + 1) // 2
-
-
-class Recorder:
-    """Stands for the loaded library: every dfm_* attribute stores (name, args) and returns 0."""
-
-    def __init__(self):
-        self.calls = []
-
-    def __getattr__(self, name):
-        if not name.startswith("dfm_"):
-            raise AttributeError(name)
-
-        def fn(*args):
-            self.calls.append((name, args))
-            return 0
-        return fn
 
 
 class _OnDevice(torch.Tensor):

@@ -12,28 +12,12 @@ import pytest
 import torch
 
 from dynamic_factor_models_amd import _lib, kalman
+from tests.api_calls import Recorder
 
 B, T, N, r, p, q, L = 2, 12, 6, 2, 2, 1, 3
 D, H, G = 2, 1, 1
 MISS, SING = _lib.DFM_F_MAY_HAVE_MISSING, _lib.DFM_F_SINGULAR_Q
 HANDLE = 0xD0F0
-
-
-class Recorder:
-    """Stands for the loaded library: every dfm_* attribute is a function that stores (name, args) and returns 0
-    (dfm_profile_read: 0 for index 0 only, so that the reader's loop ends)."""
-
-    def __init__(self):
-        self.calls = []
-
-    def __getattr__(self, name):
-        if not name.startswith("dfm_"):
-            raise AttributeError(name)
-
-        def fn(*args):
-            self.calls.append((name, args))
-            return 1 if name == "dfm_profile_read" and args[1] > 0 else 0
-        return fn
 
 
 class _OnDevice(torch.Tensor):

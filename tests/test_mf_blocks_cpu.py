@@ -186,15 +186,7 @@ def test_the_source_list_builds_the_new_kernel():
 def test_python_binding_marshals_the_mask():
     """The host wrapper through a recorder in place of the library: the symbol, the mask as N x r bytes behind W, null for None."""
     from dynamic_factor_models_amd import _lib, kalman
-
-    class Recorder:
-        def __init__(self):
-            self.calls = []
-
-        def __getattr__(self, name):
-            if not name.startswith("dfm_"):
-                raise AttributeError(name)
-            return lambda *args: self.calls.append((name, args)) or 0
+    from tests.api_calls import Recorder
 
     x, W, free, st, _ = mb.build_case(2, 9, 4, 36, 2, 1)
     ctx = kalman.DfmContext.__new__(kalman.DfmContext)

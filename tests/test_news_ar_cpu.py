@@ -12,6 +12,7 @@ import torch
 from dynamic_factor_models_amd import _lib, api, kalman, news_ar
 from tests import forecast_ar_expect as fe
 from tests import news_ar_expect as ne
+from tests.api_calls import Recorder
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KEYS = ne.KEYS
@@ -175,22 +176,6 @@ B, T, N, r, p, q = 2, 12, 6, 2, 2, 1
 HANDLE = 0xD0F1
 TARGETS = [(11, 0), (13, 5), (4, 2)]
 INPUTS = ("old", "new", "Lam", "sig2", "rho", "Avar", "Q", "mu0", "P0")
-
-
-class Recorder:
-    """Stands for the loaded library: every dfm_* attribute stores (name, args) and returns 0."""
-
-    def __init__(self):
-        self.calls = []
-
-    def __getattr__(self, name):
-        if not name.startswith("dfm_"):
-            raise AttributeError(name)
-
-        def fn(*args):
-            self.calls.append((name, args))
-            return 0
-        return fn
 
 
 class _OnDevice(torch.Tensor):

@@ -15,6 +15,7 @@ from dynamic_factor_models_amd import _lib, api, kalman, structural
 from tests import post_geometry as pg
 from tests import structural_expect as se
 from tests import structural_geometry as sg
+from tests.api_calls import Recorder
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -248,22 +249,6 @@ def test_api_refuses_before_any_device_work():
 # ------------------------------------------------------------------------------------------------------------ the binding
 B, T, N, r, p, H = 2, 12, 6, 2, 3, 4
 HANDLE = 0xD0F0
-
-
-class Recorder:
-    """Stands for the loaded library: every dfm_* attribute is a function that stores (name, args) and returns 0."""
-
-    def __init__(self):
-        self.calls = []
-
-    def __getattr__(self, name):
-        if not name.startswith("dfm_"):
-            raise AttributeError(name)
-
-        def fn(*args):
-            self.calls.append((name, args))
-            return 0
-        return fn
 
 
 class _OnDevice(torch.Tensor):
