@@ -70,6 +70,7 @@ struct RouteOpts {
     int pass_nsw = 0;                      // DFM_PASS_NSW: stream waves per workgroup of that launch (0 = automatic)
     bool pf_wpark = true;                  // DFM_PF_WPARK=0 (route): the stream waves of that launch load their own weights (no hand-over by the fill wave)
     bool wide_old = false;                 // DFM_WIDE_OLD=1: Rp = 32 balanced collapse by collapse_wide_kernel + gram_wide_kernel
+    int wide_sub = 1;                      // DFM_WIDE_SUB=n (2..8): the wide2 balanced pass in n sub-batches (measured slower: fast_route)
     bool collapse_miss_old = false;        // DFM_COLLAPSE_MISS_OLD=1: register-streamed collapse_kernel for panels with missing cells
     bool narrow_tab_off = false;           // DFM_NARROW_TAB=0 (diagnostics build): r <= 4 on the 8-wide state through collapse_kernel<4> + chunk_bridge_kernel
     bool gram_xx_valu = false;             // DFM_GRAM_XX_VALU=1: X'X of the PCA start on the VALU kernel (diagnostics)
@@ -124,6 +125,7 @@ RouteOpts route_opts_from_env() {
     o.tile_nc = pos(route_env("DFM_TILE_NC"));
     o.tile_w = pos(route_env("DFM_TILE_W"));
     o.wide_old = on(diag_env("DFM_WIDE_OLD"));
+    o.wide_sub = num(diag_env("DFM_WIDE_SUB"), 1);
     o.cov_wave = on(diag_env("DFM_COV_WAVE"));
     if (const char* v = route_env("DFM_FCAR_MSG_BYTES")) { if (atoll(v) > 0) o.fcar_msg_cap = (size_t)atoll(v); }
     return o;
@@ -698,283 +700,365 @@ int pipe_run(dfm_handle* h, int B, size_t slot_bytes, Body body) {
     return rc;
 }
 
-// gram + cov on the side stream, beside the streaming collapse on the main stream; the batch is cut
-// into sub-batches so that the (latency-bound) meanscan of sub-batch s runs on a third stream beside the
-// (bandwidth-bound) collapse of sub-batch s+1.
-int enqueue_pass_fast(dfm_handle* h, const Plan& p, int B, int T, int N, int out_r, const double* panel,
-                      const PaddedParams& pp, const double* Rv, double* f_smooth, double* P_smooth,
-                      double* loglik, const EmOpts* em = nullptr) {
+// ---- one pass on an already-planned workspace: what the caller hands over, the argument structs, the route, the schedules ----------
+// out_r = factor dimension of the f_smooth / P_smooth layout (caller's r for a plain pass, Rp for EM-internal buffers); em: null
+// for a plain pass
+struct PassIo {
+    int B, T, N, out_r;
+    const double* panel; PaddedParams pp; const double* Rv; double *f_smooth, *P_smooth, *loglik; const EmOpts* em;
+};
+// the CollapseArgs fields that the balanced and the general path share
+CollapseArgs collapse_args(dfm_handle* h, const Plan& p, const PassIo& io) {
     CollapseArgs ca;
     memset(&ca, 0, sizeof(ca));
-    ca.B = B; ca.T = T; ca.N = N;
-    ca.panel = panel; ca.Lam = pp.Lam; ca.Rv = Rv;
-    ca.bcol = at<double>(h, p.bcol); ca.scol = at<double>(h, p.scol); ca.ssum = at<double>(h, p.f_ssum);
+    ca.B = io.B; ca.T = io.T; ca.N = io.N; ca.panel = io.panel; ca.Lam = io.pp.Lam; ca.Rv = io.Rv;
+    ca.bcol = at<double>(h, p.bcol); ca.scol = at<double>(h, p.scol);
     ca.Cfull = at<double>(h, p.Cfull); ca.ldfull = at<double>(h, p.ldfull); ca.status = h->status_dev;
-    FastArgs fa;
-    memset(&fa, 0, sizeof(fa));
-    fa.B = B; fa.T = T; fa.N = N; fa.r = out_r; fa.L = fast_chunk_len(p.Rp, T);
-    fa.rstate = p.r;
-    fa.A = pp.A; fa.Q = pp.Q; fa.mu0 = pp.mu0; fa.P0 = pp.P0;
-    fa.Cfull = ca.Cfull; fa.ldfull = ca.ldfull;
-    fa.tab = at<double>(h, p.f_tab); fa.E = at<int>(h, p.f_E); fa.stead = at<double>(h, p.f_stead);
-    fa.xi0 = at<double>(h, p.f_xi0); fa.PT = at<double>(h, p.f_PT); fa.llc = at<double>(h, p.f_llc);
-    fa.fill = at<int>(h, p.f_fill); fa.PsInf = at<double>(h, p.f_PsInf);
-    fa.bcol = ca.bcol; fa.ssum = ca.ssum; fa.wtab = at<double>(h, p.wtab); fa.wrep = wtab_rows(true, p.Rp, T) * (size_t)p.Rp;
-    // collapse kernel of the balanced path: contraction on the matrix pipe where the shape allows it
-    // (collapse_mfma.hip), else the VALU kernel (collapse_dma.hip); DFM_COLLAPSE_VARIANT < 200 forces the latter
-    // shapes outside the register tilings (or DFM_COLLAPSE_VARIANT=198): the wide kernel
+    return ca;
+}
+
+// The route of the balanced pass (fastpath.hip) as a value: which collapse, with which geometry, on which of the six schedules.
+enum FastCollapse { FC_DMA, FC_MFMA, FC_WIDE, FC_WIDE2 };   // collapse_dma.hip (VALU), collapse_mfma.hip, collapse_wide.hip, collapse_wide2.hip
+enum FastSchedule {
+    FS_IN_ORDER,     // DFM_NO_SIDE=1: gram, cov, collapse, scan in order on the caller's stream
+    FS_ONE_LAUNCH,   // pass_fused.hip
+    FS_TWO_LAUNCH,   // [covariance workgroups | MFMA collapse] -> scan, one stream
+    FS_WIDE_SUB,     // DFM_WIDE_SUB=n: n sub-batches of the wide2 collapse on side, their scans on the caller's stream
+    FS_FORKED,       // cov on the caller's stream, collapse on side, (wide2) the P_smooth fill on post
+    FS_SUBBATCH      // DFM_SUBBATCH=n: gram + cov on side, n collapses on the caller's stream, their scans on post
+};
+struct FastRoute {
+    FastCollapse collapse = FC_DMA; KernelId kid = K_COLLAPSE_DMA;   // the collapse kernel and its profiling label
+    int cvariant = 0;                    // launch_collapse_dma's variant (>= 200: the MFMA kernel)
+    int wpr = 4;                         // period segments per replicate: CollapseArgs::wpr and FastArgs::nseg
+    int ntile = 0;                       // wide kernels: sum_t s_t arrives as partials per tile of the collapse (FastArgs::ntile, scol)
+    int bst = 0;                         // > 0: narrowed rows of b_t (CollapseArgs::bst, FastArgs::bst)
+    bool fuse_gram = false;              // DFM_FUSE_GRAM=1 where cov_kernel can: no Gram launch
+    bool cov_gram = false;               // whoever runs the covariance recursion forms its Gram matrices itself (FastArgs::Lam, Rv)
+    bool fill = false, fill_late = false;   // P_smooth's data-independent rows by pfill_kernel; ... on post, behind the collapse
+    FastSchedule sched = FS_FORKED; int S = 1;   // S: sub-batches of FS_SUBBATCH / FS_WIDE_SUB
+    bool wide2() const { return collapse == FC_WIDE2; }
+};
+// Pure host code: the switches of the handle, the plan and the shape in, the route out.  want_P: the caller takes P_smooth.
+FastRoute fast_route(const RouteOpts& o, const Plan& p, int B, int T, int N, int num_cu, bool want_P) {
+    FastRoute rt;
+    const int cv = o.collapse_variant;
+    // collapse kernel of the balanced path: contraction on the matrix pipe where the shape allows it (collapse_mfma.hip), else the VALU
+    // kernel (collapse_dma.hip); DFM_COLLAPSE_VARIANT < 200 forces the latter; outside the register tilings (or = 198): the wide kernel
     // Rp = 16 | 32 with an even N: the streaming collapse of collapse_wide2.hip (Rp = 16 used to take the VALU kernel: 1.4-2.1 TB/s)
-    const bool wide2_ok = !h->opt.wide_old && p.Wwide != (size_t)-1;      // (planned where collapse_wide2_supported says so: make_plan)
-    const bool use_wide = (wide2_ok && h->opt.collapse_variant == 0) || !collapse_dma_supported(p.Rp, N) || h->opt.collapse_variant == 198;
-    const bool use_mfma = !use_wide && collapse_mfma_supported(p.Rp, N) && (h->opt.collapse_variant == 0 || h->opt.collapse_variant >= 200);
-    const int cvariant = use_mfma ? (h->opt.collapse_variant >= 200 ? h->opt.collapse_variant : 200)
-                                  : (h->opt.collapse_variant == 199 ? 0 : h->opt.collapse_variant);   // 199: the VALU kernel's default
+    const bool wide2_ok = !o.wide_old && p.Wwide != (size_t)-1;      // (planned where collapse_wide2_supported says so: make_plan)
+    const bool use_wide = (wide2_ok && cv == 0) || !collapse_dma_supported(p.Rp, N) || cv == 198;
+    const bool use_mfma = !use_wide && collapse_mfma_supported(p.Rp, N) && (cv == 0 || cv >= 200);
     const bool use_wide2 = use_wide && wide2_ok;
-    if (use_wide) {   // sum_t s_t arrives as partials per tile of the collapse kernel that will run
-        fa.scol = ca.scol;
-        fa.ntile = !use_wide2 ? collapse_wide_tiles(T) : collapse_wide2_tiles(T);
-    }
+    rt.collapse = use_wide2 ? FC_WIDE2 : use_wide ? FC_WIDE : use_mfma ? FC_MFMA : FC_DMA;
+    rt.kid = use_wide ? K_COLLAPSE_WIDE : use_mfma ? K_COLLAPSE_MFMA : K_COLLAPSE_DMA;
+    rt.cvariant = use_mfma ? (cv >= 200 ? cv : 200) : (cv == 199 ? 0 : cv);   // 199: the VALU kernel's default
+    if (use_wide) rt.ntile = !use_wide2 ? collapse_wide_tiles(T) : collapse_wide2_tiles(T);
     // Rp = 32 on the streaming collapse: b_t rows 8 ceil(r / 8) doubles apart instead of 32 -- the padding components are exact zeros
     // that the mean scan (its only reader here) substitutes; at BASELINE config 4 (r = 20) a quarter of the 0.39 GB of b_t traffic
-    if (use_wide2 && p.Rp == 32) ca.bst = fa.bst = 8 * ((p.r + 7) / 8);
-    double* Wwide = use_wide2 ? at<double>(h, p.Wwide) : nullptr;
-    // Gram matrix (+ W for the Rp = 32 collapse) and the streaming collapse of this shape, on stream `st`
-    auto run_gram = [&](hipStream_t st) -> hipError_t {
-        if (use_wide2) return launch_wide_prep(ca, Wwide, p.Rp, st, p.r);
-        return gram_supported(p.Rp, N) ? launch_gram(p.Rp, ca, st) : launch_gram_wide(p.Rp, ca, st);
-    };
-    auto run_collapse = [&](const CollapseArgs& c, hipStream_t st) -> hipError_t {
-        if (use_wide2) return launch_collapse_wide2(c, Wwide, p.Rp, p.r, h->num_cu, st);
-        return use_wide ? launch_collapse_wide(p.Rp, c, st) : launch_collapse_dma(p.Rp, c, st, cvariant);
-    };
+    if (use_wide2 && p.Rp == 32) rt.bst = 8 * ((p.r + 7) / 8);
     // MFMA collapse: as many period segments per replicate as the chip has resident wave slots for this batch
     // (3 workgroups x 4 waves on each CU), so that the launch is one balanced round
-    int wpr = 4;
     if (use_mfma) {
-        wpr = h->opt.collapse_wpr > 0 ? h->opt.collapse_wpr : (h->num_cu * 12) / B;
-        if (wpr < 1) wpr = 1;
-        if (wpr > 8) wpr = 8;
-        while (wpr > 1 && T / wpr < 8) --wpr;     // keep segments a few row blocks long
+        rt.wpr = o.collapse_wpr > 0 ? o.collapse_wpr : (num_cu * 12) / B;
+        if (rt.wpr < 1) rt.wpr = 1;
+        if (rt.wpr > 8) rt.wpr = 8;
+        while (rt.wpr > 1 && T / rt.wpr < 8) --rt.wpr;     // keep segments a few row blocks long
     }
-    ca.wpr = wpr;
-    fa.nseg = use_mfma ? wpr : 4;
-    const bool fuse_gram = cov_fuses_gram(p.Rp, N) && h->opt.fuse_gram;
-    if (fuse_gram) { fa.Lam = pp.Lam; fa.Rv = Rv; }
-    fa.f_smooth = f_smooth; fa.P_smooth = P_smooth; fa.loglik = loglik;
-    fa.abl = h->opt.scan_abl;
-    if (em) {   // EM: covariance sums from cov_kernel, E[f_0 | X] from meanscan (workspace slots of S10 / S00 reused)
-        fa.SP11 = at<double>(h, p.S10); fa.SU = at<double>(h, p.S00); fa.P0s = at<double>(h, p.P0s);
-        fa.f0s = at<double>(h, p.f0s);
-    }
-    // after the scan: transition M-step + bookkeeping from the sufficient statistics
-    auto em_update = [&]() -> int {
-        if (!em) return 0;
-        EmUpdArgs ua;
-        memset(&ua, 0, sizeof(ua));
-        ua.B = B; ua.T = T; ua.fsm = f_smooth; ua.f0s = fa.f0s; ua.SP11 = fa.SP11; ua.SU = fa.SU; ua.P0s = fa.P0s;
-        ua.PT = fa.PT; ua.loglik = loglik; ua.S11 = at<double>(h, p.S11); ua.S11inv = at<double>(h, p.Sxf);
-        ua.A_out = em->A_out; ua.Q_out = em->Q_out; ua.mu0_out = em->mu0_out; ua.P0_out = em->P0_out;
-        ua.active = em->active; ua.iters = em->iters; ua.ll_path = em->ll_path; ua.k = em->k; ua.max_iter = em->max_iter;
-        ua.tol = em->tol;
-        if (h->defer_em) { h->deferred_em = ua; h->have_deferred_em = true; return 0; }
-        HIP_LAUNCH(h, K_EM_UPDATE, launch_em_update(p.Rp, ua, h->stream));
-        return 0;
-    };
-    if (h->opt.no_side) {   // diagnostics: everything in order on the main stream
-        if (!fuse_gram) HIP_LAUNCH(h, K_GRAM, run_gram(h->stream));
-        HIP_LAUNCH(h, K_COV, launch_cov(p.Rp, fa, h->stream));
-        HIP_LAUNCH(h, use_wide ? K_COLLAPSE_WIDE : use_mfma ? K_COLLAPSE_MFMA : K_COLLAPSE_DMA, run_collapse(ca, h->stream));
-        HIP_LAUNCH(h, K_MEANSCAN, launch_meanscan(p.Rp, fa, h->stream));
-        return em_update();
-    }
+    rt.fuse_gram = cov_fuses_gram(p.Rp, N) && o.fuse_gram;
+    rt.fill = !o.no_pfill && want_P;
+    // Rp = 32 (config 4): the fill is 0.86 GB of stores -- beside the collapse they cost it 0.4 ms of its 1.13; beside the latency-bound
+    // scan they are free.  So: cov -> [event] ; collapse (side) -> [event] ; fill on the third stream after both, scan on the caller's
+    // stream after the collapse, join at the end.  (A trickle of these stores from a few persistent workgroups UNDER the collapse was
+    // tried: the collapse lost what the scan gained -- profiles/r04/ab_pfill_trickle_c4.txt.)
+    rt.fill_late = rt.fill && use_wide2;
     // Measured on MI355X (profiles/r01): every cross-stream event edge costs 7-25 us, more than the
     // overlap buys at B = 1024, so the default is one sub-batch; DFM_SUBBATCH keeps the knob for big batches.
-    int S = h->opt.subbatch > 0 ? h->opt.subbatch : 1;
+    int S = o.subbatch > 0 ? o.subbatch : 1;
     if (S > B) S = B;
     if (use_wide2) S = 1;                                     // (its workspace -- W, tile queues -- is laid out for the whole batch)
-    if (S == 1 && h->opt.pass_fused && use_mfma && pass_fused_supported(p.Rp, T, N) && h->opt.collapse_variant == 0) {
-        // ONE launch: persistent workgroups, b_t / w_t and the covariance tables never leave the chip (pass_fused.hip)
-        fa.Lam = pp.Lam; fa.Rv = Rv;
-        if (h->opt.scan_abl & 256) {                                  // phase stamps of every replicate -> scol; readable through the
-            ca.scol = at<double>(h, p.scol);                      // workspace dump below (diagnostics)
-            if (const char* f = diag_env("DFM_PF_PROF_FILE")) h->prof_file = f;
-        }
-        HIP_LAUNCH(h, K_PASS_FUSED, launch_pass_fused(ca, fa, h->opt.pass_nsw, h->opt.pass_ncov, h->opt.pf_wpark, h->num_cu, h->stream));
-        if ((h->opt.scan_abl & 256) && !h->prof_file.empty()) {       // diagnostics: dump the stamps of this pass (synchronises)
-            std::vector<double> st((size_t)B * T);
-            HIP_TRY(h, hipStreamSynchronize(h->stream));
-            HIP_TRY(h, hipMemcpy(st.data(), ca.scol, st.size() * sizeof(double), hipMemcpyDeviceToHost));
-            if (FILE* fp = fopen(h->prof_file.c_str(), "w")) {
-                for (int bb = 0; bb < B; ++bb) {
-                    fprintf(fp, "%d", bb);
-                    for (int k = 0; k < 56; ++k) fprintf(fp, " %.0f", st[(size_t)bb * T + k]);
-                    fprintf(fp, "\n");
-                }
-                fclose(fp);
-            }
-        }
-        return em_update();
-    }
-    if (S == 1 && use_mfma && !fuse_gram && !h->opt.no_fuse_cov && collapse_mfma_fuses_cov(p.Rp, N)) {
-        // ONE stream, two launches: [Gram + covariance workgroups + P_smooth fill | streaming collapse] -> scan.
-        // The covariance waves sit at the front of the collapse grid (resident first, no cross-stream events).
-        if (h->opt.fused_gram) { fa.Lam = pp.Lam; fa.Rv = Rv; }   // the covariance workgroups compute their Gram matrices themselves
-        else HIP_LAUNCH(h, K_GRAM, run_gram(h->stream));
-        ca.fuse_cov = &fa;
-        HIP_LAUNCH(h, K_COLLAPSE_MFMA, launch_collapse_dma(p.Rp, ca, h->stream, cvariant));
-        ca.fuse_cov = nullptr;
-        if (P_smooth) fa.abl |= 1;
-        HIP_LAUNCH(h, K_MEANSCAN, launch_meanscan(p.Rp, fa, h->stream));
-        return em_update();
-    }
     // Wide states (collapse_wide2), DFM_WIDE_SUB = n > 1 (diagnostics; default off): the batch in n sub-batches, each a complete
     // small batch of its own (own W workspace slice, own tile queues), the mean scan of sub-batch s beside the collapse of sub-batch
     // s + 1.  MEASURED SLOWER at config 4 (B = 256): 1.39 ms -> 1.56 (n = 2) -> 1.81 (n = 4).  The scan is a latency chain per
     // replicate -- 0.41 ms for 256 replicates, 0.46 ms for 128 -- so a sub-batch's scan hides nothing and the last one still runs alone.
-    static const int wide_sub = [] { const char* v = diag_env("DFM_WIDE_SUB"); return v ? atoi(v) : 1; }();
-    const int Sw = (use_wide2 && wide_sub > 1 && wide_sub <= 8 && B >= 32 * wide_sub) ? wide_sub : 1;
-    if (S == 1 && Sw > 1) {
-        while ((int)h->ev_sub.size() < Sw + 1) {
-            hipEvent_t e;
-            HIP_TRY(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            h->ev_sub.push_back(e);
-        }
-        const int bmax = (B + Sw - 1) / Sw;
-        const size_t slice = collapse_wide2_ws_bytes(bmax, N, p.Rp);
-        auto sub_lo = [&](int s_) { return (int)((long long)B * s_ / Sw); };
-        auto sub_args = [&](int s_) {
-            const int b0 = sub_lo(s_), b1 = sub_lo(s_ + 1);
-            CollapseArgs c = ca;
-            c.B = b1 - b0;
-            c.panel = ca.panel + (size_t)b0 * T * N; c.Lam = ca.Lam + (size_t)b0 * N * p.Rp; c.Rv = ca.Rv + (size_t)b0 * N;
-            c.bcol = ca.bcol + (size_t)b0 * T * (ca.bst > 0 ? ca.bst : p.Rp); c.scol = ca.scol + (size_t)b0 * T; c.ssum = ca.ssum + (size_t)b0 * kSsumSlots;
-            c.Cfull = ca.Cfull + (size_t)b0 * p.Rp * p.Rp; c.ldfull = ca.ldfull + b0;
-            return c;
-        };
-        auto sub_ws = [&](int s_) { return reinterpret_cast<double*>(reinterpret_cast<char*>(Wwide) + (size_t)s_ * slice); };
-        for (int s_ = 0; s_ < Sw; ++s_) HIP_LAUNCH(h, K_GRAM, launch_wide_prep(sub_args(s_), sub_ws(s_), p.Rp, h->stream, p.r));
-        HIP_TRY(h, hipEventRecord(h->ev_fork, h->stream));
-        HIP_TRY(h, hipStreamWaitEvent(h->side, h->ev_fork, 0));
-        HIP_LAUNCH(h, K_COV, launch_cov(p.Rp, fa, h->stream));      // resident before the collapse fills the CUs
-        HIP_TRY(h, hipEventRecord(h->ev_sub[Sw], h->stream));                         // covariance tables done
-        for (int s_ = 0; s_ < Sw; ++s_) {
-            { ProfScope ps(h, K_COLLAPSE_WIDE, h->side); HIP_TRY(h, launch_collapse_wide2(sub_args(s_), sub_ws(s_), p.Rp, p.r, h->num_cu, h->side)); }
-            HIP_TRY(h, hipEventRecord(h->ev_sub[s_], h->side));
-        }
-        const bool fill = !h->opt.no_pfill && P_smooth;
-        if (fill) {                       // 0.86 GB of stores at config 4: beside the scan of the last sub-batch, not beside the collapse
-            HIP_TRY(h, hipStreamWaitEvent(h->post, h->ev_sub[Sw], 0));
-            HIP_TRY(h, hipStreamWaitEvent(h->post, h->ev_sub[Sw - 1], 0));
-            { ProfScope ps(h, K_PFILL, h->post); HIP_TRY(h, launch_pfill(p.Rp, fa, h->post)); }
-            HIP_TRY(h, hipEventRecord(h->ev_post, h->post));
-            fa.abl |= 1;
-        }
-        for (int s_ = 0; s_ < Sw; ++s_) {
-            HIP_TRY(h, hipStreamWaitEvent(h->stream, h->ev_sub[s_], 0));
-            FastArgs fs = fa;
-            fs.b0 = sub_lo(s_); fs.B = sub_lo(s_ + 1) - sub_lo(s_);
-            HIP_LAUNCH(h, K_MEANSCAN, launch_meanscan(p.Rp, fs, h->stream));
-        }
-        if (fill) HIP_TRY(h, hipStreamWaitEvent(h->stream, h->ev_post, 0));
-        return em_update();
+    const int Sw = (use_wide2 && o.wide_sub > 1 && o.wide_sub <= 8 && B >= 32 * o.wide_sub) ? o.wide_sub : 1;
+    if (o.no_side) rt.sched = FS_IN_ORDER;   // diagnostics: everything in order on the main stream
+    else if (S > 1) { rt.sched = FS_SUBBATCH; rt.S = S; }
+    // ONE launch: persistent workgroups, b_t / w_t and the covariance tables never leave the chip (pass_fused.hip)
+    else if (o.pass_fused && use_mfma && pass_fused_supported(p.Rp, T, N) && cv == 0) rt.sched = FS_ONE_LAUNCH;
+    // ONE stream, two launches: [Gram + covariance workgroups + P_smooth fill | streaming collapse] -> scan.
+    // The covariance waves sit at the front of the collapse grid (resident first, no cross-stream events).
+    else if (use_mfma && !rt.fuse_gram && !o.no_fuse_cov && collapse_mfma_fuses_cov(p.Rp, N)) rt.sched = FS_TWO_LAUNCH;
+    else if (Sw > 1) { rt.sched = FS_WIDE_SUB; rt.S = Sw; }
+    else rt.sched = FS_FORKED;
+    // (FS_TWO_LAUNCH, DFM_FUSED_GRAM=0: gram_kernel as its own launch in front)
+    rt.cov_gram = rt.fuse_gram || rt.sched == FS_ONE_LAUNCH || (rt.sched == FS_TWO_LAUNCH && o.fused_gram);
+    return rt;
+}
+
+FastArgs fast_args(dfm_handle* h, const Plan& p, const PassIo& io, const CollapseArgs& ca, const FastRoute& rt) {
+    FastArgs fa;
+    memset(&fa, 0, sizeof(fa));
+    fa.B = io.B; fa.T = io.T; fa.N = io.N; fa.r = io.out_r; fa.L = fast_chunk_len(p.Rp, io.T);
+    fa.rstate = p.r;
+    fa.A = io.pp.A; fa.Q = io.pp.Q; fa.mu0 = io.pp.mu0; fa.P0 = io.pp.P0;
+    fa.Cfull = ca.Cfull; fa.ldfull = ca.ldfull;
+    fa.tab = at<double>(h, p.f_tab); fa.E = at<int>(h, p.f_E); fa.stead = at<double>(h, p.f_stead);
+    fa.xi0 = at<double>(h, p.f_xi0); fa.PT = at<double>(h, p.f_PT); fa.llc = at<double>(h, p.f_llc);
+    fa.fill = at<int>(h, p.f_fill); fa.PsInf = at<double>(h, p.f_PsInf);
+    fa.bcol = ca.bcol; fa.ssum = ca.ssum; fa.wtab = at<double>(h, p.wtab); fa.wrep = wtab_rows(true, p.Rp, io.T) * (size_t)p.Rp;
+    if (rt.ntile) { fa.scol = ca.scol; fa.ntile = rt.ntile; }
+    fa.bst = rt.bst; fa.nseg = rt.wpr;
+    if (rt.cov_gram) { fa.Lam = io.pp.Lam; fa.Rv = io.Rv; }
+    fa.f_smooth = io.f_smooth; fa.P_smooth = io.P_smooth; fa.loglik = io.loglik;
+    fa.abl = h->opt.scan_abl;
+    if (io.em) {   // EM: covariance sums from cov_kernel, E[f_0 | X] from meanscan (workspace slots of S10 / S00 reused)
+        fa.SP11 = at<double>(h, p.S10); fa.SU = at<double>(h, p.S00); fa.P0s = at<double>(h, p.P0s);
+        fa.f0s = at<double>(h, p.f0s);
     }
-    if (S == 1) {
-        // The covariance kernel (128 waves, 224 VGPRs each) must be resident BEFORE the streaming collapse fills
-        // every CU, or it waits for the collapse to drain (measured: 285 us instead of 90).  It therefore goes
-        // first on the caller's stream, and the collapse is the forked work: its queue starts ~6 us later.
-        if (!fuse_gram || use_wide2) HIP_LAUNCH(h, K_GRAM, run_gram(h->stream));   // 12 us, alone
-        HIP_TRY(h, hipEventRecord(h->ev_fork, h->stream));
-        HIP_TRY(h, hipStreamWaitEvent(h->side, h->ev_fork, 0));
-        HIP_LAUNCH(h, K_COV, (h->opt.cov_wave && p.Rp == 8 && !fuse_gram) ? launch_cov_wave(fa, h->stream) : launch_cov(p.Rp, fa, h->stream));
-        { ProfScope ps(h, use_wide ? K_COLLAPSE_WIDE : use_mfma ? K_COLLAPSE_MFMA : K_COLLAPSE_DMA, h->side); HIP_TRY(h, run_collapse(ca, h->side)); }
-        HIP_TRY(h, hipEventRecord(h->ev_join, h->side));
-        const bool fill = !h->opt.no_pfill && P_smooth;
-        // Rp = 32 (config 4): the fill is 0.86 GB of stores -- beside the collapse they cost it 0.4 ms of its 1.13; beside the
-        // latency-bound scan they are free.  So: cov -> [event] ; collapse (side) -> [event] ; fill on the third stream
-        // after both, scan on the caller's stream after the collapse, join at the end.
-        // (A trickle of these stores from a few persistent workgroups UNDER the collapse was tried: the collapse lost what the scan
-        // gained -- profiles/r04/ab_pfill_trickle_c4.txt.)
-        const bool fill_late = fill && use_wide2;
-        if (fill && !fill_late) {         // the data-independent rows of P_smooth, beside the collapse
-            ProfScope ps(h, K_PFILL);
-            HIP_TRY(h, launch_pfill(p.Rp, fa, h->stream));
-            fa.abl |= 1;
-        }
-        if (fill_late) {
-            if (h->ev_sub.empty()) {
-                hipEvent_t e;
-                HIP_TRY(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-                h->ev_sub.push_back(e);
-            }
-            HIP_TRY(h, hipEventRecord(h->ev_sub[0], h->stream));            // cov_kernel's outputs
-            HIP_TRY(h, hipStreamWaitEvent(h->post, h->ev_sub[0], 0));
-            HIP_TRY(h, hipStreamWaitEvent(h->post, h->ev_join, 0));        // ... and not before the collapse is done
-            { ProfScope ps(h, K_PFILL, h->post); HIP_TRY(h, launch_pfill(p.Rp, fa, h->post)); }
-            HIP_TRY(h, hipEventRecord(h->ev_post, h->post));
-            fa.abl |= 1;
-        }
-        HIP_TRY(h, hipStreamWaitEvent(h->stream, h->ev_join, 0));
-        HIP_LAUNCH(h, K_MEANSCAN, launch_meanscan(p.Rp, fa, h->stream));
-        if (fill_late) HIP_TRY(h, hipStreamWaitEvent(h->stream, h->ev_post, 0));
-        return em_update();
-    }
-    while ((int)h->ev_sub.size() < S) {
+    return fa;
+}
+// after the scan: transition M-step + bookkeeping from the sufficient statistics
+int em_update(dfm_handle* h, const Plan& p, const PassIo& io, const FastArgs& fa) {
+    const EmOpts* em = io.em;
+    if (!em) return 0;
+    EmUpdArgs ua;
+    memset(&ua, 0, sizeof(ua));
+    ua.B = io.B; ua.T = io.T; ua.fsm = io.f_smooth; ua.f0s = fa.f0s; ua.SP11 = fa.SP11; ua.SU = fa.SU; ua.P0s = fa.P0s;
+    ua.PT = fa.PT; ua.loglik = io.loglik; ua.S11 = at<double>(h, p.S11); ua.S11inv = at<double>(h, p.Sxf);
+    ua.A_out = em->A_out; ua.Q_out = em->Q_out; ua.mu0_out = em->mu0_out; ua.P0_out = em->P0_out;
+    ua.active = em->active; ua.iters = em->iters; ua.ll_path = em->ll_path; ua.k = em->k; ua.max_iter = em->max_iter;
+    ua.tol = em->tol;
+    if (h->defer_em) { h->deferred_em = ua; h->have_deferred_em = true; return 0; }
+    HIP_LAUNCH(h, K_EM_UPDATE, launch_em_update(p.Rp, ua, h->stream));
+    return 0;
+}
+
+// Gram matrix (+ W for the wide2 collapse) and the streaming collapse of this route, on stream `st`
+hipError_t fast_gram(dfm_handle* h, const Plan& p, const FastRoute& rt, const CollapseArgs& ca, hipStream_t st) {
+    if (rt.wide2()) return launch_wide_prep(ca, at<double>(h, p.Wwide), p.Rp, st, p.r);
+    return gram_supported(p.Rp, ca.N) ? launch_gram(p.Rp, ca, st) : launch_gram_wide(p.Rp, ca, st);
+}
+hipError_t fast_collapse(dfm_handle* h, const Plan& p, const FastRoute& rt, const CollapseArgs& c, hipStream_t st) {
+    if (rt.wide2()) return launch_collapse_wide2(c, at<double>(h, p.Wwide), p.Rp, p.r, h->num_cu, st);
+    return rt.collapse == FC_WIDE ? launch_collapse_wide(p.Rp, c, st) : launch_collapse_dma(p.Rp, c, st, rt.cvariant);
+}
+// the idioms of the schedules: h->ev_sub grown to n events; an edge (record ev on `from`, `to` waits for it); the late P_smooth
+// fill on post, behind the two events that say its inputs are written and the collapse has left the memory system to it --
+// whoever calls it waits for h->ev_post on the caller's stream behind its scans
+int grow_ev_sub(dfm_handle* h, int n) {
+    while ((int)h->ev_sub.size() < n) {
         hipEvent_t e;
         HIP_TRY(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
         h->ev_sub.push_back(e);
     }
-    // fork: side and post start after everything already enqueued on the main stream (parameters, memsets)
-    HIP_TRY(h, hipEventRecord(h->ev_fork, h->stream));
-    HIP_TRY(h, hipStreamWaitEvent(h->side, h->ev_fork, 0));
-    HIP_TRY(h, hipStreamWaitEvent(h->post, h->ev_fork, 0));
-    if (!fuse_gram) { ProfScope ps(h, K_GRAM, h->side); HIP_TRY(h, run_gram(h->side)); }
-    { ProfScope ps(h, K_COV, h->side); HIP_TRY(h, launch_cov(p.Rp, fa, h->side)); }
+    return 0;
+}
+int edge(dfm_handle* h, hipEvent_t ev, hipStream_t from, hipStream_t to) {
+    HIP_TRY(h, hipEventRecord(ev, from)); HIP_TRY(h, hipStreamWaitEvent(to, ev, 0));
+    return 0;
+}
+int late_pfill(dfm_handle* h, const Plan& p, const FastArgs& fa, hipEvent_t cov_done, hipEvent_t collapse_done) {
+    HIP_TRY(h, hipStreamWaitEvent(h->post, cov_done, 0));
+    HIP_TRY(h, hipStreamWaitEvent(h->post, collapse_done, 0));
+    { ProfScope ps(h, K_PFILL, h->post); HIP_TRY(h, launch_pfill(p.Rp, fa, h->post)); }
+    HIP_TRY(h, hipEventRecord(h->ev_post, h->post));
+    return 0;
+}
+
+int pass_in_order(dfm_handle* h, const Plan& p, const CollapseArgs& ca, const FastArgs& fa, const FastRoute& rt) {
+    if (!rt.fuse_gram) HIP_LAUNCH(h, K_GRAM, fast_gram(h, p, rt, ca, h->stream));
+    HIP_LAUNCH(h, K_COV, launch_cov(p.Rp, fa, h->stream));
+    HIP_LAUNCH(h, rt.kid, fast_collapse(h, p, rt, ca, h->stream));
+    HIP_LAUNCH(h, K_MEANSCAN, launch_meanscan(p.Rp, fa, h->stream));
+    return 0;
+}
+// DFM_SCAN_ABL & 256 (diagnostics): the one-launch pass leaves phase stamps of every replicate in scol; with DFM_PF_PROF_FILE
+// they are dumped there after every pass (synchronises)
+int dump_pass_stamps(dfm_handle* h, const CollapseArgs& ca) {
+    if (const char* f = diag_env("DFM_PF_PROF_FILE")) h->prof_file = f;
+    if (h->prof_file.empty()) return 0;
+    std::vector<double> st((size_t)ca.B * ca.T);
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, hipMemcpy(st.data(), ca.scol, st.size() * sizeof(double), hipMemcpyDeviceToHost));
+    if (FILE* fp = fopen(h->prof_file.c_str(), "w")) {
+        for (int bb = 0; bb < ca.B; ++bb) {
+            fprintf(fp, "%d", bb);
+            for (int k = 0; k < 56; ++k) fprintf(fp, " %.0f", st[(size_t)bb * ca.T + k]);
+            fprintf(fp, "\n");
+        }
+        fclose(fp);
+    }
+    return 0;
+}
+int pass_one_launch(dfm_handle* h, const CollapseArgs& ca, const FastArgs& fa) {
+    HIP_LAUNCH(h, K_PASS_FUSED, launch_pass_fused(ca, fa, h->opt.pass_nsw, h->opt.pass_ncov, h->opt.pf_wpark, h->num_cu, h->stream));
+    return (h->opt.scan_abl & 256) ? dump_pass_stamps(h, ca) : 0;
+}
+int pass_two_launch(dfm_handle* h, const Plan& p, CollapseArgs& ca, FastArgs& fa, const FastRoute& rt) {
+    if (!rt.cov_gram) HIP_LAUNCH(h, K_GRAM, fast_gram(h, p, rt, ca, h->stream));   // else the covariance workgroups compute their Gram matrices themselves
+    ca.fuse_cov = &fa;
+    HIP_LAUNCH(h, rt.kid, fast_collapse(h, p, rt, ca, h->stream));
+    ca.fuse_cov = nullptr;
+    if (fa.P_smooth) fa.abl |= 1;
+    HIP_LAUNCH(h, K_MEANSCAN, launch_meanscan(p.Rp, fa, h->stream));
+    return 0;
+}
+int pass_wide_sub(dfm_handle* h, const Plan& p, const CollapseArgs& ca, FastArgs& fa, const FastRoute& rt) {
+    const int B = ca.B, T = ca.T, N = ca.N, Sw = rt.S;
+    if (int rc = grow_ev_sub(h, Sw + 1)) return rc;
+    const int bmax = (B + Sw - 1) / Sw;
+    const size_t slice = collapse_wide2_ws_bytes(bmax, N, p.Rp);
+    auto sub_lo = [&](int s_) { return (int)((long long)B * s_ / Sw); };
+    auto sub_args = [&](int s_) {
+        const int b0 = sub_lo(s_), b1 = sub_lo(s_ + 1);
+        CollapseArgs c = ca;
+        c.B = b1 - b0;
+        c.panel = ca.panel + (size_t)b0 * T * N; c.Lam = ca.Lam + (size_t)b0 * N * p.Rp; c.Rv = ca.Rv + (size_t)b0 * N;
+        c.bcol = ca.bcol + (size_t)b0 * T * (ca.bst > 0 ? ca.bst : p.Rp); c.scol = ca.scol + (size_t)b0 * T; c.ssum = ca.ssum + (size_t)b0 * kSsumSlots;
+        c.Cfull = ca.Cfull + (size_t)b0 * p.Rp * p.Rp; c.ldfull = ca.ldfull + b0;
+        return c;
+    };
+    auto sub_ws = [&](int s_) { return reinterpret_cast<double*>(at<char>(h, p.Wwide) + (size_t)s_ * slice); };
+    for (int s_ = 0; s_ < Sw; ++s_) HIP_LAUNCH(h, K_GRAM, launch_wide_prep(sub_args(s_), sub_ws(s_), p.Rp, h->stream, p.r));
+    if (int rc = edge(h, h->ev_fork, h->stream, h->side)) return rc;
+    HIP_LAUNCH(h, K_COV, launch_cov(p.Rp, fa, h->stream));      // resident before the collapse fills the CUs
+    HIP_TRY(h, hipEventRecord(h->ev_sub[Sw], h->stream));                         // covariance tables done
+    for (int s_ = 0; s_ < Sw; ++s_) {
+        { ProfScope ps(h, rt.kid, h->side); HIP_TRY(h, launch_collapse_wide2(sub_args(s_), sub_ws(s_), p.Rp, p.r, h->num_cu, h->side)); }
+        HIP_TRY(h, hipEventRecord(h->ev_sub[s_], h->side));
+    }
+    if (rt.fill_late) {               // 0.86 GB of stores at config 4: beside the scan of the last sub-batch, not beside the collapse
+        if (int rc = late_pfill(h, p, fa, h->ev_sub[Sw], h->ev_sub[Sw - 1])) return rc;
+        fa.abl |= 1;
+    }
+    for (int s_ = 0; s_ < Sw; ++s_) {
+        HIP_TRY(h, hipStreamWaitEvent(h->stream, h->ev_sub[s_], 0));
+        FastArgs fs = fa;
+        fs.b0 = sub_lo(s_); fs.B = sub_lo(s_ + 1) - sub_lo(s_);
+        HIP_LAUNCH(h, K_MEANSCAN, launch_meanscan(p.Rp, fs, h->stream));
+    }
+    if (rt.fill_late) HIP_TRY(h, hipStreamWaitEvent(h->stream, h->ev_post, 0));
+    return 0;
+}
+int pass_forked(dfm_handle* h, const Plan& p, const CollapseArgs& ca, FastArgs& fa, const FastRoute& rt) {
+    // The covariance kernel (128 waves, 224 VGPRs each) must be resident BEFORE the streaming collapse fills
+    // every CU, or it waits for the collapse to drain (measured: 285 us instead of 90).  It therefore goes
+    // first on the caller's stream, and the collapse is the forked work: its queue starts ~6 us later.
+    if (!rt.fuse_gram || rt.wide2()) HIP_LAUNCH(h, K_GRAM, fast_gram(h, p, rt, ca, h->stream));   // 12 us, alone
+    if (int rc = edge(h, h->ev_fork, h->stream, h->side)) return rc;
+    HIP_LAUNCH(h, K_COV, (h->opt.cov_wave && p.Rp == 8 && !rt.fuse_gram) ? launch_cov_wave(fa, h->stream) : launch_cov(p.Rp, fa, h->stream));
+    { ProfScope ps(h, rt.kid, h->side); HIP_TRY(h, fast_collapse(h, p, rt, ca, h->side)); }
     HIP_TRY(h, hipEventRecord(h->ev_join, h->side));
-    HIP_TRY(h, hipStreamWaitEvent(h->post, h->ev_join, 0));
+    if (rt.fill && !rt.fill_late) {   // the data-independent rows of P_smooth, beside the collapse
+        HIP_LAUNCH(h, K_PFILL, launch_pfill(p.Rp, fa, h->stream));
+        fa.abl |= 1;
+    }
+    if (rt.fill_late) {               // (why late: fast_route)
+        if (int rc = grow_ev_sub(h, 1)) return rc;
+        HIP_TRY(h, hipEventRecord(h->ev_sub[0], h->stream));            // cov_kernel's outputs
+        if (int rc = late_pfill(h, p, fa, h->ev_sub[0], h->ev_join)) return rc;   // ... and not before the collapse is done
+        fa.abl |= 1;
+    }
+    HIP_TRY(h, hipStreamWaitEvent(h->stream, h->ev_join, 0));
+    HIP_LAUNCH(h, K_MEANSCAN, launch_meanscan(p.Rp, fa, h->stream));
+    if (rt.fill_late) HIP_TRY(h, hipStreamWaitEvent(h->stream, h->ev_post, 0));
+    return 0;
+}
+// gram + cov on the side stream, beside the streaming collapse on the main stream; the batch is cut
+// into sub-batches so that the (latency-bound) meanscan of sub-batch s runs on a third stream beside the
+// (bandwidth-bound) collapse of sub-batch s+1.
+int pass_subbatch(dfm_handle* h, const Plan& p, const CollapseArgs& ca, const FastArgs& fa, const FastRoute& rt) {
+    const int B = ca.B, S = rt.S;
+    if (int rc = grow_ev_sub(h, S)) return rc;
+    // fork: side and post start after everything already enqueued on the main stream (parameters, memsets)
+    if (int rc = edge(h, h->ev_fork, h->stream, h->side)) return rc;
+    HIP_TRY(h, hipStreamWaitEvent(h->post, h->ev_fork, 0));
+    if (!rt.fuse_gram) { ProfScope ps(h, K_GRAM, h->side); HIP_TRY(h, fast_gram(h, p, rt, ca, h->side)); }
+    { ProfScope ps(h, K_COV, h->side); HIP_TRY(h, launch_cov(p.Rp, fa, h->side)); }
+    if (int rc = edge(h, h->ev_join, h->side, h->post)) return rc;
     for (int s = 0; s < S; ++s) {
         const int b0 = (int)((long long)B * s / S), b1 = (int)((long long)B * (s + 1) / S);
         CollapseArgs cs = ca;
         cs.b0 = b0; cs.B = b1 - b0;
-        HIP_LAUNCH(h, use_mfma ? K_COLLAPSE_MFMA : K_COLLAPSE_DMA, launch_collapse_dma(p.Rp, cs, h->stream, cvariant));
-        HIP_TRY(h, hipEventRecord(h->ev_sub[s], h->stream));
-        HIP_TRY(h, hipStreamWaitEvent(h->post, h->ev_sub[s], 0));
+        HIP_LAUNCH(h, rt.kid, launch_collapse_dma(p.Rp, cs, h->stream, rt.cvariant));   // (the one collapse that takes b0)
+        if (int rc = edge(h, h->ev_sub[s], h->stream, h->post)) return rc;
         FastArgs fs = fa;
         fs.b0 = b0; fs.B = b1 - b0;
         { ProfScope ps(h, K_MEANSCAN, h->post); HIP_TRY(h, launch_meanscan(p.Rp, fs, h->post)); }
     }
-    HIP_TRY(h, hipEventRecord(h->ev_post, h->post));
-    HIP_TRY(h, hipStreamWaitEvent(h->stream, h->ev_post, 0));   // join
-    return em_update();
+    return edge(h, h->ev_post, h->post, h->stream);   // join
 }
 
-// Enqueue collapse + recursion for already-planned workspace.  out_r = factor dimension of the
-// f_smooth / P_smooth layout (caller's r for a plain pass, Rp for EM-internal buffers).
-int enqueue_pass(dfm_handle* h, const Plan& p, int B, int T, int N, int out_r, const double* panel,
-                 const PaddedParams& pp, const double* Rv, double* f_smooth, double* P_smooth, double* loglik,
-                 const EmOpts* em) {
-    if (p.fast) return enqueue_pass_fast(h, p, B, T, N, out_r, panel, pp, Rv, f_smooth, P_smooth, loglik, em);
-    CollapseArgs ca;
-    memset(&ca, 0, sizeof(ca));
-    ca.B = B; ca.T = T; ca.N = N;
-    ca.panel = panel; ca.Lam = pp.Lam; ca.Rv = Rv;
-    ca.bcol = at<double>(h, p.bcol); ca.scol = at<double>(h, p.scol); ca.nobs = at<int>(h, p.nobs);
-    ca.ldrow = at<double>(h, p.ldrow); ca.Ct = at<double>(h, p.Ct); ca.Cfull = at<double>(h, p.Cfull);
-    ca.ldfull = at<double>(h, p.ldfull); ca.status = h->status_dev;
-    ca.obs_chunk = nullptr; ca.obs_table = nullptr; ca.obs_L = 0;
-    ca.kreal = (p.kdim > 0 && p.Rc == 0) ? p.kdim : 0;          // (companion state observed on every block: the AR idiosyncratic model)
+int enqueue_pass_fast(dfm_handle* h, const Plan& p, const PassIo& io) {
+    const FastRoute rt = fast_route(h->opt, p, io.B, io.T, io.N, h->num_cu, io.P_smooth != nullptr);
+    CollapseArgs ca = collapse_args(h, p, io);
+    ca.ssum = at<double>(h, p.f_ssum); ca.wpr = rt.wpr; ca.bst = rt.bst;
+    FastArgs fa = fast_args(h, p, io, ca, rt);
+    int rc = 0;
+    switch (rt.sched) {
+        case FS_IN_ORDER: rc = pass_in_order(h, p, ca, fa, rt); break;
+        case FS_ONE_LAUNCH: rc = pass_one_launch(h, ca, fa); break;
+        case FS_TWO_LAUNCH: rc = pass_two_launch(h, p, ca, fa, rt); break;
+        case FS_WIDE_SUB: rc = pass_wide_sub(h, p, ca, fa, rt); break;
+        case FS_FORKED: rc = pass_forked(h, p, ca, fa, rt); break;
+        case FS_SUBBATCH: rc = pass_subbatch(h, p, ca, fa, rt); break;
+    }
+    return rc ? rc : em_update(h, p, io, fa);
+}
+
+// the general path: which recursion launch_recursion will pick, as far as enqueue_pass has to know, and which collapse feeds it
+enum GeneralCollapse {
+    GC_COMP_TABLE,   // companion state: collapse_miss_kernel's chunk table, then chunk_unbridge_kernel
+    GC_CHUNK_TABLE,  // collapse_miss_kernel writes the table recursion_chunk_kernel reads
+    GC_MISS,         // collapse_miss_kernel, rows in the sequential kernels' layout
+    GC_WIDE2,        // Rp = 32 beyond the register tiling: wide prep, collapse_wide2, ct_miss_wide
+    GC_PLAIN         // collapse_kernel
+};
+struct GeneralRoute { bool chunked, tiled; int ct_r, Rcol; GeneralCollapse collapse; };
+GeneralRoute general_route(const RouteOpts& o, const Plan& p, int N, const RecursionArgs& ra) {
+    GeneralRoute g;
+    // (the kernel files' own predicates, asked once)
+    g.chunked = ra.wave && recursion_chunk_supported(p.Rp, ra); g.tiled = ra.wave && recursion_tile_supported(p.Rp, ra);
+    g.Rcol = p.Rc ? p.Rc : p.Rp;
+    // C_t rows: the packed leading block when recursion_tile_kernel reads them (it executes ceil(r / 4) block pivots of the 32-wide
+    // state: the rest is padding whose entries equal Cfull's), the full Rp (Rp + 1) / 2 layout for the other recursion kernels
+    g.ct_r = 0;
+    if (g.tiled && p.Wwide != (size_t)-1 && N > collapse_max_n(g.Rcol) && ct_miss_wide_compact_ok(N, 4 * ((p.r + 3) / 4))) g.ct_r = 4 * ((p.r + 3) / 4);
+    // the time-chunked recursion reads one table row per period (C_t, b_t, s_t, n_t log 2 pi + log det R_t): at Rp = 8 with loadings as
+    // wide as the state collapse_miss_kernel writes it directly
+    // (r <= 4 widened to the 8-wide state, Plan::Rc = 2 / 4: the kernel pads the loadings with zero columns in its LDS tables --
+    // CollapseArgs::lam_w -- and the table is the 8-wide one the chunks read anyway; collapse_kernel<4> + chunk_bridge_kernel took
+    // 0.25 ms per 1024 replicates of the Stock-Watson window where this takes 0.1)
+    const bool narrow_tab = p.Rc > 0 && p.Rc < 8 && p.kdim == 0 && p.rl == p.Rc && !o.narrow_tab_off;
+    const bool table = g.chunked && !o.collapse_miss_old && (p.Rc == 0 || narrow_tab);
+    // companion states (VAR(p) factor dynamics) with loadings up to 4 wide: the same table, then EVERY replicate's rows written
+    // back in the layout the sequential kernels read (chunk_unbridge_kernel<Rc>: b_t, s_t, C_t of every period, nobs = 0) --
+    // collapse_kernel<4> took 0.235 ms per 1024 replicates of the Stock-Watson window where these two take 0.12
+    const bool comp_table = p.kdim > 0 && p.kb == 0 && p.Rc > 0 && p.Rc < 8 && p.ck_rows != (size_t)-1 && p.ck_obs != (size_t)-1 &&
+                            collapse_miss_supported(8, N);
+    if (comp_table) g.collapse = GC_COMP_TABLE;
+    else if (table && p.ck_rows != (size_t)-1 && collapse_miss_supported(8, N) && (p.Rc == 0 ? g.Rcol == 8 : true)) g.collapse = GC_CHUNK_TABLE;
+    else if (!o.collapse_miss_old && collapse_miss_supported(g.Rcol, N)) g.collapse = GC_MISS;
+    else if (p.Wwide != (size_t)-1 && N > collapse_max_n(g.Rcol)) g.collapse = GC_WIDE2;   // (config 4 with missing cells)
+    else g.collapse = GC_PLAIN;
+    return g;
+}
+RecursionArgs recursion_args(dfm_handle* h, const Plan& p, const PassIo& io, const CollapseArgs& ca) {
+    const EmOpts* em = io.em;
     RecursionArgs ra;
     memset(&ra, 0, sizeof(ra));
-    ra.B = B; ra.T = T; ra.N = N; ra.r = out_r;
+    ra.B = io.B; ra.T = io.T; ra.N = io.N; ra.r = io.out_r;
     ra.rstate = p.r; ra.cov = p.cov ? 1 : 0; ra.Rc = p.Rc; ra.rl = p.rl; ra.kdim = p.kdim; ra.kb = p.kb; ra.ka = p.ka; ra.qsing = p.qsing; ra.wave = h->opt.no_rec_wave ? 0 : 1;
     ra.pair_bmax = h->opt.pair_bmax >= 0 ? h->opt.pair_bmax : 4 * h->num_cu;
-    ra.A = pp.A; ra.Q = pp.Q; ra.mu0 = pp.mu0; ra.P0 = pp.P0;
+    ra.A = io.pp.A; ra.Q = io.pp.Q; ra.mu0 = io.pp.mu0; ra.P0 = io.pp.P0;
     ra.bcol = ca.bcol; ra.scol = ca.scol; ra.nobs = ca.nobs; ra.ldrow = ca.ldrow; ra.Ct = ca.Ct;
     ra.Cfull = ca.Cfull; ra.ldfull = ca.ldfull;
-    ra.ZJtab = at<double>(h, p.ZJ); ra.wtab = at<double>(h, p.wtab); ra.eidx = nullptr;
+    ra.ZJtab = at<double>(h, p.ZJ); ra.wtab = at<double>(h, p.wtab);
     ra.chunk_scr = at<double>(h, p.ck_scr); ra.chunk_W = h->opt.chunk_w; ra.chunk_tol = h->opt.chunk_tol; ra.chunk_obs = at<double>(h, p.ck_obs); ra.chunk_cst = at<double>(h, p.ck_cst); ra.chunk_term = at<double>(h, p.ck_term); ra.chunk_fail = at<int>(h, p.ck_fail);
     ra.chunk_skip = at<int>(h, p.ck_skip);
     ra.tile_scr = at<double>(h, p.tk_scr); ra.tile_scr_bytes = p.tk_bytes; ra.tile_nc = h->opt.tile_nc; ra.tile_w = h->opt.tile_w; ra.num_cu = h->num_cu;
-    ra.f_smooth = f_smooth; ra.P_smooth = P_smooth; ra.loglik = loglik;
+    ra.f_smooth = io.f_smooth; ra.P_smooth = io.P_smooth; ra.loglik = io.loglik;
     ra.ncov = at<int>(h, p.ncov);
     if (em) {
         ra.S11 = at<double>(h, p.S11); ra.S10 = at<double>(h, p.S10); ra.S00 = at<double>(h, p.S00);
@@ -983,56 +1067,52 @@ int enqueue_pass(dfm_handle* h, const Plan& p, int B, int T, int N, int out_r, c
         ra.active = em->active; ra.iters = em->iters; ra.ll_path = em->ll_path;
         ra.k = em->k; ra.max_iter = em->max_iter; ra.tol = em->tol;
     }
-    // which recursion launch_recursion will pick, as far as this function has to know (the kernel files' own predicates, asked once)
-    const bool chunked = ra.wave && recursion_chunk_supported(p.Rp, ra), tiled = ra.wave && recursion_tile_supported(p.Rp, ra);
-    // C_t rows: the packed leading block when recursion_tile_kernel reads them (it executes ceil(r / 4) block pivots of the 32-wide
-    // state: the rest is padding whose entries equal Cfull's), the full Rp (Rp + 1) / 2 layout for the other recursion kernels
-    ca.ct_r = 0;
-    if (tiled && p.Wwide != (size_t)-1 && N > collapse_max_n(p.Rc ? p.Rc : p.Rp) &&
-        ct_miss_wide_compact_ok(N, 4 * ((p.r + 3) / 4))) ca.ct_r = 4 * ((p.r + 3) / 4);
-    ra.ct_r = ca.ct_r;
-    {
-        const int Rcol = p.Rc ? p.Rc : p.Rp;
-        // the time-chunked recursion reads one table row per period (C_t, b_t, s_t, n_t log 2 pi + log det R_t): at Rp = 8 with loadings as
-        // wide as the state collapse_miss_kernel writes it directly
-        // (r <= 4 widened to the 8-wide state, Plan::Rc = 2 / 4: the kernel pads the loadings with zero columns in its LDS tables --
-        // CollapseArgs::lam_w -- and the table is the 8-wide one the chunks read anyway; collapse_kernel<4> + chunk_bridge_kernel took
-        // 0.25 ms per 1024 replicates of the Stock-Watson window where this takes 0.1)
-        const bool narrow_tab = p.Rc > 0 && p.Rc < 8 && p.kdim == 0 && p.rl == p.Rc && !h->opt.narrow_tab_off;
-        const bool table = chunked && !h->opt.collapse_miss_old && (p.Rc == 0 || narrow_tab);
-        // companion states (VAR(p) factor dynamics) with loadings up to 4 wide: the same table, then EVERY replicate's rows written
-        // back in the layout the sequential kernels read (chunk_unbridge_kernel<Rc>: b_t, s_t, C_t of every period, nobs = 0) --
-        // collapse_kernel<4> took 0.235 ms per 1024 replicates of the Stock-Watson window where these two take 0.12
-        const bool comp_table = p.kdim > 0 && p.kb == 0 && p.Rc > 0 && p.Rc < 8 && p.ck_rows != (size_t)-1 && p.ck_obs != (size_t)-1 &&
-                                collapse_miss_supported(8, N);
-        if (comp_table) {
+    return ra;
+}
+
+// Enqueue collapse + recursion for already-planned workspace.
+int enqueue_pass(dfm_handle* h, const Plan& p, int B, int T, int N, int out_r, const double* panel,
+                 const PaddedParams& pp, const double* Rv, double* f_smooth, double* P_smooth, double* loglik,
+                 const EmOpts* em) {
+    const PassIo io{B, T, N, out_r, panel, pp, Rv, f_smooth, P_smooth, loglik, em};
+    if (p.fast) return enqueue_pass_fast(h, p, io);
+    CollapseArgs ca = collapse_args(h, p, io);
+    ca.nobs = at<int>(h, p.nobs); ca.ldrow = at<double>(h, p.ldrow); ca.Ct = at<double>(h, p.Ct);
+    ca.kreal = (p.kdim > 0 && p.Rc == 0) ? p.kdim : 0;          // (companion state observed on every block: the AR idiosyncratic model)
+    RecursionArgs ra = recursion_args(h, p, io, ca);
+    const GeneralRoute g = general_route(h->opt, p, N, ra);
+    ra.ct_r = ca.ct_r = g.ct_r;
+    switch (g.collapse) {
+        case GC_COMP_TABLE: {
             ca.lam_w = p.Rc;
             ca.obs_chunk = at<double>(h, p.ck_rows);
             ca.obs_table = at<double>(h, p.ck_obs); ca.obs_L = recursion_chunk_len(T);
             HIP_LAUNCH(h, K_COLLAPSE, launch_collapse_miss(ca, h->num_cu, h->stream));
-            RecursionArgs ua = ra;
-            ua.chunk_obs = at<double>(h, p.ck_obs);
+            RecursionArgs ua = ra;                                // (ua.chunk_obs: that table)
             ua.chunk_fail = nullptr;                              // (no flags: every replicate)
             HIP_TRY(h, launch_chunk_unbridge(ua, h->stream));
-        } else
-        if (table && p.ck_rows != (size_t)-1 && collapse_miss_supported(8, N) && (p.Rc == 0 ? Rcol == 8 : true)) {
+            break;
+        }
+        case GC_CHUNK_TABLE:
             ca.lam_w = p.Rc;
             ca.obs_chunk = at<double>(h, p.ck_rows);
             ca.obs_table = ra.chunk_obs; ca.obs_L = recursion_chunk_len(T);
             ra.chunk_obs_ready = 1;
             HIP_LAUNCH(h, K_COLLAPSE, launch_collapse_miss(ca, h->num_cu, h->stream));
-        } else
-        if (!h->opt.collapse_miss_old && collapse_miss_supported(Rcol, N)) HIP_LAUNCH(h, K_COLLAPSE, launch_collapse_miss(ca, h->num_cu, h->stream));
-        else if (p.Wwide != (size_t)-1 && N > collapse_max_n(Rcol)) {   // Rp = 32 beyond the register tiling (config 4 with missing cells)
+            break;
+        case GC_MISS: HIP_LAUNCH(h, K_COLLAPSE, launch_collapse_miss(ca, h->num_cu, h->stream)); break;
+        case GC_WIDE2: {
             double* W = at<double>(h, p.Wwide);
             double* V = at<double>(h, p.Vwide);
             HIP_LAUNCH(h, K_GRAM, launch_wide_prep(ca, W, 32, h->stream, 0, V));
             HIP_LAUNCH(h, K_COLLAPSE_WIDE, launch_collapse_wide2(ca, W, 32, p.r, h->num_cu, h->stream));
             HIP_LAUNCH(h, K_COLLAPSE, launch_ct_miss_wide(ca, W, p.r, h->stream, V));
-        } else HIP_LAUNCH(h, K_COLLAPSE, launch_collapse(Rcol, ca, h->stream));
+            break;
+        }
+        case GC_PLAIN: HIP_LAUNCH(h, K_COLLAPSE, launch_collapse(g.Rcol, ca, h->stream)); break;
     }
     h->ck_fail_dev = nullptr; h->ck_fail_n = 0;
-    if (chunked || (tiled && recursion_tile_writes_fail(ra))) { h->ck_fail_dev = ra.chunk_fail; h->ck_fail_n = B; }
+    if (g.chunked || (g.tiled && recursion_tile_writes_fail(ra))) { h->ck_fail_dev = ra.chunk_fail; h->ck_fail_n = B; }
     HIP_LAUNCH(h, K_RECURSION, launch_recursion(p.Rp, ra, h->stream));
     return 0;
 }

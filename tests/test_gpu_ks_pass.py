@@ -227,19 +227,56 @@ def test_balanced_fast_path_matches_oracle(ctx, B, N, T, r):
 _D = lambda **env: pytest.param(env, marks=diag_only())           # (switches only the diagnostics build reads)
 
 
-@pytest.mark.parametrize("env", [_D(DFM_COLLAPSE_VARIANT=199), _D(DFM_COLLAPSE_VARIANT=198), _D(DFM_NO_FUSE_COV=1), _D(DFM_COLLAPSE_WPR=1),
-                                 _D(DFM_COLLAPSE_WPR=3), _D(DFM_COLLAPSE_WPR=7), dict(DFM_PASS_FUSED=0), dict(DFM_FORCE_GENERAL=1)])
-def test_balanced_kernel_choices_agree(env):
-    """The VALU collapse, the wide collapse, the MFMA collapse with its covariance workgroups as separate launches,
-    with 1/3/7 period segments per replicate, and the general
-    (sequential) path are the same function of the inputs."""
+def _refs(shapes):
+    """Balanced batches of these shapes with the oracle's pass, computed once for every switch set that runs them."""
+    out = []
+    for (B, N, T, r) in shapes:
+        panel, st = _batch(B, N, T, r, 0.0)
+        out.append((panel, st, _oracle(panel, st), f"N={N} T={T} r={r}"))
+    return out
+
+
+@pytest.fixture(scope="module")
+def choice_refs():
+    return _refs([(5, 200, 500, 8), (3, 64, 48, 12), (4, 30, 41, 3), (3, 50, 7, 2), (2, 130, 37, 5)])
+
+
+def _choices_agree(env, refs):
     c = _ctx_with_env(**env)
     try:
-        for (B, N, T, r) in [(5, 200, 500, 8), (3, 64, 48, 12), (4, 30, 41, 3), (3, 50, 7, 2), (2, 130, 37, 5)]:
-            panel, st = _batch(B, N, T, r, 0.0)
-            _compare(_run_dev(c, panel, st, may_have_missing=False), _oracle(panel, st), f"{env} N={N} T={T} r={r}")
+        for panel, st, ref, tag in refs:
+            _compare(_run_dev(c, panel, st, may_have_missing=False), ref, f"{env} {tag}")
     finally:
         c.close()
+
+
+@pytest.mark.parametrize("env", [_D(DFM_COLLAPSE_VARIANT=199), _D(DFM_COLLAPSE_VARIANT=198), _D(DFM_NO_FUSE_COV=1), _D(DFM_COLLAPSE_WPR=1),
+                                 _D(DFM_COLLAPSE_WPR=3), _D(DFM_COLLAPSE_WPR=7), dict(DFM_PASS_FUSED=0), dict(DFM_FORCE_GENERAL=1),
+                                 _D(DFM_NO_SIDE=1), _D(DFM_SUBBATCH=2), _D(DFM_SUBBATCH=3), _D(DFM_NO_PFILL=1), _D(DFM_FUSED_GRAM=0),
+                                 _D(DFM_FUSED_GRAM=0, DFM_PASS_FUSED=0), _D(DFM_FUSE_GRAM=1), _D(DFM_WIDE_OLD=1),
+                                 _D(DFM_NO_SIDE=1, DFM_PASS_FUSED=0)])
+def test_balanced_kernel_choices_agree(env, choice_refs):
+    """The VALU collapse, the wide collapse, the MFMA collapse with its covariance workgroups as separate launches,
+    with 1/3/7 period segments per replicate, and the general
+    (sequential) path are the same function of the inputs -- and so are the schedules of the balanced pass: everything in order on
+    one stream (with the one-launch pass and without), 2 and 3 sub-batches over three streams (B = 5, 4, 3: uneven and
+    single-replicate sub-batches), the P_smooth fill inside the scan, the Gram matrices as their own launch in front of the
+    two-launch pass or inside cov_kernel, and the old wide collapse."""
+    _choices_agree(env, choice_refs)
+
+
+@pytest.fixture(scope="module")
+def wide_sub_refs():
+    # B >= 32 DFM_WIDE_SUB is what the switch asks for: 64 is the smallest batch in two halves; 65: an odd split at Rp = 32, where the
+    # P_smooth fill runs late on its own stream
+    return _refs([(64, 40, 20, 12), (65, 34, 130, 20)])
+
+
+@pytest.mark.parametrize("env", [_D(DFM_WIDE_SUB=2)])
+def test_wide_sub_batches_agree(env, wide_sub_refs):
+    """The streaming collapse of wide states in two sub-batches, each with its own workspace slice, the scan of one beside the
+    collapse of the next, is the same function of the inputs as the one-batch pass."""
+    _choices_agree(env, wide_sub_refs)
 
 
 @pytest.mark.parametrize("env", [dict(), dict(DFM_NO_CHUNK=1), dict(DFM_NO_CHUNK=1, DFM_NO_PAIR=1), _D(DFM_NO_CHUNK=1, DFM_PAIR_BMAX=3),
