@@ -60,6 +60,7 @@ _SSAR_ARGS = [c_vp] + [c_int] * 8 + [c_vp] * 11 + [ctypes.c_uint64, ctypes.c_int
 _SIM_ARGS = [c_vp] + [c_int] * 6 + [c_vp] * 7 + [ctypes.c_uint64, ctypes.c_int64, c_vp, c_vp, c_uint]
 _SIMAR_ARGS = [c_vp] + [c_int] * 7 + [c_vp] * 9 + [ctypes.c_uint64, ctypes.c_int64, c_vp, c_vp, c_uint]
 _RW_ARGS = ([c_vp] + [c_int] * 9 + [c_vp] * 10 + [c_int, ctypes.c_double] + [c_vp] * 19 + [c_uint])
+_DI_ARGS = ([c_vp] + [c_int] * 10 + [c_vp] * 4 + [c_int, ctypes.c_double] + [c_vp] * 20 + [c_uint])
 _ARPASS_ARGS = [c_vp, c_int, c_int, c_int, c_int, c_int, c_int] + [c_vp] * 11 + [c_uint]
 _AREM_ARGS = [c_vp, c_int, c_int, c_int, c_int, c_int, c_int] + [c_vp] * 8 + [c_int, ctypes.c_double] + [c_vp] * 4 + [c_uint]
 _MFPASS_ARGS = [c_vp, c_int, c_int, c_int, c_int, c_int, c_int] + [c_vp] * 11 + [c_uint]
@@ -145,6 +146,8 @@ SYMBOLS = {
     "dfm_simulate_ar_batch": (c_int, _SIMAR_ARGS),
     "dfm_rolling_eval_batch_dev": (c_int, _RW_ARGS),
     "dfm_rolling_eval_batch": (c_int, _RW_ARGS),
+    "dfm_diffusion_eval_batch_dev": (c_int, _DI_ARGS),
+    "dfm_diffusion_eval_batch": (c_int, _DI_ARGS),
     "dfm_gibbs_ar_batch_dev": (c_int, _GBAR_ARGS),
     "dfm_gibbs_ar_batch": (c_int, _GBAR_ARGS),
     "dfm_news_ar_batch_dev": (c_int, _NWAR_ARGS),

@@ -790,6 +790,86 @@ def evaluate_forecasts_rolling(m: DFMModel, H: int, window: int, *, origins=None
                     params=o["params"], iters=o["iters"], loglik_path=o["loglik_path"], mean=o["mean"], sd=o["sd"])
 
 
+def forecast_diffusion_index(m: DFMModel, H: int, window: int, *, origins=None, step: int = 1, lags=None, own_lags: Optional[int] = None,
+                             start=None, max_iter: int = 1000, tol: Optional[float] = None, ctx=None) -> dict:
+    """Diffusion-index forecasts (Stock and Watson 2002) from the NON-parametric fit (`estimate_factor`, nfac_o = 0), out of sample:
+    do the estimated factors forecast?  Rows are initperiod..lastperiod of m.data in data units, the series with inclcode == 1.  At
+    origin t (a 1-based period) the vintage is the `window` rows ending at t, with series i known through t - lags[i] only (`lags`:
+    publication lags per column of m.data, default 0); it is standardised on its own visible cells, the factors are re-estimated on
+    it by ALS (at most max_iter sweeps, tol as m.tol by default; 0 sweeps: the start's factors as they are), and every series is
+    forecast h = 0..H rows past t by a direct regression of the series at s + h on a constant, the factors at s and its own last
+    `own_lags` (default m.n_uarlag) visible values, on the complete cases of the window.  The competitors are the same regression
+    without the factors (AR) and the vintage's mean.  One dfm_diffusion_eval_batch call on the GPU: the windows are the batch of
+    the ALS, no regressor matrix is formed.  origins: increasing periods in initperiod + window - 1 .. lastperiod (default every
+    `step`-th); an origin at lastperiod gives real forecasts.  start: the factors the ALS starts from, [rows, r] (one path over
+    initperiod..lastperiod) or [origins, window, r]; the default is m.factor, so `estimate_factor` must have run -- LOOK-AHEAD IN THE
+    START VALUES ONLY (the data of every window are its own); pass factors estimated on an earlier sample to avoid it.  A series with
+    fewer than max(m.nt_min_factor_estimation, r + 1) visible cells in any window is dropped beforehand (see `cols`).
+    Returns a dict (data units):
+      origins    the 1-based periods, horizons 0 .. H, cols the column indices (0-based) of m.data that were used
+      forecast, forecast_ar   [origins, H+1, cols]; NaN where the cell is visible in the vintage (h = 0, lag 0), the regression has too
+                              few complete rows, or an own lag of the origin is missing
+      variance   [origins, H+1, cols] the regression's residual variance (no parameter or factor uncertainty)
+      error, error_ar, error_std   [origins, H+1, cols] x - forecast (..) and error over its s.d.; NaN unless the target lies in the
+                              sample, is observed and has a forecast
+      msfe, msfe_ar, msfe_mean, count   [H+1, cols] over the scored origins; relative_ar = msfe / msfe_ar, relative_mean = msfe / msfe_mean
+      factor [origins, window, r], loadings [origins, cols, r], iters, ssr [origins]   the ALS of every window
+      mean, sd   [origins, cols] of each vintage's visible cells
+    `m` is not modified."""
+    H, W, step = int(H), int(window), int(step)
+    if H < 0:
+        raise ValueError("H must be >= 0")
+    if m.nfac_o != 0:
+        raise ValueError("the diffusion-index forecasts need nfac_o = 0")
+    r = int(m.nfac_u)
+    q = int(m.n_uarlag) if own_lags is None else int(own_lags)
+    if q < 0 or 1 + r + q > 32:
+        raise ValueError("own_lags must be >= 0 and 1 + nfac_u + own_lags <= 32")
+    rows = m.lastperiod - m.initperiod + 1
+    if not (r + 2 * q + H + 3 <= W <= rows):
+        raise ValueError(f"window must lie in {r + 2 * q + H + 3}..{rows} (1 + r + 2 own_lags + H + 2 .. the rows initperiod..lastperiod)")
+    if step < 1:
+        raise ValueError("step must be >= 1")
+    first = m.initperiod + W - 1
+    org = np.arange(first, m.lastperiod + 1, step) if origins is None else np.asarray(origins, dtype=np.int64).reshape(-1)
+    if org.size < 1 or org.min() < first or org.max() > m.lastperiod or np.any(np.diff(org) <= 0):
+        raise ValueError(f"origins must increase and lie in the first full window's end..lastperiod ({first}..{m.lastperiod})")
+    F0 = np.asarray(m.factor[m.initperiod - 1:m.lastperiod, :] if start is None else start, dtype=np.float64)
+    if F0.shape not in ((rows, r), (org.size, W, r)):
+        raise ValueError(f"start must be [{rows}, {r}] (rows initperiod..lastperiod) or [{org.size}, {W}, {r}] (one per origin)")
+    if not np.all(np.isfinite(F0)):
+        raise ValueError("the start factors are not finite: run estimate_factor(m) first, or pass start")
+    if int(max_iter) < 0:
+        raise ValueError("max_iter must be >= 0")
+    cols = np.nonzero(m.inclcode == 1)[0]
+    lg = np.zeros(m.ns, dtype=np.int64) if lags is None else np.asarray(lags, dtype=np.int64).reshape(-1)
+    if lg.size != m.ns or np.any(lg < 0):
+        raise ValueError(f"lags must hold one integer >= 0 per column of m.data ({m.ns})")
+    lg = lg[cols]
+    min_obs = max(int(m.nt_min_factor_estimation), r + 1)
+    if np.any(lg > W - min_obs):
+        raise ValueError(f"a publication lag beyond window - {min_obs} leaves a series too few rows")
+    x = np.ascontiguousarray(m.data[m.initperiod - 1:m.lastperiod, :][:, cols], dtype=np.float64)
+    o0 = org - m.initperiod                                             # 0-based rows of x
+    cs = np.vstack([np.zeros((1, cols.size), dtype=np.int64), np.cumsum(~np.isnan(x), axis=0)])
+    vis = cs[o0[:, None] - lg[None, :] + 1, np.arange(cols.size)[None, :]] - cs[o0 - W + 1]      # [origins, cols] visible cells
+    keep = (vis >= min_obs).all(axis=0)
+    if keep.sum() < r:
+        raise ValueError("fewer series with enough visible cells in every window than factors")
+    if lg[keep].min() != 0:
+        raise ValueError("every kept series has a publication lag: some series must reach the origin")
+    x, lg, cols = np.ascontiguousarray(x[:, keep]), lg[keep], cols[keep]
+    kw = dict(q=q, lags=lg, min_obs=min_obs, nt_min=int(m.nt_min_factor_estimation), max_iter=int(max_iter),
+              tol=float(m.tol if tol is None else tol))
+    with _device(ctx) as ctx:
+        o = ctx.diffusion_eval_batch_host(x, o0, W, H, np.ascontiguousarray(F0), **kw)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return dict(origins=org, horizons=np.arange(H + 1), cols=cols, forecast=o["fc"], forecast_ar=o["fc_ar"], variance=o["fvar"],
+                    error=o["err"], error_ar=o["err_ar"], error_std=o["err_std"], msfe=o["msfe"], msfe_ar=o["msfe_ar"],
+                    msfe_mean=o["msfe0"], relative_ar=o["msfe"] / o["msfe_ar"], relative_mean=o["msfe"] / o["msfe0"], count=o["cnt"],
+                    factor=o["F"], loadings=o["Lam"], iters=o["iters"], ssr=o["ssr"], mean=o["mean"], sd=o["sd"])
+
+
 # ----------------------------------------------------------------------------- structural analysis of the parametric fit
 def _structural_checks(m: DFMModel):
     _need_fit(m)

@@ -180,6 +180,8 @@ struct dfm_handle {
                                            // dfm_gibbs_ar_batch_dev: the sweep's [B][T - q][r] factor path
     DevBlock rw;                           // dfm_rolling_eval_batch_dev: origins, lags, the running sums [H + 1][N], then one slice's windows,
                                            // xhat, xvar, factor rows and logliks, and the slice's part of every output the caller does not take
+                                           // dfm_diffusion_eval_batch_dev: origins, lags, the running sums, then one slice's windows, factors,
+                                           // loadings, statistics and forecasts where the caller does not take them
     std::vector<int> sv_idx;               // host copy of named / cum while their upload is in flight
     std::vector<double> sv_z;              // dfm_proxyirf_batch_dev: host copy of the instrument while its upload is in flight
     const double* odd_panel_src = nullptr; int odd_panel_dims[3] = {0, 0, 0};   // the panel whose padded copy h->odd holds (odd_pad keep_panel)
@@ -193,11 +195,11 @@ struct dfm_handle {
 };
 
 enum KernelId { K_COLLAPSE = 0, K_RECURSION, K_MSTEP_STATS, K_MSTEP_SOLVE, K_PCA, K_SYNTH, K_PAD,
-                K_COLLAPSE_DMA, K_GRAM, K_COV, K_MEANSCAN, K_PFILL, K_COLLAPSE_MFMA, K_ALS, K_OLS, K_BOOT, K_QUANT, K_COLLAPSE_WIDE, K_EM_UPDATE, K_CHOW, K_MSTEP_MFMA, K_GRAM_XX, K_PASS_FUSED, K_FC_TAIL, K_FC_FILL, K_FC_PAD, K_SS_PREP, K_SS_EXPAND, K_SS_PATH, K_SS_DIFF, K_SS_FINISH, K_SS_FILL, K_NW_REVISE, K_NW_GATHER, K_NW_GAMMA, K_NW_COV, K_NW_IMPACT, K_MF_TABLE, K_MF_MOMENTS, K_MF_SOLVE, K_SV_PREP, K_SV_IRF_FILL, K_SV_SHOCK, K_SV_PATH, K_SV_HD_FILL, K_FT_FILTER, K_FT_FILL, K_FT_EVAL, K_GB_GRAM, K_GB_LOAD, K_GB_VAR, K_SV_SIGN_TABLE, K_SV_SIGN, K_SV_SIGN_KEEP, K_PX_ROWS, K_PX_MOMENT, K_PX_SLOT_TABLE, K_PX_DEN, K_PX_FILL, K_PX_SHOCK, K_MF_SOLVE_BLOCKS, K_FCAR_BACK, K_FCAR_FWD, K_SSAR_PARAMS, K_SSAR_EXPAND, K_SSAR_DIFF, K_SSAR_FWD, K_SSAR_FINISH, K_GB_AR_SERIES, K_FTAR_FILTER, K_FTAR_FILL, K_FTAR_EVAL, K_NWAR_REVISE, K_NWAR_REC, K_NWAR_QC, K_NWAR_IMPACT, K_SIM_CELLS, K_SIMAR_CELLS, K_RW_WINDOW, K_RW_START, K_RW_SCORE, K_COUNT };
+                K_COLLAPSE_DMA, K_GRAM, K_COV, K_MEANSCAN, K_PFILL, K_COLLAPSE_MFMA, K_ALS, K_OLS, K_BOOT, K_QUANT, K_COLLAPSE_WIDE, K_EM_UPDATE, K_CHOW, K_MSTEP_MFMA, K_GRAM_XX, K_PASS_FUSED, K_FC_TAIL, K_FC_FILL, K_FC_PAD, K_SS_PREP, K_SS_EXPAND, K_SS_PATH, K_SS_DIFF, K_SS_FINISH, K_SS_FILL, K_NW_REVISE, K_NW_GATHER, K_NW_GAMMA, K_NW_COV, K_NW_IMPACT, K_MF_TABLE, K_MF_MOMENTS, K_MF_SOLVE, K_SV_PREP, K_SV_IRF_FILL, K_SV_SHOCK, K_SV_PATH, K_SV_HD_FILL, K_FT_FILTER, K_FT_FILL, K_FT_EVAL, K_GB_GRAM, K_GB_LOAD, K_GB_VAR, K_SV_SIGN_TABLE, K_SV_SIGN, K_SV_SIGN_KEEP, K_PX_ROWS, K_PX_MOMENT, K_PX_SLOT_TABLE, K_PX_DEN, K_PX_FILL, K_PX_SHOCK, K_MF_SOLVE_BLOCKS, K_FCAR_BACK, K_FCAR_FWD, K_SSAR_PARAMS, K_SSAR_EXPAND, K_SSAR_DIFF, K_SSAR_FWD, K_SSAR_FINISH, K_GB_AR_SERIES, K_FTAR_FILTER, K_FTAR_FILL, K_FTAR_EVAL, K_NWAR_REVISE, K_NWAR_REC, K_NWAR_QC, K_NWAR_IMPACT, K_SIM_CELLS, K_SIMAR_CELLS, K_RW_WINDOW, K_RW_START, K_RW_SCORE, K_DI_START, K_DI_REGRESS, K_DI_SCORE, K_COUNT };
 static const char* const kKernelNames[K_COUNT] = {"collapse_kernel", "recursion_kernel", "mstep_lam_kernel",
                                                   "mstep_solve_kernel", "pca_kernel", "synth_kernel",
                                                   "pad_params_kernel", "collapse_dma_kernel", "gram_kernel",
-                                                  "cov_kernel", "meanscan_kernel", "pfill_kernel", "collapse_mfma_kernel", "als_kernel", "ols_kernel", "var_boot_kernel", "quantile_kernel", "collapse_wide_kernel", "em_update_kernel", "chow_kernel", "mstep_mfma_kernel", "gram_xx_kernel", "pass_fused_kernel", "forecast_tail_kernel", "forecast_fill_kernel", "forecast_pad_kernel", "simsmooth_prep_kernel", "simsmooth_expand_kernel", "simsmooth_path_kernel", "simsmooth_diff_kernel", "simsmooth_finish_kernel", "simsmooth_fill_kernel", "news_revise_kernel", "news_gather_kernel", "news_gamma_kernel", "news_cov_panel_kernel", "news_impact_kernel", "mf_table_kernel", "mf_moments_kernel", "mf_solve_kernel", "sv_prep_kernel", "sv_irf_fill_kernel", "sv_shock_kernel", "sv_path_kernel", "sv_hd_fill_kernel", "filter_kernel", "filter_fill_kernel", "filter_eval_kernel", "gibbs_gram_kernel", "gibbs_load_kernel", "gibbs_var_kernel", "sv_sign_table_kernel", "sv_sign_kernel", "sv_sign_keep_kernel", "px_rows_kernel", "px_moment_kernel", "px_slot_table_kernel", "px_den_kernel", "px_fill_kernel", "px_shock_kernel", "mf_solve_blocks_kernel", "forecast_ar_back_kernel", "forecast_ar_fwd_kernel", "simsmooth_ar_params_kernel", "simsmooth_ar_expand_kernel", "simsmooth_ar_diff_kernel", "simsmooth_ar_fwd_kernel", "simsmooth_ar_finish_kernel", "gibbs_ar_series_kernel", "filter_ar_kernel", "filter_ar_fill_kernel", "filter_ar_eval_kernel", "news_ar_revise_kernel", "news_ar_rec_kernel", "news_ar_qc_kernel", "news_ar_impact_kernel", "simulate_cells_kernel", "simulate_ar_cells_kernel", "rolling_window_kernel", "rolling_start_kernel", "rolling_score_kernel"};
+                                                  "cov_kernel", "meanscan_kernel", "pfill_kernel", "collapse_mfma_kernel", "als_kernel", "ols_kernel", "var_boot_kernel", "quantile_kernel", "collapse_wide_kernel", "em_update_kernel", "chow_kernel", "mstep_mfma_kernel", "gram_xx_kernel", "pass_fused_kernel", "forecast_tail_kernel", "forecast_fill_kernel", "forecast_pad_kernel", "simsmooth_prep_kernel", "simsmooth_expand_kernel", "simsmooth_path_kernel", "simsmooth_diff_kernel", "simsmooth_finish_kernel", "simsmooth_fill_kernel", "news_revise_kernel", "news_gather_kernel", "news_gamma_kernel", "news_cov_panel_kernel", "news_impact_kernel", "mf_table_kernel", "mf_moments_kernel", "mf_solve_kernel", "sv_prep_kernel", "sv_irf_fill_kernel", "sv_shock_kernel", "sv_path_kernel", "sv_hd_fill_kernel", "filter_kernel", "filter_fill_kernel", "filter_eval_kernel", "gibbs_gram_kernel", "gibbs_load_kernel", "gibbs_var_kernel", "sv_sign_table_kernel", "sv_sign_kernel", "sv_sign_keep_kernel", "px_rows_kernel", "px_moment_kernel", "px_slot_table_kernel", "px_den_kernel", "px_fill_kernel", "px_shock_kernel", "mf_solve_blocks_kernel", "forecast_ar_back_kernel", "forecast_ar_fwd_kernel", "simsmooth_ar_params_kernel", "simsmooth_ar_expand_kernel", "simsmooth_ar_diff_kernel", "simsmooth_ar_fwd_kernel", "simsmooth_ar_finish_kernel", "gibbs_ar_series_kernel", "filter_ar_kernel", "filter_ar_fill_kernel", "filter_ar_eval_kernel", "news_ar_revise_kernel", "news_ar_rec_kernel", "news_ar_qc_kernel", "news_ar_impact_kernel", "simulate_cells_kernel", "simulate_ar_cells_kernel", "rolling_window_kernel", "rolling_start_kernel", "rolling_score_kernel", "di_start_kernel", "di_regress_kernel", "di_score_kernel"};
 
 namespace dfm { int handle_device(const dfm_handle* h) { return h->device; } }   // (probe.hip)
 
@@ -3201,6 +3203,153 @@ int dfm_rolling_eval_batch(dfm_handle* h, int T, int N, int r, int p, int W, int
     return rolling_host(h, T, N, r, p, W, H, O, min_obs, n_start, x, origins, lags, Lam_start, R_start, Avar_start, Q_start, mu0_start, P0_start,
                         sd_start, max_iter, tol, Lam, R, Avar, Q, mu0, P0, loglik_path, iters, win_mean, win_sd, win_nobs, windows, fc, fvar, err,
                         err_std, msfe, msfe0, cnt, flags);
+}
+
+// ---- diffusion-index forecasts from the non-parametric fit, out of sample (diffusion.hip) --------------------------------------
+// Per slice of at most kRwSlice windows: rolling_window_kernel and the status word's window bit as above, di_start_kernel (the start
+// factors), als_kernel on the slice's windows (one workgroup per window; none when max_iter = 0), di_regress_kernel, di_score_kernel.
+// The slice's arrays live in h->rw, as the rolling driver's do.
+static int diffusion_check(dfm_handle* h, int T, int N, int r, int q, int W, int H, int O, int min_obs, int n_start, const double* x,
+                           const int* origins, const int* lags, const double* F_start, int max_iter, unsigned flags) {
+    if (!h) return DFM_E_NULL;
+    if (T < 1 || N < 1 || r < 1 || q < 0 || O < 1) return fail(h, DFM_E_DIMS, "T, N, r, O must be >= 1 and q >= 0%s");
+    const long long K = 1ll + r + q;
+    if (K > 32) return fail(h, DFM_E_DIMS, "1 + r + q > 32 regressors%s");
+    if (H < 0) return fail(h, DFM_E_DIMS, "H must be >= 0%s");
+    if (W > T || W < K + q + H + 2) return fail(h, DFM_E_DIMS, "need 1 + r + 2 q + H + 2 <= W <= T%s");
+    if (max_iter < 0) return fail(h, DFM_E_DIMS, "max_iter must be >= 0%s");
+    if (min_obs < r + 1) return fail(h, DFM_E_DIMS, "min_obs must be >= r + 1%s");
+    if (n_start != 1 && n_start != O) return fail(h, DFM_E_DIMS, "n_start must be 1 or O%s");
+    if (!x || !origins || !F_start) return fail(h, DFM_E_NULL, "required pointer is NULL%s");
+    for (int b = 0; b < O; ++b)
+        if (origins[b] < W - 1 || origins[b] > T - 1 || (b && origins[b] <= origins[b - 1]))
+            return fail(h, DFM_E_DIMS, "origins must increase and lie in W - 1 .. T - 1%s");
+    bool lagged = false, reaches = !lags;
+    for (int i = 0; lags && i < N; ++i) {
+        if (lags[i] < 0 || lags[i] > W - min_obs) return fail(h, DFM_E_DIMS, "publication lags must lie in 0 .. W - min_obs%s");
+        lagged = lagged || lags[i] > 0;
+        reaches = reaches || lags[i] == 0;
+    }
+    if (!reaches) return fail(h, DFM_E_DIMS, "no series reaches the origin (every publication lag > 0): its factor row has no data%s");
+    if (!als_fits(pad_r(r), W, N)) return fail(h, DFM_E_DIMS, "(W + N) * pad(r) doubles exceed the 160 KB of LDS%s");
+    if (!di_series_block(W, r, pad_r((int)K))) return fail(h, DFM_E_DIMS, "W * (r + 1) doubles and the regressions' exchange rows exceed the 160 KB of LDS%s");
+    if (lagged && !(flags & DFM_F_MAY_HAVE_MISSING))
+        return fail(h, DFM_E_MISSING, "publication lags leave NaN in the windows: DFM_F_MAY_HAVE_MISSING is needed%s");
+    return 0;
+}
+
+static int diffusion_run(dfm_handle* h, int T, int N, int r, int q, int W, int H, int O, int min_obs, int nt_min, int n_start,
+                         const double* x, const int* origins, const int* lags, const double* F_start, int max_iter, double tol, double* F,
+                         double* Lam, int* als_iters, double* als_ssr, double* win_mean, double* win_sd, int* win_nobs, double* windows,
+                         double* fc, double* fc_ar, double* fvar, double* err, double* err_ar, double* err_std, double* beta,
+                         int* nobs_reg, double* msfe, double* msfe_ar, double* msfe0, int* cnt, unsigned flags) {
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t d = sizeof(double), H1 = (size_t)H + 1, K = (size_t)1 + r + q;
+    const size_t Smax = O < kRwSlice ? O : kRwSlice, SN = Smax * N;
+    size_t off = 0;
+    auto own = [&](const void* callers, size_t bytes) { return callers ? (size_t)-1 : take(off, bytes); };
+    const size_t o_org = take(off, (size_t)O * sizeof(int)), o_lag = lags ? take(off, (size_t)N * sizeof(int)) : (size_t)-1,
+                 o_sse = take(off, H1 * N * d), o_ssa = take(off, H1 * N * d), o_sse0 = take(off, H1 * N * d),
+                 o_cnt = take(off, H1 * N * sizeof(int)), o_win = own(windows, Smax * W * N * d), o_F = own(F, Smax * W * r * d),
+                 o_L = own(Lam, SN * r * d), o_it = own(als_iters, Smax * sizeof(int)), o_ssr = own(als_ssr, Smax * d),
+                 o_mean = own(win_mean, SN * d), o_sd = own(win_sd, SN * d), o_nobs = own(win_nobs, SN * sizeof(int)),
+                 o_fc = own(fc, SN * H1 * d), o_fa = own(fc_ar, SN * H1 * d), o_fv = own(fvar, SN * H1 * d);
+    HIP_TRY(h, h->rw.grow(off));
+    int* org_d = at<int>(h->rw, o_org);
+    HIP_TRY(h, hipMemcpyAsync(org_d, origins, (size_t)O * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    if (lags) HIP_TRY(h, hipMemcpyAsync(at<int>(h->rw, o_lag), lags, (size_t)N * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    RwArgs w{};
+    w.T = T; w.N = N; w.W = W; w.H = H; w.r = r; w.k = r; w.min_obs = min_obs;
+    w.x = x; w.origins = org_d; w.lags = at<int>(h->rw, o_lag); w.status = h->status_dev;
+    DiArgs a{};
+    a.T = T; a.N = N; a.W = W; a.H = H; a.r = r; a.q = q; a.K = (int)K; a.nt_min = nt_min; a.n_start = n_start;
+    a.missing_ok = (flags & DFM_F_MAY_HAVE_MISSING) != 0;
+    a.x = x; a.origins = org_d; a.lags = w.lags; a.F_start = F_start; a.status = h->status_dev;
+    a.sse = at<double>(h->rw, o_sse); a.sse_ar = at<double>(h->rw, o_ssa); a.sse0 = at<double>(h->rw, o_sse0); a.cnt = at<int>(h->rw, o_cnt);
+    a.msfe = msfe; a.msfe_ar = msfe_ar; a.msfe0 = msfe0; a.cnt_out = cnt;
+    const int Rp = pad_r(r), Rk = pad_r((int)K);
+    a.nb = di_series_block(W, r, Rk);
+    a.h_first = 1;
+    for (int i = 0; lags && i < N; ++i) a.h_first = a.h_first && lags[i] == 0;
+    for (int b0 = 0; b0 < O; b0 += kRwSlice) {
+        const int S = O - b0 < kRwSlice ? O - b0 : kRwSlice;
+        auto part = [&](auto* callers, size_t o_own, size_t per) { return callers ? callers + (size_t)b0 * per : at<std::remove_pointer_t<decltype(callers)>>(h->rw, o_own); };
+        auto opt = [&](auto* callers, size_t per) { return callers ? callers + (size_t)b0 * per : nullptr; };
+        w.b0 = b0; w.S = S;
+        w.win = part(windows, o_win, (size_t)W * N); w.mean = part(win_mean, o_mean, N); w.sd = part(win_sd, o_sd, N); w.nobs = part(win_nobs, o_nobs, N);
+        a.b0 = b0; a.S = S; a.first = b0 == 0; a.last = b0 + S == O;
+        a.win = w.win; a.mean = w.mean; a.sd = w.sd; a.nobs = w.nobs;
+        a.F = part(F, o_F, (size_t)W * r);
+        a.fc = part(fc, o_fc, H1 * N); a.fc_ar = part(fc_ar, o_fa, H1 * N); a.fvar = part(fvar, o_fv, H1 * N);
+        a.err = opt(err, H1 * N); a.err_ar = opt(err_ar, H1 * N); a.err_std = opt(err_std, H1 * N);
+        a.beta = opt(beta, H1 * N * K); a.nobs_reg = opt(nobs_reg, H1 * N);
+        double *lam = part(Lam, o_L, (size_t)N * r), *ssr = part(als_ssr, o_ssr, 1);
+        int* it = part(als_iters, o_it, 1);
+        HIP_LAUNCH(h, K_RW_WINDOW, launch_rolling_window(w, h->stream));
+        int st = 0;                                            // a thin or constant series: stop before the ALS meets its window
+        HIP_TRY(h, hipMemcpyAsync(&st, h->status_dev, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        if (st & kRwWindowBit) return status_check(h);
+        HIP_LAUNCH(h, K_DI_START, launch_di_start(a, h->stream));
+        if (max_iter > 0) {
+            AlsArgs al;
+            memset(&al, 0, sizeof(al));
+            al.B = S; al.T = W; al.N = N; al.rmax = r; al.z = a.win; al.z_stride = (long long)W * N; al.F = a.F; al.Lam = lam;
+            al.nt_min = nt_min; al.max_iter = max_iter; al.tol = tol; al.iters = it; al.ssr = ssr;
+            HIP_LAUNCH(h, K_ALS, launch_als(Rp, al, h->stream));
+        } else {                                               // the factors are the start: no loadings, no sweeps (all-ones bytes: NaN)
+            HIP_TRY(h, hipMemsetAsync(lam, 0xFF, (size_t)S * N * r * d, h->stream));
+            HIP_TRY(h, hipMemsetAsync(ssr, 0xFF, (size_t)S * d, h->stream));
+            HIP_TRY(h, hipMemsetAsync(it, 0, (size_t)S * sizeof(int), h->stream));
+        }
+        HIP_LAUNCH(h, K_DI_REGRESS, launch_di_regress(Rk, a, h->stream));
+        HIP_LAUNCH(h, K_DI_SCORE, launch_di_score(a, h->stream));
+    }
+    return 0;
+}
+
+int dfm_diffusion_eval_batch_dev(dfm_handle* h, int T, int N, int r, int q, int W, int H, int O, int min_obs, int nt_min, int n_start,
+                                 const double* x, const int* origins, const int* lags, const double* F_start, int max_iter,
+                                 double tol, double* F, double* Lam, int* als_iters, double* als_ssr, double* win_mean,
+                                 double* win_sd, int* win_nobs, double* windows, double* fc, double* fc_ar, double* fvar, double* err,
+                                 double* err_ar, double* err_std, double* beta, int* nobs_reg, double* msfe, double* msfe_ar,
+                                 double* msfe0, int* cnt, unsigned flags) {
+    if (int rc = diffusion_check(h, T, N, r, q, W, H, O, min_obs, n_start, x, origins, lags, F_start, max_iter, flags)) return rc;
+    return diffusion_run(h, T, N, r, q, W, H, O, min_obs, nt_min, n_start, x, origins, lags, F_start, max_iter, tol, F, Lam, als_iters,
+                         als_ssr, win_mean, win_sd, win_nobs, windows, fc, fc_ar, fvar, err, err_ar, err_std, beta, nobs_reg, msfe, msfe_ar,
+                         msfe0, cnt, flags);
+}
+
+int dfm_diffusion_eval_batch(dfm_handle* h, int T, int N, int r, int q, int W, int H, int O, int min_obs, int nt_min, int n_start,
+                             const double* x, const int* origins, const int* lags, const double* F_start, int max_iter, double tol,
+                             double* F, double* Lam, int* als_iters, double* als_ssr, double* win_mean, double* win_sd,
+                             int* win_nobs, double* windows, double* fc, double* fc_ar, double* fvar, double* err, double* err_ar,
+                             double* err_std, double* beta, int* nobs_reg, double* msfe, double* msfe_ar, double* msfe0, int* cnt,
+                             unsigned flags) {
+    if (int rc = diffusion_check(h, T, N, r, q, W, H, O, min_obs, n_start, x, origins, lags, F_start, max_iter, flags)) return rc;
+    if (int rc = status_epoch(h)) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t nO = (size_t)O, ON = nO * N, n_fc = nO * (H + 1) * N, n_ms = (size_t)(H + 1) * N, K = (size_t)1 + r + q;
+    HostStage st(h, 256);
+    double *x_d, *fs_d, *F_d, *L_d, *ssr_d, *mean_d, *sd_d, *win_d, *fc_d, *fa_d, *fv_d, *er_d, *ea_d, *es_d, *b_d, *ms_d, *ma_d, *m0_d;
+    int *it_d, *nobs_d, *nr_d, *cnt_d;
+    st.in(x, (size_t)T * N, x_d);
+    st.in(F_start, n_start == 1 ? (size_t)T * r : nO * W * r, fs_d);
+    // outputs only, each taking room only where the caller takes it
+    st.out(F, F ? nO * W * r : 0, F_d); st.out(Lam, Lam ? ON * r : 0, L_d); st.out(als_iters, als_iters ? nO : 0, it_d);
+    st.out(als_ssr, als_ssr ? nO : 0, ssr_d); st.out(win_mean, win_mean ? ON : 0, mean_d); st.out(win_sd, win_sd ? ON : 0, sd_d);
+    st.out(win_nobs, win_nobs ? ON : 0, nobs_d); st.out(windows, windows ? ON * W : 0, win_d);
+    st.out(fc, fc ? n_fc : 0, fc_d); st.out(fc_ar, fc_ar ? n_fc : 0, fa_d); st.out(fvar, fvar ? n_fc : 0, fv_d);
+    st.out(err, err ? n_fc : 0, er_d); st.out(err_ar, err_ar ? n_fc : 0, ea_d); st.out(err_std, err_std ? n_fc : 0, es_d);
+    st.out(beta, beta ? n_fc * K : 0, b_d); st.out(nobs_reg, nobs_reg ? n_fc : 0, nr_d);
+    st.out(msfe, msfe ? n_ms : 0, ms_d); st.out(msfe_ar, msfe_ar ? n_ms : 0, ma_d); st.out(msfe0, msfe0 ? n_ms : 0, m0_d);
+    st.out(cnt, cnt ? n_ms : 0, cnt_d);
+    if (int rc = st.begin()) return rc;
+    int rc = st.finish(diffusion_run(h, T, N, r, q, W, H, O, min_obs, nt_min, n_start, x_d, origins, lags, fs_d, max_iter, tol, F_d, L_d, it_d,
+                                     ssr_d, mean_d, sd_d, nobs_d, win_d, fc_d, fa_d, fv_d, er_d, ea_d, es_d, b_d, nr_d, ms_d, ma_d, m0_d,
+                                     cnt_d, flags));
+    if (rc == 0) rc = status_check(h);
+    return rc;
 }
 
 // ---- Bayesian estimation: the Gibbs sampler (gibbs.hip)------------------------------------------------------------------------

@@ -818,6 +818,33 @@ hipError_t launch_rolling_window(const RwArgs& a, hipStream_t s);
 hipError_t launch_rolling_start(const RwArgs& a, hipStream_t s);
 hipError_t launch_rolling_score(const RwArgs& a, hipStream_t s);
 
+// Diffusion-index forecasts from the non-parametric fit, out of sample (diffusion.hip; dfm_diffusion_eval_batch).  The windows are
+// those of RwArgs (launch_rolling_window) and run in the same slices; every array marked [S] is the slice's part.
+struct DiArgs {
+    int T, N, W, H, r, q, K;                      // panel rows, series, window rows, horizons, factors, own lags, K = 1 + r + q
+    int b0, S, nt_min, n_start;
+    int missing_ok;                               // di_start_kernel: DFM_F_MAY_HAVE_MISSING was given (else a NaN inside a window raises bit 1)
+    const double* x;                              // [T][N] the raw panel, data units
+    const int* origins; const int* lags;          // device [O], [N] (lags null: all 0)
+    const double* F_start;                        // [T][r] (n_start = 1: window b takes rows o_b - W + 1 .. o_b) or [O][W][r]
+    double* F;                                    // [S][W][r] di_start_kernel: the start; di_regress_kernel: the windows' factors
+    const double* win;                            // [S][W][N] the standardised vintages
+    const double* mean; const double* sd; const int* nobs;   // [S][N]
+    int* status;
+    double *fc, *fc_ar, *fvar;                    // [S][H + 1][N] data units; never null here (the driver's block where the caller takes none)
+    double* beta; int* nobs_reg;                  // [S][H + 1][N][K], [S][H + 1][N], each may be null
+    double *err, *err_ar, *err_std;               // [S][H + 1][N], each may be null
+    double *sse, *sse_ar, *sse0; int* cnt;        // [H + 1][N] running sums over the origins scored so far
+    double *msfe, *msfe_ar, *msfe0; int* cnt_out; // [H + 1][N], each may be null: written when last
+    int first, last;
+    int nb;                                       // series per workgroup of di_regress_kernel (set by di_series_block)
+    int h_first;                                  // 1: no series has a publication lag, so h = 0 has no regression; else 0
+};
+int di_series_block(int W, int r, int Rpad);      // the largest block of series whose LDS image fits the 160 KB at R = Rpad; 0: none does
+hipError_t launch_di_start(const DiArgs& a, hipStream_t s);
+hipError_t launch_di_regress(int Rpad, const DiArgs& a, hipStream_t s);
+hipError_t launch_di_score(const DiArgs& a, hipStream_t s);
+
 // Device-side synthetic replicates (synth.hip); all arrays in the caller's layout (r).
 struct SynthArgs {
     int B, T, N, r;

@@ -908,3 +908,4 @@ from . import gibbs_ar  # noqa: E402,F401  (attaches the Gibbs sampler's entries
 from . import news_ar  # noqa: E402,F401  (attaches its news entries)
 from . import simulate  # noqa: E402,F401  (attaches the simulated-panel entries of both models)
 from . import rolling  # noqa: E402,F401  (attaches the rolling-window evaluation entries)
+from . import diffusion  # noqa: E402,F401  (attaches the diffusion-index evaluation entries)

@@ -1080,6 +1080,51 @@ int dfm_rolling_eval_batch(dfm_handle* h, int T, int N, int r, int p, int W, int
                            double* win_mean, double* win_sd, int* win_nobs, double* windows, double* fc, double* fvar, double* err,
                            double* err_std, double* msfe, double* msfe0, int* cnt, unsigned flags);
 
+/* --- diffusion-index forecasts from the non-parametric fit, out of sample (diffusion.hip) ---------------
+ * Stock and Watson (2002): at every origin the factors are re-estimated by ALS on the window, and every series is forecast h steps
+ * ahead by a DIRECT regression on the factors and its own lags; the competitors are the same regression without the factors (AR) and
+ * the window's mean.
+ * x [T][N], origins [O], lags [N] (HOST arrays in both entries), W, min_obs, the vintages, their standardisation (win_mean, win_sd,
+ * win_nobs [O][N], windows [O][W][N]) and DFM_E_WINDOW are exactly those of dfm_rolling_eval_batch (rolling_window_kernel).
+ * Factors: F_start is [T][r] for n_start = 1 (window b starts from its rows o_b - W + 1 .. o_b) or [O][W][r] for n_start = O.  The
+ * windows are the batch of dfm_als_batch_dev with T = W, nt_min, max_iter and tol (stop: |SSR_old - SSR| < tol W N); F [O][W][r], Lam
+ * [O][N][r] (NaN: a series without loadings), als_iters [O] (int) and als_ssr [O] are its outputs.  max_iter = 0: no ALS, F is the start,
+ * Lam and als_ssr are NaN and als_iters 0 (the record for given factors).
+ * Regressions, on the standardised window z in window-local rows s = 0 .. W-1 (row W-1 is the origin): for every series i with l =
+ * lag_i and every horizon h = 0 .. H with h + l >= 1, the target z_{s+h,i} on u_s = [1, F_s (r), z_{s-l,i}, .., z_{s-l-q+1,i}], K = 1 + r +
+ * q regressors, over every row s with s - l - q + 1 >= 0, s + h <= W - 1 - l and all terms observed (complete cases); nobs_reg [O][H+1][N]
+ * (int) is their number.  Fewer than max(nt_min, K) of them: every output of that regression is NaN (dfm_ols_batch's rule).  beta
+ * [O][H+1][N][K] are the coefficients in the window's standardised units, in the order of u.  The AR benchmark is the same rows on the
+ * columns {1, own lags}.  Forecasts, data units: fc = win_mean + win_sd beta' u_{W-1}, fc_ar likewise [O][H+1][N]; NaN where an own-lag
+ * term of the origin is missing.  fvar [O][H+1][N] = win_sd^2 SSR / (nobs_reg - K) is the RESIDUAL variance of the regression only: it
+ * carries no parameter uncertainty (none of beta, none of the estimated factors); NaN where nobs_reg = K.  h + l = 0 (the cell is
+ * visible in the vintage): NaN and nobs_reg = 0.  A window whose factors hold a non-finite value (a row of the window with fewer usable
+ * cells than factors makes the ALS's unpivoted elimination return inf or NaN; als_ssr shows it) gives NaN and nobs_reg = 0 for the
+ * whole window and no error code.
+ * Scores: the target o_b + h of (b, h, i) is SCORED iff fc is finite, o_b + h < T and x is observed there: err = x - fc, err_ar = x -
+ * fc_ar, err_std = err / sqrt(fvar) [O][H+1][N], NaN on every other target.  msfe, msfe_ar, msfe0 [H+1][N] are the means of err^2,
+ * err_ar^2 and (x - win_mean[b][i])^2 over the scored origins, cnt [H+1][N] (int) their number; NaN where cnt = 0.  The sums are taken
+ * in origin order by one lane per (h, i), no atomics, continued slice after slice: bit-identical from run to run and under any slicing.
+ * Every output may be NULL.
+ * Status: 1 + r + q > 32, r < 1, q < 0, H < 0, O < 1, W > T, W < K + q + H + 2, min_obs < r + 1, n_start not 1 or O, origins out of range
+ * or not increasing, lag_i < 0 or lag_i > W - min_obs, no lag_i = 0 (some series must reach the origin, or its factor row has no
+ * data), (W + N) pad(r) doubles beyond the ALS's 160 KB of LDS, W (r + 1) doubles beyond the regressions', max_iter < 0: DFM_E_DIMS.  A lag
+ * > 0 without DFM_F_MAY_HAVE_MISSING: DFM_E_MISSING; a NaN of x inside a window without the flag: DFM_E_MISSING through the status word.
+ * The windows run in slices of at most 1024: device memory does not grow with O (beyond the origins and what the caller takes).
+ * Allocates in the handle (kept for the next call).  Outputs must not overlap the inputs. */
+int dfm_diffusion_eval_batch_dev(dfm_handle* h, int T, int N, int r, int q, int W, int H, int O, int min_obs, int nt_min, int n_start,
+                                 const double* x, const int* origins, const int* lags, const double* F_start, int max_iter,
+                                 double tol, double* F, double* Lam, int* als_iters, double* als_ssr, double* win_mean,
+                                 double* win_sd, int* win_nobs, double* windows, double* fc, double* fc_ar, double* fvar, double* err,
+                                 double* err_ar, double* err_std, double* beta, int* nobs_reg, double* msfe, double* msfe_ar,
+                                 double* msfe0, int* cnt, unsigned flags);
+int dfm_diffusion_eval_batch(dfm_handle* h, int T, int N, int r, int q, int W, int H, int O, int min_obs, int nt_min, int n_start,
+                             const double* x, const int* origins, const int* lags, const double* F_start, int max_iter, double tol,
+                             double* F, double* Lam, int* als_iters, double* als_ssr, double* win_mean, double* win_sd,
+                             int* win_nobs, double* windows, double* fc, double* fc_ar, double* fvar, double* err, double* err_ar,
+                             double* err_std, double* beta, int* nobs_reg, double* msfe, double* msfe_ar, double* msfe0, int* cnt,
+                             unsigned flags);
+
 /* --- synthetic replicates generated on the device (SURVEY.md §8(d) DGP; no reference
  * counterpart -- the reference has no RNG).  Writes the standardised panel and the DGP parameters
  * rescaled to it.  Counter-based generator keyed by (seed, first_replicate + b). */

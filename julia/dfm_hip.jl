@@ -427,6 +427,44 @@ function evaluate_forecasts_rolling(h::Handle, x::Matrix{Float64}, start, H::Int
             A = permutedims(A, (3, 2, 1)), Q = permutedims(Q, (3, 2, 1)), mu0 = permutedims(mu0), P0 = permutedims(P0, (3, 2, 1)))
 end
 
+"Diffusion-index forecasts from the non-parametric fit, out of sample (dfm_diffusion_eval_batch; include/dfm_hip.h): x is the RAW
+T x N panel (NaN = missing), origins increasing 1-based rows in W..T, lags the publication lags (length N) or nothing; F_start the
+T x r factor path every window's ALS starts from (its rows of the window), q the number of own lags in the direct regressions.
+max_iter = 0: the factors are the start.  Returns forecast, forecast_ar, variance, error, error_ar, error_std (O x (H+1) x N, horizons
+0..H), msfe, msfe_ar, msfe_mean, count ((H+1) x N), factor (O x W x r), loadings (O x N x r), iters, ssr (O), mean, sd (O x N)."
+function forecast_diffusion_index(h::Handle, x::Matrix{Float64}, F_start::Matrix{Float64}, H::Integer, W::Integer,
+                                  origins::AbstractVector{<:Integer}; q::Integer = 4, lags = nothing,
+                                  min_obs::Integer = size(F_start, 2) + 1, nt_min::Integer = 20, max_iter::Integer = 1000,
+                                  tol::Real = 1e-8)
+    T, N = size(x); r = size(F_start, 2); O = length(origins); H1 = H + 1
+    size(F_start, 1) == T || error("F_start must have one row per row of x")
+    panel = to_c_panel(x)
+    org = Vector{Cint}(origins .- 1)
+    lagC = lags === nothing ? C_NULL : Vector{Cint}(lags)
+    F0 = permutedims(F_start)
+    F = Array{Float64}(undef, r, W, O); Lam = Array{Float64}(undef, r, N, O); iters = Array{Cint}(undef, O); ssr = Array{Float64}(undef, O)
+    wm = Array{Float64}(undef, N, O); ws = Array{Float64}(undef, N, O); wn = Array{Cint}(undef, N, O)
+    fc = Array{Float64}(undef, N, H1, O); fa = Array{Float64}(undef, N, H1, O); fv = Array{Float64}(undef, N, H1, O)
+    er = Array{Float64}(undef, N, H1, O); ea = Array{Float64}(undef, N, H1, O); es = Array{Float64}(undef, N, H1, O)
+    ms = Array{Float64}(undef, N, H1); ma = Array{Float64}(undef, N, H1); ms0 = Array{Float64}(undef, N, H1); cnt = Array{Cint}(undef, N, H1)
+    missing_cells = any(isnan, x) || (lags !== nothing && any(>(0), lags))
+    flags = missing_cells ? DFM_F_MAY_HAVE_MISSING : Cuint(0)
+    GC.@preserve panel org lagC F0 F Lam iters ssr wm ws wn fc fa fv er ea es ms ma ms0 cnt begin
+        rc = ccall((:dfm_diffusion_eval_batch, LIB), Cint,
+                   (Ptr{Cvoid}, Cint, Cint, Cint, Cint, Cint, Cint, Cint, Cint, Cint, Cint, Ptr{Float64}, Ptr{Cint}, Ptr{Cint}, Ptr{Float64},
+                    Cint, Cdouble, Ptr{Float64}, Ptr{Float64}, Ptr{Cint}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cint}, Ptr{Float64},
+                    Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cint},
+                    Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cint}, Cuint),
+                   h.ptr, T, N, r, q, W, H, O, min_obs, nt_min, 1, panel, org, lagC, F0, max_iter, tol, F, Lam, iters, ssr, wm, ws, wn, C_NULL,
+                   fc, fa, fv, er, ea, es, C_NULL, C_NULL, ms, ma, ms0, cnt, flags)
+        check(h.ptr, rc)
+    end
+    p3 = a -> permutedims(a, (3, 2, 1))
+    return (forecast = p3(fc), forecast_ar = p3(fa), variance = p3(fv), error = p3(er), error_ar = p3(ea), error_std = p3(es),
+            msfe = permutedims(ms), msfe_ar = permutedims(ma), msfe_mean = permutedims(ms0), count = permutedims(cnt),
+            factor = p3(F), loadings = p3(Lam), iters = Vector{Int}(iters), ssr = ssr, mean = permutedims(wm), sd = permutedims(ws))
+end
+
 "Identified impulse responses and forecast-error variance shares of every series (dfm_irf_batch; include/dfm_hip.h): params as
 `forecast`; named = r distinct series (1-based; factor k is the common component of series named[k], their order the recursive
 ordering) or nothing (S = chol Q); cumulate = series (1-based) whose responses are cumulated; sd (length N) puts the responses
