@@ -31,6 +31,31 @@ __device__ __forceinline__ void load_xperm(double (&Mp)[R], const double* M, int
     for (int s = 0; s < R; ++s) Mp[s] = M[i * R + (i ^ s)];
 }
 
+// ---- R = 8 on the fp64 matrix pipe ------------------------------------------------------------------------------------
+// A steady recurrence applies the SAME matrix to the state of every chunk, so one step of the EIGHT chunks of a wave is an
+// 8 x 8 by 8 x 8 product X <- M X + U: two v_mfma_f64_4x4x4 (four 4 x 4 blocks each) with X, U in the instruction's D layout --
+// lane l holds X[mm8_row(l)][mm8_col(l)], block (dI, dJ) = bits 3, 2 of l (collapse_mfma.hip has the lane roles).  Block
+// (dI, dJ) of the result is M[dI][dI] X[dI][dJ] + M[dI][1 - dI] X[1 - dI][dJ]: the first product takes X as it stands as its B
+// operand, the second takes X of lane l ^ 8 (one DPP row_ror:8, issued beside the first product) -- no select, no LDS, and the
+// result is the next step's operand.  The matrix is two doubles per lane (matvec_x: eight, and 14 DPP moves per step).
+constexpr int kDppRowRor8 = 0x128;     // lane i <- lane i ^ 8 (within 16)
+__device__ __forceinline__ int mm8_row(int lane) { return 4 * ((lane >> 3) & 1) + (lane >> 4); }   // state component
+__device__ __forceinline__ int mm8_col(int lane) { return lane & 7; }                              // chunk of the wave
+struct Mm8Op {
+    double own, oth;       // M[4 dI + q][4 dI + K], M[4 dI + q][4 (1 - dI) + K]   (q = l % 4, K = l / 16)
+};
+__device__ __forceinline__ Mm8Op load_mm8(const double* M, int lane) {   // M: row-major 8 x 8
+    const int dI = (lane >> 3) & 1;
+    const double* row = M + (4 * dI + (lane & 3)) * 8 + (lane >> 4);
+    return {row[4 * dI], row[4 * (dI ^ 1)]};
+}
+// M X + add, all three in the D layout
+__device__ __forceinline__ double mm8(const Mm8Op& A, double x, double add = 0.0) {
+    const double xr = dpp_mov<kDppRowRor8>(x);
+    const double y = __builtin_amdgcn_mfma_f64_4x4x4f64(A.own, x, add, 0, 0, 0);
+    return __builtin_amdgcn_mfma_f64_4x4x4f64(A.oth, xr, y, 0, 0, 0);
+}
+
 constexpr int kPF = 8;    // chain steps per prefetch block
 // transient covariance steps staged in LDS (later ones are read from global memory)
 __host__ __device__ constexpr int ecap(int R) { return R <= 8 ? 8 : R <= 16 ? 4 : 2; }

@@ -26,8 +26,12 @@
 //                                parked in its highest rows once that scan is done (w_ready; the stream waves count w_taken
 //                                before they store b_t over the park).
 //   the last 4 waves     SCAN    the time-parallel mean recursion (dfm_scan.h, the algorithm of meanscan_kernel) with
-//                                b_t / w_t in LDS: f_smooth, log-likelihood.  Its internal barriers are 4-wave barriers on
-//                                an LDS counter.
+//                                b_t in LDS: f_smooth, log-likelihood.  Its internal barriers are 4-wave barriers on
+//                                an LDS counter.  Production route (scan_reg): a wave holds the states of its 8 chunks as
+//                                one 8 x 8 operand of the fp64 matrix pipe, and every step of a steady or transient
+//                                recurrence is two v_mfma_f64_4x4x4 (dfm_scan.h mm8) whose result is the next step's
+//                                operand.  scan_seq (transient longer than the staged tables) and the diagnostics
+//                                build's scan_lds keep the lane-group mat-vecs (matvec_x).
 //
 // Against the two-launch pass (fused collapse launch + meanscan_kernel): no b_t round trip through HBM (33 MB written,
 // read back), no w_t scratch (33 MB + 33 MB), no second launch whose ~55 us of dependent scans ran behind the stream
@@ -39,6 +43,7 @@
 #include <string.h>
 
 #include <type_traits>
+#include <utility>
 
 #include "dfm_cov8.h"
 #include "dfm_gram.h"
@@ -384,7 +389,7 @@ __device__ __forceinline__ void scan_lds(const FastArgs& a, int b, int tid, doub
 //     no "every w_t is written" barrier between the directions; xi_T / f_T live in the group that produced them;
 //   * the forward transient (E - 1 <= kPfEcap steps) is computed by EVERY group redundantly: no broadcast barrier;
 //   * chunk carries: ONE barrier, then every group runs the affine maps of the chunks before it sequentially (<= 31
-//     dependent 8 x 8 mat-vecs of ~50 cycles, operands prefetched) instead of a 5-level Kogge-Stone with a barrier per level;
+//     dependent 8 x 8 products, operands prefetched) instead of a 5-level Kogge-Stone with a barrier per level;
 //   * backward, the (partial) top chunk starts from its TRUE state f_T, so no power of J for a partial chunk is needed and
 //     its rows are emitted in that first run;
 //   * the backward transient runs in group 0 right behind its own phase 3 (it owns the lowest range);
@@ -392,8 +397,29 @@ __device__ __forceinline__ void scan_lds(const FastArgs& a, int b, int tid, doub
 //     log-likelihood and releases the b_t buffer / the table set -- nobody waits at a barrier for it.
 // Conditions (else scan_lds): L <= kRegL, E - 1 <= kPfEcap (all transient tables in LDS).  Same outputs to rounding (the sum
 // xi_t' w_t is accumulated in another order).
+//
+// Where the arithmetic runs: a "group" is a COLUMN of the wave's 8 x 8 state operand on the fp64 matrix pipe (dfm_scan.h mm8:
+// lane l holds component mm8_row(l) of chunk 8 w + mm8_col(l)).  G, Z, J, G^L, J^L, P_T and the transient's Z_e, G_e, J_e are A
+// operands of two doubles per lane, read from the LDS table set; b_t / w_t / the chunk end states e_k enter as the C operand
+// (e_k: the same LDS value in every column, the stop at a column's own chunk is a select); the result is the next step's B
+// operand.  A step of the chain is two dependent v_mfma_f64_4x4x4 and one row_ror:8 issued beside the first; w_t = Z xi_t is
+// two more, off the chain, in the gaps of the other pair.  Columns do not mix in a product, so an idle column (a chunk past T)
+// cannot reach a live one; rows i >= r are padding of the tables exactly as for the mat-vecs.  The lane-group form (matvec_x:
+// 14 DPP moves + 8 dependent-pair FMAs per step, eight doubles per lane and matrix) stays in scan_seq / scan_lds.
 // ------------------------------------------------------------------------------------------------------------------
 constexpr int kRegL = 16;
+
+// f(std::integral_constant<int, j>) for j = 0 .. N - 1.  The index is a constant where the body is compiled, so a register array
+// indexed by it is split into scalars; indexed by the counter of an unrolled loop it stays ONE 2 N-register tuple, and with
+// matrix-pipe instructions inside the steps' (uniform) branches the whole tuple was copied and spilled at every step.
+template <class F, int... J>
+__device__ __forceinline__ void pf_steps(F&& f, std::integer_sequence<int, J...>) {
+    (f(std::integral_constant<int, J>{}), ...);
+}
+template <int N, class F>
+__device__ __forceinline__ void pf_steps(F&& f) {
+    pf_steps(f, std::make_integer_sequence<int, N>{});
+}
 
 template <class Sync, class Prio>
 __device__ __forceinline__ void scan_reg(const FastArgs& a, int b, int tid, const double* bt, const double* s_tab, const double* s_mat,
@@ -404,7 +430,8 @@ __device__ __forceinline__ void scan_reg(const FastArgs& a, int b, int tid, cons
         if (pslot && tid == 0) pslot[k] = (double)__builtin_amdgcn_s_memrealtime();
     };
     constexpr int R = kPfR, NST = kPfNstTab, LM = kRegL;
-    const int c = tid / R, i = tid % R, lane = tid & 63;
+    const int lane = tid & 63;
+    const int c = (tid >> 6) * 8 + mm8_col(lane), i = mm8_row(lane);   // D layout of the matrix pipe (dfm_scan.h): chunk, state component
     const int T = a.T, r = a.r, L = a.L;
     const int ts = E - 1;                                     // <= kPfEcap
     double* fout = a.f_smooth + (size_t)b * T * r;
@@ -419,25 +446,23 @@ __device__ __forceinline__ void scan_reg(const FastArgs& a, int b, int tid, cons
 #pragma unroll
     for (int t = 0; t < kPfEcap; ++t) {
         if (t < ts) {                                         // (uniform)
-            double Zp[R], Gp[R];
             const double* ent = s_tab + (size_t)t * 3 * R * R;
-            load_xperm<R>(Zp, ent, i);
-            load_xperm<R>(Gp, ent + 2 * R * R, i);
+            const Mm8Op Zp = load_mm8(ent, lane), Gp = load_mm8(ent + 2 * R * R, lane);
             const double btv = bt[t * R + i];
-            const double w = matvec_x<R>(Zp, xi);
+            const double w = mm8(Zp, xi);
             if (c == 0) {
                 dot = fma(xi, w, dot);
                 wtr[t * R + i] = w;                           // (LDS; read back by the same lanes in the backward transient)
             }
-            xi = matvec_x<R>(Gp, xi, btv);
+            xi = mm8(Gp, xi, btv);
         }
     }
     mark(1);
 
     // ---- phase 1: b_t of the group's range into registers; chunk run from a zero state ------------------------------
     double u[LM];
-#pragma unroll
-    for (int j = 0; j < LM; ++j) {
+    pf_steps<LM>([&](auto jc) __attribute__((always_inline)) {
+        constexpr int j = decltype(jc)::value;
         u[j] = 0.0;
         if (j < L) {                                          // (uniform)
             const bool ok = j < Lc;
@@ -445,18 +470,17 @@ __device__ __forceinline__ void scan_reg(const FastArgs& a, int b, int tid, cons
             const double x = bt[tc * R + i];
             u[j] = ok ? x : 0.0;
         }
-    }
-    double Gp[R];
-    load_xperm<R>(Gp, s_mat + 2 * R * R, i);
+    });
+    const Mm8Op Gp = load_mm8(s_mat + 2 * R * R, lane);
     {
         double e = 0.0;
-#pragma unroll
-        for (int j = 0; j < LM; ++j) {
+        pf_steps<LM>([&](auto jc) __attribute__((always_inline)) {
+            constexpr int j = decltype(jc)::value;
             if (j < L) {
-                const double vn = matvec_x<R>(Gp, e, u[j]);
+                const double vn = mm8(Gp, e, u[j]);
                 e = (j < Lc) ? vn : e;
             }
-        }
+        });
         sE[c * R + i] = e;
     }
     mark(2);
@@ -465,15 +489,14 @@ __device__ __forceinline__ void scan_reg(const FastArgs& a, int b, int tid, cons
     // ---- state entering the group's chunk: the chunks before it, one after the other ---------------------------------
     double v = xi;
     {
-        double ML[R];
-        load_xperm<R>(ML, s_mat + kPfGL * R * R, i);          // G^L
+        const Mm8Op ML = load_mm8(s_mat + kPfGL * R * R, lane);   // G^L
         for (int k0 = 0; k0 <= wlo; k0 += 8) {                // (uniform: blocks of 8 chunks up to this wave's own)
             double ek[8];
 #pragma unroll
             for (int q = 0; q < 8; ++q) ek[q] = sE[(k0 + q) * R + i];
 #pragma unroll
             for (int q = 0; q < 8; ++q) {
-                const double vn = matvec_x<R>(ML, v, ek[q]);
+                const double vn = mm8(ML, v, ek[q]);
                 v = (k0 + q < c) ? vn : v;
             }
         }
@@ -481,45 +504,42 @@ __device__ __forceinline__ void scan_reg(const FastArgs& a, int b, int tid, cons
     mark(3);
     // ---- phase 3: re-run from the true state; w_t replaces b_t in the registers ---------------------------------------
     {
-        double Zp[R];
-        load_xperm<R>(Zp, s_mat, i);
-#pragma unroll
-        for (int j = 0; j < LM; ++j) {
+        const Mm8Op Zp = load_mm8(s_mat, lane);
+        pf_steps<LM>([&](auto jc) __attribute__((always_inline)) {
+            constexpr int j = decltype(jc)::value;
             if (j < L) {
                 const bool ok = j < Lc;
-                const double w = matvec_x<R>(Zp, v);
-                const double vn = matvec_x<R>(Gp, v, u[j]);
+                const double w = mm8(Zp, v);
+                const double vn = mm8(Gp, v, u[j]);
                 dot = ok ? fma(v, w, dot) : dot;
                 u[j] = w;
                 v = ok ? vn : v;
             }
-        }
+        });
     }
     mark(4);
     // ---- terminal (group clast: v = xi_T) + backward run of the chunk -------------------------------------------------
-    double Jp[R];
-    load_xperm<R>(Jp, s_mat + R * R, i);
+    const Mm8Op Jp = load_mm8(s_mat + R * R, lane);
     double eb;                                                // state leaving the chunk downwards
     {
-        double PTp[R];
-        load_xperm<R>(PTp, s_mat + NST * R * R, i);
-        const double fT = matvec_x<R>(PTp, v);                // meaningful in group clast only
+        const Mm8Op PTp = load_mm8(s_mat + NST * R * R, lane);
+        const double fT = mm8(PTp, v);                // meaningful in group clast only
         const bool top = (c == clast);
         if (top) {
             dot = fma(v, fT, dot);                            // the log-likelihood needs sum xi'w + xi_T' f_T
             if (i < r) fout[(size_t)(T - 1) * r + i] = fT;
         }
         eb = top ? fT : 0.0;                                  // the top chunk starts from its true state, the others from zero
-#pragma unroll
-        for (int j = LM - 1; j >= 0; --j) {
+        pf_steps<LM>([&](auto jc) __attribute__((always_inline)) {
+            constexpr int j = LM - 1 - decltype(jc)::value;
             if (j < L) {
                 const bool ok = j < Lc;
-                const double vn = matvec_x<R>(Jp, eb, u[j]);
+                const double vn = mm8(Jp, eb, u[j]);
                 eb = ok ? vn : eb;
                 const int t = t0 + j;
                 if (top && ok && t >= 1 && i < r) fout[(size_t)(t - 1) * r + i] = eb;   // f of period t -> row t - 1
             }
-        }
+        });
         sEb[c * R + i] = eb;
     }
     mark(5);
@@ -528,8 +548,7 @@ __device__ __forceinline__ void scan_reg(const FastArgs& a, int b, int tid, cons
     // ---- backward carries: the true state leaving the top chunk, then the zero-state runs of the chunks in between -----
     double vb = 0.0;
     if (wlo < clast) {                                        // (uniform) this wave has a group below the top chunk
-        double JL[R];
-        load_xperm<R>(JL, s_mat + (size_t)kPfJL * R * R, i);        // J^L
+        const Mm8Op JL = load_mm8(s_mat + (size_t)kPfJL * R * R, lane);   // J^L
         vb = sEb[clast * R + i];
         for (int k0 = clast - 1; k0 > wlo; k0 -= 8) {         // chunks k0, k0 - 1, .. (those above c apply)
             double ek[8];
@@ -537,7 +556,7 @@ __device__ __forceinline__ void scan_reg(const FastArgs& a, int b, int tid, cons
             for (int q = 0; q < 8; ++q) { const int k = k0 - q; ek[q] = sEb[(k > 0 ? k : 0) * R + i]; }
 #pragma unroll
             for (int q = 0; q < 8; ++q) {
-                const double vn = matvec_x<R>(JL, vb, ek[q]);
+                const double vn = mm8(JL, vb, ek[q]);
                 vb = (k0 - q > c) ? vn : vb;
             }
         }
@@ -546,14 +565,14 @@ __device__ __forceinline__ void scan_reg(const FastArgs& a, int b, int tid, cons
     // ---- backward phase 3 (groups below the top chunk; all of them hold full chunks) -------------------------------
     {
         const bool below = c < clast;
-#pragma unroll
-        for (int j = LM - 1; j >= 0; --j) {
+        pf_steps<LM>([&](auto jc) __attribute__((always_inline)) {
+            constexpr int j = LM - 1 - decltype(jc)::value;
             if (j < L) {
-                vb = matvec_x<R>(Jp, vb, u[j]);
+                vb = mm8(Jp, vb, u[j]);
                 const int t = t0 + j;
                 if (below && t >= 1 && i < r) fout[(size_t)(t - 1) * r + i] = vb;
             }
-        }
+        });
         vb = below ? vb : eb;                                 // group 0 == top chunk (short panels): its first run was the true one
     }
     mark(7);
@@ -563,14 +582,13 @@ __device__ __forceinline__ void scan_reg(const FastArgs& a, int b, int tid, cons
 #pragma unroll
         for (int t = kPfEcap - 1; t >= 0; --t) {
             if (t < ts) {
-                double Jt[R];
-                load_xperm<R>(Jt, s_tab + (size_t)t * 3 * R * R + R * R, i);
-                vt = matvec_x<R>(Jt, vt, wtr[t * R + (tid & 7)]);
+                const Mm8Op Jt = load_mm8(s_tab + (size_t)t * 3 * R * R + R * R, lane);
+                vt = mm8(Jt, vt, wtr[t * R + i]);
                 if (c == 0 && t >= 1 && i < r) fout[(size_t)(t - 1) * r + i] = vt;
             }
         }
         if (a.f0s && c == 0) {                                // E[f_0 | X] (EM)
-            int ii = tid & 7;
+            int ii = i;
             asm volatile("" : "+v"(ii));                      // address formed here: a pointer kept live across the scan is spilled
             a.f0s[(size_t)b * R + ii] = vt;
         }

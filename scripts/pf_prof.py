@@ -53,7 +53,8 @@ for k, nm in enumerate(names):
     v = s[:, cur] - s[:, prev]
     print(f"  {nm:24s} {v.mean():6.2f}")
     prev = cur
-nsw = int(os.environ.get("DFM_PASS_NSW", 5))
+from dynamic_factor_models_amd import _lib                   # the stream-wave count the launcher itself picks for this shape
+nsw = int(_lib.load()._ZN3dfm19pass_fused_pick_nswEiii(500, 200, int(os.environ.get("DFM_PASS_NSW", 0))))
 print("per stream wave: segment duration (us) / end relative to wave 0's end")
 for w in range(nsw):
     dur = s[:, 24 + w] - s[:, 32 + w]; rel = s[:, 24 + w] - s[:, 24]
@@ -68,6 +69,7 @@ print("per workgroup (us; min p10 p50 p90 p99 max):")
 print("  last scan end      ", pc(fin))
 print("  last stream end    ", pc(str_end))
 print("  first cov chain end", pc(cov0))
+print("  tail: last stream end -> last scan end", pc(fin - str_end))
 slow = np.argsort(fin)[-8:]
 print("  slowest workgroups :", [(int(g), round(float(fin[g]), 1), round(float(cov0[g]), 1)) for g in slow], "(id, last scan end, first cov end)")
 print("  XCD (id % 8) of the 32 slowest:", sorted(int(g) % 8 for g in np.argsort(fin)[-32:]))
